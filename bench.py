@@ -37,6 +37,10 @@ timed sweeps.  --scaling strong splits the work items of every launch across the
 --scaling launches gives every rank a share of the launch (frequency) sequence; both fix the total work.
 
 Inputs are resident in HBM before the timed region.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs of its own after the
+timed region: the per-kind sweeps (config.per_kind), the reference's launch shape (config.reference_launch_shape) and the
+CPU baseline (cpu_baseline).  --dump-outputs DIR writes what the timed steps computed (see dump_outputs).
 """
 import argparse
 import json
@@ -61,6 +65,8 @@ BYTES_PER_TALLY_EVENT = 12                   # 4 B density read + 8 B tally read
 C3_GL = 0.02                                 # pc
 C3_CELLS = 49526352                          # synth.octree_cloud(256, levels=4, frac=0.10, seed=1234); oracle/build.py ref "oct256"
 R_SUN, T_SUN = 6.957e10, 5800.0
+DUMP_BYTES = 60 << 20                        # --dump-outputs: all files together stay below 64 MB
+DUMP_SEED = 20240521                         # the cells of a sampled output (the same on every run of the same shape)
 
 
 def c2_workload():
@@ -197,6 +203,28 @@ def measured_traffic(workload):
     return None
 
 
+def level_sums(cloud, a):
+    """float64 sums of a per-cell array over each level of the hierarchy: a check on every cell of a sampled output"""
+    return np.asarray([np.sum(a[int(o):int(o) + int(n)], dtype=np.float64) for o, n in zip(cloud.OFF, cloud.LCELLS)])
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> float32 / float64 array) as <path>/<name>.npy.  Where the whole set
+    would pass DUMP_BYTES, the arrays of less than 1 MiB are written whole and the larger ones share the rest of the budget
+    as <name>_sample.npy: the elements (of the flattened array) at indices drawn without replacement by
+    np.random.default_rng(DUMP_SEED).choice(size, k), in increasing order -- the same elements for the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    large = [k for k, a in arrays.items() if total > DUMP_BYTES and a.nbytes >= (1 << 20)]
+    share = (DUMP_BYTES - sum(a.nbytes for k, a in arrays.items() if k not in large)) // max(len(large), 1)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if name in large:
+            k = min(a.size, share // a.itemsize)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, k, replace=False))
+            name, a = name + "_sample", a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
 
 def run_c4(args, world, rank, local_rank, dist, torch):
     """--workload C4 (BASELINE.json configs[3]): the scattered-light kernels on the config-3 hierarchy -- 3 observers, 256^2 pixels,
@@ -278,6 +306,9 @@ def run_c4(args, world, rank, local_rank, dist, torch):
     st = eng.stats()
     steps_rays = eng.sca_ray_steps()
     form, passes = eng.last_form(), eng.last_passes()
+    if args.dump_outputs and rank == 0:                     # the images of the timed batch (summed over the ranks), an image per frequency
+        dump_outputs(args.dump_outputs, {"images": np.ascontiguousarray(t.cpu().numpy() if world > 1 else imgs, np.float32),
+                                         "stats": np.asarray([st["packets"], st["tally_events"], st["scatterings"], steps_rays], np.float64)})
     packets_total = st["packets"]
     if world > 1:
         dev = "cpu" if os.environ.get("SOC_BENCH_REHEARSE_ON_ONE_GPU") else "cuda"
@@ -304,7 +335,7 @@ def run_c4(args, world, rank, local_rank, dist, torch):
                             "traffic": None, "kernel": ("soc_lray_pass (rays on brick-local hierarchies: soc_lbrick_walk<RAY> + soc_sca_events) (+ soc_brick_scan, "
                                                         "soc_brick_scatter), %d passes" % passes) if form == 3 else "soc_sca_kernel (direct)",
                             "kernel_ms": kavg_s * 1e3, "algorithmic_bytes_per_launch": alg}}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline_c4(work, eng, shapes, step, ps, emit, (OD, RA, DE, N), args.cpu_budget)
             except Exception as e:
@@ -357,9 +388,16 @@ def main():
     ap.add_argument("--first-step", type=int, default=-1,
                     help="index of the first timed step (default: the number of warm-up steps, i.e. the steps follow the warm-up); "
                          "tools/profile_bench.sh profiles the driver's timed steps without running its warm-up: --warmup 0 --first-step 5")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-reference-shape", action="store_true")
-    ap.add_argument("--no-per-kind", action="store_true", help="skip the per-kind sweeps after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the per-kind sweeps, the reference's launch shape and the CPU baseline "
+                         "(each can be left out with the --no-... option of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed as DIR/<name>.npy: the per-cell absorptions TABS (C3INT: and the INT "
+                         "column of the last frequency; C4: the images), their sums per hierarchy level and the event counts; "
+                         "a fixed, seeded sample of the cells where the whole arrays pass 64 MB")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-reference-shape", action="store_true", help="with --full: skip the reference's launch shape")
+    ap.add_argument("--no-per-kind", action="store_true", help="with --full: skip the per-kind sweeps after the timed region")
     ap.add_argument("--cpu-budget", type=float, default=16.0)
     ap.add_argument("--in-flight", type=int, default=0,
                     help="launches executed together in one brick sweep (soc_batch_begin/end); 1 = one launch at a time; "
@@ -426,6 +464,7 @@ def main():
     weak = args.scaling == "weak"
     mixed_sweeps = (args.workload in ("C3", "C3INT")) and not args.separate_kinds     # the config-3 hierarchy: brick-local walk, kinds share sweeps
     inflight = [0]                                                   # work items of this rank in its first sweep
+    last_int = [None]                                                # C3INT: the INT column read back last
     KDEV = 1.0 / world if weak else 1.0                              # ASOC.py:180,1501
 
     def run_steps(i0, n, in_flight, kinds=None):
@@ -483,7 +522,7 @@ def main():
                 if open_groups >= args.int_groups or ic == len(chunks) - 1:
                     eng.batch_end()
                     for k in range(open_groups):
-                        eng.batch_read_int(k)                       # a frequency's column of the absorbed file (device -> host, as ASOC.py:1482)
+                        last_int[0] = eng.batch_read_int(k)         # a frequency's column of the absorbed file (device -> host, as ASOC.py:1482)
                     open_groups = 0
             else:
                 eng.batch_end()
@@ -508,6 +547,8 @@ def main():
         eng.set_emission(work["step"](1)["EMIT"], None)           # resident before the timed region (same for every frequency)
     if args.warmup:
         run_steps(0, args.warmup, args.in_flight)
+        fence()
+        eng.zero(0)                                                  # TABS after the timed region = the timed steps' alone
     eng.stats(reset=True)
     fence()
     t0 = time.perf_counter()
@@ -518,6 +559,15 @@ def main():
     st = eng.stats()
     passes = eng.last_passes()
     form = eng.last_form()                       # of the timed sweeps (the launch-shape measurement below is a direct kernel)
+    if args.dump_outputs and rank == 0:
+        # before the --full measurements, which add to TABS.  Several ranks: TABS is the all-reduced sum; the counts are rank 0's.
+        tabs_out = eng.read_tally(0)
+        outs = {"tabs": tabs_out, "tabs_level_sums": level_sums(cloud, tabs_out),
+                "stats": np.asarray([st["packets"], st["tally_events"], st["scatterings"]], np.float64)}
+        if keep_int and last_int[0] is not None:
+            outs["int_last"] = last_int[0]
+            outs["int_last_level_sums"] = level_sums(cloud, last_int[0])
+        dump_outputs(args.dump_outputs, outs)
 
     packets_rank = st["packets"]
     events_rank = st["tally_events"]
@@ -526,7 +576,7 @@ def main():
     # per-kind rates: the kinds share the timed sweep, so each kind's launches of the first 8 timed steps are run again in a
     # sweep of their own (outside the timed region; fewer launches per sweep than the timed one)
     per_kind = None
-    if rank == 0 and world == 1 and len(work["kinds"]) > 1 and not args.no_per_kind and not keep_int:
+    if rank == 0 and world == 1 and len(work["kinds"]) > 1 and args.full and not args.no_per_kind and not keep_int:
         per_kind = {}
         for kd in work["kinds"]:
             eng.stats(reset=True)
@@ -549,7 +599,7 @@ def main():
 
     # the reference's own launch shape (GLOBAL_0 = 32768), shortened: BATCH cut so that it takes about a second
     ref_shape = None
-    if rank == 0 and world == 1 and args.workload == "C3" and not args.no_reference_shape:
+    if rank == 0 and world == 1 and args.workload == "C3" and args.full and not args.no_reference_shape:
         try:
             s = work["step"](0)
             L = launch.ps_launch(32768 * 2000, 1, C3_GL, launch.GLOBAL_0)
@@ -607,7 +657,7 @@ def main():
             out["config"]["reference_launch_shape"] = ref_shape
         if per_kind:
             out["config"]["per_kind"] = per_kind
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(work, args.cpu_budget)
             except Exception as e:                      # the baseline must never hide the GPU number

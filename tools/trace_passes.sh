@@ -4,7 +4,7 @@ OUT=$ROOT/gpurun_out/trace1
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 800 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -o t -- python3 $ROOT/bench.py --workload C3 --steps 20 --warmup 0 --no-cpu-baseline --no-reference-shape > $OUT/bench.log 2>&1
+timeout -k 10 800 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -o t -- python3 $ROOT/bench.py --workload C3 --steps 20 --warmup 0 --full --no-cpu-baseline --no-reference-shape > $OUT/bench.log 2>&1
 cd $ROOT
 F=$(find $OUT/t -name '*kernel_trace.csv' | head -1)
 python3 - "$F" $OUT/passes.txt <<'PY'
