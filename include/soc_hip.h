@@ -176,8 +176,9 @@ int soc_batch_begin(soc_ctx *ctx, int max_launches);
 int soc_batch_end(soc_ctx *ctx);
 /* The same for runs that keep the per-frequency INT tally (the absorbed file, ASOC.py:1482-1498): every deferred
  * launch gets its own, zeroed INT tally instead of the shared one (TABS stays shared).  At most max_launches (<= 16)
- * launches of one kind per batch; after soc_batch_end, soc_batch_read_int(k) copies the INT tally of the k-th launch of
- * the batch (n = CELLS).  Replaces K x [kernel launch + enqueue_copy(INT)] by K launches + K copies. */
+ * launches per batch; where the next launch cannot share the pending launches' sweep (another kind), they run first, as in
+ * soc_batch_begin, and their INT tallies stay readable.  After soc_batch_end, soc_batch_read_int(k) copies the INT tally of
+ * the k-th launch of the batch (n = CELLS).  Replaces K x [kernel launch + enqueue_copy(INT)] by K launches + K copies. */
 int soc_batch_begin_int(soc_ctx *ctx, int max_launches);
 /* The launches of ONE frequency that keep the INT tally (the source blocks of ASOC.py:1028-1545 at one IFREQ: point sources,
  * background, diffuse emission): deferred until soc_batch_end like soc_batch_begin's, all tallying into the handle's INT buffer

@@ -282,6 +282,59 @@ class AbsorptionRun:
         parts = launch.shard_launches([L["GLOBAL"] for _, _, L in seq], [L["PACKETS"] for _, _, L in seq], self.rank, self.world)
         return {(II, f): pc for (II, f, _), pc in zip(seq, parts)}, None
 
+    def _seed(self, IFREQ, rng):
+        """seed of the launches at IFREQ (ASOC.py:1247); with seed <= 0 a random one, the same on every rank"""
+        if self.U.SEED > 0:
+            return launch.launch_seed(self.U.SEED, IFREQ, 1, 0)       # sharded launches reproduce ONE device (ASOC.py:179-181)
+        seed = float(rng.random())
+        if self.comm and self.world > 1:          # every rank must use the same streams
+            seed = self._bcast_seed(seed)
+        return seed
+
+    def _launch(self, II, L, IFREQ, seed, first, count):
+        """Issue the launch of source block II (shape L) at frequency IFREQ on the work items [first, first+count)
+        (ASOC.py:1196-1461): the block's inputs of the frequency -- source weights, the diffuse emission, a loaded
+        region-of-interest record, the Healpix sky -- then the sim_* call.  Returns the launch's (TW, BG, PS), or None
+        where the block sends nothing at this frequency (no DIFFUSERAD column for it, an empty sky)."""
+        U, e, c = self.U, self.eng, self.cloud
+        t0 = time.time()
+        FREQ = float(self.FFREQ[IFREQ])
+        FF = np.float32(launch.trapezoid_weight(self.FFREQ, IFREQ))
+        PS = (self.LPS[:, IFREQ] * np.float32(L["WPS"])) / np.float32(FREQ) if II == 0 else np.zeros(1, np.float32)
+        BG = np.float32(float(self.IBG[IFREQ]) * L["WBG"] / FREQ) if (II == 1 and len(self.IBG) == self.NFREQ) else np.float32(0.0)
+        if II == 2:
+            dr_ind = IFREQ + (self.DIFFUSERAD.shape[1] - self.NFREQ)
+            if dr_ind < 0 or dr_ind >= self.DIFFUSERAD.shape[1]:
+                return None
+            EMIT = np.zeros(c.CELLS, np.float32)
+            for level in range(c.LEVELS):
+                coeff = U.GL * PARSEC / (8.0 ** level) * U.K_DIFFUSE
+                a, b = int(c.OFF[level]), int(c.OFF[level] + c.LCELLS[level])
+                EMIT[a:b] = self.DIFFUSERAD[a:b, dr_ind] * coeff
+            e.set_emission(EMIT, None)
+        if II == 3:
+            # scale in again the dependence on the grid length (ASOC.py:1419-1421)
+            e.set_roi_load(self.ROI_DIM, U.ROI_NSIDE,
+                           np.asarray(self.ROI_LOAD[IFREQ, :] * U.ROI_LOAD_SCALE / (U.GL * U.GL), np.float32))
+        hp = (II == 1) and len(self.HPBG) > 0
+        if hp:
+            sky = files.hpbg_for_frequency(self.HPBG[IFREQ], L["WBG"] / FREQ, U.HPBG_WEIGHTED)
+            if sky is None:
+                return None                                    # empty sky (ASOC.py:1200)
+            e.set_hpbg(*sky)
+        self.timers["Tpush"] += time.time() - t0
+        t0 = time.time()
+        if II == 2:
+            e.sim_cl(II, L["PACKETS"], L["BATCH"], seed, FF, L["GLOBAL"], gid_first=first, gid_count=count)
+        elif hp:
+            e.sim_hp(L["PACKETS"], L["BATCH"], seed, FF, L["GLOBAL"], gid_first=first, gid_count=count)
+        else:
+            e.sim_pb(II, L["PACKETS"], L["BATCH"], seed, BG, FF, PSPOS=U.PSPOS[:max(U.NO_PS, 1), :3], PS=PS, XPS=self.XPS,
+                     GLOBAL=L["GLOBAL"], gid_first=first, gid_count=count)
+        self.timers["Tkernel"] += time.time() - t0
+        self.packets += L["PACKETS"]
+        return FF, BG, PS
+
     def simulate_constant_sources(self):
         """for II in (point sources, background, diffuse): for IFREQ: launch (ASOC.py:1028-1545).
         Returns CTABS[CELLS] and FABSORBED[CELLS,NFREQ] (or None with noabsorbed)."""
@@ -296,7 +349,6 @@ class AbsorptionRun:
             self.log("=== CLOAD => %s" % U.file_constant_load)
             return np.fromfile(U.file_constant_load, np.float32, CELLS), FABSORBED
         rng = np.random.default_rng()
-        DEVICES, ID, KDEV = 1, 0, 1.0                 # sharded launches reproduce ONE device (ASOC.py:179-181)
         # region of interest (ASOC.py:909-944): record what enters ROI / send in what an enclosing run recorded
         self.ROI_SAVE = self.ROI_LOAD = None
         if U.WITH_ROI_LOAD:
@@ -309,7 +361,7 @@ class AbsorptionRun:
         # launches of the constant sources are handed to the engine as one batch: on hierarchies walked brick-locally the
         # point-source, background and diffuse launches of all frequencies share brick sweeps (include/soc_hip.h:
         # soc_batch_begin; up to 128 launches per sweep), elsewhere the engine starts a new sweep where the kind changes.
-        one_batch = (not self.with_int) and (not U.WITH_ROI_SAVE) and hasattr(e, "batch_begin") and U.ITERATIONS >= 1
+        one_batch = (not self.with_int) and (not U.WITH_ROI_SAVE) and U.ITERATIONS >= 1
         # several ranks, shard == "launches": the launches themselves are dealt out (see __init__).  Runs that keep the per-frequency
         # absorptions: a frequency belongs to one rank (not with the intensity file, region-of-interest records or emission iterations,
         # which need every frequency on every rank -- those keep the work-item split)
@@ -319,56 +371,30 @@ class AbsorptionRun:
             if (not own_freq) or (FABSORBED is not None and U.SAVE_INTENSITY == 0 and (not U.WITH_ROI_SAVE) and self.CLPAC < 1 and thin == 1):
                 shares, self.freq_owner = self._launch_shares(by_frequency=own_freq)
         owned = self.freq_owner is not None
-        # Runs that keep the per-frequency absorptions on a hierarchy: frequency by frequency, the source blocks of a frequency as one
-        # batch that tallies into one INT array (soc_batch_begin_shared_int), so that its point-source, background and diffuse
-        # launches share brick sweeps and brick queues.  (Cartesian grids: the per-launch INT batches below; the intensity file,
-        # region-of-interest records and a Healpix sky keep the block-by-block loop.)
+        # Runs that keep the per-frequency absorptions on a hierarchy: frequency by frequency, the source blocks of a frequency in
+        # one sweep with one INT tally, so that its point-source, background and diffuse launches share brick sweeps and brick
+        # queues.  (Cartesian grids: the INT batches below; the intensity file, region-of-interest records and a Healpix sky keep
+        # the block-by-block loop.)
         if (self.with_int and FABSORBED is not None and c.LEVELS > 1 and U.SAVE_INTENSITY == 0 and not U.WITH_ROI_SAVE
-                and not U.WITH_ROI_LOAD and len(self.HPBG) == 0 and hasattr(e, "batch_begin_shared_int") and U.ITERATIONS >= 1
-                and (shares is None or owned)):
+                and not U.WITH_ROI_LOAD and len(self.HPBG) == 0 and U.ITERATIONS >= 1 and (shares is None or owned)):
             return self._simulate_by_frequency(CTABS, FABSORBED, shares, owned, rng)
         if one_batch:
             e.zero(0)
             e.batch_begin(0)
         for II in range(4):
-            if U.ITERATIONS < 1:
+            L = self._constant_launch(II)
+            if U.ITERATIONS < 1 or L is None:
                 continue
-            WPS = WBG = 0.0
-            if II == 0:
-                if (self.PSPAC < 1) or (U.NO_PS < 1):
-                    continue
-                L = launch.ps_launch(self.PSPAC, U.NO_PS, U.GL, self.GLOBAL_0)
-                WPS = L["WPS"]
-                self.log("=== PS  GLOBAL %d x BATCH %d = %d" % (L["GLOBAL"], L["BATCH"], L["PACKETS"]))
-            elif II == 1:
-                if self.BGPAC < 1:
-                    continue
-                L = launch.hpbg_launch(self.BGPAC, c.NX, c.NY, c.NZ) if len(self.HPBG) > 0 else \
-                    launch.bg_launch(self.BGPAC, int(U.AREA))
-                WBG = L["WBG"]
-                self.log("=== BG: BGPAC %d, BATCH %d, GLOBAL %d" % (L["PACKETS"], L["BATCH"], L["GLOBAL"]))
-            elif II == 2:
-                if len(self.DIFFUSERAD) < 1 or self.DFPAC < 1:
-                    continue
-                L = launch.cl_launch(self.DFPAC, CELLS, self.GLOBAL_0)
-                self.log("=== DFPAC %d, GLOBAL %d, BATCH %d" % (self.DFPAC, L["GLOBAL"], L["BATCH"]))
-            else:
-                if U.ROIPAC < 1 or self.ROI_LOAD is None:
-                    continue
-                L = launch.roi_launch(U.ROIPAC, files.roi_elements(self.ROI_DIM), U.ROI_NSIDE)
-                self.log("=== ROI: GLOBAL %d, BATCH %d, elements %d" % (L["GLOBAL"], L["BATCH"], L["PACKETS"]))
+            self.log("=== %s  GLOBAL %d x BATCH %d = %d" % (['PS', 'BG', 'DE', 'ROI'][II], L["GLOBAL"], L["BATCH"], L["PACKETS"]))
             first, count = self.comm.shard(L["GLOBAL"]) if self.comm else (0, L["GLOBAL"])
             if not one_batch:
                 e.zero(0)
-            # TABS-only runs (noabsorbed): nothing is read back per frequency, so consecutive frequencies
-            # are handed to the engine together and share brick sweeps (include/soc_hip.h: soc_batch_begin)
-            deferred = (not one_batch) and (not self.with_int) and self.ROI_SAVE is None and hasattr(e, "batch_begin")   # the engine decides per launch
             # runs that keep the per-frequency absorptions, Cartesian grids: up to 16 frequencies per batch, every launch
-            # with its own INT tally, read after the batch -- and summed over the ranks then, on its way to the host array.
+            # a group with its own INT tally, read after the batch -- and summed over the ranks then, on its way to the host array.
             # (Hierarchies: one launch at a time; with `global` large enough each is a brick sweep of its own, the INT
             # tally in LDS beside TABS -- DESIGN.md.)
             int_batched = (self.with_int and FABSORBED is not None and self.ROI_SAVE is None and II != 3 and c.LEVELS == 1
-                           and U.SAVE_INTENSITY == 0 and hasattr(e, "batch_begin_int"))
+                           and U.SAVE_INTENSITY == 0)
             group = []
 
             def end_group():
@@ -379,10 +405,8 @@ class AbsorptionRun:
                         arr = self.comm.all_reduce_host(arr)
                     FABSORBED[:, f] += arr[0::self.absthin]
                 del group[:]
-            if deferred:
-                e.batch_begin(0)
             if int_batched:
-                e.batch_begin_int(16)
+                e.batch_begin_int_groups(16)
             for IFREQ in range(NFREQ):
                 FREQ = float(FFREQ[IFREQ])
                 if (FREQ < U.SIM_F[0]) or (FREQ > U.SIM_F[1]):
@@ -391,63 +415,31 @@ class AbsorptionRun:
                 ABS, SCA = self._optical_for(IFREQ)
                 if self.with_int and not int_batched:
                     e.zero(1)
-                PS = (self.LPS[:, IFREQ] * np.float32(WPS)) / np.float32(FREQ) if II == 0 else np.zeros(1, np.float32)
-                BG = np.float32(float(self.IBG[IFREQ]) * WBG / FREQ) if len(self.IBG) == NFREQ else np.float32(0.0)
-                FF = np.float32(launch.trapezoid_weight(FFREQ, IFREQ))
                 self._scatter_tables_for(IFREQ)
-                if U.SEED > 0:
-                    seed = launch.launch_seed(U.SEED, IFREQ, DEVICES, ID)
-                else:
-                    seed = float(rng.random())
-                    if self.comm and self.world > 1:      # every rank must use the same streams
-                        seed = self._bcast_seed(seed)
+                seed = self._seed(IFREQ, rng)
                 if shares is not None:
                     first, count = shares.get((II, IFREQ), (0, 0))
                     if count == 0:
                         continue                          # another rank's launch
-                if II == 2:
-                    dr_ind = IFREQ + (self.DIFFUSERAD.shape[1] - NFREQ)
-                    if dr_ind < 0 or dr_ind >= self.DIFFUSERAD.shape[1]:
-                        continue
-                    EMIT = np.zeros(CELLS, np.float32)
-                    for level in range(c.LEVELS):
-                        coeff = U.GL * PARSEC / (8.0 ** level) * U.K_DIFFUSE
-                        a, b = int(c.OFF[level]), int(c.OFF[level] + c.LCELLS[level])
-                        EMIT[a:b] = self.DIFFUSERAD[a:b, dr_ind] * coeff
-                    e.set_emission(EMIT, None)
-                if II == 3:
-                    # scale in again the dependence on the grid length (ASOC.py:1419-1421)
-                    e.set_roi_load(self.ROI_DIM, U.ROI_NSIDE,
-                                   np.asarray(self.ROI_LOAD[IFREQ, :] * U.ROI_LOAD_SCALE / (U.GL * U.GL), np.float32))
                 if self.ROI_SAVE is not None:
                     e.roi_zero()                                   # per frequency (ASOC.py:1301-1302)
-                hp = (II == 1) and len(self.HPBG) > 0
-                if hp:
-                    sky = files.hpbg_for_frequency(self.HPBG[IFREQ], WBG / FREQ, U.HPBG_WEIGHTED)
-                    if sky is None:
-                        continue                                   # empty sky (ASOC.py:1200)
-                    e.set_hpbg(*sky)
+                if int_batched:
+                    e.batch_next_int()
                 self.timers["Tpush"] += time.time() - t0
+                w = self._launch(II, L, IFREQ, seed, first, count)
+                if w is None:
+                    continue
                 t0 = time.time()
-                if II == 2:
-                    e.sim_cl(II, L["PACKETS"], L["BATCH"], seed, FF, L["GLOBAL"], gid_first=first, gid_count=count)
-                elif hp:
-                    e.sim_hp(L["PACKETS"], L["BATCH"], seed, FF, L["GLOBAL"], gid_first=first, gid_count=count)
-                else:
-                    e.sim_pb(II, L["PACKETS"], L["BATCH"], seed, BG, FF,
-                             PSPOS=U.PSPOS[:max(U.NO_PS, 1), :3], PS=PS, XPS=self.XPS,
-                             GLOBAL=L["GLOBAL"], gid_first=first, gid_count=count)
                 if self.with_int and self.comm and not int_batched and not owned:
                     self.comm.all_reduce_tally(e, 1)      # one all-reduce of the per-cell buffer per frequency
                 if int_batched:
                     group.append(IFREQ)
                     if len(group) == 16:
                         end_group()
-                        e.batch_begin_int(16)
-                elif not (deferred or one_batch):
+                        e.batch_begin_int_groups(16)
+                elif not one_batch:
                     e.sync()
                 self.timers["Tkernel"] += time.time() - t0
-                self.packets += L["PACKETS"]
                 t0 = time.time()
                 if (FABSORBED is not None or U.SAVE_INTENSITY > 0) and not int_batched:
                     TMP = e.read_tally(1)
@@ -464,13 +456,9 @@ class AbsorptionRun:
                     self.ROI_SAVE[IFREQ, :] += rec * np.float32(U.GL * U.GL)
                 self.timers["Tpull"] += time.time() - t0
                 if self.verbose and self.rank == 0:
+                    FF, BG, PS = w
                     print("  FREQ %3d/%3d  %10.3e   BG %12.4e  PS %12.4e   TW %10.3e" % (
                         IFREQ + 1, NFREQ, FREQ, BG, PS[0], FF))
-            if deferred:
-                t0 = time.time()
-                e.batch_end()
-                e.sync()
-                self.timers["Tkernel"] += time.time() - t0
             if int_batched:
                 t0 = time.time()
                 end_group()
@@ -508,13 +496,12 @@ class AbsorptionRun:
 
     def _simulate_by_frequency(self, CTABS, FABSORBED, shares, owned, rng):
         """for IFREQ: for II in (point sources, background, diffuse): launch -- the loop of ASOC.py:1028-1545 with the frequency
-        outside, for runs that keep the per-frequency absorptions: the launches of one frequency are one batch with one INT
-        tally.  TABS integrates over everything on the device and is read once (CTABS is the sum over the blocks anyway).
-        Where the engine has them, groups: up to FREQS_PER_SWEEP frequencies are deferred into one sweep, each with its own INT tally
-        (soc_batch_begin_int_groups / soc_batch_next_int) -- that many times the packets per brick and pass -- and read after it."""
+        outside, for runs that keep the per-frequency absorptions: the launches of one frequency are a group with one INT tally
+        (soc_batch_begin_int_groups / soc_batch_next_int), up to FREQS_PER_SWEEP groups are deferred into one sweep -- that many
+        times the packets per brick and pass -- and their tallies read after it.  TABS integrates over everything on the device and
+        is read once (CTABS is the sum over the blocks anyway)."""
         U, e, c = self.U, self.eng, self.cloud
-        CELLS, NFREQ, FFREQ = c.CELLS, self.NFREQ, self.FFREQ
-        grouped = hasattr(e, "batch_begin_int_groups")
+        NFREQ, FFREQ = self.NFREQ, self.FFREQ
         pend = []
 
         def end_sweep():
@@ -540,68 +527,26 @@ class AbsorptionRun:
             if (FREQ < U.SIM_F[0]) or (FREQ > U.SIM_F[1]):
                 continue
             t0 = time.time()
-            ABS, SCA = self._optical_for(IFREQ)
+            self._optical_for(IFREQ)
             self._scatter_tables_for(IFREQ)
-            FF = np.float32(launch.trapezoid_weight(FFREQ, IFREQ))
-            if U.SEED > 0:
-                seed = launch.launch_seed(U.SEED, IFREQ, 1, 0)
-            else:
-                seed = float(rng.random())
-                if self.comm and self.world > 1:          # every rank must use the same streams
-                    seed = self._bcast_seed(seed)
+            seed = self._seed(IFREQ, rng)
             mine = [(II, L) + ((0, L["GLOBAL"]) if shares is None else shares.get((II, IFREQ), (0, 0))) for II, L in blocks]
             if shares is None and self.comm:
                 mine = [(II, L) + self.comm.shard(L["GLOBAL"]) for II, L in blocks]
             mine = [m for m in mine if m[3] > 0]
             if not mine:
                 continue                                  # another rank's frequency
-            if grouped:
-                if not pend:
-                    e.batch_begin_int_groups(self.FREQS_PER_SWEEP)
-                e.batch_next_int()
-            else:
-                e.zero(1)
-                e.batch_begin_shared_int(len(mine))
+            if not pend:
+                e.batch_begin_int_groups(self.FREQS_PER_SWEEP)
+            e.batch_next_int()
             self.timers["Tpush"] += time.time() - t0
             for II, L, first, count in mine:
-                t0 = time.time()
-                if II == 2:
-                    dr_ind = IFREQ + (self.DIFFUSERAD.shape[1] - NFREQ)
-                    if dr_ind < 0 or dr_ind >= self.DIFFUSERAD.shape[1]:
-                        continue
-                    EMIT = np.zeros(CELLS, np.float32)
-                    for level in range(c.LEVELS):
-                        coeff = U.GL * PARSEC / (8.0 ** level) * U.K_DIFFUSE
-                        a, b = int(c.OFF[level]), int(c.OFF[level] + c.LCELLS[level])
-                        EMIT[a:b] = self.DIFFUSERAD[a:b, dr_ind] * coeff
-                    e.set_emission(EMIT, None)
-                self.timers["Tpush"] += time.time() - t0
-                t0 = time.time()
-                if II == 2:
-                    e.sim_cl(II, L["PACKETS"], L["BATCH"], seed, FF, L["GLOBAL"], gid_first=first, gid_count=count)
-                else:
-                    PS = (self.LPS[:, IFREQ] * np.float32(L["WPS"])) / np.float32(FREQ) if II == 0 else np.zeros(1, np.float32)
-                    BG = np.float32(float(self.IBG[IFREQ]) * L["WBG"] / FREQ) if (II == 1 and len(self.IBG) == NFREQ) else np.float32(0.0)
-                    e.sim_pb(II, L["PACKETS"], L["BATCH"], seed, BG, FF, PSPOS=U.PSPOS[:max(U.NO_PS, 1), :3], PS=PS, XPS=self.XPS,
-                             GLOBAL=L["GLOBAL"], gid_first=first, gid_count=count)
-                self.timers["Tkernel"] += time.time() - t0
-                self.packets += L["PACKETS"]
-            if grouped:
-                pend.append(IFREQ)
-                if len(pend) >= self.FREQS_PER_SWEEP:
-                    end_sweep()
-            else:
-                t0 = time.time()
-                e.batch_end()
-                e.sync()
-                if self.comm and not owned:
-                    self.comm.all_reduce_tally(e, 1)          # one all-reduce of the per-cell buffer per frequency
-                self.timers["Tkernel"] += time.time() - t0
-                t0 = time.time()
-                FABSORBED[:, IFREQ] += e.read_tally(1)[0::self.absthin]
-                self.timers["Tpull"] += time.time() - t0
+                self._launch(II, L, IFREQ, seed, first, count)
+            pend.append(IFREQ)
+            if len(pend) >= self.FREQS_PER_SWEEP:
+                end_sweep()
             if self.verbose and self.rank == 0:
-                print("  FREQ %3d/%3d  %10.3e   TW %10.3e" % (IFREQ + 1, NFREQ, FREQ, FF))
+                print("  FREQ %3d/%3d  %10.3e   TW %10.3e" % (IFREQ + 1, NFREQ, FREQ, np.float32(launch.trapezoid_weight(FFREQ, IFREQ))))
         if pend:
             end_sweep()
         if self.comm:

@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -91,10 +92,13 @@ struct soc_ctx {
     unsigned long long emit_slot_gen = 0;
     int    emit_slot_last = -1;
     int    int_slots_done = 0;                    // launches of the last executed sweep whose INT can be read
-    bool   batch_keep_int = false;                // soc_batch_begin_int: deferred launches keep their own INT tally
-    bool   batch_share_int = false;               // soc_batch_begin_shared_int: deferred launches tally into the handle's INT together
-    bool   batch_group_int = false;               // soc_batch_begin_int_groups: the launches between two soc_batch_next_int calls share an INT tally
-    bool   int_group_open = false;                // ... and the current group has its tally
+    // the INT tally of the launches of a batch (set by the soc_batch_begin* call that opened it):
+    //   INT_OFF        soc_batch_begin: launches with the INT tally are not deferred
+    //   INT_SHARED     soc_batch_begin_shared_int: all tally into the handle's dINT
+    //   INT_PER_LAUNCH soc_batch_begin_int: every launch a zeroed slot of its own (dINTslot)
+    //   INT_PER_GROUP  soc_batch_begin_int_groups: the launches up to the next soc_batch_next_int share a slot
+    enum IntMode { INT_OFF, INT_SHARED, INT_PER_LAUNCH, INT_PER_GROUP } int_mode = INT_OFF;
+    bool   int_group_open = false;                // INT_PER_GROUP: the current group has its slot
     size_t emitslot_cells = 0;
     size_t optslot_cells = 0;
     int    csc_slot_bins = 0;
@@ -174,6 +178,23 @@ static bool lt_capable(const soc_ctx *c, bool abu)
 #define SOC_SCA_RAYS_LAUNCH 4000000
 #define SOC_LT_LONE_LAUNCH 1000000                           // work items from which a lone launch goes to the sweep there
 
+// One absorption launch through the direct kernel of its kind (SOURCE 4 and 5 mark Healpix and cell-emission launches for the
+// brick sweep; the direct kernels take them as 1 and 2)
+static int run_direct(soc_ctx *c, SocSim S, const SocVariant &V)
+{
+    c->last_passes = 0;
+    if (S.SOURCE == SOC_SOURCE_HP) {
+        S.SOURCE = 1;
+        HIPCHK(c, soc_launch_sim_hp(c->G, S, V, c->stream));
+    } else if (S.SOURCE == SOC_SOURCE_CL) {
+        S.SOURCE = 2;
+        HIPCHK(c, soc_launch_sim_cl(c->G, S, V, c->stream));
+    } else {
+        HIPCHK(c, soc_launch_sim_pb(c->G, S, V, c->stream));
+    }
+    return SOC_OK;
+}
+
 // Execute the launches deferred since soc_batch_begin: one brick sweep for all of them.
 static int flush_pending(soc_ctx *c)
 {
@@ -206,25 +227,11 @@ static int flush_pending(soc_ctx *c)
         if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "sweep of the rays of %d deferred scattered-light launches failed: %s", (int)todo.size(), hipGetErrorString(e));
         return SOC_OK;
     }
-    V.abu = todo[0].OPT != nullptr;                          // what makes a launch deferrable (see soc_sim_pb)
-    V.wint = ((c->batch_keep_int || c->batch_share_int) && c->with_int) ? c->with_int : 0;
+    V.abu = todo[0].OPT != nullptr;                          // what makes a launch deferrable (see route_sim)
+    V.wint = c->int_mode != soc_ctx::INT_OFF ? c->with_int : 0;
     HIPCHK(c, hipSetDevice(c->device));
-    if (V.octree && todo.size() == 1 && c->exec_mode < 0 && !(lt_capable(c, V.abu != 0) && todo[0].gid_count >= SOC_LT_LONE_LAUNCH)) {
-        // a single launch on a hierarchy: the direct kernel is as fast (1.9e10 vs 2.0e10 steps/s at 256^3, 4 levels)
-        c->last_passes = 0;
-        if (todo[0].SOURCE == SOC_SOURCE_HP) {
-            SocSim S1 = todo[0];
-            S1.SOURCE = 1;
-            HIPCHK(c, soc_launch_sim_hp(c->G, S1, V, c->stream));
-        } else if (todo[0].SOURCE == SOC_SOURCE_CL) {
-            SocSim S1 = todo[0];
-            S1.SOURCE = 2;
-            HIPCHK(c, soc_launch_sim_cl(c->G, S1, V, c->stream));
-        } else {
-            HIPCHK(c, soc_launch_sim_pb(c->G, todo[0], V, c->stream));
-        }
-        return SOC_OK;
-    }
+    if (V.octree && todo.size() == 1 && c->exec_mode < 0 && !(lt_capable(c, V.abu != 0) && todo[0].gid_count >= SOC_LT_LONE_LAUNCH))
+        return run_direct(c, todo[0], V);      // a single launch on a hierarchy: the direct kernel is as fast (1.9e10 vs 2.0e10 steps/s at 256^3, 4 levels)
     // packets in flight: chosen by the sweep from the number of bricks (-1)
     hipError_t e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form);
     if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep of %d deferred launches failed: %s", (int)todo.size(), hipGetErrorString(e));
@@ -497,7 +504,7 @@ int soc_set_optical(soc_ctx *c, const float *ABS, const float *SCA, int ndust)
 int soc_set_opt(soc_ctx *c, const float *OPT)
 {
     if (!c) return SOC_ERR_ARG;
-    // no flush: a deferred launch keeps its own copy of the opacities (soc_sim_pb)
+    // no flush: a deferred launch keeps its own copy of the opacities (route_sim)
     if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_set_opt: call soc_set_grid first");
     HIPCHK(c, hipSetDevice(c->device));
     c->opt_from_abu = false;
@@ -549,7 +556,7 @@ int soc_set_abundances(soc_ctx *c, int NDUST, int single, const float *ABU)
 int soc_set_optical_abu(soc_ctx *c, const float *AFABS, const float *AFSCA, int ndust)
 {
     if (!c) return SOC_ERR_ARG;
-    // no flush: a deferred launch keeps its own copy of the opacities (soc_sim_pb)
+    // no flush: a deferred launch keeps its own copy of the opacities (route_sim)
     if (!c->abu_ndust || c->abu_cells != (size_t)c->G.CELLS) return fail(c, SOC_ERR_STATE, "soc_set_optical_abu: call soc_set_abundances (after soc_set_grid) first");
     if (!AFABS || !AFSCA || ndust != c->abu_ndust) return fail(c, SOC_ERR_ARG, "soc_set_optical_abu: need the cross sections of the %d species", c->abu_ndust);
     HIPCHK(c, hipSetDevice(c->device));
@@ -781,12 +788,13 @@ static int upload_sources(soc_ctx *c, const char *who, SocSim &S, const float *P
 static int snapshot_inputs(soc_ctx *c, SocSim &S, const SocVariant &V, int slot);
 #define SOC_OPT_SLOTS 16        // launches with per-cell opacities per sweep (8 B per cell and launch, in one buffer)
 
-// a sweep runs one kernel variant: launches of one kind (SimRAM_PB, _HP or _CL), all with or all without per-cell opacities
-// soc_batch_begin_int: the next launch of the batch -- deferred or not -- gets its own, zeroed INT tally
+static bool int_slots(const soc_ctx *c) { return c->int_mode == soc_ctx::INT_PER_LAUNCH || c->int_mode == soc_ctx::INT_PER_GROUP; }
+
+// INT slot modes: the next launch of the batch -- deferred or not -- tallies INT into the current group's slot, or into a new, zeroed one
 static int take_int_slot(soc_ctx *c, const char *who, SocSim &S)
 {
-    if (!(c->batching && c->batch_keep_int && c->with_int)) return SOC_OK;
-    if (c->batch_group_int && c->int_group_open) {           // a further launch of the current group: the group's tally
+    if (!(c->batching && int_slots(c) && c->with_int)) return SOC_OK;
+    if (c->int_mode == soc_ctx::INT_PER_GROUP && c->int_group_open) {     // a further launch of the current group: the group's tally
         S.INT = c->dINTslot[c->int_slots_done - 1];
         return SOC_OK;
     }
@@ -806,6 +814,7 @@ static int take_int_slot(soc_ctx *c, const char *who, SocSim &S)
     return SOC_OK;
 }
 
+// a sweep runs one kernel variant: its launches are all SimRAM_PB, all _HP or all _CL ones, all with or all without per-cell opacities
 // ... except on brick-local hierarchies, where the walk and the event workgroups take the kind from the launch: there the
 // point-source, background, Healpix and cell-emission launches of a TABS-only run share one sweep
 static bool same_sweep(const soc_ctx *c, int source, bool abu)
@@ -817,6 +826,68 @@ static bool same_sweep(const soc_ctx *c, int source, bool abu)
     const int kn = (source == SOC_SOURCE_CL) ? 2 : (source == SOC_SOURCE_HP) ? 1 : 0;
     if ((P.OPT != nullptr) != abu) return false;
     return kp == kn || lt_capable(c, abu);      // (brick-local hierarchies: the kinds share sweeps, also with per-group INT tallies)
+}
+
+static int snapshot_emission(soc_ctx *c, SocSim &S, int slot);
+
+// The kinds of absorption launch and what sets them apart on the way to a kernel (the eligibility terms: route_sim)
+enum SimKind { SIM_PB, SIM_HP, SIM_CL };
+static const struct {
+    const char *who;
+    long long   min_items;              // automatic mode: work items from which the brick sweep pays
+    const char *not_applicable;         // what keeps soc_set_exec(1) from the brick sweep
+} sim_kinds[3] = {
+    { "soc_sim_pb", 65536,  "mirror, with_int 2, roisave/roiload, > 15 levels or > 2^18 bricks" },
+    { "soc_sim_hp", 65536,  "mirror, with_int 2, > 15 levels or > 2^18 bricks" },
+    { "soc_sim_cl", 262144, "mirror, with_int 2, USE_EMWEIGHT 2, ALI, roisave, > 15 levels or > 2^18 bricks" },
+};
+
+// Route an absorption launch, after the checks of its soc_sim_* call and fill_sim: the brick sweep or the direct kernel, now or
+// deferred into the open batch.  items: the work items the thresholds count.  slot_inputs(slot) stores the kind's own inputs of
+// the launch: slot >= 0 the launch is deferred and keeps them in that slot, -1 it runs now.
+static int route_sim(soc_ctx *c, SimKind kind, SocSim &S, const SocVariant &V, long long items, const std::function<int(int)> &slot_inputs)
+{
+    const char *who = sim_kinds[kind].who;
+    const bool lt = lt_capable(c, V.abu != 0);
+    const int B = 1 << c->brick_log2;
+    const long long nb = (long long)((c->G.NX + B - 1) / B) * ((c->G.NY + B - 1) / B) * ((c->G.NZ + B - 1) / B);
+    // the open batch takes the launch with its INT tally (soc_batch_begin: only launches without one)
+    const bool int_batch = c->batching && (!V.wint || c->int_mode != soc_ctx::INT_OFF);
+    // the brick sweep applies: mirror, with_int 2 and region-of-interest records need the brick-local sweep (packets of a loaded
+    // record, SOURCE 3: any sweep); cell emission also needs USE_EMWEIGHT 0/1 and, with ALI, the brick-local sweep without with_int 2
+    bool bricks = c->exec_mode != 0 && nb <= (1 << 18) && c->G.LEVELS <= 15 && c->device < 16
+                  && (c->mirror == 0 || lt) && (c->with_int != 2 || lt)
+                  && (kind == SIM_HP || !c->roi.save || (lt && c->mirror == 0))
+                  && (kind != SIM_CL || (c->use_emweight != 2 && (!c->with_ali || (lt && c->with_int != 2))));
+    // automatic mode: enough work items to fill the chip.  Hierarchies: the sweep pays from two launches per sweep on (256^3 roots,
+    // 4 levels: 1.9e10 steps/s with one launch, 2.8e10 with two, 4.4e10 with eight; direct kernel 2.0e10), so there only launches
+    // of a batch use it (see flush_pending) -- and, on brick-local hierarchies, a lone launch with enough work items
+    if (c->exec_mode < 0)
+        bricks = bricks && items >= sim_kinds[kind].min_items && nb >= 8 && (!V.octree || int_batch || (lt && items >= SOC_LT_LONE_LAUNCH));
+    if (c->exec_mode == 1 && !bricks)
+        return fail(c, SOC_ERR_ARG, "%s: brick sweep requested but not applicable (%s)", who, sim_kinds[kind].not_applicable);
+    // inside soc_batch_begin/end a brick launch is deferred: its per-launch inputs are snapshotted and it runs with the others.
+    // Not with_int 2 in the INT slot modes; not WITH_MSF (per-species tables are not snapshotted)
+    const bool defer = int_batch && bricks && !(int_slots(c) && V.wint == 2) && c->msf_ndust <= 1;
+    if (!defer || !same_sweep(c, S.SOURCE, V.abu != 0)) FLUSH(c);
+    int r = take_int_slot(c, who, S);
+    if (r) return r;
+    const int slot = defer ? (int)c->pending.size() : -1;
+    r = slot_inputs(slot);
+    if (r) return r;
+    c->last_passes = 0;
+    if (defer) {
+        r = snapshot_inputs(c, S, V, slot);
+        if (r) return r;
+        c->pending.push_back(S);
+        if ((!int_slots(c) && (int)c->pending.size() >= (V.abu ? std::min(c->batch_max, SOC_OPT_SLOTS) : c->batch_max))
+            || (int)c->pending.size() >= SOC_MAXLAUNCH) FLUSH(c);      // (with INT tallies per launch or group: a sweep's worth of launches)
+        return SOC_OK;
+    }
+    if (!bricks) return run_direct(c, S, V);
+    hipError_t e = soc_brick_run_pb(c->device, c->G, &S, 1, V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form);
+    if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep failed: %s", hipGetErrorString(e));
+    return SOC_OK;
 }
 
 int soc_sim_pb(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, float BG, float TW,
@@ -840,64 +911,23 @@ int soc_sim_pb(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, float
     SocSim S;
     SocVariant V;
     fill_sim(c, S, V, SOURCE, BATCH, SEED, BG, TW, GLOBAL, gid_first, gid_count);
+    S.NO_PS = 1;
     S.ROI = (c->roi.save || c->roi.load) ? c->dRoi : nullptr;
     S.ROISAVE = c->roi.save;
     S.ROILOAD = c->roi.load ? c->roi.NELEM : 0;
-    // brick sweep: enough work items to fill the chip.  Hierarchies: it pays from two launches per sweep on
-    // (256^3 roots, 4 levels: 1.9e10 steps/s with one launch, 2.8e10 with two, 4.4e10 with eight; direct kernel
-    // 2.0e10), so in automatic mode only deferred launches use it (see flush_pending)
-    const int B = 1 << c->brick_log2;
-    const long long nb = (long long)((c->G.NX + B - 1) / B) * ((c->G.NY + B - 1) / B) * ((c->G.NZ + B - 1) / B);
-    bool bricks = (c->exec_mode != 0) && nb <= (1 << 18) && c->G.LEVELS <= 15 && c->device < 16 && (c->mirror == 0 || lt_capable(c, V.abu != 0)) && (c->with_int != 2 || lt_capable(c, V.abu != 0))
-                  && (!c->roi.save || (lt_capable(c, V.abu != 0) && c->mirror == 0));      // region-of-interest records: the brick-local sweep's event workgroups (packets of a loaded record, SOURCE 3: any sweep)
-    if (c->exec_mode < 0) bricks = bricks && gid_count >= 65536 && nb >= 8
-                                   && (!V.octree || (c->batching && (!V.wint || c->batch_keep_int || c->batch_share_int)) || (lt_capable(c, V.abu != 0) && gid_count >= SOC_LT_LONE_LAUNCH));
-    if (c->exec_mode == 1 && !bricks)
-        return fail(c, SOC_ERR_ARG, "soc_sim_pb: brick sweep requested but not applicable (mirror, with_int 2, roisave/roiload, > 15 levels or > 2^18 bricks)");
-    // inside soc_batch_begin/end a brick launch with scalar opacities and no INT tally is deferred:
-    // its per-launch inputs are snapshotted (scattering table, sources) and it runs with the others
-    const bool defer = c->batching && bricks && (!V.wint || (c->batch_keep_int && V.wint != 2) || c->batch_share_int) && c->msf_ndust <= 1;   // WITH_MSF: per-species tables are not snapshotted
-    if (!defer) FLUSH(c);
-    if (defer && c->batch_keep_int && !same_sweep(c, SOURCE, V.abu != 0))
-        return fail(c, SOC_ERR_STATE, "soc_sim_pb: a batch with the INT tally holds launches of one kind");
-    if (defer && !same_sweep(c, SOURCE, V.abu != 0)) FLUSH(c);
-    r = take_int_slot(c, "soc_sim_pb", S);
-    if (r) return r;
-    const int slot = defer ? (int)c->pending.size() : 0;
-    if (SOURCE == 0) {
-        r = upload_sources(c, "soc_sim_pb", S, PSPOS, PS, NO_PS, XPS_NSIDE, XPS_SIDE, XPS_AREA, false, slot);
-        if (r) return r;
-    } else {
-        S.NO_PS = 1;
-    }
-    c->last_passes = 0;
-    if (defer) {
-        r = snapshot_inputs(c, S, V, slot);
-        if (r) return r;
-        c->pending.push_back(S);
-        if ((!c->batch_keep_int && (int)c->pending.size() >= (V.abu ? std::min(c->batch_max, SOC_OPT_SLOTS) : c->batch_max))
-            || (int)c->pending.size() >= SOC_MAXLAUNCH) FLUSH(c);      // (with INT tallies per launch or group: a sweep's worth of launches)
-        return SOC_OK;
-    }
-    if (bricks) {
-        hipError_t e = soc_brick_run_pb(c->device, c->G, &S, 1, V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form);
-        if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep failed: %s", hipGetErrorString(e));
-        return SOC_OK;
-    }
-    HIPCHK(c, soc_launch_sim_pb(c->G, S, V, c->stream));
-    return SOC_OK;
+    return route_sim(c, SIM_PB, S, V, gid_count, [&](int slot) {      // the point sources, in the launch's slot of the source buffers
+        return SOURCE == 0 ? upload_sources(c, "soc_sim_pb", S, PSPOS, PS, NO_PS, XPS_NSIDE, XPS_SIDE, XPS_AREA, false, slot < 0 ? 0 : slot) : SOC_OK;
+    });
 }
 
-int soc_batch_begin(soc_ctx *c, int max_launches)
+static int batch_begin(soc_ctx *c, int max_launches, soc_ctx::IntMode int_mode)
 {
     if (!c) return SOC_ERR_ARG;
     if (max_launches < 0 || max_launches > SOC_MAXLAUNCH)
         return fail(c, SOC_ERR_ARG, "soc_batch_begin: max_launches %d (1..%d, 0 = default)", max_launches, SOC_MAXLAUNCH);
     FLUSH(c);
     c->batching = true;
-    c->batch_keep_int = false;
-    c->batch_share_int = false;
-    c->batch_group_int = false;
+    c->int_mode = int_mode;
     c->int_group_open = false;
     c->int_slots_done = 0;
     // default: as many as one sweep takes (the packets in flight are limited separately, see flush_pending)
@@ -905,36 +935,16 @@ int soc_batch_begin(soc_ctx *c, int max_launches)
     return SOC_OK;
 }
 
-int soc_batch_begin_int(soc_ctx *c, int max_launches)
-{
-    int r = soc_batch_begin(c, max_launches);
-    if (r) return r;
-    c->batch_keep_int = true;
-    return SOC_OK;
-}
-
-int soc_batch_begin_int_groups(soc_ctx *c, int max_groups)
-{
-    int r = soc_batch_begin(c, max_groups);
-    if (r) return r;
-    c->batch_keep_int = true;
-    c->batch_group_int = true;
-    return SOC_OK;
-}
+int soc_batch_begin(soc_ctx *c, int max_launches) { return batch_begin(c, max_launches, soc_ctx::INT_OFF); }
+int soc_batch_begin_shared_int(soc_ctx *c, int max_launches) { return batch_begin(c, max_launches, soc_ctx::INT_SHARED); }
+int soc_batch_begin_int(soc_ctx *c, int max_launches) { return batch_begin(c, max_launches, soc_ctx::INT_PER_LAUNCH); }
+int soc_batch_begin_int_groups(soc_ctx *c, int max_groups) { return batch_begin(c, max_groups, soc_ctx::INT_PER_GROUP); }
 
 int soc_batch_next_int(soc_ctx *c)
 {
     if (!c) return SOC_ERR_ARG;
-    if (!(c->batching && c->batch_group_int)) return fail(c, SOC_ERR_STATE, "soc_batch_next_int: call soc_batch_begin_int_groups first");
+    if (!(c->batching && c->int_mode == soc_ctx::INT_PER_GROUP)) return fail(c, SOC_ERR_STATE, "soc_batch_next_int: call soc_batch_begin_int_groups first");
     c->int_group_open = false;                               // the next launch takes a new, zeroed INT tally
-    return SOC_OK;
-}
-
-int soc_batch_begin_shared_int(soc_ctx *c, int max_launches)
-{
-    int r = soc_batch_begin(c, max_launches);
-    if (r) return r;
-    c->batch_share_int = true;
     return SOC_OK;
 }
 
@@ -1115,44 +1125,16 @@ int soc_sim_hp(soc_ctx *c, int PACKETS, int BATCH, float SEED, float TW, int GLO
     SocVariant V;
     fill_sim(c, S, V, 1, BATCH, SEED, 0.0f, TW, GLOBAL, gid_first, gid_count);
     S.NO_PS = 1;
-    // the brick sweep as for soc_sim_pb: the walk is SimRAM_PB's, only the creation of a packet differs
-    const int B = 1 << c->brick_log2;
-    const long long nb = (long long)((c->G.NX + B - 1) / B) * ((c->G.NY + B - 1) / B) * ((c->G.NZ + B - 1) / B);
-    bool bricks = (c->exec_mode != 0) && nb <= (1 << 18) && c->G.LEVELS <= 15 && c->device < 16 && (c->mirror == 0 || lt_capable(c, V.abu != 0)) && (c->with_int != 2 || lt_capable(c, V.abu != 0));
-    if (c->exec_mode < 0) bricks = bricks && gid_count >= 65536 && nb >= 8
-                                   && (!V.octree || (c->batching && (!V.wint || c->batch_keep_int || c->batch_share_int)) || (lt_capable(c, V.abu != 0) && gid_count >= SOC_LT_LONE_LAUNCH));
-    if (c->exec_mode == 1 && !bricks)
-        return fail(c, SOC_ERR_ARG, "soc_sim_hp: brick sweep requested but not applicable (mirror, with_int 2, > 15 levels or > 2^18 bricks)");
-    const bool defer = c->batching && bricks && (!V.wint || (c->batch_keep_int && V.wint != 2) || c->batch_share_int) && c->msf_ndust <= 1;   // WITH_MSF: per-species tables are not snapshotted
-    if (!defer) FLUSH(c);
-    if (defer && c->batch_keep_int && !same_sweep(c, SOC_SOURCE_HP, V.abu != 0))
-        return fail(c, SOC_ERR_STATE, "soc_sim_hp: a batch with the INT tally holds launches of one kind");
-    if (defer && !same_sweep(c, SOC_SOURCE_HP, V.abu != 0)) FLUSH(c);
-    r = take_int_slot(c, "soc_sim_hp", S);
-    if (r) return r;
-    c->last_passes = 0;
-    if (bricks) S.SOURCE = SOC_SOURCE_HP;
-    if (defer) {
-        const int slot = (int)c->pending.size();
-        r = snapshot_inputs(c, S, V, slot);
-        if (r) return r;
+    S.SOURCE = SOC_SOURCE_HP;          // the brick sweep as for soc_sim_pb: the walk is SimRAM_PB's, only the creation of a packet differs
+    return route_sim(c, SIM_HP, S, V, gid_count, [&](int slot) {      // a deferred launch keeps its own copy of the sky
+        if (slot < 0) return SOC_OK;
         if (!c->dHPslots) HIPCHK(c, dev_alloc(&c->dHPslots, (size_t)SOC_MAXLAUNCH * 2 * 49152));
         float *sky = c->dHPslots + (size_t)slot * 2 * 49152;
         HIPCHK(c, hipMemcpyAsync(sky, c->dHPBG, 49152 * 4, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(sky + 49152, c->dHPBGP, 49152 * 4, hipMemcpyDeviceToDevice, c->stream));
         S.HPBG = sky;  S.HPBGP = sky + 49152;
-        c->pending.push_back(S);
-        if ((!c->batch_keep_int && (int)c->pending.size() >= (V.abu ? std::min(c->batch_max, SOC_OPT_SLOTS) : c->batch_max))
-            || (int)c->pending.size() >= SOC_MAXLAUNCH) FLUSH(c);      // (with INT tallies per launch or group: a sweep's worth of launches)
         return SOC_OK;
-    }
-    if (bricks) {
-        hipError_t e = soc_brick_run_pb(c->device, c->G, &S, 1, V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form);
-        if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep failed: %s", hipGetErrorString(e));
-        return SOC_OK;
-    }
-    HIPCHK(c, soc_launch_sim_hp(c->G, S, V, c->stream));
-    return SOC_OK;
+    });
 }
 
 // a deferred cell-emission launch keeps its own copy of the emission (and of the packet weights): the caller uploads the next frequency's
@@ -1197,46 +1179,13 @@ int soc_sim_cl(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, float
     if (c->with_ali) S.XAB = c->dXAB;
     S.ROI = c->roi.save ? c->dRoi : nullptr;                // SimRAM_CL records too (kernel_ASOC.c:1250-1254)
     S.ROISAVE = c->roi.save;
+    S.SOURCE = SOC_SOURCE_CL;
     // The brick sweep: the same walk, the event workgroups step through the work item's cells.  It needs packets in
     // flight to sort -- one per work item that has a cell, min(GLOBAL, CELLS): with the reference's GLOBAL = 32768
     // the direct kernel (1.5e10 steps/s at C2, the rate of the fabric atomics) stays; `global` in the ini file
     // raises it.  Host-listed cells (USE_EMWEIGHT 2), ALI and region-of-interest records: direct kernel.
-    const int B = 1 << c->brick_log2;
-    const long long nb = (long long)((c->G.NX + B - 1) / B) * ((c->G.NY + B - 1) / B) * ((c->G.NZ + B - 1) / B);
     const long long inflight = std::min<long long>((long long)gid_first + gid_count, c->G.CELLS) - gid_first;
-    bool bricks = (c->exec_mode != 0) && nb <= (1 << 18) && c->G.LEVELS <= 15 && c->device < 16 && (c->mirror == 0 || lt_capable(c, V.abu != 0)) && (c->with_int != 2 || lt_capable(c, V.abu != 0))
-                  && c->use_emweight != 2 && (!c->with_ali || (lt_capable(c, V.abu != 0) && c->with_int != 2)) && (!c->roi.save || (lt_capable(c, V.abu != 0) && c->mirror == 0));
-    if (c->exec_mode < 0) bricks = bricks && inflight >= 262144 && nb >= 8
-                                   && (!V.octree || (c->batching && (!V.wint || c->batch_keep_int || c->batch_share_int)) || (lt_capable(c, V.abu != 0) && inflight >= SOC_LT_LONE_LAUNCH));
-    if (c->exec_mode == 1 && !bricks)
-        return fail(c, SOC_ERR_ARG, "soc_sim_cl: brick sweep requested but not applicable (mirror, with_int 2, USE_EMWEIGHT 2, ALI, roisave, > 15 levels or > 2^18 bricks)");
-    const bool defer = c->batching && bricks && (!V.wint || (c->batch_keep_int && V.wint != 2) || c->batch_share_int) && c->msf_ndust <= 1;   // WITH_MSF: per-species tables are not snapshotted
-    if (!defer) FLUSH(c);
-    if (defer && c->batch_keep_int && !same_sweep(c, SOC_SOURCE_CL, V.abu != 0))
-        return fail(c, SOC_ERR_STATE, "soc_sim_cl: a batch with the INT tally holds launches of one kind");
-    if (defer && !same_sweep(c, SOC_SOURCE_CL, V.abu != 0)) FLUSH(c);
-    r = take_int_slot(c, "soc_sim_cl", S);
-    if (r) return r;
-    c->last_passes = 0;
-    if (bricks) S.SOURCE = SOC_SOURCE_CL;
-    if (defer) {
-        const int slot = (int)c->pending.size();
-        r = snapshot_inputs(c, S, V, slot);
-        if (r) return r;
-        r = snapshot_emission(c, S, slot);
-        if (r) return r;
-        c->pending.push_back(S);
-        if ((!c->batch_keep_int && (int)c->pending.size() >= (V.abu ? std::min(c->batch_max, SOC_OPT_SLOTS) : c->batch_max))
-            || (int)c->pending.size() >= SOC_MAXLAUNCH) FLUSH(c);      // (with INT tallies per launch or group: a sweep's worth of launches)
-        return SOC_OK;
-    }
-    if (bricks) {
-        hipError_t e = soc_brick_run_pb(c->device, c->G, &S, 1, V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form);
-        if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep failed: %s", hipGetErrorString(e));
-        return SOC_OK;
-    }
-    HIPCHK(c, soc_launch_sim_cl(c->G, S, V, c->stream));
-    return SOC_OK;
+    return route_sim(c, SIM_CL, S, V, inflight, [&](int slot) { return slot < 0 ? SOC_OK : snapshot_emission(c, S, slot); });
 }
 
 // ------------------------------------------------------------------------------------

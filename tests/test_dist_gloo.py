@@ -31,7 +31,7 @@ import pytest
 @pytest.mark.parametrize("grid", ["octree", "cartesian"])
 def test_two_rank_sharded_run_equals_single(grid, tmp_path):
     """octree: one launch per frequency, INT all-reduced per frequency; cartesian: frequencies batched with their own INT
-    tallies (soc_batch_begin_int), each summed over the ranks when it is read"""
+    tallies (soc_batch_begin_int_groups, a group per frequency), each summed over the ranks when it is read"""
     sys.path.insert(0, os.path.join(REPO, "tests"))
     from test_host import _write_model
     from oracle_engine import OracleEngine

@@ -477,9 +477,58 @@ def test_deferred_launches_with_int_tally(octree, engine, oracle_soc):
     engine.set_features(0, 0, 0)
 
 
+def test_int_groups_of_mixed_kinds(engine, oracle_soc):
+    """soc_batch_begin_int_groups on a hierarchy that is not walked brick-locally: a group of a background and a
+    cell-emission launch cannot share a sweep, so the engine runs what is pending where the kind changes (the group's
+    INT tally survives it); every group's INT and the shared TABS equal the oracle's"""
+    cl = synth.octree_cloud(40, levels=3, frac=0.1, seed=3)
+    _, csc6 = synth.hg_scattering_table(0.6)
+    _, csc0 = synth.hg_scattering_table(0.1)
+    rr = np.random.default_rng(8)
+    leaf = cl.DENS > 0
+    Gbg, Gcl = 8 * cl.AREA, launch_fix(cl.CELLS)
+    groups = []
+    for k, (csc, a, s) in enumerate(((csc6, 2e-5, 6e-5), (csc0, 5e-5, 2e-5))):
+        EMIT = np.where(leaf, rr.uniform(0.5, 2.0, cl.CELLS), 0.0).astype(np.float32)
+        groups.append((Job(cl, csc, ABS=a, SCA=s, SOURCE=1, BATCH=2 - k, SEED=0.3711 + 0.2 * k, BG=1.0 + k, TW=1.0 + k, WITH_INT=1),
+                       Job(cl, csc, ABS=a, SCA=s, SOURCE=2, BATCH=1, SEED=0.11 + 0.3 * k, TW=0.5 + k, GLOBAL=Gcl, EMIT=EMIT, WITH_INT=1)))
+    T = np.zeros(cl.CELLS, np.float32)
+    INT, n = [], 0
+    for bg, ce in groups:
+        I = np.zeros(cl.CELLS, np.float32)
+        n += oracle_soc.sim(bg, 0, TABS=T, INT=I, nthreads=8)[2]
+        n += oracle_soc.sim(ce, 1, TABS=T, INT=I, nthreads=8)[2]
+        INT.append(I)
+    engine.set_cloud(cl)
+    engine.set_features(1, 0, 0)
+    engine.set_opt(None)
+    engine.set_mirror(0)
+    engine.set_ali(0)
+    engine.set_exec(1, 4)
+    engine.zero(0)
+    engine.zero(1)
+    engine.stats(reset=True)
+    engine.batch_begin_int_groups(0)
+    for bg, ce in groups:
+        engine.batch_next_int()
+        engine.set_scatter_table(bg.DSC, bg.CSC)
+        engine.set_optical(bg.ABS, bg.SCA)
+        engine.sim_pb(1, bg.PACKETS, bg.BATCH, bg.SEED, bg.BG, bg.TW, GLOBAL=Gbg)
+        engine.set_emission(ce.EMIT, None)
+        engine.sim_cl(2, 0, ce.BATCH, ce.SEED, ce.TW, Gcl)
+    engine.batch_end()
+    engine.sync()
+    assert engine.last_form() == 2 and engine.stats()["tally_events"] == n
+    assert_tally_close(engine.read_tally(0), T, rtol=1e-5)
+    for k in range(2):
+        assert_tally_close(engine.batch_read_int(k), INT[k], rtol=1e-5)
+    engine.set_features(0, 0, 0)
+    engine.set_exec(-1, 4)
+
+
 def test_absorbed_file_run_with_int_batches(engine, tmp_path):
     """asoc.py with an absorbed file (per-frequency INT tallies) on a Cartesian model: the frequencies of a source
-    block go through soc_batch_begin_int; file and tallies equal the oracle engine's run"""
+    block go through soc_batch_begin_int_groups, one frequency per group; file and tallies equal the oracle engine's run"""
     import os
     import sys
     sys.path.insert(0, os.path.dirname(__file__))
