@@ -252,6 +252,14 @@ int soc_last_passes(soc_ctx *ctx);
 /* how the last launch was executed: 0 direct kernel, 1 brick sweep on a Cartesian grid, 2 on a hierarchy read from global
  * memory, 3 on brick-local hierarchies (soc_ltree.h: hierarchies whose Index() the reference evaluates in double) */
 int soc_last_form(soc_ctx *ctx);
+/* the compiled absorption kernel the last launch or sweep of the handle ran on (-1 before any ran), for verification:
+ *   bits 0-1  form: 0 direct kernel, 1-3 as soc_last_form
+ *   bits 2-4  kind: direct 0 SimRAM_PB, 1 SimRAM_HP, 2 SimRAM_CL; sweeps the pass kernel's KIND -- 0 PB, 1 HP, 2 CL,
+ *             3 PB with background packets only (the lean kernel), 4 launches of several kinds (brick-local only)
+ *   bits 5-6  WINT: 0 TABS only, 1 INT tally, 2 INT and INTX/Y/Z (brick-local), 3 the INT tally alone in LDS (brick-local)
+ *   bit 7 octree, bit 8 Index() in double, bit 9 per-cell opacities, bit 10 ALI (brick-local), bit 11 the sweep of rays of
+ *   the scattered-light kernels (then the other fields are 0 but form 3, octree, double) */
+int soc_last_variant(soc_ctx *ctx);
 
 /* HIP-event timing on the handle's stream: bracket launches, then read elapsed ms */
 int soc_timer_start(soc_ctx *ctx);

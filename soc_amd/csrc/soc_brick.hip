@@ -2120,7 +2120,8 @@ static void soc_brick_launch_pass(int vkey, int kind, int nblocks, int T, size_t
 }
 
 hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int nlaunch, const SocVariant &V, int LB,
-                            int population, const SocBrickTune &tune, hipStream_t st, int *passes_out, int *form_out, const SocSca *sca)
+                            int population, const SocBrickTune &tune, hipStream_t st, int *passes_out, int *form_out, int *variant_out,
+                            const SocSca *sca)
 {
     if (form_out) *form_out = 0;
     // rays of the scattered-light kernels (soc_sca_events): flat images of SimRAM_PB / PS / CL with scalar opacities and one scattering function
@@ -2411,5 +2412,10 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int
     }
     if (passes_out) *passes_out = passes;
     if (form_out) *form_out = A.LT ? 3 : (V.octree ? 2 : 1);
+    if (variant_out) {                                                // the pass kernel the loop above launched
+        if (sca)       *variant_out = soc_variant_code(3, 0, 0, true, true, false, false, true);
+        else if (A.LT) *variant_out = soc_variant_code(3, kind, A.int_only ? 3 : V.wint, true, true, false, A.ali != 0, false);
+        else           *variant_out = soc_variant_code(V.octree ? 2 : 1, kind, V.wint ? 1 : 0, V.octree, V.octree && V.dbl, V.abu != 0, false, false);
+    }
     return hipSuccess;
 }

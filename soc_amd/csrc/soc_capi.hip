@@ -110,6 +110,7 @@ struct soc_ctx {
     int with_int = 0, ps_method = 0, use_emweight = 0, mirror = 0;
     // execution
     int exec_mode = -1, brick_log2 = 4, last_passes = 0, last_form = 0;
+    int last_variant = -1;                        // soc_last_variant: the absorption kernel last launched (-1: none yet)
     SocBrickTune tune{};
     // equilibrium temperature / emission (soc_emit.hip)
     float *dT = nullptr, *dTTT = nullptr, *dEbuf = nullptr, *dEF = nullptr;
@@ -183,6 +184,9 @@ static bool lt_capable(const soc_ctx *c, bool abu)
 static int run_direct(soc_ctx *c, SocSim S, const SocVariant &V)
 {
     c->last_passes = 0;
+    if (S.gid_count > 0)                    // (the launch wrappers run nothing without work items; Cartesian grids take the float kernels)
+        c->last_variant = soc_variant_code(0, S.SOURCE == SOC_SOURCE_HP ? 1 : S.SOURCE == SOC_SOURCE_CL ? 2 : 0, V.wint ? 1 : 0, V.octree,
+                                           V.octree && V.dbl, V.abu != 0, false, false);
     if (S.SOURCE == SOC_SOURCE_HP) {
         S.SOURCE = 1;
         HIPCHK(c, soc_launch_sim_hp(c->G, S, V, c->stream));
@@ -215,7 +219,7 @@ static int flush_pending(soc_ctx *c)
         for (const SocSim &S1 : todo) items += S1.gid_count;
         hipError_t e = hipErrorNotSupported;
         if (c->exec_mode == 1 || items >= SOC_SCA_RAYS_LAUNCH)     // (too few rays to fill the brick queues: the direct kernel, launch by launch)
-            e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form, &X);
+            e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form, &c->last_variant, &X);
         if (e == hipErrorNotSupported) {
             for (SocSim &S1 : todo) {
                 X.kind = S1.SCAKIND - 1;  X.DSC = S1.DSC;  X.OUT = S1.OUT;
@@ -233,7 +237,7 @@ static int flush_pending(soc_ctx *c)
     if (V.octree && todo.size() == 1 && c->exec_mode < 0 && !(lt_capable(c, V.abu != 0) && todo[0].gid_count >= SOC_LT_LONE_LAUNCH))
         return run_direct(c, todo[0], V);      // a single launch on a hierarchy: the direct kernel is as fast (1.9e10 vs 2.0e10 steps/s at 256^3, 4 levels)
     // packets in flight: chosen by the sweep from the number of bricks (-1)
-    hipError_t e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form);
+    hipError_t e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form, &c->last_variant);
     if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep of %d deferred launches failed: %s", (int)todo.size(), hipGetErrorString(e));
     return SOC_OK;
 }
@@ -490,6 +494,7 @@ int soc_set_tuning(soc_ctx *c, const char *name, int value)
 
 int soc_last_passes(soc_ctx *c) { return c ? c->last_passes : 0; }
 int soc_last_form(soc_ctx *c) { return (c && c->last_passes > 0) ? c->last_form : 0; }
+int soc_last_variant(soc_ctx *c) { return c ? c->last_variant : -1; }
 
 int soc_set_optical(soc_ctx *c, const float *ABS, const float *SCA, int ndust)
 {
@@ -885,7 +890,7 @@ static int route_sim(soc_ctx *c, SimKind kind, SocSim &S, const SocVariant &V, l
         return SOC_OK;
     }
     if (!bricks) return run_direct(c, S, V);
-    hipError_t e = soc_brick_run_pb(c->device, c->G, &S, 1, V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form);
+    hipError_t e = soc_brick_run_pb(c->device, c->G, &S, 1, V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form, &c->last_variant);
     if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep failed: %s", hipGetErrorString(e));
     return SOC_OK;
 }
@@ -1348,7 +1353,7 @@ static int sca_launch(soc_ctx *c, const char *who, int kind, SocSim &S, SocVaria
         if (kind == SOC_SCA_CL) R.SOURCE = SOC_SOURCE_CL;
         SocVariant W = V;
         W.wint = 0;
-        hipError_t e = soc_brick_run_pb(c->device, c->G, &R, 1, W, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form, &X);
+        hipError_t e = soc_brick_run_pb(c->device, c->G, &R, 1, W, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form, &c->last_variant, &X);
         if (e == hipSuccess) return SOC_OK;
         if (e != hipErrorNotSupported || c->exec_mode == 1) return fail(c, SOC_ERR_HIP, "%s: brick sweep failed: %s", who, hipGetErrorString(e));
     }

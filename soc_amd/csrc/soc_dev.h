@@ -190,9 +190,19 @@ struct SocBrickTune {
 // brick-sweep execution (soc_brick.hip): LDS-resident tallies, packets sorted by brick
 // population: packets in flight (0 = all work items at once, -1 = chosen from the number of bricks): the other work
 // items are admitted as earlier ones finish
+// variant_out: the code of the pass kernel that ran (soc_variant_code; untouched when no kernel ran)
 hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *S, int nlaunch, const SocVariant &V, int LB,
                             int population, const SocBrickTune &tune, hipStream_t st, int *passes_out, int *form_out,
-                            const struct SocSca *sca = nullptr);      // sca: the launch is one of the scattered-light kernels (rays, soc_sca_events)
+                            int *variant_out, const struct SocSca *sca = nullptr);      // sca: the launch is one of the scattered-light kernels (rays, soc_sca_events)
+
+// The compiled absorption kernel a launch ran on, as soc_last_variant reports it (bit layout: include/soc_hip.h, SOC_VAR_*).
+// form 0 direct (kind 0 PB, 1 HP, 2 CL), 1 Cartesian sweep, 2 sweep of a hierarchy in global memory, 3 brick-local sweep
+// (kind: the KIND template argument 0-4); wint: the WINT template argument; rays: the scattered-light sweep of rays.
+static inline int soc_variant_code(int form, int kind, int wint, bool octree, bool dbl, bool abu, bool ali, bool rays)
+{
+    return form | (kind << 2) | (wint << 5) | (octree ? 1 << 7 : 0) | (dbl ? 1 << 8 : 0) | (abu ? 1 << 9 : 0) | (ali ? 1 << 10 : 0)
+           | (rays ? 1 << 11 : 0);
+}
 void soc_brick_release(int device);
 void soc_brick_invalidate(int device);      // the grid changed: bricks of a hierarchy are rebuilt at the next sweep
 

@@ -31,6 +31,7 @@ API = {
     "soc_set_features": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "soc_set_exec": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "soc_last_form": (C.c_int, [C.c_void_p]),
+    "soc_last_variant": (C.c_int, [C.c_void_p]),
     "soc_set_tuning": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "soc_last_passes": (C.c_int, [C.c_void_p]),
     "soc_set_optical": (C.c_int, [C.c_void_p, _F, _F, C.c_int]),
@@ -120,6 +121,17 @@ API = {
 }
 
 _lib = None
+
+VARIANT_FORMS = ("direct", "cartesian", "global_tree", "brick_local")
+
+
+def decode_variant(code):
+    """soc_last_variant's code (bit layout: include/soc_hip.h) as a dict; None for -1 (no kernel has run)"""
+    code = int(code)
+    if code < 0:
+        return None
+    return dict(form=code & 3, kind=(code >> 2) & 7, wint=(code >> 5) & 3, octree=(code >> 7) & 1, dbl=(code >> 8) & 1,
+                abu=(code >> 9) & 1, ali=(code >> 10) & 1, rays=(code >> 11) & 1, code=code)
 
 
 class SocError(RuntimeError):
@@ -263,6 +275,10 @@ class Engine:
     def last_form(self):
         """0 direct kernel, 1 brick sweep (Cartesian), 2 hierarchy in global memory, 3 brick-local hierarchies"""
         return int(self.lib.soc_last_form(self.h))
+
+    def last_variant(self):
+        """the compiled absorption kernel of the last launch or sweep: decode_variant(soc_last_variant), None before any ran"""
+        return decode_variant(self.lib.soc_last_variant(self.h))
 
     def set_tuning(self, **params):
         """shape of the brick sweep (soc_set_tuning): threads, chunk, steps_per_visit, swap_lanes, climb_lanes,

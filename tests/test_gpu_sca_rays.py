@@ -34,7 +34,7 @@ def _rays(engine, job, view, kind, g0, g1):
     engine.set_exec(1, 4)
     try:
         img, st = run_sca(engine, job, view, kind, g0, g1 - g0)
-        assert engine.last_passes() > 0 and engine.last_form() == 3
+        assert engine.last_passes() > 0 and engine.last_form() == 3 and engine.last_variant()["rays"] == 1
         assert engine.sca_ray_steps() > st["packets"]
     finally:
         engine.set_exec(-1, 4)
@@ -152,6 +152,7 @@ def test_a_batch_of_launches_with_an_image_per_frequency(engine, parking):
     engine.batch_end()
     st = engine.stats()
     assert engine.last_form() == 3 and engine.last_passes() > 0   # ... and all of it ran as one sweep
+    assert engine.last_variant()["rays"] == 1                     # (of rays)
     for key in ("tally_events", "packets", "scatterings"):
         assert st[key] == sum(s[key] for s in stats)
     for f in range(3):
