@@ -258,7 +258,9 @@ int soc_last_form(soc_ctx *ctx);
  *             3 PB with background packets only (the lean kernel), 4 launches of several kinds (brick-local only)
  *   bits 5-6  WINT: 0 TABS only, 1 INT tally, 2 INT and INTX/Y/Z (brick-local), 3 the INT tally alone in LDS (brick-local)
  *   bit 7 octree, bit 8 Index() in double, bit 9 per-cell opacities, bit 10 ALI (brick-local), bit 11 the sweep of rays of
- *   the scattered-light kernels (then the other fields are 0 but form 3, octree, double) */
+ *   the scattered-light kernels (then the other fields are 0 but form 3, octree, double, and bits 12-13)
+ *   bit 12 (sweeps of rays) the image was a Healpix map seen from a position (soc_sca_set_healpix)
+ *   bit 13 (sweeps of rays) the sweep held a SimRAM_HP launch (soc_sca_sim_hp: the Healpix sky as the source) */
 int soc_last_variant(soc_ctx *ctx);
 
 /* HIP-event timing on the handle's stream: bracket launches, then read elapsed ms */

@@ -8,11 +8,14 @@ field and the dust emission (SimRAM_CL) frequency by frequency with peel-off tow
 OUTCOMING[NFREQ, NDIR, NPIX.y, NPIX.x] in Jy/sr (ASOCS.py:887-899) with the reference's header.
 
 The host loop (source block II -> frequency; then the CLPAC loop) and every launch formula
-are the reference's; the kernels are soc_amd/csrc/soc_sca.hip.  With several ranks each
-launch is split by logical work-item id and the image is summed with one all-reduce.
-``perspective x y z`` switches to one Healpix map (``outnside``) seen from that position,
-``hpbg`` to the Healpix background (sca SimRAM_HP).  Not covered (refused with a clear
-message): ROI files, several scattering functions.
+are the reference's.  The kernels: the direct kernel soc_sca_kernel (soc_amd/csrc/soc_sca.hip)
+and, on hierarchies that take the brick-local form, the sweep of rays (soc_brick.hip:
+soc_lray_pass), which runs the launches of a source block deferred into one batch.  With
+several ranks each launch is split by logical work-item id and the image is summed with one
+all-reduce.  ``perspective x y z`` switches to one Healpix map (``outnside``) seen from that
+position, ``hpbg`` to the Healpix background (sca SimRAM_HP); both run on either kernel.
+Several scattering functions (-D WITH_MSF) and per-cell opacities run on the direct kernel.
+Not covered (refused with a clear message): ROI files (``roiload``), ``singleabu``.
 """
 import sys
 import time

@@ -636,7 +636,12 @@ __device__ __forceinline__ int soc_cell_index(const SocGrid &G, int level, int c
 //   unit spends its time on), 8 B per cell instead of 12.
 // ALI: -D WITH_ALI (kernel_ASOC.c:1394-1396, :1486-1494; SimRAM_CL only): what a packet deposits in the cell that emitted it goes to the XAB
 // tally instead of TABS.  The LDS then holds the cell numbers of the brick's slots (sC) and an XAB tally (sX) as well: 16 B per cell.
-template <int WINT, bool RAY = false, bool ALI = false>
+// LIM (RAY only): the sweep of a Healpix image, whose peel-off rays end at the observer (kernel_ASOC_sca.c:329-335).  Such a ray carries
+// MINUS the distance it has left in the free-path slot (B.w < 0: no free path ends there) and steps min(left, ds) + 1e-6 -- added in double
+// for SimRAM_PB launches, flag bit 1 of the launch -- and it is done when nothing is left: it goes to queue 0 of its launch (the one of the
+// rays that left the model) with the optical depth of that last step added, the position wherever GetStep put it (the event lane does not
+// read it).  Its record's B.w goes back to memory with it.
+template <int WINT, bool RAY = false, bool ALI = false, bool LIM = false>
 __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPack &K, const SocBrickArgs &A, const int bid)
 {
     if (bid >= *A.ndesc) return;
@@ -663,7 +668,7 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
     const SocSim &S = K.S[0];
     for (int l = threadIdx.x; l < K.n; l += nthr) {
         sL[4 * l] = K.S[l].ABS;  sL[4 * l + 1] = K.S[l].SCA;  sL[4 * l + 2] = K.S[l].TW;
-        sL[4 * l + 3] = __int_as_float((K.S[l].SOURCE == SOC_SOURCE_CL) ? 1 : 0);
+        sL[4 * l + 3] = __int_as_float(((K.S[l].SOURCE == SOC_SOURCE_CL) ? 1 : 0) | ((LIM && K.S[l].SCAKIND == SOC_SCA_PB + 1) ? 2 : 0));
     }
     const int mybrick = (A.NBQ > A.NB) ? (D.brick % A.NB) : D.brick;
     const int qbase = D.brick - mybrick;                   // first brick queue of this workgroup's launch (0 when the launches share queues)
@@ -710,6 +715,7 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
     int   cx = 0, cy = 0, cz = 0, level = 0, slot = 0, obase = 0, nvisit = 0, key = 0, cslot = 0, lq = 0, evq = 0;      // evq: first event queue of the packet's launch      // obase: slot of the first cell of the packet's octet
     int   what = SOC_LTM_STEP;                              // what the Index() part has to do for the lane: finish a step, an arrival, or find the packet's cell
     bool  nonudge = false;                                 // SimRAM_CL: no nudge after a failed step (kernel_ASOC.c:1530-1540 has none)
+    bool  dblstep = false;                                 // LIM: the launch adds the 1e-6 of a peel-off step in double (SimRAM_PB)
     uint32_t dz = 0, dw = 0, wid = 0;
     int   mode = SOC_BM_SWAP;
     bool  have = false, nhave = false;                                       // the packet in hand, the prefetched one
@@ -777,6 +783,7 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                         { const soc_f4v v = { tau, __int_as_float(cx), __int_as_float(cy), __int_as_float(cz | (lq << SOC_LQ_SHIFT)) };  SOC_NT_STORE(v, (SOC_GLOBAL soc_f4v *)&q->C); }
                         q->D.z = (dz & 0x1fffffffu) | ((uint32_t)level << 29);
                         q->D.w = dw;
+                        if (LIM) SOC_NT_STORE(free_path, &q->B.w);                 // (the distance a peel-off ray has left)
                         SOC_NT_STORE((uint32_t)key, &keyq_c[cslot]);              // its rank in that queue is settled after the walk, for all packets at once
                     }
                     // (4) the prefetched packet becomes the current one
@@ -793,6 +800,7 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                         evq = A.NBQ + A.EQ * n_lq;
                         level = (int)(dz >> 29);
                         kabs = l4.x;  ksca = l4.y;  tw = l4.z;  nonudge = RAY || ((__float_as_int(l4.w) & 1) != 0);
+                        if (LIM) dblstep = (__float_as_int(l4.w) & 2) != 0;
                         nvisit = 0;
                         mode = have ? SOC_BM_STEP : mode;
                         slot = -1;  obase = -1;
@@ -849,10 +857,25 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                 ds = ds * soc_lt_pow2(-level);                                    // ldexp(ds, -level)
                 tauA = ds * dens * kabs;
                 dtau = ds * dens * (RAY ? photons : ksca);
-                const bool scat = free_path < (tau + dtau);                       // the free path ends in this cell:
+                bool scat = free_path < (tau + dtau);                             // the free path ends in this cell:
+                if (LIM) {
+                    // a peel-off ray towards an observer at a finite distance: only as far as the observer (kernel_ASOC_sca.c:329-335)
+                    const bool lim = free_path < 0.0f;
+                    float d = (-free_path < ds) ? -free_path : ds;
+                    d = dblstep ? (float)((double)d + 1.0e-6) : (d + 1.0e-6f);
+                    d = lim ? d : ds;
+                    dtau = d * dens * photons;
+                    free_path = lim ? (free_path + d) : free_path;                // -(left - d)
+                    const bool stop = lim & !(free_path < 0.0f);                 // nothing left: done, at queue 0 of its launch
+                    scat = !lim & (free_path < (tau + dtau));
+                    tau = stop ? (tau + dtau) : tau;
+                    n_tally += stop ? 1u : 0u;
+                    mode = stop ? SOC_BM_SWAP : mode;  key = stop ? evq : key;
+                    move = !stop;
+                }
                 px = scat ? p0x : px;  py = scat ? p0y : py;  pz = scat ? p0z : pz;   // back to the start of the step
                 mode = scat ? SOC_BM_SWAP : mode;  key = scat ? (evq + 1) : key;  // -> scattering queue of its launch
-                move = !scat;
+                move = move & !scat;
             }
             // ---- Index (kernel_ASOC_aux.c:198-278), first half: where the point is, and the read of the slot the descent starts from;
             // the tally of the step while that read is in flight; the descent to the leaf; the outcome.  ONE divergent region, and the
@@ -1390,11 +1413,17 @@ __global__ __launch_bounds__(1024) void soc_lbrick_pass_ali(const SocGrid G, con
 // step was one that exact geometry does not decide (queue 2, soc_ltree.h).  The chain of blocks a lane runs through is the one
 // of soc_sca_kernel's service arm (soc_sca.hip), whose order of operations and of RNG draws is the reference's; it ends when the
 // lane has a ray to walk again or the work item is finished.
-//   ray record:  A = position, kappa factor | B = direction, free path (+inf for look-ahead and peel-off rays) | C = optical
-//                depth so far, cell coordinates | D = RNG state, III | scatterings << 24 | level << 29, SimRAM_CL: emitting cell
-//   park record: A = packet position, photons | B = packet direction | C = its cell coordinates, level | D = kind of the current
-//                ray (SOC_RM_*), observer index
-// Not on this path (the caller falls back to soc_sca_kernel): Healpix images, SimRAM_HP, per-cell opacities, WITH_MSF.
+//   ray record:  A = position, kappa factor | B = direction, free path (+inf for look-ahead and flat-image peel-off rays; minus the
+//                distance left to the observer for Healpix peel-off rays) | C = optical depth so far, cell coordinates | D = RNG
+//                state, III | scatterings << 24 | level << 29, SimRAM_CL: emitting cell
+//   park record: A = packet position, photons | B = packet direction, 1/d^2 of a Healpix peel-off ray | C = its cell coordinates,
+//                level | D = kind of the current ray (SOC_RM_*), observer index
+// Healpix images seen from a position (SocSca::NDIR < 0, soc_lray_pass<true, .>): the peel-off ray starts towards the observer from
+// the root position of the scattering (RootPos) and ends at the observer or where it leaves the model (soc_lbrick_walk<., RAY, ., LIM>);
+// the event lane adds delta / d^2 to the pixel of its direction.  SimRAM_HP (the Healpix sky as the source, soc_lray_pass<., true>):
+// soc_hp_sca_create, the CL weighting (HG_TEST, +-0.9999, no draw on an empty line of sight), no surface element; a packet that misses
+// the cloud is counted and the next one is created.
+// Not on this path (the caller falls back to soc_sca_kernel): per-cell opacities, WITH_MSF.
 // ---------------------------------------------------------------------------------------
 enum { SOC_RM_NONE = 0, SOC_RM_FFS = 1, SOC_RM_MAIN = 2, SOC_RM_PEEL = 3 };
 enum { SOC_RE_SCAT = 4, SOC_RE_PEEL_END = 5, SOC_RE_FFS_END = 6, SOC_RE_CREATE = 7, SOC_RE_DONE = 8 };     // blocks between rays
@@ -1406,6 +1435,7 @@ struct SocRayLane {                                                   // what so
     soc_rng_t rng;
 };
 
+template <bool HPX, bool HPSKY>
 __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPack &K, const SocBrickArgs &A, const int ebid, const int slice)
 {
     const SocSca &V = A.sca;
@@ -1425,7 +1455,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
     const int evk = (D.brick - A.NBQ) % A.EQ;                 // 0 left the model (or not started), 1 scattering, 2 slow step
     const SocSim &S = K.S[lq];
     const int  KIND = S.SCAKIND - 1;                          // the kernel of this queue's launch (uniform in the workgroup)
-    const bool CLW = (KIND == SOC_SCA_CL);
+    const bool CLW = (KIND == SOC_SCA_CL) || (HPSKY && (KIND == SOC_SCA_HP));      // +-0.9999 clamp, HG_TEST weight, no draw on an empty line of sight
     const int qbase = 0;                                      // rays of all launches share the brick queues (no tallies in LDS)
     extern __shared__ float lds[];
     int   *sH   = (int *)lds;
@@ -1438,7 +1468,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
     unsigned int n_add = 0, n_pkt = 0, n_scat = 0;
     uint32_t mypack = 0;
     const float kabs = S.ABS, ksca = S.SCA;
-    const int   NDIRS = V.NDIR;
+    const int   NDIRS = HPX ? 1 : V.NDIR;                     // HPX: one Healpix map seen from the position ODIRS[0]
 
     for (int j = threadIdx.x; j < D.count; j += blockDim.x) {
         const uint32_t wid = A.idq[D.start + j];
@@ -1459,6 +1489,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
         float dx_ = q.B.x, dy_ = q.B.y, dz_ = q.B.z;
         int   mcx = __float_as_int(q.C.x), mcy = __float_as_int(q.C.y), mcz = __float_as_int(q.C.z), mlevel = __float_as_int(q.C.w);
         int   rmode = (int)q.D.x, idir = (int)q.D.y;
+        float invd2 = q.B.w;                                  // HPX: 1/d^2 of the current peel-off ray
         w.ind = -1;  w.dens = 0.0f;
         int   lvl_post = 0, mode;
         bool  cc_ok = true;                                   // (ccx, ccy, ccz) are the coordinates of cell (w.level, w.ind)
@@ -1505,7 +1536,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
 
         const int id = (int)(S.gid0 + (wid - K.first[lq]));
         SocSurfElem E;
-        if (KIND != SOC_SCA_CL) E = soc_surface_element(G, S, id);
+        if ((KIND != SOC_SCA_CL) && !(HPSKY && (KIND == SOC_SCA_HP))) E = soc_surface_element(G, S, id);      // (SimRAM_HP has none)
         while (mode > SOC_RM_PEEL && mode != SOC_RE_DONE) {
             // ---- start of a scattering event
             if (mode == SOC_RE_SCAT) {
@@ -1520,7 +1551,20 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                 mx = w.px;  my = w.py;  mz = w.pz;  dx_ = w.ux;  dy_ = w.uy;  dz_ = w.uz;
                 mlevel = w.level;  mcx = ccx;  mcy = ccy;  mcz = ccz;
                 idir = 0;
-                if (NDIRS > 0) {
+                if (HPX) {
+                    // direction and distance to the observer from the root position of the scattering (:319-327); the ray carries
+                    // minus the distance in its free-path slot (soc_lbrick_walk<., RAY, ., LIM>)
+                    float rx = w.px, ry = w.py, rz = w.pz;
+                    soc_rootpos(G, sOFF, rx, ry, rz, w.level, w.ind);
+                    const float4 o = V.ODIRS[0];
+                    w.ux = o.x - rx;  w.uy = o.y - ry;  w.uz = o.z - rz;
+                    const float dxrem = soc_sqrtf(w.ux * w.ux + w.uy * w.uy + w.uz * w.uz);
+                    invd2 = 1.0f / (dxrem * dxrem);
+                    soc_normalize(w.ux, w.uy, w.uz);
+                    tau = 0.0f;
+                    free_path = -dxrem;
+                    mode = (dxrem > 0.0f) ? SOC_RM_PEEL : SOC_RE_PEEL_END;
+                } else if (NDIRS > 0) {
                     const float4 o = V.ODIRS[0];
                     w.ux = o.x;  w.uy = o.y;  w.uz = o.z;
                     tau = 0.0f;
@@ -1546,14 +1590,24 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                         b = b < 0 ? 0 : (b > S.BINS - 1 ? S.BINS - 1 : b);
                         delta = w.photons * soc_expf(-taup) * S.DSC[b];
                     }
-                    const float qx = w.px - V.CX, qy = w.py - V.CY, qz = w.pz - V.CZ;
-                    const float4 ra = V.ORA[idir], de = V.ODE[idir];
-                    int i = (int)((0.5f * V.NPIX_X - 0.00005f) + (qx * ra.x + qy * ra.y + qz * ra.z) / V.MAP_DX);
-                    int jj = (int)((0.5f * V.NPIX_Y - 0.00005f) + (qx * de.x + qy * de.y + qz * de.z) / V.MAP_DX);
-                    if ((i >= 0) && (jj >= 0) && (i < V.NPIX_X) && (jj < V.NPIX_Y)) {
-                        i += idir * V.NPIX_X * V.NPIX_Y + jj * V.NPIX_X;
-                        soc_tally(S.OUT, i, delta);
+                    if (HPX) {
+                        // 1/d^2 and the pixel of the direction towards the observer (:352-360)
+                        delta = invd2 * delta;
+                        const float theta = soc_acosf(-w.uz);
+                        const float phi   = soc_atan2f(w.uy, w.ux);
+                        const int pix = soc_angles2pixel_ring(-V.NDIR, phi, theta);
+                        if (pix >= 0) soc_tally(S.OUT, pix, delta);
                         n_add++;
+                    } else {
+                        const float qx = w.px - V.CX, qy = w.py - V.CY, qz = w.pz - V.CZ;
+                        const float4 ra = V.ORA[idir], de = V.ODE[idir];
+                        int i = (int)((0.5f * V.NPIX_X - 0.00005f) + (qx * ra.x + qy * ra.y + qz * ra.z) / V.MAP_DX);
+                        int jj = (int)((0.5f * V.NPIX_Y - 0.00005f) + (qx * de.x + qy * de.y + qz * de.z) / V.MAP_DX);
+                        if ((i >= 0) && (jj >= 0) && (i < V.NPIX_X) && (jj < V.NPIX_Y)) {
+                            i += idir * V.NPIX_X * V.NPIX_Y + jj * V.NPIX_X;
+                            soc_tally(S.OUT, i, delta);
+                            n_add++;
+                        }
                     }
                     idir++;
                 }
@@ -1672,6 +1726,15 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                     }
                     III = IRAY;
                     cl_cell = (uint32_t)ICELL;
+                } else if (HPSKY && (KIND == SOC_SCA_HP)) {
+                    if (III >= S.BATCH) {
+                        mode = SOC_RE_DONE;
+                    } else {
+                        soc_hp_sca_create<true>(G, S, sOFF, w);
+                        III++;
+                        n_pkt++;
+                        have = (w.ind >= 0);                  // a packet that misses the cloud is counted and skipped (:222)
+                    }
                 } else {
                     if (III >= S.BATCH) {
                         mode = SOC_RE_DONE;
@@ -1682,11 +1745,13 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                     }
                 }
                 if (have) {
-                    n_pkt++;
-                    if (soc_fabsf(w.ux) < SOC_DEPS) w.ux = SOC_DEPS;
-                    if (soc_fabsf(w.uy) < SOC_DEPS) w.uy = SOC_DEPS;
-                    if (soc_fabsf(w.uz) < SOC_DEPS) w.uz = SOC_DEPS;
-                    soc_normalize(w.ux, w.uy, w.uz);
+                    if (!HPSKY || (KIND != SOC_SCA_HP)) {     // SimRAM_HP has conditioned the direction itself
+                        n_pkt++;
+                        if (soc_fabsf(w.ux) < SOC_DEPS) w.ux = SOC_DEPS;
+                        if (soc_fabsf(w.uy) < SOC_DEPS) w.uy = SOC_DEPS;
+                        if (soc_fabsf(w.uz) < SOC_DEPS) w.uz = SOC_DEPS;
+                        soc_normalize(w.ux, w.uy, w.uz);
+                    }
                     tau  = 0.0f;
                     scat = 0;
                     cc_ok = false;
@@ -1711,13 +1776,13 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
             rmode = mode;
         }
         const float kk = (mode == SOC_RM_PEEL) ? (kabs + ksca) : ksca;
-        const float fp = (mode == SOC_RM_MAIN) ? free_path : __builtin_inff();
+        const float fp = ((mode == SOC_RM_MAIN) || (HPX && (mode == SOC_RM_PEEL))) ? free_path : __builtin_inff();
         o.A = make_float4(w.px, w.py, w.pz, kk);
         o.B = make_float4(w.ux, w.uy, w.uz, fp);
         o.C = make_float4(tau, __int_as_float(ccx), __int_as_float(ccy), __int_as_float(ccz | (lq << SOC_LQ_SHIFT)));
-        o.D = make_uint4(w.rng.x, w.rng.c, (uint32_t)III | ((uint32_t)scat << 24) | ((uint32_t)w.level << 29), CLW ? cl_cell : 0u);
+        o.D = make_uint4(w.rng.x, w.rng.c, (uint32_t)III | ((uint32_t)scat << 24) | ((uint32_t)w.level << 29), (CLW && (KIND == SOC_SCA_CL)) ? cl_cell : 0u);
         r.A = make_float4(mx, my, mz, w.photons);
-        r.B = make_float4(dx_, dy_, dz_, 0.0f);
+        r.B = make_float4(dx_, dy_, dz_, HPX ? invd2 : 0.0f);
         r.C = make_float4(__int_as_float(mcx), __int_as_float(mcy), __int_as_float(mcz), __int_as_float(mlevel));
         r.D = make_uint4((uint32_t)rmode, (uint32_t)idir, 0u, 0u);
         pk[wid] = o;
@@ -1739,15 +1804,18 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
     }
 }
 
+// HPX: the view is a Healpix map seen from a position (SocSca::NDIR < 0): peel-off rays that end at the observer.  HPSKY: the sweep
+// holds SimRAM_HP launches (the creation of their packets stays out of the kernels of sweeps without them: registers)
+template <bool HPX, bool HPSKY>
 __global__ __launch_bounds__(1024) void soc_lray_pass(const SocGrid G, const SocSimPack *Kp, const SocBrickArgs A, const int nwalk, const int slices)
 {
     const SocSimPack &K = *Kp;
     const int b = (int)blockIdx.x;
     if (b < nwalk) {
-        soc_lbrick_walk<false, true>(G, K, A, b);
+        soc_lbrick_walk<false, true, false, HPX>(G, K, A, b);
     } else {
         const int e = b - nwalk;
-        soc_sca_events(G, K, A, e / slices, e % slices);
+        soc_sca_events<HPX, HPSKY>(G, K, A, e / slices, e % slices);
     }
 }
 
@@ -2072,11 +2140,19 @@ static void soc_lbrick_launch_pass(int wint, int kind, int nblocks, int T, size_
 #undef SOC_LB_CASE
 }
 
-static hipError_t soc_lray_launch_pass(int nblocks, int T, size_t lds, hipStream_t st, const SocGrid &G, const SocSimPack *K,
+template <bool HPX, bool HPSKY>
+static void soc_lray_launch_one(int nblocks, int T, size_t lds, hipStream_t st, const SocGrid &G, const SocSimPack *K,
+                                const SocBrickArgs &A, int nwalk, int slices)
+{
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)soc_lray_pass<HPX, HPSKY>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    soc_lray_pass<HPX, HPSKY><<<nblocks, T, lds, st>>>(G, K, A, nwalk, slices);
+}
+
+static hipError_t soc_lray_launch_pass(bool hpsky, int nblocks, int T, size_t lds, hipStream_t st, const SocGrid &G, const SocSimPack *K,
                                        const SocBrickArgs &A, int nwalk, int slices)
 {
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)soc_lray_pass, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    soc_lray_pass<<<nblocks, T, lds, st>>>(G, K, A, nwalk, slices);
+    if (A.sca.NDIR < 0) { if (hpsky) soc_lray_launch_one<true, true>(nblocks, T, lds, st, G, K, A, nwalk, slices);  else soc_lray_launch_one<true, false>(nblocks, T, lds, st, G, K, A, nwalk, slices); }
+    else                { if (hpsky) soc_lray_launch_one<false, true>(nblocks, T, lds, st, G, K, A, nwalk, slices); else soc_lray_launch_one<false, false>(nblocks, T, lds, st, G, K, A, nwalk, slices); }
     return hipSuccess;
 }
 
@@ -2124,13 +2200,17 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int
                             const SocSca *sca)
 {
     if (form_out) *form_out = 0;
-    // rays of the scattered-light kernels (soc_sca_events): flat images of SimRAM_PB / PS / CL with scalar opacities and one scattering function
+    // rays of the scattered-light kernels (soc_sca_events): flat or Healpix images of SimRAM_PB / PS / CL / HP with scalar opacities and one
+    // scattering function
+    bool sca_hp = false;
     if (sca) {
-        if (sca->NDIR < 0 || V.abu || V.wint) return hipErrorNotSupported;
+        if (sca->NDIR == 0 || V.abu || V.wint) return hipErrorNotSupported;
         for (int l = 0; l < nlaunch; l++) {
             const int k = Sin[l].SCAKIND - 1;
-            if ((k != SOC_SCA_PB && k != SOC_SCA_PS && k != SOC_SCA_CL) || Sin[l].NDUST > 1 || Sin[l].BINS < 1 || !Sin[l].OUT) return hipErrorNotSupported;
-            if ((k != SOC_SCA_CL) && !Sin[l].DSC) return hipErrorNotSupported;
+            if ((k != SOC_SCA_PB && k != SOC_SCA_PS && k != SOC_SCA_CL && k != SOC_SCA_HP) || Sin[l].NDUST > 1 || Sin[l].BINS < 1 || !Sin[l].OUT) return hipErrorNotSupported;
+            if ((k == SOC_SCA_PB || k == SOC_SCA_PS) && !Sin[l].DSC) return hipErrorNotSupported;
+            if ((k == SOC_SCA_HP) && (!Sin[l].HPBG || (Sin[l].HPBG_WEIGHTED && !Sin[l].HPBGP))) return hipErrorNotSupported;
+            sca_hp = sca_hp || (k == SOC_SCA_HP);
             if ((k == SOC_SCA_CL) != (Sin[l].SOURCE == SOC_SOURCE_CL)) return hipErrorInvalidValue;
         }
     }
@@ -2236,7 +2316,7 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int
         const SocSim &S = Sin[l];
         if (S.BATCH >= (1 << 24)) return hipErrorNotSupported;       // III shares a word with the scattering count
         uint32_t c = S.gid_count;
-        if ((S.SOURCE == 1 || S.SOURCE == SOC_SOURCE_HP) && !tune.oversub) {
+        if ((S.SOURCE == 1 || S.SOURCE == SOC_SOURCE_HP) && S.SCAKIND != SOC_SCA_HP + 1 && !tune.oversub) {      // (the sca SimRAM_HP has no surface elements)
             const long long lim = 8LL * 2 * ((long long)G.NX * G.NY + (long long)G.NY * G.NZ + (long long)G.NZ * G.NX);
             if ((long long)S.gid0 >= lim) c = 0;
             else if ((long long)S.gid0 + c > lim) c = (uint32_t)(lim - S.gid0);
@@ -2385,7 +2465,7 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int
             A.idq = bb.idq[c];  A.idq_next = bb.idq[1 - c];
             A.desc = bb.desc[c];  A.ndesc = bb.ndesc + c;
             A.desc_next = bb.desc[1 - c];  A.ndesc_next = bb.ndesc + (1 - c);
-            if (sca)         BCHK(soc_lray_launch_pass(maxdesc_now + nev_now, A.T, lds, st, G, bb.pack, A, maxdesc_now, slices));
+            if (sca)         BCHK(soc_lray_launch_pass(sca_hp, maxdesc_now + nev_now, A.T, lds, st, G, bb.pack, A, maxdesc_now, slices));
             else if (A.LT)   soc_lbrick_launch_pass(A.int_only ? 3 : V.wint, kind, maxdesc_now + nev_now, A.T, lds, st, G, bb.pack, A, maxdesc_now, slices);
             else if (!V.octree) soc_brick_launch_pass<false, false>(vkey, kind, maxdesc_now + nev_now, A.T, lds, st, G, bb.pack, A, maxdesc_now, slices);
             else if (!V.dbl) soc_brick_launch_pass<true, false>(vkey, kind, maxdesc_now + nev_now, A.T, lds, st, G, bb.pack, A, maxdesc_now, slices);
@@ -2413,7 +2493,7 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int
     if (passes_out) *passes_out = passes;
     if (form_out) *form_out = A.LT ? 3 : (V.octree ? 2 : 1);
     if (variant_out) {                                                // the pass kernel the loop above launched
-        if (sca)       *variant_out = soc_variant_code(3, 0, 0, true, true, false, false, true);
+        if (sca)       *variant_out = soc_variant_code(3, 0, 0, true, true, false, false, true) | (sca->NDIR < 0 ? SOC_VAR_HEALPIX : 0) | (sca_hp ? SOC_VAR_HPSKY : 0);
         else if (A.LT) *variant_out = soc_variant_code(3, kind, A.int_only ? 3 : V.wint, true, true, false, A.ali != 0, false);
         else           *variant_out = soc_variant_code(V.octree ? 2 : 1, kind, V.wint ? 1 : 0, V.octree, V.octree && V.dbl, V.abu != 0, false, false);
     }

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#define SOC_HPBG_PIX 49152         // pixels of the Healpix sky (NSIDE 64, fixed in the reference: ASOC.py:297)
 
 struct soc_ctx {
     int device = 0;
@@ -978,7 +979,7 @@ int soc_set_hpbg(soc_ctx *c, const float *BG, const float *HPBGP)
     if (!c) return SOC_ERR_ARG;
     // no flush: a deferred SimRAM_HP launch keeps its own copy of the sky (soc_sim_hp)
     if (!BG) return fail(c, SOC_ERR_ARG, "soc_set_hpbg: BG is NULL");
-    const int NPIX = 49152;                                 // NSIDE = 64, fixed in the reference (ASOC.py:297)
+    const int NPIX = SOC_HPBG_PIX;
     for (int i = 0; i < NPIX; i++)
         if (!std::isfinite(BG[i])) return fail(c, SOC_ERR_ARG, "soc_set_hpbg: BG[%d] is not finite", i);
     if (HPBGP) {
@@ -1118,6 +1119,17 @@ static int snapshot_inputs(soc_ctx *c, SocSim &S, const SocVariant &V, int slot)
     return SOC_OK;
 }
 
+// a deferred SimRAM_HP launch (absorption or scattered light) keeps its own copy of the sky: the caller sets the next frequency's
+static int snapshot_hpbg(soc_ctx *c, SocSim &S, int slot)
+{
+    if (!c->dHPslots) HIPCHK(c, dev_alloc(&c->dHPslots, (size_t)SOC_MAXLAUNCH * 2 * SOC_HPBG_PIX));
+    float *sky = c->dHPslots + (size_t)slot * 2 * SOC_HPBG_PIX;
+    HIPCHK(c, hipMemcpyAsync(sky, c->dHPBG, SOC_HPBG_PIX * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sky + SOC_HPBG_PIX, c->dHPBGP, SOC_HPBG_PIX * 4, hipMemcpyDeviceToDevice, c->stream));
+    S.HPBG = sky;  S.HPBGP = sky + SOC_HPBG_PIX;
+    return SOC_OK;
+}
+
 int soc_sim_hp(soc_ctx *c, int PACKETS, int BATCH, float SEED, float TW, int GLOBAL, int gid_first, int gid_count)
 {
     (void)PACKETS;
@@ -1131,15 +1143,7 @@ int soc_sim_hp(soc_ctx *c, int PACKETS, int BATCH, float SEED, float TW, int GLO
     fill_sim(c, S, V, 1, BATCH, SEED, 0.0f, TW, GLOBAL, gid_first, gid_count);
     S.NO_PS = 1;
     S.SOURCE = SOC_SOURCE_HP;          // the brick sweep as for soc_sim_pb: the walk is SimRAM_PB's, only the creation of a packet differs
-    return route_sim(c, SIM_HP, S, V, gid_count, [&](int slot) {      // a deferred launch keeps its own copy of the sky
-        if (slot < 0) return SOC_OK;
-        if (!c->dHPslots) HIPCHK(c, dev_alloc(&c->dHPslots, (size_t)SOC_MAXLAUNCH * 2 * 49152));
-        float *sky = c->dHPslots + (size_t)slot * 2 * 49152;
-        HIPCHK(c, hipMemcpyAsync(sky, c->dHPBG, 49152 * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(sky + 49152, c->dHPBGP, 49152 * 4, hipMemcpyDeviceToDevice, c->stream));
-        S.HPBG = sky;  S.HPBGP = sky + 49152;
-        return SOC_OK;
-    });
+    return route_sim(c, SIM_HP, S, V, gid_count, [&](int slot) { return slot < 0 ? SOC_OK : snapshot_hpbg(c, S, slot); });
 }
 
 // a deferred cell-emission launch keeps its own copy of the emission (and of the packet weights): the caller uploads the next frequency's
@@ -1293,18 +1297,25 @@ int soc_sca_zero(soc_ctx *c)
     return SOC_OK;
 }
 
-// Rays on brick-local hierarchies (soc_brick.hip: soc_sca_events) take flat images, scalar opacities and one scattering function
-static bool sca_rays_ok(const soc_ctx *c, int kind)
+// Rays on brick-local hierarchies (soc_brick.hip: soc_sca_events) take flat and Healpix images and every kind of launch (PB, PS, CL,
+// HP alike: the kind only changes the event lane), with scalar opacities and one scattering function.  What keeps the launches of the
+// current state off the sweep, or nullptr when they can run there.
+static const char *sca_rays_refusal(const soc_ctx *c)
 {
-    return c->have_view && c->view.NDIR > 0 && kind != SOC_SCA_HP && lt_capable(c, c->dOPT != nullptr) && c->msf_ndust <= 1 && c->device < 16;
+    if (!c->have_view || c->view.NDIR == 0) return "no view";
+    if (c->msf_ndust > 1) return "several scattering functions (WITH_MSF) need the direct kernel";
+    if (c->dOPT != nullptr) return "per-cell opacities need the direct kernel";
+    if (!lt_capable(c, false) || c->device >= 16) return "the hierarchy is not one the brick-local walk takes (2-8 levels, Index() in double)";
+    return nullptr;
 }
+static bool sca_rays_ok(const soc_ctx *c) { return sca_rays_refusal(c) == nullptr; }
 
 // Start of a soc_sca_sim_* call: inside soc_batch_begin/end a launch that can run as rays is deferred -- the slot its inputs are
 // kept in is returned -- and runs with the others of the batch in one sweep; otherwise (-1) what is pending runs first.
-static int sca_begin(soc_ctx *c, int kind, int *slot)
+static int sca_begin(soc_ctx *c, int *slot)
 {
     *slot = -1;
-    const bool defer = c->batching && c->exec_mode != 0 && sca_rays_ok(c, kind);
+    const bool defer = c->batching && c->exec_mode != 0 && sca_rays_ok(c);
     if (!defer || !c->pending_sca || (int)c->pending.size() >= c->batch_max) FLUSH(c);
     if (defer) *slot = (int)c->pending.size();
     return SOC_OK;
@@ -1322,9 +1333,9 @@ static int sca_launch(soc_ctx *c, const char *who, int kind, SocSim &S, SocVaria
     S.TABS = nullptr;  S.INT = nullptr;
     S.SCAKIND = kind + 1;  S.DSC = X.DSC;  S.OUT = X.OUT;
     c->last_passes = 0;  c->last_form = 0;
-    const bool rays_ok = sca_rays_ok(c, kind);
+    const bool rays_ok = sca_rays_ok(c);
     if (c->exec_mode == 1 && !rays_ok)
-        return fail(c, SOC_ERR_ARG, "%s: brick sweep requested but not applicable (needs a hierarchy walked in double, a flat image, scalar opacities, one scattering function)", who);
+        return fail(c, SOC_ERR_ARG, "%s: brick sweep requested but not applicable: %s", who, sca_rays_refusal(c));
     if (slot >= 0) {
         // deferred: the launch keeps its own copies of the scattering functions (and of the emission; the point sources are in their slot already)
         SocVariant W = V;
@@ -1342,6 +1353,10 @@ static int sca_launch(soc_ctx *c, const char *who, int kind, SocSim &S, SocVaria
             r = snapshot_emission(c, S, slot);
             if (r) return r;
             S.SOURCE = SOC_SOURCE_CL;
+        }
+        if (kind == SOC_SCA_HP) {
+            r = snapshot_hpbg(c, S, slot);
+            if (r) return r;
         }
         c->pending.push_back(S);
         c->pending_sca = true;
@@ -1368,7 +1383,7 @@ int soc_sca_sim_ps(soc_ctx *c, int PACKETS, int BATCH, float SEED, float BG, con
     (void)PACKETS;
     if (!c) return SOC_ERR_ARG;
     int slot = -1;
-    int r = sca_begin(c, SOC_SCA_PS, &slot);
+    int r = sca_begin(c, &slot);
     if (r) return r;
     r = check_launch(c, "soc_sca_sim_ps", BATCH, GLOBAL, gid_first, gid_count);
     if (r) return r;
@@ -1388,7 +1403,7 @@ int soc_sca_sim_pb(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, f
     (void)PACKETS;
     if (!c) return SOC_ERR_ARG;
     int slot = -1;
-    int r = sca_begin(c, SOC_SCA_PB, &slot);
+    int r = sca_begin(c, &slot);
     if (r) return r;
     r = check_launch(c, "soc_sca_sim_pb", BATCH, GLOBAL, gid_first, gid_count);
     if (r) return r;
@@ -1412,7 +1427,7 @@ int soc_sca_sim_cl(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, i
     (void)PACKETS;  (void)SOURCE;
     if (!c) return SOC_ERR_ARG;
     int slot = -1;
-    int r = sca_begin(c, SOC_SCA_CL, &slot);
+    int r = sca_begin(c, &slot);
     if (r) return r;
     r = check_launch(c, "soc_sca_sim_cl", BATCH, GLOBAL, gid_first, gid_count);
     if (r) return r;
@@ -1430,7 +1445,7 @@ int soc_sca_sim_hp(soc_ctx *c, int PACKETS, int BATCH, float SEED, int GLOBAL, i
     (void)PACKETS;
     if (!c) return SOC_ERR_ARG;
     int slot = -1;
-    int r = sca_begin(c, SOC_SCA_HP, &slot);
+    int r = sca_begin(c, &slot);
     if (r) return r;
     r = check_launch(c, "soc_sca_sim_hp", BATCH, GLOBAL, gid_first, gid_count);
     if (r) return r;

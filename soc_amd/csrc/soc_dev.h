@@ -203,6 +203,8 @@ static inline int soc_variant_code(int form, int kind, int wint, bool octree, bo
     return form | (kind << 2) | (wint << 5) | (octree ? 1 << 7 : 0) | (dbl ? 1 << 8 : 0) | (abu ? 1 << 9 : 0) | (ali ? 1 << 10 : 0)
            | (rays ? 1 << 11 : 0);
 }
+#define SOC_VAR_HEALPIX (1 << 12)   // sweeps of rays: the image was a Healpix map seen from a position
+#define SOC_VAR_HPSKY   (1 << 13)   // sweeps of rays: the sweep held a SimRAM_HP launch (the Healpix sky as the source)
 void soc_brick_release(int device);
 void soc_brick_invalidate(int device);      // the grid changed: bricks of a hierarchy are rebuilt at the next sweep
 

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Throughput of the scattered-light kernel (config 4) on its geometry: 256^3-root octree with 3 refinement levels,
-3 observers, 256^2 pixels, forced first scattering; background, point-source and cell-emission launches.
+3 observers, 256^2 pixels, forced first scattering; background, point-source and cell-emission launches, and launches of the
+Healpix sky as the source (SimRAM_HP, --kinds hp).  --healpix NSIDE X Y Z: one Healpix map seen from (X, Y, Z) [root cells] instead.
 
-    python tools/exp_sca.py [--n 256] [--batch 1] [--ndir 3]
+    python tools/exp_sca.py [--n 256] [--batch 1] [--ndir 3] [--healpix 64 128.3 127.7 126.9] [--kinds bg,ps,cl,hp]
 
 Prints one JSON line per launch kind: packets/s and the read-only roofline of SURVEY.md 8(d): 4 B (density) per cell
 step of a packet, of a look-ahead and of a peel-off ray (the kernel counts them)."""
@@ -30,6 +31,8 @@ def main():
     ap.add_argument("--ps-global", type=int, default=1048576)
     ap.add_argument("--tune", default="{}", help="soc_set_tuning settings as JSON")
     ap.add_argument("--launches", type=int, default=1, help="launches (seeds) per measurement, deferred into one batch: soc_batch_begin ... soc_batch_end, as soc_amd.asocs runs the frequencies of a source block")
+    ap.add_argument("--healpix", nargs=4, type=float, metavar=("NSIDE", "X", "Y", "Z"), help="a Healpix map of NSIDE seen from (X, Y, Z) in root-grid units instead of --ndir flat images")
+    ap.add_argument("--kinds", default="bg,ps,cl", help="launch kinds to time, of bg (SimRAM_PB background), ps (SimRAM_PS), cl (SimRAM_CL), hp (SimRAM_HP: the Healpix sky)")
     a = ap.parse_args()
     N = a.n
     cloud = synth.octree_cloud(N, levels=a.levels, frac=0.10, seed=1234) if a.levels > 1 else synth.cartesian_cloud(N, seed=1234)
@@ -46,16 +49,25 @@ def main():
     th = [math.radians(30 + 25 * i) for i in range(a.ndir)]
     ph = [math.radians(40 * i) for i in range(a.ndir)]
     _, OD, RA, DE = launch.set_observer_directions(th, ph)
-    eng.sca_set_view(OD, RA, DE, (256, 256), N / 256.0 * 1.5, (N / 2, N / 2, N / 2), 1)
+    if a.healpix:
+        eng.sca_set_healpix(int(a.healpix[0]), a.healpix[1:], 1)
+    else:
+        eng.sca_set_view(OD, RA, DE, (256, 256), N / 256.0 * 1.5, (N / 2, N / 2, N / 2), 1)
     AREA = 6 * N * N
     GLOBAL = launch.Fix(8 * AREA, 64)
     ps = np.array([[N / 2 + 0.3, N / 2 + 0.2, N / 2 + 0.1]], np.float32)
     emit = np.where(cloud.DENS > 0, cloud.DENS * 1e-3, 0).astype(np.float32)
     eng.set_emission(emit)
-    runs = (("SimRAM_PB background", lambda s: eng.sca_sim_pb(1, 8 * AREA * a.batch, a.batch, s, 1.0, GLOBAL=GLOBAL)),
-            ("SimRAM_PS point source", lambda s: eng.sca_sim_ps(a.ps_global * 8, 8, s, 0.0, ps, [1.0], GLOBAL=a.ps_global)),
-            ("SimRAM_CL cell emission", lambda s: eng.sca_sim_cl(2, cloud.CELLS, 1, s, a.cl_global)))
-    for name, fn in runs:
+    kinds = a.kinds.split(",")
+    if "hp" in kinds:
+        eng.set_hpbg(np.random.default_rng(8).lognormal(0, 1, 49152).astype(np.float32))   # a synthetic sky, uniform pixel choice
+    runs = (("bg", "SimRAM_PB background", lambda s: eng.sca_sim_pb(1, 8 * AREA * a.batch, a.batch, s, 1.0, GLOBAL=GLOBAL)),
+            ("ps", "SimRAM_PS point source", lambda s: eng.sca_sim_ps(a.ps_global * 8, 8, s, 0.0, ps, [1.0], GLOBAL=a.ps_global)),
+            ("cl", "SimRAM_CL cell emission", lambda s: eng.sca_sim_cl(2, cloud.CELLS, 1, s, a.cl_global)),
+            ("hp", "SimRAM_HP Healpix sky", lambda s: eng.sca_sim_hp(GLOBAL * a.batch, a.batch, s, GLOBAL)))
+    for key, name, fn in runs:
+        if key not in kinds:
+            continue
         best = None
         for rep in range(2):
             eng.sca_zero()
@@ -71,7 +83,7 @@ def main():
             ms = eng.timer_stop()
             st = eng.stats()
             st["ray_steps"] = eng.sca_ray_steps()
-            st["passes"], st["form"] = eng.last_passes(), eng.last_form()
+            st["passes"], st["form"], st["variant"] = eng.last_passes(), eng.last_form(), eng.last_variant()
             if best is None or ms < best[0]:
                 best = (ms, st)
         ms, st = best
@@ -81,7 +93,10 @@ def main():
             roof = {"ray_steps": st["ray_steps"], "steps_per_s": st["ray_steps"] / ms * 1e3, "passes": st["passes"],
                     "roofline": {"bound": "hbm", "achieved": 4.0 * st["ray_steps"] / ms * 1e-6, "peak": 8000.0, "unit": "GB/s",
                                  "frac": 4.0 * st["ray_steps"] / ms * 1e-6 / 8000.0}}
-        print(json.dumps({"kernel": "soc_lray_pass (rays on brick-local hierarchies)" if rays else "soc_sca_kernel", **roof, "launch": name, "launches_in_the_batch": a.launches, "cells": cloud.CELLS, "ndir": a.ndir, "kernel_ms": ms,
+        view = ("healpix NSIDE %d from (%g, %g, %g)" % (int(a.healpix[0]), *a.healpix[1:])) if a.healpix else "%d flat images" % a.ndir
+        ndir = -int(a.healpix[0]) if a.healpix else a.ndir                       # (NDIR as the kernels see it: -NSIDE for a Healpix map)
+        print(json.dumps({"kernel": "soc_lray_pass (rays on brick-local hierarchies)" if rays else "soc_sca_kernel", **roof, "launch": name, "launches_in_the_batch": a.launches, "cells": cloud.CELLS, "ndir": ndir, "view": view, "kernel_ms": ms,
+                          "variant": st["variant"],
                           "packets": st["packets"], "packets_per_s": st["packets"] / ms * 1e3,
                           "image_contributions": st["tally_events"], "scatterings": st["scatterings"]}), flush=True)
     eng.close()
