@@ -1951,9 +1951,7 @@ __global__ __launch_bounds__(SOC_BRICK_T) void soc_brick_scatter(SocBrickArgs A,
 // ---------------------------------------------------------------------------------------
 
 struct SocBrickBuffers {
-    size_t cap_items = 0;
-    int    cap_nq = 0, cap_desc = 0;
-    size_t cap_park = 0;
+    size_t cap_items = 0, cap_nq = 0, cap_desc = 0, cap_park = 0;
     SocPk2 *pk = nullptr, *park = nullptr;
     uint32_t *idq[2] = { nullptr, nullptr }, *keyq = nullptr, *posq = nullptr;
     SocSimPack *pack = nullptr;
@@ -1974,6 +1972,17 @@ static hipError_t brick_alloc(T **p, size_t n)
 {
     if (*p) { (void)hipFree(*p);  *p = nullptr; }
     return hipMalloc((void **)p, (n ? n : 1) * sizeof(T));
+}
+
+// The buffers of a sweep only grow: below n elements they are replaced -- once the stream is done with the old ones -- and cap is n.
+template <typename... T>
+static hipError_t grow(size_t &cap, size_t n, hipStream_t st, T **...p)
+{
+    if (cap >= n) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(st);
+    ((e = (e == hipSuccess) ? brick_alloc(p, n) : e), ...);
+    if (e == hipSuccess) cap = n;
+    return e;
 }
 
 static void soc_oct_release(int device);
@@ -2113,204 +2122,172 @@ static hipError_t soc_lb_build(int device, const SocGrid &G, int cap, hipStream_
     return hipSuccess;
 }
 
-template <int WINT, int KIND>
-static void soc_lbrick_launch_one(int nblocks, int T, size_t lds, hipStream_t st, const SocGrid &G, const SocSimPack *K,
-                                  const SocBrickArgs &A, int nwalk, int slices)
+// ---------------------------------------------------------------------------------------
+// One sweep (soc_brick_run_pb), in steps: the scattered-light launches checked; the plan; the bricks of the planned form; the
+// launches packed; the rest of the plan (KIND, LDS); the buffers; the passes.
+// ---------------------------------------------------------------------------------------
+
+// The pass kernels, indexed by the plan: a sweep runs one of them
+typedef void (*SocPassFn)(const SocGrid, const SocSimPack *, const SocBrickArgs, const int, const int);
+// Cartesian grids and hierarchies in global memory: [Cartesian | hierarchy | hierarchy with Index() in double][per-cell opacities][INT tally][KIND 0-3]
+static const SocPassFn soc_brick_pass_fns[3][2][2][4] = {
+    { { { soc_brick_pass<0, 0, 0, 0, 0>, soc_brick_pass<0, 0, 0, 0, 1>, soc_brick_pass<0, 0, 0, 0, 2>, soc_brick_pass<0, 0, 0, 0, 3> },
+        { soc_brick_pass<0, 0, 0, 1, 0>, soc_brick_pass<0, 0, 0, 1, 1>, soc_brick_pass<0, 0, 0, 1, 2>, soc_brick_pass<0, 0, 0, 1, 3> } },
+      { { soc_brick_pass<0, 0, 1, 0, 0>, soc_brick_pass<0, 0, 1, 0, 1>, soc_brick_pass<0, 0, 1, 0, 2>, soc_brick_pass<0, 0, 1, 0, 3> },
+        { soc_brick_pass<0, 0, 1, 1, 0>, soc_brick_pass<0, 0, 1, 1, 1>, soc_brick_pass<0, 0, 1, 1, 2>, soc_brick_pass<0, 0, 1, 1, 3> } } },
+    { { { soc_brick_pass<1, 0, 0, 0, 0>, soc_brick_pass<1, 0, 0, 0, 1>, soc_brick_pass<1, 0, 0, 0, 2>, soc_brick_pass<1, 0, 0, 0, 3> },
+        { soc_brick_pass<1, 0, 0, 1, 0>, soc_brick_pass<1, 0, 0, 1, 1>, soc_brick_pass<1, 0, 0, 1, 2>, soc_brick_pass<1, 0, 0, 1, 3> } },
+      { { soc_brick_pass<1, 0, 1, 0, 0>, soc_brick_pass<1, 0, 1, 0, 1>, soc_brick_pass<1, 0, 1, 0, 2>, soc_brick_pass<1, 0, 1, 0, 3> },
+        { soc_brick_pass<1, 0, 1, 1, 0>, soc_brick_pass<1, 0, 1, 1, 1>, soc_brick_pass<1, 0, 1, 1, 2>, soc_brick_pass<1, 0, 1, 1, 3> } } },
+    { { { soc_brick_pass<1, 1, 0, 0, 0>, soc_brick_pass<1, 1, 0, 0, 1>, soc_brick_pass<1, 1, 0, 0, 2>, soc_brick_pass<1, 1, 0, 0, 3> },
+        { soc_brick_pass<1, 1, 0, 1, 0>, soc_brick_pass<1, 1, 0, 1, 1>, soc_brick_pass<1, 1, 0, 1, 2>, soc_brick_pass<1, 1, 0, 1, 3> } },
+      { { soc_brick_pass<1, 1, 1, 0, 0>, soc_brick_pass<1, 1, 1, 0, 1>, soc_brick_pass<1, 1, 1, 0, 2>, soc_brick_pass<1, 1, 1, 0, 3> },
+        { soc_brick_pass<1, 1, 1, 1, 0>, soc_brick_pass<1, 1, 1, 1, 1>, soc_brick_pass<1, 1, 1, 1, 2>, soc_brick_pass<1, 1, 1, 1, 3> } } } };
+// brick-local hierarchies: [WINT 0-3][KIND 0-4]; with the XAB tally (ALI, KIND 2): [WINT 0-1]
+static const SocPassFn soc_lbrick_pass_fns[4][5] = {
+    { soc_lbrick_pass<0, 0>, soc_lbrick_pass<0, 1>, soc_lbrick_pass<0, 2>, soc_lbrick_pass<0, 3>, soc_lbrick_pass<0, 4> },
+    { soc_lbrick_pass<1, 0>, soc_lbrick_pass<1, 1>, soc_lbrick_pass<1, 2>, soc_lbrick_pass<1, 3>, soc_lbrick_pass<1, 4> },
+    { soc_lbrick_pass<2, 0>, soc_lbrick_pass<2, 1>, soc_lbrick_pass<2, 2>, soc_lbrick_pass<2, 3>, soc_lbrick_pass<2, 4> },
+    { soc_lbrick_pass<3, 0>, soc_lbrick_pass<3, 1>, soc_lbrick_pass<3, 2>, soc_lbrick_pass<3, 3>, soc_lbrick_pass<3, 4> } };
+static const SocPassFn soc_lbrick_pass_ali_fns[2] = { soc_lbrick_pass_ali<0>, soc_lbrick_pass_ali<1> };
+// rays: [Healpix image seen from a position][SimRAM_HP launches]
+static const SocPassFn soc_lray_pass_fns[2][2] = { { soc_lray_pass<0, 0>, soc_lray_pass<0, 1> }, { soc_lray_pass<1, 0>, soc_lray_pass<1, 1> } };
+
+static SocPassFn pass_kernel(const SocSweepPlan &pl)
 {
-    if (lds > 64 * 1024)                           // more dynamic LDS than the default limit (per device and kernel; cheap)
-        (void)hipFuncSetAttribute((const void *)soc_lbrick_pass<WINT, KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    soc_lbrick_pass<WINT, KIND><<<nblocks, T, lds, st>>>(G, K, A, nwalk, slices);
+    if (pl.rays)      return soc_lray_pass_fns[pl.hpx][pl.hpsky];
+    if (pl.form == 3) return pl.ali ? soc_lbrick_pass_ali_fns[pl.wint] : soc_lbrick_pass_fns[pl.wint][pl.kind];
+    return soc_brick_pass_fns[pl.octree + pl.dbl][pl.abu][pl.wint][pl.kind];
 }
 
-static void soc_lbrick_launch_pass(int wint, int kind, int nblocks, int T, size_t lds, hipStream_t st, const SocGrid &G, const SocSimPack *K,
-                                   const SocBrickArgs &A, int nwalk, int slices)
+// Step 1: rays of the scattered-light kernels (soc_sca_events) take flat or Healpix images of SimRAM_PB / PS / CL / HP with scalar
+// opacities and one scattering function
+static hipError_t check_sca(const SocSim *S, int nlaunch, const SocVariant &V, const SocSca *sca)
 {
-    if (A.ali) {                                             // SimRAM_CL with the XAB tally (soc_brick_run_pb has checked kind and wint)
-#define SOC_LBA_CASE(W) do { if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)soc_lbrick_pass_ali<W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                             soc_lbrick_pass_ali<W><<<nblocks, T, lds, st>>>(G, K, A, nwalk, slices); } while (0)
-        if (wint) SOC_LBA_CASE(1); else SOC_LBA_CASE(0);
-#undef SOC_LBA_CASE
-        return;
+    if (!sca) return hipSuccess;
+    if (sca->NDIR == 0 || V.abu || V.wint) return hipErrorNotSupported;
+    for (int l = 0; l < nlaunch; l++) {
+        const int k = S[l].SCAKIND - 1;
+        if ((k != SOC_SCA_PB && k != SOC_SCA_PS && k != SOC_SCA_CL && k != SOC_SCA_HP) || S[l].NDUST > 1 || S[l].BINS < 1 || !S[l].OUT) return hipErrorNotSupported;
+        if ((k == SOC_SCA_PB || k == SOC_SCA_PS) && !S[l].DSC) return hipErrorNotSupported;
+        if ((k == SOC_SCA_HP) && (!S[l].HPBG || (S[l].HPBG_WEIGHTED && !S[l].HPBGP))) return hipErrorNotSupported;
+        if ((k == SOC_SCA_CL) != (S[l].SOURCE == SOC_SOURCE_CL)) return hipErrorInvalidValue;
     }
-#define SOC_LB_CASE(W, KD) soc_lbrick_launch_one<W, KD>(nblocks, T, lds, st, G, K, A, nwalk, slices)
-    if (wint == 3) { if (kind == 4) SOC_LB_CASE(3, 4);  else if (kind == 3) SOC_LB_CASE(3, 3);  else if (kind == 2) SOC_LB_CASE(3, 2);  else if (kind == 1) SOC_LB_CASE(3, 1);  else SOC_LB_CASE(3, 0); }
-    else if (wint == 2) { if (kind == 4) SOC_LB_CASE(2, 4);  else if (kind == 3) SOC_LB_CASE(2, 3);  else if (kind == 2) SOC_LB_CASE(2, 2);  else if (kind == 1) SOC_LB_CASE(2, 1);  else SOC_LB_CASE(2, 0); }
-    else if (wint) { if (kind == 4) SOC_LB_CASE(1, 4);  else if (kind == 3) SOC_LB_CASE(1, 3);  else if (kind == 2) SOC_LB_CASE(1, 2);  else if (kind == 1) SOC_LB_CASE(1, 1);  else SOC_LB_CASE(1, 0); }
-    else      { if (kind == 4) SOC_LB_CASE(false, 4); else if (kind == 3) SOC_LB_CASE(false, 3); else if (kind == 2) SOC_LB_CASE(false, 2); else if (kind == 1) SOC_LB_CASE(false, 1); else SOC_LB_CASE(false, 0); }
-#undef SOC_LB_CASE
-}
-
-template <bool HPX, bool HPSKY>
-static void soc_lray_launch_one(int nblocks, int T, size_t lds, hipStream_t st, const SocGrid &G, const SocSimPack *K,
-                                const SocBrickArgs &A, int nwalk, int slices)
-{
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)soc_lray_pass<HPX, HPSKY>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    soc_lray_pass<HPX, HPSKY><<<nblocks, T, lds, st>>>(G, K, A, nwalk, slices);
-}
-
-static hipError_t soc_lray_launch_pass(bool hpsky, int nblocks, int T, size_t lds, hipStream_t st, const SocGrid &G, const SocSimPack *K,
-                                       const SocBrickArgs &A, int nwalk, int slices)
-{
-    if (A.sca.NDIR < 0) { if (hpsky) soc_lray_launch_one<true, true>(nblocks, T, lds, st, G, K, A, nwalk, slices);  else soc_lray_launch_one<true, false>(nblocks, T, lds, st, G, K, A, nwalk, slices); }
-    else                { if (hpsky) soc_lray_launch_one<false, true>(nblocks, T, lds, st, G, K, A, nwalk, slices); else soc_lray_launch_one<false, false>(nblocks, T, lds, st, G, K, A, nwalk, slices); }
     return hipSuccess;
 }
 
-// LB: log2 of the brick edge (Cartesian grids; hierarchies use bricks of <= CAP leaves).  nlaunch launches
-// (same geometry, same tallies; no INT tally when nlaunch > 1) share one sweep: more
-// packets in flight per pass, and the passes in which one launch's last work items finish are filled by the
-// others.  Returns hipErrorNotSupported when the launches cannot use bricks.
-template <bool OCT, bool DBL, bool ABU, bool WINT, int KIND>
-static void soc_brick_launch_one(int nblocks, int T, size_t lds, hipStream_t st, const SocGrid &G, const SocSimPack *K,
-                                 const SocBrickArgs &A, int nwalk, int slices)
+// Step 2: the form of the sweep, WINT, ALI, the image of the rays, the cells per brick and the tuning, from the inputs alone.
+// lb_ok: false once soc_lb_build has found that the hierarchy cannot be cut into brick-local ones.
+static hipError_t plan_sweep(SocSweepPlan &pl, const SocGrid &G, const SocSim *S, int nlaunch, const SocVariant &V,
+                             const SocBrickTune &tune, const SocSca *sca, bool lb_ok)
 {
-    if (lds > 64 * 1024)                           // more dynamic LDS than the default limit; the attribute is per device, so it is set
-        (void)hipFuncSetAttribute((const void *)soc_brick_pass<OCT, DBL, ABU, WINT, KIND>,     // on every launch (microseconds)
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    soc_brick_pass<OCT, DBL, ABU, WINT, KIND><<<nblocks, T, lds, st>>>(G, K, A, nwalk, slices);
-}
-
-// vkey: bit 0 INT tally, bit 1 per-cell opacities; kind 0 SimRAM_PB, 1 SimRAM_HP, 2 SimRAM_CL, 3 SimRAM_PB with
-// background packets only (they differ in how the
-// event workgroups create a packet; separate kernels so that none carries the registers of the others)
-template <bool OCT, bool DBL, int KIND>
-static void soc_brick_launch_kind(int vkey, int nblocks, int T, size_t lds, hipStream_t st, const SocGrid &G, const SocSimPack *K,
-                                  const SocBrickArgs &A, int nwalk, int slices)
-{
-    switch (vkey) {
-    case 0:  soc_brick_launch_one<OCT, DBL, false, false, KIND>(nblocks, T, lds, st, G, K, A, nwalk, slices); break;
-    case 1:  soc_brick_launch_one<OCT, DBL, false, true, KIND>(nblocks, T, lds, st, G, K, A, nwalk, slices); break;
-    case 2:  soc_brick_launch_one<OCT, DBL, true, false, KIND>(nblocks, T, lds, st, G, K, A, nwalk, slices); break;
-    default: soc_brick_launch_one<OCT, DBL, true, true, KIND>(nblocks, T, lds, st, G, K, A, nwalk, slices); break;
+    const bool lt = lb_ok && soc_brick_local(G, V, tune);
+    pl = soc_grid_plan(lt ? 3 : V.octree ? 2 : 1, 0, V);
+    pl.rays = sca != nullptr;
+    pl.hpx = sca && sca->NDIR < 0;
+    for (int l = 0; l < nlaunch && sca; l++) pl.hpsky = pl.hpsky || (S[l].SCAKIND == SOC_SCA_HP + 1);
+    // workgroup shape; soc_set_tuning overrides (measured on C2 and on the 256^3-root hierarchy, see DESIGN.md)
+    const auto pick = [](int t, int d) { return (t > 0) ? t : d; };
+    pl.T = pick(tune.T, 512);
+    if (lt) {
+        pl.P = pick(tune.P, 16384);
+        pl.KCAP = pick(tune.KCAP, 64);
+        pl.FTH = pick(tune.FTH, 16);
+        pl.CTH = pick(tune.CTH, 8);
+        // the tail of a long chunk: 32 of 64 lanes out of work (measured: 24 ... 32 +2 %, 48 +1 %, 56 0; 65 = never)
+        pl.TAIL = pick(tune.TAIL, 32);
+        // short brick queues wait (soc_brick_scan): 4096 = 8 packets per lane, measured on config 3 (1024 ... 16384; +5 % point source,
+        // +9 % diffuse emission against no parking); soc_set_tuning("park_below", 1) = never
+        pl.PARK = pick(tune.park, 4096);
+        pl.slow_every = tune.slow_every;
+    } else {
+        pl.P = pick(tune.P, V.octree ? 4096 : 2048);             // 8 | 4 x the default T, also with another T; hierarchies: one chunk per brick queue (measured)
+        pl.KCAP = pick(tune.KCAP, V.octree ? 32 : 48);           // measured on C2 / on the 256^3-root hierarchy
+        pl.FTH = pick(tune.FTH, V.octree ? 16 : 24);
+        pl.CTH = pick(tune.CTH, pl.FTH);
+        pl.TAIL = pick(tune.TAIL, 0);
+        pl.CAP = pick(tune.CAP, 6144);                           // with P = 4096: 48 KB of LDS, three workgroups per CU (measured)
     }
-}
-
-template <bool OCT, bool DBL>
-static void soc_brick_launch_pass(int vkey, int kind, int nblocks, int T, size_t lds, hipStream_t st, const SocGrid &G, const SocSimPack *K,
-                                  const SocBrickArgs &A, int nwalk, int slices)
-{
-    if (kind == 3)      soc_brick_launch_kind<OCT, DBL, 3>(vkey, nblocks, T, lds, st, G, K, A, nwalk, slices);
-    else if (kind == 2) soc_brick_launch_kind<OCT, DBL, 2>(vkey, nblocks, T, lds, st, G, K, A, nwalk, slices);
-    else if (kind == 1) soc_brick_launch_kind<OCT, DBL, 1>(vkey, nblocks, T, lds, st, G, K, A, nwalk, slices);
-    else                soc_brick_launch_kind<OCT, DBL, 0>(vkey, nblocks, T, lds, st, G, K, A, nwalk, slices);
-}
-
-hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int nlaunch, const SocVariant &V, int LB,
-                            int population, const SocBrickTune &tune, hipStream_t st, int *passes_out, int *form_out, int *variant_out,
-                            const SocSca *sca)
-{
-    if (form_out) *form_out = 0;
-    // rays of the scattered-light kernels (soc_sca_events): flat or Healpix images of SimRAM_PB / PS / CL / HP with scalar opacities and one
-    // scattering function
-    bool sca_hp = false;
-    if (sca) {
-        if (sca->NDIR == 0 || V.abu || V.wint) return hipErrorNotSupported;
-        for (int l = 0; l < nlaunch; l++) {
-            const int k = Sin[l].SCAKIND - 1;
-            if ((k != SOC_SCA_PB && k != SOC_SCA_PS && k != SOC_SCA_CL && k != SOC_SCA_HP) || Sin[l].NDUST > 1 || Sin[l].BINS < 1 || !Sin[l].OUT) return hipErrorNotSupported;
-            if ((k == SOC_SCA_PB || k == SOC_SCA_PS) && !Sin[l].DSC) return hipErrorNotSupported;
-            if ((k == SOC_SCA_HP) && (!Sin[l].HPBG || (Sin[l].HPBG_WEIGHTED && !Sin[l].HPBGP))) return hipErrorNotSupported;
-            sca_hp = sca_hp || (k == SOC_SCA_HP);
-            if ((k == SOC_SCA_CL) != (Sin[l].SOURCE == SOC_SOURCE_CL)) return hipErrorInvalidValue;
-        }
+    if (pl.T < 64 || pl.T > 1024 || (pl.T & 63) || pl.P < 1 || pl.P > SOC_LBRICK_PMAX || pl.KCAP < 1) return hipErrorInvalidValue;
+    pl.EQ = 2;
+    if (!lt) {
+        if (sca || V.wint == 2) return hipErrorNotSupported;
+        for (int l = 0; l < nlaunch; l++) if (S[l].ROISAVE) return hipErrorNotSupported;      // region-of-interest records: brick-local hierarchies only
+        if (pl.T > 512 || pl.P > SOC_BRICK_PMAX || pl.CAP < 8 || pl.CAP > (1 << SOC_SLOT_BITS)) return hipErrorInvalidValue;
+        return hipSuccess;
     }
-    if (device < 0 || device >= 16 || nlaunch < 1 || nlaunch > SOC_MAXLAUNCH) return hipErrorNotSupported;
-    const int B = 1 << LB;
-    SocBrickArgs A{};
+    // INT tally with one weight per group of launches (an absorbed-file sweep: the source blocks of ONE frequency): the INT-only form
+    bool int_only = !sca && (V.wint == 1);
+    for (int l = 0; l < nlaunch && int_only; l++)
+        for (int m = 0; m < l; m++) if (S[m].INT == S[l].INT && S[m].TW != S[l].TW) { int_only = false;  break; }
+    // WITH_ALI: every launch a SimRAM_CL one with the XAB tally
+    bool ali = !sca && (V.wint != 2);
+    for (int l = 0; l < nlaunch; l++) ali = ali && (S[l].SOURCE == SOC_SOURCE_CL) && (S[l].XAB != nullptr) && (S[l].XAB == S[0].XAB);
+    if (ali) int_only = false;
+    pl.wint = int_only ? 3 : V.wint;
+    pl.ali = ali;
+    // cells per brick: what lets two workgroups share a CU's 160 KB of LDS (8 B per cell, 12 B with the INT tally, + 9 KB)
+    // (rays: 4 B per cell, twice the cells in the same LDS)
+    // (the vector sums of SAVE_INTENSITY 2: 24 B per cell)
+    // (ALI: 8 B per cell more for XAB and the cell numbers)
+    pl.capl = (tune.CAP > 0) ? tune.CAP : (sca ? 17408 : (ali ? (V.wint ? 3456 : 4352) : (V.wint == 2 ? 2944 : (V.wint && !int_only) ? 5888 : 8704)));
+    if (pl.capl < 8 || pl.capl > 36864) return hipErrorInvalidValue;
+    pl.EQ = 3;
+    for (int l = 0; l < nlaunch; l++) pl.roi = pl.roi || (S[l].ROISAVE && S[l].ROI);
+    if (pl.roi) {
+        for (int l = 0; l < nlaunch; l++) if (!(S[l].ROISAVE && S[l].ROI) || S[l].MIRROR) return hipErrorNotSupported;      // one record, no reflecting faces
+        pl.EQ = 4;                                                       // + the queue of packets that have just stepped into ROI
+    }
+    return hipSuccess;
+}
+
+// Step 3: the bricks of the planned form and the sweep's arguments for them.  hipErrorNotSupported from the brick-local form: the
+// hierarchy cannot be cut that way (soc_lb_build).
+static hipError_t build_bricks(SocBrickArgs &A, const SocSweepPlan &pl, int device, const SocGrid &G, int LB, hipStream_t st, bool verbose)
+{
+    A = SocBrickArgs{};
     A.LB = LB;
     A.ev_brick = -1;
-    // workgroup shape; soc_set_tuning overrides (measured on C2 and on the 256^3-root hierarchy, see DESIGN.md)
-    A.T = 512;
-    A.P = (V.octree ? 8 : 4) * A.T;                  // hierarchies: one chunk per brick queue (measured)
-    A.KCAP = V.octree ? 32 : 48;                     // measured on C2 / on the 256^3-root hierarchy
-    A.FTH = V.octree ? 16 : 24;
-    A.CAP = 6144;                                    // with P = 4096: 48 KB of LDS, three workgroups per CU (measured)
-    A.TAIL = 0;
-    if (tune.TAIL > 0) A.TAIL = tune.TAIL;
-    if (tune.T > 0)    A.T = tune.T;
-    if (tune.P > 0)    A.P = tune.P;
-    if (tune.KCAP > 0) A.KCAP = tune.KCAP;
-    if (tune.FTH > 0)  A.FTH = tune.FTH;
-    A.CTH = A.FTH;
-    if (tune.CTH > 0)  A.CTH = tune.CTH;
-    if (tune.CAP > 0)  A.CAP = tune.CAP;
-    if (A.T < 64 || A.T > 1024 || (A.T & 63) || A.P < 1 || A.P > SOC_LBRICK_PMAX || A.KCAP < 1) return hipErrorInvalidValue;
-    A.EQ = 2;
-    // hierarchies whose Index() is evaluated in double: the walk on brick-local hierarchies (soc_ltree.h), unless the
-    // grid does not allow it (per-cell opacities, more than 8 levels, coordinates beyond 24 bits, a root cell whose
-    // subtree exceeds the brick) or soc_set_tuning("global_tree", 1) asks for the older form
-    if (V.octree && V.dbl && !V.abu && !tune.global_tree && G.LEVELS <= 8
-        && ((long long)std::max(G.NX, std::max(G.NY, G.NZ)) << (G.LEVELS - 1)) < (1LL << 24)
-        && std::max(G.NX, std::max(G.NY, G.NZ)) < 4096) {        // (root-cell numbers from 24-bit multiplies: SOC_MAD24)
-        // cells per brick: what lets two workgroups share a CU's 160 KB of LDS (8 B per cell, 12 B with the INT tally, + 9 KB)
-        // (rays: 4 B per cell, twice the cells in the same LDS)
-        // (the vector sums of SAVE_INTENSITY 2: 24 B per cell)
-        // WITH_ALI (every launch a SimRAM_CL one with the XAB tally): 8 B per cell more for XAB and the cell numbers
-        // INT tally with one weight per group of launches (an absorbed-file sweep: the source blocks of ONE frequency): the INT-only form
-        bool int_only = !sca && (V.wint == 1);
-        for (int l = 0; l < nlaunch && int_only; l++)
-            for (int m = 0; m < l; m++) if (Sin[m].INT == Sin[l].INT && Sin[m].TW != Sin[l].TW) { int_only = false;  break; }
-        bool ali = !sca && (V.wint != 2);
-        for (int l = 0; l < nlaunch; l++) ali = ali && (Sin[l].SOURCE == SOC_SOURCE_CL) && (Sin[l].XAB != nullptr) && (Sin[l].XAB == Sin[0].XAB);
-        if (ali) int_only = false;
-        const int capl = (tune.CAP > 0) ? tune.CAP : (sca ? 17408 : (ali ? (V.wint ? 3456 : 4352) : (V.wint == 2 ? 2944 : (V.wint && !int_only) ? 5888 : 8704)));
-        if (capl < 8 || capl > 36864) return hipErrorInvalidValue;
-        const hipError_t e = soc_lb_build(device, G, capl, st, tune.verbose != 0);
-        if (e == hipSuccess) {
-            const SocLBricksDev &lb = g_lb[device];
-            A.LT = 1;  A.EQ = 3;
-            A.ali = ali ? 1 : 0;
-            A.int_only = int_only ? 1 : 0;
-            for (int l = 0; l < nlaunch; l++) if (Sin[l].ROISAVE && Sin[l].ROI) A.roi_on = 1;
-            if (A.roi_on) {
-                for (int l = 0; l < nlaunch; l++) if (!(Sin[l].ROISAVE && Sin[l].ROI) || Sin[l].MIRROR) return hipErrorNotSupported;      // one record, no reflecting faces
-                A.EQ = 4;                                                    // + the queue of packets that have just stepped into ROI
-            }
-            A.NBX = A.NBY = A.NBZ = 0;
-            A.NB = lb.NB;
-            A.CAP = (lb.max_slots + 63) & ~63;                           // slots in LDS
-            A.lbr = lb.lbr;  A.btree = lb.btree;  A.bcell = lb.bcell;  A.bbase = lb.bbase;  A.rbrick = lb.rbrick;
-            int k = 1;
-            while ((1 << k) <= std::max(G.NX, std::max(G.NY, G.NZ))) k++;
-            A.sib_thr = ldexpf(1.0f, k - 29);
-            A.kexp = k - 30;
-            A.slow_every = tune.slow_every;
-            A.P = (tune.P > 0) ? tune.P : 16384;
-            A.KCAP = (tune.KCAP > 0) ? tune.KCAP : 64;
-            A.FTH = (tune.FTH > 0) ? tune.FTH : 16;
-            A.CTH = (tune.CTH > 0) ? tune.CTH : 8;
-            // the tail of a long chunk: 32 of 64 lanes out of work (measured: 24 ... 32 +2 %, 48 +1 %, 56 0; 65 = never)
-            A.TAIL = (tune.TAIL > 0) ? tune.TAIL : 32;
-            // short brick queues wait (soc_brick_scan): 4096 = 8 packets per lane, measured on config 3 (1024 ... 16384; +5 % point source,
-            // +9 % diffuse emission against no parking); soc_set_tuning("park_below", 1) = never
-            A.PARK = (tune.park > 0) ? tune.park : 4096;
-        } else if (e != hipErrorNotSupported) {
-            return e;
-        }
-    }
-    if ((sca || V.wint == 2) && !A.LT) return hipErrorNotSupported;
-    if (!A.LT) for (int l = 0; l < nlaunch; l++) if (Sin[l].ROISAVE) return hipErrorNotSupported;      // region-of-interest records: brick-local hierarchies only
-    if (!A.LT && (A.T > 512 || A.P > SOC_BRICK_PMAX || A.CAP < 8 || A.CAP > (1 << SOC_SLOT_BITS))) return hipErrorInvalidValue;
-    if (A.LT) {
-        // set above
-    } else
-    if (V.octree) {
-        if (G.LEVELS > 15) return hipErrorNotSupported;                  // the level shares a packet word with slot and launch
-        BCHK(soc_oct_build(device, G, A.CAP, st, tune.verbose != 0));
-        const SocOctBricks &ob = g_ob[device];
-        A.NBX = A.NBY = A.NBZ = 0;
-        A.NB = ob.NB;
-        A.DS = ob.DS;  A.bcell = ob.bcell;  A.bbase = ob.bbase;
-        int k = 1;
-        while ((1 << k) <= std::max(G.NX, std::max(G.NY, G.NZ))) k++;
-        A.sib_thr = ldexpf(1.0f, k - 29);
-    } else {
+    A.T = pl.T;  A.P = pl.P;  A.KCAP = pl.KCAP;  A.FTH = pl.FTH;  A.CTH = pl.CTH;  A.CAP = pl.CAP;  A.TAIL = pl.TAIL;  A.PARK = pl.PARK;
+    A.EQ = pl.EQ;  A.slow_every = pl.slow_every;
+    A.LT = (pl.form == 3);  A.int_only = (pl.wint == 3);  A.ali = pl.ali;  A.roi_on = pl.roi;
+    if (pl.form == 1) {
+        const int B = 1 << LB;
         A.NBX = (G.NX + B - 1) / B;  A.NBY = (G.NY + B - 1) / B;  A.NBZ = (G.NZ + B - 1) / B;
         A.NB = A.NBX * A.NBY * A.NBZ;
-        if (A.NB > (1 << 18)) return hipErrorNotSupported;
+        return (A.NB > (1 << 18)) ? hipErrorNotSupported : hipSuccess;
     }
+    int k = 1;                                                           // 2^k > max(NX, NY, NZ)
+    while ((1 << k) <= std::max(G.NX, std::max(G.NY, G.NZ))) k++;
+    A.sib_thr = ldexpf(1.0f, k - 29);
+    A.kexp = k - 30;
+    if (pl.form == 3) {
+        BCHK(soc_lb_build(device, G, pl.capl, st, verbose));
+        const SocLBricksDev &lb = g_lb[device];
+        A.NB = lb.NB;
+        A.CAP = (lb.max_slots + 63) & ~63;                               // slots in LDS
+        A.lbr = lb.lbr;  A.btree = lb.btree;  A.bcell = lb.bcell;  A.bbase = lb.bbase;  A.rbrick = lb.rbrick;
+        return hipSuccess;
+    }
+    if (G.LEVELS > 15) return hipErrorNotSupported;                      // the level shares a packet word with slot and launch
+    BCHK(soc_oct_build(device, G, A.CAP, st, verbose));
+    const SocOctBricks &ob = g_ob[device];
+    A.NB = ob.NB;
+    A.DS = ob.DS;  A.bcell = ob.bcell;  A.bbase = ob.bbase;
+    return hipSuccess;
+}
 
-    SocSimPack K{};
+struct SocSweepSize {
+    uint32_t count;            // work items of the packed launches
+    int NQ;                    // queues: the brick queues, the event queues of every launch, one for finished work items
+    int maxdesc;               // workgroup descriptors of a pass, at most
+};
+
+// Step 4: the launches with work items into one SocSimPack, each one's range clipped to the work items that do something; the
+// launches that tally into one INT array form a group with brick queues of its own
+static hipError_t pack_launches(SocSimPack &K, SocSweepSize &sz, SocBrickArgs &A, const SocSweepPlan &pl, const SocGrid &G,
+                                const SocSim *Sin, int nlaunch, const SocBrickTune &tune)
+{
     uint32_t count = 0;
     for (int l = 0; l < nlaunch; l++) {
         const SocSim &S = Sin[l];
@@ -2331,7 +2308,7 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int
             if ((long long)S.gid0 >= G.CELLS) c = 0;
             else if ((long long)S.gid0 + c > G.CELLS) c = (uint32_t)(G.CELLS - S.gid0);
             if (S.USE_EMWEIGHT == 2) return hipErrorNotSupported;
-            if (S.XAB && !A.ali) return hipErrorNotSupported;
+            if (S.XAB && !pl.ali) return hipErrorNotSupported;
         }
         if (S.BATCH <= 0 && S.SOURCE != SOC_SOURCE_CL) c = 0;
         if (c == 0) continue;                                         // nothing to do for this launch
@@ -2342,16 +2319,14 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int
         count += c;
         K.n++;
     }
-    if (K.n == 0) { if (passes_out) *passes_out = 0;  return hipSuccess; }
     for (int l = K.n; l <= SOC_MAXLAUNCH; l++) K.first[l] = count;
     // several launches with per-cell opacities: their OPT arrays are slots of one buffer (soc_capi.hip)
-    A.opt_stride = 0;
-    if (V.abu && K.n > 1) {
+    if (pl.abu && K.n > 1) {
         A.opt_stride = (long long)(K.S[1].OPT - K.S[0].OPT);
         for (int l = 1; l < K.n; l++)
             if ((long long)(K.S[l].OPT - K.S[0].OPT) != l * A.opt_stride) return hipErrorInvalidValue;
     }
-    // launches with the INT tally: brick queues per launch, so that a workgroup's LDS tallies belong to one launch
+    // launches with the INT tally: brick queues per group, so that a workgroup's LDS tallies belong to one INT array
     // (launches that tally into ONE INT array -- the source blocks of one frequency, soc_batch_begin_shared_int -- share the queues)
     int ngrp = 0;
     for (int l = 0; l < K.n; l++) {
@@ -2360,95 +2335,94 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int
         if (g == ngrp) K.gfirst[ngrp++] = l;
         K.grp[l] = g;
     }
-    if (!V.wint) { ngrp = 1;  for (int l = 0; l < K.n; l++) K.grp[l] = 0; }
+    if (!pl.wint) { ngrp = 1;  for (int l = 0; l < K.n; l++) K.grp[l] = 0; }
     A.NBQ = (ngrp > 1) ? A.NB * ngrp : A.NB;
     if ((long long)A.NB * ngrp > (1 << 20)) return hipErrorNotSupported;
-    const int NQ = A.NBQ + A.EQ * K.n + 1;
-    // packets in flight: `population` of them (0: all work items at once); the other work items are admitted, in
-    // order, as earlier ones finish.  Queues, descriptors and the grids of the passes are sized for that many.
-    if (population < 0) {
-        // measured: about 5300 packets per brick on Cartesian grids (C2, 512 bricks: 2.7e6 -> 8.5e8 packets/s, 2.1e6 and
-        // 3.1e6 -> 8.1e8; 256^3, 4096 bricks: 2.6e7 -> 1.09e11 steps/s, 2.7e6 -> 8.1e10), 2.6e7 on the 256^3-root
-        // hierarchy (1.3e7 -> 3.7e10 steps/s, 5.0e7 -> 4.0e10)
-        // brick-local hierarchies: 3e8 (256^3 roots, 4 levels, 8194 bricks: 5.0e7 -> 4.6e10 steps/s, 1.0e8 -> 5.0e10, 3.0e8 -> 5.3e10:
-        // the longer a workgroup lives, the less its last iterations -- lanes running dry -- weigh)
-        // (round 3, the bench's 20 launches = 3.36e8 work items: all at once 3.87e8 packets/s, capped at 3e8 3.79e8, at 2.4e8 3.79e8 -> 6e8)
-        const long long p = A.LT ? 600000000LL : V.octree ? 26000000LL : std::max(2700000LL, 5300LL * A.NBQ);
-        population = (int)std::min(p, 2000000000LL);
-    }
-    if (tune.POP > 0) population = tune.POP;
-    A.target = (population > 0 && (uint32_t)population < count) ? population : (int)count;
-    const uint32_t live = (uint32_t)A.target;
-    const int maxdesc = (int)((live + A.P - 1) / A.P) + NQ + K.n;
-    A.HS = (NQ > 4096) ? 1024 : 0;
+    A.nl = K.n;
+    sz.count = count;
+    sz.NQ = A.NBQ + A.EQ * K.n + 1;
+    return hipSuccess;
+}
+
+// Step 5: the rest of the plan, from the packed launches: packets in flight, the arrivals table, the LDS of the pass kernel, KIND
+static hipError_t plan_kernel(SocSweepPlan &pl, SocBrickArgs &A, SocSweepSize &sz, const SocSimPack &K, const SocBrickTune &tune)
+{
+    // packets in flight: the other work items are admitted, in order, as earlier ones finish.  Queues, descriptors and the grids of the
+    // passes are sized for that many.
+    // measured: about 5300 packets per brick on Cartesian grids (C2, 512 bricks: 2.7e6 -> 8.5e8 packets/s, 2.1e6 and
+    // 3.1e6 -> 8.1e8; 256^3, 4096 bricks: 2.6e7 -> 1.09e11 steps/s, 2.7e6 -> 8.1e10), 2.6e7 on the 256^3-root
+    // hierarchy (1.3e7 -> 3.7e10 steps/s, 5.0e7 -> 4.0e10)
+    // brick-local hierarchies: 3e8 (256^3 roots, 4 levels, 8194 bricks: 5.0e7 -> 4.6e10 steps/s, 1.0e8 -> 5.0e10, 3.0e8 -> 5.3e10:
+    // the longer a workgroup lives, the less its last iterations -- lanes running dry -- weigh)
+    // (round 3, the bench's 20 launches = 3.36e8 work items: all at once 3.87e8 packets/s, capped at 3e8 3.79e8, at 2.4e8 3.79e8 -> 6e8)
+    const long long pop = (pl.form == 3) ? 600000000LL : pl.octree ? 26000000LL : std::max(2700000LL, 5300LL * A.NBQ);
+    A.target = (int)std::min<long long>((tune.POP > 0) ? tune.POP : std::min(pop, 2000000000LL), sz.count);
+    sz.maxdesc = (int)(((uint32_t)A.target + A.P - 1) / A.P) + sz.NQ + K.n;
+    A.HS = (sz.NQ > 4096) ? 1024 : 0;
     if (tune.HS > 0) A.HS = tune.HS;
     if (A.HS & (A.HS - 1)) return hipErrorInvalidValue;
+    // LDS: the brick's tallies (brick-local: its cells too -- + INT, + the vector sums, + XAB and the cell numbers; rays: the cells only),
+    // the arrivals table, the launches' counters
+    const int BV = pl.octree ? A.CAP : (1 << (3 * A.LB));
+    const int nh = A.HS ? 2 * A.HS : sz.NQ;
+    const size_t lds_walk = (pl.form == 3) ? (size_t)(BV * (pl.rays ? 1 : (2 + (pl.wint == 2 ? 4 : (pl.wint == 1) ? 1 : 0) + (pl.ali ? 2 : 0)))
+                                                      + ((nh + 3) & ~3) + 4 + 4 * SOC_MAXLAUNCH) * 4
+                                           : (size_t)(BV * (1 + pl.wint) + nh + 2 + 3 * SOC_MAXLAUNCH + SOC_MAXL + A.P) * 4;
+    const size_t lds_ev = (size_t)(nh + 4 + SOC_MAXL) * 4;
+    pl.lds = std::max(lds_walk, lds_ev);
+    if (pl.lds > 160 * 1024) return hipErrorNotSupported;
+    // KIND: the kind of every launch; background packets only: the lean kernel.  Launches of several kinds: brick-local hierarchies
+    // only, where the walk takes the kind from the launch (soc_capi.hip sees to it elsewhere).  (Rays: one kernel for every kind.)
+    if (!pl.rays) {
+        bool several = false, all_bg = true;
+        pl.kind = soc_source_kind(K.S[0].SOURCE);
+        for (int l = 0; l < K.n; l++) {
+            several = several || (soc_source_kind(K.S[l].SOURCE) != pl.kind);
+            all_bg = all_bg && (K.S[l].SOURCE == 1);
+        }
+        if (several && pl.form != 3) return hipErrorInvalidValue;
+        if (several) pl.kind = 4;
+        else if (all_bg && !tune.nolean) pl.kind = 3;
+    }
+    if (pl.form != 3) for (int l = 0; l < K.n; l++) if (K.S[l].MIRROR) return hipErrorNotSupported;      // reflecting faces: the event workgroups of brick-local hierarchies only
+    return hipSuccess;
+}
 
-    SocBrickBuffers &bb = g_bb[device];
-    if (bb.cap_items < count) {
-        BCHK(hipStreamSynchronize(st));
-        BCHK(brick_alloc(&bb.pk, count));
-        BCHK(brick_alloc(&bb.idq[0], count));
-        BCHK(brick_alloc(&bb.idq[1], count));
-        BCHK(brick_alloc(&bb.keyq, count));
-        BCHK(brick_alloc(&bb.posq, count));
-        bb.cap_items = count;
+// Step 6: the device buffers, grown to the sweep's size
+static hipError_t reserve_buffers(SocBrickBuffers &bb, SocBrickArgs &A, const SocSweepSize &sz, const SocSca *sca, hipStream_t st)
+{
+    BCHK(grow(bb.cap_items, sz.count, st, &bb.pk, &bb.idq[0], &bb.idq[1], &bb.keyq, &bb.posq));
+    BCHK(grow(bb.cap_nq, sz.NQ, st, &bb.hist, &bb.off));
+    BCHK(grow(bb.cap_desc, sz.maxdesc, st, &bb.desc[0], &bb.desc[1]));
+    if (sca) {
+        BCHK(grow(bb.cap_park, sz.count, st, &bb.park));
+        A.park = bb.park;
+        A.sca = *sca;
     }
-    if (bb.cap_nq < NQ) {
-        BCHK(hipStreamSynchronize(st));
-        BCHK(brick_alloc(&bb.hist, NQ));
-        BCHK(brick_alloc(&bb.off, NQ));
-        bb.cap_nq = NQ;
-    }
-    if (bb.cap_desc < maxdesc) {
-        BCHK(hipStreamSynchronize(st));
-        BCHK(brick_alloc(&bb.desc[0], maxdesc));
-        BCHK(brick_alloc(&bb.desc[1], maxdesc));
-        bb.cap_desc = maxdesc;
-    }
-    if (sca && bb.cap_park < count) {
-        BCHK(hipStreamSynchronize(st));
-        BCHK(brick_alloc(&bb.park, count));
-        bb.cap_park = count;
-    }
-    A.park = sca ? bb.park : nullptr;
-    if (sca) A.sca = *sca;
     if (!bb.pack) BCHK(brick_alloc(&bb.pack, 1));
     if (!bb.ndesc) { BCHK(brick_alloc(&bb.ndesc, 4));  BCHK(brick_alloc(&bb.total, 1));  BCHK(brick_alloc(&bb.admit, 1 + 3 * SOC_MAXLAUNCH)); }
     A.pk = bb.pk;  A.keyq = bb.keyq;  A.posq = bb.posq;  A.hist = bb.hist;  A.off = bb.off;  A.total = bb.total;
     A.admit = bb.admit;
-    A.nl = K.n;
     A.first = (const uint32_t *)((const char *)bb.pack + offsetof(SocSimPack, first));
+    return hipSuccess;
+}
 
-    const int BV = V.octree ? A.CAP : (1 << (3 * LB));
-    const int nh = A.HS ? 2 * A.HS : NQ;
-    const size_t lds_walk = A.LT ? (size_t)(BV * (sca ? 1 : (2 + (V.wint == 2 ? 4 : (V.wint && !A.int_only) ? 1 : 0) + (A.ali ? 2 : 0))) + ((nh + 3) & ~3) + 4 + 4 * SOC_MAXLAUNCH) * 4
-                                 : (size_t)(BV * (1 + (V.wint ? 1 : 0)) + nh + 2 + 3 * SOC_MAXLAUNCH + SOC_MAXL + A.P) * 4;
-    const size_t lds_ev = (size_t)(nh + 4 + SOC_MAXL) * 4;
-    const size_t lds = lds_walk > lds_ev ? lds_walk : lds_ev;
-    if (lds > 160 * 1024) return hipErrorNotSupported;
-    const int vkey = (V.abu ? 2 : 0) | (V.wint ? 1 : 0);
-    int kind = (K.S[0].SOURCE == SOC_SOURCE_CL) ? 2 : (K.S[0].SOURCE == SOC_SOURCE_HP) ? 1 : 0;
-    bool all_bg = (kind == 0);
-    for (int l = 0; l < K.n; l++) {
-        const int kl = (K.S[l].SOURCE == SOC_SOURCE_CL) ? 2 : (K.S[l].SOURCE == SOC_SOURCE_HP) ? 1 : 0;
-        if (kl != kind) {                                             // launches of several kinds: brick-local hierarchies only, where the walk
-            if (!A.LT) return hipErrorInvalidValue;                   // takes the kind from the launch (soc_capi.hip sees to it elsewhere)
-            kind = 4;
-            break;
-        }
-        all_bg = all_bg && (K.S[l].SOURCE == 1);
-    }
-    if (kind != 4 && all_bg && !tune.nolean) kind = 3;  // background packets only: the lean kernel
-    if (!A.LT) for (int l = 0; l < K.n; l++) if (K.S[l].MIRROR) return hipErrorNotSupported;      // reflecting faces: the event workgroups of brick-local hierarchies only
+// Step 7: the passes, 64 at a time between looks at the packets left in the queues
+static hipError_t run_passes(int &passes, const SocSweepPlan &pl, SocBrickArgs A, const SocSweepSize &sz, const SocGrid &G,
+                             const SocSimPack &K, const SocBrickBuffers &bb, const SocBrickTune &tune, hipStream_t st)
+{
+    const SocPassFn pass = pass_kernel(pl);
+    if (pl.lds > 64 * 1024)                        // more dynamic LDS than the default limit (per device and kernel)
+        (void)hipFuncSetAttribute((const void *)pass, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const uint32_t live = (uint32_t)A.target;
     const int slices = (A.P + A.T - 1) / A.T;
     const int nev = ((int)((live + A.P - 1) / A.P) + (A.EQ + 1) * K.n) * slices;
-
     BCHK(hipMemcpyAsync(bb.pack, &K, sizeof(SocSimPack), hipMemcpyHostToDevice, st));
-    BCHK(hipStreamSynchronize(st));                                   // K is on this stack
-    soc_brick2_init<<<(max(count, (uint32_t)NQ) + 255) / 256, 256, 0, st>>>(bb.pack, A, count, bb.idq[0], bb.desc[0], bb.ndesc, bb.hist);
+    BCHK(hipStreamSynchronize(st));                                   // K is on the caller's stack
+    soc_brick2_init<<<(std::max(sz.count, (uint32_t)sz.NQ) + 255) / 256, 256, 0, st>>>(bb.pack, A, sz.count, bb.idq[0], bb.desc[0], bb.ndesc, bb.hist);
     BCHK(hipGetLastError());
-    int passes = 0, total = 1;
+    passes = 0;
+    int total = 1;
     const auto t_begin = std::chrono::steady_clock::now();
     auto t_last = t_begin;
     // The grids of a pass are sized for the packets that can be in the queues.  Once every work item has been admitted that number only
@@ -2458,20 +2432,16 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int
     long long live_now = (long long)live;
     while (total > 0) {
         const int chunks_now = (int)((live_now + A.P - 1) / A.P);
-        const int maxdesc_now = std::min<long long>(maxdesc, chunks_now + std::min<long long>(NQ, live_now) + K.n);
+        const int maxdesc_now = std::min<long long>(sz.maxdesc, chunks_now + std::min<long long>(sz.NQ, live_now) + K.n);
         const int nev_now = std::min<long long>(nev, (long long)(chunks_now + (A.EQ + 1) * K.n) * slices);
         for (int k = 0; k < 64; k++, passes++) {
             const int c = k & 1;
             A.idq = bb.idq[c];  A.idq_next = bb.idq[1 - c];
             A.desc = bb.desc[c];  A.ndesc = bb.ndesc + c;
             A.desc_next = bb.desc[1 - c];  A.ndesc_next = bb.ndesc + (1 - c);
-            if (sca)         BCHK(soc_lray_launch_pass(sca_hp, maxdesc_now + nev_now, A.T, lds, st, G, bb.pack, A, maxdesc_now, slices));
-            else if (A.LT)   soc_lbrick_launch_pass(A.int_only ? 3 : V.wint, kind, maxdesc_now + nev_now, A.T, lds, st, G, bb.pack, A, maxdesc_now, slices);
-            else if (!V.octree) soc_brick_launch_pass<false, false>(vkey, kind, maxdesc_now + nev_now, A.T, lds, st, G, bb.pack, A, maxdesc_now, slices);
-            else if (!V.dbl) soc_brick_launch_pass<true, false>(vkey, kind, maxdesc_now + nev_now, A.T, lds, st, G, bb.pack, A, maxdesc_now, slices);
-            else             soc_brick_launch_pass<true, true>(vkey, kind, maxdesc_now + nev_now, A.T, lds, st, G, bb.pack, A, maxdesc_now, slices);
+            pass<<<maxdesc_now + nev_now, A.T, pl.lds, st>>>(G, bb.pack, A, maxdesc_now, slices);
             SocBrickArgs Q = A;                           // the sort sees NQ - 1 live queues; the last one = finished
-            Q.NB = NQ - 1;
+            Q.NB = sz.NQ - 1;
             Q.ev_brick = A.NBQ;
             soc_brick_scan<<<1, 1024, 0, st>>>(Q);
             soc_brick_scatter<<<maxdesc_now + 16 * K.n, SOC_BRICK_T, 0, st>>>(Q, maxdesc_now);
@@ -2481,7 +2451,7 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int
         BCHK(hipMemcpyAsync(&total, bb.total, sizeof(int), hipMemcpyDeviceToHost, st));
         BCHK(hipMemcpyAsync(&admitted, bb.admit, sizeof(int), hipMemcpyDeviceToHost, st));
         BCHK(hipStreamSynchronize(st));
-        if ((uint32_t)admitted >= count) live_now = std::min<long long>(live_now, std::max(total, 1));
+        if ((uint32_t)admitted >= sz.count) live_now = std::min<long long>(live_now, std::max(total, 1));
         if (tune.verbose > 1) {                                       // the course of a sweep: packets in the queues every 64 passes
             const auto t_now = std::chrono::steady_clock::now();
             fprintf(stderr, "soc_brick: pass %6d  packets in queues %10d  %8.2f ms per pass\n", passes, total,
@@ -2490,12 +2460,36 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *Sin, int
         }
         if (passes > 4000000) return hipErrorUnknown;                 // cannot happen: every pass retires work
     }
-    if (passes_out) *passes_out = passes;
-    if (form_out) *form_out = A.LT ? 3 : (V.octree ? 2 : 1);
-    if (variant_out) {                                                // the pass kernel the loop above launched
-        if (sca)       *variant_out = soc_variant_code(3, 0, 0, true, true, false, false, true) | (sca->NDIR < 0 ? SOC_VAR_HEALPIX : 0) | (sca_hp ? SOC_VAR_HPSKY : 0);
-        else if (A.LT) *variant_out = soc_variant_code(3, kind, A.int_only ? 3 : V.wint, true, true, false, A.ali != 0, false);
-        else           *variant_out = soc_variant_code(V.octree ? 2 : 1, kind, V.wint ? 1 : 0, V.octree, V.octree && V.dbl, V.abu != 0, false, false);
+    return hipSuccess;
+}
+
+// LB: log2 of the brick edge (Cartesian grids; hierarchies use bricks of <= CAP leaves).  nlaunch launches (same geometry, same
+// tallies) share one sweep: more packets in flight per pass, and the passes in which one launch's last work items finish are filled
+// by the others.  hipErrorNotSupported: the launches cannot use bricks (the callers run the direct kernels); hipErrorInvalidValue:
+// the tuning is out of range, or the launches cannot share one sweep.
+hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *S, int nlaunch, const SocVariant &V, int LB,
+                            const SocBrickTune &tune, hipStream_t st, SocSweepResult *res, const SocSca *sca)
+{
+    res->form = 0;
+    BCHK(check_sca(S, nlaunch, V, sca));
+    if (device < 0 || device >= 16 || nlaunch < 1 || nlaunch > SOC_MAXLAUNCH) return hipErrorNotSupported;
+    SocSweepPlan pl;
+    BCHK(plan_sweep(pl, G, S, nlaunch, V, tune, sca, true));
+    SocBrickArgs A;
+    hipError_t e = build_bricks(A, pl, device, G, LB, st, tune.verbose != 0);
+    if (e == hipErrorNotSupported && pl.form == 3) {                  // a root cell with more cells below it than a brick holds:
+        BCHK(plan_sweep(pl, G, S, nlaunch, V, tune, sca, false));     // the sweep that reads the hierarchy from global memory
+        e = build_bricks(A, pl, device, G, LB, st, tune.verbose != 0);
     }
+    BCHK(e);
+    SocSimPack K{};
+    SocSweepSize sz{};
+    BCHK(pack_launches(K, sz, A, pl, G, S, nlaunch, tune));
+    if (K.n == 0) { res->passes = 0;  return hipSuccess; }            // no launch has work items
+    BCHK(plan_kernel(pl, A, sz, K, tune));
+    BCHK(reserve_buffers(g_bb[device], A, sz, sca, st));
+    int passes = 0;
+    BCHK(run_passes(passes, pl, A, sz, G, K, g_bb[device], tune, st));
+    *res = SocSweepResult{ passes, pl.form, soc_variant_code(pl) };
     return hipSuccess;
 }

@@ -110,8 +110,8 @@ struct soc_ctx {
     // features
     int with_int = 0, ps_method = 0, use_emweight = 0, mirror = 0;
     // execution
-    int exec_mode = -1, brick_log2 = 4, last_passes = 0, last_form = 0;
-    int last_variant = -1;                        // soc_last_variant: the absorption kernel last launched (-1: none yet)
+    int exec_mode = -1, brick_log2 = 4;
+    SocSweepResult last;                          // the last sweep's passes and form; variant: soc_last_variant, the absorption kernel last launched (-1: none yet)
     SocBrickTune tune{};
     // equilibrium temperature / emission (soc_emit.hip)
     float *dT = nullptr, *dTTT = nullptr, *dEbuf = nullptr, *dEF = nullptr;
@@ -167,13 +167,7 @@ static size_t view_pixels(const soc_ctx *c)
 
 // Hierarchies on which the brick sweep keeps the brick's cells in LDS (soc_brick.hip, soc_ltree.h): there a lone
 // launch with enough work items pays too -- also with the INT tally, which lives in LDS beside TABS.
-static bool lt_capable(const soc_ctx *c, bool abu)
-{
-    const SocGrid &G = c->G;
-    const int n = G.NX > G.NY ? (G.NX > G.NZ ? G.NX : G.NZ) : (G.NY > G.NZ ? G.NY : G.NZ);
-    return G.LEVELS > 1 && G.LEVELS <= 8 && G.NX > ((G.LEVELS < 3) ? 399 : 100) && !abu && !c->tune.global_tree
-           && (((long long)n << (G.LEVELS - 1)) < (1LL << 24)) && n < 4096;
-}
+static bool lt_capable(const soc_ctx *c, bool abu) { return soc_brick_local(c->G, soc_grid_variant(c->G, abu), c->tune); }
 // ... the launches of the scattered-light kernels (alone, or those of a batch together) go to the sweep of rays.  Measured on the 256^3-root
 // hierarchy (tools/exp_sca.py): 1.0e6 work items 0.47x the direct kernel, 3.1e6 0.92x, 8.4e6 1.3x, 5.0e7 1.6x (best direct launch shape), 32
 // launches of 3.1e6 in one batch 4.4x
@@ -184,10 +178,9 @@ static bool lt_capable(const soc_ctx *c, bool abu)
 // brick sweep; the direct kernels take them as 1 and 2)
 static int run_direct(soc_ctx *c, SocSim S, const SocVariant &V)
 {
-    c->last_passes = 0;
+    c->last.passes = 0;
     if (S.gid_count > 0)                    // (the launch wrappers run nothing without work items; Cartesian grids take the float kernels)
-        c->last_variant = soc_variant_code(0, S.SOURCE == SOC_SOURCE_HP ? 1 : S.SOURCE == SOC_SOURCE_CL ? 2 : 0, V.wint ? 1 : 0, V.octree,
-                                           V.octree && V.dbl, V.abu != 0, false, false);
+        c->last.variant = soc_variant_code(soc_grid_plan(0, soc_source_kind(S.SOURCE), V));
     if (S.SOURCE == SOC_SOURCE_HP) {
         S.SOURCE = 1;
         HIPCHK(c, soc_launch_sim_hp(c->G, S, V, c->stream));
@@ -206,13 +199,11 @@ static int flush_pending(soc_ctx *c)
     if (c->pending.empty()) return SOC_OK;
     std::vector<SocSim> todo;
     todo.swap(c->pending);
-    SocVariant V;
-    V.octree = c->G.LEVELS > 1;  V.dbl = c->G.NX > ((c->G.LEVELS < 3) ? 399 : 100);
+    SocVariant V = soc_grid_variant(c->G);
     if (c->pending_sca) {
         // deferred launches of the scattered-light kernels: one sweep of rays for all of them; where the sweep does not apply
         // (it did when they were deferred: the grid has not changed since) each runs through the direct kernel
         c->pending_sca = false;
-        V.abu = 0;  V.wint = 0;
         HIPCHK(c, hipSetDevice(c->device));
         SocSca X = c->view;
         X.kind = todo[0].SCAKIND - 1;  X.DSC = todo[0].DSC;  X.OUT = todo[0].OUT;
@@ -220,7 +211,7 @@ static int flush_pending(soc_ctx *c)
         for (const SocSim &S1 : todo) items += S1.gid_count;
         hipError_t e = hipErrorNotSupported;
         if (c->exec_mode == 1 || items >= SOC_SCA_RAYS_LAUNCH)     // (too few rays to fill the brick queues: the direct kernel, launch by launch)
-            e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form, &c->last_variant, &X);
+            e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, c->tune, c->stream, &c->last, &X);
         if (e == hipErrorNotSupported) {
             for (SocSim &S1 : todo) {
                 X.kind = S1.SCAKIND - 1;  X.DSC = S1.DSC;  X.OUT = S1.OUT;
@@ -237,8 +228,7 @@ static int flush_pending(soc_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     if (V.octree && todo.size() == 1 && c->exec_mode < 0 && !(lt_capable(c, V.abu != 0) && todo[0].gid_count >= SOC_LT_LONE_LAUNCH))
         return run_direct(c, todo[0], V);      // a single launch on a hierarchy: the direct kernel is as fast (1.9e10 vs 2.0e10 steps/s at 256^3, 4 levels)
-    // packets in flight: chosen by the sweep from the number of bricks (-1)
-    hipError_t e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form, &c->last_variant);
+    hipError_t e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, c->tune, c->stream, &c->last);
     if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep of %d deferred launches failed: %s", (int)todo.size(), hipGetErrorString(e));
     return SOC_OK;
 }
@@ -493,9 +483,9 @@ int soc_set_tuning(soc_ctx *c, const char *name, int value)
     return fail(c, SOC_ERR_ARG, "soc_set_tuning: unknown parameter '%s'", name);
 }
 
-int soc_last_passes(soc_ctx *c) { return c ? c->last_passes : 0; }
-int soc_last_form(soc_ctx *c) { return (c && c->last_passes > 0) ? c->last_form : 0; }
-int soc_last_variant(soc_ctx *c) { return c ? c->last_variant : -1; }
+int soc_last_passes(soc_ctx *c) { return c ? c->last.passes : 0; }
+int soc_last_form(soc_ctx *c) { return (c && c->last.passes > 0) ? c->last.form : 0; }
+int soc_last_variant(soc_ctx *c) { return c ? c->last.variant : -1; }
 
 int soc_set_optical(soc_ctx *c, const float *ABS, const float *SCA, int ndust)
 {
@@ -736,10 +726,8 @@ static void fill_sim(soc_ctx *c, SocSim &S, SocVariant &V, int SOURCE, int BATCH
     S.INTV = (c->with_int == 2) ? c->dINTV : nullptr;  S.CELLS = c->G.CELLS;
     S.NDUST = c->msf_ndust;
     if (c->msf_ndust > 1) { S.MSF_SCA = c->dAF + c->msf_ndust;  S.ABU = c->dABU; }
-    V.octree = c->G.LEVELS > 1;
-    V.dbl = c->G.NX > ((c->G.LEVELS < 3) ? 399 : 100);   // DIMLIM, kernel_ASOC_aux.c:25-37
-    V.abu = c->dOPT != nullptr;
-    V.wint = c->with_int;                                  // 0, 1, or 2: INT and the vector sums (the brick-local sweep and the direct kernels)
+    // with_int 0, 1, or 2: INT and the vector sums (the brick-local sweep and the direct kernels)
+    V = soc_grid_variant(c->G, c->dOPT != nullptr, c->with_int);
 }
 
 // Point sources of one launch -> device.  xps_as_float: the scattered-light kernels declare
@@ -828,10 +816,8 @@ static bool same_sweep(const soc_ctx *c, int source, bool abu)
     if (c->pending.empty()) return true;
     if (c->pending_sca) return false;                        // deferred scattered-light launches: another kind of sweep
     const SocSim &P = c->pending[0];
-    const int kp = (P.SOURCE == SOC_SOURCE_CL) ? 2 : (P.SOURCE == SOC_SOURCE_HP) ? 1 : 0;
-    const int kn = (source == SOC_SOURCE_CL) ? 2 : (source == SOC_SOURCE_HP) ? 1 : 0;
     if ((P.OPT != nullptr) != abu) return false;
-    return kp == kn || lt_capable(c, abu);      // (brick-local hierarchies: the kinds share sweeps, also with per-group INT tallies)
+    return soc_source_kind(P.SOURCE) == soc_source_kind(source) || lt_capable(c, abu);      // (brick-local hierarchies: the kinds share sweeps, also with per-group INT tallies)
 }
 
 static int snapshot_emission(soc_ctx *c, SocSim &S, int slot);
@@ -881,7 +867,7 @@ static int route_sim(soc_ctx *c, SimKind kind, SocSim &S, const SocVariant &V, l
     const int slot = defer ? (int)c->pending.size() : -1;
     r = slot_inputs(slot);
     if (r) return r;
-    c->last_passes = 0;
+    c->last.passes = 0;
     if (defer) {
         r = snapshot_inputs(c, S, V, slot);
         if (r) return r;
@@ -891,7 +877,7 @@ static int route_sim(soc_ctx *c, SimKind kind, SocSim &S, const SocVariant &V, l
         return SOC_OK;
     }
     if (!bricks) return run_direct(c, S, V);
-    hipError_t e = soc_brick_run_pb(c->device, c->G, &S, 1, V, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form, &c->last_variant);
+    hipError_t e = soc_brick_run_pb(c->device, c->G, &S, 1, V, c->brick_log2, c->tune, c->stream, &c->last);
     if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep failed: %s", hipGetErrorString(e));
     return SOC_OK;
 }
@@ -1332,7 +1318,7 @@ static int sca_launch(soc_ctx *c, const char *who, int kind, SocSim &S, SocVaria
     X.OUT = c->out_slots ? c->dOUTslots + (size_t)c->out_slot_cur * c->out_slot_pixels : c->dOUT;
     S.TABS = nullptr;  S.INT = nullptr;
     S.SCAKIND = kind + 1;  S.DSC = X.DSC;  S.OUT = X.OUT;
-    c->last_passes = 0;  c->last_form = 0;
+    c->last.passes = 0;  c->last.form = 0;
     const bool rays_ok = sca_rays_ok(c);
     if (c->exec_mode == 1 && !rays_ok)
         return fail(c, SOC_ERR_ARG, "%s: brick sweep requested but not applicable: %s", who, sca_rays_refusal(c));
@@ -1368,7 +1354,7 @@ static int sca_launch(soc_ctx *c, const char *who, int kind, SocSim &S, SocVaria
         if (kind == SOC_SCA_CL) R.SOURCE = SOC_SOURCE_CL;
         SocVariant W = V;
         W.wint = 0;
-        hipError_t e = soc_brick_run_pb(c->device, c->G, &R, 1, W, c->brick_log2, -1, c->tune, c->stream, &c->last_passes, &c->last_form, &c->last_variant, &X);
+        hipError_t e = soc_brick_run_pb(c->device, c->G, &R, 1, W, c->brick_log2, c->tune, c->stream, &c->last, &X);
         if (e == hipSuccess) return SOC_OK;
         if (e != hipErrorNotSupported || c->exec_mode == 1) return fail(c, SOC_ERR_HIP, "%s: brick sweep failed: %s", who, hipGetErrorString(e));
     }
@@ -2160,10 +2146,7 @@ int soc_probe_trace(soc_ctx *c, const float pos[3], const float dir[3], int maxs
     HIPCHK(c, hipMalloc((void **)&dLev, (size_t)maxsteps * 8));
     HIPCHK(c, hipMalloc((void **)&dN, 4));
     float h[9] = { pos[0], pos[1], pos[2], dir[0], dir[1], dir[2], 0, 0, 0 };
-    SocVariant V;
-    V.octree = c->G.LEVELS > 1;
-    V.dbl = c->G.NX > ((c->G.LEVELS < 3) ? 399 : 100);
-    V.abu = 0; V.wint = 0;
+    const SocVariant V = soc_grid_variant(c->G);
     hipError_t e = hipMemcpy(dIn, h, sizeof h, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = soc_launch_trace(c->G, V, dIn, dIn + 3, maxsteps, dLev, dLev + maxsteps, dDs, dIn + 6, dN, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 
 #define SOC_MAXL 16            /* hierarchy levels supported (reference models use <= 8) */
 
@@ -187,24 +188,76 @@ struct SocBrickTune {
     int verbose;
 };
 
-// brick-sweep execution (soc_brick.hip): LDS-resident tallies, packets sorted by brick
-// population: packets in flight (0 = all work items at once, -1 = chosen from the number of bricks): the other work
-// items are admitted as earlier ones finish
-// variant_out: the code of the pass kernel that ran (soc_variant_code; untouched when no kernel ran)
-hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *S, int nlaunch, const SocVariant &V, int LB,
-                            int population, const SocBrickTune &tune, hipStream_t st, int *passes_out, int *form_out,
-                            int *variant_out, const struct SocSca *sca = nullptr);      // sca: the launch is one of the scattered-light kernels (rays, soc_sca_events)
+// KIND of a launch's source: 0 SimRAM_PB, 1 SimRAM_HP, 2 SimRAM_CL
+static inline int soc_source_kind(int source) { return (source == SOC_SOURCE_CL) ? 2 : (source == SOC_SOURCE_HP) ? 1 : 0; }
 
-// The compiled absorption kernel a launch ran on, as soc_last_variant reports it (bit layout: include/soc_hip.h, SOC_VAR_*).
-// form 0 direct (kind 0 PB, 1 HP, 2 CL), 1 Cartesian sweep, 2 sweep of a hierarchy in global memory, 3 brick-local sweep
-// (kind: the KIND template argument 0-4); wint: the WINT template argument; rays: the scattered-light sweep of rays.
-static inline int soc_variant_code(int form, int kind, int wint, bool octree, bool dbl, bool abu, bool ali, bool rays)
+// the grid's kernels: octree for hierarchies, Index() in double beyond DIMLIM (kernel_ASOC_aux.c:25-37)
+static inline SocVariant soc_grid_variant(const SocGrid &G, bool abu = false, int wint = 0)
 {
-    return form | (kind << 2) | (wint << 5) | (octree ? 1 << 7 : 0) | (dbl ? 1 << 8 : 0) | (abu ? 1 << 9 : 0) | (ali ? 1 << 10 : 0)
-           | (rays ? 1 << 11 : 0);
+    SocVariant V;
+    V.octree = G.LEVELS > 1;
+    V.dbl = G.NX > ((G.LEVELS < 3) ? 399 : 100);
+    V.abu = abu;
+    V.wint = wint;
+    return V;
 }
+
+// Grids on which the brick sweep walks brick-local hierarchies (soc_brick.hip, soc_ltree.h): 2-8 levels with Index() in double, scalar
+// opacities, cell coordinates within 24 bits and root-cell numbers from 24-bit multiplies (SOC_MAD24) -- unless
+// soc_set_tuning("global_tree", 1) asks for the sweep that reads the hierarchy from global memory
+static inline bool soc_brick_local(const SocGrid &G, const SocVariant &V, const SocBrickTune &tune)
+{
+    const int n = std::max(G.NX, std::max(G.NY, G.NZ));
+    return V.octree && V.dbl && !V.abu && !tune.global_tree && G.LEVELS <= 8 && ((long long)n << (G.LEVELS - 1)) < (1LL << 24) && n < 4096;
+}
+
+// What a brick sweep runs, decided before it runs (soc_brick.hip: plan_sweep, completed by plan_kernel once the launches are packed).
+// Form 0 describes a launch of the direct kernels (soc_capi.hip: run_direct).
+struct SocSweepPlan {
+    int  form;                 // 0 direct kernel, 1 Cartesian sweep, 2 sweep of a hierarchy in global memory, 3 brick-local sweep
+    int  kind;                 // the KIND template argument: 0 SimRAM_PB, 1 _HP, 2 _CL, 3 background packets only, 4 several (brick-local); rays: 0
+    int  wint;                 // the WINT template argument: 0, 1, 2 (brick-local), 3 the INT-only form of the brick-local walk
+    bool octree, dbl, abu;     // the grid's kernels (dbl: octree and Index() in double)
+    bool ali;                  // brick-local: every launch a SimRAM_CL one with the XAB tally (WITH_ALI)
+    bool rays, hpx, hpsky;     // the scattered-light sweep of rays; its image a Healpix map seen from a position; SimRAM_HP launches in it
+    bool roi;                  // brick-local: the record of packets entering ROI (a fourth event queue per launch)
+    int  capl;                 // brick-local: cells per brick
+    // SocBrickArgs: the form's defaults with soc_set_tuning applied (CAP: leaves per brick of a hierarchy in global memory)
+    int  T, P, KCAP, FTH, CTH, CAP, TAIL, PARK, EQ, slow_every;
+    size_t lds;                // dynamic LDS of the pass kernel
+};
+
+// the plan of the grid's own kernels: the direct ones (form 0), the Cartesian and global-tree sweeps
+static inline SocSweepPlan soc_grid_plan(int form, int kind, const SocVariant &V)
+{
+    SocSweepPlan p{};
+    p.form = form;
+    p.kind = kind;
+    p.wint = V.wint ? 1 : 0;
+    p.octree = V.octree;
+    p.dbl = V.octree && V.dbl;
+    p.abu = V.abu;
+    return p;
+}
+
+// The compiled absorption kernel a plan runs, as soc_last_variant reports it (bit layout: include/soc_hip.h, SOC_VAR_*)
 #define SOC_VAR_HEALPIX (1 << 12)   // sweeps of rays: the image was a Healpix map seen from a position
 #define SOC_VAR_HPSKY   (1 << 13)   // sweeps of rays: the sweep held a SimRAM_HP launch (the Healpix sky as the source)
+static inline int soc_variant_code(const SocSweepPlan &p)
+{
+    return p.form | (p.kind << 2) | (p.wint << 5) | (p.octree ? 1 << 7 : 0) | (p.dbl ? 1 << 8 : 0) | (p.abu ? 1 << 9 : 0) | (p.ali ? 1 << 10 : 0)
+           | (p.rays ? 1 << 11 : 0) | (p.hpx ? SOC_VAR_HEALPIX : 0) | (p.hpsky ? SOC_VAR_HPSKY : 0);
+}
+
+// What a brick sweep reports: passes (0 when no launch had work items), form (0 unless the sweep ran), variant (untouched when no kernel ran)
+struct SocSweepResult {
+    int passes = 0, form = 0, variant = -1;
+};
+
+// brick-sweep execution (soc_brick.hip): LDS-resident tallies, packets sorted by brick; sca: the launches are ones of the
+// scattered-light kernels (rays, soc_sca_events)
+hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *S, int nlaunch, const SocVariant &V, int LB,
+                            const SocBrickTune &tune, hipStream_t st, SocSweepResult *res, const struct SocSca *sca = nullptr);
 void soc_brick_release(int device);
 void soc_brick_invalidate(int device);      // the grid changed: bricks of a hierarchy are rebuilt at the next sweep
 

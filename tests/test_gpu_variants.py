@@ -1,7 +1,7 @@
 """Every compiled absorption kernel variant the dispatch rules can reach, run once against the oracle.
 
 The host picks one of about a hundred kernels per launch or sweep: the direct kernels (SOC_DISPATCH, soc_kernels.hip), the sweeps of
-Cartesian grids and of hierarchies in global memory (soc_brick_launch_pass) and the brick-local sweep (soc_lbrick_launch_pass).
+Cartesian grids and of hierarchies in global memory (soc_brick_pass_fns) and the brick-local sweep (soc_lbrick_pass_fns, _ali_fns).
 soc_last_variant names the one that ran.  REACHABLE lists what the rules can produce, CASES holds one small run per entry; each
 asserts the variant, tally events equal to the oracle's (packets and scatterings equal to the direct kernels' for the sweeps: the
 oracle counts only tally events) and every tally the variant writes equal to the oracle's to fp32 summation order.  The scenarios
@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 FIELDS = ("form", "kind", "wint", "octree", "dbl", "abu", "ali")       # the fields of Engine.last_variant() a key lists
 PB, HP, CL = 0, 1, 2                                                    # the kernels: SimRAM_PB, _HP, _CL (a sweep's KIND 0-2 too)
 
-# ---- what the dispatch rules can produce (soc_capi.hip route_sim / flush_pending, soc_brick.hip soc_brick_run_pb) ----
+# ---- what the dispatch rules can produce (soc_capi.hip route_sim / flush_pending, soc_brick.hip plan_sweep / plan_kernel) ----
 CLOUDS = ((0, 0), (1, 0), (1, 1))                                       # (octree, dbl): Cartesian, hierarchy with float / double Index()
 REACHABLE = set()
 # direct kernels: every kernel x grid x opacities x INT tally (exec mode 0 takes any launch there).
@@ -33,7 +33,7 @@ REACHABLE |= {(0, k, w, o, d, a, 0) for k in (PB, HP, CL) for (o, d) in CLOUDS f
 #             ALI -- a cell-emission launch with XAB is swept on brick-local hierarchies only; dbl on Cartesian grids -- as above
 REACHABLE |= {(f, k, w, o, d, a, 0) for (f, o, d) in ((1, 0, 0), (2, 1, 0), (2, 1, 1)) for k in range(4) for a in (0, 1) for w in (0, 1)}
 # brick-local sweep (form 3): WINT 0-3 x KIND 0-4, and the ALI kernels with and without the INT tally.
-#   excluded: per-cell opacities -- they keep the global-tree form (lt_capable); ALI with another KIND -- ALI needs every launch to be
+#   excluded: per-cell opacities -- they keep the global-tree form (soc_brick_local); ALI with another KIND -- ALI needs every launch to be
 #             CL with one XAB; ALI with WINT 2 -- route_sim keeps with_int 2 from it; ALI with WINT 3 -- ALI turns the INT-only form off
 REACHABLE |= {(3, k, w, 1, 1, 0, 0) for w in range(4) for k in range(5)} | {(3, CL, w, 1, 1, 0, 1) for w in (0, 1)}
 
