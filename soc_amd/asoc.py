@@ -72,6 +72,7 @@ def _check_supported(USER, NDUST, WITH_MSF):
 class AbsorptionRun:
     """The constant-source part of an ASOC run.  ``engine`` is a soc_amd.lib.Engine (or an
     object with the same methods); ``comm`` a soc_amd.dist.Comm."""
+    _hpbg_launch = staticmethod(launch.hpbg_launch)           # the Healpix background's launch shape, see _constant_launch
 
     def __init__(self, USER, engine, comm=None, verbose=None, workdir=".", shard="items"):
         """shard (several ranks): "items" -- every launch is split by work-item ranges (identical packets and events per rank, one
@@ -90,6 +91,7 @@ class AbsorptionRun:
         self.verbose = USER.VERBOSE if verbose is None else verbose
         self.timers = dict(Tkernel=0.0, Tpush=0.0, Tpull=0.0)
         self.packets = 0
+        self.freq_owner = None                 # {IFREQ: rank} where shard == "launches" gives frequencies to ranks (_plan)
         self._load_inputs()
 
     def log(self, *a):
@@ -170,22 +172,15 @@ class AbsorptionRun:
         e.set_mirror(launch.mirror_mask(U.MIRROR))
         # `stepweight a b c`: the reference hands the kernels -D SW_A=int(a) -D SW_B=b -D STEP_WEIGHT=int(c), each float
         # written with %.3e (ASOC.py:348,357) -- the drop-in passes the same values
-        sw = int(U.STEP_WEIGHT[2])
-        if sw > 0 or hasattr(e, "set_step_weight"):
-            e.set_step_weight(sw, float("%.3e" % int(U.STEP_WEIGHT[0])), float("%.3e" % U.STEP_WEIGHT[1]))
-        if U.CR_HEATING > 0 or hasattr(e, "set_cr_heating"):
-            # -D CR_HEATING=%d -D CR_HEATING_RATE=%.3ef with (USER.CR_HEATING>0), USER.CR_HEATING (ASOC.py:352,362): device solve only,
-            # as in the reference (its host loop, used with ALI, has no such term)
-            e.set_cr_heating(float("%.3e" % U.CR_HEATING) if U.CR_HEATING > 0 else 0.0)
-        if U.ROI_MAP or hasattr(e, "set_map_roi"):
-            e.set_map_roi(U.ROI if U.ROI_MAP else None)              # -D ROI_MAP (ASOC.py:345,354; :3126-3133)
-        if U.LEVEL_THRESHOLD > 0 or hasattr(e, "set_map_threshold"):
-            e.set_map_threshold(max(0, int(U.LEVEL_THRESHOLD)))      # -D LEVEL_THRESHOLD (ASOC.py:349,359)
-        if U.MAP_INTERPOLATION > 0 or hasattr(e, "set_map_interpolation"):
-            e.set_map_interpolation(int(U.MAP_INTERPOLATION))        # -D MAP_INTERPOLATION (ini key mapint; ASOC.py:352,362)
+        e.set_step_weight(int(U.STEP_WEIGHT[2]), float("%.3e" % int(U.STEP_WEIGHT[0])), float("%.3e" % U.STEP_WEIGHT[1]))
+        # -D CR_HEATING=%d -D CR_HEATING_RATE=%.3ef with (USER.CR_HEATING>0), USER.CR_HEATING (ASOC.py:352,362): device solve only,
+        # as in the reference (its host loop, used with ALI, has no such term)
+        e.set_cr_heating(float("%.3e" % U.CR_HEATING) if U.CR_HEATING > 0 else 0.0)
+        e.set_map_roi(U.ROI if U.ROI_MAP else None)                  # -D ROI_MAP (ASOC.py:345,354; :3126-3133)
+        e.set_map_threshold(max(0, int(U.LEVEL_THRESHOLD)))          # -D LEVEL_THRESHOLD (ASOC.py:349,359)
+        e.set_map_interpolation(int(U.MAP_INTERPOLATION))            # -D MAP_INTERPOLATION (ini key mapint; ASOC.py:352,362)
         if self.WITH_ABU:
-            if U.OPT_IS_HALF or hasattr(e, "set_opt_half"):
-                e.set_opt_half(bool(U.OPT_IS_HALF))            # OPT as fp16 (ASOC.py:1158-1159)
+            e.set_opt_half(bool(U.OPT_IS_HALF))                # OPT as fp16 (ASOC.py:1158-1159)
             e.set_abundances(self.ABU, single=bool(U.SINGLE_ABU))
         if self.comm:
             self.comm.attach(e, c.CELLS)
@@ -252,7 +247,7 @@ class AbsorptionRun:
         if II == 1:
             if self.BGPAC < 1:
                 return None
-            return launch.hpbg_launch(self.BGPAC, c.NX, c.NY, c.NZ) if len(self.HPBG) > 0 else launch.bg_launch(self.BGPAC, int(U.AREA))
+            return self._hpbg_launch(self.BGPAC, c.NX, c.NY, c.NZ) if len(self.HPBG) > 0 else launch.bg_launch(self.BGPAC, int(U.AREA))
         if II == 2:
             if len(self.DIFFUSERAD) < 1 or self.DFPAC < 1:
                 return None
@@ -335,8 +330,70 @@ class AbsorptionRun:
         self.packets += L["PACKETS"]
         return FF, BG, PS
 
+    # The batch policies of the constant-source launches (_plan).
+    ONE_BATCH, FREQ_GROUPS, LAUNCH_GROUPS, SEQUENTIAL = "one batch", "INT groups per frequency", "INT groups per launch", "sequential"
+
+    # Frequencies of an absorbed-file run on a hierarchy that share a sweep (an INT tally and, for cell emission, a copy of the emission each).
+    # Measured on config 3 (bench.py --workload C3INT --int-groups 4): 2.00e8 packets/s against 2.09e8 with one frequency per sweep -- the
+    # brick queues are per frequency (a workgroup's LDS tallies belong to one INT array), so more frequencies mean more queues of the same
+    # length, not longer ones; the default stays 1.
+    FREQS_PER_SWEEP = 1
+
+    def _sends(self, II, IFREQ):
+        """False where _launch sends nothing: no DIFFUSERAD column for the frequency, an empty Healpix sky (files.hpbg_for_frequency)"""
+        if II == 2:
+            return 0 <= IFREQ + self.DIFFUSERAD.shape[1] - self.NFREQ < self.DIFFUSERAD.shape[1]
+        if II == 1 and len(self.HPBG) > 0 and self.U.HPBG_WEIGHTED:
+            return bool(np.max(np.asarray(self.HPBG[IFREQ], np.float64)) >= 1.0e-40)
+        return True
+
+    def _plan(self, absorbed, thin):
+        """The launches of the constant sources on this rank and how they are batched, decided before any engine call.
+        Returns (segments, owner).  segments: [(policy, name, steps)]; TABS is zeroed before a segment and read after it (name:
+        its source block or "all source blocks").  steps: [(IFREQ, launches, summed)] in issue order, the launches
+        [(II, L, first, count)] that share the frequency's optical data, scatter tables and seed; count is this rank's work
+        items (0: another rank's launch).  summed: the step's tallies are summed over the ranks, so every rank enters its
+        collectives, also a rank with no work items in it -- derived from rank-independent data only.  owner: {IFREQ: rank}
+        where shard == "launches" gives every frequency to one rank (no collective for INT then), else None.
+        The policies:
+          ONE_BATCH      TABS-only runs: all launches one batch (soc_batch_begin); on brick-local hierarchies the point-source,
+                         background and diffuse launches of all frequencies share brick sweeps (up to 128 launches per sweep),
+                         elsewhere the engine starts a new sweep where the kind changes.  TABS is read once.
+          FREQ_GROUPS    absorbed file on a hierarchy: frequency outside, the launches of one frequency an INT group
+                         (soc_batch_begin_int_groups / soc_batch_next_int), FREQS_PER_SWEEP groups per batch, so that the
+                         blocks of a frequency share brick sweeps and brick queues.  TABS is read once.
+          LAUNCH_GROUPS  absorbed file on a Cartesian grid: block outside, every launch an INT group, 16 per batch.
+          SEQUENTIAL     the rest (intensity file, region-of-interest records, a Healpix sky on a hierarchy): INT, the
+                         intensity and the ROI record read after every launch."""
+        U, c = self.U, self.cloud
+        if U.ITERATIONS < 1:
+            return [], None
+        blocks = [(II, self._constant_launch(II)) for II in range(4)]
+        blocks = [(II, L) for II, L in blocks if L is not None]
+        freqs = [f for f in range(self.NFREQ) if U.SIM_F[0] <= float(self.FFREQ[f]) <= U.SIM_F[1]]
+        # shard == "launches" (see __init__): runs that keep the per-frequency absorptions give a frequency to one rank (not with the
+        # intensity file, region-of-interest records or emission iterations, which need every frequency on every rank -- those keep
+        # the work-item split); TABS-only runs deal out the launch sequence
+        shares, owner = None, None
+        if self.shard == "launches" and self.world > 1:
+            own_freq = self.with_int
+            if (not own_freq) or (absorbed and U.SAVE_INTENSITY == 0 and (not U.WITH_ROI_SAVE) and self.CLPAC < 1 and thin == 1):
+                shares, owner = self._launch_shares(by_frequency=own_freq)
+        summed = self.world > 1 and owner is None and bool(self.with_int or U.WITH_ROI_SAVE)
+
+        def step(IFREQ, blocks):
+            launches = [(II, L) + (shares.get((II, IFREQ), (0, 0)) if shares else launch.shard_range(L["GLOBAL"], self.rank, self.world))
+                        for II, L in blocks]
+            return IFREQ, launches, summed and any(self._sends(II, IFREQ) for II, _ in blocks)
+        if absorbed and c.LEVELS > 1 and U.SAVE_INTENSITY == 0 and not U.WITH_ROI_SAVE and not U.WITH_ROI_LOAD and len(self.HPBG) == 0:
+            return [(self.FREQ_GROUPS, "all source blocks", [step(f, blocks) for f in freqs])], owner
+        if not self.with_int and not U.WITH_ROI_SAVE:
+            return [(self.ONE_BATCH, "all source blocks", [step(f, [b]) for b in blocks for f in freqs])], owner
+        return [(self.LAUNCH_GROUPS if (absorbed and c.LEVELS == 1 and U.SAVE_INTENSITY == 0 and not U.WITH_ROI_SAVE and II != 3)
+                 else self.SEQUENTIAL, ['PS', 'BG', 'DE', 'ROI'][II], [step(f, [(II, L)]) for f in freqs]) for II, L in blocks], owner
+
     def simulate_constant_sources(self):
-        """for II in (point sources, background, diffuse): for IFREQ: launch (ASOC.py:1028-1545).
+        """for II in (point sources, background, diffuse): for IFREQ: launch (ASOC.py:1028-1545), in the order and batches of _plan.
         Returns CTABS[CELLS] and FABSORBED[CELLS,NFREQ] (or None with noabsorbed)."""
         U, e, c = self.U, self.eng, self.cloud
         CELLS, NFREQ, FFREQ = c.CELLS, self.NFREQ, self.FFREQ
@@ -357,205 +414,114 @@ class AbsorptionRun:
             n = e.set_roi_save(U.ROI, U.ROI_STEP, U.ROI_NSIDE)
             self.ROI_SAVE = files.create_roi_save(U.FILE_ROI_SAVE, U.ROI, U.ROI_STEP, U.ROI_NSIDE, NFREQ) if self.rank == 0 \
                 else np.zeros((NFREQ, n), np.float32)
-        # TABS-only runs (noabsorbed): nothing is read back per frequency and CTABS is the sum over the source blocks, so ALL
-        # launches of the constant sources are handed to the engine as one batch: on hierarchies walked brick-locally the
-        # point-source, background and diffuse launches of all frequencies share brick sweeps (include/soc_hip.h:
-        # soc_batch_begin; up to 128 launches per sweep), elsewhere the engine starts a new sweep where the kind changes.
-        one_batch = (not self.with_int) and (not U.WITH_ROI_SAVE) and U.ITERATIONS >= 1
-        # several ranks, shard == "launches": the launches themselves are dealt out (see __init__).  Runs that keep the per-frequency
-        # absorptions: a frequency belongs to one rank (not with the intensity file, region-of-interest records or emission iterations,
-        # which need every frequency on every rank -- those keep the work-item split)
-        shares, self.freq_owner = None, None
-        if self.shard == "launches" and self.comm and self.world > 1 and U.ITERATIONS >= 1:
-            own_freq = self.with_int
-            if (not own_freq) or (FABSORBED is not None and U.SAVE_INTENSITY == 0 and (not U.WITH_ROI_SAVE) and self.CLPAC < 1 and thin == 1):
-                shares, self.freq_owner = self._launch_shares(by_frequency=own_freq)
-        owned = self.freq_owner is not None
-        # Runs that keep the per-frequency absorptions on a hierarchy: frequency by frequency, the source blocks of a frequency in
-        # one sweep with one INT tally, so that its point-source, background and diffuse launches share brick sweeps and brick
-        # queues.  (Cartesian grids: the INT batches below; the intensity file, region-of-interest records and a Healpix sky keep
-        # the block-by-block loop.)
-        if (self.with_int and FABSORBED is not None and c.LEVELS > 1 and U.SAVE_INTENSITY == 0 and not U.WITH_ROI_SAVE
-                and not U.WITH_ROI_LOAD and len(self.HPBG) == 0 and U.ITERATIONS >= 1 and (shares is None or owned)):
-            return self._simulate_by_frequency(CTABS, FABSORBED, shares, owned, rng)
-        if one_batch:
+        segments, self.freq_owner = self._plan(FABSORBED is not None, thin)
+        for policy, name, steps in segments:
+            grouped = policy in (self.FREQ_GROUPS, self.LAUNCH_GROUPS)
+            per_batch = self.FREQS_PER_SWEEP if policy == self.FREQ_GROUPS else 16
             e.zero(0)
-            e.batch_begin(0)
-        for II in range(4):
-            L = self._constant_launch(II)
-            if U.ITERATIONS < 1 or L is None:
-                continue
-            self.log("=== %s  GLOBAL %d x BATCH %d = %d" % (['PS', 'BG', 'DE', 'ROI'][II], L["GLOBAL"], L["BATCH"], L["PACKETS"]))
-            first, count = self.comm.shard(L["GLOBAL"]) if self.comm else (0, L["GLOBAL"])
-            if not one_batch:
-                e.zero(0)
-            # runs that keep the per-frequency absorptions, Cartesian grids: up to 16 frequencies per batch, every launch
-            # a group with its own INT tally, read after the batch -- and summed over the ranks then, on its way to the host array.
-            # (Hierarchies: one launch at a time; with `global` large enough each is a brick sweep of its own, the INT
-            # tally in LDS beside TABS -- DESIGN.md.)
-            int_batched = (self.with_int and FABSORBED is not None and self.ROI_SAVE is None and II != 3 and c.LEVELS == 1
-                           and U.SAVE_INTENSITY == 0)
-            group = []
-
-            def end_group():
-                e.batch_end()
-                for k, f in enumerate(group):
-                    arr = e.batch_read_int(k)
-                    if self.comm and self.world > 1 and not owned:
-                        arr = self.comm.all_reduce_host(arr)
-                    FABSORBED[:, f] += arr[0::self.absthin]
-                del group[:]
-            if int_batched:
-                e.batch_begin_int_groups(16)
-            for IFREQ in range(NFREQ):
-                FREQ = float(FFREQ[IFREQ])
-                if (FREQ < U.SIM_F[0]) or (FREQ > U.SIM_F[1]):
-                    continue
+            if policy == self.ONE_BATCH:
+                e.batch_begin(0)
+            elif policy == self.LAUNCH_GROUPS:
+                e.batch_begin_int_groups(per_batch)
+            shown, pend = set(), []
+            for IFREQ, launches, summed in steps:
+                for II, L, _, _ in launches:
+                    if II not in shown:
+                        shown.add(II)
+                        self.log("=== %s  GLOBAL %d x BATCH %d = %d" % (['PS', 'BG', 'DE', 'ROI'][II], L["GLOBAL"], L["BATCH"], L["PACKETS"]))
                 t0 = time.time()
-                ABS, SCA = self._optical_for(IFREQ)
-                if self.with_int and not int_batched:
+                ABS, _ = self._optical_for(IFREQ)
+                if self.with_int and policy == self.SEQUENTIAL:
                     e.zero(1)
                 self._scatter_tables_for(IFREQ)
                 seed = self._seed(IFREQ, rng)
-                if shares is not None:
-                    first, count = shares.get((II, IFREQ), (0, 0))
-                    if count == 0:
-                        continue                          # another rank's launch
+                mine = [m for m in launches if m[3] > 0]
+                if not mine and not summed:
+                    continue                                   # another rank's launches
                 if self.ROI_SAVE is not None:
-                    e.roi_zero()                                   # per frequency (ASOC.py:1301-1302)
-                if int_batched:
+                    e.roi_zero()                               # per frequency (ASOC.py:1301-1302)
+                if policy == self.FREQ_GROUPS and not pend:
+                    e.batch_begin_int_groups(per_batch)
+                if grouped:
                     e.batch_next_int()
                 self.timers["Tpush"] += time.time() - t0
-                w = self._launch(II, L, IFREQ, seed, first, count)
-                if w is None:
-                    continue
+                sent = [self._launch(II, L, IFREQ, seed, first, count) for II, L, first, count in mine]
+                sent = [w for w in sent if w is not None]
+                if not sent and not summed:
+                    continue                                   # nothing to send at this frequency
+                if grouped:
+                    pend.append((IFREQ, len(sent) > 0, summed))
+                    if len(pend) >= per_batch:
+                        self._read_int_groups(pend, FABSORBED, policy == self.FREQ_GROUPS)
+                        if policy == self.LAUNCH_GROUPS:
+                            e.batch_begin_int_groups(per_batch)
+                else:
+                    t0 = time.time()
+                    if self.with_int and summed:
+                        self.comm.all_reduce_tally(e, 1)      # one all-reduce of the per-cell buffer per frequency
+                    if policy == self.SEQUENTIAL:
+                        e.sync()
+                    self.timers["Tkernel"] += time.time() - t0
+                    t0 = time.time()
+                    if FABSORBED is not None or U.SAVE_INTENSITY > 0:
+                        TMP = e.read_tally(1)
+                        if FABSORBED is not None:
+                            FABSORBED[:, IFREQ] += TMP[0::thin]
+                        if U.SAVE_INTENSITY > 0:
+                            self._save_intensity(IFREQ, float(FFREQ[IFREQ]), ABS, TMP)
+                    if self.ROI_SAVE is not None:
+                        # += : point sources, background and a loaded record all pass here; GL^2 scales away the
+                        # dependence on the current grid length (ASOC.py:1466-1475)
+                        rec = e.roi_read()
+                        if summed:
+                            rec = self.comm.all_reduce_host(rec)
+                        self.ROI_SAVE[IFREQ, :] += rec * np.float32(U.GL * U.GL)
+                    self.timers["Tpull"] += time.time() - t0
+                if self.verbose and self.rank == 0 and sent:
+                    FF, BG, PS = sent[0]
+                    if policy == self.FREQ_GROUPS:
+                        print("  FREQ %3d/%3d  %10.3e   TW %10.3e" % (IFREQ + 1, NFREQ, FFREQ[IFREQ], FF))
+                    else:
+                        print("  FREQ %3d/%3d  %10.3e   BG %12.4e  PS %12.4e   TW %10.3e" % (IFREQ + 1, NFREQ, FFREQ[IFREQ], BG, PS[0], FF))
+            if pend or policy == self.LAUNCH_GROUPS:
+                self._read_int_groups(pend, FABSORBED, policy == self.FREQ_GROUPS)
+            if policy == self.ONE_BATCH:
                 t0 = time.time()
-                if self.with_int and self.comm and not int_batched and not owned:
-                    self.comm.all_reduce_tally(e, 1)      # one all-reduce of the per-cell buffer per frequency
-                if int_batched:
-                    group.append(IFREQ)
-                    if len(group) == 16:
-                        end_group()
-                        e.batch_begin_int_groups(16)
-                elif not one_batch:
-                    e.sync()
+                e.batch_end()
+                e.sync()
                 self.timers["Tkernel"] += time.time() - t0
-                t0 = time.time()
-                if (FABSORBED is not None or U.SAVE_INTENSITY > 0) and not int_batched:
-                    TMP = e.read_tally(1)
-                    if FABSORBED is not None:
-                        FABSORBED[:, IFREQ] += TMP[0::self.absthin]
-                    if U.SAVE_INTENSITY > 0:
-                        self._save_intensity(IFREQ, FREQ, ABS, TMP)
-                if self.ROI_SAVE is not None:
-                    # += : point sources, background and a loaded record all pass here; GL^2 scales away the
-                    # dependence on the current grid length (ASOC.py:1466-1475)
-                    rec = e.roi_read()
-                    if self.comm:
-                        rec = self.comm.all_reduce_host(rec)
-                    self.ROI_SAVE[IFREQ, :] += rec * np.float32(U.GL * U.GL)
-                self.timers["Tpull"] += time.time() - t0
-                if self.verbose and self.rank == 0:
-                    FF, BG, PS = w
-                    print("  FREQ %3d/%3d  %10.3e   BG %12.4e  PS %12.4e   TW %10.3e" % (
-                        IFREQ + 1, NFREQ, FREQ, BG, PS[0], FF))
-            if int_batched:
-                t0 = time.time()
-                end_group()
-                self.timers["Tkernel"] += time.time() - t0
-            if one_batch:
-                continue                                   # the tally is read once, after the last block
             if self.comm:
-                self.comm.all_reduce_tally(e, 0)          # TABS: integrated over frequency on the device
+                self.comm.all_reduce_tally(e, 0)              # TABS: integrated over frequency (and the segment's blocks) on the device
             t0 = time.time()
             CTABS += e.read_tally(0)
             self.timers["Tpull"] += time.time() - t0
-            self.log("******  CONSTANT   %10s   CTABS -> %12.4e" % (['PS', 'BG', 'DE', 'ROI'][II], float(np.mean(CTABS))))
-        if one_batch:
-            t0 = time.time()
-            e.batch_end()
-            e.sync()
-            self.timers["Tkernel"] += time.time() - t0
-            if self.comm:
-                self.comm.all_reduce_tally(e, 0)          # ONE all-reduce of TABS for all source blocks
-            t0 = time.time()
-            CTABS += e.read_tally(0)
-            self.timers["Tpull"] += time.time() - t0
-            self.log("******  CONSTANT   all source blocks   CTABS -> %12.4e" % float(np.mean(CTABS)))
+            self.log("******  CONSTANT   %10s   CTABS -> %12.4e" % (name, float(np.mean(CTABS))))
         if self.ROI_LOAD is not None:
             e.set_roi_load(None, 0, None)
         if isinstance(self.ROI_SAVE, np.memmap):
             self.ROI_SAVE.flush()
         return CTABS, FABSORBED
 
-    # Frequencies of an absorbed-file run on a hierarchy that share a sweep (an INT tally and, for cell emission, a copy of the emission each).
-    # Measured on config 3 (bench.py --workload C3INT --int-groups 4): 2.00e8 packets/s against 2.09e8 with one frequency per sweep -- the
-    # brick queues are per frequency (a workgroup's LDS tallies belong to one INT array), so more frequencies mean more queues of the same
-    # length, not longer ones; the default stays 1.
-    FREQS_PER_SWEEP = 1
-
-    def _simulate_by_frequency(self, CTABS, FABSORBED, shares, owned, rng):
-        """for IFREQ: for II in (point sources, background, diffuse): launch -- the loop of ASOC.py:1028-1545 with the frequency
-        outside, for runs that keep the per-frequency absorptions: the launches of one frequency are a group with one INT tally
-        (soc_batch_begin_int_groups / soc_batch_next_int), up to FREQS_PER_SWEEP groups are deferred into one sweep -- that many
-        times the packets per brick and pass -- and their tallies read after it.  TABS integrates over everything on the device and
-        is read once (CTABS is the sum over the blocks anyway)."""
-        U, e, c = self.U, self.eng, self.cloud
-        NFREQ, FFREQ = self.NFREQ, self.FFREQ
-        pend = []
-
-        def end_sweep():
-            t0 = time.time()
-            e.batch_end()
-            e.sync()
-            self.timers["Tkernel"] += time.time() - t0
-            t0 = time.time()
-            for k, f in enumerate(pend):
-                arr = e.batch_read_int(k)
-                if self.comm and self.world > 1 and not owned:
-                    arr = self.comm.all_reduce_host(arr)      # the per-cell buffer of one frequency, summed over the ranks
-                FABSORBED[:, f] += arr[0::self.absthin]
-            self.timers["Tpull"] += time.time() - t0
-            del pend[:]
-        blocks = [(II, self._constant_launch(II)) for II in range(3)]
-        blocks = [(II, L) for II, L in blocks if L is not None]
-        for II, L in blocks:
-            self.log("=== %s  GLOBAL %d x BATCH %d = %d" % (['PS', 'BG', 'DE'][II], L["GLOBAL"], L["BATCH"], L["PACKETS"]))
-        e.zero(0)
-        for IFREQ in range(NFREQ):
-            FREQ = float(FFREQ[IFREQ])
-            if (FREQ < U.SIM_F[0]) or (FREQ > U.SIM_F[1]):
-                continue
-            t0 = time.time()
-            self._optical_for(IFREQ)
-            self._scatter_tables_for(IFREQ)
-            seed = self._seed(IFREQ, rng)
-            mine = [(II, L) + ((0, L["GLOBAL"]) if shares is None else shares.get((II, IFREQ), (0, 0))) for II, L in blocks]
-            if shares is None and self.comm:
-                mine = [(II, L) + self.comm.shard(L["GLOBAL"]) for II, L in blocks]
-            mine = [m for m in mine if m[3] > 0]
-            if not mine:
-                continue                                  # another rank's frequency
-            if not pend:
-                e.batch_begin_int_groups(self.FREQS_PER_SWEEP)
-            e.batch_next_int()
-            self.timers["Tpush"] += time.time() - t0
-            for II, L, first, count in mine:
-                self._launch(II, L, IFREQ, seed, first, count)
-            pend.append(IFREQ)
-            if len(pend) >= self.FREQS_PER_SWEEP:
-                end_sweep()
-            if self.verbose and self.rank == 0:
-                print("  FREQ %3d/%3d  %10.3e   TW %10.3e" % (IFREQ + 1, NFREQ, FREQ, np.float32(launch.trapezoid_weight(FFREQ, IFREQ))))
-        if pend:
-            end_sweep()
-        if self.comm:
-            self.comm.all_reduce_tally(e, 0)              # TABS: integrated over frequency and source blocks on the device
+    def _read_int_groups(self, pend, FABSORBED, sync):
+        """End the batch of INT groups pend = [(IFREQ, launched, summed)] and add each group's tally to FABSORBED: summed over the
+        ranks where the plan says so, zeros where this rank launched nothing in the group (the group has no tally slot)."""
+        e = self.eng
         t0 = time.time()
-        CTABS += e.read_tally(0)
+        e.batch_end()
+        if sync:
+            e.sync()
+        self.timers["Tkernel"] += time.time() - t0
+        t0 = time.time()
+        slot = 0
+        for IFREQ, launched, summed in pend:
+            arr = np.zeros(self.cloud.CELLS, np.float32)
+            if launched:
+                arr, slot = e.batch_read_int(slot), slot + 1
+            if summed:
+                arr = self.comm.all_reduce_host(arr)
+            FABSORBED[:, IFREQ] += arr[0::self.absthin]
+        del pend[:]
         self.timers["Tpull"] += time.time() - t0
-        self.log("******  CONSTANT   all source blocks   CTABS -> %12.4e" % float(np.mean(CTABS)))
-        return CTABS, FABSORBED
 
     # ---------------------------------------------------------------------------------
     def emission_iterations(self, CTABS, FABSORBED):
@@ -622,7 +588,7 @@ class AbsorptionRun:
                 skip = U.EMWEIGHT_SKIP - 1
                 # TABS-only iterations: the frequencies are handed to the engine together; with `global` raised to
                 # about the number of cells they share brick sweeps (include/soc_hip.h: soc_batch_begin, soc_sim_cl)
-                deferred = (not self.with_int) and (not ali) and U.USE_EMWEIGHT < 2 and hasattr(e, "batch_begin")
+                deferred = (not self.with_int) and (not ali) and U.USE_EMWEIGHT < 2
                 if deferred:
                     e.batch_begin(0)
                 for IFREQ in range(NFREQ):
@@ -914,13 +880,13 @@ class AbsorptionRun:
         CTABS, FABSORBED = self.simulate_constant_sources()
         U = self.U
         self.TNEW, self.EMITTED = None, None
-        if U.ITERATIONS > 0 and (self.CLPAC > 0 or ((not U.NOSOLVE) and U.NOABSORBED)) and hasattr(self.eng, "solve_temperature"):
+        if U.ITERATIONS > 0 and (self.CLPAC > 0 or ((not U.NOSOLVE) and U.NOABSORBED)):
             self.TNEW, self.EMITTED = self.emission_iterations(CTABS, FABSORBED)
-        elif U.LOAD_TEMPERATURE and U.ITERATIONS < 1 and hasattr(self.eng, "emission"):
+        elif U.LOAD_TEMPERATURE and U.ITERATIONS < 1:
             self.TNEW, self.EMITTED = self.emission_from_temperature_file()
-        if (not U.NOMAP) and self.EMITTED is not None and hasattr(self.eng, "map"):
+        if (not U.NOMAP) and self.EMITTED is not None:
             self.write_maps(self.EMITTED)
-        if U.NO_PS > 0 and U.pssavetau_freq > 0.0 and U.NPIX[1] > 0 and hasattr(self.eng, "ps_tau"):
+        if U.NO_PS > 0 and U.pssavetau_freq > 0.0 and U.NPIX[1] > 0:
             self.write_ps_tau()
         if self.rank == 0 and self.INTENSITY is not None:          # ASOC.py:2733-2757
             files.finish_intensity_file(U.SAVE_INTENSITY_FILE, self.INTENSITY, self.cloud.CELLS, self.NFREQ, U.SAVE_INTENSITY == 2)
@@ -928,13 +894,13 @@ class AbsorptionRun:
         if self.rank == 0:
             if len(U.file_constant_save) > 0:
                 CTABS.tofile(U.file_constant_save)                 # ASOC.py:1547-1549
-            if FABSORBED is not None and getattr(self, "freq_owner", None) is None:
+            if FABSORBED is not None and self.freq_owner is None:
                 files.scale_absorbed(FABSORBED, self.cloud, U.GL, U.NNNLIMIT, self.absthin)
                 files.write_absorbed(U.file_absorbed, FABSORBED)   # ASOC.py:2866-2875
             elif FABSORBED is None:
                 prefix = U.KEYS.get('prefix', ['soc'])[0] if U.KEYS.get('prefix') else 'soc'
                 CTABS.tofile(prefix + ".ctabs")
-        if FABSORBED is not None and getattr(self, "freq_owner", None) is not None:
+        if FABSORBED is not None and self.freq_owner is not None:
             # every rank holds the columns of the frequencies it simulated and writes them itself: no collective (as a2e.run_sharded)
             files.scale_absorbed(FABSORBED, self.cloud, U.GL, U.NNNLIMIT, self.absthin)
             if self.rank == 0:

@@ -29,6 +29,8 @@ from .launch import PLANCK, PARSEC, Fix
 
 
 class ScatteringRun(AbsorptionRun):
+    _hpbg_launch = staticmethod(launch.hpbg_sca_launch)       # the Healpix background's launch shape (ASOCS.py), see _constant_launch
+
     def _load_inputs(self):
         super()._load_inputs()
         U, c = self.U, self.cloud
@@ -80,21 +82,12 @@ class ScatteringRun(AbsorptionRun):
         e.set_features(with_int=0, ps_method=U.PS_METHOD, use_emweight=min(max(U.USE_EMWEIGHT, 0), 1))
         e.set_mirror(launch.mirror_mask(U.MIRROR))
         if self.WITH_ABU:
-            if U.OPT_IS_HALF or hasattr(e, "set_opt_half"):
-                e.set_opt_half(bool(U.OPT_IS_HALF))            # ASOCS.py:524-525
+            e.set_opt_half(bool(U.OPT_IS_HALF))                # ASOCS.py:524-525
             e.set_abundances(self.ABU)                         # once; OPT per frequency on the device (ASOCS.py:519-523)
         if self.healpix:
             e.sca_set_healpix(U.OUT_NSIDE, U.INTOBS, U.FFS)
-            npix = 12 * U.OUT_NSIDE * U.OUT_NSIDE
         else:
             e.sca_set_view(self.ODIR, self.RA, self.DE, U.NPIX, U.MAP_DX, U.MAPCENTRE, U.FFS)
-            npix = self.NDIR * U.NPIX[0] * U.NPIX[1]
-        # The frequencies of a source block are ONE batch with an image each (soc_sca_batch_images): the launches that can run as rays on
-        # brick-local hierarchies are deferred and share sweeps (many more rays per brick and pass than one launch has), the others run
-        # at once into their frequency's image.  Several ranks then add the images up once per block, on the host.
-        self.batched = hasattr(e, "sca_batch_images")
-        if self.comm and not self.batched:
-            self.comm.attach_image(e, npix)
 
     def _update_emwei(self, IFREQ):
         """Packets per cell from the emission, every third frequency (ASOCS.py:546-595)."""
@@ -124,31 +117,16 @@ class ScatteringRun(AbsorptionRun):
             seed = self._bcast_seed(seed)
         return seed
 
-    def _collect(self, OUTCOMING, IFREQ):
-        if self.batched:
-            self._launched.append(IFREQ)                          # read after the batch (_end_block)
-            return
-        t0 = time.time()
-        OUT = self.comm.all_reduce_image(self.eng) if self.comm else self.eng.sca_read_out()
-        OUTCOMING[IFREQ] += OUT
-        self.timers["Tpull"] += time.time() - t0
-
+    # The frequencies of a source block are ONE batch with an image each (soc_sca_batch_images): the launches that can run as rays on
+    # brick-local hierarchies are deferred and share sweeps (many more rays per brick and pass than one launch has), the others run
+    # at once into their frequency's image.  Several ranks then add the images up once per block, on the host.
     def _begin_block(self, max_launches=0):
         """max_launches: cell-emission launches keep a copy of the emission each (8 B per cell), so their batches are shorter"""
-        self._launched = []
-        if self.batched:
-            self.eng.batch_begin(max_launches)
-            self.eng.sca_batch_images(self.NFREQ)
-
-    def _begin_frequency(self, IFREQ):
-        if self.batched:
-            self.eng.sca_batch_select(IFREQ)
-        else:
-            self.eng.sca_zero()
+        self._launched = []                                        # the frequencies launched, read after the batch (_end_block)
+        self.eng.batch_begin(max_launches)
+        self.eng.sca_batch_images(self.NFREQ)
 
     def _end_block(self, OUTCOMING):
-        if not self.batched:
-            return
         t0 = time.time()
         self.eng.batch_end()
         self.eng.sync()
@@ -172,22 +150,10 @@ class ScatteringRun(AbsorptionRun):
             np.zeros((NFREQ, self.NDIR, U.NPIX[1], U.NPIX[0]), np.float32)
         EMIT = np.zeros(CELLS, np.float32)
         for II in range(3):                                        # ASOCS.py:428-723
-            WPS = WBG = 0.0
-            if II == 0:
-                if (self.PSPAC < 1) or (U.NO_PS < 1):
-                    continue
-                L = launch.ps_launch(self.PSPAC, U.NO_PS, U.GL, self.GLOBAL_0)
-                WPS = L["WPS"]
-            elif II == 1:
-                if self.BGPAC < 1:
-                    continue
-                L = launch.hpbg_sca_launch(self.BGPAC, c.NX, c.NY, c.NZ) if len(self.HPBG) > 0 else \
-                    launch.bg_launch(self.BGPAC, int(U.AREA))
-                WBG = L["WBG"]
-            else:
-                if len(self.DIFFUSERAD) < 1 or self.DFPAC < 1:
-                    continue
-                L = dict(GLOBAL=self.GLOBAL_0, BATCH=int(self.DFPAC / CELLS), PACKETS=self.DFPAC)
+            L = self._constant_launch(II)
+            if L is None:
+                continue
+            WPS, WBG = L.get("WPS", 0.0), L.get("WBG", 0.0)
             self.log("=== II=%d  GLOBAL %d, BATCH %d, PACKETS %d" % (II, L["GLOBAL"], L["BATCH"], L["PACKETS"]))
             first, count = self.comm.shard(L["GLOBAL"]) if self.comm else (0, L["GLOBAL"])
             self._skip = 2
@@ -197,7 +163,7 @@ class ScatteringRun(AbsorptionRun):
                 if (FREQ < U.SIM_F[0]) or (FREQ > U.SIM_F[1]):
                     continue
                 t0 = time.time()
-                self._begin_frequency(IFREQ)
+                e.sca_batch_select(IFREQ)
                 self._optical_for(IFREQ)
                 BG = np.float32(float(self.IBG[IFREQ]) * WBG / FREQ) if len(self.IBG) == NFREQ else np.float32(0.0)
                 PS = (self.LPS[:, IFREQ] * np.float32(WPS)) / np.float32(FREQ) if II == 0 else np.zeros(1, np.float32)
@@ -229,11 +195,9 @@ class ScatteringRun(AbsorptionRun):
                     e.sca_sim_pb(II, L["PACKETS"], L["BATCH"], seed, BG, GLOBAL=L["GLOBAL"], gid_first=first, gid_count=count)
                 else:
                     e.sca_sim_cl(II, L["PACKETS"], L["BATCH"], seed, L["GLOBAL"], gid_first=first, gid_count=count)
-                if not self.batched:
-                    e.sync()
                 self.timers["Tkernel"] += time.time() - t0
                 self.packets += L["PACKETS"]
-                self._collect(OUTCOMING, IFREQ)
+                self._launched.append(IFREQ)
                 if self.verbose and self.rank == 0:
                     print("  FREQ %3d/%3d  %10.3e --  BG %10.3e  PS %10.3e" % (IFREQ + 1, NFREQ, FREQ, BG, PS[0]))
             self._end_block(OUTCOMING)
@@ -247,7 +211,7 @@ class ScatteringRun(AbsorptionRun):
             self._begin_block(16)
             for IFREQ in range(NFREQ):
                 FREQ = float(FFREQ[IFREQ])
-                self._begin_frequency(IFREQ)
+                e.sca_batch_select(IFREQ)
                 if (FREQ < U.SIM_F[0]) or (FREQ > U.SIM_F[1]):
                     continue
                 if IFREQ < self.REMIT_I1 or IFREQ > self.REMIT_I2:
@@ -268,11 +232,9 @@ class ScatteringRun(AbsorptionRun):
                 self.timers["Tpush"] += time.time() - t0
                 t0 = time.time()
                 e.sca_sim_cl(2, self.CLPAC, BATCH, seed, GLOBAL, gid_first=first, gid_count=count)
-                if not self.batched:
-                    e.sync()
                 self.timers["Tkernel"] += time.time() - t0
                 self.packets += CELLS * BATCH
-                self._collect(OUTCOMING, IFREQ)
+                self._launched.append(IFREQ)
             self._end_block(OUTCOMING)
         return OUTCOMING
 

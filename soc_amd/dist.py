@@ -44,23 +44,17 @@ class Comm:
         """(first, count) of the logical work items this rank executes."""
         return shard_range(GLOBAL, self.rank, self.world)
 
-    def _engine_stream(self, engine):
-        """The engine runs on a stream torch created, and that stream is torch's current one: c10d orders its
-        collective behind the current stream and the current stream behind the collective, so tally kernels,
-        all-reduce and read-back run in program order.  (torch's default stream has the null handle, which
-        soc_set_stream reads as "the engine's own stream" -- a stream no collective is ordered with.)"""
-        t = self.torch
-        if self._stream is None:
-            self._stream = t.cuda.Stream()
-            t.cuda.set_stream(self._stream)
-        engine.set_stream(self._stream.cuda_stream)
-
     def attach(self, engine, cells):
-        """RCCL path: make the engine's tallies torch tensors so they are reduced in place, on a stream
-        shared with torch (see _engine_stream)."""
+        """RCCL path: make the engine's tallies torch tensors so they are reduced in place.  The engine runs on a stream
+        torch created, and that stream is torch's current one: c10d orders its collective behind the current stream and
+        the current stream behind the collective, so tally kernels, all-reduce and read-back run in program order.
+        (torch's default stream has the null handle, which soc_set_stream reads as "the engine's own stream" -- a stream
+        no collective is ordered with.)"""
         if self.world > 1 and self.backend == "nccl":
             t = self.torch
-            self._engine_stream(engine)
+            self._stream = t.cuda.Stream()
+            t.cuda.set_stream(self._stream)
+            engine.set_stream(self._stream.cuda_stream)
             for which in (0, 1):
                 buf = t.zeros(cells, dtype=t.float32, device="cuda")
                 engine.bind_tally(which, buf.data_ptr(), cells)
@@ -90,26 +84,6 @@ class Comm:
             t = t.cuda()
         self.dist.all_reduce(t)
         return t.cpu().numpy()
-
-    def attach_image(self, engine, npix):
-        """Same for the scattered-light image OUT[NDIR*NPIX_Y*NPIX_X]."""
-        if self.world > 1 and self.backend == "nccl":
-            t = self.torch
-            self._engine_stream(engine)
-            buf = t.zeros(npix, dtype=t.float32, device="cuda")
-            engine.sca_bind_out(buf.data_ptr())
-            self._tensors["out"] = buf
-
-    def all_reduce_image(self, engine):
-        """Sum the image over all ranks; returns it as a host array [NDIR, NPIX_Y, NPIX_X]."""
-        if self.world == 1:
-            return engine.sca_read_out()
-        if self.backend == "nccl":
-            self.dist.all_reduce(self._tensors["out"])
-            return engine.sca_read_out()
-        arr = self.torch.from_numpy(np.ascontiguousarray(engine.sca_read_out()))
-        self.dist.all_reduce(arr)
-        return arr.numpy()
 
     def barrier(self):
         if self.world > 1:

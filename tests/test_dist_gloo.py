@@ -197,6 +197,64 @@ def test_two_rank_roi_record_equals_single(tmp_path):
     assert np.allclose(both, single, rtol=1e-5, atol=1e-7 * single.max())
 
 
+def _single_then_two_ranks(d, ini, shard, port):
+    """Run ini in one process, move the files it wrote to d (abs.data, roi.save) into d/single, then run it on two gloo ranks
+    with `shard` (short timeout: a rank that misses a collective fails the test also where the transport would hang).
+    Returns the single process's CTABS."""
+    from oracle_engine import OracleEngine
+    from soc_amd.ini import User
+    from soc_amd.asoc import AbsorptionRun
+    for sub in ("r0", "r1", "single"):
+        os.makedirs(os.path.join(d, sub))
+    os.chdir(os.path.join(d, "single"))
+    C1, _ = AbsorptionRun(User(ini), OracleEngine("soc"), verbose=0).run()
+    for name in ("abs.data", "roi.save"):
+        if os.path.exists(os.path.join(d, name)):
+            os.rename(os.path.join(d, name), os.path.join(d, "single", name))
+    script = os.path.join(d, "worker.py")
+    with open(script, "w") as fp:
+        fp.write(WORKER.format(repo=REPO))
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
+    subprocess.check_call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
+                           "--master-addr", "127.0.0.1", "--master-port", str(port), script, ini, d, shard],
+                          env=env, timeout=120)
+    return C1
+
+
+def test_two_ranks_where_one_has_no_work_items_of_a_frequency(tmp_path):
+    """Absorbed file on a hierarchy, shard="items", launches of 64 work items: rank 1 has none of them, and still enters the
+    all-reduce of every frequency's INT tally (it adds zeros)"""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from test_host import _write_model
+    from soc_amd import synth, files
+    d = str(tmp_path)
+    ini = _write_model(d, synth.octree_cloud(6, levels=2, frac=0.1, seed=9), with_ps=True, with_diffuse=True,
+                       extra="global 64\nbgpackets 0\n")
+    C1 = _single_then_two_ranks(d, ini, "items", 29545)
+    for r in (0, 1):
+        C = np.load(os.path.join(d, "r%d" % r, "ctabs_rank%d.npy" % r))
+        assert np.allclose(C, C1, rtol=1e-5, atol=1e-7 * np.abs(C1).max())
+    F1 = files.read_absorbed(os.path.join(d, "single", "abs.data"))
+    A = files.read_absorbed(os.path.join(d, "abs.data"))
+    assert A.shape == F1.shape and (F1 > 0).any() and np.allclose(A, F1, rtol=1e-5, atol=1e-7 * np.abs(F1).max())
+
+
+def test_two_ranks_share_the_launches_of_a_roi_record(tmp_path):
+    """TABS-only run with roisave, shard="launches": a rank without work items in a launch still enters the all-reduce of
+    that frequency's ROI record, so both ranks sum the records of the same frequency"""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from test_host import _write_model
+    from soc_amd import synth
+    d = str(tmp_path)
+    ini = _write_model(d, synth.cartesian_cloud(8, seed=3),
+                       extra="gridlength 5e-7\nroi 2 5 2 5 3 4\nroisave %s/roi.save 1\nroinside 2\nnoabsorbed\n" % d)
+    _single_then_two_ranks(d, ini, "launches", 29547)
+    single = np.fromfile(os.path.join(d, "single", "roi.save"), np.float32, offset=20)
+    assert (single > 0).sum() > 100
+    both = np.fromfile(os.path.join(d, "roi.save"), np.float32, offset=20)
+    assert np.array_equal(both > 0, single > 0)
+    assert np.allclose(both, single, rtol=1e-5, atol=1e-7 * single.max())
+
 A2E_WORKER = r"""
 import os, sys
 sys.path.insert(0, {repo!r}); sys.path.insert(0, os.path.join({repo!r}, "tests"))
