@@ -64,31 +64,20 @@ struct soc_ctx {
     // tallies
     float *dTABS = nullptr, *dINT = nullptr;
     bool   own_TABS = false, own_INT = false;
-    // point-source scratch: slot 0 for immediate launches, one slot per deferred launch of a batch
-    struct SrcBuf {
-        float4 *PSPOS = nullptr;
-        float  *PS = nullptr, *XPS_AREA = nullptr;
-        int    *XPS_NSIDE = nullptr, *XPS_SIDE = nullptr;
-        int     cap = 0;
-    } src[SOC_MAXLAUNCH];
-    // deferred launches (soc_batch_begin .. soc_batch_end): executed together in one brick sweep
+    // deferred launches (soc_batch_begin .. soc_batch_end): executed together in one brick sweep (scattered light: one sweep of rays)
     bool   batching = false;
     int    batch_max = 4;
     std::vector<SocSim> pending;
-    bool   pending_sca = false;                               // the deferred launches are scattered-light ones (rays; soc_sca_sim_*)
-    float *dDSCslot[SOC_MAXLAUNCH] = {};                      // their discrete scattering functions
-    int    dsc_slot_bins = 0;
+    // Device copies of launch inputs, one buffer per store and launch slot (slot_buf): a deferred launch keeps in its slot what the
+    // caller overwrites for the next frequency; slot 0 also holds the point sources of a launch that runs at once.  SLOT_INT holds the
+    // INT tallies of a batch by group (soc_batch_read_int), SLOT_OPT one buffer in slot 0 (the sweep strides through it).  A buffer is
+    // allocated when its slot first needs more than it holds (128 slots of a 5e7-cell model up front would be 50 GB).
+    enum SlotStore { SLOT_SRC, SLOT_CSC, SLOT_DSC, SLOT_OPT, SLOT_EMIT, SLOT_HP, SLOT_INT, SLOT_STORES };
+    void  *slots[SLOT_STORES][SOC_MAXLAUNCH] = {};
+    size_t slot_bytes[SLOT_STORES][SOC_MAXLAUNCH] = {};
     float *dOUTslots = nullptr;                               // soc_sca_batch_images: several images, one per frequency of a batch
     int    out_slots = 0, out_slot_cur = 0;
     size_t out_slot_pixels = 0;
-    float *dCSCslot[SOC_MAXLAUNCH] = {};
-    float2 *dOPTslots = nullptr;                  // [SOC_OPT_SLOTS][CELLS] per-cell opacities of deferred launches (one buffer: the sweep strides through it)
-    float *dHPslots = nullptr;                    // [SOC_MAXLAUNCH][2][49152] Healpix skies of deferred SimRAM_HP launches
-    // EMIT | EMWEI copies of deferred SimRAM_CL launches and INT tallies of deferred launches (soc_batch_read_int): one buffer per
-    // launch slot, allocated when a batch first reaches that slot (128 slots of a 5e7-cell model up front would be 50 GB)
-    float *dEMITslot[SOC_MAXLAUNCH] = {};
-    float *dINTslot[SOC_MAXLAUNCH] = {};
-    size_t intslot_cells = 0;
     unsigned long long emit_gen = 0;              // bumped by soc_set_emission: launches deferred without a change in between share one copy
     unsigned long long emit_slot_gen = 0;
     int    emit_slot_last = -1;
@@ -96,13 +85,10 @@ struct soc_ctx {
     // the INT tally of the launches of a batch (set by the soc_batch_begin* call that opened it):
     //   INT_OFF        soc_batch_begin: launches with the INT tally are not deferred
     //   INT_SHARED     soc_batch_begin_shared_int: all tally into the handle's dINT
-    //   INT_PER_LAUNCH soc_batch_begin_int: every launch a zeroed slot of its own (dINTslot)
+    //   INT_PER_LAUNCH soc_batch_begin_int: every launch a zeroed slot of its own (SLOT_INT)
     //   INT_PER_GROUP  soc_batch_begin_int_groups: the launches up to the next soc_batch_next_int share a slot
     enum IntMode { INT_OFF, INT_SHARED, INT_PER_LAUNCH, INT_PER_GROUP } int_mode = INT_OFF;
     bool   int_group_open = false;                // INT_PER_GROUP: the current group has its slot
-    size_t emitslot_cells = 0;
-    size_t optslot_cells = 0;
-    int    csc_slot_bins = 0;
     // rng
     uint64_t *dSeedTab = nullptr;
     unsigned long long *dStats = nullptr;
@@ -157,6 +143,45 @@ static hipError_t dev_alloc(T **p, size_t n)
     return hipMalloc((void **)p, (n ? n : 1) * sizeof(T));
 }
 
+// Slot k of a store of copies (soc_ctx::slots), at least `bytes` large.  A larger buffer replaces a smaller one once the stream has
+// drained (a launch in flight may read the old one); the contents stay otherwise.
+template <typename T>
+static int slot_buf(soc_ctx *c, int store, int k, size_t bytes, T **out)
+{
+    void *&p = c->slots[store][k];
+    size_t &cap = c->slot_bytes[store][k];
+    if (bytes > cap) {
+        if (p) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            (void)hipFree(p);
+            p = nullptr;  cap = 0;
+        }
+        HIPCHK(c, hipMalloc(&p, bytes));
+        cap = bytes;
+    }
+    *out = (T *)p;
+    return SOC_OK;
+}
+
+// A deferred launch's own copy of na floats of the handle at a (and of nb more at b, right behind them) in slot k of a store
+// (a null a: the slot only)
+static int slot_copy(soc_ctx *c, int store, int k, float **out, const float *a, size_t na, const float *b = nullptr, size_t nb = 0)
+{
+    int r = slot_buf(c, store, k, (na + nb) * 4, out);
+    if (r) return r;
+    if (a) HIPCHK(c, hipMemcpyAsync(*out, a, na * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (b) HIPCHK(c, hipMemcpyAsync(*out + na, b, nb * 4, hipMemcpyDeviceToDevice, c->stream));
+    return SOC_OK;
+}
+
+static void release_slots(soc_ctx *c)
+{
+    for (auto &store : c->slots)
+        for (void *&p : store)
+            if (p) { (void)hipFree(p);  p = nullptr; }
+    memset(c->slot_bytes, 0, sizeof c->slot_bytes);
+}
+
 // number of floats of the scattered-light image: NDIR maps of NPIX_X x NPIX_Y pixels, or one Healpix map
 static size_t view_pixels(const soc_ctx *c)
 {
@@ -174,61 +199,54 @@ static bool lt_capable(const soc_ctx *c, bool abu) { return soc_brick_local(c->G
 #define SOC_SCA_RAYS_LAUNCH 4000000
 #define SOC_LT_LONE_LAUNCH 1000000                           // work items from which a lone launch goes to the sweep there
 
-// One absorption launch through the direct kernel of its kind (SOURCE 4 and 5 mark Healpix and cell-emission launches for the
-// brick sweep; the direct kernels take them as 1 and 2)
+// One launch through the direct kernel of its kind (SOURCE 4 and 5 mark Healpix and cell-emission launches for the brick sweep; the
+// direct kernels take them as 1 and 2).  A scattered-light launch adds to its own image; soc_last_variant reports absorption kernels only.
 static int run_direct(soc_ctx *c, SocSim S, const SocVariant &V)
 {
     c->last.passes = 0;
-    if (S.gid_count > 0)                    // (the launch wrappers run nothing without work items; Cartesian grids take the float kernels)
-        c->last.variant = soc_variant_code(soc_grid_plan(0, soc_source_kind(S.SOURCE), V));
-    if (S.SOURCE == SOC_SOURCE_HP) {
-        S.SOURCE = 1;
-        HIPCHK(c, soc_launch_sim_hp(c->G, S, V, c->stream));
-    } else if (S.SOURCE == SOC_SOURCE_CL) {
-        S.SOURCE = 2;
-        HIPCHK(c, soc_launch_sim_cl(c->G, S, V, c->stream));
-    } else {
-        HIPCHK(c, soc_launch_sim_pb(c->G, S, V, c->stream));
+    const int kind = soc_source_kind(S.SOURCE);
+    if (kind) S.SOURCE = kind;
+    if (S.SCAKIND) {
+        SocSca X = c->view;
+        X.kind = S.SCAKIND - 1;  X.DSC = S.DSC;  X.OUT = S.OUT;
+        HIPCHK(c, soc_launch_sca(c->G, S, X, V, c->stream));
+        return SOC_OK;
     }
+    if (S.gid_count > 0)                    // (the launch wrappers run nothing without work items; Cartesian grids take the float kernels)
+        c->last.variant = soc_variant_code(soc_grid_plan(0, kind, V));
+    if (kind == 1)      HIPCHK(c, soc_launch_sim_hp(c->G, S, V, c->stream));
+    else if (kind == 2) HIPCHK(c, soc_launch_sim_cl(c->G, S, V, c->stream));
+    else                HIPCHK(c, soc_launch_sim_pb(c->G, S, V, c->stream));
     return SOC_OK;
 }
 
-// Execute the launches deferred since soc_batch_begin: one brick sweep for all of them.
+// Execute the launches deferred since soc_batch_begin: one brick sweep for all of them (scattered light: one sweep of rays).  They run
+// through the direct kernel instead when that is as fast -- a lone absorption launch on a hierarchy (1.9e10 vs 2.0e10 steps/s at 256^3,
+// 4 levels), scattered-light launches with too few rays to fill the brick queues -- and scattered-light launches also where the sweep
+// does not apply (it did when they were deferred: the grid has not changed since).
 static int flush_pending(soc_ctx *c)
 {
     if (c->pending.empty()) return SOC_OK;
     std::vector<SocSim> todo;
     todo.swap(c->pending);
-    SocVariant V = soc_grid_variant(c->G);
-    if (c->pending_sca) {
-        // deferred launches of the scattered-light kernels: one sweep of rays for all of them; where the sweep does not apply
-        // (it did when they were deferred: the grid has not changed since) each runs through the direct kernel
-        c->pending_sca = false;
-        HIPCHK(c, hipSetDevice(c->device));
-        SocSca X = c->view;
-        X.kind = todo[0].SCAKIND - 1;  X.DSC = todo[0].DSC;  X.OUT = todo[0].OUT;
-        unsigned long long items = 0;
-        for (const SocSim &S1 : todo) items += S1.gid_count;
-        hipError_t e = hipErrorNotSupported;
-        if (c->exec_mode == 1 || items >= SOC_SCA_RAYS_LAUNCH)     // (too few rays to fill the brick queues: the direct kernel, launch by launch)
-            e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, c->tune, c->stream, &c->last, &X);
-        if (e == hipErrorNotSupported) {
-            for (SocSim &S1 : todo) {
-                X.kind = S1.SCAKIND - 1;  X.DSC = S1.DSC;  X.OUT = S1.OUT;
-                if (S1.SOURCE == SOC_SOURCE_CL) S1.SOURCE = 2;
-                HIPCHK(c, soc_launch_sca(c->G, S1, X, V, c->stream));
-            }
-            return SOC_OK;
+    const bool rays = todo[0].SCAKIND != 0;
+    // what made the launches deferrable (see route_sim)
+    const SocVariant V = soc_grid_variant(c->G, todo[0].OPT != nullptr, (!rays && c->int_mode != soc_ctx::INT_OFF) ? c->with_int : 0);
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long items = 0;
+    for (const SocSim &S : todo) items += S.gid_count;
+    const bool direct = rays ? (c->exec_mode != 1 && items < SOC_SCA_RAYS_LAUNCH)
+                             : (V.octree && todo.size() == 1 && c->exec_mode < 0 && !(lt_capable(c, V.abu != 0) && items >= SOC_LT_LONE_LAUNCH));
+    hipError_t e = hipErrorNotSupported;
+    if (!direct)
+        e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, c->tune, c->stream, &c->last, rays ? &c->view : nullptr);
+    if (direct || (rays && e == hipErrorNotSupported)) {
+        for (const SocSim &S : todo) {
+            int r = run_direct(c, S, V);
+            if (r) return r;
         }
-        if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "sweep of the rays of %d deferred scattered-light launches failed: %s", (int)todo.size(), hipGetErrorString(e));
         return SOC_OK;
     }
-    V.abu = todo[0].OPT != nullptr;                          // what makes a launch deferrable (see route_sim)
-    V.wint = c->int_mode != soc_ctx::INT_OFF ? c->with_int : 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (V.octree && todo.size() == 1 && c->exec_mode < 0 && !(lt_capable(c, V.abu != 0) && todo[0].gid_count >= SOC_LT_LONE_LAUNCH))
-        return run_direct(c, todo[0], V);      // a single launch on a hierarchy: the direct kernel is as fast (1.9e10 vs 2.0e10 steps/s at 256^3, 4 levels)
-    hipError_t e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, c->tune, c->stream, &c->last);
     if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep of %d deferred launches failed: %s", (int)todo.size(), hipGetErrorString(e));
     return SOC_OK;
 }
@@ -311,16 +329,8 @@ void soc_destroy(soc_ctx *c)
     (void)flush_pending(c);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto &b : c->src) {
-        void *sb[] = { b.PSPOS, b.PS, b.XPS_AREA, b.XPS_NSIDE, b.XPS_SIDE };
-        for (void *q : sb) if (q) (void)hipFree(q);
-    }
-    for (float *q : c->dCSCslot) if (q) (void)hipFree(q);
-    for (float *q : c->dDSCslot) if (q) (void)hipFree(q);
-    if (c->dOUTslots) (void)hipFree(c->dOUTslots);
-    for (float *q : c->dEMITslot) if (q) (void)hipFree(q);
-    for (float *q : c->dINTslot) if (q) (void)hipFree(q);
-    void *bufs[] = { c->dHPslots, c->dOPTslots, c->dABU, c->dAF, c->dRoi, c->dRoiSave, c->dRoiLoad, c->dDENS, c->dPAR, c->dCSC, c->dDSC, c->dOPT, c->dEMIT, c->dEMWEI, c->dXAB, c->dINTV, c->dEMINDEX, c->dSeedTab, c->dStats, c->dODIR, c->dORA, c->dODE, c->dHPBG, c->dHPBGP, c->dT, c->dTTT, c->dEbuf, c->dEF, c->dMapEmit, c->dMap, c->dMapTau,
+    release_slots(c);
+    void *bufs[] = { c->dOUTslots, c->dABU, c->dAF, c->dRoi, c->dRoiSave, c->dRoiLoad, c->dDENS, c->dPAR, c->dCSC, c->dDSC, c->dOPT, c->dEMIT, c->dEMWEI, c->dXAB, c->dINTV, c->dEMINDEX, c->dSeedTab, c->dStats, c->dODIR, c->dORA, c->dODE, c->dHPBG, c->dHPBGP, c->dT, c->dTTT, c->dEbuf, c->dEF, c->dMapEmit, c->dMap, c->dMapTau,
                      c->aIw, c->aTdown, c->aEA, c->aAF, c->aABS, c->aEMIT, c->aAll, c->aSum, c->aFirst, c->aLast, c->aIwOff, c->aDst, c->aIbeg };
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (c->own_TABS && c->dTABS) (void)hipFree(c->dTABS);
@@ -738,7 +748,6 @@ static void fill_sim(soc_ctx *c, SocSim &S, SocVariant &V, int SOURCE, int BATCH
 static int upload_sources(soc_ctx *c, const char *who, SocSim &S, const float *PSPOS, const float *PS, int NO_PS,
                           const int32_t *XPS_NSIDE, const int32_t *XPS_SIDE, const float *XPS_AREA, bool xps_as_float, int slot = 0)
 {
-    soc_ctx::SrcBuf &B = c->src[slot];
     if (NO_PS < 1 || !PSPOS || !PS) return fail(c, SOC_ERR_ARG, "%s: point sources need PSPOS, PS and NO_PS>=1", who);
     if ((c->ps_method == 2 || c->ps_method == 5) && (!XPS_NSIDE || !XPS_SIDE || !XPS_AREA))
         return fail(c, SOC_ERR_ARG, "%s: PS_METHOD %d needs XPS_NSIDE/XPS_SIDE/XPS_AREA", who, c->ps_method);
@@ -757,111 +766,184 @@ static int upload_sources(soc_ctx *c, const char *who, SocSim &S, const float *P
         for (auto &v : nside) { float f;  memcpy(&f, &v, 4);  v = (f * 0.999999f < 1.0f) ? 0 : (int32_t)f; }
         for (auto &v : side)  { float f;  memcpy(&f, &v, 4);  v = (int32_t)f; }
     }
-    if (NO_PS > B.cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_alloc(&B.PSPOS, (size_t)NO_PS));
-        HIPCHK(c, dev_alloc(&B.PS, (size_t)NO_PS));
-        HIPCHK(c, dev_alloc(&B.XPS_NSIDE, (size_t)NO_PS));
-        HIPCHK(c, dev_alloc(&B.XPS_SIDE, (size_t)3 * NO_PS));
-        HIPCHK(c, dev_alloc(&B.XPS_AREA, (size_t)3 * NO_PS));
-        B.cap = NO_PS;
-    }
-    HIPCHK(c, hipMemcpyAsync(B.PSPOS, PSPOS, (size_t)NO_PS * 16, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(B.PS, PS, (size_t)NO_PS * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(B.XPS_NSIDE, nside.data(), (size_t)NO_PS * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(B.XPS_SIDE, side.data(), (size_t)NO_PS * 12, hipMemcpyHostToDevice, c->stream));
-    if (XPS_AREA)  HIPCHK(c, hipMemcpyAsync(B.XPS_AREA, XPS_AREA, (size_t)NO_PS * 12, hipMemcpyHostToDevice, c->stream));
-    else           HIPCHK(c, hipMemsetAsync(B.XPS_AREA, 0, (size_t)NO_PS * 12, c->stream));
+    // the slot holds PSPOS [NO_PS] float4 | PS [NO_PS] | XPS_NSIDE [NO_PS] | XPS_SIDE [3 NO_PS] | XPS_AREA [3 NO_PS]
+    const size_t n = (size_t)NO_PS;
+    char *p = nullptr;
+    int r = slot_buf(c, soc_ctx::SLOT_SRC, slot, 48 * n, &p);
+    if (r) return r;
+    float4 *pspos = (float4 *)p;
+    float  *ps = (float *)(p + 16 * n), *area = (float *)(p + 36 * n);
+    int    *xnside = (int *)(p + 20 * n), *xside = (int *)(p + 24 * n);
+    HIPCHK(c, hipMemcpyAsync(pspos, PSPOS, n * 16, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ps, PS, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(xnside, nside.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(xside, side.data(), n * 12, hipMemcpyHostToDevice, c->stream));
+    if (XPS_AREA)  HIPCHK(c, hipMemcpyAsync(area, XPS_AREA, n * 12, hipMemcpyHostToDevice, c->stream));
+    else           HIPCHK(c, hipMemsetAsync(area, 0, n * 12, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     S.NO_PS = NO_PS;
-    S.PSPOS = B.PSPOS; S.PS = B.PS;
-    S.XPS_NSIDE = B.XPS_NSIDE; S.XPS_SIDE = B.XPS_SIDE; S.XPS_AREA = B.XPS_AREA;
+    S.PSPOS = pspos; S.PS = ps;
+    S.XPS_NSIDE = xnside; S.XPS_SIDE = xside; S.XPS_AREA = area;
     return SOC_OK;
 }
 
-static int snapshot_inputs(soc_ctx *c, SocSim &S, const SocVariant &V, int slot);
 #define SOC_OPT_SLOTS 16        // launches with per-cell opacities per sweep (8 B per cell and launch, in one buffer)
 
 static bool int_slots(const soc_ctx *c) { return c->int_mode == soc_ctx::INT_PER_LAUNCH || c->int_mode == soc_ctx::INT_PER_GROUP; }
 
-// INT slot modes: the next launch of the batch -- deferred or not -- tallies INT into the current group's slot, or into a new, zeroed one
+// INT slot modes: the next launch of the batch with an INT tally -- deferred or not -- tallies INT into the current group's slot, or
+// into a new, zeroed one (a scattered-light launch tallies nothing but its image: no S.INT)
 static int take_int_slot(soc_ctx *c, const char *who, SocSim &S)
 {
-    if (!(c->batching && int_slots(c) && c->with_int)) return SOC_OK;
+    if (!(c->batching && int_slots(c) && c->with_int && S.INT)) return SOC_OK;
     if (c->int_mode == soc_ctx::INT_PER_GROUP && c->int_group_open) {     // a further launch of the current group: the group's tally
-        S.INT = c->dINTslot[c->int_slots_done - 1];
+        S.INT = (float *)c->slots[soc_ctx::SLOT_INT][c->int_slots_done - 1];
         return SOC_OK;
     }
     if (c->int_slots_done >= c->batch_max)
         return fail(c, SOC_ERR_STATE, "%s: %d launches of this batch hold an INT tally; soc_batch_end and soc_batch_read_int first", who, c->batch_max);
     const size_t cells = (size_t)c->G.CELLS;
-    if (c->intslot_cells != cells) {                       // another grid: the slots are re-made as they are reached
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (float *&q : c->dINTslot) if (q) { (void)hipFree(q);  q = nullptr; }
-        c->intslot_cells = cells;
-    }
-    if (!c->dINTslot[c->int_slots_done]) HIPCHK(c, dev_alloc(&c->dINTslot[c->int_slots_done], cells));
-    S.INT = c->dINTslot[c->int_slots_done];
+    int r = slot_buf(c, soc_ctx::SLOT_INT, c->int_slots_done, cells * 4, &S.INT);
+    if (r) return r;
     c->int_group_open = true;
     HIPCHK(c, hipMemsetAsync(S.INT, 0, cells * 4, c->stream));
     c->int_slots_done++;
     return SOC_OK;
 }
 
-// a sweep runs one kernel variant: its launches are all SimRAM_PB, all _HP or all _CL ones, all with or all without per-cell opacities
-// ... except on brick-local hierarchies, where the walk and the event workgroups take the kind from the launch: there the
-// point-source, background, Healpix and cell-emission launches of a TABS-only run share one sweep
-static bool same_sweep(const soc_ctx *c, int source, bool abu)
+// What a deferred launch keeps in its slot besides its SocSim and its kind's own inputs (route_sim's slot_inputs): the scattering
+// table, a scattered-light launch's discrete scattering function and, with abundances, the per-cell opacities (the caller overwrites
+// them for the next frequency)
+static int keep_inputs(soc_ctx *c, SocSim &S, const SocVariant &V, int slot)
 {
-    if (c->pending.empty()) return true;
-    if (c->pending_sca) return false;                        // deferred scattered-light launches: another kind of sweep
-    const SocSim &P = c->pending[0];
-    if ((P.OPT != nullptr) != abu) return false;
-    return soc_source_kind(P.SOURCE) == soc_source_kind(source) || lt_capable(c, abu);      // (brick-local hierarchies: the kinds share sweeps, also with per-group INT tallies)
+    float *csc = nullptr, *dsc = nullptr;
+    int r = slot_copy(c, soc_ctx::SLOT_CSC, slot, &csc, c->dCSC, c->BINS);
+    if (!r && S.DSC) r = slot_copy(c, soc_ctx::SLOT_DSC, slot, &dsc, c->have_dsc ? c->dDSC : nullptr, c->BINS);
+    if (r) return r;
+    S.CSC = csc;
+    if (S.DSC) S.DSC = dsc;
+    if (V.abu) {                                            // the per-cell opacities: a slot of one buffer
+        if (slot >= SOC_OPT_SLOTS) return fail(c, SOC_ERR_STATE, "a batch holds at most %d launches with per-cell opacities", SOC_OPT_SLOTS);
+        const size_t cells = (size_t)c->G.CELLS;
+        float2 *opt = nullptr;
+        r = slot_buf(c, soc_ctx::SLOT_OPT, 0, SOC_OPT_SLOTS * cells * 8, &opt);
+        if (r) return r;
+        S.OPT = opt + (size_t)slot * cells;
+        HIPCHK(c, hipMemcpyAsync(opt + (size_t)slot * cells, c->dOPT, cells * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return SOC_OK;
 }
 
-static int snapshot_emission(soc_ctx *c, SocSim &S, int slot);
+// slot_inputs of SimRAM_HP launches (absorption or scattered light): a deferred one keeps its own copy of the sky (the caller sets the
+// next frequency's)
+static int keep_sky(soc_ctx *c, SocSim &S, int slot)
+{
+    if (slot < 0) return SOC_OK;
+    float *sky = nullptr;
+    int r = slot_copy(c, soc_ctx::SLOT_HP, slot, &sky, c->dHPBG, SOC_HPBG_PIX, c->dHPBGP, SOC_HPBG_PIX);
+    S.HPBG = sky;  S.HPBGP = sky + SOC_HPBG_PIX;
+    return r;
+}
 
-// The kinds of absorption launch and what sets them apart on the way to a kernel (the eligibility terms: route_sim)
-enum SimKind { SIM_PB, SIM_HP, SIM_CL };
+// slot_inputs of cell-emission launches: a deferred one keeps its own copy of EMIT | EMWEI (the caller uploads the next frequency's);
+// the copy of an earlier launch serves when soc_set_emission has not been called since
+static int keep_emission(soc_ctx *c, SocSim &S, int slot)
+{
+    if (slot < 0) return SOC_OK;
+    const size_t cells = (size_t)c->G.CELLS;
+    if (!(c->emit_slot_last >= 0 && c->emit_slot_last < slot && c->emit_slot_gen == c->emit_gen)) {
+        float *em = nullptr;
+        int r = slot_copy(c, soc_ctx::SLOT_EMIT, slot, &em, c->dEMIT, cells, c->dEMWEI, cells);
+        if (r) return r;
+        c->emit_slot_last = slot;  c->emit_slot_gen = c->emit_gen;
+    }
+    const float *em = (const float *)c->slots[soc_ctx::SLOT_EMIT][c->emit_slot_last];
+    S.EMIT = em;  S.EMWEI = em + cells;
+    return SOC_OK;
+}
+
+// A sweep holds launches of one family: absorption, or scattered light (rays: brick-local hierarchies, where all kinds share one).  An
+// absorption sweep runs one kernel variant: its launches are all SimRAM_PB, all _HP or all _CL ones, all with or all without per-cell
+// opacities ... except on brick-local hierarchies, where the walk and the event workgroups take the kind from the launch: there the
+// point-source, background, Healpix and cell-emission launches of a TABS-only run share one sweep
+static bool same_sweep(const soc_ctx *c, const SocSim &S, bool abu)
+{
+    if (c->pending.empty()) return true;
+    const SocSim &P = c->pending[0];
+    if ((P.SCAKIND != 0) != (S.SCAKIND != 0) || (P.OPT != nullptr) != abu) return false;
+    return soc_source_kind(P.SOURCE) == soc_source_kind(S.SOURCE) || lt_capable(c, abu);      // (brick-local hierarchies: the kinds share sweeps, also with per-group INT tallies)
+}
+
+// The kinds of launch and what sets them apart on the way to a kernel (use_sweep, route_sim)
+enum SimKind { SIM_PB, SIM_HP, SIM_CL, SCA_PB, SCA_CL, SCA_PS, SCA_HP };
 static const struct {
     const char *who;
-    long long   min_items;              // automatic mode: work items from which the brick sweep pays
-    const char *not_applicable;         // what keeps soc_set_exec(1) from the brick sweep
-} sim_kinds[3] = {
-    { "soc_sim_pb", 65536,  "mirror, with_int 2, roisave/roiload, > 15 levels or > 2^18 bricks" },
-    { "soc_sim_hp", 65536,  "mirror, with_int 2, > 15 levels or > 2^18 bricks" },
-    { "soc_sim_cl", 262144, "mirror, with_int 2, USE_EMWEIGHT 2, ALI, roisave, > 15 levels or > 2^18 bricks" },
+    int         scakind;                // SocSim::SCAKIND: SOC_SCA_* + 1 for the scattered-light kernels (run as rays); 0 absorption
+    long long   min_items;              // absorption, automatic mode: work items from which the brick sweep pays
+    const char *not_applicable;         // absorption: what keeps soc_set_exec(1) from the brick sweep
+} sim_kinds[] = {
+    { "soc_sim_pb", 0, 65536,  "mirror, with_int 2, roisave/roiload, > 15 levels or > 2^18 bricks" },
+    { "soc_sim_hp", 0, 65536,  "mirror, with_int 2, > 15 levels or > 2^18 bricks" },
+    { "soc_sim_cl", 0, 262144, "mirror, with_int 2, USE_EMWEIGHT 2, ALI, roisave, > 15 levels or > 2^18 bricks" },
+    { "soc_sca_sim_pb", SOC_SCA_PB + 1, 0, nullptr },
+    { "soc_sca_sim_cl", SOC_SCA_CL + 1, 0, nullptr },
+    { "soc_sca_sim_ps", SOC_SCA_PS + 1, 0, nullptr },
+    { "soc_sca_sim_hp", SOC_SCA_HP + 1, 0, nullptr },
 };
 
-// Route an absorption launch, after the checks of its soc_sim_* call and fill_sim: the brick sweep or the direct kernel, now or
-// deferred into the open batch.  items: the work items the thresholds count.  slot_inputs(slot) stores the kind's own inputs of
-// the launch: slot >= 0 the launch is deferred and keeps them in that slot, -1 it runs now.
-static int route_sim(soc_ctx *c, SimKind kind, SocSim &S, const SocVariant &V, long long items, const std::function<int(int)> &slot_inputs)
+// Whether a launch goes to a sweep: the brick sweep, or for scattered light the sweep of rays on brick-local hierarchies (soc_brick.hip:
+// soc_sca_events), which takes flat and Healpix images and every kind of launch (the kind only changes the event lane) with scalar
+// opacities and one scattering function.  *why: what keeps soc_set_exec(1) from it, nullptr when nothing does.  batch: the open batch
+// takes the launch.  Automatic mode also asks for enough work items to fill the chip.  Absorption counts the launch's (items).
+// Hierarchies: the brick sweep pays from two launches per sweep on (256^3 roots, 4 levels: 1.9e10 steps/s with one launch, 2.8e10 with
+// two, 4.4e10 with eight; direct kernel 2.0e10), so there only launches of a batch use it (see flush_pending) -- and, on brick-local
+// hierarchies, a lone launch with enough work items.  Rays: the launches of a batch are deferred and flush_pending counts those of their
+// sweep; a lone launch counts its own.
+static bool use_sweep(const soc_ctx *c, SimKind kind, const SocVariant &V, long long items, bool batch, const char **why)
 {
-    const char *who = sim_kinds[kind].who;
+    if (sim_kinds[kind].scakind) {
+        *why = (!c->have_view || c->view.NDIR == 0) ? "no view"
+             : (c->msf_ndust > 1) ? "several scattering functions (WITH_MSF) need the direct kernel"
+             : (c->dOPT != nullptr) ? "per-cell opacities need the direct kernel"
+             : (!lt_capable(c, false) || c->device >= 16) ? "the hierarchy is not one the brick-local walk takes (2-8 levels, Index() in double)"
+             : nullptr;
+        return c->exec_mode != 0 && !*why && (c->exec_mode == 1 || batch || items >= SOC_SCA_RAYS_LAUNCH);
+    }
     const bool lt = lt_capable(c, V.abu != 0);
     const int B = 1 << c->brick_log2;
     const long long nb = (long long)((c->G.NX + B - 1) / B) * ((c->G.NY + B - 1) / B) * ((c->G.NZ + B - 1) / B);
-    // the open batch takes the launch with its INT tally (soc_batch_begin: only launches without one)
-    const bool int_batch = c->batching && (!V.wint || c->int_mode != soc_ctx::INT_OFF);
     // the brick sweep applies: mirror, with_int 2 and region-of-interest records need the brick-local sweep (packets of a loaded
     // record, SOURCE 3: any sweep); cell emission also needs USE_EMWEIGHT 0/1 and, with ALI, the brick-local sweep without with_int 2
-    bool bricks = c->exec_mode != 0 && nb <= (1 << 18) && c->G.LEVELS <= 15 && c->device < 16
-                  && (c->mirror == 0 || lt) && (c->with_int != 2 || lt)
-                  && (kind == SIM_HP || !c->roi.save || (lt && c->mirror == 0))
-                  && (kind != SIM_CL || (c->use_emweight != 2 && (!c->with_ali || (lt && c->with_int != 2))));
-    // automatic mode: enough work items to fill the chip.  Hierarchies: the sweep pays from two launches per sweep on (256^3 roots,
-    // 4 levels: 1.9e10 steps/s with one launch, 2.8e10 with two, 4.4e10 with eight; direct kernel 2.0e10), so there only launches
-    // of a batch use it (see flush_pending) -- and, on brick-local hierarchies, a lone launch with enough work items
-    if (c->exec_mode < 0)
-        bricks = bricks && items >= sim_kinds[kind].min_items && nb >= 8 && (!V.octree || int_batch || (lt && items >= SOC_LT_LONE_LAUNCH));
-    if (c->exec_mode == 1 && !bricks)
-        return fail(c, SOC_ERR_ARG, "%s: brick sweep requested but not applicable (%s)", who, sim_kinds[kind].not_applicable);
-    // inside soc_batch_begin/end a brick launch is deferred: its per-launch inputs are snapshotted and it runs with the others.
-    // Not with_int 2 in the INT slot modes; not WITH_MSF (per-species tables are not snapshotted)
-    const bool defer = int_batch && bricks && !(int_slots(c) && V.wint == 2) && c->msf_ndust <= 1;
-    if (!defer || !same_sweep(c, S.SOURCE, V.abu != 0)) FLUSH(c);
+    const bool ok = nb <= (1 << 18) && c->G.LEVELS <= 15 && c->device < 16
+                    && (c->mirror == 0 || lt) && (c->with_int != 2 || lt)
+                    && (kind == SIM_HP || !c->roi.save || (lt && c->mirror == 0))
+                    && (kind != SIM_CL || (c->use_emweight != 2 && (!c->with_ali || (lt && c->with_int != 2))));
+    *why = ok ? nullptr : sim_kinds[kind].not_applicable;
+    return c->exec_mode != 0 && ok
+           && (c->exec_mode == 1 || (items >= sim_kinds[kind].min_items && nb >= 8 && (!V.octree || batch || (lt && items >= SOC_LT_LONE_LAUNCH))));
+}
+
+// Route a launch, after the checks of its soc_sim_* or soc_sca_sim_* call and fill_sim: a sweep or the direct kernel, now or deferred
+// into the open batch.  items: the work items the thresholds count.  slot_inputs(slot) stores the kind's own inputs of the launch:
+// slot >= 0 the launch is deferred and keeps them in that slot, -1 it runs now.
+static int route_sim(soc_ctx *c, SimKind kind, SocSim &S, const SocVariant &V, long long items, const std::function<int(int)> &slot_inputs)
+{
+    const char *who = sim_kinds[kind].who;
+    // the open batch takes the launch with its INT tally (soc_batch_begin: only launches without one)
+    const bool batch = c->batching && (!V.wint || c->int_mode != soc_ctx::INT_OFF);
+    const char *why = nullptr;
+    const bool sweep = use_sweep(c, kind, V, items, batch, &why);
+    if (c->exec_mode == 1 && !sweep) {
+        if (S.SCAKIND) {
+            c->last.passes = 0;                             // (a refused scattered-light launch reports no sweep)
+            return fail(c, SOC_ERR_ARG, "%s: brick sweep requested but not applicable: %s", who, why);
+        }
+        return fail(c, SOC_ERR_ARG, "%s: brick sweep requested but not applicable (%s)", who, why);
+    }
+    // inside soc_batch_begin/end a launch that goes to a sweep is deferred: its per-launch inputs are kept in its slot and it runs with
+    // the others.  Not with_int 2 in the INT slot modes; not WITH_MSF (per-species tables are not kept)
+    const bool defer = batch && sweep && !(int_slots(c) && V.wint == 2) && c->msf_ndust <= 1;
+    if (!defer || !same_sweep(c, S, V.abu != 0)) FLUSH(c);
     int r = take_int_slot(c, who, S);
     if (r) return r;
     const int slot = defer ? (int)c->pending.size() : -1;
@@ -869,16 +951,19 @@ static int route_sim(soc_ctx *c, SimKind kind, SocSim &S, const SocVariant &V, l
     if (r) return r;
     c->last.passes = 0;
     if (defer) {
-        r = snapshot_inputs(c, S, V, slot);
+        r = keep_inputs(c, S, V, slot);
         if (r) return r;
         c->pending.push_back(S);
-        if ((!int_slots(c) && (int)c->pending.size() >= (V.abu ? std::min(c->batch_max, SOC_OPT_SLOTS) : c->batch_max))
-            || (int)c->pending.size() >= SOC_MAXLAUNCH) FLUSH(c);      // (with INT tallies per launch or group: a sweep's worth of launches)
+        // a sweep's worth of launches (with INT tallies per launch or group, take_int_slot holds the batch to batch_max)
+        const int full = (int_slots(c) && S.INT) ? SOC_MAXLAUNCH : V.abu ? std::min(c->batch_max, SOC_OPT_SLOTS) : c->batch_max;
+        if ((int)c->pending.size() >= full) FLUSH(c);
         return SOC_OK;
     }
-    if (!bricks) return run_direct(c, S, V);
-    hipError_t e = soc_brick_run_pb(c->device, c->G, &S, 1, V, c->brick_log2, c->tune, c->stream, &c->last);
-    if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep failed: %s", hipGetErrorString(e));
+    if (!sweep) return run_direct(c, S, V);
+    hipError_t e = soc_brick_run_pb(c->device, c->G, &S, 1, V, c->brick_log2, c->tune, c->stream, &c->last, S.SCAKIND ? &c->view : nullptr);
+    if (e == hipErrorNotSupported && S.SCAKIND && c->exec_mode != 1)
+        return run_direct(c, S, V);                         // rays: the direct kernel where the sweep does not apply after all
+    if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "%s: brick sweep failed: %s", who, hipGetErrorString(e));
     return SOC_OK;
 }
 
@@ -947,7 +1032,7 @@ int soc_batch_read_int(soc_ctx *c, int k, float *out, long n)
     if (k < 0 || k >= c->int_slots_done) return fail(c, SOC_ERR_ARG, "soc_batch_read_int: launch %d of %d deferred with the INT tally", k, c->int_slots_done);
     if (!out || n != (long)c->G.CELLS) return fail(c, SOC_ERR_ARG, "soc_batch_read_int: the tally has %d cells, buffer %ld", c->G.CELLS, n);
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->dINTslot[k], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->slots[soc_ctx::SLOT_INT][k], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SOC_OK;
 }
@@ -1080,42 +1165,6 @@ int soc_set_roi_load(soc_ctx *c, const int32_t *DIM, int ROI_NSIDE, const float 
     return roi_upload(c);
 }
 
-// what a deferred launch needs besides its SocSim: its own copies of the scattering table and, with abundances,
-// of the per-cell opacities (the caller overwrites both for the next frequency)
-static int snapshot_inputs(soc_ctx *c, SocSim &S, const SocVariant &V, int slot)
-{
-    if (c->csc_slot_bins != c->BINS) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; k < SOC_MAXLAUNCH; k++) HIPCHK(c, dev_alloc(&c->dCSCslot[k], (size_t)c->BINS));
-        c->csc_slot_bins = c->BINS;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->dCSCslot[slot], c->dCSC, (size_t)c->BINS * 4, hipMemcpyDeviceToDevice, c->stream));
-    S.CSC = c->dCSCslot[slot];
-    if (V.abu) {                                            // the per-cell opacities of this launch: slot of one buffer
-        if (slot >= SOC_OPT_SLOTS) return fail(c, SOC_ERR_STATE, "a batch holds at most %d launches with per-cell opacities", SOC_OPT_SLOTS);
-        const size_t cells = (size_t)c->G.CELLS;
-        if (c->optslot_cells != cells) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, dev_alloc(&c->dOPTslots, cells * SOC_OPT_SLOTS));
-            c->optslot_cells = cells;
-        }
-        HIPCHK(c, hipMemcpyAsync(c->dOPTslots + (size_t)slot * cells, c->dOPT, cells * 8, hipMemcpyDeviceToDevice, c->stream));
-        S.OPT = c->dOPTslots + (size_t)slot * cells;
-    }
-    return SOC_OK;
-}
-
-// a deferred SimRAM_HP launch (absorption or scattered light) keeps its own copy of the sky: the caller sets the next frequency's
-static int snapshot_hpbg(soc_ctx *c, SocSim &S, int slot)
-{
-    if (!c->dHPslots) HIPCHK(c, dev_alloc(&c->dHPslots, (size_t)SOC_MAXLAUNCH * 2 * SOC_HPBG_PIX));
-    float *sky = c->dHPslots + (size_t)slot * 2 * SOC_HPBG_PIX;
-    HIPCHK(c, hipMemcpyAsync(sky, c->dHPBG, SOC_HPBG_PIX * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sky + SOC_HPBG_PIX, c->dHPBGP, SOC_HPBG_PIX * 4, hipMemcpyDeviceToDevice, c->stream));
-    S.HPBG = sky;  S.HPBGP = sky + SOC_HPBG_PIX;
-    return SOC_OK;
-}
-
 int soc_sim_hp(soc_ctx *c, int PACKETS, int BATCH, float SEED, float TW, int GLOBAL, int gid_first, int gid_count)
 {
     (void)PACKETS;
@@ -1129,32 +1178,7 @@ int soc_sim_hp(soc_ctx *c, int PACKETS, int BATCH, float SEED, float TW, int GLO
     fill_sim(c, S, V, 1, BATCH, SEED, 0.0f, TW, GLOBAL, gid_first, gid_count);
     S.NO_PS = 1;
     S.SOURCE = SOC_SOURCE_HP;          // the brick sweep as for soc_sim_pb: the walk is SimRAM_PB's, only the creation of a packet differs
-    return route_sim(c, SIM_HP, S, V, gid_count, [&](int slot) { return slot < 0 ? SOC_OK : snapshot_hpbg(c, S, slot); });
-}
-
-// a deferred cell-emission launch keeps its own copy of the emission (and of the packet weights): the caller uploads the next frequency's
-static int snapshot_emission(soc_ctx *c, SocSim &S, int slot)
-{
-    const size_t cells = (size_t)c->G.CELLS;
-    if (c->emitslot_cells != cells) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (float *&q : c->dEMITslot) if (q) { (void)hipFree(q);  q = nullptr; }
-        c->emitslot_cells = cells;
-        c->emit_slot_last = -1;
-    }
-    // (the copy of an earlier launch of this batch serves when soc_set_emission has not been called since)
-    int es = slot;
-    if (c->emit_slot_last >= 0 && c->emit_slot_last < slot && c->emit_slot_gen == c->emit_gen) {
-        es = c->emit_slot_last;
-    } else {
-        if (!c->dEMITslot[slot]) HIPCHK(c, dev_alloc(&c->dEMITslot[slot], cells * 2));
-        HIPCHK(c, hipMemcpyAsync(c->dEMITslot[slot], c->dEMIT, cells * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->dEMITslot[slot] + cells, c->dEMWEI, cells * 4, hipMemcpyDeviceToDevice, c->stream));
-        c->emit_slot_last = slot;  c->emit_slot_gen = c->emit_gen;
-    }
-    float *em = c->dEMITslot[es];
-    S.EMIT = em;  S.EMWEI = em + cells;
-    return SOC_OK;
+    return route_sim(c, SIM_HP, S, V, gid_count, [&](int slot) { return keep_sky(c, S, slot); });
 }
 
 int soc_sim_cl(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, float TW,
@@ -1180,12 +1204,24 @@ int soc_sim_cl(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, float
     // the direct kernel (1.5e10 steps/s at C2, the rate of the fabric atomics) stays; `global` in the ini file
     // raises it.  Host-listed cells (USE_EMWEIGHT 2), ALI and region-of-interest records: direct kernel.
     const long long inflight = std::min<long long>((long long)gid_first + gid_count, c->G.CELLS) - gid_first;
-    return route_sim(c, SIM_CL, S, V, inflight, [&](int slot) { return slot < 0 ? SOC_OK : snapshot_emission(c, S, slot); });
+    return route_sim(c, SIM_CL, S, V, inflight, [&](int slot) { return keep_emission(c, S, slot); });
 }
 
 // ------------------------------------------------------------------------------------
 // scattered-light images (ASOCS.py / kernel_ASOC_sca.c)
 // ------------------------------------------------------------------------------------
+
+// The image of a new view, npix values (the old one's: old): the library's own is made anew (zeroed) when the size changes; a
+// caller-owned one stays bound only at the same size
+static int view_image(soc_ctx *c, const char *who, size_t npix, size_t old)
+{
+    if (c->dOUT && npix == old) return SOC_OK;
+    if (c->dOUT && !c->own_OUT) return fail(c, SOC_ERR_STATE, "%s: image size changed while a caller-owned image is bound", who);
+    HIPCHK(c, dev_alloc(&c->dOUT, npix));
+    c->own_OUT = true;
+    HIPCHK(c, hipMemsetAsync(c->dOUT, 0, npix * 4, c->stream));
+    return SOC_OK;
+}
 
 int soc_sca_set_view(soc_ctx *c, int NDIR, const float *ODIR, const float *RA, const float *DE,
                      int NPIX_X, int NPIX_Y, float MAP_DX, const float *CENTRE, int FFS)
@@ -1214,16 +1250,8 @@ int soc_sca_set_view(soc_ctx *c, int NDIR, const float *ODIR, const float *RA, c
         HIPCHK(c, dev_alloc(&c->dORA, (size_t)NDIR));
         HIPCHK(c, dev_alloc(&c->dODE, (size_t)NDIR));
     }
-    if (npix != old || !c->dOUT) {
-        if (!c->own_OUT && c->dOUT && npix != old)
-            return fail(c, SOC_ERR_STATE, "soc_sca_set_view: image size changed while a caller-owned image is bound");
-        if (c->own_OUT || !c->dOUT) {
-            c->dOUT = nullptr;
-            HIPCHK(c, dev_alloc(&c->dOUT, npix));
-            c->own_OUT = true;
-            HIPCHK(c, hipMemsetAsync(c->dOUT, 0, npix * 4, c->stream));
-        }
-    }
+    int r = view_image(c, "soc_sca_set_view", npix, old);
+    if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));            // launches in flight still read the previous view
     HIPCHK(c, hipMemcpy(c->dODIR, ODIR, (size_t)NDIR * 16, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->dORA, RA, (size_t)NDIR * 16, hipMemcpyHostToDevice));
@@ -1252,16 +1280,8 @@ int soc_sca_set_healpix(soc_ctx *c, int NSIDE, const float *OBSERVER, int FFS)
         HIPCHK(c, dev_alloc(&c->dORA, (size_t)1));
         HIPCHK(c, dev_alloc(&c->dODE, (size_t)1));
     }
-    if (npix != old || !c->dOUT) {
-        if (!c->own_OUT && c->dOUT && npix != old)
-            return fail(c, SOC_ERR_STATE, "soc_sca_set_healpix: image size changed while a caller-owned image is bound");
-        if (c->own_OUT || !c->dOUT) {
-            c->dOUT = nullptr;
-            HIPCHK(c, dev_alloc(&c->dOUT, npix));
-            c->own_OUT = true;
-            HIPCHK(c, hipMemsetAsync(c->dOUT, 0, npix * 4, c->stream));
-        }
-    }
+    int r = view_image(c, "soc_sca_set_healpix", npix, old);
+    if (r) return r;
     const float obs[4] = { OBSERVER[0], OBSERVER[1], OBSERVER[2], 0.0f };
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(c->dODIR, obs, 16, hipMemcpyHostToDevice));
@@ -1283,82 +1303,23 @@ int soc_sca_zero(soc_ctx *c)
     return SOC_OK;
 }
 
-// Rays on brick-local hierarchies (soc_brick.hip: soc_sca_events) take flat and Healpix images and every kind of launch (PB, PS, CL,
-// HP alike: the kind only changes the event lane), with scalar opacities and one scattering function.  What keeps the launches of the
-// current state off the sweep, or nullptr when they can run there.
-static const char *sca_rays_refusal(const soc_ctx *c)
+// fill_sim for a launch of the scattered-light kernels, after the checks of its soc_sca_sim_* call: the checks they share, the image it
+// adds to (soc_sca_batch_select's, else the view's) and its discrete scattering function; the rays tally nothing else
+static int fill_sca(soc_ctx *c, SimKind kind, SocSim &S, SocVariant &V, int SOURCE, int BATCH, float SEED, float BG,
+                    int GLOBAL, int gid_first, int gid_count)
 {
-    if (!c->have_view || c->view.NDIR == 0) return "no view";
-    if (c->msf_ndust > 1) return "several scattering functions (WITH_MSF) need the direct kernel";
-    if (c->dOPT != nullptr) return "per-cell opacities need the direct kernel";
-    if (!lt_capable(c, false) || c->device >= 16) return "the hierarchy is not one the brick-local walk takes (2-8 levels, Index() in double)";
-    return nullptr;
-}
-static bool sca_rays_ok(const soc_ctx *c) { return sca_rays_refusal(c) == nullptr; }
-
-// Start of a soc_sca_sim_* call: inside soc_batch_begin/end a launch that can run as rays is deferred -- the slot its inputs are
-// kept in is returned -- and runs with the others of the batch in one sweep; otherwise (-1) what is pending runs first.
-static int sca_begin(soc_ctx *c, int *slot)
-{
-    *slot = -1;
-    const bool defer = c->batching && c->exec_mode != 0 && sca_rays_ok(c);
-    if (!defer || !c->pending_sca || (int)c->pending.size() >= c->batch_max) FLUSH(c);
-    if (defer) *slot = (int)c->pending.size();
-    return SOC_OK;
-}
-
-static int sca_launch(soc_ctx *c, const char *who, int kind, SocSim &S, SocVariant &V, int slot)
-{
+    const char *who = sim_kinds[kind].who;
+    const int k = sim_kinds[kind].scakind - 1;
     if (!c->have_view) return fail(c, SOC_ERR_STATE, "%s: call soc_sca_set_view first", who);
-    if (kind != SOC_SCA_CL && kind != SOC_SCA_HP && !c->have_dsc) return fail(c, SOC_ERR_STATE, "%s: soc_set_scatter_table was called without DSC", who);
+    if (k != SOC_SCA_CL && k != SOC_SCA_HP && !c->have_dsc) return fail(c, SOC_ERR_STATE, "%s: soc_set_scatter_table was called without DSC", who);
     if (c->BINS > 8000) return fail(c, SOC_ERR_ARG, "%s: BINS=%d > 8000", who, c->BINS);
-    SocSca X = c->view;
-    X.kind = kind;
-    X.DSC = c->dDSC;
-    X.OUT = c->out_slots ? c->dOUTslots + (size_t)c->out_slot_cur * c->out_slot_pixels : c->dOUT;
+    HIPCHK(c, hipSetDevice(c->device));
+    fill_sim(c, S, V, SOURCE, BATCH, SEED, BG, 0.0f, GLOBAL, gid_first, gid_count);
+    S.NO_PS = 1;
     S.TABS = nullptr;  S.INT = nullptr;
-    S.SCAKIND = kind + 1;  S.DSC = X.DSC;  S.OUT = X.OUT;
-    c->last.passes = 0;  c->last.form = 0;
-    const bool rays_ok = sca_rays_ok(c);
-    if (c->exec_mode == 1 && !rays_ok)
-        return fail(c, SOC_ERR_ARG, "%s: brick sweep requested but not applicable: %s", who, sca_rays_refusal(c));
-    if (slot >= 0) {
-        // deferred: the launch keeps its own copies of the scattering functions (and of the emission; the point sources are in their slot already)
-        SocVariant W = V;
-        W.abu = 0;
-        int r = snapshot_inputs(c, S, W, slot);
-        if (r) return r;
-        if (c->dsc_slot_bins != c->BINS) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (int k = 0; k < SOC_MAXLAUNCH; k++) HIPCHK(c, dev_alloc(&c->dDSCslot[k], (size_t)c->BINS));
-            c->dsc_slot_bins = c->BINS;
-        }
-        if (c->have_dsc) HIPCHK(c, hipMemcpyAsync(c->dDSCslot[slot], c->dDSC, (size_t)c->BINS * 4, hipMemcpyDeviceToDevice, c->stream));
-        S.DSC = c->dDSCslot[slot];
-        if (kind == SOC_SCA_CL) {
-            r = snapshot_emission(c, S, slot);
-            if (r) return r;
-            S.SOURCE = SOC_SOURCE_CL;
-        }
-        if (kind == SOC_SCA_HP) {
-            r = snapshot_hpbg(c, S, slot);
-            if (r) return r;
-        }
-        c->pending.push_back(S);
-        c->pending_sca = true;
-        return SOC_OK;
-    }
-    // a lone launch: as rays when it is large enough to fill the brick queues; soc_set_exec(1) asks for it, (0) for the direct kernel
-    if (rays_ok && (c->exec_mode == 1 || (c->exec_mode < 0 && S.gid_count >= SOC_SCA_RAYS_LAUNCH))) {
-        SocSim R = S;
-        if (kind == SOC_SCA_CL) R.SOURCE = SOC_SOURCE_CL;
-        SocVariant W = V;
-        W.wint = 0;
-        hipError_t e = soc_brick_run_pb(c->device, c->G, &R, 1, W, c->brick_log2, c->tune, c->stream, &c->last, &X);
-        if (e == hipSuccess) return SOC_OK;
-        if (e != hipErrorNotSupported || c->exec_mode == 1) return fail(c, SOC_ERR_HIP, "%s: brick sweep failed: %s", who, hipGetErrorString(e));
-    }
-    HIPCHK(c, soc_launch_sca(c->G, S, X, V, c->stream));
+    S.SCAKIND = k + 1;  S.DSC = c->dDSC;
+    S.OUT = c->out_slots ? c->dOUTslots + (size_t)c->out_slot_cur * c->out_slot_pixels : c->dOUT;
+    V.wint = 0;
     return SOC_OK;
 }
 
@@ -1368,18 +1329,15 @@ int soc_sca_sim_ps(soc_ctx *c, int PACKETS, int BATCH, float SEED, float BG, con
 {
     (void)PACKETS;
     if (!c) return SOC_ERR_ARG;
-    int slot = -1;
-    int r = sca_begin(c, &slot);
+    int r = check_launch(c, "soc_sca_sim_ps", BATCH, GLOBAL, gid_first, gid_count);
     if (r) return r;
-    r = check_launch(c, "soc_sca_sim_ps", BATCH, GLOBAL, gid_first, gid_count);
-    if (r) return r;
-    HIPCHK(c, hipSetDevice(c->device));
     SocSim S;
     SocVariant V;
-    fill_sim(c, S, V, 0, BATCH, SEED, BG, 0.0f, GLOBAL, gid_first, gid_count);
-    r = upload_sources(c, "soc_sca_sim_ps", S, PSPOS, PS, NO_PS, XPS_NSIDE, XPS_SIDE, XPS_AREA, true, slot < 0 ? 0 : slot);
+    r = fill_sca(c, SCA_PS, S, V, 0, BATCH, SEED, BG, GLOBAL, gid_first, gid_count);
     if (r) return r;
-    return sca_launch(c, "soc_sca_sim_ps", SOC_SCA_PS, S, V, slot);
+    return route_sim(c, SCA_PS, S, V, gid_count, [&](int slot) {
+        return upload_sources(c, "soc_sca_sim_ps", S, PSPOS, PS, NO_PS, XPS_NSIDE, XPS_SIDE, XPS_AREA, true, slot < 0 ? 0 : slot);
+    });
 }
 
 int soc_sca_sim_pb(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, float BG, const float *PSPOS, const float *PS,
@@ -1388,60 +1346,45 @@ int soc_sca_sim_pb(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, f
 {
     (void)PACKETS;
     if (!c) return SOC_ERR_ARG;
-    int slot = -1;
-    int r = sca_begin(c, &slot);
-    if (r) return r;
-    r = check_launch(c, "soc_sca_sim_pb", BATCH, GLOBAL, gid_first, gid_count);
+    int r = check_launch(c, "soc_sca_sim_pb", BATCH, GLOBAL, gid_first, gid_count);
     if (r) return r;
     if (SOURCE != 0 && SOURCE != 1)
         return fail(c, SOC_ERR_ARG, "soc_sca_sim_pb: SOURCE=%d (0 point sources, 1 background; ROI_LOAD is not supported)", SOURCE);
-    HIPCHK(c, hipSetDevice(c->device));
     SocSim S;
     SocVariant V;
-    fill_sim(c, S, V, SOURCE, BATCH, SEED, BG, 0.0f, GLOBAL, gid_first, gid_count);
-    if (SOURCE == 0) {
-        r = upload_sources(c, "soc_sca_sim_pb", S, PSPOS, PS, NO_PS, XPS_NSIDE, XPS_SIDE, XPS_AREA, true, slot < 0 ? 0 : slot);
-        if (r) return r;
-    } else {
-        S.NO_PS = 1;
-    }
-    return sca_launch(c, "soc_sca_sim_pb", SOC_SCA_PB, S, V, slot);
+    r = fill_sca(c, SCA_PB, S, V, SOURCE, BATCH, SEED, BG, GLOBAL, gid_first, gid_count);
+    if (r) return r;
+    return route_sim(c, SCA_PB, S, V, gid_count, [&](int slot) {
+        return SOURCE == 0 ? upload_sources(c, "soc_sca_sim_pb", S, PSPOS, PS, NO_PS, XPS_NSIDE, XPS_SIDE, XPS_AREA, true, slot < 0 ? 0 : slot) : SOC_OK;
+    });
 }
 
 int soc_sca_sim_cl(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, int GLOBAL, int gid_first, int gid_count)
 {
     (void)PACKETS;  (void)SOURCE;
     if (!c) return SOC_ERR_ARG;
-    int slot = -1;
-    int r = sca_begin(c, &slot);
-    if (r) return r;
-    r = check_launch(c, "soc_sca_sim_cl", BATCH, GLOBAL, gid_first, gid_count);
+    int r = check_launch(c, "soc_sca_sim_cl", BATCH, GLOBAL, gid_first, gid_count);
     if (r) return r;
     if (!c->have_emit) return fail(c, SOC_ERR_STATE, "soc_sca_sim_cl: call soc_set_emission first");
-    HIPCHK(c, hipSetDevice(c->device));
     SocSim S;
     SocVariant V;
-    fill_sim(c, S, V, 2, BATCH, SEED, 0.0f, 0.0f, GLOBAL, gid_first, gid_count);
-    S.NO_PS = 1;
-    return sca_launch(c, "soc_sca_sim_cl", SOC_SCA_CL, S, V, slot);
+    r = fill_sca(c, SCA_CL, S, V, SOC_SOURCE_CL, BATCH, SEED, 0.0f, GLOBAL, gid_first, gid_count);
+    if (r) return r;
+    return route_sim(c, SCA_CL, S, V, gid_count, [&](int slot) { return keep_emission(c, S, slot); });
 }
 
 int soc_sca_sim_hp(soc_ctx *c, int PACKETS, int BATCH, float SEED, int GLOBAL, int gid_first, int gid_count)
 {
     (void)PACKETS;
     if (!c) return SOC_ERR_ARG;
-    int slot = -1;
-    int r = sca_begin(c, &slot);
-    if (r) return r;
-    r = check_launch(c, "soc_sca_sim_hp", BATCH, GLOBAL, gid_first, gid_count);
+    int r = check_launch(c, "soc_sca_sim_hp", BATCH, GLOBAL, gid_first, gid_count);
     if (r) return r;
     if (!c->have_hpbg) return fail(c, SOC_ERR_STATE, "soc_sca_sim_hp: call soc_set_hpbg first");
-    HIPCHK(c, hipSetDevice(c->device));
     SocSim S;
     SocVariant V;
-    fill_sim(c, S, V, 1, BATCH, SEED, 0.0f, 0.0f, GLOBAL, gid_first, gid_count);
-    S.NO_PS = 1;
-    return sca_launch(c, "soc_sca_sim_hp", SOC_SCA_HP, S, V, slot);
+    r = fill_sca(c, SCA_HP, S, V, 1, BATCH, SEED, 0.0f, GLOBAL, gid_first, gid_count);
+    if (r) return r;
+    return route_sim(c, SCA_HP, S, V, gid_count, [&](int slot) { return keep_sky(c, S, slot); });
 }
 
 int soc_sca_read_out(soc_ctx *c, float *out, int64_t n)

@@ -173,3 +173,92 @@ def _defer(eng, job, view, kind, gid_first, gid_count):
     else:
         eng.set_emission(job.EMIT, job.EMWEI)
         eng.sca_sim_cl(job.SOURCE, job.PACKETS, job.BATCH, job.SEED, job.GLOBAL, gid_first=gid_first, gid_count=gid_count)
+
+
+def _run_batches(eng, cl, view, batches):
+    """zeroed image and TABS, then every batch between its own batch_begin and batch_end (soc_set_exec(1): small batches still sweep);
+    a launch is (kind, job, gid_first, gid_end) with kind None for an absorption launch (SimRAM_PB, or SimRAM_CL for SOURCE 2), or a
+    function of the engine that makes calls of its own"""
+    eng.set_cloud(cl)
+    eng.set_features(0, 0, 0)
+    eng.set_opt(None)
+    eng.set_mirror(0)
+    eng.set_exec(1, 4)
+    try:
+        eng.sca_set_view(view.ODIR, view.RA, view.DE, view.NPIX, view.MAP_DX, view.CENTRE, view.FFS)
+        eng.sca_zero()
+        eng.zero(0)
+        eng.stats(reset=True)
+        for launches in batches:
+            eng.batch_begin(0)
+            for launch in launches:
+                if callable(launch):
+                    launch(eng)
+                    continue
+                kind, job, g0, g1 = launch
+                if kind is not None:
+                    _defer(eng, job, view, kind, g0, g1 - g0)
+                    continue
+                eng.set_optical(job.ABS, job.SCA)
+                eng.set_scatter_table(job.DSC, job.CSC)
+                if job.SOURCE == 2:
+                    eng.set_emission(job.EMIT, job.EMWEI)
+                    eng.sim_cl(2, job.PACKETS, job.BATCH, job.SEED, job.TW, job.GLOBAL, gid_first=g0, gid_count=g1 - g0)
+                else:
+                    eng.sim_pb(job.SOURCE, job.PACKETS, job.BATCH, job.SEED, job.BG, job.TW, GLOBAL=job.GLOBAL, gid_first=g0, gid_count=g1 - g0)
+            eng.batch_end()
+        eng.sync()
+        return eng.sca_read_out(), eng.read_tally(0), eng.stats()
+    finally:
+        eng.set_exec(-1, 4)
+
+
+def test_a_batch_of_both_families(engine):
+    """scattered-light launches, then absorption launches, then scattered-light launches again in ONE batch: a sweep holds the launches of
+    one family, so each change of family runs what is pending.  Event counts, image and TABS equal those of the same launches with the
+    batch ended and begun again by hand at each change of family."""
+    from soc_amd import synth
+    from util import assert_tally_close
+    cl = cloud104()
+    k = 2.0 / (104 * float(cl.DENS[:104 ** 3][cl.DENS[:104 ** 3] > 0].mean()))
+    view = view104(angles=((60.0, 200.0), (10.0, 80.0)))
+    ps = np.array([[52.3, 51.7, 50.2]], np.float32)
+    emit = np.where(cl.DENS > 0, cl.DENS * 1e-3, 1e-4).astype(np.float32)
+    dsc2, csc2 = synth.hg_scattering_table(0.2)
+    sca1 = dict(ABS=0.3 * k, SCA=k, DSC=cases._DSC)
+    sca2 = dict(ABS=0.2 * k, SCA=0.8 * k, DSC=dsc2)
+    families = [
+        [(0, Job(cl, cases._CSC, SOURCE=1, BATCH=2, SEED=0.31, BG=1.0, **sca1), 1000, 21000),
+         (2, Job(cl, cases._CSC, SOURCE=0, BATCH=6, SEED=0.22, GLOBAL=4096, PSPOS=ps, PS=[1.5], **sca1), 0, 4096),
+         (1, Job(cl, cases._CSC, SOURCE=2, BATCH=1, SEED=0.43, GLOBAL=16384, EMIT=emit, **sca1), 0, 8192)],
+        [(None, Job(cl, cases._CSC, ABS=3e-6, SCA=3e-5, SOURCE=1, BATCH=4, SEED=0.377, BG=1.0), 100000, 106000),
+         (None, Job(cl, csc2, ABS=2e-6, SCA=5e-5, SOURCE=2, BATCH=1, SEED=0.59, GLOBAL=16384, EMIT=emit, TW=0.5), 0, 8192)],
+        [(1, Job(cl, csc2, SOURCE=2, BATCH=1, SEED=0.61, GLOBAL=16384, EMIT=emit * 2, **sca2), 4000, 12000),
+         (0, Job(cl, csc2, SOURCE=1, BATCH=2, SEED=0.74, BG=2.0, **sca2), 30000, 45000)]]
+    img_s, tabs_s, st_s = _run_batches(engine, cl, view, families)
+    img, tabs, st = _run_batches(engine, cl, view, [sum(families, [])])
+    assert engine.last_passes() > 0 and engine.last_form() == 3 and engine.last_variant()["rays"] == 1
+    assert st == st_s and st["tally_events"] > 0 and st["scatterings"] > 0
+    assert (img_s > 0).sum() > 100 and (tabs_s > 0).sum() > 1000
+    assert_image_close(img, img_s)
+    assert_tally_close(tabs, tabs_s, rtol=1e-5)
+
+
+def test_a_refused_launch_in_a_batch_leaves_the_deferred_ones(engine):
+    """a soc_sca_sim_* call refused inside a batch (its work items outside GLOBAL) raises; the launches deferred before and after it
+    run at soc_batch_end as they would without it"""
+    from soc_amd.lib import SocError
+    cl = cloud104()
+    k = 2.0 / (104 * float(cl.DENS[:104 ** 3][cl.DENS[:104 ** 3] > 0].mean()))
+    view = view104()
+    emit = np.where(cl.DENS > 0, cl.DENS * 1e-3, 1e-4).astype(np.float32)
+    launches = [(0, Job(cl, cases._CSC, ABS=0.3 * k, SCA=k, SOURCE=1, BATCH=2, SEED=0.52, BG=1.0, DSC=cases._DSC), 2000, 14000),
+                (1, Job(cl, cases._CSC, ABS=0.3 * k, SCA=k, SOURCE=2, BATCH=1, SEED=0.18, GLOBAL=8192, EMIT=emit, DSC=cases._DSC), 0, 8192)]
+    want, _, st_want = _run_batches(engine, cl, view, [launches])
+
+    def refused(eng):
+        with pytest.raises(SocError, match="outside GLOBAL"):
+            eng.sca_sim_pb(1, 0, 2, 0.5, 1.0, GLOBAL=1000, gid_first=900, gid_count=200)
+    got, _, st = _run_batches(engine, cl, view, [[launches[0], refused, launches[1]]])
+    assert st == st_want and st["tally_events"] > 0
+    assert_image_close(got, want)
