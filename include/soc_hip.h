@@ -87,7 +87,7 @@ int soc_set_exec(soc_ctx *ctx, int mode, int brick_log2);
  * hierarchies), "chunk" (packets per workgroup, <= 4096; <= 32768 on brick-local hierarchies), "steps_per_visit" (cell steps
  * before a packet goes back to its queue), "swap_lanes" (lanes of a wave that must wait before the packet swap runs),
  * "climb_lanes" (the same for the deferred Index() of the global-tree form), "brick_cells" (cells per brick on hierarchies,
- * <= 36864), "tail_lanes", "park_below" (hierarchies: brick queues shorter than this and than the mean wait a pass; 1 = never), "population" (packets in flight), "hash_slots" (per-workgroup
+ * <= 36864; rays on single-level grids: bricks of the largest cube within), "tail_lanes", "park_below" (hierarchies: brick queues shorter than this and than the mean wait a pass; 1 = never), "population" (packets in flight), "hash_slots" (per-workgroup
  * arrival table, power of two), "general_kernel" (1: no background-only kernel), "global_tree" (1: hierarchies are walked in
  * global memory also where the brick-local form applies), "slow_every" (test knob of that form),
  * "oversubscribe", "verbose". */
@@ -243,14 +243,16 @@ int soc_read_par(soc_ctx *ctx, int32_t *out, int64_t n);
 /* counters accumulated by the kernels since the last reset:
  * out[0] tally events, out[1] packets created, out[2] scattering events */
 int soc_stats(soc_ctx *ctx, uint64_t out[3], int reset);
-/* cell steps of all rays (look-ahead, packet, peel-off) of the scattered-light launches that ran as sweeps of rays on brick-local
- * hierarchies, as of the last soc_stats call (what the read-only roofline of SURVEY 8(d) counts: 4 B per step); -1: no handle */
+/* cell steps of all rays (look-ahead, packet, peel-off) of the scattered-light launches that ran as sweeps of rays (brick-local
+ * hierarchies, single-level grids), as of the last soc_stats call (what the read-only roofline of SURVEY 8(d) counts: 4 B per step); -1: no handle */
 int64_t soc_sca_ray_steps(soc_ctx *ctx);
 
 /* number of brick-sweep passes of the last launch (0 if it ran in direct mode) */
 int soc_last_passes(soc_ctx *ctx);
 /* how the last launch was executed: 0 direct kernel, 1 brick sweep on a Cartesian grid, 2 on a hierarchy read from global
- * memory, 3 on brick-local hierarchies (soc_ltree.h: hierarchies whose Index() the reference evaluates in double) */
+ * memory, 3 on brick-local hierarchies (soc_ltree.h: hierarchies whose Index() the reference evaluates in double) -- and, for the
+ * scattered-light launches, the sweep of rays on a single-level (Cartesian) grid, whose bricks hold root cells only (form 3 with the
+ * octree bit of soc_last_variant clear; absorption launches on Cartesian grids stay form 1) */
 int soc_last_form(soc_ctx *ctx);
 /* the compiled absorption kernel the last launch or sweep of the handle ran on (-1 before any ran), for verification:
  *   bits 0-1  form: 0 direct kernel, 1-3 as soc_last_form
@@ -258,7 +260,8 @@ int soc_last_form(soc_ctx *ctx);
  *             3 PB with background packets only (the lean kernel), 4 launches of several kinds (brick-local only)
  *   bits 5-6  WINT: 0 TABS only, 1 INT tally, 2 INT and INTX/Y/Z (brick-local), 3 the INT tally alone in LDS (brick-local)
  *   bit 7 octree, bit 8 Index() in double, bit 9 per-cell opacities, bit 10 ALI (brick-local), bit 11 the sweep of rays of
- *   the scattered-light kernels (then the other fields are 0 but form 3, octree, double, and bits 12-13)
+ *   the scattered-light kernels (then the other fields are 0 but form 3, octree, double, and bits 12-13; on a single-level grid
+ *   form 3 with octree = 0: the field has two bits, there is no form 4)
  *   bit 12 (sweeps of rays) the image was a Healpix map seen from a position (soc_sca_set_healpix)
  *   bit 13 (sweeps of rays) the sweep held a SimRAM_HP launch (soc_sca_sim_hp: the Healpix sky as the source) */
 int soc_last_variant(soc_ctx *ctx);
@@ -317,8 +320,9 @@ void *soc_sca_out_ptr(soc_ctx *ctx);
 
 /* Scattered-light launches in batches.  The reference runs one kernel after the other per frequency and source (ASOCS.py:655-708)
  * and reads the image after each frequency (:710-716).  Between soc_batch_begin and soc_batch_end (above) the soc_sca_sim_ps / _pb /
- * _cl launches that can run as rays on brick-local hierarchies (flat image, scalar opacities, one scattering function, a hierarchy
- * whose Index() the reference evaluates in double) are deferred, each with a snapshot of its inputs, and run together in one sweep
+ * _cl launches that can run as rays (flat or Healpix image, scalar opacities, one scattering function; a hierarchy whose Index() the
+ * reference evaluates in double, or a single-level grid -- there in automatic mode only from 8 bricks of 16^3 cells on, and the batch
+ * runs as a sweep from 2.5e7 work items on, as the direct kernel below) are deferred, each with a snapshot of its inputs, and run together in one sweep
  * -- more rays per brick and pass than any single launch has; every other launch runs at once, as without the batch.
  * soc_sca_batch_images(n) gives the batch n zeroed images (n = 0: the one image of soc_sca_set_view again); the launches that
  * follow soc_sca_batch_select(k) add to image k -- one image per frequency -- and soc_sca_batch_read(k, ...) replaces the

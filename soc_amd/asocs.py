@@ -9,8 +9,8 @@ OUTCOMING[NFREQ, NDIR, NPIX.y, NPIX.x] in Jy/sr (ASOCS.py:887-899) with the refe
 
 The host loop (source block II -> frequency; then the CLPAC loop) and every launch formula
 are the reference's.  The kernels: the direct kernel soc_sca_kernel (soc_amd/csrc/soc_sca.hip)
-and, on hierarchies that take the brick-local form, the sweep of rays (soc_brick.hip:
-soc_lray_pass), which runs the launches of a source block deferred into one batch.  With
+and, on hierarchies that take the brick-local form and on Cartesian grids (there for batches
+large enough to pay), the sweep of rays (soc_brick.hip: soc_lray_pass), which runs the launches of a source block deferred into one batch.  With
 several ranks each launch is split by logical work-item id and the image is summed with one
 all-reduce.  ``perspective x y z`` switches to one Healpix map (``outnside``) seen from that
 position, ``hpbg`` to the Healpix background (sca SimRAM_HP); both run on either kernel.
@@ -117,9 +117,9 @@ class ScatteringRun(AbsorptionRun):
             seed = self._bcast_seed(seed)
         return seed
 
-    # The frequencies of a source block are ONE batch with an image each (soc_sca_batch_images): the launches that can run as rays on
-    # brick-local hierarchies are deferred and share sweeps (many more rays per brick and pass than one launch has), the others run
-    # at once into their frequency's image.  Several ranks then add the images up once per block, on the host.
+    # The frequencies of a source block are ONE batch with an image each (soc_sca_batch_images): the launches that can run as rays --
+    # on brick-local hierarchies, and on Cartesian grids where a batch was measured to pay -- are deferred and share sweeps (many more
+    # rays per brick and pass than one launch has), the others run at once into their frequency's image.  Several ranks then add the images up once per block, on the host.
     def _begin_block(self, max_launches=0):
         """max_launches: cell-emission launches keep a copy of the emission each (8 B per cell), so their batches are shorter"""
         self._launched = []                                        # the frequencies launched, read after the batch (_end_block)

@@ -641,7 +641,10 @@ __device__ __forceinline__ int soc_cell_index(const SocGrid &G, int level, int c
 // for SimRAM_PB launches, flag bit 1 of the launch -- and it is done when nothing is left: it goes to queue 0 of its launch (the one of the
 // rays that left the model) with the optical depth of that last step added, the position wherever GetStep put it (the event lane does not
 // read it).  Its record's B.w goes back to memory with it.
-template <int WINT, bool RAY = false, bool ALI = false, bool LIM = false>
+// CART (RAY only): a single-level grid (bricks of soc_cbricks_build: boxes of root cells, their densities in LDS).  Index() is then
+// a floor and a bounds test (kernel_ASOC_aux.c:216-221): no soc_lt_aim / soc_lt_land, no level, no octet -- the new slot follows from
+// the root cell the step ended in, and a ray whose step ends in a root cell outside the brick's box leaves for that cell's brick.
+template <int WINT, bool RAY = false, bool ALI = false, bool LIM = false, bool CART = false>
 __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPack &K, const SocBrickArgs &A, const int bid)
 {
     if (bid >= *A.ndesc) return;
@@ -808,7 +811,8 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                         // the step that brought it here (ARRIVE), or the cell its coordinates name.  A root-level packet in (or
                         // into) a root cell that is not refined -- the common case -- is settled here.
                         // (with the record of packets entering ROI an arrival is always finished in the step arm, where the test for it sits)
-                        const bool settled = (level == 0) && (!n_arrive || ((n_rec > 0.0f) && !(!RAY && A.roi_on)));
+                        // (a single-level grid: always -- every cell is a root cell with a density)
+                        const bool settled = CART || ((level == 0) && (!n_arrive || ((n_rec > 0.0f) && !(!RAY && A.roi_on))));
                         what = settled ? SOC_LTM_STEP : (n_arrive ? SOC_LTM_ARRIVE : SOC_LTM_PLACE);
                         slot = settled ? n_s2 : slot;  dens = settled ? n_rec : dens;
                         cx = settled ? n_ix : cx;  cy = settled ? n_iy : cy;  cz = settled ? n_iz : cz;
@@ -881,6 +885,37 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
             // the tally of the step while that read is in flight; the descent to the leaf; the outcome.  ONE divergent region, and the
             // outcome by selects: every `if` of a divergent wave costs scalar bookkeeping of the exec mask that the wave issues in order
             // with its vector instructions (the walk is bound by instruction issue) ----
+            if (CART) {
+                // ---- Index on one level (kernel_ASOC_aux.c:216-221): outside the model, or the root cell that holds the point.  The ray's
+                // slot follows from that cell's place in the brick's box; outside the box the ray keeps its cell and the advanced position
+                // and goes to the queue of the cell's brick, which takes it up there (ARRIVE).  One divergent region, outcome by selects ----
+                if (move) {
+                    n_tally++;
+                    tau += dtau;
+                    const int  ix = (int)soc_floorf(px), iy = (int)soc_floorf(py), iz = (int)soc_floorf(pz);
+                    const bool outside = (px == 0.0f) | (py == 0.0f) | (pz == 0.0f)                       // pos <= 0 leaves the model (:217)
+                                         | ((unsigned)ix >= (unsigned)NX) | ((unsigned)iy >= (unsigned)NY) | ((unsigned)iz >= (unsigned)NZ);
+                    const int  rx = ix - KB.x0, ry = iy - KB.y0, rz = iz - KB.z0;
+                    const bool inbox = !(((unsigned)rx >= (unsigned)KB.bx) | ((unsigned)ry >= (unsigned)KB.by) | ((unsigned)rz >= (unsigned)KB.bz));
+                    const bool inside = inbox & !outside;
+                    const int  ns = inside ? SOC_MAD24(SOC_MAD24(rz, KB.by, ry), KB.bx, rx) : slot0;
+                    const float rec = sD[ns];
+                    // failed step (the same cell again): nudge -- SimRAM_PB / HP packets only; GetStep alone moves a ray
+                    const float nz = (inside & !nonudge & (ns == slot0)) ? SOC_PEPS : 0.0f;
+                    px += nz * ux;  py += nz * uy;  pz += nz * uz;
+                    slot = ns;  dens = rec;
+                    cx = inside ? ix : cx;  cy = inside ? iy : cy;  cz = inside ? iz : cz;
+                    nvisit += inside ? 1 : 0;
+                    // where the ray goes when it does not stay: its own queue again (step budget used), the brick of the root cell it steps
+                    // into (looked up after the walk: -1 - root cell), queue 0 of its launch (outside the model)
+                    const int kleave = -1 - SOC_MAD24(SOC_MAD24(iz, NY, iy), NX, ix);
+                    const bool out = !inside | (nvisit >= A.KCAP);
+                    key  = out ? (inside ? D.brick : (outside ? evq : kleave)) : key;
+                    mode = out ? SOC_BM_SWAP : mode;
+                    dw  |= (!inside & !outside) ? SOC_LT_ARRIVE : 0u;
+                }
+                SOC_PROF_T(2);
+            } else
             if (move) {
                 SocLtAim AM;
                 int   r;
@@ -1806,13 +1841,15 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
 
 // HPX: the view is a Healpix map seen from a position (SocSca::NDIR < 0): peel-off rays that end at the observer.  HPSKY: the sweep
 // holds SimRAM_HP launches (the creation of their packets stays out of the kernels of sweeps without them: registers)
-template <bool HPX, bool HPSKY>
+// CART: the grid has one level (soc_lbrick_walk<., ., ., ., CART>); the event workgroups are the same -- a Cartesian ray is an ordinary
+// entry to them, on level 0 of a hierarchy that has no other
+template <bool HPX, bool HPSKY, bool CART>
 __global__ __launch_bounds__(1024) void soc_lray_pass(const SocGrid G, const SocSimPack *Kp, const SocBrickArgs A, const int nwalk, const int slices)
 {
     const SocSimPack &K = *Kp;
     const int b = (int)blockIdx.x;
     if (b < nwalk) {
-        soc_lbrick_walk<false, true, false, HPX>(G, K, A, b);
+        soc_lbrick_walk<false, true, false, HPX, CART>(G, K, A, b);
     } else {
         const int e = b - nwalk;
         soc_sca_events<HPX, HPSKY>(G, K, A, e / slices, e % slices);
@@ -2081,8 +2118,9 @@ static hipError_t soc_oct_build(int device, const SocGrid &G, int CAP, hipStream
     return hipSuccess;
 }
 
-// Bricks for the walk on brick-local hierarchies.  hipErrorNotSupported: the hierarchy cannot be cut that way (a root
-// cell with more than cap cells below it) -- the caller keeps the sweep that reads the hierarchy from global memory.
+// Bricks for the walk on brick-local hierarchies, and for the rays on single-level grids.  hipErrorNotSupported: the hierarchy cannot
+// be cut that way (a root cell with more than cap cells below it) -- the caller keeps the sweep that reads the hierarchy from global
+// memory; a single-level grid holds a cell without a positive density -- its rays stay with the direct kernel.
 static hipError_t soc_lb_build(int device, const SocGrid &G, int cap, hipStream_t st, bool verbose)
 {
     SocLBricksDev &lb = g_lb[device];
@@ -2096,7 +2134,10 @@ static hipError_t soc_lb_build(int device, const SocGrid &G, int cap, hipStream_
     BCHK(hipStreamSynchronize(st));
     BCHK(hipMemcpy(D.data(), G.DENS, (size_t)G.CELLS * 4, hipMemcpyDeviceToHost));
     SocLBricksHost H;
-    if (!soc_lbricks_build(G.NX, G.NY, G.NZ, G.LEVELS, G.LCELLS, G.OFF, D.data(), cap, H) || H.bricks.size() >= (1u << 20)) {
+    // (a single-level grid: boxes of root cells, `cap` the cube of their edge)
+    const bool built = (G.LEVELS == 1) ? soc_cbricks_build(G.NX, G.NY, G.NZ, D.data(), soc_cart_edge(cap), H)
+                                       : soc_lbricks_build(G.NX, G.NY, G.NZ, G.LEVELS, G.LCELLS, G.OFF, D.data(), cap, H);
+    if (!built || H.bricks.size() >= (1u << 20)) {
         lb.failed = true;
         return hipErrorNotSupported;
     }
@@ -2117,8 +2158,8 @@ static hipError_t soc_lb_build(int device, const SocGrid &G, int cap, hipStream_
     lb.NB = NB;  lb.max_slots = H.max_slots;
     lb.valid = true;
     if (verbose)
-        fprintf(stderr, "soc_brick: hierarchy of %d cells -> %d brick-local hierarchies of <= %d cells (largest %d, mean %.0f)\n",
-                G.CELLS, NB, cap, H.max_slots, (double)G.CELLS / NB);
+        fprintf(stderr, "soc_brick: %s of %d cells -> %d brick-local hierarchies of <= %d cells (largest %d, mean %.0f)\n",
+                (G.LEVELS == 1) ? "grid" : "hierarchy", G.CELLS, NB, cap, H.max_slots, (double)G.CELLS / NB);
     return hipSuccess;
 }
 
@@ -2150,12 +2191,13 @@ static const SocPassFn soc_lbrick_pass_fns[4][5] = {
     { soc_lbrick_pass<2, 0>, soc_lbrick_pass<2, 1>, soc_lbrick_pass<2, 2>, soc_lbrick_pass<2, 3>, soc_lbrick_pass<2, 4> },
     { soc_lbrick_pass<3, 0>, soc_lbrick_pass<3, 1>, soc_lbrick_pass<3, 2>, soc_lbrick_pass<3, 3>, soc_lbrick_pass<3, 4> } };
 static const SocPassFn soc_lbrick_pass_ali_fns[2] = { soc_lbrick_pass_ali<0>, soc_lbrick_pass_ali<1> };
-// rays: [Healpix image seen from a position][SimRAM_HP launches]
-static const SocPassFn soc_lray_pass_fns[2][2] = { { soc_lray_pass<0, 0>, soc_lray_pass<0, 1> }, { soc_lray_pass<1, 0>, soc_lray_pass<1, 1> } };
+// rays: [single-level grid][Healpix image seen from a position][SimRAM_HP launches]
+static const SocPassFn soc_lray_pass_fns[2][2][2] = { { { soc_lray_pass<0, 0, 0>, soc_lray_pass<0, 1, 0> }, { soc_lray_pass<1, 0, 0>, soc_lray_pass<1, 1, 0> } },
+                                                      { { soc_lray_pass<0, 0, 1>, soc_lray_pass<0, 1, 1> }, { soc_lray_pass<1, 0, 1>, soc_lray_pass<1, 1, 1> } } };
 
 static SocPassFn pass_kernel(const SocSweepPlan &pl)
 {
-    if (pl.rays)      return soc_lray_pass_fns[pl.hpx][pl.hpsky];
+    if (pl.rays)      return soc_lray_pass_fns[pl.octree ? 0 : 1][pl.hpx][pl.hpsky];
     if (pl.form == 3) return pl.ali ? soc_lbrick_pass_ali_fns[pl.wint] : soc_lbrick_pass_fns[pl.wint][pl.kind];
     return soc_brick_pass_fns[pl.octree + pl.dbl][pl.abu][pl.wint][pl.kind];
 }
@@ -2181,7 +2223,9 @@ static hipError_t check_sca(const SocSim *S, int nlaunch, const SocVariant &V, c
 static hipError_t plan_sweep(SocSweepPlan &pl, const SocGrid &G, const SocSim *S, int nlaunch, const SocVariant &V,
                              const SocBrickTune &tune, const SocSca *sca, bool lb_ok)
 {
-    const bool lt = lb_ok && soc_brick_local(G, V, tune);
+    // rays on a single-level grid: the brick-local form with bricks of root cells (absorption launches there keep form 1)
+    const bool cart = lb_ok && sca && soc_brick_cart(G, V);
+    const bool lt = cart || (lb_ok && soc_brick_local(G, V, tune));
     pl = soc_grid_plan(lt ? 3 : V.octree ? 2 : 1, 0, V);
     pl.rays = sca != nullptr;
     pl.hpx = sca && sca->NDIR < 0;
@@ -2230,7 +2274,9 @@ static hipError_t plan_sweep(SocSweepPlan &pl, const SocGrid &G, const SocSim *S
     // (rays: 4 B per cell, twice the cells in the same LDS)
     // (the vector sums of SAVE_INTENSITY 2: 24 B per cell)
     // (ALI: 8 B per cell more for XAB and the cell numbers)
-    pl.capl = (tune.CAP > 0) ? tune.CAP : (sca ? 17408 : (ali ? (V.wint ? 3456 : 4352) : (V.wint == 2 ? 2944 : (V.wint && !int_only) ? 5888 : 8704)));
+    // (rays on a single-level grid: the cube of soc_cart_default_edge, 16 or 24 cells)
+    const int cedge = soc_cart_default_edge(G);
+    pl.capl = (tune.CAP > 0) ? tune.CAP : cart ? cedge * cedge * cedge : (sca ? 17408 : (ali ? (V.wint ? 3456 : 4352) : (V.wint == 2 ? 2944 : (V.wint && !int_only) ? 5888 : 8704)));
     if (pl.capl < 8 || pl.capl > 36864) return hipErrorInvalidValue;
     pl.EQ = 3;
     for (int l = 0; l < nlaunch; l++) pl.roi = pl.roi || (S[l].ROISAVE && S[l].ROI);
@@ -2363,7 +2409,7 @@ static hipError_t plan_kernel(SocSweepPlan &pl, SocBrickArgs &A, SocSweepSize &s
     if (A.HS & (A.HS - 1)) return hipErrorInvalidValue;
     // LDS: the brick's tallies (brick-local: its cells too -- + INT, + the vector sums, + XAB and the cell numbers; rays: the cells only),
     // the arrivals table, the launches' counters
-    const int BV = pl.octree ? A.CAP : (1 << (3 * A.LB));
+    const int BV = (pl.octree || pl.form == 3) ? A.CAP : (1 << (3 * A.LB));
     const int nh = A.HS ? 2 * A.HS : sz.NQ;
     const size_t lds_walk = (pl.form == 3) ? (size_t)(BV * (pl.rays ? 1 : (2 + (pl.wint == 2 ? 4 : (pl.wint == 1) ? 1 : 0) + (pl.ali ? 2 : 0)))
                                                       + ((nh + 3) & ~3) + 4 + 4 * SOC_MAXLAUNCH) * 4
@@ -2478,7 +2524,7 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *S, int n
     SocBrickArgs A;
     hipError_t e = build_bricks(A, pl, device, G, LB, st, tune.verbose != 0);
     if (e == hipErrorNotSupported && pl.form == 3) {                  // a root cell with more cells below it than a brick holds:
-        BCHK(plan_sweep(pl, G, S, nlaunch, V, tune, sca, false));     // the sweep that reads the hierarchy from global memory
+        BCHK(plan_sweep(pl, G, S, nlaunch, V, tune, sca, false));     // the sweep that reads the hierarchy from global memory (rays: none)
         e = build_bricks(A, pl, device, G, LB, st, tune.verbose != 0);
     }
     BCHK(e);

@@ -197,6 +197,23 @@ static bool lt_capable(const soc_ctx *c, bool abu) { return soc_brick_local(c->G
 // hierarchy (tools/exp_sca.py): 1.0e6 work items 0.47x the direct kernel, 3.1e6 0.92x, 8.4e6 1.3x, 5.0e7 1.6x (best direct launch shape), 32
 // launches of 3.1e6 in one batch 4.4x
 #define SOC_SCA_RAYS_LAUNCH 4000000
+// Single-level (Cartesian) grids whose scattered-light launches can run as a sweep of rays (soc_dev.h: soc_brick_cart) ...
+static bool cart_capable(const soc_ctx *c) { return soc_brick_cart(c->G, soc_grid_variant(c->G, false)); }
+// ... and the rule of automatic mode there.  Measured on synth.cartesian_cloud grids, background launches of the reference's shape (8 work
+// items per surface element), 3 observers, 256^2 pixels, the sweep of rays against the direct kernel (tools/exp_sca.py --compare; DESIGN.md
+// section 5, profiles/sca_cartesian_lines.json):
+//   lone launch                  128^3 (7.9e5 work items) 0.29x   256^3 (3.1e6) 0.66x   512^3 (1.3e7) 0.97x
+//   batch of 6.3e6 work items    128^3 1.01x                      256^3 1.02x
+//   batch of 2.5e7 work items    128^3 1.75x                      256^3 2.12x           512^3 1.44x (1.0e8: 2.57x)
+// A lone launch never came out ahead: it keeps the direct kernel.  The launches of a batch go to the sweep from 2.5e7 work items on, the
+// smallest batch measured to pay beyond run-to-run scatter (1 %) on every grid; at 6.3e6 the two paths are level.
+#define SOC_CART_RAYS_BATCH 25000000LL                      /* work items of the launches of a batch together */
+static bool cart_rays_pay(const soc_ctx *c, long long items, bool batch)
+{
+    const int B = SOC_CART_BRICK_EDGE;
+    const long long nb = (long long)((c->G.NX + B - 1) / B) * ((c->G.NY + B - 1) / B) * ((c->G.NZ + B - 1) / B);
+    return batch && nb >= 8 && items >= SOC_CART_RAYS_BATCH;      // (nb >= 8 bricks of 16^3: the floor of the absorption rule)
+}
 #define SOC_LT_LONE_LAUNCH 1000000                           // work items from which a lone launch goes to the sweep there
 
 // One launch through the direct kernel of its kind (SOURCE 4 and 5 mark Healpix and cell-emission launches for the brick sweep; the
@@ -235,7 +252,7 @@ static int flush_pending(soc_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     unsigned long long items = 0;
     for (const SocSim &S : todo) items += S.gid_count;
-    const bool direct = rays ? (c->exec_mode != 1 && items < SOC_SCA_RAYS_LAUNCH)
+    const bool direct = rays ? (c->exec_mode != 1 && !(cart_capable(c) ? cart_rays_pay(c, (long long)items, true) : items >= SOC_SCA_RAYS_LAUNCH))
                              : (V.octree && todo.size() == 1 && c->exec_mode < 0 && !(lt_capable(c, V.abu != 0) && items >= SOC_LT_LONE_LAUNCH));
     hipError_t e = hipErrorNotSupported;
     if (!direct)
@@ -871,7 +888,8 @@ static bool same_sweep(const soc_ctx *c, const SocSim &S, bool abu)
     if (c->pending.empty()) return true;
     const SocSim &P = c->pending[0];
     if ((P.SCAKIND != 0) != (S.SCAKIND != 0) || (P.OPT != nullptr) != abu) return false;
-    return soc_source_kind(P.SOURCE) == soc_source_kind(S.SOURCE) || lt_capable(c, abu);      // (brick-local hierarchies: the kinds share sweeps, also with per-group INT tallies)
+    // (brick-local hierarchies: the kinds share sweeps, also with per-group INT tallies; rays on single-level grids: one kernel for every kind)
+    return soc_source_kind(P.SOURCE) == soc_source_kind(S.SOURCE) || lt_capable(c, abu) || (S.SCAKIND != 0 && cart_capable(c));
 }
 
 // The kinds of launch and what sets them apart on the way to a kernel (use_sweep, route_sim)
@@ -905,8 +923,11 @@ static bool use_sweep(const soc_ctx *c, SimKind kind, const SocVariant &V, long 
         *why = (!c->have_view || c->view.NDIR == 0) ? "no view"
              : (c->msf_ndust > 1) ? "several scattering functions (WITH_MSF) need the direct kernel"
              : (c->dOPT != nullptr) ? "per-cell opacities need the direct kernel"
-             : (!lt_capable(c, false) || c->device >= 16) ? "the hierarchy is not one the brick-local walk takes (2-8 levels, Index() in double)"
+             : (!(lt_capable(c, false) || cart_capable(c)) || c->device >= 16)
+                   ? "the grid is not one the sweep of rays takes (a hierarchy of 2-8 levels with Index() in double, or a single-level grid below 4096 cells per edge)"
              : nullptr;
+        if (cart_capable(c))                                // (the launches of a batch are deferred where a batch can pay; flush_pending counts them)
+            return c->exec_mode != 0 && !*why && (c->exec_mode == 1 || (batch ? cart_rays_pay(c, SOC_CART_RAYS_BATCH, true) : cart_rays_pay(c, items, false)));
         return c->exec_mode != 0 && !*why && (c->exec_mode == 1 || batch || items >= SOC_SCA_RAYS_LAUNCH);
     }
     const bool lt = lt_capable(c, V.abu != 0);

@@ -211,17 +211,46 @@ static inline bool soc_brick_local(const SocGrid &G, const SocVariant &V, const 
     return V.octree && V.dbl && !V.abu && !tune.global_tree && G.LEVELS <= 8 && ((long long)n << (G.LEVELS - 1)) < (1LL << 24) && n < 4096;
 }
 
+// Single-level (Cartesian) grids on which the scattered-light launches run as a sweep of rays (soc_brick.hip: the CART arm of
+// soc_lbrick_walk, bricks from soc_cbricks_build): scalar opacities, root-cell numbers from 24-bit multiplies (SOC_MAD24: rows of
+// root cells below 2^23).  A sibling of soc_brick_local: absorption launches on such grids keep the Cartesian sweep (form 1).
+static inline bool soc_brick_cart(const SocGrid &G, const SocVariant &V)
+{
+    const int n = std::max(G.NX, std::max(G.NY, G.NZ));
+    return !V.octree && !V.abu && G.LEVELS == 1 && n < 4096 && ((long long)G.NY * G.NZ) < (1LL << 23);
+}
+// Rays on single-level grids: cells along the edge of a brick, measured (profiles/sca_cartesian_lines.json; rays
+// against the direct kernel, background launches): 128^3 -- 8: 0.13x, 16: 0.29x, 24: 0.23x; 256^3 -- 8: 0.09x, 16: 0.45x, 24: 0.66x,
+// 32: 0.57x; 512^3 -- 16: 0.46x, 24: 0.97x, 32: 0.77x.  A sweep needs as many passes as its longest chain of brick visits, and a pass
+// costs three kernel launches: larger bricks, fewer passes -- until a brick's 4 B per cell leave one workgroup per CU (32^3 = 128 KB).
+// 24^3 cells are 54 KB of LDS (two workgroups per CU), 16^3 are 16 KB.
+#define SOC_CART_BRICK_EDGE 16                               /* grids below SOC_CART_BRICK_WIDE cells along their longest edge */
+#define SOC_CART_BRICK_EDGE_WIDE 24
+#define SOC_CART_BRICK_WIDE 256
+static inline int soc_cart_default_edge(const SocGrid &G)
+{
+    return (std::max(G.NX, std::max(G.NY, G.NZ)) >= SOC_CART_BRICK_WIDE) ? SOC_CART_BRICK_EDGE_WIDE : SOC_CART_BRICK_EDGE;
+}
+// cells along the edge of such a brick: the largest cube within `cells` (soc_set_tuning("brick_cells"))
+static inline int soc_cart_edge(int cells)
+{
+    int e = 1;
+    while ((long long)(e + 1) * (e + 1) * (e + 1) <= cells) e++;
+    return e;
+}
+
 // What a brick sweep runs, decided before it runs (soc_brick.hip: plan_sweep, completed by plan_kernel once the launches are packed).
 // Form 0 describes a launch of the direct kernels (soc_capi.hip: run_direct).
 struct SocSweepPlan {
     int  form;                 // 0 direct kernel, 1 Cartesian sweep, 2 sweep of a hierarchy in global memory, 3 brick-local sweep
+                               // (form 3 with octree == false: the sweep of rays on a Cartesian grid, whose bricks hold root cells only)
     int  kind;                 // the KIND template argument: 0 SimRAM_PB, 1 _HP, 2 _CL, 3 background packets only, 4 several (brick-local); rays: 0
     int  wint;                 // the WINT template argument: 0, 1, 2 (brick-local), 3 the INT-only form of the brick-local walk
     bool octree, dbl, abu;     // the grid's kernels (dbl: octree and Index() in double)
     bool ali;                  // brick-local: every launch a SimRAM_CL one with the XAB tally (WITH_ALI)
     bool rays, hpx, hpsky;     // the scattered-light sweep of rays; its image a Healpix map seen from a position; SimRAM_HP launches in it
     bool roi;                  // brick-local: the record of packets entering ROI (a fourth event queue per launch)
-    int  capl;                 // brick-local: cells per brick
+    int  capl;                 // brick-local: cells per brick (rays on a Cartesian grid: the cube of the brick's edge)
     // SocBrickArgs: the form's defaults with soc_set_tuning applied (CAP: leaves per brick of a hierarchy in global memory)
     int  T, P, KCAP, FTH, CTH, CAP, TAIL, PARK, EQ, slow_every;
     size_t lds;                // dynamic LDS of the pass kernel

@@ -1,4 +1,5 @@
-// soc_lbricks.h -- host-side construction of the brick-local hierarchies of soc_ltree.h.  Plain C++ (no HIP), so the
+// soc_lbricks.h -- host-side construction of the brick-local hierarchies of soc_ltree.h, and of the bricks of root cells of
+// single-level grids (soc_cbricks_build, at the end).  Plain C++ (no HIP), so the
 // same code is compiled into libsoc_hip.so and -- with -fsanitize=address,undefined -- into the CPU tests.
 //
 // A brick is a box of root cells together with everything below them, at most `cap` cells (leaves and refined
@@ -149,6 +150,46 @@ inline bool soc_lbricks_build(int NX, int NY, int NZ, int LEVELS, const int *LCE
     const bool ok = B.build();
     if (!ok) out = SocLBricksHost();
     return ok;
+}
+
+// Bricks of a single-level (Cartesian) grid, for the sweep of rays on such grids (soc_brick.hip: soc_lbrick_walk<., RAY, ., ., CART>):
+// boxes of at most edge^3 root cells, the last box of an axis as short as the grid leaves it (an axis shorter than `edge` is one box).
+// The same tables as above with nothing below the root cells: a brick's slots are its cells, x fastest, and hold their densities.
+// Returns false for a grid with a cell whose density is not positive: the hierarchy's own walk (the event lanes use it) would read
+// such a cell as a link.
+inline bool soc_cbricks_build(int NX, int NY, int NZ, const float *DENS, int edge, SocLBricksHost &out)
+{
+    out = SocLBricksHost();
+    if (NX < 1 || NY < 1 || NZ < 1 || edge < 1) return false;
+    const size_t cells = (size_t)NX * NY * NZ;
+    for (size_t i = 0; i < cells; i++) if (!(DENS[i] > 0.0f)) return false;
+    out.rbrick.assign(cells, -1);
+    out.btree.resize(cells);
+    out.bcell.resize(cells);
+    size_t fill = 0;
+    for (int z0 = 0; z0 < NZ; z0 += edge)
+        for (int y0 = 0; y0 < NY; y0 += edge)
+            for (int x0 = 0; x0 < NX; x0 += edge) {
+                SocLBrick K;
+                K.x0 = x0;  K.y0 = y0;  K.z0 = z0;
+                K.bx = (x0 + edge <= NX) ? edge : NX - x0;  K.by = (y0 + edge <= NY) ? edge : NY - y0;  K.bz = (z0 + edge <= NZ) ? edge : NZ - z0;
+                K.base = (int)fill;
+                K.nslot = K.bx * K.by * K.bz;
+                const int id = (int)out.bricks.size();
+                for (int z = z0; z < z0 + K.bz; z++)
+                    for (int y = y0; y < y0 + K.by; y++)
+                        for (int x = x0; x < x0 + K.bx; x++) {
+                            const size_t r = ((size_t)z * NY + y) * NX + x;
+                            out.rbrick[r] = id;
+                            out.bcell[fill] = (int)r;
+                            out.btree[fill] = DENS[r];
+                            fill++;
+                        }
+                out.bricks.push_back(K);
+                if (K.nslot > out.max_slots) out.max_slots = K.nslot;
+            }
+    out.ok = true;
+    return true;
 }
 
 #endif  // SOC_LBRICKS_H
