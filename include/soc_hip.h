@@ -437,11 +437,46 @@ int soc_a2e_pre(soc_ctx *ctx, int NFREQ, int NE, float FACTOR, const float *FREQ
 
 /* replaces kernel_T(...) + the per-frequency kernel_emission(...) launches of SolveEquilibriumDust for one batch of cells
  * (A2E_MABU.py:520-560,608 -> kernel_eqsolver.c EqTemperature :5-62, Emission :66-79): ABS is [batch*NFREQ], the share of
- * the absorptions taken by this dust component (split_absorbed, kernel_A2E_MABU_aux.c:3-23, is done on the host side of
- * soc_amd/driver.py); TTT holds NE temperatures; outputs T[batch] and EMIT[batch*NFREQ] per unit density and abundance */
+ * the absorptions taken by this dust component (split_absorbed, kernel_A2E_MABU_aux.c:3-23, is done by the caller:
+ * soc_amd/mabu.py, host path); TTT holds NE temperatures; outputs T[batch] and EMIT[batch*NFREQ] per unit density and abundance */
 int soc_eqsolver(soc_ctx *ctx, int batch, int icell, int CELLS, int NFREQ, int NE, float FACTOR, float kE,
                  float oplgkE, float Emin, const float *FREQ, const float *KABS, const float *TTT,
                  const float *ABS, float *T, float *EMIT);
+
+/* ---- the whole multi-dust stage with the cells RESIDENT in device memory: A2E_MABU.py:700-1140 ---- */
+
+/* The reference keeps the absorptions on the host, and for every dust component uploads them in batches, splits them
+ * (kernel_A2E_MABU_aux.c:3-23 through A2E_MABU.py:760-800), writes the share to a file, runs a solver program on it and adds
+ * the emission it reads back, weighted by the abundances (A2E_MABU.py:1128-1140).  Here the arrays stay on the device from the
+ * absorbed file to the sum:
+ *   soc_mabu_begin(cells, NFREQ, NDUST, &fit) reserves the absorptions as the absorbed file holds them, the current dust's share
+ *       PART and its emission EM (the arrays of soc_a2e_resident_*: that family's _solve works on them in place, its _upload
+ *       and _download write rows of PART and read rows of EM, its _begin and _end are refused with SOC_ERR_STATE until
+ *       soc_mabu_end -- as soc_mabu_begin is while a soc_a2e_resident_begin is open; a second soc_mabu_begin replaces the
+ *       first), the zeroed sum SUM (cells*NFREQ floats each), ABU[cells*NDUST] and
+ *       RABS[NFREQ*NDUST] (double).  *fit (may be NULL) receives the number of cells that fit the free device memory; when
+ *       `cells` do not, the call fails with SOC_ERR_STATE and the caller solves the cells in ranges of at most *fit;
+ *   soc_mabu_upload(c0, n, ABS) fills rows [c0, c0+n) of the absorptions (any chunking: a memory-mapped absorbed file);
+ *   soc_mabu_set_tables(ABU, RABS) uploads the abundances of the resident cells and the relative cross sections
+ *       (A2E_MABU.py:245-342), once;
+ *   soc_mabu_split(idust, clip_last) computes PART = ABS * RABS[:, idust] / sum_j ABU[:, j] * RABS[:, j] with the types of
+ *       kernel_A2E_MABU_aux.c:3-23 (products in double, the sum rounded to float after every dust, the quotient in double) and
+ *       zeroes EM; clip_last != 0 then clips the last channel of PART as A2E.py:184-185 does in front of the stochastic solver;
+ *   soc_mabu_solve_eq(...) is soc_eqsolver (A2E_MABU.py:520-560,608 -> kernel_eqsolver.c:5-79) on PART, its emission left in EM;
+ *       a stochastically heated dust is solved with soc_a2e_set_size + soc_a2e_resident_solve per grain size instead
+ *       (A2E.py:520-600), which add to EM;
+ *   soc_mabu_accumulate(idust) adds EM * ABU[:, idust] to SUM: float product, float sum (A2E_MABU.py:1128-1140);
+ *   soc_mabu_download(c0, n, SUM) reads rows of the sum; soc_mabu_read_part rows of PART (tests); soc_mabu_end frees it all. */
+int soc_mabu_begin(soc_ctx *ctx, int64_t cells, int NFREQ, int NDUST, int64_t *cells_fit);
+int soc_mabu_upload(soc_ctx *ctx, int64_t c0, int64_t n, const float *ABS);
+int soc_mabu_set_tables(soc_ctx *ctx, const float *ABU, const double *RABS);
+int soc_mabu_split(soc_ctx *ctx, int idust, int clip_last);
+int soc_mabu_solve_eq(soc_ctx *ctx, int NE, float FACTOR, float kE, float oplgkE, float Emin, const float *FREQ,
+                      const float *KABS, const float *TTT);
+int soc_mabu_accumulate(soc_ctx *ctx, int idust);
+int soc_mabu_download(soc_ctx *ctx, int64_t c0, int64_t n, float *SUM);
+int soc_mabu_read_part(soc_ctx *ctx, int64_t c0, int64_t n, float *PART);
+int soc_mabu_end(soc_ctx *ctx);
 
 /* ---- verification probes (used by the parity tests only) ---- */
 /* RNG stream states and first draws of logical work items [gid_first, gid_first+n)

@@ -113,6 +113,12 @@ struct soc_ctx {
     float *aAll = nullptr, *aSum = nullptr;                  // soc_a2e_resident_*: absorptions of all cells, emission summed over the sizes
     int64_t a2e_cells = 0;  int a2e_res_nfreq = 0;
     int   *aFirst = nullptr, *aLast = nullptr, *aIwOff = nullptr, *aDst = nullptr, *aIbeg = nullptr;
+    // the multi-dust stage (soc_mabu_*): absorptions as the absorbed file holds them, the sum over the dusts, abundances, relative cross
+    // sections, temperatures and tables of an equilibrium dust; the current dust's share and its emission are aAll and aSum
+    float  *mABS = nullptr, *mSUM = nullptr, *mABU = nullptr, *mT = nullptr, *mTab = nullptr;
+    double *mRABS = nullptr;
+    int     mabu_ndust = 0, mtab_cap = 0;
+    bool    mabu_tables = false;
 };
 
 static std::string g_create_err;
@@ -348,7 +354,8 @@ void soc_destroy(soc_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     release_slots(c);
     void *bufs[] = { c->dOUTslots, c->dABU, c->dAF, c->dRoi, c->dRoiSave, c->dRoiLoad, c->dDENS, c->dPAR, c->dCSC, c->dDSC, c->dOPT, c->dEMIT, c->dEMWEI, c->dXAB, c->dINTV, c->dEMINDEX, c->dSeedTab, c->dStats, c->dODIR, c->dORA, c->dODE, c->dHPBG, c->dHPBGP, c->dT, c->dTTT, c->dEbuf, c->dEF, c->dMapEmit, c->dMap, c->dMapTau,
-                     c->aIw, c->aTdown, c->aEA, c->aAF, c->aABS, c->aEMIT, c->aAll, c->aSum, c->aFirst, c->aLast, c->aIwOff, c->aDst, c->aIbeg };
+                     c->aIw, c->aTdown, c->aEA, c->aAF, c->aABS, c->aEMIT, c->aAll, c->aSum, c->aFirst, c->aLast, c->aIwOff, c->aDst, c->aIbeg,
+                     c->mABS, c->mSUM, c->mABU, c->mT, c->mTab, c->mRABS };
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (c->own_TABS && c->dTABS) (void)hipFree(c->dTABS);
     if (c->own_INT && c->dINT) (void)hipFree(c->dINT);
@@ -1887,6 +1894,7 @@ int soc_a2e_resident_begin(soc_ctx *c, int64_t cells, int NFREQ)
     if (!c) return SOC_ERR_ARG;
     FLUSH(c);
     if (cells < 1 || NFREQ < 2 || cells > (int64_t)2147483647) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_begin: cells=%lld NFREQ=%d", (long long)cells, NFREQ);
+    if (c->mABS) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_begin: the resident arrays are those of soc_mabu_begin (soc_mabu_end first)");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     size_t free_b = 0, total_b = 0;
@@ -1945,6 +1953,7 @@ int soc_a2e_resident_download(soc_ctx *c, int64_t c0, int64_t n, float *AEMIT)
 int soc_a2e_resident_end(soc_ctx *c)
 {
     if (!c) return SOC_ERR_ARG;
+    if (c->mABS) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_end: the resident arrays are those of soc_mabu_begin (soc_mabu_end frees them)");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->aAll) { (void)hipFree(c->aAll);  c->aAll = nullptr; }
@@ -2005,6 +2014,170 @@ int soc_eqsolver(soc_ctx *c, int batch, int icell, int CELLS, int NFREQ, int NE,
                  const float *ABS, float *T, float *EMIT)
 {
     return eqtemp_common(c, "soc_eqsolver", true, batch, icell, CELLS, NFREQ, NE, FACTOR, kE, oplgkE, Emin, FREQ, KABS, TTT, ABS, T, EMIT);
+}
+
+// ---- the multi-dust stage with the cells resident in HBM (A2E_MABU.py:700-1140) ----
+static void mabu_release(soc_ctx *c)
+{
+    void **bufs[] = { (void **)&c->mABS, (void **)&c->mSUM, (void **)&c->mABU, (void **)&c->mT, (void **)&c->mTab, (void **)&c->mRABS,
+                      (void **)&c->aAll, (void **)&c->aSum };
+    for (void **b : bufs) if (*b) { (void)hipFree(*b);  *b = nullptr; }
+    c->a2e_cells = 0;  c->mabu_ndust = 0;  c->mtab_cap = 0;  c->mabu_tables = false;
+}
+
+int soc_mabu_begin(soc_ctx *c, int64_t cells, int NFREQ, int NDUST, int64_t *cells_fit)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (cells_fit) *cells_fit = 0;
+    if (cells < 1 || NFREQ < 2 || NDUST < 1 || cells > (int64_t)2147483647 || (size_t)NFREQ * NDUST * sizeof(double) > SOC_MABU_LDS)
+        return fail(c, SOC_ERR_ARG, "soc_mabu_begin: cells=%lld NFREQ=%d NDUST=%d (NFREQ x NDUST doubles must fit %d KB of LDS)",
+                    (long long)cells, NFREQ, NDUST, SOC_MABU_LDS / 1024);
+    if (c->aAll && !c->mABS) return fail(c, SOC_ERR_STATE, "soc_mabu_begin: the resident arrays are those of an open soc_a2e_resident_begin (soc_a2e_resident_end first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    mabu_release(c);                                        // (a soc_mabu_begin that is still open is replaced)
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    // per cell: absorptions, the dust's share, its emission, the sum (NFREQ floats each), NDUST abundances, a temperature
+    const size_t per_cell = (size_t)NFREQ * 16 + (size_t)NDUST * 4 + 4, reserve = (size_t)1 << 30;
+    const size_t need = (size_t)cells * per_cell;
+    if (cells_fit) *cells_fit = free_b > reserve ? (int64_t)((free_b - reserve) / per_cell) : 0;
+    if (need + reserve > free_b)
+        return fail(c, SOC_ERR_STATE, "soc_mabu_begin: %lld cells x %d frequencies x %d dusts need %.1f GB of device memory, %.1f GB are free (%lld cells fit: solve the cells in ranges)",
+                    (long long)cells, NFREQ, NDUST, need * 1e-9, free_b * 1e-9, (long long)(free_b > reserve ? (free_b - reserve) / per_cell : 0));
+    const size_t n = (size_t)cells * NFREQ;
+    hipError_t e = dev_alloc(&c->mABS, n);
+    if (e == hipSuccess) e = dev_alloc(&c->aAll, n);
+    if (e == hipSuccess) e = dev_alloc(&c->aSum, n);
+    if (e == hipSuccess) e = dev_alloc(&c->mSUM, n);
+    if (e == hipSuccess) e = dev_alloc(&c->mABU, (size_t)cells * NDUST);
+    if (e == hipSuccess) e = dev_alloc(&c->mT, (size_t)cells);
+    if (e == hipSuccess) e = dev_alloc(&c->mRABS, (size_t)NFREQ * NDUST);
+    if (e == hipSuccess) e = hipMemsetAsync(c->mSUM, 0, n * 4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->aSum, 0, n * 4, c->stream);
+    if (e != hipSuccess) {
+        mabu_release(c);
+        return fail(c, SOC_ERR_HIP, "soc_mabu_begin: %s", hipGetErrorString(e));
+    }
+    c->a2e_cells = cells;  c->a2e_res_nfreq = NFREQ;  c->mabu_ndust = NDUST;
+    return SOC_OK;
+}
+
+#define MABU_OPEN(c, who)                                                                                   \
+    do {                                                                                                    \
+        if (!(c)->mABS || !(c)->aAll || !(c)->aSum) return fail((c), SOC_ERR_STATE, who ": call soc_mabu_begin first");   \
+    } while (0)
+#define MABU_ROWS(c, who, c0, n)                                                                            \
+    do {                                                                                                    \
+        if ((c0) < 0 || (n) < 1 || (c0) + (n) > (c)->a2e_cells)                                             \
+            return fail((c), SOC_ERR_ARG, who ": cells [%lld, %lld) of %lld", (long long)(c0), (long long)((c0) + (n)), (long long)(c)->a2e_cells);   \
+    } while (0)
+
+int soc_mabu_upload(soc_ctx *c, int64_t c0, int64_t n, const float *ABS)
+{
+    if (!c || !ABS) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_upload");
+    MABU_ROWS(c, "soc_mabu_upload", c0, n);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(c->mABS + (size_t)c0 * c->a2e_res_nfreq, ABS, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host buffer may be a temporary)
+    return SOC_OK;
+}
+
+int soc_mabu_set_tables(soc_ctx *c, const float *ABU, const double *RABS)
+{
+    if (!c || !ABU || !RABS) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_set_tables");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(c->mABU, ABU, (size_t)c->a2e_cells * c->mabu_ndust * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->mRABS, RABS, (size_t)c->a2e_res_nfreq * c->mabu_ndust * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mabu_tables = true;
+    return SOC_OK;
+}
+
+int soc_mabu_split(soc_ctx *c, int idust, int clip_last)
+{
+    if (!c) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_split");
+    if (!c->mabu_tables) return fail(c, SOC_ERR_STATE, "soc_mabu_split: call soc_mabu_set_tables first");
+    if (idust < 0 || idust >= c->mabu_ndust) return fail(c, SOC_ERR_ARG, "soc_mabu_split: dust %d of %d", idust, c->mabu_ndust);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int NFREQ = c->a2e_res_nfreq;
+    HIPCHK(c, soc_launch_mabu_split(c->a2e_cells, NFREQ, c->mabu_ndust, idust, c->mABS, c->mABU, c->mRABS, c->aAll, c->stream));
+    if (clip_last) HIPCHK(c, soc_launch_mabu_clip(c->a2e_cells, NFREQ, c->aAll, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->aSum, 0, (size_t)c->a2e_cells * NFREQ * 4, c->stream));
+    return SOC_OK;
+}
+
+int soc_mabu_solve_eq(soc_ctx *c, int NE, float FACTOR, float kE, float oplgkE, float Emin, const float *FREQ, const float *KABS, const float *TTT)
+{
+    if (!c) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_solve_eq");
+    if (NE < 2 || !FREQ || !KABS || !TTT) return fail(c, SOC_ERR_ARG, "soc_mabu_solve_eq: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int NFREQ = c->a2e_res_nfreq;
+    if (2 * NFREQ + NE > c->mtab_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, dev_alloc(&c->mTab, (size_t)2 * NFREQ + NE));
+        c->mtab_cap = 2 * NFREQ + NE;
+    }
+    float *dF = c->mTab, *dK = dF + NFREQ, *dT3 = dK + NFREQ;
+    HIPCHK(c, hipMemcpyAsync(dF, FREQ, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dK, KABS, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dT3, TTT, (size_t)NE * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host tables may be temporaries)
+    SocEqTArgs A{};
+    A.batch = (int)c->a2e_cells;  A.icell = 0;  A.CELLS = (int)c->a2e_cells;  A.NFREQ = NFREQ;  A.NIP = NE;
+    A.FACTOR = FACTOR;  A.kE = kE;  A.oplgkE = oplgkE;  A.Emin = Emin;
+    A.FREQ = dF;  A.KABS = dK;  A.TTT = dT3;  A.ABS = c->aAll;  A.T = c->mT;  A.EMIT = c->aSum;
+    HIPCHK(c, soc_launch_eqsolver(A, c->stream));
+    return SOC_OK;
+}
+
+int soc_mabu_accumulate(soc_ctx *c, int idust)
+{
+    if (!c) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_accumulate");
+    if (!c->mabu_tables) return fail(c, SOC_ERR_STATE, "soc_mabu_accumulate: call soc_mabu_set_tables first");
+    if (idust < 0 || idust >= c->mabu_ndust) return fail(c, SOC_ERR_ARG, "soc_mabu_accumulate: dust %d of %d", idust, c->mabu_ndust);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, soc_launch_mabu_sum(c->a2e_cells, c->a2e_res_nfreq, c->mabu_ndust, idust, c->aSum, c->mABU, c->mSUM, c->stream));
+    return SOC_OK;
+}
+
+static int mabu_read(soc_ctx *c, const float *src, int64_t c0, int64_t n, float *out)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, src + (size_t)c0 * c->a2e_res_nfreq, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
+int soc_mabu_download(soc_ctx *c, int64_t c0, int64_t n, float *SUM)
+{
+    if (!c || !SUM) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_download");
+    MABU_ROWS(c, "soc_mabu_download", c0, n);
+    return mabu_read(c, c->mSUM, c0, n, SUM);
+}
+
+int soc_mabu_read_part(soc_ctx *c, int64_t c0, int64_t n, float *PART)
+{
+    if (!c || !PART) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_read_part");
+    MABU_ROWS(c, "soc_mabu_read_part", c0, n);
+    return mabu_read(c, c->aAll, c0, n, PART);
+}
+
+int soc_mabu_end(soc_ctx *c)
+{
+    if (!c) return SOC_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->mABS) mabu_release(c);
+    return SOC_OK;
 }
 
 int soc_a2e_pre(soc_ctx *c, int NFREQ, int NE, float FACTOR, const float *FREQ, const float *Ef, const float *SKABS, const float *E,

@@ -176,6 +176,14 @@ hipError_t soc_launch_a2e_dosolve(const SocA2EArgs &A, hipStream_t st);
 hipError_t soc_launch_a2e_eqtemp(const SocEqTArgs &A, hipStream_t st);
 hipError_t soc_launch_eqsolver(const SocEqTArgs &A, hipStream_t st);
 
+// the multi-dust emission stage (soc_mabu.hip): split of the absorptions between the dust components, clip of the last channel
+// in front of the stochastic solver, abundance-weighted sum of the emission.  RABS[NFREQ][NDUST] (double) must fit SOC_MABU_LDS.
+#define SOC_MABU_LDS (64 * 1024)
+hipError_t soc_launch_mabu_split(long long cells, int NFREQ, int NDUST, int idust, const float *ABS, const float *ABU, const double *RABS,
+                                 float *PART, hipStream_t st);
+hipError_t soc_launch_mabu_clip(long long cells, int NFREQ, float *PART, hipStream_t st);
+hipError_t soc_launch_mabu_sum(long long cells, int NFREQ, int NDUST, int idust, const float *EM, const float *ABU, float *SUM, hipStream_t st);
+
 // Shape of the brick sweep; 0 = the built-in choice for the grid (measured).  Set per context with
 // soc_set_tuning (include/soc_hip.h); the parity tests use small CAP / HS values to exercise brick boundaries.
 struct SocBrickTune {

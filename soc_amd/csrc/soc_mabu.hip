@@ -1,0 +1,147 @@
+// soc_mabu.hip -- the streaming kernels of the multi-dust emission stage (A2E_MABU.py): the split of the absorptions
+// between the dust components (kernel_A2E_MABU_aux.c:3-23), the clip of the last channel in front of the stochastic
+// solver (A2E.py:184-185) and the abundance-weighted sum of the components' emission (A2E_MABU.py:1128-1140).
+//
+// The arrays are [cell][frequency] row-major with NFREQ around 50, so the reference's loop -- one work item per cell
+// that walks its frequencies -- reads with a stride of a row between neighbouring lanes.  Here the array is taken flat: a
+// tile is 1024 consecutive floats, a lane its four consecutive ones (one 16-byte load and store), consecutive lanes
+// consecutive 16 bytes; cell and frequency of an element follow from its flat index.  A grid of at most 2048 workgroups
+// strides over the tiles and carries the (cell, frequency) of its tile's first element along, so that the 64-bit
+// division happens once per workgroup.  RABS (NFREQ x NDUST doubles) sits in LDS; a cell's abundances come through the
+// cache (4 x NDUST bytes per cell from memory).
+#include "soc_dev.h"
+
+#define MABU_T    256
+#define MABU_TILE (MABU_T * 4)
+
+// first element of the workgroup's tiles as (cell, frequency), and the step from one tile of the workgroup to its next
+struct MabuWalk {
+    long long q;           // cell of the tile's first element
+    int r, dq, dr;         // its frequency; cells and frequencies the stride adds
+    __device__ MabuWalk(long long tile, int NFREQ)
+    {
+        const long long i0 = tile * MABU_TILE;
+        q = i0 / NFREQ;  r = (int)(i0 - q * NFREQ);
+        const long long S = (long long)gridDim.x * MABU_TILE;
+        dq = (int)(S / NFREQ);  dr = (int)(S - (long long)dq * NFREQ);
+    }
+    __device__ void next(int NFREQ)
+    {
+        q += dq;  r += dr;
+        if (r >= NFREQ) { r -= NFREQ;  q++; }
+    }
+};
+
+// PART = ABS * RABS[:, idust] / den, den = sum_j ABU[:, j] * RABS[:, j]: every product in double, den rounded to float
+// after each addition (dusts in index order), the quotient taken in double and rounded once
+__device__ __forceinline__ float mabu_part(float a, const float *abu, const double *R, int NDUST, int idust)
+{
+    float den = 0.0f;
+    for (int j = 0; j < NDUST; j++) den = (float)((double)den + (double)abu[j] * R[j]);
+    return (float)((double)a * R[idust] / (double)den);
+}
+
+__global__ __launch_bounds__(MABU_T) void soc_mabu_split_kernel(long long N, int NFREQ, int NDUST, int idust, const float *__restrict__ ABS,
+                                                                const float *__restrict__ ABU, const double *__restrict__ RABS,
+                                                                float *__restrict__ PART)
+{
+    extern __shared__ double sR[];                                     // RABS[NFREQ][NDUST]
+    for (int i = threadIdx.x; i < NFREQ * NDUST; i += MABU_T) sR[i] = RABS[i];
+    __syncthreads();
+    const long long tiles = (N + MABU_TILE - 1) / MABU_TILE;
+    MabuWalk W(blockIdx.x, NFREQ);
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x, W.next(NFREQ)) {
+        const long long i = tile * MABU_TILE + threadIdx.x * 4;
+        if (i >= N) continue;
+        const unsigned t = (unsigned)W.r + threadIdx.x * 4u;           // < NFREQ + 1024
+        long long c = W.q + t / (unsigned)NFREQ;
+        int f = (int)(t % (unsigned)NFREQ);
+        float v[4];
+        const bool whole = i + 3 < N;
+        if (whole) { const float4 x = *(const float4 *)(ABS + i);  v[0] = x.x;  v[1] = x.y;  v[2] = x.z;  v[3] = x.w; }
+        else for (int k = 0; k < 4; k++) v[k] = i + k < N ? ABS[i + k] : 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (i + k < N) v[k] = mabu_part(v[k], ABU + c * NDUST, sR + f * NDUST, NDUST, idust);
+            if (++f == NFREQ) { f = 0;  c++; }
+        }
+        if (whole) *(float4 *)(PART + i) = make_float4(v[0], v[1], v[2], v[3]);
+        else for (int k = 0; k < 4; k++) if (i + k < N) PART[i + k] = v[k];
+    }
+}
+
+// SUM += EM * ABU[:, idust]: the float product rounded, then the float addition (the two roundings of the host's
+// EMITTED += em * ABU[:, idust]; the build has -ffp-contract=off, so no fma)
+__global__ __launch_bounds__(MABU_T) void soc_mabu_sum_kernel(long long N, int NFREQ, int NDUST, int idust, const float *__restrict__ EM,
+                                                              const float *__restrict__ ABU, float *__restrict__ SUM)
+{
+    const long long tiles = (N + MABU_TILE - 1) / MABU_TILE;
+    MabuWalk W(blockIdx.x, NFREQ);
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x, W.next(NFREQ)) {
+        const long long i = tile * MABU_TILE + threadIdx.x * 4;
+        if (i >= N) continue;
+        const unsigned t = (unsigned)W.r + threadIdx.x * 4u;
+        long long c = W.q + t / (unsigned)NFREQ;
+        int f = (int)(t % (unsigned)NFREQ);
+        float e[4], s[4];
+        const bool whole = i + 3 < N;
+        if (whole) {
+            const float4 x = *(const float4 *)(EM + i), y = *(const float4 *)(SUM + i);
+            e[0] = x.x;  e[1] = x.y;  e[2] = x.z;  e[3] = x.w;  s[0] = y.x;  s[1] = y.y;  s[2] = y.z;  s[3] = y.w;
+        } else for (int k = 0; k < 4; k++) { e[k] = i + k < N ? EM[i + k] : 0.0f;  s[k] = i + k < N ? SUM[i + k] : 0.0f; }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (i + k < N) { const float p = e[k] * ABU[c * NDUST + idust];  s[k] = s[k] + p; }
+            if (++f == NFREQ) { f = 0;  c++; }
+        }
+        if (whole) *(float4 *)(SUM + i) = make_float4(s[0], s[1], s[2], s[3]);
+        else for (int k = 0; k < 4; k++) if (i + k < N) SUM[i + k] = s[k];
+    }
+}
+
+// A2E.py:184-185 on the device: PART[:, NFREQ-1] = clip(PART[:, NFREQ-1], 0, 0.2 * PART[:, NFREQ-2]) with numpy's clip --
+// min(max(x, lo), hi), a NaN in x kept, a NaN in hi taken.  One lane per cell: two neighbouring words of its row.
+__global__ void soc_mabu_clip_kernel(long long cells, int NFREQ, float *PART)
+{
+    for (long long c = blockIdx.x * (long long)blockDim.x + threadIdx.x; c < cells; c += (long long)gridDim.x * blockDim.x) {
+        float *row = PART + c * NFREQ;
+        const float x = row[NFREQ - 1], hi = 0.2f * row[NFREQ - 2];
+        const float t = (x != x) ? x : (x > 0.0f ? x : 0.0f);
+        row[NFREQ - 1] = (t != t) ? t : (t < hi ? t : hi);
+    }
+}
+
+static int mabu_grid(long long N)
+{
+    const long long tiles = (N + MABU_TILE - 1) / MABU_TILE;
+    return (int)(tiles < 2048 ? tiles : 2048);                          // 256 CUs x 8 workgroups; the rest by the stride
+}
+
+hipError_t soc_launch_mabu_split(long long cells, int NFREQ, int NDUST, int idust, const float *ABS, const float *ABU, const double *RABS,
+                                 float *PART, hipStream_t st)
+{
+    if (cells <= 0) return hipSuccess;
+    const size_t lds = (size_t)NFREQ * NDUST * sizeof(double);
+    if (NFREQ < 1 || NDUST < 1 || idust < 0 || idust >= NDUST || lds > SOC_MABU_LDS) return hipErrorInvalidValue;
+    const long long N = cells * NFREQ;
+    soc_mabu_split_kernel<<<mabu_grid(N), MABU_T, lds, st>>>(N, NFREQ, NDUST, idust, ABS, ABU, RABS, PART);
+    return hipGetLastError();
+}
+
+hipError_t soc_launch_mabu_sum(long long cells, int NFREQ, int NDUST, int idust, const float *EM, const float *ABU, float *SUM, hipStream_t st)
+{
+    if (cells <= 0) return hipSuccess;
+    if (NFREQ < 1 || NDUST < 1 || idust < 0 || idust >= NDUST) return hipErrorInvalidValue;
+    const long long N = cells * NFREQ;
+    soc_mabu_sum_kernel<<<mabu_grid(N), MABU_T, 0, st>>>(N, NFREQ, NDUST, idust, EM, ABU, SUM);
+    return hipGetLastError();
+}
+
+hipError_t soc_launch_mabu_clip(long long cells, int NFREQ, float *PART, hipStream_t st)
+{
+    if (cells <= 0) return hipSuccess;
+    if (NFREQ < 2) return hipErrorInvalidValue;
+    const long long blocks = (cells + 255) / 256;
+    soc_mabu_clip_kernel<<<(int)(blocks < 16384 ? blocks : 16384), 256, 0, st>>>(cells, NFREQ, PART);
+    return hipGetLastError();
+}

@@ -16,6 +16,8 @@ TALLY_INT = 1
 TALLY_XAB = 2
 TALLY_INTX, TALLY_INTY, TALLY_INTZ = 3, 4, 5      # with_int == 2 (SAVE_INTENSITY 2)
 
+SOC_OK, SOC_ERR_ARG, SOC_ERR_STATE, SOC_ERR_HIP = 0, -1, -2, -3      # include/soc_hip.h
+
 _F = C.POINTER(C.c_float)
 _I = C.POINTER(C.c_int32)
 _U = C.POINTER(C.c_uint32)
@@ -115,6 +117,15 @@ API = {
                                  C.c_float, C.c_float, _F, _F, _F, _F, _F, _F]),
     "soc_eqsolver": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                C.c_float, C.c_float, _F, _F, _F, _F, _F, _F]),
+    "soc_mabu_begin": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "soc_mabu_upload": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
+    "soc_mabu_set_tables": (C.c_int, [C.c_void_p, _F, C.POINTER(C.c_double)]),
+    "soc_mabu_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "soc_mabu_solve_eq": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _F, _F, _F]),
+    "soc_mabu_accumulate": (C.c_int, [C.c_void_p, C.c_int]),
+    "soc_mabu_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
+    "soc_mabu_read_part": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
+    "soc_mabu_end": (C.c_int, [C.c_void_p]),
     "soc_probe_rng": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_int, _U, _U]),
     "soc_probe_math": (C.c_int, [C.c_void_p, C.c_int, _F, _F, C.c_int64]),
     "soc_probe_trace": (C.c_int, [C.c_void_p, _F, _F, C.c_int, _I, _I, _F, _F, _I]),
@@ -137,6 +148,14 @@ def decode_variant(code):
 
 class SocError(RuntimeError):
     pass
+
+
+class DoesNotFit(SocError):
+    """mabu_begin: the cells do not fit the free device memory; cells_fit of them would"""
+
+    def __init__(self, text, cells_fit):
+        SocError.__init__(self, text)
+        self.cells_fit = int(cells_fit)
 
 
 def _torch_runtime_first():
@@ -200,6 +219,7 @@ class Engine:
         self.device = int(device)
         self.CELLS = 0
         self.NPAR = 0
+        self._mabu = None                                  # (cells, NFREQ, NDUST) between mabu_begin and mabu_end
 
     def close(self):
         if getattr(self, "h", None):
@@ -732,6 +752,69 @@ class Engine:
                                           np.float32(kE), np.float32(oplgkE), np.float32(Emin), _f(FREQ), _f(KABS),
                                           _f(TTT), _f(ABS), _f(T), _f(E)))
         return T, E
+
+    # ---- the multi-dust stage with the cells resident in device memory (soc_mabu_*; driven by soc_amd.mabu.solve_emission) ----
+    def mabu_begin(self, cells, NFREQ, NDUST):
+        fit = C.c_int64(0)
+        rc = self.lib.soc_mabu_begin(self.h, int(cells), int(NFREQ), int(NDUST), C.byref(fit))
+        if rc == SOC_ERR_STATE and 0 < fit.value < int(cells):    # with a cell count: not enough device memory
+            raise DoesNotFit("%s (code %d)" % (self.lib.soc_last_error(self.h).decode(), rc), fit.value)
+        self._chk(rc)
+        self._mabu = (int(cells), int(NFREQ), int(NDUST))
+
+    def _mabu_open(self, who):
+        """(cells, NFREQ, NDUST) of the open mabu_begin"""
+        if self._mabu is None:
+            raise SocError("%s: call mabu_begin first" % who)
+        return self._mabu
+
+    def mabu_upload(self, c0, ABS):
+        NFREQ = self._mabu_open("mabu_upload")[1]
+        ABS = np.ascontiguousarray(ABS, np.float32)
+        if ABS.ndim != 2 or ABS.shape[1] != NFREQ:
+            raise SocError("mabu_upload: an array of shape %s for rows of %d frequencies" % (ABS.shape, NFREQ))
+        self._chk(self.lib.soc_mabu_upload(self.h, int(c0), ABS.shape[0], _f(ABS)))
+
+    def mabu_set_tables(self, ABU, RABS):
+        cells, NFREQ, NDUST = self._mabu_open("mabu_set_tables")
+        ABU, RABS = np.ascontiguousarray(ABU, np.float32), np.ascontiguousarray(RABS, np.float64)
+        if ABU.shape != (cells, NDUST) or RABS.shape != (NFREQ, NDUST):
+            raise SocError("mabu_set_tables: ABU%s, RABS%s for %d cells, %d frequencies, %d dusts" % (ABU.shape, RABS.shape, cells, NFREQ, NDUST))
+        self._chk(self.lib.soc_mabu_set_tables(self.h, _f(ABU), RABS.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def mabu_split(self, idust, clip_last=False):
+        self._chk(self.lib.soc_mabu_split(self.h, int(idust), int(bool(clip_last))))
+
+    def mabu_solve_eq(self, NE, FACTOR, kE, oplgkE, Emin, FREQ, KABS, TTT):
+        NFREQ = self._mabu_open("mabu_solve_eq")[1]
+        FREQ, KABS, TTT = (np.ascontiguousarray(a, np.float32) for a in (FREQ, KABS, TTT))
+        if FREQ.size != NFREQ or KABS.size != NFREQ or TTT.size != int(NE):
+            raise SocError("mabu_solve_eq: FREQ, KABS must hold %d floats, TTT %d" % (NFREQ, int(NE)))
+        self._chk(self.lib.soc_mabu_solve_eq(self.h, int(NE), np.float32(FACTOR), np.float32(kE), np.float32(oplgkE), np.float32(Emin),
+                                             _f(FREQ), _f(KABS), _f(TTT)))
+
+    def mabu_accumulate(self, idust):
+        self._chk(self.lib.soc_mabu_accumulate(self.h, int(idust)))
+
+    def mabu_download(self, c0, n, out=None):
+        """rows [c0, c0 + n) of the sum; out: a C-contiguous float32 array [n, NFREQ] to fill (anything else is refused)"""
+        NFREQ = self._mabu_open("mabu_download")[1]
+        if out is None:
+            out = np.zeros((int(n), NFREQ), np.float32)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable
+                  and out.shape == (int(n), NFREQ)):
+            raise SocError("mabu_download: out must be a writeable C-contiguous float32 array of shape (%d, %d)" % (int(n), NFREQ))
+        self._chk(self.lib.soc_mabu_download(self.h, int(c0), int(n), _f(out)))
+        return out
+
+    def mabu_read_part(self, c0, n):
+        out = np.zeros((int(n), self._mabu_open("mabu_read_part")[1]), np.float32)
+        self._chk(self.lib.soc_mabu_read_part(self.h, int(c0), int(n), _f(out)))
+        return out
+
+    def mabu_end(self):
+        self._chk(self.lib.soc_mabu_end(self.h))
+        self._mabu = None
 
     # ---- probes ----
     def probe_rng(self, SEED, gid_first, n, ndraw):

@@ -1,0 +1,322 @@
+#!/usr/bin/env python3
+"""mabu -- emission of a model with several dust components from its absorptions:
+
+    python -m soc_amd.mabu  soc.ini  absorbed.data  emitted.data
+
+Counterpart of ``A2E_MABU.py ini absorbed.data emitted.data`` (reference A2E_MABU.py:236-342, 700-1180): the dust list,
+the abundance files and `singleabu` come from the ini, an equilibrium dust is solved from its dust file, a
+stochastically heated one (gsetdust) from its <dust>.solver file (soc_amd.a2e_pre writes it).  For every dust the
+absorptions are split in proportion to cross section x abundance (kernel_A2E_MABU_aux.c:3-23), the emission of that
+share is solved, and the emissions are summed weighted by the abundances (A2E_MABU.py:1128-1140).
+
+solve_emission is that stage, shared with soc_amd.driver.  With an engine that has the soc_mabu_* calls the arrays stay
+in device memory from the absorbed file to the sum (the absorptions go up once, the sum comes down once); with any
+other engine the stage runs as numpy around the engine's per-dust solvers.  The two give the same bits.
+
+With N GPUs (python -m torch.distributed.run --nproc-per-node N -m soc_amd.mabu ...) every rank solves its share of
+the cells and writes its rows of the emitted file.  The reference's optional fourth argument (ofreq.dat: emission on a
+subset of the frequencies) and the library / neural-network shortcuts are refused.
+"""
+import os
+import sys
+import time
+
+import numpy as np
+from scipy.interpolate import interp1d
+
+from . import a2e, files
+from .asoc import UnsupportedOption
+from .ini import User
+from .launch import FACTOR
+from .lib import DoesNotFit
+from .synth import a2e_absorption_fraction
+
+NE_EQ = 30000                    # A2E_MABU.py:478
+REFUSED_KEYS = ('nnmake', 'nnsolve', 'nnabs', 'nnemit', 'nnthin', 'absthin', 'libabs', 'libmaps', 'aalg', 'crheating')
+CHUNK = 1 << 20                  # cells per upload / download call
+
+
+def refuse(U):
+    bad = [k for k in REFUSED_KEYS if k in U.KEYS]
+    if bad:
+        raise UnsupportedOption("ini options outside the in-memory pipeline (neural-network / library shortcuts, "
+                                "polarisation, cosmic-ray heating): " + ", ".join(bad))
+
+
+def dust_kind(name):
+    """'gsetdust' (stochastically heated: needs <name>.solver) or 'eqdust' (ASOC_driver.py:66-68)"""
+    with open(name) as fp:
+        return fp.readline().split()[0]
+
+
+def simple_name(name):
+    """the dust file the transfer run uses for a gsetdust (ASOC_driver.py:247-248: prefix gs_ dropped, _simple added)"""
+    d, b = os.path.split(name)
+    return os.path.join(d, '%s_simple.dust' % b.replace('.dust', '').replace('gs_', ''))
+
+
+def solver_name(name):
+    """ASOC_driver.py:199-201 / A2E_MABU.py:264"""
+    d, b = os.path.split(name)
+    b = b.replace('.dust', '')
+    if b.startswith('gs_'):
+        b = b[3:]
+    return os.path.join(d, b + '.solver')
+
+
+def require_solvers(dusts, kinds):
+    """a solver file per stochastically heated dust -- soc_amd.a2e_pre writes them (ASOC_driver.py:196-228 calls A2E_pre.py there)"""
+    for d, k in zip(dusts, kinds):
+        if k == 'gsetdust' and not os.path.exists(solver_name(d)):
+            raise FileNotFoundError("%s: the solver file of %s is missing; write it with python -m soc_amd.a2e_pre %s <frequency file> %s"
+                                    % (solver_name(d), d, d, solver_name(d)))
+
+
+def planck_safe(f, T):
+    """A2E_MABU.py PlanckSafe: 2h f^3 / c^2 / (exp(hf/kT) - 1), overflow-safe"""
+    H_K, H_CC = 4.79924335e-11, 7.372496678e-48
+    return 2.0 * H_CC * f * f * f / (np.exp(np.clip(H_K * f / T, -100.0, 100.0)) - 1.0)
+
+
+def eq_dust_table(dust):
+    """E -> T table of an equilibrium dust (A2E_MABU.py:470-490): FREQ, KABS per unit density, Emin, kE, oplgkE, TTT[NE]"""
+    with open(dust) as fp:
+        lines = fp.readlines()
+    gd, gr = float(lines[1].split()[0]), float(lines[2].split()[0])
+    d = np.loadtxt(dust, skiprows=4, ndmin=2)
+    FREQ = np.asarray(d[:, 0], np.float32)
+    KABS = np.asarray(d[:, 2] * gd * np.pi * gr ** 2.0, np.float32)
+    TSTEP = 1600.0 / NE_EQ
+    TT = 1.0 + TSTEP * np.arange(NE_EQ)
+    F64 = np.asarray(FREQ, np.float64)
+    DF = FREQ[2:] - FREQ[:-2]
+    Eout = np.zeros(NE_EQ, np.float64)
+    # vectorised over the temperatures (the reference loops): same sums, frequency by frequency
+    B = KABS[None, :] * planck_safe(F64[None, :], TT[:, None])
+    res = B[:, 0] * (FREQ[1] - FREQ[0]) + B[:, -1] * (FREQ[-1] - FREQ[-2]) + np.sum(B[:, 1:-1] * DF[None, :], axis=1)
+    Eout[:] = (4.0 * np.pi * FACTOR) * 0.5 * res
+    Emin, Emax = Eout[0], Eout[NE_EQ - 1] * 0.9999
+    kE = (Emax / Emin) ** (1.0 / (NE_EQ - 1.0))
+    oplgkE = 1.0 / np.log10(kE)
+    TTT = np.asarray(interp1d(Eout, TT)(Emin * kE ** np.arange(NE_EQ)), np.float32)
+    return FREQ, KABS, Emin, kE, oplgkE, TTT
+
+
+def relative_cross_sections(dusts, kinds):
+    """RABS[NFREQ, NDUST] (A2E_MABU.py:245-342): absorption cross section per unit density of every component --
+    from the dust file (eqdust) or summed over the sizes of the solver file -- normalised per frequency, float64"""
+    cols, FREQ = [], None
+    for name, kind in zip(dusts, kinds):
+        if kind == 'eqdust':
+            with open(name) as fp:
+                lines = fp.readlines()
+            gd, radius = float(lines[1].split()[0]), float(lines[2].split()[0])
+            d = np.loadtxt(name, skiprows=4, ndmin=2)
+            FREQ = d[:, 0]
+            cols.append(np.pi * radius ** 2.0 * gd * d[:, 2])
+        else:
+            sol = files.read_solver(solver_name(name))
+            FREQ = np.asarray(sol["FREQ"], np.float64)
+            cols.append(np.sum(np.asarray(sol["SK_ABS"], np.float64), axis=0))
+    RABS = np.clip(np.asarray(cols, np.float64).T, 1.0e-40, 1.0e30)
+    RABS /= (1.0e-40 + RABS.sum(axis=1))[:, None]
+    return np.clip(RABS, 1.0e-30, 1.0), FREQ
+
+
+def split_absorbed(ABSORBED, RABS, ABU, idust):
+    """kernel_A2E_MABU_aux.c:3-23: OUT[c, f] = IN[c, f] * RABS[f, idust] / sum_j ABU[c, j] * RABS[f, j], with the kernel's
+    types: the denominator accumulates in float (each product formed in double), the quotient is taken in double"""
+    cells, nfreq = ABSORBED.shape
+    ndust = RABS.shape[1]
+    den = np.zeros((cells, nfreq), np.float32)
+    for j in range(ndust):
+        den = (den.astype(np.float64) + ABU[:, j:j + 1].astype(np.float64) * RABS[None, :, j]).astype(np.float32)
+    return (ABSORBED.astype(np.float64) * RABS[None, :, idust] / den.astype(np.float64)).astype(np.float32)
+
+
+def abundance_table(ABU, single, CELLS, NDUST):
+    """ABU[CELLS, NDUST] float32 from what files.read_abundances gave (None: no abundance file; with `singleabu` the first
+    column x and 1-x for the two dusts, ASOC.py:1148-1153): ones where no file is given"""
+    if ABU is None:
+        return np.ones((CELLS, NDUST), np.float32)
+    if single:
+        if NDUST != 2:
+            raise ValueError("singleabu assumes exactly two dust components")
+        x = np.ravel(np.asarray(ABU, np.float32).reshape(CELLS, -1)[:, 0])
+        return np.stack([x, 1.0 - x], axis=1).astype(np.float32)
+    return np.asarray(ABU, np.float32).reshape(CELLS, NDUST)
+
+
+# ---- the stage ------------------------------------------------------------------------------------------------------
+def _tables(dusts, kinds, NFREQ):
+    """per dust what its solver needs: eq_dust_table of an equilibrium dust, the solver file of a stochastically heated one"""
+    out = []
+    for d, k in zip(dusts, kinds):
+        if k == 'eqdust':
+            out.append(eq_dust_table(d))
+        else:
+            sol = files.read_solver(solver_name(d))
+            if sol["NFREQ"] != NFREQ:
+                raise ValueError("absorbed file has %d frequencies, solver %d" % (NFREQ, sol["NFREQ"]))
+            out.append(sol)
+    return out
+
+
+def offers_device_path(engine, kinds, tables):
+    """THE probe of the stage: the engine has the soc_mabu_* calls, and every size of every solver file is solved
+    stochastically (a size without its tables goes through a2e.run's equilibrium branch, which works on host arrays)"""
+    return hasattr(engine, "mabu_begin") and \
+        all(k == 'eqdust' or len(t["sizes"]) >= t["NSIZE"] for k, t in zip(kinds, tables))
+
+
+def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, log):
+    n, NFREQ = FABS.shape
+    for idust in range(len(dusts)):
+        t0 = time.time()
+        part = split_absorbed(FABS, RABS, ABU, idust)
+        if kinds[idust] == 'eqdust':
+            Fq, KABS, Emin, kE, oplgkE, TTT = tables[idust]
+            em = np.zeros((n, NFREQ), np.float32)
+            B = 32768                                          # A2E_MABU.py:493 (any batch gives the same cells)
+            for a in range(0, n, B):
+                b = min(a + B, n)
+                _, em[a:b] = engine.eqsolver(c0 + a, CELLS, NE_EQ, FACTOR, kE, oplgkE, Emin, Fq, KABS, TTT, part[a:b])
+        else:
+            em, _ = a2e.run(engine, tables[idust], part, verbose=False)
+        EM += em * ABU[:, idust:idust + 1]                     # A2E_MABU.py:1128-1140
+        log("  dust %d/%d %-24s %s  %.2f s" % (idust + 1, len(dusts), dusts[idust], kinds[idust], time.time() - t0))
+    return 1
+
+
+def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells, log):
+    """the cells in ranges that fit the device (one range where all do): cells are independent, so this is a loop"""
+    n, NFREQ = FABS.shape
+    NDUST = len(dusts)
+    step = n if not range_cells else max(1, min(n, int(range_cells)))
+    a = ranges = 0
+    while a < n:
+        b = min(a + step, n)
+        t0 = time.time()
+        try:
+            engine.mabu_begin(b - a, NFREQ, NDUST)
+        except DoesNotFit as err:
+            step = err.cells_fit
+            log("  %s" % err)
+            continue
+        try:
+            for i in range(a, b, CHUNK):
+                engine.mabu_upload(i - a, FABS[i:min(i + CHUNK, b)])
+            engine.mabu_set_tables(ABU[a:b], RABS)
+            for idust in range(NDUST):
+                if kinds[idust] == 'eqdust':
+                    Fq, KABS, Emin, kE, oplgkE, TTT = tables[idust]
+                    engine.mabu_split(idust)
+                    engine.mabu_solve_eq(NE_EQ, FACTOR, kE, oplgkE, Emin, Fq, KABS, TTT)
+                else:
+                    sol = tables[idust]
+                    engine.mabu_split(idust, clip_last=True)                       # A2E.py:184-185
+                    for isize in range(sol["NSIZE"]):                              # the sum over the sizes: A2E.py:596-600
+                        engine.a2e_set_size(sol["NE"], NFREQ, sol["sizes"][isize], a2e_absorption_fraction(sol, isize))
+                        engine.a2e_resident_solve()
+                engine.mabu_accumulate(idust)
+            for i in range(a, b, CHUNK):
+                m = min(i + CHUNK, b) - i
+                engine.mabu_download(i - a, m, out=EM[i:i + m])
+        finally:
+            engine.mabu_end()
+        ranges += 1
+        log("  cells %d-%d of this rank: %d dusts  %.2f s" % (a, b, NDUST, time.time() - t0))
+        a = b
+    return ranges
+
+
+def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, path=None, range_cells=None, log=None):
+    """Stage 2 of a multi-dust run for the cells a2e.cell_range(CELLS, rank, world) of this rank.  FABSORBED[CELLS, NFREQ] as the
+    absorbed file holds it (scaled, files.scale_absorbed; a memory map will do), ABU[CELLS, NDUST] float32.
+    Returns (EM[c1 - c0, NFREQ], info) with info["path"] 'device' or 'host' and info["ranges"], the number of cell ranges.
+    path: None = the device path where the engine offers it, or 'device' / 'host' to insist (tests, measurements);
+    range_cells: an upper limit for the cells resident at a time (default: what the free device memory takes)."""
+    log = log or (lambda *a: None)
+    CELLS, NFREQ = FABSORBED.shape
+    RABS, FREQ = relative_cross_sections(dusts, kinds)
+    if RABS.shape[0] != NFREQ:
+        raise ValueError("the dusts have %d frequencies, the absorptions %d" % (RABS.shape[0], NFREQ))
+    tables = _tables(dusts, kinds, NFREQ)
+    offered = offers_device_path(engine, kinds, tables)
+    if path not in (None, 'device', 'host') or (path == 'device' and not offered):
+        raise ValueError("solve_emission: path %r is not available with this engine and these solver files" % (path,))
+    device = offered if path is None else path == 'device'
+    c0, c1 = a2e.cell_range(CELLS, rank, world)
+    EM = np.zeros((c1 - c0, NFREQ), np.float32)
+    ranges = 0
+    if c1 > c0 and device:
+        ranges = _solve_device(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, EM, range_cells, log)
+    elif c1 > c0:
+        ranges = _solve_host(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, c0, CELLS, EM, log)
+    return EM, dict(path='device' if device else 'host', ranges=ranges)
+
+
+# ---- the program ----------------------------------------------------------------------------------------------------
+def run(ini, absorbed, emitted, engine, comm=None, ofreq=None, verbose=False, **stage):
+    """The whole program for one rank of `comm` (or alone): memory-map the absorbed file, solve this rank's cells, write them
+    into this rank's rows of the emitted file.  No collective on the data path (as a2e.run_sharded): the ranks only wait for
+    rank 0 to have created the file, and for each other at the end.  Returns solve_emission's info."""
+    if ofreq is not None:
+        raise UnsupportedOption("a fourth argument (%s: emission on a subset of the frequencies, A2E_MABU.py ofreq.dat) is not supported: "
+                                "the emitted file holds every frequency of the absorbed file" % ofreq)
+    rank, world = (comm.rank, comm.world) if comm else (0, 1)
+    U = User(ini)
+    refuse(U)
+    dusts = list(U.file_optical)
+    if len(dusts) < 1:
+        raise ValueError("%s names no dust (keyword optical)" % ini)
+    kinds = [dust_kind(d) for d in dusts]
+    require_solvers(dusts, kinds)
+    dims = np.fromfile(absorbed, np.int32, 2)
+    CELLS, NFREQ = int(dims[0]), int(dims[1])
+    FABS = np.memmap(absorbed, dtype=np.float32, mode='r', offset=8, shape=(CELLS, NFREQ))
+    ABU = abundance_table(files.read_abundances(U.file_abundance, CELLS), U.SINGLE_ABU, CELLS, len(dusts))
+    log = print if (verbose and rank == 0) else None
+    if world == 1:
+        EM, info = solve_emission(engine, dusts, kinds, FABS, ABU, log=log, **stage)
+        files.write_emitted(emitted, EM)
+        return info
+    if rank == 0:
+        files.create_absorbed(emitted, CELLS, NFREQ)            # (the emitted file has the layout of the absorbed file)
+    comm.barrier()
+    EM, info = solve_emission(engine, dusts, kinds, FABS, ABU, rank, world, log=log, **stage)
+    c0, c1 = a2e.cell_range(CELLS, rank, world)
+    if c1 > c0:
+        out = np.memmap(emitted, dtype=np.float32, mode='r+', offset=8, shape=(CELLS, NFREQ))
+        out[c0:c1, :] = EM
+        out.flush()
+        del out
+    comm.barrier()
+    return info
+
+
+def main(argv=None):
+    argv = sys.argv if argv is None else argv
+    if len(argv) < 4:
+        print("Usage:  python -m soc_amd.mabu  soc.ini absorbed emitted")
+        print("        (N GPUs: python -m torch.distributed.run --nproc-per-node N -m soc_amd.mabu ...)")
+        return 1
+    from .dist import Comm
+    comm = Comm()                      # (imports torch first when there are several ranks: see lib.load_library)
+    from .lib import Engine
+    t0 = time.time()
+    eng = Engine(comm.local_rank)
+    try:
+        info = run(argv[1], argv[2], argv[3], eng, comm if comm.world > 1 else None, ofreq=argv[4] if len(argv) > 4 else None,
+                   verbose=True)
+    finally:
+        eng.close()
+        comm.close()
+    if comm.rank == 0:
+        print('@@  mabu %.3f SECONDS   (%s path, %d cell range%s on rank 0, %d ranks)'
+              % (time.time() - t0, info["path"], info["ranges"], "" if info["ranges"] == 1 else "s", comm.world))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
