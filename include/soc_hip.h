@@ -483,8 +483,12 @@ int soc_mabu_end(soc_ctx *ctx);
  * (MWC64X_SeedStreams + MWC64X_NextUint, mwc64x_rng.cl:35-48) */
 int soc_probe_rng(soc_ctx *ctx, float SEED, uint32_t gid_first, uint32_t n, int ndraw,
                   uint32_t *state_xc, uint32_t *draws);
-/* device math header: fn 0 exp, 1 log, 2 sin, 3 cos, 4 acos, 5 sqrt, 6 fmod(x,1), 7 1/x */
+/* device math header, y[i] = f(x[i]): fn 0 exp, 1 log, 2 sin, 3 cos, 4 acos, 5 sqrt, 6 fmod(x,1), 7 1/x, 8 expm1 (x <= 0),
+ * 9 x^1.5, 10 log in fp64, 11 exp_small (-0.34 < x <= 0), 12 log10, 13 floor: the functions of soc_math.h the kernels call */
 int soc_probe_math(soc_ctx *ctx, int fn, const float *x, float *y, int64_t n);
+/* the two-argument functions, y[i] = f(x[i], x2[i]): fn 14 pown(x, (int)x2), 15 atan2(y = x, x = x2).  With x2 == NULL
+ * this is soc_probe_math; a function called with the wrong number of arguments is refused. */
+int soc_probe_math2(soc_ctx *ctx, int fn, const float *x, const float *x2, float *y, int64_t n);
 /* follow one ray (IndexG + GetStep until exit); returns the number of steps in *nsteps */
 int soc_probe_trace(soc_ctx *ctx, const float pos[3], const float dir[3], int maxsteps,
                     int32_t *levels, int32_t *inds, float *ds, float endpos[3], int32_t *nsteps);

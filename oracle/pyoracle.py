@@ -158,6 +158,7 @@ class Oracle:
         L.orc_sim.restype = C.c_long
         L.orc_sim.argtypes = [C.POINTER(OrcModel), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         L.orc_math_eval.argtypes = [C.c_int, _F, _F, C.c_long]
+        L.orc_math_eval2.argtypes = [C.c_int, _F, _F, _F, C.c_long]
         L.orc_indexg.argtypes = [C.POINTER(OrcModel), _F, _I, _I]
         assert L.orc_math_mode() == (1 if mode == "soc" else 0)
 
@@ -295,11 +296,20 @@ class Oracle:
         self.lib.orc_emission(c0, c1, FREQ.size, np.float32(FACTOR), np.float32(LENGTH), _fp(FREQ), _fp(FABS), _fp(T), _fp(out))
         return out
 
-    def math(self, fn, x):
+    def math(self, fn, x, x2=None):
+        """the oracle's math (soc_math.h in soc mode); pown(x, n = x2) and atan2(y = x, x = x2) take the second array"""
         x = np.ascontiguousarray(x, np.float32)
         y = np.zeros_like(x)
-        code = dict(exp=0, log=1, sin=2, cos=3, acos=4, sqrt=5, fmod1=6, expm1=8, pow15=9, logd=10)[fn]
-        self.lib.orc_math_eval(code, _fp(x), _fp(y), x.size)
+        code = dict(exp=0, log=1, sin=2, cos=3, acos=4, sqrt=5, fmod1=6, expm1=8, pow15=9, logd=10,
+                    exp_small=11, log10=12, floor=13, pown=14, atan2=15)[fn]
+        if (code in (14, 15)) != (x2 is not None):
+            raise ValueError("math(%s): wrong number of arguments" % fn)
+        if x2 is None:
+            self.lib.orc_math_eval(code, _fp(x), _fp(y), x.size)
+            return y
+        x2 = np.ascontiguousarray(x2, np.float32)
+        assert x2.shape == x.shape
+        self.lib.orc_math_eval2(code, _fp(x), _fp(x2), _fp(y), x.size)
         return y
 
 

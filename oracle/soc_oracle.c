@@ -47,6 +47,7 @@
 #  define M_POWN(x, n) powf((x), (float)(n))          /* as the reference shim resolves OpenCL pown */
 #  define M_EXPM1(x) expm1f(x)
 #  define M_POW15(x) powf((x), 1.5f)
+#  define M_EXP_SMALL(x) expf(x)
 static inline void M_SINCOS(float x, float *s, float *c) { *s = sinf(x); *c = cosf(x); }
 #else
 #  include "../soc_amd/csrc/soc_math.h"
@@ -67,6 +68,7 @@ static inline void M_SINCOS(float x, float *s, float *c) { *s = sinf(x); *c = co
 #  define M_POWN(x, n) soc_pownf((x), (n))
 #  define M_EXPM1(x) soc_expm1f(x)
 #  define M_POW15(x) soc_pow15f(x)
+#  define M_EXP_SMALL(x) soc_expf_small(x)
 static inline void M_SINCOS(float x, float *s, float *c) { soc_sincosf(x, s, c); }
 #endif
 
@@ -1883,8 +1885,8 @@ EXPORT void orc_emission(int c0, int c1, int nfreq, float FACTOR, float LENGTH, 
     }
 }
 
-/* math probes for tests/test_math.py */
-EXPORT void orc_math_eval(int fn, const float *x, float *y, long n)
+/* math probes for tests/test_math.py and the device probes; x2 (may be NULL): second argument of pown and atan2 */
+EXPORT void orc_math_eval2(int fn, const float *x, const float *x2, float *y, long n)
 {
     for (long i = 0; i < n; i++) {
         switch (fn) {
@@ -1898,7 +1900,14 @@ EXPORT void orc_math_eval(int fn, const float *x, float *y, long n)
         case 8: y[i] = M_EXPM1(x[i]); break;
         case 9: y[i] = M_POW15(x[i]); break;
         case 10: y[i] = (float)M_LOGD((double)x[i]); break;
+        case 11: y[i] = M_EXP_SMALL(x[i]); break;
+        case 12: y[i] = M_LOG10(x[i]); break;
+        case 13: y[i] = M_FLOOR(x[i]); break;
+        case 14: y[i] = x2 ? M_POWN(x[i], (int)x2[i]) : 0.0f; break;
+        case 15: y[i] = x2 ? M_ATAN2(x[i], x2[i]) : 0.0f; break;
         default: y[i] = 0.0f;
         }
     }
 }
+
+EXPORT void orc_math_eval(int fn, const float *x, float *y, long n) { orc_math_eval2(fn, x, NULL, y, n); }

@@ -2249,24 +2249,31 @@ int soc_probe_rng(soc_ctx *c, float SEED, uint32_t gid_first, uint32_t n, int nd
     return SOC_OK;
 }
 
-int soc_probe_math(soc_ctx *c, int fn, const float *x, float *y, int64_t n)
+int soc_probe_math2(soc_ctx *c, int fn, const float *x, const float *x2, float *y, int64_t n)
 {
     if (!c) return SOC_ERR_ARG;
     FLUSH(c);
     if (!x || !y || n <= 0) return fail(c, SOC_ERR_ARG, "soc_probe_math: bad arguments");
+    if (fn < 0 || fn > 15) return fail(c, SOC_ERR_ARG, "soc_probe_math: no function %d", fn);
+    if ((fn == 14 || fn == 15) != (x2 != nullptr)) return fail(c, SOC_ERR_ARG, "soc_probe_math: function %d takes %s", fn, x2 ? "one argument" : "two arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    float *dx = nullptr, *dy = nullptr;
-    HIPCHK(c, hipMalloc((void **)&dx, (size_t)n * 4));
-    HIPCHK(c, hipMalloc((void **)&dy, (size_t)n * 4));
-    hipError_t e = hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = soc_launch_math_probe(fn, dx, dy, (long)n, c->stream);
+    float *dx = nullptr, *dx2 = nullptr, *dy = nullptr;
+    hipError_t e = hipMalloc((void **)&dx, (size_t)n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&dy, (size_t)n * 4);
+    if (e == hipSuccess && x2) e = hipMalloc((void **)&dx2, (size_t)n * 4);
+    if (e == hipSuccess) e = hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && x2) e = hipMemcpy(dx2, x2, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = soc_launch_math_probe(fn, dx, dx2, dy, (long)n, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(y, dy, (size_t)n * 4, hipMemcpyDeviceToHost);
     (void)hipFree(dx);
+    (void)hipFree(dx2);
     (void)hipFree(dy);
     if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "soc_probe_math: %s", hipGetErrorString(e));
     return SOC_OK;
 }
+
+int soc_probe_math(soc_ctx *c, int fn, const float *x, float *y, int64_t n) { return soc_probe_math2(c, fn, x, nullptr, y, n); }
 
 int soc_probe_trace(soc_ctx *c, const float pos[3], const float dir[3], int maxsteps,
                     int32_t *levels, int32_t *inds, float *ds, float endpos[3], int32_t *nsteps)

@@ -99,7 +99,7 @@ hipError_t soc_launch_sim_hp(const SocGrid &G, const SocSim &S, const SocVariant
 hipError_t soc_launch_parents(const SocGrid &G, int *PAR, hipStream_t st);
 hipError_t soc_launch_seed_probe(uint64_t seed_mul, const uint64_t *tab, uint32_t gid0, uint32_t n,
                                  int ndraw, uint32_t *out_state, uint32_t *out_draws, hipStream_t st);
-hipError_t soc_launch_math_probe(int fn, const float *x, float *y, long n, hipStream_t st);
+hipError_t soc_launch_math_probe(int fn, const float *x, const float *x2, float *y, long n, hipStream_t st);
 hipError_t soc_launch_trace(const SocGrid &G, const SocVariant &V, const float *pos, const float *dir,
                             int maxsteps, int *levels, int *inds, float *dss, float *endpos, int *nsteps,
                             hipStream_t st);

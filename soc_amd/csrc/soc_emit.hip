@@ -9,6 +9,11 @@
 #include "soc_dev.h"
 #include "soc_math.h"
 
+// clamp() of OpenCL, fmin(fmax(x, lo), hi): a NaN comes out as lo, where soc_clampf passes it on.  The interpolation
+// below is inf - inf when wi overflows, which a large negative absorbed energy in a thin cell makes it do; the reference
+// and the oracle then give 3 K.  For every other x this is soc_clampf.
+__device__ static inline float soc_clamp_cl(float x, float lo, float hi) { return (x > lo) ? ((x < hi) ? x : hi) : lo; }
+
 // TNEW[cell] from the absorbed energy per cell (array "EMIT" in the reference), all levels in one launch
 __global__ void soc_eqtemp_kernel(const SocGrid G, const float adhoc, const float kE, const float Emin, const int NE,
                                   const float FACTOR, const float LENGTH, const float cr_rate, const float *TTT, const float *EABS, float *TNEW)
@@ -29,7 +34,7 @@ __global__ void soc_eqtemp_kernel(const SocGrid G, const float adhoc, const floa
         int iE = (int)soc_floorf(oplgkE * soc_log10f((Ein / beta) / Emin));
         iE = iE < 0 ? 0 : (iE > NE - 2 ? NE - 2 : iE);
         const float wi = (Emin * soc_pownf(kE, iE + 1) - (Ein / beta)) / (Emin * soc_pownf(kE, iE) * (kE - 1.0f));
-        TNEW[ind] = (d > 1.0e-7f) ? soc_clampf(wi * TTT[iE] + (1.0f - wi) * TTT[iE + 1], 3.0f, 1600.0f) : 10.0f;
+        TNEW[ind] = (d > 1.0e-7f) ? soc_clamp_cl(wi * TTT[iE] + (1.0f - wi) * TTT[iE + 1], 3.0f, 1600.0f) : 10.0f;
     }
 }
 

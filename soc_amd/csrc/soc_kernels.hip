@@ -368,11 +368,12 @@ __global__ void soc_seed_probe_kernel(uint64_t seed_mul, const uint64_t *tab, ui
     for (int i = 0; i < ndraw; i++) out_draws[(size_t)t * ndraw + i] = soc_next_uint(&s);
 }
 
-__global__ void soc_math_probe_kernel(int fn, const float *x, float *y, long n)
+__global__ void soc_math_probe_kernel(int fn, const float *x, const float *x2, float *y, long n)
 {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float v = x[i], r = 0.0f;
+    const float w = x2 ? x2[i] : 0.0f;                // second argument of the two-argument functions
     switch (fn) {
     case 0: r = soc_expf(v); break;
     case 1: r = soc_logf(v); break;
@@ -385,6 +386,11 @@ __global__ void soc_math_probe_kernel(int fn, const float *x, float *y, long n)
     case 8: r = soc_expm1f(v); break;
     case 9: r = soc_pow15f(v); break;
     case 10: r = (float)soc_logd((double)v); break;
+    case 11: r = soc_expf_small(v); break;
+    case 12: r = soc_log10f(v); break;
+    case 13: r = soc_floorf(v); break;
+    case 14: r = soc_pownf(v, (int)w); break;
+    case 15: r = soc_atan2f(v, w); break;
     default: break;
     }
     y[i] = r;
@@ -498,10 +504,10 @@ hipError_t soc_launch_seed_probe(uint64_t seed_mul, const uint64_t *tab, uint32_
     return hipGetLastError();
 }
 
-hipError_t soc_launch_math_probe(int fn, const float *x, float *y, long n, hipStream_t st)
+hipError_t soc_launch_math_probe(int fn, const float *x, const float *x2, float *y, long n, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
-    soc_math_probe_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(fn, x, y, n);
+    soc_math_probe_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(fn, x, x2, y, n);
     return hipGetLastError();
 }
 

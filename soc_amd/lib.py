@@ -128,6 +128,7 @@ API = {
     "soc_mabu_end": (C.c_int, [C.c_void_p]),
     "soc_probe_rng": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_int, _U, _U]),
     "soc_probe_math": (C.c_int, [C.c_void_p, C.c_int, _F, _F, C.c_int64]),
+    "soc_probe_math2": (C.c_int, [C.c_void_p, C.c_int, _F, _F, _F, C.c_int64]),
     "soc_probe_trace": (C.c_int, [C.c_void_p, _F, _F, C.c_int, _I, _I, _F, _F, _I]),
 }
 
@@ -824,11 +825,19 @@ class Engine:
                                          st.ctypes.data_as(_U), dr.ctypes.data_as(_U)))
         return st, dr[:, :ndraw]
 
-    def probe_math(self, fn, x):
-        code = dict(exp=0, log=1, sin=2, cos=3, acos=4, sqrt=5, fmod1=6, rcp=7, expm1=8, pow15=9, logd=10)[fn]
+    def probe_math(self, fn, x, x2=None):
+        """soc_math.h on the device; pown(x, n = x2) and atan2(y = x, x = x2) take the second array"""
+        code = dict(exp=0, log=1, sin=2, cos=3, acos=4, sqrt=5, fmod1=6, rcp=7, expm1=8, pow15=9, logd=10,
+                    exp_small=11, log10=12, floor=13, pown=14, atan2=15)[fn]
         x = np.ascontiguousarray(x, np.float32)
         y = np.zeros_like(x)
-        self._chk(self.lib.soc_probe_math(self.h, code, _f(x), _f(y), x.size))
+        if x2 is None:
+            self._chk(self.lib.soc_probe_math(self.h, code, _f(x), _f(y), x.size))
+            return y
+        x2 = np.ascontiguousarray(x2, np.float32)
+        if x2.shape != x.shape:
+            raise SocError("probe_math: the two arguments differ in shape")
+        self._chk(self.lib.soc_probe_math2(self.h, code, _f(x), _f(x2), _f(y), x.size))
         return y
 
     def probe_trace(self, pos, direction, maxsteps=100000):

@@ -44,6 +44,8 @@ void hp_math(int fn, const float *x, float *y, long n)
         case 11: y[i] = soc_expf_small(x[i]); break;
         case 9: y[i] = soc_pow15f(x[i]); break;
         case 10: y[i] = (float)soc_logd((double)x[i]); break;
+        case 12: y[i] = soc_log10f(x[i]); break;
+        case 13: y[i] = soc_floorf(x[i]); break;
         default: y[i] = 0.0f;
         }
     }
@@ -57,4 +59,9 @@ void hp_div_by_rcp(const float *n, const float *u, float *q, long cnt)
 void hp_atan2(const float *y, const float *x, float *r, long cnt)
 {
     for (long i = 0; i < cnt; i++) r[i] = soc_atan2f(y[i], x[i]);
+}
+
+void hp_pown(const float *x, const int *n, float *r, long cnt)
+{
+    for (long i = 0; i < cnt; i++) r[i] = soc_pownf(x[i], n[i]);
 }

@@ -54,7 +54,7 @@ class HostProbe:
         return u, r
 
     def math(self, fn, x):
-        code = dict(exp=0, log=1, sin=2, cos=3, acos=4, sqrt=5, fmod1=6, expm1=8, pow15=9, logd=10, exp_small=11)[fn]
+        code = dict(exp=0, log=1, sin=2, cos=3, acos=4, sqrt=5, fmod1=6, expm1=8, pow15=9, logd=10, exp_small=11, log10=12, floor=13)[fn]
         x = np.ascontiguousarray(x, np.float32)
         y = np.zeros_like(x)
         self.lib.hp_math(code, x.ctypes.data_as(_F), y.ctypes.data_as(_F), x.size)
@@ -72,4 +72,11 @@ class HostProbe:
         x = np.ascontiguousarray(x, np.float32)
         r = np.zeros_like(y)
         self.lib.hp_atan2(y.ctypes.data_as(_F), x.ctypes.data_as(_F), r.ctypes.data_as(_F), y.size)
+        return r
+
+    def pown(self, x, n):
+        x = np.ascontiguousarray(x, np.float32)
+        n = np.ascontiguousarray(n, np.int32)
+        r = np.zeros_like(x)
+        self.lib.hp_pown(x.ctypes.data_as(_F), n.ctypes.data_as(C.POINTER(C.c_int)), r.ctypes.data_as(_F), x.size)
         return r

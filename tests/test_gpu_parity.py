@@ -42,18 +42,89 @@ def test_rng_streams_contiguous_block_vs_oracle(engine, oracle_soc):
         assert np.array_equal(dr[k], oracle_soc.draws(*s, 4)[0])
 
 
-@pytest.mark.parametrize("fn", ["exp", "log", "sin", "cos", "acos", "sqrt", "fmod1", "expm1", "pow15", "logd"])
-def test_device_math_bit_identical_to_host_build(fn, engine, oracle_soc):
+def _all_floats(lo, hi):
+    """every float32 in [lo, hi] (same sign, lo nearer zero)"""
+    a, b = np.float32(lo).view(np.uint32), np.float32(hi).view(np.uint32)
+    return np.arange(a, b + 1, dtype=np.uint32).view(np.float32)
+
+
+def _table_bases():
+    """kE of launch.temperature_table for NE = 2, 3000 and the default 6000 (the dust of tests/test_temperature.py)"""
+    from soc_amd import launch
+    FF = np.logspace(np.log10(3e11), np.log10(3e15), 40)
+    return {NE: np.float32(launch.temperature_table(FF, 1e-5 * (FF / 1e13) ** 1.6, 0.01, NE=NE)[1]) for NE in (2, 3000, 6000)}
+
+
+def _math_inputs(fn, oracle_soc):
+    """arguments at which the kernels call the functions of soc_math.h; a pair for pown (x, n) and atan2 (y, x)"""
     rng = np.random.default_rng(11)
-    x = {"exp": np.concatenate([rng.uniform(-90, 5, 200000), -np.logspace(-9, 1, 20000)]),
-         "log": np.concatenate([rng.uniform(0, 1, 200000), np.logspace(-38, 30, 20000), [0.0, 1.0]]),
-         "sin": rng.uniform(-7, 7, 200000), "cos": rng.uniform(-7, 7, 200000),
-         "acos": np.concatenate([rng.uniform(-1, 1, 200000), [1.0, -1.0, 0.5, -0.5]]),
-         "sqrt": rng.uniform(0, 1e4, 200000), "fmod1": rng.uniform(-300, 300, 200000),
-         "expm1": -np.concatenate([rng.uniform(0, 40, 100000), np.logspace(-30, 0, 100000)]),
-         "pow15": rng.uniform(0.1, 3.0, 200000),
-         "logd": np.concatenate([rng.uniform(0, 1, 200000), np.logspace(-38, 30, 20000)])}[fn].astype(np.float32)
-    assert np.array_equal(engine.probe_math(fn, x).view(np.uint32), oracle_soc.math(fn, x).view(np.uint32))
+    f32 = np.float32
+    if fn == "exp":
+        # the emission kernel's Planck exponent runs from ~1e-6 to 4.8e4: beyond 88.72 it must be +inf, below -87 zero
+        return np.concatenate([rng.uniform(-90, 5, 200000), -np.logspace(-9, 1, 20000), rng.uniform(5, 89, 200000),
+                               _all_floats(88.70, 88.75), -_all_floats(86.99, 87.01), rng.uniform(-110, -85, 50000),
+                               np.logspace(-9, 5, 20000), -np.logspace(1.9, 38.5, 5000),
+                               [88.72, 89.0, 100.0, 4.8e4, 3e38, np.inf, -np.inf, -3e38, 0.0, -0.0]]).astype(f32), None
+    if fn == "log10":
+        near = []
+        for NE, k in _table_bases().items():                          # where the floor of the table lookup is decided
+            n = np.arange(NE + 1)
+            for v in (np.float64(k) ** n, oracle_soc.math("pown", np.full(NE + 1, k, f32), n).astype(np.float64)):
+                v = v[v < 3e38].astype(f32)
+                for _ in range(3):
+                    near.append(v)
+                    v = np.nextafter(v, f32(0))
+                v = near[-3]
+                for _ in range(2):
+                    v = np.nextafter(v, f32(np.inf))
+                    near.append(v)
+        return np.concatenate([rng.integers(1, 0x7f800000, 600000).astype(np.uint32).view(f32),        # normal and subnormal
+                               rng.integers(1, 0x00800000, 50000).astype(np.uint32).view(f32), rng.uniform(0, 2, 200000).astype(f32),
+                               f32([0.0, 1.0, 1e-45, 1.1754942e-38, 1.17549435e-38, 3.4028235e38, np.inf, 10.0, 0.1])] + near), None
+    if fn == "exp_small":
+        return np.concatenate([-np.linspace(0, 0.34, 400001), -np.logspace(-45, -0.47, 100000), -_all_floats(0.3399, 0.34),
+                               [0.0, -0.0, -0.34]]).astype(f32), None
+    if fn == "floor":
+        return np.concatenate([rng.uniform(-7000, 7000, 200000), rng.uniform(-1, 1, 1000) * 1e-30, np.arange(-6001, 6001),
+                               [0.0, -0.0, 8388607.5, -8388607.5, 3e38, -3e38, np.inf, -np.inf]]).astype(f32), None
+    if fn == "pown":
+        x, n = [np.full(17, 8.0, f32)], [np.arange(17)]               # 8^level, level 0..SOC_MAXL
+        for NE, k in _table_bases().items():
+            for b in (k, f32(1.0) / k):                               # kE^iE, iE 0..NE, and a base below 1
+                x.append(np.full(NE + 1, b, f32))
+                n.append(np.arange(NE + 1))
+        for b in (8.0, 0.5, 0.1, 0.999, 1.9999999, 3.0, -1.7):       # negative n: 1 / x^|n| in the header
+            x.append(np.full(65, b, f32))
+            n.append(np.arange(-32, 33))
+        x.append(rng.uniform(0.5, 2.0, 100000).astype(f32))
+        n.append(rng.integers(0, 100, 100000))
+        return np.concatenate(x), np.concatenate(n).astype(f32)
+    if fn == "atan2":
+        y, x = rng.standard_normal(200000), rng.standard_normal(200000)      # four quadrants
+        y[:20000] *= 10.0 ** rng.uniform(-40, -3, 20000)                      # |y| << |x|
+        x[20000:40000] *= 10.0 ** rng.uniform(-40, -3, 20000)                 # |x| << |y|
+        ax = np.array([0.0, -0.0, 1.0, -1.0, 1e-45, -1e-45, 3e38, -3e38, 0.5, -2.0])
+        yy, xx = np.meshgrid(ax, ax)                                          # both axes, signed zeros, extremes
+        return np.concatenate([y, yy.ravel(), x[:1000], x[:1000]]).astype(f32), np.concatenate([x, xx.ravel(), x[:1000], -x[:1000]]).astype(f32)
+    return {"log": np.concatenate([rng.uniform(0, 1, 200000), np.logspace(-38, 30, 20000), [0.0, 1.0]]),
+            "sin": rng.uniform(-7, 7, 200000), "cos": rng.uniform(-7, 7, 200000),
+            "acos": np.concatenate([rng.uniform(-1, 1, 200000), [1.0, -1.0, 0.5, -0.5]]),
+            "sqrt": rng.uniform(0, 1e4, 200000), "fmod1": rng.uniform(-300, 300, 200000),
+            "expm1": -np.concatenate([rng.uniform(0, 40, 100000), np.logspace(-30, 0, 100000)]),
+            "pow15": rng.uniform(0.1, 3.0, 200000),
+            "logd": np.concatenate([rng.uniform(0, 1, 200000), np.logspace(-38, 30, 20000)])}[fn].astype(f32), None
+
+
+@pytest.mark.parametrize("fn", ["exp", "log", "sin", "cos", "acos", "sqrt", "fmod1", "expm1", "pow15", "logd",
+                                "log10", "exp_small", "floor", "pown", "atan2"])
+def test_device_math_bit_identical_to_host_build(fn, engine, oracle_soc):
+    x, x2 = _math_inputs(fn, oracle_soc)
+    got, want = engine.probe_math(fn, x, x2), oracle_soc.math(fn, x, x2)
+    if fn == "exp":                                                   # what the emission kernel relies on
+        assert np.isposinf(want[x > np.float32(88.72)]).all() and (want[x < -87.0] == 0).all() and np.isfinite(want[x <= np.float32(88.72)]).all()
+    bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
+    assert bad.size == 0, "%s: %d of %d differ, first at x = %r%s: device %r, host %r" % (
+        fn, bad.size, x.size, x[bad[0]], "" if x2 is None else ", %r" % x2[bad[0]], got[bad[0]], want[bad[0]])
 
 
 def test_device_division_correctly_rounded(engine):

@@ -108,8 +108,73 @@ def test_atan2(hp):
     assert sp[0] == 0 and abs(sp[1] - np.pi / 2) < 1e-6 and abs(sp[2] + np.pi / 2) < 1e-6 and abs(sp[3] - np.pi) < 1e-6
 
 
+def _kE_tables():
+    """kE of launch.temperature_table for the table sizes the tests and the product use"""
+    from soc_amd import launch
+    FF = np.logspace(np.log10(3e11), np.log10(3e15), 40)
+    return {NE: np.float32(launch.temperature_table(FF, 1e-5 * (FF / 1e13) ** 1.6, 0.01, NE=NE)[1]) for NE in (2, 3000, 6000)}
+
+
+def test_log10(hp):
+    """soc_log10f = soc_logf * log10(e): the bound of test_log (2 ulp) plus one ulp for the extra multiplication.
+    Measured worst error over the inputs below: 1.94 ulp, at x = 0.58265 (soc_logf alone: 0.76 ulp)."""
+    kE = _kE_tables()
+    near = np.concatenate([np.float64(k) ** np.arange(0, NE + 1) for NE, k in kE.items() if NE > 2])
+    near = near[near < 3e38].astype(np.float32)
+    near = np.concatenate([np.nextafter(near, np.float32(0)), near, np.nextafter(near, np.float32(np.inf))])
+    x = np.concatenate([np.logspace(-37, 38, 200001), np.linspace(0.5, 2.0, 100001), (np.arange(1, 2 ** 20, 97) * 2.0 ** -32),
+                        np.logspace(-45, -37.9, 20001), near]).astype(np.float32)
+    x = x[x > 0]
+    err = ulp_err(hp.math("log10", x), np.log10(x.astype(np.float64)))
+    print("log10: worst error %.3f ulp at x = %r" % (err.max(), x[err.argmax()]))
+    assert err.max() < 3.0
+    sp = hp.math("log10", np.array([0.0, 1.0, -1.0, np.inf, 10.0, 1e-45], np.float32))
+    assert sp[0] == -np.inf and sp[1] == 0.0 and np.isnan(sp[2]) and sp[3] == np.inf and sp[4] == 1.0
+    assert abs(sp[5] / np.log10(float(np.float32(1e-45))) - 1) < 1e-6
+
+
+def test_pown(hp):
+    """soc_pownf against the float64 power.  Every fp32 product adds a relative error of at most u = 2^-24 and the
+    errors of the factors add with their exponents, so x^n from n-1 products, in any order, is within
+    (1+u)^(n-1) - 1 ~ (n-1) u of the exact power; one ulp of the result is at least u times it.  The bound is therefore
+    n-1 ulp for every case (5999 ulp for the largest n used, kE^6000), plus 1 for the division of a negative n.
+    Measured worst error: 2260.1 ulp, at (1/kE)^5952 of the NE = 6000 table (kE^5951: 1711.8 ulp; NE = 3000: 716.2 ulp at
+    kE^2975); the worst error is 0.74 of its bound.  Powers of 8 and n = 0, 1 are exact."""
+    x, n = [], []
+    for NE, k in _kE_tables().items():
+        for b in (k, np.float32(1.0) / k):                           # table base and a base below 1
+            x.append(np.full(NE + 1, b, np.float32))
+            n.append(np.arange(NE + 1))
+    for b in (8.0, 0.5, 0.1, 0.999, 0.5000001, 1.9999999, 3.0, -1.7):
+        x.append(np.full(33, b, np.float32))
+        n.append(np.arange(-16, 17))                                 # the header defines n < 0 as 1 / x^|n|
+    rng = np.random.default_rng(6)
+    x.append(rng.uniform(0.5, 2.0, 100000).astype(np.float32))
+    n.append(rng.integers(0, 100, 100000))
+    x, n = np.concatenate(x), np.concatenate(n).astype(np.int32)
+    got = hp.pown(x, n)
+    want = x.astype(np.float64) ** n
+    ok = (np.abs(want) > 1.2e-38) & (np.abs(want) < 3.4e38)          # normal results: the kernels never leave that range
+    assert ok.sum() > 0.99 * ok.size
+    err = ulp_err(got[ok], want[ok])
+    bound = np.maximum(np.abs(n[ok]) - 1, 0) + (n[ok] < 0) + 0.5     # 0.5: the float64 power itself is not a float
+    print("pown: worst error %.1f ulp at %r^%d; worst error/bound %.3f" % (err.max(), x[ok][err.argmax()], n[ok][err.argmax()], (err / bound).max()))
+    assert (err <= bound).all()
+    assert np.array_equal(hp.pown(np.full(17, 8.0, np.float32), np.arange(17)), (8.0 ** np.arange(17)).astype(np.float32))
+    assert (got[n == 0] == 1.0).all() and np.array_equal(got[n == 1], x[n == 1])
+
+
+def test_floor(hp):
+    x = np.concatenate([np.random.default_rng(8).uniform(-7000, 7000, 100000), [0.0, -0.0, -0.5, 0.5, 5998.0, -1e-30, 3e38, -3e38, np.inf, -np.inf]]).astype(np.float32)
+    assert np.array_equal(hp.math("floor", x).view(np.uint32), np.floor(x).view(np.uint32))
+
+
 def test_oracle_soc_mode_uses_this_header(hp, oracle_soc):
     x = np.random.default_rng(5).uniform(-20, 5, 20000).astype(np.float32)
     for fn, xx in (("exp", x), ("log", np.abs(x) + 1e-9), ("sin", x), ("cos", x), ("acos", np.clip(x / 20, -1, 1)),
-                   ("expm1", -np.abs(x)), ("pow15", np.abs(x) + 0.1), ("logd", np.abs(x) + 1e-9)):
+                   ("expm1", -np.abs(x)), ("pow15", np.abs(x) + 0.1), ("logd", np.abs(x) + 1e-9),
+                   ("log10", np.abs(x) + 1e-9), ("floor", 300 * x), ("exp_small", -np.abs(x) / 60)):
         assert np.array_equal(hp.math(fn, xx).view(np.uint32), oracle_soc.math(fn, xx).view(np.uint32))
+    n = np.arange(x.size) % 40 - 8
+    assert np.array_equal(hp.pown(np.abs(x) / 8 + 0.3, n).view(np.uint32), oracle_soc.math("pown", np.abs(x) / 8 + 0.3, n).view(np.uint32))
+    assert np.array_equal(hp.atan2(x, x[::-1] + 7).view(np.uint32), oracle_soc.math("atan2", x, x[::-1] + 7).view(np.uint32))
