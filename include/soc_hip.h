@@ -377,10 +377,29 @@ int soc_emission(soc_ctx *ctx, int nfreq, const float *FREQ, const float *FABS, 
  * RA (right), DE (up) through CENTRE -- or, with INTOBS given (INTOBS[0] > -1e10), the longitude x latitude image seen
  * from that position; healpix = 1: Healpix map of NSIDE = NPIX_X seen from INTOBS.  MAP gets the surface brightness
  * integral, SAVETAU the optical depth or (save_colden) column density x LENGTH.  -D MAP_INTERPOLATION, ROI_MAP and
- * LEVEL_THRESHOLD: soc_set_map_interpolation, soc_set_map_roi, soc_set_map_threshold.  Polarisation maps are not covered. */
+ * LEVEL_THRESHOLD: soc_set_map_interpolation, soc_set_map_roi, soc_set_map_threshold.  Polarisation maps: soc_polmap. */
 int soc_map(soc_ctx *ctx, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const float *EMIT, const float *DIR,
             const float *RA, const float *DE, const float *CENTRE, const float *INTOBS, float ABS, float SCA,
             int save_colden, float LENGTH, float *MAP, float *SAVETAU);
+
+/* replaces the Bx_buf, By_buf, Bz_buf uploads of ASOC.py:3722-3727: the magnetic field of the polarisation maps, CELLS
+ * floats per component in the order of the cloud file (all cells, parents included).  The device keeps one 16-byte record
+ * (Bx, By, Bz, pad) per cell.  A polarisation reduction factor is encoded in the length of the vectors by the caller
+ * (ASOC.py:3681-3719).  Three NULL pointers free the field; soc_set_grid with another cell count drops it. */
+int soc_set_bfield(soc_ctx *ctx, const float *Bx, const float *By, const float *Bz);
+
+/* replaces the PolMapping launch + copy of ASOC.py:3790-3796 -> kernel_ASOC_map.c:972-1137 (-D POLSTAT=0: MAP = I, Q, U,
+ * column density x LENGTH), :1147-1384 (POLSTAT=1: rT, rI, jT, jI, two passes along the ray), :1594-1693 (POLSTAT=3: <B>,
+ * <B_LOS>, <B_POS>, tau): one orthographic map of NPIX_X x NPIX_Y pixels of MAP_DX root cells towards DIR with image axes
+ * RA (right), DE (up) through CENTRE; MAP holds the four planes, 4*NPIX_X*NPIX_Y floats.  polred = -D POLRED (the
+ * polarisation fraction of a cell is |B| instead of p0), rho_weight = -D POL_RHO_WEIGHT (POLSTAT 0: density instead of
+ * emission weights), p0 = -D p00.  Extinction is ABS+SCA or the per-cell OPT of soc_set_opt*; -D LEVEL_THRESHOLD is
+ * soc_set_map_threshold.  A ray that misses the cloud gives 0/0 = NaN for POLSTAT 1 and 3, as in the reference.
+ * Refused with an error code: no field set (SOC_ERR_STATE); polstat other than 0, 1, 3, polred with polstat 3, or a
+ * component of DIR that is zero -- the walk divides by it (SOC_ERR_ARG). */
+int soc_polmap(soc_ctx *ctx, int polstat, int polred, int rho_weight, float p0, int NPIX_X, int NPIX_Y, float MAP_DX,
+               const float *EMIT, const float *DIR, const float *RA, const float *DE, const float *CENTRE, float ABS,
+               float SCA, float LENGTH, float *MAP);
 
 /* ---- stochastically heated grains: A2E.py / kernel_A2E.c ---- */
 
@@ -486,7 +505,8 @@ int soc_probe_rng(soc_ctx *ctx, float SEED, uint32_t gid_first, uint32_t n, int 
 /* device math header, y[i] = f(x[i]): fn 0 exp, 1 log, 2 sin, 3 cos, 4 acos, 5 sqrt, 6 fmod(x,1), 7 1/x, 8 expm1 (x <= 0),
  * 9 x^1.5, 10 log in fp64, 11 exp_small (-0.34 < x <= 0), 12 log10, 13 floor: the functions of soc_math.h the kernels call */
 int soc_probe_math(soc_ctx *ctx, int fn, const float *x, float *y, int64_t n);
-/* the two-argument functions, y[i] = f(x[i], x2[i]): fn 14 pown(x, (int)x2), 15 atan2(y = x, x = x2).  With x2 == NULL
+/* the two-argument functions, y[i] = f(x[i], x2[i]): fn 14 pown(x, (int)x2), 15 atan2(y = x, x = x2), 16 fmod(x, x2) for
+ * x2 > 0 and a quotient below 2^22.  With x2 == NULL
  * this is soc_probe_math; a function called with the wrong number of arguments is refused. */
 int soc_probe_math2(soc_ctx *ctx, int fn, const float *x, const float *x2, float *y, int64_t n);
 /* follow one ray (IndexG + GetStep until exit); returns the number of steps in *nsteps */

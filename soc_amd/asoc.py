@@ -30,7 +30,7 @@ class UnsupportedOption(RuntimeError):
     pass
 
 
-def _check_supported(USER, NDUST, WITH_MSF):
+def _check_supported(USER, NDUST, WITH_MSF, engine=None):
     bad = []
     if USER.DO_SPLIT:
         bad.append("split")
@@ -51,8 +51,24 @@ def _check_supported(USER, NDUST, WITH_MSF):
         bad.append("nnmake with absthin and mmapabs (the reference adds thinned rows to a full-size memory map there and stops, ASOC.py:623-630, :1496)")
     if 'nnmake' in USER.KEYS and USER.ABSTHIN > 1 and USER.WITH_REFERENCE and not USER.NOABSORBED:
         bad.append("nnmake with absthin and the reference field (not built)")
-    if USER.POLMAP or USER.POLSIM or len(USER.BFILES) > 0 or len(getattr(USER, "file_polred", "")) > 0:
-        bad.append("polmap / polred / magnetic-field files (polarisation maps)")
+    # polarisation maps (ASOC.py:3651-3801): PolMapping with -D POLSTAT 0, 1, 3 on an engine that has the kernel
+    if USER.POLSIM:
+        bad.append("polsim (polarised scattered light, kernel_ASOC_pol.c)")
+    if USER.POLMAP:
+        if not (hasattr(engine, "polmap") and hasattr(engine, "set_bfield")):
+            bad.append("polmap / polred / magnetic-field files (polarisation maps): this engine has no polarisation-map kernel (polmap, set_bfield)")
+        if USER.POLSTAT == 2:
+            bad.append("polstat 2 (perspective polarisation images with cube replication, kernel_ASOC_map.c:1397-1590)")
+        elif USER.POLSTAT in (4, 5):
+            bad.append("polstat %d (the 2025 variants of PolMapping, kernel_ASOC_map.c:1698 on)" % USER.POLSTAT)
+        elif USER.POLSTAT not in (0, 1, 3):
+            bad.append("polstat %d (PolMapping knows 0..5)" % USER.POLSTAT)
+        if USER.NPIX[1] < 0:
+            bad.append("polmap with a Healpix map (mapping with a negative second argument: PolHealpixMapping, kernel_ASOC_map_H.c)")
+        if any(k.startswith('libmap') for k in USER.KEYS):
+            bad.append("polmap together with libmaps (ASOC.py:3666-3667 stops there as well)")
+    elif len(getattr(USER, "file_polred", "")) > 0:
+        bad.append("polred without polmap (the factor is encoded in the magnetic field of a polarisation map)")
     if USER.FAST_MAP >= 2:
         bad.append("mapping with a fourth argument >= 2 (FAST_MAP 2..998: kernel_ASOC_map_X.c, all frequencies per launch -- the reference's "
                    "own branch stops at ASOC.py:3553, a list compared with a float; >= 999: one map per hierarchy level, kernel_ASOC_map_H.c)")
@@ -113,7 +129,7 @@ class AbsorptionRun:
                              "restrict the simulated range with `simum` instead")
         self.FDSC, self.FCSC = files.read_scattering_functions(U.file_scafunc, self.NFREQ, U.DSC_BINS)
         self.WITH_MSF = WITH_MSF = len(self.FDSC) > 1
-        _check_supported(U, self.NDUST, WITH_MSF)
+        _check_supported(U, self.NDUST, WITH_MSF, self.eng)
         self.IBG = files.read_background_intensity(U.file_background, self.NFREQ, U.scale_background) \
             if U.BGPAC > 0 else []
         self.LPS = files.read_source_luminosities(U.file_pointsource[:U.NO_PS], self.NFREQ, U.PS_SCALING) \
@@ -747,7 +763,7 @@ class AbsorptionRun:
         frequency.  `perspective` gives the longitude x latitude image seen from that position.  Optical-depth
         images for `savetau` frequencies are written as <file>_tau_<um>.bin, the column density (`savetau file -1`) as
         <file>_colden.fits; `fits` with `mapum` gives one FITS image per direction and frequency instead.  NPIX.y < 0:
-        write_healpix_maps.  Map interpolation, ROI maps and polarisation maps are refused (_check_supported)."""
+        write_healpix_maps.  Polarisation maps: write_polmaps."""
         U, e, c = self.U, self.eng, self.cloud
         if U.NPIX[1] == 0:
             self.log("mapping with NPIX.y == 0: neither the flat (NPIX.y > 0, ASOC.py:2924) nor the Healpix branch (NPIX.y < 0, :3185)")
@@ -816,6 +832,88 @@ class AbsorptionRun:
                         np.asarray(TAU, np.float32).tofile(name + '.bin')
         for fp in fps:
             fp.close()
+
+    def polarisation_field(self):
+        """The three B files of `polmap` (the layout of the cloud file: every cell, parents included) with the polarisation
+        reduction factor R of `polred` encoded in the length of the vectors, B * R / sqrt(B^2 + 1e-10) (ASOC.py:3676-3720):
+        `adhoc` -- R from the dust temperatures of the `temperature` file; `rhofun_<threshold>_<width>` -- from the density
+        (times `density`); anything else -- a plain file [cells, {R}], clipped to [1e-6, 0.999999].  polstat 3 uses the
+        vectors as they are."""
+        U, c = self.U, self.cloud
+        BB = [np.asarray(files.read_temperature(f, c), np.float32) for f in U.BFILES[:3]]
+        polred = getattr(U, "file_polred", "")
+        if U.POLSTAT != 3 and len(polred) > 0:
+            if polred == 'adhoc':
+                R = files.read_temperature(U.file_temperature, c)
+                R = (R - 13.3) / 2.0 + 1.0e-4
+                R = np.exp(R) / (np.exp(R) + np.exp(-R))
+            elif polred.find('rhofun') >= 0:
+                s = polred.split('_')
+                th, sw = float(s[1]), float(s[2])
+                R = files.read_temperature(U.file_cloud, c)             # the density as the file holds it (read_otfile)
+                if U.KDENSITY != 1.0:
+                    R *= U.KDENSITY
+                R = np.clip(R, 0.1, 1e10)
+                R = 0.5 * (1.0 + np.tanh((np.log10(th) - np.log10(R)) / sw))
+            else:
+                R = np.clip(np.fromfile(polred, np.float32)[1:], 1.0e-6, 0.999999)
+                if R.size != c.CELLS:
+                    raise files.FileError("%s: %d polarisation reduction factors for %d cells" % (polred, R.size, c.CELLS))
+            R = R / np.sqrt(BB[0] ** 2 + BB[1] ** 2 + BB[2] ** 2 + 1.0e-10)
+            for k in range(3):
+                BB[k] *= R
+        return [np.ascontiguousarray(b, np.float32) for b in BB]
+
+    def polmap_frequencies(self):
+        """indices of the frequencies that get a polarisation map (ASOC.py:3755-3762): those of the emitted range that are
+        within 1 % of a `mapum` wavelength -- or, without `mapum`, inside `wavelength`"""
+        U, FFREQ = self.U, self.FFREQ
+        m = np.nonzero((FFREQ >= U.REMIT_F[0]) & (FFREQ <= U.REMIT_F[1]))[0]
+        I1, I2 = int(m[0]), int(m[-1])
+        singles = np.asarray(getattr(U, "SINGLE_MAP_FREQ", []), np.float32)
+        sel = []
+        for IFREQ in range(I1, I2 + 1):
+            FREQ = FFREQ[IFREQ]
+            if len(singles) > 0:
+                if np.min(np.abs(FREQ - singles)) > 0.01 * FREQ:
+                    continue
+            elif (FREQ < U.MAP_FREQ[0]) or (FREQ > U.MAP_FREQ[1]):
+                continue
+            sel.append(IFREQ)
+        return I1, sel
+
+    def write_polmaps(self, EMITTED):
+        """`polmap bx by bz`: polarisation maps from the emission (ASOC.py:3651-3801 -> PolMapping): for every selected
+        frequency and observer direction polmap_<um>_<dir>.fits with data [4, NPIX.y, NPIX.x] -- I, Q, U [Jy/sr] and the
+        column density (polstat 0), the line-of-sight statistics rT, rI, jT, jI of the field (polstat 1), or <B>, <B_LOS>,
+        <B_POS>, tau (polstat 3).  Written under `nomap` as well, as in the reference (:3655)."""
+        U, e, c = self.U, self.eng, self.cloud
+        if not (U.POLMAP > 0 and U.NPIX[1] > 0):
+            return []
+        e.set_bfield(*self.polarisation_field())
+        I1, sel = self.polmap_frequencies()
+        NDIR, ODIR, RA, DE = launch.set_observer_directions(U.OBS_THETA, U.OBS_PHI)
+        centre = U.MAPCENTRE if U.MAPCENTRE[0] > -1e7 else (0.5 * c.NX, 0.5 * c.NY, 0.5 * c.NZ)   # ASOC_aux.py:791-793
+        KK = (1.0e23 / launch.FACTOR) * PLANCK / (4.0 * np.pi) * (U.GL * PARSEC)                 # ASOC.py:3753-3754
+        _, LENGTH_f = launch.kernel_literals(U.GL)
+        pix = U.GL * U.MAP_DX / (U.DISTANCE if U.DISTANCE > 0.0 else 1000.0)
+        polred = int(U.POLSTAT != 3 and len(getattr(U, "file_polred", "")) > 0)                  # -D POLRED (ASOC.py:349,359)
+        p0 = float("%.4f" % U.p0)                                                               # -D p00=%.4ff
+        written = []
+        for IFREQ in sel:
+            FREQ = float(self.FFREQ[IFREQ])
+            ABS, SCA = self._optical_for(IFREQ)
+            EMIT = np.asarray(KK * FREQ * EMITTED[:, IFREQ - I1], np.float32)                    # :3788
+            for idir in range(NDIR):
+                MAP = e.polmap(EMIT, ODIR[idir], RA[idir], DE[idir], U.NPIX, U.MAP_DX, centre, ABS, SCA, polstat=int(U.POLSTAT),
+                               polred=polred, rho_weight=int(U.POL_RHO_WEIGHT > 0), p0=p0, LENGTH=LENGTH_f)
+                if self.rank != 0:
+                    continue
+                name = "polmap_%.1f_%02d.fits" % (1.0e4 * launch.C_LIGHT / FREQ, idir)          # f2um (:3800)
+                files.write_fits(name, np.asarray(MAP, np.float32).reshape(4, U.NPIX[1], U.NPIX[0]), U.FITS_RA, U.FITS_DE, pix, planes=True)
+                written.append(name)
+        e.set_bfield(None)
+        return written
 
     def write_ps_tau(self):
         """`pssavetau file um`: for every observer direction <file>_<idir>.dat with one line per point source -- its index,
@@ -886,6 +984,8 @@ class AbsorptionRun:
             self.TNEW, self.EMITTED = self.emission_from_temperature_file()
         if (not U.NOMAP) and self.EMITTED is not None:
             self.write_maps(self.EMITTED)
+        if U.POLMAP and self.EMITTED is not None:                 # also under `nomap` (ASOC.py:3655)
+            self.write_polmaps(self.EMITTED)
         if U.NO_PS > 0 and U.pssavetau_freq > 0.0 and U.NPIX[1] > 0:
             self.write_ps_tau()
         if self.rank == 0 and self.INTENSITY is not None:          # ASOC.py:2733-2757

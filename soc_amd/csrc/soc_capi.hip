@@ -107,6 +107,9 @@ struct soc_ctx {
     // map making (soc_map.hip)
     float *dMapEmit = nullptr, *dMap = nullptr, *dMapTau = nullptr;
     size_t map_cap = 0, mapemit_cap = 0;
+    float4 *dBfield = nullptr;         // magnetic field, one (Bx, By, Bz, pad) per cell (soc_set_bfield)
+    float  *dPolMap = nullptr;         // the four planes of a polarisation map
+    size_t  polmap_cap = 0;
     // A2E
     int a2e_NE = 0, a2e_NFREQ = 0, a2e_npair = 0, a2e_cap = 0, a2e_noIw = 0;
     float *aIw = nullptr, *aTdown = nullptr, *aEA = nullptr, *aAF = nullptr, *aABS = nullptr, *aEMIT = nullptr;
@@ -353,7 +356,7 @@ void soc_destroy(soc_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     release_slots(c);
-    void *bufs[] = { c->dOUTslots, c->dABU, c->dAF, c->dRoi, c->dRoiSave, c->dRoiLoad, c->dDENS, c->dPAR, c->dCSC, c->dDSC, c->dOPT, c->dEMIT, c->dEMWEI, c->dXAB, c->dINTV, c->dEMINDEX, c->dSeedTab, c->dStats, c->dODIR, c->dORA, c->dODE, c->dHPBG, c->dHPBGP, c->dT, c->dTTT, c->dEbuf, c->dEF, c->dMapEmit, c->dMap, c->dMapTau,
+    void *bufs[] = { c->dOUTslots, c->dABU, c->dAF, c->dRoi, c->dRoiSave, c->dRoiLoad, c->dDENS, c->dPAR, c->dCSC, c->dDSC, c->dOPT, c->dEMIT, c->dEMWEI, c->dXAB, c->dINTV, c->dEMINDEX, c->dSeedTab, c->dStats, c->dODIR, c->dORA, c->dODE, c->dHPBG, c->dHPBGP, c->dT, c->dTTT, c->dEbuf, c->dEF, c->dMapEmit, c->dMap, c->dMapTau, c->dBfield, c->dPolMap,
                      c->aIw, c->aTdown, c->aEA, c->aAF, c->aABS, c->aEMIT, c->aAll, c->aSum, c->aFirst, c->aLast, c->aIwOff, c->aDst, c->aIbeg,
                      c->mABS, c->mSUM, c->mABU, c->mT, c->mTab, c->mRABS };
     for (void *b : bufs) if (b) (void)hipFree(b);
@@ -443,6 +446,7 @@ int soc_set_grid(soc_ctx *c, int NX, int NY, int NZ, int LEVELS, const int32_t *
             }
         }
         if (c->dEMINDEX) { (void)hipFree(c->dEMINDEX); c->dEMINDEX = nullptr; }
+        if (c->dBfield) { (void)hipFree(c->dBfield); c->dBfield = nullptr; }
         c->have_T = false;  c->with_ali = false;  c->have_emindex = false;
         c->abu_ndust = 0;  c->abu_cells = 0;
     }
@@ -1764,6 +1768,77 @@ int soc_map(soc_ctx *c, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const
     return SOC_OK;
 }
 
+// polarisation maps (ASOC.py:3651-3801 -> PolMapping, kernel_ASOC_map.c:972-1137, :1147-1384, :1594-1693)
+int soc_set_bfield(soc_ctx *c, const float *Bx, const float *By, const float *Bz)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!Bx && !By && !Bz) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->dBfield) { (void)hipFree(c->dBfield); c->dBfield = nullptr; }
+        return SOC_OK;
+    }
+    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_set_bfield: call soc_set_grid first");
+    if (!Bx || !By || !Bz) return fail(c, SOC_ERR_ARG, "soc_set_bfield: Bx, By and Bz are needed (all NULL frees the field)");
+    const size_t cells = (size_t)c->G.CELLS;
+    float *tmp = nullptr;
+    if (hipMalloc((void **)&tmp, 3 * cells * 4) != hipSuccess) return fail(c, SOC_ERR_HIP, "soc_set_bfield: allocation");
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && !c->dBfield) e = hipMalloc((void **)&c->dBfield, cells * sizeof(float4));
+    if (e == hipSuccess) e = hipMemcpyAsync(tmp, Bx, cells * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(tmp + cells, By, cells * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(tmp + 2 * cells, Bz, cells * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = soc_launch_pack_bfield((int)cells, tmp, tmp + cells, tmp + 2 * cells, c->dBfield, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(tmp);
+    if (e != hipSuccess) {
+        if (c->dBfield) { (void)hipFree(c->dBfield); c->dBfield = nullptr; }
+        return fail(c, SOC_ERR_HIP, "soc_set_bfield: %s", hipGetErrorString(e));
+    }
+    return SOC_OK;
+}
+
+int soc_polmap(soc_ctx *c, int polstat, int polred, int rho_weight, float p0, int NPIX_X, int NPIX_Y, float MAP_DX, const float *EMIT,
+               const float *DIR, const float *RA, const float *DE, const float *CENTRE, float ABS, float SCA, float LENGTH, float *MAP)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_polmap: call soc_set_grid first");
+    if (polstat != 0 && polstat != 1 && polstat != 3) return fail(c, SOC_ERR_ARG, "soc_polmap: polstat %d (0, 1 or 3)", polstat);
+    if (polstat == 3 && polred) return fail(c, SOC_ERR_ARG, "soc_polmap: polstat 3 uses the full field vector, polred cannot be encoded in it");
+    if (!c->dBfield) return fail(c, SOC_ERR_STATE, "soc_polmap: call soc_set_bfield first");
+    if (!EMIT || !MAP || !DIR || !RA || !DE || !CENTRE || !(MAP_DX > 0.0f)) return fail(c, SOC_ERR_ARG, "soc_polmap: EMIT, MAP, DIR, RA, DE, CENTRE and MAP_DX > 0 are needed");
+    if (NPIX_X < 1 || NPIX_Y < 1 || (int64_t)NPIX_X * NPIX_Y > 2147483647LL / 4) return fail(c, SOC_ERR_ARG, "soc_polmap: NPIX %d x %d", NPIX_X, NPIX_Y);
+    // the walk divides by the components of -DIR without clamping them (kernel_ASOC_map.c:1033): a zero would send the position to NaN
+    for (int k = 0; k < 3; k++) if (!std::isfinite(DIR[k]) || DIR[k] == 0.0f) return fail(c, SOC_ERR_ARG, "soc_polmap: DIR[%d] = %g", k, (double)DIR[k]);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)NPIX_X * NPIX_Y, cells = (size_t)c->G.CELLS;
+    if (c->mapemit_cap < cells) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, dev_alloc(&c->dMapEmit, cells));
+        c->mapemit_cap = cells;
+    }
+    if (c->polmap_cap < 4 * npix) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, dev_alloc(&c->dPolMap, 4 * npix));
+        c->polmap_cap = 4 * npix;
+    }
+    SocPolArgs A;
+    memset(&A, 0, sizeof A);
+    A.polstat = polstat;  A.polred = polred ? 1 : 0;  A.rho_weight = rho_weight ? 1 : 0;
+    A.LEVEL_THRESHOLD = c->map_level_threshold;
+    A.NPIX_X = NPIX_X;  A.NPIX_Y = NPIX_Y;
+    A.p0 = p0;  A.MAP_DX = MAP_DX;  A.ABS = ABS;  A.SCA = SCA;  A.LENGTH = LENGTH;
+    for (int k = 0; k < 3; k++) { A.DIR[k] = DIR[k];  A.RA[k] = RA[k];  A.DE[k] = DE[k];  A.CENTRE[k] = CENTRE[k]; }
+    A.EMIT = c->dMapEmit;  A.OPT = c->dOPT;  A.B = c->dBfield;  A.MAP = c->dPolMap;
+    HIPCHK(c, hipMemcpyAsync(c->dMapEmit, EMIT, cells * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, soc_launch_polmap(c->G, A, c->dOPT != nullptr, c->stream));
+    HIPCHK(c, hipMemcpyAsync(MAP, c->dPolMap, 4 * npix * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
 int soc_ps_tau(soc_ctx *c, int NO_PS, const float *PSPOS, const float *DIR, float ABS, float SCA, float LENGTH, float *pscolden, float *pstau)
 {
     if (!c) return SOC_ERR_ARG;
@@ -2254,8 +2329,8 @@ int soc_probe_math2(soc_ctx *c, int fn, const float *x, const float *x2, float *
     if (!c) return SOC_ERR_ARG;
     FLUSH(c);
     if (!x || !y || n <= 0) return fail(c, SOC_ERR_ARG, "soc_probe_math: bad arguments");
-    if (fn < 0 || fn > 15) return fail(c, SOC_ERR_ARG, "soc_probe_math: no function %d", fn);
-    if ((fn == 14 || fn == 15) != (x2 != nullptr)) return fail(c, SOC_ERR_ARG, "soc_probe_math: function %d takes %s", fn, x2 ? "one argument" : "two arguments");
+    if (fn < 0 || fn > 16) return fail(c, SOC_ERR_ARG, "soc_probe_math: no function %d", fn);
+    if ((fn == 14 || fn == 15 || fn == 16) != (x2 != nullptr)) return fail(c, SOC_ERR_ARG, "soc_probe_math: function %d takes %s", fn, x2 ? "one argument" : "two arguments");
     HIPCHK(c, hipSetDevice(c->device));
     float *dx = nullptr, *dx2 = nullptr, *dy = nullptr;
     hipError_t e = hipMalloc((void **)&dx, (size_t)n * 4);

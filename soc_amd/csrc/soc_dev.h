@@ -145,6 +145,22 @@ struct SocMapArgs {
     float *MAP, *SAVETAU;
 };
 hipError_t soc_launch_map(const SocGrid &G, const SocMapArgs &A, bool abu, hipStream_t st);
+// polarisation maps (soc_map.hip): one launch of PolMapping (kernel_ASOC_map.c:974-994, :1164-1184, :1600-1620)
+struct SocPolArgs {
+    int   polstat;                 // -D POLSTAT: 0 = I, Q, U, column density; 1 = rT, rI, jT, jI; 3 = <B>, <B_LOS>, <B_POS>, tau
+    int   polred, rho_weight;      // -D POLRED (p = |B| per cell), -D POL_RHO_WEIGHT
+    int   LEVEL_THRESHOLD;
+    int   NPIX_X, NPIX_Y;
+    float p0;                      // -D p00
+    float MAP_DX, ABS, SCA, LENGTH;
+    float DIR[3], RA[3], DE[3], CENTRE[3];
+    const float  *EMIT;
+    const float2 *OPT;
+    const float4 *B;               // [CELLS] (Bx, By, Bz, pad)
+    float *MAP;                    // [4 * NPIX_Y * NPIX_X]
+};
+hipError_t soc_launch_polmap(const SocGrid &G, const SocPolArgs &A, bool abu, hipStream_t st);
+hipError_t soc_launch_pack_bfield(int cells, const float *Bx, const float *By, const float *Bz, float4 *B, hipStream_t st);
 hipError_t soc_launch_pstau(const SocGrid &G, int no, const float4 *PSPOS, const float *DIR, float ABS, float SCA, const float2 *OPT, float LENGTH,
                             float *pscolden, float *pstau, hipStream_t st);
 

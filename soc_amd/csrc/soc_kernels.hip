@@ -391,6 +391,7 @@ __global__ void soc_math_probe_kernel(int fn, const float *x, const float *x2, f
     case 13: r = soc_floorf(v); break;
     case 14: r = soc_pownf(v, (int)w); break;
     case 15: r = soc_atan2f(v, w); break;
+    case 16: r = soc_fmodf_small(v, w); break;
     default: break;
     }
     y[i] = r;

@@ -1,4 +1,4 @@
-// soc_map.hip -- map making: Mapping and HealpixMapping of kernel_ASOC_map.c (:496-888, :890-970) for
+// soc_map.hip -- map making: Mapping, HealpixMapping and PolMapping of kernel_ASOC_map.c (:496-888, :890-970, :972-1693) for
 // gfx950.  One lane per map pixel integrates emission x extinction along its line
 // of sight through the (hierarchical) grid.
 //
@@ -8,7 +8,7 @@
 // "POS.z<=0.0") -- so after every step out of an octet the position is rebuilt from the root.  That
 // changes the last bits of positions and step lengths, hence of the maps; it is restated here as written
 // (soc_map_index) and pinned bit-exactly by the x86 build of the reference (oracle/_ref/refmap_*.so).
-// -D MAP_INTERPOLATION, ROI_MAP and LEVEL_THRESHOLD are launch arguments here; the polarisation kernels are not covered.
+// -D MAP_INTERPOLATION, ROI_MAP and LEVEL_THRESHOLD are launch arguments here; PolMapping (POLSTAT 0, 1, 3) follows at the end of the file.
 #include "soc_walk.h"
 
 #define SOC_MAP_PEPS 5.0e-4f
@@ -311,6 +311,250 @@ hipError_t soc_launch_pstau(const SocGrid &G, int no, const float4 *PSPOS, const
     else if (!dbl) { if (abu) SOC_PT(true, false, true);  else SOC_PT(true, false, false); }
     else           { if (abu) SOC_PT(true, true, true);   else SOC_PT(true, true, false); }
 #undef SOC_PT
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// polarisation maps: PolMapping of kernel_ASOC_map.c, -D POLSTAT=0 (:972-1137), =1 (:1147-1384), =3 (:1594-1693)
+// ------------------------------------------------------------------------------------
+// One lane per pixel, as Mapping.  -D POLRED, POL_RHO_WEIGHT and LEVEL_THRESHOLD are launch arguments, p00 is A.p0.  The
+// magnetic field is one float4 (Bx, By, Bz, pad) per cell: a step reads it with one 16-byte load.  The arithmetic keeps
+// the reference's operations and their order; dot, length and normalize are what oracle/ref_builtins.inc gives the x86
+// build of the reference (soc_normalize is the same normalize).
+#define SOC_POL_PI     3.1415926536f
+#define SOC_POL_TWOPI  6.2831853072f
+#define SOC_POL_PIHALF 1.5707963268f
+
+__device__ __forceinline__ float soc_dot3(float ax, float ay, float az, float bx, float by, float bz) { return ax * bx + ay * by + az * bz; }
+
+__device__ __forceinline__ bool soc_pol_outside(const SocGrid &G, float x, float y, float z)
+{
+    return (x <= 0.0f) || (x >= G.NX) || (y <= 0.0f) || (y >= G.NY) || (z <= 0.0f) || (z >= G.NZ);
+}
+
+// The ray's entry (:1011-1033, the same lines in every POLSTAT block): PolMapping starts BEHIND the cloud and takes the
+// largest of the three face crossings that stays inside, each minus EPS -- not Mapping's entry; no NX >= 200 branch,
+// no INTOBS, and the walking direction -DIR is not clamped.
+__device__ __forceinline__ void soc_pol_entry(const SocGrid &G, const SocPolArgs &A, int id, float &px, float &py, float &pz)
+{
+    const int   NX = G.NX, NY = G.NY, NZ = G.NZ;
+    const int   i = id % A.NPIX_X, j = id / A.NPIX_X;
+    const float dx = A.DIR[0], dy = A.DIR[1], dz = A.DIR[2];
+    px = A.CENTRE[0] + (i - 0.5f * (A.NPIX_X - 1)) * A.MAP_DX * A.RA[0] + (j - 0.5f * (A.NPIX_Y - 1)) * A.MAP_DX * A.DE[0];
+    py = A.CENTRE[1] + (i - 0.5f * (A.NPIX_X - 1)) * A.MAP_DX * A.RA[1] + (j - 0.5f * (A.NPIX_Y - 1)) * A.MAP_DX * A.DE[1];
+    pz = A.CENTRE[2] + (i - 0.5f * (A.NPIX_X - 1)) * A.MAP_DX * A.RA[2] + (j - 0.5f * (A.NPIX_Y - 1)) * A.MAP_DX * A.DE[2];
+    px -= (NX + NY + NZ) * dx;  py -= (NX + NY + NZ) * dy;  pz -= (NX + NY + NZ) * dz;
+    float sx, sy, sz;
+    if (dx >= 0.0f) sx = (NX - px) / (dx + 1.0e-10f) - SOC_MAP_EPS;  else sx = (0.0f - px) / dx - SOC_MAP_EPS;
+    if (dy >= 0.0f) sy = (NY - py) / (dy + 1.0e-10f) - SOC_MAP_EPS;  else sy = (0.0f - py) / dy - SOC_MAP_EPS;
+    if (dz >= 0.0f) sz = (NZ - pz) / (dz + 1.0e-10f) - SOC_MAP_EPS;  else sz = (0.0f - pz) / dz - SOC_MAP_EPS;
+    if (soc_pol_outside(G, px + sx * dx, py + sx * dy, pz + sx * dz)) sx = -1e10f;
+    if (soc_pol_outside(G, px + sy * dx, py + sy * dy, pz + sy * dz)) sy = -1e10f;
+    if (soc_pol_outside(G, px + sz * dx, py + sz * dy, pz + sz * dz)) sz = -1e10f;
+    sx = __builtin_fmaxf(sx, __builtin_fmaxf(sy, sz));
+    px = px + sx * dx;  py = py + sx * dy;  pz = pz + sx * dz;
+}
+
+// emission weight of one step (:1095-1099, :1255-1259, :1329-1333)
+__device__ __forceinline__ float soc_pol_emitted(float TAU, float DTAU, float sx, float emit, float rho)
+{
+    if (DTAU < 1.0e-3f) return soc_expf(-TAU) * (1.0f - 0.5f * DTAU) * sx * emit * rho;
+    return soc_expf(-TAU) * ((1.0f - soc_expf(-DTAU)) / DTAU) * sx * emit * rho;
+}
+
+template <bool OCT, bool DBL, bool ABU, int POLSTAT>
+__global__ __launch_bounds__(256) void soc_polmap_kernel(const SocGrid G, const SocPolArgs A)
+{
+    __shared__ int sOFF[SOC_MAXL];
+    if (threadIdx.x < SOC_MAXL) sOFF[threadIdx.x] = G.OFF[threadIdx.x];
+    __syncthreads();
+    const int npix = A.NPIX_X * A.NPIX_Y;
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= npix) return;
+    const float dx = A.DIR[0], dy = A.DIR[1], dz = A.DIR[2];
+    const float tx = -dx, ty = -dy, tz = -dz;                             // away from the observer
+    const float rx = -A.RA[0], ry = -A.RA[1], rz = -A.RA[2];              // "our RA is an axis pointing to the right" (:1083-1085)
+    const float ex = A.DE[0], ey = A.DE[1], ez = A.DE[2];
+    const float OPTSUM = A.SCA + A.ABS;
+    float p0x, p0y, p0z;
+    soc_pol_entry(G, A, id, p0x, p0y, p0z);
+    float px = p0x, py = p0y, pz = p0z, dens = 0.0f, TAU = 0.0f;
+    int   level = 0, ind = -1;
+    soc_indexg<OCT>(G, sOFF, px, py, pz, level, ind, dens);
+
+    if (POLSTAT == 0) {                                                   // I, Q, U, column density (:1060-1126)
+        float I = 0.0f, Q = 0.0f, U = 0.0f, colden = 0.0f, p = A.p0;
+        while (ind >= 0) {
+            const int   oind = sOFF[level] + ind, olevel = level;
+            const float rho = dens;
+            const float sx = soc_map_getstep<OCT, DBL>(G, sOFF, px, py, pz, tx, ty, tz, level, ind, dens);
+            float DTAU;
+            if (ABU) { const float2 o = A.OPT[oind];  DTAU = sx * rho * (o.x + o.y); }
+            else     DTAU = sx * rho * OPTSUM;
+            const float4 B = A.B[oind];
+            float bx = B.x, by = B.y, bz = B.z;
+            if (A.polred) p = soc_sqrtf(bx * bx + by * by + bz * bz);     // -D POLRED: p = |B|
+            soc_normalize(bx, by, bz);
+            const float Psi = 0.5f * SOC_POL_PI + soc_atan2f(soc_dot3(bx, by, bz, rx, ry, rz), soc_dot3(bx, by, bz, ex, ey, ez));
+            const float bd = soc_dot3(bx, by, bz, dx, dy, dz);
+            const float cc = 0.99999f - 0.99998f * bd * bd;               // cos^2 of the angle to the plane of the sky
+            float sz;
+            if (A.rho_weight) sz = sx * rho;                              // -D POL_RHO_WEIGHT
+            else              sz = soc_pol_emitted(TAU, DTAU, sx, A.EMIT[oind], rho);
+            if (olevel >= A.LEVEL_THRESHOLD) {                            // -D LEVEL_THRESHOLD: coarser cells only absorb (:1104)
+                float s2, c2;
+                soc_sincosf(2.0f * Psi, &s2, &c2);
+                I += sz * (1.0f - p * (cc - 0.6666667f));
+                Q += p * sz * c2 * cc;
+                U += p * sz * s2 * cc;
+            }
+            TAU += DTAU;
+            colden += sx * rho;
+        }
+        A.MAP[0 * (size_t)npix + id] = I;
+        A.MAP[1 * (size_t)npix + id] = Q;
+        A.MAP[2 * (size_t)npix + id] = U;
+        A.MAP[3 * (size_t)npix + id] = colden * A.LENGTH;
+    } else if (POLSTAT == 1) {                                            // rT, rI, jT, jI: two passes (:1229-1378)
+        float sR = 0.0f, sJ = 0.0f, sRG = 0.0f, sJG = 0.0f, RQ = 0.0f, RU = 0.0f, JQ = 0.0f, JU = 0.0f;
+        while (ind >= 0) {
+            const int   oind = sOFF[level] + ind, olevel = level;
+            float rho = dens;
+            const float sx = soc_map_getstep<OCT, DBL>(G, sOFF, px, py, pz, tx, ty, tz, level, ind, dens);
+            float DTAU;
+            if (ABU) { const float2 o = A.OPT[oind];  DTAU = sx * rho * (o.x + o.y); }
+            else     DTAU = sx * rho * OPTSUM;
+            const float4 B = A.B[oind];
+            float bx = B.x, by = B.y, bz = B.z;
+            const float PR = soc_sqrtf(bx * bx + by * by + bz * bz);
+            soc_normalize(bx, by, bz);
+            const float Psi = 0.5f * SOC_POL_PI + soc_atan2f(soc_dot3(bx, by, bz, rx, ry, rz), soc_dot3(bx, by, bz, ex, ey, ez));
+            const float bd = soc_dot3(bx, by, bz, dx, dy, dz);
+            const float cc = 0.99999f - 0.99998f * bd * bd;
+            float sz = soc_pol_emitted(TAU, DTAU, sx, A.EMIT[oind], rho);
+            if (olevel < A.LEVEL_THRESHOLD) { sz = 0.0f;  rho = 0.0f; }   // (:1263)
+            float s2, c2;
+            soc_sincosf(2.0f * Psi, &s2, &c2);
+            if (A.polred) {
+                sR  += rho * sx * PR;
+                sRG += rho * sx * PR * cc;
+                RQ  += rho * sx * PR * c2 * cc;
+                RU  += rho * sx * PR * s2 * cc;
+                sJ  += sz * PR;
+                sJG += sz * PR * cc;
+                JQ  += sz * PR * c2 * cc;
+                JU  += sz * PR * s2 * cc;
+            } else {
+                sR  += rho * sx;
+                sRG += rho * sx * cc;
+                RQ  += rho * sx * c2 * cc;
+                RU  += rho * sx * s2 * cc;
+                sJ  += sz;
+                sJG += sz * cc;
+                JQ  += sz * c2 * cc;
+                JU  += sz * s2 * cc;
+            }
+            TAU += DTAU;
+        }
+        A.MAP[1 * (size_t)npix + id] = soc_acosf(soc_sqrtf(sRG / sR));
+        A.MAP[3 * (size_t)npix + id] = soc_acosf(soc_sqrtf(sJG / sJ));
+        const float RChi = (float)(0.5 * soc_atan2f(RU, RQ));             // "0.5*atan2(...)": the literal is a double (:1305-1306)
+        const float JChi = (float)(0.5 * soc_atan2f(JU, JQ));
+        px = p0x;  py = p0y;  pz = p0z;
+        soc_indexg<OCT>(G, sOFF, px, py, pz, level, ind, dens);
+        TAU = 0.0f;
+        float sRP = 0.0f, sJP = 0.0f;
+        sR = 0.0f;  sJ = 0.0f;
+        while (ind >= 0) {
+            const int   oind = sOFF[level] + ind, olevel = level;
+            float rho = dens;
+            const float sx = soc_map_getstep<OCT, DBL>(G, sOFF, px, py, pz, tx, ty, tz, level, ind, dens);
+            float DTAU;
+            if (ABU) { const float2 o = A.OPT[oind];  DTAU = sx * rho * (o.x + o.y); }
+            else     DTAU = sx * rho * OPTSUM;
+            const float4 B = A.B[oind];
+            float bx = B.x, by = B.y, bz = B.z;
+            const float PR = soc_sqrtf(bx * bx + by * by + bz * bz);
+            soc_normalize(bx, by, bz);
+            const float Chi = 0.5f * SOC_POL_PI + soc_atan2f(soc_dot3(bx, by, bz, rx, ry, rz), soc_dot3(bx, by, bz, ex, ey, ez));
+            float sz = soc_pol_emitted(TAU, DTAU, sx, A.EMIT[oind], rho);
+            if (olevel < A.LEVEL_THRESHOLD) { sz = 0.0f;  rho = 0.0f; }   // (:1339)
+            float d = soc_fmodf_small(soc_fabsf(SOC_POL_TWOPI + RChi - Chi), SOC_POL_PI);
+            if (d > SOC_POL_PIHALF) d = SOC_POL_PI - d;
+            float e = soc_fmodf_small(soc_fabsf(SOC_POL_TWOPI + JChi - Chi), SOC_POL_PI);
+            if (e > SOC_POL_PIHALF) e = SOC_POL_PI - e;
+            if (A.polred) {
+                sR  += rho * PR * sx;
+                sRP += rho * PR * sx * d * d;
+                sJ  += sz * PR;
+                sJP += sz * PR * e * e;
+            } else {
+                sR  += rho * sx;
+                sRP += rho * sx * d * d;
+                sJ  += sz;
+                sJP += sz * e * e;
+            }
+            TAU += DTAU;
+        }
+        A.MAP[0 * (size_t)npix + id] = soc_sqrtf(sRP / sR);
+        A.MAP[2 * (size_t)npix + id] = soc_sqrtf(sJP / sJ);
+    } else {                                                              // <B>, <B_LOS>, <B_POS>, tau (:1661-1687)
+        float SUM_BPOS = 0.0f, SUM_BLOS = 0.0f, SUM_B = 0.0f, WEIGHT = 0.0f;
+        while (ind >= 0) {
+            const int   oind = sOFF[level] + ind, olevel = level;
+            float rho = dens;
+            const float sx = soc_map_getstep<OCT, DBL>(G, sOFF, px, py, pz, tx, ty, tz, level, ind, dens);
+            float DTAU;
+            if (ABU) { const float2 o = A.OPT[oind];  DTAU = sx * rho * (o.x + o.y); }
+            else     DTAU = sx * rho * OPTSUM;
+            const float4 B = A.B[oind];
+            if (olevel < A.LEVEL_THRESHOLD) rho = 0.0f;                   // (:1674)
+            const float br = soc_dot3(B.x, B.y, B.z, rx, ry, rz), be = soc_dot3(B.x, B.y, B.z, ex, ey, ez);
+            WEIGHT   += sx * rho;
+            SUM_B    += sx * rho * soc_sqrtf(B.x * B.x + B.y * B.y + B.z * B.z);
+            SUM_BLOS += sx * rho * soc_fabsf(soc_dot3(B.x, B.y, B.z, tx, ty, tz));
+            SUM_BPOS += sx * rho * soc_sqrtf(br * br + be * be);          // pow(x, 2.0f) is the exact square, rounded once
+            TAU      += DTAU;
+        }
+        A.MAP[0 * (size_t)npix + id] = SUM_B / WEIGHT;
+        A.MAP[1 * (size_t)npix + id] = SUM_BLOS / WEIGHT;
+        A.MAP[2 * (size_t)npix + id] = SUM_BPOS / WEIGHT;
+        A.MAP[3 * (size_t)npix + id] = TAU;
+    }
+}
+
+template <int POLSTAT>
+static void soc_polmap_dispatch(const SocGrid &G, const SocPolArgs &A, bool abu, dim3 grid, dim3 block, hipStream_t st)
+{
+    const bool oct = G.LEVELS > 1, dbl = oct && (G.NX > 100);            // kernel_ASOC_map.c:297
+    if (!oct)      { if (abu) soc_polmap_kernel<false, false, true, POLSTAT><<<grid, block, 0, st>>>(G, A); else soc_polmap_kernel<false, false, false, POLSTAT><<<grid, block, 0, st>>>(G, A); }
+    else if (!dbl) { if (abu) soc_polmap_kernel<true, false, true, POLSTAT><<<grid, block, 0, st>>>(G, A);  else soc_polmap_kernel<true, false, false, POLSTAT><<<grid, block, 0, st>>>(G, A); }
+    else           { if (abu) soc_polmap_kernel<true, true, true, POLSTAT><<<grid, block, 0, st>>>(G, A);   else soc_polmap_kernel<true, true, false, POLSTAT><<<grid, block, 0, st>>>(G, A); }
+}
+
+hipError_t soc_launch_polmap(const SocGrid &G, const SocPolArgs &A, bool abu, hipStream_t st)
+{
+    const int npix = A.NPIX_X * A.NPIX_Y;
+    if (npix <= 0) return hipSuccess;
+    const dim3 grid((npix + 255) / 256), block(256);
+    if (A.polstat == 0)      soc_polmap_dispatch<0>(G, A, abu, grid, block, st);
+    else if (A.polstat == 1) soc_polmap_dispatch<1>(G, A, abu, grid, block, st);
+    else if (A.polstat == 3) soc_polmap_dispatch<3>(G, A, abu, grid, block, st);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// (Bx, By, Bz) -> one float4 per cell
+__global__ void soc_pack_bfield_kernel(int cells, const float *Bx, const float *By, const float *Bz, float4 *B)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cells) B[i] = make_float4(Bx[i], By[i], Bz[i], 0.0f);
+}
+
+hipError_t soc_launch_pack_bfield(int cells, const float *Bx, const float *By, const float *Bz, float4 *B, hipStream_t st)
+{
+    if (cells <= 0) return hipSuccess;
+    soc_pack_bfield_kernel<<<(cells + 255) / 256, 256, 0, st>>>(cells, Bx, By, Bz, B);
     return hipGetLastError();
 }
 

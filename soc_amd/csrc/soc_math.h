@@ -60,6 +60,20 @@ SOC_HD double soc_fmod1d(double x)
     return __builtin_copysign(r, x);
 }
 
+// fmod(x, y) for y > 0 and a quotient |x|/y below 2^22 (the polarisation statistics fold an angle
+// difference into [0, pi): kernel_ASOC_map.c:1350-1363): exact, result has the sign of x.  n = trunc(|x|/y) from
+// the rounded quotient is right or off by one; |x| - n*y is then representable, so the fma returns it
+// exactly, and a remainder outside [0, y) shows which way n has to move.
+SOC_HD float soc_fmodf_small(float x, float y)
+{
+    const float a = soc_fabsf(x);
+    float n = __builtin_truncf(a / y);
+    float r = SOC_FMA(-n, y, a);
+    if (r < 0.0f)    { n -= 1.0f;  r = SOC_FMA(-n, y, a); }
+    else if (r >= y) { n += 1.0f;  r = SOC_FMA(-n, y, a); }
+    return __builtin_copysignf(r, x);
+}
+
 // ldexp(x, -level) / ldexp(x, +level) for 0 <= level <= 30: exact power-of-two scaling
 SOC_HD float soc_scale_down(float x, int level) { return x * soc_u2f((uint32_t)(127 - level) << 23); }
 SOC_HD float soc_scale_up(float x, int level) { return x * soc_u2f((uint32_t)(127 + level) << 23); }

@@ -111,6 +111,8 @@ class Pipeline:
         if self.want_maps:
             U.NOMAP = 0
             rt.write_maps(EMITTED)
+        if U.POLMAP:                                               # also under `nomap` (ASOC.py:3655)
+            rt.write_polmaps(EMITTED)
         self.timers["maps"] = time.time() - t0
         self.log("@@ driver: transfer %.2f s, emission %.2f s, maps %.2f s" % (self.timers["transfer"], self.timers["emission"], self.timers["maps"]))
         return CTABS, FABSORBED, EMITTED

@@ -482,10 +482,12 @@ def _fits_card(key, value, comment=""):
     return card[:80].ljust(80)
 
 
-def write_fits(path, data, lon, lat, pix, freq=(), galactic=False):
+def write_fits(path, data, lon, lat, pix, freq=(), galactic=False, planes=False):
     """One primary HDU with the header MakeFits gives its images: data[n, m] (or [nchn, n, m] with `freq`), float32
     big-endian; tangent projection centred on (lon, lat) [deg], pixel `pix` [rad].  Written by hand (80-character cards,
-    2880-byte blocks) -- the image has no astropy."""
+    2880-byte blocks) -- the image has no astropy.  planes: data[k, n, m] put into the header of a 2-d image, as the
+    polarisation maps are (ASOC.py:3798-3799: MakeFits without frequencies, then data = MAP.reshape(4, n, m)) -- a third
+    axis without channel cards or frequency comments."""
     a = np.asarray(data, np.float32)
     cube = a.ndim == 3
     n, m = a.shape[-2], a.shape[-1]
@@ -502,7 +504,7 @@ def write_fits(path, data, lon, lat, pix, freq=(), galactic=False):
     else:
         cards += [_fits_card("CTYPE1", "RA---TAN"), _fits_card("CTYPE2", "DEC--TAN"), _fits_card("COORDSYS", "EQUATORIAL"),
                   _fits_card("EQUINOX", 2000.0)]
-    if cube:
+    if cube and not planes:
         cards += [_fits_card("CRPIX3", 1), _fits_card("CRVAL3", 0.0), _fits_card("CDELT3", 1), _fits_card("CTYPE3", "channel")]
         for i, f in enumerate(freq):
             cards.append(("COMMENT F[ %3d ] = %.4e" % (i, float(f))).ljust(80))

@@ -102,6 +102,9 @@ API = {
     "soc_emission": (C.c_int, [C.c_void_p, C.c_int, _F, _F, C.c_float, C.c_float, _F]),
     "soc_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F, _F, C.c_float, C.c_float, C.c_int,
                           C.c_float, _F, _F]),
+    "soc_set_bfield": (C.c_int, [C.c_void_p, _F, _F, _F]),
+    "soc_polmap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F,
+                             C.c_float, C.c_float, C.c_float, _F]),
     "soc_ps_tau": (C.c_int, [C.c_void_p, C.c_int, _F, _F, C.c_float, C.c_float, C.c_float, _F, _F]),
     "soc_a2e_set_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _F, _I, _I, _F, _F, _I, _F]),
     "soc_a2e_solve": (C.c_int, [C.c_void_p, C.c_int, _F, _F]),
@@ -525,6 +528,31 @@ class Engine:
                                    _f(MAP), _f(TAU)))
         return MAP, TAU
 
+    def set_bfield(self, Bx, By=None, Bz=None):
+        """The magnetic field of the polarisation maps: three arrays of CELLS floats (cloud-file order, parents included).
+        set_bfield(None) frees it."""
+        if Bx is None:
+            self._chk(self.lib.soc_set_bfield(self.h, None, None, None))
+            return
+        B = [np.ascontiguousarray(b, np.float32).ravel() for b in (Bx, By, Bz)]
+        if any(b.size != self.CELLS for b in B):
+            raise SocError("set_bfield: Bx, By and Bz must hold CELLS floats each")
+        self._chk(self.lib.soc_set_bfield(self.h, _f(B[0]), _f(B[1]), _f(B[2])))
+
+    def polmap(self, EMIT, DIR, RA, DE, NPIX, MAP_DX, CENTRE, ABS, SCA, polstat=0, polred=0, rho_weight=0, p0=0.2, LENGTH=1.0):
+        """One polarisation map (kernel_ASOC_map.c PolMapping): [4, NPIX.y, NPIX.x] = I, Q, U, column density (polstat 0),
+        rT, rI, jT, jI (polstat 1) or <B>, <B_LOS>, <B_POS>, tau (polstat 3)."""
+        EMIT = np.ascontiguousarray(EMIT, np.float32)
+        if EMIT.size != self.CELLS:
+            raise SocError("polmap: EMIT must hold CELLS floats")
+        v = [np.ascontiguousarray(np.asarray(a, np.float32).ravel()[:3]) for a in (DIR, RA, DE, CENTRE)]
+        nx, ny = int(NPIX[0]), int(NPIX[1])
+        MAP = np.zeros((4, max(ny, 0), max(nx, 0)), np.float32)
+        self._chk(self.lib.soc_polmap(self.h, int(polstat), int(polred), int(rho_weight), np.float32(p0), nx, ny, np.float32(MAP_DX),
+                                      _f(EMIT), _f(v[0]), _f(v[1]), _f(v[2]), _f(v[3]), np.float32(ABS), np.float32(SCA),
+                                      np.float32(LENGTH), _f(MAP)))
+        return MAP
+
     def ps_tau(self, PSPOS, DIR, ABS, SCA, LENGTH=1.0):
         """PSTau: (column density * LENGTH, optical depth) from every point source towards the observer direction DIR"""
         P = np.zeros((len(PSPOS), 4), np.float32)
@@ -826,9 +854,9 @@ class Engine:
         return st, dr[:, :ndraw]
 
     def probe_math(self, fn, x, x2=None):
-        """soc_math.h on the device; pown(x, n = x2) and atan2(y = x, x = x2) take the second array"""
+        """soc_math.h on the device; pown(x, n = x2), atan2(y = x, x = x2) and fmod(x, x2) take the second array"""
         code = dict(exp=0, log=1, sin=2, cos=3, acos=4, sqrt=5, fmod1=6, rcp=7, expm1=8, pow15=9, logd=10,
-                    exp_small=11, log10=12, floor=13, pown=14, atan2=15)[fn]
+                    exp_small=11, log10=12, floor=13, pown=14, atan2=15, fmod=16)[fn]
         x = np.ascontiguousarray(x, np.float32)
         y = np.zeros_like(x)
         if x2 is None:

@@ -215,3 +215,36 @@ def a2e_absorption_fraction(sol, isize):
     AF = np.asarray(sol["SK_ABS"][isize, :], np.float64) / np.asarray(K_ABS, np.float64)
     AF /= S_FRAC[isize] * sol["GD"]
     return np.asarray(np.clip(AF, 1.0e-32, 1.0e+100), np.float32)
+
+
+def cell_centres(cloud):
+    """[CELLS, 3] centres of all cells (parents included) in root-grid units."""
+    c = cloud
+    P = np.zeros((c.CELLS, 3), np.float64)
+    i = np.arange(c.NX * c.NY * c.NZ)
+    P[:len(i), 0], P[:len(i), 1], P[:len(i), 2] = i % c.NX + 0.5, (i // c.NX) % c.NY + 0.5, i // (c.NX * c.NY) + 0.5
+    oct_xyz = np.asarray([[k % 2, (k // 2) % 2, k // 4] for k in range(8)], np.float64) - 0.5
+    for l in range(c.LEVELS - 1):
+        d = c.DENS[c.OFF[l]:c.OFF[l] + c.LCELLS[l]]
+        parents = np.nonzero(d <= 0.0)[0]
+        first = F2I(-d[parents]).astype(np.int64) + c.OFF[l + 1]
+        for k in range(8):
+            P[first + k] = P[c.OFF[l] + parents] + oct_xyz[k] * 0.5 ** (l + 1)
+    return P
+
+
+def magnetic_field(cloud, seed=1, modes=4):
+    """A magnetic field for polarisation maps, as three float32 arrays of CELLS values (the layout of the B files of the
+    `polmap` key: every cell, parents included).  The direction varies smoothly with position (a sum of a few random
+    long-wavelength modes), the length of every vector is drawn from (0, 1)."""
+    rng = np.random.default_rng(seed)
+    P = cell_centres(cloud) / max(cloud.NX, cloud.NY, cloud.NZ)
+    B = np.zeros((cloud.CELLS, 3), np.float64)
+    for _ in range(modes):
+        k = rng.uniform(-1.5, 1.5, 3) * 2.0 * np.pi
+        B += np.outer(np.cos(P @ k + rng.uniform(0.0, 2.0 * np.pi)), rng.standard_normal(3))
+    B += 0.3 * rng.standard_normal(3)
+    B /= np.sqrt((B * B).sum(axis=1, keepdims=True)) + 1.0e-12
+    B *= rng.uniform(0.02, 0.98, (cloud.CELLS, 1))
+    B = np.asarray(B, np.float32)
+    return np.ascontiguousarray(B[:, 0]), np.ascontiguousarray(B[:, 1]), np.ascontiguousarray(B[:, 2])
