@@ -46,6 +46,10 @@ int  soc_create(int device, soc_ctx **out);
 void soc_destroy(soc_ctx *ctx);
 const char *soc_last_error(const soc_ctx *ctx);   /* ctx may be NULL: last creation error */
 const char *soc_version(void);
+/* bytes of device memory the library's handles hold at the moment, all handles of the process together: what they allocated themselves.
+ * Memory of the caller (soc_bind_tally, soc_sca_bind_out) and the scratch of the brick sweep do not count.  A counter on the host:
+ * it reads no device state.  After the last soc_destroy it is back where it was before the first soc_create. */
+int64_t soc_device_bytes(void);
 
 /* run on an externally owned HIP stream (e.g. the stream of the caller's framework); NULL = own stream.
  * NOTE: a framework's "default stream" is the null handle too -- pass a stream the framework created

@@ -1,8 +1,7 @@
 // soc_capi.hip -- host side of libsoc_hip.so: the C ABI declared in include/soc_hip.h.
 // Owns device memory, validates the model on the host before anything reaches a kernel,
 // derives the per-launch seed constants and dispatches the kernels of soc_kernels.hip.
-#include "../../include/soc_hip.h"
-#include "soc_dev.h"
+#include "soc_host.h"
 #include "soc_rng.h"
 
 #include <cmath>
@@ -10,123 +9,14 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
-#include <string>
-#include <vector>
 
 #define SOC_HPBG_PIX 49152         // pixels of the Healpix sky (NSIDE 64, fixed in the reference: ASOC.py:297)
 
-struct soc_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::string err;
-    // model
-    bool have_grid = false;
-    SocGrid G{};
-    float *dDENS = nullptr;
-    int   *dPAR = nullptr;
-    int64_t npar = 0;
-    // tables / per-frequency data
-    float *dCSC = nullptr, *dDSC = nullptr;
-    int    BINS = 0;
-    bool   have_dsc = false;
-    // scattered-light view (soc_sca_*)
-    SocSca view{};
-    float4 *dODIR = nullptr, *dORA = nullptr, *dODE = nullptr;
-    float  *dOUT = nullptr;
-    bool    own_OUT = false, have_view = false;
-    float  ABS = 0.0f, SCA = 0.0f;
-    bool   have_optical = false;
-    float2 *dOPT = nullptr;
-    float *dEMIT = nullptr, *dEMWEI = nullptr, *dXAB = nullptr;
-    float *dINTV = nullptr;            // -D SAVE_INTENSITY=2: INTX | INTY | INTZ, CELLS floats each (with_int == 2)
-    size_t intv_cells = 0;
-    int   *dEMINDEX = nullptr;
-    bool   have_emit = false, have_emindex = false, with_ali = false;
-    float *dHPBG = nullptr, *dHPBGP = nullptr;    // Healpix sky of the current frequency (NSIDE 64)
-    float *dABU = nullptr, *dAF = nullptr;        // abundances [CELLS, NDUST] (or [CELLS]), cross sections of the frequency
-    int    abu_ndust = 0, abu_single = 0;
-    int    map_level_threshold = 0;    // -D LEVEL_THRESHOLD (soc_set_map_threshold)
-    int    map_interpolation = 0;      // -D MAP_INTERPOLATION (soc_set_map_interpolation)
-    int    map_roi_on = 0, map_roi[6] = { 0, 0, 0, 0, 0, 0 };   // -D ROI_MAP (soc_set_map_roi)
-    float  cr_rate = 0.0f;             // -D CR_HEATING_RATE with -D CR_HEATING=1 (soc_set_cr_heating); 0 = off
-    bool   opt_half = false;          // -D OPT_IS_HALF: OPT rounded through fp16 (soc_set_opt_half)
-    bool   opt_from_abu = false;       // dOPT and dAF hold the current frequency's soc_set_optical_abu values
-    int    msf_ndust = 1;              // > 1: -D WITH_MSF, dCSC/dDSC hold [msf_ndust][BINS] (soc_set_scatter_tables)
-    int    step_weight = 0;            // -D STEP_WEIGHT (soc_set_step_weight)
-    float  sw_a = 0.0f, sw_b = 0.0f;
-    size_t abu_cells = 0;
-    SocRoi roi{};                                 // region of interest (host copy of *dRoi)
-    SocRoi *dRoi = nullptr;
-    float *dRoiSave = nullptr, *dRoiLoad = nullptr;
-    size_t roi_save_n = 0, roi_load_cap = 0;
-    bool   have_hpbg = false, hpbg_weighted = false;
-    // tallies
-    float *dTABS = nullptr, *dINT = nullptr;
-    bool   own_TABS = false, own_INT = false;
-    // deferred launches (soc_batch_begin .. soc_batch_end): executed together in one brick sweep (scattered light: one sweep of rays)
-    bool   batching = false;
-    int    batch_max = 4;
-    std::vector<SocSim> pending;
-    // Device copies of launch inputs, one buffer per store and launch slot (slot_buf): a deferred launch keeps in its slot what the
-    // caller overwrites for the next frequency; slot 0 also holds the point sources of a launch that runs at once.  SLOT_INT holds the
-    // INT tallies of a batch by group (soc_batch_read_int), SLOT_OPT one buffer in slot 0 (the sweep strides through it).  A buffer is
-    // allocated when its slot first needs more than it holds (128 slots of a 5e7-cell model up front would be 50 GB).
-    enum SlotStore { SLOT_SRC, SLOT_CSC, SLOT_DSC, SLOT_OPT, SLOT_EMIT, SLOT_HP, SLOT_INT, SLOT_STORES };
-    void  *slots[SLOT_STORES][SOC_MAXLAUNCH] = {};
-    size_t slot_bytes[SLOT_STORES][SOC_MAXLAUNCH] = {};
-    float *dOUTslots = nullptr;                               // soc_sca_batch_images: several images, one per frequency of a batch
-    int    out_slots = 0, out_slot_cur = 0;
-    size_t out_slot_pixels = 0;
-    unsigned long long emit_gen = 0;              // bumped by soc_set_emission: launches deferred without a change in between share one copy
-    unsigned long long emit_slot_gen = 0;
-    int    emit_slot_last = -1;
-    int    int_slots_done = 0;                    // launches of the last executed sweep whose INT can be read
-    // the INT tally of the launches of a batch (set by the soc_batch_begin* call that opened it):
-    //   INT_OFF        soc_batch_begin: launches with the INT tally are not deferred
-    //   INT_SHARED     soc_batch_begin_shared_int: all tally into the handle's dINT
-    //   INT_PER_LAUNCH soc_batch_begin_int: every launch a zeroed slot of its own (SLOT_INT)
-    //   INT_PER_GROUP  soc_batch_begin_int_groups: the launches up to the next soc_batch_next_int share a slot
-    enum IntMode { INT_OFF, INT_SHARED, INT_PER_LAUNCH, INT_PER_GROUP } int_mode = INT_OFF;
-    bool   int_group_open = false;                // INT_PER_GROUP: the current group has its slot
-    // rng
-    uint64_t *dSeedTab = nullptr;
-    unsigned long long *dStats = nullptr;
-    unsigned long long ray_steps = 0;                        // cell steps of the rays of the scattered-light sweeps, as of the last soc_stats
-    // features
-    int with_int = 0, ps_method = 0, use_emweight = 0, mirror = 0;
-    // execution
-    int exec_mode = -1, brick_log2 = 4;
-    SocSweepResult last;                          // the last sweep's passes and form; variant: soc_last_variant, the absorption kernel last launched (-1: none yet)
-    SocBrickTune tune{};
-    // equilibrium temperature / emission (soc_emit.hip)
-    float *dT = nullptr, *dTTT = nullptr, *dEbuf = nullptr, *dEF = nullptr;
-    int    ttt_cap = 0, ef_cap = 0;
-    size_t ebuf_cap = 0;
-    bool   have_T = false;
-    // map making (soc_map.hip)
-    float *dMapEmit = nullptr, *dMap = nullptr, *dMapTau = nullptr;
-    size_t map_cap = 0, mapemit_cap = 0;
-    float4 *dBfield = nullptr;         // magnetic field, one (Bx, By, Bz, pad) per cell (soc_set_bfield)
-    float  *dPolMap = nullptr;         // the four planes of a polarisation map
-    size_t  polmap_cap = 0;
-    // A2E
-    int a2e_NE = 0, a2e_NFREQ = 0, a2e_npair = 0, a2e_cap = 0, a2e_noIw = 0;
-    float *aIw = nullptr, *aTdown = nullptr, *aEA = nullptr, *aAF = nullptr, *aABS = nullptr, *aEMIT = nullptr;
-    float *aAll = nullptr, *aSum = nullptr;                  // soc_a2e_resident_*: absorptions of all cells, emission summed over the sizes
-    int64_t a2e_cells = 0;  int a2e_res_nfreq = 0;
-    int   *aFirst = nullptr, *aLast = nullptr, *aIwOff = nullptr, *aDst = nullptr, *aIbeg = nullptr;
-    // the multi-dust stage (soc_mabu_*): absorptions as the absorbed file holds them, the sum over the dusts, abundances, relative cross
-    // sections, temperatures and tables of an equilibrium dust; the current dust's share and its emission are aAll and aSum
-    float  *mABS = nullptr, *mSUM = nullptr, *mABU = nullptr, *mT = nullptr, *mTab = nullptr;
-    double *mRABS = nullptr;
-    int     mabu_ndust = 0, mtab_cap = 0;
-    bool    mabu_tables = false;
-};
+std::atomic<int64_t> soc_dev_bytes{0};
 
 static std::string g_create_err;
 
-static int fail(soc_ctx *c, int code, const char *fmt, ...)
+int fail(soc_ctx *c, int code, const char *fmt, ...)
 {
     char buf[512];
     va_list ap;
@@ -138,37 +28,13 @@ static int fail(soc_ctx *c, int code, const char *fmt, ...)
     return code;
 }
 
-#define HIPCHK(c, call)                                                                       \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail((c), SOC_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));     \
-    } while (0)
-
-template <typename T>
-static hipError_t dev_alloc(T **p, size_t n)
-{
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    return hipMalloc((void **)p, (n ? n : 1) * sizeof(T));
-}
-
 // Slot k of a store of copies (soc_ctx::slots), at least `bytes` large.  A larger buffer replaces a smaller one once the stream has
 // drained (a launch in flight may read the old one); the contents stay otherwise.
 template <typename T>
 static int slot_buf(soc_ctx *c, int store, int k, size_t bytes, T **out)
 {
-    void *&p = c->slots[store][k];
-    size_t &cap = c->slot_bytes[store][k];
-    if (bytes > cap) {
-        if (p) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            (void)hipFree(p);
-            p = nullptr;  cap = 0;
-        }
-        HIPCHK(c, hipMalloc(&p, bytes));
-        cap = bytes;
-    }
-    *out = (T *)p;
+    HIPCHK(c, c->slots[store][k].reserve(bytes, c->stream));
+    *out = (T *)c->slots[store][k].p;
     return SOC_OK;
 }
 
@@ -181,14 +47,6 @@ static int slot_copy(soc_ctx *c, int store, int k, float **out, const float *a, 
     if (a) HIPCHK(c, hipMemcpyAsync(*out, a, na * 4, hipMemcpyDeviceToDevice, c->stream));
     if (b) HIPCHK(c, hipMemcpyAsync(*out + na, b, nb * 4, hipMemcpyDeviceToDevice, c->stream));
     return SOC_OK;
-}
-
-static void release_slots(soc_ctx *c)
-{
-    for (auto &store : c->slots)
-        for (void *&p : store)
-            if (p) { (void)hipFree(p);  p = nullptr; }
-    memset(c->slot_bytes, 0, sizeof c->slot_bytes);
 }
 
 // number of floats of the scattered-light image: NDIR maps of NPIX_X x NPIX_Y pixels, or one Healpix map
@@ -250,7 +108,7 @@ static int run_direct(soc_ctx *c, SocSim S, const SocVariant &V)
 // through the direct kernel instead when that is as fast -- a lone absorption launch on a hierarchy (1.9e10 vs 2.0e10 steps/s at 256^3,
 // 4 levels), scattered-light launches with too few rays to fill the brick queues -- and scattered-light launches also where the sweep
 // does not apply (it did when they were deferred: the grid has not changed since).
-static int flush_pending(soc_ctx *c)
+int flush_pending(soc_ctx *c)
 {
     if (c->pending.empty()) return SOC_OK;
     std::vector<SocSim> todo;
@@ -276,11 +134,6 @@ static int flush_pending(soc_ctx *c)
     if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "brick sweep of %d deferred launches failed: %s", (int)todo.size(), hipGetErrorString(e));
     return SOC_OK;
 }
-#define FLUSH(c)                                    \
-    do {                                            \
-        int f_ = flush_pending(c);                  \
-        if (f_) return f_;                          \
-    } while (0)
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -336,9 +189,9 @@ int soc_create(int device, soc_ctx **out)
     // seed tables: T[k][b] = G^(b*256^k) mod M with G = A^(2^38) mod M  (soc_rng.h)
     std::vector<uint64_t> tab(1024);
     soc_build_seed_table(tab.data());
-    if ((e = hipMalloc((void **)&c->dSeedTab, 1024 * sizeof(uint64_t))) != hipSuccess ||
+    if ((e = c->dSeedTab.reset(1024, c->stream)) != hipSuccess ||
         (e = hipMemcpy(c->dSeedTab, tab.data(), 1024 * sizeof(uint64_t), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMalloc((void **)&c->dStats, 4 * sizeof(unsigned long long))) != hipSuccess ||
+        (e = c->dStats.reset(4, c->stream)) != hipSuccess ||
         (e = hipMemsetAsync(c->dStats, 0, 4 * sizeof(unsigned long long), c->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
         int r = fail(nullptr, SOC_ERR_HIP, "soc_create: %s", hipGetErrorString(e));
@@ -355,20 +208,14 @@ void soc_destroy(soc_ctx *c)
     (void)flush_pending(c);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    release_slots(c);
-    void *bufs[] = { c->dOUTslots, c->dABU, c->dAF, c->dRoi, c->dRoiSave, c->dRoiLoad, c->dDENS, c->dPAR, c->dCSC, c->dDSC, c->dOPT, c->dEMIT, c->dEMWEI, c->dXAB, c->dINTV, c->dEMINDEX, c->dSeedTab, c->dStats, c->dODIR, c->dORA, c->dODE, c->dHPBG, c->dHPBGP, c->dT, c->dTTT, c->dEbuf, c->dEF, c->dMapEmit, c->dMap, c->dMapTau, c->dBfield, c->dPolMap,
-                     c->aIw, c->aTdown, c->aEA, c->aAF, c->aABS, c->aEMIT, c->aAll, c->aSum, c->aFirst, c->aLast, c->aIwOff, c->aDst, c->aIbeg,
-                     c->mABS, c->mSUM, c->mABU, c->mT, c->mTab, c->mRABS };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    if (c->own_TABS && c->dTABS) (void)hipFree(c->dTABS);
-    if (c->own_INT && c->dINT) (void)hipFree(c->dINT);
-    if (c->own_OUT && c->dOUT) (void)hipFree(c->dOUT);
+    if (c->device >= 64 || --g_handles[c->device] <= 0) soc_brick_release(c->device);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->device >= 64 || --g_handles[c->device] <= 0) soc_brick_release(c->device);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                                               // (every DevBuf of the handle frees what it owns)
 }
+
+int64_t soc_device_bytes(void) { return soc_dev_bytes.load(); }
 
 int soc_set_stream(soc_ctx *c, void *hip_stream)
 {
@@ -417,36 +264,32 @@ int soc_set_grid(soc_ctx *c, int NX, int NY, int NZ, int LEVELS, const int32_t *
         }
     }
     // refused before anything of the handle changes: a refused call leaves the old grid usable
-    if (c->have_grid && (int64_t)G.CELLS != c->G.CELLS && ((c->dTABS && !c->own_TABS) || (c->dINT && !c->own_INT)))
+    if (c->have_grid && (int64_t)G.CELLS != c->G.CELLS && ((c->dTABS && !c->dTABS.owned) || (c->dINT && !c->dINT.owned)))
         return fail(c, SOC_ERR_STATE, "soc_set_grid: a caller-owned tally of %d cells is bound; soc_bind_tally(ctx, which, NULL, 0) first, re-bind after", c->G.CELLS);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, dev_alloc(&c->dDENS, (size_t)cells));
+    HIPCHK(c, c->dDENS.reset((size_t)cells, c->stream));
     HIPCHK(c, hipMemcpy(c->dDENS, DENS, (size_t)cells * 4, hipMemcpyHostToDevice));
     c->npar = cells - nxyz;
-    HIPCHK(c, dev_alloc(&c->dPAR, (size_t)c->npar));
+    HIPCHK(c, c->dPAR.reset((size_t)c->npar, c->stream));
     HIPCHK(c, hipMemsetAsync(c->dPAR, 0, (size_t)(c->npar ? c->npar : 1) * 4, c->stream));
     G.DENS = c->dDENS;
     G.PAR = c->dPAR;
     if ((int64_t)G.CELLS != c->G.CELLS || !c->have_grid) {
         // tallies follow the cell count
-        if (c->own_TABS || !c->dTABS) { c->dTABS = nullptr; HIPCHK(c, dev_alloc(&c->dTABS, (size_t)cells)); c->own_TABS = true; HIPCHK(c, hipMemsetAsync(c->dTABS, 0, (size_t)cells * 4, c->stream)); }
-        if (c->own_INT || !c->dINT) { c->dINT = nullptr; HIPCHK(c, dev_alloc(&c->dINT, (size_t)cells)); c->own_INT = true; HIPCHK(c, hipMemsetAsync(c->dINT, 0, (size_t)cells * 4, c->stream)); }
-        if (c->dOPT) { (void)hipFree(c->dOPT); c->dOPT = nullptr; }
+        for (DevBuf<float> *t : { &c->dTABS, &c->dINT })
+            if (t->owned || !*t) { HIPCHK(c, t->reset((size_t)cells, c->stream)); HIPCHK(c, hipMemsetAsync(t->p, 0, (size_t)cells * 4, c->stream)); }
+        c->dOPT.release();
         c->have_emit = false;
         // everything else that is sized by the cell count
-        if (c->dT) { (void)hipFree(c->dT); c->dT = nullptr; }
-        if (c->dXAB) { (void)hipFree(c->dXAB); c->dXAB = nullptr; }
+        c->dT.release();  c->dXAB.release();  c->dEMINDEX.release();  c->dBfield.release();
         if (c->dINTV) {                                       // INTX, INTY, INTZ follow the cell count like TABS and INT (with_int stays 2)
-            (void)hipFree(c->dINTV);  c->dINTV = nullptr;  c->intv_cells = 0;
+            c->dINTV.release();
             if (c->with_int == 2) {
-                HIPCHK(c, dev_alloc(&c->dINTV, (size_t)3 * cells));
-                c->intv_cells = (size_t)cells;
+                HIPCHK(c, c->dINTV.reset((size_t)3 * cells, c->stream));
                 HIPCHK(c, hipMemsetAsync(c->dINTV, 0, (size_t)3 * cells * 4, c->stream));
             }
         }
-        if (c->dEMINDEX) { (void)hipFree(c->dEMINDEX); c->dEMINDEX = nullptr; }
-        if (c->dBfield) { (void)hipFree(c->dBfield); c->dBfield = nullptr; }
         c->have_T = false;  c->with_ali = false;  c->have_emindex = false;
         c->abu_ndust = 0;  c->abu_cells = 0;
     }
@@ -469,10 +312,9 @@ int soc_set_features(soc_ctx *c, int with_int, int ps_method, int use_emweight)
     if (with_int == 2) {                                    // SAVE_INTENSITY == 2: three more tallies (kernel_ASOC.c:604-612)
         if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_set_features: with_int 2 needs soc_set_grid first (it allocates INTX, INTY, INTZ)");
         HIPCHK(c, hipSetDevice(c->device));
-        if (c->intv_cells != (size_t)c->G.CELLS) {
+        if (c->dINTV.n != (size_t)3 * c->G.CELLS) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, dev_alloc(&c->dINTV, (size_t)3 * c->G.CELLS));
-            c->intv_cells = (size_t)c->G.CELLS;
+            HIPCHK(c, c->dINTV.reset((size_t)3 * c->G.CELLS, c->stream));
             HIPCHK(c, hipMemsetAsync(c->dINTV, 0, (size_t)3 * c->G.CELLS * 4, c->stream));
         }
     }
@@ -544,10 +386,10 @@ int soc_set_opt(soc_ctx *c, const float *OPT)
     c->opt_from_abu = false;
     if (!OPT) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->dOPT) { (void)hipFree(c->dOPT); c->dOPT = nullptr; }
+        c->dOPT.release();
         return SOC_OK;
     }
-    if (!c->dOPT) HIPCHK(c, dev_alloc(&c->dOPT, (size_t)c->G.CELLS));
+    if (!c->dOPT) HIPCHK(c, c->dOPT.reset((size_t)c->G.CELLS, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->dOPT, OPT, (size_t)c->G.CELLS * 8, hipMemcpyHostToDevice, c->stream));
     if (c->opt_half) HIPCHK(c, soc_launch_opt_half(c->G.CELLS, c->dOPT, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -579,8 +421,8 @@ int soc_set_abundances(soc_ctx *c, int NDUST, int single, const float *ABU)
     for (size_t i = 0; i < n; i++)
         if (!std::isfinite(ABU[i])) return fail(c, SOC_ERR_ARG, "soc_set_abundances: ABU[%zu] is not finite", i);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, dev_alloc(&c->dABU, n));
-    HIPCHK(c, dev_alloc(&c->dAF, (size_t)2 * NDUST));
+    HIPCHK(c, c->dABU.reset(n, c->stream));
+    HIPCHK(c, c->dAF.reset((size_t)2 * NDUST, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->dABU, ABU, n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->abu_ndust = NDUST;  c->abu_single = single ? 1 : 0;  c->abu_cells = (size_t)c->G.CELLS;
@@ -596,7 +438,7 @@ int soc_set_optical_abu(soc_ctx *c, const float *AFABS, const float *AFSCA, int 
     HIPCHK(c, hipSetDevice(c->device));
     float af[128];
     for (int d = 0; d < ndust; d++) { af[d] = AFABS[d];  af[ndust + d] = AFSCA[d]; }
-    if (!c->dOPT) HIPCHK(c, dev_alloc(&c->dOPT, (size_t)c->G.CELLS));
+    if (!c->dOPT) HIPCHK(c, c->dOPT.reset((size_t)c->G.CELLS, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->dAF, af, (size_t)2 * ndust * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));             // af is on the stack
     HIPCHK(c, soc_launch_opt(c->G.CELLS, ndust, c->abu_single, c->dABU, c->dAF, c->dOPT, c->stream));
@@ -626,8 +468,8 @@ int soc_set_scatter_tables(soc_ctx *c, int NDUST, const float *DSC, const float 
     const size_t n = (size_t)NDUST * BINS;
     if (BINS != c->BINS || NDUST != c->msf_ndust || !c->dCSC) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_alloc(&c->dCSC, n));
-        HIPCHK(c, dev_alloc(&c->dDSC, n));
+        HIPCHK(c, c->dCSC.reset(n, c->stream));
+        HIPCHK(c, c->dDSC.reset(n, c->stream));
         c->BINS = BINS;
         c->msf_ndust = NDUST;
         c->have_dsc = false;
@@ -664,8 +506,8 @@ int soc_set_emission(soc_ctx *c, const float *EMIT, const float *EMWEI)
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->G.CELLS;
     if (!c->have_emit) {
-        HIPCHK(c, dev_alloc(&c->dEMIT, n));
-        HIPCHK(c, dev_alloc(&c->dEMWEI, n));
+        HIPCHK(c, c->dEMIT.reset(n, c->stream));
+        HIPCHK(c, c->dEMWEI.reset(n, c->stream));
         HIPCHK(c, hipMemsetAsync(c->dEMWEI, 0, n * 4, c->stream));
         c->have_emit = true;
     }
@@ -684,7 +526,7 @@ int soc_set_emindex(soc_ctx *c, const int32_t *EMINDEX)
     for (int i = 0; i < c->G.CELLS; i++)
         if (EMINDEX[i] >= c->G.CELLS) return fail(c, SOC_ERR_ARG, "soc_set_emindex: EMINDEX[%d] = %d is not a cell", i, EMINDEX[i]);
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->dEMINDEX) HIPCHK(c, dev_alloc(&c->dEMINDEX, (size_t)c->G.CELLS));
+    if (!c->dEMINDEX) HIPCHK(c, c->dEMINDEX.reset((size_t)c->G.CELLS, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->dEMINDEX, EMINDEX, (size_t)c->G.CELLS * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_emindex = true;
@@ -698,7 +540,7 @@ int soc_set_ali(soc_ctx *c, int with_ali)
     if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_set_ali: call soc_set_grid first");
     HIPCHK(c, hipSetDevice(c->device));
     if (with_ali && !c->dXAB) {
-        HIPCHK(c, dev_alloc(&c->dXAB, (size_t)c->G.CELLS));
+        HIPCHK(c, c->dXAB.reset((size_t)c->G.CELLS, c->stream));
         HIPCHK(c, hipMemsetAsync(c->dXAB, 0, (size_t)c->G.CELLS * 4, c->stream));
     }
     c->with_ali = with_ali != 0;
@@ -825,7 +667,7 @@ static int take_int_slot(soc_ctx *c, const char *who, SocSim &S)
 {
     if (!(c->batching && int_slots(c) && c->with_int && S.INT)) return SOC_OK;
     if (c->int_mode == soc_ctx::INT_PER_GROUP && c->int_group_open) {     // a further launch of the current group: the group's tally
-        S.INT = (float *)c->slots[soc_ctx::SLOT_INT][c->int_slots_done - 1];
+        S.INT = (float *)c->slots[soc_ctx::SLOT_INT][c->int_slots_done - 1].p;
         return SOC_OK;
     }
     if (c->int_slots_done >= c->batch_max)
@@ -885,7 +727,7 @@ static int keep_emission(soc_ctx *c, SocSim &S, int slot)
         if (r) return r;
         c->emit_slot_last = slot;  c->emit_slot_gen = c->emit_gen;
     }
-    const float *em = (const float *)c->slots[soc_ctx::SLOT_EMIT][c->emit_slot_last];
+    const float *em = (const float *)c->slots[soc_ctx::SLOT_EMIT][c->emit_slot_last].p;
     S.EMIT = em;  S.EMWEI = em + cells;
     return SOC_OK;
 }
@@ -1064,7 +906,7 @@ int soc_batch_read_int(soc_ctx *c, int k, float *out, long n)
     if (k < 0 || k >= c->int_slots_done) return fail(c, SOC_ERR_ARG, "soc_batch_read_int: launch %d of %d deferred with the INT tally", k, c->int_slots_done);
     if (!out || n != (long)c->G.CELLS) return fail(c, SOC_ERR_ARG, "soc_batch_read_int: the tally has %d cells, buffer %ld", c->G.CELLS, n);
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->slots[soc_ctx::SLOT_INT][k], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->slots[soc_ctx::SLOT_INT][k].p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SOC_OK;
 }
@@ -1093,8 +935,8 @@ int soc_set_hpbg(soc_ctx *c, const float *BG, const float *HPBGP)
     }
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->dHPBG) {
-        HIPCHK(c, dev_alloc(&c->dHPBG, (size_t)NPIX));
-        HIPCHK(c, dev_alloc(&c->dHPBGP, (size_t)NPIX));
+        HIPCHK(c, c->dHPBG.reset((size_t)NPIX, c->stream));
+        HIPCHK(c, c->dHPBGP.reset((size_t)NPIX, c->stream));
     }
     HIPCHK(c, hipMemcpyAsync(c->dHPBG, BG, (size_t)NPIX * 4, hipMemcpyHostToDevice, c->stream));
     if (HPBGP) HIPCHK(c, hipMemcpyAsync(c->dHPBGP, HPBGP, (size_t)NPIX * 4, hipMemcpyHostToDevice, c->stream));
@@ -1108,7 +950,7 @@ int soc_set_hpbg(soc_ctx *c, const float *BG, const float *HPBGP)
 
 static int roi_upload(soc_ctx *c)
 {
-    if (!c->dRoi) HIPCHK(c, hipMalloc((void **)&c->dRoi, sizeof(SocRoi)));
+    HIPCHK(c, c->dRoi.reserve(1, c->stream));
     c->roi.SAVE = c->dRoiSave;
     c->roi.LOAD = c->dRoiLoad;
     HIPCHK(c, hipMemcpyAsync(c->dRoi, &c->roi, sizeof(SocRoi), hipMemcpyHostToDevice, c->stream));
@@ -1123,7 +965,6 @@ int soc_set_roi_save(soc_ctx *c, const int32_t *ROI, int ROI_STEP, int ROI_NSIDE
     HIPCHK(c, hipSetDevice(c->device));
     if (!ROI) {                                             // off
         c->roi.save = 0;
-        c->roi_save_n = 0;
         return roi_upload(c);
     }
     if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_set_roi_save: call soc_set_grid first");
@@ -1138,11 +979,10 @@ int soc_set_roi_save(soc_ctx *c, const int32_t *ROI, int ROI_STEP, int ROI_NSIDE
     const int64_t total = (n[0] * n[1] + n[1] * n[2] + n[2] * n[0]) * 12 * ROI_NSIDE * ROI_NSIDE;
     if (total > 2147483647LL) return fail(c, SOC_ERR_ARG, "soc_set_roi_save: %lld record entries (int32 indices in the kernel)", (long long)total);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, dev_alloc(&c->dRoiSave, (size_t)total));
+    HIPCHK(c, c->dRoiSave.reset((size_t)total, c->stream));
     HIPCHK(c, hipMemsetAsync(c->dRoiSave, 0, (size_t)total * 4, c->stream));
     for (int i = 0; i < 6; i++) c->roi.ROI[i] = ROI[i];
     c->roi.STEP = ROI_STEP;  c->roi.NSIDE = ROI_NSIDE;  c->roi.save = 1;
-    c->roi_save_n = (size_t)total;
     return roi_upload(c);
 }
 
@@ -1152,7 +992,7 @@ int soc_roi_zero(soc_ctx *c)
     FLUSH(c);
     if (!c->roi.save) return fail(c, SOC_ERR_STATE, "soc_roi_zero: call soc_set_roi_save first");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemsetAsync(c->dRoiSave, 0, c->roi_save_n * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->dRoiSave, 0, c->dRoiSave.n * 4, c->stream));
     return SOC_OK;
 }
 
@@ -1161,9 +1001,9 @@ int soc_roi_read(soc_ctx *c, float *out, long n)
     if (!c) return SOC_ERR_ARG;
     FLUSH(c);
     if (!c->roi.save) return fail(c, SOC_ERR_STATE, "soc_roi_read: call soc_set_roi_save first");
-    if (!out || n != (long)c->roi_save_n) return fail(c, SOC_ERR_ARG, "soc_roi_read: the record has %zu entries, buffer %ld", c->roi_save_n, n);
+    if (!out || n != (long)c->dRoiSave.n) return fail(c, SOC_ERR_ARG, "soc_roi_read: the record has %zu entries, buffer %ld", c->dRoiSave.n, n);
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->dRoiSave, c->roi_save_n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->dRoiSave, c->dRoiSave.n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SOC_OK;
 }
@@ -1186,11 +1026,7 @@ int soc_set_roi_load(soc_ctx *c, const int32_t *DIM, int ROI_NSIDE, const float 
     if (nelem > 21474836LL || total > 2147483647LL) return fail(c, SOC_ERR_ARG, "soc_set_roi_load: %lld surface elements", (long long)nelem);
     for (int64_t i = 0; i < total; i++)
         if (!std::isfinite(LOAD[i])) return fail(c, SOC_ERR_ARG, "soc_set_roi_load: LOAD[%lld] is not finite", (long long)i);
-    if (c->roi_load_cap < (size_t)total) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_alloc(&c->dRoiLoad, (size_t)total));
-        c->roi_load_cap = (size_t)total;
-    }
+    HIPCHK(c, c->dRoiLoad.reserve((size_t)total, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->dRoiLoad, LOAD, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
     for (int i = 0; i < 3; i++) c->roi.DIM[i] = DIM[i];
     c->roi.NELEM = (int)nelem;  c->roi.NSIDE = ROI_NSIDE;  c->roi.load = 1;
@@ -1248,9 +1084,8 @@ int soc_sim_cl(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, float
 static int view_image(soc_ctx *c, const char *who, size_t npix, size_t old)
 {
     if (c->dOUT && npix == old) return SOC_OK;
-    if (c->dOUT && !c->own_OUT) return fail(c, SOC_ERR_STATE, "%s: image size changed while a caller-owned image is bound", who);
-    HIPCHK(c, dev_alloc(&c->dOUT, npix));
-    c->own_OUT = true;
+    if (c->dOUT && !c->dOUT.owned) return fail(c, SOC_ERR_STATE, "%s: image size changed while a caller-owned image is bound", who);
+    HIPCHK(c, c->dOUT.reset(npix, c->stream));
     HIPCHK(c, hipMemsetAsync(c->dOUT, 0, npix * 4, c->stream));
     return SOC_OK;
 }
@@ -1278,9 +1113,9 @@ int soc_sca_set_view(soc_ctx *c, int NDIR, const float *ODIR, const float *RA, c
     const size_t old = view_pixels(c);
     if (NDIR != c->view.NDIR || !c->dODIR) {
         c->view.NDIR = 0;
-        HIPCHK(c, dev_alloc(&c->dODIR, (size_t)NDIR));
-        HIPCHK(c, dev_alloc(&c->dORA, (size_t)NDIR));
-        HIPCHK(c, dev_alloc(&c->dODE, (size_t)NDIR));
+        HIPCHK(c, c->dODIR.reset((size_t)NDIR, c->stream));
+        HIPCHK(c, c->dORA.reset((size_t)NDIR, c->stream));
+        HIPCHK(c, c->dODE.reset((size_t)NDIR, c->stream));
     }
     int r = view_image(c, "soc_sca_set_view", npix, old);
     if (r) return r;
@@ -1308,9 +1143,9 @@ int soc_sca_set_healpix(soc_ctx *c, int NSIDE, const float *OBSERVER, int FFS)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t npix = (size_t)12 * NSIDE * NSIDE, old = view_pixels(c);
     if (!c->dODIR || c->view.NDIR < 1) {
-        HIPCHK(c, dev_alloc(&c->dODIR, (size_t)1));
-        HIPCHK(c, dev_alloc(&c->dORA, (size_t)1));
-        HIPCHK(c, dev_alloc(&c->dODE, (size_t)1));
+        HIPCHK(c, c->dODIR.reset(1, c->stream));
+        HIPCHK(c, c->dORA.reset(1, c->stream));
+        HIPCHK(c, c->dODE.reset(1, c->stream));
     }
     int r = view_image(c, "soc_sca_set_healpix", npix, old);
     if (r) return r;
@@ -1432,7 +1267,7 @@ int soc_sca_read_out(soc_ctx *c, float *out, int64_t n)
     return SOC_OK;
 }
 
-void *soc_sca_out_ptr(soc_ctx *c) { return (c && c->have_view) ? (void *)c->dOUT : nullptr; }
+void *soc_sca_out_ptr(soc_ctx *c) { return (c && c->have_view) ? (void *)c->dOUT.p : nullptr; }
 
 int soc_sca_batch_images(soc_ctx *c, int n)
 {
@@ -1443,10 +1278,7 @@ int soc_sca_batch_images(soc_ctx *c, int n)
     HIPCHK(c, hipSetDevice(c->device));
     const size_t pix = view_pixels(c);
     if (n > 0) {
-        if ((size_t)n * pix > (size_t)c->out_slots * c->out_slot_pixels || !c->dOUTslots) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, dev_alloc(&c->dOUTslots, (size_t)n * pix));
-        }
+        HIPCHK(c, c->dOUTslots.reserve((size_t)n * pix, c->stream));
         HIPCHK(c, hipMemsetAsync(c->dOUTslots, 0, (size_t)n * pix * 4, c->stream));
     }
     c->out_slots = n;  c->out_slot_pixels = pix;  c->out_slot_cur = 0;
@@ -1480,15 +1312,11 @@ int soc_sca_bind_out(soc_ctx *c, void *device_ptr)
     if (!c->have_view) return fail(c, SOC_ERR_STATE, "soc_sca_bind_out: call soc_sca_set_view first");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->own_OUT && c->dOUT) (void)hipFree(c->dOUT);
-    c->dOUT = nullptr;
+    const size_t npix = view_pixels(c);
     if (device_ptr) {
-        c->dOUT = (float *)device_ptr;
-        c->own_OUT = false;
+        c->dOUT.bind((float *)device_ptr, npix);
     } else {                                                // back to memory of the library
-        const size_t npix = view_pixels(c);
-        HIPCHK(c, dev_alloc(&c->dOUT, npix));
-        c->own_OUT = true;
+        HIPCHK(c, c->dOUT.reset(npix, c->stream));
         HIPCHK(c, hipMemsetAsync(c->dOUT, 0, npix * 4, c->stream));
     }
     return SOC_OK;
@@ -1541,17 +1369,12 @@ int soc_bind_tally(soc_ctx *c, int which, void *device_ptr, int64_t n)
         return fail(c, SOC_ERR_ARG, "soc_bind_tally: the buffer holds %lld floats, the grid has %d cells", (long long)n, c->G.CELLS);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    float **buf = (which == SOC_TALLY_TABS) ? &c->dTABS : &c->dINT;
-    bool  *own = (which == SOC_TALLY_TABS) ? &c->own_TABS : &c->own_INT;
-    if (*own && *buf) (void)hipFree(*buf);
-    *buf = nullptr;
+    DevBuf<float> &buf = (which == SOC_TALLY_TABS) ? c->dTABS : c->dINT;
     if (device_ptr) {
-        *buf = (float *)device_ptr;
-        *own = false;
+        buf.bind((float *)device_ptr, (size_t)n);
     } else {                                                // back to memory of the library
-        HIPCHK(c, dev_alloc(buf, (size_t)c->G.CELLS));
-        *own = true;
-        HIPCHK(c, hipMemsetAsync(*buf, 0, (size_t)c->G.CELLS * 4, c->stream));
+        HIPCHK(c, buf.reset((size_t)c->G.CELLS, c->stream));
+        HIPCHK(c, hipMemsetAsync(buf, 0, (size_t)c->G.CELLS * 4, c->stream));
     }
     return SOC_OK;
 }
@@ -1602,783 +1425,6 @@ int soc_timer_stop(soc_ctx *c, float *elapsed_ms)
     float ms = 0.0f;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     if (elapsed_ms) *elapsed_ms = ms;
-    return SOC_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// A2E: stochastically heated grains
-// ---------------------------------------------------------------------------------------
-
-// ------------------------------------------------------------------------------------
-// equilibrium temperature and emission (ASOC.py `CLT` / `CLE` paths)
-// ------------------------------------------------------------------------------------
-
-int soc_solve_temperature(soc_ctx *c, float adhoc, float kE, float Emin, int NE, const float *TTT, float FACTOR, float LENGTH,
-                          const float *EABS, float *TNEW)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_solve_temperature: call soc_set_grid first");
-    if (!TTT || !EABS || NE < 2 || !(kE > 1.0f) || !(Emin > 0.0f) || !(adhoc > 0.0f) || !(LENGTH > 0.0f))
-        return fail(c, SOC_ERR_ARG, "soc_solve_temperature: need TTT[NE>=2], EABS, kE>1, Emin>0, adhoc>0, LENGTH>0");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t cells = (size_t)c->G.CELLS;
-    if (!c->dT) HIPCHK(c, dev_alloc(&c->dT, cells));
-    if (NE > c->ttt_cap) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, dev_alloc(&c->dTTT, (size_t)NE)); c->ttt_cap = NE; }
-    if (c->ebuf_cap < cells) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, dev_alloc(&c->dEbuf, cells)); c->ebuf_cap = cells; }
-    HIPCHK(c, hipMemcpyAsync(c->dTTT, TTT, (size_t)NE * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dEbuf, EABS, cells * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, soc_launch_eqtemp(c->G, adhoc, kE, Emin, NE, FACTOR, LENGTH, c->cr_rate, c->dTTT, c->dEbuf, c->dT, c->stream));
-    if (TNEW) HIPCHK(c, hipMemcpyAsync(TNEW, c->dT, cells * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->have_T = true;
-    return SOC_OK;
-}
-
-int soc_set_cr_heating(soc_ctx *c, float rate)
-{
-    if (!c) return SOC_ERR_ARG;
-    if (!(rate >= 0.0f) || !std::isfinite(rate)) return fail(c, SOC_ERR_ARG, "soc_set_cr_heating: rate %g (>= 0; 0 switches it off)", (double)rate);
-    c->cr_rate = rate;
-    return SOC_OK;
-}
-
-int soc_set_map_roi(soc_ctx *c, const int32_t *ROI)
-{
-    if (!c) return SOC_ERR_ARG;
-    if (!ROI) { c->map_roi_on = 0;  return SOC_OK; }
-    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_set_map_roi: call soc_set_grid first");
-    const int N[3] = { c->G.NX, c->G.NY, c->G.NZ };
-    for (int k = 0; k < 3; k++)
-        if (ROI[2 * k] < 0 || ROI[2 * k + 1] < ROI[2 * k] || ROI[2 * k + 1] >= N[k])
-            return fail(c, SOC_ERR_ARG, "soc_set_map_roi: limits %d..%d on axis %d of a grid of %d root cells", ROI[2 * k], ROI[2 * k + 1], k, N[k]);
-    for (int k = 0; k < 6; k++) c->map_roi[k] = ROI[k];
-    c->map_roi_on = 1;
-    return SOC_OK;
-}
-
-int soc_set_map_threshold(soc_ctx *c, int level)
-{
-    if (!c) return SOC_ERR_ARG;
-    if (level < 0 || level > SOC_MAXL) return fail(c, SOC_ERR_ARG, "soc_set_map_threshold: level %d", level);
-    c->map_level_threshold = level;
-    return SOC_OK;
-}
-
-int soc_set_map_interpolation(soc_ctx *c, int mode)
-{
-    if (!c) return SOC_ERR_ARG;
-    if (mode < 0 || mode > 2) return fail(c, SOC_ERR_ARG, "soc_set_map_interpolation: mode %d (0, 1 or 2)", mode);
-    c->map_interpolation = mode;
-    return SOC_OK;
-}
-
-int soc_set_temperature(soc_ctx *c, const float *T)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (!c->have_grid || !T) return fail(c, SOC_ERR_STATE, "soc_set_temperature: needs a grid and T[CELLS]");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->dT) HIPCHK(c, dev_alloc(&c->dT, (size_t)c->G.CELLS));
-    HIPCHK(c, hipMemcpyAsync(c->dT, T, (size_t)c->G.CELLS * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->have_T = true;
-    return SOC_OK;
-}
-
-int soc_emission(soc_ctx *c, int nfreq, const float *FREQ, const float *FABS, float FACTOR, float LENGTH, float *EMITTED)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (!c->have_T) return fail(c, SOC_ERR_STATE, "soc_emission: call soc_solve_temperature or soc_set_temperature first");
-    if (nfreq < 1 || !FREQ || !FABS || !EMITTED || !(LENGTH > 0.0f)) return fail(c, SOC_ERR_ARG, "soc_emission: nfreq %d", nfreq);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (2 * nfreq > c->ef_cap) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, dev_alloc(&c->dEF, (size_t)2 * nfreq)); c->ef_cap = 2 * nfreq; }
-    HIPCHK(c, hipMemcpyAsync(c->dEF, FREQ, (size_t)nfreq * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dEF + nfreq, FABS, (size_t)nfreq * 4, hipMemcpyHostToDevice, c->stream));
-    // batches of cells, all frequencies (the layout of the emitted file: EMITTED[CELLS][nfreq])
-    const int cells = c->G.CELLS;
-    int batch = (int)(((size_t)64 << 20) / (size_t)nfreq);            // <= 256 MB of floats per batch
-    if (batch < 1) batch = 1;
-    if (batch > cells) batch = cells;
-    const size_t need = (size_t)batch * nfreq;
-    if (c->ebuf_cap < need) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, dev_alloc(&c->dEbuf, need)); c->ebuf_cap = need; }
-    for (int a = 0; a < cells; a += batch) {
-        const int b = (a + batch < cells) ? a + batch : cells;
-        HIPCHK(c, soc_launch_emission(a, b, nfreq, FACTOR, LENGTH, c->dEF, c->dEF + nfreq, c->dT, c->dEbuf, c->stream));
-        HIPCHK(c, hipMemcpyAsync(EMITTED + (size_t)a * nfreq, c->dEbuf, (size_t)(b - a) * nfreq * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return SOC_OK;
-}
-
-// ------------------------------------------------------------------------------------
-// map making (ASOC.py:2924-3177 -> kernel_ASOC_map.c Mapping / HealpixMapping)
-// ------------------------------------------------------------------------------------
-
-int soc_map(soc_ctx *c, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const float *EMIT, const float *DIR, const float *RA,
-            const float *DE, const float *CENTRE, const float *INTOBS, float ABS, float SCA, int save_colden, float LENGTH,
-            float *MAP, float *SAVETAU)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_map: call soc_set_grid first");
-    if (!EMIT || !MAP || !SAVETAU) return fail(c, SOC_ERR_ARG, "soc_map: EMIT, MAP and SAVETAU are needed");
-    const bool inside = INTOBS && INTOBS[0] > -1e10f;
-    if (healpix) {
-        if (NPIX_X < 1 || NPIX_X > 8192 || !inside) return fail(c, SOC_ERR_ARG, "soc_map: Healpix maps need NSIDE (NPIX_X) and an observer position");
-    } else {
-        if (NPIX_X < 1 || NPIX_Y < 1 || (int64_t)NPIX_X * NPIX_Y > 2147483647LL) return fail(c, SOC_ERR_ARG, "soc_map: NPIX %d x %d", NPIX_X, NPIX_Y);
-        if (!inside && (!DIR || !RA || !DE || !CENTRE || !(MAP_DX > 0.0f))) return fail(c, SOC_ERR_ARG, "soc_map: DIR, RA, DE, CENTRE and MAP_DX > 0 are needed");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npix = healpix ? (size_t)12 * NPIX_X * NPIX_X : (size_t)NPIX_X * NPIX_Y;
-    const size_t cells = (size_t)c->G.CELLS;
-    if (c->mapemit_cap < cells) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_alloc(&c->dMapEmit, cells));
-        c->mapemit_cap = cells;
-    }
-    if (c->map_cap < npix) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_alloc(&c->dMap, npix));
-        HIPCHK(c, dev_alloc(&c->dMapTau, npix));
-        c->map_cap = npix;
-    }
-    SocMapArgs A;
-    memset(&A, 0, sizeof A);
-    A.mode = healpix ? 1 : 0;
-    A.NPIX_X = NPIX_X;  A.NPIX_Y = healpix ? 1 : NPIX_Y;  A.SAVE_COLDEN = save_colden;
-    A.LEVEL_THRESHOLD = c->map_level_threshold;
-    A.MAPINT = healpix ? 0 : c->map_interpolation;
-    A.ROI_MAP = c->map_roi_on;
-    for (int k = 0; k < 6; k++) A.ROI[k] = c->map_roi[k];
-    A.MAP_DX = MAP_DX;  A.ABS = ABS;  A.SCA = SCA;  A.LENGTH = LENGTH;
-    for (int k = 0; k < 3; k++) {
-        A.DIR[k] = DIR ? DIR[k] : 0.0f;  A.RA[k] = RA ? RA[k] : 0.0f;  A.DE[k] = DE ? DE[k] : 0.0f;
-        A.CENTRE[k] = CENTRE ? CENTRE[k] : 0.0f;
-        A.INTOBS[k] = inside ? INTOBS[k] : (k == 0 ? -1.0e12f : 0.0f);
-    }
-    A.EMIT = c->dMapEmit;  A.OPT = c->dOPT;  A.MAP = c->dMap;  A.SAVETAU = c->dMapTau;
-    HIPCHK(c, hipMemcpyAsync(c->dMapEmit, EMIT, cells * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, soc_launch_map(c->G, A, c->dOPT != nullptr, c->stream));
-    HIPCHK(c, hipMemcpyAsync(MAP, c->dMap, npix * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(SAVETAU, c->dMapTau, npix * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SOC_OK;
-}
-
-// polarisation maps (ASOC.py:3651-3801 -> PolMapping, kernel_ASOC_map.c:972-1137, :1147-1384, :1594-1693)
-int soc_set_bfield(soc_ctx *c, const float *Bx, const float *By, const float *Bz)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!Bx && !By && !Bz) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->dBfield) { (void)hipFree(c->dBfield); c->dBfield = nullptr; }
-        return SOC_OK;
-    }
-    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_set_bfield: call soc_set_grid first");
-    if (!Bx || !By || !Bz) return fail(c, SOC_ERR_ARG, "soc_set_bfield: Bx, By and Bz are needed (all NULL frees the field)");
-    const size_t cells = (size_t)c->G.CELLS;
-    float *tmp = nullptr;
-    if (hipMalloc((void **)&tmp, 3 * cells * 4) != hipSuccess) return fail(c, SOC_ERR_HIP, "soc_set_bfield: allocation");
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && !c->dBfield) e = hipMalloc((void **)&c->dBfield, cells * sizeof(float4));
-    if (e == hipSuccess) e = hipMemcpyAsync(tmp, Bx, cells * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(tmp + cells, By, cells * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(tmp + 2 * cells, Bz, cells * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = soc_launch_pack_bfield((int)cells, tmp, tmp + cells, tmp + 2 * cells, c->dBfield, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) {
-        if (c->dBfield) { (void)hipFree(c->dBfield); c->dBfield = nullptr; }
-        return fail(c, SOC_ERR_HIP, "soc_set_bfield: %s", hipGetErrorString(e));
-    }
-    return SOC_OK;
-}
-
-int soc_polmap(soc_ctx *c, int polstat, int polred, int rho_weight, float p0, int NPIX_X, int NPIX_Y, float MAP_DX, const float *EMIT,
-               const float *DIR, const float *RA, const float *DE, const float *CENTRE, float ABS, float SCA, float LENGTH, float *MAP)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_polmap: call soc_set_grid first");
-    if (polstat != 0 && polstat != 1 && polstat != 3) return fail(c, SOC_ERR_ARG, "soc_polmap: polstat %d (0, 1 or 3)", polstat);
-    if (polstat == 3 && polred) return fail(c, SOC_ERR_ARG, "soc_polmap: polstat 3 uses the full field vector, polred cannot be encoded in it");
-    if (!c->dBfield) return fail(c, SOC_ERR_STATE, "soc_polmap: call soc_set_bfield first");
-    if (!EMIT || !MAP || !DIR || !RA || !DE || !CENTRE || !(MAP_DX > 0.0f)) return fail(c, SOC_ERR_ARG, "soc_polmap: EMIT, MAP, DIR, RA, DE, CENTRE and MAP_DX > 0 are needed");
-    if (NPIX_X < 1 || NPIX_Y < 1 || (int64_t)NPIX_X * NPIX_Y > 2147483647LL / 4) return fail(c, SOC_ERR_ARG, "soc_polmap: NPIX %d x %d", NPIX_X, NPIX_Y);
-    // the walk divides by the components of -DIR without clamping them (kernel_ASOC_map.c:1033): a zero would send the position to NaN
-    for (int k = 0; k < 3; k++) if (!std::isfinite(DIR[k]) || DIR[k] == 0.0f) return fail(c, SOC_ERR_ARG, "soc_polmap: DIR[%d] = %g", k, (double)DIR[k]);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npix = (size_t)NPIX_X * NPIX_Y, cells = (size_t)c->G.CELLS;
-    if (c->mapemit_cap < cells) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_alloc(&c->dMapEmit, cells));
-        c->mapemit_cap = cells;
-    }
-    if (c->polmap_cap < 4 * npix) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_alloc(&c->dPolMap, 4 * npix));
-        c->polmap_cap = 4 * npix;
-    }
-    SocPolArgs A;
-    memset(&A, 0, sizeof A);
-    A.polstat = polstat;  A.polred = polred ? 1 : 0;  A.rho_weight = rho_weight ? 1 : 0;
-    A.LEVEL_THRESHOLD = c->map_level_threshold;
-    A.NPIX_X = NPIX_X;  A.NPIX_Y = NPIX_Y;
-    A.p0 = p0;  A.MAP_DX = MAP_DX;  A.ABS = ABS;  A.SCA = SCA;  A.LENGTH = LENGTH;
-    for (int k = 0; k < 3; k++) { A.DIR[k] = DIR[k];  A.RA[k] = RA[k];  A.DE[k] = DE[k];  A.CENTRE[k] = CENTRE[k]; }
-    A.EMIT = c->dMapEmit;  A.OPT = c->dOPT;  A.B = c->dBfield;  A.MAP = c->dPolMap;
-    HIPCHK(c, hipMemcpyAsync(c->dMapEmit, EMIT, cells * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, soc_launch_polmap(c->G, A, c->dOPT != nullptr, c->stream));
-    HIPCHK(c, hipMemcpyAsync(MAP, c->dPolMap, 4 * npix * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SOC_OK;
-}
-
-int soc_ps_tau(soc_ctx *c, int NO_PS, const float *PSPOS, const float *DIR, float ABS, float SCA, float LENGTH, float *pscolden, float *pstau)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_ps_tau: call soc_set_grid first");
-    if (NO_PS < 1 || NO_PS > 1000000 || !PSPOS || !DIR || !pscolden || !pstau) return fail(c, SOC_ERR_ARG, "soc_ps_tau: need NO_PS >= 1 sources, DIR and the two output arrays");
-    for (int k = 0; k < 3; k++) if (!std::isfinite(DIR[k]) || DIR[k] == 0.0f) return fail(c, SOC_ERR_ARG, "soc_ps_tau: DIR[%d] = %g", k, (double)DIR[k]);
-    HIPCHK(c, hipSetDevice(c->device));
-    float *d = nullptr;                                     // PSPOS (4 floats per source) | colden | tau
-    const size_t n = (size_t)NO_PS;
-    if (hipMalloc((void **)&d, n * 6 * 4) != hipSuccess) return fail(c, SOC_ERR_HIP, "soc_ps_tau: allocation");
-    hipError_t e = hipMemcpyAsync(d, PSPOS, n * 16, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = soc_launch_pstau(c->G, NO_PS, (const float4 *)d, DIR, ABS, SCA, c->dOPT, LENGTH, d + 4 * n, d + 5 * n, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(pscolden, d + 4 * n, n * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(pstau, d + 5 * n, n * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "soc_ps_tau: %s", hipGetErrorString(e));
-    return SOC_OK;
-}
-
-int soc_a2e_set_size(soc_ctx *c, int NE, int NFREQ, int noIw, const float *Iw, const int32_t *L1,
-                     const int32_t *L2, const float *Tdown, const float *EA, const int32_t *Ibeg, const float *AF)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (NE < 3 || NE > 280 || NFREQ < 2 || noIw < 0 || !Iw || !L1 || !L2 || !Tdown || !EA || !Ibeg || !AF)
-        return fail(c, SOC_ERR_ARG, "soc_a2e_set_size: bad arguments (3 <= NE <= 280, NFREQ >= 2)");
-    // pair tables in the reference's (l, u) loop order; validate every window on the host
-    const int npair = (NE * NE - NE) / 2;
-    std::vector<int> first(npair), last(npair), off(npair), dst(npair);
-    long long iw = 0;
-    int e = 0;
-    for (int l = 0; l < NE - 1; l++) {
-        for (int u = l + 1; u < NE; u++, e++) {
-            const int i0 = L1[l * NE + u], i1 = L2[l * NE + u];
-            if (i1 >= i0 && (i0 < 0 || i1 >= NFREQ))
-                return fail(c, SOC_ERR_ARG, "soc_a2e_set_size: window [%d,%d] of pair (l=%d,u=%d) outside 0..%d", i0, i1, l, u, NFREQ - 1);
-            first[e] = i0;  last[e] = i1;  off[e] = (int)iw;  dst[e] = (u * u - u) / 2 + l;
-            if (i1 >= i0) iw += i1 - i0 + 1;
-        }
-    }
-    if (iw != noIw) return fail(c, SOC_ERR_ARG, "soc_a2e_set_size: windows need %lld weights, noIw = %d", iw, noIw);
-    for (int f = 0; f < NFREQ; f++)
-        if (Ibeg[f] < 0 || Ibeg[f] > NE) return fail(c, SOC_ERR_ARG, "soc_a2e_set_size: Ibeg[%d] = %d", f, Ibeg[f]);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, dev_alloc(&c->aIw, (size_t)noIw));
-    HIPCHK(c, dev_alloc(&c->aFirst, (size_t)npair));
-    HIPCHK(c, dev_alloc(&c->aLast, (size_t)npair));
-    HIPCHK(c, dev_alloc(&c->aIwOff, (size_t)npair));
-    HIPCHK(c, dev_alloc(&c->aDst, (size_t)npair));
-    HIPCHK(c, dev_alloc(&c->aTdown, (size_t)NE));
-    HIPCHK(c, dev_alloc(&c->aEA, (size_t)NE * NFREQ));
-    HIPCHK(c, dev_alloc(&c->aIbeg, (size_t)NFREQ));
-    HIPCHK(c, dev_alloc(&c->aAF, (size_t)NFREQ));
-    if (noIw) HIPCHK(c, hipMemcpy(c->aIw, Iw, (size_t)noIw * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->aFirst, first.data(), (size_t)npair * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->aLast, last.data(), (size_t)npair * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->aIwOff, off.data(), (size_t)npair * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->aDst, dst.data(), (size_t)npair * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->aTdown, Tdown, (size_t)NE * 4, hipMemcpyHostToDevice));
-    {   // transposed on the way: EAT[i * NFREQ + f] = EA[f * NE + i], so that the lanes of the emission loop (one
-        // frequency each) read neighbouring words (the sum over the enthalpy bins keeps its order)
-        std::vector<float> eat((size_t)NE * NFREQ);
-        for (int f = 0; f < NFREQ; f++)
-            for (int i = 0; i < NE; i++) eat[(size_t)i * NFREQ + f] = EA[(size_t)f * NE + i];
-        HIPCHK(c, hipMemcpy(c->aEA, eat.data(), (size_t)NE * NFREQ * 4, hipMemcpyHostToDevice));
-    }
-    HIPCHK(c, hipMemcpy(c->aIbeg, Ibeg, (size_t)NFREQ * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->aAF, AF, (size_t)NFREQ * 4, hipMemcpyHostToDevice));
-    if (NFREQ != c->a2e_NFREQ) c->a2e_cap = 0;
-    c->a2e_NE = NE;  c->a2e_NFREQ = NFREQ;  c->a2e_npair = npair;  c->a2e_noIw = noIw;
-    return SOC_OK;
-}
-
-static int a2e_reserve(soc_ctx *c, int batch)
-{
-    if (c->a2e_NE == 0) return fail(c, SOC_ERR_STATE, "A2E: call soc_a2e_set_size first");
-    if (batch < 1) return fail(c, SOC_ERR_ARG, "A2E: batch = %d", batch);
-    if (batch > c->a2e_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_alloc(&c->aABS, (size_t)batch * c->a2e_NFREQ));
-        HIPCHK(c, dev_alloc(&c->aEMIT, (size_t)batch * c->a2e_NFREQ));
-        c->a2e_cap = batch;
-    }
-    return SOC_OK;
-}
-
-int soc_a2e_upload(soc_ctx *c, int batch, const float *AABS)
-{
-    if (!c || !AABS) return SOC_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    int r = a2e_reserve(c, batch);
-    if (r) return r;
-    HIPCHK(c, hipMemcpyAsync(c->aABS, AABS, (size_t)batch * c->a2e_NFREQ * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SOC_OK;
-}
-
-int soc_a2e_run(soc_ctx *c, int batch)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->a2e_NE == 0 || batch < 1 || batch > c->a2e_cap) return fail(c, SOC_ERR_STATE, "soc_a2e_run: upload a batch first");
-    SocA2EArgs A{};
-    A.NE = c->a2e_NE;  A.NFREQ = c->a2e_NFREQ;  A.npair = c->a2e_npair;  A.batch = batch;
-    A.Iw = c->aIw;  A.pair_first = c->aFirst;  A.pair_last = c->aLast;  A.pair_iw = c->aIwOff;  A.pair_dst = c->aDst;
-    A.Tdown = c->aTdown;  A.EA = c->aEA;  A.Ibeg = c->aIbeg;  A.AF = c->aAF;  A.AABS = c->aABS;  A.AEMIT = c->aEMIT;
-    HIPCHK(c, soc_launch_a2e_dosolve(A, c->stream));
-    return SOC_OK;
-}
-
-int soc_a2e_download(soc_ctx *c, int batch, float *AEMIT)
-{
-    if (!c || !AEMIT) return SOC_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (batch < 1 || batch > c->a2e_cap) return fail(c, SOC_ERR_ARG, "soc_a2e_download: batch = %d", batch);
-    HIPCHK(c, hipMemcpyAsync(AEMIT, c->aEMIT, (size_t)batch * c->a2e_NFREQ * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SOC_OK;
-}
-
-// ---- config 5 with the cells resident in HBM ----
-int soc_a2e_resident_begin(soc_ctx *c, int64_t cells, int NFREQ)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (cells < 1 || NFREQ < 2 || cells > (int64_t)2147483647) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_begin: cells=%lld NFREQ=%d", (long long)cells, NFREQ);
-    if (c->mABS) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_begin: the resident arrays are those of soc_mabu_begin (soc_mabu_end first)");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    const size_t need = (size_t)cells * NFREQ * 8;
-    if (need + ((size_t)1 << 30) > free_b + (c->aAll ? (size_t)c->a2e_cells * c->a2e_res_nfreq * 8 : 0))
-        return fail(c, SOC_ERR_STATE, "soc_a2e_resident_begin: %lld cells x %d frequencies need %.1f GB of device memory, %.1f GB are free (use soc_a2e_solve in batches)",
-                    (long long)cells, NFREQ, need * 1e-9, free_b * 1e-9);
-    HIPCHK(c, dev_alloc(&c->aAll, (size_t)cells * NFREQ));
-    HIPCHK(c, dev_alloc(&c->aSum, (size_t)cells * NFREQ));
-    HIPCHK(c, hipMemsetAsync(c->aSum, 0, (size_t)cells * NFREQ * 4, c->stream));
-    c->a2e_cells = cells;  c->a2e_res_nfreq = NFREQ;
-    return SOC_OK;
-}
-
-int soc_a2e_resident_upload(soc_ctx *c, int64_t c0, int64_t n, const float *AABS)
-{
-    if (!c || !AABS) return SOC_ERR_ARG;
-    if (!c->aAll || c0 < 0 || n < 1 || c0 + n > c->a2e_cells) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_upload: cells [%lld, %lld) of %lld", (long long)c0, (long long)(c0 + n), (long long)c->a2e_cells);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->aAll + (size_t)c0 * c->a2e_res_nfreq, AABS, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host buffer may be a temporary)
-    return SOC_OK;
-}
-
-int soc_a2e_resident_solve(soc_ctx *c)
-{
-    if (!c) return SOC_ERR_ARG;
-    if (!c->aAll) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve: call soc_a2e_resident_begin first");
-    if (c->a2e_NE == 0 || c->a2e_NFREQ != c->a2e_res_nfreq) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve: soc_a2e_set_size with NFREQ = %d first", c->a2e_res_nfreq);
-    HIPCHK(c, hipSetDevice(c->device));
-    SocA2EArgs A{};
-    A.NE = c->a2e_NE;  A.NFREQ = c->a2e_NFREQ;  A.npair = c->a2e_npair;
-    A.Iw = c->aIw;  A.pair_first = c->aFirst;  A.pair_last = c->aLast;  A.pair_iw = c->aIwOff;  A.pair_dst = c->aDst;
-    A.Tdown = c->aTdown;  A.EA = c->aEA;  A.Ibeg = c->aIbeg;  A.AF = c->aAF;
-    A.accumulate = 1;
-    const int64_t step = 1 << 20;                           // cells per launch (the grid is one workgroup per four cells)
-    for (int64_t c0 = 0; c0 < c->a2e_cells; c0 += step) {
-        A.batch = (int)std::min<int64_t>(step, c->a2e_cells - c0);
-        A.AABS = c->aAll + (size_t)c0 * A.NFREQ;  A.AEMIT = c->aSum + (size_t)c0 * A.NFREQ;
-        HIPCHK(c, soc_launch_a2e_dosolve(A, c->stream));
-    }
-    return SOC_OK;
-}
-
-int soc_a2e_resident_download(soc_ctx *c, int64_t c0, int64_t n, float *AEMIT)
-{
-    if (!c || !AEMIT) return SOC_ERR_ARG;
-    if (!c->aSum || c0 < 0 || n < 1 || c0 + n > c->a2e_cells) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_download: cells [%lld, %lld) of %lld", (long long)c0, (long long)(c0 + n), (long long)c->a2e_cells);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(AEMIT, c->aSum + (size_t)c0 * c->a2e_res_nfreq, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SOC_OK;
-}
-
-int soc_a2e_resident_end(soc_ctx *c)
-{
-    if (!c) return SOC_ERR_ARG;
-    if (c->mABS) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_end: the resident arrays are those of soc_mabu_begin (soc_mabu_end frees them)");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->aAll) { (void)hipFree(c->aAll);  c->aAll = nullptr; }
-    if (c->aSum) { (void)hipFree(c->aSum);  c->aSum = nullptr; }
-    c->a2e_cells = 0;
-    return SOC_OK;
-}
-
-int soc_a2e_solve(soc_ctx *c, int batch, const float *AABS, float *AEMIT)
-{
-    int r = soc_a2e_upload(c, batch, AABS);
-    if (r) return r;
-    r = soc_a2e_run(c, batch);
-    if (r) return r;
-    return soc_a2e_download(c, batch, AEMIT);
-}
-
-static int eqtemp_common(soc_ctx *c, const char *who, bool eqsolver, int batch, int icell, int CELLS, int NFREQ, int NIP, float FACTOR, float kE,
-                   float oplgkE, float Emin, const float *FREQ, const float *KABS, const float *TTT,
-                   const float *ABS, float *T, float *EMIT)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (batch < 1 || NFREQ < 2 || NIP < 2 || !FREQ || !KABS || !TTT || !ABS || !T || !EMIT)
-        return fail(c, SOC_ERR_ARG, "%s: bad arguments", who);
-    HIPCHK(c, hipSetDevice(c->device));
-    float *d = nullptr;
-    const size_t n = (size_t)2 * NFREQ + NIP + (size_t)2 * batch * NFREQ + batch;
-    HIPCHK(c, hipMalloc((void **)&d, n * 4));
-    float *dF = d, *dK = dF + NFREQ, *dT3 = dK + NFREQ, *dA = dT3 + NIP, *dE = dA + (size_t)batch * NFREQ, *dT = dE + (size_t)batch * NFREQ;
-    hipError_t e = hipMemcpy(dF, FREQ, (size_t)NFREQ * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dK, KABS, (size_t)NFREQ * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dT3, TTT, (size_t)NIP * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dA, ABS, (size_t)batch * NFREQ * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemsetAsync(dE, 0, ((size_t)batch * NFREQ + batch) * 4, c->stream);
-    SocEqTArgs A{};
-    A.batch = batch;  A.icell = icell;  A.CELLS = CELLS;  A.NFREQ = NFREQ;  A.NIP = NIP;
-    A.FACTOR = FACTOR;  A.kE = kE;  A.oplgkE = oplgkE;  A.Emin = Emin;
-    A.FREQ = dF;  A.KABS = dK;  A.TTT = dT3;  A.ABS = dA;  A.T = dT;  A.EMIT = dE;
-    if (e == hipSuccess) e = eqsolver ? soc_launch_eqsolver(A, c->stream) : soc_launch_a2e_eqtemp(A, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(T, dT, (size_t)batch * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(EMIT, dE, (size_t)batch * NFREQ * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return SOC_OK;
-}
-
-int soc_a2e_eqtemp(soc_ctx *c, int batch, int icell, int CELLS, int NFREQ, int NIP, float FACTOR, float kE,
-                   float oplgkE, float Emin, const float *FREQ, const float *KABS, const float *TTT,
-                   const float *ABS, float *T, float *EMIT)
-{
-    return eqtemp_common(c, "soc_a2e_eqtemp", false, batch, icell, CELLS, NFREQ, NIP, FACTOR, kE, oplgkE, Emin, FREQ, KABS, TTT, ABS, T, EMIT);
-}
-
-int soc_eqsolver(soc_ctx *c, int batch, int icell, int CELLS, int NFREQ, int NE, float FACTOR, float kE,
-                 float oplgkE, float Emin, const float *FREQ, const float *KABS, const float *TTT,
-                 const float *ABS, float *T, float *EMIT)
-{
-    return eqtemp_common(c, "soc_eqsolver", true, batch, icell, CELLS, NFREQ, NE, FACTOR, kE, oplgkE, Emin, FREQ, KABS, TTT, ABS, T, EMIT);
-}
-
-// ---- the multi-dust stage with the cells resident in HBM (A2E_MABU.py:700-1140) ----
-static void mabu_release(soc_ctx *c)
-{
-    void **bufs[] = { (void **)&c->mABS, (void **)&c->mSUM, (void **)&c->mABU, (void **)&c->mT, (void **)&c->mTab, (void **)&c->mRABS,
-                      (void **)&c->aAll, (void **)&c->aSum };
-    for (void **b : bufs) if (*b) { (void)hipFree(*b);  *b = nullptr; }
-    c->a2e_cells = 0;  c->mabu_ndust = 0;  c->mtab_cap = 0;  c->mabu_tables = false;
-}
-
-int soc_mabu_begin(soc_ctx *c, int64_t cells, int NFREQ, int NDUST, int64_t *cells_fit)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (cells_fit) *cells_fit = 0;
-    if (cells < 1 || NFREQ < 2 || NDUST < 1 || cells > (int64_t)2147483647 || (size_t)NFREQ * NDUST * sizeof(double) > SOC_MABU_LDS)
-        return fail(c, SOC_ERR_ARG, "soc_mabu_begin: cells=%lld NFREQ=%d NDUST=%d (NFREQ x NDUST doubles must fit %d KB of LDS)",
-                    (long long)cells, NFREQ, NDUST, SOC_MABU_LDS / 1024);
-    if (c->aAll && !c->mABS) return fail(c, SOC_ERR_STATE, "soc_mabu_begin: the resident arrays are those of an open soc_a2e_resident_begin (soc_a2e_resident_end first)");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    mabu_release(c);                                        // (a soc_mabu_begin that is still open is replaced)
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    // per cell: absorptions, the dust's share, its emission, the sum (NFREQ floats each), NDUST abundances, a temperature
-    const size_t per_cell = (size_t)NFREQ * 16 + (size_t)NDUST * 4 + 4, reserve = (size_t)1 << 30;
-    const size_t need = (size_t)cells * per_cell;
-    if (cells_fit) *cells_fit = free_b > reserve ? (int64_t)((free_b - reserve) / per_cell) : 0;
-    if (need + reserve > free_b)
-        return fail(c, SOC_ERR_STATE, "soc_mabu_begin: %lld cells x %d frequencies x %d dusts need %.1f GB of device memory, %.1f GB are free (%lld cells fit: solve the cells in ranges)",
-                    (long long)cells, NFREQ, NDUST, need * 1e-9, free_b * 1e-9, (long long)(free_b > reserve ? (free_b - reserve) / per_cell : 0));
-    const size_t n = (size_t)cells * NFREQ;
-    hipError_t e = dev_alloc(&c->mABS, n);
-    if (e == hipSuccess) e = dev_alloc(&c->aAll, n);
-    if (e == hipSuccess) e = dev_alloc(&c->aSum, n);
-    if (e == hipSuccess) e = dev_alloc(&c->mSUM, n);
-    if (e == hipSuccess) e = dev_alloc(&c->mABU, (size_t)cells * NDUST);
-    if (e == hipSuccess) e = dev_alloc(&c->mT, (size_t)cells);
-    if (e == hipSuccess) e = dev_alloc(&c->mRABS, (size_t)NFREQ * NDUST);
-    if (e == hipSuccess) e = hipMemsetAsync(c->mSUM, 0, n * 4, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->aSum, 0, n * 4, c->stream);
-    if (e != hipSuccess) {
-        mabu_release(c);
-        return fail(c, SOC_ERR_HIP, "soc_mabu_begin: %s", hipGetErrorString(e));
-    }
-    c->a2e_cells = cells;  c->a2e_res_nfreq = NFREQ;  c->mabu_ndust = NDUST;
-    return SOC_OK;
-}
-
-#define MABU_OPEN(c, who)                                                                                   \
-    do {                                                                                                    \
-        if (!(c)->mABS || !(c)->aAll || !(c)->aSum) return fail((c), SOC_ERR_STATE, who ": call soc_mabu_begin first");   \
-    } while (0)
-#define MABU_ROWS(c, who, c0, n)                                                                            \
-    do {                                                                                                    \
-        if ((c0) < 0 || (n) < 1 || (c0) + (n) > (c)->a2e_cells)                                             \
-            return fail((c), SOC_ERR_ARG, who ": cells [%lld, %lld) of %lld", (long long)(c0), (long long)((c0) + (n)), (long long)(c)->a2e_cells);   \
-    } while (0)
-
-int soc_mabu_upload(soc_ctx *c, int64_t c0, int64_t n, const float *ABS)
-{
-    if (!c || !ABS) return SOC_ERR_ARG;
-    MABU_OPEN(c, "soc_mabu_upload");
-    MABU_ROWS(c, "soc_mabu_upload", c0, n);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->mABS + (size_t)c0 * c->a2e_res_nfreq, ABS, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host buffer may be a temporary)
-    return SOC_OK;
-}
-
-int soc_mabu_set_tables(soc_ctx *c, const float *ABU, const double *RABS)
-{
-    if (!c || !ABU || !RABS) return SOC_ERR_ARG;
-    MABU_OPEN(c, "soc_mabu_set_tables");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->mABU, ABU, (size_t)c->a2e_cells * c->mabu_ndust * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->mRABS, RABS, (size_t)c->a2e_res_nfreq * c->mabu_ndust * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->mabu_tables = true;
-    return SOC_OK;
-}
-
-int soc_mabu_split(soc_ctx *c, int idust, int clip_last)
-{
-    if (!c) return SOC_ERR_ARG;
-    MABU_OPEN(c, "soc_mabu_split");
-    if (!c->mabu_tables) return fail(c, SOC_ERR_STATE, "soc_mabu_split: call soc_mabu_set_tables first");
-    if (idust < 0 || idust >= c->mabu_ndust) return fail(c, SOC_ERR_ARG, "soc_mabu_split: dust %d of %d", idust, c->mabu_ndust);
-    HIPCHK(c, hipSetDevice(c->device));
-    const int NFREQ = c->a2e_res_nfreq;
-    HIPCHK(c, soc_launch_mabu_split(c->a2e_cells, NFREQ, c->mabu_ndust, idust, c->mABS, c->mABU, c->mRABS, c->aAll, c->stream));
-    if (clip_last) HIPCHK(c, soc_launch_mabu_clip(c->a2e_cells, NFREQ, c->aAll, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->aSum, 0, (size_t)c->a2e_cells * NFREQ * 4, c->stream));
-    return SOC_OK;
-}
-
-int soc_mabu_solve_eq(soc_ctx *c, int NE, float FACTOR, float kE, float oplgkE, float Emin, const float *FREQ, const float *KABS, const float *TTT)
-{
-    if (!c) return SOC_ERR_ARG;
-    MABU_OPEN(c, "soc_mabu_solve_eq");
-    if (NE < 2 || !FREQ || !KABS || !TTT) return fail(c, SOC_ERR_ARG, "soc_mabu_solve_eq: bad arguments");
-    HIPCHK(c, hipSetDevice(c->device));
-    const int NFREQ = c->a2e_res_nfreq;
-    if (2 * NFREQ + NE > c->mtab_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_alloc(&c->mTab, (size_t)2 * NFREQ + NE));
-        c->mtab_cap = 2 * NFREQ + NE;
-    }
-    float *dF = c->mTab, *dK = dF + NFREQ, *dT3 = dK + NFREQ;
-    HIPCHK(c, hipMemcpyAsync(dF, FREQ, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dK, KABS, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dT3, TTT, (size_t)NE * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host tables may be temporaries)
-    SocEqTArgs A{};
-    A.batch = (int)c->a2e_cells;  A.icell = 0;  A.CELLS = (int)c->a2e_cells;  A.NFREQ = NFREQ;  A.NIP = NE;
-    A.FACTOR = FACTOR;  A.kE = kE;  A.oplgkE = oplgkE;  A.Emin = Emin;
-    A.FREQ = dF;  A.KABS = dK;  A.TTT = dT3;  A.ABS = c->aAll;  A.T = c->mT;  A.EMIT = c->aSum;
-    HIPCHK(c, soc_launch_eqsolver(A, c->stream));
-    return SOC_OK;
-}
-
-int soc_mabu_accumulate(soc_ctx *c, int idust)
-{
-    if (!c) return SOC_ERR_ARG;
-    MABU_OPEN(c, "soc_mabu_accumulate");
-    if (!c->mabu_tables) return fail(c, SOC_ERR_STATE, "soc_mabu_accumulate: call soc_mabu_set_tables first");
-    if (idust < 0 || idust >= c->mabu_ndust) return fail(c, SOC_ERR_ARG, "soc_mabu_accumulate: dust %d of %d", idust, c->mabu_ndust);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, soc_launch_mabu_sum(c->a2e_cells, c->a2e_res_nfreq, c->mabu_ndust, idust, c->aSum, c->mABU, c->mSUM, c->stream));
-    return SOC_OK;
-}
-
-static int mabu_read(soc_ctx *c, const float *src, int64_t c0, int64_t n, float *out)
-{
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, src + (size_t)c0 * c->a2e_res_nfreq, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SOC_OK;
-}
-
-int soc_mabu_download(soc_ctx *c, int64_t c0, int64_t n, float *SUM)
-{
-    if (!c || !SUM) return SOC_ERR_ARG;
-    MABU_OPEN(c, "soc_mabu_download");
-    MABU_ROWS(c, "soc_mabu_download", c0, n);
-    return mabu_read(c, c->mSUM, c0, n, SUM);
-}
-
-int soc_mabu_read_part(soc_ctx *c, int64_t c0, int64_t n, float *PART)
-{
-    if (!c || !PART) return SOC_ERR_ARG;
-    MABU_OPEN(c, "soc_mabu_read_part");
-    MABU_ROWS(c, "soc_mabu_read_part", c0, n);
-    return mabu_read(c, c->aAll, c0, n, PART);
-}
-
-int soc_mabu_end(soc_ctx *c)
-{
-    if (!c) return SOC_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->mABS) mabu_release(c);
-    return SOC_OK;
-}
-
-int soc_a2e_pre(soc_ctx *c, int NFREQ, int NE, float FACTOR, const float *FREQ, const float *Ef, const float *SKABS, const float *E,
-                const float *T, int32_t *L1, int32_t *L2, float *Iw, int32_t *noIw, float *Tdown)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (NFREQ < 2 || NE < 2 || NE > 4096 || !FREQ || !Ef || !SKABS || !E || !T || !L1 || !L2 || !Iw || !noIw || !Tdown)
-        return fail(c, SOC_ERR_ARG, "soc_a2e_pre: NFREQ %d, NE %d or a NULL array", NFREQ, NE);
-    for (int i = 1; i < NFREQ; i++)
-        if (!(FREQ[i] > FREQ[i - 1]) || !(Ef[i] > Ef[i - 1])) return fail(c, SOC_ERR_ARG, "soc_a2e_pre: FREQ, Ef must increase (entry %d)", i);
-    for (int i = 1; i <= NE; i++)
-        if (!(E[i] > E[i - 1])) return fail(c, SOC_ERR_ARG, "soc_a2e_pre: the enthalpy grid E[NE+1] must increase (entry %d)", i);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nIw = (size_t)NE * NE * NFREQ, nW = (size_t)NE * NFREQ;
-    float *d = nullptr, *dIw = nullptr;
-    int   *dL = nullptr;
-    // one block of floats: FREQ | Ef | SKABS (NFREQ each) | E | T (NE+1 each) | Tdown (NE) | wrk (NE*NFREQ)
-    const size_t nf = 3 * (size_t)NFREQ + 2 * (size_t)(NE + 1) + NE + nW;
-    hipError_t e = hipMalloc((void **)&d, nf * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&dIw, nIw * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&dL, (2 * (size_t)NE * NE + NE) * 4);
-    if (e == hipSuccess) {
-        float *dF = d, *dEf = dF + NFREQ, *dSK = dEf + NFREQ, *dE = dSK + NFREQ, *dT = dE + NE + 1, *dTd = dT + NE + 1, *dW = dTd + NE;
-        int *dL1 = dL, *dL2 = dL1 + (size_t)NE * NE, *dN = dL2 + (size_t)NE * NE;
-        e = hipMemcpyAsync(dF, FREQ, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dEf, Ef, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dSK, SKABS, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dE, E, (size_t)(NE + 1) * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dT, T, (size_t)(NE + 1) * 4, hipMemcpyHostToDevice, c->stream);
-        // entries the kernels do not write (pairs with u <= l, the unused tail of Iw) are 0 here; the reference leaves them to chance
-        if (e == hipSuccess) e = hipMemsetAsync(dL, 0, (2 * (size_t)NE * NE + NE) * 4, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(dIw, 0, nIw * 4, c->stream);
-        if (e == hipSuccess) e = soc_launch_a2e_pre(NFREQ, NE, FACTOR, dF, dEf, dSK, dE, dT, dL1, dL2, dIw, dW, dN, dTd, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(L1, dL1, (size_t)NE * NE * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(L2, dL2, (size_t)NE * NE * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(noIw, dN, (size_t)(NE - 1) * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(Iw, dIw, nIw * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(Tdown, dTd, (size_t)NE * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    (void)hipFree(d);
-    (void)hipFree(dIw);
-    (void)hipFree(dL);
-    if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "soc_a2e_pre: %s", hipGetErrorString(e));
-    return SOC_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// probes
-// ---------------------------------------------------------------------------------------
-
-int soc_probe_rng(soc_ctx *c, float SEED, uint32_t gid_first, uint32_t n, int ndraw, uint32_t *state_xc, uint32_t *draws)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (!state_xc || !draws || ndraw < 0 || n == 0) return fail(c, SOC_ERR_ARG, "soc_probe_rng: bad arguments");
-    HIPCHK(c, hipSetDevice(c->device));
-    uint32_t *dS = nullptr, *dD = nullptr;
-    HIPCHK(c, hipMalloc((void **)&dS, (size_t)n * 8));
-    HIPCHK(c, hipMalloc((void **)&dD, (size_t)n * (ndraw ? ndraw : 1) * 4));
-    hipError_t e = soc_launch_seed_probe(soc_seed_mul(SEED), c->dSeedTab, gid_first, n, ndraw, dS, dD, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(state_xc, dS, (size_t)n * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && ndraw) e = hipMemcpy(draws, dD, (size_t)n * ndraw * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(dS);
-    (void)hipFree(dD);
-    if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "soc_probe_rng: %s", hipGetErrorString(e));
-    return SOC_OK;
-}
-
-int soc_probe_math2(soc_ctx *c, int fn, const float *x, const float *x2, float *y, int64_t n)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (!x || !y || n <= 0) return fail(c, SOC_ERR_ARG, "soc_probe_math: bad arguments");
-    if (fn < 0 || fn > 16) return fail(c, SOC_ERR_ARG, "soc_probe_math: no function %d", fn);
-    if ((fn == 14 || fn == 15 || fn == 16) != (x2 != nullptr)) return fail(c, SOC_ERR_ARG, "soc_probe_math: function %d takes %s", fn, x2 ? "one argument" : "two arguments");
-    HIPCHK(c, hipSetDevice(c->device));
-    float *dx = nullptr, *dx2 = nullptr, *dy = nullptr;
-    hipError_t e = hipMalloc((void **)&dx, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&dy, (size_t)n * 4);
-    if (e == hipSuccess && x2) e = hipMalloc((void **)&dx2, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && x2) e = hipMemcpy(dx2, x2, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = soc_launch_math_probe(fn, dx, dx2, dy, (long)n, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(y, dy, (size_t)n * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(dx);
-    (void)hipFree(dx2);
-    (void)hipFree(dy);
-    if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "soc_probe_math: %s", hipGetErrorString(e));
-    return SOC_OK;
-}
-
-int soc_probe_math(soc_ctx *c, int fn, const float *x, float *y, int64_t n) { return soc_probe_math2(c, fn, x, nullptr, y, n); }
-
-int soc_probe_trace(soc_ctx *c, const float pos[3], const float dir[3], int maxsteps,
-                    int32_t *levels, int32_t *inds, float *ds, float endpos[3], int32_t *nsteps)
-{
-    if (!c) return SOC_ERR_ARG;
-    FLUSH(c);
-    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_probe_trace: call soc_set_grid first");
-    if (!pos || !dir || maxsteps < 1 || !levels || !inds || !ds || !endpos || !nsteps) return fail(c, SOC_ERR_ARG, "soc_probe_trace: bad arguments");
-    HIPCHK(c, hipSetDevice(c->device));
-    float *dIn = nullptr, *dDs = nullptr;
-    int *dLev = nullptr, *dN = nullptr;
-    HIPCHK(c, hipMalloc((void **)&dIn, 9 * 4));
-    HIPCHK(c, hipMalloc((void **)&dDs, (size_t)maxsteps * 4));
-    HIPCHK(c, hipMalloc((void **)&dLev, (size_t)maxsteps * 8));
-    HIPCHK(c, hipMalloc((void **)&dN, 4));
-    float h[9] = { pos[0], pos[1], pos[2], dir[0], dir[1], dir[2], 0, 0, 0 };
-    const SocVariant V = soc_grid_variant(c->G);
-    hipError_t e = hipMemcpy(dIn, h, sizeof h, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = soc_launch_trace(c->G, V, dIn, dIn + 3, maxsteps, dLev, dLev + maxsteps, dDs, dIn + 6, dN, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(nsteps, dN, 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(levels, dLev, (size_t)maxsteps * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(inds, dLev + maxsteps, (size_t)maxsteps * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(ds, dDs, (size_t)maxsteps * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(endpos, dIn + 6, 12, hipMemcpyDeviceToHost);
-    (void)hipFree(dIn);
-    (void)hipFree(dDs);
-    (void)hipFree(dLev);
-    (void)hipFree(dN);
-    if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "soc_probe_trace: %s", hipGetErrorString(e));
     return SOC_OK;
 }
 

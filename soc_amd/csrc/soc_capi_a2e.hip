@@ -1,0 +1,442 @@
+// soc_capi_a2e.hip -- host side of libsoc_hip.so: stochastically heated grains (A2E), the equilibrium-temperature solvers and the
+// multi-dust stage (kernels: soc_a2e.hip, soc_a2e_pre.hip, soc_mabu.hip).
+#include "soc_host.h"
+
+#include <algorithm>
+#include <vector>
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int soc_a2e_set_size(soc_ctx *c, int NE, int NFREQ, int noIw, const float *Iw, const int32_t *L1,
+                     const int32_t *L2, const float *Tdown, const float *EA, const int32_t *Ibeg, const float *AF)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (NE < 3 || NE > 280 || NFREQ < 2 || noIw < 0 || !Iw || !L1 || !L2 || !Tdown || !EA || !Ibeg || !AF)
+        return fail(c, SOC_ERR_ARG, "soc_a2e_set_size: bad arguments (3 <= NE <= 280, NFREQ >= 2)");
+    // pair tables in the reference's (l, u) loop order; validate every window on the host
+    const int npair = (NE * NE - NE) / 2;
+    std::vector<int> first(npair), last(npair), off(npair), dst(npair);
+    long long iw = 0;
+    int e = 0;
+    for (int l = 0; l < NE - 1; l++) {
+        for (int u = l + 1; u < NE; u++, e++) {
+            const int i0 = L1[l * NE + u], i1 = L2[l * NE + u];
+            if (i1 >= i0 && (i0 < 0 || i1 >= NFREQ))
+                return fail(c, SOC_ERR_ARG, "soc_a2e_set_size: window [%d,%d] of pair (l=%d,u=%d) outside 0..%d", i0, i1, l, u, NFREQ - 1);
+            first[e] = i0;  last[e] = i1;  off[e] = (int)iw;  dst[e] = (u * u - u) / 2 + l;
+            if (i1 >= i0) iw += i1 - i0 + 1;
+        }
+    }
+    if (iw != noIw) return fail(c, SOC_ERR_ARG, "soc_a2e_set_size: windows need %lld weights, noIw = %d", iw, noIw);
+    for (int f = 0; f < NFREQ; f++)
+        if (Ibeg[f] < 0 || Ibeg[f] > NE) return fail(c, SOC_ERR_ARG, "soc_a2e_set_size: Ibeg[%d] = %d", f, Ibeg[f]);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->aIw.reset((size_t)noIw, c->stream));
+    for (DevBuf<int> *b : { &c->aFirst, &c->aLast, &c->aIwOff, &c->aDst }) HIPCHK(c, b->reset((size_t)npair, c->stream));
+    HIPCHK(c, c->aTdown.reset((size_t)NE, c->stream));
+    HIPCHK(c, c->aEA.reset((size_t)NE * NFREQ, c->stream));
+    HIPCHK(c, c->aIbeg.reset((size_t)NFREQ, c->stream));
+    HIPCHK(c, c->aAF.reset((size_t)NFREQ, c->stream));
+    if (noIw) HIPCHK(c, hipMemcpy(c->aIw, Iw, (size_t)noIw * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->aFirst, first.data(), (size_t)npair * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->aLast, last.data(), (size_t)npair * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->aIwOff, off.data(), (size_t)npair * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->aDst, dst.data(), (size_t)npair * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->aTdown, Tdown, (size_t)NE * 4, hipMemcpyHostToDevice));
+    {   // transposed on the way: EAT[i * NFREQ + f] = EA[f * NE + i], so that the lanes of the emission loop (one
+        // frequency each) read neighbouring words (the sum over the enthalpy bins keeps its order)
+        std::vector<float> eat((size_t)NE * NFREQ);
+        for (int f = 0; f < NFREQ; f++)
+            for (int i = 0; i < NE; i++) eat[(size_t)i * NFREQ + f] = EA[(size_t)f * NE + i];
+        HIPCHK(c, hipMemcpy(c->aEA, eat.data(), (size_t)NE * NFREQ * 4, hipMemcpyHostToDevice));
+    }
+    HIPCHK(c, hipMemcpy(c->aIbeg, Ibeg, (size_t)NFREQ * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->aAF, AF, (size_t)NFREQ * 4, hipMemcpyHostToDevice));
+    if (NFREQ != c->a2e_NFREQ) { c->aABS.release();  c->aEMIT.release(); }      // (a batch uploaded for another NFREQ is none: soc_a2e_run)
+    c->a2e_NE = NE;  c->a2e_NFREQ = NFREQ;  c->a2e_npair = npair;  c->a2e_noIw = noIw;
+    return SOC_OK;
+}
+
+static int a2e_reserve(soc_ctx *c, int batch)
+{
+    if (c->a2e_NE == 0) return fail(c, SOC_ERR_STATE, "A2E: call soc_a2e_set_size first");
+    if (batch < 1) return fail(c, SOC_ERR_ARG, "A2E: batch = %d", batch);
+    HIPCHK(c, c->aABS.reserve((size_t)batch * c->a2e_NFREQ, c->stream));
+    HIPCHK(c, c->aEMIT.reserve((size_t)batch * c->a2e_NFREQ, c->stream));
+    return SOC_OK;
+}
+
+int soc_a2e_upload(soc_ctx *c, int batch, const float *AABS)
+{
+    if (!c || !AABS) return SOC_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = a2e_reserve(c, batch);
+    if (r) return r;
+    HIPCHK(c, hipMemcpyAsync(c->aABS, AABS, (size_t)batch * c->a2e_NFREQ * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
+int soc_a2e_run(soc_ctx *c, int batch)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->a2e_NE == 0 || batch < 1 || (size_t)batch * c->a2e_NFREQ > c->aEMIT.n) return fail(c, SOC_ERR_STATE, "soc_a2e_run: upload a batch first");
+    SocA2EArgs A{};
+    A.NE = c->a2e_NE;  A.NFREQ = c->a2e_NFREQ;  A.npair = c->a2e_npair;  A.batch = batch;
+    A.Iw = c->aIw;  A.pair_first = c->aFirst;  A.pair_last = c->aLast;  A.pair_iw = c->aIwOff;  A.pair_dst = c->aDst;
+    A.Tdown = c->aTdown;  A.EA = c->aEA;  A.Ibeg = c->aIbeg;  A.AF = c->aAF;  A.AABS = c->aABS;  A.AEMIT = c->aEMIT;
+    HIPCHK(c, soc_launch_a2e_dosolve(A, c->stream));
+    return SOC_OK;
+}
+
+int soc_a2e_download(soc_ctx *c, int batch, float *AEMIT)
+{
+    if (!c || !AEMIT) return SOC_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (batch < 1 || !c->aEMIT || (size_t)batch * c->a2e_NFREQ > c->aEMIT.n) return fail(c, SOC_ERR_ARG, "soc_a2e_download: batch = %d", batch);
+    HIPCHK(c, hipMemcpyAsync(AEMIT, c->aEMIT, (size_t)batch * c->a2e_NFREQ * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
+// ---- config 5 with the cells resident in HBM ----
+static void resident_release(soc_ctx *c)
+{
+    c->aAll.release();  c->aSum.release();
+    c->a2e_cells = 0;
+}
+
+int soc_a2e_resident_begin(soc_ctx *c, int64_t cells, int NFREQ)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (cells < 1 || NFREQ < 2 || cells > (int64_t)2147483647) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_begin: cells=%lld NFREQ=%d", (long long)cells, NFREQ);
+    if (c->mABS) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_begin: the resident arrays are those of soc_mabu_begin (soc_mabu_end first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    const size_t need = (size_t)cells * NFREQ * 8;
+    if (need + ((size_t)1 << 30) > free_b + (c->aAll ? (size_t)c->a2e_cells * c->a2e_res_nfreq * 8 : 0))
+        return fail(c, SOC_ERR_STATE, "soc_a2e_resident_begin: %lld cells x %d frequencies need %.1f GB of device memory, %.1f GB are free (use soc_a2e_solve in batches)",
+                    (long long)cells, NFREQ, need * 1e-9, free_b * 1e-9);
+    const size_t n = (size_t)cells * NFREQ;
+    hipError_t e = c->aAll.reset(n, c->stream);
+    if (e == hipSuccess) e = c->aSum.reset(n, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->aSum, 0, n * 4, c->stream);
+    if (e != hipSuccess) {                                  // all or nothing: half of the arrays would be gigabytes nobody can use
+        resident_release(c);
+        return fail(c, SOC_ERR_HIP, "soc_a2e_resident_begin: %s", hipGetErrorString(e));
+    }
+    c->a2e_cells = cells;  c->a2e_res_nfreq = NFREQ;
+    return SOC_OK;
+}
+
+int soc_a2e_resident_upload(soc_ctx *c, int64_t c0, int64_t n, const float *AABS)
+{
+    if (!c || !AABS) return SOC_ERR_ARG;
+    if (!c->aAll || c0 < 0 || n < 1 || c0 + n > c->a2e_cells) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_upload: cells [%lld, %lld) of %lld", (long long)c0, (long long)(c0 + n), (long long)c->a2e_cells);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(c->aAll + (size_t)c0 * c->a2e_res_nfreq, AABS, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host buffer may be a temporary)
+    return SOC_OK;
+}
+
+int soc_a2e_resident_solve(soc_ctx *c)
+{
+    if (!c) return SOC_ERR_ARG;
+    if (!c->aAll) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve: call soc_a2e_resident_begin first");
+    if (c->a2e_NE == 0 || c->a2e_NFREQ != c->a2e_res_nfreq) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve: soc_a2e_set_size with NFREQ = %d first", c->a2e_res_nfreq);
+    HIPCHK(c, hipSetDevice(c->device));
+    SocA2EArgs A{};
+    A.NE = c->a2e_NE;  A.NFREQ = c->a2e_NFREQ;  A.npair = c->a2e_npair;
+    A.Iw = c->aIw;  A.pair_first = c->aFirst;  A.pair_last = c->aLast;  A.pair_iw = c->aIwOff;  A.pair_dst = c->aDst;
+    A.Tdown = c->aTdown;  A.EA = c->aEA;  A.Ibeg = c->aIbeg;  A.AF = c->aAF;
+    A.accumulate = 1;
+    const int64_t step = 1 << 20;                           // cells per launch (the grid is one workgroup per four cells)
+    for (int64_t c0 = 0; c0 < c->a2e_cells; c0 += step) {
+        A.batch = (int)std::min<int64_t>(step, c->a2e_cells - c0);
+        A.AABS = c->aAll + (size_t)c0 * A.NFREQ;  A.AEMIT = c->aSum + (size_t)c0 * A.NFREQ;
+        HIPCHK(c, soc_launch_a2e_dosolve(A, c->stream));
+    }
+    return SOC_OK;
+}
+
+int soc_a2e_resident_download(soc_ctx *c, int64_t c0, int64_t n, float *AEMIT)
+{
+    if (!c || !AEMIT) return SOC_ERR_ARG;
+    if (!c->aSum || c0 < 0 || n < 1 || c0 + n > c->a2e_cells) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_download: cells [%lld, %lld) of %lld", (long long)c0, (long long)(c0 + n), (long long)c->a2e_cells);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(AEMIT, c->aSum + (size_t)c0 * c->a2e_res_nfreq, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
+int soc_a2e_resident_end(soc_ctx *c)
+{
+    if (!c) return SOC_ERR_ARG;
+    if (c->mABS) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_end: the resident arrays are those of soc_mabu_begin (soc_mabu_end frees them)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    resident_release(c);
+    return SOC_OK;
+}
+
+int soc_a2e_solve(soc_ctx *c, int batch, const float *AABS, float *AEMIT)
+{
+    int r = soc_a2e_upload(c, batch, AABS);
+    if (r) return r;
+    r = soc_a2e_run(c, batch);
+    if (r) return r;
+    return soc_a2e_download(c, batch, AEMIT);
+}
+
+static int eqtemp_common(soc_ctx *c, const char *who, bool eqsolver, int batch, int icell, int CELLS, int NFREQ, int NIP, float FACTOR, float kE,
+                   float oplgkE, float Emin, const float *FREQ, const float *KABS, const float *TTT,
+                   const float *ABS, float *T, float *EMIT)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (batch < 1 || NFREQ < 2 || NIP < 2 || !FREQ || !KABS || !TTT || !ABS || !T || !EMIT)
+        return fail(c, SOC_ERR_ARG, "%s: bad arguments", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<float> d;
+    const size_t n = (size_t)2 * NFREQ + NIP + (size_t)2 * batch * NFREQ + batch;
+    HIPCHK(c, d.reset(n, c->stream));
+    float *dF = d, *dK = dF + NFREQ, *dT3 = dK + NFREQ, *dA = dT3 + NIP, *dE = dA + (size_t)batch * NFREQ, *dT = dE + (size_t)batch * NFREQ;
+    HIPCHK(c, hipMemcpy(dF, FREQ, (size_t)NFREQ * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dK, KABS, (size_t)NFREQ * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dT3, TTT, (size_t)NIP * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dA, ABS, (size_t)batch * NFREQ * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(dE, 0, ((size_t)batch * NFREQ + batch) * 4, c->stream));
+    SocEqTArgs A{};
+    A.batch = batch;  A.icell = icell;  A.CELLS = CELLS;  A.NFREQ = NFREQ;  A.NIP = NIP;
+    A.FACTOR = FACTOR;  A.kE = kE;  A.oplgkE = oplgkE;  A.Emin = Emin;
+    A.FREQ = dF;  A.KABS = dK;  A.TTT = dT3;  A.ABS = dA;  A.T = dT;  A.EMIT = dE;
+    HIPCHK(c, eqsolver ? soc_launch_eqsolver(A, c->stream) : soc_launch_a2e_eqtemp(A, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(T, dT, (size_t)batch * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(EMIT, dE, (size_t)batch * NFREQ * 4, hipMemcpyDeviceToHost));
+    return SOC_OK;
+}
+
+int soc_a2e_eqtemp(soc_ctx *c, int batch, int icell, int CELLS, int NFREQ, int NIP, float FACTOR, float kE,
+                   float oplgkE, float Emin, const float *FREQ, const float *KABS, const float *TTT,
+                   const float *ABS, float *T, float *EMIT)
+{
+    return eqtemp_common(c, "soc_a2e_eqtemp", false, batch, icell, CELLS, NFREQ, NIP, FACTOR, kE, oplgkE, Emin, FREQ, KABS, TTT, ABS, T, EMIT);
+}
+
+int soc_eqsolver(soc_ctx *c, int batch, int icell, int CELLS, int NFREQ, int NE, float FACTOR, float kE,
+                 float oplgkE, float Emin, const float *FREQ, const float *KABS, const float *TTT,
+                 const float *ABS, float *T, float *EMIT)
+{
+    return eqtemp_common(c, "soc_eqsolver", true, batch, icell, CELLS, NFREQ, NE, FACTOR, kE, oplgkE, Emin, FREQ, KABS, TTT, ABS, T, EMIT);
+}
+
+// ---- the multi-dust stage with the cells resident in HBM (A2E_MABU.py:700-1140) ----
+static void mabu_release(soc_ctx *c)
+{
+    c->mABS.release();  c->mSUM.release();  c->mABU.release();  c->mT.release();  c->mTab.release();  c->mRABS.release();
+    resident_release(c);
+    c->mabu_ndust = 0;  c->mabu_tables = false;
+}
+
+int soc_mabu_begin(soc_ctx *c, int64_t cells, int NFREQ, int NDUST, int64_t *cells_fit)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (cells_fit) *cells_fit = 0;
+    if (cells < 1 || NFREQ < 2 || NDUST < 1 || cells > (int64_t)2147483647 || (size_t)NFREQ * NDUST * sizeof(double) > SOC_MABU_LDS)
+        return fail(c, SOC_ERR_ARG, "soc_mabu_begin: cells=%lld NFREQ=%d NDUST=%d (NFREQ x NDUST doubles must fit %d KB of LDS)",
+                    (long long)cells, NFREQ, NDUST, SOC_MABU_LDS / 1024);
+    if (c->aAll && !c->mABS) return fail(c, SOC_ERR_STATE, "soc_mabu_begin: the resident arrays are those of an open soc_a2e_resident_begin (soc_a2e_resident_end first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    mabu_release(c);                                        // (a soc_mabu_begin that is still open is replaced)
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    // per cell: absorptions, the dust's share, its emission, the sum (NFREQ floats each), NDUST abundances, a temperature
+    const size_t per_cell = (size_t)NFREQ * 16 + (size_t)NDUST * 4 + 4, reserve = (size_t)1 << 30;
+    const size_t need = (size_t)cells * per_cell;
+    if (cells_fit) *cells_fit = free_b > reserve ? (int64_t)((free_b - reserve) / per_cell) : 0;
+    if (need + reserve > free_b)
+        return fail(c, SOC_ERR_STATE, "soc_mabu_begin: %lld cells x %d frequencies x %d dusts need %.1f GB of device memory, %.1f GB are free (%lld cells fit: solve the cells in ranges)",
+                    (long long)cells, NFREQ, NDUST, need * 1e-9, free_b * 1e-9, (long long)(free_b > reserve ? (free_b - reserve) / per_cell : 0));
+    const size_t n = (size_t)cells * NFREQ;
+    hipError_t e = c->mABS.reset(n, c->stream);
+    if (e == hipSuccess) e = c->aAll.reset(n, c->stream);
+    if (e == hipSuccess) e = c->aSum.reset(n, c->stream);
+    if (e == hipSuccess) e = c->mSUM.reset(n, c->stream);
+    if (e == hipSuccess) e = c->mABU.reset((size_t)cells * NDUST, c->stream);
+    if (e == hipSuccess) e = c->mT.reset((size_t)cells, c->stream);
+    if (e == hipSuccess) e = c->mRABS.reset((size_t)NFREQ * NDUST, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->mSUM, 0, n * 4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->aSum, 0, n * 4, c->stream);
+    if (e != hipSuccess) {
+        mabu_release(c);
+        return fail(c, SOC_ERR_HIP, "soc_mabu_begin: %s", hipGetErrorString(e));
+    }
+    c->a2e_cells = cells;  c->a2e_res_nfreq = NFREQ;  c->mabu_ndust = NDUST;
+    return SOC_OK;
+}
+
+#define MABU_OPEN(c, who)                                                                                   \
+    do {                                                                                                    \
+        if (!(c)->mABS || !(c)->aAll || !(c)->aSum) return fail((c), SOC_ERR_STATE, who ": call soc_mabu_begin first");   \
+    } while (0)
+#define MABU_ROWS(c, who, c0, n)                                                                            \
+    do {                                                                                                    \
+        if ((c0) < 0 || (n) < 1 || (c0) + (n) > (c)->a2e_cells)                                             \
+            return fail((c), SOC_ERR_ARG, who ": cells [%lld, %lld) of %lld", (long long)(c0), (long long)((c0) + (n)), (long long)(c)->a2e_cells);   \
+    } while (0)
+
+int soc_mabu_upload(soc_ctx *c, int64_t c0, int64_t n, const float *ABS)
+{
+    if (!c || !ABS) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_upload");
+    MABU_ROWS(c, "soc_mabu_upload", c0, n);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(c->mABS + (size_t)c0 * c->a2e_res_nfreq, ABS, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host buffer may be a temporary)
+    return SOC_OK;
+}
+
+int soc_mabu_set_tables(soc_ctx *c, const float *ABU, const double *RABS)
+{
+    if (!c || !ABU || !RABS) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_set_tables");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(c->mABU, ABU, (size_t)c->a2e_cells * c->mabu_ndust * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->mRABS, RABS, (size_t)c->a2e_res_nfreq * c->mabu_ndust * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mabu_tables = true;
+    return SOC_OK;
+}
+
+int soc_mabu_split(soc_ctx *c, int idust, int clip_last)
+{
+    if (!c) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_split");
+    if (!c->mabu_tables) return fail(c, SOC_ERR_STATE, "soc_mabu_split: call soc_mabu_set_tables first");
+    if (idust < 0 || idust >= c->mabu_ndust) return fail(c, SOC_ERR_ARG, "soc_mabu_split: dust %d of %d", idust, c->mabu_ndust);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int NFREQ = c->a2e_res_nfreq;
+    HIPCHK(c, soc_launch_mabu_split(c->a2e_cells, NFREQ, c->mabu_ndust, idust, c->mABS, c->mABU, c->mRABS, c->aAll, c->stream));
+    if (clip_last) HIPCHK(c, soc_launch_mabu_clip(c->a2e_cells, NFREQ, c->aAll, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->aSum, 0, (size_t)c->a2e_cells * NFREQ * 4, c->stream));
+    return SOC_OK;
+}
+
+int soc_mabu_solve_eq(soc_ctx *c, int NE, float FACTOR, float kE, float oplgkE, float Emin, const float *FREQ, const float *KABS, const float *TTT)
+{
+    if (!c) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_solve_eq");
+    if (NE < 2 || !FREQ || !KABS || !TTT) return fail(c, SOC_ERR_ARG, "soc_mabu_solve_eq: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int NFREQ = c->a2e_res_nfreq;
+    HIPCHK(c, c->mTab.reserve((size_t)2 * NFREQ + NE, c->stream));
+    float *dF = c->mTab, *dK = dF + NFREQ, *dT3 = dK + NFREQ;
+    HIPCHK(c, hipMemcpyAsync(dF, FREQ, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dK, KABS, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dT3, TTT, (size_t)NE * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host tables may be temporaries)
+    SocEqTArgs A{};
+    A.batch = (int)c->a2e_cells;  A.icell = 0;  A.CELLS = (int)c->a2e_cells;  A.NFREQ = NFREQ;  A.NIP = NE;
+    A.FACTOR = FACTOR;  A.kE = kE;  A.oplgkE = oplgkE;  A.Emin = Emin;
+    A.FREQ = dF;  A.KABS = dK;  A.TTT = dT3;  A.ABS = c->aAll;  A.T = c->mT;  A.EMIT = c->aSum;
+    HIPCHK(c, soc_launch_eqsolver(A, c->stream));
+    return SOC_OK;
+}
+
+int soc_mabu_accumulate(soc_ctx *c, int idust)
+{
+    if (!c) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_accumulate");
+    if (!c->mabu_tables) return fail(c, SOC_ERR_STATE, "soc_mabu_accumulate: call soc_mabu_set_tables first");
+    if (idust < 0 || idust >= c->mabu_ndust) return fail(c, SOC_ERR_ARG, "soc_mabu_accumulate: dust %d of %d", idust, c->mabu_ndust);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, soc_launch_mabu_sum(c->a2e_cells, c->a2e_res_nfreq, c->mabu_ndust, idust, c->aSum, c->mABU, c->mSUM, c->stream));
+    return SOC_OK;
+}
+
+static int mabu_read(soc_ctx *c, const float *src, int64_t c0, int64_t n, float *out)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, src + (size_t)c0 * c->a2e_res_nfreq, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
+int soc_mabu_download(soc_ctx *c, int64_t c0, int64_t n, float *SUM)
+{
+    if (!c || !SUM) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_download");
+    MABU_ROWS(c, "soc_mabu_download", c0, n);
+    return mabu_read(c, c->mSUM, c0, n, SUM);
+}
+
+int soc_mabu_read_part(soc_ctx *c, int64_t c0, int64_t n, float *PART)
+{
+    if (!c || !PART) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_read_part");
+    MABU_ROWS(c, "soc_mabu_read_part", c0, n);
+    return mabu_read(c, c->aAll, c0, n, PART);
+}
+
+int soc_mabu_end(soc_ctx *c)
+{
+    if (!c) return SOC_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->mABS) mabu_release(c);
+    return SOC_OK;
+}
+
+int soc_a2e_pre(soc_ctx *c, int NFREQ, int NE, float FACTOR, const float *FREQ, const float *Ef, const float *SKABS, const float *E,
+                const float *T, int32_t *L1, int32_t *L2, float *Iw, int32_t *noIw, float *Tdown)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (NFREQ < 2 || NE < 2 || NE > 4096 || !FREQ || !Ef || !SKABS || !E || !T || !L1 || !L2 || !Iw || !noIw || !Tdown)
+        return fail(c, SOC_ERR_ARG, "soc_a2e_pre: NFREQ %d, NE %d or a NULL array", NFREQ, NE);
+    for (int i = 1; i < NFREQ; i++)
+        if (!(FREQ[i] > FREQ[i - 1]) || !(Ef[i] > Ef[i - 1])) return fail(c, SOC_ERR_ARG, "soc_a2e_pre: FREQ, Ef must increase (entry %d)", i);
+    for (int i = 1; i <= NE; i++)
+        if (!(E[i] > E[i - 1])) return fail(c, SOC_ERR_ARG, "soc_a2e_pre: the enthalpy grid E[NE+1] must increase (entry %d)", i);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nIw = (size_t)NE * NE * NFREQ, nW = (size_t)NE * NFREQ;
+    DevBuf<float> d, dIw;
+    DevBuf<int>   dL;
+    // one block of floats: FREQ | Ef | SKABS (NFREQ each) | E | T (NE+1 each) | Tdown (NE) | wrk (NE*NFREQ)
+    const size_t nf = 3 * (size_t)NFREQ + 2 * (size_t)(NE + 1) + NE + nW;
+    HIPCHK(c, d.reset(nf, c->stream));
+    HIPCHK(c, dIw.reset(nIw, c->stream));
+    HIPCHK(c, dL.reset(2 * (size_t)NE * NE + NE, c->stream));
+    float *dF = d, *dEf = dF + NFREQ, *dSK = dEf + NFREQ, *dE = dSK + NFREQ, *dT = dE + NE + 1, *dTd = dT + NE + 1, *dW = dTd + NE;
+    int *dL1 = dL, *dL2 = dL1 + (size_t)NE * NE, *dN = dL2 + (size_t)NE * NE;
+    HIPCHK(c, hipMemcpyAsync(dF, FREQ, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dEf, Ef, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dSK, SKABS, (size_t)NFREQ * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dE, E, (size_t)(NE + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dT, T, (size_t)(NE + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    // entries the kernels do not write (pairs with u <= l, the unused tail of Iw) are 0 here; the reference leaves them to chance
+    HIPCHK(c, hipMemsetAsync(dL, 0, (2 * (size_t)NE * NE + NE) * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(dIw, 0, nIw * 4, c->stream));
+    HIPCHK(c, soc_launch_a2e_pre(NFREQ, NE, FACTOR, dF, dEf, dSK, dE, dT, dL1, dL2, dIw, dW, dN, dTd, c->stream));
+    HIPCHK(c, hipMemcpyAsync(L1, dL1, (size_t)NE * NE * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(L2, dL2, (size_t)NE * NE * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(noIw, dN, (size_t)(NE - 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(Iw, dIw, nIw * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(Tdown, dTd, (size_t)NE * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

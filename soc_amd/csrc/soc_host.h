@@ -1,0 +1,180 @@
+// soc_host.h -- what the host units of libsoc_hip.so share (soc_capi.hip, soc_capi_post.hip, soc_capi_a2e.hip, soc_capi_probe.hip):
+// the handle, the one type that owns device memory, and the error and flush idioms.  Kernels do not include it.
+#pragma once
+#include "../../include/soc_hip.h"
+#include "soc_dev.h"
+
+#include <atomic>
+#include <string>
+#include <vector>
+
+#define SOC_HIDDEN __attribute__((visibility("hidden")))
+
+// bytes of device memory that owning DevBufs hold, all handles of the process together (soc_device_bytes)
+extern SOC_HIDDEN std::atomic<int64_t> soc_dev_bytes;
+
+// n elements of device memory at p: the library's own (owned: freed by release() and by the destructor) or a caller's (bind)
+template <typename T>
+struct DevBuf {
+    T     *p = nullptr;
+    size_t n = 0;                      // capacity in elements (an owned buffer of 0 elements is allocated with one)
+    bool   owned = false;
+
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n), owned(o.owned) { o.p = nullptr;  o.n = 0;  o.owned = false; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { release();  p = o.p;  n = o.n;  owned = o.owned;  o.p = nullptr;  o.n = 0;  o.owned = false; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+
+    operator T *() const { return p; }
+    explicit operator bool() const { return p != nullptr; }
+    size_t bytes() const { return (n ? n : 1) * sizeof(T); }
+
+    void release()
+    {
+        if (p && owned) { (void)hipFree(p);  soc_dev_bytes -= (int64_t)bytes(); }
+        p = nullptr;  n = 0;  owned = false;
+    }
+    // a caller's memory: used, never freed
+    void bind(T *ptr, size_t count) { release();  p = ptr;  n = count;  owned = false; }
+    // exactly `need` elements of the library's own, whatever is held; the contents are not kept.  The stream drains before a buffer
+    // goes (a launch in flight may still read it); a failed wait leaves it in place
+    hipError_t reset(size_t need, hipStream_t stream)
+    {
+        if (p) { hipError_t e = hipStreamSynchronize(stream);  if (e != hipSuccess) return e; }
+        release();
+        hipError_t e = hipMalloc((void **)&p, (need ? need : 1) * sizeof(T));
+        if (e != hipSuccess) { p = nullptr;  return e; }
+        n = need;  owned = true;
+        soc_dev_bytes += (int64_t)bytes();
+        return hipSuccess;
+    }
+    // at least `need` elements: nothing to do when they are there, else reset(need)
+    hipError_t reserve(size_t need, hipStream_t stream) { return n >= need ? hipSuccess : reset(need, stream); }
+};
+
+struct soc_ctx {
+    int device = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::string err;
+    // model
+    bool have_grid = false;
+    SocGrid G{};
+    DevBuf<float> dDENS;
+    DevBuf<int>   dPAR;
+    int64_t npar = 0;
+    // tables / per-frequency data
+    DevBuf<float> dCSC, dDSC;
+    int    BINS = 0;
+    bool   have_dsc = false;
+    // scattered-light view (soc_sca_*)
+    SocSca view{};
+    DevBuf<float4> dODIR, dORA, dODE;
+    DevBuf<float>  dOUT;               // the image: the library's own, or a caller's (soc_sca_bind_out)
+    bool   have_view = false;
+    float  ABS = 0.0f, SCA = 0.0f;
+    bool   have_optical = false;
+    DevBuf<float2> dOPT;
+    DevBuf<float>  dEMIT, dEMWEI, dXAB;
+    DevBuf<float>  dINTV;              // -D SAVE_INTENSITY=2: INTX | INTY | INTZ, CELLS floats each (with_int == 2)
+    DevBuf<int>    dEMINDEX;
+    bool   have_emit = false, have_emindex = false, with_ali = false;
+    DevBuf<float> dHPBG, dHPBGP;       // Healpix sky of the current frequency (NSIDE 64)
+    DevBuf<float> dABU, dAF;           // abundances [CELLS, NDUST] (or [CELLS]), cross sections of the frequency
+    int    abu_ndust = 0, abu_single = 0;
+    int    map_level_threshold = 0;    // -D LEVEL_THRESHOLD (soc_set_map_threshold)
+    int    map_interpolation = 0;      // -D MAP_INTERPOLATION (soc_set_map_interpolation)
+    int    map_roi_on = 0, map_roi[6] = { 0, 0, 0, 0, 0, 0 };   // -D ROI_MAP (soc_set_map_roi)
+    float  cr_rate = 0.0f;             // -D CR_HEATING_RATE with -D CR_HEATING=1 (soc_set_cr_heating); 0 = off
+    bool   opt_half = false;          // -D OPT_IS_HALF: OPT rounded through fp16 (soc_set_opt_half)
+    bool   opt_from_abu = false;       // dOPT and dAF hold the current frequency's soc_set_optical_abu values
+    int    msf_ndust = 1;              // > 1: -D WITH_MSF, dCSC/dDSC hold [msf_ndust][BINS] (soc_set_scatter_tables)
+    int    step_weight = 0;            // -D STEP_WEIGHT (soc_set_step_weight)
+    float  sw_a = 0.0f, sw_b = 0.0f;
+    size_t abu_cells = 0;              // the cell count the abundances were set for; 0: none are set (dABU may still be allocated)
+    SocRoi roi{};                      // region of interest (host copy of *dRoi)
+    DevBuf<SocRoi> dRoi;
+    DevBuf<float>  dRoiSave, dRoiLoad; // the record written (its entries: dRoiSave.n) and the one loaded
+    bool   have_hpbg = false, hpbg_weighted = false;
+    // tallies: the library's own, or a caller's (soc_bind_tally)
+    DevBuf<float> dTABS, dINT;
+    // deferred launches (soc_batch_begin .. soc_batch_end): executed together in one brick sweep (scattered light: one sweep of rays)
+    bool   batching = false;
+    int    batch_max = 4;
+    std::vector<SocSim> pending;
+    // Device copies of launch inputs, one buffer (of bytes) per store and launch slot (slot_buf): a deferred launch keeps in its slot
+    // what the caller overwrites for the next frequency; slot 0 also holds the point sources of a launch that runs at once.  SLOT_INT
+    // holds the INT tallies of a batch by group (soc_batch_read_int), SLOT_OPT one buffer in slot 0 (the sweep strides through it).  A
+    // buffer is allocated when its slot first needs more than it holds (128 slots of a 5e7-cell model up front would be 50 GB).
+    enum SlotStore { SLOT_SRC, SLOT_CSC, SLOT_DSC, SLOT_OPT, SLOT_EMIT, SLOT_HP, SLOT_INT, SLOT_STORES };
+    DevBuf<char> slots[SLOT_STORES][SOC_MAXLAUNCH];
+    DevBuf<float> dOUTslots;                                  // soc_sca_batch_images: several images, one per frequency of a batch
+    int    out_slots = 0, out_slot_cur = 0;
+    size_t out_slot_pixels = 0;
+    unsigned long long emit_gen = 0;              // bumped by soc_set_emission: launches deferred without a change in between share one copy
+    unsigned long long emit_slot_gen = 0;
+    int    emit_slot_last = -1;
+    int    int_slots_done = 0;                    // launches of the last executed sweep whose INT can be read
+    // the INT tally of the launches of a batch (set by the soc_batch_begin* call that opened it):
+    //   INT_OFF        soc_batch_begin: launches with the INT tally are not deferred
+    //   INT_SHARED     soc_batch_begin_shared_int: all tally into the handle's dINT
+    //   INT_PER_LAUNCH soc_batch_begin_int: every launch a zeroed slot of its own (SLOT_INT)
+    //   INT_PER_GROUP  soc_batch_begin_int_groups: the launches up to the next soc_batch_next_int share a slot
+    enum IntMode { INT_OFF, INT_SHARED, INT_PER_LAUNCH, INT_PER_GROUP } int_mode = INT_OFF;
+    bool   int_group_open = false;                // INT_PER_GROUP: the current group has its slot
+    // rng
+    DevBuf<uint64_t> dSeedTab;
+    DevBuf<unsigned long long> dStats;
+    unsigned long long ray_steps = 0;                        // cell steps of the rays of the scattered-light sweeps, as of the last soc_stats
+    // features
+    int with_int = 0, ps_method = 0, use_emweight = 0, mirror = 0;
+    // execution
+    int exec_mode = -1, brick_log2 = 4;
+    SocSweepResult last;                          // the last sweep's passes and form; variant: soc_last_variant, the absorption kernel last launched (-1: none yet)
+    SocBrickTune tune{};
+    // equilibrium temperature / emission (soc_emit.hip)
+    DevBuf<float> dT, dTTT, dEbuf, dEF;
+    bool   have_T = false;
+    // map making (soc_map.hip)
+    DevBuf<float>  dMapEmit, dMap, dMapTau;
+    DevBuf<float4> dBfield;            // magnetic field, one (Bx, By, Bz, pad) per cell (soc_set_bfield)
+    DevBuf<float>  dPolMap;            // the four planes of a polarisation map
+    // A2E
+    int a2e_NE = 0, a2e_NFREQ = 0, a2e_npair = 0, a2e_noIw = 0;
+    DevBuf<float> aIw, aTdown, aEA, aAF;
+    DevBuf<float> aABS, aEMIT;                               // a batch of cells, a2e_NFREQ floats each (soc_a2e_set_size with another NFREQ releases them)
+    DevBuf<float> aAll, aSum;                                // soc_a2e_resident_*: absorptions of all cells, emission summed over the sizes
+    int64_t a2e_cells = 0;                                   // cells resident in aAll and aSum, a2e_res_nfreq floats each: the rows a call may address
+    int     a2e_res_nfreq = 0;
+    DevBuf<int> aFirst, aLast, aIwOff, aDst, aIbeg;
+    // the multi-dust stage (soc_mabu_*): absorptions as the absorbed file holds them, the sum over the dusts, abundances, relative cross
+    // sections, temperatures and tables of an equilibrium dust; the current dust's share and its emission are aAll and aSum
+    DevBuf<float>  mABS, mSUM, mABU, mT, mTab;
+    DevBuf<double> mRABS;
+    int     mabu_ndust = 0;
+    bool    mabu_tables = false;
+};
+
+// the error text of a refused call, for soc_last_error (c == nullptr: of soc_create); returns code
+SOC_HIDDEN int fail(soc_ctx *c, int code, const char *fmt, ...);
+
+#define HIPCHK(c, call)                                                                       \
+    do {                                                                                      \
+        hipError_t e_ = (call);                                                               \
+        if (e_ != hipSuccess)                                                                 \
+            return fail((c), SOC_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));     \
+    } while (0)
+
+// Execute the launches deferred since soc_batch_begin (soc_capi.hip)
+SOC_HIDDEN int flush_pending(soc_ctx *c);
+#define FLUSH(c)                                    \
+    do {                                            \
+        int f_ = flush_pending(c);                  \
+        if (f_) return f_;                          \
+    } while (0)

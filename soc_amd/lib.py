@@ -28,6 +28,7 @@ API = {
     "soc_destroy": (None, [C.c_void_p]),
     "soc_last_error": (C.c_char_p, [C.c_void_p]),
     "soc_version": (C.c_char_p, []),
+    "soc_device_bytes": (C.c_int64, []),
     "soc_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "soc_set_grid": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _I, _F]),
     "soc_set_features": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -199,6 +200,12 @@ def load_library(path=None):
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def device_bytes():
+    """Bytes of device memory the engines of this process hold (soc_device_bytes): their own allocations, not a caller's bound
+    tensors, not the scratch of the brick sweep."""
+    return int(load_library().soc_device_bytes())
 
 
 def _f(a):
