@@ -405,6 +405,25 @@ int soc_polmap(soc_ctx *ctx, int polstat, int polred, int rho_weight, float p0, 
                const float *EMIT, const float *DIR, const float *RA, const float *DE, const float *CENTRE, float ABS,
                float SCA, float LENGTH, float *MAP);
 
+/* replaces the PolHealpixMapping launch + copy of ASOC.py:3946-3952 -> kernel_ASOC_map_H.c:576-841 (-D POLSTAT=0): the all-sky
+ * polarisation map of NSIDE seen from the position INTOBS[3] (root-grid coordinates) inside the model; MAP holds four planes
+ * of 12*NSIDE^2 floats in RING order: I, Q, U and column density x LENGTH.  The field is that of soc_set_bfield.  polred =
+ * -D POLRED, p0 = -D p00, interpolate = -D INTERPOLATE (0: the cell's density; 1: four-point and 2: 3x3x3 blends on a
+ * Cartesian grid; 3: 27 look-ups around the middle of the step, also on hierarchies), minlos / maxlos = -D MINLOS / MAXLOS
+ * [root cells]: nothing is registered before minlos and the ray ends at maxlos; y_shear = the Y_SHEAR argument (periodic in
+ * x and y, y shifted by that many root cells across the x faces).  Extinction is ABS+SCA or the per-cell OPT of
+ * soc_set_opt* (the line that file keeps under "#ifdef USE_ABU", :736-740, which ASOC.py never defines: the reference itself
+ * always takes the scalars); -D LEVEL_THRESHOLD is soc_set_map_threshold.  That file has its own Index() (:216-289): on a
+ * hierarchy a ray keeps octet coordinates when it climbs into a root leaf, restated as written.  An observer outside the
+ * model gives four planes of zeros.  A ray is ended after 2^15 cell steps: on a hierarchy that walk can
+ * cycle without end, and the reference then does not return.
+ * Refused with an error code, nothing changed: no field set (SOC_ERR_STATE); NSIDE < 1, interpolate outside 0..3, interpolate
+ * 1 or 2 on a hierarchy (LEVELS > 1: the reference indexes level 0 as a plain grid there and reads links as densities),
+ * y_shear != 0 with maxlos >= 1e9 (a ray near the equator would wrap ~NZ/1e-5 root cells) (SOC_ERR_ARG).  -D POLSTAT > 0
+ * does not compile in that file (:928) and is not offered. */
+int soc_polmap_healpix(soc_ctx *ctx, int NSIDE, int polred, float p0, int interpolate, float minlos, float maxlos,
+                       float y_shear, const float *EMIT, const float *INTOBS, float ABS, float SCA, float LENGTH, float *MAP);
+
 /* ---- stochastically heated grains: A2E.py / kernel_A2E.c ---- */
 
 /* replaces the PSTau launch of ASOC.py:3576-3645 (ini key pssavetau; kernel_ASOC_map.c:1545-1584): for every point source

@@ -63,8 +63,18 @@ def _check_supported(USER, NDUST, WITH_MSF, engine=None):
             bad.append("polstat %d (the 2025 variants of PolMapping, kernel_ASOC_map.c:1698 on)" % USER.POLSTAT)
         elif USER.POLSTAT not in (0, 1, 3):
             bad.append("polstat %d (PolMapping knows 0..5)" % USER.POLSTAT)
-        if USER.NPIX[1] < 0:
-            bad.append("polmap with a Healpix map (mapping with a negative second argument: PolHealpixMapping, kernel_ASOC_map_H.c)")
+        if USER.NPIX[1] < 0:                                  # ASOC.py:3808-3958 -> PolHealpixMapping, kernel_ASOC_map_H.c
+            if not hasattr(engine, "polmap_healpix"):
+                bad.append("polmap with a Healpix map (mapping with a negative second argument: PolHealpixMapping, kernel_ASOC_map_H.c): "
+                           "this engine has no polmap_healpix")
+            if USER.POLSTAT in (1, 3):
+                bad.append("polstat %d with a Healpix map (kernel_ASOC_map_H.c does not compile with -D POLSTAT > 0: a ';' is missing at :928 "
+                           "and Y_SHEAR is no argument of that kernel)" % USER.POLSTAT)
+            if int(USER.INTERPOLATE) not in (0, 1, 2, 3):
+                bad.append("interpolate %s with a Healpix polarisation map (kernel_ASOC_map_H.c:646-733 knows 0..3)" % USER.INTERPOLATE)
+            if USER.Y_SHEAR != 0.0 and not (float("%.3e" % USER.MAXLOS) < 1.0e9):
+                bad.append("yshear with a Healpix polarisation map and no finite maxlos (polmap bx by bz maxlos: without it a ray near "
+                           "the equator wraps ~NZ/1e-5 root cells)")
         if any(k.startswith('libmap') for k in USER.KEYS):
             bad.append("polmap together with libmaps (ASOC.py:3666-3667 stops there as well)")
     elif len(getattr(USER, "file_polred", "")) > 0:
@@ -76,8 +86,9 @@ def _check_supported(USER, NDUST, WITH_MSF, engine=None):
         bad.append("mapint other than 0, 1, 2 (kernel_ASOC_map.c:656-810 knows those: a larger value leaves Adens, Aemit ... unset there)")
     if len(USER.kernel_defs.strip()) > 0:
         bad.append("DEFS (extra -D options for the OpenCL compiler)")
-    # accepted without effect, because they have none in the reference either: `interpolate` and `yshear` reach only the
-    # per-level map kernel (kernel_ASOC_map_H.c, FAST_MAP >= 999: refused above), `externalmask` only the SUBITERATIONS
+    # `interpolate` and `yshear` have an effect in one branch only, the Healpix polarisation map (write_healpix_polmaps);
+    # elsewhere they are accepted without effect, because they have none in the reference either (kernel_ASOC_map_H.c is
+    # otherwise built for FAST_MAP >= 999 only: refused above).  Likewise without effect: `externalmask` reaches only the SUBITERATIONS
     # branch (refused above), `sourcemap` is parsed and never read (ASOC_aux.py:322), `bgmethod` is a -D that no kernel tests
     # (`loadtemp` with iterations > 0 has no effect in the reference: the temperatures read are replaced before any use --
     # the block that would use them with ALI, ASOC.py:2062-2071, is switched off there -- so it has none here)
@@ -141,6 +152,10 @@ class AbsorptionRun:
         c = self.cloud
         U.AREA, U.CELLS = float(c.AREA), c.CELLS
         self.log("NX %d, NY %d, NZ %d LEVELS %d, CELLS %d" % (c.NX, c.NY, c.NZ, c.LEVELS, c.CELLS))
+        if U.POLMAP and U.NPIX[1] < 0 and int(U.INTERPOLATE) in (1, 2) and c.LEVELS > 1:      # known only now that the cloud is read
+            raise UnsupportedOption("ini options not supported by this engine: interpolate %d with a Healpix polarisation map of a hierarchy "
+                                    "(kernel_ASOC_map_H.c:654-707 indexes level 0 as a plain grid there and reads links as densities; 0 or 3)"
+                                    % int(U.INTERPOLATE))
         self.ABU = files.read_abundances(U.file_abundance, c.CELLS)
         self.WITH_ABU = self.ABU is not None
         if self.WITH_ABU and U.SINGLE_ABU:
@@ -833,12 +848,13 @@ class AbsorptionRun:
         for fp in fps:
             fp.close()
 
-    def polarisation_field(self):
+    def polarisation_field(self, healpix=False):
         """The three B files of `polmap` (the layout of the cloud file: every cell, parents included) with the polarisation
         reduction factor R of `polred` encoded in the length of the vectors, B * R / sqrt(B^2 + 1e-10) (ASOC.py:3676-3720):
         `adhoc` -- R from the dust temperatures of the `temperature` file; `rhofun_<threshold>_<width>` -- from the density
         (times `density`); anything else -- a plain file [cells, {R}], clipped to [1e-6, 0.999999].  polstat 3 uses the
-        vectors as they are."""
+        vectors as they are.  healpix: the encoding of the Healpix branch (ASOC.py:3836-3872), B * R / sqrt(B^2) with a
+        file's R as it is."""
         U, c = self.U, self.cloud
         BB = [np.asarray(files.read_temperature(f, c), np.float32) for f in U.BFILES[:3]]
         polred = getattr(U, "file_polred", "")
@@ -856,10 +872,15 @@ class AbsorptionRun:
                 R = np.clip(R, 0.1, 1e10)
                 R = 0.5 * (1.0 + np.tanh((np.log10(th) - np.log10(R)) / sw))
             else:
-                R = np.clip(np.fromfile(polred, np.float32)[1:], 1.0e-6, 0.999999)
+                R = np.fromfile(polred, np.float32)[1:]
+                if not healpix:
+                    R = np.clip(R, 1.0e-6, 0.999999)
                 if R.size != c.CELLS:
                     raise files.FileError("%s: %d polarisation reduction factors for %d cells" % (polred, R.size, c.CELLS))
-            R = R / np.sqrt(BB[0] ** 2 + BB[1] ** 2 + BB[2] ** 2 + 1.0e-10)
+            if healpix:
+                R = R / np.sqrt(BB[0] ** 2 + BB[1] ** 2 + BB[2] ** 2)
+            else:
+                R = R / np.sqrt(BB[0] ** 2 + BB[1] ** 2 + BB[2] ** 2 + 1.0e-10)
             for k in range(3):
                 BB[k] *= R
         return [np.ascontiguousarray(b, np.float32) for b in BB]
@@ -912,6 +933,44 @@ class AbsorptionRun:
                 name = "polmap_%.1f_%02d.fits" % (1.0e4 * launch.C_LIGHT / FREQ, idir)          # f2um (:3800)
                 files.write_fits(name, np.asarray(MAP, np.float32).reshape(4, U.NPIX[1], U.NPIX[0]), U.FITS_RA, U.FITS_DE, pix, planes=True)
                 written.append(name)
+        e.set_bfield(None)
+        return written
+
+    def write_healpix_polmaps(self, EMITTED):
+        """`polmap bx by bz [[minlos] maxlos]` with `mapping NSIDE -1 dx` and `perspective x y z`: all-sky polarisation maps
+        seen from inside the model (ASOC.py:3808-3958 -> PolHealpixMapping, kernel_ASOC_map_H.c, POLSTAT 0): for every
+        frequency of the emitted range inside `wavelength` (:3911-3918; no `mapum` in this branch) pol_healpix.fits.<IFREQ>,
+        a Healpix table with the columns I_STOKES, Q_STOKES, U_STOKES [Jy/sr] and N.  Unlike the flat maps these are not
+        written under `nomap` (:3808).  `interpolate` and `yshear` act here, and only here."""
+        U, e, c = self.U, self.eng, self.cloud
+        if not (U.POLMAP > 0 and U.NOMAP == 0 and U.NPIX[1] < 0):
+            return []
+        # the field with `polred` encoded as THIS branch of the reference does it (:3867-3869): a file's R is not clipped and
+        # nothing is added under the root -- unlike the flat branch (:3710-3716)
+        BB = self.polarisation_field(healpix=True)
+        polred = int(len(getattr(U, "file_polred", "")) > 0)                                     # -D POLRED (ASOC.py:349,359)
+        e.set_bfield(*BB)
+        FFREQ = self.FFREQ
+        m = np.nonzero((FFREQ >= U.REMIT_F[0]) & (FFREQ <= U.REMIT_F[1]))[0]
+        I1, I2 = int(m[0]), int(m[-1])
+        sel = [i for i in range(I1, I2 + 1) if U.MAP_FREQ[0] <= float(FFREQ[i]) <= U.MAP_FREQ[1]]
+        KK = (1.0e23 / launch.FACTOR) * PLANCK / (4.0 * np.pi) * (U.GL * PARSEC)                 # :3909-3910
+        _, LENGTH_f = launch.kernel_literals(U.GL)
+        p0 = float("%.4f" % U.p0)                                                               # -D p00=%.4ff (ASOC.py:349)
+        minlos, maxlos = float("%.3e" % U.MINLOS), float("%.3e" % U.MAXLOS)                      # -D MINLOS=%.3ef -D MAXLOS=%.3ef
+        NSIDE = int(U.NPIX[0])
+        written = []
+        for IFREQ in sel:
+            FREQ = float(FFREQ[IFREQ])
+            ABS, SCA = self._optical_for(IFREQ)
+            EMIT = np.asarray(KK * FREQ * EMITTED[:, IFREQ - I1], np.float32)                    # :3944
+            MAP = e.polmap_healpix(EMIT, NSIDE, U.INTOBS, ABS, SCA, polred=polred, p0=p0, interpolate=int(U.INTERPOLATE), minlos=minlos,
+                                   maxlos=maxlos, y_shear=float(U.Y_SHEAR), LENGTH=LENGTH_f)
+            if self.rank != 0:
+                continue
+            name = "pol_healpix.fits.%d" % IFREQ
+            files.write_healpix_fits(name, np.asarray(MAP, np.float32).reshape(4, -1), files.HEALPIX_POL_COLUMNS, NSIDE)
+            written.append(name)
         e.set_bfield(None)
         return written
 
@@ -986,6 +1045,7 @@ class AbsorptionRun:
             self.write_maps(self.EMITTED)
         if U.POLMAP and self.EMITTED is not None:                 # also under `nomap` (ASOC.py:3655)
             self.write_polmaps(self.EMITTED)
+            self.write_healpix_polmaps(self.EMITTED)              # NPIX.y < 0, and not under `nomap` (:3808)
         if U.NO_PS > 0 and U.pssavetau_freq > 0.0 and U.NPIX[1] > 0:
             self.write_ps_tau()
         if self.rank == 0 and self.INTENSITY is not None:          # ASOC.py:2733-2757

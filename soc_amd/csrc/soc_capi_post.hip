@@ -224,6 +224,42 @@ int soc_polmap(soc_ctx *c, int polstat, int polred, int rho_weight, float p0, in
     return SOC_OK;
 }
 
+// all-sky polarisation map (ASOC.py:3808-3958 -> PolHealpixMapping, kernel_ASOC_map_H.c:576-841)
+int soc_polmap_healpix(soc_ctx *c, int NSIDE, int polred, float p0, int interpolate, float minlos, float maxlos, float y_shear,
+                       const float *EMIT, const float *INTOBS, float ABS, float SCA, float LENGTH, float *MAP)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_polmap_healpix: call soc_set_grid first");
+    if (!c->dBfield) return fail(c, SOC_ERR_STATE, "soc_polmap_healpix: call soc_set_bfield first");
+    if (!EMIT || !MAP || !INTOBS) return fail(c, SOC_ERR_ARG, "soc_polmap_healpix: EMIT, INTOBS and MAP are needed");
+    if (NSIDE < 1 || NSIDE > 8192) return fail(c, SOC_ERR_ARG, "soc_polmap_healpix: NSIDE %d (1..8192)", NSIDE);
+    if (interpolate < 0 || interpolate > 3) return fail(c, SOC_ERR_ARG, "soc_polmap_healpix: interpolate %d (0..3)", interpolate);
+    if ((interpolate == 1 || interpolate == 2) && c->G.LEVELS > 1)
+        return fail(c, SOC_ERR_ARG, "soc_polmap_healpix: interpolate %d indexes level 0 as a plain grid and would read links as densities on a hierarchy of %d levels (0 or 3 there)",
+                    interpolate, c->G.LEVELS);
+    if (!std::isfinite(y_shear) || std::isnan(minlos) || std::isnan(maxlos) || !std::isfinite(p0))
+        return fail(c, SOC_ERR_ARG, "soc_polmap_healpix: p0, minlos, maxlos and y_shear must be numbers");
+    // a ray near the equator leaves through a z face only after ~NZ/1e-5 root cells: without a line-of-sight limit it wraps that long
+    if (y_shear != 0.0f && !(maxlos < 1.0e9f)) return fail(c, SOC_ERR_ARG, "soc_polmap_healpix: y_shear %g needs maxlos < 1e9 (given %g)", (double)y_shear, (double)maxlos);
+    for (int k = 0; k < 3; k++) if (!std::isfinite(INTOBS[k])) return fail(c, SOC_ERR_ARG, "soc_polmap_healpix: INTOBS[%d] = %g", k, (double)INTOBS[k]);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)12 * NSIDE * NSIDE, cells = (size_t)c->G.CELLS;
+    HIPCHK(c, c->dMapEmit.reserve(cells, c->stream));
+    HIPCHK(c, c->dPolMap.reserve(4 * npix, c->stream));
+    SocHPolArgs A;
+    memset(&A, 0, sizeof A);
+    A.NSIDE = NSIDE;  A.polred = polred ? 1 : 0;  A.LEVEL_THRESHOLD = c->map_level_threshold;  A.INTERPOLATE = interpolate;
+    A.p0 = p0;  A.MINLOS = minlos;  A.MAXLOS = maxlos;  A.Y_SHEAR = y_shear;  A.ABS = ABS;  A.SCA = SCA;  A.LENGTH = LENGTH;
+    for (int k = 0; k < 3; k++) A.INTOBS[k] = INTOBS[k];
+    A.EMIT = c->dMapEmit;  A.OPT = c->dOPT;  A.B = c->dBfield;  A.MAP = c->dPolMap;
+    HIPCHK(c, hipMemcpyAsync(c->dMapEmit, EMIT, cells * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, soc_launch_hpolmap(c->G, A, c->dOPT != nullptr, c->stream));
+    HIPCHK(c, hipMemcpyAsync(MAP, c->dPolMap, 4 * npix * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
 int soc_ps_tau(soc_ctx *c, int NO_PS, const float *PSPOS, const float *DIR, float ABS, float SCA, float LENGTH, float *pscolden, float *pstau)
 {
     if (!c) return SOC_ERR_ARG;

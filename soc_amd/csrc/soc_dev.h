@@ -160,6 +160,22 @@ struct SocPolArgs {
     float *MAP;                    // [4 * NPIX_Y * NPIX_X]
 };
 hipError_t soc_launch_polmap(const SocGrid &G, const SocPolArgs &A, bool abu, hipStream_t st);
+// all-sky polarisation map (soc_map.hip): one launch of PolHealpixMapping (kernel_ASOC_map_H.c:576-597), -D POLSTAT=0
+#define SOC_HPOL_MAXSTEPS (1 << 15)    // cell steps after which a ray is ended: on hierarchies the reference's walk can cycle for ever
+struct SocHPolArgs {
+    int   NSIDE, polred, LEVEL_THRESHOLD;
+    int   INTERPOLATE;             // -D INTERPOLATE 0..3 (kernel_ASOC_map_H.c:646-733)
+    float p0;                      // -D p00
+    float MINLOS, MAXLOS;          // -D MINLOS, -D MAXLOS [root cells]
+    float Y_SHEAR;                 // periodic in x and y, y shifted by this many root cells across the x faces (:800-826)
+    float ABS, SCA, LENGTH;
+    float INTOBS[3];
+    const float  *EMIT;
+    const float2 *OPT;
+    const float4 *B;               // [CELLS] (Bx, By, Bz, pad)
+    float *MAP;                    // [4 * 12 * NSIDE^2]
+};
+hipError_t soc_launch_hpolmap(const SocGrid &G, const SocHPolArgs &A, bool abu, hipStream_t st);
 hipError_t soc_launch_pack_bfield(int cells, const float *Bx, const float *By, const float *Bz, float4 *B, hipStream_t st);
 hipError_t soc_launch_pstau(const SocGrid &G, int no, const float4 *PSPOS, const float *DIR, float ABS, float SCA, const float2 *OPT, float LENGTH,
                             float *pscolden, float *pstau, hipStream_t st);

@@ -1,5 +1,5 @@
-// soc_map.hip -- map making: Mapping, HealpixMapping and PolMapping of kernel_ASOC_map.c (:496-888, :890-970, :972-1693) for
-// gfx950.  One lane per map pixel integrates emission x extinction along its line
+// soc_map.hip -- map making: Mapping, HealpixMapping and PolMapping of kernel_ASOC_map.c (:496-888, :890-970, :972-1693) and
+// PolHealpixMapping of kernel_ASOC_map_H.c (:576-841) for gfx950.  One lane per map pixel integrates emission x extinction along its line
 // of sight through the (hierarchical) grid.
 //
 // The reference's map file has its own copies of the traversal helpers, and they are not the ones of the
@@ -8,14 +8,18 @@
 // "POS.z<=0.0") -- so after every step out of an octet the position is rebuilt from the root.  That
 // changes the last bits of positions and step lengths, hence of the maps; it is restated here as written
 // (soc_map_index) and pinned bit-exactly by the x86 build of the reference (oracle/_ref/refmap_*.so).
-// -D MAP_INTERPOLATION, ROI_MAP and LEVEL_THRESHOLD are launch arguments here; PolMapping (POLSTAT 0, 1, 3) follows at the end of the file.
+// -D MAP_INTERPOLATION, ROI_MAP and LEVEL_THRESHOLD are launch arguments here; PolMapping (POLSTAT 0, 1, 3) and
+// PolHealpixMapping (POLSTAT 0, with the differences of its own file's walk) follow at the end of the file.
 #include "soc_walk.h"
 
 #define SOC_MAP_PEPS 5.0e-4f
 #define SOC_MAP_EPS  2.5e-4f
 
 
-template <bool OCT, typename T>
+// HFILE: the Index() of kernel_ASOC_map_H.c (:216-289, PolHealpixMapping) instead.  It is this one except that it does not
+// write the position back where the climb ends on the root grid -- neither when the ray has left the model (:246-248) nor
+// when the root cell found there is a leaf (:252): the ray then goes on at level 0 with the octet's local coordinates.
+template <bool OCT, typename T, bool HFILE = false>
 __device__ __forceinline__ void soc_map_index(const SocGrid &G, const int *sOFF, float &px, float &py, float &pz,
                                               int &level, int &ind, float &dens)
 {
@@ -40,12 +44,12 @@ __device__ __forceinline__ void soc_map_index(const SocGrid &G, const int *sOFF,
                 PZ += ind / (NX * NY);
                 if ((PX <= ZERO) || (PX >= NX) || (PY <= ZERO) || (PY >= NY) || (PZ <= ZERO) || (PZ >= NZ)) {
                     ind = -1;
-                    px = (float)PX;  py = (float)PY;  pz = (float)PZ;
+                    if (!HFILE) { px = (float)PX;  py = (float)PY;  pz = (float)PZ; }
                     return;
                 }
                 ind  = (int)SocReal<T>::floorr(PZ) * NX * NY + (int)SocReal<T>::floorr(PY) * NX + (int)SocReal<T>::floorr(PX);
                 dens = G.DENS[ind];
-                if (dens > 0.0f) { px = (float)PX;  py = (float)PY;  pz = (float)PZ;  return; }
+                if (dens > 0.0f) { if (!HFILE) { px = (float)PX;  py = (float)PY;  pz = (float)PZ; }  return; }
                 break;
             } else {
                 const int sid = ind % 8;
@@ -70,7 +74,7 @@ __device__ __forceinline__ void soc_map_index(const SocGrid &G, const int *sOFF,
     }
 }
 
-template <bool OCT, bool DBL>
+template <bool OCT, bool DBL, bool HFILE = false>
 __device__ __forceinline__ float soc_map_getstep(const SocGrid &G, const int *sOFF, float &px, float &py, float &pz,
                                                  float ux, float uy, float uz, int &level, int &ind, float &dens)
 {
@@ -82,8 +86,8 @@ __device__ __forceinline__ float soc_map_getstep(const SocGrid &G, const int *sO
     py += s * uy;
     pz += s * uz;
     s = soc_scale_down(s, level);
-    if (DBL) soc_map_index<OCT, double>(G, sOFF, px, py, pz, level, ind, dens);
-    else     soc_map_index<OCT, float>(G, sOFF, px, py, pz, level, ind, dens);
+    if (DBL) soc_map_index<OCT, double, HFILE>(G, sOFF, px, py, pz, level, ind, dens);
+    else     soc_map_index<OCT, float, HFILE>(G, sOFF, px, py, pz, level, ind, dens);
     return s;
 }
 
@@ -541,6 +545,167 @@ hipError_t soc_launch_polmap(const SocGrid &G, const SocPolArgs &A, bool abu, hi
     else if (A.polstat == 1) soc_polmap_dispatch<1>(G, A, abu, grid, block, st);
     else if (A.polstat == 3) soc_polmap_dispatch<3>(G, A, abu, grid, block, st);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// all-sky polarisation map: PolHealpixMapping of kernel_ASOC_map_H.c, -D POLSTAT=0 (:576-841)
+// ------------------------------------------------------------------------------------
+// One lane per RING pixel; I, Q, U and the column density as seen from INTOBS inside the model.  That file carries its
+// own walk (:179-380).  Compared with kernel_ASOC_map.c: IndexG (:179-212) is the same text and GetStep (:297-326) the same
+// arithmetic (PEPS = 5e-4; the other file's double branch for NX > 9999 is missing here) -- soc_indexg and
+// soc_map_getstep are reused; Index (:216-289) differs, see soc_map_index<.., HFILE = true>.  The consequence is restated,
+// not repaired: on a hierarchy a ray that steps from an octet into a root leaf goes on from the corner of the grid.
+// -D INTERPOLATE is compiled in; mode 3 keeps its 27 look-ups in registers.  -D POLRED, LEVEL_THRESHOLD, p00, MINLOS and
+// MAXLOS are launch arguments.  The extinction of a step is ABS + SCA, or the per-cell sum the file has under
+// "#ifdef USE_ABU" (:736-740) when the handle holds per-cell opacities.  A ray ends after SOC_HPOL_MAXSTEPS steps.
+template <bool OCT, bool DBL, bool ABU, int INTERP>
+__global__ __launch_bounds__(256) void soc_hpolmap_kernel(const SocGrid G, const SocHPolArgs A)
+{
+    __shared__ int sOFF[SOC_MAXL];
+    if (threadIdx.x < SOC_MAXL) sOFF[threadIdx.x] = G.OFF[threadIdx.x];
+    __syncthreads();
+    const int npix = 12 * A.NSIDE * A.NSIDE;
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= npix) return;
+    const int NX = G.NX, NY = G.NY, NZ = G.NZ;
+    float phi, theta, st, ct, sp, cp;
+    soc_pixel2angles_ring(A.NSIDE, id, phi, theta);
+    soc_sincosf(theta, &st, &ct);
+    soc_sincosf(phi, &sp, &cp);
+    float tx = +st * cp, ty = +st * sp, tz = -ct;                          // HDIR (:616-621)
+    if (soc_fabsf(tx) < 1.0e-5f) tx = 1.0e-5f;
+    if (soc_fabsf(ty) < 1.0e-5f) ty = 1.0e-5f;
+    if (soc_fabsf(tz) < 1.0e-5f) tz = 1.0e-5f;
+    float px = A.INTOBS[0], py = A.INTOBS[1], pz = A.INTOBS[2];
+    if ((soc_fmod1f(px) < 1.0e-5f) || (soc_fmod1f(px) < 0.99999f)) px += 2.0e-5f;       // as written (:623-625)
+    if ((soc_fmod1f(py) < 1.0e-5f) || (soc_fmod1f(py) < 0.99999f)) py += 2.0e-5f;
+    if ((soc_fmod1f(pz) < 1.0e-5f) || (soc_fmod1f(pz) < 0.99999f)) pz += 2.0e-5f;
+    const float rx = -sp, ry = +cp, rz = 0.0f;                             // HRA points left, HDE to the north (:628-634)
+    const float ex = -ct * cp, ey = -ct * sp, ez = +st;
+    const float OPTSUM = A.SCA + A.ABS;
+    int   level = 0, ind = -1;
+    float dens = 0.0f, TAU = 0.0f, colden = 0.0f, los = 0.0f, I = 0.0f, Q = 0.0f, U = 0.0f, p = A.p0;
+    soc_indexg<OCT>(G, sOFF, px, py, pz, level, ind, dens);
+    for (int steps = 0; (ind >= 0) && (steps < SOC_HPOL_MAXSTEPS); steps++) {
+        const int   oind = sOFF[level] + ind, olevel = level;
+        float mx = px, my = py, mz = pz;                                   // MPOS, the position before the step
+        float rho = dens;
+        float sx = soc_map_getstep<OCT, DBL, true>(G, sOFF, px, py, pz, tx, ty, tz, level, ind, dens);
+        if (INTERP > 0) { const float h = 0.5f * sx;  mx = mx + h * tx;  my = my + h * ty;  mz = mz + h * tz; }
+        if (INTERP == 1) {                                                 // four points of a Cartesian grid (:654-682)
+            const int i0 = min(max((int)soc_floorf(mx), 0), NX - 1), j0 = min(max((int)soc_floorf(my), 0), NY - 1),
+                      k0 = min(max((int)soc_floorf(mz), 0), NZ - 1);
+            mx = soc_fmod1f(mx) - 0.5f;  my = soc_fmod1f(my) - 0.5f;  mz = soc_fmod1f(mz) - 0.5f;
+            float sum = (3.0f - soc_fabsf(mx) - soc_fabsf(my) - soc_fabsf(mz)) * rho;
+            if (mx > 0.0f) sum += mx * G.DENS[k0 * NX * NY + j0 * NX + max(0, i0 - 1)];
+            else           sum += -mx * G.DENS[k0 * NX * NY + j0 * NX + min(i0 + 1, NX - 1)];
+            if (my > 0.0f) sum += +my * G.DENS[k0 * NX * NY + max(j0 - 1, 0) * NX + i0];
+            else           sum += -my * G.DENS[k0 * NX * NY + min(j0 + 1, NY - 1) * NX + i0];
+            if (mz > 0.0f) sum += +mz * G.DENS[max(k0 - 1, 0) * NX * NY + j0 * NX + i0];
+            else           sum += -mz * G.DENS[min(k0 + 1, NZ - 1) * NX * NY + j0 * NX + i0];
+            rho = 0.333333f * sum;
+        }
+        if (INTERP == 2) {                                                 // 3 x 3 x 3 cells, inverse-distance weights (:686-707)
+            const int i0 = (int)soc_floorf(mx), j0 = (int)soc_floorf(my), k0 = (int)soc_floorf(mz);
+            float sum = 0.0f, weight = 0.0f;
+            for (int k = max(0, k0 - 1); k < min(k0 + 2, NZ); k++)
+                for (int j = max(0, j0 - 1); j < min(j0 + 2, NY); j++)
+                    for (int i = max(0, i0 - 1); i < min(i0 + 2, NX); i++) {
+                        const float ax = mx - (i + 0.5f), ay = my - (j + 0.5f), az = mz - (k + 0.5f);
+                        const float w = 1.0f / (0.1f + soc_sqrtf(ax * ax + ay * ay + az * az));
+                        weight += w;
+                        sum += w * G.DENS[k * NY * NX + j * NX + i];
+                    }
+            rho = sum / weight;
+        }
+        if (INTERP == 3) {                                                 // 27 IndexG look-ups at +- the cell size (:711-733)
+            float sum = 0.0f, weight = 0.0f;
+            const float delta = soc_scale_down(1.0f, olevel);             // pow(0.5f, olevel)
+            for (int k = -1; k < 2; k++)
+                for (int j = -1; j < 2; j++)
+                    for (int i = -1; i < 2; i++) {
+                        float ax = mx + i * delta, ay = my + j * delta, az = mz + k * delta, nd = 0.0f;
+                        int   mlevel = 0, mind = -1;
+                        soc_indexg<OCT>(G, sOFF, ax, ay, az, mlevel, mind, nd);
+                        if (mind >= 0) {
+                            const float w = 1.0f / soc_sqrtf(0.2f + (float)(i * i) + (float)(j * j) + (float)(k * k));
+                            weight += w;
+                            sum += w * nd;
+                        }
+                    }
+            rho = sum / weight;
+        }
+        float DTAU;
+        if (ABU) { const float2 o = A.OPT[oind];  DTAU = sx * rho * (o.x + o.y); }
+        else     DTAU = sx * rho * OPTSUM;
+        los += sx;
+        if (los > A.MAXLOS) {                                              // trims the step, not DTAU (:743-746)
+            ind = -1;  pz = -1.0f;
+            sx = A.MAXLOS - (los - sx);
+        }
+        const float4 B = A.B[oind];
+        float bx = B.x, by = B.y, bz = B.z;
+        if (A.polred) p = soc_sqrtf(bx * bx + by * by + bz * bz);          // -D POLRED: p = |B|
+        soc_normalize(bx, by, bz);
+        // "0.5*PI+atan2(...)": the literal is a double (:768)
+        const float Psi = (float)(0.5 * (double)SOC_POL_PI + (double)soc_atan2f(soc_dot3(bx, by, bz, rx, ry, rz), soc_dot3(bx, by, bz, ex, ey, ez)));
+        const float bd = soc_dot3(bx, by, bz, tx, ty, tz);
+        const float cc = 0.99999f - 0.99998f * bd * bd;
+        const float sz = soc_pol_emitted(TAU, DTAU, sx, A.EMIT[oind], rho);
+        if (los < A.MINLOS) continue;                                      // nothing registered yet, TAU and the shear included (:776)
+        if (olevel >= A.LEVEL_THRESHOLD) {
+            float s2, c2;
+            soc_sincosf(2.0f * Psi, &s2, &c2);
+            I += sz * (1.0f - p * (cc - 0.6666667f));
+            Q += p * sz * c2 * cc;
+            U += p * sz * s2 * cc;
+        }
+        TAU += DTAU;
+        colden += sx * rho;
+        if ((A.Y_SHEAR != 0.0f) && (ind < 0) && (los < A.MAXLOS)) {        // shearing box: re-entry in x and y (:800-826)
+            if ((pz > 0.0f) && (pz < NZ)) {
+                if (py < 0.0f) py = NY - SOC_MAP_PEPS;
+                if (py > NY)   py = +SOC_MAP_PEPS;
+                if (px < 0.0f) { px = NX - SOC_MAP_PEPS;  py = soc_fmodf_small(py + NY - A.Y_SHEAR, (float)NY); }
+                if (px > NX)   { px = +SOC_MAP_PEPS;      py = soc_fmodf_small(py + A.Y_SHEAR, (float)NY); }
+                soc_indexg<OCT>(G, sOFF, px, py, pz, level, ind, dens);
+            }
+        }
+    }
+    A.MAP[0 * (size_t)npix + id] = I;
+    A.MAP[1 * (size_t)npix + id] = Q;
+    A.MAP[2 * (size_t)npix + id] = U;
+    A.MAP[3 * (size_t)npix + id] = colden * A.LENGTH;
+}
+
+template <bool OCT, bool DBL, int INTERP>
+static void soc_hpolmap_launch(const SocGrid &G, const SocHPolArgs &A, bool abu, dim3 grid, dim3 block, hipStream_t st)
+{
+    if (abu) soc_hpolmap_kernel<OCT, DBL, true, INTERP><<<grid, block, 0, st>>>(G, A);
+    else     soc_hpolmap_kernel<OCT, DBL, false, INTERP><<<grid, block, 0, st>>>(G, A);
+}
+
+hipError_t soc_launch_hpolmap(const SocGrid &G, const SocHPolArgs &A, bool abu, hipStream_t st)
+{
+    const int npix = 12 * A.NSIDE * A.NSIDE;
+    if (npix <= 0) return hipSuccess;
+    const dim3 grid((npix + 255) / 256), block(256);
+    const bool oct = G.LEVELS > 1, dbl = oct && (G.NX > 100);            // kernel_ASOC_map_H.c:14, :222
+    const int  m = A.INTERPOLATE;
+    if ((m < 0) || (m > 3) || (oct && ((m == 1) || (m == 2)))) return hipErrorInvalidValue;   // 1, 2 index level 0 as a plain grid
+    if (!oct) {
+        if (m == 0)      soc_hpolmap_launch<false, false, 0>(G, A, abu, grid, block, st);
+        else if (m == 1) soc_hpolmap_launch<false, false, 1>(G, A, abu, grid, block, st);
+        else if (m == 2) soc_hpolmap_launch<false, false, 2>(G, A, abu, grid, block, st);
+        else             soc_hpolmap_launch<false, false, 3>(G, A, abu, grid, block, st);
+    } else if (!dbl) {
+        if (m == 0) soc_hpolmap_launch<true, false, 0>(G, A, abu, grid, block, st);
+        else        soc_hpolmap_launch<true, false, 3>(G, A, abu, grid, block, st);
+    } else {
+        if (m == 0) soc_hpolmap_launch<true, true, 0>(G, A, abu, grid, block, st);
+        else        soc_hpolmap_launch<true, true, 3>(G, A, abu, grid, block, st);
+    }
     return hipGetLastError();
 }
 

@@ -550,3 +550,92 @@ def read_fits(path):
     data = np.frombuffer(raw, ">f4", n, pos).astype(np.float32).reshape(shape)
     hdr["COMMENT"] = comments
     return hdr, data
+
+
+HEALPIX_POL_COLUMNS = ["I_STOKES", "Q_STOKES", "U_STOKES", "N"]
+
+
+def write_healpix_fits(path, columns, names, nside):
+    """The binary table healpy.write_map(path, columns, fits_IDL=False, coord='G', column_names=names) writes
+    (ASOC.py:3955-3958): an empty primary HDU, then one BINTABLE with a big-endian float32 ('E') column per map, RING
+    order, rows of 1024 values when npix is a multiple of 1024 and one value per row otherwise; PIXTYPE, ORDERING,
+    COORDSYS, NSIDE, FIRSTPIX, LASTPIX, INDXSCHM as healpy sets them.  Written by hand, as write_fits is.  Neither healpy
+    nor astropy was at hand where this was written: that healpy reads the file has not been checked, only its structure
+    (2880-byte blocks, the order of the mandatory keywords) and the round trip through read_healpix_fits."""
+    cols = [np.ascontiguousarray(c, np.float32).ravel() for c in columns]
+    npix = 12 * int(nside) ** 2
+    if len(cols) != len(names) or any(c.size != npix for c in cols):
+        raise FileError("%s: %d columns of %s values for %d names and NSIDE %d" % (path, len(cols), [c.size for c in cols], len(names), nside))
+    rep = 1024 if npix % 1024 == 0 else 1
+    rows = npix // rep
+    head = "".join([_fits_card("SIMPLE", True, "conforms to FITS standard"), _fits_card("BITPIX", 8, "array data type"),
+                    _fits_card("NAXIS", 0, "number of array dimensions"), _fits_card("EXTEND", True), "END".ljust(80)])
+    head += " " * (-len(head) % 2880)
+    cards = [_fits_card("XTENSION", "BINTABLE", "binary table extension"), _fits_card("BITPIX", 8, "array data type"),
+             _fits_card("NAXIS", 2, "number of array dimensions"), _fits_card("NAXIS1", 4 * rep * len(cols), "length of dimension 1"),
+             _fits_card("NAXIS2", rows, "length of dimension 2"), _fits_card("PCOUNT", 0, "number of group parameters"),
+             _fits_card("GCOUNT", 1, "number of groups"), _fits_card("TFIELDS", len(cols), "number of table fields")]
+    for k, name in enumerate(names):
+        cards += [_fits_card("TTYPE%d" % (k + 1), name), _fits_card("TFORM%d" % (k + 1), "%dE" % rep if rep > 1 else "E")]
+    cards += [_fits_card("PIXTYPE", "HEALPIX", "HEALPIX pixelisation"), _fits_card("ORDERING", "RING", "Pixel ordering scheme, either RING or NESTED"),
+              _fits_card("COORDSYS", "G", "Ecliptic, Galactic or Celestial (equatorial)"), _fits_card("EXTNAME", "xtension", "name of this binary table extension"),
+              _fits_card("NSIDE", int(nside), "Resolution parameter of HEALPIX"), _fits_card("FIRSTPIX", 0, "First pixel # (0 based)"),
+              _fits_card("LASTPIX", npix - 1, "Last pixel # (0 based)"), _fits_card("INDXSCHM", "IMPLICIT", "Indexing: IMPLICIT or EXPLICIT"),
+              _fits_card("OBJECT", "FULLSKY", "Sky coverage, either FULLSKY or PARTIAL"), "END".ljust(80)]
+    table = "".join(cards)
+    table += " " * (-len(table) % 2880)
+    body = np.stack([c.reshape(rows, rep) for c in cols], axis=1).astype(">f4").tobytes()      # row = (col 1 x rep, col 2 x rep, ...)
+    body += b"\0" * (-len(body) % 2880)
+    with open(path, "wb") as fp:
+        fp.write(head.encode("ascii"))
+        fp.write(table.encode("ascii"))
+        fp.write(body)
+
+
+def _fits_header(raw, pos):
+    """-> (dict, keys in file order, offset of the block after the header)"""
+    hdr, order = {}, []
+    while True:
+        block = raw[pos:pos + 2880].decode("ascii")
+        if len(block) < 2880:
+            raise FileError("FITS header without END")
+        pos += 2880
+        for i in range(0, 2880, 80):
+            card = block[i:i + 80]
+            key = card[:8].strip()
+            if key == "END":
+                return hdr, order, pos
+            if card[8:10] == "= ":
+                v = card[10:].split(" / ")[0].strip()
+                order.append(key)
+                if v.startswith("'"):
+                    hdr[key] = v.strip("'").strip()
+                elif v in ("T", "F"):
+                    hdr[key] = (v == "T")
+                else:
+                    hdr[key] = float(v) if any(c in v for c in ".EN") else int(v)
+
+
+def read_healpix_fits(path):
+    """-> (header dict of the table, names, columns [TFIELDS, npix] float32) of a file write_healpix_fits wrote"""
+    with open(path, "rb") as fp:
+        raw = fp.read()
+    if len(raw) % 2880:
+        raise FileError("%s: %d bytes are no whole number of FITS blocks" % (path, len(raw)))
+    prim, _, pos = _fits_header(raw, 0)
+    if prim.get("NAXIS") != 0:
+        raise FileError("%s: the primary HDU holds data" % path)
+    hdr, order, pos = _fits_header(raw, pos)
+    if hdr.get("XTENSION") != "BINTABLE" or hdr.get("PIXTYPE") != "HEALPIX":
+        raise FileError("%s: no Healpix binary table" % path)
+    n = hdr["TFIELDS"]
+    forms = [hdr["TFORM%d" % (k + 1)] for k in range(n)]
+    if len(set(forms)) != 1 or not forms[0].endswith("E"):
+        raise FileError("%s: columns %s" % (path, forms))
+    rep = int(forms[0][:-1] or 1)
+    rows = hdr["NAXIS2"]
+    if hdr["NAXIS1"] != 4 * rep * n:
+        raise FileError("%s: NAXIS1 %d for %d columns of %dE" % (path, hdr["NAXIS1"], n, rep))
+    data = np.frombuffer(raw, ">f4", rows * n * rep, pos).astype(np.float32).reshape(rows, n, rep)
+    hdr["_ORDER"] = order
+    return hdr, [hdr["TTYPE%d" % (k + 1)] for k in range(n)], np.ascontiguousarray(data.transpose(1, 0, 2).reshape(n, rows * rep))

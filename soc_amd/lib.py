@@ -106,6 +106,8 @@ API = {
     "soc_set_bfield": (C.c_int, [C.c_void_p, _F, _F, _F]),
     "soc_polmap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F,
                              C.c_float, C.c_float, C.c_float, _F]),
+    "soc_polmap_healpix": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, _F, _F,
+                                     C.c_float, C.c_float, C.c_float, _F]),
     "soc_ps_tau": (C.c_int, [C.c_void_p, C.c_int, _F, _F, C.c_float, C.c_float, C.c_float, _F, _F]),
     "soc_a2e_set_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _F, _I, _I, _F, _F, _I, _F]),
     "soc_a2e_solve": (C.c_int, [C.c_void_p, C.c_int, _F, _F]),
@@ -558,6 +560,23 @@ class Engine:
         self._chk(self.lib.soc_polmap(self.h, int(polstat), int(polred), int(rho_weight), np.float32(p0), nx, ny, np.float32(MAP_DX),
                                       _f(EMIT), _f(v[0]), _f(v[1]), _f(v[2]), _f(v[3]), np.float32(ABS), np.float32(SCA),
                                       np.float32(LENGTH), _f(MAP)))
+        return MAP
+
+    def polmap_healpix(self, EMIT, NSIDE, INTOBS, ABS, SCA, polred=0, p0=0.2, interpolate=0, minlos=-1.0, maxlos=1e10, y_shear=0.0,
+                       LENGTH=1.0):
+        """One all-sky polarisation map seen from INTOBS (kernel_ASOC_map_H.c PolHealpixMapping, POLSTAT 0):
+        [4, 12*NSIDE^2] = I, Q, U, column density in RING order."""
+        EMIT = np.ascontiguousarray(EMIT, np.float32)
+        if EMIT.size != self.CELLS:
+            raise SocError("polmap_healpix: EMIT must hold CELLS floats")
+        obs = np.ascontiguousarray(np.asarray(INTOBS, np.float32).ravel()[:3])
+        if obs.size != 3:
+            raise SocError("polmap_healpix: INTOBS must hold three floats")
+        nside = int(NSIDE)
+        MAP = np.zeros((4, 12 * max(nside, 0) ** 2), np.float32)
+        self._chk(self.lib.soc_polmap_healpix(self.h, nside, int(polred), np.float32(p0), int(interpolate), np.float32(minlos),
+                                              np.float32(maxlos), np.float32(y_shear), _f(EMIT), _f(obs), np.float32(ABS), np.float32(SCA),
+                                              np.float32(LENGTH), _f(MAP)))
         return MAP
 
     def ps_tau(self, PSPOS, DIR, ABS, SCA, LENGTH=1.0):

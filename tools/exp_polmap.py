@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Time soc_polmap (POLSTAT 0, 1, 3) against soc_map of the same size on one GPU.
+"""Time soc_polmap (POLSTAT 0, 1, 3) against soc_map of the same size on one GPU -- and, with --healpix NSIDE,
+soc_polmap_healpix (interpolate 0 and 3) against soc_map(healpix=1) of the same NSIDE, seen from near the cloud's centre.
 
     python tools/exp_polmap.py [--cases c128 oct104abu oct256] [--reps 7] [--out profiles/polmap_lines.json]
+    python tools/exp_polmap.py --healpix 256 [--cases ...] [--out profiles/hpolmap_lines.json]
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/exp_polmap.py --cases c128 oct104abu --reps 3 --out /dev/null
 
 Cases: c128 = 500 x 333 pixels of a 128^3 Cartesian cloud; oct104abu = 300 x 300 pixels of the 104^3-root octree with per-cell
@@ -54,7 +56,10 @@ def main():
     ap.add_argument("--cases", nargs="+", default=["c128", "oct104abu", "oct256"])
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "polmap_lines.json"))
+    ap.add_argument("--healpix", type=int, default=0, help="NSIDE: time the all-sky maps instead of the flat ones")
     a = ap.parse_args()
+    if a.healpix and a.out.endswith("polmap_lines.json") and not a.out.endswith("hpolmap_lines.json"):
+        a.out = os.path.join(ROOT, "profiles", "hpolmap_lines.json")
     _, ODIR, RA, DE = launch.set_observer_directions([math.radians(50.0)], [math.radians(35.0)])
     eng = Engine(0)
     try:
@@ -68,6 +73,19 @@ def main():
             eng.set_opt(np.asarray(rng.uniform(0.25, 1.0, (c.CELLS, 2)) * k["opt"], np.float32) if k["abu"] else None)
             eng.set_bfield(*synth.magnetic_field(c, seed=6))
             ABS, SCA = 0.4 * k["opt"], 0.6 * k["opt"]
+            if a.healpix:
+                obs = (0.5 * c.NX + 0.3, 0.5 * c.NY - 0.4, 0.5 * c.NZ + 0.2)
+                line = dict(case=name, cells=c.CELLS, levels=c.LEVELS, nside=a.healpix, observer=list(obs), reps=a.reps, commit=commit())
+                line["soc_map_healpix"] = timed(eng, lambda: eng.map(EMIT, ODIR[0], RA[0], DE[0], (a.healpix, -1), 1.0, centre, ABS, SCA, INTOBS=obs,
+                                                                     healpix=a.healpix), a.reps)
+                for mode in (0, 3):
+                    line["soc_polmap_healpix_i%d" % mode] = timed(eng, lambda: eng.polmap_healpix(EMIT, a.healpix, obs, ABS, SCA, interpolate=mode), a.reps)
+                    line["ratio_i%d" % mode] = line["soc_polmap_healpix_i%d" % mode]["median_ms"] / line["soc_map_healpix"]["median_ms"]
+                eng.set_bfield(None)
+                print(json.dumps(line))
+                with open(a.out, "a") as fp:
+                    fp.write(json.dumps(line) + "\n")
+                continue
             line = dict(case=name, cells=c.CELLS, levels=c.LEVELS, npix=list(k["NPIX"]), reps=a.reps, commit=commit())
             line["soc_map"] = timed(eng, lambda: eng.map(EMIT, ODIR[0], RA[0], DE[0], k["NPIX"], k["MAP_DX"], centre, ABS, SCA, save_colden=1), a.reps)
             for polstat in (0, 1, 3):
