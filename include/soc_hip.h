@@ -386,6 +386,28 @@ int soc_map(soc_ctx *ctx, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, con
             const float *RA, const float *DE, const float *CENTRE, const float *INTOBS, float ABS, float SCA,
             int save_colden, float LENGTH, float *MAP, float *SAVETAU);
 
+/* `mapping nx ny dx NF`, 2 <= NF <= 998 (ASOC.py:3442-3568: "this many frequencies per kernel call"; the reference's branch
+ * asks for a kernel_ASOC_map_X.c that it does not ship and stops): the maps of a batch of frequencies from one walk per pixel.
+ * The products are defined as those of soc_map, frequency by frequency, bit for bit.
+ * soc_map_block_max: the most frequencies one batch may hold. */
+int soc_map_block_max(void);
+
+/* stands in for the EMITX upload of ASOC.py:3520-3545: one batch of nf frequencies into device memory the handle owns, where it
+ * stays for any number of soc_map_block calls (the directions of a run).  EMITX[CELLS][nf] is the emission, cell-major;
+ * ABSX[nf] and SCAX[nf] the scalar opacities; OPTX, when not NULL, [CELLS][nf][2] per-cell opacities (absorption,
+ * scattering) that are used instead -- the per-cell OPT of soc_set_opt* plays no part in soc_map_block.  nf = 0 frees the
+ * batch; soc_set_grid with another cell count drops it.  nf < 0 or nf > soc_map_block_max() is SOC_ERR_ARG. */
+int soc_map_set_block(soc_ctx *ctx, int nf, const float *EMITX, const float *ABSX, const float *SCAX, const float *OPTX);
+
+/* stands in for the kernel_map_X launch + copies of ASOC.py:3546-3568: the maps of the resident batch for one view, with the
+ * arguments of soc_map (healpix, NPIX_X, NPIX_Y, MAP_DX, DIR, RA, DE, CENTRE, INTOBS, LENGTH) and its switches
+ * (soc_set_map_threshold, soc_set_map_interpolation, soc_set_map_roi).  MAPX[nf][npix] and TAUX[nf][npix] get, plane by
+ * plane, what soc_map gives as MAP and (save_colden = 0) SAVETAU for that frequency; COLDEN[npix] what it gives as SAVETAU
+ * with save_colden = 1.  Without a resident batch: SOC_ERR_ARG. */
+int soc_map_block(soc_ctx *ctx, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const float *DIR, const float *RA,
+                  const float *DE, const float *CENTRE, const float *INTOBS, float LENGTH, float *MAPX, float *TAUX,
+                  float *COLDEN);
+
 /* replaces the Bx_buf, By_buf, Bz_buf uploads of ASOC.py:3722-3727: the magnetic field of the polarisation maps, CELLS
  * floats per component in the order of the cloud file (all cells, parents included).  The device keeps one 16-byte record
  * (Bx, By, Bz, pad) per cell.  A polarisation reduction factor is encoded in the length of the vectors by the caller

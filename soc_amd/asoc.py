@@ -79,9 +79,13 @@ def _check_supported(USER, NDUST, WITH_MSF, engine=None):
             bad.append("polmap together with libmaps (ASOC.py:3666-3667 stops there as well)")
     elif len(getattr(USER, "file_polred", "")) > 0:
         bad.append("polred without polmap (the factor is encoded in the magnetic field of a polarisation map)")
-    if USER.FAST_MAP >= 2:
+    # `mapping nx ny dx NF`, 2 <= NF <= 998 (ASOC.py:3442-3568: NF frequencies per kernel call): the maps of the plain path, NF
+    # frequencies per walk, on an engine that has the kernel (write_maps, _map_blocks)
+    if USER.FAST_MAP >= 999:
+        bad.append("mapping with a fourth argument >= 999 (one map per hierarchy level, kernel_ASOC_map_H.c)")
+    elif USER.FAST_MAP >= 2 and not (hasattr(engine, "map_block") and hasattr(engine, "set_map_block")):
         bad.append("mapping with a fourth argument >= 2 (FAST_MAP 2..998: kernel_ASOC_map_X.c, all frequencies per launch -- the reference's "
-                   "own branch stops at ASOC.py:3553, a list compared with a float; >= 999: one map per hierarchy level, kernel_ASOC_map_H.c)")
+                   "own branch stops at ASOC.py:3553, a list compared with a float): this engine has no batch map kernel (map_block, set_map_block)")
     if USER.MAP_INTERPOLATION > 2 or USER.MAP_INTERPOLATION < 0:
         bad.append("mapint other than 0, 1, 2 (kernel_ASOC_map.c:656-810 knows those: a larger value leaves Adens, Aemit ... unset there)")
     if len(USER.kernel_defs.strip()) > 0:
@@ -804,6 +808,8 @@ class AbsorptionRun:
                 fp = open("map_dir_%02d.bin" % idir, "wb")
                 np.asarray([U.NPIX[0], U.NPIX[1]], np.int32).tofile(fp)
                 fps.append(fp)
+        # what is computed: (IFREQ, save_spe, save_tau, save_colden) in ascending frequency
+        sel = []
         first_freq = True
         for IFREQ in range(NFREQ):
             FREQ = float(FFREQ[IFREQ])
@@ -821,30 +827,48 @@ class AbsorptionRun:
                 save_spe = False
             if not save_spe and not save_tau and not save_colden:
                 continue
-            ABS, SCA = self._optical_for(IFREQ)
-            EMIT = np.asarray(KK * FREQ * EMITTED[:, IFREQ - I1], np.float32) if save_spe else np.zeros(c.CELLS, np.float32)
-            um = launch.C_LIGHT / FREQ * 1.0e4
+            sel.append((IFREQ, save_spe, save_tau, save_colden))
+
+        def emission(IFREQ, save_spe):
+            return np.asarray(KK * float(FFREQ[IFREQ]) * EMITTED[:, IFREQ - I1], np.float32) if save_spe else np.zeros(c.CELLS, np.float32)
+
+        def write(IFREQ, idir, MAP, TAU, save_spe, save_tau, save_colden):
+            """the files of one frequency and direction; TAU: the optical depth, or with save_colden the column density"""
+            if self.rank != 0:
+                return
+            um = launch.C_LIGHT / float(FFREQ[IFREQ]) * 1.0e4
             ums = '%.0f' % um if um > 20.0 else ('%.1f' % um if um > 2.0 else '%.2f' % um)
-            for idir in range(NDIR):
-                MAP, TAU = e.map(EMIT, ODIR[idir], RA[idir], DE[idir], U.NPIX, U.MAP_DX, centre, ABS, SCA,
-                                 INTOBS=U.INTOBS, save_colden=save_colden, LENGTH=LENGTH_f)
-                if self.rank != 0:
-                    continue
-                suffix = '_dir%d' % idir if NDIR > 1 else ''
-                tail = '' if NDIR == 1 else '_%03d' % idir
-                if save_spe:
-                    if using_fits:                                  # :3143-3148
-                        files.write_fits("%s_%s%s.fits" % (U.FITS_PREFIX, ums, tail), MAP, U.FITS_RA, U.FITS_DE, pix)
-                    else:
-                        np.asarray(MAP, np.float32).tofile(fps[idir])
-                if save_colden:                                     # always a FITS image in the reference (:3152-3159)
-                    files.write_fits('%s_colden%s%s.fits' % (U.file_savetau, suffix, tail), TAU, U.FITS_RA, U.FITS_DE, pix)
-                if save_tau:                                        # :3160-3171
-                    name = '%s_tau_%s%s%s' % (U.file_savetau, ums, suffix, tail)
-                    if using_fits:
-                        files.write_fits(name + '.fits', TAU, U.FITS_RA, U.FITS_DE, pix)
-                    else:
-                        np.asarray(TAU, np.float32).tofile(name + '.bin')
+            suffix = '_dir%d' % idir if NDIR > 1 else ''
+            tail = '' if NDIR == 1 else '_%03d' % idir
+            if save_spe:
+                if using_fits:                                  # :3143-3148
+                    files.write_fits("%s_%s%s.fits" % (U.FITS_PREFIX, ums, tail), MAP, U.FITS_RA, U.FITS_DE, pix)
+                else:
+                    np.asarray(MAP, np.float32).tofile(fps[idir])
+            if save_colden:                                     # always a FITS image in the reference (:3152-3159)
+                files.write_fits('%s_colden%s%s.fits' % (U.file_savetau, suffix, tail), TAU, U.FITS_RA, U.FITS_DE, pix)
+            if save_tau:                                        # :3160-3171
+                name = '%s_tau_%s%s%s' % (U.file_savetau, ums, suffix, tail)
+                if using_fits:
+                    files.write_fits(name + '.fits', TAU, U.FITS_RA, U.FITS_DE, pix)
+                else:
+                    np.asarray(TAU, np.float32).tofile(name + '.bin')
+
+        if 2 <= U.FAST_MAP <= 998:
+            # `mapping nx ny dx NF`: the same maps, up to NF frequencies per walk along the lines of sight
+            views = [(ODIR[idir], RA[idir], DE[idir]) for idir in range(NDIR)]
+            for batch, planes in self._map_blocks(sel, emission, views, centre, LENGTH_f):
+                for idir, (MAPX, TAUX, COLDEN) in enumerate(planes):
+                    for k, (IFREQ, save_spe, save_tau, save_colden) in enumerate(batch):
+                        write(IFREQ, idir, MAPX[k], COLDEN if save_colden else TAUX[k], save_spe, save_tau, save_colden)
+        else:
+            for IFREQ, save_spe, save_tau, save_colden in sel:
+                ABS, SCA = self._optical_for(IFREQ)
+                EMIT = emission(IFREQ, save_spe)
+                for idir in range(NDIR):
+                    MAP, TAU = e.map(EMIT, ODIR[idir], RA[idir], DE[idir], U.NPIX, U.MAP_DX, centre, ABS, SCA,
+                                     INTOBS=U.INTOBS, save_colden=save_colden, LENGTH=LENGTH_f)
+                    write(IFREQ, idir, MAP, TAU, save_spe, save_tau, save_colden)
         for fp in fps:
             fp.close()
 
@@ -1012,16 +1036,50 @@ class AbsorptionRun:
             fp = open("map_dir_%02d_H.bin" % 0, "wb")              # NDIR = 1 for Healpix maps (ASOC.py:2917)
             np.asarray([U.NPIX[0], U.NPIX[1]], np.int32).tofile(fp)
             np.asarray([len(sel), c.LEVELS], np.int32).tofile(fp)
-        for IFREQ in sel:
-            FREQ = float(FFREQ[IFREQ])
-            ABS, SCA = self._optical_for(IFREQ)
-            EMIT = np.asarray(EMITTED[:, IFREQ - I1] * np.float32(KK) * np.float32(FREQ), np.float32)    # :3283
-            MAP, _ = e.map(EMIT, ODIR[0], RA[0], DE[0], U.NPIX, U.MAP_DX, centre, ABS, SCA, INTOBS=U.INTOBS, save_colden=0,
-                           LENGTH=LENGTH_f, healpix=NSIDE)
-            if fp:
-                np.asarray(MAP, np.float32).tofile(fp)
+
+        def emission(IFREQ, save_spe=True):
+            return np.asarray(EMITTED[:, IFREQ - I1] * np.float32(KK) * np.float32(float(FFREQ[IFREQ])), np.float32)    # :3283
+
+        if 2 <= U.FAST_MAP <= 998:                                 # `mapping NSIDE -1 dx NF`: NF frequencies per walk
+            for batch, planes in self._map_blocks([(i, True, 0, 0) for i in sel], emission, [(ODIR[0], RA[0], DE[0])], centre, LENGTH_f,
+                                                  healpix=NSIDE):
+                for k in range(len(batch)):
+                    if fp:
+                        np.asarray(planes[0][0][k], np.float32).tofile(fp)
+        else:
+            for IFREQ in sel:
+                ABS, SCA = self._optical_for(IFREQ)
+                MAP, _ = e.map(emission(IFREQ), ODIR[0], RA[0], DE[0], U.NPIX, U.MAP_DX, centre, ABS, SCA, INTOBS=U.INTOBS, save_colden=0,
+                               LENGTH=LENGTH_f, healpix=NSIDE)
+                if fp:
+                    np.asarray(MAP, np.float32).tofile(fp)
         if fp:
             fp.close()
+
+    def _map_blocks(self, sel, emission, views, centre, LENGTH_f, healpix=0):
+        """`mapping nx ny dx NF` (2 <= NF <= 998; ASOC.py:3442-3568): the frequencies of sel = [(IFREQ, save_spe, save_tau,
+        save_colden)] in batches of at most min(NF, engine.map_block_max).  A batch is uploaded once -- emission(IFREQ, save_spe)
+        as the columns of EMITX[CELLS, nf], the opacities _optical_for sets for the plain path (with abundances the per-cell
+        ones it builds, read back into OPTX[CELLS, nf, 2]) -- and mapped for every view = (DIR, RA, DE).  Yields (batch,
+        [(MAPX, TAUX, COLDEN) per view])."""
+        U, e, c = self.U, self.eng, self.cloud
+        nb = max(1, min(int(U.FAST_MAP), int(e.map_block_max)))
+        for b0 in range(0, len(sel), nb):
+            batch = sel[b0:b0 + nb]
+            EMITX = np.zeros((c.CELLS, len(batch)), np.float32)
+            ABSX, SCAX = np.zeros(len(batch), np.float32), np.zeros(len(batch), np.float32)
+            OPTX = np.zeros((c.CELLS, len(batch), 2), np.float32) if self.WITH_ABU else None
+            for k, (IFREQ, save_spe, _, _) in enumerate(batch):
+                ABSX[k], SCAX[k] = self._optical_for(IFREQ)
+                if OPTX is not None:
+                    OPTX[:, k, :] = np.asarray(e.read_opt(), np.float32).reshape(c.CELLS, 2)
+                if save_spe:
+                    EMITX[:, k] = emission(IFREQ, save_spe)
+            e.set_map_block(EMITX, ABSX, SCAX, OPTX)
+            del EMITX, OPTX
+            yield batch, [e.map_block(d, ra, de, U.NPIX, U.MAP_DX, centre, INTOBS=U.INTOBS, LENGTH=LENGTH_f, healpix=healpix)
+                          for d, ra, de in views]
+        e.set_map_block(None)
 
     def _bcast_seed(self, seed):
         t = self.comm.torch.tensor([seed], dtype=self.comm.torch.float64,

@@ -115,6 +115,39 @@ int soc_emission(soc_ctx *c, int nfreq, const float *FREQ, const float *FABS, fl
 // map making (ASOC.py:2924-3177 -> kernel_ASOC_map.c Mapping / HealpixMapping)
 // ------------------------------------------------------------------------------------
 
+// the view of soc_map and soc_map_block: their shared arguments checked (who: the caller's name for the message) ...
+static int check_view(soc_ctx *c, const char *who, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const float *DIR, const float *RA,
+                      const float *DE, const float *CENTRE, const float *INTOBS)
+{
+    const bool inside = INTOBS && INTOBS[0] > -1e10f;
+    if (healpix) {
+        if (NPIX_X < 1 || NPIX_X > 8192 || !inside) return fail(c, SOC_ERR_ARG, "%s: Healpix maps need NSIDE (NPIX_X) and an observer position", who);
+    } else {
+        if (NPIX_X < 1 || NPIX_Y < 1 || (int64_t)NPIX_X * NPIX_Y > 2147483647LL) return fail(c, SOC_ERR_ARG, "%s: NPIX %d x %d", who, NPIX_X, NPIX_Y);
+        if (!inside && (!DIR || !RA || !DE || !CENTRE || !(MAP_DX > 0.0f))) return fail(c, SOC_ERR_ARG, "%s: DIR, RA, DE, CENTRE and MAP_DX > 0 are needed", who);
+    }
+    return SOC_OK;
+}
+
+// ... and written into the launch arguments, with the handle's switches (V: zeroed by the caller)
+static void fill_view(const soc_ctx *c, SocMapView &V, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const float *DIR, const float *RA,
+                      const float *DE, const float *CENTRE, const float *INTOBS, float LENGTH)
+{
+    const bool inside = INTOBS && INTOBS[0] > -1e10f;
+    V.mode = healpix ? 1 : 0;
+    V.NPIX_X = NPIX_X;  V.NPIX_Y = healpix ? 1 : NPIX_Y;
+    V.LEVEL_THRESHOLD = c->map_level_threshold;
+    V.MAPINT = healpix ? 0 : c->map_interpolation;
+    V.ROI_MAP = c->map_roi_on;
+    for (int k = 0; k < 6; k++) V.ROI[k] = c->map_roi[k];
+    V.MAP_DX = MAP_DX;  V.LENGTH = LENGTH;
+    for (int k = 0; k < 3; k++) {
+        V.DIR[k] = DIR ? DIR[k] : 0.0f;  V.RA[k] = RA ? RA[k] : 0.0f;  V.DE[k] = DE ? DE[k] : 0.0f;
+        V.CENTRE[k] = CENTRE ? CENTRE[k] : 0.0f;
+        V.INTOBS[k] = inside ? INTOBS[k] : (k == 0 ? -1.0e12f : 0.0f);
+    }
+}
+
 int soc_map(soc_ctx *c, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const float *EMIT, const float *DIR, const float *RA,
             const float *DE, const float *CENTRE, const float *INTOBS, float ABS, float SCA, int save_colden, float LENGTH,
             float *MAP, float *SAVETAU)
@@ -123,13 +156,7 @@ int soc_map(soc_ctx *c, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const
     FLUSH(c);
     if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_map: call soc_set_grid first");
     if (!EMIT || !MAP || !SAVETAU) return fail(c, SOC_ERR_ARG, "soc_map: EMIT, MAP and SAVETAU are needed");
-    const bool inside = INTOBS && INTOBS[0] > -1e10f;
-    if (healpix) {
-        if (NPIX_X < 1 || NPIX_X > 8192 || !inside) return fail(c, SOC_ERR_ARG, "soc_map: Healpix maps need NSIDE (NPIX_X) and an observer position");
-    } else {
-        if (NPIX_X < 1 || NPIX_Y < 1 || (int64_t)NPIX_X * NPIX_Y > 2147483647LL) return fail(c, SOC_ERR_ARG, "soc_map: NPIX %d x %d", NPIX_X, NPIX_Y);
-        if (!inside && (!DIR || !RA || !DE || !CENTRE || !(MAP_DX > 0.0f))) return fail(c, SOC_ERR_ARG, "soc_map: DIR, RA, DE, CENTRE and MAP_DX > 0 are needed");
-    }
+    if (int r = check_view(c, "soc_map", healpix, NPIX_X, NPIX_Y, MAP_DX, DIR, RA, DE, CENTRE, INTOBS)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t npix = healpix ? (size_t)12 * NPIX_X * NPIX_X : (size_t)NPIX_X * NPIX_Y;
     const size_t cells = (size_t)c->G.CELLS;
@@ -138,23 +165,76 @@ int soc_map(soc_ctx *c, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const
     HIPCHK(c, c->dMapTau.reserve(npix, c->stream));
     SocMapArgs A;
     memset(&A, 0, sizeof A);
-    A.mode = healpix ? 1 : 0;
-    A.NPIX_X = NPIX_X;  A.NPIX_Y = healpix ? 1 : NPIX_Y;  A.SAVE_COLDEN = save_colden;
-    A.LEVEL_THRESHOLD = c->map_level_threshold;
-    A.MAPINT = healpix ? 0 : c->map_interpolation;
-    A.ROI_MAP = c->map_roi_on;
-    for (int k = 0; k < 6; k++) A.ROI[k] = c->map_roi[k];
-    A.MAP_DX = MAP_DX;  A.ABS = ABS;  A.SCA = SCA;  A.LENGTH = LENGTH;
-    for (int k = 0; k < 3; k++) {
-        A.DIR[k] = DIR ? DIR[k] : 0.0f;  A.RA[k] = RA ? RA[k] : 0.0f;  A.DE[k] = DE ? DE[k] : 0.0f;
-        A.CENTRE[k] = CENTRE ? CENTRE[k] : 0.0f;
-        A.INTOBS[k] = inside ? INTOBS[k] : (k == 0 ? -1.0e12f : 0.0f);
-    }
+    fill_view(c, A, healpix, NPIX_X, NPIX_Y, MAP_DX, DIR, RA, DE, CENTRE, INTOBS, LENGTH);
+    A.SAVE_COLDEN = save_colden;  A.ABS = ABS;  A.SCA = SCA;
     A.EMIT = c->dMapEmit;  A.OPT = c->dOPT;  A.MAP = c->dMap;  A.SAVETAU = c->dMapTau;
     HIPCHK(c, hipMemcpyAsync(c->dMapEmit, EMIT, cells * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, soc_launch_map(c->G, A, c->dOPT != nullptr, c->stream));
     HIPCHK(c, hipMemcpyAsync(MAP, c->dMap, npix * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(SAVETAU, c->dMapTau, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
+// maps of a batch of frequencies (`mapping nx ny dx NF`, ASOC.py:3442-3568 -> the kernel_ASOC_map_X.c the reference lacks)
+int soc_map_block_max(void) { return SOC_MAPX_MAX; }
+
+int soc_map_set_block(soc_ctx *c, int nf, const float *EMITX, const float *ABSX, const float *SCAX, const float *OPTX)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (nf == 0) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->dMapXEmit.release();  c->dMapXOpt.release();  c->dMapXOpa.release();  c->dMapXOut.release();
+        c->mapx_nf = 0;
+        return SOC_OK;
+    }
+    if (nf < 0 || nf > SOC_MAPX_MAX) return fail(c, SOC_ERR_ARG, "soc_map_set_block: %d frequencies in a batch (1..%d; 0 frees it)", nf, SOC_MAPX_MAX);
+    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_map_set_block: call soc_set_grid first");
+    if (!EMITX || !ABSX || !SCAX) return fail(c, SOC_ERR_ARG, "soc_map_set_block: EMITX, ABSX and SCAX are needed");
+    const size_t n = (size_t)c->G.CELLS * (size_t)nf;
+    c->mapx_nf = 0;                                           // (a batch that may be half written is none)
+    HIPCHK(c, c->dMapXEmit.reserve(n, c->stream));
+    HIPCHK(c, c->dMapXOpa.reserve((size_t)2 * SOC_MAPX_MAX, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dMapXEmit, EMITX, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dMapXOpa, ABSX, (size_t)nf * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dMapXOpa + nf, SCAX, (size_t)nf * 4, hipMemcpyHostToDevice, c->stream));
+    if (OPTX) {
+        HIPCHK(c, c->dMapXOpt.reserve(n, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->dMapXOpt, OPTX, n * 8, hipMemcpyHostToDevice, c->stream));
+    } else if (c->dMapXOpt) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->dMapXOpt.release();
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mapx_nf = nf;
+    return SOC_OK;
+}
+
+int soc_map_block(soc_ctx *c, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const float *DIR, const float *RA, const float *DE,
+                  const float *CENTRE, const float *INTOBS, float LENGTH, float *MAPX, float *TAUX, float *COLDEN)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_map_block: call soc_set_grid first");
+    if (c->mapx_nf < 1) return fail(c, SOC_ERR_ARG, "soc_map_block: no batch is resident; soc_map_set_block with 1..%d frequencies first", SOC_MAPX_MAX);
+    if (!MAPX || !TAUX || !COLDEN) return fail(c, SOC_ERR_ARG, "soc_map_block: MAPX, TAUX and COLDEN are needed");
+    if (int r = check_view(c, "soc_map_block", healpix, NPIX_X, NPIX_Y, MAP_DX, DIR, RA, DE, CENTRE, INTOBS)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = healpix ? (size_t)12 * NPIX_X * NPIX_X : (size_t)NPIX_X * NPIX_Y;
+    const size_t nf = (size_t)c->mapx_nf;
+    HIPCHK(c, c->dMapXOut.reserve((2 * nf + 1) * npix, c->stream));
+    SocMapXArgs A;
+    memset(&A, 0, sizeof A);
+    fill_view(c, A, healpix, NPIX_X, NPIX_Y, MAP_DX, DIR, RA, DE, CENTRE, INTOBS, LENGTH);
+    A.nf = c->mapx_nf;
+    A.EMIT = c->dMapXEmit;  A.ABS = c->dMapXOpa;  A.SCA = c->dMapXOpa + nf;  A.OPT = c->dMapXOpt;
+    A.MAP = c->dMapXOut;  A.TAU = c->dMapXOut + nf * npix;  A.COLDEN = c->dMapXOut + 2 * nf * npix;
+    HIPCHK(c, soc_launch_mapx(c->G, A, c->stream));
+    HIPCHK(c, hipMemcpyAsync(MAPX, A.MAP, nf * npix * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(TAUX, A.TAU, nf * npix * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(COLDEN, A.COLDEN, npix * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SOC_OK;
 }

@@ -132,19 +132,36 @@ hipError_t soc_launch_opt(int cells, int ndust, int single, const float *ABU, co
 hipError_t soc_launch_opt_half(int cells, float2 *OPT, hipStream_t st);
 
 // map making (soc_map.hip): one launch of Mapping / HealpixMapping (kernel_ASOC_map.c:496-516, 890-910)
-struct SocMapArgs {
+// what fixes the lines of sight of a map, whatever is integrated along them
+struct SocMapView {
     int   mode;                    // 0 Mapping, 1 HealpixMapping (NSIDE = NPIX_X)
-    int   NPIX_X, NPIX_Y, SAVE_COLDEN;
+    int   NPIX_X, NPIX_Y;
     int   ROI_MAP, ROI[6];         // -D ROI_MAP: only the emission of cells inside ROI = [x0,x1,y0,y1,z0,z1] (root cells, inclusive)
     int   LEVEL_THRESHOLD;         // Mapping: no emission from levels below it (-D LEVEL_THRESHOLD, kernel_ASOC_map.c:825-834)
     int   MAPINT;                  // Mapping: -D MAP_INTERPOLATION 0 | 1 | 2 (kernel_ASOC_map.c:656-810)
-    float MAP_DX, ABS, SCA, LENGTH;
+    float MAP_DX, LENGTH;
     float DIR[3], RA[3], DE[3], CENTRE[3], INTOBS[3];
+};
+struct SocMapArgs : SocMapView {
+    int   SAVE_COLDEN;
+    float ABS, SCA;
     const float  *EMIT;
     const float2 *OPT;
     float *MAP, *SAVETAU;
 };
 hipError_t soc_launch_map(const SocGrid &G, const SocMapArgs &A, bool abu, hipStream_t st);
+// the maps of a batch of frequencies from one walk per pixel (soc_map.hip: soc_mapx_kernel; the `mapping nx ny dx NF` of
+// ASOC.py:3442-3568, whose kernel_ASOC_map_X.c the reference does not ship): nf <= SOC_MAPX_MAX frequencies, cell-major inputs
+#define SOC_MAPX_MAX 32
+struct SocMapXArgs : SocMapView {
+    int   nf;
+    const float  *EMIT;            // [CELLS][nf]
+    const float  *ABS, *SCA;       // [nf]: the scalar opacities (OPT == nullptr)
+    const float2 *OPT;             // [CELLS][nf] per-cell opacities, or nullptr
+    float *MAP, *TAU;              // [nf][npix]
+    float *COLDEN;                 // [npix] column density x LENGTH
+};
+hipError_t soc_launch_mapx(const SocGrid &G, const SocMapXArgs &A, hipStream_t st);
 // polarisation maps (soc_map.hip): one launch of PolMapping (kernel_ASOC_map.c:974-994, :1164-1184, :1600-1620)
 struct SocPolArgs {
     int   polstat;                 // -D POLSTAT: 0 = I, Q, U, column density; 1 = rT, rI, jT, jI; 3 = <B>, <B_LOS>, <B_POS>, tau

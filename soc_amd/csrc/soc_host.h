@@ -143,6 +143,11 @@ struct soc_ctx {
     bool   have_T = false;
     // map making (soc_map.hip)
     DevBuf<float>  dMapEmit, dMap, dMapTau;
+    // the resident batch of soc_map_set_block: emission [CELLS][mapx_nf], ABS | SCA [2 * mapx_nf], per-cell opacities (or none);
+    // the planes of soc_map_block: MAPX | TAUX | COLDEN
+    DevBuf<float>  dMapXEmit, dMapXOpa, dMapXOut;
+    DevBuf<float2> dMapXOpt;
+    int     mapx_nf = 0;               // 0: no batch
     DevBuf<float4> dBfield;            // magnetic field, one (Bx, By, Bz, pad) per cell (soc_set_bfield)
     DevBuf<float>  dPolMap;            // the four planes of a polarisation map
     // A2E

@@ -106,12 +106,13 @@ __device__ __forceinline__ bool soc_map_inroi(const SocGrid &G, const int *sOFF,
 }
 
 // One neighbour of the MAP_INTERPOLATION block (kernel_ASOC_map.c:716-731, :771-788): from the middle of the step the
-// distance (cell units) to the next cell along +V, else along -V (V stays flipped), else "none" (0.5, nothing to blend)
+// distance (cell units) to the next cell along +V, else along -V (V stays flipped), else "none" (0.5, nothing to blend).
+// ncell is that cell's place in the per-cell arrays, -1 for "none": its emission then counts as 0.
 template <bool OCT, bool DBL>
-__device__ __forceinline__ void soc_map_neighbour(const SocGrid &G, const int *sOFF, const float *EMIT, float p0x, float p0y, float p0z,
+__device__ __forceinline__ void soc_map_neighbour(const SocGrid &G, const int *sOFF, float p0x, float p0y, float p0z,
                                                   float tx, float ty, float tz, float w, int level0, int ind0, float K,
                                                   float &vx, float &vy, float &vz, float lim, bool second_try_unscaled,
-                                                  float &dist, float &ndens, float &nemit)
+                                                  float &dist, float &ndens, int &ncell)
 {
     for (int attempt = 0; attempt < 2; attempt++) {
         int   slevel = level0, sind = ind0;
@@ -120,23 +121,20 @@ __device__ __forceinline__ void soc_map_neighbour(const SocGrid &G, const int *s
         float mx = p0x + w * tx, my = p0y + w * ty, mz = p0z + w * tz;
         float a = soc_map_getstep<OCT, DBL>(G, sOFF, mx, my, mz, vx, vy, vz, slevel, sind, nd);
         if (!(attempt && second_try_unscaled)) a = a / K;                 // (:736 has no "b /= K" in the MAP_INTERPOLATION==2 block)
-        if ((a <= lim) && (sind >= 0)) { dist = a;  ndens = nd;  nemit = EMIT[sOFF[slevel] + sind];  return; }
+        if ((a <= lim) && (sind >= 0)) { dist = a;  ndens = nd;  ncell = sOFF[slevel] + sind;  return; }
     }
-    dist = 0.5f;  ndens = 0.0f;  nemit = 0.0f;
+    dist = 0.5f;  ndens = 0.0f;  ncell = -1;
 }
 
-template <bool OCT, bool DBL, bool ABU>
-__global__ __launch_bounds__(256) void soc_map_kernel(const SocGrid G, const SocMapArgs A)
+// ------------------------------------------------------------------------------------
+// One line of sight of Mapping / HealpixMapping, without what is integrated along it: where pixel `id` enters the model, and one
+// step of the walk.  soc_map_kernel (one frequency) and soc_mapx_kernel (a batch of frequencies) are these two functions plus
+// soc_map_blend and soc_map_add per frequency -- the same operations in the same order, so the same bits.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ void soc_map_entry(const SocGrid &G, const SocMapView &A, int id, float &px, float &py, float &pz,
+                                              float &tx, float &ty, float &tz)
 {
-    __shared__ int sOFF[SOC_MAXL];
-    if (threadIdx.x < SOC_MAXL) sOFF[threadIdx.x] = G.OFF[threadIdx.x];
-    __syncthreads();
-    const int npix = A.mode ? 12 * A.NPIX_X * A.NPIX_X : A.NPIX_X * A.NPIX_Y;
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= npix) return;
     const int NX = G.NX, NY = G.NY, NZ = G.NZ;
-    float TAU = 0.0f, PHOTONS = 0.0f, colden = 0.0f;
-    float px, py, pz, tx, ty, tz;
     if (A.mode) {
         // HealpixMapping: all-sky map seen from INTOBS (:913-925)
         float phi, theta, st, ct, sp, cp;
@@ -206,75 +204,190 @@ __global__ __launch_bounds__(256) void soc_map_kernel(const SocGrid G, const Soc
             if (soc_fabsf(tz) < 1.0e-5f) tz = 1.0e-5f;
         }
     }
+}
+
+// the two directions across the ray along which MAP_INTERPOLATION looks for neighbours (:664-682)
+struct SocMapCross { float ax, ay, az, bx, by, bz; };
+__device__ __forceinline__ SocMapCross soc_map_cross(float tx, float ty, float tz)
+{
+    SocMapCross X;
+    if (soc_fabsf(tx) > soc_fabsf(ty)) {
+        if (soc_fabsf(tz) > soc_fabsf(tx)) { X.ax = 0.0005f;  X.ay = 1.0f;  X.az = -ty / tz; }
+        else                               { X.ax = -tz / tx;  X.ay = 0.0005f;  X.az = 1.0f; }
+    } else {
+        if (soc_fabsf(tz) > soc_fabsf(ty)) { X.ax = 0.0005f;  X.ay = 1.0f;  X.az = -ty / tz; }
+        else                               { X.ax = 1.0f;  X.ay = -tx / ty;  X.az = 0.0005f; }
+    }
+    soc_normalize(X.ax, X.ay, X.az);
+    X.bx = ty * X.az - tz * X.ay;
+    X.by = tz * X.ax - tx * X.az;
+    X.bz = tx * X.ay - ty * X.ax;
+    soc_normalize(X.bx, X.by, X.bz);
+    return X;
+}
+
+// One step: the cell it crosses (oind in the per-cell arrays, on level olevel), its length sx and the density d0 -- with
+// MAP_INTERPOLATION already blended --, whether the cell's emission counts (`roimap`, `threshold`), and for the blend of the
+// emission the two neighbour cells with the weights of soc_map_blend.
+struct SocMapStep {
+    int   oind, olevel, na, nb;
+    float sx, d0, wa, wb, wc;
+    bool  emits;
+};
+
+// (MAP_INTERPOLATION == 2: :746-751; == 1: :806-808) of the cell's own value and its neighbours'
+__device__ __forceinline__ float soc_map_blend(int MI, const SocMapStep &S, float own, float A, float B)
+{
+    if (MI == 2) return S.wa * A + S.wb * B + S.wc * own;
+    return S.wc * own + S.wa * A + S.wb * B;
+}
+
+template <bool OCT, bool DBL>
+__device__ __forceinline__ SocMapStep soc_map_step(const SocGrid &G, const int *sOFF, const SocMapView &A, SocMapCross &X,
+                                                   float &px, float &py, float &pz, float tx, float ty, float tz,
+                                                   int &level, int &ind, float &dens)
+{
+    SocMapStep S;
+    const int MI = A.MAPINT;
+    S.oind = sOFF[level] + ind;
+    S.olevel = level;
+    S.na = -1;  S.nb = -1;
+    S.wa = 0.0f;  S.wb = 0.0f;  S.wc = 1.0f;
+    const float p0x = px, p0y = py, p0z = pz;
+    const int   ind0 = ind;
+    S.d0 = dens;
+    S.sx = soc_map_getstep<OCT, DBL>(G, sOFF, px, py, pz, tx, ty, tz, level, ind, dens);
+    if (MI > 0) {
+        const float K = soc_scale_down(1.0f, S.olevel);               // local -> root-grid length
+        float a, b, Ad, Bd;
+        if (MI == 2) {                                                // steps of at most 0.22 cells (:709-715)
+            a = 0.22f * K;
+            if (S.sx > a) {
+                S.sx = a;
+                px = p0x + 0.22f * tx;  py = p0y + 0.22f * ty;  pz = p0z + 0.22f * tz;
+                ind = ind0;  level = S.olevel;
+                if (DBL) soc_map_index<OCT, double>(G, sOFF, px, py, pz, level, ind, dens);
+                else     soc_map_index<OCT, float>(G, sOFF, px, py, pz, level, ind, dens);
+            }
+        }
+        const float w = 0.5f * S.sx / K;
+        const float lim = (MI == 2) ? 0.52f : 0.502f;
+        soc_map_neighbour<OCT, DBL>(G, sOFF, p0x, p0y, p0z, tx, ty, tz, w, S.olevel, ind0, K, X.ax, X.ay, X.az, lim, false, a, Ad, S.na);
+        soc_map_neighbour<OCT, DBL>(G, sOFF, p0x, p0y, p0z, tx, ty, tz, w, S.olevel, ind0, K, X.bx, X.by, X.bz, lim, MI == 2, b, Bd, S.nb);
+        if (MI == 2) {                                                // :746-751
+            a = soc_clampf(a, 0.0f, 0.51f);
+            b = soc_clampf(b, 0.0f, 0.51f);
+            S.wa = 0.5f - a;  S.wb = 0.5f - b;  S.wc = a + b;
+        } else {                                                      // :806-808
+            S.wa = 0.5f - a;  S.wb = 0.5f - b;
+            S.wc = 1.0f - S.wa - S.wb;
+        }
+        S.d0 = soc_map_blend(MI, S, S.d0, Ad, Bd);
+    }
+    if (A.ROI_MAP && !soc_map_inroi<OCT>(G, sOFF, A.ROI, S.olevel, S.oind - sOFF[S.olevel])) S.emits = false;   // `roimap`: cells outside ROI do not emit
+    else if (!A.mode && (S.olevel < A.LEVEL_THRESHOLD)) S.emits = false;  // `threshold`: coarse levels do not emit (they still absorb); Mapping only
+    else S.emits = true;
+    return S;
+}
+
+// what one frequency adds on a step (:825-846, :950-955): emission seen through the optical depth in front of it, then that depth grows
+__device__ __forceinline__ void soc_map_add(const SocMapStep &S, float emit, float DTAU, float &TAU, float &PHOTONS)
+{
+    if (!S.emits) { }
+    else if (DTAU < 1.0e-3f) PHOTONS += soc_expf(-TAU) * (1.0f - 0.5f * DTAU) * S.sx * emit * S.d0;
+    else                     PHOTONS += soc_expf(-TAU) * ((1.0f - soc_expf(-DTAU)) / DTAU) * S.sx * emit * S.d0;
+    TAU += DTAU;
+}
+
+template <bool OCT, bool DBL, bool ABU>
+__global__ __launch_bounds__(256) void soc_map_kernel(const SocGrid G, const SocMapArgs A)
+{
+    __shared__ int sOFF[SOC_MAXL];
+    if (threadIdx.x < SOC_MAXL) sOFF[threadIdx.x] = G.OFF[threadIdx.x];
+    __syncthreads();
+    const int npix = A.mode ? 12 * A.NPIX_X * A.NPIX_X : A.NPIX_X * A.NPIX_Y;
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= npix) return;
+    float TAU = 0.0f, PHOTONS = 0.0f, colden = 0.0f;
+    float px, py, pz, tx, ty, tz;
+    soc_map_entry(G, A, id, px, py, pz, tx, ty, tz);
     int   level = 0, ind = -1;
     float dens = 0.0f;
     soc_indexg<OCT>(G, sOFF, px, py, pz, level, ind, dens);
     const int MI = A.MAPINT;
-    float adx = 0.0f, ady = 0.0f, adz = 0.0f, bdx = 0.0f, bdy = 0.0f, bdz = 0.0f;
-    if (MI > 0) {                                                         // two directions across the ray (:664-682)
-        if (soc_fabsf(tx) > soc_fabsf(ty)) {
-            if (soc_fabsf(tz) > soc_fabsf(tx)) { adx = 0.0005f;  ady = 1.0f;  adz = -ty / tz; }
-            else                               { adx = -tz / tx;  ady = 0.0005f;  adz = 1.0f; }
-        } else {
-            if (soc_fabsf(tz) > soc_fabsf(ty)) { adx = 0.0005f;  ady = 1.0f;  adz = -ty / tz; }
-            else                               { adx = 1.0f;  ady = -tx / ty;  adz = 0.0005f; }
-        }
-        soc_normalize(adx, ady, adz);
-        bdx = ty * adz - tz * ady;
-        bdy = tz * adx - tx * adz;
-        bdz = tx * ady - ty * adx;
-        soc_normalize(bdx, bdy, bdz);
-    }
+    SocMapCross X = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+    if (MI > 0) X = soc_map_cross(tx, ty, tz);
     while (ind >= 0) {
-        const int   oind = sOFF[level] + ind;
-        const int   olevel = level;
-        const float p0x = px, p0y = py, p0z = pz;
-        const int   ind0 = ind;
-        float d0 = dens;
-        float sx = soc_map_getstep<OCT, DBL>(G, sOFF, px, py, pz, tx, ty, tz, level, ind, dens);
-        float emit = A.EMIT[oind];
-        if (MI > 0) {
-            const float K = soc_scale_down(1.0f, olevel);                 // local -> root-grid length
-            float a, b, Ad, Bd, Ae, Be;
-            if (MI == 2) {                                                // steps of at most 0.22 cells (:709-715)
-                a = 0.22f * K;
-                if (sx > a) {
-                    sx = a;
-                    px = p0x + 0.22f * tx;  py = p0y + 0.22f * ty;  pz = p0z + 0.22f * tz;
-                    ind = ind0;  level = olevel;
-                    if (DBL) soc_map_index<OCT, double>(G, sOFF, px, py, pz, level, ind, dens);
-                    else     soc_map_index<OCT, float>(G, sOFF, px, py, pz, level, ind, dens);
-                }
-            }
-            const float w = 0.5f * sx / K;
-            const float lim = (MI == 2) ? 0.52f : 0.502f;
-            soc_map_neighbour<OCT, DBL>(G, sOFF, A.EMIT, p0x, p0y, p0z, tx, ty, tz, w, olevel, ind0, K, adx, ady, adz, lim, false, a, Ad, Ae);
-            soc_map_neighbour<OCT, DBL>(G, sOFF, A.EMIT, p0x, p0y, p0z, tx, ty, tz, w, olevel, ind0, K, bdx, bdy, bdz, lim, MI == 2, b, Bd, Be);
-            if (MI == 2) {                                                // :746-751
-                a = soc_clampf(a, 0.0f, 0.51f);
-                b = soc_clampf(b, 0.0f, 0.51f);
-                const float c0 = 0.5f - a, c1 = 0.5f - b, c2 = a + b;
-                emit = c0 * Ae + c1 * Be + c2 * emit;
-                d0   = c0 * Ad + c1 * Bd + c2 * d0;
-            } else {                                                      // :806-808
-                a = 0.5f - a;  b = 0.5f - b;
-                const float c2 = 1.0f - a - b;
-                emit = c2 * emit + a * Ae + b * Be;
-                d0   = c2 * d0 + a * Ad + b * Bd;
-            }
-        }
+        const SocMapStep S = soc_map_step<OCT, DBL>(G, sOFF, A, X, px, py, pz, tx, ty, tz, level, ind, dens);
+        float emit = A.EMIT[S.oind];
+        if (MI > 0) emit = soc_map_blend(MI, S, emit, (S.na >= 0) ? A.EMIT[S.na] : 0.0f, (S.nb >= 0) ? A.EMIT[S.nb] : 0.0f);
         float DTAU;
-        if (ABU) { const float2 o = A.OPT[oind];  DTAU = sx * d0 * (o.x + o.y); }
-        else     DTAU = sx * d0 * (A.SCA + A.ABS);
-        if (A.ROI_MAP && !soc_map_inroi<OCT>(G, sOFF, A.ROI, olevel, oind - sOFF[olevel])) { }   // `roimap`: cells outside ROI do not emit
-        else if (!A.mode && (olevel < A.LEVEL_THRESHOLD)) { }             // `threshold`: coarse levels do not emit (they still absorb); Mapping only
-        else if (DTAU < 1.0e-3f) PHOTONS += soc_expf(-TAU) * (1.0f - 0.5f * DTAU) * sx * emit * d0;
-        else                     PHOTONS += soc_expf(-TAU) * ((1.0f - soc_expf(-DTAU)) / DTAU) * sx * emit * d0;
-        TAU += DTAU;
-        if (A.mode || (A.SAVE_COLDEN > 0)) colden += sx * d0;
+        if (ABU) { const float2 o = A.OPT[S.oind];  DTAU = S.sx * S.d0 * (o.x + o.y); }
+        else     DTAU = S.sx * S.d0 * (A.SCA + A.ABS);
+        soc_map_add(S, emit, DTAU, TAU, PHOTONS);
+        if (A.mode || (A.SAVE_COLDEN > 0)) colden += S.sx * S.d0;
     }
     A.MAP[id] = PHOTONS;
     A.SAVETAU[id] = A.SAVE_COLDEN ? (colden * A.LENGTH) : TAU;
+}
+
+// Mapping / HealpixMapping for a batch of A.nf <= KF frequencies: one walk per pixel, and per step and frequency what
+// soc_map_kernel does for its one -- plane f is, bit for bit, soc_map_kernel's map of frequency f.  (The reference names this
+// kernel_ASOC_map_X.c, ASOC.py:3442-3568, and does not ship it.)  The accumulators are registers: KF is a template argument
+// and every loop over it is unrolled, frequencies beyond A.nf are skipped by a test that is uniform over the grid.  Per-cell
+// inputs are cell-major, [CELLS][nf]: a step reads one cell's frequencies from adjacent addresses (64-bit offsets: CELLS * nf
+// passes 2^31 on production models).
+template <bool OCT, bool DBL, bool ABU, int KF>
+__global__ __launch_bounds__(256) void soc_mapx_kernel(const SocGrid G, const SocMapXArgs A)
+{
+    __shared__ int sOFF[SOC_MAXL];
+    if (threadIdx.x < SOC_MAXL) sOFF[threadIdx.x] = G.OFF[threadIdx.x];
+    __syncthreads();
+    const int npix = A.mode ? 12 * A.NPIX_X * A.NPIX_X : A.NPIX_X * A.NPIX_Y;
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= npix) return;
+    const int nf = A.nf;
+    float TAU[KF], PHOTONS[KF], OPTSUM[KF], colden = 0.0f;
+#pragma unroll
+    for (int f = 0; f < KF; f++) {
+        TAU[f] = 0.0f;  PHOTONS[f] = 0.0f;
+        OPTSUM[f] = (!ABU && (f < nf)) ? (A.SCA[f] + A.ABS[f]) : 0.0f;
+    }
+    float px, py, pz, tx, ty, tz;
+    soc_map_entry(G, A, id, px, py, pz, tx, ty, tz);
+    int   level = 0, ind = -1;
+    float dens = 0.0f;
+    soc_indexg<OCT>(G, sOFF, px, py, pz, level, ind, dens);
+    const int MI = A.MAPINT;
+    SocMapCross X = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+    if (MI > 0) X = soc_map_cross(tx, ty, tz);
+    while (ind >= 0) {
+        const SocMapStep S = soc_map_step<OCT, DBL>(G, sOFF, A, X, px, py, pz, tx, ty, tz, level, ind, dens);
+        const float  *E  = A.EMIT + (size_t)S.oind * nf;
+        const float  *Ea = A.EMIT + (size_t)((S.na >= 0) ? S.na : 0) * nf;
+        const float  *Eb = A.EMIT + (size_t)((S.nb >= 0) ? S.nb : 0) * nf;
+        const float2 *O  = ABU ? (A.OPT + (size_t)S.oind * nf) : nullptr;
+#pragma unroll
+        for (int f = 0; f < KF; f++) {
+            if (f < nf) {
+                float emit = E[f];
+                if (MI > 0) emit = soc_map_blend(MI, S, emit, (S.na >= 0) ? Ea[f] : 0.0f, (S.nb >= 0) ? Eb[f] : 0.0f);
+                float DTAU;
+                if (ABU) { const float2 o = O[f];  DTAU = S.sx * S.d0 * (o.x + o.y); }
+                else     DTAU = S.sx * S.d0 * OPTSUM[f];
+                soc_map_add(S, emit, DTAU, TAU[f], PHOTONS[f]);
+            }
+        }
+        colden += S.sx * S.d0;
+    }
+#pragma unroll
+    for (int f = 0; f < KF; f++) {
+        if (f < nf) {
+            A.MAP[(size_t)f * npix + id] = PHOTONS[f];
+            A.TAU[(size_t)f * npix + id] = TAU[f];
+        }
+    }
+    A.COLDEN[id] = colden * A.LENGTH;
 }
 
 // PSTau (kernel_ASOC_map.c:1545-1584): column density and optical depth from every point source towards the observer
@@ -732,5 +845,29 @@ hipError_t soc_launch_map(const SocGrid &G, const SocMapArgs &A, bool abu, hipSt
     if (!oct)      { if (abu) soc_map_kernel<false, false, true><<<grid, block, 0, st>>>(G, A); else soc_map_kernel<false, false, false><<<grid, block, 0, st>>>(G, A); }
     else if (!dbl) { if (abu) soc_map_kernel<true, false, true><<<grid, block, 0, st>>>(G, A);  else soc_map_kernel<true, false, false><<<grid, block, 0, st>>>(G, A); }
     else           { if (abu) soc_map_kernel<true, true, true><<<grid, block, 0, st>>>(G, A);   else soc_map_kernel<true, true, false><<<grid, block, 0, st>>>(G, A); }
+    return hipGetLastError();
+}
+
+// The widths soc_mapx_kernel is compiled for; a batch runs in the narrowest that holds it.  Registers per lane (DESIGN.md
+// section 5 has the table): the walk's own plus three per frequency, no scratch at any width up to SOC_MAPX_MAX.
+template <bool OCT, bool DBL, bool ABU>
+static void soc_mapx_dispatch(const SocGrid &G, const SocMapXArgs &A, dim3 grid, dim3 block, hipStream_t st)
+{
+    if (A.nf <= 4)       soc_mapx_kernel<OCT, DBL, ABU, 4><<<grid, block, 0, st>>>(G, A);
+    else if (A.nf <= 8)  soc_mapx_kernel<OCT, DBL, ABU, 8><<<grid, block, 0, st>>>(G, A);
+    else if (A.nf <= 16) soc_mapx_kernel<OCT, DBL, ABU, 16><<<grid, block, 0, st>>>(G, A);
+    else                 soc_mapx_kernel<OCT, DBL, ABU, SOC_MAPX_MAX><<<grid, block, 0, st>>>(G, A);
+}
+
+hipError_t soc_launch_mapx(const SocGrid &G, const SocMapXArgs &A, hipStream_t st)
+{
+    const int npix = A.mode ? 12 * A.NPIX_X * A.NPIX_X : A.NPIX_X * A.NPIX_Y;
+    if (npix <= 0) return hipSuccess;
+    if (A.nf < 1 || A.nf > SOC_MAPX_MAX) return hipErrorInvalidValue;
+    const dim3 grid((npix + 255) / 256), block(256);
+    const bool oct = G.LEVELS > 1, dbl = oct && (G.NX > 100), abu = A.OPT != nullptr;   // kernel_ASOC_map.c:297
+    if (!oct)      { if (abu) soc_mapx_dispatch<false, false, true>(G, A, grid, block, st); else soc_mapx_dispatch<false, false, false>(G, A, grid, block, st); }
+    else if (!dbl) { if (abu) soc_mapx_dispatch<true, false, true>(G, A, grid, block, st);  else soc_mapx_dispatch<true, false, false>(G, A, grid, block, st); }
+    else           { if (abu) soc_mapx_dispatch<true, true, true>(G, A, grid, block, st);   else soc_mapx_dispatch<true, true, false>(G, A, grid, block, st); }
     return hipGetLastError();
 }

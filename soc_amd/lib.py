@@ -103,6 +103,9 @@ API = {
     "soc_emission": (C.c_int, [C.c_void_p, C.c_int, _F, _F, C.c_float, C.c_float, _F]),
     "soc_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F, _F, C.c_float, C.c_float, C.c_int,
                           C.c_float, _F, _F]),
+    "soc_map_block_max": (C.c_int, []),
+    "soc_map_set_block": (C.c_int, [C.c_void_p, C.c_int, _F, _F, _F, _F]),
+    "soc_map_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F, C.c_float, _F, _F, _F]),
     "soc_set_bfield": (C.c_int, [C.c_void_p, _F, _F, _F]),
     "soc_polmap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F,
                              C.c_float, C.c_float, C.c_float, _F]),
@@ -536,6 +539,49 @@ class Engine:
                                    _f(v[3]), _f(v[4]), np.float32(ABS), np.float32(SCA), int(save_colden), np.float32(LENGTH),
                                    _f(MAP), _f(TAU)))
         return MAP, TAU
+
+    @property
+    def map_block_max(self):
+        """the most frequencies one set_map_block batch may hold (soc_map_block_max)"""
+        return int(self.lib.soc_map_block_max())
+
+    def set_map_block(self, EMITX, ABS=None, SCA=None, OPT=None):
+        """One batch of frequencies for map_block, resident on the device until the next call: EMITX[CELLS, nf] emission,
+        ABS[nf] and SCA[nf] scalar opacities, OPT[CELLS, nf, 2] per-cell opacities used instead when given (the OPT of
+        set_opt plays no part in map_block).  set_map_block(None) frees the batch."""
+        if EMITX is None:
+            self._chk(self.lib.soc_map_set_block(self.h, 0, None, None, None, None))
+            self._map_block_nf = 0
+            return
+        EMITX = np.ascontiguousarray(EMITX, np.float32)
+        if EMITX.ndim != 2 or EMITX.shape[0] != self.CELLS or EMITX.shape[1] < 1:
+            raise SocError("set_map_block: EMITX must be [CELLS, nf] with nf >= 1")
+        nf = int(EMITX.shape[1])
+        ABS = np.ascontiguousarray(ABS, np.float32).ravel()
+        SCA = np.ascontiguousarray(SCA, np.float32).ravel()
+        if ABS.size != nf or SCA.size != nf:
+            raise SocError("set_map_block: ABS and SCA must hold one value per frequency (%d)" % nf)
+        if OPT is not None:
+            OPT = np.ascontiguousarray(OPT, np.float32)
+            if OPT.shape != (self.CELLS, nf, 2):
+                raise SocError("set_map_block: OPT must be [CELLS, nf, 2]")
+        # (a refused call leaves the resident batch, and so the plane count map_block allocates for, as it was)
+        self._chk(self.lib.soc_map_set_block(self.h, nf, _f(EMITX), _f(ABS), _f(SCA), _f(OPT)))
+        self._map_block_nf = nf
+
+    def map_block(self, DIR, RA, DE, NPIX, MAP_DX, CENTRE, INTOBS=None, LENGTH=1.0, healpix=0):
+        """The maps of the resident batch for one view, from one walk per pixel (the arguments and switches of map).  Returns
+        (MAPX, TAUX, COLDEN): [nf, NPIX.y, NPIX.x] twice and [NPIX.y, NPIX.x] -- or [nf, 12*NSIDE^2] and [12*NSIDE^2]; plane f
+        of MAPX and TAUX is what map gives for frequency f, COLDEN what it gives as SAVETAU with save_colden=1."""
+        v = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).ravel()[:3]) for a in (DIR, RA, DE, CENTRE, INTOBS)]
+        nx, ny = (int(healpix), 1) if healpix else (int(NPIX[0]), int(NPIX[1]))
+        shape = (12 * nx * nx,) if healpix else (max(ny, 0), max(nx, 0))
+        nf = getattr(self, "_map_block_nf", 0)
+        MAPX, TAUX = np.zeros((nf,) + shape, np.float32), np.zeros((nf,) + shape, np.float32)
+        COLDEN = np.zeros(shape, np.float32)
+        self._chk(self.lib.soc_map_block(self.h, int(bool(healpix)), nx, ny, np.float32(MAP_DX), _f(v[0]), _f(v[1]), _f(v[2]), _f(v[3]),
+                                         _f(v[4]), np.float32(LENGTH), _f(MAPX), _f(TAUX), _f(COLDEN)))
+        return MAPX, TAUX, COLDEN
 
     def set_bfield(self, Bx, By=None, Bz=None):
         """The magnetic field of the polarisation maps: three arrays of CELLS floats (cloud-file order, parents included).
