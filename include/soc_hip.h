@@ -386,6 +386,24 @@ int soc_map(soc_ctx *ctx, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, con
             const float *RA, const float *DE, const float *CENTRE, const float *INTOBS, float ABS, float SCA,
             int save_colden, float LENGTH, float *MAP, float *SAVETAU);
 
+/* `mapping nx ny dx 999` (a fourth argument >= 999): replaces the kernel_map launch + copy of ASOC.py:3409-3418 -> the Mapping
+ * of kernel_ASOC_map_H.c (:380-497): one image per hierarchy level.  MAP holds LEVELS planes of NPIX_Y*NPIX_X floats; plane l
+ * is the line-of-sight integral of EMIT[CELLS] (x density) over the cells of level l only, attenuated by everything in
+ * front of them -- the planes add up to one map.  The view is soc_map's with healpix = 0: the orthographic map towards DIR
+ * with image axes RA, DE through CENTRE, or with INTOBS given (INTOBS[0] > -1e10; NULL: external view) the longitude x
+ * latitude image seen from there.  That file has its own ray entry and its own Index() (see soc_polmap_healpix), restated as
+ * written: on a Cartesian grid the one plane is soc_map's image up to the entry point (an EPS apart); on a hierarchy a ray that
+ * climbs out of an octet into a root leaf goes on from the corner of the grid and usually ends there, so the planes hold only
+ * what lies in front of that point (DESIGN.md section 5 has figures).  Extinction is ABS+SCA or the per-cell OPT of
+ * soc_set_opt* (the line that file keeps under "#ifdef USE_ABU", :474-478, which ASOC.py never defines: the reference itself
+ * always takes the scalars).  That kernel tests neither -D MAP_INTERPOLATION, LEVEL_THRESHOLD nor ROI_MAP:
+ * soc_set_map_interpolation, soc_set_map_threshold and soc_set_map_roi have no effect here.  A pixel whose ray misses the
+ * model is 0 on every level.  A ray is ended after 2^15 cell steps, as in soc_polmap_healpix.
+ * SOC_ERR_STATE without a grid; SOC_ERR_ARG for NPIX_X or NPIX_Y < 1, LEVELS*NPIX_X*NPIX_Y beyond int, EMIT or MAP NULL, an
+ * external view without DIR, RA, DE, CENTRE or MAP_DX > 0 or with a component of DIR that is zero (the walk divides by it). */
+int soc_map_levels(soc_ctx *ctx, int NPIX_X, int NPIX_Y, float MAP_DX, const float *EMIT, const float *DIR, const float *RA,
+                   const float *DE, const float *CENTRE, const float *INTOBS, float ABS, float SCA, float *MAP);
+
 /* `mapping nx ny dx NF`, 2 <= NF <= 998 (ASOC.py:3442-3568: "this many frequencies per kernel call"; the reference's branch
  * asks for a kernel_ASOC_map_X.c that it does not ship and stops): the maps of a batch of frequencies from one walk per pixel.
  * The products are defined as those of soc_map, frequency by frequency, bit for bit.

@@ -81,8 +81,20 @@ def _check_supported(USER, NDUST, WITH_MSF, engine=None):
         bad.append("polred without polmap (the factor is encoded in the magnetic field of a polarisation map)")
     # `mapping nx ny dx NF`, 2 <= NF <= 998 (ASOC.py:3442-3568: NF frequencies per kernel call): the maps of the plain path, NF
     # frequencies per walk, on an engine that has the kernel (write_maps, _map_blocks)
+    # `mapping nx ny dx 999` (a fourth argument >= 999; ASOC.py:2903, :3323-3438): one image per hierarchy level from the Mapping of
+    # kernel_ASOC_map_H.c, on an engine that has the kernel (write_level_maps)
     if USER.FAST_MAP >= 999:
-        bad.append("mapping with a fourth argument >= 999 (one map per hierarchy level, kernel_ASOC_map_H.c)")
+        if not hasattr(engine, "map_levels"):
+            bad.append("mapping with a fourth argument >= 999 (one map per hierarchy level, kernel_ASOC_map_H.c): this engine has no "
+                       "per-level map kernel (map_levels)")
+        if USER.NPIX[1] < 0:
+            bad.append("mapping with a fourth argument >= 999 and a Healpix map (negative second argument): the HealpixMapping of "
+                       "kernel_ASOC_map_H.c writes one map into a buffer sized for LEVELS and does not separate the levels")
+        if len(getattr(USER, "savetau_freq", [])) > 0 or len(getattr(USER, "file_savetau", "")) > 0:
+            bad.append("savetau with a fourth mapping argument >= 999 (ASOC.py:3337 hands pyopencl np.float, and the kernel writes COLDEN "
+                       "only under WITH_COLDEN, which ASOC.py never defines: the file would hold an uninitialised buffer)")
+        if any(k.startswith('libmap') for k in USER.KEYS):
+            bad.append("libmaps with a fourth mapping argument >= 999 (ASOC.py:3325-3326 stops there as well)")
     elif USER.FAST_MAP >= 2 and not (hasattr(engine, "map_block") and hasattr(engine, "set_map_block")):
         bad.append("mapping with a fourth argument >= 2 (FAST_MAP 2..998: kernel_ASOC_map_X.c, all frequencies per launch -- the reference's "
                    "own branch stops at ASOC.py:3553, a list compared with a float): this engine has no batch map kernel (map_block, set_map_block)")
@@ -92,7 +104,7 @@ def _check_supported(USER, NDUST, WITH_MSF, engine=None):
         bad.append("DEFS (extra -D options for the OpenCL compiler)")
     # `interpolate` and `yshear` have an effect in one branch only, the Healpix polarisation map (write_healpix_polmaps);
     # elsewhere they are accepted without effect, because they have none in the reference either (kernel_ASOC_map_H.c is
-    # otherwise built for FAST_MAP >= 999 only: refused above).  Likewise without effect: `externalmask` reaches only the SUBITERATIONS
+    # otherwise built for FAST_MAP >= 999 only, and its Mapping tests neither).  Likewise without effect: `externalmask` reaches only the SUBITERATIONS
     # branch (refused above), `sourcemap` is parsed and never read (ASOC_aux.py:322), `bgmethod` is a -D that no kernel tests
     # (`loadtemp` with iterations > 0 has no effect in the reference: the temperatures read are replaced before any use --
     # the block that would use them with ALI, ASOC.py:2062-2071, is switched off there -- so it has none here)
@@ -787,6 +799,8 @@ class AbsorptionRun:
         if U.NPIX[1] == 0:
             self.log("mapping with NPIX.y == 0: neither the flat (NPIX.y > 0, ASOC.py:2924) nor the Healpix branch (NPIX.y < 0, :3185)")
             return
+        if U.FAST_MAP >= 999:
+            return self.write_level_maps(EMITTED)
         if U.NPIX[1] < 0:
             return self.write_healpix_maps(EMITTED)
         NFREQ, FFREQ = self.NFREQ, self.FFREQ
@@ -871,6 +885,42 @@ class AbsorptionRun:
                     write(IFREQ, idir, MAP, TAU, save_spe, save_tau, save_colden)
         for fp in fps:
             fp.close()
+
+    def write_level_maps(self, EMITTED):
+        """`mapping nx ny dx 999` (a fourth argument >= 999): one image per hierarchy level (ASOC.py:3323-3438 -> the Mapping of
+        kernel_ASOC_map_H.c).  For every direction map_dir_XX_H.bin = int32 NPIX.x, NPIX.y, then int32 number of frequencies
+        written, LEVELS, then per frequency of the emitted range inside `wavelength` LEVELS float32 images [NPIX.y, NPIX.x]
+        [Jy/sr]: image l holds the emission of the cells of level l, attenuated by everything in front of them.  `perspective`
+        gives the longitude x latitude images seen from that position.  `mapum` selects nothing here (ASOC.py:3363-3375), and
+        `mapint`, `threshold` and `roimap` have no effect: that kernel tests none of them.  With abundances the extinction is
+        the per-cell sum (`singleabu`, `optishalf` included), which the reference has under a macro it never defines.
+        The walk is that kernel file's own, bit for bit: on a hierarchy it loses a ray where the ray climbs out of an octet into
+        a root leaf, so the images hold only what lies in front of that point."""
+        U, e, c = self.U, self.eng, self.cloud
+        FFREQ = self.FFREQ
+        m = np.nonzero((FFREQ >= U.REMIT_F[0]) & (FFREQ <= U.REMIT_F[1]))[0]
+        I1, I2 = int(m[0]), int(m[-1])
+        NDIR, ODIR, RA, DE = launch.set_observer_directions(U.OBS_THETA, U.OBS_PHI)
+        centre = U.MAPCENTRE if U.MAPCENTRE[0] > -1e7 else (0.5 * c.NX, 0.5 * c.NY, 0.5 * c.NZ)   # ASOC_aux.py:791-793
+        KK = (1.0e23 / launch.FACTOR) * PLANCK / (4.0 * np.pi) * (U.GL * PARSEC)                 # ASOC.py:3369-3370
+        sel = [i for i in range(I1, I2 + 1) if U.MAP_FREQ[0] <= float(FFREQ[i]) <= U.MAP_FREQ[1]]
+        fps = []
+        if self.rank == 0:
+            for idir in range(NDIR):
+                fp = open("map_dir_%02d_H.bin" % idir, "wb")
+                np.asarray([U.NPIX[0], U.NPIX[1]], np.int32).tofile(fp)
+                np.asarray([len(sel), c.LEVELS], np.int32).tofile(fp)
+                fps.append(fp)
+        for IFREQ in sel:
+            ABS, SCA = self._optical_for(IFREQ)
+            EMIT = np.asarray(EMITTED[:, IFREQ - I1] * np.float32(KK) * np.float32(float(FFREQ[IFREQ])), np.float32)    # :3404
+            for idir in range(NDIR):
+                MAP = e.map_levels(EMIT, ODIR[idir], RA[idir], DE[idir], U.NPIX, U.MAP_DX, centre, ABS, SCA, INTOBS=U.INTOBS)
+                if self.rank == 0:
+                    np.asarray(MAP, np.float32).tofile(fps[idir])
+        for fp in fps:
+            fp.close()
+        return ["map_dir_%02d_H.bin" % idir for idir in range(NDIR)]
 
     def polarisation_field(self, healpix=False):
         """The three B files of `polmap` (the layout of the cloud file: every cell, parents included) with the polarisation

@@ -176,6 +176,45 @@ int soc_map(soc_ctx *c, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const
     return SOC_OK;
 }
 
+// one map per hierarchy level (`mapping nx ny dx 999`, ASOC.py:3323-3438 -> the Mapping of kernel_ASOC_map_H.c:380-497)
+int soc_map_levels(soc_ctx *c, int NPIX_X, int NPIX_Y, float MAP_DX, const float *EMIT, const float *DIR, const float *RA, const float *DE,
+                   const float *CENTRE, const float *INTOBS, float ABS, float SCA, float *MAP)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_map_levels: call soc_set_grid first");
+    if (!EMIT || !MAP) return fail(c, SOC_ERR_ARG, "soc_map_levels: EMIT and MAP are needed");
+    const int64_t planes = (int64_t)c->G.LEVELS;
+    if (NPIX_X < 1 || NPIX_Y < 1 || (int64_t)NPIX_X * NPIX_Y > 2147483647LL / planes)
+        return fail(c, SOC_ERR_ARG, "soc_map_levels: NPIX %d x %d (with %d levels)", NPIX_X, NPIX_Y, c->G.LEVELS);
+    const bool inside = INTOBS && INTOBS[0] > -1e10f;
+    if (inside) {
+        for (int k = 0; k < 3; k++) if (!std::isfinite(INTOBS[k])) return fail(c, SOC_ERR_ARG, "soc_map_levels: INTOBS[%d] = %g", k, (double)INTOBS[k]);
+    } else {
+        if (!DIR || !RA || !DE || !CENTRE || !(MAP_DX > 0.0f)) return fail(c, SOC_ERR_ARG, "soc_map_levels: DIR, RA, DE, CENTRE and MAP_DX > 0 are needed");
+        // the walk divides by the components of -DIR without clamping them (kernel_ASOC_map_H.c:460): a zero would send the position to NaN
+        for (int k = 0; k < 3; k++) if (!std::isfinite(DIR[k]) || DIR[k] == 0.0f) return fail(c, SOC_ERR_ARG, "soc_map_levels: DIR[%d] = %g", k, (double)DIR[k]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)NPIX_X * NPIX_Y, cells = (size_t)c->G.CELLS, n = (size_t)planes * npix;
+    HIPCHK(c, c->dMapEmit.reserve(cells, c->stream));
+    HIPCHK(c, c->dMap.reserve(n, c->stream));
+    SocMapLevArgs A;
+    memset(&A, 0, sizeof A);
+    A.NPIX_X = NPIX_X;  A.NPIX_Y = NPIX_Y;  A.MAP_DX = MAP_DX;  A.ABS = ABS;  A.SCA = SCA;
+    for (int k = 0; k < 3; k++) {
+        A.DIR[k] = DIR ? DIR[k] : 0.0f;  A.RA[k] = RA ? RA[k] : 0.0f;  A.DE[k] = DE ? DE[k] : 0.0f;
+        A.CENTRE[k] = CENTRE ? CENTRE[k] : 0.0f;
+        A.INTOBS[k] = inside ? INTOBS[k] : (k == 0 ? -1.0e12f : 0.0f);
+    }
+    A.EMIT = c->dMapEmit;  A.OPT = c->dOPT;  A.MAP = c->dMap;
+    HIPCHK(c, hipMemcpyAsync(c->dMapEmit, EMIT, cells * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, soc_launch_maplev(c->G, A, c->dOPT != nullptr, c->stream));
+    HIPCHK(c, hipMemcpyAsync(MAP, c->dMap, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
 // maps of a batch of frequencies (`mapping nx ny dx NF`, ASOC.py:3442-3568 -> the kernel_ASOC_map_X.c the reference lacks)
 int soc_map_block_max(void) { return SOC_MAPX_MAX; }
 

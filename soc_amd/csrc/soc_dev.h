@@ -193,6 +193,18 @@ struct SocHPolArgs {
     float *MAP;                    // [4 * 12 * NSIDE^2]
 };
 hipError_t soc_launch_hpolmap(const SocGrid &G, const SocHPolArgs &A, bool abu, hipStream_t st);
+// per-level maps (soc_map.hip): one launch of the Mapping of kernel_ASOC_map_H.c (:380-398), `mapping nx ny dx 999`
+#define SOC_MAPLEV_MAXSTEPS SOC_HPOL_MAXSTEPS   // the walk is that file's: the same end of a ray that cycles
+struct SocMapLevArgs {
+    int   NPIX_X, NPIX_Y;
+    float MAP_DX, ABS, SCA;
+    float DIR[3], RA[3], DE[3], CENTRE[3];
+    float INTOBS[3];               // INTOBS[0] > -1e10: the longitude x latitude image seen from there
+    const float  *EMIT;
+    const float2 *OPT;
+    float *MAP;                    // [LEVELS * NPIX_Y * NPIX_X]
+};
+hipError_t soc_launch_maplev(const SocGrid &G, const SocMapLevArgs &A, bool abu, hipStream_t st);
 hipError_t soc_launch_pack_bfield(int cells, const float *Bx, const float *By, const float *Bz, float4 *B, hipStream_t st);
 hipError_t soc_launch_pstau(const SocGrid &G, int no, const float4 *PSPOS, const float *DIR, float ABS, float SCA, const float2 *OPT, float LENGTH,
                             float *pscolden, float *pstau, hipStream_t st);

@@ -9,7 +9,8 @@
 // changes the last bits of positions and step lengths, hence of the maps; it is restated here as written
 // (soc_map_index) and pinned bit-exactly by the x86 build of the reference (oracle/_ref/refmap_*.so).
 // -D MAP_INTERPOLATION, ROI_MAP and LEVEL_THRESHOLD are launch arguments here; PolMapping (POLSTAT 0, 1, 3) and
-// PolHealpixMapping (POLSTAT 0, with the differences of its own file's walk) follow at the end of the file.
+// PolHealpixMapping (POLSTAT 0, with the differences of its own file's walk) follow, and last the per-level Mapping of
+// kernel_ASOC_map_H.c (:380-497).
 #include "soc_walk.h"
 
 #define SOC_MAP_PEPS 5.0e-4f
@@ -452,7 +453,8 @@ __device__ __forceinline__ bool soc_pol_outside(const SocGrid &G, float x, float
 // The ray's entry (:1011-1033, the same lines in every POLSTAT block): PolMapping starts BEHIND the cloud and takes the
 // largest of the three face crossings that stays inside, each minus EPS -- not Mapping's entry; no NX >= 200 branch,
 // no INTOBS, and the walking direction -DIR is not clamped.
-__device__ __forceinline__ void soc_pol_entry(const SocGrid &G, const SocPolArgs &A, int id, float &px, float &py, float &pz)
+template <typename ARGS>                                                // SocPolArgs, or the SocMapLevArgs of the per-level Mapping (same lines)
+__device__ __forceinline__ void soc_pol_entry(const SocGrid &G, const ARGS &A, int id, float &px, float &py, float &pz)
 {
     const int   NX = G.NX, NY = G.NY, NZ = G.NZ;
     const int   i = id % A.NPIX_X, j = id / A.NPIX_X;
@@ -819,6 +821,95 @@ hipError_t soc_launch_hpolmap(const SocGrid &G, const SocHPolArgs &A, bool abu, 
         if (m == 0) soc_hpolmap_launch<true, true, 0>(G, A, abu, grid, block, st);
         else        soc_hpolmap_launch<true, true, 3>(G, A, abu, grid, block, st);
     }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// per-level maps: Mapping of kernel_ASOC_map_H.c (:380-497), `mapping nx ny dx 999`
+// ------------------------------------------------------------------------------------
+// One lane per pixel; plane ilev of MAP holds what the cells of hierarchy level ilev emit towards the pixel, seen through
+// everything in front of them.  The entry is that file's, not soc_map_entry: the external view starts behind the cloud and
+// takes the largest face crossing (soc_pol_entry is the same text, :438-459) and walks along -DIR without clamping it; the
+// perspective view looks along (-cos t sin p, -cos t cos p, sin t).  The walk is that file's too (soc_map_index<.., HFILE = true>).
+// That Mapping tests neither MAP_INTERPOLATION, LEVEL_THRESHOLD nor ROI_MAP: `mapint`, `threshold` and `roimap` have no effect
+// here, as in the reference.  The extinction of a step is ABS + SCA, or the per-cell sum that file keeps under "#ifdef USE_ABU"
+// (:474-478) when the handle holds per-cell opacities.  A ray ends after SOC_MAPLEV_MAXSTEPS steps (soc_dev.h).
+// The LEVELS accumulators are registers: NL is a template argument, the loops over it are unrolled and a step adds to the one
+// of its level under a compare-select -- an array indexed by the run-time level would live in scratch.
+template <bool OCT, bool DBL, bool ABU, int NL>
+__global__ __launch_bounds__(256) void soc_maplev_kernel(const SocGrid G, const SocMapLevArgs A)
+{
+    __shared__ int sOFF[SOC_MAXL];
+    if (threadIdx.x < SOC_MAXL) sOFF[threadIdx.x] = G.OFF[threadIdx.x];
+    __syncthreads();
+    const int npix = A.NPIX_X * A.NPIX_Y;
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= npix) return;
+    float PHOTONS[NL];
+#pragma unroll
+    for (int l = 0; l < NL; l++) PHOTONS[l] = 0.0f;
+    float px, py, pz, tx, ty, tz;
+    if (A.INTOBS[0] > -1e10f) {                                           // perspective image from inside the model (:412-434)
+        const int i = id % A.NPIX_X, j = id / A.NPIX_X;
+        float phi = SOC_POL_TWOPI * i / (float)(A.NPIX_X);
+        phi += SOC_POL_PI;
+        const float pix = SOC_POL_TWOPI / A.NPIX_X;
+        const float theta = pix * (j - (A.NPIX_Y - 1) / 2);
+        float st, ct, sp, cp;
+        soc_sincosf(theta, &st, &ct);
+        soc_sincosf(phi, &sp, &cp);
+        px = A.INTOBS[0];  py = A.INTOBS[1];  pz = A.INTOBS[2];
+        tx = -ct * sp;  ty = -ct * cp;  tz = +st;
+        if (soc_fabsf(tx) < 1.0e-5f) tx = 1.0e-5f;
+        if (soc_fabsf(ty) < 1.0e-5f) ty = 1.0e-5f;
+        if (soc_fabsf(tz) < 1.0e-5f) tz = 1.0e-5f;
+        if (soc_fmod1f(px) < 1.0e-5f) px += 2.0e-5f;
+        if (soc_fmod1f(py) < 1.0e-5f) py += 2.0e-5f;
+        if (soc_fmod1f(pz) < 1.0e-5f) pz += 2.0e-5f;
+    } else {                                                              // external map (:436-460)
+        soc_pol_entry(G, A, id, px, py, pz);
+        tx = -A.DIR[0];  ty = -A.DIR[1];  tz = -A.DIR[2];
+    }
+    const float OPTSUM = A.SCA + A.ABS;
+    int   level = 0, ind = -1;
+    float dens = 0.0f, TAU = 0.0f;
+    soc_indexg<OCT>(G, sOFF, px, py, pz, level, ind, dens);
+    for (int steps = 0; (ind >= 0) && (steps < SOC_MAPLEV_MAXSTEPS); steps++) {
+        const int   oind = sOFF[level] + ind, olevel = level;
+        const float rho = dens;
+        const float sx = soc_map_getstep<OCT, DBL, true>(G, sOFF, px, py, pz, tx, ty, tz, level, ind, dens);
+        float DTAU;
+        if (ABU) { const float2 o = A.OPT[oind];  DTAU = sx * rho * (o.x + o.y); }
+        else     DTAU = sx * rho * OPTSUM;
+        const float add = soc_pol_emitted(TAU, DTAU, sx, A.EMIT[oind], rho);                      // (:480-484)
+#pragma unroll
+        for (int l = 0; l < NL; l++) PHOTONS[l] = (olevel == l) ? (PHOTONS[l] + add) : PHOTONS[l];
+        TAU += DTAU;
+    }
+#pragma unroll
+    for (int l = 0; l < NL; l++)
+        if (l < G.LEVELS) A.MAP[(size_t)l * npix + id] = PHOTONS[l];
+}
+
+// the accumulator counts soc_maplev_kernel is compiled for; a model runs in the narrowest that holds its levels
+template <bool OCT, bool DBL, bool ABU>
+static void soc_maplev_dispatch(const SocGrid &G, const SocMapLevArgs &A, dim3 grid, dim3 block, hipStream_t st)
+{
+    if (G.LEVELS <= 4)      soc_maplev_kernel<OCT, DBL, ABU, 4><<<grid, block, 0, st>>>(G, A);
+    else if (G.LEVELS <= 8) soc_maplev_kernel<OCT, DBL, ABU, 8><<<grid, block, 0, st>>>(G, A);
+    else                    soc_maplev_kernel<OCT, DBL, ABU, SOC_MAXL><<<grid, block, 0, st>>>(G, A);
+}
+
+hipError_t soc_launch_maplev(const SocGrid &G, const SocMapLevArgs &A, bool abu, hipStream_t st)
+{
+    const int npix = A.NPIX_X * A.NPIX_Y;
+    if (npix <= 0) return hipSuccess;
+    if (G.LEVELS < 1 || G.LEVELS > SOC_MAXL) return hipErrorInvalidValue;
+    const dim3 grid((npix + 255) / 256), block(256);
+    const bool oct = G.LEVELS > 1, dbl = oct && (G.NX > 100);            // kernel_ASOC_map_H.c:14, :222
+    if (!oct)      { if (abu) soc_maplev_kernel<false, false, true, 4><<<grid, block, 0, st>>>(G, A); else soc_maplev_kernel<false, false, false, 4><<<grid, block, 0, st>>>(G, A); }
+    else if (!dbl) { if (abu) soc_maplev_dispatch<true, false, true>(G, A, grid, block, st);  else soc_maplev_dispatch<true, false, false>(G, A, grid, block, st); }
+    else           { if (abu) soc_maplev_dispatch<true, true, true>(G, A, grid, block, st);   else soc_maplev_dispatch<true, true, false>(G, A, grid, block, st); }
     return hipGetLastError();
 }
 

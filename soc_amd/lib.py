@@ -103,6 +103,7 @@ API = {
     "soc_emission": (C.c_int, [C.c_void_p, C.c_int, _F, _F, C.c_float, C.c_float, _F]),
     "soc_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F, _F, C.c_float, C.c_float, C.c_int,
                           C.c_float, _F, _F]),
+    "soc_map_levels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F, _F, C.c_float, C.c_float, _F]),
     "soc_map_block_max": (C.c_int, []),
     "soc_map_set_block": (C.c_int, [C.c_void_p, C.c_int, _F, _F, _F, _F]),
     "soc_map_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F, C.c_float, _F, _F, _F]),
@@ -235,6 +236,7 @@ class Engine:
         self.device = int(device)
         self.CELLS = 0
         self.NPAR = 0
+        self.LEVELS = 0
         self._mabu = None                                  # (cells, NFREQ, NDUST) between mabu_begin and mabu_end
 
     def close(self):
@@ -264,6 +266,7 @@ class Engine:
         self._chk(self.lib.soc_set_grid(self.h, int(NX), int(NY), int(NZ), int(LEVELS), _i(LCELLS), _f(DENS)))
         self.CELLS = int(DENS.size)
         self.NPAR = self.CELLS - int(NX) * int(NY) * int(NZ)
+        self.LEVELS = int(LEVELS)
 
     def set_cloud(self, cloud):
         self.set_grid(cloud.NX, cloud.NY, cloud.NZ, cloud.LEVELS, cloud.LCELLS, cloud.DENS)
@@ -582,6 +585,21 @@ class Engine:
         self._chk(self.lib.soc_map_block(self.h, int(bool(healpix)), nx, ny, np.float32(MAP_DX), _f(v[0]), _f(v[1]), _f(v[2]), _f(v[3]),
                                          _f(v[4]), np.float32(LENGTH), _f(MAPX), _f(TAUX), _f(COLDEN)))
         return MAPX, TAUX, COLDEN
+
+    def map_levels(self, EMIT, DIR, RA, DE, NPIX, MAP_DX, CENTRE, ABS, SCA, INTOBS=None):
+        """One image per hierarchy level (the Mapping of kernel_ASOC_map_H.c, `mapping nx ny dx 999`): [LEVELS, NPIX.y, NPIX.x],
+        plane l the emission of the cells of level l seen through everything in front of them.  INTOBS: the longitude x latitude
+        image seen from that position instead of the orthographic map.  `mapint`, `threshold` and `roimap` (set_map_interpolation,
+        set_map_threshold, set_map_roi) have no effect here, as in the reference."""
+        EMIT = np.ascontiguousarray(EMIT, np.float32)
+        if EMIT.size != self.CELLS:
+            raise SocError("map_levels: EMIT must hold CELLS floats")
+        v = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).ravel()[:3]) for a in (DIR, RA, DE, CENTRE, INTOBS)]
+        nx, ny = int(NPIX[0]), int(NPIX[1])
+        MAP = np.zeros((self.LEVELS, max(ny, 0), max(nx, 0)), np.float32)
+        self._chk(self.lib.soc_map_levels(self.h, nx, ny, np.float32(MAP_DX), _f(EMIT), _f(v[0]), _f(v[1]), _f(v[2]), _f(v[3]), _f(v[4]),
+                                          np.float32(ABS), np.float32(SCA), _f(MAP)))
+        return MAP
 
     def set_bfield(self, Bx, By=None, Bz=None):
         """The magnetic field of the polarisation maps: three arrays of CELLS floats (cloud-file order, parents included).
