@@ -226,6 +226,29 @@ int soc_set_hpbg(soc_ctx *ctx, const float *BG, const float *HPBGP);
  * soc_sim_pb (direct kernel or brick sweep, deferred inside soc_batch_begin/end with its own copy of the sky) */
 int soc_sim_hp(soc_ctx *ctx, int PACKETS, int BATCH, float SEED, float TW, int GLOBAL, int gid_first, int gid_count);
 
+/* replaces the kernel_bg_split launch of `split 1` runs (ASOC.py:1343-1347 -> SimBgSplit, kernel_ASOC.c:2117-2851): the
+ * isotropic background with packet splitting.  Each work item sends BATCH root rays from each of its SELEM surface elements
+ * (element id + elem*GLOBAL, the work item returns at the first one >= AREA, :2194-2198); a ray that steps into a refined cell
+ * becomes four, one per sub-element of the face it entered through (:2566-2709; a ray born in a refined boundary cell at once,
+ * :2300-2428), the others waiting on a stack of max_split entries per work item (-D MAX_SPLIT; max_split <= 0: 4300,
+ * ASOC_aux.py:54).  The stack -- gid_count (rounded up to 64) x max_split x 10 words of device memory, laid out so that a wave's
+ * pushes and pops coalesce -- is allocated on first use, kept for the handle and freed with it.  GLOBAL is the logical launch
+ * size (GLOBAL_SPLIT, ASOC.py:311-315) and the work-item range works as in soc_sim_pb.  Always the direct kernel: the brick sweep
+ * stands aside, and inside soc_batch_begin/end the launch runs at once, after what was deferred before it.
+ * Refused (SOC_ERR_ARG / SOC_ERR_STATE, the handle stays usable): no grid, max_split < 14 (a split needs 4 free entries above
+ * the reference's NBUF > MAX_SPLIT-10 test), SELEM < 1, a range outside GLOBAL, a stack that does not fit in device memory (the
+ * message carries its size), and what SimBgSplit has no branch for: reflecting faces (soc_set_mirror), weighted free paths
+ * (soc_set_step_weight), a region-of-interest record (soc_set_roi_save).  A single-level grid never splits but is accepted.
+ * A split whose 4^d entries would not fit the stack -- the reference writes them without looking -- is an overflow drop. */
+int soc_sim_bg_split(soc_ctx *ctx, int PACKETS, int BATCH, float SEED, float BG, float TW, int SELEM, int max_split,
+                     int GLOBAL, int gid_first, int gid_count);
+/* counters of the soc_sim_bg_split launches since the last reset, summed over work items: out[0] root rays started,
+ * out[1] split events, out[2] those over two or more levels, out[3] rays ended on reaching a level below the one they were
+ * created on, out[4] stack-overflow drops (the ray and all on its stack), out[5] work items that returned at 30000 steps */
+int soc_split_stats(soc_ctx *ctx, uint64_t out[6], int reset);
+/* the largest number of stack entries a work item of those launches held, as of the last soc_split_stats call; -1: no handle */
+int64_t soc_split_max_depth(soc_ctx *ctx);
+
 /* replaces queue.finish() (ASOC.py:1461) */
 int soc_sync(soc_ctx *ctx);
 

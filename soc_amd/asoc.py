@@ -33,7 +33,19 @@ class UnsupportedOption(RuntimeError):
 def _check_supported(USER, NDUST, WITH_MSF, engine=None):
     bad = []
     if USER.DO_SPLIT:
-        bad.append("split")
+        # packet splitting of the isotropic background (SimBgSplit, kernel_ASOC.c:2117-2851) on an engine that has the kernel
+        if not hasattr(engine, "sim_bg_split"):
+            bad.append("split (the engine has no sim_bg_split)")
+        if len(USER.file_hpbg) > 2 and USER.BGPAC > 0:
+            bad.append("split with a Healpix background (SimHpSplit, kernel_ASOC.c:2871 on, has split rules of its own; out of scope)")
+        if launch.mirror_mask(USER.MIRROR):
+            bad.append("split with mirror (SimBgSplit has no Mirror() call)")
+        if int(USER.STEP_WEIGHT[2]) > 0:
+            bad.append("split with stepweight (SimBgSplit draws unweighted free paths only)")
+        if USER.WITH_ROI_SAVE:
+            bad.append("split with roisave (SimBgSplit keeps no region-of-interest record)")
+        if USER.MAX_SPLIT != 0 and USER.MAX_SPLIT < 14:
+            bad.append("maxsplit %d (at least 14: a split adds 4 entries above the kernel's NBUF > MAX_SPLIT-10 test)" % USER.MAX_SPLIT)
     if int(USER.STEP_WEIGHT[2]) > 2:
         bad.append("stepweight with a third argument > 2 (the kernel then uses an uninitialised free path, kernel_ASOC.c:516-535)")
     if USER.DIR_WEIGHT[0] > 0:
@@ -195,6 +207,10 @@ class AbsorptionRun:
         self.PSPAC, self.BGPAC, self.CLPAC, self.DFPAC = pc["PSPAC"], pc["BGPAC"], pc["CLPAC"], pc["DFPAC"]
         if U.ITERATIONS < 1:
             U.NOABSORBED = 1
+        self.SPLIT = bool(U.DO_SPLIT) and U.BGPAC > 0 and len(self.HPBG) == 0
+        if self.SPLIT:
+            # `split 1`: BATCH rays from every surface element; the corrected BGPAC = AREA*BATCH (ASOC.py:1073-1074)
+            self.BGPAC = launch.bg_split_launch(U.BGPAC, int(U.AREA), LOCAL)["PACKETS"]
         self.log('PACKETS: PSPAC %d   BGPAC %d  CLPAC %d  DFPAC %d' % (self.PSPAC, self.BGPAC, self.CLPAC, self.DFPAC))
         self.XPS = files.analyse_external_point_sources(c.NX, c.NY, c.NZ, U.PSPOS, int(U.NO_PS), int(U.PS_METHOD))
         # launch size for point-source / cell-emission launches: reference default 32768
@@ -294,6 +310,8 @@ class AbsorptionRun:
         if II == 1:
             if self.BGPAC < 1:
                 return None
+            if self.SPLIT:
+                return launch.bg_split_launch(U.BGPAC, int(U.AREA), self.LOCAL)
             return self._hpbg_launch(self.BGPAC, c.NX, c.NY, c.NZ) if len(self.HPBG) > 0 else launch.bg_launch(self.BGPAC, int(U.AREA))
         if II == 2:
             if len(self.DIFFUSERAD) < 1 or self.DFPAC < 1:
@@ -370,6 +388,8 @@ class AbsorptionRun:
             e.sim_cl(II, L["PACKETS"], L["BATCH"], seed, FF, L["GLOBAL"], gid_first=first, gid_count=count)
         elif hp:
             e.sim_hp(L["PACKETS"], L["BATCH"], seed, FF, L["GLOBAL"], gid_first=first, gid_count=count)
+        elif II == 1 and "SELEM" in L:                         # `split 1`: kernel_bg_split (ASOC.py:1343-1347)
+            e.sim_bg_split(L["PACKETS"], L["BATCH"], seed, BG, FF, L["SELEM"], int(U.MAX_SPLIT), GLOBAL=L["GLOBAL"], gid_first=first, gid_count=count)
         else:
             e.sim_pb(II, L["PACKETS"], L["BATCH"], seed, BG, FF, PSPOS=U.PSPOS[:max(U.NO_PS, 1), :3], PS=PS, XPS=self.XPS,
                      GLOBAL=L["GLOBAL"], gid_first=first, gid_count=count)

@@ -93,6 +93,7 @@ class User:
         s.PSPOS = np.zeros((MAXPS, 4), np.float32)      # cl float3 = 4 floats
         s.PSPOS[:, 0] = -1e10
         s.DO_SPLIT = 0
+        s.MAX_SPLIT = 0                  # `maxsplit N`: stack entries per work item of a `split 1` run; 0 = 4300 (ASOC_aux.py:54)
         s.POLMAP = 0
         s.POLSIM = 0
         s.BFILES = []
@@ -383,6 +384,7 @@ _KEYWORDS = [
     ('scatter', 1, _set('file_scattering', str)),
     ('emit', 1, _set('file_emitted', str)),
     ('split', 1, _set('DO_SPLIT', int)),
+    ('maxsplit', 1, _set('MAX_SPLIT', int)),
     ('mapint', 1, _set('MAP_INTERPOLATION', int)),
     ('polstat', 1, _set('POLSTAT', int)),
     ('absthin', 1, _set('ABSTHIN', int)),

@@ -65,6 +65,18 @@ def bg_launch(BGPAC, AREA):
     return dict(GLOBAL=GLOBAL, BATCH=BATCH, PACKETS=PACKETS, WBG=WBG)
 
 
+def bg_split_launch(BGPAC, AREA, LOCAL=LOCAL_GPU, GLOBAL=GLOBAL_0):
+    """Isotropic background with packet splitting (`split 1`; ASOC.py:311-315, :1067-1075): a work item does SELEM surface
+    elements and sends BATCH root rays from each; GLOBAL (the reference's GLOBAL_SPLIT) is the smallest multiple of LOCAL with
+    SELEM*GLOBAL > AREA.  BGPAC is the ini file's value, not the rounded one; PACKETS the corrected count AREA*BATCH.
+    Returns dict(GLOBAL, BATCH, PACKETS, WBG, SELEM)."""
+    AREA = int(AREA)
+    SELEM = max([1, AREA // GLOBAL])
+    GLOBAL = Fix((AREA // SELEM) + 1, LOCAL)
+    BATCH = max([1, int(BGPAC / AREA)])
+    return dict(GLOBAL=GLOBAL, BATCH=BATCH, PACKETS=int(AREA * BATCH), WBG=np.pi / (PLANCK * BATCH), SELEM=SELEM)
+
+
 def hpbg_launch(BGPAC, NX, NY, NZ):
     """Healpix background (ASOC.py:1050-1059): 100 packets per work item, no systematic
     traversal of surface elements.  Work items with id >= 8*AREA return at once in the kernel

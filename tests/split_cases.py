@@ -1,0 +1,148 @@
+"""The packet-splitting cases (`split 1`, SimBgSplit) of tests/golden/split.npz: models and launches.  Shared by the tests and
+by tools/make_split_golden.py, which records what the reference's kernel gives for them, work item by work item in id order.
+
+Together the cases reach every branch of the kernel (COVERAGE is asserted over their counters before anything is recorded):
+  a ray born in a refined boundary cell (oct4b: 30 % of 4^3 root cells refined, boundary ones among them);
+  a neighbour two levels deeper (kat: synth.kat_octree(), root cell 21 -> level-1 cell 7 -> level 2);
+  the stop after more than 20 scatterings (oct4b_opaque: 30 optical depths of scattering per root cell);
+  the drop of a ray with its stack (nest5_ms16: max_split 16 on five nested levels -- with single-level jumps a stack reaches
+  NBUF = 9 > MAX_SPLIT-10 only at the fourth refinement in a row);
+  work items that return at ind >= AREA after their first elements (oct6_selem3: 96 work items x 3 elements for AREA 216),
+  and, in every case, the work items of the launch's padding, which return at their first element.
+"""
+import json
+
+import numpy as np
+
+from soc_amd import synth
+from oracle.pyoracle import Job
+
+_CSC = synth.hg_scattering_table(0.6)[1]
+
+
+def launch_shape(AREA, SELEM, LOCAL=32):
+    """GLOBAL of a launch whose work items do SELEM elements each: the smallest multiple of LOCAL above AREA // SELEM (ASOC.py:315)"""
+    return ((AREA // SELEM + 1 + LOCAL - 1) // LOCAL) * LOCAL
+
+
+def case(model, BATCH, SELEM=1, max_split=64, SEED=0.5, ABS=1e-4, SCA=3e-4, variant="scalar", BG=1.0, TW=1.0):
+    return dict(model=model, BATCH=BATCH, SELEM=SELEM, max_split=max_split, SEED=SEED, ABS=ABS, SCA=SCA, variant=variant, BG=BG, TW=TW)
+
+
+# variant: scalar | abu (per-cell OPT) | abuh (OPT rounded through fp16 and widened again, as the engine keeps it) | msf
+# (two scattering functions, WITH_MSF) | int2 (saveint 2: INT and the vector sums INTX, INTY, INTZ)
+CASES = {
+    "kat":          case("kat", 3, SEED=0.4137, ABS=1e-3, SCA=3e-3),
+    "kat_int2":     case("kat", 2, SEED=0.77, ABS=1e-3, SCA=3e-3, variant="int2", TW=2.5),
+    "oct4b":        case("oct4b", 2, SEED=0.2891),
+    "oct4b_opaque": case("oct4b", 2, SEED=0.611, ABS=1e-5, SCA=3e-2),
+    "oct4b_abu":    case("oct4b", 2, SEED=0.35, variant="abu", BG=3.0),
+    "oct4b_abuh":   case("oct4b", 2, SEED=0.35, variant="abuh"),
+    "oct4b_msf":    case("oct4b", 3, SEED=0.93, variant="msf"),
+    "nest5_ms16":   case("nest5", 4, max_split=16, SEED=0.1234),
+    "oct6_selem3":  case("oct6", 4, SELEM=3, SEED=0.8080),
+}
+
+COUNTERS = ("roots", "splits", "deep_splits", "ended_below_RL", "overflow_drops", "long_returns")
+
+_models = {}
+
+
+def model(name):
+    if name not in _models:
+        if name == "kat":
+            c = synth.kat_octree()
+        elif name == "oct4b":
+            c = synth.octree_cloud(4, levels=3, frac=0.3, seed=11)
+        elif name == "oct6":
+            c = synth.octree_cloud(6, levels=3, frac=0.15, seed=5)
+        elif name == "nest5":
+            c = nested_cloud(5)
+        elif name == "full4":                      # every root cell refined once, uniform: the normalisation check
+            c = synth.octree_cloud(4, levels=2, frac=1.0, uniform=1.0e3)
+        else:
+            raise KeyError(name)
+        _models[name] = c
+    return _models[name]
+
+
+def nested_cloud(levels, seed=2):
+    """4^3 root cells; on every level the central 2 x 2 x 2 cells of the 4 x 4 x 4 block are refined, so every level is a block of 64
+    cells inside the one above and neighbours differ by one level at most.  Level l > 0 holds the octets of the eight central
+    cells of level l-1 in the order of their positions (x fastest); the central cell of octet j is its sub-cell 7-j."""
+    rr = np.random.default_rng(seed)
+    H = [np.clip(np.exp(0.3 * rr.standard_normal(64)) * 1.0e3, 1.0, 1.0e5).astype(np.float32) for _ in range(levels)]
+    for l in range(levels - 1):
+        for j in range(8):
+            ox, oy, oz = j % 2, (j // 2) % 2, j // 4
+            cell = (1 + ox) + 4 * (1 + oy) + 16 * (1 + oz) if l == 0 else 8 * j + 7 - j
+            H[l][cell] = -synth.I2F(8 * j)
+    return synth.Cloud(4, 4, 4, H)
+
+
+def per_cell_opt(cloud, ABS, SCA, seed=3):
+    rr = np.random.default_rng(seed)
+    OPT = np.zeros((cloud.CELLS, 2), np.float32)
+    OPT[:, 0] = ABS * rr.uniform(0.5, 2.0, cloud.CELLS)
+    OPT[:, 1] = SCA * rr.uniform(0.5, 2.0, cloud.CELLS)
+    return OPT
+
+
+def msf_inputs(cloud, ABS, SCA, ndust=2, seed=6):
+    """-D WITH_MSF inputs (per-dust cross sections and scattering functions, abundances) and the OPT the host sums from them"""
+    rr = np.random.default_rng(seed)
+    A = (ABS * rr.uniform(0.5, 2, ndust)).astype(np.float32)
+    S = (SCA * rr.uniform(0.5, 2, ndust)).astype(np.float32)
+    CSC = np.stack([synth.hg_scattering_table(g)[1] for g in np.linspace(0.1, 0.7, ndust)]).astype(np.float32)
+    ABU = rr.uniform(0.2, 1.5, (cloud.CELLS, ndust)).astype(np.float32)
+    OPT = np.zeros((cloud.CELLS, 2), np.float32)
+    for i in range(ndust):
+        OPT[:, 0] += ABU[:, i] * A[i]
+        OPT[:, 1] += ABU[:, i] * S[i]
+    return dict(OPT=OPT, MSF=(A, S, CSC, ABU))
+
+
+def job(name):
+    """(Job, SELEM, max_split) of a case; Job.GLOBAL is the launch's GLOBAL_SPLIT"""
+    k = CASES[name]
+    c = model(k["model"])
+    kw = dict(ABS=k["ABS"], SCA=k["SCA"], SOURCE=1, BATCH=k["BATCH"], SEED=k["SEED"], BG=k["BG"], TW=k["TW"],
+              GLOBAL=launch_shape(c.AREA, k["SELEM"]), WITH_INT=1)
+    v = k["variant"]
+    if v == "abu":
+        kw["OPT"] = per_cell_opt(c, k["ABS"], k["SCA"])
+    elif v == "abuh":
+        kw["OPT"] = per_cell_opt(c, k["ABS"], k["SCA"]).astype(np.float16).astype(np.float32)
+    elif v == "msf":
+        kw.update(msf_inputs(c, k["ABS"], k["SCA"]))
+    elif v == "int2":
+        kw["WITH_INT"] = 2
+    return Job(c, _CSC, **kw), k["SELEM"], k["max_split"]
+
+
+def coverage(stats_by_case):
+    """What the cases must reach, over all of them together: every counter except the 30000-step return above zero, that one
+    zero; per case what it is there for.  stats_by_case: {name: dict(COUNTERS..., max_depth, guard)}.  Returns a list of failures."""
+    bad = []
+    total = {k: sum(int(s[k]) for s in stats_by_case.values()) for k in COUNTERS}
+    for k in COUNTERS[:5]:
+        if total[k] < 1:
+            bad.append("no case reaches '%s'" % k)
+    if total["long_returns"] != 0:
+        bad.append("%d work items returned at 30000 steps" % total["long_returns"])
+    for name, s in stats_by_case.items():
+        if int(s.get("guard", 0)) != 0:
+            bad.append("%s: %d splits would have run past the reference's stack slab" % (name, int(s["guard"])))
+    want = {"kat": "deep_splits", "oct4b": "initial", "oct4b_opaque": "stop20", "nest5_ms16": "overflow_drops"}
+    for name, key in want.items():
+        if key and name in stats_by_case and int(stats_by_case[name][key]) < 1:
+            bad.append("%s does not reach '%s'" % (name, key))
+    k = CASES["oct6_selem3"]
+    A, G = model(k["model"]).AREA, launch_shape(model(k["model"]).AREA, k["SELEM"])
+    if not any(i + G < A <= i + (k["SELEM"] - 1) * G for i in range(G)):
+        bad.append("oct6_selem3: no work item returns at ind >= AREA after its first elements")
+    return bad
+
+
+def meta():
+    return json.dumps(dict(cases=CASES))
