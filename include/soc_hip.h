@@ -449,6 +449,28 @@ int soc_map_block(soc_ctx *ctx, int healpix, int NPIX_X, int NPIX_Y, float MAP_D
                   const float *DE, const float *CENTRE, const float *INTOBS, float LENGTH, float *MAPX, float *TAUX,
                   float *COLDEN);
 
+/* `maplevels 1`: the levels of the plain map -- the resident batch of soc_map_set_block for one view, one plane per frequency
+ * and hierarchy level.  It stands in for nothing in the reference: what the reference offers per level is the Mapping of
+ * kernel_ASOC_map_H.c, and that is soc_map_levels, on that file's own walk.
+ * Definition: MAPL[f][l][npix] is, bit for bit, the MAP that soc_map (equally soc_map_block) gives for frequency f under the
+ * same view and switches when the emission of every cell that is not on level l is set to 0.0f; densities and opacities are
+ * left as they are.  Plane l is what the cells of level l emit towards the pixel, attenuated by everything in front of them;
+ * the planes of a pixel add up to its plain-map value up to the order of the fp32 additions.  With soc_set_map_interpolation
+ * 1 | 2 the blend of a step is evaluated per level with the contributors of other levels replaced by 0.0f (a neighbour on
+ * another level feeds that level's plane); whether a step emits at all (soc_set_map_roi, soc_set_map_threshold) and the
+ * blended density stay properties of the cell being crossed.  The optical depth is that of the plain map: opacity is not masked.
+ * The arguments are those of soc_map_block (healpix = 1: a map of NSIDE = NPIX_X seen from INTOBS).  The batch is read, never
+ * changed: a soc_map_block after the call gives what it gave before.  The planes are staged in device memory the handle owns,
+ * freed with the batch and with the handle.
+ * SOC_ERR_STATE without a grid; SOC_ERR_ARG without a resident batch, for MAPL NULL, NPIX_X or NPIX_Y < 1, a view soc_map_block
+ * refuses, and for nf * LEVELS * npix floats that do not fit the free device memory (the message states the size).  A refused
+ * call leaves tallies, batch and handle as they were.
+ * soc_map_block_levels_width: the most frequencies one kernel launch of the handle's model takes (8 up to 8 levels, else 4);
+ * wider batches run as several launches. */
+int soc_map_block_levels(soc_ctx *ctx, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const float *DIR, const float *RA,
+                         const float *DE, const float *CENTRE, const float *INTOBS, float *MAPL);
+int soc_map_block_levels_width(soc_ctx *ctx);
+
 /* replaces the Bx_buf, By_buf, Bz_buf uploads of ASOC.py:3722-3727: the magnetic field of the polarisation maps, CELLS
  * floats per component in the order of the cloud file (all cells, parents included).  The device keeps one 16-byte record
  * (Bx, By, Bz, pad) per cell.  A polarisation reduction factor is encoded in the length of the vectors by the caller

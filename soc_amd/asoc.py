@@ -110,6 +110,15 @@ def _check_supported(USER, NDUST, WITH_MSF, engine=None):
     elif USER.FAST_MAP >= 2 and not (hasattr(engine, "map_block") and hasattr(engine, "set_map_block")):
         bad.append("mapping with a fourth argument >= 2 (FAST_MAP 2..998: kernel_ASOC_map_X.c, all frequencies per launch -- the reference's "
                    "own branch stops at ASOC.py:3553, a list compared with a float): this engine has no batch map kernel (map_block, set_map_block)")
+    # `maplevels 1` (not a key of the reference): the plain map split by hierarchy level, from the walk of the plain map
+    # (write_maps, write_healpix_maps -> map_block_levels)
+    if getattr(USER, "MAP_LEVELS", 0) > 0:
+        if not (hasattr(engine, "map_block_levels") and hasattr(engine, "map_block") and hasattr(engine, "set_map_block")):
+            bad.append("maplevels (the plain map split by hierarchy level): this engine has no kernel for it (map_block_levels, with "
+                       "set_map_block and map_block)")
+        if USER.FAST_MAP >= 999:
+            bad.append("maplevels together with mapping with a fourth argument >= 999 (two different per-level products: that mode "
+                       "never reaches the walk of the plain map, whose levels maplevels writes)")
     if USER.MAP_INTERPOLATION > 2 or USER.MAP_INTERPOLATION < 0:
         bad.append("mapint other than 0, 1, 2 (kernel_ASOC_map.c:656-810 knows those: a larger value leaves Adens, Aemit ... unset there)")
     if len(USER.kernel_defs.strip()) > 0:
@@ -814,7 +823,13 @@ class AbsorptionRun:
         frequency.  `perspective` gives the longitude x latitude image seen from that position.  Optical-depth
         images for `savetau` frequencies are written as <file>_tau_<um>.bin, the column density (`savetau file -1`) as
         <file>_colden.fits; `fits` with `mapum` gives one FITS image per direction and frequency instead.  NPIX.y < 0:
-        write_healpix_maps.  Polarisation maps: write_polmaps."""
+        write_healpix_maps.  Polarisation maps: write_polmaps.
+        `maplevels 1` (not a key of the reference) adds map_dir_XX_L.bin per direction (map_dir_00_L.bin for a Healpix map):
+        int32 NPIX.x, NPIX.y, int32 [images, LEVELS], then for every image of the plain file, in its order, LEVELS float32 planes
+        [Jy/sr] -- plane l is the plain map with the emission of all cells not on hierarchy level l set to zero, so the planes of
+        an image add up to it.  The frequencies then go through _map_blocks in batches of min(max(1, FAST_MAP), map_block_max);
+        the plain products are the same bytes.  With `fits` + `mapum` the level file is still this .bin.  maplevels has no
+        effect on the `polmap` products (write_polmaps, write_healpix_polmaps)."""
         U, e, c = self.U, self.eng, self.cloud
         if U.NPIX[1] == 0:
             self.log("mapping with NPIX.y == 0: neither the flat (NPIX.y > 0, ASOC.py:2924) nor the Healpix branch (NPIX.y < 0, :3185)")
@@ -842,6 +857,7 @@ class AbsorptionRun:
                 fp = open("map_dir_%02d.bin" % idir, "wb")
                 np.asarray([U.NPIX[0], U.NPIX[1]], np.int32).tofile(fp)
                 fps.append(fp)
+        maplevels = getattr(U, "MAP_LEVELS", 0) > 0
         # what is computed: (IFREQ, save_spe, save_tau, save_colden) in ascending frequency
         sel = []
         first_freq = True
@@ -888,7 +904,20 @@ class AbsorptionRun:
                 else:
                     np.asarray(TAU, np.float32).tofile(name + '.bin')
 
-        if 2 <= U.FAST_MAP <= 998:
+        if maplevels:
+            # `maplevels 1`: the maps through the batch path (the same bytes), and per direction map_dir_XX_L.bin with the levels of
+            # every image of the plain file, in its order -- a .bin also where `fits` + `mapum` turn the plain maps into FITS files
+            lfps = [self._open_level_file(idir, sum(1 for q in sel if q[1])) for idir in range(NDIR)] if self.rank == 0 else []
+            views = [(ODIR[idir], RA[idir], DE[idir]) for idir in range(NDIR)]
+            for batch, planes in self._map_blocks(sel, emission, views, centre, LENGTH_f, levels=True):
+                for idir, (MAPX, TAUX, COLDEN, MAPL) in enumerate(planes):
+                    for k, (IFREQ, save_spe, save_tau, save_colden) in enumerate(batch):
+                        write(IFREQ, idir, MAPX[k], COLDEN if save_colden else TAUX[k], save_spe, save_tau, save_colden)
+                        if save_spe and lfps:
+                            np.asarray(MAPL[k], np.float32).tofile(lfps[idir])
+            for fp in lfps:
+                fp.close()
+        elif 2 <= U.FAST_MAP <= 998:
             # `mapping nx ny dx NF`: the same maps, up to NF frequencies per walk along the lines of sight
             views = [(ODIR[idir], RA[idir], DE[idir]) for idir in range(NDIR)]
             for batch, planes in self._map_blocks(sel, emission, views, centre, LENGTH_f):
@@ -905,6 +934,14 @@ class AbsorptionRun:
                     write(IFREQ, idir, MAP, TAU, save_spe, save_tau, save_colden)
         for fp in fps:
             fp.close()
+
+    def _open_level_file(self, idir, images):
+        """map_dir_XX_L.bin of `maplevels 1`: int32 NPIX.x, NPIX.y, int32 [images, LEVELS]; the caller appends per image LEVELS float32
+        planes [Jy/sr], plane l what the cells of level l add to the plain map's image."""
+        fp = open("map_dir_%02d_L.bin" % idir, "wb")
+        np.asarray([self.U.NPIX[0], self.U.NPIX[1]], np.int32).tofile(fp)
+        np.asarray([images, self.cloud.LEVELS], np.int32).tofile(fp)
+        return fp
 
     def write_level_maps(self, EMITTED):
         """`mapping nx ny dx 999` (a fourth argument >= 999): one image per hierarchy level (ASOC.py:3323-3438 -> the Mapping of
@@ -1110,7 +1147,17 @@ class AbsorptionRun:
         def emission(IFREQ, save_spe=True):
             return np.asarray(EMITTED[:, IFREQ - I1] * np.float32(KK) * np.float32(float(FFREQ[IFREQ])), np.float32)    # :3283
 
-        if 2 <= U.FAST_MAP <= 998:                                 # `mapping NSIDE -1 dx NF`: NF frequencies per walk
+        if getattr(U, "MAP_LEVELS", 0) > 0:                       # `maplevels 1`: the same map through the batch path, and its levels
+            lfp = self._open_level_file(0, len(sel)) if self.rank == 0 else None
+            for batch, planes in self._map_blocks([(i, True, 0, 0) for i in sel], emission, [(ODIR[0], RA[0], DE[0])], centre, LENGTH_f,
+                                                  healpix=NSIDE, levels=True):
+                for k in range(len(batch)):
+                    if fp:
+                        np.asarray(planes[0][0][k], np.float32).tofile(fp)
+                        np.asarray(planes[0][3][k], np.float32).tofile(lfp)
+            if lfp:
+                lfp.close()
+        elif 2 <= U.FAST_MAP <= 998:                               # `mapping NSIDE -1 dx NF`: NF frequencies per walk
             for batch, planes in self._map_blocks([(i, True, 0, 0) for i in sel], emission, [(ODIR[0], RA[0], DE[0])], centre, LENGTH_f,
                                                   healpix=NSIDE):
                 for k in range(len(batch)):
@@ -1126,12 +1173,13 @@ class AbsorptionRun:
         if fp:
             fp.close()
 
-    def _map_blocks(self, sel, emission, views, centre, LENGTH_f, healpix=0):
+    def _map_blocks(self, sel, emission, views, centre, LENGTH_f, healpix=0, levels=False):
         """`mapping nx ny dx NF` (2 <= NF <= 998; ASOC.py:3442-3568): the frequencies of sel = [(IFREQ, save_spe, save_tau,
         save_colden)] in batches of at most min(NF, engine.map_block_max).  A batch is uploaded once -- emission(IFREQ, save_spe)
         as the columns of EMITX[CELLS, nf], the opacities _optical_for sets for the plain path (with abundances the per-cell
         ones it builds, read back into OPTX[CELLS, nf, 2]) -- and mapped for every view = (DIR, RA, DE).  Yields (batch,
-        [(MAPX, TAUX, COLDEN) per view])."""
+        [(MAPX, TAUX, COLDEN) per view]); with levels (`maplevels 1`) every view's tuple has a fourth member, the planes
+        MAPL[nf, LEVELS, ...] of engine.map_block_levels for the same batch and view."""
         U, e, c = self.U, self.eng, self.cloud
         nb = max(1, min(int(U.FAST_MAP), int(e.map_block_max)))
         for b0 in range(0, len(sel), nb):
@@ -1147,8 +1195,12 @@ class AbsorptionRun:
                     EMITX[:, k] = emission(IFREQ, save_spe)
             e.set_map_block(EMITX, ABSX, SCAX, OPTX)
             del EMITX, OPTX
-            yield batch, [e.map_block(d, ra, de, U.NPIX, U.MAP_DX, centre, INTOBS=U.INTOBS, LENGTH=LENGTH_f, healpix=healpix)
-                          for d, ra, de in views]
+            planes = [e.map_block(d, ra, de, U.NPIX, U.MAP_DX, centre, INTOBS=U.INTOBS, LENGTH=LENGTH_f, healpix=healpix)
+                      for d, ra, de in views]
+            if levels:
+                planes = [tuple(p) + (e.map_block_levels(d, ra, de, U.NPIX, U.MAP_DX, centre, INTOBS=U.INTOBS, healpix=healpix),)
+                          for p, (d, ra, de) in zip(planes, views)]
+            yield batch, planes
         e.set_map_block(None)
 
     def _bcast_seed(self, seed):

@@ -283,7 +283,7 @@ int soc_set_grid(soc_ctx *c, int NX, int NY, int NZ, int LEVELS, const int32_t *
         c->have_emit = false;
         // everything else that is sized by the cell count
         c->dT.release();  c->dXAB.release();  c->dEMINDEX.release();  c->dBfield.release();
-        c->dMapXEmit.release();  c->dMapXOpt.release();  c->mapx_nf = 0;
+        c->dMapXEmit.release();  c->dMapXOpt.release();  c->dMapLOut.release();  c->mapx_nf = 0;
         if (c->dINTV) {                                       // INTX, INTY, INTZ follow the cell count like TABS and INT (with_int stays 2)
             c->dINTV.release();
             if (c->with_int == 2) {

@@ -225,7 +225,7 @@ int soc_map_set_block(soc_ctx *c, int nf, const float *EMITX, const float *ABSX,
     HIPCHK(c, hipSetDevice(c->device));
     if (nf == 0) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->dMapXEmit.release();  c->dMapXOpt.release();  c->dMapXOpa.release();  c->dMapXOut.release();
+        c->dMapXEmit.release();  c->dMapXOpt.release();  c->dMapXOpa.release();  c->dMapXOut.release();  c->dMapLOut.release();
         c->mapx_nf = 0;
         return SOC_OK;
     }
@@ -274,6 +274,49 @@ int soc_map_block(soc_ctx *c, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX,
     HIPCHK(c, hipMemcpyAsync(MAPX, A.MAP, nf * npix * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(TAUX, A.TAU, nf * npix * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(COLDEN, A.COLDEN, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
+// the levels of the plain map (`maplevels 1`; nothing in the reference -- its per-level Mapping is soc_map_levels): the resident
+// batch is read, the planes are a buffer of their own
+int soc_map_block_levels_width(soc_ctx *c)
+{
+    if (!c) return SOC_ERR_ARG;
+    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_map_block_levels_width: call soc_set_grid first");
+    return soc_maplevx_width(c->G.LEVELS);
+}
+
+int soc_map_block_levels(soc_ctx *c, int healpix, int NPIX_X, int NPIX_Y, float MAP_DX, const float *DIR, const float *RA, const float *DE,
+                         const float *CENTRE, const float *INTOBS, float *MAPL)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_map_block_levels: call soc_set_grid first");
+    if (c->mapx_nf < 1) return fail(c, SOC_ERR_ARG, "soc_map_block_levels: no batch is resident; soc_map_set_block with 1..%d frequencies first", SOC_MAPX_MAX);
+    if (!MAPL) return fail(c, SOC_ERR_ARG, "soc_map_block_levels: MAPL is needed");
+    if (int r = check_view(c, "soc_map_block_levels", healpix, NPIX_X, NPIX_Y, MAP_DX, DIR, RA, DE, CENTRE, INTOBS)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = healpix ? (size_t)12 * NPIX_X * NPIX_X : (size_t)NPIX_X * NPIX_Y;
+    const size_t nf = (size_t)c->mapx_nf, n = nf * (size_t)c->G.LEVELS * npix;
+    if (c->dMapLOut.n < n) {
+        // refused rather than tried: a failed allocation of this size would leave the handle with an error of the runtime's
+        size_t avail = 0, total = 0;
+        HIPCHK(c, hipMemGetInfo(&avail, &total));
+        if (c->dMapLOut.owned) avail += c->dMapLOut.bytes();
+        if (n * 4 > avail)
+            return fail(c, SOC_ERR_ARG, "soc_map_block_levels: %d frequencies x %d levels x %zu pixels are %.3f GiB of planes, %.3f GiB of device memory are free",
+                        c->mapx_nf, c->G.LEVELS, npix, (double)(n * 4) / 1073741824.0, (double)avail / 1073741824.0);
+        HIPCHK(c, c->dMapLOut.reset(n, c->stream));
+    }
+    SocMapLXArgs A;
+    memset(&A, 0, sizeof A);
+    fill_view(c, A, healpix, NPIX_X, NPIX_Y, MAP_DX, DIR, RA, DE, CENTRE, INTOBS, 1.0f);
+    A.nf = c->mapx_nf;
+    A.EMIT = c->dMapXEmit;  A.ABS = c->dMapXOpa;  A.SCA = c->dMapXOpa + nf;  A.OPT = c->dMapXOpt;
+    A.MAPL = c->dMapLOut;
+    HIPCHK(c, soc_launch_maplevx(c->G, A, c->stream));
+    HIPCHK(c, hipMemcpyAsync(MAPL, A.MAPL, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SOC_OK;
 }

@@ -169,6 +169,17 @@ struct SocMapXArgs : SocMapView {
     float *COLDEN;                 // [npix] column density x LENGTH
 };
 hipError_t soc_launch_mapx(const SocGrid &G, const SocMapXArgs &A, hipStream_t st);
+// the levels of the plain map (soc_map.hip: soc_maplevx_kernel, `maplevels 1`): the batch of SocMapXArgs, one plane per frequency and level
+struct SocMapLXArgs : SocMapView {
+    int   nf;                      // frequencies of the batch = row stride of EMIT and OPT
+    int   f0, kf;                  // one launch: its first column and its columns (set by soc_launch_maplevx)
+    const float  *EMIT;            // [CELLS][nf]
+    const float  *ABS, *SCA;       // [nf]: the scalar opacities (OPT == nullptr)
+    const float2 *OPT;             // [CELLS][nf] per-cell opacities, or nullptr
+    float *MAPL;                   // [nf][LEVELS][npix]
+};
+hipError_t soc_launch_maplevx(const SocGrid &G, const SocMapLXArgs &A, hipStream_t st);
+int soc_maplevx_width(int LEVELS);     // the most columns one launch takes
 // polarisation maps (soc_map.hip): one launch of PolMapping (kernel_ASOC_map.c:974-994, :1164-1184, :1600-1620)
 struct SocPolArgs {
     int   polstat;                 // -D POLSTAT: 0 = I, Q, U, column density; 1 = rT, rI, jT, jI; 3 = <B>, <B_LOS>, <B_POS>, tau

@@ -147,8 +147,8 @@ struct soc_ctx {
     // map making (soc_map.hip)
     DevBuf<float>  dMapEmit, dMap, dMapTau;
     // the resident batch of soc_map_set_block: emission [CELLS][mapx_nf], ABS | SCA [2 * mapx_nf], per-cell opacities (or none);
-    // the planes of soc_map_block: MAPX | TAUX | COLDEN
-    DevBuf<float>  dMapXEmit, dMapXOpa, dMapXOut;
+    // the planes of soc_map_block: MAPX | TAUX | COLDEN; those of soc_map_block_levels: MAPL[mapx_nf][LEVELS][npix], freed with the batch
+    DevBuf<float>  dMapXEmit, dMapXOpa, dMapXOut, dMapLOut;
     DevBuf<float2> dMapXOpt;
     int     mapx_nf = 0;               // 0: no batch
     DevBuf<float4> dBfield;            // magnetic field, one (Bx, By, Bz, pad) per cell (soc_set_bfield)

@@ -291,12 +291,17 @@ __device__ __forceinline__ SocMapStep soc_map_step(const SocGrid &G, const int *
     return S;
 }
 
-// what one frequency adds on a step (:825-846, :950-955): emission seen through the optical depth in front of it, then that depth grows
+// what one frequency adds on a step (:825-846, :950-955): emission seen through the optical depth in front of it, then that depth grows.
+// soc_map_weight is the head of that product, up to the step length; the term is soc_map_weight * emit * S.d0, multiplied from the left.
+__device__ __forceinline__ float soc_map_weight(const SocMapStep &S, float DTAU, float TAU)
+{
+    if (DTAU < 1.0e-3f) return soc_expf(-TAU) * (1.0f - 0.5f * DTAU) * S.sx;
+    return soc_expf(-TAU) * ((1.0f - soc_expf(-DTAU)) / DTAU) * S.sx;
+}
+
 __device__ __forceinline__ void soc_map_add(const SocMapStep &S, float emit, float DTAU, float &TAU, float &PHOTONS)
 {
-    if (!S.emits) { }
-    else if (DTAU < 1.0e-3f) PHOTONS += soc_expf(-TAU) * (1.0f - 0.5f * DTAU) * S.sx * emit * S.d0;
-    else                     PHOTONS += soc_expf(-TAU) * ((1.0f - soc_expf(-DTAU)) / DTAU) * S.sx * emit * S.d0;
+    if (S.emits) PHOTONS += soc_map_weight(S, DTAU, TAU) * emit * S.d0;
     TAU += DTAU;
 }
 
@@ -389,6 +394,91 @@ __global__ __launch_bounds__(256) void soc_mapx_kernel(const SocGrid G, const So
         }
     }
     A.COLDEN[id] = colden * A.LENGTH;
+}
+
+// The levels of the plain map (`maplevels 1`): the walk of soc_mapx_kernel with one accumulator per hierarchy level and frequency.
+// Plane (f, l) is, bit for bit, soc_map_kernel's map of frequency f when the emission of every cell not on level l is 0.0f and
+// everything else -- densities, opacities, view, switches -- stays: what level l emits towards the pixel, seen through all that lies in
+// front of it.  The reference has no such kernel; its per-level Mapping is soc_maplev_kernel below, on another walk.
+// On a step the cell crossed adds to the plane of its level.  With MAP_INTERPOLATION the blend of soc_map_blend is taken once per
+// distinct level among the cell and its two neighbours, the operands of the other levels replaced by 0.0f: a neighbour feeds the
+// plane of its own level.  (A level none of the three is on would get the blend of three zeros: +0, which changes no sum.)  Whether
+// the step emits (S.emits) and the density S.d0 are the crossed cell's, as in the plain kernel; TAU grows once per step and frequency.
+// The accumulators are LDS, lane-minor: word (l * KF + f) * 256 + tid of the dynamic array -- indexed by the run-time level without
+// scratch or a compare-select chain, touched by their own lane only (no barrier, no bank conflict), LEVELS * KF * 1 KiB per workgroup;
+// behind them OFF[] and OFF[] + LCELLS[] of every level.  A launch takes columns [A.f0, A.f0 + A.kf), kf <= KF, of the resident
+// cell-major batch [CELLS][A.nf]; columns outside are never read.
+template <bool OCT, bool DBL, bool ABU, int KF>
+__global__ __launch_bounds__(256) void soc_maplevx_kernel(const SocGrid G, const SocMapLXArgs A)
+{
+    extern __shared__ float soc_maplevx_lds[];
+    const int NL = G.LEVELS, tid = threadIdx.x;
+    int *sOFF = (int *)(soc_maplevx_lds + NL * KF * 256);
+    int *sEND = sOFF + SOC_MAXL;
+    if (tid < SOC_MAXL) { sOFF[tid] = G.OFF[tid];  sEND[tid] = G.OFF[tid] + G.LCELLS[tid]; }
+    __syncthreads();
+    const int npix = A.mode ? 12 * A.NPIX_X * A.NPIX_X : A.NPIX_X * A.NPIX_Y;
+    const int id = blockIdx.x * blockDim.x + tid;
+    if (id >= npix) return;
+    const int nf = A.nf, kf = A.kf;
+    float *acc = soc_maplevx_lds + tid;                                   // word (l, f) of this lane: acc[(l * KF + f) * 256]
+    for (int k = 0; k < NL * KF; k++) acc[k * 256] = 0.0f;
+    float TAU[KF], OPTSUM[KF];
+#pragma unroll
+    for (int f = 0; f < KF; f++) {
+        TAU[f] = 0.0f;
+        OPTSUM[f] = (!ABU && (f < kf)) ? (A.SCA[A.f0 + f] + A.ABS[A.f0 + f]) : 0.0f;
+    }
+    float px, py, pz, tx, ty, tz;
+    soc_map_entry(G, A, id, px, py, pz, tx, ty, tz);
+    int   level = 0, ind = -1;
+    float dens = 0.0f;
+    soc_indexg<OCT>(G, sOFF, px, py, pz, level, ind, dens);
+    const int MI = A.MAPINT;
+    SocMapCross X = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+    if (MI > 0) X = soc_map_cross(tx, ty, tz);
+    while (ind >= 0) {
+        const SocMapStep S = soc_map_step<OCT, DBL>(G, sOFF, A, X, px, py, pz, tx, ty, tz, level, ind, dens);
+        // the levels of the neighbours; a missing one contributes 0.0f whatever its level is called
+        int la = S.olevel, lb = S.olevel;
+        if (MI > 0) {
+            for (int l = 0; l < NL; l++) {
+                if ((S.na >= sOFF[l]) && (S.na < sEND[l])) la = l;
+                if ((S.nb >= sOFF[l]) && (S.nb < sEND[l])) lb = l;
+            }
+        }
+        const float  *E  = A.EMIT + (size_t)S.oind * nf + A.f0;
+        const float  *Ea = A.EMIT + (size_t)((S.na >= 0) ? S.na : 0) * nf + A.f0;
+        const float  *Eb = A.EMIT + (size_t)((S.nb >= 0) ? S.nb : 0) * nf + A.f0;
+        const float2 *O  = ABU ? (A.OPT + (size_t)S.oind * nf + A.f0) : nullptr;
+        float *acc0 = acc + S.olevel * (KF * 256), *acca = acc + la * (KF * 256), *accb = acc + lb * (KF * 256);
+#pragma unroll
+        for (int f = 0; f < KF; f++) {
+            if (f < kf) {
+                float DTAU;
+                if (ABU) { const float2 o = O[f];  DTAU = S.sx * S.d0 * (o.x + o.y); }
+                else     DTAU = S.sx * S.d0 * OPTSUM[f];
+                if (S.emits) {
+                    const float w = soc_map_weight(S, DTAU, TAU[f]);
+                    const float own = E[f];
+                    if (MI > 0) {
+                        const float a = (S.na >= 0) ? Ea[f] : 0.0f, b = (S.nb >= 0) ? Eb[f] : 0.0f;
+                        acc0[f * 256] += w * soc_map_blend(MI, S, own, (la == S.olevel) ? a : 0.0f, (lb == S.olevel) ? b : 0.0f) * S.d0;
+                        if (la != S.olevel) acca[f * 256] += w * soc_map_blend(MI, S, 0.0f, a, (lb == la) ? b : 0.0f) * S.d0;
+                        if ((lb != S.olevel) && (lb != la)) accb[f * 256] += w * soc_map_blend(MI, S, 0.0f, 0.0f, b) * S.d0;
+                    } else {
+                        acc0[f * 256] += w * own * S.d0;
+                    }
+                }
+                TAU[f] += DTAU;
+            }
+        }
+    }
+    for (int l = 0; l < NL; l++) {
+#pragma unroll
+        for (int f = 0; f < KF; f++)
+            if (f < kf) A.MAPL[((size_t)(A.f0 + f) * NL + l) * npix + id] = acc[(l * KF + f) * 256];
+    }
 }
 
 // PSTau (kernel_ASOC_map.c:1545-1584): column density and optical depth from every point source towards the observer
@@ -961,4 +1051,49 @@ hipError_t soc_launch_mapx(const SocGrid &G, const SocMapXArgs &A, hipStream_t s
     else if (!dbl) { if (abu) soc_mapx_dispatch<true, false, true>(G, A, grid, block, st);  else soc_mapx_dispatch<true, false, false>(G, A, grid, block, st); }
     else           { if (abu) soc_mapx_dispatch<true, true, true>(G, A, grid, block, st);   else soc_mapx_dispatch<true, true, false>(G, A, grid, block, st); }
     return hipGetLastError();
+}
+
+// The widths soc_maplevx_kernel is compiled for.  A launch's accumulators take LEVELS * KF KiB of LDS; the widest instance a model
+// uses keeps that at or below 64 KiB (8 columns up to 8 levels, 4 up to SOC_MAXL), so two workgroups fit a CU.
+int soc_maplevx_width(int LEVELS) { return (LEVELS <= 8) ? 8 : 4; }
+
+template <bool OCT, bool DBL, bool ABU, int KF>
+static hipError_t soc_maplevx_launch(const SocGrid &G, const SocMapLXArgs &A, dim3 grid, dim3 block, hipStream_t st)
+{
+    const size_t lds = (size_t)G.LEVELS * KF * 256 * sizeof(float) + 2 * SOC_MAXL * sizeof(int);
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)soc_maplevx_kernel<OCT, DBL, ABU, KF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    soc_maplevx_kernel<OCT, DBL, ABU, KF><<<grid, block, lds, st>>>(G, A);
+    return hipGetLastError();
+}
+
+template <bool OCT, bool DBL, bool ABU>
+static hipError_t soc_maplevx_dispatch(const SocGrid &G, const SocMapLXArgs &A, dim3 grid, dim3 block, hipStream_t st)
+{
+    if (A.kf == 1)      return soc_maplevx_launch<OCT, DBL, ABU, 1>(G, A, grid, block, st);
+    else if (A.kf <= 4) return soc_maplevx_launch<OCT, DBL, ABU, 4>(G, A, grid, block, st);
+    else                return soc_maplevx_launch<OCT, DBL, ABU, 8>(G, A, grid, block, st);
+}
+
+// all A.nf columns of the resident batch, in launches of at most soc_maplevx_width columns (A.f0 and A.kf are set here)
+hipError_t soc_launch_maplevx(const SocGrid &G, const SocMapLXArgs &A0, hipStream_t st)
+{
+    const int npix = A0.mode ? 12 * A0.NPIX_X * A0.NPIX_X : A0.NPIX_X * A0.NPIX_Y;
+    if (npix <= 0) return hipSuccess;
+    if (A0.nf < 1 || A0.nf > SOC_MAPX_MAX || G.LEVELS < 1 || G.LEVELS > SOC_MAXL) return hipErrorInvalidValue;
+    const dim3 grid((npix + 255) / 256), block(256);
+    const bool oct = G.LEVELS > 1, dbl = oct && (G.NX > 100), abu = A0.OPT != nullptr;   // kernel_ASOC_map.c:297
+    const int  width = soc_maplevx_width(G.LEVELS);
+    SocMapLXArgs A = A0;
+    for (A.f0 = 0; A.f0 < A.nf; A.f0 += width) {
+        A.kf = std::min(width, A.nf - A.f0);
+        hipError_t e;
+        if (!oct)      e = abu ? soc_maplevx_dispatch<false, false, true>(G, A, grid, block, st) : soc_maplevx_dispatch<false, false, false>(G, A, grid, block, st);
+        else if (!dbl) e = abu ? soc_maplevx_dispatch<true, false, true>(G, A, grid, block, st)  : soc_maplevx_dispatch<true, false, false>(G, A, grid, block, st);
+        else           e = abu ? soc_maplevx_dispatch<true, true, true>(G, A, grid, block, st)   : soc_maplevx_dispatch<true, true, false>(G, A, grid, block, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }

@@ -143,6 +143,7 @@ class User:
         s.ROIPAC = 0
         s.OUT_NSIDE = 128
         s.MAP_INTERPOLATION = 0
+        s.MAP_LEVELS = 0                 # `maplevels N` (not a key of the reference): N > 0 adds map_dir_XX_L.bin, the plain map split by hierarchy level
         s.FITS = 0
         s.FITS_PREFIX = 'map'
         s.FITS_RA = 0.0
@@ -386,6 +387,7 @@ _KEYWORDS = [
     ('split', 1, _set('DO_SPLIT', int)),
     ('maxsplit', 1, _set('MAX_SPLIT', int)),
     ('mapint', 1, _set('MAP_INTERPOLATION', int)),
+    ('maplevels', 1, _set('MAP_LEVELS', int)),
     ('polstat', 1, _set('POLSTAT', int)),
     ('absthin', 1, _set('ABSTHIN', int)),
     ('nnnlimit', 1, _set('NNNLIMIT', float)),

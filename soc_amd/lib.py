@@ -111,6 +111,8 @@ API = {
     "soc_map_block_max": (C.c_int, []),
     "soc_map_set_block": (C.c_int, [C.c_void_p, C.c_int, _F, _F, _F, _F]),
     "soc_map_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F, C.c_float, _F, _F, _F]),
+    "soc_map_block_levels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F, _F]),
+    "soc_map_block_levels_width": (C.c_int, [C.c_void_p]),
     "soc_set_bfield": (C.c_int, [C.c_void_p, _F, _F, _F]),
     "soc_polmap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F,
                              C.c_float, C.c_float, C.c_float, _F]),
@@ -607,6 +609,29 @@ class Engine:
         self._chk(self.lib.soc_map_block(self.h, int(bool(healpix)), nx, ny, np.float32(MAP_DX), _f(v[0]), _f(v[1]), _f(v[2]), _f(v[3]),
                                          _f(v[4]), np.float32(LENGTH), _f(MAPX), _f(TAUX), _f(COLDEN)))
         return MAPX, TAUX, COLDEN
+
+    def map_block_levels(self, DIR, RA, DE, NPIX, MAP_DX, CENTRE, INTOBS=None, healpix=0):
+        """The levels of the plain map (`maplevels 1`) for the resident batch and one view, with the arguments and switches of
+        map_block: [nf, LEVELS, NPIX.y, NPIX.x] -- or [nf, LEVELS, 12*NSIDE^2] with healpix = NSIDE.  Plane (f, l) is, bit for
+        bit, what map gives for frequency f when the emission of every cell not on level l is 0: what level l emits towards the
+        pixel, seen through everything in front of it.  The planes of a pixel add up to map_block's value up to the order of
+        the additions.  The batch is read, not changed.  Not the reference's per-level product: that is map_levels."""
+        v = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).ravel()[:3]) for a in (DIR, RA, DE, CENTRE, INTOBS)]
+        nx, ny = (int(healpix), 1) if healpix else (int(NPIX[0]), int(NPIX[1]))
+        shape = (12 * nx * nx,) if healpix else (max(ny, 0), max(nx, 0))
+        nf = getattr(self, "_map_block_nf", 0)
+        MAPL = np.zeros((nf, self.LEVELS) + shape, np.float32)
+        self._chk(self.lib.soc_map_block_levels(self.h, int(bool(healpix)), nx, ny, np.float32(MAP_DX), _f(v[0]), _f(v[1]), _f(v[2]),
+                                                _f(v[3]), _f(v[4]), _f(MAPL)))
+        return MAPL
+
+    @property
+    def map_block_levels_width(self):
+        """the most frequencies one launch of map_block_levels' kernel takes for the model set (wider batches: several launches)"""
+        w = int(self.lib.soc_map_block_levels_width(self.h))
+        if w < 1:
+            self._chk(w)
+        return w
 
     def map_levels(self, EMIT, DIR, RA, DE, NPIX, MAP_DX, CENTRE, ABS, SCA, INTOBS=None):
         """One image per hierarchy level (the Mapping of kernel_ASOC_map_H.c, `mapping nx ny dx 999`): [LEVELS, NPIX.y, NPIX.x],
