@@ -600,6 +600,20 @@ __device__ __forceinline__ void soc_brick_walk(const SocGrid &G, const SocSimPac
 // ---------------------------------------------------------------------------------------
 #define SOC_LT_ARRIVE 0x80000000u
 #define SOC_LQ_SHIFT 24           // packet word C.w of this form: cz | launch << 24 (coordinates stay below 2^24, see soc_brick_run_pb)
+// What a lane of soc_lbrick_walk does next, one code per lane.  STAY: it steps.  OWN .. DONE: its packet goes back to memory, to the queue the
+// code names -- the swap arm forms the key where it stores the packet; the step arm only writes the code.  LEAVE .. LOST are
+// 1 + the outcome of soc_lt_aim / soc_lt_land (SOC_LT_LEAVE, _EXIT, _SLOW, _LOST).  NONE: a lane that holds no packet and takes up the next one,
+// IDLE: nothing is left for it.
+enum { SOC_OC_STAY = 0, SOC_OC_OWN = 1, SOC_OC_LEAVE = 2, SOC_OC_EXIT = 3, SOC_OC_SLOW = 4, SOC_OC_LOST = 5, SOC_OC_SCAT = 6, SOC_OC_ROI = 7, SOC_OC_DONE = 8,
+       SOC_OC_NONE = 9, SOC_OC_IDLE = 10 };
+// the event queue of a code, counted from the first event queue of the packet's launch: creation (EXIT, DONE) 0, scattering 1, slow step 2,
+// ROI entry 3 -- four bits per code, in one 32-bit word: codes 0 .. 7 have a nibble of their own, and DONE (8) reads nibble 0 through the
+// wrapped shift (4 * 8) & 31 = 0, which holds the 0 it needs.  A code above 8, or another queue for STAY or DONE, needs a wider table.
+#define SOC_OC_EVQ 0x31020000u
+#define SOC_OC_EVQ_OF(oc) ((SOC_OC_EVQ >> ((4 * (oc)) & 31)) & 15u)
+static_assert(SOC_OC_EVQ_OF(SOC_OC_EXIT) == 0 && SOC_OC_EVQ_OF(SOC_OC_DONE) == 0 && SOC_OC_EVQ_OF(SOC_OC_SCAT) == 1 && SOC_OC_EVQ_OF(SOC_OC_SLOW) == 2
+              && SOC_OC_EVQ_OF(SOC_OC_ROI) == 3 && SOC_OC_DONE == 8 && SOC_OC_NONE == 9, "the event queue of every code that is stored, the wrap of DONE included");
+static_assert(SOC_OC_LEAVE == SOC_LT_LEAVE + 1 && SOC_OC_EXIT == SOC_LT_EXIT + 1 && SOC_OC_SLOW == SOC_LT_SLOW + 1 && SOC_OC_LOST == SOC_LT_LOST + 1, "outcome codes follow soc_ltree.h");
 
 // integer coordinates of cell (level, ind) on its level: octants on the way up through PAR, then the root cell
 __device__ __forceinline__ void soc_cell_coords(const SocGrid &G, const int *sOFF, int level, int ind, int &cx, int &cy, int &cz)
@@ -715,12 +729,13 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
     float rux = 1.0f, ruy = 1.0f, ruz = 1.0f;              // correctly rounded reciprocals of the direction
     float gx = 0.0f, gy = 0.0f, gz = 0.0f;                 // GetStep's target inside the cell per axis: 1 + PEPS or -PEPS
     float kabs = 0.0f, ksca = 0.0f, tw = 0.0f;
-    int   cx = 0, cy = 0, cz = 0, level = 0, slot = 0, obase = 0, nvisit = 0, key = 0, cslot = 0, lq = 0, evq = 0;      // evq: first event queue of the packet's launch      // obase: slot of the first cell of the packet's octet
+    int   cx = 0, cy = 0, cz = 0, level = 0, slot = 0, obase = 0, nvisit = 0, cslot = 0, lq = 0;      // obase: slot of the first cell of the packet's octet
+    int   kl = 0;                                          // -1 - root cell the last step ended in: the queue key of a packet that leaves (the pass epilogue looks the brick up)
     int   what = SOC_LTM_STEP;                              // what the Index() part has to do for the lane: finish a step, an arrival, or find the packet's cell
     bool  nonudge = false;                                 // SimRAM_CL: no nudge after a failed step (kernel_ASOC.c:1530-1540 has none)
     bool  dblstep = false;                                 // LIM: the launch adds the 1e-6 of a peel-off step in double (SimRAM_PB)
     uint32_t dz = 0, dw = 0, wid = 0;
-    int   mode = SOC_BM_SWAP;
+    int   oc = SOC_OC_NONE;
     bool  have = false, nhave = false;                                       // the packet in hand, the prefetched one
     soc_f4v na = { 0.0f, 0.0f, 0.0f, 0.0f }, nb = na, nc = na;
     soc_u2v ndzw = { 0u, 0u };
@@ -740,20 +755,20 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
     // per arm, not once per read.
     while (!parked) {
         {
-            SOC_PROF(0, 1);  SOC_PROF(1, __popcll(__ballot(mode == SOC_BM_STEP)));  SOC_PROF(7, __popcll(__ballot(mode == SOC_BM_IDLE)));
-            if (D.count < 4 * nthr)  { SOC_DPROF(0, 1);  SOC_DPROF(1, __popcll(__ballot(mode == SOC_BM_IDLE))); }
-            if (D.count < 16 * nthr) { SOC_DPROF(2, 1);  SOC_DPROF(3, __popcll(__ballot(mode == SOC_BM_IDLE))); }
-            if (__ballot(nhave | nnhave) == 0ull) { SOC_DPROF(4, 1);  SOC_DPROF(5, __popcll(__ballot(mode == SOC_BM_IDLE))); }
+            SOC_PROF(0, 1);  SOC_PROF(1, __popcll(__ballot(oc == SOC_OC_STAY)));  SOC_PROF(7, __popcll(__ballot(oc == SOC_OC_IDLE)));
+            if (D.count < 4 * nthr)  { SOC_DPROF(0, 1);  SOC_DPROF(1, __popcll(__ballot(oc == SOC_OC_IDLE))); }
+            if (D.count < 16 * nthr) { SOC_DPROF(2, 1);  SOC_DPROF(3, __popcll(__ballot(oc == SOC_OC_IDLE))); }
+            if (__ballot(nhave | nnhave) == 0ull) { SOC_DPROF(4, 1);  SOC_DPROF(5, __popcll(__ballot(oc == SOC_OC_IDLE))); }
             // (tuning tail_lanes: a long chunk is used up and that many lanes of the wave are out of work -- the others send their packets back
             //  to this brick's queue instead of finishing their visits before mostly idle lanes.  Only packets that have made a step in this
             //  visit, and only in chunks of at least 8 packets per lane: every pass makes progress, short queues run to their end.)
-            if (A.TAIL > 0 && D.count >= 8 * nthr && __popcll(__ballot(mode == SOC_BM_IDLE)) >= A.TAIL
-                && mode == SOC_BM_STEP && what == SOC_LTM_STEP && nvisit > 0) { mode = SOC_BM_SWAP;  key = D.brick; }
-            const unsigned long long m = __ballot(mode == SOC_BM_SWAP);
-            const bool nobody_steps = (__ballot(mode == SOC_BM_STEP) == 0ull);
+            if (A.TAIL > 0 && D.count >= 8 * nthr && __popcll(__ballot(oc == SOC_OC_IDLE)) >= A.TAIL
+                && oc == SOC_OC_STAY && what == SOC_LTM_STEP && nvisit > 0) oc = SOC_OC_OWN;
+            const unsigned long long m = __ballot(oc - 1u < (unsigned)SOC_OC_NONE);
+            const bool nobody_steps = (__ballot(oc == SOC_OC_STAY) == 0ull);
             if (m != 0ull && (nobody_steps || __popcll(m) >= A.FTH)) {
                 SOC_PROF(4, 1);  SOC_PROF(5, __popcll(m));
-                if (mode == SOC_BM_SWAP) {
+                if (oc - 1u < (unsigned)SOC_OC_NONE) {
                     // A lane holds three packets: the one it walks, the next one, whose record was asked for when the
                     // current one was taken up, and the one after that, of which the id has been asked for -- each a
                     // visit ahead of its use, so nothing in this arm waits for global memory.  The chunk itself is never
@@ -785,8 +800,15 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                         { const soc_f4v v = { px, py, pz, photons };  SOC_NT_STORE(v, (SOC_GLOBAL soc_f4v *)&q->A); }
                         { const soc_f4v v = { tau, __int_as_float(cx), __int_as_float(cy), __int_as_float(cz | (lq << SOC_LQ_SHIFT)) };  SOC_NT_STORE(v, (SOC_GLOBAL soc_f4v *)&q->C); }
                         q->D.z = (dz & 0x1fffffffu) | ((uint32_t)level << 29);
-                        q->D.w = dw;
+                        // (a step that another brick or the slow-step queue completes: old cell + advanced position)
+                        q->D.w = dw | (((oc == SOC_OC_LEAVE) | (oc == SOC_OC_SLOW)) ? SOC_LT_ARRIVE : 0u);
                         if (LIM) SOC_NT_STORE(free_path, &q->B.w);                 // (the distance a peel-off ray has left)
+                        // where the packet goes: its own queue again (step budget used, tail cut-off), the brick of the root cell it steps
+                        // into (looked up after the walk: -1 - root cell; N < 4096), an event queue of its launch (creation: outside the model or
+                        // a ray done; scattering; slow step: old cell, advanced position; ROI entry), or -- cannot happen, the sender looked the
+                        // brick up -- retirement
+                        const int evk = A.NBQ + A.EQ * lq + (int)SOC_OC_EVQ_OF(oc);
+                        const int key = (oc == SOC_OC_OWN) ? D.brick : ((oc == SOC_OC_LEAVE) ? kl : ((oc == SOC_OC_LOST) ? (NQ - 1) : evk));
                         SOC_NT_STORE((uint32_t)key, &keyq_c[cslot]);              // its rank in that queue is settled after the walk, for all packets at once
                     }
                     // (4) the prefetched packet becomes the current one
@@ -800,12 +822,11 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                         gx = (ux > 0.0f) ? (1.0f + SOC_PEPS) : -SOC_PEPS;  gy = (uy > 0.0f) ? (1.0f + SOC_PEPS) : -SOC_PEPS;  gz = (uz > 0.0f) ? (1.0f + SOC_PEPS) : -SOC_PEPS;
                         tau = nc.x;  cx = __float_as_int(nc.y);  cy = __float_as_int(nc.z);  cz = n_cz & ((1 << SOC_LQ_SHIFT) - 1);
                         lq = n_lq;                                                // the launch of the work item
-                        evq = A.NBQ + A.EQ * n_lq;
                         level = (int)(dz >> 29);
                         kabs = l4.x;  ksca = l4.y;  tw = l4.z;  nonudge = RAY || ((__float_as_int(l4.w) & 1) != 0);
                         if (LIM) dblstep = (__float_as_int(l4.w) & 2) != 0;
                         nvisit = 0;
-                        mode = have ? SOC_BM_STEP : mode;
+                        oc = have ? SOC_OC_STAY : oc;
                         slot = -1;  obase = -1;
                         // The first pass of the packet through the Index() part finds its cell in this brick: the second half of
                         // the step that brought it here (ARRIVE), or the cell its coordinates name.  A root-level packet in (or
@@ -832,13 +853,16 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                     nnslot = __builtin_amdgcn_readfirstlane(base) + rank;
                     nnhave = nnslot < D.count;
                     if (nnhave) nnwid = SOC_NT_LOAD(&idq_c[nnslot]);
-                    if (!have) mode = (nhave | nnhave) ? SOC_BM_SWAP : SOC_BM_IDLE;      // (the first two turns of a lane only reserve)
+                    if (!have) oc = (nhave | nnhave) ? SOC_OC_NONE : SOC_OC_IDLE;      // (the first two turns of a lane only reserve)
                 }
             }
         }
         SOC_PROF_T(0);                                     // swap
-        if (__ballot(mode != SOC_BM_IDLE) == 0ull) break;
-        if (mode == SOC_BM_STEP) {
+        if (__ballot(oc != SOC_OC_IDLE) == 0ull) break;
+#if defined(SOC_BRICK_PROF)
+        int prof_trips = 0;                                // trips of this lane through the descent loop of soc_lt_land in this iteration
+#endif
+        if (oc == SOC_OC_STAY) {
             bool move = true;
             const int slot0 = slot;
             float tauA = 0.0f, dtau = 0.0f;
@@ -874,11 +898,11 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                     scat = !lim & (free_path < (tau + dtau));
                     tau = stop ? (tau + dtau) : tau;
                     n_tally += stop ? 1u : 0u;
-                    mode = stop ? SOC_BM_SWAP : mode;  key = stop ? evq : key;
+                    oc = stop ? SOC_OC_DONE : SOC_OC_STAY;
                     move = !stop;
                 }
                 px = scat ? p0x : px;  py = scat ? p0y : py;  pz = scat ? p0z : pz;   // back to the start of the step
-                mode = scat ? SOC_BM_SWAP : mode;  key = scat ? (evq + 1) : key;  // -> scattering queue of its launch
+                oc = scat ? SOC_OC_SCAT : oc;                                      // -> scattering queue of its launch
                 move = move & !scat;
             }
             // ---- Index (kernel_ASOC_aux.c:198-278), first half: where the point is, and the read of the slot the descent starts from;
@@ -908,26 +932,19 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                     nvisit += inside ? 1 : 0;
                     // where the ray goes when it does not stay: its own queue again (step budget used), the brick of the root cell it steps
                     // into (looked up after the walk: -1 - root cell), queue 0 of its launch (outside the model)
-                    const int kleave = -1 - SOC_MAD24(SOC_MAD24(iz, NY, iy), NX, ix);
-                    const bool out = !inside | (nvisit >= A.KCAP);
-                    key  = out ? (inside ? D.brick : (outside ? evq : kleave)) : key;
-                    mode = out ? SOC_BM_SWAP : mode;
-                    dw  |= (!inside & !outside) ? SOC_LT_ARRIVE : 0u;
+                    kl = -1 - SOC_MAD24(SOC_MAD24(iz, NY, iy), NX, ix);
+                    oc = inside ? ((nvisit >= A.KCAP) ? SOC_OC_OWN : SOC_OC_STAY) : (outside ? SOC_OC_EXIT : SOC_OC_LEAVE);
                 }
                 SOC_PROF_T(2);
             } else
             if (move) {
                 SocLtAim AM;
-                int   r;
-                float rec = 1.0f;
-                if ((A.slow_every > 0) && (what == SOC_LTM_STEP) && (level > 0) && (((n_tally + 1u + wid) % (unsigned)A.slow_every) == 0u)) {
-                    r = SOC_LT_SLOW;                                              // test knob: this step goes through the slow-step queue
-                    AM = SocLtAim{};
-                } else {
-                    soc_lt_aim(KB, NX, NY, NZ, Lmax, kexp, what, px, py, pz, level, cx, cy, cz, obase, AM);
-                    r = AM.r;
-                    rec = sD[AM.s];
-                }
+                soc_lt_aim(KB, NX, NY, NZ, Lmax, kexp, what, px, py, pz, level, cx, cy, cz, obase, AM);
+                int   r = AM.r;
+                const float rec = sD[AM.s];
+                // test knob: this step goes through the slow-step queue (as a select on the outcome: a branch around soc_lt_aim gave every
+                // lane the moves that merge its results with the other side's, in every iteration)
+                if ((A.slow_every > 0) && (what == SOC_LTM_STEP) && (level > 0) && (((n_tally + 1u + wid) % (unsigned)A.slow_every) == 0u)) r = SOC_LT_SLOW;
                 // the tally of the step.  A lane that only places its packet (no GetStep: tauA = dtau = 0) adds zeros to slot 0
                 // and multiplies its photons by exp(-0) = 1: cheaper than a branch of its own
                 {
@@ -947,22 +964,23 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                 }
                 SOC_PROF_T(1);                                 // GetStep + tally
                 const int orx = cx >> level, ory = cy >> level, orz = cz >> level;      // (the root cell the step starts from: for the record of packets entering ROI)
+#if defined(SOC_BRICK_PROF)
+                const bool prof_lands = (r == SOC_LT_INSIDE);
+#endif
                 if (r == SOC_LT_INSIDE) r = soc_lt_land(sD, AM, Lmax, what, rec, px, py, pz, level, cx, cy, cz, slot, obase, dens);
+#if defined(SOC_BRICK_PROF)
+                prof_trips = prof_lands ? (level - AM.l) : 0;
+#endif
                 const bool inside = (r == SOC_LT_INSIDE);
                 const bool moved  = inside & (what != SOC_LTM_PLACE);
                 // failed step: nudge (SimRAM_PB / HP only); + 0 * u leaves the position as it is
                 const float nz = (moved & !nonudge & (slot == slot0)) ? SOC_PEPS : 0.0f;
                 px += nz * ux;  py += nz * uy;  pz += nz * uz;
                 nvisit += moved ? 1 : 0;
-                const bool leave = (r == SOC_LT_LEAVE), slowq = (r == SOC_LT_SLOW);
-                // where the packet goes when it does not stay: its own queue again (step budget used), the brick of the root cell it
-                // steps into (looked up after the walk: -1 - root cell; N < 4096), the creation queue of its launch (outside the model),
-                // the slow-step queue (old cell, advanced position), or -- cannot happen, the sender looked the brick up -- retirement
-                const int kleave = -1 - SOC_MAD24(SOC_MAD24(AM.Rz, NY, AM.Ry), NX, AM.Rx);
-                const int kout = leave ? kleave : ((r == SOC_LT_EXIT) ? evq : (slowq ? (evq + 2) : (NQ - 1)));
-                const bool out = !inside | (moved & (nvisit >= A.KCAP));
-                key  = out ? (inside ? D.brick : kout) : key;
-                mode = out ? SOC_BM_SWAP : mode;
+                // the outcome code when the packet does not stay (the swap arm makes the queue key of it): its own queue again (step budget
+                // used), or what soc_lt_aim / soc_lt_land said; the root cell the step ended in, should it be another brick's
+                kl = -1 - SOC_MAD24(SOC_MAD24(AM.Rz, NY, AM.Ry), NX, AM.Rx);
+                oc = inside ? ((moved & (nvisit >= A.KCAP)) ? SOC_OC_OWN : SOC_OC_STAY) : (r + 1);
                 if (!RAY && A.roi_on) {
                     // WITH_ROI_SAVE (kernel_ASOC.c:615-642, :1510-1535), at the end of a full step: the packet was outside ROI and is inside
                     // now -> the event workgroups add it to the record (root position, direction, photons) and send it back here
@@ -970,14 +988,19 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                     const bool was = (orx >= rx0) & (orx <= rx1) & (ory >= ry0) & (ory <= ry1) & (orz >= rz0) & (orz <= rz1);
                     const bool is  = (nrx >= rx0) & (nrx <= rx1) & (nry >= ry0) & (nry <= ry1) & (nrz >= rz0) & (nrz <= rz1);
                     const bool entered = moved & is & !was;
-                    key  = entered ? (evq + 3) : key;
-                    mode = entered ? SOC_BM_SWAP : mode;
+                    oc = entered ? SOC_OC_ROI : oc;
                 }
-                dw  |= (leave | slowq) ? SOC_LT_ARRIVE : 0u;
                 what = SOC_LTM_STEP;
             }
             SOC_PROF_T(2);                                 // Index
         }
+#if defined(SOC_BRICK_PROF)
+        {   // the descent loop: trips of the wave (its deepest lane), lanes that make at least one trip, wave-iterations with two or more trips
+            int wtrips = 0;
+            for (int t = 1; t < SOC_MAXL; t++) wtrips += (__ballot(prof_trips >= t) != 0ull) ? 1 : 0;
+            SOC_PROF(2, wtrips);  SOC_PROF(3, __popcll(__ballot(prof_trips >= 1)));  SOC_PROF(6, (wtrips >= 2) ? 1 : 0);
+        }
+#endif
     }
 
     SOC_PROF_T(5);                                         // (what the last iteration left: next to nothing)

@@ -53,6 +53,9 @@ SOC_HD int soc_lt_link(float d) { return (int)(soc_f2u(d) ^ 0x80000000u); }
 // exact 2^k for -126 <= k <= 127
 SOC_HD float soc_lt_pow2(int k) { return soc_u2f((uint32_t)(127 + k) << 23); }
 
+// x | y << 1 | z << 2 of three octant bits (each 0 or 1), as two shift-and-adds
+SOC_HD unsigned soc_lt_octant(unsigned x, unsigned y, unsigned z) { return x + ((y + (z << 1)) << 1); }
+
 // Is the step one that Index() (double) would not resolve by exact geometry?  level > 0, pos after the step.
 // thr = 2^(k + level - 30): below it pos/2^level + root coordinate has more than 53 significant bits.
 SOC_HD bool soc_lt_degenerate(float px, float py, float pz, float flx, float fly, float flz, float thr)
@@ -128,7 +131,8 @@ SOC_HD void soc_lt_aim(const SocLBrick &K, const int NX, const int NY, const int
     const bool inbox = !(((unsigned)rx >= (unsigned)K.bx) | ((unsigned)ry >= (unsigned)K.by) | ((unsigned)rz >= (unsigned)K.bz));
     const bool outside = out0 | ((unsigned)A.Rx >= (unsigned)NX) | ((unsigned)A.Ry >= (unsigned)NY) | ((unsigned)A.Rz >= (unsigned)NZ);
     const int  sroot = SOC_MAD24(SOC_MAD24(rz, K.by, ry), K.bx, rx);
-    const int  ssib  = obase + (((Jx >> D) & 1) | (((Jy >> D) & 1) << 1) | (((Jz >> D) & 1) << 2));
+    // (the octant of a sibling: J < 2^(D+1) on every axis, so J >> D is the octant bit itself, no mask; read only where sib holds)
+    const int  ssib  = obase + (int)soc_lt_octant((unsigned)Jx >> D, (unsigned)Jy >> D, (unsigned)Jz >> D);
     const bool go = !slow & (sib | (inbox & !out0));
     A.s = go ? (sib ? ssib : sroot) : 0;
     A.l = sib ? L : 0;

@@ -110,6 +110,9 @@ def main():
                       "wave cycles: swap %.1f %%, GetStep + tally %.1f %%, Index %.1f %%" % (
                           p[0], p[1] / max(p[0], 1), p[7] / max(p[0], 1), p[0] / max(p[4], 1), p[5] / max(p[4], 1),
                           100 * p[8] / tt, 100 * p[9] / tt, 100 * p[10] / tt), flush=True)
+                if p[2] or p[3]:
+                    print("   descent loop of soc_lt_land: %.3f trips per wave-iteration, %.1f lanes with a trip, two or more trips in %.1f %% of the wave-iterations" % (
+                        p[2] / max(p[0], 1), p[3] / max(p[0], 1), 100 * p[6] / max(p[0], 1)), flush=True)
                 if p[11] or p[12]:
                     life = max(sum(p[8:16]), 1)
                     print("   a wave's life in its workgroup: prologue %.1f %%, loop %.1f %%, wait for the workgroup's other waves %.1f %%, tallies to global memory %.1f %%, "
