@@ -523,6 +523,11 @@ int soc_ps_tau(soc_ctx *ctx, int NO_PS, const float *PSPOS, const float *DIR, fl
 int soc_a2e_set_size(soc_ctx *ctx, int NE, int NFREQ, int noIw, const float *Iw, const int32_t *L1,
                      const int32_t *L2, const float *Tdown, const float *EA, const int32_t *Ibeg, const float *AF);
 
+/* how DoSolve is launched for the size last given to soc_a2e_set_size (read-only; nothing runs): out[0] cells per workgroup
+ * (4, 2 or 1), out[1] threads per workgroup (256 or 1024), out[2] bytes of dynamic LDS.  SOC_ERR_STATE before any
+ * soc_a2e_set_size.  A size of which not one cell fits the 160 KB of LDS is refused by soc_a2e_set_size itself. */
+int soc_a2e_launch_shape(soc_ctx *ctx, int out[3]);
+
 /* replaces enqueue_copy(ABS_buf) + DoSolve(...) + enqueue_copy(emit, EMIT_buf) for one batch of
  * cells (A2E.py:387-412 -> kernel_A2E.c:2-104): AABS, AEMIT are [batch*NFREQ] host arrays */
 int soc_a2e_solve(soc_ctx *ctx, int batch, const float *AABS, float *AEMIT);

@@ -5,7 +5,8 @@
 // interleaved by LOCAL (NE=128 -> 266 MB per batch of 8192 cells; the source comments put
 // most of the run time into building and re-reading it), a private XL[NE].
 //
-// Here: a workgroup of sixteen waves solves C cells (C = 4 where four matrices fit the CU's LDS: NE <= 128); L lives in LDS
+// Here: a workgroup of sixteen waves solves C cells (C = 4, 2 or 1: the largest with C*per_cell + 4*NFREQ <= 160 KB of LDS,
+// per_cell = 4*((NE^2-NE)/2 + NE + NFREQ) -- soc_a2e_shape; at NFREQ = 50 that is 4 up to NE = 142, 2 up to 201, 1 up to 280); L lives in LDS
 // (32.5 KB per cell at NE=128) and never touches HBM:
 //   1. heating rates, by ALL lanes of the workgroup for ALL its cells: the (l,u) pairs are spread over the 1024 lanes; a lane
 //      reads a pair's integration weights once and adds them up for its C cells (the weights are the same for every cell:
@@ -273,15 +274,33 @@ hipError_t soc_launch_eqsolver(const SocEqTArgs &A, hipStream_t st)
     return hipGetLastError();
 }
 
+// the launch shape of DoSolve for one problem size, the only place that chooses it: out = { cells per workgroup, threads per
+// workgroup, bytes of dynamic LDS }; false where not even one cell fits the CU's LDS (out[2] then holds the bytes one cell needs)
+bool soc_a2e_shape(int NE, int NFREQ, int out[3])
+{
+    // cells per workgroup: four (one per wave) where their matrices fit the 160 KB of LDS, else two, else one
+    const size_t per_cell = ((size_t)(NE * NE - NE) / 2 + (size_t)NE + (size_t)NFREQ) * 4, shared = (size_t)NFREQ * 4;
+    if (per_cell + shared > SOC_A2E_LDS) {
+        out[0] = out[1] = 0;
+        out[2] = (per_cell + shared > 0x7fffffff) ? 0x7fffffff : (int)(per_cell + shared);
+        return false;
+    }
+    const int C = (4 * per_cell + shared <= SOC_A2E_LDS) ? 4 : (2 * per_cell + shared <= SOC_A2E_LDS) ? 2 : 1;
+    const size_t lds = C * per_cell + shared;
+    out[0] = C;
+    // sixteen waves per workgroup where one workgroup fills the CU's LDS; four where four or more fit (NE <= 70 at NFREQ = 50)
+    out[1] = (lds * 4 <= SOC_A2E_LDS) ? 256 : A2E_T;
+    out[2] = (int)lds;
+    return true;
+}
+
 template <int C>
-static hipError_t a2e_launch(const SocA2EArgs &A, size_t lds, hipStream_t st)
+static hipError_t a2e_launch(const SocA2EArgs &A, int T, size_t lds, hipStream_t st)
 {
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void *)soc_a2e_dosolve_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    // sixteen waves per workgroup where one workgroup fills the CU's LDS; four where four or more fit (NE <= 64)
-    const int T = (lds * 4 <= 160 * 1024) ? 256 : A2E_T;
     soc_a2e_dosolve_kernel<C><<<(A.batch + C - 1) / C, T, lds, st>>>(A);
     return hipGetLastError();
 }
@@ -289,12 +308,11 @@ static hipError_t a2e_launch(const SocA2EArgs &A, size_t lds, hipStream_t st)
 hipError_t soc_launch_a2e_dosolve(const SocA2EArgs &A, hipStream_t st)
 {
     if (A.batch <= 0) return hipSuccess;
-    // cells per workgroup: four (one per wave) where their matrices fit the 160 KB of LDS, else two, else one
-    const size_t per_cell = (size_t)((A.NE * A.NE - A.NE) / 2 + A.NE + A.NFREQ) * 4, shared = (size_t)A.NFREQ * 4;
-    if (per_cell + shared > 160 * 1024) return hipErrorInvalidValue;
-    if (4 * per_cell + shared <= 160 * 1024) return a2e_launch<4>(A, 4 * per_cell + shared, st);
-    if (2 * per_cell + shared <= 160 * 1024) return a2e_launch<2>(A, 2 * per_cell + shared, st);
-    return a2e_launch<1>(A, per_cell + shared, st);
+    int shape[3];
+    if (!soc_a2e_shape(A.NE, A.NFREQ, shape)) return hipErrorInvalidValue;
+    if (shape[0] == 4) return a2e_launch<4>(A, shape[1], (size_t)shape[2], st);
+    if (shape[0] == 2) return a2e_launch<2>(A, shape[1], (size_t)shape[2], st);
+    return a2e_launch<1>(A, shape[1], (size_t)shape[2], st);
 }
 
 hipError_t soc_launch_a2e_eqtemp(const SocEqTArgs &A, hipStream_t st)

@@ -15,6 +15,10 @@ int soc_a2e_set_size(soc_ctx *c, int NE, int NFREQ, int noIw, const float *Iw, c
     FLUSH(c);
     if (NE < 3 || NE > 280 || NFREQ < 2 || noIw < 0 || !Iw || !L1 || !L2 || !Tdown || !EA || !Ibeg || !AF)
         return fail(c, SOC_ERR_ARG, "soc_a2e_set_size: bad arguments (3 <= NE <= 280, NFREQ >= 2)");
+    int shape[3];
+    if (!soc_a2e_shape(NE, NFREQ, shape))                   // (refused here, with the tables of the size before untouched, not at the launch)
+        return fail(c, SOC_ERR_ARG, "soc_a2e_set_size: NE = %d with NFREQ = %d needs %d bytes of LDS for one cell, the limit is %d",
+                    NE, NFREQ, shape[2], SOC_A2E_LDS);
     // pair tables in the reference's (l, u) loop order; validate every window on the host
     const int npair = (NE * NE - NE) / 2;
     std::vector<int> first(npair), last(npair), off(npair), dst(npair);
@@ -57,6 +61,14 @@ int soc_a2e_set_size(soc_ctx *c, int NE, int NFREQ, int noIw, const float *Iw, c
     HIPCHK(c, hipMemcpy(c->aAF, AF, (size_t)NFREQ * 4, hipMemcpyHostToDevice));
     if (NFREQ != c->a2e_NFREQ) { c->aABS.release();  c->aEMIT.release(); }      // (a batch uploaded for another NFREQ is none: soc_a2e_run)
     c->a2e_NE = NE;  c->a2e_NFREQ = NFREQ;  c->a2e_npair = npair;  c->a2e_noIw = noIw;
+    return SOC_OK;
+}
+
+int soc_a2e_launch_shape(soc_ctx *c, int out[3])
+{
+    if (!c || !out) return SOC_ERR_ARG;
+    if (c->a2e_NE == 0) return fail(c, SOC_ERR_STATE, "soc_a2e_launch_shape: call soc_a2e_set_size first");
+    (void)soc_a2e_shape(c->a2e_NE, c->a2e_NFREQ, out);        // (fits: soc_a2e_set_size refuses a size that does not)
     return SOC_OK;
 }
 

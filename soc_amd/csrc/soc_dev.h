@@ -251,6 +251,9 @@ struct SocEqTArgs {
     float *T, *EMIT;
 };
 
+#define SOC_A2E_LDS (160 * 1024)     // bytes of LDS a DoSolve workgroup may take (the CU's)
+// cells per workgroup, threads per workgroup and dynamic LDS bytes of DoSolve at this size; false: one cell does not fit (it needs out[2] bytes)
+bool soc_a2e_shape(int NE, int NFREQ, int out[3]);
 hipError_t soc_launch_a2e_dosolve(const SocA2EArgs &A, hipStream_t st);
 hipError_t soc_launch_a2e_eqtemp(const SocEqTArgs &A, hipStream_t st);
 hipError_t soc_launch_eqsolver(const SocEqTArgs &A, hipStream_t st);

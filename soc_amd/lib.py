@@ -120,6 +120,7 @@ API = {
                                      C.c_float, C.c_float, C.c_float, _F]),
     "soc_ps_tau": (C.c_int, [C.c_void_p, C.c_int, _F, _F, C.c_float, C.c_float, C.c_float, _F, _F]),
     "soc_a2e_set_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _F, _I, _I, _F, _F, _I, _F]),
+    "soc_a2e_launch_shape": (C.c_int, [C.c_void_p, _I]),
     "soc_a2e_solve": (C.c_int, [C.c_void_p, C.c_int, _F, _F]),
     "soc_a2e_upload": (C.c_int, [C.c_void_p, C.c_int, _F]),
     "soc_a2e_run": (C.c_int, [C.c_void_p, C.c_int]),
@@ -854,9 +855,15 @@ class Engine:
         if a["L1"].size != NE * NE or a["L2"].size != NE * NE or a["Tdown"].size != NE or a["EA"].size != NE * NFREQ \
                 or a["Ibeg"].size != NFREQ or AF.size != NFREQ:
             raise SocError("a2e_set_size: array sizes do not match NE=%d NFREQ=%d" % (NE, NFREQ))
-        self._a2e_nfreq = NFREQ
         self._chk(self.lib.soc_a2e_set_size(self.h, int(NE), int(NFREQ), int(a["Iw"].size), _f(a["Iw"]), _i(a["L1"]),
                                             _i(a["L2"]), _f(a["Tdown"]), _f(a["EA"]), _i(a["Ibeg"]), _f(AF)))
+        self._a2e_nfreq = NFREQ                              # (a refused size leaves the one before in place)
+
+    def a2e_launch_shape(self):
+        """(cells per workgroup, threads per workgroup, dynamic LDS bytes) of DoSolve for the size of the last a2e_set_size."""
+        out = np.zeros(3, np.int32)
+        self._chk(self.lib.soc_a2e_launch_shape(self.h, _i(out)))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def a2e_solve(self, AABS):
         AABS = np.ascontiguousarray(AABS, np.float32)

@@ -6,11 +6,6 @@ header; DoSolve keeps the reference's fp32 operations and their order everywhere
 each row in one lane (i ascending, mul then add), finished values handed down by v_readlane -- and uses +,*,/,max
 only, so it equals the reference's own golden output as well."""
 
-
-def _same_bits(got, want):
-    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
-    ok = np.isfinite(want)
-    return np.array_equal(np.isfinite(got), ok) and np.array_equal(got[ok].view(np.uint32), want[ok].view(np.uint32))
 import os
 import sys
 
@@ -23,6 +18,7 @@ from soc_amd import files, synth
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 from make_golden import a2e_case  # noqa: E402
+from util import same_bits as _same_bits  # noqa: E402
 
 GOLD = np.load(os.path.join(HERE, "golden", "a2e.npz"))
 

@@ -77,3 +77,10 @@ def assert_tally_close(got, want, rtol=1e-5, floor_frac=1e-6):
     bad = np.abs(got - want) > tol
     assert not bad.any(), "%d of %d cells differ; worst rel %.3e" % (
         bad.sum(), bad.size, (np.abs(got - want) / np.maximum(np.abs(want), 1e-300))[bad].max())
+
+
+def same_bits(got, want):
+    """The standard of the bit-exact kernels: equal bits wherever the oracle's value is finite, and the same finite / non-finite pattern."""
+    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
+    ok = np.isfinite(want)
+    return np.array_equal(np.isfinite(got), ok) and np.array_equal(got[ok].view(np.uint32), want[ok].view(np.uint32))
