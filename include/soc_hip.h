@@ -242,12 +242,30 @@ int soc_sim_hp(soc_ctx *ctx, int PACKETS, int BATCH, float SEED, float TW, int G
  * A split whose 4^d entries would not fit the stack -- the reference writes them without looking -- is an overflow drop. */
 int soc_sim_bg_split(soc_ctx *ctx, int PACKETS, int BATCH, float SEED, float BG, float TW, int SELEM, int max_split,
                      int GLOBAL, int gid_first, int gid_count);
-/* counters of the soc_sim_bg_split launches since the last reset, summed over work items: out[0] root rays started,
+/* replaces the kernel_hp_split launch of `split 1` runs with a Healpix sky (ASOC.py:1336-1340 -> SimHpSplit,
+ * kernel_ASOC.c:2871-3550).  Work item id sends BATCH root rays, each created like a SimRAM_HP packet -- sky pixel uniform or by
+ * HPBGP, entry face with probability ~ |DIR_i| -- except that the face is chosen on the direction as it comes from the pixel and
+ * the clamp to DEPS follows IndexG (:2963-2988).  No work item returns early (SimRAM_HP's do at id >= 8*AREA).  Splitting, stack,
+ * max_split and the work-item range are soc_sim_bg_split's, with two rules of the reference's own: inside the walk a ray splits
+ * only where (NBUF+4) < (MAX_SPLIT-1) -- on a nearly full stack it goes on unsplit on the finer level with PHOTONS unscaled
+ * (:3263; counted, soc_split_skipped) -- and the replicas of a jump over two or more levels are written level by level where
+ * (NBUF + 4*no) < MAX_SPLIT (:3352).  GLOBAL is the number of work items launched (GLOBAL_SPLIT, ASOC.py:311-315; the weight of
+ * the sky counts Fix(GLOBAL_SPLIT, 64), launch.hp_split_launch).
+ * Like soc_sim_bg_split the launch is not deferred: inside soc_batch_begin/end it runs at once, after what was deferred before
+ * it, on the handle's stream, and reads the sky that is current at the call.  A following soc_set_hpbg cannot overtake the
+ * kernel: its copies go to the same stream and it synchronises that stream.
+ * Refused as soc_sim_bg_split refuses (max_split < 14, mirror, step weight, roi save, range, memory), and without a sky:
+ * "call soc_set_hpbg first".  Whether the sky is weighted is soc_set_hpbg's decision (HPBGP given or not). */
+int soc_sim_hp_split(soc_ctx *ctx, int PACKETS, int BATCH, float SEED, float TW, int max_split, int GLOBAL, int gid_first, int gid_count);
+/* counters of the soc_sim_bg_split and soc_sim_hp_split launches since the last reset, summed over work items: out[0] root rays started,
  * out[1] split events, out[2] those over two or more levels, out[3] rays ended on reaching a level below the one they were
  * created on, out[4] stack-overflow drops (the ray and all on its stack), out[5] work items that returned at 30000 steps */
 int soc_split_stats(soc_ctx *ctx, uint64_t out[6], int reset);
 /* the largest number of stack entries a work item of those launches held, as of the last soc_split_stats call; -1: no handle */
 int64_t soc_split_max_depth(soc_ctx *ctx);
+/* splits that soc_sim_hp_split launches skipped because the stack was nearly full, as of the last soc_split_stats call (the
+ * isotropic kernel never counts here); -1: no handle */
+int64_t soc_split_skipped(soc_ctx *ctx);
 
 /* replaces queue.finish() (ASOC.py:1461) */
 int soc_sync(soc_ctx *ctx);

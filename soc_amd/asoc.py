@@ -33,17 +33,18 @@ class UnsupportedOption(RuntimeError):
 def _check_supported(USER, NDUST, WITH_MSF, engine=None):
     bad = []
     if USER.DO_SPLIT:
-        # packet splitting of the isotropic background (SimBgSplit, kernel_ASOC.c:2117-2851) on an engine that has the kernel
+        # packet splitting of the background (SimBgSplit, kernel_ASOC.c:2117-2851; with a Healpix sky SimHpSplit, :2871-3550) on an
+        # engine that has the kernel
         if not hasattr(engine, "sim_bg_split"):
             bad.append("split (the engine has no sim_bg_split)")
-        if len(USER.file_hpbg) > 2 and USER.BGPAC > 0:
-            bad.append("split with a Healpix background (SimHpSplit, kernel_ASOC.c:2871 on, has split rules of its own; out of scope)")
+        if len(USER.file_hpbg) > 2 and USER.BGPAC > 0 and not hasattr(engine, "sim_hp_split"):
+            bad.append("split with a Healpix background (SimHpSplit, kernel_ASOC.c:2871 on, has split rules of its own): this engine has no sim_hp_split")
         if launch.mirror_mask(USER.MIRROR):
-            bad.append("split with mirror (SimBgSplit has no Mirror() call)")
+            bad.append("split with mirror (SimBgSplit and SimHpSplit have no Mirror() call)")
         if int(USER.STEP_WEIGHT[2]) > 0:
-            bad.append("split with stepweight (SimBgSplit draws unweighted free paths only)")
+            bad.append("split with stepweight (SimBgSplit and SimHpSplit draw unweighted free paths only)")
         if USER.WITH_ROI_SAVE:
-            bad.append("split with roisave (SimBgSplit keeps no region-of-interest record)")
+            bad.append("split with roisave (SimBgSplit and SimHpSplit keep no region-of-interest record)")
         if USER.MAX_SPLIT != 0 and USER.MAX_SPLIT < 14:
             bad.append("maxsplit %d (at least 14: a split adds 4 entries above the kernel's NBUF > MAX_SPLIT-10 test)" % USER.MAX_SPLIT)
     if int(USER.STEP_WEIGHT[2]) > 2:
@@ -217,6 +218,9 @@ class AbsorptionRun:
         if U.ITERATIONS < 1:
             U.NOABSORBED = 1
         self.SPLIT = bool(U.DO_SPLIT) and U.BGPAC > 0 and len(self.HPBG) == 0
+        # `split 1` with a Healpix sky (SimHpSplit): packet.info keeps the rounded BGPAC above, which is what the reference writes
+        # for this combination (ASOC.py:251 comes before the launch loop that recomputes BGPAC, :1050-1059)
+        self.HP_SPLIT = bool(U.DO_SPLIT) and U.BGPAC > 0 and len(self.HPBG) > 0
         if self.SPLIT:
             # `split 1`: BATCH rays from every surface element; the corrected BGPAC = AREA*BATCH (ASOC.py:1073-1074)
             self.BGPAC = launch.bg_split_launch(U.BGPAC, int(U.AREA), LOCAL)["PACKETS"]
@@ -232,7 +236,9 @@ class AbsorptionRun:
         self.INTENSITY = None
 
     def write_packet_info(self, path="packet.info"):
-        """int32 [BGPAC, PSPAC, DFPAC, CLPAC] (ASOC.py:251)"""
+        """int32 [BGPAC, PSPAC, DFPAC, CLPAC] (ASOC.py:251).  BGPAC is the count rounded to multiples of AREA and LOCAL (ASOC.py:235),
+        also for `split 1` with a Healpix sky, whose launch sends GLOBAL_SPLIT*100 rays: the reference writes the file before its
+        launch loop recomputes BGPAC.  Only `split 1` with the isotropic background carries the corrected count AREA*BATCH."""
         if self.rank == 0:
             np.asarray([self.BGPAC, self.PSPAC, self.DFPAC, self.CLPAC], np.int32).tofile(path)
 
@@ -321,6 +327,8 @@ class AbsorptionRun:
                 return None
             if self.SPLIT:
                 return launch.bg_split_launch(U.BGPAC, int(U.AREA), self.LOCAL)
+            if self.HP_SPLIT:
+                return launch.hp_split_launch(self.BGPAC, c.NX, c.NY, c.NZ, int(U.AREA), self.LOCAL)
             return self._hpbg_launch(self.BGPAC, c.NX, c.NY, c.NZ) if len(self.HPBG) > 0 else launch.bg_launch(self.BGPAC, int(U.AREA))
         if II == 2:
             if len(self.DIFFUSERAD) < 1 or self.DFPAC < 1:
@@ -395,6 +403,8 @@ class AbsorptionRun:
         t0 = time.time()
         if II == 2:
             e.sim_cl(II, L["PACKETS"], L["BATCH"], seed, FF, L["GLOBAL"], gid_first=first, gid_count=count)
+        elif hp and "GLOBAL_W" in L:                           # `split 1` with a Healpix sky: kernel_hp_split (ASOC.py:1336-1340)
+            e.sim_hp_split(L["PACKETS"], L["BATCH"], seed, FF, int(U.MAX_SPLIT), GLOBAL=L["GLOBAL"], gid_first=first, gid_count=count)
         elif hp:
             e.sim_hp(L["PACKETS"], L["BATCH"], seed, FF, L["GLOBAL"], gid_first=first, gid_count=count)
         elif II == 1 and "SELEM" in L:                         # `split 1`: kernel_bg_split (ASOC.py:1343-1347)

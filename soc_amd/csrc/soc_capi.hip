@@ -874,6 +874,38 @@ int soc_sim_pb(soc_ctx *c, int SOURCE, int PACKETS, int BATCH, float SEED, float
 
 #define SOC_MAX_SPLIT_DEFAULT 4300      // ASOC_aux.py:54
 
+// What the two split launches share: the checks on max_split and on what neither kernel has a branch for, the ray stacks (a tile of
+// max_split x 10 x 64 words per wave of the range, kept for the handle) and the counters.  max_split <= 0 becomes the default.
+static int split_prepare(soc_ctx *c, const char *who, int &max_split, int gid_count)
+{
+    if (max_split <= 0) max_split = SOC_MAX_SPLIT_DEFAULT;
+    if (max_split < 14)
+        return fail(c, SOC_ERR_ARG, "%s: max_split %d (at least 14: a split adds 4 entries above the NBUF > MAX_SPLIT-10 test)", who, max_split);
+    // what SimBgSplit and SimHpSplit have no branch for (kernel_ASOC.c:2117-3550: no Mirror(), no STEP_WEIGHT, no ROI arguments)
+    if (c->mirror) return fail(c, SOC_ERR_STATE, "%s: reflecting faces (mirror mask %d) are not part of the split kernel", who, c->mirror);
+    if (c->step_weight) return fail(c, SOC_ERR_STATE, "%s: weighted free paths (step weight mode %d) are not part of the split kernel", who, c->step_weight);
+    if (c->roi.save) return fail(c, SOC_ERR_STATE, "%s: a region-of-interest record (roi save) is not part of the split kernel", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t waves = ((size_t)gid_count + 63) / 64, words = waves * (size_t)max_split * 640;
+    if ((double)waves * (double)max_split * 640.0 > (double)c->dSplitStack.n) {
+        size_t mfree = 0, mtotal = 0;
+        HIPCHK(c, hipMemGetInfo(&mfree, &mtotal));
+        const size_t held = c->dSplitStack.owned ? c->dSplitStack.bytes() : 0;
+        if ((double)waves * (double)max_split * 2560.0 > (double)(mfree + held))      // (in double: the product can pass 2^64)
+            return fail(c, SOC_ERR_ARG, "%s: the ray stacks of %d work items x max_split %d need %.3f GB of device memory, %.3f GB are free",
+                        who, gid_count, max_split, (double)waves * (double)max_split * 2560.0e-9, (double)(mfree + held) * 1e-9);
+        FLUSH(c);
+        hipError_t e = c->dSplitStack.reserve(words, c->stream);
+        if (e != hipSuccess)
+            return fail(c, SOC_ERR_HIP, "%s: allocating %.3f GB for the ray stacks failed: %s", who, (double)words * 4e-9, hipGetErrorString(e));
+    }
+    if (!c->dSplitStats) {
+        HIPCHK(c, c->dSplitStats.reserve(8, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->dSplitStats, 0, 8 * sizeof(unsigned long long), c->stream));
+    }
+    return SOC_OK;
+}
+
 int soc_sim_bg_split(soc_ctx *c, int PACKETS, int BATCH, float SEED, float BG, float TW, int SELEM, int max_split,
                      int GLOBAL, int gid_first, int gid_count)
 {
@@ -881,34 +913,12 @@ int soc_sim_bg_split(soc_ctx *c, int PACKETS, int BATCH, float SEED, float BG, f
     if (!c) return SOC_ERR_ARG;
     int r = check_launch(c, "soc_sim_bg_split", BATCH, GLOBAL, gid_first, gid_count);
     if (r) return r;
-    if (max_split <= 0) max_split = SOC_MAX_SPLIT_DEFAULT;
-    if (max_split < 14)
+    if (max_split > 0 && max_split < 14)
         return fail(c, SOC_ERR_ARG, "soc_sim_bg_split: max_split %d (at least 14: a split adds 4 entries above the NBUF > MAX_SPLIT-10 test)", max_split);
     if (SELEM < 1) return fail(c, SOC_ERR_ARG, "soc_sim_bg_split: SELEM %d (surface elements per work item, >= 1)", SELEM);
     if ((int64_t)SELEM * GLOBAL > 2147483647LL) return fail(c, SOC_ERR_ARG, "soc_sim_bg_split: SELEM %d x GLOBAL %d exceeds int32", SELEM, GLOBAL);
-    // what SimBgSplit has no branch for (kernel_ASOC.c:2117-2851: no Mirror(), no STEP_WEIGHT, no ROI arguments)
-    if (c->mirror) return fail(c, SOC_ERR_STATE, "soc_sim_bg_split: reflecting faces (mirror mask %d) are not part of the split kernel", c->mirror);
-    if (c->step_weight) return fail(c, SOC_ERR_STATE, "soc_sim_bg_split: weighted free paths (step weight mode %d) are not part of the split kernel", c->step_weight);
-    if (c->roi.save) return fail(c, SOC_ERR_STATE, "soc_sim_bg_split: a region-of-interest record (roi save) is not part of the split kernel");
-    HIPCHK(c, hipSetDevice(c->device));
-    // the stacks: a tile of max_split x 10 x 64 words per wave of the range
-    const size_t waves = ((size_t)gid_count + 63) / 64, words = waves * (size_t)max_split * 640;
-    if ((double)waves * (double)max_split * 640.0 > (double)c->dSplitStack.n) {
-        size_t mfree = 0, mtotal = 0;
-        HIPCHK(c, hipMemGetInfo(&mfree, &mtotal));
-        const size_t held = c->dSplitStack.owned ? c->dSplitStack.bytes() : 0;
-        if ((double)waves * (double)max_split * 2560.0 > (double)(mfree + held))      // (in double: the product can pass 2^64)
-            return fail(c, SOC_ERR_ARG, "soc_sim_bg_split: the ray stacks of %d work items x max_split %d need %.3f GB of device memory, %.3f GB are free",
-                        gid_count, max_split, (double)waves * (double)max_split * 2560.0e-9, (double)(mfree + held) * 1e-9);
-        FLUSH(c);
-        hipError_t e = c->dSplitStack.reserve(words, c->stream);
-        if (e != hipSuccess)
-            return fail(c, SOC_ERR_HIP, "soc_sim_bg_split: allocating %.3f GB for the ray stacks failed: %s", (double)words * 4e-9, hipGetErrorString(e));
-    }
-    if (!c->dSplitStats) {
-        HIPCHK(c, c->dSplitStats.reserve(8, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->dSplitStats, 0, 8 * sizeof(unsigned long long), c->stream));
-    }
+    r = split_prepare(c, "soc_sim_bg_split", max_split, gid_count);
+    if (r) return r;
     SocSim S;
     SocVariant V;
     fill_sim(c, S, V, 1, BATCH, SEED, BG, TW, GLOBAL, gid_first, gid_count);
@@ -920,6 +930,31 @@ int soc_sim_bg_split(soc_ctx *c, int PACKETS, int BATCH, float SEED, float BG, f
     SocSplit P;
     P.SELEM = SELEM;  P.max_split = max_split;  P.stack = c->dSplitStack;  P.counters = c->dSplitStats;
     HIPCHK(c, soc_launch_sim_bg_split(c->G, S, P, V, c->stream));
+    return SOC_OK;
+}
+
+int soc_sim_hp_split(soc_ctx *c, int PACKETS, int BATCH, float SEED, float TW, int max_split, int GLOBAL, int gid_first, int gid_count)
+{
+    (void)PACKETS;
+    if (!c) return SOC_ERR_ARG;
+    int r = check_launch(c, "soc_sim_hp_split", BATCH, GLOBAL, gid_first, gid_count);
+    if (r) return r;
+    if (!c->have_hpbg) return fail(c, SOC_ERR_STATE, "soc_sim_hp_split: call soc_set_hpbg first");
+    r = split_prepare(c, "soc_sim_hp_split", max_split, gid_count);
+    if (r) return r;
+    SocSim S;
+    SocVariant V;
+    fill_sim(c, S, V, 1, BATCH, SEED, 0.0f, TW, GLOBAL, gid_first, gid_count);
+    S.NO_PS = 1;
+    // Not deferred, so the kernel reads the handle's own sky, the one current at this call.  A following soc_set_hpbg cannot overtake
+    // it: its copies are issued on this stream, behind the kernel, and it synchronises the stream before it returns.
+    FLUSH(c);
+    r = take_int_slot(c, "soc_sim_hp_split", S);
+    if (r) return r;
+    c->last.passes = 0;
+    SocSplit P;
+    P.SELEM = 1;  P.max_split = max_split;  P.stack = c->dSplitStack;  P.counters = c->dSplitStats;
+    HIPCHK(c, soc_launch_sim_hp_split(c->G, S, P, V, c->stream));
     return SOC_OK;
 }
 
@@ -936,10 +971,12 @@ int soc_split_stats(soc_ctx *c, uint64_t out[6], int reset)
     }
     if (out) for (int i = 0; i < 6; i++) out[i] = h[i];
     c->split_depth = h[6];
+    c->split_skipped = h[7];
     return SOC_OK;
 }
 
 int64_t soc_split_max_depth(soc_ctx *c) { return c ? (int64_t)c->split_depth : -1; }
+int64_t soc_split_skipped(soc_ctx *c) { return c ? (int64_t)c->split_skipped : -1; }
 
 static int batch_begin(soc_ctx *c, int max_launches, soc_ctx::IntMode int_mode)
 {

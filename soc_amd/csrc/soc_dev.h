@@ -96,13 +96,14 @@ struct SocVariant {
 hipError_t soc_launch_sim_pb(const SocGrid &G, const SocSim &S, const SocVariant &V, hipStream_t st);
 hipError_t soc_launch_sim_cl(const SocGrid &G, const SocSim &S, const SocVariant &V, hipStream_t st);
 hipError_t soc_launch_sim_hp(const SocGrid &G, const SocSim &S, const SocVariant &V, hipStream_t st);
-// SimBgSplit (soc_split.hip; kernel_ASOC.c:2117-2143): what a split launch has beyond SocSim
+// SimBgSplit and SimHpSplit (soc_split.hip; kernel_ASOC.c:2117-2143, :2871-2894): what a split launch has beyond SocSim
 struct SocSplit {
-    int    SELEM, max_split;   /* -D SELEM, -D MAX_SPLIT                                                       */
+    int    SELEM, max_split;   /* -D SELEM (SimBgSplit only), -D MAX_SPLIT                                     */
     float *stack;              /* per wave a tile of max_split x 10 x 64 words: word (slot, field, lane) at (slot*10 + field)*64 + lane */
-    unsigned long long *counters;   /* soc_split_stats: six sums and [6] the maximum stack depth               */
+    unsigned long long *counters;   /* soc_split_stats: six sums, [6] the maximum stack depth, [7] SimHpSplit's skipped splits */
 };
 hipError_t soc_launch_sim_bg_split(const SocGrid &G, const SocSim &S, const SocSplit &P, const SocVariant &V, hipStream_t st);
+hipError_t soc_launch_sim_hp_split(const SocGrid &G, const SocSim &S, const SocSplit &P, const SocVariant &V, hipStream_t st);
 hipError_t soc_launch_parents(const SocGrid &G, int *PAR, hipStream_t st);
 hipError_t soc_launch_seed_probe(uint64_t seed_mul, const uint64_t *tab, uint32_t gid0, uint32_t n,
                                  int ndraw, uint32_t *out_state, uint32_t *out_draws, hipStream_t st);

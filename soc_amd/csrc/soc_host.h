@@ -131,9 +131,10 @@ struct soc_ctx {
     // rng
     DevBuf<uint64_t> dSeedTab;
     DevBuf<unsigned long long> dStats;
-    DevBuf<float> dSplitStack;                               // soc_sim_bg_split: the ray stacks, kept from the first launch on
-    DevBuf<unsigned long long> dSplitStats;                  // soc_split_stats: 6 sums and the maximum stack depth
+    DevBuf<float> dSplitStack;                               // soc_sim_bg_split / soc_sim_hp_split: the ray stacks, kept from the first launch on
+    DevBuf<unsigned long long> dSplitStats;                  // soc_split_stats: 6 sums, the maximum stack depth, the skipped splits
     unsigned long long split_depth = 0;                      // that maximum, as of the last soc_split_stats
+    unsigned long long split_skipped = 0;                    // the skipped splits of soc_sim_hp_split, as of the last soc_split_stats
     unsigned long long ray_steps = 0;                      // cell steps of the rays of the scattered-light sweeps, as of the last soc_stats
     // features
     int with_int = 0, ps_method = 0, use_emweight = 0, mirror = 0;

@@ -808,7 +808,9 @@ __device__ __forceinline__ int soc_hp_select_pixel(const SocSim &S, soc_rng_t *r
 
 // Creation of a SimRAM_HP packet (kernel_ASOC.c:878-947): direction from the sky pixel, entry
 // face chosen with probability proportional to |DIR_i|, uniform position on that face.
-template <bool OCT, typename W>
+// RAW: the order of SimHpSplit (:2953-2981), which forms the face probabilities and tests the signs on the direction as it
+// comes from the pixel; the caller clamps to DEPS and normalises after this (:2985-2988).
+template <bool OCT, typename W, bool RAW = false>
 __device__ __forceinline__ void soc_hp_create(const SocGrid &G, const SocSim &S, const int *sOFF, W &w)
 {
     const int NX = G.NX, NY = G.NY, NZ = G.NZ;
@@ -821,10 +823,12 @@ __device__ __forceinline__ void soc_hp_create(const SocGrid &G, const SocSim &S,
     w.ux = +st * cp;
     w.uy = +st * sp;
     w.uz = -ct;
-    if (soc_fabsf(w.ux) < SOC_DEPS) w.ux = SOC_DEPS;
-    if (soc_fabsf(w.uy) < SOC_DEPS) w.uy = SOC_DEPS;
-    if (soc_fabsf(w.uz) < SOC_DEPS) w.uz = SOC_DEPS;
-    soc_normalize(w.ux, w.uy, w.uz);
+    if (!RAW) {
+        if (soc_fabsf(w.ux) < SOC_DEPS) w.ux = SOC_DEPS;
+        if (soc_fabsf(w.uy) < SOC_DEPS) w.uy = SOC_DEPS;
+        if (soc_fabsf(w.uz) < SOC_DEPS) w.uz = SOC_DEPS;
+        soc_normalize(w.ux, w.uy, w.uz);
+    }
     float x = soc_fabsf(w.ux), y = soc_fabsf(w.uy), z = soc_fabsf(w.uz);
     float ds = x + y + z;
     x /= ds;  y /= ds;  z /= ds;

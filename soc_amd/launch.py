@@ -90,6 +90,23 @@ def hpbg_launch(BGPAC, NX, NY, NZ):
     return dict(GLOBAL=GLOBAL, BATCH=BATCH, PACKETS=PACKETS, WBG=WBG)
 
 
+def hp_split_launch(BGPAC, NX, NY, NZ, AREA, LOCAL=LOCAL_GPU, GLOBAL=GLOBAL_0):
+    """Healpix background with packet splitting (`split 1` + `hpbg`; ASOC.py:311-315, :1050-1059, :1336-1340): the kernel runs
+    on GLOBAL_SPLIT work items -- bg_split_launch's GLOBAL -- of 100 root rays each, while the weight counts
+    GLOBAL_W = Fix(GLOBAL_SPLIT, 64) work items.  With a LOCAL of 32 and a GLOBAL_SPLIT that is no multiple of 64 fewer rays are
+    sent than the weight counts -- kept as in the reference.  BGPAC only says that the block is simulated.
+    Returns dict(GLOBAL, BATCH, PACKETS, WBG, GLOBAL_W); PACKETS = GLOBAL_W*100, the reference's BGPAC."""
+    AREA = int(AREA)
+    SELEM = max([1, AREA // GLOBAL])
+    GLOBAL = Fix((AREA // SELEM) + 1, LOCAL)
+    BATCH = 100
+    GLOBAL_W = Fix(GLOBAL, 64)
+    PACKETS = GLOBAL_W * BATCH
+    WBG = np.pi / PLANCK
+    WBG /= (GLOBAL_W * BATCH) / (2 * (NX * NY + NX * NZ + NY * NZ))
+    return dict(GLOBAL=GLOBAL, BATCH=BATCH, PACKETS=PACKETS, WBG=WBG, GLOBAL_W=GLOBAL_W)
+
+
 def hpbg_sca_launch(BGPAC, NX, NY, NZ):
     """Healpix background of the scattering run (ASOCS.py:480-497): one packet per work item, aimed at a
     sphere of radius Rout that contains the cloud; the kernel rejects those that miss.

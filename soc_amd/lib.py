@@ -53,6 +53,8 @@ API = {
                              C.c_int, C.c_int, C.c_int]),
     "soc_sim_bg_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_int]),
+    "soc_sim_hp_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "soc_split_skipped": (C.c_int64, [C.c_void_p]),
     "soc_split_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
     "soc_split_max_depth": (C.c_int64, [C.c_void_p]),
     "soc_batch_begin": (C.c_int, [C.c_void_p, C.c_int]),
@@ -460,15 +462,24 @@ class Engine:
         self._chk(self.lib.soc_sim_bg_split(self.h, int(PACKETS), int(BATCH), np.float32(SEED), np.float32(BG), np.float32(TW),
                                             int(SELEM), int(max_split), int(GLOBAL), int(gid_first), int(gid_count)))
 
+    def sim_hp_split(self, PACKETS, BATCH, SEED, TW, max_split=0, GLOBAL=None, gid_first=0, gid_count=None):
+        """Healpix sky (set_hpbg) with packet splitting (`split 1` + `hpbg`, SimHpSplit): BATCH root rays per work item;
+        max_split 0 = the reference's 4300 stack entries per work item"""
+        gid_count = (GLOBAL - gid_first) if gid_count is None else gid_count
+        self._chk(self.lib.soc_sim_hp_split(self.h, int(PACKETS), int(BATCH), np.float32(SEED), np.float32(TW),
+                                            int(max_split), int(GLOBAL), int(gid_first), int(gid_count)))
+
     SPLIT_COUNTERS = ("roots", "splits", "deep_splits", "ended_below_RL", "overflow_drops", "long_returns")
 
     def split_stats(self, reset=False):
-        """counters of the sim_bg_split launches since the last reset (SPLIT_COUNTERS, summed over work items) and max_depth,
-        the largest number of stack entries a work item held"""
+        """counters of the sim_bg_split and sim_hp_split launches since the last reset (SPLIT_COUNTERS, summed over work items),
+        max_depth, the largest number of stack entries a work item held, and skipped_splits, the splits sim_hp_split launches
+        skipped on a nearly full stack"""
         out = (C.c_uint64 * 6)()
         self._chk(self.lib.soc_split_stats(self.h, out, int(reset)))
         st = {k: int(out[i]) for i, k in enumerate(self.SPLIT_COUNTERS)}
         st["max_depth"] = int(self.lib.soc_split_max_depth(self.h))
+        st["skipped_splits"] = int(self.lib.soc_split_skipped(self.h))
         return st
 
     def sim_cl(self, SOURCE, PACKETS, BATCH, SEED, TW, GLOBAL, gid_first=0, gid_count=None):
