@@ -628,6 +628,46 @@ int soc_mabu_download(soc_ctx *ctx, int64_t c0, int64_t n, float *SUM);
 int soc_mabu_read_part(soc_ctx *ctx, int64_t c0, int64_t n, float *PART);
 int soc_mabu_end(soc_ctx *ctx);
 
+/* ---- the library method for dust emission: soc_library.py with kernel_soc_library.c ---- */
+
+/* A model with stochastically heated grains is simulated at three reference frequencies only; the emission of a cell is then
+ * looked up in an N x N x N table (2 <= N <= 64, a run-time value: the .lib file carries it) indexed by the log10 of the
+ * absorptions at those frequencies.  All arithmetic is fp32 in the order the reference writes it.
+ *
+ * soc_library_set makes a library resident (the arrays of a .lib file, soc_library.py:279-290): I0, dI0 the first bin centre
+ * and the bin width of axis 0, I1[N], dI1[N] those of axis 1 for every i, I2[N*N], dI2[N*N] those of axis 2 for every (i, j),
+ * X, Y, Z [N^3] the coordinates of every bin's representative cell, E[N^3][NFREQ] its emission (first value > 1e31: the bin is
+ * empty).  ocol, when given, selects and orders nout of the NFREQ emission columns once, at upload (the ofreq.dat subset of
+ * soc_library.py:298-306, :392-396); without it nout is taken as NFREQ.  N = 0 forgets the library.
+ *
+ * soc_library_solve is LibrarySolve with METHOD 0 (kernel_soc_library.c:27-51) with the host loop around it
+ * (soc_library.py:379-406) on host arrays: ABS3[n][3] -> EMI[n][nout].  Per cell x = (log10(clamp(a0, 1e-29, 1e10)) - I0) / dI0,
+ * i = clamp((int)round(x), 0, N-1) with halves away from zero (a value no int holds clamps by its sign), then y, j from
+ * I1[i], dI1[i] and z, k from I2[i*N+j], dI2[i*N+j].  A cell is a miss if one of |x-X|, |y-Y|, |z-Z| at bin k+N*(j+N*i) exceeds
+ * 1.1 or the bin is empty; the reference writes element 0 of such a row only, here the row is 1e32 followed by zeros.  miss (room
+ * for n entries; may be NULL) receives the missed cells in ascending order, *nmiss their count.
+ *
+ * soc_library_solve_resident reads the three reference columns col[3] straight out of the absorptions of
+ * soc_a2e_resident_begin / _upload and leaves the emission in that family's sum array (soc_a2e_resident_download fetches it):
+ * the library's nout must be the row length of the resident arrays. */
+int soc_library_set(soc_ctx *ctx, int N, int NFREQ, float I0, float dI0, const float *I1, const float *dI1, const float *I2,
+                    const float *dI2, const float *X, const float *Y, const float *Z, const float *E, int nout, const int32_t *ocol);
+int soc_library_solve(soc_ctx *ctx, int64_t n, const float *ABS3, float *EMI, int32_t *miss, int64_t *nmiss);
+int soc_library_solve_resident(soc_ctx *ctx, const int32_t *col, int32_t *miss, int64_t *nmiss);
+
+/* The grid of a library and the representative cell of every bin (soc_library.py:127-217; there N + N^2 masked passes over all
+ * cells on the host and a Python loop over every cell, here four sweeps on the device).  ABS3[cells][3] holds the reference
+ * columns, or is NULL and col[3] names them in the resident absorptions (cells must be the resident count).
+ *   IREF = log10(clip(a, 1e-25, 1)); I0, dI0 from the minimum and maximum of axis 0 (:137-142); I1[i], dI1[i] from those of
+ *   axis 1 over the cells with |IREF0 - (I0 + i*dI0)| < 0.5*dI0 (100, 0.001 without a cell, :146-157); I2, dI2 [N*N] the same on
+ *   axis 2 over the cells inside both windows (100, 0.001 with fewer than two cells, :159-170), an undefined (i, j) then taking
+ *   the grid of the last defined one in raster order (:178-185); per cell X, I = clip(rint(X)), Y, J, Z, K with halves to even
+ *   (numpy's round; the indices are clipped before they index I1 and I2) and dis = |X-I| + |Y-J| + |Z-K| in fp32; per bin the
+ *   cell of least dis wins, the lowest index on a tie (:206-213).  IND[N^3] is that cell, -1 where dis > 1.5 or no cell fell
+ *   (:217); XX, YY, ZZ [N^3] are the winner's coordinates (0 where no cell fell). */
+int soc_library_build(soc_ctx *ctx, int N, int64_t cells, const float *ABS3, const int32_t *col, float *I0, float *dI0, float *I1,
+                      float *dI1, float *I2, float *dI2, int32_t *IND, float *XX, float *YY, float *ZZ);
+
 /* ---- verification probes (used by the parity tests only) ---- */
 /* RNG stream states and first draws of logical work items [gid_first, gid_first+n)
  * (MWC64X_SeedStreams + MWC64X_NextUint, mwc64x_rng.cl:35-48) */

@@ -120,6 +120,23 @@ def _check_supported(USER, NDUST, WITH_MSF, engine=None):
         if USER.FAST_MAP >= 999:
             bad.append("maplevels together with mapping with a fourth argument >= 999 (two different per-level products: that mode "
                        "never reaches the walk of the plain map, whose levels maplevels writes)")
+    # the library method (ASOC.py:116-130): `libabs` simulates the frequencies of its file only, `libmaps` maps them from an emitted
+    # file that holds only them
+    if USER.LIB_ABS:
+        if USER.LIB_MAPS:
+            bad.append("libabs together with libmaps (one run either simulates the reference frequencies or maps the library's emission: "
+                       "both keys fill the same list of frequencies, ASOC.py:116-117)")
+        if USER.SAVE_INTENSITY > 0:
+            bad.append("libabs with saveint (the intensity file holds all frequencies, the run simulates a few: ASOC.py:2852 stops there as well)")
+        if USER.ITERATIONS > 0 and USER.CLPAC > 0:
+            bad.append("libabs with iterations > 0 and cellpackets (the dust emission cannot be solved from the reference frequencies "
+                       "alone; ASOC.py:2364 calls the combination senseless)")
+        if USER.ABSTHIN > 1 or 'nnmake' in USER.KEYS:
+            bad.append("libabs with absthin or nnmake (the thinned absorptions train a network on all frequencies; the library needs "
+                       "the reference frequencies of every cell)")
+    if USER.LIB_MAPS and getattr(USER, "MAP_LEVELS", 0) > 0:
+        bad.append("libmaps with maplevels (the per-level maps go through the batch path, libmaps through the plain one: ASOC.py:127 "
+                   "sets FAST_MAP = 0)")
     if USER.MAP_INTERPOLATION > 2 or USER.MAP_INTERPOLATION < 0:
         bad.append("mapint other than 0, 1, 2 (kernel_ASOC_map.c:656-810 knows those: a larger value leaves Adens, Aemit ... unset there)")
     if len(USER.kernel_defs.strip()) > 0:
@@ -179,6 +196,20 @@ class AbsorptionRun:
         self.FDSC, self.FCSC = files.read_scattering_functions(U.file_scafunc, self.NFREQ, U.DSC_BINS)
         self.WITH_MSF = WITH_MSF = len(self.FDSC) > 1
         _check_supported(U, self.NDUST, WITH_MSF, self.eng)
+        # the library method: {IFREQ: column} of the frequencies within 0.1 % of one of `libabs file` / `libmaps file`, counted in table
+        # order (OIFREQ of ASOC.py:1126-1140 -- before the `simum` test -- and :3032-3046); None without either key
+        self.lib_col = None
+        if U.LIB_ABS or U.LIB_MAPS:
+            if U.FSELECT_ERROR or len(U.FSELECT) < 1:
+                raise ValueError(U.FSELECT_ERROR or "the file of libabs / libmaps lists no frequency")
+            fsel = np.asarray(U.FSELECT, np.float64)
+            hit = [f for f in range(self.NFREQ) if np.min(np.abs((float(self.FFREQ[f]) - fsel) / float(self.FFREQ[f]))) <= 0.001]
+            if len(hit) > len(fsel):
+                raise ValueError("%s lists %d frequencies, %d of the dust file's lie within 0.1 %% of one" % ("libabs" if U.LIB_ABS else "libmaps", len(fsel), len(hit)))
+            self.lib_col = {f: k for k, f in enumerate(hit)}
+        if U.LIB_MAPS:                                             # ASOC.py:124-129 (after the check: it looks at the `mapping` of the ini file)
+            U.ITERATIONS, U.NOSOLVE, U.FAST_MAP = 0, 1, 0
+            U.MAP_FREQ = [1.0e-10, 1.0e30]
         self.IBG = files.read_background_intensity(U.file_background, self.NFREQ, U.scale_background) \
             if U.BGPAC > 0 else []
         self.LPS = files.read_source_luminosities(U.file_pointsource[:U.NO_PS], self.NFREQ, U.PS_SCALING) \
@@ -348,8 +379,7 @@ class AbsorptionRun:
             if L is None:
                 continue
             for IFREQ in range(self.NFREQ):
-                FREQ = float(self.FFREQ[IFREQ])
-                if (FREQ < U.SIM_F[0]) or (FREQ > U.SIM_F[1]):
+                if not self._simulated(IFREQ):
                     continue
                 seq.append((II, IFREQ, L))
         if by_frequency:
@@ -358,6 +388,17 @@ class AbsorptionRun:
             return {(II, f): ((0, L["GLOBAL"]) if owner[f] == self.rank else (0, 0)) for II, f, L in seq}, owner
         parts = launch.shard_launches([L["GLOBAL"] for _, _, L in seq], [L["PACKETS"] for _, _, L in seq], self.rank, self.world)
         return {(II, f): pc for (II, f, _), pc in zip(seq, parts)}, None
+
+    def _simulated(self, IFREQ):
+        """the frequency is one the constant sources are simulated at: inside `simum`, and with `libabs` one of its file"""
+        FREQ = float(self.FFREQ[IFREQ])
+        if self.U.LIB_ABS and IFREQ not in self.lib_col:
+            return False
+        return self.U.SIM_F[0] <= FREQ <= self.U.SIM_F[1]
+
+    def _abs_col(self, IFREQ):
+        """the column of the absorbed file that holds IFREQ (`libabs`: only the selected frequencies have one)"""
+        return self.lib_col[IFREQ] if self.U.LIB_ABS else IFREQ
 
     def _seed(self, IFREQ, rng):
         """seed of the launches at IFREQ (ASOC.py:1247); with seed <= 0 a random one, the same on every rank"""
@@ -456,7 +497,7 @@ class AbsorptionRun:
             return [], None
         blocks = [(II, self._constant_launch(II)) for II in range(4)]
         blocks = [(II, L) for II, L in blocks if L is not None]
-        freqs = [f for f in range(self.NFREQ) if U.SIM_F[0] <= float(self.FFREQ[f]) <= U.SIM_F[1]]
+        freqs = [f for f in range(self.NFREQ) if self._simulated(f)]
         # shard == "launches" (see __init__): runs that keep the per-frequency absorptions give a frequency to one rank (not with the
         # intensity file, region-of-interest records or emission iterations, which need every frequency on every rank -- those keep
         # the work-item split); TABS-only runs deal out the launch sequence
@@ -487,7 +528,8 @@ class AbsorptionRun:
         # `nnmake` with `absthin N`: the absorptions of every N-th cell only (ASOC.py:100-105, :632-638)
         thin = U.ABSTHIN if (U.ABSTHIN > 1 and 'nnmake' in U.KEYS) else 1
         self.absthin = thin
-        FABSORBED = None if U.NOABSORBED else np.zeros(((CELLS + thin - 1) // thin, NFREQ), np.float32)
+        # (`libabs`: a column per frequency of its file, ASOC.py:621)
+        FABSORBED = None if U.NOABSORBED else np.zeros(((CELLS + thin - 1) // thin, len(U.FSELECT) if U.LIB_ABS else NFREQ), np.float32)
         if len(U.file_constant_load) > 0:
             self.log("=== CLOAD => %s" % U.file_constant_load)
             return np.fromfile(U.file_constant_load, np.float32, CELLS), FABSORBED
@@ -552,7 +594,7 @@ class AbsorptionRun:
                     if FABSORBED is not None or U.SAVE_INTENSITY > 0:
                         TMP = e.read_tally(1)
                         if FABSORBED is not None:
-                            FABSORBED[:, IFREQ] += TMP[0::thin]
+                            FABSORBED[:, self._abs_col(IFREQ)] += TMP[0::thin]
                         if U.SAVE_INTENSITY > 0:
                             self._save_intensity(IFREQ, float(FFREQ[IFREQ]), ABS, TMP)
                     if self.ROI_SAVE is not None:
@@ -605,7 +647,7 @@ class AbsorptionRun:
                 arr, slot = e.batch_read_int(slot), slot + 1
             if summed:
                 arr = self.comm.all_reduce_host(arr)
-            FABSORBED[:, IFREQ] += arr[0::self.absthin]
+            FABSORBED[:, self._abs_col(IFREQ)] += arr[0::self.absthin]
         del pend[:]
         self.timers["Tpull"] += time.time() - t0
 
@@ -851,6 +893,8 @@ class AbsorptionRun:
         NFREQ, FFREQ = self.NFREQ, self.FFREQ
         m = np.nonzero((FFREQ >= U.REMIT_F[0]) & (FFREQ <= U.REMIT_F[1]))[0]
         I1, I2 = int(m[0]), int(m[-1])
+        if U.LIB_MAPS:                                             # every frequency of the file, whatever `remit` says (ASOC.py:202-204)
+            I1, I2 = 0, NFREQ - 1
         NDIR, ODIR, RA, DE = launch.set_observer_directions(U.OBS_THETA, U.OBS_PHI)
         centre = U.MAPCENTRE if U.MAPCENTRE[0] > -1e7 else (0.5 * c.NX, 0.5 * c.NY, 0.5 * c.NZ)   # ASOC_aux.py:791-793
         KK = (1.0e23 / launch.FACTOR) * PLANCK / (4.0 * np.pi) * (U.GL * PARSEC)                 # ASOC.py:2997-2998
@@ -873,6 +917,8 @@ class AbsorptionRun:
         first_freq = True
         for IFREQ in range(NFREQ):
             FREQ = float(FFREQ[IFREQ])
+            if U.LIB_MAPS and IFREQ not in self.lib_col:           # the loop is over the whole table, the others are skipped (ASOC.py:3032-3038)
+                continue
             save_spe = (IFREQ >= I1) and (IFREQ <= I2)
             if (FREQ < U.MAP_FREQ[0]) or (FREQ > U.MAP_FREQ[1]):
                 continue
@@ -890,7 +936,8 @@ class AbsorptionRun:
             sel.append((IFREQ, save_spe, save_tau, save_colden))
 
         def emission(IFREQ, save_spe):
-            return np.asarray(KK * float(FFREQ[IFREQ]) * EMITTED[:, IFREQ - I1], np.float32) if save_spe else np.zeros(c.CELLS, np.float32)
+            col = self.lib_col[IFREQ] if U.LIB_MAPS else IFREQ - I1     # (ASOC.py:3104-3105: column OIFREQ of the library's emission)
+            return np.asarray(KK * float(FFREQ[IFREQ]) * EMITTED[:, col], np.float32) if save_spe else np.zeros(c.CELLS, np.float32)
 
         def write(IFREQ, idir, MAP, TAU, save_spe, save_tau, save_colden):
             """the files of one frequency and direction; TAU: the optical depth, or with save_colden the column density"""
@@ -1147,7 +1194,9 @@ class AbsorptionRun:
         centre = U.MAPCENTRE if U.MAPCENTRE[0] > -1e7 else (0.5 * c.NX, 0.5 * c.NY, 0.5 * c.NZ)
         KK = (1.0e23 / launch.FACTOR) * PLANCK / (4.0 * np.pi) * (U.GL * PARSEC)
         _, LENGTH_f = launch.kernel_literals(U.GL)
-        sel = [i for i in range(I1, I2 + 1) if U.MAP_FREQ[0] <= float(FFREQ[i]) <= U.MAP_FREQ[1]]
+        if U.LIB_MAPS:                                             # ASOC.py:202-204, :3234-3250
+            I1, I2 = 0, self.NFREQ - 1
+        sel = [i for i in range(I1, I2 + 1) if U.MAP_FREQ[0] <= float(FFREQ[i]) <= U.MAP_FREQ[1] and not (U.LIB_MAPS and i not in self.lib_col)]
         fp = None
         if self.rank == 0:
             fp = open("map_dir_%02d_H.bin" % 0, "wb")              # NDIR = 1 for Healpix maps (ASOC.py:2917)
@@ -1155,7 +1204,8 @@ class AbsorptionRun:
             np.asarray([len(sel), c.LEVELS], np.int32).tofile(fp)
 
         def emission(IFREQ, save_spe=True):
-            return np.asarray(EMITTED[:, IFREQ - I1] * np.float32(KK) * np.float32(float(FFREQ[IFREQ])), np.float32)    # :3283
+            col = self.lib_col[IFREQ] if U.LIB_MAPS else IFREQ - I1     # :3279-3280
+            return np.asarray(EMITTED[:, col] * np.float32(KK) * np.float32(float(FFREQ[IFREQ])), np.float32)    # :3283
 
         if getattr(U, "MAP_LEVELS", 0) > 0:                       # `maplevels 1`: the same map through the batch path, and its levels
             lfp = self._open_level_file(0, len(sel)) if self.rank == 0 else None
@@ -1229,6 +1279,8 @@ class AbsorptionRun:
         self.TNEW, self.EMITTED = None, None
         if U.ITERATIONS > 0 and (self.CLPAC > 0 or ((not U.NOSOLVE) and U.NOABSORBED)):
             self.TNEW, self.EMITTED = self.emission_iterations(CTABS, FABSORBED)
+        elif U.LIB_MAPS:                                           # the emission of the library, its frequencies only (ASOC.py:601-603)
+            self.EMITTED = files.mmap_emitted(U.file_emitted, self.cloud.CELLS, len(U.FSELECT))
         elif U.LOAD_TEMPERATURE and U.ITERATIONS < 1:
             self.TNEW, self.EMITTED = self.emission_from_temperature_file()
         if (not U.NOMAP) and self.EMITTED is not None:
@@ -1256,9 +1308,10 @@ class AbsorptionRun:
             if self.rank == 0:
                 files.create_absorbed(U.file_absorbed, FABSORBED.shape[0], FABSORBED.shape[1])
             self.comm.barrier()
-            mine = [f for f, r in self.freq_owner.items() if r == self.rank]
+            mine = [self._abs_col(f) for f, r in self.freq_owner.items() if r == self.rank]
             if self.rank == 0:
-                mine += [f for f in range(FABSORBED.shape[1]) if f not in self.freq_owner]      # frequencies outside `simum`: nobody's
+                owned = {self._abs_col(f) for f in self.freq_owner}
+                mine += [k for k in range(FABSORBED.shape[1]) if k not in owned]               # frequencies outside `simum`: nobody's
             files.write_absorbed_columns(U.file_absorbed, FABSORBED, mine)
             self.comm.barrier()
         wall = time.time() - t00

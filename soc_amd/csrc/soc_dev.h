@@ -267,6 +267,38 @@ hipError_t soc_launch_mabu_split(long long cells, int NFREQ, int NDUST, int idus
 hipError_t soc_launch_mabu_clip(long long cells, int NFREQ, float *PART, hipStream_t st);
 hipError_t soc_launch_mabu_sum(long long cells, int NFREQ, int NDUST, int idust, const float *EM, const float *ABU, float *SUM, hipStream_t st);
 
+// the library method (soc_library.hip).  The reference columns of cell `c` are ABS[c * stride + c0 | c1 | c2].
+struct SocLibSolve {
+    long long    n;                  // cells
+    int          N, nout;            // bins per axis; emission columns of E and of a row of EMI
+    float        I0, dI0;
+    const float *I1, *dI1;           // [N]
+    const float *I2, *dI2;           // [N*N]
+    const float *X, *Y, *Z;          // [N^3]
+    const float *E0;                 // [N^3] the first stored emission value of every bin (> 1e31: the bin is empty)
+    const float *E;                  // [N^3][nout]
+    const float *ABS;
+    long long    stride;
+    int          c0, c1, c2;
+    float       *EMI;                // [n][nout]
+    int         *miss;               // [n] the cells without an answer, in the order they were found
+    unsigned long long *nmiss;       // their count (0 before the launch)
+};
+struct SocLibBuild {
+    long long    cells;
+    int          N;
+    const float *ABS;
+    long long    stride;
+    int          c0, c1, c2;
+    float        I0, dI0;
+    const float *I1, *dI1, *I2, *dI2;
+};
+hipError_t soc_launch_library_solve(const SocLibSolve &A, hipStream_t st);
+// level 0 | 1 | 2: TAB = 1 | N | N^2 minima, maxima and counts (keys 0xffffffff, 0, 0 before the launch) of axis `level`
+hipError_t soc_launch_library_range(const SocLibBuild &A, int level, unsigned *TAB, hipStream_t st);
+// BEST[N^3] all ones before the launch; IND, XX, YY, ZZ [N^3]
+hipError_t soc_launch_library_pick(const SocLibBuild &A, unsigned long long *BEST, int *IND, float *XX, float *YY, float *ZZ, hipStream_t st);
+
 // Shape of the brick sweep; 0 = the built-in choice for the grid (measured).  Set per context with
 // soc_set_tuning (include/soc_hip.h); the parity tests use small CAP / HS values to exercise brick boundaries.
 struct SocBrickTune {

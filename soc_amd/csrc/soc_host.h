@@ -1,4 +1,4 @@
-// soc_host.h -- what the host units of libsoc_hip.so share (soc_capi.hip, soc_capi_post.hip, soc_capi_a2e.hip, soc_capi_probe.hip):
+// soc_host.h -- what the host units of libsoc_hip.so share (soc_capi.hip, soc_capi_post.hip, soc_capi_a2e.hip, soc_capi_library.hip, soc_capi_probe.hip):
 // the handle, the one type that owns device memory, and the error and flush idioms.  Kernels do not include it.
 #pragma once
 #include "../../include/soc_hip.h"
@@ -168,6 +168,13 @@ struct soc_ctx {
     DevBuf<double> mRABS;
     int     mabu_ndust = 0;
     bool    mabu_tables = false;
+    // the library method (soc_library_*): the resident table -- I1 | dI1 | I2 | dI2 | X | Y | Z | E0 in one block, the selected emission
+    // columns [N^3][lib_nout] -- and the miss list of a look-up
+    int     lib_N = 0, lib_nout = 0;
+    float   lib_I0 = 0.0f, lib_dI0 = 0.0f;
+    DevBuf<float> lTab, lE;
+    DevBuf<int>   lMiss;
+    DevBuf<unsigned long long> lCount;
 };
 
 // the error text of a refused call, for soc_last_error (c == nullptr: of soc_create); returns code

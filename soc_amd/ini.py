@@ -144,6 +144,10 @@ class User:
         s.OUT_NSIDE = 128
         s.MAP_INTERPOLATION = 0
         s.MAP_LEVELS = 0                 # `maplevels N` (not a key of the reference): N > 0 adds map_dir_XX_L.bin, the plain map split by hierarchy level
+        s.LIB_ABS = False                # `libabs file`: simulate the frequencies listed in the file only (the library method)
+        s.LIB_MAPS = False               # `libmaps file`: maps of those frequencies from an emitted file that holds only them
+        s.FSELECT = np.zeros(0, np.float64)
+        s.FSELECT_ERROR = ''             # why the file of `libabs` / `libmaps` could not be read
         s.FITS = 0
         s.FITS_PREFIX = 'map'
         s.FITS_RA = 0.0
@@ -328,6 +332,20 @@ def _polmap(u, s):
         u.MINLOS, u.MAXLOS = float(s[4]), float(s[5])
 
 
+def _fselect(flag):
+    """`libabs file` / `libmaps file` (ASOC_aux.py:346-357): the frequencies [Hz] of the library method; one value is an array too"""
+    def handler(u, s):
+        setattr(u, flag, True)
+        try:
+            f = np.loadtxt(s[1])
+        except OSError as err:                       # reported by the run, after the combinations it refuses whatever the file holds
+            u.FSELECT, u.FSELECT_ERROR = np.zeros(0, np.float64), "%s %s: %s" % (s[0], s[1], err)
+            return
+        u.FSELECT = np.asarray(f, np.float32).reshape(1,) if np.size(f) == 1 else np.asarray(f)
+        u.FSELECT_ERROR = ''
+    return handler
+
+
 def _mapping(u, s):
     u.NPIX = (int(s[1]), int(s[2]))
     u.MAP_DX = float(s[3])
@@ -394,6 +412,8 @@ _KEYWORDS = [
     ('dustfile', 1, _set('DUST_FILE', str)),
     ('radiusalign', 1, _set('ALIGN_DAT', str)),
     ('platform', 1, _platform),
+    ('libabs', 1, _fselect('LIB_ABS')),
+    ('libmap', 1, _fselect('LIB_MAPS')),
     ('diffus', 1, _diffuse),
     ('optic', 1, _optical),
     ('externalm', 1, _set('file_external_mask', str)),

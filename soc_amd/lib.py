@@ -145,6 +145,10 @@ API = {
     "soc_mabu_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
     "soc_mabu_read_part": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
     "soc_mabu_end": (C.c_int, [C.c_void_p]),
+    "soc_library_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, _F, _F, _F, _F, _F, _F, _F, _F, C.c_int, _I]),
+    "soc_library_solve": (C.c_int, [C.c_void_p, C.c_int64, _F, _F, _I, C.POINTER(C.c_int64)]),
+    "soc_library_solve_resident": (C.c_int, [C.c_void_p, _I, _I, C.POINTER(C.c_int64)]),
+    "soc_library_build": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _F, _I, _F, _F, _F, _F, _F, _F, _I, _F, _F, _F]),
     "soc_probe_rng": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_int, _U, _U]),
     "soc_probe_math": (C.c_int, [C.c_void_p, C.c_int, _F, _F, C.c_int64]),
     "soc_probe_math2": (C.c_int, [C.c_void_p, C.c_int, _F, _F, _F, C.c_int64]),
@@ -999,6 +1003,74 @@ class Engine:
     def mabu_end(self):
         self._chk(self.lib.soc_mabu_end(self.h))
         self._mabu = None
+
+    # ---- the library method for dust emission (soc_library_*; driven by soc_amd.library) ----
+    LIBRARY_TABLES = ("I1", "dI1", "I2", "dI2", "X", "Y", "Z")
+
+    def library_set(self, lib, ocol=None):
+        """Make a library resident: lib is a dict with N, I0, dI0, I1[N], dI1[N], I2[N,N], dI2[N,N], X, Y, Z [N,N,N] and
+        E[N^3, NFREQ] (soc_amd.library.read_library); ocol selects and orders emission columns.  library_set(None) forgets it."""
+        if lib is None:
+            self._chk(self.lib.soc_library_set(self.h, 0, 0, 0.0, 0.0, None, None, None, None, None, None, None, None, 0, None))
+            self._lib_nout = 0
+            return
+        N = int(lib["N"])
+        t = [np.ascontiguousarray(lib[k], np.float32) for k in self.LIBRARY_TABLES]
+        E = np.ascontiguousarray(lib["E"], np.float32)
+        if N < 1 or [a.size for a in t] != [N, N, N * N, N * N, N ** 3, N ** 3, N ** 3] or E.ndim != 2 or E.shape[0] != N ** 3:
+            raise SocError("library_set: the tables do not have the sizes of N = %d" % N)
+        oc = None if ocol is None else np.ascontiguousarray(ocol, np.int32)
+        nout = E.shape[1] if oc is None else oc.size
+        self._chk(self.lib.soc_library_set(self.h, N, int(E.shape[1]), np.float32(lib["I0"]), np.float32(lib["dI0"]),
+                                           *[_f(a) for a in t], _f(E), int(nout), _i(oc)))
+        self._lib_nout = int(nout)
+
+    def library_solve(self, ABS3):
+        """ABS3[n, 3], the absorptions at the three reference frequencies -> (EMI[n, nout], the missed cells in ascending order);
+        a missed row is 1e32 followed by zeros"""
+        ABS3 = np.ascontiguousarray(ABS3, np.float32)
+        if ABS3.ndim != 2 or ABS3.shape[1] != 3:
+            raise SocError("library_solve: ABS3 must be [n, 3]")
+        n = ABS3.shape[0]
+        EMI = np.zeros((n, getattr(self, "_lib_nout", 0)), np.float32)
+        miss, nmiss = np.zeros(n, np.int32), C.c_int64(0)
+        self._chk(self.lib.soc_library_solve(self.h, n, _f(ABS3), _f(EMI), _i(miss), C.byref(nmiss)))
+        return EMI, miss[:nmiss.value].copy()
+
+    def library_solve_resident(self, cols):
+        """the look-up on the absorptions of a2e_resident_begin / _upload, reference columns cols[3]; the emission is left in the
+        resident sum (a2e_resident_download).  Returns the missed cells in ascending order."""
+        cols = np.ascontiguousarray(cols, np.int32)
+        if cols.size != 3:
+            raise SocError("library_solve_resident: three columns")
+        miss, nmiss = np.zeros(self._a2e_res[0], np.int32), C.c_int64(0)
+        self._chk(self.lib.soc_library_solve_resident(self.h, _i(cols), _i(miss), C.byref(nmiss)))
+        return miss[:nmiss.value].copy()
+
+    def library_build(self, N, ABS3=None, cols=None):
+        """The grid of a library and every bin's representative cell from ABS3[cells, 3], or from the columns cols[3] of the
+        resident absorptions (ABS3 None).  Returns dict(N, I0, dI0, I1, dI1, I2, dI2, IND[N^3], X, Y, Z [N,N,N])."""
+        N = int(N)
+        if ABS3 is not None:
+            ABS3 = np.ascontiguousarray(ABS3, np.float32)
+            if ABS3.ndim != 2 or ABS3.shape[1] != 3:
+                raise SocError("library_build: ABS3 must be [cells, 3]")
+            cells, cols = ABS3.shape[0], None
+        else:
+            cols = np.ascontiguousarray(cols, np.int32)
+            if cols.size != 3 or getattr(self, "_a2e_res", None) is None:
+                raise SocError("library_build: ABS3, or three columns of the resident absorptions")
+            cells = self._a2e_res[0]
+        if not 2 <= N <= 64:
+            raise SocError("library_build: N = %d (2..64)" % N)
+        I0, dI0 = np.zeros(1, np.float32), np.zeros(1, np.float32)
+        I1, dI1 = np.zeros(N, np.float32), np.zeros(N, np.float32)
+        I2, dI2 = np.zeros((N, N), np.float32), np.zeros((N, N), np.float32)
+        IND = np.zeros(N ** 3, np.int32)
+        X, Y, Z = (np.zeros((N, N, N), np.float32) for _ in range(3))
+        self._chk(self.lib.soc_library_build(self.h, N, int(cells), _f(ABS3), _i(cols), _f(I0), _f(dI0), _f(I1), _f(dI1), _f(I2), _f(dI2),
+                                             _i(IND), _f(X), _f(Y), _f(Z)))
+        return dict(N=N, I0=I0[0], dI0=dI0[0], I1=I1, dI1=dI1, I2=I2, dI2=dI2, IND=IND, X=X, Y=Y, Z=Z)
 
     # ---- probes ----
     def probe_rng(self, SEED, gid_first, n, ndraw):
