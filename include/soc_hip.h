@@ -566,6 +566,26 @@ int soc_a2e_resident_solve(soc_ctx *ctx);
 int soc_a2e_resident_download(soc_ctx *ctx, int64_t c0, int64_t n, float *AEMIT);
 int soc_a2e_resident_end(soc_ctx *ctx);
 
+/* Polarised emission beside the emission: the emission of the grains larger than each cell's minimum aligned size a_alg, which the
+ * reference's host adds up per batch and size (A2E.py:192-197 the second array, :413-429 the weights of a stochastic size).  Here the
+ * sum over the sizes lives on the device, so the solver kernel's epilogue adds W * emission to a second sum:
+ *   soc_a2e_resident_begin_pol(cells, NFREQ, polarised) is soc_a2e_resident_begin that, with polarised != 0, also allocates that
+ *       second sum (zeroed; 4*cells*NFREQ bytes more, counted in the memory check) and 8 bytes per cell for a_alg and log10(a_alg);
+ *   soc_a2e_resident_upload_aalg(c0, n, aalg, lgaalg) fills rows [c0, c0+n) of both (the file of A2E.py:415 and its log10 as numpy
+ *       takes it, :425); rows never uploaded are aligned for no size;
+ *   soc_a2e_set_size_aalg(ASIZE[isize], ASIZE[isize+1] or 0 for the last size, log10(ASIZE[isize]),
+ *       log10(ASIZE[isize+1]) - log10(ASIZE[isize])) gives the weights of the size of the last soc_a2e_set_size (A2E.py:417, :423-425):
+ *       W = 1 where ASIZE[isize] >= a_alg, (log10(a_alg) - log10(ASIZE[isize])) / the difference where a_alg lies strictly between the
+ *       two sizes, else 0 -- one float subtraction, one float division, then the float product W * emission and the float sum, each
+ *       rounded as numpy's float32 expressions are.  soc_a2e_set_size clears the weights: a size solved without this call adds
+ *       nothing to the polarised sum;
+ *   soc_a2e_resident_download_p(c0, n, PEMIT) reads rows of the polarised sum (SOC_ERR_STATE where it was not asked for).
+ * Without these calls the family behaves as before. */
+int soc_a2e_resident_begin_pol(soc_ctx *ctx, int64_t cells, int NFREQ, int polarised);
+int soc_a2e_resident_upload_aalg(soc_ctx *ctx, int64_t c0, int64_t n, const float *aalg, const float *lgaalg);
+int soc_a2e_set_size_aalg(soc_ctx *ctx, float asize, float asize_next, float lg_asize, float lg_step);
+int soc_a2e_resident_download_p(soc_ctx *ctx, int64_t c0, int64_t n, float *PEMIT);
+
 /* replaces kernel_T(...) = EqTemperature for one batch (A2E.py:511-530 -> kernel_A2E.c:110-154);
  * TTT holds NIP temperatures, ABS is [batch*NFREQ] (already multiplied by AF on the host),
  * outputs T[batch] and EMIT[batch*NFREQ] */
@@ -627,6 +647,26 @@ int soc_mabu_accumulate(soc_ctx *ctx, int idust);
 int soc_mabu_download(soc_ctx *ctx, int64_t c0, int64_t n, float *SUM);
 int soc_mabu_read_part(soc_ctx *ctx, int64_t c0, int64_t n, float *PART);
 int soc_mabu_end(soc_ctx *ctx);
+
+/* `polarisation <dust> <aalg file>` of A2E_MABU.py (:158-167): the polarisation reduction factor R = polarised / total emission.
+ *   soc_mabu_begin_pol(cells, NFREQ, NDUST, polarised, &fit) is soc_mabu_begin that, with polarised != 0, also reserves the current
+ *       dust's polarised emission PEM (the polarised sum of soc_a2e_resident_*), its zeroed sum PSUM and a_alg with its log10
+ *       (8*NFREQ + 8 bytes more per cell, counted in *fit); soc_mabu_split then zeroes PEM as well;
+ *   soc_a2e_resident_upload_aalg fills the rows of a_alg of the current dust's aalg file (the rows of the resident cell range);
+ *   a stochastically heated dust gets PEM from soc_a2e_set_size_aalg before every soc_a2e_resident_solve (A2E_MABU.py:971-984 runs
+ *       A2E.py with the aalg file);
+ *   soc_mabu_pol_eq(NA, APOL, TAB) gives an equilibrium dust's PEM = EM * ipR_f(a_alg) (A2E_MABU.py:615-637): APOL[NA] the sizes of
+ *       <dust>.rpol (not decreasing), TAB[NFREQ][NA] its columns interpolated to the frequencies (:626-633, done by the caller);
+ *       ipR_f is linear between the nodes (slope = (y1-y0)/(x1-x0), y = slope*(a-x0) + y0 in double, the node value on a node) and
+ *       0 outside them (:635), the product with EM is taken in double and rounded to float once (:637);
+ *   soc_mabu_accumulate_p(idust) adds PEM * ABU[:, idust] to PSUM as soc_mabu_accumulate does for the emission (:1139-1147);
+ *   soc_mabu_ratio() turns PSUM into R = PSUM / (SUM + 1e-32) in float (:1182), once, after the last dust;
+ *   soc_mabu_download_p(c0, n, R) reads rows of it (:1195-1197). */
+int soc_mabu_begin_pol(soc_ctx *ctx, int64_t cells, int NFREQ, int NDUST, int polarised, int64_t *cells_fit);
+int soc_mabu_pol_eq(soc_ctx *ctx, int NA, const double *APOL, const double *TAB);
+int soc_mabu_accumulate_p(soc_ctx *ctx, int idust);
+int soc_mabu_ratio(soc_ctx *ctx);
+int soc_mabu_download_p(soc_ctx *ctx, int64_t c0, int64_t n, float *R);
 
 /* ---- the library method for dust emission: soc_library.py with kernel_soc_library.c ---- */
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """a2e -- emission of stochastically heated grains on MI355X:
 
-    python -m soc_amd.a2e  dust.solver  absorbed.data  emitted.data  [GPU [NSTOCH [IFREQ]]]
+    python -m soc_amd.a2e  dust.solver  absorbed.data  emitted.data  [GPU [NSTOCH [IFREQ [aalg]]]]
 
 Drop-in for ``A2E.py solver absorbed emitted`` (reference A2E.py:64-66): same solver file
 (written by A2E_pre.py), same absorbed/emitted files.  For every grain size the absorptions of
@@ -9,7 +9,11 @@ all cells go through the HIP ``DoSolve`` (sizes < NSTOCH) or ``EqTemperature`` (
 and the emission is accumulated (A2E.py:453-600).  Differences that are the point of the
 rewrite: no run-time kernel build, no 266 MB global scratch matrix (the transition matrix
 lives in LDS), batches are sized by memory, not by the scratch buffer.
+
+With the seventh argument, a file {CELLS} aalg[CELLS] of each cell's minimum aligned grain size, the emission of the grains larger
+than that is written to <emitted>.P as well (A2E.py:28-29, 192-197, 413-429, 533-539): the polarised emission.
 """
+import os
 import sys
 import time
 
@@ -48,14 +52,52 @@ def eq_table(sol, isize):
     return Emin, kE, oplgkE, TTT, np.asarray(KABS, np.float32)
 
 
-def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True):
-    """ABSORBED[CELLS,NFREQ] -> EMITTED[CELLS,NFREQ or 1].  Returns (EMITTED, kernel_seconds)."""
+def aalg_weights(ASIZE, isize, aalg, stochastic=True):
+    """The share of size `isize` that is aligned in cells of minimum aligned size aalg (A2E.py:413-429; for an equilibrium size the
+    hard mask alone, :533-539).  Returns (full, part, w): full where ASIZE[isize] >= aalg (weight 1), part where aalg lies strictly
+    between this size and the next (none for the last size), w[cells] float32 the weight there (0 elsewhere):
+    (log10(aalg) - log10(ASIZE[isize])) / (log10(ASIZE[isize+1]) - log10(ASIZE[isize])), float32 all the way as numpy evaluates the
+    reference's line.  The weight grows towards the upper size, as the reference's does."""
+    ASIZE, aalg = np.asarray(ASIZE, np.float32), np.asarray(aalg, np.float32)
+    full = ASIZE[isize] >= aalg
+    part = np.zeros(aalg.shape, bool)
+    w = np.zeros(aalg.shape, np.float32)
+    if stochastic and isize < ASIZE.size - 1:
+        part = (ASIZE[isize] < aalg) & (ASIZE[isize + 1] > aalg)
+        w[part] = (np.log10(aalg[part]) - np.log10(ASIZE[isize])) / (np.log10(ASIZE[isize + 1]) - np.log10(ASIZE[isize]))
+    return full, part, w
+
+
+def aalg_weight(ASIZE, isize, aalg, stochastic=True):
+    """aalg_weights as one array W[cells]: 1, w or 0"""
+    full, part, w = aalg_weights(ASIZE, isize, aalg, stochastic)
+    return np.where(full, np.float32(1.0), np.where(part, w, np.float32(0.0))).astype(np.float32)
+
+
+def _add_polarised(PEM, emit, full, part, w):
+    """PEMITTED[m] += emit[m] and PEMITTED[m] += w * emit[m] (A2E.py:417-429) on rows of PEM; emit[rows, columns of PEM]"""
+    PEM[full] += emit[full]
+    if part.any():
+        PEM[part] += w[part, None] * emit[part]
+
+
+def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, aalg=None):
+    """ABSORBED[CELLS,NFREQ] -> EMITTED[CELLS,NFREQ or 1].  Returns (EMITTED, kernel_seconds), or with aalg[CELLS] -- the minimum
+    aligned grain size of every cell -- (EMITTED, PEMITTED, kernel_seconds), PEMITTED the emission of the aligned grains."""
     CELLS, NFREQ = ABSORBED.shape
     if NFREQ != sol["NFREQ"]:
         raise ValueError("absorbed file has %d frequencies, solver %d" % (NFREQ, sol["NFREQ"]))
     ABSORBED = np.array(ABSORBED, np.float32)        # A2E.py:184-185: clip the last channel
     ABSORBED[:, NFREQ - 1] = np.clip(ABSORBED[:, NFREQ - 1], 0.0, 0.2 * ABSORBED[:, NFREQ - 2])
     EMITTED = np.zeros((CELLS, 1 if IFREQ >= 0 else NFREQ), np.float32)
+    PEMITTED = None
+    if aalg is not None:
+        aalg = np.ascontiguousarray(aalg, np.float32)
+        if aalg.shape != (CELLS,):
+            raise ValueError("aalg holds %s values, the absorptions %d cells" % (aalg.shape, CELLS))
+        PEMITTED = np.zeros_like(EMITTED)
+    cols = slice(IFREQ, IFREQ + 1) if IFREQ >= 0 else slice(None)
+    ASIZE = sol["SIZE_A"]
     tker = 0.0
     # The stochastically heated sizes with the cells resident in device memory (soc_a2e_resident_*): absorptions up once, every size a
     # launch over all cells that adds its emission to a sum on the device, the sum down once -- instead of NSIZE round trips of every
@@ -63,9 +105,12 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True):
     # follow it (they come last in the loop: isize >= NSTOCH), so the result is the same to the bit.
     nstoch = min(int(NSTOCH), len(sol["sizes"]), sol["NSIZE"])
     resident = False
-    if nstoch > 0 and hasattr(engine, "a2e_resident_begin"):
+    if nstoch > 0 and hasattr(engine, "a2e_resident_begin") and (aalg is None or hasattr(engine, "a2e_resident_upload_aalg")):
         try:
-            engine.a2e_resident_begin(CELLS, NFREQ)
+            if aalg is None:
+                engine.a2e_resident_begin(CELLS, NFREQ)
+            else:
+                engine.a2e_resident_begin(CELLS, NFREQ, polarised=True)
             resident = True
         except Exception as err:                                  # not enough device memory: batches as before
             if verbose:
@@ -75,8 +120,12 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True):
             t0 = time.time()
             for icell in range(0, CELLS, batch):
                 engine.a2e_resident_upload(icell, ABSORBED[icell:min(icell + batch, CELLS), :])
+                if aalg is not None:
+                    engine.a2e_resident_upload_aalg(icell, aalg[icell:min(icell + batch, CELLS)])
             for isize in range(nstoch):
                 engine.a2e_set_size(sol["NE"], NFREQ, sol["sizes"][isize], a2e_absorption_fraction(sol, isize))
+                if aalg is not None:
+                    engine.a2e_set_size_aalg(ASIZE, isize)       # (the kernel's epilogue adds W * emission to the second sum)
                 engine.a2e_resident_solve()
                 if verbose:
                     print("    isize = %d   stochastic heating" % isize)
@@ -87,6 +136,8 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True):
                     EMITTED[icell:b, 0] += emit[:, IFREQ]
                 else:
                     EMITTED[icell:b, :] += emit
+                if aalg is not None:
+                    PEMITTED[icell:b, :] += engine.a2e_resident_download_p(icell, b - icell)[:, cols]
             tker += time.time() - t0
         finally:
             engine.a2e_resident_end()
@@ -107,6 +158,9 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True):
                     EMITTED[icell:b, 0] += emit[:, IFREQ] * scale
                 else:
                     EMITTED[icell:b, :] += emit * scale
+                if aalg is not None:                               # A2E.py:533-539: the hard mask, the reference's own product
+                    full = aalg_weights(ASIZE, isize, aalg[icell:b], stochastic=False)[0]
+                    PEMITTED[icell:b][full] += emit[full][:, cols] * sol["GD"] * sol["S_FRAC"][isize]
             continue
         if resident:
             continue
@@ -120,9 +174,23 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True):
                 EMITTED[icell:b, 0] += emit[:, IFREQ]
             else:
                 EMITTED[icell:b, :] += emit
+            if aalg is not None:                                   # A2E.py:413-429, on the emission of this batch and size
+                _add_polarised(PEMITTED[icell:b], emit[:, cols], *aalg_weights(ASIZE, isize, aalg[icell:b]))
         if verbose:
             print("    isize = %d   stochastic heating" % isize)
+    if aalg is not None:
+        return EMITTED, PEMITTED, tker
     return EMITTED, tker
+
+
+def read_aalg(filename, CELLS):
+    """aalg file {CELLS} aalg[CELLS] float32 (A2E.py:382-386: a file for another number of cells is refused)"""
+    cells = np.fromfile(filename, np.int32, 1)
+    if cells.size != 1 or int(cells[0]) != CELLS:
+        raise files.FileError("%s is an aalg file for %s cells, the run has %d" % (filename, int(cells[0]) if cells.size else "no", CELLS))
+    if os.path.getsize(filename) < 4 + 4 * CELLS:
+        raise files.FileError("%s: fewer than %d values" % (filename, CELLS))
+    return np.memmap(filename, dtype=np.float32, mode='r', offset=4, shape=(CELLS,))
 
 
 def cell_range(CELLS, rank, world):
@@ -131,20 +199,24 @@ def cell_range(CELLS, rank, world):
     return min(rank * per, CELLS), min((rank + 1) * per, CELLS)
 
 
-def run_sharded(engine_factory, solver, absorbed, emitted, NSTOCH=999, IFREQ=-1, comm=None, verbose=True):
+def run_sharded(engine_factory, solver, absorbed, emitted, NSTOCH=999, IFREQ=-1, comm=None, verbose=True, aalg=None):
     """The whole program for one rank of `comm` (or alone): memory-map the absorbed file, solve this rank's cells,
     write them into this rank's part of the emitted file.  No collective on the data path -- the ranks only wait
-    for rank 0 to have created the file, and for each other at the end.  Returns (cells solved, kernel seconds)."""
+    for rank 0 to have created the file, and for each other at the end.  aalg: the file of the minimum aligned grain sizes; the
+    polarised emission then goes to <emitted>.P in the same way.  Returns (cells solved, kernel seconds)."""
     rank, world = (comm.rank, comm.world) if comm else (0, 1)
     sol = files.read_solver(solver)
     dims = np.fromfile(absorbed, np.int32, 2)
     CELLS, NFREQ = int(dims[0]), int(dims[1])
     ABS = np.memmap(absorbed, dtype=np.float32, mode='r', offset=8, shape=(CELLS, NFREQ))
     nout = 1 if IFREQ >= 0 else NFREQ
+    AALG = read_aalg(aalg, CELLS) if aalg else None
+    outs = [emitted] + ([emitted + '.P'] if aalg else [])
     if rank == 0:
-        with open(emitted, 'wb') as fp:
-            np.asarray([CELLS, nout], np.int32).tofile(fp)
-            fp.truncate(8 + 4 * CELLS * nout)
+        for name in outs:
+            with open(name, 'wb') as fp:
+                np.asarray([CELLS, nout], np.int32).tofile(fp)
+                fp.truncate(8 + 4 * CELLS * nout)
     if comm:
         comm.barrier()
     c0, c1 = cell_range(CELLS, rank, world)
@@ -152,14 +224,16 @@ def run_sharded(engine_factory, solver, absorbed, emitted, NSTOCH=999, IFREQ=-1,
     if c1 > c0:
         eng = engine_factory()
         try:
-            EM, tker = run(eng, sol, ABS[c0:c1, :], NSTOCH, IFREQ, verbose=verbose and rank == 0)
+            res = run(eng, sol, ABS[c0:c1, :], NSTOCH, IFREQ, verbose=verbose and rank == 0, aalg=None if AALG is None else AALG[c0:c1])
+            tker = res[-1]
         finally:
             if hasattr(eng, "close"):
                 eng.close()
-        out = np.memmap(emitted, dtype=np.float32, mode='r+', offset=8, shape=(CELLS, nout))
-        out[c0:c1, :] = EM
-        out.flush()
-        del out
+        for name, EM in zip(outs, res[:-1]):
+            out = np.memmap(name, dtype=np.float32, mode='r+', offset=8, shape=(CELLS, nout))
+            out[c0:c1, :] = EM
+            out.flush()
+            del out
     if comm:
         comm.barrier()
     return c1 - c0, tker
@@ -168,17 +242,18 @@ def run_sharded(engine_factory, solver, absorbed, emitted, NSTOCH=999, IFREQ=-1,
 def main(argv=None):
     argv = sys.argv if argv is None else argv
     if len(argv) < 4:
-        print("Usage:  python -m soc_amd.a2e  solver absorbed emitted [GPU [NSTOCH [IFREQ]]]")
+        print("Usage:  python -m soc_amd.a2e  solver absorbed emitted [GPU [NSTOCH [IFREQ [aalg]]]]")
         print("        (N GPUs: python -m torch.distributed.run --nproc-per-node N -m soc_amd.a2e ...)")
         return 1
     from .lib import Engine
     from .dist import Comm
     NSTOCH = int(argv[5]) if len(argv) > 5 else 999
     IFREQ = int(argv[6]) if len(argv) > 6 else -1
+    aalg = argv[7] if len(argv) > 7 else None                  # A2E.py:104
     t0 = time.time()
     comm = Comm()
     n, tker = run_sharded(lambda: Engine(comm.local_rank), argv[1], argv[2], argv[3], NSTOCH, IFREQ,
-                          comm if comm.world > 1 else None)
+                          comm if comm.world > 1 else None, aalg=aalg)
     DT = time.time() - t0
     if comm.rank == 0:
         print('@@  a2e %.3f SECONDS   (solver calls %.3f s on rank 0, %d ranks)' % (DT, tker, comm.world))

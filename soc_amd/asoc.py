@@ -1036,16 +1036,20 @@ class AbsorptionRun:
             fp.close()
         return ["map_dir_%02d_H.bin" % idir for idir in range(NDIR)]
 
-    def polarisation_field(self, healpix=False):
+    def polarisation_field(self, healpix=False, R=None):
         """The three B files of `polmap` (the layout of the cloud file: every cell, parents included) with the polarisation
         reduction factor R of `polred` encoded in the length of the vectors, B * R / sqrt(B^2 + 1e-10) (ASOC.py:3676-3720):
         `adhoc` -- R from the dust temperatures of the `temperature` file; `rhofun_<threshold>_<width>` -- from the density
         (times `density`); anything else -- a plain file [cells, {R}], clipped to [1e-6, 0.999999].  polstat 3 uses the
         vectors as they are.  healpix: the encoding of the Healpix branch (ASOC.py:3836-3872), B * R / sqrt(B^2) with a
-        file's R as it is."""
+        file's R as it is.  R: the factors R[cells] themselves where the ini names no `polred` -- treated as a plain file's are."""
         U, c = self.U, self.cloud
         BB = [np.asarray(files.read_temperature(f, c), np.float32) for f in U.BFILES[:3]]
         polred = getattr(U, "file_polred", "")
+        if len(polred) == 0 and R is not None:
+            polred, given = "the polarisation reduction factors of the emission stage", np.asarray(R, np.float32)
+        else:
+            given = None
         if U.POLSTAT != 3 and len(polred) > 0:
             if polred == 'adhoc':
                 R = files.read_temperature(U.file_temperature, c)
@@ -1060,7 +1064,7 @@ class AbsorptionRun:
                 R = np.clip(R, 0.1, 1e10)
                 R = 0.5 * (1.0 + np.tanh((np.log10(th) - np.log10(R)) / sw))
             else:
-                R = np.fromfile(polred, np.float32)[1:]
+                R = np.fromfile(polred, np.float32)[1:] if given is None else given
                 if not healpix:
                     R = np.clip(R, 1.0e-6, 0.999999)
                 if R.size != c.CELLS:
@@ -1091,27 +1095,34 @@ class AbsorptionRun:
             sel.append(IFREQ)
         return I1, sel
 
-    def write_polmaps(self, EMITTED):
+    def write_polmaps(self, EMITTED, R=None):
         """`polmap bx by bz`: polarisation maps from the emission (ASOC.py:3651-3801 -> PolMapping): for every selected
         frequency and observer direction polmap_<um>_<dir>.fits with data [4, NPIX.y, NPIX.x] -- I, Q, U [Jy/sr] and the
         column density (polstat 0), the line-of-sight statistics rT, rI, jT, jI of the field (polstat 1), or <B>, <B_LOS>,
-        <B_POS>, tau (polstat 3).  Written under `nomap` as well, as in the reference (:3655)."""
+        <B_POS>, tau (polstat 3).  Written under `nomap` as well, as in the reference (:3655).  R[CELLS, columns of EMITTED]: the
+        polarisation reduction factor per frequency from the emission stage, used where the ini has no `polred` -- every map with
+        the column of its frequency (the reference needs that column copied into a `polred` file by hand, A2E_MABU.py:1190-1195)."""
         U, e, c = self.U, self.eng, self.cloud
         if not (U.POLMAP > 0 and U.NPIX[1] > 0):
             return []
-        e.set_bfield(*self.polarisation_field())
+        if len(getattr(U, "file_polred", "")) > 0:
+            R = None
+        if R is None:
+            e.set_bfield(*self.polarisation_field())
         I1, sel = self.polmap_frequencies()
         NDIR, ODIR, RA, DE = launch.set_observer_directions(U.OBS_THETA, U.OBS_PHI)
         centre = U.MAPCENTRE if U.MAPCENTRE[0] > -1e7 else (0.5 * c.NX, 0.5 * c.NY, 0.5 * c.NZ)   # ASOC_aux.py:791-793
         KK = (1.0e23 / launch.FACTOR) * PLANCK / (4.0 * np.pi) * (U.GL * PARSEC)                 # ASOC.py:3753-3754
         _, LENGTH_f = launch.kernel_literals(U.GL)
         pix = U.GL * U.MAP_DX / (U.DISTANCE if U.DISTANCE > 0.0 else 1000.0)
-        polred = int(U.POLSTAT != 3 and len(getattr(U, "file_polred", "")) > 0)                  # -D POLRED (ASOC.py:349,359)
+        polred = int(U.POLSTAT != 3 and (len(getattr(U, "file_polred", "")) > 0 or R is not None))    # -D POLRED (ASOC.py:349,359)
         p0 = float("%.4f" % U.p0)                                                               # -D p00=%.4ff
         written = []
         for IFREQ in sel:
             FREQ = float(self.FFREQ[IFREQ])
             ABS, SCA = self._optical_for(IFREQ)
+            if R is not None:
+                e.set_bfield(*self.polarisation_field(R=R[:, IFREQ - I1]))
             EMIT = np.asarray(KK * FREQ * EMITTED[:, IFREQ - I1], np.float32)                    # :3788
             for idir in range(NDIR):
                 MAP = e.polmap(EMIT, ODIR[idir], RA[idir], DE[idir], U.NPIX, U.MAP_DX, centre, ABS, SCA, polstat=int(U.POLSTAT),
@@ -1124,20 +1135,22 @@ class AbsorptionRun:
         e.set_bfield(None)
         return written
 
-    def write_healpix_polmaps(self, EMITTED):
+    def write_healpix_polmaps(self, EMITTED, R=None):
         """`polmap bx by bz [[minlos] maxlos]` with `mapping NSIDE -1 dx` and `perspective x y z`: all-sky polarisation maps
         seen from inside the model (ASOC.py:3808-3958 -> PolHealpixMapping, kernel_ASOC_map_H.c, POLSTAT 0): for every
         frequency of the emitted range inside `wavelength` (:3911-3918; no `mapum` in this branch) pol_healpix.fits.<IFREQ>,
         a Healpix table with the columns I_STOKES, Q_STOKES, U_STOKES [Jy/sr] and N.  Unlike the flat maps these are not
-        written under `nomap` (:3808).  `interpolate` and `yshear` act here, and only here."""
+        written under `nomap` (:3808).  `interpolate` and `yshear` act here, and only here.  R: as in write_polmaps."""
         U, e, c = self.U, self.eng, self.cloud
         if not (U.POLMAP > 0 and U.NOMAP == 0 and U.NPIX[1] < 0):
             return []
+        if len(getattr(U, "file_polred", "")) > 0:
+            R = None
         # the field with `polred` encoded as THIS branch of the reference does it (:3867-3869): a file's R is not clipped and
         # nothing is added under the root -- unlike the flat branch (:3710-3716)
-        BB = self.polarisation_field(healpix=True)
-        polred = int(len(getattr(U, "file_polred", "")) > 0)                                     # -D POLRED (ASOC.py:349,359)
-        e.set_bfield(*BB)
+        polred = int(len(getattr(U, "file_polred", "")) > 0 or R is not None)                    # -D POLRED (ASOC.py:349,359)
+        if R is None:
+            e.set_bfield(*self.polarisation_field(healpix=True))
         FFREQ = self.FFREQ
         m = np.nonzero((FFREQ >= U.REMIT_F[0]) & (FFREQ <= U.REMIT_F[1]))[0]
         I1, I2 = int(m[0]), int(m[-1])
@@ -1152,6 +1165,8 @@ class AbsorptionRun:
             FREQ = float(FFREQ[IFREQ])
             ABS, SCA = self._optical_for(IFREQ)
             EMIT = np.asarray(KK * FREQ * EMITTED[:, IFREQ - I1], np.float32)                    # :3944
+            if R is not None:
+                e.set_bfield(*self.polarisation_field(healpix=True, R=R[:, IFREQ - I1]))
             MAP = e.polmap_healpix(EMIT, NSIDE, U.INTOBS, ABS, SCA, polred=polred, p0=p0, interpolate=int(U.INTERPOLATE), minlos=minlos,
                                    maxlos=maxlos, y_shear=float(U.Y_SHEAR), LENGTH=LENGTH_f)
             if self.rank != 0:

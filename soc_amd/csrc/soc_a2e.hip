@@ -61,7 +61,14 @@ __device__ __forceinline__ float a2e_row_sum(const float *Lr, const float *X, co
                                      // per CU, so the waves that hide the latency of the weight reads must be its own); four of them solve
 #define A2E_Q 2                      // pairs a lane has in flight in step 1
 
-template <int C>
+// POL: the emission is also added, weighted, to a second row PEMIT -- the polarised emission of the grains larger than the cell's
+// minimum aligned size a (A2E.py:413-429).  The weight of this size (A.p_size = ASIZE[isize], A.p_next = ASIZE[isize+1], or 0 for the
+// last size, which has no partial arm):  1 where p_size >= a;  (log10(a) - log10(p_size)) / (log10(p_next) - log10(p_size)) where
+// p_size < a < p_next;  else 0, and the row is not touched.  AALG holds a and log10(a) per cell (the logarithm is numpy's, taken on the
+// host); the subtraction, the division, the product w * I and the sum are single fp32 operations (the build has -ffp-contract=off), so
+// the bits are those of numpy's float32 expressions.  Without POL the kernel is the one it was: the three plain instances keep their
+// instructions.
+template <int C, bool POL>
 __global__ __launch_bounds__(A2E_T) void soc_a2e_dosolve_kernel(const SocA2EArgs A)
 {
     extern __shared__ float lds[];
@@ -206,6 +213,13 @@ __global__ __launch_bounds__(A2E_T) void soc_a2e_dosolve_kernel(const SocA2EArgs
     // 4. emission (kernel_A2E.c:95-100): one frequency per lane, serial over the bins
     if (mine) {
         float *EMIT = A.AEMIT + (size_t)(cell0 + wv) * NFREQ;
+        int   arm = 0;                                        // 0: this size is not aligned in the cell, 1: wholly, 2: in part (weight pw)
+        float pw = 0.0f;
+        if constexpr (POL) {
+            const float a = A.AALG[2 * (size_t)(cell0 + wv)], lga = A.AALG[2 * (size_t)(cell0 + wv) + 1];
+            if (A.p_size >= a) arm = 1;
+            else if (A.p_size < a && A.p_next > a) { arm = 2;  pw = (lga - A.p_lgsize) / A.p_lgden; }
+        }
         for (int f = lane; f < NFREQ; f += 64) {
             float I = 0.0f;
             const float *ea = A.EA + f;                       // EA transposed: [bin][frequency]
@@ -213,6 +227,11 @@ __global__ __launch_bounds__(A2E_T) void soc_a2e_dosolve_kernel(const SocA2EArgs
 #pragma unroll 8
             for (int i = ib; i < NE; i++) I += ea[(size_t)i * NFREQ] * XL[i];
             EMIT[f] = A.accumulate ? (EMIT[f] + I) : I;       // (the host's EMITTED += emit of A2E.py:596-600, size after size: the same fp32 additions)
+            if constexpr (POL) {
+                float *P = A.PEMIT + (size_t)(cell0 + wv) * NFREQ + f;
+                if (arm == 1) *P = *P + I;                    // PEMITTED[m] += emit[m]          (A2E.py:417-421)
+                else if (arm == 2) { const float wI = pw * I;  *P = *P + wI; }     // PEMITTED[m] += w * emit[m]   (A2E.py:424-429)
+            }
         }
     }
     A2E_PROF(4);                                         // emission
@@ -294,15 +313,22 @@ bool soc_a2e_shape(int NE, int NFREQ, int out[3])
     return true;
 }
 
+template <int C, bool POL>
+static hipError_t a2e_launch_as(const SocA2EArgs &A, int T, size_t lds, hipStream_t st)
+{
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)soc_a2e_dosolve_kernel<C, POL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    soc_a2e_dosolve_kernel<C, POL><<<(A.batch + C - 1) / C, T, lds, st>>>(A);
+    return hipGetLastError();
+}
+
 template <int C>
 static hipError_t a2e_launch(const SocA2EArgs &A, int T, size_t lds, hipStream_t st)
 {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)soc_a2e_dosolve_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    soc_a2e_dosolve_kernel<C><<<(A.batch + C - 1) / C, T, lds, st>>>(A);
-    return hipGetLastError();
+    if (A.PEMIT) return a2e_launch_as<C, true>(A, T, lds, st);
+    return a2e_launch_as<C, false>(A, T, lds, st);
 }
 
 hipError_t soc_launch_a2e_dosolve(const SocA2EArgs &A, hipStream_t st)
@@ -310,6 +336,7 @@ hipError_t soc_launch_a2e_dosolve(const SocA2EArgs &A, hipStream_t st)
     if (A.batch <= 0) return hipSuccess;
     int shape[3];
     if (!soc_a2e_shape(A.NE, A.NFREQ, shape)) return hipErrorInvalidValue;
+    if (A.PEMIT && !A.AALG) return hipErrorInvalidValue;
     if (shape[0] == 4) return a2e_launch<4>(A, shape[1], (size_t)shape[2], st);
     if (shape[0] == 2) return a2e_launch<2>(A, shape[1], (size_t)shape[2], st);
     return a2e_launch<1>(A, shape[1], (size_t)shape[2], st);

@@ -61,6 +61,7 @@ int soc_a2e_set_size(soc_ctx *c, int NE, int NFREQ, int noIw, const float *Iw, c
     HIPCHK(c, hipMemcpy(c->aAF, AF, (size_t)NFREQ * 4, hipMemcpyHostToDevice));
     if (NFREQ != c->a2e_NFREQ) { c->aABS.release();  c->aEMIT.release(); }      // (a batch uploaded for another NFREQ is none: soc_a2e_run)
     c->a2e_NE = NE;  c->a2e_NFREQ = NFREQ;  c->a2e_npair = npair;  c->a2e_noIw = noIw;
+    c->a2e_pol_set = false;                                 // (the weights belong to a size: soc_a2e_set_size_aalg gives those of this one)
     return SOC_OK;
 }
 
@@ -119,11 +120,16 @@ int soc_a2e_download(soc_ctx *c, int batch, float *AEMIT)
 // ---- config 5 with the cells resident in HBM ----
 static void resident_release(soc_ctx *c)
 {
-    c->aAll.release();  c->aSum.release();
-    c->a2e_cells = 0;
+    c->aAll.release();  c->aSum.release();  c->aPSum.release();  c->aAalg.release();
+    c->a2e_cells = 0;  c->a2e_pol_set = false;
 }
 
 int soc_a2e_resident_begin(soc_ctx *c, int64_t cells, int NFREQ)
+{
+    return soc_a2e_resident_begin_pol(c, cells, NFREQ, 0);
+}
+
+int soc_a2e_resident_begin_pol(soc_ctx *c, int64_t cells, int NFREQ, int polarised)
 {
     if (!c) return SOC_ERR_ARG;
     FLUSH(c);
@@ -133,14 +139,24 @@ int soc_a2e_resident_begin(soc_ctx *c, int64_t cells, int NFREQ)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    const size_t need = (size_t)cells * NFREQ * 8;
-    if (need + ((size_t)1 << 30) > free_b + (c->aAll ? (size_t)c->a2e_cells * c->a2e_res_nfreq * 8 : 0))
+    const size_t need = (size_t)cells * NFREQ * 8 + (polarised ? (size_t)cells * NFREQ * 4 + (size_t)cells * 8 : 0);
+    const size_t held = (c->aAll ? (size_t)c->a2e_cells * c->a2e_res_nfreq * 8 : 0) + (c->aPSum.n + c->aAalg.n) * 4;
+    if (need + ((size_t)1 << 30) > free_b + held)
         return fail(c, SOC_ERR_STATE, "soc_a2e_resident_begin: %lld cells x %d frequencies need %.1f GB of device memory, %.1f GB are free (use soc_a2e_solve in batches)",
                     (long long)cells, NFREQ, need * 1e-9, free_b * 1e-9);
     const size_t n = (size_t)cells * NFREQ;
     hipError_t e = c->aAll.reset(n, c->stream);
     if (e == hipSuccess) e = c->aSum.reset(n, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->aSum, 0, n * 4, c->stream);
+    if (polarised) {
+        if (e == hipSuccess) e = c->aPSum.reset(n, c->stream);
+        if (e == hipSuccess) e = c->aAalg.reset((size_t)cells * 2, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(c->aPSum, 0, n * 4, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(c->aAalg, 0xff, (size_t)cells * 8, c->stream);    // (NaN: rows never uploaded are aligned for no size)
+    } else {
+        c->aPSum.release();  c->aAalg.release();
+    }
+    c->a2e_pol_set = false;
     if (e != hipSuccess) {                                  // all or nothing: half of the arrays would be gigabytes nobody can use
         resident_release(c);
         return fail(c, SOC_ERR_HIP, "soc_a2e_resident_begin: %s", hipGetErrorString(e));
@@ -159,6 +175,28 @@ int soc_a2e_resident_upload(soc_ctx *c, int64_t c0, int64_t n, const float *AABS
     return SOC_OK;
 }
 
+int soc_a2e_resident_upload_aalg(soc_ctx *c, int64_t c0, int64_t n, const float *aalg, const float *lgaalg)
+{
+    if (!c || !aalg || !lgaalg) return SOC_ERR_ARG;
+    if (!c->aAalg || !c->aPSum) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_upload_aalg: polarised output was not asked for (soc_a2e_resident_begin_pol, soc_mabu_begin_pol)");
+    if (c0 < 0 || n < 1 || c0 + n > c->a2e_cells) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_upload_aalg: cells [%lld, %lld) of %lld", (long long)c0, (long long)(c0 + n), (long long)c->a2e_cells);
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<float> both((size_t)n * 2);
+    for (int64_t i = 0; i < n; i++) { both[2 * i] = aalg[i];  both[2 * i + 1] = lgaalg[i]; }
+    HIPCHK(c, hipMemcpyAsync(c->aAalg + (size_t)c0 * 2, both.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
+int soc_a2e_set_size_aalg(soc_ctx *c, float asize, float asize_next, float lg_asize, float lg_step)
+{
+    if (!c) return SOC_ERR_ARG;
+    if (c->a2e_NE == 0) return fail(c, SOC_ERR_STATE, "soc_a2e_set_size_aalg: call soc_a2e_set_size first");
+    c->a2e_pol[0] = asize;  c->a2e_pol[1] = asize_next;  c->a2e_pol[2] = lg_asize;  c->a2e_pol[3] = lg_step;
+    c->a2e_pol_set = true;
+    return SOC_OK;
+}
+
 int soc_a2e_resident_solve(soc_ctx *c)
 {
     if (!c) return SOC_ERR_ARG;
@@ -170,10 +208,13 @@ int soc_a2e_resident_solve(soc_ctx *c)
     A.Iw = c->aIw;  A.pair_first = c->aFirst;  A.pair_last = c->aLast;  A.pair_iw = c->aIwOff;  A.pair_dst = c->aDst;
     A.Tdown = c->aTdown;  A.EA = c->aEA;  A.Ibeg = c->aIbeg;  A.AF = c->aAF;
     A.accumulate = 1;
+    const bool pol = c->aPSum && c->aAalg && c->a2e_pol_set;   // (a size without soc_a2e_set_size_aalg adds nothing to the polarised sum)
+    if (pol) { A.p_size = c->a2e_pol[0];  A.p_next = c->a2e_pol[1];  A.p_lgsize = c->a2e_pol[2];  A.p_lgden = c->a2e_pol[3]; }
     const int64_t step = 1 << 20;                           // cells per launch (the grid is one workgroup per four cells)
     for (int64_t c0 = 0; c0 < c->a2e_cells; c0 += step) {
         A.batch = (int)std::min<int64_t>(step, c->a2e_cells - c0);
         A.AABS = c->aAll + (size_t)c0 * A.NFREQ;  A.AEMIT = c->aSum + (size_t)c0 * A.NFREQ;
+        if (pol) { A.PEMIT = c->aPSum + (size_t)c0 * A.NFREQ;  A.AALG = c->aAalg + (size_t)c0 * 2; }
         HIPCHK(c, soc_launch_a2e_dosolve(A, c->stream));
     }
     return SOC_OK;
@@ -185,6 +226,17 @@ int soc_a2e_resident_download(soc_ctx *c, int64_t c0, int64_t n, float *AEMIT)
     if (!c->aSum || c0 < 0 || n < 1 || c0 + n > c->a2e_cells) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_download: cells [%lld, %lld) of %lld", (long long)c0, (long long)(c0 + n), (long long)c->a2e_cells);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpyAsync(AEMIT, c->aSum + (size_t)c0 * c->a2e_res_nfreq, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
+int soc_a2e_resident_download_p(soc_ctx *c, int64_t c0, int64_t n, float *PEMIT)
+{
+    if (!c || !PEMIT) return SOC_ERR_ARG;
+    if (!c->aPSum) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_download_p: polarised output was not asked for (soc_a2e_resident_begin_pol, soc_mabu_begin_pol)");
+    if (c0 < 0 || n < 1 || c0 + n > c->a2e_cells) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_download_p: cells [%lld, %lld) of %lld", (long long)c0, (long long)(c0 + n), (long long)c->a2e_cells);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(PEMIT, c->aPSum + (size_t)c0 * c->a2e_res_nfreq, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SOC_OK;
 }
@@ -255,11 +307,17 @@ int soc_eqsolver(soc_ctx *c, int batch, int icell, int CELLS, int NFREQ, int NE,
 static void mabu_release(soc_ctx *c)
 {
     c->mABS.release();  c->mSUM.release();  c->mABU.release();  c->mT.release();  c->mTab.release();  c->mRABS.release();
+    c->mPSUM.release();  c->mPol.release();
     resident_release(c);
     c->mabu_ndust = 0;  c->mabu_tables = false;
 }
 
 int soc_mabu_begin(soc_ctx *c, int64_t cells, int NFREQ, int NDUST, int64_t *cells_fit)
+{
+    return soc_mabu_begin_pol(c, cells, NFREQ, NDUST, 0, cells_fit);
+}
+
+int soc_mabu_begin_pol(soc_ctx *c, int64_t cells, int NFREQ, int NDUST, int polarised, int64_t *cells_fit)
 {
     if (!c) return SOC_ERR_ARG;
     FLUSH(c);
@@ -274,7 +332,8 @@ int soc_mabu_begin(soc_ctx *c, int64_t cells, int NFREQ, int NDUST, int64_t *cel
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
     // per cell: absorptions, the dust's share, its emission, the sum (NFREQ floats each), NDUST abundances, a temperature
-    const size_t per_cell = (size_t)NFREQ * 16 + (size_t)NDUST * 4 + 4, reserve = (size_t)1 << 30;
+    // with polarised output also the dust's polarised emission and its sum (NFREQ floats each), a_alg and its logarithm
+    const size_t per_cell = (size_t)NFREQ * 16 + (size_t)NDUST * 4 + 4 + (polarised ? (size_t)NFREQ * 8 + 8 : 0), reserve = (size_t)1 << 30;
     const size_t need = (size_t)cells * per_cell;
     if (cells_fit) *cells_fit = free_b > reserve ? (int64_t)((free_b - reserve) / per_cell) : 0;
     if (need + reserve > free_b)
@@ -290,6 +349,14 @@ int soc_mabu_begin(soc_ctx *c, int64_t cells, int NFREQ, int NDUST, int64_t *cel
     if (e == hipSuccess) e = c->mRABS.reset((size_t)NFREQ * NDUST, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->mSUM, 0, n * 4, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->aSum, 0, n * 4, c->stream);
+    if (polarised) {
+        if (e == hipSuccess) e = c->aPSum.reset(n, c->stream);
+        if (e == hipSuccess) e = c->mPSUM.reset(n, c->stream);
+        if (e == hipSuccess) e = c->aAalg.reset((size_t)cells * 2, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(c->aPSum, 0, n * 4, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(c->mPSUM, 0, n * 4, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(c->aAalg, 0xff, (size_t)cells * 8, c->stream);
+    }
     if (e != hipSuccess) {
         mabu_release(c);
         return fail(c, SOC_ERR_HIP, "soc_mabu_begin: %s", hipGetErrorString(e));
@@ -342,6 +409,8 @@ int soc_mabu_split(soc_ctx *c, int idust, int clip_last)
     HIPCHK(c, soc_launch_mabu_split(c->a2e_cells, NFREQ, c->mabu_ndust, idust, c->mABS, c->mABU, c->mRABS, c->aAll, c->stream));
     if (clip_last) HIPCHK(c, soc_launch_mabu_clip(c->a2e_cells, NFREQ, c->aAll, c->stream));
     HIPCHK(c, hipMemsetAsync(c->aSum, 0, (size_t)c->a2e_cells * NFREQ * 4, c->stream));
+    if (c->aPSum) HIPCHK(c, hipMemsetAsync(c->aPSum, 0, (size_t)c->a2e_cells * NFREQ * 4, c->stream));
+    c->a2e_pol_set = false;
     return SOC_OK;
 }
 
@@ -377,6 +446,53 @@ int soc_mabu_accumulate(soc_ctx *c, int idust)
     return SOC_OK;
 }
 
+#define MABU_POL(c, who)                                                                                    \
+    do {                                                                                                    \
+        if (!(c)->mPSUM || !(c)->aPSum || !(c)->aAalg) return fail((c), SOC_ERR_STATE, who ": polarised output was not asked for (soc_mabu_begin_pol)");   \
+    } while (0)
+
+int soc_mabu_pol_eq(soc_ctx *c, int NA, const double *APOL, const double *TAB)
+{
+    if (!c || !APOL || !TAB) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_pol_eq");
+    MABU_POL(c, "soc_mabu_pol_eq");
+    if (NA < 2) return fail(c, SOC_ERR_ARG, "soc_mabu_pol_eq: %d sizes (at least 2)", NA);
+    for (int i = 1; i < NA; i++)
+        if (!(APOL[i] >= APOL[i - 1])) return fail(c, SOC_ERR_ARG, "soc_mabu_pol_eq: the sizes must not decrease (entry %d)", i);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int NFREQ = c->a2e_res_nfreq;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->mPol.reserve((size_t)NA * (NFREQ + 1), c->stream));
+    double *dA = c->mPol, *dT = dA + NA;
+    HIPCHK(c, hipMemcpyAsync(dA, APOL, (size_t)NA * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dT, TAB, (size_t)NA * NFREQ * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host tables may be temporaries)
+    HIPCHK(c, soc_launch_mabu_poleq(c->a2e_cells, NFREQ, NA, c->aSum, c->aAalg, dA, dT, c->aPSum, c->stream));
+    return SOC_OK;
+}
+
+int soc_mabu_accumulate_p(soc_ctx *c, int idust)
+{
+    if (!c) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_accumulate_p");
+    MABU_POL(c, "soc_mabu_accumulate_p");
+    if (!c->mabu_tables) return fail(c, SOC_ERR_STATE, "soc_mabu_accumulate_p: call soc_mabu_set_tables first");
+    if (idust < 0 || idust >= c->mabu_ndust) return fail(c, SOC_ERR_ARG, "soc_mabu_accumulate_p: dust %d of %d", idust, c->mabu_ndust);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, soc_launch_mabu_sum(c->a2e_cells, c->a2e_res_nfreq, c->mabu_ndust, idust, c->aPSum, c->mABU, c->mPSUM, c->stream));
+    return SOC_OK;
+}
+
+int soc_mabu_ratio(soc_ctx *c)
+{
+    if (!c) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_ratio");
+    MABU_POL(c, "soc_mabu_ratio");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, soc_launch_mabu_ratio(c->a2e_cells, c->a2e_res_nfreq, c->mSUM, c->mPSUM, c->stream));
+    return SOC_OK;
+}
+
 static int mabu_read(soc_ctx *c, const float *src, int64_t c0, int64_t n, float *out)
 {
     HIPCHK(c, hipSetDevice(c->device));
@@ -391,6 +507,15 @@ int soc_mabu_download(soc_ctx *c, int64_t c0, int64_t n, float *SUM)
     MABU_OPEN(c, "soc_mabu_download");
     MABU_ROWS(c, "soc_mabu_download", c0, n);
     return mabu_read(c, c->mSUM, c0, n, SUM);
+}
+
+int soc_mabu_download_p(soc_ctx *c, int64_t c0, int64_t n, float *PSUM)
+{
+    if (!c || !PSUM) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_download_p");
+    MABU_POL(c, "soc_mabu_download_p");
+    MABU_ROWS(c, "soc_mabu_download_p", c0, n);
+    return mabu_read(c, c->mPSUM, c0, n, PSUM);
 }
 
 int soc_mabu_read_part(soc_ctx *c, int64_t c0, int64_t n, float *PART)

@@ -243,6 +243,11 @@ struct SocA2EArgs {
     const float *AABS;               // [batch*NFREQ]
     float       *AEMIT;              // [batch*NFREQ]
     int          accumulate;         // 1: AEMIT += the emission of this size (the sum over the sizes stays on the device: soc_a2e_resident_*)
+    // polarised emission (A2E.py:413-429), NULL without: PEMIT += W * the emission, W from the cell's minimum aligned size and these scalars
+    float       *PEMIT;              // [batch*NFREQ]
+    const float *AALG;               // [batch][2]: a_alg and log10(a_alg) of the cell
+    float        p_size, p_next;     // ASIZE[isize]; ASIZE[isize+1], or 0 for the last size (no partial arm)
+    float        p_lgsize, p_lgden;  // log10(ASIZE[isize]); log10(ASIZE[isize+1]) - log10(ASIZE[isize])
 };
 
 struct SocEqTArgs {
@@ -266,6 +271,11 @@ hipError_t soc_launch_mabu_split(long long cells, int NFREQ, int NDUST, int idus
                                  float *PART, hipStream_t st);
 hipError_t soc_launch_mabu_clip(long long cells, int NFREQ, float *PART, hipStream_t st);
 hipError_t soc_launch_mabu_sum(long long cells, int NFREQ, int NDUST, int idust, const float *EM, const float *ABU, float *SUM, hipStream_t st);
+// `polarisation`: PEM = EM * ipR_f(a_alg) of an equilibrium dust (AALG[cells][2]: a_alg and its log10; APOL[NA], TAB[NFREQ][NA] double),
+// and PSUM = PSUM / (SUM + 1e-32)
+hipError_t soc_launch_mabu_poleq(long long cells, int NFREQ, int NA, const float *EM, const float *AALG, const double *APOL, const double *TAB,
+                                 float *PEM, hipStream_t st);
+hipError_t soc_launch_mabu_ratio(long long cells, int NFREQ, const float *SUM, float *PSUM, hipStream_t st);
 
 // the library method (soc_library.hip).  The reference columns of cell `c` are ABS[c * stride + c0 | c1 | c2].
 struct SocLibSolve {

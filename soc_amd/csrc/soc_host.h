@@ -159,13 +159,18 @@ struct soc_ctx {
     DevBuf<float> aIw, aTdown, aEA, aAF;
     DevBuf<float> aABS, aEMIT;                               // a batch of cells, a2e_NFREQ floats each (soc_a2e_set_size with another NFREQ releases them)
     DevBuf<float> aAll, aSum;                                // soc_a2e_resident_*: absorptions of all cells, emission summed over the sizes
+    DevBuf<float> aPSum, aAalg;                              // polarised output (soc_a2e_resident_begin_pol, soc_mabu_begin_pol): the weighted sum over
+                                                             // the sizes, and a_alg with its log10 per cell ([cells][2])
+    bool    a2e_pol_set = false;                             // soc_a2e_set_size_aalg has given the weights of the current size
+    float   a2e_pol[4] = { 0, 0, 0, 0 };                     // ASIZE[isize], ASIZE[isize+1] or 0, log10(ASIZE[isize]), the difference of the logarithms
     int64_t a2e_cells = 0;                                   // cells resident in aAll and aSum, a2e_res_nfreq floats each: the rows a call may address
     int     a2e_res_nfreq = 0;
     DevBuf<int> aFirst, aLast, aIwOff, aDst, aIbeg;
     // the multi-dust stage (soc_mabu_*): absorptions as the absorbed file holds them, the sum over the dusts, abundances, relative cross
     // sections, temperatures and tables of an equilibrium dust; the current dust's share and its emission are aAll and aSum
     DevBuf<float>  mABS, mSUM, mABU, mT, mTab;
-    DevBuf<double> mRABS;
+    DevBuf<double> mRABS, mPol;                              // (mPol: APOL[NA] and TAB[NFREQ][NA] of soc_mabu_pol_eq)
+    DevBuf<float>  mPSUM;                                    // soc_mabu_begin_pol: the abundance-weighted sum of the polarised emission, then R
     int     mabu_ndust = 0;
     bool    mabu_tables = false;
     // the library method (soc_library_*): the resident table -- I1 | dI1 | I2 | dI2 | X | Y | Z | E0 in one block, the selected emission

@@ -18,8 +18,11 @@ at config 3) and the emission over through files.  Here
   3. the maps are written from that emission array (AbsorptionRun.write_maps: maps.ini of ASOC_driver.py:447-473).
 
 Same ini keys, same dust / solver / abundance / cloud files.  `emitted` is written (it is a product); the
-`absorbed` file only with --keep-files.  The neural-network and library shortcuts (nnmake, nnsolve, libabs ...),
-polarisation (aalg) and cosmic-ray heating are not part of this path and are refused.  With several ranks the
+`absorbed` file only with --keep-files.  `polarisation <dust> <aalg file>` lines (A2E_MABU.py:158-167) go to the same stage 2: the
+polarisation reduction factor R[CELLS, NFREQ] stays in memory, and where the ini asks for `polmap` without `polred` every polarisation
+map is made with the column of its own frequency (the reference writes <emitted>.R and needs one column copied into a `polred` file by
+hand, A2E_MABU.py:1190-1195); with `polred` the file wins; --keep-files writes <emitted>.R as well.  The neural-network and library
+shortcuts (nnmake, nnsolve, libabs ...) and cosmic-ray heating are not part of this path and are refused.  With several ranks the
 first stage shards work items (soc_amd.dist), the second the cells; rank 0 writes.
 """
 import sys
@@ -50,6 +53,8 @@ class Pipeline:
         # dust list as the user wrote it, and the simple dusts the transfer run works with (ASOC_driver.py:240-250)
         self.dusts = list(U.file_optical)
         self.kinds = [dust_kind(d) for d in self.dusts]
+        self.pol = mabu.polarisation_lines(ini, self.dusts)       # per dust its aalg file or None; None without such lines
+        self.R = None
         U.file_optical = [d if k != 'gsetdust' else simple_name(d) for d, k in zip(self.dusts, self.kinds)]
         self.want_maps = not U.NOMAP
         self.want_solve = True
@@ -71,18 +76,25 @@ class Pipeline:
 
     # ---- stage 2 ----------------------------------------------------------------------------------------------
     def solve_emission(self, FABSORBED, ABU):
-        """FABSORBED[CELLS, NFREQ] as the absorbed file holds it (scaled, files.scale_absorbed) -> EMITTED[CELLS, NFREQ]"""
-        em, info = mabu.solve_emission(self.eng, self.dusts, self.kinds, FABSORBED, ABU, self.rank, self.world, log=self.log)
+        """FABSORBED[CELLS, NFREQ] as the absorbed file holds it (scaled, files.scale_absorbed) -> EMITTED[CELLS, NFREQ]; with
+        `polarisation` lines self.R[CELLS, NFREQ] is the polarisation reduction factor"""
+        em, info = mabu.solve_emission(self.eng, self.dusts, self.kinds, FABSORBED, ABU, self.rank, self.world, log=self.log, pol=self.pol)
         self.timers["emission_path"] = info["path"]            # 'device' (soc_mabu_*) or 'host'
+        self.R = info.get("R")
         if not (self.comm and self.world > 1):
             return em
         CELLS, NFREQ = FABSORBED.shape
         c0, c1 = a2e.cell_range(CELLS, self.rank, self.world)
-        EMITTED = np.zeros((CELLS, NFREQ), np.float32)             # every rank solved its cells: put the array together
-        EMITTED[c0:c1] = em
-        for f in range(NFREQ):
-            EMITTED[:, f] = self.comm.all_reduce_host(np.ascontiguousarray(EMITTED[:, f]))
-        return EMITTED
+
+        def whole(part):
+            A = np.zeros((CELLS, NFREQ), np.float32)               # every rank solved its cells: put the array together
+            A[c0:c1] = part
+            for f in range(NFREQ):
+                A[:, f] = self.comm.all_reduce_host(np.ascontiguousarray(A[:, f]))
+            return A
+        if self.R is not None:
+            self.R = whole(self.R)
+        return whole(em)
 
     # ---- the three stages -----------------------------------------------------------------------------------------
     def run(self, keep_files=False):
@@ -107,12 +119,18 @@ class Pipeline:
                 files.write_emitted(U.file_emitted, EMITTED)
             if keep_files and len(U.file_absorbed) > 0:
                 files.write_absorbed(U.file_absorbed, FABSORBED)
+            if keep_files and self.R is not None and len(U.file_emitted) > 0:
+                mabu.write_reduction(U.file_emitted + '.R', self.R)
         t0 = time.time()
         if self.want_maps:
             U.NOMAP = 0
             rt.write_maps(EMITTED)
         if U.POLMAP:                                               # also under `nomap` (ASOC.py:3655)
-            rt.write_polmaps(EMITTED)
+            if self.R is not None and len(getattr(U, "file_polred", "")) > 0:
+                self.log("driver: polmap takes the polarisation reduction factor from the `polred` file %s, not from the `polarisation` lines" % U.file_polred)
+            rt.write_polmaps(EMITTED, R=self.R)
+            if self.R is not None:                                 # (all-sky polarisation maps are a product of this path with R only)
+                rt.write_healpix_polmaps(EMITTED, R=self.R)
         self.timers["maps"] = time.time() - t0
         self.log("@@ driver: transfer %.2f s, emission %.2f s, maps %.2f s" % (self.timers["transfer"], self.timers["emission"], self.timers["maps"]))
         return CTABS, FABSORBED, EMITTED

@@ -132,6 +132,10 @@ API = {
     "soc_a2e_resident_solve": (C.c_int, [C.c_void_p]),
     "soc_a2e_resident_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
     "soc_a2e_resident_end": (C.c_int, [C.c_void_p]),
+    "soc_a2e_resident_begin_pol": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int]),
+    "soc_a2e_resident_upload_aalg": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F, _F]),
+    "soc_a2e_set_size_aalg": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "soc_a2e_resident_download_p": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
     "soc_a2e_eqtemp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                  C.c_float, C.c_float, _F, _F, _F, _F, _F, _F]),
     "soc_eqsolver": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
@@ -145,6 +149,11 @@ API = {
     "soc_mabu_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
     "soc_mabu_read_part": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
     "soc_mabu_end": (C.c_int, [C.c_void_p]),
+    "soc_mabu_begin_pol": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "soc_mabu_pol_eq": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "soc_mabu_accumulate_p": (C.c_int, [C.c_void_p, C.c_int]),
+    "soc_mabu_ratio": (C.c_int, [C.c_void_p]),
+    "soc_mabu_download_p": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
     "soc_library_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, _F, _F, _F, _F, _F, _F, _F, _F, C.c_int, _I]),
     "soc_library_solve": (C.c_int, [C.c_void_p, C.c_int64, _F, _F, _I, C.POINTER(C.c_int64)]),
     "soc_library_solve_resident": (C.c_int, [C.c_void_p, _I, _I, C.POINTER(C.c_int64)]),
@@ -891,9 +900,36 @@ class Engine:
         self._chk(self.lib.soc_a2e_upload(self.h, AABS.shape[0], _f(AABS)))
 
     # the cells resident in device memory: absorptions up once, the sum over the sizes down once (soc_a2e_resident_*)
-    def a2e_resident_begin(self, cells, NFREQ):
-        self._chk(self.lib.soc_a2e_resident_begin(self.h, int(cells), int(NFREQ)))
+    def a2e_resident_begin(self, cells, NFREQ, polarised=False):
+        """polarised: also a second, weighted sum for the polarised emission (a2e_resident_upload_aalg, a2e_set_size_aalg,
+        a2e_resident_download_p)"""
+        if polarised:
+            self._chk(self.lib.soc_a2e_resident_begin_pol(self.h, int(cells), int(NFREQ), 1))
+        else:
+            self._chk(self.lib.soc_a2e_resident_begin(self.h, int(cells), int(NFREQ)))
         self._a2e_res = (int(cells), int(NFREQ))
+
+    def a2e_resident_upload_aalg(self, c0, aalg):
+        """rows [c0, c0 + len(aalg)) of the minimum aligned grain size; its log10 is numpy's float32 one (A2E.py:425)"""
+        aalg = np.ascontiguousarray(aalg, np.float32)
+        if aalg.ndim != 1 or aalg.size < 1:
+            raise SocError("a2e_resident_upload_aalg: one value per cell, an array of shape %s was given" % (aalg.shape,))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lg = np.ascontiguousarray(np.log10(aalg), np.float32)
+        self._chk(self.lib.soc_a2e_resident_upload_aalg(self.h, int(c0), aalg.size, _f(aalg), _f(lg)))
+
+    def a2e_set_size_aalg(self, ASIZE, isize):
+        """the weights of size `isize` of the solver file's ASIZE for the polarised sum, after a2e_set_size (which clears them)"""
+        ASIZE = np.asarray(ASIZE, np.float32)
+        last = isize >= ASIZE.size - 1
+        lg = np.log10(ASIZE[isize])
+        step = np.float32(0.0) if last else np.log10(ASIZE[isize + 1]) - lg
+        self._chk(self.lib.soc_a2e_set_size_aalg(self.h, ASIZE[isize], np.float32(0.0) if last else ASIZE[isize + 1], np.float32(lg), np.float32(step)))
+
+    def a2e_resident_download_p(self, c0, n, out=None):
+        out = np.zeros((int(n), self._a2e_res[1]), np.float32) if out is None else out
+        self._chk(self.lib.soc_a2e_resident_download_p(self.h, int(c0), int(n), _f(out)))
+        return out
 
     def a2e_resident_upload(self, c0, AABS):
         AABS = np.ascontiguousarray(AABS, np.float32)
@@ -942,9 +978,13 @@ class Engine:
         return T, E
 
     # ---- the multi-dust stage with the cells resident in device memory (soc_mabu_*; driven by soc_amd.mabu.solve_emission) ----
-    def mabu_begin(self, cells, NFREQ, NDUST):
+    def mabu_begin(self, cells, NFREQ, NDUST, polarised=False):
+        """polarised: also the arrays of the `polarisation` lines (mabu_pol_eq, mabu_accumulate_p, mabu_ratio, mabu_download_p)"""
         fit = C.c_int64(0)
-        rc = self.lib.soc_mabu_begin(self.h, int(cells), int(NFREQ), int(NDUST), C.byref(fit))
+        if polarised:
+            rc = self.lib.soc_mabu_begin_pol(self.h, int(cells), int(NFREQ), int(NDUST), 1, C.byref(fit))
+        else:
+            rc = self.lib.soc_mabu_begin(self.h, int(cells), int(NFREQ), int(NDUST), C.byref(fit))
         if rc == SOC_ERR_STATE and 0 < fit.value < int(cells):    # with a cell count: not enough device memory
             raise DoesNotFit("%s (code %d)" % (self.lib.soc_last_error(self.h).decode(), rc), fit.value)
         self._chk(rc)
@@ -993,6 +1033,32 @@ class Engine:
                   and out.shape == (int(n), NFREQ)):
             raise SocError("mabu_download: out must be a writeable C-contiguous float32 array of shape (%d, %d)" % (int(n), NFREQ))
         self._chk(self.lib.soc_mabu_download(self.h, int(c0), int(n), _f(out)))
+        return out
+
+    def mabu_pol_eq(self, apol, tab):
+        """PEM = EM * ipR_f(a_alg) of an equilibrium dust: apol[NA] increasing, tab[NFREQ, NA] float64 (mabu.rpol_table)"""
+        NFREQ = self._mabu_open("mabu_pol_eq")[1]
+        apol, tab = np.ascontiguousarray(apol, np.float64), np.ascontiguousarray(tab, np.float64)
+        if apol.ndim != 1 or tab.shape != (NFREQ, apol.size):
+            raise SocError("mabu_pol_eq: apol%s, tab%s for %d frequencies" % (apol.shape, tab.shape, NFREQ))
+        D = C.POINTER(C.c_double)
+        self._chk(self.lib.soc_mabu_pol_eq(self.h, int(apol.size), apol.ctypes.data_as(D), tab.ctypes.data_as(D)))
+
+    def mabu_accumulate_p(self, idust):
+        self._chk(self.lib.soc_mabu_accumulate_p(self.h, int(idust)))
+
+    def mabu_ratio(self):
+        self._chk(self.lib.soc_mabu_ratio(self.h))
+
+    def mabu_download_p(self, c0, n, out=None):
+        """rows [c0, c0 + n) of the polarised sum -- after mabu_ratio, of R; out as in mabu_download"""
+        NFREQ = self._mabu_open("mabu_download_p")[1]
+        if out is None:
+            out = np.zeros((int(n), NFREQ), np.float32)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable
+                  and out.shape == (int(n), NFREQ)):
+            raise SocError("mabu_download_p: out must be a writeable C-contiguous float32 array of shape (%d, %d)" % (int(n), NFREQ))
+        self._chk(self.lib.soc_mabu_download_p(self.h, int(c0), int(n), _f(out)))
         return out
 
     def mabu_read_part(self, c0, n):

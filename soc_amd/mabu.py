@@ -13,6 +13,15 @@ solve_emission is that stage, shared with soc_amd.driver.  With an engine that h
 in device memory from the absorbed file to the sum (the absorptions go up once, the sum comes down once); with any
 other engine the stage runs as numpy around the engine's per-dust solvers.  The two give the same bits.
 
+Ini lines ``polarisation <dust> <aalg file>`` (A2E_MABU.py:158-167; the key is matched by its prefix `polari`) name, for a dust of
+the ini, the file {CELLS} aalg[CELLS] of each cell's minimum aligned grain size.  Such a dust gets a polarised emission beside its
+emission -- a stochastically heated one from the solver (soc_amd.a2e with aalg, A2E_MABU.py:971-984), an equilibrium one from the
+table <dust>.rpol (A2E_MABU.py:615-637) -- these are summed weighted by the abundances like the emission (:1139-1147), and
+<emitted>.R = polarised / (total + 1e-32) is written: {CELLS}, then [CELLS, NFREQ] float32 (:1182, :1188-1198), the polarisation
+reduction factor that `polred` of a map run reads.  The reference compares the dust names with `.dust` stripped in one place and
+unstripped in others (:585, :972, :1111), so that whether a line takes effect depends on how the name is written; here the names
+are compared with `.dust` stripped on both sides.  Without such lines nothing changes and no .R file appears.
+
 With N GPUs (python -m torch.distributed.run --nproc-per-node N -m soc_amd.mabu ...) every rank solves its share of
 the cells and writes its rows of the emitted file.  The reference's optional fourth argument (ofreq.dat: emission on a
 subset of the frequencies) and the library / neural-network shortcuts are refused.
@@ -40,7 +49,7 @@ def refuse(U):
     bad = [k for k in REFUSED_KEYS if k in U.KEYS]
     if bad:
         raise UnsupportedOption("ini options outside the in-memory pipeline (neural-network / library shortcuts, "
-                                "polarisation, cosmic-ray heating): " + ", ".join(bad))
+                                "cosmic-ray heating): " + ", ".join(bad))
 
 
 def dust_kind(name):
@@ -134,6 +143,89 @@ def split_absorbed(ABSORBED, RABS, ABU, idust):
     return (ABSORBED.astype(np.float64) * RABS[None, :, idust] / den.astype(np.float64)).astype(np.float32)
 
 
+# ---- polarisation <dust> <aalg file> ----------------------------------------------------------------------------------
+def strip_dust(name):
+    return name.replace('.dust', '')
+
+
+def polarisation_lines(ini, dusts):
+    """The `polarisation <dust> <aalg file>` lines of the ini (A2E_MABU.py:161-167) as a list along `dusts`: the aalg file of a
+    dust, None for a dust without a line; None where the ini has no such line.  Names are compared with `.dust` stripped on both
+    sides (a later line for the same dust replaces the earlier, as the reference's dict does)."""
+    AALG, where = {}, {}
+    with open(ini) as fp:
+        for line in fp:
+            s = line.split('#')[0].split()
+            if len(s) > 0 and s[0][0:6] == 'polari':
+                if len(s) < 3:
+                    raise ValueError("%s: `%s`: the line must be `polarisation dust_name aalg_file_name`" % (ini, line.strip()))
+                AALG[strip_dust(s[1])] = s[2]
+                where[strip_dust(s[1])] = line.strip()
+    if not AALG:
+        return None
+    known = [strip_dust(d) for d in dusts]
+    for name in AALG:
+        if name not in known:
+            raise ValueError("%s: `%s` names a dust that is not in the ini (its dusts: %s)" % (ini, where[name], ", ".join(dusts)))
+    return [AALG.get(k) for k in known]
+
+
+def rpol_table(dust, FREQ):
+    """<dust>.rpol (first row frequencies, first column sizes: R[a, freq], the share of the cross section in grains larger than a)
+    interpolated to the frequencies FREQ (float32, as SolveEquilibriumDust holds them) as A2E_MABU.py:621-633 does per frequency: the
+    column pick, the weight wj in log frequency -- 0 where the pick is the last column, negative below the first column -- and
+    tmp = (1 - wj) * R[:, i] + wj * R[:, j].  Returns (apol[NA] increasing, tab[NFREQ, NA]) float64; the sizes are sorted as
+    interp1d sorts them."""
+    FREQ = np.asarray(FREQ, np.float32)
+    d = np.loadtxt('%s.rpol' % strip_dust(dust), ndmin=2)
+    Rpol, apol, fpol = d[1:, 1:], d[1:, 0], d[0, 1:]
+    if len(apol) < 2 or len(fpol) < 1:
+        raise ValueError("%s.rpol: at least two sizes and one frequency" % strip_dust(dust))
+    order = np.argsort(apol, kind='mergesort')
+    apol, Rpol = apol[order], Rpol[order]
+    tab = np.zeros((len(FREQ), len(apol)), np.float64)
+    for ifreq in range(len(FREQ)):
+        i = np.argmin(abs(fpol - FREQ[ifreq]))
+        if fpol[i] > FREQ[ifreq]:
+            i = max([i - 1, 0])
+        j = min([i + 1, len(fpol) - 1])
+        if i == j:
+            wj = 0.0
+        else:
+            wj = (np.log(FREQ[ifreq]) - np.log(fpol[i])) / (np.log(fpol[j]) - np.log(fpol[i]))
+        tab[ifreq] = (1.0 - wj) * Rpol[:, i] + wj * Rpol[:, j]
+    return np.ascontiguousarray(apol, np.float64), tab
+
+
+def interp_rpol(apol, y, a):
+    """interp1d(apol, y, bounds_error=False, fill_value=0.0)(a) written out (A2E_MABU.py:635): linear between the nodes --
+    slope = (y1 - y0) / (x1 - x0), slope * (a - x0) + y0 in float64 --, the node's value on a node, 0 outside the nodes"""
+    x = np.asarray(a, np.float64)
+    j = np.clip(np.searchsorted(apol, x, side='right') - 1, 0, len(apol) - 2)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        slope = (y[j + 1] - y[j]) / (apol[j + 1] - apol[j])
+        out = slope * (x - apol[j]) + y[j]
+    out = np.where(x == apol[j], y[j], out)
+    out = np.where(x == apol[-1], y[-1], out)
+    out = np.where((x < apol[0]) | (x > apol[-1]), 0.0, out)
+    return np.where(np.isnan(x), x, out)
+
+
+def polarised_eq(EM, aalg, apol, tab):
+    """PEMITTED[:, f] = EMITTED[:, f] * ipR_f(aalg) (A2E_MABU.py:637): float32 times float64, rounded to float32 once"""
+    PEM = np.zeros(EM.shape, np.float32)
+    with np.errstate(over='ignore', invalid='ignore'):
+        for f in range(EM.shape[1]):
+            PEM[:, f] = EM[:, f] * interp_rpol(apol, tab[f], aalg)
+    return PEM
+
+
+def reduction_factor(PSUM, SUM):
+    """A2E_MABU.py:1182: polarised intensity -> polarisation reduction factor, float32"""
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        return np.asarray(PSUM / (SUM + 1.0e-32), np.float32)
+
+
 def abundance_table(ABU, single, CELLS, NDUST):
     """ABU[CELLS, NDUST] float32 from what files.read_abundances gave (None: no abundance file; with `singleabu` the first
     column x and 1-x for the two dusts, ASOC.py:1148-1153): ones where no file is given"""
@@ -162,17 +254,19 @@ def _tables(dusts, kinds, NFREQ):
     return out
 
 
-def offers_device_path(engine, kinds, tables):
-    """THE probe of the stage: the engine has the soc_mabu_* calls, and every size of every solver file is solved
-    stochastically (a size without its tables goes through a2e.run's equilibrium branch, which works on host arrays)"""
-    return hasattr(engine, "mabu_begin") and \
+def offers_device_path(engine, kinds, tables, polarised=False):
+    """THE probe of the stage: the engine has the soc_mabu_* calls (with `polarisation` lines those too), and every size of every
+    solver file is solved stochastically (a size without its tables goes through a2e.run's equilibrium branch, which works on host arrays)"""
+    return hasattr(engine, "mabu_begin") and (not polarised or hasattr(engine, "mabu_pol_eq")) and \
         all(k == 'eqdust' or len(t["sizes"]) >= t["NSIZE"] for k, t in zip(kinds, tables))
 
 
-def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, log):
+def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, log, AALG=None, ptabs=None, PEM=None):
     n, NFREQ = FABS.shape
     for idust in range(len(dusts)):
         t0 = time.time()
+        aalg = AALG[idust] if AALG else None
+        pem = None
         part = split_absorbed(FABS, RABS, ABU, idust)
         if kinds[idust] == 'eqdust':
             Fq, KABS, Emin, kE, oplgkE, TTT = tables[idust]
@@ -181,24 +275,40 @@ def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, lo
             for a in range(0, n, B):
                 b = min(a + B, n)
                 _, em[a:b] = engine.eqsolver(c0 + a, CELLS, NE_EQ, FACTOR, kE, oplgkE, Emin, Fq, KABS, TTT, part[a:b])
+            if aalg is not None:
+                pem = polarised_eq(em, aalg, *ptabs[idust])    # A2E_MABU.py:615-637
+        elif aalg is not None:
+            em, pem, _ = a2e.run(engine, tables[idust], part, verbose=False, aalg=aalg)      # A2E_MABU.py:971-984
         else:
             em, _ = a2e.run(engine, tables[idust], part, verbose=False)
         EM += em * ABU[:, idust:idust + 1]                     # A2E_MABU.py:1128-1140
+        if pem is not None:
+            PEM += pem * ABU[:, idust:idust + 1]               # A2E_MABU.py:1139-1147
         log("  dust %d/%d %-24s %s  %.2f s" % (idust + 1, len(dusts), dusts[idust], kinds[idust], time.time() - t0))
     return 1
 
 
-def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells, log):
-    """the cells in ranges that fit the device (one range where all do): cells are independent, so this is a loop"""
+def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells, log, AALG=None, ptabs=None, R=None):
+    """the cells in ranges that fit the device (one range where all do): cells are independent, so this is a loop.  With AALG (per
+    dust the minimum aligned sizes of these cells, or None) the two more resident arrays of the polarised emission are asked for,
+    the rows of a dust's aalg follow the cell range, and R receives polarised / total."""
     n, NFREQ = FABS.shape
     NDUST = len(dusts)
+
+    def upload_aalg(aalg, a, b):
+        for i in range(a, b, CHUNK):
+            engine.a2e_resident_upload_aalg(i - a, aalg[i:min(i + CHUNK, b)])
+
     step = n if not range_cells else max(1, min(n, int(range_cells)))
     a = ranges = 0
     while a < n:
         b = min(a + step, n)
         t0 = time.time()
         try:
-            engine.mabu_begin(b - a, NFREQ, NDUST)
+            if AALG:
+                engine.mabu_begin(b - a, NFREQ, NDUST, polarised=True)
+            else:
+                engine.mabu_begin(b - a, NFREQ, NDUST)
         except DoesNotFit as err:
             step = err.cells_fit
             log("  %s" % err)
@@ -208,20 +318,34 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
                 engine.mabu_upload(i - a, FABS[i:min(i + CHUNK, b)])
             engine.mabu_set_tables(ABU[a:b], RABS)
             for idust in range(NDUST):
+                aalg = AALG[idust] if AALG else None
                 if kinds[idust] == 'eqdust':
                     Fq, KABS, Emin, kE, oplgkE, TTT = tables[idust]
                     engine.mabu_split(idust)
                     engine.mabu_solve_eq(NE_EQ, FACTOR, kE, oplgkE, Emin, Fq, KABS, TTT)
+                    if aalg is not None:                                           # A2E_MABU.py:615-637
+                        upload_aalg(aalg, a, b)
+                        engine.mabu_pol_eq(*ptabs[idust])
                 else:
                     sol = tables[idust]
                     engine.mabu_split(idust, clip_last=True)                       # A2E.py:184-185
+                    if aalg is not None:
+                        upload_aalg(aalg, a, b)
                     for isize in range(sol["NSIZE"]):                              # the sum over the sizes: A2E.py:596-600
                         engine.a2e_set_size(sol["NE"], NFREQ, sol["sizes"][isize], a2e_absorption_fraction(sol, isize))
+                        if aalg is not None:
+                            engine.a2e_set_size_aalg(sol["SIZE_A"], isize)         # A2E.py:413-429, in the kernel's epilogue
                         engine.a2e_resident_solve()
                 engine.mabu_accumulate(idust)
+                if aalg is not None:
+                    engine.mabu_accumulate_p(idust)                                # A2E_MABU.py:1139-1147
+            if AALG:
+                engine.mabu_ratio()                                                # A2E_MABU.py:1182
             for i in range(a, b, CHUNK):
                 m = min(i + CHUNK, b) - i
                 engine.mabu_download(i - a, m, out=EM[i:i + m])
+                if AALG:
+                    engine.mabu_download_p(i - a, m, out=R[i:i + m])
         finally:
             engine.mabu_end()
         ranges += 1
@@ -230,30 +354,41 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
     return ranges
 
 
-def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, path=None, range_cells=None, log=None):
+def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, path=None, range_cells=None, log=None, pol=None):
     """Stage 2 of a multi-dust run for the cells a2e.cell_range(CELLS, rank, world) of this rank.  FABSORBED[CELLS, NFREQ] as the
     absorbed file holds it (scaled, files.scale_absorbed; a memory map will do), ABU[CELLS, NDUST] float32.
     Returns (EM[c1 - c0, NFREQ], info) with info["path"] 'device' or 'host' and info["ranges"], the number of cell ranges.
     path: None = the device path where the engine offers it, or 'device' / 'host' to insist (tests, measurements);
-    range_cells: an upper limit for the cells resident at a time (default: what the free device memory takes)."""
+    range_cells: an upper limit for the cells resident at a time (default: what the free device memory takes);
+    pol: polarisation_lines' list -- per dust its aalg file or None; info["R"] is then R[c1 - c0, NFREQ], polarised / total."""
     log = log or (lambda *a: None)
     CELLS, NFREQ = FABSORBED.shape
     RABS, FREQ = relative_cross_sections(dusts, kinds)
     if RABS.shape[0] != NFREQ:
         raise ValueError("the dusts have %d frequencies, the absorptions %d" % (RABS.shape[0], NFREQ))
     tables = _tables(dusts, kinds, NFREQ)
-    offered = offers_device_path(engine, kinds, tables)
+    c0, c1 = a2e.cell_range(CELLS, rank, world)
+    AALG = ptabs = None
+    if pol is not None and any(p is not None for p in pol):
+        AALG = [None if p is None else a2e.read_aalg(p, CELLS)[c0:c1] for p in pol]
+        ptabs = [rpol_table(d, t[0]) if (p is not None and k == 'eqdust') else None for d, k, t, p in zip(dusts, kinds, tables, pol)]
+    offered = offers_device_path(engine, kinds, tables, AALG is not None)
     if path not in (None, 'device', 'host') or (path == 'device' and not offered):
         raise ValueError("solve_emission: path %r is not available with this engine and these solver files" % (path,))
     device = offered if path is None else path == 'device'
-    c0, c1 = a2e.cell_range(CELLS, rank, world)
     EM = np.zeros((c1 - c0, NFREQ), np.float32)
+    R = np.zeros((c1 - c0, NFREQ), np.float32) if AALG else None
     ranges = 0
     if c1 > c0 and device:
-        ranges = _solve_device(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, EM, range_cells, log)
+        ranges = _solve_device(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, EM, range_cells, log, AALG, ptabs, R)
     elif c1 > c0:
-        ranges = _solve_host(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, c0, CELLS, EM, log)
-    return EM, dict(path='device' if device else 'host', ranges=ranges)
+        ranges = _solve_host(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, c0, CELLS, EM, log, AALG, ptabs, R)
+        if AALG:
+            R[:] = reduction_factor(R, EM)                         # (R held the sum of the polarised emission)
+    info = dict(path='device' if device else 'host', ranges=ranges)
+    if AALG:
+        info["R"] = R
+    return EM, info
 
 
 # ---- the program ----------------------------------------------------------------------------------------------------
@@ -270,6 +405,7 @@ def run(ini, absorbed, emitted, engine, comm=None, ofreq=None, verbose=False, **
     dusts = list(U.file_optical)
     if len(dusts) < 1:
         raise ValueError("%s names no dust (keyword optical)" % ini)
+    pol = polarisation_lines(ini, dusts)
     kinds = [dust_kind(d) for d in dusts]
     require_solvers(dusts, kinds)
     dims = np.fromfile(absorbed, np.int32, 2)
@@ -278,21 +414,35 @@ def run(ini, absorbed, emitted, engine, comm=None, ofreq=None, verbose=False, **
     ABU = abundance_table(files.read_abundances(U.file_abundance, CELLS), U.SINGLE_ABU, CELLS, len(dusts))
     log = print if (verbose and rank == 0) else None
     if world == 1:
-        EM, info = solve_emission(engine, dusts, kinds, FABS, ABU, log=log, **stage)
+        EM, info = solve_emission(engine, dusts, kinds, FABS, ABU, log=log, pol=pol, **stage)
         files.write_emitted(emitted, EM)
+        if pol is not None:
+            write_reduction(emitted + '.R', info.pop("R"))
         return info
     if rank == 0:
         files.create_absorbed(emitted, CELLS, NFREQ)            # (the emitted file has the layout of the absorbed file)
+        if pol is not None:
+            with open(emitted + '.R', 'wb') as fp:
+                np.asarray([CELLS], np.int32).tofile(fp)
+                fp.truncate(4 + 4 * CELLS * NFREQ)
     comm.barrier()
-    EM, info = solve_emission(engine, dusts, kinds, FABS, ABU, rank, world, log=log, **stage)
+    EM, info = solve_emission(engine, dusts, kinds, FABS, ABU, rank, world, log=log, pol=pol, **stage)
     c0, c1 = a2e.cell_range(CELLS, rank, world)
     if c1 > c0:
-        out = np.memmap(emitted, dtype=np.float32, mode='r+', offset=8, shape=(CELLS, NFREQ))
-        out[c0:c1, :] = EM
-        out.flush()
-        del out
+        for name, offset, rows in [(emitted, 8, EM)] + ([(emitted + '.R', 4, info.pop("R"))] if pol is not None else []):
+            out = np.memmap(name, dtype=np.float32, mode='r+', offset=offset, shape=(CELLS, NFREQ))
+            out[c0:c1, :] = rows
+            out.flush()
+            del out
     comm.barrier()
     return info
+
+
+def write_reduction(filename, R):
+    """<emitted>.R (A2E_MABU.py:1188-1198): the header is {CELLS} alone (the layout of a `polred` file), then R[CELLS, NFREQ] float32"""
+    with open(filename, 'wb') as fp:
+        np.asarray([R.shape[0]], np.int32).tofile(fp)
+        np.asarray(R, np.float32).tofile(fp)
 
 
 def main(argv=None):
