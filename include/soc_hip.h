@@ -94,7 +94,11 @@ int soc_set_exec(soc_ctx *ctx, int mode, int brick_log2);
  * <= 36864; rays on single-level grids: bricks of the largest cube within), "tail_lanes", "park_below" (hierarchies: brick queues shorter than this and than the mean wait a pass; 1 = never), "population" (packets in flight), "hash_slots" (per-workgroup
  * arrival table, power of two), "general_kernel" (1: no background-only kernel), "global_tree" (1: hierarchies are walked in
  * global memory also where the brick-local form applies), "slow_every" (test knob of that form),
- * "oversubscribe", "verbose". */
+ * "oversubscribe", "verbose", "abu_local" (1: launches with per-cell opacities -- soc_set_opt, soc_set_optical_abu -- take the
+ * brick-local form of a hierarchy that has one too, the opacities of a brick's cells in LDS; 0, the built-in choice: they are routed as
+ * without the key, through the sweep that reads the hierarchy and OPT from global memory.  Not with with_int 2 or soc_set_ali, which
+ * keep today's paths.  Launches deferred between two soc_set_opt / soc_set_optical_abu calls then share one copy of the opacities,
+ * and a batch holds at most 16 such copies). */
 int soc_set_tuning(soc_ctx *ctx, const char *name, int value);
 
 /* replaces the per-frequency uploads of ABS, SCA (ASOC.py:1171-1175); ndust must be 1

@@ -16,6 +16,7 @@ ahead-of-time compiled library (no per-run kernel build), and with several ranks
 launch is split by logical work-item id with one all-reduce of the tallies
 (soc_amd/dist.py).
 """
+import functools
 import sys
 import time
 
@@ -149,6 +150,22 @@ def _check_supported(USER, NDUST, WITH_MSF, engine=None):
     # the block that would use them with ALI, ASOC.py:2062-2071, is switched off there -- so it has none here)
     if bad:
         raise UnsupportedOption("ini options not supported by this engine: " + ", ".join(bad))
+
+
+def _abu_local(method):
+    """A transfer stage of AbsorptionRun: with an abundance file the engine's `abu_local` routing is on while it runs (see
+    AbsorptionRun.ABU_LOCAL), and the engine has its built-in routing back afterwards."""
+    @functools.wraps(method)
+    def stage(self, *a, **kw):
+        on = self.WITH_ABU and self.ABU_LOCAL
+        if on:
+            self._tune(abu_local=1)
+        try:
+            return method(self, *a, **kw)
+        finally:
+            if on:
+                self._tune(abu_local=0)
+    return stage
 
 
 class AbsorptionRun:
@@ -293,6 +310,22 @@ class AbsorptionRun:
             e.set_abundances(self.ABU, single=bool(U.SINGLE_ABU))
         if self.comm:
             self.comm.attach(e, c.CELLS)
+
+    def _tune(self, **kw):
+        """Engine.set_tuning, where the engine has sweeps to shape (the oracle's stand-in has one path)"""
+        tune = getattr(self.eng, "set_tuning", None)
+        if tune is not None:
+            tune(**kw)
+
+    def _log_form(self, name):
+        """verbosity >= 1: what the segment's last sweep ran as (Engine.last_form / last_variant)"""
+        form = getattr(self.eng, "last_form", None)
+        if form is None or not (self.verbose and self.rank == 0):
+            return
+        f = form()
+        v = self.eng.last_variant() if f else None
+        names = ("direct kernels", "Cartesian brick sweep", "sweep of the hierarchy in global memory", "brick-local sweep")
+        print("      %s: last launches ran as form %d (%s)%s" % (name, f, names[f], ", per-cell opacities" if (v and v.get("abu")) else ""))
 
     def _optical_for(self, IFREQ):
         """scalar ABS,SCA summed over species, or OPT[CELLS,2] with abundances (ASOC.py:1146-1175)"""
@@ -466,6 +499,13 @@ class AbsorptionRun:
     # length, not longer ones; the default stays 1.
     FREQS_PER_SWEEP = 1
 
+    # Runs with an abundance file (per-cell opacities): the engine's tuning key `abu_local`, which takes their launches to the brick-local
+    # walk of a hierarchy that has one (the opacities of a brick's cells in LDS) instead of the sweep that reads the hierarchy and OPT
+    # from global memory.  Measured on config 3 with two species of variable abundance, 9 launches in one sweep (tools/exp_abu.py,
+    # profiles/abu_local_lines.json): 9.67e9 cell steps/s against 6.58e9, 1.47x with a spread of 0.14 % over the repeats, equal event
+    # counts -- so the key is on.  with_int 2 and ALI are not part of that walk; the engine routes them as before either way.
+    ABU_LOCAL = True
+
     def _sends(self, II, IFREQ):
         """False where _launch sends nothing: no DIFFUSERAD column for the frequency, an empty Healpix sky (files.hpbg_for_frequency)"""
         if II == 2:
@@ -519,6 +559,7 @@ class AbsorptionRun:
         return [(self.LAUNCH_GROUPS if (absorbed and c.LEVELS == 1 and U.SAVE_INTENSITY == 0 and not U.WITH_ROI_SAVE and II != 3)
                  else self.SEQUENTIAL, ['PS', 'BG', 'DE', 'ROI'][II], [step(f, [(II, L)]) for f in freqs]) for II, L in blocks], owner
 
+    @_abu_local
     def simulate_constant_sources(self):
         """for II in (point sources, background, diffuse): for IFREQ: launch (ASOC.py:1028-1545), in the order and batches of _plan.
         Returns CTABS[CELLS] and FABSORBED[CELLS,NFREQ] (or None with noabsorbed)."""
@@ -618,6 +659,7 @@ class AbsorptionRun:
                 e.batch_end()
                 e.sync()
                 self.timers["Tkernel"] += time.time() - t0
+            self._log_form(name)
             if self.comm:
                 self.comm.all_reduce_tally(e, 0)              # TABS: integrated over frequency (and the segment's blocks) on the device
             t0 = time.time()
@@ -652,6 +694,7 @@ class AbsorptionRun:
         self.timers["Tpull"] += time.time() - t0
 
     # ---------------------------------------------------------------------------------
+    @_abu_local
     def emission_iterations(self, CTABS, FABSORBED):
         """Simulation <-> temperature cycles (ASOC.py:1593-2260, the paths without reference field and
         ALI): per iteration the dust emission of the previous one is simulated with SimRAM_CL

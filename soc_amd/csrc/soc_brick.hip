@@ -148,6 +148,10 @@ struct SocBrickArgs {
     // scattered-light images on brick-local hierarchies (soc_sca_events): the view, and the parked packet of every work item
     SocPk2 *park;
     SocSca sca;
+    // per-cell opacities on brick-local hierarchies (the ABU arm of soc_lbrick_walk): the OPT array of every group of launches in
+    // brick-slot order (soc_lbrick_opt), group g at kopt + g * kopt_stride
+    const float2 *kopt;
+    long long kopt_stride;
 };
 
 #include "soc_octbricks.h"     // SOC_SLOT_BITS, SocOctBuilder
@@ -658,7 +662,13 @@ __device__ __forceinline__ int soc_cell_index(const SocGrid &G, int level, int c
 // CART (RAY only): a single-level grid (bricks of soc_cbricks_build: boxes of root cells, their densities in LDS).  Index() is then
 // a floor and a bounds test (kernel_ASOC_aux.c:216-221): no soc_lt_aim / soc_lt_land, no level, no octet -- the new slot follows from
 // the root cell the step ended in, and a ray whose step ends in a root cell outside the brick's box leaves for that cell's brick.
-template <int WINT, bool RAY = false, bool ALI = false, bool LIM = false, bool CART = false>
+// ABU: per-cell opacities (-D WITH_ABU, kernel_ASOC.c:573-574).  kabs and ksca belong to the cell, not to the launch: the opacities of the
+// brick's cells sit in LDS for the whole visit (sK, a float2 per slot: 8 B per cell more), copied in the prologue from the OPT array of the
+// workgroup's group of launches in brick-slot order (soc_lbrick_opt).  A lane reads its cell's pair with one ds_read_b64 at the head of
+// GetStep -- by then the slot is the one the landing, the arrival or the placement gave it together with the density, and the pair is
+// not needed before tauA, a fract and three divisions later -- so no global load enters the step arm and one read site serves every way
+// a lane comes by a cell.  WINT 0, 1 and 3 only; the event workgroups read OPT of the queue's launch in global memory as they always did.
+template <int WINT, bool RAY = false, bool ALI = false, bool LIM = false, bool CART = false, bool ABU = false>
 __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPack &K, const SocBrickArgs &A, const int bid)
 {
     if (bid >= *A.ndesc) return;
@@ -679,7 +689,8 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
     int   *sC   = (int *)(sX + (ALI ? BV : 0));            // [BV] global number of the cell in every slot (ALI)
     float *sD   = (float *)(sC + (ALI ? BV : 0));          // [BV] density | link of every cell of the brick (RAY: nothing else)
     const int NQ = A.NBQ + A.EQ * A.nl + 1;
-    int   *sH   = (int *)(sD + BV);                        // arrivals per queue, next pass
+    const float2 *sK = (const float2 *)(sD + BV);          // [BV] (kabs, ksca) of every cell of the brick (ABU)
+    int   *sH   = (int *)(sD + BV + (ABU ? 2 * BV : 0));   // arrivals per queue, next pass
     int   *sCtl = sH + (A.HS ? 2 * A.HS : ((NQ + 3) & ~3));   // [0] next packet, [1] tally events
     float *sL   = (float *)(sCtl + 4);                     // [4 * MAXLAUNCH] ABS, SCA, TW, flags (bit 0: SimRAM_CL) of every launch
     const SocSim &S = K.S[0];
@@ -701,6 +712,11 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
             sD[i] = src[i];  if (!RAY && WINT != 3) sT[i] = 0.0f;  if (WINT) sI[i] = 0.0f;
             if (WINT == 2) { sV[i] = 0.0f;  sV[BV + i] = 0.0f;  sV[2 * BV + i] = 0.0f; }
             if (ALI) { sX[i] = 0.0f;  sC[i] = A.bcell[KB.base + i]; }
+        }
+        if (ABU) {                                         // the opacities of this queue's group of launches, in slot order (entries of refined cells are never used)
+            const float2 *ksrc = A.kopt + (long long)(qbase / A.NB) * A.kopt_stride + KB.base;
+            float2 *dst = (float2 *)(sD + BV);
+            for (int i = threadIdx.x; i < KB.nslot; i += nthr) dst[i] = ksrc[i];
         }
     }
     soc_qh_init(sH, A.HS, NQ);
@@ -868,6 +884,7 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
             float tauA = 0.0f, dtau = 0.0f;
             // ---- one cell step (kernel_ASOC.c:565-683): GetStep ----
             if (what == SOC_LTM_STEP) {
+                if (ABU) { const float2 o = sK[slot];  kabs = o.x;  ksca = o.y; }      // the cell's opacities: asked for here, used at tauA
                 const float p0x = px, p0y = py, p0z = pz;
                 float fx, fy, fz;
                 if (__ballot(__builtin_fminf(px, __builtin_fminf(py, pz)) < 0.0f) == 0ull) {
@@ -1458,6 +1475,29 @@ __global__ __launch_bounds__(1024) void soc_lbrick_pass_ali(const SocGrid G, con
     }
 }
 
+// per-cell opacities (-D WITH_ABU): the ABU arm of the walk; the kind of a launch is the launch's (KIND 4)
+template <int WINT>
+__global__ __launch_bounds__(1024) void soc_lbrick_pass_abu(const SocGrid G, const SocSimPack *Kp, const SocBrickArgs A, const int nwalk, const int slices)
+{
+    const SocSimPack &K = *Kp;
+    const int b = (int)blockIdx.x;
+    if (b < nwalk) {
+        soc_lbrick_walk<WINT, false, false, false, false, true>(G, K, A, b);
+    } else {
+        const int e = b - nwalk;
+        soc_brick_events<true, true, WINT, 4, true>(G, K, A, e / slices, e % slices);
+    }
+}
+
+// OPT of every group of launches -> brick-slot order (slot -> cell: bcell, the table the ALI form uses), once per sweep: the prologue of
+// soc_lbrick_walk<., ABU> then copies a brick's opacities as it copies its cells, nslot contiguous entries from the brick's base
+__global__ __launch_bounds__(256) void soc_lbrick_opt(const SocSimPack *Kp, const int *bcell, long long nslots, float2 *kopt)
+{
+    const SocSim &S = Kp->S[Kp->gfirst[blockIdx.y]];
+    float2 *dst = kopt + (long long)blockIdx.y * nslots;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += (long long)gridDim.x * blockDim.x) dst[i] = S.OPT[bcell[i]];
+}
+
 // ---------------------------------------------------------------------------------------
 // Scattered-light images (kernel_ASOC_sca.c) on brick-local hierarchies.
 //
@@ -2011,8 +2051,9 @@ __global__ __launch_bounds__(SOC_BRICK_T) void soc_brick_scatter(SocBrickArgs A,
 // ---------------------------------------------------------------------------------------
 
 struct SocBrickBuffers {
-    size_t cap_items = 0, cap_nq = 0, cap_desc = 0, cap_park = 0;
+    size_t cap_items = 0, cap_nq = 0, cap_desc = 0, cap_park = 0, cap_kopt = 0;
     SocPk2 *pk = nullptr, *park = nullptr;
+    float2 *kopt = nullptr;                                // per-cell opacities in brick-slot order, one array per group of launches
     uint32_t *idq[2] = { nullptr, nullptr }, *keyq = nullptr, *posq = nullptr;
     SocSimPack *pack = nullptr;
     int *hist = nullptr, *off = nullptr, *ndesc = nullptr, *total = nullptr, *admit = nullptr;
@@ -2051,7 +2092,7 @@ void soc_brick_release(int device)
 {
     if (device < 0 || device >= 16) return;
     SocBrickBuffers &b = g_bb[device];
-    void *ptrs[] = { b.pack, b.pk, b.park, b.idq[0], b.idq[1], b.keyq, b.posq, b.hist, b.off, b.ndesc, b.total, b.admit, b.desc[0], b.desc[1] };
+    void *ptrs[] = { b.pack, b.pk, b.park, b.kopt, b.idq[0], b.idq[1], b.keyq, b.posq, b.hist, b.off, b.ndesc, b.total, b.admit, b.desc[0], b.desc[1] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     b = SocBrickBuffers();
     soc_oct_release(device);
@@ -2082,7 +2123,7 @@ static SocOctBricks g_ob[16];
 struct SocLBricksDev {
     bool valid = false, failed = false;
     int  NB = 0, cap = 0, max_slots = 0;
-    size_t cells = 0;
+    size_t cells = 0, slots = 0;               // slots: entries of btree and bcell
     const float *dens_key = nullptr;
     SocLBrick *lbr = nullptr;
     float *btree = nullptr;
@@ -2178,7 +2219,7 @@ static hipError_t soc_lb_build(int device, const SocGrid &G, int cap, hipStream_
     BCHK(hipMemcpy(lb.bcell, H.bcell.data(), H.bcell.size() * 4, hipMemcpyHostToDevice));
     BCHK(hipMemcpy(lb.bbase, bbase.data(), bbase.size() * 4, hipMemcpyHostToDevice));
     BCHK(hipMemcpy(lb.rbrick, H.rbrick.data(), H.rbrick.size() * 4, hipMemcpyHostToDevice));
-    lb.NB = NB;  lb.max_slots = H.max_slots;
+    lb.NB = NB;  lb.max_slots = H.max_slots;  lb.slots = H.btree.size();
     lb.valid = true;
     if (verbose)
         fprintf(stderr, "soc_brick: %s of %d cells -> %d brick-local hierarchies of <= %d cells (largest %d, mean %.0f)\n",
@@ -2214,6 +2255,8 @@ static const SocPassFn soc_lbrick_pass_fns[4][5] = {
     { soc_lbrick_pass<2, 0>, soc_lbrick_pass<2, 1>, soc_lbrick_pass<2, 2>, soc_lbrick_pass<2, 3>, soc_lbrick_pass<2, 4> },
     { soc_lbrick_pass<3, 0>, soc_lbrick_pass<3, 1>, soc_lbrick_pass<3, 2>, soc_lbrick_pass<3, 3>, soc_lbrick_pass<3, 4> } };
 static const SocPassFn soc_lbrick_pass_ali_fns[2] = { soc_lbrick_pass_ali<0>, soc_lbrick_pass_ali<1> };
+// ... with per-cell opacities: [WINT 0, 1, 3] (plan_sweep keeps with_int 2 and ALI with abundances off this form)
+static const SocPassFn soc_lbrick_pass_abu_fns[4] = { soc_lbrick_pass_abu<0>, soc_lbrick_pass_abu<1>, nullptr, soc_lbrick_pass_abu<3> };
 // rays: [single-level grid][Healpix image seen from a position][SimRAM_HP launches]
 static const SocPassFn soc_lray_pass_fns[2][2][2] = { { { soc_lray_pass<0, 0, 0>, soc_lray_pass<0, 1, 0> }, { soc_lray_pass<1, 0, 0>, soc_lray_pass<1, 1, 0> } },
                                                       { { soc_lray_pass<0, 0, 1>, soc_lray_pass<0, 1, 1> }, { soc_lray_pass<1, 0, 1>, soc_lray_pass<1, 1, 1> } } };
@@ -2221,6 +2264,7 @@ static const SocPassFn soc_lray_pass_fns[2][2][2] = { { { soc_lray_pass<0, 0, 0>
 static SocPassFn pass_kernel(const SocSweepPlan &pl)
 {
     if (pl.rays)      return soc_lray_pass_fns[pl.octree ? 0 : 1][pl.hpx][pl.hpsky];
+    if (pl.form == 3 && pl.abu) return soc_lbrick_pass_abu_fns[pl.wint];
     if (pl.form == 3) return pl.ali ? soc_lbrick_pass_ali_fns[pl.wint] : soc_lbrick_pass_fns[pl.wint][pl.kind];
     return soc_brick_pass_fns[pl.octree + pl.dbl][pl.abu][pl.wint][pl.kind];
 }
@@ -2248,7 +2292,11 @@ static hipError_t plan_sweep(SocSweepPlan &pl, const SocGrid &G, const SocSim *S
 {
     // rays on a single-level grid: the brick-local form with bricks of root cells (absorption launches there keep form 1)
     const bool cart = lb_ok && sca && soc_brick_cart(G, V);
-    const bool lt = cart || (lb_ok && soc_brick_local(G, V, tune));
+    // (per-cell opacities: soc_brick_local asks for soc_set_tuning("abu_local", 1) and refuses with_int 2; a launch with the XAB tally
+    // of WITH_ALI keeps the sweep that reads the hierarchy from global memory -- the abundance kernels have no ALI arm)
+    bool xab = false;
+    for (int l = 0; l < nlaunch; l++) xab = xab || (S[l].XAB != nullptr);
+    const bool lt = cart || (lb_ok && soc_brick_local(G, V, tune) && !(V.abu && xab));
     pl = soc_grid_plan(lt ? 3 : V.octree ? 2 : 1, 0, V);
     pl.rays = sca != nullptr;
     pl.hpx = sca && sca->NDIR < 0;
@@ -2298,8 +2346,12 @@ static hipError_t plan_sweep(SocSweepPlan &pl, const SocGrid &G, const SocSim *S
     // (the vector sums of SAVE_INTENSITY 2: 24 B per cell)
     // (ALI: 8 B per cell more for XAB and the cell numbers)
     // (rays on a single-level grid: the cube of soc_cart_default_edge, 16 or 24 cells)
+    // (per-cell opacities: 8 B per cell more for the cell's (kabs, ksca) -- 16 B, the ALI figure, or 20 B with TABS and INT side by side.
+    //  soc_lb_build keeps the bricks of ONE cap: a process that alternates sweeps with scalar and with per-cell opacities on one grid
+    //  rebuilds the brick tables at every change -- on the host, a few seconds on a 5e7-cell model)
     const int cedge = soc_cart_default_edge(G);
-    pl.capl = (tune.CAP > 0) ? tune.CAP : cart ? cedge * cedge * cedge : (sca ? 17408 : (ali ? (V.wint ? 3456 : 4352) : (V.wint == 2 ? 2944 : (V.wint && !int_only) ? 5888 : 8704)));
+    const int cap_abu = (V.wint && !int_only) ? 3456 : 4352;
+    pl.capl = (tune.CAP > 0) ? tune.CAP : cart ? cedge * cedge * cedge : (sca ? 17408 : V.abu ? cap_abu : (ali ? (V.wint ? 3456 : 4352) : (V.wint == 2 ? 2944 : (V.wint && !int_only) ? 5888 : 8704)));
     if (pl.capl < 8 || pl.capl > 36864) return hipErrorInvalidValue;
     pl.EQ = 3;
     for (int l = 0; l < nlaunch; l++) pl.roi = pl.roi || (S[l].ROISAVE && S[l].ROI);
@@ -2336,6 +2388,7 @@ static hipError_t build_bricks(SocBrickArgs &A, const SocSweepPlan &pl, int devi
         A.NB = lb.NB;
         A.CAP = (lb.max_slots + 63) & ~63;                               // slots in LDS
         A.lbr = lb.lbr;  A.btree = lb.btree;  A.bcell = lb.bcell;  A.bbase = lb.bbase;  A.rbrick = lb.rbrick;
+        A.kopt_stride = pl.abu ? (long long)lb.slots : 0;
         return hipSuccess;
     }
     if (G.LEVELS > 15) return hipErrorNotSupported;                      // the level shares a packet word with slot and launch
@@ -2389,22 +2442,24 @@ static hipError_t pack_launches(SocSimPack &K, SocSweepSize &sz, SocBrickArgs &A
         K.n++;
     }
     for (int l = K.n; l <= SOC_MAXLAUNCH; l++) K.first[l] = count;
-    // several launches with per-cell opacities: their OPT arrays are slots of one buffer (soc_capi.hip)
-    if (pl.abu && K.n > 1) {
+    // several launches with per-cell opacities: their OPT arrays are slots of one buffer (soc_capi.hip), which the Cartesian sweep and
+    // the one of a hierarchy in global memory stride through; the brick-local form takes every group's array by its pointer
+    if (pl.abu && pl.form != 3 && K.n > 1) {
         A.opt_stride = (long long)(K.S[1].OPT - K.S[0].OPT);
         for (int l = 1; l < K.n; l++)
             if ((long long)(K.S[l].OPT - K.S[0].OPT) != l * A.opt_stride) return hipErrorInvalidValue;
     }
     // launches with the INT tally: brick queues per group, so that a workgroup's LDS tallies belong to one INT array
     // (launches that tally into ONE INT array -- the source blocks of one frequency, soc_batch_begin_shared_int -- share the queues)
+    // (per-cell opacities on brick-local hierarchies: a workgroup's LDS holds the opacities of ONE OPT array too -- the group is the pair (INT, OPT))
+    const bool by_int = pl.wint != 0, by_opt = pl.abu && pl.form == 3;
     int ngrp = 0;
     for (int l = 0; l < K.n; l++) {
         int g = 0;
-        while (g < ngrp && K.S[K.gfirst[g]].INT != K.S[l].INT) g++;
+        while (g < ngrp && ((by_int && K.S[K.gfirst[g]].INT != K.S[l].INT) || (by_opt && K.S[K.gfirst[g]].OPT != K.S[l].OPT))) g++;
         if (g == ngrp) K.gfirst[ngrp++] = l;
         K.grp[l] = g;
     }
-    if (!pl.wint) { ngrp = 1;  for (int l = 0; l < K.n; l++) K.grp[l] = 0; }
     A.NBQ = (ngrp > 1) ? A.NB * ngrp : A.NB;
     if ((long long)A.NB * ngrp > (1 << 20)) return hipErrorNotSupported;
     A.nl = K.n;
@@ -2434,7 +2489,7 @@ static hipError_t plan_kernel(SocSweepPlan &pl, SocBrickArgs &A, SocSweepSize &s
     // the arrivals table, the launches' counters
     const int BV = (pl.octree || pl.form == 3) ? A.CAP : (1 << (3 * A.LB));
     const int nh = A.HS ? 2 * A.HS : sz.NQ;
-    const size_t lds_walk = (pl.form == 3) ? (size_t)(BV * (pl.rays ? 1 : (2 + (pl.wint == 2 ? 4 : (pl.wint == 1) ? 1 : 0) + (pl.ali ? 2 : 0)))
+    const size_t lds_walk = (pl.form == 3) ? (size_t)(BV * (pl.rays ? 1 : (2 + (pl.wint == 2 ? 4 : (pl.wint == 1) ? 1 : 0) + (pl.ali ? 2 : 0) + (pl.abu ? 2 : 0)))
                                                       + ((nh + 3) & ~3) + 4 + 4 * SOC_MAXLAUNCH) * 4
                                            : (size_t)(BV * (1 + pl.wint) + nh + 2 + 3 * SOC_MAXLAUNCH + SOC_MAXL + A.P) * 4;
     const size_t lds_ev = (size_t)(nh + 4 + SOC_MAXL) * 4;
@@ -2452,7 +2507,9 @@ static hipError_t plan_kernel(SocSweepPlan &pl, SocBrickArgs &A, SocSweepSize &s
         if (several && pl.form != 3) return hipErrorInvalidValue;
         if (several) pl.kind = 4;
         else if (all_bg && !tune.nolean) pl.kind = 3;
+        if (pl.form == 3 && pl.abu) pl.kind = 4;                          // per-cell opacities: one kernel per WINT, the kind from the launch
     }
+    if (pl.form == 3 && pl.abu && (pl.wint == 2 || pl.ali)) return hipErrorNotSupported;      // (plan_sweep does not plan these)
     if (pl.form != 3) for (int l = 0; l < K.n; l++) if (K.S[l].MIRROR) return hipErrorNotSupported;      // reflecting faces: the event workgroups of brick-local hierarchies only
     return hipSuccess;
 }
@@ -2467,6 +2524,10 @@ static hipError_t reserve_buffers(SocBrickBuffers &bb, SocBrickArgs &A, const So
         BCHK(grow(bb.cap_park, sz.count, st, &bb.park));
         A.park = bb.park;
         A.sca = *sca;
+    }
+    if (A.LT && A.kopt_stride > 0) {                                   // (kopt_stride: set by build_bricks for sweeps with per-cell opacities)
+        BCHK(grow(bb.cap_kopt, (size_t)(A.NBQ / A.NB) * (size_t)A.kopt_stride, st, &bb.kopt));
+        A.kopt = bb.kopt;
     }
     if (!bb.pack) BCHK(brick_alloc(&bb.pack, 1));
     if (!bb.ndesc) { BCHK(brick_alloc(&bb.ndesc, 4));  BCHK(brick_alloc(&bb.total, 1));  BCHK(brick_alloc(&bb.admit, 1 + 3 * SOC_MAXLAUNCH)); }
@@ -2488,6 +2549,11 @@ static hipError_t run_passes(int &passes, const SocSweepPlan &pl, SocBrickArgs A
     const int nev = ((int)((live + A.P - 1) / A.P) + (A.EQ + 1) * K.n) * slices;
     BCHK(hipMemcpyAsync(bb.pack, &K, sizeof(SocSimPack), hipMemcpyHostToDevice, st));
     BCHK(hipStreamSynchronize(st));                                   // K is on the caller's stack
+    if (pl.form == 3 && pl.abu) {                                     // every group's OPT in brick-slot order
+        const unsigned nbx = (unsigned)std::min<long long>((A.kopt_stride + 255) / 256, 16384);
+        soc_lbrick_opt<<<dim3(nbx, (unsigned)(A.NBQ / A.NB)), 256, 0, st>>>(bb.pack, A.bcell, A.kopt_stride, bb.kopt);
+        BCHK(hipGetLastError());
+    }
     soc_brick2_init<<<(std::max(sz.count, (uint32_t)sz.NQ) + 255) / 256, 256, 0, st>>>(bb.pack, A, sz.count, bb.idq[0], bb.desc[0], bb.ndesc, bb.hist);
     BCHK(hipGetLastError());
     passes = 0;
@@ -2548,6 +2614,10 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *S, int n
     hipError_t e = build_bricks(A, pl, device, G, LB, st, tune.verbose != 0);
     if (e == hipErrorNotSupported && pl.form == 3) {                  // a root cell with more cells below it than a brick holds:
         BCHK(plan_sweep(pl, G, S, nlaunch, V, tune, sca, false));     // the sweep that reads the hierarchy from global memory (rays: none)
+        // (launches deferred for the brick-local form share OPT arrays, soc_capi.hip: that sweep cannot stride through them, and the
+        // caller runs them through the direct kernels)
+        for (int l = 1; l < nlaunch && V.abu; l++)
+            if ((long long)(S[l].OPT - S[0].OPT) != l * (long long)(S[1].OPT - S[0].OPT)) return hipErrorNotSupported;
         e = build_bricks(A, pl, device, G, LB, st, tune.verbose != 0);
     }
     BCHK(e);

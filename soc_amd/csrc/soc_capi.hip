@@ -59,7 +59,11 @@ static size_t view_pixels(const soc_ctx *c)
 
 // Hierarchies on which the brick sweep keeps the brick's cells in LDS (soc_brick.hip, soc_ltree.h): there a lone
 // launch with enough work items pays too -- also with the INT tally, which lives in LDS beside TABS.
-static bool lt_capable(const soc_ctx *c, bool abu) { return soc_brick_local(c->G, soc_grid_variant(c->G, abu), c->tune); }
+// With per-cell opacities: soc_set_tuning("abu_local", 1), and neither with_int 2 nor ALI (soc_dev.h: soc_brick_local).
+static bool lt_capable(const soc_ctx *c, bool abu)
+{
+    return soc_brick_local(c->G, soc_grid_variant(c->G, abu, c->with_int), c->tune) && !(abu && c->with_ali);
+}
 // ... the launches of the scattered-light kernels (alone, or those of a batch together) go to the sweep of rays.  Measured on the 256^3-root
 // hierarchy (tools/exp_sca.py): 1.0e6 work items 0.47x the direct kernel, 3.1e6 0.92x, 8.4e6 1.3x, 5.0e7 1.6x (best direct launch shape), 32
 // launches of 3.1e6 in one batch 4.4x
@@ -113,6 +117,7 @@ int flush_pending(soc_ctx *c)
     if (c->pending.empty()) return SOC_OK;
     std::vector<SocSim> todo;
     todo.swap(c->pending);
+    c->opt_used = 0;                                        // (the next deferred launch with per-cell opacities takes a copy of its own)
     const bool rays = todo[0].SCAKIND != 0;
     // what made the launches deferrable (see route_sim)
     const SocVariant V = soc_grid_variant(c->G, todo[0].OPT != nullptr, (!rays && c->int_mode != soc_ctx::INT_OFF) ? c->with_int : 0);
@@ -124,7 +129,8 @@ int flush_pending(soc_ctx *c)
     hipError_t e = hipErrorNotSupported;
     if (!direct)
         e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, c->tune, c->stream, &c->last, rays ? &c->view : nullptr);
-    if (direct || (rays && e == hipErrorNotSupported)) {
+    // (per-cell opacities: launches deferred for the brick-local form whose hierarchy cannot be cut into bricks after all)
+    if (direct || ((rays || V.abu) && e == hipErrorNotSupported)) {
         for (const SocSim &S : todo) {
             int r = run_direct(c, S, V);
             if (r) return r;
@@ -354,7 +360,8 @@ int soc_set_tuning(soc_ctx *c, const char *name, int value)
         { "threads", &c->tune.T }, { "chunk", &c->tune.P }, { "steps_per_visit", &c->tune.KCAP }, { "swap_lanes", &c->tune.FTH },
         { "climb_lanes", &c->tune.CTH }, { "brick_cells", &c->tune.CAP }, { "tail_lanes", &c->tune.TAIL }, { "park_below", &c->tune.park }, { "population", &c->tune.POP },
         { "hash_slots", &c->tune.HS }, { "global_tree", &c->tune.global_tree }, { "slow_every", &c->tune.slow_every },
-        { "general_kernel", &c->tune.nolean }, { "oversubscribe", &c->tune.oversub }, { "verbose", &c->tune.verbose } };
+        { "general_kernel", &c->tune.nolean }, { "oversubscribe", &c->tune.oversub }, { "verbose", &c->tune.verbose },
+        { "abu_local", &c->tune.abu_local } };
     for (auto &t : tab)
         if (!strcmp(name, t.n)) {
             if (t.p == &c->tune.CAP && value != c->tune.CAP) soc_brick_invalidate(c->device);
@@ -385,6 +392,7 @@ int soc_set_opt(soc_ctx *c, const float *OPT)
     if (!c->have_grid) return fail(c, SOC_ERR_STATE, "soc_set_opt: call soc_set_grid first");
     HIPCHK(c, hipSetDevice(c->device));
     c->opt_from_abu = false;
+    c->opt_gen++;
     if (!OPT) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->dOPT.release();
@@ -437,6 +445,7 @@ int soc_set_optical_abu(soc_ctx *c, const float *AFABS, const float *AFSCA, int 
     if (!c->abu_ndust || c->abu_cells != (size_t)c->G.CELLS) return fail(c, SOC_ERR_STATE, "soc_set_optical_abu: call soc_set_abundances (after soc_set_grid) first");
     if (!AFABS || !AFSCA || ndust != c->abu_ndust) return fail(c, SOC_ERR_ARG, "soc_set_optical_abu: need the cross sections of the %d species", c->abu_ndust);
     HIPCHK(c, hipSetDevice(c->device));
+    c->opt_gen++;
     float af[128];
     for (int d = 0; d < ndust; d++) { af[d] = AFABS[d];  af[ndust + d] = AFSCA[d]; }
     if (!c->dOPT) HIPCHK(c, c->dOPT.reset((size_t)c->G.CELLS, c->stream));
@@ -658,7 +667,8 @@ static int upload_sources(soc_ctx *c, const char *who, SocSim &S, const float *P
     return SOC_OK;
 }
 
-#define SOC_OPT_SLOTS 16        // launches with per-cell opacities per sweep (8 B per cell and launch, in one buffer)
+#define SOC_OPT_SLOTS 16        // per-cell opacity arrays per sweep (8 B per cell each, in one buffer): one per launch, or -- brick-local
+                                // hierarchies, where launches share them -- one per soc_set_opt / soc_set_optical_abu call
 
 static bool int_slots(const soc_ctx *c) { return c->int_mode == soc_ctx::INT_PER_LAUNCH || c->int_mode == soc_ctx::INT_PER_GROUP; }
 
@@ -694,13 +704,21 @@ static int keep_inputs(soc_ctx *c, SocSim &S, const SocVariant &V, int slot)
     S.CSC = csc;
     if (S.DSC) S.DSC = dsc;
     if (V.abu) {                                            // the per-cell opacities: a slot of one buffer
-        if (slot >= SOC_OPT_SLOTS) return fail(c, SOC_ERR_STATE, "a batch holds at most %d launches with per-cell opacities", SOC_OPT_SLOTS);
+        // The Cartesian sweep and the sweep of a hierarchy in global memory address OPT as launch x stride: launch `slot` keeps its copy in
+        // slot `slot`.  The brick-local form takes every launch's array by its pointer, and launches with ONE array share their brick
+        // queues: there the launches deferred since the last soc_set_opt / soc_set_optical_abu (opt_gen, as keep_emission does for EMIT)
+        // share one copy -- the point-source, background and cell-emission launches of a frequency -- and the slots count arrays.
+        const bool local = lt_capable(c, true);
+        const bool shared = local && c->opt_used > 0 && c->opt_slot_gen == c->opt_gen;
+        const int k = !local ? slot : shared ? c->opt_used - 1 : c->opt_used;
+        if (k >= SOC_OPT_SLOTS) return fail(c, SOC_ERR_STATE, "a batch holds at most %d per-cell opacity arrays", SOC_OPT_SLOTS);
         const size_t cells = (size_t)c->G.CELLS;
         float2 *opt = nullptr;
         r = slot_buf(c, soc_ctx::SLOT_OPT, 0, SOC_OPT_SLOTS * cells * 8, &opt);
         if (r) return r;
-        S.OPT = opt + (size_t)slot * cells;
-        HIPCHK(c, hipMemcpyAsync(opt + (size_t)slot * cells, c->dOPT, cells * 8, hipMemcpyDeviceToDevice, c->stream));
+        S.OPT = opt + (size_t)k * cells;
+        if (!shared) HIPCHK(c, hipMemcpyAsync(opt + (size_t)k * cells, c->dOPT, cells * 8, hipMemcpyDeviceToDevice, c->stream));
+        if (local && !shared) { c->opt_used = k + 1;  c->opt_slot_gen = c->opt_gen; }
     }
     return SOC_OK;
 }
@@ -754,9 +772,9 @@ static const struct {
     long long   min_items;              // absorption, automatic mode: work items from which the brick sweep pays
     const char *not_applicable;         // absorption: what keeps soc_set_exec(1) from the brick sweep
 } sim_kinds[] = {
-    { "soc_sim_pb", 0, 65536,  "mirror, with_int 2, roisave/roiload, > 15 levels or > 2^18 bricks" },
-    { "soc_sim_hp", 0, 65536,  "mirror, with_int 2, > 15 levels or > 2^18 bricks" },
-    { "soc_sim_cl", 0, 262144, "mirror, with_int 2, USE_EMWEIGHT 2, ALI, roisave, > 15 levels or > 2^18 bricks" },
+    { "soc_sim_pb", 0, 65536,  "mirror, with_int 2, roisave/roiload off brick-local hierarchies (per-cell opacities: those need soc_set_tuning abu_local and no with_int 2), > 15 levels or > 2^18 bricks" },
+    { "soc_sim_hp", 0, 65536,  "mirror, with_int 2 off brick-local hierarchies (per-cell opacities: those need soc_set_tuning abu_local and no with_int 2), > 15 levels or > 2^18 bricks" },
+    { "soc_sim_cl", 0, 262144, "mirror, with_int 2, ALI, roisave off brick-local hierarchies (per-cell opacities: those need soc_set_tuning abu_local and neither with_int 2 nor ALI), USE_EMWEIGHT 2, > 15 levels or > 2^18 bricks" },
     { "soc_sca_sim_pb", SOC_SCA_PB + 1, 0, nullptr },
     { "soc_sca_sim_cl", SOC_SCA_CL + 1, 0, nullptr },
     { "soc_sca_sim_ps", SOC_SCA_PS + 1, 0, nullptr },
@@ -819,6 +837,9 @@ static int route_sim(soc_ctx *c, SimKind kind, SocSim &S, const SocVariant &V, l
     // the others.  Not with_int 2 in the INT slot modes; not WITH_MSF (per-species tables are not kept)
     const bool defer = batch && sweep && !(int_slots(c) && V.wint == 2) && c->msf_ndust <= 1;
     if (!defer || !same_sweep(c, S, V.abu != 0)) FLUSH(c);
+    // (brick-local hierarchies: the launch would bring the sweep's 17th opacity array, see keep_inputs)
+    const bool abu_shared = V.abu && lt_capable(c, true);
+    if (defer && abu_shared && c->opt_used >= SOC_OPT_SLOTS && c->opt_slot_gen != c->opt_gen) FLUSH(c);
     int r = take_int_slot(c, who, S);
     if (r) return r;
     const int slot = defer ? (int)c->pending.size() : -1;
@@ -830,7 +851,7 @@ static int route_sim(soc_ctx *c, SimKind kind, SocSim &S, const SocVariant &V, l
         if (r) return r;
         c->pending.push_back(S);
         // a sweep's worth of launches (with INT tallies per launch or group, take_int_slot holds the batch to batch_max)
-        const int full = (int_slots(c) && S.INT) ? SOC_MAXLAUNCH : V.abu ? std::min(c->batch_max, SOC_OPT_SLOTS) : c->batch_max;
+        const int full = (int_slots(c) && S.INT) ? SOC_MAXLAUNCH : (V.abu && !abu_shared) ? std::min(c->batch_max, SOC_OPT_SLOTS) : c->batch_max;
         if ((int)c->pending.size() >= full) FLUSH(c);
         return SOC_OK;
     }

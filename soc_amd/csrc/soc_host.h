@@ -120,6 +120,9 @@ struct soc_ctx {
     unsigned long long emit_gen = 0;              // bumped by soc_set_emission: launches deferred without a change in between share one copy
     unsigned long long emit_slot_gen = 0;
     int    emit_slot_last = -1;
+    unsigned long long opt_gen = 0;               // bumped by soc_set_opt / soc_set_optical_abu: on brick-local hierarchies the launches deferred
+    unsigned long long opt_slot_gen = 0;          // without a change in between share one copy of the per-cell opacities (keep_inputs)
+    int    opt_used = 0;                          // ... the copies the pending launches hold: slots [0, opt_used) of SLOT_OPT
     int    int_slots_done = 0;                    // launches of the last executed sweep whose INT can be read
     // the INT tally of the launches of a batch (set by the soc_batch_begin* call that opened it):
     //   INT_OFF        soc_batch_begin: launches with the INT tally are not deferred
