@@ -600,7 +600,8 @@ int soc_a2e_eqtemp(soc_ctx *ctx, int batch, int icell, int CELLS, int NFREQ, int
 /* What A2E_pre.py computes per grain size for a <dust>.solver file (A2E_pre.py:233-256; kernel_A2E_pre.c:580-736
  * PrepareIntegrationWeightsTrapezoid, :123-212 PrepareTdown; -D FACTOR of A2E_pre.py:134 is an argument).
  * In:  FREQ[NFREQ], Ef[NFREQ] = PLANCK*FREQ, SKABS[NFREQ] = pi a^2 Q_abs of ONE grain of this size, the enthalpy grid E[NE+1]
- *      with its temperatures T[NE+1].
+ *      with its temperatures T[NE+1].  2 <= NFREQ <= 639 (the weights kernel keeps 64 columns of NFREQ floats in the 160 KB of
+ *      LDS of a workgroup; a larger NFREQ is SOC_ERR_ARG before anything is allocated), 2 <= NE <= 4096.
  * Out: L1, L2[NE*NE] (first and last frequency feeding the transition l -> u at [l*NE+u]; -1, -2 = none; entries with
  *      u <= l are 0 -- the caller sets [0] = -2 as A2E_pre.py:246,249 does), Iw[NE*NE*NFREQ] (the weights of lower bin l
  *      start at l*NE*NFREQ, noIw[l] of them: the file holds them back to back), noIw[NE-1], Tdown[NE]. */

@@ -190,7 +190,7 @@ hipError_t soc_launch_a2e_pre(int NFREQ, int NE, float FACTOR, const float *FREQ
 {
     (void)wrk;                                             // (the accumulators live in LDS)
     const size_t lds = ((size_t)NFREQ * PRE_T + PRE_T) * 4;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;     // NFREQ <= 639
+    if (NFREQ > SOC_A2E_PRE_NFREQ_MAX) return hipErrorInvalidValue;       // (soc_a2e_pre refuses it by name before it allocates)
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void *)soc_pre_weights_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

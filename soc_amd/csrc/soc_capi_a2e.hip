@@ -542,6 +542,9 @@ int soc_a2e_pre(soc_ctx *c, int NFREQ, int NE, float FACTOR, const float *FREQ, 
     FLUSH(c);
     if (NFREQ < 2 || NE < 2 || NE > 4096 || !FREQ || !Ef || !SKABS || !E || !T || !L1 || !L2 || !Iw || !noIw || !Tdown)
         return fail(c, SOC_ERR_ARG, "soc_a2e_pre: NFREQ %d, NE %d or a NULL array", NFREQ, NE);
+    if (NFREQ > SOC_A2E_PRE_NFREQ_MAX)                      // before anything is allocated or copied
+        return fail(c, SOC_ERR_ARG, "soc_a2e_pre: NFREQ = %d, the limit is %d: the weights kernel keeps 64 columns of NFREQ floats in the "
+                                    "160 KB of LDS of a workgroup", NFREQ, SOC_A2E_PRE_NFREQ_MAX);
     for (int i = 1; i < NFREQ; i++)
         if (!(FREQ[i] > FREQ[i - 1]) || !(Ef[i] > Ef[i - 1])) return fail(c, SOC_ERR_ARG, "soc_a2e_pre: FREQ, Ef must increase (entry %d)", i);
     for (int i = 1; i <= NE; i++)

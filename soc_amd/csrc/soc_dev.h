@@ -132,6 +132,7 @@ hipError_t soc_launch_emission(int c0, int c1, int nfreq, float FACTOR, float LE
                                const float *T, float *EMIT, hipStream_t st);
 
 // solver-file preprocessing (soc_a2e_pre.hip): integration weights and cooling rates of one grain size
+#define SOC_A2E_PRE_NFREQ_MAX 639      // the weights kernel keeps 64 columns of NFREQ floats and 64 ints in LDS: (639*64 + 64)*4 B = 160 KB
 hipError_t soc_launch_a2e_pre(int NFREQ, int NE, float FACTOR, const float *FREQ, const float *Ef, const float *SKABS, const float *E, const float *T,
                               int *L1, int *L2, float *IW, float *wrk, int *noIw, float *Tdown, hipStream_t st);
 
