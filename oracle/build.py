@@ -245,7 +245,7 @@ def map_ref_models():
     from soc_amd import synth
     oct8 = synth.octree_cloud(8, levels=3, frac=0.15, seed=7)
     oct104 = synth.octree_cloud(104, levels=3, frac=0.002, seed=11)
-    return {
+    m = {
         "c8": dict(NX=8, NY=8, NZ=8, LEVELS=1, CELLS=512),
         "c8abu": dict(NX=8, NY=8, NZ=8, LEVELS=1, CELLS=512, WITH_ABU=1),
         "oct8": dict(NX=8, NY=8, NZ=8, LEVELS=oct8.LEVELS, CELLS=oct8.CELLS),
@@ -258,6 +258,19 @@ def map_ref_models():
         "oct8mi2": dict(NX=8, NY=8, NZ=8, LEVELS=oct8.LEVELS, CELLS=oct8.CELLS, MAP_INTERPOLATION=2),
         "oct104mi2": dict(NX=104, NY=104, NZ=104, LEVELS=oct104.LEVELS, CELLS=oct104.CELLS, MAP_INTERPOLATION=2),
     }
+    # grids whose three sides differ (synth.NONCUBIC); the hierarchies with MAP_INTERPOLATION 0, 1 and 2
+    for name in synth.NONCUBIC:
+        c = synth.noncubic_cloud(name)
+        g = dict(NX=c.NX, NY=c.NY, NZ=c.NZ, LEVELS=c.LEVELS, CELLS=c.CELLS)
+        m[name] = dict(g)
+        if c.LEVELS > 1:
+            m[name + "mi1"] = dict(g, MAP_INTERPOLATION=1)
+            m[name + "mi2"] = dict(g, MAP_INTERPOLATION=2)
+    g = m["oct759"]
+    m["oct759roi"] = dict(g, ROI_MAP=1)
+    m["oct759thr"] = dict(g, LEVEL_THRESHOLD=1)
+    m["oct104x6x5abu"] = dict(m["oct104x6x5"], WITH_ABU=1)
+    return m
 
 
 def sca_ref_models():
@@ -336,6 +349,9 @@ def ref_models():
     # config 3 of BASELINE.json (bench.py's cpu_baseline): synth.octree_cloud(256, levels=4, frac=0.10, seed=1234);
     # the cell count is written out (the cloud takes a second and 400 MB to generate) and checked by bench.py
     m["oct256"] = dict(NX=256, NY=256, NZ=256, LEVELS=4, CELLS=49526352, GL=0.02)
+    for name in ("oct759", "oct104x6x5", "oct6x104x5"):             # hierarchies whose three sides differ (synth.NONCUBIC)
+        c = synth.noncubic_cloud(name)
+        m[name] = dict(NX=c.NX, NY=c.NY, NZ=c.NZ, LEVELS=c.LEVELS, CELLS=c.CELLS)
     return m
 
 

@@ -65,15 +65,17 @@ def cartesian_cloud(N, seed=1234, uniform=None, NY=None, NZ=None):
     return Cloud(N, NY, NZ, [d])
 
 
-def octree_cloud(N, levels=4, frac=0.10, seed=1234, sigma=0.3, uniform=None):
-    """N^3 root grid; on every level the densest ``frac`` of the leaf cells are refined into
+def octree_cloud(N, levels=4, frac=0.10, seed=1234, sigma=0.3, uniform=None, NY=None, NZ=None):
+    """N^3 (or N x NY x NZ) root grid; on every level the densest ``frac`` of the leaf cells are refined into
     8 children (density = parent x lognormal(sigma), renormalised to conserve mass), for
     ``levels`` hierarchy levels in total (levels=4 <=> 3 refinement levels)."""
+    NY = N if NY is None else NY
+    NZ = N if NZ is None else NZ
     rng = np.random.default_rng(seed)
     if uniform is not None:
-        d0 = np.full(N * N * N, uniform, np.float64)
+        d0 = np.full(N * NY * NZ, uniform, np.float64)
     else:
-        d0 = np.clip(np.exp(rng.standard_normal(N * N * N)) * 1.0e3, 1.0, 1.0e5)
+        d0 = np.clip(np.exp(rng.standard_normal(N * NY * NZ)) * 1.0e3, 1.0, 1.0e5)
     H = [d0]
     for l in range(levels - 1):
         cur = H[l]
@@ -102,7 +104,31 @@ def octree_cloud(N, levels=4, frac=0.10, seed=1234, sigma=0.3, uniform=None):
     for h in H:
         leaf = h > 0
         h[leaf] = np.maximum(h[leaf], 1.0e-6)
-    return Cloud(N, N, N, H)
+    return Cloud(N, NY, NZ, H)
+
+
+# Models whose three sides differ (tests, golden generators and the reference builds of oracle/build.py name them here, once).
+# r*: single level, (NX, NY, NZ, seed); oct*: hierarchy, (NX, NY, NZ, levels, frac, seed).
+#   r759, oct759     all three sides differ
+#   oct104x6x5       NX > 100 with >= 3 levels: Index() in double; oct6x104x5, oct5x6x104: NY / NZ > 100 but NX is not: float
+#   r208x6x5         NX >= 200: the first branch of the map kernels' ray entry; r6x208x5: NY >= 200 but NX is not
+NONCUBIC = {
+    "r759": (7, 5, 9, 3),
+    "oct759": (7, 5, 9, 3, 0.15, 7),
+    "oct104x6x5": (104, 6, 5, 3, 0.05, 11),
+    "oct6x104x5": (6, 104, 5, 3, 0.05, 11),
+    "oct5x6x104": (5, 6, 104, 4, 0.05, 11),
+    "r208x6x5": (208, 6, 5, 3),
+    "r6x208x5": (6, 208, 5, 3),
+}
+NONCUBIC_CELLS = {"r759": 315, "oct759": 1139, "oct104x6x5": 4864, "oct6x104x5": 4864, "oct5x6x104": 5064, "r208x6x5": 6240, "r6x208x5": 6240}
+
+
+def noncubic_cloud(name):
+    k = NONCUBIC[name]
+    if len(k) == 4:
+        return cartesian_cloud(k[0], seed=k[3], NY=k[1], NZ=k[2])
+    return octree_cloud(k[0], levels=k[3], frac=k[4], seed=k[5], NY=k[1], NZ=k[2])
 
 
 def kat_octree():

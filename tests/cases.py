@@ -144,6 +144,8 @@ CASES = {
     "roi_oct8_load_save": ("oct8roils", 0, lambda: _roil(_oct8(), (2, 2, 2), 2, 2, SEED=0.71, WITH_INT=1,
                                                           ROI=[3, 4, 3, 5, 2, 5], ROI_STEP=2)),
     "bg_oct8": ("oct8", 0, lambda: Job(_oct8(), _CSC, ABS=1e-4, SCA=3e-4, SOURCE=1, BATCH=30, SEED=0.41)),
+    # a hierarchy whose three sides differ (synth.NONCUBIC): 7 x 5 x 9 root cells
+    "bg_oct759": ("oct759", 0, lambda: Job(synth.noncubic_cloud("oct759"), _CSC, ABS=1e-4, SCA=3e-4, SOURCE=1, BATCH=10, SEED=0.43)),
     "bg_oct4": ("oct4", 0, lambda: Job(synth.kat_octree(), _CSC, ABS=2e-3, SCA=4e-3, SOURCE=1, BATCH=40, SEED=0.51)),
     "ps_in_c8": ("c8ps0", 0, lambda: Job(_c8(), _CSC, ABS=1e-4, SCA=3e-4, SOURCE=0, BATCH=40, SEED=0.2, GLOBAL=256,
                                            PSPOS=_PS_IN, PS=[1.0, 2.0])),

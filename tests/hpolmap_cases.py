@@ -55,6 +55,23 @@ CASES = {
     "oct8_shear":     case("oct8", "near", yshear=2.5, maxlos=20.0),
     "oct104_centre":  case("oct104", "centre"),                  # NX > 100: Index() in double
     "oct104_deep":    case("oct104", "deep2", thr=1, interp=3),
+    # grids whose three sides differ (synth.NONCUBIC): the 3 x 3 x 3 neighbour sums of INTERPOLATE and the periodic wrap of
+    # Y_SHEAR read NX, NY and NZ apart
+    "r759_centre":    case("r759", "centre"),
+    "r759_face":      case("r759", "face"),
+    "r759_integral":  case("r759", "integral"),
+    "r759_i1":        case("r759", "face", interp=1),
+    "r759_i2":        case("r759", "face", interp=2),
+    "r759_i3":        case("r759", "centre", interp=3),
+    "r759_shear":     case("r759", "centre", yshear=2.5, maxlos=20.0),
+    "r759_shear_i2":  case("r759", "face", yshear=2.5, maxlos=20.0, interp=2),
+    "oct759_near":    case("oct759", "near"),
+    "oct759_face":    case("oct759", "face"),
+    "oct759_integral": case("oct759", "integral"),
+    "oct759_i3":      case("oct759", "near", interp=3),
+    "oct759_shear":   case("oct759", "near", yshear=2.5, maxlos=20.0),
+    "oct104x6x5_near": case("oct104x6x5", "near"),               # NX > 100: Index() in double
+    "oct6x104x5_near": case("oct6x104x5", "near"),               # NY > 100 but NX is not: Index() in float
 }
 
 

@@ -28,6 +28,16 @@ CASES = {
     "c8abuh_v1":  case("c8abuh", 1),                       # OPT rounded through fp16 and widened again, as the engine keeps it
     "oct104_v0":  case("oct104", 0),                       # NX > 100: Index() in double
     "oct104_v1":  case("oct104", 1),
+    # grids whose three sides differ (synth.NONCUBIC)
+    "r759_v0":    case("r759", 0),
+    "r759_v1":    case("r759", 1),
+    "oct759_v0":  case("oct759", 0),
+    "oct759_v1":  case("oct759", 1),
+    "oct759_in":  case("oct759", (4.3, 3.6, 4.2)),
+    "oct104x6x5_v0": case("oct104x6x5", 0),                # NX > 100: Index() in double
+    "oct104x6x5_v1": case("oct104x6x5", 1),
+    "oct6x104x5_v0": case("oct6x104x5", 0),                # NY > 100 but NX is not: Index() in float
+    "oct6x104x5_v1": case("oct6x104x5", 1),
 }
 
 model = pc.model

@@ -38,6 +38,18 @@ int lt_info(void *h, int *nbricks, int *max_slots, long *nslots)
     return 0;
 }
 
+// the boxes of the bricks, six ints each (x0, y0, z0, bx, by, bz), and the brick of every root cell
+void lt_bricks(void *h, int *boxes, int *rbrick)
+{
+    Harness *H = (Harness *)h;
+    for (size_t b = 0; b < H->B.bricks.size(); b++) {
+        const SocLBrick &K = H->B.bricks[b];
+        int *o = boxes + 6 * b;
+        o[0] = K.x0;  o[1] = K.y0;  o[2] = K.z0;  o[3] = K.bx;  o[4] = K.by;  o[5] = K.bz;
+    }
+    for (size_t i = 0; i < H->B.rbrick.size(); i++) rbrick[i] = H->B.rbrick[i];
+}
+
 // consistency of the bricks with the hierarchy: every cell has exactly one slot, links and densities are those of DENS
 int lt_check(void *h, const float *DENS, long cells)
 {

@@ -25,6 +25,14 @@ CASES = {
     "oct8_s1_thr2":   ("oct8", 1, 0, 0, 2),
     "oct8_s3":        ("oct8", 3, 0, 0, 0),
     "oct8_s3_thr1":   ("oct8", 3, 0, 0, 1),
+    # grids whose three sides differ (synth.NONCUBIC)
+    "r759_s0":        ("r759", 0, 0, 0, 0),
+    "oct759_s0":      ("oct759", 0, 0, 0, 0),
+    "oct759_s1":      ("oct759", 1, 0, 0, 0),
+    "oct759_s3":      ("oct759", 3, 0, 0, 0),
+    "oct759_s0_thr1": ("oct759", 0, 1, 1, 1),
+    "oct104x6x5_s0":  ("oct104x6x5", 0, 0, 0, 0),     # NX > 100: Index() in double
+    "oct6x104x5_s0":  ("oct6x104x5", 0, 0, 0, 0),     # NY > 100 but NX is not: Index() in float
 }
 
 NPIX = (24, 20)                            # 480 pixels: not a multiple of 256
@@ -47,14 +55,17 @@ def model(name):
         cloud = synth.octree_cloud(8, levels=3, frac=0.15, seed=7)
     elif name == "oct104":
         cloud = synth.octree_cloud(104, levels=3, frac=0.002, seed=11)
+    elif name in synth.NONCUBIC:
+        cloud = synth.noncubic_cloud(name)
     else:
         raise KeyError(name)
     rng = np.random.default_rng(2024)
     m = dict(cloud=cloud, B=synth.magnetic_field(cloud, seed=5), OPT=None)
     m["EMIT"] = np.asarray(rng.uniform(0.5e-3, 1.5e-3, cloud.CELLS), np.float32)
     big = cloud.NX > 100
-    m["ABS"], m["SCA"] = (np.float32(4.0e-6), np.float32(6.0e-6)) if big else (np.float32(4.0e-5), np.float32(6.0e-5))
-    m["MAP_DX"] = 7.0 if big else 0.6
+    long_side = max(cloud.NX, cloud.NY, cloud.NZ) > 100        # the thin slabs: the opacities of the large models, the pixels of the small ones
+    m["ABS"], m["SCA"] = (np.float32(4.0e-6), np.float32(6.0e-6)) if long_side else (np.float32(4.0e-5), np.float32(6.0e-5))
+    m["MAP_DX"] = 7.0 if (big and name not in synth.NONCUBIC) else 0.6
     if "abu" in name:
         OPT = np.asarray(rng.uniform(2.0e-5, 8.0e-5, (cloud.CELLS, 2)), np.float32)
         if name.endswith("h"):

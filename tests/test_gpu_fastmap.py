@@ -16,7 +16,12 @@ from test_maps import CSC, DE, LENGTH, MAP_CASES, N, OD, RA, _opt
 pytestmark = pytest.mark.gpu
 
 CASES = ["map_oct8", "map_c8_abu", "map_oct8_inside", "map_oct8_healpix", "map_oct8_colden", "map_oct8_roimap", "map_oct8_threshold",
-         "map_oct8_mapint1", "map_oct8_mapint2", "map_oct104_mapint2_double", "map_c208_entry"]
+         "map_oct8_mapint1", "map_oct8_mapint2", "map_oct104_mapint2_double", "map_c208_entry",
+         # grids whose three sides differ (synth.NONCUBIC)
+         "map_r759", "map_oct759", "map_oct759_inside", "map_oct759_mapint1", "map_oct759_mapint2", "map_oct759_roimap", "map_oct759_threshold",
+         "map_oct104x6x5", "map_oct104x6x5_inside", "map_oct104x6x5_mapint2", "map_oct104x6x5_abu", "map_oct6x104x5", "map_oct6x104x5_inside",
+         "map_oct6x104x5_mapint2", "map_oct5x6x104", "map_oct5x6x104_mapint1", "map_r208x6x5", "map_r208x6x5_inside", "map_r6x208x5",
+         "map_r6x208x5_inside"]
 ABS0, SCA0 = np.float32(1e-3), np.float32(3e-3)               # the opacities of tests/test_maps.py::run_case
 
 
@@ -159,6 +164,36 @@ def test_block_planes_equal_the_oracle(name, engine, cases, oracle_soc):
         _, col = oracle_mapping(oracle_soc, Job(case.cloud, CSC, ABS=case.ABS[0], SCA=case.SCA[0]), case.EMITX[:, 0].copy(), *case.args(v),
                                 kw.get("intobs", NO_INTOBS), 1, LENGTH, kw.get("healpix", 0))
         assert _same(COLDEN.ravel(), col.ravel())
+    _reset(engine)
+
+
+@pytest.mark.parametrize("name", ["map_oct759_1080", "map_oct759_healpix5"])
+def test_more_than_one_workgroup_and_a_ragged_last_one(name, engine, cases, oracle_soc):
+    """1080 pixels are four workgroups of 256 and one of 56 lanes, 300 are one and 44 lanes: blockIdx.x * blockDim.x and the plane
+    stride f * npix + id matter.  Widths 1, 3 (after a full-width batch of NaN) and 32: every plane equals the per-frequency
+    kernel's, and three of them the oracle's."""
+    case = cases(name)
+    kw = case.kw
+    npix = 12 * kw["healpix"] ** 2 if kw.get("healpix") else kw["npix"][0] * kw["npix"][1]
+    assert npix > 256 and npix % 256 != 0
+    for nf in (1, 3, engine.map_block_max):
+        if nf == 3:
+            case.poison(engine)
+        case.upload(engine, nf)
+        for v in range(case.views):
+            MAPX, TAUX, COLDEN = case.block(engine, v)
+            assert MAPX.shape[0] == nf and TAUX.shape[0] == nf and MAPX[0].size == npix
+            for f in range(nf):
+                m, t = case.ref[f][v]
+                assert _same(MAPX[f], m) and _same(TAUX[f], t), (name, nf, f, v)
+            assert _same(COLDEN, case.colden[v]) and np.isfinite(MAPX).all() and np.isfinite(TAUX).all()
+            assert (MAPX[0] > 0).sum() > 30
+            if nf == 3:
+                for f in range(3):
+                    job = Job(case.cloud, CSC, ABS=case.ABS[f], SCA=case.SCA[f])
+                    m, t = oracle_mapping(oracle_soc, job, case.EMITX[:, f].copy(), *case.args(v), kw.get("intobs", NO_INTOBS), 0, LENGTH,
+                                          kw.get("healpix", 0))
+                    assert _same(MAPX[f].ravel(), m.ravel()) and _same(TAUX[f].ravel(), t.ravel()), (name, f, v)
     _reset(engine)
 
 

@@ -19,10 +19,19 @@ from test_maps import DE, LENGTH, MAP_CASES, N, OD, RA, _opt
 pytestmark = pytest.mark.gpu
 
 CASES = ["map_oct8", "map_oct8_inside", "map_oct8_healpix", "map_oct8_roimap", "map_oct8_threshold", "map_oct8_mapint1", "map_oct8_mapint2",
-         "map_oct8_mapint1_inside", "map_oct104_double", "map_oct104_mapint2_double", "map_c8_abu", "map_oct8_mapint2+abu"]
+         "map_oct8_mapint1_inside", "map_oct104_double", "map_oct104_mapint2_double", "map_c8_abu", "map_oct8_mapint2+abu",
+         # grids whose three sides differ (synth.NONCUBIC)
+         "map_r759", "map_oct759", "map_oct759_inside", "map_oct759_mapint2", "map_oct759_mapint2+abu", "map_oct759_threshold",
+         "map_oct759_healpix5", "map_oct104x6x5", "map_oct104x6x5_mapint1", "map_oct104x6x5_abu", "map_oct6x104x5", "map_oct6x104x5_mapint2",
+         "map_oct6x104x5_inside", "map_oct5x6x104_mapint1", "map_r208x6x5", "map_r6x208x5"]
+# (not map_oct104x6x5_mapint2 and map_oct5x6x104_mapint2: with `mapint 2` along 104 cells the CPU oracle's own fp32 sum along the ray and
+# the sum of its per-level sums are 2.09e-6 and 1.88e-6 apart, at the 2e-6 of LCase.check, which was sized on rays of 8 root cells;
+# tests/test_gpu_fastmap.py and tests/test_maps.py have those two cases against the per-frequency kernel and the oracle)
 # which planes the definition lights in view 0 (found with the CPU oracle in soc mode); the others are dark
 LIT = {"map_oct8": [0, 1, 2], "map_oct8_mapint2": [0, 1, 2], "map_oct8_roimap": [0, 1, 2], "map_oct8_healpix": [0, 1, 2],
-       "map_oct8_inside": [0, 1, 2], "map_oct8_threshold": [1, 2], "map_oct104_double": [0, 1]}
+       "map_oct8_inside": [0, 1, 2], "map_oct8_threshold": [1, 2], "map_oct104_double": [0, 1],
+       "map_oct759": [0, 1, 2], "map_oct759_threshold": [1, 2], "map_oct759_healpix5": [0, 1, 2], "map_oct104x6x5": [0, 1],
+       "map_oct6x104x5": [0, 1, 2], "map_oct5x6x104_mapint1": [0, 1, 2]}
 DEEP = {6: 8648, 9: 120184}                                   # levels -> cells of synth.octree_cloud(4, levels, frac=0.3, seed=3)
 
 

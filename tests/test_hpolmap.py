@@ -35,7 +35,7 @@ def test_golden_file_holds_every_case_and_its_inputs_are_reproduced():
     assert os.path.getsize(GOLDEN) < 1 << 20
     # every switch the kernel has is in some case
     K = hc.CASES.values()
-    assert {k["model"] for k in K} == {"c8", "c8abu", "c8abuh", "oct8", "oct104"}
+    assert {k["model"] for k in K} == {"c8", "c8abu", "c8abuh", "oct8", "oct104", "r759", "oct759", "oct104x6x5", "oct6x104x5"}
     assert {k["polred"] for k in K} == {0, 1} and {k["thr"] for k in K} == {0, 1, 2} and {k["interp"] for k in K} == {0, 1, 2, 3}
     assert any(k["maxlos"] < 8 for k in K) and any(k["minlos"] > 0 for k in K) and any(k["yshear"] == 2.5 and k["maxlos"] == 20.0 for k in K)
 

@@ -37,7 +37,7 @@ def test_golden_file_holds_every_case_and_its_inputs_are_reproduced():
         assert np.array_equal(g["fp_" + k["model"]], lc.fingerprint(m)), "the inputs of %s changed" % name
     assert os.path.getsize(GOLDEN) < 1 << 20
     K = lc.CASES.values()
-    assert {k["model"] for k in K} == {"c8", "c8abu", "c8abuh", "oct8", "oct104"}
+    assert {k["model"] for k in K} == {"c8", "c8abu", "c8abuh", "oct8", "oct104", "r759", "oct759", "oct104x6x5", "oct6x104x5"}
     assert lc.CASES["oct8_face"]["view"] == (0.5, 3.0, 2.9)
     for model in ("c8", "oct8", "oct104"):                                  # both external views of every geometry
         assert {k["view"] for k in K if k["model"] == model and k["dx"] is None and not isinstance(k["view"], tuple)} == {0, 1}

@@ -52,6 +52,15 @@ class LTree:
         self.lib.lt_info(self.h, C.byref(nb), C.byref(ms), C.byref(ns))
         return nb.value, ms.value, ns.value
 
+    def bricks(self):
+        """([bricks, 6] boxes x0, y0, z0, bx, by, bz; [NZ, NY, NX] brick of every root cell)"""
+        c = self.cloud
+        boxes = np.zeros((self.info()[0], 6), np.int32)
+        rb = np.full(c.NX * c.NY * c.NZ, -7, np.int32)
+        self.lib.lt_bricks.argtypes = [C.c_void_p, _I, _I]
+        self.lib.lt_bricks(self.h, boxes.ctypes.data_as(_I), rb.ctypes.data_as(_I))
+        return boxes, rb.reshape(c.NZ, c.NY, c.NX)
+
     def check(self):
         return self.lib.lt_check(self.h, self.DENS.ctypes.data_as(_F), self.cloud.CELLS)
 
@@ -127,6 +136,69 @@ def test_local_tree_steps_are_the_oracles_steps(name, cap, oracle_soc):
         steps += n
         deeper.update(lev.tolist())
     assert steps > 250000 and deeper == set(range(cloud.LEVELS))
+    assert slow < 0.02 * len(pos)
+    lt.close()
+
+
+# hierarchies whose three sides differ (synth.NONCUBIC).  cap: cells per brick (soc_set_tuning brick_cells on the device).
+#   oct759, 200: the one 7 x 5 x 9 tile is halved along z, y and x; 1139 and more: the whole model is one brick
+#   oct104x6x5, 100: tiles of 16 x 6 x 5 root cells (8 x 6 x 5 at the far x face) halved down to 4 x 3 x 5, 4 x 3 x 2, 2 x 3 x 3 ...
+RAGGED = [("oct759", 200), ("oct104x6x5", 100), ("oct6x104x5", 100), ("oct5x6x104", 200)]
+
+
+@pytest.mark.parametrize("name,cap", RAGGED + [("oct759", 1139), ("oct104x6x5", 12288)])
+def test_bricks_of_grids_with_unequal_sides(name, cap):
+    """every root cell belongs to exactly one brick, whose box holds it; with the small caps the far faces cut the bricks to three
+    different extents, with the large one oct759 is a single brick"""
+    cloud = synth.noncubic_cloud(name)
+    lt = LTree(cloud, cap)
+    assert lt.h, "bricks could not be built"
+    nb, ms, ns = lt.info()
+    assert ms <= cap and ns == cloud.CELLS and lt.check() == 0
+    boxes, rb = lt.bricks()
+    assert rb.min() == 0 and rb.max() == nb - 1
+    count = np.zeros((cloud.NZ, cloud.NY, cloud.NX), np.int32)
+    for b, (x0, y0, z0, bx, by, bz) in enumerate(boxes):
+        assert bx >= 1 and by >= 1 and bz >= 1 and x0 + bx <= cloud.NX and y0 + by <= cloud.NY and z0 + bz <= cloud.NZ
+        count[z0:z0 + bz, y0:y0 + by, x0:x0 + bx] += 1
+        assert (rb[z0:z0 + bz, y0:y0 + by, x0:x0 + bx] == b).all()
+    assert (count == 1).all()                                   # a partition of the root grid
+    if (name, cap) in RAGGED:
+        assert nb > 1 and all(n % 16 != 0 for n in (cloud.NX, cloud.NY, cloud.NZ))   # no side is a multiple of the tile's edge
+        assert any(len({bx, by, bz}) == 3 for _, _, _, bx, by, bz in boxes), "no brick with three different extents"
+        assert sum(len(set(boxes[:, 3 + axis].tolist())) > 1 for axis in range(3)) >= 2  # bricks of different extents along two axes or more
+    elif name == "oct759":
+        assert nb == 1 and tuple(boxes[0]) == (0, 0, 0, 7, 5, 9)
+    lt.close()
+
+
+@pytest.mark.parametrize("cap", [100, 12288])
+def test_local_tree_steps_on_a_slab_are_the_oracles_steps(cap, oracle_soc):
+    """oct104x6x5 (NX > 100, three levels: Index() in double, the grid the device walks brick-locally) at the two brick sizes of
+    tests/test_gpu_noncubic.py: as test_local_tree_steps_are_the_oracles_steps, on fewer and shorter rays"""
+    cloud = synth.noncubic_cloud("oct104x6x5")
+    lt = LTree(cloud, cap)
+    assert lt.h and lt.check() == 0
+    job = Job(cloud, np.linspace(1, -1, 16).astype(np.float32))
+    pos, u = _rays(cloud, 3000, np.random.default_rng(11))
+    steps = slow = 0
+    deeper = set()
+    for i in range(len(pos)):
+        lev, cel, ds, end, st = lt.trace(pos[i], u[i])
+        assert st in (0, 2), "ray %d: status %d" % (i, st)
+        olev, oind, ods, oend = oracle_soc.trace(job, pos[i], u[i], maxsteps=20000)
+        n = len(lev)
+        if st == 2:
+            slow += 1
+            assert n <= len(olev)
+        else:
+            assert n == len(olev), "ray %d: %d steps, oracle %d" % (i, n, len(olev))
+            assert np.array_equal(end.view(np.uint32), oend.view(np.uint32)), "ray %d: end position" % i
+        assert np.array_equal(lev, olev[:n]) and np.array_equal(cel, cloud.OFF[olev[:n]] + oind[:n]), "ray %d: cells differ" % i
+        assert np.array_equal(ds.view(np.uint32), ods[:n].view(np.uint32)), "ray %d: step lengths differ" % i
+        steps += n
+        deeper.update(lev.tolist())
+    assert steps > 4 * len(pos) and deeper == set(range(cloud.LEVELS))   # the slab is 5 and 6 cells thick: short rays
     assert slow < 0.02 * len(pos)
     lt.close()
 

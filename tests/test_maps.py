@@ -44,6 +44,38 @@ MAP_CASES = {
     "map_oct104_double": ("oct104", lambda: synth.octree_cloud(104, levels=3, frac=0.002, seed=11), dict(npix=(24, 24), dx=4.0)),
     "map_c208_entry": ("c208", lambda: synth.cartesian_cloud(208, uniform=1.0), dict(npix=(10, 10), dx=20.0)),
 }
+
+
+def _nc(name):
+    return lambda: synth.noncubic_cloud(name)
+
+
+# Grids whose three sides differ (synth.NONCUBIC).  Each model has a pixel grid of its own, NONCUBIC_VIEW = (NPIX, MAP_DX) of the
+# orthographic views: square pixels sized to the long side of a slab would light a handful of them.  test_noncubic_views_* assert on
+# the recorded reference maps that every such case lights more than 30 pixels, has rays that miss the model and directions with a
+# zero component (views 1 and 2 look along x and z: the 1e-5 clamp of the direction runs).
+NONCUBIC_VIEW = {"r759": ((12, 10), 1.0), "oct759": ((12, 10), 1.0), "oct104x6x5": ((16, 12), 0.7), "oct6x104x5": ((16, 12), 0.7),
+                 "oct5x6x104": ((16, 12), 0.7), "r208x6x5": ((16, 12), 0.7), "r6x208x5": ((16, 12), 0.7)}
+NONCUBIC_ORTHO = []
+for _m, (_npix, _dx) in NONCUBIC_VIEW.items():
+    _c = synth.NONCUBIC[_m]
+    _obs = (0.5 * _c[0] + 0.2, 0.5 * _c[1] + 0.1, 0.5 * _c[2] - 0.1)
+    MAP_CASES["map_" + _m] = (_m, _nc(_m), dict(npix=_npix, dx=_dx))
+    MAP_CASES["map_%s_inside" % _m] = (_m, _nc(_m), dict(intobs=_obs, npix=(16, 9)))
+    NONCUBIC_ORTHO.append("map_" + _m)
+    if len(_c) > 4:
+        for _i in (1, 2):
+            MAP_CASES["map_%s_mapint%d" % (_m, _i)] = ("%smi%d" % (_m, _i), _nc(_m), dict(mapint=_i, npix=_npix, dx=_dx))
+            NONCUBIC_ORTHO.append("map_%s_mapint%d" % (_m, _i))
+MAP_CASES.update({
+    "map_oct759_roimap": ("oct759roi", _nc("oct759"), dict(roi=[1, 5, 1, 3, 2, 7], npix=(12, 10), dx=1.0)),             # -D ROI_MAP=1
+    "map_oct759_threshold": ("oct759thr", _nc("oct759"), dict(threshold=1, npix=(12, 10), dx=1.0)),                     # -D LEVEL_THRESHOLD=1
+    "map_oct104x6x5_abu": ("oct104x6x5abu", _nc("oct104x6x5"), dict(abu=True, npix=(16, 12), dx=0.7)),
+    # more than one workgroup of 256 pixels with a ragged last one: 40 x 27 = 1080 = 4 * 256 + 56; NSIDE 5 = 300 = 256 + 44
+    "map_oct759_1080": ("oct759", _nc("oct759"), dict(npix=(40, 27), dx=0.3)),
+    "map_oct759_healpix5": ("oct759", _nc("oct759"), dict(intobs=(3.7, 2.6, 4.4), healpix=5)),
+})
+NONCUBIC_ORTHO += ["map_oct759_roimap", "map_oct759_threshold", "map_oct104x6x5_abu", "map_oct759_1080"]
 LENGTH = np.float32(3.08568e16)
 
 
@@ -70,6 +102,26 @@ def test_map_oracle_bit_exact_vs_reference_golden(name, oracle_libm):
     assert (m > 0).sum() > 30
     assert np.array_equal(m.view(np.uint32), GOLD[name + "_map"].view(np.uint32))
     assert np.array_equal(t.view(np.uint32), GOLD[name + "_tau"].view(np.uint32))
+
+
+@pytest.mark.parametrize("name", NONCUBIC_ORTHO)
+def test_noncubic_views_light_pixels_and_miss_the_model(name):
+    """on the recorded maps of the reference, not on a device's: per view, and the three views are the oblique one and the two along
+    x and z (a direction with two zero components each)"""
+    _, _, kw = MAP_CASES[name]
+    n = kw["npix"][0] * kw["npix"][1]
+    m, t = GOLD[name + "_map"].reshape(N, n), GOLD[name + "_tau"].reshape(N, n)
+    assert (m > 0).sum() > 30
+    assert (t == 0).any() and (m[t == 0] == 0).all()           # rays that miss the model
+    assert (np.abs(OD[1, :3]) <= 1e-5).sum() == 2 and (np.abs(OD[2, :3]) <= 1e-5).sum() == 2   # zero components, at the host's clamp
+    assert (m[1] > 0).any() and (m[2] > 0).any() and (m[0] > 0).any()
+    if kw.get("npix") == (40, 27):
+        assert n > 256 and n % 256 != 0
+
+
+def test_healpix5_does_not_fill_its_last_workgroup():
+    m = GOLD["map_oct759_healpix5_map"]
+    assert m.size == 12 * 5 * 5 and m.size > 256 and m.size % 256 != 0 and (m > 0).sum() > 30
 
 
 @pytest.mark.parametrize("name", ["map_c8", "map_oct8_inside", "map_oct8_healpix"])
@@ -177,18 +229,24 @@ def test_fits_maps_and_column_density(tmp_path):
 _PS4 = np.array([[4.3, 4.2, 4.1], [2.5, 6.5, 3.3], [0.2, 0.3, 7.9], [7.7, 0.4, 0.6]], np.float32)
 
 
+def _ps4(cloud):
+    """the four sources of the 8^3 models at the same relative places of another grid (a cube: the factor NX / 8 on every axis)"""
+    return _PS4 * (np.asarray([cloud.NX, cloud.NY, cloud.NZ], np.float32) / np.float32(8.0))
+
+
 @pytest.mark.skipif(not RefMap.available("oct8"), reason="reference builds (oracle/_ref) not present")
 def test_pstau_oracle_bit_exact_vs_reference(oracle_libm):
     """PSTau (kernel_ASOC_map.c:1545-1584) compiled from the reference, scalar and per-cell opacities"""
     from oracle.pyoracle import oracle_pstau
     o8 = synth.octree_cloud(8, levels=3, frac=0.15, seed=7)
     LEN = float("%.5e" % (0.01 * 3.08567758e18))              # the -D LENGTH of the build (oracle/build.py)
-    for ref, opt in (("oct8", None), ("c8abu", True)):
-        cloud = o8 if ref == "oct8" else synth.cartesian_cloud(8, seed=3)
+    for ref, opt in (("oct8", None), ("c8abu", True), ("oct759", None), ("oct104x6x5", None), ("oct104x6x5abu", True)):
+        cloud = o8 if ref == "oct8" else synth.cartesian_cloud(8, seed=3) if ref == "c8abu" else synth.noncubic_cloud(ref.replace("abu", ""))
         job = Job(cloud, CSC, ABS=1e-3, SCA=3e-3, OPT=_opt(cloud.CELLS) if opt else None)
+        ps = _ps4(cloud)
         for k in range(N):
-            c, t = oracle_pstau(oracle_libm, job, _PS4, OD[k], LEN)
-            c2, t2 = RefMap(ref).pstau(job, oracle_libm.parents(job), _PS4, OD[k])
+            c, t = oracle_pstau(oracle_libm, job, ps, OD[k], LEN)
+            c2, t2 = RefMap(ref).pstau(job, oracle_libm.parents(job), ps, OD[k])
             assert np.array_equal(c.view(np.uint32), c2.view(np.uint32)) and np.array_equal(t.view(np.uint32), t2.view(np.uint32))
             assert (t > 0).all() and (c > 0).all()
 
@@ -197,9 +255,11 @@ def test_pstau_oracle_bit_exact_vs_reference(oracle_libm):
 def test_pstau_hip_bit_identical_to_oracle(engine, oracle_soc):
     from oracle.pyoracle import oracle_pstau
     for cloud, opt in ((synth.octree_cloud(8, levels=3, frac=0.15, seed=7), False), (synth.cartesian_cloud(8, seed=3), True),
-                       (synth.octree_cloud(104, levels=3, frac=0.002, seed=11), False)):
+                       (synth.octree_cloud(104, levels=3, frac=0.002, seed=11), False), (synth.noncubic_cloud("oct759"), False),
+                       (synth.noncubic_cloud("oct104x6x5"), False), (synth.noncubic_cloud("oct6x104x5"), True), (synth.noncubic_cloud("oct5x6x104"), False),
+                       (synth.noncubic_cloud("r759"), False)):
         job = Job(cloud, CSC, ABS=1e-3, SCA=3e-3, OPT=_opt(cloud.CELLS) if opt else None)
-        ps = _PS4 * np.float32(cloud.NX / 8.0)
+        ps = _ps4(cloud)
         engine.set_cloud(cloud)
         engine.set_opt(job.OPT)
         for k in range(N):

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.skipif(not Ref.available("c8"), reason="reference build
 
 
 @pytest.mark.parametrize("name", ["bg_c8", "bg_oct8", "ps_ext2_c8", "cl_oct8_emw", "bg_c8_sw1", "bg_oct8_sw2", "cl_oct8_sw2", "bg_oct8_msf",
-                                  "cl_oct8_msf", "hp_oct8_msf", "bg_c8_int2", "cl_oct8_int2", "ps_in_oct8"])
+                                  "cl_oct8_msf", "hp_oct8_msf", "bg_c8_int2", "cl_oct8_int2", "ps_in_oct8", "bg_oct759"])
 def test_live_bit_exact(name, oracle_libm):
     ref, kind, mk = cases.CASES[name]
     job = mk()
@@ -44,6 +44,32 @@ def test_double_index_path_bit_exact(oracle_libm):
         a = oracle_libm.trace(job, pos, d)
         b = Ref("oct104").trace(job, pos, d)
         assert np.array_equal(a[1], b[1]) and np.array_equal(a[2].view(np.uint32), b[2].view(np.uint32))
+
+
+@pytest.mark.parametrize("name", ["oct759", "oct104x6x5", "oct6x104x5"])
+def test_hierarchies_with_unequal_sides_bit_exact(name, oracle_libm, oracle_soc):
+    """root grids 7 x 5 x 9, 104 x 6 x 5 (NX > 100: Index() in double) and 6 x 104 x 5 (NY > 100, NX not: float): the whole background
+    launch and 100 rays from random places in random directions, step by step"""
+    o = synth.noncubic_cloud(name)
+    _, csc = synth.hg_scattering_table(0.6)
+    job = Job(o, csc, ABS=1e-4, SCA=3e-4, SOURCE=1, BATCH=2 if name == "oct759" else 1, SEED=0.41)
+    T, _, n = oracle_libm.sim(job, 0)
+    T2, _ = Ref(name).sim(job, 0)
+    assert n > 40000 and np.array_equal(T.view(np.uint32), T2.view(np.uint32))
+    r = Ref(name)
+    rays = np.random.default_rng(3)
+    steps = 0
+    for _ in range(100):
+        pos = rays.uniform(0.01, 0.99, 3) * [o.NX, o.NY, o.NZ]
+        d = rays.standard_normal(3)
+        d = (d / np.sqrt((d ** 2).sum())).astype(np.float32)
+        d[np.abs(d) < 5e-5] = 5e-5
+        a, b, c = oracle_libm.trace(job, pos, d), r.trace(job, pos, d), oracle_soc.trace(job, pos, d)
+        for x in (a, c):
+            assert np.array_equal(x[0], b[0]) and np.array_equal(x[1], b[1])
+            assert np.array_equal(x[2].view(np.uint32), b[2].view(np.uint32))
+        steps += len(b[0])
+    assert steps > 500
 
 
 def test_random_rays_octree(oracle_libm, oracle_soc):
