@@ -2050,17 +2050,7 @@ __global__ __launch_bounds__(SOC_BRICK_T) void soc_brick_scatter(SocBrickArgs A,
 // host orchestration
 // ---------------------------------------------------------------------------------------
 
-struct SocBrickBuffers {
-    size_t cap_items = 0, cap_nq = 0, cap_desc = 0, cap_park = 0, cap_kopt = 0;
-    SocPk2 *pk = nullptr, *park = nullptr;
-    float2 *kopt = nullptr;                                // per-cell opacities in brick-slot order, one array per group of launches
-    uint32_t *idq[2] = { nullptr, nullptr }, *keyq = nullptr, *posq = nullptr;
-    SocSimPack *pack = nullptr;
-    int *hist = nullptr, *off = nullptr, *ndesc = nullptr, *total = nullptr, *admit = nullptr;
-    SocDesc *desc[2] = { nullptr, nullptr };
-};
-
-static SocBrickBuffers g_bb[16];                          // one set per device ordinal
+#include "soc_devbuf.h"
 
 #define BCHK(call)                          \
     do {                                    \
@@ -2068,34 +2058,22 @@ static SocBrickBuffers g_bb[16];                          // one set per device 
         if (e_ != hipSuccess) return e_;    \
     } while (0)
 
+// Packet records, queues and descriptors of a sweep.  A buffer only grows (reserve_buffers), each with a capacity of its own (DevBuf::n).
+struct SocBrickBuffers {
+    DevBuf<SocPk2> pk, park;
+    DevBuf<float2> kopt;                                   // per-cell opacities in brick-slot order, one array per group of launches
+    DevBuf<uint32_t> idq[2], keyq, posq;
+    DevBuf<SocSimPack> pack;
+    DevBuf<int> hist, off, ndesc, total, admit;
+    DevBuf<SocDesc> desc[2];
+};
+
+// the bricks of a grid on the device: as many elements as v holds, whatever d held
 template <typename T>
-static hipError_t brick_alloc(T **p, size_t n)
+static hipError_t upload(DevBuf<T> &d, const std::vector<T> &v, hipStream_t st)
 {
-    if (*p) { (void)hipFree(*p);  *p = nullptr; }
-    return hipMalloc((void **)p, (n ? n : 1) * sizeof(T));
-}
-
-// The buffers of a sweep only grow: below n elements they are replaced -- once the stream is done with the old ones -- and cap is n.
-template <typename... T>
-static hipError_t grow(size_t &cap, size_t n, hipStream_t st, T **...p)
-{
-    if (cap >= n) return hipSuccess;
-    hipError_t e = hipStreamSynchronize(st);
-    ((e = (e == hipSuccess) ? brick_alloc(p, n) : e), ...);
-    if (e == hipSuccess) cap = n;
-    return e;
-}
-
-static void soc_oct_release(int device);
-
-void soc_brick_release(int device)
-{
-    if (device < 0 || device >= 16) return;
-    SocBrickBuffers &b = g_bb[device];
-    void *ptrs[] = { b.pack, b.pk, b.park, b.kopt, b.idq[0], b.idq[1], b.keyq, b.posq, b.hist, b.off, b.ndesc, b.total, b.admit, b.desc[0], b.desc[1] };
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    b = SocBrickBuffers();
-    soc_oct_release(device);
+    BCHK(d.reset(v.size(), st));
+    return hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2113,52 +2091,36 @@ struct SocOctBricks {
     bool valid = false;
     int  NB = 0, CAP = 0;
     size_t cells = 0, leaves = 0;
-    const float *dens_key = nullptr;           // the hierarchy the bricks were built for
-    float2 *DS = nullptr;
-    int *bcell = nullptr, *bbase = nullptr;
+    DevBuf<float2> DS;
+    DevBuf<int> bcell, bbase;
 };
-static SocOctBricks g_ob[16];
 
 // brick-local hierarchies (soc_lbricks.h) on the device, built once per grid and cap
 struct SocLBricksDev {
     bool valid = false, failed = false;
     int  NB = 0, cap = 0, max_slots = 0;
     size_t cells = 0, slots = 0;               // slots: entries of btree and bcell
-    const float *dens_key = nullptr;
-    SocLBrick *lbr = nullptr;
-    float *btree = nullptr;
-    int *bcell = nullptr, *bbase = nullptr, *rbrick = nullptr;
+    DevBuf<SocLBrick> lbr;
+    DevBuf<float> btree;
+    DevBuf<int> bcell, bbase, rbrick;
 };
-static SocLBricksDev g_lb[16];
 
-static void soc_lb_release(int device)
+// What the sweeps of one handle keep on the device (soc_ctx::sweep): nothing of it is shared between handles, and all of it is counted
+// by soc_device_bytes.  The bricks are the ones of the handle's grid: soc_set_grid and soc_set_tuning("brick_cells") mark them stale.
+struct SocSweepState {
+    SocBrickBuffers bb;
+    SocOctBricks ob;
+    SocLBricksDev lb;
+};
+
+SocSweepState *soc_sweep_new() { return new SocSweepState(); }
+void soc_sweep_delete(SocSweepState *sw) { delete sw; }
+void soc_sweep_invalidate(SocSweepState *sw) { sw->ob.valid = false;  sw->lb.valid = false;  sw->lb.failed = false; }
+
+static hipError_t soc_oct_build(SocOctBricks &ob, const SocGrid &G, int CAP, hipStream_t st, bool verbose)
 {
-    SocLBricksDev &o = g_lb[device];
-    void *ptrs[] = { o.lbr, o.btree, o.bcell, o.bbase, o.rbrick };
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    o = SocLBricksDev();
-}
-
-void soc_brick_invalidate(int device)
-{
-    if (device >= 0 && device < 16) { g_ob[device].valid = false;  g_lb[device].valid = false;  g_lb[device].failed = false; }
-}
-
-static void soc_oct_release(int device)
-{
-    soc_lb_release(device);
-    SocOctBricks &o = g_ob[device];
-    if (o.DS) (void)hipFree(o.DS);
-    if (o.bcell) (void)hipFree(o.bcell);
-    if (o.bbase) (void)hipFree(o.bbase);
-    o = SocOctBricks();
-}
-
-
-static hipError_t soc_oct_build(int device, const SocGrid &G, int CAP, hipStream_t st, bool verbose)
-{
-    SocOctBricks &ob = g_ob[device];
-    if (ob.valid && ob.CAP == CAP && ob.cells == (size_t)G.CELLS && ob.dens_key == G.DENS) return hipSuccess;
+    if (ob.valid && ob.CAP == CAP && ob.cells == (size_t)G.CELLS) return hipSuccess;
+    ob.valid = false;
     std::vector<float> D((size_t)G.CELLS);
     BCHK(hipStreamSynchronize(st));
     BCHK(hipMemcpy(D.data(), G.DENS, (size_t)G.CELLS * 4, hipMemcpyDeviceToHost));
@@ -2168,13 +2130,10 @@ static hipError_t soc_oct_build(int device, const SocGrid &G, int CAP, hipStream
     if (NB < 1 || NB >= (1 << (32 - SOC_SLOT_BITS))) return hipErrorNotSupported;
     std::vector<float2> DS((size_t)G.CELLS);
     for (size_t i = 0; i < (size_t)G.CELLS; i++) { float y;  memcpy(&y, &B.slotmap[i], 4);  DS[i] = make_float2(D[i], y); }
-    BCHK(brick_alloc(&ob.DS, (size_t)G.CELLS));
-    BCHK(brick_alloc(&ob.bcell, B.bcell.size()));
-    BCHK(brick_alloc(&ob.bbase, B.bbase.size()));
-    BCHK(hipMemcpy(ob.DS, DS.data(), (size_t)G.CELLS * 8, hipMemcpyHostToDevice));
-    BCHK(hipMemcpy(ob.bcell, B.bcell.data(), B.bcell.size() * 4, hipMemcpyHostToDevice));
-    BCHK(hipMemcpy(ob.bbase, B.bbase.data(), B.bbase.size() * 4, hipMemcpyHostToDevice));
-    ob.NB = NB;  ob.CAP = CAP;  ob.cells = (size_t)G.CELLS;  ob.leaves = B.bcell.size();  ob.dens_key = G.DENS;
+    BCHK(upload(ob.DS, DS, st));
+    BCHK(upload(ob.bcell, B.bcell, st));
+    BCHK(upload(ob.bbase, B.bbase, st));
+    ob.NB = NB;  ob.CAP = CAP;  ob.cells = (size_t)G.CELLS;  ob.leaves = B.bcell.size();
     ob.valid = true;
     if (verbose)
         fprintf(stderr, "soc_brick: hierarchy of %d cells, %zu leaves -> %d bricks of <= %d leaves (mean %.0f)\n",
@@ -2185,15 +2144,14 @@ static hipError_t soc_oct_build(int device, const SocGrid &G, int CAP, hipStream
 // Bricks for the walk on brick-local hierarchies, and for the rays on single-level grids.  hipErrorNotSupported: the hierarchy cannot
 // be cut that way (a root cell with more than cap cells below it) -- the caller keeps the sweep that reads the hierarchy from global
 // memory; a single-level grid holds a cell without a positive density -- its rays stay with the direct kernel.
-static hipError_t soc_lb_build(int device, const SocGrid &G, int cap, hipStream_t st, bool verbose)
+static hipError_t soc_lb_build(SocLBricksDev &lb, const SocGrid &G, int cap, hipStream_t st, bool verbose)
 {
-    SocLBricksDev &lb = g_lb[device];
-    if (lb.cap == cap && lb.cells == (size_t)G.CELLS && lb.dens_key == G.DENS) {
+    if (lb.cap == cap && lb.cells == (size_t)G.CELLS) {
         if (lb.valid) return hipSuccess;
         if (lb.failed) return hipErrorNotSupported;
     }
-    soc_lb_release(device);
-    lb.cap = cap;  lb.cells = (size_t)G.CELLS;  lb.dens_key = G.DENS;
+    lb.valid = false;  lb.failed = false;
+    lb.cap = cap;  lb.cells = (size_t)G.CELLS;
     std::vector<float> D((size_t)G.CELLS);
     BCHK(hipStreamSynchronize(st));
     BCHK(hipMemcpy(D.data(), G.DENS, (size_t)G.CELLS * 4, hipMemcpyDeviceToHost));
@@ -2209,16 +2167,11 @@ static hipError_t soc_lb_build(int device, const SocGrid &G, int cap, hipStream_
     std::vector<int> bbase((size_t)NB + 1);
     for (int b = 0; b < NB; b++) bbase[b] = H.bricks[b].base;
     bbase[NB] = (int)H.btree.size();
-    BCHK(brick_alloc(&lb.lbr, (size_t)NB));
-    BCHK(brick_alloc(&lb.btree, H.btree.size()));
-    BCHK(brick_alloc(&lb.bcell, H.bcell.size()));
-    BCHK(brick_alloc(&lb.bbase, bbase.size()));
-    BCHK(brick_alloc(&lb.rbrick, H.rbrick.size()));
-    BCHK(hipMemcpy(lb.lbr, H.bricks.data(), (size_t)NB * sizeof(SocLBrick), hipMemcpyHostToDevice));
-    BCHK(hipMemcpy(lb.btree, H.btree.data(), H.btree.size() * 4, hipMemcpyHostToDevice));
-    BCHK(hipMemcpy(lb.bcell, H.bcell.data(), H.bcell.size() * 4, hipMemcpyHostToDevice));
-    BCHK(hipMemcpy(lb.bbase, bbase.data(), bbase.size() * 4, hipMemcpyHostToDevice));
-    BCHK(hipMemcpy(lb.rbrick, H.rbrick.data(), H.rbrick.size() * 4, hipMemcpyHostToDevice));
+    BCHK(upload(lb.lbr, H.bricks, st));
+    BCHK(upload(lb.btree, H.btree, st));
+    BCHK(upload(lb.bcell, H.bcell, st));
+    BCHK(upload(lb.bbase, bbase, st));
+    BCHK(upload(lb.rbrick, H.rbrick, st));
     lb.NB = NB;  lb.max_slots = H.max_slots;  lb.slots = H.btree.size();
     lb.valid = true;
     if (verbose)
@@ -2364,7 +2317,7 @@ static hipError_t plan_sweep(SocSweepPlan &pl, const SocGrid &G, const SocSim *S
 
 // Step 3: the bricks of the planned form and the sweep's arguments for them.  hipErrorNotSupported from the brick-local form: the
 // hierarchy cannot be cut that way (soc_lb_build).
-static hipError_t build_bricks(SocBrickArgs &A, const SocSweepPlan &pl, int device, const SocGrid &G, int LB, hipStream_t st, bool verbose)
+static hipError_t build_bricks(SocBrickArgs &A, const SocSweepPlan &pl, SocSweepState &sw, const SocGrid &G, int LB, hipStream_t st, bool verbose)
 {
     A = SocBrickArgs{};
     A.LB = LB;
@@ -2383,8 +2336,8 @@ static hipError_t build_bricks(SocBrickArgs &A, const SocSweepPlan &pl, int devi
     A.sib_thr = ldexpf(1.0f, k - 29);
     A.kexp = k - 30;
     if (pl.form == 3) {
-        BCHK(soc_lb_build(device, G, pl.capl, st, verbose));
-        const SocLBricksDev &lb = g_lb[device];
+        BCHK(soc_lb_build(sw.lb, G, pl.capl, st, verbose));
+        const SocLBricksDev &lb = sw.lb;
         A.NB = lb.NB;
         A.CAP = (lb.max_slots + 63) & ~63;                               // slots in LDS
         A.lbr = lb.lbr;  A.btree = lb.btree;  A.bcell = lb.bcell;  A.bbase = lb.bbase;  A.rbrick = lb.rbrick;
@@ -2392,8 +2345,8 @@ static hipError_t build_bricks(SocBrickArgs &A, const SocSweepPlan &pl, int devi
         return hipSuccess;
     }
     if (G.LEVELS > 15) return hipErrorNotSupported;                      // the level shares a packet word with slot and launch
-    BCHK(soc_oct_build(device, G, A.CAP, st, verbose));
-    const SocOctBricks &ob = g_ob[device];
+    BCHK(soc_oct_build(sw.ob, G, A.CAP, st, verbose));
+    const SocOctBricks &ob = sw.ob;
     A.NB = ob.NB;
     A.DS = ob.DS;  A.bcell = ob.bcell;  A.bbase = ob.bbase;
     return hipSuccess;
@@ -2514,26 +2467,32 @@ static hipError_t plan_kernel(SocSweepPlan &pl, SocBrickArgs &A, SocSweepSize &s
     return hipSuccess;
 }
 
-// Step 6: the device buffers, grown to the sweep's size
+// Step 6: the device buffers, grown to the sweep's size.  (The packet records first: bench.py's timed window holds the growth from the
+// warm-up's sweep to its own, and reserving them after the queues measured 0.08 % slower there.)
 static hipError_t reserve_buffers(SocBrickBuffers &bb, SocBrickArgs &A, const SocSweepSize &sz, const SocSca *sca, hipStream_t st)
 {
-    BCHK(grow(bb.cap_items, sz.count, st, &bb.pk, &bb.idq[0], &bb.idq[1], &bb.keyq, &bb.posq));
-    BCHK(grow(bb.cap_nq, sz.NQ, st, &bb.hist, &bb.off));
-    BCHK(grow(bb.cap_desc, sz.maxdesc, st, &bb.desc[0], &bb.desc[1]));
+    BCHK(bb.pk.reserve(sz.count, st));
+    for (DevBuf<uint32_t> *q : { &bb.idq[0], &bb.idq[1], &bb.keyq, &bb.posq }) BCHK(q->reserve(sz.count, st));
+    BCHK(bb.hist.reserve(sz.NQ, st));
+    BCHK(bb.off.reserve(sz.NQ, st));
+    BCHK(bb.desc[0].reserve(sz.maxdesc, st));
+    BCHK(bb.desc[1].reserve(sz.maxdesc, st));
     if (sca) {
-        BCHK(grow(bb.cap_park, sz.count, st, &bb.park));
+        BCHK(bb.park.reserve(sz.count, st));
         A.park = bb.park;
         A.sca = *sca;
     }
     if (A.LT && A.kopt_stride > 0) {                                   // (kopt_stride: set by build_bricks for sweeps with per-cell opacities)
-        BCHK(grow(bb.cap_kopt, (size_t)(A.NBQ / A.NB) * (size_t)A.kopt_stride, st, &bb.kopt));
+        BCHK(bb.kopt.reserve((size_t)(A.NBQ / A.NB) * (size_t)A.kopt_stride, st));
         A.kopt = bb.kopt;
     }
-    if (!bb.pack) BCHK(brick_alloc(&bb.pack, 1));
-    if (!bb.ndesc) { BCHK(brick_alloc(&bb.ndesc, 4));  BCHK(brick_alloc(&bb.total, 1));  BCHK(brick_alloc(&bb.admit, 1 + 3 * SOC_MAXLAUNCH)); }
+    BCHK(bb.pack.reserve(1, st));
+    BCHK(bb.ndesc.reserve(4, st));
+    BCHK(bb.total.reserve(1, st));
+    BCHK(bb.admit.reserve(1 + 3 * SOC_MAXLAUNCH, st));
     A.pk = bb.pk;  A.keyq = bb.keyq;  A.posq = bb.posq;  A.hist = bb.hist;  A.off = bb.off;  A.total = bb.total;
     A.admit = bb.admit;
-    A.first = (const uint32_t *)((const char *)bb.pack + offsetof(SocSimPack, first));
+    A.first = (const uint32_t *)((const char *)bb.pack.p + offsetof(SocSimPack, first));
     return hipSuccess;
 }
 
@@ -2602,23 +2561,23 @@ static hipError_t run_passes(int &passes, const SocSweepPlan &pl, SocBrickArgs A
 // tallies) share one sweep: more packets in flight per pass, and the passes in which one launch's last work items finish are filled
 // by the others.  hipErrorNotSupported: the launches cannot use bricks (the callers run the direct kernels); hipErrorInvalidValue:
 // the tuning is out of range, or the launches cannot share one sweep.
-hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *S, int nlaunch, const SocVariant &V, int LB,
+hipError_t soc_brick_run_pb(SocSweepState &sw, const SocGrid &G, const SocSim *S, int nlaunch, const SocVariant &V, int LB,
                             const SocBrickTune &tune, hipStream_t st, SocSweepResult *res, const SocSca *sca)
 {
     res->form = 0;
     BCHK(check_sca(S, nlaunch, V, sca));
-    if (device < 0 || device >= 16 || nlaunch < 1 || nlaunch > SOC_MAXLAUNCH) return hipErrorNotSupported;
+    if (nlaunch < 1 || nlaunch > SOC_MAXLAUNCH) return hipErrorNotSupported;
     SocSweepPlan pl;
     BCHK(plan_sweep(pl, G, S, nlaunch, V, tune, sca, true));
     SocBrickArgs A;
-    hipError_t e = build_bricks(A, pl, device, G, LB, st, tune.verbose != 0);
+    hipError_t e = build_bricks(A, pl, sw, G, LB, st, tune.verbose != 0);
     if (e == hipErrorNotSupported && pl.form == 3) {                  // a root cell with more cells below it than a brick holds:
         BCHK(plan_sweep(pl, G, S, nlaunch, V, tune, sca, false));     // the sweep that reads the hierarchy from global memory (rays: none)
         // (launches deferred for the brick-local form share OPT arrays, soc_capi.hip: that sweep cannot stride through them, and the
         // caller runs them through the direct kernels)
         for (int l = 1; l < nlaunch && V.abu; l++)
             if ((long long)(S[l].OPT - S[0].OPT) != l * (long long)(S[1].OPT - S[0].OPT)) return hipErrorNotSupported;
-        e = build_bricks(A, pl, device, G, LB, st, tune.verbose != 0);
+        e = build_bricks(A, pl, sw, G, LB, st, tune.verbose != 0);
     }
     BCHK(e);
     SocSimPack K{};
@@ -2626,9 +2585,9 @@ hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *S, int n
     BCHK(pack_launches(K, sz, A, pl, G, S, nlaunch, tune));
     if (K.n == 0) { res->passes = 0;  return hipSuccess; }            // no launch has work items
     BCHK(plan_kernel(pl, A, sz, K, tune));
-    BCHK(reserve_buffers(g_bb[device], A, sz, sca, st));
+    BCHK(reserve_buffers(sw.bb, A, sz, sca, st));
     int passes = 0;
-    BCHK(run_passes(passes, pl, A, sz, G, K, g_bb[device], tune, st));
+    BCHK(run_passes(passes, pl, A, sz, G, K, sw.bb, tune, st));
     *res = SocSweepResult{ passes, pl.form, soc_variant_code(pl) };
     return hipSuccess;
 }

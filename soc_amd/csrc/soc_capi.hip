@@ -128,7 +128,7 @@ int flush_pending(soc_ctx *c)
                              : (V.octree && todo.size() == 1 && c->exec_mode < 0 && !(lt_capable(c, V.abu != 0) && items >= SOC_LT_LONE_LAUNCH));
     hipError_t e = hipErrorNotSupported;
     if (!direct)
-        e = soc_brick_run_pb(c->device, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, c->tune, c->stream, &c->last, rays ? &c->view : nullptr);
+        e = soc_brick_run_pb(*c->sweep, c->G, todo.data(), (int)todo.size(), V, c->brick_log2, c->tune, c->stream, &c->last, rays ? &c->view : nullptr);
     // (per-cell opacities: launches deferred for the brick-local form whose hierarchy cannot be cut into bricks after all)
     if (direct || ((rays || V.abu) && e == hipErrorNotSupported)) {
         for (const SocSim &S : todo) {
@@ -147,8 +147,6 @@ extern "C" {
 const char *soc_version(void) { return "soc_hip 0.1 (gfx950)"; }
 
 const char *soc_last_error(const soc_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
-
-static int g_handles[64];              // live handles per GPU: the brick scratch of a GPU goes with the last one
 
 int soc_create(int device, soc_ctx **out)
 {
@@ -191,7 +189,6 @@ int soc_create(int device, soc_ctx **out)
         return r;
     }
     c->stream = c->own_stream;
-    if (device < 64) g_handles[device]++;
     // seed tables: T[k][b] = G^(b*256^k) mod M with G = A^(2^38) mod M  (soc_rng.h)
     std::vector<uint64_t> tab(1024);
     soc_build_seed_table(tab.data());
@@ -214,11 +211,10 @@ void soc_destroy(soc_ctx *c)
     (void)flush_pending(c);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->device >= 64 || --g_handles[c->device] <= 0) soc_brick_release(c->device);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;                                               // (every DevBuf of the handle frees what it owns)
+    delete c;                                               // (every DevBuf of the handle frees what it owns, those of its sweeps included)
 }
 
 int64_t soc_device_bytes(void) { return soc_dev_bytes.load(); }
@@ -302,7 +298,7 @@ int soc_set_grid(soc_ctx *c, int NX, int NY, int NZ, int LEVELS, const int32_t *
     }
     c->G = G;
     c->have_grid = true;
-    soc_brick_invalidate(c->device);
+    soc_sweep_invalidate(c->sweep);
     HIPCHK(c, soc_launch_parents(c->G, c->dPAR, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SOC_OK;
@@ -364,7 +360,7 @@ int soc_set_tuning(soc_ctx *c, const char *name, int value)
         { "abu_local", &c->tune.abu_local } };
     for (auto &t : tab)
         if (!strcmp(name, t.n)) {
-            if (t.p == &c->tune.CAP && value != c->tune.CAP) soc_brick_invalidate(c->device);
+            if (t.p == &c->tune.CAP && value != c->tune.CAP) soc_sweep_invalidate(c->sweep);
             *t.p = value;
             return SOC_OK;
         }
@@ -795,7 +791,7 @@ static bool use_sweep(const soc_ctx *c, SimKind kind, const SocVariant &V, long 
         *why = (!c->have_view || c->view.NDIR == 0) ? "no view"
              : (c->msf_ndust > 1) ? "several scattering functions (WITH_MSF) need the direct kernel"
              : (c->dOPT != nullptr) ? "per-cell opacities need the direct kernel"
-             : (!(lt_capable(c, false) || cart_capable(c)) || c->device >= 16)
+             : !(lt_capable(c, false) || cart_capable(c))
                    ? "the grid is not one the sweep of rays takes (a hierarchy of 2-8 levels with Index() in double, or a single-level grid below 4096 cells per edge)"
              : nullptr;
         if (cart_capable(c))                                // (the launches of a batch are deferred where a batch can pay; flush_pending counts them)
@@ -807,7 +803,7 @@ static bool use_sweep(const soc_ctx *c, SimKind kind, const SocVariant &V, long 
     const long long nb = (long long)((c->G.NX + B - 1) / B) * ((c->G.NY + B - 1) / B) * ((c->G.NZ + B - 1) / B);
     // the brick sweep applies: mirror, with_int 2 and region-of-interest records need the brick-local sweep (packets of a loaded
     // record, SOURCE 3: any sweep); cell emission also needs USE_EMWEIGHT 0/1 and, with ALI, the brick-local sweep without with_int 2
-    const bool ok = nb <= (1 << 18) && c->G.LEVELS <= 15 && c->device < 16
+    const bool ok = nb <= (1 << 18) && c->G.LEVELS <= 15
                     && (c->mirror == 0 || lt) && (c->with_int != 2 || lt)
                     && (kind == SIM_HP || !c->roi.save || (lt && c->mirror == 0))
                     && (kind != SIM_CL || (c->use_emweight != 2 && (!c->with_ali || (lt && c->with_int != 2))));
@@ -856,7 +852,7 @@ static int route_sim(soc_ctx *c, SimKind kind, SocSim &S, const SocVariant &V, l
         return SOC_OK;
     }
     if (!sweep) return run_direct(c, S, V);
-    hipError_t e = soc_brick_run_pb(c->device, c->G, &S, 1, V, c->brick_log2, c->tune, c->stream, &c->last, S.SCAKIND ? &c->view : nullptr);
+    hipError_t e = soc_brick_run_pb(*c->sweep, c->G, &S, 1, V, c->brick_log2, c->tune, c->stream, &c->last, S.SCAKIND ? &c->view : nullptr);
     if (e == hipErrorNotSupported && S.SCAKIND && c->exec_mode != 1)
         return run_direct(c, S, V);                         // rays: the direct kernel where the sweep does not apply after all
     if (e != hipSuccess) return fail(c, SOC_ERR_HIP, "%s: brick sweep failed: %s", who, hipGetErrorString(e));

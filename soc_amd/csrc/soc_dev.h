@@ -422,10 +422,13 @@ struct SocSweepResult {
 };
 
 // brick-sweep execution (soc_brick.hip): LDS-resident tallies, packets sorted by brick; sca: the launches are ones of the
-// scattered-light kernels (rays, soc_sca_events)
-hipError_t soc_brick_run_pb(int device, const SocGrid &G, const SocSim *S, int nlaunch, const SocVariant &V, int LB,
+// scattered-light kernels (rays, soc_sca_events).  SocSweepState: the packet records, queues and bricks that a handle's sweeps keep
+// on the device, every one an owning DevBuf; soc_sweep_delete frees them.
+struct SocSweepState;
+SocSweepState *soc_sweep_new();
+void soc_sweep_delete(SocSweepState *sw);
+void soc_sweep_invalidate(SocSweepState *sw);      // the grid changed: its bricks are rebuilt at the next sweep (nothing is freed)
+hipError_t soc_brick_run_pb(SocSweepState &sw, const SocGrid &G, const SocSim *S, int nlaunch, const SocVariant &V, int LB,
                             const SocBrickTune &tune, hipStream_t st, SocSweepResult *res, const struct SocSca *sca = nullptr);
-void soc_brick_release(int device);
-void soc_brick_invalidate(int device);      // the grid changed: bricks of a hierarchy are rebuilt at the next sweep
 
 #endif

@@ -1,62 +1,13 @@
 // soc_host.h -- what the host units of libsoc_hip.so share (soc_capi.hip, soc_capi_post.hip, soc_capi_a2e.hip, soc_capi_library.hip, soc_capi_probe.hip):
-// the handle, the one type that owns device memory, and the error and flush idioms.  Kernels do not include it.
+// the handle, the error and flush idioms.  Every device allocation of a handle is a DevBuf (soc_devbuf.h) that the handle owns: its
+// members, and the packet records, queues and bricks of its brick sweeps (SocSweepState, soc_brick.hip).  Kernels do not include it.
 #pragma once
 #include "../../include/soc_hip.h"
 #include "soc_dev.h"
+#include "soc_devbuf.h"
 
-#include <atomic>
 #include <string>
 #include <vector>
-
-#define SOC_HIDDEN __attribute__((visibility("hidden")))
-
-// bytes of device memory that owning DevBufs hold, all handles of the process together (soc_device_bytes)
-extern SOC_HIDDEN std::atomic<int64_t> soc_dev_bytes;
-
-// n elements of device memory at p: the library's own (owned: freed by release() and by the destructor) or a caller's (bind)
-template <typename T>
-struct DevBuf {
-    T     *p = nullptr;
-    size_t n = 0;                      // capacity in elements (an owned buffer of 0 elements is allocated with one)
-    bool   owned = false;
-
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n), owned(o.owned) { o.p = nullptr;  o.n = 0;  o.owned = false; }
-    DevBuf &operator=(DevBuf &&o) noexcept
-    {
-        if (this != &o) { release();  p = o.p;  n = o.n;  owned = o.owned;  o.p = nullptr;  o.n = 0;  o.owned = false; }
-        return *this;
-    }
-    ~DevBuf() { release(); }
-
-    operator T *() const { return p; }
-    explicit operator bool() const { return p != nullptr; }
-    size_t bytes() const { return (n ? n : 1) * sizeof(T); }
-
-    void release()
-    {
-        if (p && owned) { (void)hipFree(p);  soc_dev_bytes -= (int64_t)bytes(); }
-        p = nullptr;  n = 0;  owned = false;
-    }
-    // a caller's memory: used, never freed
-    void bind(T *ptr, size_t count) { release();  p = ptr;  n = count;  owned = false; }
-    // exactly `need` elements of the library's own, whatever is held; the contents are not kept.  The stream drains before a buffer
-    // goes (a launch in flight may still read it); a failed wait leaves it in place
-    hipError_t reset(size_t need, hipStream_t stream)
-    {
-        if (p) { hipError_t e = hipStreamSynchronize(stream);  if (e != hipSuccess) return e; }
-        release();
-        hipError_t e = hipMalloc((void **)&p, (need ? need : 1) * sizeof(T));
-        if (e != hipSuccess) { p = nullptr;  return e; }
-        n = need;  owned = true;
-        soc_dev_bytes += (int64_t)bytes();
-        return hipSuccess;
-    }
-    // at least `need` elements: nothing to do when they are there, else reset(need)
-    hipError_t reserve(size_t need, hipStream_t stream) { return n >= need ? hipSuccess : reset(need, stream); }
-};
 
 struct soc_ctx {
     int device = 0;
@@ -145,6 +96,8 @@ struct soc_ctx {
     int exec_mode = -1, brick_log2 = 4;
     SocSweepResult last;                          // the last sweep's passes and form; variant: soc_last_variant, the absorption kernel last launched (-1: none yet)
     SocBrickTune tune{};
+    SocSweepState *sweep = soc_sweep_new();       // what the handle's brick sweeps keep on the device (soc_brick.hip); goes with the handle
+    ~soc_ctx() { soc_sweep_delete(sweep); }
     // equilibrium temperature / emission (soc_emit.hip)
     DevBuf<float> dT, dTTT, dEbuf, dEF;
     bool   have_T = false;

@@ -231,8 +231,8 @@ def load_library(path=None):
 
 
 def device_bytes():
-    """Bytes of device memory the engines of this process hold (soc_device_bytes): their own allocations, not a caller's bound
-    tensors, not the scratch of the brick sweep."""
+    """Bytes of device memory the engines of this process hold (soc_device_bytes): their own allocations, the packet records, queues
+    and bricks of their brick sweeps included; not a caller's bound tensors."""
     return int(load_library().soc_device_bytes())
 
 

@@ -1,7 +1,9 @@
 """Who owns the device memory of a handle, as assertions on soc_device_bytes: everything a handle allocated goes with it, paired
 calls give back what they took, buffers grow once and stay, a caller's tensor is borrowed and never freed, and a handle that
 changed its grid behaves like a new one.  Every count follows from the sizes the test passes (an owned buffer of n elements is
-n * sizeof(element) bytes); nothing is measured."""
+n * sizeof(element) bytes); nothing is measured.  The memory of the brick sweeps (packet records, queues, bricks) is the handle's
+too: it is counted, it goes with the handle, and two handles on one GPU do not disturb each other -- its sizes belong to the plan
+of a sweep, so the tests of it assert differences and no formulas."""
 import math
 
 import numpy as np
@@ -9,6 +11,8 @@ import pytest
 
 from soc_amd import launch, synth
 from soc_amd.lib import Engine, SocError, device_bytes
+from test_gpu_noncubic import cloud as noncubic, oracle, report, sources
+from util import assert_tally_close, run_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -234,3 +238,116 @@ def test_regrid(eng):
         fresh.close()
     assert res[0][1] == res[1][1] and res[0][1]["tally_events"] > 0
     assert np.array_equal(res[0][0].view(np.uint32), res[1][0].view(np.uint32))
+    n0 = device_bytes()
+    eng.set_exec(1, 2)                                                   # ... and sweeps the new grid: bricks of the new hierarchy, its own
+    eng.zero(0)
+    eng.stats(reset=True)
+    launch_ps(eng)
+    assert eng.last_passes() > 0 and eng.last_form() == 2 and device_bytes() > n0
+    assert eng.stats()["tally_events"] == res[0][1]["tally_events"]      # the packets of the direct launches, walked again
+    assert_tally_close(eng.read_tally(0), res[0][0], rtol=1e-5)         # (to fp32 summation order, the bar of the sweeps everywhere)
+
+
+# ---- the memory of the brick sweeps: the smallest grid the project has for each form (tests/test_gpu_noncubic.py) ----
+def sweep_scalar(eng, cloud):
+    return lambda: launch_ps(eng)
+
+
+def sweep_rays(eng, cloud):
+    """scattered light as a sweep of rays: the parked packets and the bricks of a single-level grid"""
+    ODIR, RA, DE = view()
+    eng.sca_set_view(ODIR, RA, DE, NPIX, 0.6, centre(cloud))
+    eng.sca_zero()
+    return lambda: eng.sca_sim_pb(0, 0, 1, 0.47, 0.0, PSPOS=PSPOS, PS=PS, GLOBAL=ITEMS)
+
+
+def sweep_abu_local(eng, cloud):
+    """per-cell opacities on the brick-local walk: the opacities in brick-slot order"""
+    rr = np.random.default_rng(11)
+    eng.set_tuning(abu_local=1)
+    eng.set_opt(np.stack([2.0e-3 * rr.uniform(0.5, 2, cloud.CELLS), 4.0e-3 * rr.uniform(0.5, 2, cloud.CELLS)], axis=1).astype(np.float32))
+    return lambda: launch_ps(eng)
+
+
+SWEEPS = {                                                             # grid, the form of the sweep, its preparation
+    "cartesian": (cart8, 1, sweep_scalar),
+    "global_tree": (lambda: noncubic("oct759"), 2, sweep_scalar),
+    "brick_local": (lambda: noncubic("oct104x6x5"), 3, sweep_scalar),
+    "rays": (cart8, 3, sweep_rays),
+    "abu_local": (lambda: noncubic("oct104x6x5"), 3, sweep_abu_local),
+}
+
+
+@pytest.mark.parametrize("case", sorted(SWEEPS))
+def test_sweep_memory_goes_with_the_handle(case):
+    grid, form, prepare = SWEEPS[case]
+    cloud = grid()
+    before = device_bytes()
+    e = Engine(0)
+    try:
+        setup(e, cloud)
+        e.set_exec(1, 2)
+        run = prepare(e, cloud)
+        n0 = device_bytes()
+        run()
+        assert e.last_passes() > 0 and e.last_form() == form, (e.last_passes(), e.last_form())
+        n1 = device_bytes()
+        assert n1 > n0                                                # the sweep's buffers and bricks are counted
+        run()
+        assert e.last_passes() > 0 and e.last_form() == form
+        assert device_bytes() == n1                                   # ... and stay as they are for the same sweep again
+    finally:
+        e.close()
+    assert device_bytes() == before
+
+
+def oracle_sweep(eng, oracle_soc, name, src, form, first):
+    """A forced sweep of a source of tests/test_gpu_noncubic.py, held to the oracle as `check` there holds it: the same event count,
+    tallies to fp32 summation order.  first: the whole of run_engine, soc_set_grid included; else the launch alone, on the bricks
+    the handle has."""
+    kind, job, g0, g1 = sources(name)[src]
+    assert kind == 0
+    T, I, n = oracle(oracle_soc, (name, src), job, kind, gid0=g0, gid1=g1)
+    assert n > 1000 and (T > 0).sum() > 900
+    if first:
+        Tg, Ig, st = run_engine(eng, job, kind, gid_first=g0, gid_count=g1 - g0, exec_mode=1, brick_log2=2)
+    else:
+        eng.zero(0)
+        eng.zero(1)
+        eng.stats(reset=True)
+        eng.sim_pb(job.SOURCE, job.PACKETS, job.BATCH, job.SEED, job.BG, job.TW, PSPOS=job.PSPOS[:, :3], PS=job.PS,
+                   XPS=(job.XPS_NSIDE, job.XPS_SIDE, job.XPS_AREA), GLOBAL=job.GLOBAL, gid_first=g0, gid_count=g1 - g0)
+        eng.sync()
+        Tg, Ig, st = eng.read_tally(0), eng.read_tally(1), eng.stats()
+    assert eng.last_passes() > 0 and eng.last_form() == form, (eng.last_passes(), eng.last_form())
+    report("%s %s form %d" % (name, src, form), Tg, T, st["tally_events"])
+    assert st["tally_events"] == n, "trajectories diverged from the oracle"
+    assert_tally_close(Tg, T, rtol=1e-5)
+    if job.WITH_INT:
+        assert_tally_close(Ig, I, rtol=1e-5)
+
+
+def test_handles_on_one_gpu_do_not_disturb_each_other(oracle_soc):
+    A, B = Engine(0), None
+    try:
+        oracle_sweep(A, oracle_soc, "oct104x6x5", "ps", 3, True)
+        held = device_bytes()                                         # (B opens after this: all it ever holds is in b_held)
+        B = Engine(0)
+        oracle_sweep(B, oracle_soc, "oct759", "ps", 2, True)
+        b_held = device_bytes() - held
+        assert b_held > 0
+        oracle_sweep(A, oracle_soc, "oct104x6x5", "ps", 3, False)
+        assert device_bytes() == held + b_held                        # A built and grew nothing: its bricks were still its own
+        B.set_cloud(oct4())                                           # (marks B's bricks stale and frees none of them: B holds what it held,
+        b_held = device_bytes() - held                                #  with the arrays of the new grid in place of the old)
+        oracle_sweep(A, oracle_soc, "oct104x6x5", "ps", 3, False)
+        assert device_bytes() == held + b_held
+        B.close()
+        B = None
+        assert device_bytes() == held
+        oracle_sweep(A, oracle_soc, "oct104x6x5", "ps", 3, False)
+        assert device_bytes() == held
+    finally:
+        A.close()
+        if B is not None:
+            B.close()
