@@ -97,6 +97,11 @@ typedef uint32_t soc_u2v __attribute__((ext_vector_type(2)));
 // operation counts as an LDS operation too (lgkmcnt) -- every wait for an LDS read then waits for the global loads in flight
 // as well, the prefetched packet records included.  The walk's loop casts its pointers to the global address space.
 #define SOC_GLOBAL __attribute__((address_space(1)))
+// (soc_lbrick_walk) entry `slot` of one of the chunk's queue arrays: a slot stays below SOC_LBRICK_PMAX, so its byte offset has 32 bits and the access takes the
+// array's base from scalar registers -- no 64-bit address per lane
+#define SOC_CHUNK_AT(base, slot) ((decltype(base))((SOC_GLOBAL const char *)(base) + (uint32_t)((uint32_t)(slot) << 2)))
+// (soc_lbrick_walk, swap arm) a field of the prefetched record becomes the lane's own: a move the compiler cannot fold into the record's register
+#define SOC_TAKE(dst, src) asm volatile("v_mov_b32 %0, %1" : "=v"(dst) : "v"(src))
 __device__ __forceinline__ float4 soc_ld4(const float4 *p) { const soc_f4v v = SOC_NT_LOAD((const soc_f4v *)p);  return make_float4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ void soc_st4(float4 *p, float4 a) { soc_f4v v = { a.x, a.y, a.z, a.w };  SOC_NT_STORE(v, (soc_f4v *)p); }
 
@@ -787,20 +792,23 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                 if (oc - 1u < (unsigned)SOC_OC_NONE) {
                     // A lane holds three packets: the one it walks, the next one, whose record was asked for when the
                     // current one was taken up, and the one after that, of which the id has been asked for -- each a
-                    // visit ahead of its use, so nothing in this arm waits for global memory.  The chunk itself is never
-                    // copied: ids, queues and places stay in global memory (idq, keyq, posq), so a chunk may be the whole
-                    // queue of the brick.
-                    // (1) the lane reserves the packet after next: one LDS atomic per wave, neighbouring lanes read neighbouring ids
-                    const unsigned long long am = __ballot(true);
-                    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
-                    int base = 0;
-                    if (rank == 0) base = atomicAdd(&sCtl[0], __popcll(am));
-                    asm volatile("" :: "v"(na), "v"(nb), "v"(nc), "v"(ndzw), "v"(nnwid));      // what is in flight has landed: no later use waits behind the stores below
+                    // visit ahead of its use.  The only wait for global memory in this arm is the one at its top, for what
+                    // the previous entry asked for; what this entry asks for lands in the registers that carry it to the
+                    // next entry.  The chunk itself is never copied: ids, queues and places stay in global memory (idq,
+                    // keyq, posq), so a chunk may be the whole queue of the brick.
+                    // (1) the lane reserves the packet after next.  One LDS atomic per wave: the compiler aggregates the lanes'
+                    // additions (first active lane adds their number, every lane gets the old value + its rank among the
+                    // active lanes), so neighbouring lanes read neighbouring ids; aggregated here as well the arm did it twice.
+                    // (Without that pass the result is still right, but every lane issues its own ds_add_rtn.  Likewise the place of the
+                    // arm's s_waitcnt vmcnt is the compiler's choice.  After a change of compiler or of this arm, tools/isa_loop_count.py
+                    // shows both: one ds_add_rtn in the arm, and no wait that follows loads of its own arm -- profiles/swap_land_static_mix.txt)
+                    const int n_res = atomicAdd(&sCtl[0], 1);
                     // (2) what the prefetched packet needs from LDS -- its launch's constants and, for a root-level packet, the root cell
                     // it is in (or comes into: ARRIVE) -- is asked for now; addresses from a stale record (no packet) stay inside the arrays
                     const int  n_cz = __float_as_int(nc.w);
                     const int  n_lq = (int)(((uint32_t)n_cz >> SOC_LQ_SHIFT) & (SOC_MAXLAUNCH - 1));
                     const bool n_arrive = (ndzw.y & SOC_LT_ARRIVE) != 0u;
+                    const int  n_level = (int)(ndzw.x >> 29);
                     const int  n_ix = n_arrive ? (int)soc_floorf(na.x) : __float_as_int(nc.y), n_iy = n_arrive ? (int)soc_floorf(na.y) : __float_as_int(nc.z),
                                n_iz = n_arrive ? (int)soc_floorf(na.z) : (n_cz & ((1 << SOC_LQ_SHIFT) - 1));
                     int n_s2 = SOC_MAD24(SOC_MAD24(n_iz - KB.z0, KB.by, n_iy - KB.y0), KB.bx, n_ix - KB.x0);
@@ -815,7 +823,7 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                         // wait for all loads in flight, 19 % of the wave's cycles; loaded here, every entry of this arm one L2 latency)
                         { const soc_f4v v = { px, py, pz, photons };  SOC_NT_STORE(v, (SOC_GLOBAL soc_f4v *)&q->A); }
                         { const soc_f4v v = { tau, __int_as_float(cx), __int_as_float(cy), __int_as_float(cz | (lq << SOC_LQ_SHIFT)) };  SOC_NT_STORE(v, (SOC_GLOBAL soc_f4v *)&q->C); }
-                        q->D.z = (dz & 0x1fffffffu) | ((uint32_t)level << 29);
+                        q->D.z = dz | ((uint32_t)level << 29);                    // (dz: without the level bits since the take-up)
                         // (a step that another brick or the slow-step queue completes: old cell + advanced position)
                         q->D.w = dw | (((oc == SOC_OC_LEAVE) | (oc == SOC_OC_SLOW)) ? SOC_LT_ARRIVE : 0u);
                         if (LIM) SOC_NT_STORE(free_path, &q->B.w);                 // (the distance a peel-off ray has left)
@@ -825,50 +833,57 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                         // brick up -- retirement
                         const int evk = A.NBQ + A.EQ * lq + (int)SOC_OC_EVQ_OF(oc);
                         const int key = (oc == SOC_OC_OWN) ? D.brick : ((oc == SOC_OC_LEAVE) ? kl : ((oc == SOC_OC_LOST) ? (NQ - 1) : evk));
-                        SOC_NT_STORE((uint32_t)key, &keyq_c[cslot]);              // its rank in that queue is settled after the walk, for all packets at once
+                        SOC_NT_STORE((uint32_t)key, SOC_CHUNK_AT(keyq_c, cslot));              // its rank in that queue is settled after the walk, for all packets at once
                     }
-                    // (4) the prefetched packet becomes the current one
+                    // (4) the prefetched packet becomes the current one: EVERYTHING that reads its record (na, nb, nc, ndzw) comes before
+                    // the loads of (5), so that those can land in the very registers the record is carried in.  The nine fields that are
+                    // taken as they are get a move of their own (SOC_TAKE): a plain assignment leaves the choice to the compiler, which
+                    // kept the old record where it was, loaded the new one elsewhere, waited for it at the end of the arm and copied it back.
+                    // (all lanes of the arm: what a lane without a prefetched packet decodes here is never used)
                     have = nhave;
                     wid = nwid;  cslot = nslot;
-                    {   // (all lanes of the arm: what a lane without a prefetched packet decodes here is never used)
-                        dz = ndzw.x;  dw = ndzw.y & ~SOC_LT_ARRIVE;
-                        px = na.x;  py = na.y;  pz = na.z;  photons = na.w;
-                        ux = nb.x;  uy = nb.y;  uz = nb.z;  free_path = nb.w;
-                        rux = 1.0f / ux;  ruy = 1.0f / uy;  ruz = 1.0f / uz;
-                        gx = (ux > 0.0f) ? (1.0f + SOC_PEPS) : -SOC_PEPS;  gy = (uy > 0.0f) ? (1.0f + SOC_PEPS) : -SOC_PEPS;  gz = (uz > 0.0f) ? (1.0f + SOC_PEPS) : -SOC_PEPS;
-                        tau = nc.x;  cx = __float_as_int(nc.y);  cy = __float_as_int(nc.z);  cz = n_cz & ((1 << SOC_LQ_SHIFT) - 1);
-                        lq = n_lq;                                                // the launch of the work item
-                        level = (int)(dz >> 29);
-                        kabs = l4.x;  ksca = l4.y;  tw = l4.z;  nonudge = RAY || ((__float_as_int(l4.w) & 1) != 0);
-                        if (LIM) dblstep = (__float_as_int(l4.w) & 2) != 0;
-                        nvisit = 0;
-                        oc = have ? SOC_OC_STAY : oc;
-                        slot = -1;  obase = -1;
+                    SOC_TAKE(px, na.x);  SOC_TAKE(py, na.y);  SOC_TAKE(pz, na.z);  SOC_TAKE(photons, na.w);
+                    SOC_TAKE(ux, nb.x);  SOC_TAKE(uy, nb.y);  SOC_TAKE(uz, nb.z);  SOC_TAKE(free_path, nb.w);
+                    SOC_TAKE(tau, nc.x);
+                    dz = ndzw.x & 0x1fffffffu;  dw = ndzw.y & ~SOC_LT_ARRIVE;
+                    level = n_level;
+                    lq = n_lq;                                                    // the launch of the work item
+                    kabs = l4.x;  ksca = l4.y;  tw = l4.z;  nonudge = RAY || ((__float_as_int(l4.w) & 1) != 0);
+                    if (LIM) dblstep = (__float_as_int(l4.w) & 2) != 0;
+                    nvisit = 0;
+                    oc = have ? SOC_OC_STAY : oc;
+                    obase = -1;
+                    {
                         // The first pass of the packet through the Index() part finds its cell in this brick: the second half of
                         // the step that brought it here (ARRIVE), or the cell its coordinates name.  A root-level packet in (or
                         // into) a root cell that is not refined -- the common case -- is settled here.
                         // (with the record of packets entering ROI an arrival is always finished in the step arm, where the test for it sits)
                         // (a single-level grid: always -- every cell is a root cell with a density)
-                        const bool settled = CART || ((level == 0) && (!n_arrive || ((n_rec > 0.0f) && !(!RAY && A.roi_on))));
+                        const bool settled = CART || ((n_level == 0) && (!n_arrive || ((n_rec > 0.0f) && !(!RAY && A.roi_on))));
                         what = settled ? SOC_LTM_STEP : (n_arrive ? SOC_LTM_ARRIVE : SOC_LTM_PLACE);
-                        slot = settled ? n_s2 : slot;  dens = settled ? n_rec : dens;
-                        cx = settled ? n_ix : cx;  cy = settled ? n_iy : cy;  cz = settled ? n_iz : cz;
+                        slot = settled ? n_s2 : -1;  dens = settled ? n_rec : dens;
+                        cx = settled ? n_ix : __float_as_int(nc.y);  cy = settled ? n_iy : __float_as_int(nc.z);  cz = settled ? n_iz : (n_cz & ((1 << SOC_LQ_SHIFT) - 1));
                     }
                     // (5) the record of the packet after it (its id has arrived), and the id of the one after that
                     nhave = nnhave;
                     nwid = nnwid;  nslot = nnslot;
-                    asm volatile("" : "+v"(nwid) :: "memory");                // (the copy is made HERE: nnwid is dead below and the load at the end of the arm lands
-                                                                              //  in its register; left to itself the compiler loads into a fresh register, waits for
-                                                                              //  EVERY load in flight -- the records just asked for -- and copies: 14 % of the cycles)
+                    // (the copy of the id is made HERE: nnwid is dead below and the load at the end of the arm lands in its register.  The
+                    //  record is dead as well: redefined here, what a lane without a prefetched packet keeps and what the others load
+                    //  are one set of registers.  What (4) computed from the record is an input, or the compiler computes it below
+                    //  from a copy of the record that it keeps for the purpose)
+                    asm volatile("" : "+v"(nwid), "+v"(na), "+v"(nb), "+v"(nc), "+v"(ndzw) : "v"(cx), "v"(cy), "v"(cz), "v"(dz), "v"(dw), "v"(level), "v"(what) : "memory");
                     if (nhave) {
                         // (vector-typed loop variables: the loads land in the registers that carry the values around the loop)
                         const SOC_GLOBAL SocPk2 *q = pk + nwid;
                         na = SOC_NT_LOAD((const SOC_GLOBAL soc_f4v *)&q->A);  nb = SOC_NT_LOAD((const SOC_GLOBAL soc_f4v *)&q->B);  nc = SOC_NT_LOAD((const SOC_GLOBAL soc_f4v *)&q->C);
                         ndzw = *(const SOC_GLOBAL soc_u2v *)&q->D.z;
                     }
-                    nnslot = __builtin_amdgcn_readfirstlane(base) + rank;
+                    nnslot = n_res;
                     nnhave = nnslot < D.count;
-                    if (nnhave) nnwid = SOC_NT_LOAD(&idq_c[nnslot]);
+                    if (nnhave) nnwid = SOC_NT_LOAD(SOC_CHUNK_AT(idq_c, nnslot));
+                    // (the reciprocals read the copies: the record's registers belong to the loads by now)
+                    rux = 1.0f / ux;  ruy = 1.0f / uy;  ruz = 1.0f / uz;
+                    gx = (ux > 0.0f) ? (1.0f + SOC_PEPS) : -SOC_PEPS;  gy = (uy > 0.0f) ? (1.0f + SOC_PEPS) : -SOC_PEPS;  gz = (uz > 0.0f) ? (1.0f + SOC_PEPS) : -SOC_PEPS;
                     if (!have) oc = (nhave | nnhave) ? SOC_OC_NONE : SOC_OC_IDLE;      // (the first two turns of a lane only reserve)
                 }
             }

@@ -4,7 +4,9 @@
     python tools/isa_loop_count.py FILE.s KERNEL_SUBSTRING
 
 Finds the kernel whose (mangled) name contains KERNEL_SUBSTRING, takes the depth-1 loop that holds the tally's ds_add_f32 and counts VALU / SALU /
-LDS / VMEM instructions of the basic blocks that belong to it, split at the first v_fract_f32 (swap arm | step arm)."""
+LDS / VMEM instructions of the basic blocks that belong to it, split at the first v_fract_f32 (swap arm | step arm).  Per arm it then lists
+every s_waitcnt that names vmcnt, with the global loads and stores issued before it in the same arm (in program order): a wait that follows
+loads of its own arm with a count below the accesses issued since waits for memory the arm asked for itself."""
 import re
 import sys
 
@@ -19,13 +21,14 @@ def main():
     blocks, cur = [], None
     for l in body:
         if re.match(r"^(\.LBB\w+:|; %bb\.\d+:)", l):
-            cur = {"head": l, "notes": l, "ins": []}
+            cur = {"head": l, "notes": l, "ins": [], "full": []}
             blocks.append(cur)
         elif cur is not None:
             if l.strip().startswith(";"):
                 cur["notes"] += " " + l
             elif l.strip() and not l.strip().startswith("."):
                 cur["ins"].append(l.strip().split()[0])
+                cur["full"].append(l.strip())
     loops = {}
     for b in blocks:
         m = re.search(r"=>\s*This Loop Header: Depth=1", b["notes"])
@@ -42,14 +45,28 @@ def main():
     order = [b for b in blocks if b in loops[name]]
     seen_fract = False
     part = {"swap": [], "step": []}
+    full = {"swap": [], "step": []}
     for b in order:
         if any(i.startswith("v_fract") for i in b["ins"]) or any(i.startswith("v_trunc") for i in b["ins"]):
             seen_fract = True
         part["step" if seen_fract else "swap"] += b["ins"]
+        full["step" if seen_fract else "swap"] += b["full"]
     for k, ins in part.items():
         c = lambda p: sum(1 for i in ins if re.match(p, i))
         print("%-5s VALU %4d  SALU %4d  LDS %3d  VMEM %3d   (v_mov %d, v_cndmask %d, v_cmp %d)" % (
             k, c(r"v_"), c(r"s_"), c(r"ds_"), c(r"(global|flat|buffer)_"), c(r"v_mov"), c(r"v_cndmask"), c(r"v_cmp")))
+    for k, ins in full.items():
+        print("%-5s ds_add_rtn (the reservation of the swap arm: one per wave when the compiler aggregates the lanes' additions): %d" % (
+            k, sum(1 for l in ins if l.startswith("ds_add_rtn"))))
+        loads = stores = 0
+        for n, l in enumerate(ins):
+            if re.match(r"(global|flat|buffer)_load", l):
+                loads += 1
+            elif re.match(r"(global|flat|buffer)_(store|atomic)", l):
+                stores += 1
+            m = re.match(r"s_waitcnt\b.*vmcnt\((\d+)\)", l)
+            if m:
+                print("%-5s instruction %3d: s_waitcnt vmcnt(%s) after %d global loads and %d global stores of this arm" % (k, n, m.group(1), loads, stores))
 
 
 if __name__ == "__main__":
