@@ -98,7 +98,10 @@ int soc_set_exec(soc_ctx *ctx, int mode, int brick_log2);
  * brick-local form of a hierarchy that has one too, the opacities of a brick's cells in LDS; 0, the built-in choice: they are routed as
  * without the key, through the sweep that reads the hierarchy and OPT from global memory.  Not with with_int 2 or soc_set_ali, which
  * keep today's paths.  Launches deferred between two soc_set_opt / soc_set_optical_abu calls then share one copy of the opacities,
- * and a batch holds at most 16 such copies). */
+ * and a batch holds at most 16 such copies), "float_local" (1: hierarchies on which Index() runs in float -- NX <= 100, or NX <= 399
+ * with two levels -- take the brick-local form too, in its float form: absorption launches, also with mirror, with_int 2, ROI records
+ * and ALI, and the sweep of rays of the scattered-light launches; 0, the built-in choice: such grids are routed as without the key.
+ * Launches with per-cell opacities on such a grid, and every launch on a grid with Index() in double, are routed the same either way). */
 int soc_set_tuning(soc_ctx *ctx, const char *name, int value);
 
 /* replaces the per-frequency uploads of ABS, SCA (ASOC.py:1171-1175); ndust must be 1

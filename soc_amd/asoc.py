@@ -154,18 +154,45 @@ def _check_supported(USER, NDUST, WITH_MSF, engine=None):
 
 def _abu_local(method):
     """A transfer stage of AbsorptionRun: with an abundance file the engine's `abu_local` routing is on while it runs (see
-    AbsorptionRun.ABU_LOCAL), and the engine has its built-in routing back afterwards."""
+    AbsorptionRun.ABU_LOCAL), on a hierarchy whose Index() runs in float its `float_local` routing (AbsorptionRun.FLOAT_LOCAL), and the
+    engine has its built-in routing back afterwards.  A run with neither issues no tuning call."""
     @functools.wraps(method)
     def stage(self, *a, **kw):
-        on = self.WITH_ABU and self.ABU_LOCAL
+        keys = []
+        if self.WITH_ABU and self.ABU_LOCAL:
+            keys.append("abu_local")
+        if self.FLOAT_LOCAL and float_index(self.cloud):
+            keys.append("float_local")
+        for k in keys:
+            self._tune(**{k: 1})
+        try:
+            return method(self, *a, **kw)
+        finally:
+            for k in reversed(keys):
+                self._tune(**{k: 0})
+    return stage
+
+
+def _float_local(method):
+    """the `float_local` half of _abu_local alone: the stage of the scattered-light driver (soc_amd.asocs), whose launches with
+    per-cell opacities have no sweep to be routed to"""
+    @functools.wraps(method)
+    def stage(self, *a, **kw):
+        on = self.FLOAT_LOCAL and float_index(self.cloud)
         if on:
-            self._tune(abu_local=1)
+            self._tune(float_local=1)
         try:
             return method(self, *a, **kw)
         finally:
             if on:
-                self._tune(abu_local=0)
+                self._tune(float_local=0)
     return stage
+
+
+def float_index(cloud):
+    """a hierarchy on which the reference evaluates Index() with float3 POS (kernel_ASOC_aux.c:25-37): NX <= 399 with two levels,
+    NX <= 100 with three or more"""
+    return cloud.LEVELS > 1 and cloud.NX <= (399 if cloud.LEVELS < 3 else 100)
 
 
 class AbsorptionRun:
@@ -505,6 +532,18 @@ class AbsorptionRun:
     # profiles/abu_local_lines.json): 9.67e9 cell steps/s against 6.58e9, 1.47x with a spread of 0.14 % over the repeats, equal event
     # counts -- so the key is on.  with_int 2 and ALI are not part of that walk; the engine routes them as before either way.
     ABU_LOCAL = True
+
+    # Hierarchies whose Index() the reference evaluates in float (NX <= 100, or <= 399 with two levels): the engine's tuning key
+    # `float_local`, which takes their launches to the brick-local walk in its float form (soc_ltree.h) instead of the sweep that reads
+    # the hierarchy from global memory -- and mirror, `saveint 2`, ROI records and ALI launches to a sweep at all.  The rule for this
+    # switch: on only if tools/exp_float_local.py (profiles/float_local_lines.json) shows the float form faster on both of its geometries
+    # by more than the spread of the repeats.  Measured, 9 launches in one batch, equal event counts: octree_cloud(64, levels=4) 1.65e10
+    # cell steps/s against 1.02e10 (1.61x), octree_cloud(256, levels=2) 5.71e10 against 1.74e10 (3.28x), spread 0.7 % -- so the key is on.
+    # (The float form runs the nine launches as one sweep, the older path as one sweep per kind of launch: part of the ratio, not
+    # measured apart.  What the key also reroutes in automatic mode -- batched scattered-light launches to the sweep of rays, lone
+    # launches of 1e6 work items and more, launches with mirror, saveint 2, ROI records or ALI to form 3 -- is tested for results but was
+    # NOT measured against the direct kernels it replaces.)
+    FLOAT_LOCAL = True
 
     def _sends(self, II, IFREQ):
         """False where _launch sends nothing: no DIFFUSERAD column for the frequency, an empty Healpix sky (files.hpbg_for_frequency)"""

@@ -23,7 +23,7 @@ import time
 import numpy as np
 
 from . import files, launch
-from .asoc import AbsorptionRun, UnsupportedOption
+from .asoc import AbsorptionRun, UnsupportedOption, _float_local
 from .ini import User
 from .launch import PLANCK, PARSEC, Fix
 
@@ -142,6 +142,7 @@ class ScatteringRun(AbsorptionRun):
         self.timers["Tpull"] += time.time() - t0
 
     # ---------------------------------------------------------------------------------
+    @_float_local
     def simulate(self):
         """-> OUTCOMING[NFREQ, NDIR, NPIX.y, NPIX.x], photons per pixel before the final scaling"""
         U, e, c = self.U, self.eng, self.cloud

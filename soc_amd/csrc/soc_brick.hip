@@ -673,7 +673,10 @@ __device__ __forceinline__ int soc_cell_index(const SocGrid &G, int level, int c
 // GetStep -- by then the slot is the one the landing, the arrival or the placement gave it together with the density, and the pair is
 // not needed before tauA, a fract and three divisions later -- so no global load enters the step arm and one read site serves every way
 // a lane comes by a cell.  WINT 0, 1 and 3 only; the event workgroups read OPT of the queue's launch in global memory as they always did.
-template <int WINT, bool RAY = false, bool ALI = false, bool LIM = false, bool CART = false, bool ABU = false>
+// FLT: the float form of Index() (soc_ltree.h) -- hierarchies on which the reference evaluates it with float3 POS: every step that starts
+// below the root grid climbs fma by fma, from the packet's integer coordinates, to the level where the reference's own climb stops, and
+// descends from there.  The arithmetic of GetStep, the tallies and the queues are the same; not combined with ABU.
+template <int WINT, bool RAY = false, bool ALI = false, bool LIM = false, bool CART = false, bool ABU = false, bool FLT = false>
 __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPack &K, const SocBrickArgs &A, const int bid)
 {
     if (bid >= *A.ndesc) return;
@@ -971,7 +974,8 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
             } else
             if (move) {
                 SocLtAim AM;
-                soc_lt_aim(KB, NX, NY, NZ, Lmax, kexp, what, px, py, pz, level, cx, cy, cz, obase, AM);
+                if (FLT) soc_lt_aim_flt(KB, NX, NY, NZ, Lmax, what, px, py, pz, level, cx, cy, cz, obase, AM);
+                else     soc_lt_aim(KB, NX, NY, NZ, Lmax, kexp, what, px, py, pz, level, cx, cy, cz, obase, AM);
                 int   r = AM.r;
                 const float rec = sD[AM.s];
                 // test knob: this step goes through the slow-step queue (as a select on the outcome: a branch around soc_lt_aim gave every
@@ -999,7 +1003,8 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
 #if defined(SOC_BRICK_PROF)
                 const bool prof_lands = (r == SOC_LT_INSIDE);
 #endif
-                if (r == SOC_LT_INSIDE) r = soc_lt_land(sD, AM, Lmax, what, rec, px, py, pz, level, cx, cy, cz, slot, obase, dens);
+                if (FLT) { if (r == SOC_LT_INSIDE) r = soc_lt_land_flt(sD, AM, Lmax, what, rec, px, py, pz, level, cx, cy, cz, slot, obase, dens); }
+                else if (r == SOC_LT_INSIDE) r = soc_lt_land(sD, AM, Lmax, what, rec, px, py, pz, level, cx, cy, cz, slot, obase, dens);
 #if defined(SOC_BRICK_PROF)
                 prof_trips = prof_lands ? (level - AM.l) : 0;
 #endif
@@ -1133,7 +1138,8 @@ __device__ __forceinline__ bool soc_roi_create(const SocGrid &G, const SocSim &S
 }
 
 // creation and scattering, one lane per queued packet
-template <bool OCT, bool ABU, int WINT, int KIND, bool LT>
+// FLT (LT only): Index() in float -- the slow step and the root position a packet leaves the model at (soc_ltree.h, the float form)
+template <bool OCT, bool ABU, int WINT, int KIND, bool LT, bool FLT = false>
 __device__ __forceinline__ void soc_brick_events(const SocGrid &G, const SocSimPack &K, const SocBrickArgs &A, const int ebid, const int slice)
 {
     constexpr int  SRC = (KIND == 3) ? 1 : -1;             // KIND 3: SimRAM_PB with SOURCE == 1 (background) only
@@ -1203,7 +1209,9 @@ __device__ __forceinline__ void soc_brick_events(const SocGrid &G, const SocSimP
         if (LT && create && (S.MIRROR > 0)) {
             const bool started = CL ? (((int)cl_cell >= 0) && (III > 0)) : (III > 0);      // (a work item that has sent no packet yet holds none)
             if (started) {
-                if (w.level > 0) {
+                if (FLT) {
+                    soc_lt_rootpos_f(w.px, w.py, w.pz, w.level, ccx, ccy, ccz);      // the climb itself, level by level
+                } else if (w.level > 0) {
                     const float sc = soc_lt_pow2(-w.level);
                     w.px = SOC_FMA(w.px, sc, (float)(ccx & ~1) * sc);  w.py = SOC_FMA(w.py, sc, (float)(ccy & ~1) * sc);  w.pz = SOC_FMA(w.pz, sc, (float)(ccz & ~1) * sc);
                 }
@@ -1218,10 +1226,11 @@ __device__ __forceinline__ void soc_brick_events(const SocGrid &G, const SocSimP
             key = qbase + A.rbrick[((ccz >> w.level) * G.NY + (ccy >> w.level)) * G.NX + (ccx >> w.level)];
         } else
         if (LT && (evk == 2)) {
-            // slow step: Index() itself, in double, for a step that exact geometry does not decide (soc_ltree.h).  The
-            // packet holds its old cell and the advanced position; tallies of the step are done.
+            // slow step: Index() itself, in double (FLT: in float), for a step that exact geometry does not decide (soc_ltree.h).
+            // The packet holds its old cell and the advanced position; tallies of the step are done.
             const int ind0 = w.ind, level0 = w.level;
-            soc_index<true, double>(G, sOFF, w.px, w.py, w.pz, w.level, w.ind, w.dens);
+            if (FLT) soc_index<true, float>(G, sOFF, w.px, w.py, w.pz, w.level, w.ind, w.dens);
+            else     soc_index<true, double>(G, sOFF, w.px, w.py, w.pz, w.level, w.ind, w.dens);
             if (S.ROISAVE && (w.ind >= 0) && (soc_inroi(G, sOFF, *S.ROI, level0, ind0) < 0) && (soc_inroi(G, sOFF, *S.ROI, w.level, w.ind) >= 0))
                 soc_roi_save(G, sOFF, *S.ROI, w.px, w.py, w.pz, w.ux, w.uy, w.uz, w.level, w.ind, w.photons);      // the step took it into ROI (kernel_ASOC.c:615-642)
             if (!CL && (w.ind >= 0) && (w.level == level0) && (w.ind == ind0)) {   // failed step: nudge (SimRAM_PB / HP only), before Mirror as in the step
@@ -1504,6 +1513,35 @@ __global__ __launch_bounds__(1024) void soc_lbrick_pass_abu(const SocGrid G, con
     }
 }
 
+// hierarchies with Index() in float (soc_set_tuning("float_local", 1)): the FLT form of the walk and of the event workgroups; one
+// kernel per WINT, the kind of a launch is the launch's (KIND 4)
+template <int WINT>
+__global__ __launch_bounds__(1024) void soc_lbrick_pass_flt(const SocGrid G, const SocSimPack *Kp, const SocBrickArgs A, const int nwalk, const int slices)
+{
+    const SocSimPack &K = *Kp;
+    const int b = (int)blockIdx.x;
+    if (b < nwalk) {
+        soc_lbrick_walk<WINT, false, false, false, false, false, true>(G, K, A, b);
+    } else {
+        const int e = b - nwalk;
+        soc_brick_events<true, false, WINT, 4, true, true>(G, K, A, e / slices, e % slices);
+    }
+}
+
+// ... SimRAM_CL launches with the XAB tally of -D WITH_ALI
+template <int WINT>
+__global__ __launch_bounds__(1024) void soc_lbrick_pass_ali_flt(const SocGrid G, const SocSimPack *Kp, const SocBrickArgs A, const int nwalk, const int slices)
+{
+    const SocSimPack &K = *Kp;
+    const int b = (int)blockIdx.x;
+    if (b < nwalk) {
+        soc_lbrick_walk<WINT, false, true, false, false, false, true>(G, K, A, b);
+    } else {
+        const int e = b - nwalk;
+        soc_brick_events<true, false, WINT, 2, true, true>(G, K, A, e / slices, e % slices);
+    }
+}
+
 // OPT of every group of launches -> brick-slot order (slot -> cell: bcell, the table the ALI form uses), once per sweep: the prologue of
 // soc_lbrick_walk<., ABU> then copies a brick's opacities as it copies its cells, nslot contiguous entries from the brick's base
 __global__ __launch_bounds__(256) void soc_lbrick_opt(const SocSimPack *Kp, const int *bcell, long long nslots, float2 *kopt)
@@ -1548,7 +1586,24 @@ struct SocRayLane {                                                   // what so
     soc_rng_t rng;
 };
 
-template <bool HPX, bool HPSKY>
+// The grid as the code inlined into the lane loop of soc_sca_events sees it: G itself, or (FLT) a fresh copy whose extents the compiler
+// cannot trace to G's.  What that code derives from the extents ((float)NX, face areas, the bounding sphere, NZ - PEPS ...) is then
+// formed at the call and not before the lane loop, where those uniform values held registers across the whole loop and were spilled
+// to scratch.  (A fresh copy at every call: an opaque value carried round the loop is no longer uniform to the compiler.)
+// (without FLT the call sees G itself, by reference: the instances for Index() in double compile as they did)
+template <bool FLT> struct SocGridHere;
+template <> struct SocGridHere<false> {
+    static __device__ __forceinline__ const SocGrid &get(const SocGrid &G) { return G; }
+};
+template <> struct SocGridHere<true> {
+    static __device__ __forceinline__ SocGrid get(const SocGrid &G)
+    {
+        SocGrid g = G;
+        asm volatile("" : "+s"(g.NX), "+s"(g.NY), "+s"(g.NZ));
+        return g;
+    }
+};
+template <bool HPX, bool HPSKY, bool FLT = false>
 __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPack &K, const SocBrickArgs &A, const int ebid, const int slice)
 {
     const SocSca &V = A.sca;
@@ -1612,21 +1667,24 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
         } else if (evk == 1) {
             // the packet's free path ends in this step (:1000-1015 PB, :1295-1310 CL, :1789-1805 PS); the record holds the start of the step.
             // The offset of the scattering is scaled with the level AFTER the step: GetStep once more, on the global hierarchy.
-            w.ind = soc_cell_index(G, w.level, ccx, ccy, ccz, w.dens);
+            w.ind = soc_cell_index(SocGridHere<FLT>::get(G), w.level, ccx, ccy, ccz, w.dens);
             float tx = w.px, ty = w.py, tz = w.pz, td = w.dens;
             int   tl = w.level, ti = w.ind;
-            (void)soc_getstep_rcp<true, true>(G, sOFF, tx, ty, tz, w.ux, w.uy, w.uz, 1.0f / w.ux, 1.0f / w.uy, 1.0f / w.uz, tl, ti, td);
+            (void)soc_getstep_rcp<true, !FLT>(SocGridHere<FLT>::get(G), sOFF, tx, ty, tz, w.ux, w.uy, w.uz, 1.0f / w.ux, 1.0f / w.uy, 1.0f / w.uz, tl, ti, td);
             lvl_post = tl;
             mode = SOC_RE_SCAT;
         } else {
             if (evk == 2) {
-                // slow step: Index() itself, in double; the record holds the old cell and the advanced position, the optical depth of the step is added
-                w.ind = soc_cell_index(G, w.level, ccx, ccy, ccz, w.dens);
-                soc_index<true, double>(G, sOFF, w.px, w.py, w.pz, w.level, w.ind, w.dens);
+                // slow step: Index() itself, in double (FLT: in float); the record holds the old cell and the advanced position, the optical depth of the step is added
+                w.ind = soc_cell_index(SocGridHere<FLT>::get(G), w.level, ccx, ccy, ccz, w.dens);
+                if (FLT) soc_index<true, float>(SocGridHere<FLT>::get(G), sOFF, w.px, w.py, w.pz, w.level, w.ind, w.dens);
+                else     soc_index<true, double>(SocGridHere<FLT>::get(G), sOFF, w.px, w.py, w.pz, w.level, w.ind, w.dens);
                 cc_ok = false;
             } else {
                 // the ray has left the model: the root-grid position Index() leaves behind (kernel_ASOC_aux.c:238-241)
-                if (w.level > 0) {
+                if (FLT) {
+                    soc_lt_rootpos_f(w.px, w.py, w.pz, w.level, ccx, ccy, ccz);
+                } else if (w.level > 0) {
                     const float sc = soc_lt_pow2(-w.level);
                     w.px = SOC_FMA(w.px, sc, (float)(ccx & ~1) * sc);  w.py = SOC_FMA(w.py, sc, (float)(ccy & ~1) * sc);  w.pz = SOC_FMA(w.pz, sc, (float)(ccz & ~1) * sc);
                 }
@@ -1640,7 +1698,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                 mode = SOC_RE_PEEL_END;
             } else {
                 if (S.MIRROR > 0) {                           // kernel_ASOC_sca.c:983, :1283, :1781
-                    soc_mirror<true>(G, sOFF, S.MIRROR, w.px, w.py, w.pz, w.ux, w.uy, w.uz, w.level, w.ind, w.dens);
+                    soc_mirror<true>(SocGridHere<FLT>::get(G), sOFF, S.MIRROR, w.px, w.py, w.pz, w.ux, w.uy, w.uz, w.level, w.ind, w.dens);
                     cc_ok = false;
                 }
                 mode = (w.ind >= 0) ? SOC_RM_MAIN : SOC_RE_CREATE;
@@ -1649,7 +1707,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
 
         const int id = (int)(S.gid0 + (wid - K.first[lq]));
         SocSurfElem E;
-        if ((KIND != SOC_SCA_CL) && !(HPSKY && (KIND == SOC_SCA_HP))) E = soc_surface_element(G, S, id);      // (SimRAM_HP has none)
+        if ((KIND != SOC_SCA_CL) && !(HPSKY && (KIND == SOC_SCA_HP))) E = soc_surface_element(SocGridHere<FLT>::get(G), S, id);      // (SimRAM_HP has none)
         while (mode > SOC_RM_PEEL && mode != SOC_RE_DONE) {
             // ---- start of a scattering event
             if (mode == SOC_RE_SCAT) {
@@ -1668,7 +1726,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                     // direction and distance to the observer from the root position of the scattering (:319-327); the ray carries
                     // minus the distance in its free-path slot (soc_lbrick_walk<., RAY, ., LIM>)
                     float rx = w.px, ry = w.py, rz = w.pz;
-                    soc_rootpos(G, sOFF, rx, ry, rz, w.level, w.ind);
+                    soc_rootpos(SocGridHere<FLT>::get(G), sOFF, rx, ry, rz, w.level, w.ind);
                     const float4 o = V.ODIRS[0];
                     w.ux = o.x - rx;  w.uy = o.y - ry;  w.uz = o.z - rz;
                     const float dxrem = soc_sqrtf(w.ux * w.ux + w.uy * w.uy + w.uz * w.uz);
@@ -1843,7 +1901,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                     if (III >= S.BATCH) {
                         mode = SOC_RE_DONE;
                     } else {
-                        soc_hp_sca_create<true>(G, S, sOFF, w);
+                        soc_hp_sca_create<true>(SocGridHere<FLT>::get(G), S, sOFF, w);
                         III++;
                         n_pkt++;
                         have = (w.ind >= 0);                  // a packet that misses the cloud is counted and skipped (:222)
@@ -1852,7 +1910,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                     if (III >= S.BATCH) {
                         mode = SOC_RE_DONE;
                     } else {
-                        soc_pb_create<true>(G, S, sOFF, E, III, w);
+                        soc_pb_create<true>(SocGridHere<FLT>::get(G), S, sOFF, E, III, w);
                         III++;
                         have = true;
                     }
@@ -1868,7 +1926,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                     tau  = 0.0f;
                     scat = 0;
                     cc_ok = false;
-                    if (w.ind >= 0) { soc_cell_coords(G, sOFF, w.level, w.ind, ccx, ccy, ccz);  cc_ok = true; }
+                    if (w.ind >= 0) { soc_cell_coords(SocGridHere<FLT>::get(G), sOFF, w.level, w.ind, ccx, ccy, ccz);  cc_ok = true; }
                     if (V.FFS > 0) {
                         mx = w.px;  my = w.py;  mz = w.pz;  mlevel = w.level;  mcx = ccx;  mcy = ccy;  mcz = ccz;
                         if (w.ind >= 0) { mode = SOC_RM_FFS;  rmode = SOC_RM_FFS; }
@@ -1884,7 +1942,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
         int key = NQ - 1;                                     // work item finished
         SocPk2 o, r;
         if (mode != SOC_RE_DONE) {
-            if (!cc_ok) soc_cell_coords(G, sOFF, w.level, w.ind, ccx, ccy, ccz);
+            if (!cc_ok) soc_cell_coords(SocGridHere<FLT>::get(G), sOFF, w.level, w.ind, ccx, ccy, ccz);
             key = qbase + A.rbrick[((ccz >> w.level) * G.NY + (ccy >> w.level)) * G.NX + (ccx >> w.level)];
             rmode = mode;
         }
@@ -1921,16 +1979,17 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
 // holds SimRAM_HP launches (the creation of their packets stays out of the kernels of sweeps without them: registers)
 // CART: the grid has one level (soc_lbrick_walk<., ., ., ., CART>); the event workgroups are the same -- a Cartesian ray is an ordinary
 // entry to them, on level 0 of a hierarchy that has no other
-template <bool HPX, bool HPSKY, bool CART>
+// FLT: a hierarchy with Index() in float (soc_lbrick_walk<., ., ., ., ., ., FLT>, soc_sca_events<., ., FLT>)
+template <bool HPX, bool HPSKY, bool CART, bool FLT = false>
 __global__ __launch_bounds__(1024) void soc_lray_pass(const SocGrid G, const SocSimPack *Kp, const SocBrickArgs A, const int nwalk, const int slices)
 {
     const SocSimPack &K = *Kp;
     const int b = (int)blockIdx.x;
     if (b < nwalk) {
-        soc_lbrick_walk<false, true, false, HPX, CART>(G, K, A, b);
+        soc_lbrick_walk<false, true, false, HPX, CART, false, FLT>(G, K, A, b);
     } else {
         const int e = b - nwalk;
-        soc_sca_events<HPX, HPSKY>(G, K, A, e / slices, e % slices);
+        soc_sca_events<HPX, HPSKY, FLT>(G, K, A, e / slices, e % slices);
     }
 }
 
@@ -2225,13 +2284,21 @@ static const SocPassFn soc_lbrick_pass_fns[4][5] = {
 static const SocPassFn soc_lbrick_pass_ali_fns[2] = { soc_lbrick_pass_ali<0>, soc_lbrick_pass_ali<1> };
 // ... with per-cell opacities: [WINT 0, 1, 3] (plan_sweep keeps with_int 2 and ALI with abundances off this form)
 static const SocPassFn soc_lbrick_pass_abu_fns[4] = { soc_lbrick_pass_abu<0>, soc_lbrick_pass_abu<1>, nullptr, soc_lbrick_pass_abu<3> };
-// rays: [single-level grid][Healpix image seen from a position][SimRAM_HP launches]
+// ... on hierarchies with Index() in float: [WINT 0-3]; ALI: [WINT 0-1]
+static const SocPassFn soc_lbrick_pass_flt_fns[4] = { soc_lbrick_pass_flt<0>, soc_lbrick_pass_flt<1>, soc_lbrick_pass_flt<2>, soc_lbrick_pass_flt<3> };
+static const SocPassFn soc_lbrick_pass_ali_flt_fns[2] = { soc_lbrick_pass_ali_flt<0>, soc_lbrick_pass_ali_flt<1> };
+// rays: [single-level grid][Healpix image seen from a position][SimRAM_HP launches]; on hierarchies with Index() in float: [Healpix image][SimRAM_HP]
 static const SocPassFn soc_lray_pass_fns[2][2][2] = { { { soc_lray_pass<0, 0, 0>, soc_lray_pass<0, 1, 0> }, { soc_lray_pass<1, 0, 0>, soc_lray_pass<1, 1, 0> } },
                                                       { { soc_lray_pass<0, 0, 1>, soc_lray_pass<0, 1, 1> }, { soc_lray_pass<1, 0, 1>, soc_lray_pass<1, 1, 1> } } };
 
+static const SocPassFn soc_lray_pass_flt_fns[2][2] = { { soc_lray_pass<0, 0, 0, 1>, soc_lray_pass<0, 1, 0, 1> }, { soc_lray_pass<1, 0, 0, 1>, soc_lray_pass<1, 1, 0, 1> } };
+
 static SocPassFn pass_kernel(const SocSweepPlan &pl)
 {
-    if (pl.rays)      return soc_lray_pass_fns[pl.octree ? 0 : 1][pl.hpx][pl.hpsky];
+    const bool flt = (pl.form == 3) && pl.octree && !pl.dbl;      // a brick-local hierarchy with Index() in float (plan_sweep: never with per-cell opacities)
+    if (pl.rays)      return flt ? soc_lray_pass_flt_fns[pl.hpx][pl.hpsky] : soc_lray_pass_fns[pl.octree ? 0 : 1][pl.hpx][pl.hpsky];
+    if (flt && pl.abu) return nullptr;
+    if (flt)          return pl.ali ? soc_lbrick_pass_ali_flt_fns[pl.wint] : soc_lbrick_pass_flt_fns[pl.wint];
     if (pl.form == 3 && pl.abu) return soc_lbrick_pass_abu_fns[pl.wint];
     if (pl.form == 3) return pl.ali ? soc_lbrick_pass_ali_fns[pl.wint] : soc_lbrick_pass_fns[pl.wint][pl.kind];
     return soc_brick_pass_fns[pl.octree + pl.dbl][pl.abu][pl.wint][pl.kind];
@@ -2476,6 +2543,7 @@ static hipError_t plan_kernel(SocSweepPlan &pl, SocBrickArgs &A, SocSweepSize &s
         if (several) pl.kind = 4;
         else if (all_bg && !tune.nolean) pl.kind = 3;
         if (pl.form == 3 && pl.abu) pl.kind = 4;                          // per-cell opacities: one kernel per WINT, the kind from the launch
+        if (pl.form == 3 && pl.octree && !pl.dbl) pl.kind = pl.ali ? 2 : 4;      // Index() in float: likewise
     }
     if (pl.form == 3 && pl.abu && (pl.wint == 2 || pl.ali)) return hipErrorNotSupported;      // (plan_sweep does not plan these)
     if (pl.form != 3) for (int l = 0; l < K.n; l++) if (K.S[l].MIRROR) return hipErrorNotSupported;      // reflecting faces: the event workgroups of brick-local hierarchies only

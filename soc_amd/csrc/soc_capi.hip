@@ -60,6 +60,7 @@ static size_t view_pixels(const soc_ctx *c)
 // Hierarchies on which the brick sweep keeps the brick's cells in LDS (soc_brick.hip, soc_ltree.h): there a lone
 // launch with enough work items pays too -- also with the INT tally, which lives in LDS beside TABS.
 // With per-cell opacities: soc_set_tuning("abu_local", 1), and neither with_int 2 nor ALI (soc_dev.h: soc_brick_local).
+// Hierarchies with Index() in float: soc_set_tuning("float_local", 1) and scalar opacities.
 static bool lt_capable(const soc_ctx *c, bool abu)
 {
     return soc_brick_local(c->G, soc_grid_variant(c->G, abu, c->with_int), c->tune) && !(abu && c->with_ali);
@@ -357,7 +358,7 @@ int soc_set_tuning(soc_ctx *c, const char *name, int value)
         { "climb_lanes", &c->tune.CTH }, { "brick_cells", &c->tune.CAP }, { "tail_lanes", &c->tune.TAIL }, { "park_below", &c->tune.park }, { "population", &c->tune.POP },
         { "hash_slots", &c->tune.HS }, { "global_tree", &c->tune.global_tree }, { "slow_every", &c->tune.slow_every },
         { "general_kernel", &c->tune.nolean }, { "oversubscribe", &c->tune.oversub }, { "verbose", &c->tune.verbose },
-        { "abu_local", &c->tune.abu_local } };
+        { "abu_local", &c->tune.abu_local }, { "float_local", &c->tune.float_local } };
     for (auto &t : tab)
         if (!strcmp(name, t.n)) {
             if (t.p == &c->tune.CAP && value != c->tune.CAP) soc_sweep_invalidate(c->sweep);
@@ -768,9 +769,9 @@ static const struct {
     long long   min_items;              // absorption, automatic mode: work items from which the brick sweep pays
     const char *not_applicable;         // absorption: what keeps soc_set_exec(1) from the brick sweep
 } sim_kinds[] = {
-    { "soc_sim_pb", 0, 65536,  "mirror, with_int 2, roisave/roiload off brick-local hierarchies (per-cell opacities: those need soc_set_tuning abu_local and no with_int 2), > 15 levels or > 2^18 bricks" },
-    { "soc_sim_hp", 0, 65536,  "mirror, with_int 2 off brick-local hierarchies (per-cell opacities: those need soc_set_tuning abu_local and no with_int 2), > 15 levels or > 2^18 bricks" },
-    { "soc_sim_cl", 0, 262144, "mirror, with_int 2, ALI, roisave off brick-local hierarchies (per-cell opacities: those need soc_set_tuning abu_local and neither with_int 2 nor ALI), USE_EMWEIGHT 2, > 15 levels or > 2^18 bricks" },
+    { "soc_sim_pb", 0, 65536,  "mirror, with_int 2, roisave/roiload off brick-local hierarchies (Index() in float: those need soc_set_tuning float_local; per-cell opacities: soc_set_tuning abu_local, Index() in double and no with_int 2), > 15 levels or > 2^18 bricks" },
+    { "soc_sim_hp", 0, 65536,  "mirror, with_int 2 off brick-local hierarchies (Index() in float: those need soc_set_tuning float_local; per-cell opacities: soc_set_tuning abu_local, Index() in double and no with_int 2), > 15 levels or > 2^18 bricks" },
+    { "soc_sim_cl", 0, 262144, "mirror, with_int 2, ALI, roisave off brick-local hierarchies (Index() in float: those need soc_set_tuning float_local; per-cell opacities: soc_set_tuning abu_local, Index() in double and neither with_int 2 nor ALI), USE_EMWEIGHT 2, > 15 levels or > 2^18 bricks" },
     { "soc_sca_sim_pb", SOC_SCA_PB + 1, 0, nullptr },
     { "soc_sca_sim_cl", SOC_SCA_CL + 1, 0, nullptr },
     { "soc_sca_sim_ps", SOC_SCA_PS + 1, 0, nullptr },
@@ -792,7 +793,7 @@ static bool use_sweep(const soc_ctx *c, SimKind kind, const SocVariant &V, long 
              : (c->msf_ndust > 1) ? "several scattering functions (WITH_MSF) need the direct kernel"
              : (c->dOPT != nullptr) ? "per-cell opacities need the direct kernel"
              : !(lt_capable(c, false) || cart_capable(c))
-                   ? "the grid is not one the sweep of rays takes (a hierarchy of 2-8 levels with Index() in double, or a single-level grid below 4096 cells per edge)"
+                   ? "the grid is not one the sweep of rays takes (a hierarchy of 2-8 levels with Index() in double -- in float: with soc_set_tuning float_local --, or a single-level grid below 4096 cells per edge)"
              : nullptr;
         if (cart_capable(c))                                // (the launches of a batch are deferred where a batch can pay; flush_pending counts them)
             return c->exec_mode != 0 && !*why && (c->exec_mode == 1 || (batch ? cart_rays_pay(c, SOC_CART_RAYS_BATCH, true) : cart_rays_pay(c, items, false)));

@@ -321,6 +321,7 @@ struct SocBrickTune {
     int oversub;               // experiment: background work items beyond 8*AREA are not clipped
     int verbose;
     int abu_local;             // brick-local hierarchies: launches with per-cell opacities (WITH_ABU) take the brick-local walk too (0 = built-in choice: off)
+    int float_local;           // hierarchies with Index() in float (NX <= DIMLIM) take the brick-local walk too, in its float form (0 = built-in choice: off)
 };
 
 // KIND of a launch's source: 0 SimRAM_PB, 1 SimRAM_HP, 2 SimRAM_CL
@@ -343,10 +344,13 @@ static inline SocVariant soc_grid_variant(const SocGrid &G, bool abu = false, in
 // with soc_set_tuning("abu_local", 1), and not with with_int 2 (the abundance kernels are built for WINT 0, 1 and 3); launches with the
 // XAB tally of WITH_ALI stay off it too (plan_sweep in soc_brick.hip, lt_capable in soc_capi.hip).  Without the key such launches are
 // routed as they always were: the sweep that reads the hierarchy and OPT from global memory.
+// Hierarchies with Index() in float (!V.dbl): only with soc_set_tuning("float_local", 1) -- the float form of soc_ltree.h -- and only with
+// scalar opacities (no kernel combines the float form with per-cell opacities); without the key, and with per-cell opacities, they are
+// routed as they always were.  On a grid with Index() in double the key changes nothing.
 static inline bool soc_brick_local(const SocGrid &G, const SocVariant &V, const SocBrickTune &tune)
 {
     const int n = std::max(G.NX, std::max(G.NY, G.NZ));
-    return V.octree && V.dbl && (!V.abu || (tune.abu_local && V.wint != 2)) && !tune.global_tree && G.LEVELS <= 8 && ((long long)n << (G.LEVELS - 1)) < (1LL << 24) && n < 4096;
+    return V.octree && (V.dbl || (tune.float_local && !V.abu)) && (!V.abu || (tune.abu_local && V.wint != 2)) && !tune.global_tree && G.LEVELS <= 8 && ((long long)n << (G.LEVELS - 1)) < (1LL << 24) && n < 4096;
 }
 
 // Single-level (Cartesian) grids on which the scattered-light launches run as a sweep of rays (soc_brick.hip: the CART arm of

@@ -20,8 +20,31 @@
 // inclusive tests of :264 pick a cell by rule, not by geometry) or tiny -- are recognised (soc_lt_degenerate) and
 // left to soc_index<double> itself (the "slow step" queue of the brick sweep).
 //
-// Shared by the device walk (soc_brick.hip) and the host (tests/ltree_host.cpp follows rays through bricks built
-// by soc_lbricks.h and is compared with the oracle's Index step by step).
+// THE FLOAT FORM (soc_lt_aim_flt / soc_lt_land_flt): hierarchies on which the reference evaluates Index() with float3 POS
+// (NX <= DIMLIM).  There the climb rounds at every level: POS = POS*0.5 + b, with b the octant bit of the cell that is left (the
+// root-cell coordinate on arrival at level 0).  POS*0.5 is exact, so a level is ONE fma(P, 0.5f, b), and what Index() returns is the
+// outcome of exactly that sequence of roundings -- not the rounded geometry, so no single fma from the packet's own level gives it.
+// Everything after the climb is as exact in float as in double: the stop test (0 <= P <= 2 on every axis, or the root grid), floor()
+// for the cell, 2*fmod(P,1) on the way down (P in [0,2]: a subtraction of 0 or 1 and a doubling lose nothing).  So the float form is
+//   * the climb itself, fma by fma, from the packet's integer coordinates: b_j = (c >> j) & 1 below the root grid, c >> L on it; it
+//     stops at the first level where 0 <= P <= 2 holds on all axes (:254, inclusive) or on the root grid.  Every step that starts below
+//     the root grid climbs at least once -- also one into a sibling of the packet's own octet, whose pos does change (P_1 is in
+//     general not pos/2 + b exactly);
+//   * from the stop level l_s, with P_stop and the octet origin o_s = (c >> j) & ~1 there, what the double form does from the packet's
+//     level: F = (o_s << D) + floor(P_stop * 2^D) with D = Lmax - l_s, the descent by the bits of F, and
+//     pos' = P_stop * 2^(l - l_s) + (o_s * 2^(l - l_s) - O_new), which here is an exact operation: the fma rounds nothing.
+// A coordinate that a rounding puts exactly on a cell face needs no care: the reference picks the cell by floor() and descends by the
+// digits of the same number, and so do the integers built from P_stop; RN is monotonic and integers are representable, so a rounded
+// coordinate cannot cross a face without landing on it.  The exception is P_stop == 2.0f on an axis below the root grid: the inclusive
+// test accepts it and floor() then indexes past the octet (:256).  Such a step, and one from a coordinate so small that it could
+// be flushed to zero (below 2^-100, zero itself included: see soc_lt_aim_flt), is left to soc_index<float> itself (SOC_LT_SLOW).
+// The thresholds of the double form (onface, kexp) have no role here.  A sibling under the packet's own parent -- the climb stopped one level up, in the parent's own cell -- takes its slot
+// from the packet's octet (obase) and the next bit of F; everything else descends from the brick's root cell.
+// soc_lt_rootpos_f() is the climb carried to the root grid: the position Index() leaves behind when the packet has left the model
+// (:230-233), which Mirror and the creation of the next packet start from.
+//
+// Shared by the device walk (soc_brick.hip) and the host (tests/ltree_host.cpp and tests/ltree_float_host.cpp follow rays through
+// bricks built by soc_lbricks.h and are compared with the oracle's Index step by step).
 #ifndef SOC_LTREE_H
 #define SOC_LTREE_H
 
@@ -101,7 +124,20 @@ struct SocLtAim {
     int ox, oy, oz;            // origin of the packet's octet on its level (0 on the root grid)
     int s, l;                  // the descent starts at slot s, a cell of level l
     int r;                     // SOC_LT_INSIDE: go on with soc_lt_land(tree[s]); else the outcome
+    float Px, Py, Pz;          // float form: the position where the climb stopped, on level L of the hierarchy
+    int L;                     // (the double form neither writes nor reads these four)
 };
+
+// float form: the climb of Index() (:211-262) carried to the root grid, fma by fma -- the position Index() leaves behind when the
+// packet has left the model (level > 0: no stop below the root grid came before it)
+SOC_HD void soc_lt_rootpos_f(float &px, float &py, float &pz, int level, int cx, int cy, int cz)
+{
+    while (level > 0) {
+        cx >>= 1;  cy >>= 1;  cz >>= 1;  level--;
+        const int m = (level > 0) ? 1 : ~0;
+        px = SOC_FMA(px, 0.5f, (float)(cx & m));  py = SOC_FMA(py, 0.5f, (float)(cy & m));  pz = SOC_FMA(pz, 0.5f, (float)(cz & m));
+    }
+}
 
 SOC_HD void soc_lt_aim(const SocLBrick &K, const int NX, const int NY, const int NZ, const int Lmax, const int kexp, const int what,
                        const float px, const float py, const float pz, const int level, const int cx, const int cy, const int cz,
@@ -176,16 +212,83 @@ SOC_HD int soc_lt_land(const TREE tree, const SocLtAim &A, const int Lmax, const
     return lost ? SOC_LT_LOST : SOC_LT_INSIDE;
 }
 
-// both halves in one call (host harness, slow paths)
+// ---------------------------------------------------------------------------------------------------------------
+// The float form (header comment): the same two halves.  soc_lt_aim_flt() makes the climb first -- fma by fma, from the packet's
+// integer coordinates -- and then works on the level, the position and the octet the climb stopped at (A.L, A.Px ..), which
+// soc_lt_land_flt() takes from A.  A placement makes no climb.  The functions of the double form above are not touched by it.
+// ---------------------------------------------------------------------------------------------------------------
+SOC_HD void soc_lt_aim_flt(const SocLBrick &K, const int NX, const int NY, const int NZ, const int Lmax, const int what,
+                           float px, float py, float pz, const int level, int cx, int cy, int cz, const int obase, SocLtAim &A)
+{
+    const bool place = (what == SOC_LTM_PLACE);
+    // A coordinate that is zero (or so small that hardware which flushes denormals would make it one) goes to the slow queue.  Not for the
+    // arithmetic -- fma(P, 0.5f, b) has no intermediate underflow -- but for the outcome rules below: from level 1 in root cell 0 such
+    // a coordinate climbs to P == 0 exactly, which the reference leaves the model with (:214, P <= 0), while `sib` holds for it (the
+    // point's ancestor IS the parent) and `go = sib | ...` would take the shortcut past `out0`.  Do not remove it as redundant.
+    const bool tiny = !(soc_fminf(soc_fabsf(px), soc_fminf(soc_fabsf(py), soc_fabsf(pz))) >= soc_lt_pow2(-100));
+    int L = level, j = 0;
+    while (!place && (L > 0)) {
+        cx >>= 1;  cy >>= 1;  cz >>= 1;  L--;  j++;
+        const int m = (L > 0) ? 1 : ~0;                     // the octant bit of the cell that is left; on arrival at level 0 the root cell
+        px = SOC_FMA(px, 0.5f, (float)(cx & m));  py = SOC_FMA(py, 0.5f, (float)(cy & m));  pz = SOC_FMA(pz, 0.5f, (float)(cz & m));
+        if ((px >= 0.0f) && (px <= 2.0f) && (py >= 0.0f) && (py <= 2.0f) && (pz >= 0.0f) && (pz <= 2.0f)) break;      // (:254, inclusive)
+    }
+    A.L = L;  A.Px = px;  A.Py = py;  A.Pz = pz;
+    const int  D = Lmax - L;
+    const bool deep = (L > 0);
+    const int  om = deep ? ~1 : 0;
+    A.ox = cx & om;  A.oy = cy & om;  A.oz = cz & om;
+    int Jx, Jy, Jz;                                          // floor(P * 2^D): the cell within the octet and D digits below it
+    {
+        const float sc = soc_lt_pow2(D);
+        Jx = (int)soc_floorf(px * sc);  Jy = (int)soc_floorf(py * sc);  Jz = (int)soc_floorf(pz * sc);
+    }
+    if (place) { Jx = (int)((unsigned)(cx - A.ox) << D);  Jy = (int)((unsigned)(cy - A.oy) << D);  Jz = (int)((unsigned)(cz - A.oz) << D); }
+    A.Fx = (int)((unsigned)A.ox << D) + Jx;  A.Fy = (int)((unsigned)A.oy << D) + Jy;  A.Fz = (int)((unsigned)A.oz << D) + Jz;
+    A.Rx = A.Fx >> Lmax;  A.Ry = A.Fy >> Lmax;  A.Rz = A.Fz >> Lmax;
+    // a sibling under the packet's own parent: the climb stopped one level up and the ancestor of the point on that level is the
+    // parent -- (cx, cy, cz) by now.  Its slot: the packet's octet and the bit of F on the packet's own level.
+    const bool sib = (j == 1) & ((A.Fx >> D) == cx) & ((A.Fy >> D) == cy) & ((A.Fz >> D) == cz);
+    // a stop below the root grid at exactly 2.0f: floor() indexes past the octet there (:256)
+    const bool slow = !place & (level > 0) & ((deep & ((px == 2.0f) | (py == 2.0f) | (pz == 2.0f))) | tiny);
+    const bool out0 = !deep & !place & ((px == 0.0f) | (py == 0.0f) | (pz == 0.0f));   // root grid: pos <= 0 leaves the model (:214)
+    const int  rx = A.Rx - K.x0, ry = A.Ry - K.y0, rz = A.Rz - K.z0;
+    const bool inbox = !(((unsigned)rx >= (unsigned)K.bx) | ((unsigned)ry >= (unsigned)K.by) | ((unsigned)rz >= (unsigned)K.bz));
+    const bool outside = out0 | ((unsigned)A.Rx >= (unsigned)NX) | ((unsigned)A.Ry >= (unsigned)NY) | ((unsigned)A.Rz >= (unsigned)NZ);
+    const int  sroot = SOC_MAD24(SOC_MAD24(rz, K.by, ry), K.bx, rx);
+    const int  Dp = Lmax - level;
+    const int  ssib = obase + (int)soc_lt_octant((unsigned)(A.Fx >> Dp) & 1u, (unsigned)(A.Fy >> Dp) & 1u, (unsigned)(A.Fz >> Dp) & 1u);
+    const bool go = !slow & (sib | (inbox & !out0));
+    A.s = go ? (sib ? ssib : sroot) : 0;
+    A.l = sib ? level : 0;
+    A.r = go ? SOC_LT_INSIDE : (slow ? SOC_LT_SLOW : (place ? SOC_LT_LOST : (outside ? SOC_LT_EXIT : SOC_LT_LEAVE)));
+}
+
+// rec = tree[A.s].  Only for A.r == SOC_LT_INSIDE.  The descent and the new place, from where the climb stopped: there the fma of
+// soc_lt_land() rounds nothing.
 template <typename TREE>
+SOC_HD int soc_lt_land_flt(const TREE tree, const SocLtAim &A, const int Lmax, const int what, float rec,
+                           float &px, float &py, float &pz, int &level, int &cx, int &cy, int &cz, int &slot, int &obase, float &dens)
+{
+    float qx = A.Px, qy = A.Py, qz = A.Pz;                  // (a placement: the packet's own position and level, which come back as they were)
+    int   l = A.L;
+    const int r = soc_lt_land(tree, A, Lmax, what, rec, qx, qy, qz, l, cx, cy, cz, slot, obase, dens);
+    px = qx;  py = qy;  pz = qz;  level = l;
+    return r;
+}
+
+// both halves in one call (host harness, slow paths)
+template <bool FLT = false, typename TREE>
 SOC_HD int soc_lt_move(const TREE tree, const SocLBrick &K, const int NX, const int NY, const int NZ, const int Lmax, const int kexp,
                        const int what, float &px, float &py, float &pz, int &level, int &cx, int &cy, int &cz, int &slot, int &obase,
                        float &dens, int &Rx, int &Ry, int &Rz)
 {
     SocLtAim A;
-    soc_lt_aim(K, NX, NY, NZ, Lmax, kexp, what, px, py, pz, level, cx, cy, cz, obase, A);
+    if (FLT) soc_lt_aim_flt(K, NX, NY, NZ, Lmax, what, px, py, pz, level, cx, cy, cz, obase, A);
+    else     soc_lt_aim(K, NX, NY, NZ, Lmax, kexp, what, px, py, pz, level, cx, cy, cz, obase, A);
     Rx = A.Rx;  Ry = A.Ry;  Rz = A.Rz;
     if (A.r != SOC_LT_INSIDE) return A.r;
+    if (FLT) return soc_lt_land_flt(tree, A, Lmax, what, tree[A.s], px, py, pz, level, cx, cy, cz, slot, obase, dens);
     return soc_lt_land(tree, A, Lmax, what, tree[A.s], px, py, pz, level, cx, cy, cz, slot, obase, dens);
 }
 
