@@ -599,9 +599,9 @@ __device__ __forceinline__ void soc_brick_walk(const SocGrid &G, const SocSimPac
 // ---------------------------------------------------------------------------------------
 // The walk on brick-local hierarchies (soc_ltree.h): hierarchies whose Index() the reference evaluates in double.
 // The workgroup copies its brick's cells into LDS (sD: density, or the link to the octet's slots), so a cell step
-// reads and writes LDS only: GetStep's arithmetic, the tally (ds_add_f32), then the new cell from the packet's
+// reads and writes LDS only: GetStep's arithmetic and the amounts of the tally, then the new cell from the packet's
 // integer cell coordinates -- a sibling by slot arithmetic, anything else by a descent from the brick's root cells
-// (soc_lt_aim / soc_lt_land) -- and the new local position from one fma.  Global memory is touched when a packet is taken from
+// (soc_lt_aim / soc_lt_land) -- the new local position from one fma, and the tally itself (ds_add_f32).  Global memory is touched when a packet is taken from
 // the queue or put back, and for the brick of the root cell a leaving packet goes to (rbrick).
 // Packet record here: A = position, photons | B = direction, free path | C = tau, cell coordinates (cx, cy, cz on the
 // cell's level) | D = RNG state, III | scatterings << 24 | level << 29, SimRAM_CL: emitting cell; bit 31: the step
@@ -648,6 +648,17 @@ __device__ __forceinline__ int soc_cell_index(const SocGrid &G, int level, int c
         dens = G.DENS[G.OFF[l] + ind];
     }
     return ind;
+}
+
+// the LDS atomics of one cell step of soc_lbrick_walk: what the step left in slot `st` (delta, in photons), to every tally of the instance
+template <int WINT, bool ALI>
+__device__ __forceinline__ void soc_lbrick_tally(float *sT, float *sI, float *sV, float *sX, const int *sC, const int BV, const int st,
+                                                 const float delta, const float tw, const float ux, const float uy, const float uz, const uint32_t dw)
+{
+    if (ALI) atomicAdd((sC[st] == (int)dw) ? &sX[st] : &sT[st], delta * tw);      // (SimRAM_CL: the record's last word is the emitting cell)
+    else if (WINT != 3) atomicAdd(&sT[st], delta * tw);
+    if (WINT) atomicAdd(&sI[st], delta);
+    if (WINT == 2) { atomicAdd(&sV[st], delta * ux);  atomicAdd(&sV[BV + st], delta * uy);  atomicAdd(&sV[2 * BV + st], delta * uz); }
 }
 
 // RAY: the read-only rays of the scattered-light kernels (soc_sca_events below): no tallies (the LDS holds the cells only), the optical
@@ -775,8 +786,10 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
     // arithmetic and the tally -- skipped by a lane whose packet has just come in from another brick or still needs its
     // cell looked up -- and Index() in the one-path form of soc_ltree.h (soc_lt_aim / soc_lt_land), which serves all of them.
     // Reads of LDS are issued ahead of the arithmetic that does not need them (the slot Index() starts from before the
-    // exponential of the tally; the three reads of the swap arm together, before the stores), so a wave waits for LDS once
-    // per arm, not once per read.
+    // exponential of the tally; the three reads of the swap arm together, before the stores), so a wave waits once for the
+    // reads of an arm, not once per read -- and then once per trip of the landing's descent.  The tally's atomics are issued
+    // after that descent, so that none of these waits is a wait for an atomic of the same iteration
+    // (tools/isa_loop_count.py lists the step arm's lgkmcnt waits; profiles/tally_order_static_mix.txt).
     while (!parked) {
         {
             SOC_PROF(0, 1);  SOC_PROF(1, __popcll(__ballot(oc == SOC_OC_STAY)));  SOC_PROF(7, __popcll(__ballot(oc == SOC_OC_IDLE)));
@@ -983,22 +996,25 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
                 if ((A.slow_every > 0) && (what == SOC_LTM_STEP) && (level > 0) && (((n_tally + 1u + wid) % (unsigned)A.slow_every) == 0u)) r = SOC_LT_SLOW;
                 // the tally of the step.  A lane that only places its packet (no GetStep: tauA = dtau = 0) adds zeros to slot 0
                 // and multiplies its photons by exp(-0) = 1: cheaper than a branch of its own
+                // The amounts are formed here, while the read above is in flight; the LDS atomics themselves are issued AFTER the
+                // landing (soc_lbrick_tally below).  LDS operations of a wave retire in order, and the descent loop of the landing waits
+                // for each of its reads with lgkmcnt(0): an atomic issued ahead of it made the first trip wait for the atomic as well --
+                // a wave-wide scattered ds_add_f32 holds the LDS more than ten times as long as a read (profiles/r03_lds_ops_micro.txt) --
+                // though nothing needs its completion: it returns nothing, and the loop's exit and the barrier before the flush order it.
+                float delta = 0.0f;
+                int   st = 0;
                 {
                     const bool stepped = (what == SOC_LTM_STEP);
                     n_tally += stepped ? 1u : 0u;
                     tau += dtau;
                     if (!RAY) {
                         const float e = (__ballot(!(tauA < 0.34f)) == 0ull) ? soc_expf_small(-tauA) : soc_expf(-tauA);
-                        const float delta = (tauA > SOC_TAULIM) ? (photons * (1.0f - e)) : (photons * tauA * (1.0f - 0.5f * tauA));
-                        const int st = stepped ? slot0 : 0;
-                        if (ALI) atomicAdd((sC[st] == (int)dw) ? &sX[st] : &sT[st], delta * tw);      // (SimRAM_CL: the record's last word is the emitting cell)
-                        else if (WINT != 3) atomicAdd(&sT[st], delta * tw);
-                        if (WINT) atomicAdd(&sI[st], delta);
-                        if (WINT == 2) { atomicAdd(&sV[st], delta * ux);  atomicAdd(&sV[BV + st], delta * uy);  atomicAdd(&sV[2 * BV + st], delta * uz); }
+                        delta = (tauA > SOC_TAULIM) ? (photons * (1.0f - e)) : (photons * tauA * (1.0f - 0.5f * tauA));
+                        st = stepped ? slot0 : 0;
                         photons *= e;
                     }
                 }
-                SOC_PROF_T(1);                                 // GetStep + tally
+                SOC_PROF_T(1);                                 // GetStep + tally amounts
                 const int orx = cx >> level, ory = cy >> level, orz = cz >> level;      // (the root cell the step starts from: for the record of packets entering ROI)
 #if defined(SOC_BRICK_PROF)
                 const bool prof_lands = (r == SOC_LT_INSIDE);
@@ -1008,6 +1024,9 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
 #if defined(SOC_BRICK_PROF)
                 prof_trips = prof_lands ? (level - AM.l) : 0;
 #endif
+                // the tally of the step, whatever its outcome (a step that leaves, exits or goes slow has crossed its cell as well): in
+                // flight across the back-edge -- the next wait that can see it is the one for the next iteration's first read
+                if (!RAY) soc_lbrick_tally<WINT, ALI>(sT, sI, sV, sX, sC, BV, st, delta, tw, ux, uy, uz, dw);
                 const bool inside = (r == SOC_LT_INSIDE);
                 const bool moved  = inside & (what != SOC_LTM_PLACE);
                 // failed step: nudge (SimRAM_PB / HP only); + 0 * u leaves the position as it is

@@ -79,6 +79,14 @@ SOC_HD float soc_lt_pow2(int k) { return soc_u2f((uint32_t)(127 + k) << 23); }
 // x | y << 1 | z << 2 of three octant bits (each 0 or 1), as two shift-and-adds
 SOC_HD unsigned soc_lt_octant(unsigned x, unsigned y, unsigned z) { return x + ((y + (z << 1)) << 1); }
 
+// the smallest of three (IEEE minimum: one v_min3_f32 on the device) and x - floor(x) (v_fract_f32), for soc_lt_aim's slow-step test
+SOC_HD float soc_lt_min3(float a, float b, float c) { return __builtin_fminf(a, __builtin_fminf(b, c)); }
+#if defined(__HIP_DEVICE_COMPILE__)
+#  define SOC_LT_FRACT(x) __builtin_amdgcn_fractf(x)
+#else
+#  define SOC_LT_FRACT(x) ((x) - soc_floorf(x))
+#endif
+
 // Is the step one that Index() (double) would not resolve by exact geometry?  level > 0, pos after the step.
 // thr = 2^(k + level - 30): below it pos/2^level + root coordinate has more than 53 significant bits.
 SOC_HD bool soc_lt_degenerate(float px, float py, float pz, float flx, float fly, float flz, float thr)
@@ -157,11 +165,23 @@ SOC_HD void soc_lt_aim(const SocLBrick &K, const int NX, const int NY, const int
     A.Rx = A.Fx >> Lmax;  A.Ry = A.Fy >> Lmax;  A.Rz = A.Fz >> Lmax;
     // a sibling in the packet's own octet: floor(pos) in {0,1}^3, i.e. nothing of J above bit D
     const bool sib = deep & !place & ((((unsigned)(Jx | Jy | Jz)) >> (D + 1)) == 0u);
-    // not for exact geometry to decide (soc_lt_degenerate; a sibling: POS/2 + octant only, bound 2^(kexp+1))
-    const float mabs = soc_fminf(soc_fabsf(px), soc_fminf(soc_fabsf(py), soc_fabsf(pz)));
-    const float mmin = soc_fminf(px, soc_fminf(py, pz));
-    const bool onface = (px == soc_floorf(px)) || (py == soc_floorf(py)) || (pz == soc_floorf(pz));
-    const bool slow = deep & !place & (sib ? !(mmin >= soc_lt_pow2(kexp + 1)) : (!(mabs >= soc_lt_pow2(kexp + L)) | onface));
+    // not for exact geometry to decide (soc_lt_degenerate; a sibling: POS/2 + octant only, bound 2^(kexp+1)).  Straight-line: both
+    // bounds tests are formed for every lane and `sib` selects the minimum and the bound (a wave holds lanes of both kinds, so a
+    // branch ran both sides under exec-mask bookkeeping), three-way minima (v_min3_f32, with |x| as an operand modifier) and the
+    // face test as "the smallest of the three fractional parts is zero".  The same predicate as
+    //     sib ? !(soc_fminf(px, soc_fminf(py, pz)) >= 2^(kexp+1))
+    //         : (!(soc_fminf(|px|, soc_fminf(|py|, |pz|)) >= 2^(kexp+L)) | px == floor(px) | py == floor(py) | pz == floor(pz))
+    // for every finite position: the IEEE minimum differs from soc_fminf ((b < a) ? b : a) only when an operand is a NaN and in the
+    // sign of a zero result, and the `>=` against a positive bound and the `== 0` below tell neither -0 from +0; x - floor(x) is
+    // zero exactly when x is an integer (a difference of two floats is zero only if they are equal; v_fract_f32 likewise, and its
+    // clamp below 1 keeps a tiny negative x away from 0), fractional parts are never negative, so their minimum is zero exactly
+    // when one of them is.  (An infinite coordinate -- GetStep's minimum over the axes never makes one -- has no fractional part.)
+    const float mabs = soc_lt_min3(soc_fabsf(px), soc_fabsf(py), soc_fabsf(pz));
+    const float mmin = soc_lt_min3(px, py, pz);
+    const bool onface = (soc_lt_min3(SOC_LT_FRACT(px), SOC_LT_FRACT(py), SOC_LT_FRACT(pz)) == 0.0f);
+    const float mlow = sib ? mmin : mabs;
+    const float bound = soc_lt_pow2(kexp + (sib ? 1 : L));
+    const bool slow = deep & !place & (!(mlow >= bound) | (!sib & onface));
     const bool out0 = !deep & !place & ((px == 0.0f) | (py == 0.0f) | (pz == 0.0f));   // root grid: pos <= 0 leaves the model (:214)
     const int  rx = A.Rx - K.x0, ry = A.Ry - K.y0, rz = A.Rz - K.z0;
     const bool inbox = !(((unsigned)rx >= (unsigned)K.bx) | ((unsigned)ry >= (unsigned)K.by) | ((unsigned)rz >= (unsigned)K.bz));
