@@ -91,7 +91,10 @@ int soc_set_exec(soc_ctx *ctx, int mode, int brick_log2);
  * hierarchies), "chunk" (packets per workgroup, <= 4096; <= 32768 on brick-local hierarchies), "steps_per_visit" (cell steps
  * before a packet goes back to its queue), "swap_lanes" (lanes of a wave that must wait before the packet swap runs),
  * "climb_lanes" (the same for the deferred Index() of the global-tree form), "brick_cells" (cells per brick on hierarchies,
- * <= 36864; rays on single-level grids: bricks of the largest cube within), "tail_lanes", "park_below" (hierarchies: brick queues shorter than this and than the mean wait a pass; 1 = never), "population" (packets in flight), "hash_slots" (per-workgroup
+ * <= 36864; rays on single-level grids: bricks of the largest cube within), "brick_partition" (brick-local hierarchies: how the root
+ * grid is cut into the boxes of the bricks.  0, the built-in choice, and 2: of two partitions -- tiles of 16^3 root cells halved until
+ * they fit, and slabs / columns / boxes sized by the cells they hold -- the one whose boxes have the smaller total face area;
+ * 1: the tiles alone.  A change rebuilds the handle's bricks at its next sweep, as a change of "brick_cells" does), "tail_lanes", "park_below" (hierarchies: brick queues shorter than this and than the mean wait a pass; 1 = never), "population" (packets in flight), "hash_slots" (per-workgroup
  * arrival table, power of two), "general_kernel" (1: no background-only kernel), "global_tree" (1: hierarchies are walked in
  * global memory also where the brick-local form applies), "slow_every" (test knob of that form),
  * "oversubscribe", "verbose", "abu_local" (1: launches with per-cell opacities -- soc_set_opt, soc_set_optical_abu -- take the

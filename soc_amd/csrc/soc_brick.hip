@@ -2191,6 +2191,7 @@ struct SocOctBricks {
 // brick-local hierarchies (soc_lbricks.h) on the device, built once per grid and cap
 struct SocLBricksDev {
     bool valid = false, failed = false;
+    bool tiles = false;                        // the bricks are the tiles of soc_lbricks.h alone
     int  NB = 0, cap = 0, max_slots = 0;
     size_t cells = 0, slots = 0;               // slots: entries of btree and bcell
     DevBuf<SocLBrick> lbr;
@@ -2237,21 +2238,24 @@ static hipError_t soc_oct_build(SocOctBricks &ob, const SocGrid &G, int CAP, hip
 // Bricks for the walk on brick-local hierarchies, and for the rays on single-level grids.  hipErrorNotSupported: the hierarchy cannot
 // be cut that way (a root cell with more than cap cells below it) -- the caller keeps the sweep that reads the hierarchy from global
 // memory; a single-level grid holds a cell without a positive density -- its rays stay with the direct kernel.
-static hipError_t soc_lb_build(SocLBricksDev &lb, const SocGrid &G, int cap, hipStream_t st, bool verbose)
+// tiles: soc_set_tuning("brick_partition", 1) -- the tiles of soc_lbricks.h alone (the bricks of a handle are rebuilt when the key changes).
+static hipError_t soc_lb_build(SocLBricksDev &lb, const SocGrid &G, int cap, bool tiles, hipStream_t st, bool verbose)
 {
-    if (lb.cap == cap && lb.cells == (size_t)G.CELLS) {
+    if (lb.cap == cap && lb.tiles == tiles && lb.cells == (size_t)G.CELLS) {
         if (lb.valid) return hipSuccess;
         if (lb.failed) return hipErrorNotSupported;
     }
     lb.valid = false;  lb.failed = false;
-    lb.cap = cap;  lb.cells = (size_t)G.CELLS;
+    lb.cap = cap;  lb.tiles = tiles;  lb.cells = (size_t)G.CELLS;
     std::vector<float> D((size_t)G.CELLS);
     BCHK(hipStreamSynchronize(st));
     BCHK(hipMemcpy(D.data(), G.DENS, (size_t)G.CELLS * 4, hipMemcpyDeviceToHost));
     SocLBricksHost H;
+    const auto t0 = std::chrono::steady_clock::now();
     // (a single-level grid: boxes of root cells, `cap` the cube of their edge)
     const bool built = (G.LEVELS == 1) ? soc_cbricks_build(G.NX, G.NY, G.NZ, D.data(), soc_cart_edge(cap), H)
-                                       : soc_lbricks_build(G.NX, G.NY, G.NZ, G.LEVELS, G.LCELLS, G.OFF, D.data(), cap, H);
+                                       : soc_lbricks_build(G.NX, G.NY, G.NZ, G.LEVELS, G.LCELLS, G.OFF, D.data(), cap, H, tiles ? SOC_LB_TILES : SOC_LB_BEST);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!built || H.bricks.size() >= (1u << 20)) {
         lb.failed = true;
         return hipErrorNotSupported;
@@ -2267,9 +2271,14 @@ static hipError_t soc_lb_build(SocLBricksDev &lb, const SocGrid &G, int cap, hip
     BCHK(upload(lb.rbrick, H.rbrick, st));
     lb.NB = NB;  lb.max_slots = H.max_slots;  lb.slots = H.btree.size();
     lb.valid = true;
-    if (verbose)
-        fprintf(stderr, "soc_brick: %s of %d cells -> %d brick-local hierarchies of <= %d cells (largest %d, mean %.0f)\n",
-                (G.LEVELS == 1) ? "grid" : "hierarchy", G.CELLS, NB, cap, H.max_slots, (double)G.CELLS / NB);
+    if (verbose) {
+        double area = 0.0;                                               // faces of root cells on the boxes of all bricks
+        for (const SocLBrick &K : H.bricks) area += 2.0 * ((double)K.bx * K.by + (double)K.by * K.bz + (double)K.bz * K.bx);
+        fprintf(stderr, "soc_brick: %s of %d cells -> %d brick-local hierarchies of <= %d cells (largest %d, mean %.0f, fill %.3f), face area %.4g",
+                (G.LEVELS == 1) ? "grid" : "hierarchy", G.CELLS, NB, cap, H.max_slots, (double)G.CELLS / NB, (double)G.CELLS / NB / cap, area);
+        if (G.LEVELS > 1) fprintf(stderr, " (%s; tiles %.4g, slabs %.4g)", H.slabs ? "slabs" : "tiles", H.area_tiles, H.area_slabs);
+        fprintf(stderr, ", built in %.2f s\n", secs);
+    }
     return hipSuccess;
 }
 
@@ -2407,6 +2416,7 @@ static hipError_t plan_sweep(SocSweepPlan &pl, const SocGrid &G, const SocSim *S
     const int cap_abu = (V.wint && !int_only) ? 3456 : 4352;
     pl.capl = (tune.CAP > 0) ? tune.CAP : cart ? cedge * cedge * cedge : (sca ? 17408 : V.abu ? cap_abu : (ali ? (V.wint ? 3456 : 4352) : (V.wint == 2 ? 2944 : (V.wint && !int_only) ? 5888 : 8704)));
     if (pl.capl < 8 || pl.capl > 36864) return hipErrorInvalidValue;
+    pl.tiles = (tune.partition == 1);
     pl.EQ = 3;
     for (int l = 0; l < nlaunch; l++) pl.roi = pl.roi || (S[l].ROISAVE && S[l].ROI);
     if (pl.roi) {
@@ -2437,7 +2447,7 @@ static hipError_t build_bricks(SocBrickArgs &A, const SocSweepPlan &pl, SocSweep
     A.sib_thr = ldexpf(1.0f, k - 29);
     A.kexp = k - 30;
     if (pl.form == 3) {
-        BCHK(soc_lb_build(sw.lb, G, pl.capl, st, verbose));
+        BCHK(soc_lb_build(sw.lb, G, pl.capl, pl.tiles, st, verbose));
         const SocLBricksDev &lb = sw.lb;
         A.NB = lb.NB;
         A.CAP = (lb.max_slots + 63) & ~63;                               // slots in LDS
@@ -2536,7 +2546,10 @@ static hipError_t plan_kernel(SocSweepPlan &pl, SocBrickArgs &A, SocSweepSize &s
     const long long pop = (pl.form == 3) ? 600000000LL : pl.octree ? 26000000LL : std::max(2700000LL, 5300LL * A.NBQ);
     A.target = (int)std::min<long long>((tune.POP > 0) ? tune.POP : std::min(pop, 2000000000LL), sz.count);
     sz.maxdesc = (int)(((uint32_t)A.target + A.P - 1) / A.P) + sz.NQ + K.n;
-    A.HS = (sz.NQ > 4096) ? 1024 : 0;
+    // the arrivals table: one entry per queue while that is no larger than the hash table of 2 x 1024 entries.  (The cells per brick are
+    // chosen so that two workgroups share a CU's LDS with 8 KB left for this table; with 2049 ... 4096 queues the table of one entry per
+    // queue took up to 16 KB and left room for one workgroup.)
+    A.HS = (sz.NQ > 2048) ? 1024 : 0;
     if (tune.HS > 0) A.HS = tune.HS;
     if (A.HS & (A.HS - 1)) return hipErrorInvalidValue;
     // LDS: the brick's tallies (brick-local: its cells too -- + INT, + the vector sums, + XAB and the cell numbers; rays: the cells only),

@@ -358,10 +358,12 @@ int soc_set_tuning(soc_ctx *c, const char *name, int value)
         { "climb_lanes", &c->tune.CTH }, { "brick_cells", &c->tune.CAP }, { "tail_lanes", &c->tune.TAIL }, { "park_below", &c->tune.park }, { "population", &c->tune.POP },
         { "hash_slots", &c->tune.HS }, { "global_tree", &c->tune.global_tree }, { "slow_every", &c->tune.slow_every },
         { "general_kernel", &c->tune.nolean }, { "oversubscribe", &c->tune.oversub }, { "verbose", &c->tune.verbose },
-        { "abu_local", &c->tune.abu_local }, { "float_local", &c->tune.float_local } };
+        { "abu_local", &c->tune.abu_local }, { "float_local", &c->tune.float_local }, { "brick_partition", &c->tune.partition } };
     for (auto &t : tab)
         if (!strcmp(name, t.n)) {
+            if (t.p == &c->tune.partition && value > 2) return fail(c, SOC_ERR_ARG, "soc_set_tuning: brick_partition = %d (0 built-in, 1 tiles, 2 smallest face area)", value);
             if (t.p == &c->tune.CAP && value != c->tune.CAP) soc_sweep_invalidate(c->sweep);
+            if (t.p == &c->tune.partition && (value == 1) != (c->tune.partition == 1)) soc_sweep_invalidate(c->sweep);      // (0 and 2 build the same bricks)
             *t.p = value;
             return SOC_OK;
         }

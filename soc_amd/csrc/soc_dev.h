@@ -321,6 +321,8 @@ struct SocBrickTune {
     int oversub;               // experiment: background work items beyond 8*AREA are not clipped
     int verbose;
     int abu_local;             // brick-local hierarchies: launches with per-cell opacities (WITH_ABU) take the brick-local walk too (0 = built-in choice: off)
+    int partition;             // brick-local hierarchies: how the root grid is cut into bricks (soc_lbricks.h).  0 = built-in choice: of the tiles and the slabs the
+                               // partition with the smaller total face area; 1 = the tiles alone (16^3 root cells, halved); 2 = as 0
     int float_local;           // hierarchies with Index() in float (NX <= DIMLIM) take the brick-local walk too, in its float form (0 = built-in choice: off)
 };
 
@@ -393,6 +395,7 @@ struct SocSweepPlan {
     bool rays, hpx, hpsky;     // the scattered-light sweep of rays; its image a Healpix map seen from a position; SimRAM_HP launches in it
     bool roi;                  // brick-local: the record of packets entering ROI (a fourth event queue per launch)
     int  capl;                 // brick-local: cells per brick (rays on a Cartesian grid: the cube of the brick's edge)
+    bool tiles;                // brick-local: the bricks are the tiles of soc_lbricks.h alone (soc_set_tuning("brick_partition", 1))
     // SocBrickArgs: the form's defaults with soc_set_tuning applied (CAP: leaves per brick of a hierarchy in global memory)
     int  T, P, KCAP, FTH, CTH, CAP, TAIL, PARK, EQ, slow_every;
     size_t lds;                // dynamic LDS of the pass kernel

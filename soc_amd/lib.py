@@ -344,7 +344,8 @@ class Engine:
 
     def set_tuning(self, **params):
         """shape of the brick sweep (soc_set_tuning): threads, chunk, steps_per_visit, swap_lanes, climb_lanes,
-        brick_cells, tail_lanes, park_below, population, hash_slots, general_kernel, oversubscribe, verbose, abu_local
+        brick_cells, brick_partition (brick-local hierarchies: 1 the tiles of 16^3 root cells alone, 2 -- and 0 -- the partition with the
+        smaller total face area), tail_lanes, park_below, population, hash_slots, general_kernel, oversubscribe, verbose, abu_local
         (1: launches with per-cell opacities take the brick-local walk of a hierarchy that has one), float_local (1: hierarchies
         whose Index() runs in float -- NX <= 100, or <= 399 with two levels -- take the brick-local walk too, in its float form);
         0 = built-in"""
