@@ -24,7 +24,8 @@ import numpy as np
 
 from . import files, launch
 from .ini import User
-from .launch import PLANCK, PARSEC
+from .launch import PARSEC
+from .maps import MapProducts
 
 
 class UnsupportedOption(RuntimeError):
@@ -152,41 +153,28 @@ def _check_supported(USER, NDUST, WITH_MSF, engine=None):
         raise UnsupportedOption("ini options not supported by this engine: " + ", ".join(bad))
 
 
-def _abu_local(method):
-    """A transfer stage of AbsorptionRun: with an abundance file the engine's `abu_local` routing is on while it runs (see
+def _local_routing(abu=True):
+    """Decorator of a transfer stage of AbsorptionRun: with an abundance file the engine's `abu_local` routing is on while it runs (see
     AbsorptionRun.ABU_LOCAL), on a hierarchy whose Index() runs in float its `float_local` routing (AbsorptionRun.FLOAT_LOCAL), and the
-    engine has its built-in routing back afterwards.  A run with neither issues no tuning call."""
-    @functools.wraps(method)
-    def stage(self, *a, **kw):
-        keys = []
-        if self.WITH_ABU and self.ABU_LOCAL:
-            keys.append("abu_local")
-        if self.FLOAT_LOCAL and float_index(self.cloud):
-            keys.append("float_local")
-        for k in keys:
-            self._tune(**{k: 1})
-        try:
-            return method(self, *a, **kw)
-        finally:
-            for k in reversed(keys):
-                self._tune(**{k: 0})
-    return stage
-
-
-def _float_local(method):
-    """the `float_local` half of _abu_local alone: the stage of the scattered-light driver (soc_amd.asocs), whose launches with
-    per-cell opacities have no sweep to be routed to"""
-    @functools.wraps(method)
-    def stage(self, *a, **kw):
-        on = self.FLOAT_LOCAL and float_index(self.cloud)
-        if on:
-            self._tune(float_local=1)
-        try:
-            return method(self, *a, **kw)
-        finally:
-            if on:
-                self._tune(float_local=0)
-    return stage
+    engine has its built-in routing back afterwards, in reverse order.  A run with neither issues no tuning call.  abu=False: the
+    `float_local` half alone, for the scattered-light driver (soc_amd.asocs), whose launches with per-cell opacities have no sweep to go to."""
+    def wrap(method):
+        @functools.wraps(method)
+        def stage(self, *a, **kw):
+            keys = []
+            if abu and self.WITH_ABU and self.ABU_LOCAL:
+                keys.append("abu_local")
+            if self.FLOAT_LOCAL and float_index(self.cloud):
+                keys.append("float_local")
+            for k in keys:
+                self._tune(**{k: 1})
+            try:
+                return method(self, *a, **kw)
+            finally:
+                for k in reversed(keys):
+                    self._tune(**{k: 0})
+        return stage
+    return wrap
 
 
 def float_index(cloud):
@@ -195,7 +183,7 @@ def float_index(cloud):
     return cloud.LEVELS > 1 and cloud.NX <= (399 if cloud.LEVELS < 3 else 100)
 
 
-class AbsorptionRun:
+class AbsorptionRun(MapProducts):
     """The constant-source part of an ASOC run.  ``engine`` is a soc_amd.lib.Engine (or an
     object with the same methods); ``comm`` a soc_amd.dist.Comm."""
     _hpbg_launch = staticmethod(launch.hpbg_launch)           # the Healpix background's launch shape, see _constant_launch
@@ -460,6 +448,11 @@ class AbsorptionRun:
         """the column of the absorbed file that holds IFREQ (`libabs`: only the selected frequencies have one)"""
         return self.lib_col[IFREQ] if self.U.LIB_ABS else IFREQ
 
+    def emitted_range(self):
+        """(I1, I2): the first and the last frequency inside `remit`, the columns of the emitted file (ASOC.py:199-200)"""
+        m = np.nonzero((self.FFREQ >= self.U.REMIT_F[0]) & (self.FFREQ <= self.U.REMIT_F[1]))[0]
+        return int(m[0]), int(m[-1])
+
     def _seed(self, IFREQ, rng):
         """seed of the launches at IFREQ (ASOC.py:1247); with seed <= 0 a random one, the same on every rank"""
         if self.U.SEED > 0:
@@ -598,7 +591,7 @@ class AbsorptionRun:
         return [(self.LAUNCH_GROUPS if (absorbed and c.LEVELS == 1 and U.SAVE_INTENSITY == 0 and not U.WITH_ROI_SAVE and II != 3)
                  else self.SEQUENTIAL, ['PS', 'BG', 'DE', 'ROI'][II], [step(f, [(II, L)]) for f in freqs]) for II, L in blocks], owner
 
-    @_abu_local
+    @_local_routing()
     def simulate_constant_sources(self):
         """for II in (point sources, background, diffuse): for IFREQ: launch (ASOC.py:1028-1545), in the order and batches of _plan.
         Returns CTABS[CELLS] and FABSORBED[CELLS,NFREQ] (or None with noabsorbed)."""
@@ -733,7 +726,7 @@ class AbsorptionRun:
         self.timers["Tpull"] += time.time() - t0
 
     # ---------------------------------------------------------------------------------
-    @_abu_local
+    @_local_routing()
     def emission_iterations(self, CTABS, FABSORBED):
         """Simulation <-> temperature cycles (ASOC.py:1593-2260, the paths without reference field and
         ALI): per iteration the dust emission of the previous one is simulated with SimRAM_CL
@@ -744,8 +737,7 @@ class AbsorptionRun:
         Returns (TNEW or None, EMITTED[CELLS, REMIT_NFREQ])."""
         U, e, c = self.U, self.eng, self.cloud
         CELLS, NFREQ, FFREQ = c.CELLS, self.NFREQ, self.FFREQ
-        m = np.nonzero((FFREQ >= U.REMIT_F[0]) & (FFREQ <= U.REMIT_F[1]))[0]
-        I1, I2 = int(m[0]), int(m[-1])
+        I1, I2 = self.emitted_range()
         solve = (not U.NOSOLVE) and bool(U.NOABSORBED)
         if solve and self.NDUST > 1:
             raise ValueError("temperatures can be solved here for a single dust component only (ASOC.py:260-263)")
@@ -940,8 +932,7 @@ class AbsorptionRun:
         U, e, c = self.U, self.eng, self.cloud
         if self.NDUST > 1:
             raise ValueError("loadtemp recomputes the emission of a single equilibrium dust (ASOC.py:757-760 uses AFABS[0])")
-        m = np.nonzero((self.FFREQ >= U.REMIT_F[0]) & (self.FFREQ <= U.REMIT_F[1]))[0]
-        I1, I2 = int(m[0]), int(m[-1])
+        I1, I2 = self.emitted_range()
         TNEW = files.read_temperature(U.file_temperature, c)
         FACTOR_f, LENGTH_f = launch.kernel_literals(U.GL)
         e.set_temperature(TNEW)
@@ -951,415 +942,6 @@ class AbsorptionRun:
         return TNEW, EMITTED
 
     # ---------------------------------------------------------------------------------
-    def write_maps(self, EMITTED):
-        """Surface-brightness maps from the emission (ASOC.py:2924-3177, the plain `Mapping` path): for every
-        direction map_dir_XX.bin = int32 NPIX.x, NPIX.y + one float32 [NPIX.y, NPIX.x] image [Jy/sr] per selected
-        frequency.  `perspective` gives the longitude x latitude image seen from that position.  Optical-depth
-        images for `savetau` frequencies are written as <file>_tau_<um>.bin, the column density (`savetau file -1`) as
-        <file>_colden.fits; `fits` with `mapum` gives one FITS image per direction and frequency instead.  NPIX.y < 0:
-        write_healpix_maps.  Polarisation maps: write_polmaps.
-        `maplevels 1` (not a key of the reference) adds map_dir_XX_L.bin per direction (map_dir_00_L.bin for a Healpix map):
-        int32 NPIX.x, NPIX.y, int32 [images, LEVELS], then for every image of the plain file, in its order, LEVELS float32 planes
-        [Jy/sr] -- plane l is the plain map with the emission of all cells not on hierarchy level l set to zero, so the planes of
-        an image add up to it.  The frequencies then go through _map_blocks in batches of min(max(1, FAST_MAP), map_block_max);
-        the plain products are the same bytes.  With `fits` + `mapum` the level file is still this .bin.  maplevels has no
-        effect on the `polmap` products (write_polmaps, write_healpix_polmaps)."""
-        U, e, c = self.U, self.eng, self.cloud
-        if U.NPIX[1] == 0:
-            self.log("mapping with NPIX.y == 0: neither the flat (NPIX.y > 0, ASOC.py:2924) nor the Healpix branch (NPIX.y < 0, :3185)")
-            return
-        if U.FAST_MAP >= 999:
-            return self.write_level_maps(EMITTED)
-        if U.NPIX[1] < 0:
-            return self.write_healpix_maps(EMITTED)
-        NFREQ, FFREQ = self.NFREQ, self.FFREQ
-        m = np.nonzero((FFREQ >= U.REMIT_F[0]) & (FFREQ <= U.REMIT_F[1]))[0]
-        I1, I2 = int(m[0]), int(m[-1])
-        if U.LIB_MAPS:                                             # every frequency of the file, whatever `remit` says (ASOC.py:202-204)
-            I1, I2 = 0, NFREQ - 1
-        NDIR, ODIR, RA, DE = launch.set_observer_directions(U.OBS_THETA, U.OBS_PHI)
-        centre = U.MAPCENTRE if U.MAPCENTRE[0] > -1e7 else (0.5 * c.NX, 0.5 * c.NY, 0.5 * c.NZ)   # ASOC_aux.py:791-793
-        KK = (1.0e23 / launch.FACTOR) * PLANCK / (4.0 * np.pi) * (U.GL * PARSEC)                 # ASOC.py:2997-2998
-        _, LENGTH_f = launch.kernel_literals(U.GL)
-        singles = np.asarray(getattr(U, "SINGLE_MAP_FREQ", []), np.float64)
-        savetau = np.asarray(getattr(U, "savetau_freq", []), np.float64)
-        # `fits` together with `mapum`: one FITS file per direction and selected frequency instead of map_dir_XX.bin
-        # (ASOC.py:2977-2996); the header is MakeFits' (files.write_fits), the pixel GL*MAP_DX over the distance (1 kpc unless given)
-        using_fits = (getattr(U, "FITS", 0) > 0) and (len(singles) > 0)
-        pix = U.GL * U.MAP_DX / (U.DISTANCE if U.DISTANCE > 0.0 else 1000.0)
-        fps = []
-        if self.rank == 0 and not using_fits:
-            for idir in range(NDIR):
-                fp = open("map_dir_%02d.bin" % idir, "wb")
-                np.asarray([U.NPIX[0], U.NPIX[1]], np.int32).tofile(fp)
-                fps.append(fp)
-        maplevels = getattr(U, "MAP_LEVELS", 0) > 0
-        # what is computed: (IFREQ, save_spe, save_tau, save_colden) in ascending frequency
-        sel = []
-        first_freq = True
-        for IFREQ in range(NFREQ):
-            FREQ = float(FFREQ[IFREQ])
-            if U.LIB_MAPS and IFREQ not in self.lib_col:           # the loop is over the whole table, the others are skipped (ASOC.py:3032-3038)
-                continue
-            save_spe = (IFREQ >= I1) and (IFREQ <= I2)
-            if (FREQ < U.MAP_FREQ[0]) or (FREQ > U.MAP_FREQ[1]):
-                continue
-            save_tau, save_colden = 0, 0
-            if len(savetau) > 0:                                   # ASOC.py:3048-3058
-                if np.min(np.abs((savetau - FREQ) / FREQ)) < 0.001:
-                    save_tau = 1
-                if (save_tau == 0) and first_freq and (np.min(savetau) <= 0.0):
-                    save_colden = 1                                # `savetau file -1`: column density, with the first mapped frequency
-            first_freq = False
-            if len(singles) > 0 and np.min(np.abs(FREQ - singles)) / FREQ > 0.005:
-                save_spe = False
-            if not save_spe and not save_tau and not save_colden:
-                continue
-            sel.append((IFREQ, save_spe, save_tau, save_colden))
-
-        def emission(IFREQ, save_spe):
-            col = self.lib_col[IFREQ] if U.LIB_MAPS else IFREQ - I1     # (ASOC.py:3104-3105: column OIFREQ of the library's emission)
-            return np.asarray(KK * float(FFREQ[IFREQ]) * EMITTED[:, col], np.float32) if save_spe else np.zeros(c.CELLS, np.float32)
-
-        def write(IFREQ, idir, MAP, TAU, save_spe, save_tau, save_colden):
-            """the files of one frequency and direction; TAU: the optical depth, or with save_colden the column density"""
-            if self.rank != 0:
-                return
-            um = launch.C_LIGHT / float(FFREQ[IFREQ]) * 1.0e4
-            ums = '%.0f' % um if um > 20.0 else ('%.1f' % um if um > 2.0 else '%.2f' % um)
-            suffix = '_dir%d' % idir if NDIR > 1 else ''
-            tail = '' if NDIR == 1 else '_%03d' % idir
-            if save_spe:
-                if using_fits:                                  # :3143-3148
-                    files.write_fits("%s_%s%s.fits" % (U.FITS_PREFIX, ums, tail), MAP, U.FITS_RA, U.FITS_DE, pix)
-                else:
-                    np.asarray(MAP, np.float32).tofile(fps[idir])
-            if save_colden:                                     # always a FITS image in the reference (:3152-3159)
-                files.write_fits('%s_colden%s%s.fits' % (U.file_savetau, suffix, tail), TAU, U.FITS_RA, U.FITS_DE, pix)
-            if save_tau:                                        # :3160-3171
-                name = '%s_tau_%s%s%s' % (U.file_savetau, ums, suffix, tail)
-                if using_fits:
-                    files.write_fits(name + '.fits', TAU, U.FITS_RA, U.FITS_DE, pix)
-                else:
-                    np.asarray(TAU, np.float32).tofile(name + '.bin')
-
-        if maplevels:
-            # `maplevels 1`: the maps through the batch path (the same bytes), and per direction map_dir_XX_L.bin with the levels of
-            # every image of the plain file, in its order -- a .bin also where `fits` + `mapum` turn the plain maps into FITS files
-            lfps = [self._open_level_file(idir, sum(1 for q in sel if q[1])) for idir in range(NDIR)] if self.rank == 0 else []
-            views = [(ODIR[idir], RA[idir], DE[idir]) for idir in range(NDIR)]
-            for batch, planes in self._map_blocks(sel, emission, views, centre, LENGTH_f, levels=True):
-                for idir, (MAPX, TAUX, COLDEN, MAPL) in enumerate(planes):
-                    for k, (IFREQ, save_spe, save_tau, save_colden) in enumerate(batch):
-                        write(IFREQ, idir, MAPX[k], COLDEN if save_colden else TAUX[k], save_spe, save_tau, save_colden)
-                        if save_spe and lfps:
-                            np.asarray(MAPL[k], np.float32).tofile(lfps[idir])
-            for fp in lfps:
-                fp.close()
-        elif 2 <= U.FAST_MAP <= 998:
-            # `mapping nx ny dx NF`: the same maps, up to NF frequencies per walk along the lines of sight
-            views = [(ODIR[idir], RA[idir], DE[idir]) for idir in range(NDIR)]
-            for batch, planes in self._map_blocks(sel, emission, views, centre, LENGTH_f):
-                for idir, (MAPX, TAUX, COLDEN) in enumerate(planes):
-                    for k, (IFREQ, save_spe, save_tau, save_colden) in enumerate(batch):
-                        write(IFREQ, idir, MAPX[k], COLDEN if save_colden else TAUX[k], save_spe, save_tau, save_colden)
-        else:
-            for IFREQ, save_spe, save_tau, save_colden in sel:
-                ABS, SCA = self._optical_for(IFREQ)
-                EMIT = emission(IFREQ, save_spe)
-                for idir in range(NDIR):
-                    MAP, TAU = e.map(EMIT, ODIR[idir], RA[idir], DE[idir], U.NPIX, U.MAP_DX, centre, ABS, SCA,
-                                     INTOBS=U.INTOBS, save_colden=save_colden, LENGTH=LENGTH_f)
-                    write(IFREQ, idir, MAP, TAU, save_spe, save_tau, save_colden)
-        for fp in fps:
-            fp.close()
-
-    def _open_level_file(self, idir, images):
-        """map_dir_XX_L.bin of `maplevels 1`: int32 NPIX.x, NPIX.y, int32 [images, LEVELS]; the caller appends per image LEVELS float32
-        planes [Jy/sr], plane l what the cells of level l add to the plain map's image."""
-        fp = open("map_dir_%02d_L.bin" % idir, "wb")
-        np.asarray([self.U.NPIX[0], self.U.NPIX[1]], np.int32).tofile(fp)
-        np.asarray([images, self.cloud.LEVELS], np.int32).tofile(fp)
-        return fp
-
-    def write_level_maps(self, EMITTED):
-        """`mapping nx ny dx 999` (a fourth argument >= 999): one image per hierarchy level (ASOC.py:3323-3438 -> the Mapping of
-        kernel_ASOC_map_H.c).  For every direction map_dir_XX_H.bin = int32 NPIX.x, NPIX.y, then int32 number of frequencies
-        written, LEVELS, then per frequency of the emitted range inside `wavelength` LEVELS float32 images [NPIX.y, NPIX.x]
-        [Jy/sr]: image l holds the emission of the cells of level l, attenuated by everything in front of them.  `perspective`
-        gives the longitude x latitude images seen from that position.  `mapum` selects nothing here (ASOC.py:3363-3375), and
-        `mapint`, `threshold` and `roimap` have no effect: that kernel tests none of them.  With abundances the extinction is
-        the per-cell sum (`singleabu`, `optishalf` included), which the reference has under a macro it never defines.
-        The walk is that kernel file's own, bit for bit: on a hierarchy it loses a ray where the ray climbs out of an octet into
-        a root leaf, so the images hold only what lies in front of that point."""
-        U, e, c = self.U, self.eng, self.cloud
-        FFREQ = self.FFREQ
-        m = np.nonzero((FFREQ >= U.REMIT_F[0]) & (FFREQ <= U.REMIT_F[1]))[0]
-        I1, I2 = int(m[0]), int(m[-1])
-        NDIR, ODIR, RA, DE = launch.set_observer_directions(U.OBS_THETA, U.OBS_PHI)
-        centre = U.MAPCENTRE if U.MAPCENTRE[0] > -1e7 else (0.5 * c.NX, 0.5 * c.NY, 0.5 * c.NZ)   # ASOC_aux.py:791-793
-        KK = (1.0e23 / launch.FACTOR) * PLANCK / (4.0 * np.pi) * (U.GL * PARSEC)                 # ASOC.py:3369-3370
-        sel = [i for i in range(I1, I2 + 1) if U.MAP_FREQ[0] <= float(FFREQ[i]) <= U.MAP_FREQ[1]]
-        fps = []
-        if self.rank == 0:
-            for idir in range(NDIR):
-                fp = open("map_dir_%02d_H.bin" % idir, "wb")
-                np.asarray([U.NPIX[0], U.NPIX[1]], np.int32).tofile(fp)
-                np.asarray([len(sel), c.LEVELS], np.int32).tofile(fp)
-                fps.append(fp)
-        for IFREQ in sel:
-            ABS, SCA = self._optical_for(IFREQ)
-            EMIT = np.asarray(EMITTED[:, IFREQ - I1] * np.float32(KK) * np.float32(float(FFREQ[IFREQ])), np.float32)    # :3404
-            for idir in range(NDIR):
-                MAP = e.map_levels(EMIT, ODIR[idir], RA[idir], DE[idir], U.NPIX, U.MAP_DX, centre, ABS, SCA, INTOBS=U.INTOBS)
-                if self.rank == 0:
-                    np.asarray(MAP, np.float32).tofile(fps[idir])
-        for fp in fps:
-            fp.close()
-        return ["map_dir_%02d_H.bin" % idir for idir in range(NDIR)]
-
-    def polarisation_field(self, healpix=False, R=None):
-        """The three B files of `polmap` (the layout of the cloud file: every cell, parents included) with the polarisation
-        reduction factor R of `polred` encoded in the length of the vectors, B * R / sqrt(B^2 + 1e-10) (ASOC.py:3676-3720):
-        `adhoc` -- R from the dust temperatures of the `temperature` file; `rhofun_<threshold>_<width>` -- from the density
-        (times `density`); anything else -- a plain file [cells, {R}], clipped to [1e-6, 0.999999].  polstat 3 uses the
-        vectors as they are.  healpix: the encoding of the Healpix branch (ASOC.py:3836-3872), B * R / sqrt(B^2) with a
-        file's R as it is.  R: the factors R[cells] themselves where the ini names no `polred` -- treated as a plain file's are."""
-        U, c = self.U, self.cloud
-        BB = [np.asarray(files.read_temperature(f, c), np.float32) for f in U.BFILES[:3]]
-        polred = getattr(U, "file_polred", "")
-        if len(polred) == 0 and R is not None:
-            polred, given = "the polarisation reduction factors of the emission stage", np.asarray(R, np.float32)
-        else:
-            given = None
-        if U.POLSTAT != 3 and len(polred) > 0:
-            if polred == 'adhoc':
-                R = files.read_temperature(U.file_temperature, c)
-                R = (R - 13.3) / 2.0 + 1.0e-4
-                R = np.exp(R) / (np.exp(R) + np.exp(-R))
-            elif polred.find('rhofun') >= 0:
-                s = polred.split('_')
-                th, sw = float(s[1]), float(s[2])
-                R = files.read_temperature(U.file_cloud, c)             # the density as the file holds it (read_otfile)
-                if U.KDENSITY != 1.0:
-                    R *= U.KDENSITY
-                R = np.clip(R, 0.1, 1e10)
-                R = 0.5 * (1.0 + np.tanh((np.log10(th) - np.log10(R)) / sw))
-            else:
-                R = np.fromfile(polred, np.float32)[1:] if given is None else given
-                if not healpix:
-                    R = np.clip(R, 1.0e-6, 0.999999)
-                if R.size != c.CELLS:
-                    raise files.FileError("%s: %d polarisation reduction factors for %d cells" % (polred, R.size, c.CELLS))
-            if healpix:
-                R = R / np.sqrt(BB[0] ** 2 + BB[1] ** 2 + BB[2] ** 2)
-            else:
-                R = R / np.sqrt(BB[0] ** 2 + BB[1] ** 2 + BB[2] ** 2 + 1.0e-10)
-            for k in range(3):
-                BB[k] *= R
-        return [np.ascontiguousarray(b, np.float32) for b in BB]
-
-    def polmap_frequencies(self):
-        """indices of the frequencies that get a polarisation map (ASOC.py:3755-3762): those of the emitted range that are
-        within 1 % of a `mapum` wavelength -- or, without `mapum`, inside `wavelength`"""
-        U, FFREQ = self.U, self.FFREQ
-        m = np.nonzero((FFREQ >= U.REMIT_F[0]) & (FFREQ <= U.REMIT_F[1]))[0]
-        I1, I2 = int(m[0]), int(m[-1])
-        singles = np.asarray(getattr(U, "SINGLE_MAP_FREQ", []), np.float32)
-        sel = []
-        for IFREQ in range(I1, I2 + 1):
-            FREQ = FFREQ[IFREQ]
-            if len(singles) > 0:
-                if np.min(np.abs(FREQ - singles)) > 0.01 * FREQ:
-                    continue
-            elif (FREQ < U.MAP_FREQ[0]) or (FREQ > U.MAP_FREQ[1]):
-                continue
-            sel.append(IFREQ)
-        return I1, sel
-
-    def write_polmaps(self, EMITTED, R=None):
-        """`polmap bx by bz`: polarisation maps from the emission (ASOC.py:3651-3801 -> PolMapping): for every selected
-        frequency and observer direction polmap_<um>_<dir>.fits with data [4, NPIX.y, NPIX.x] -- I, Q, U [Jy/sr] and the
-        column density (polstat 0), the line-of-sight statistics rT, rI, jT, jI of the field (polstat 1), or <B>, <B_LOS>,
-        <B_POS>, tau (polstat 3).  Written under `nomap` as well, as in the reference (:3655).  R[CELLS, columns of EMITTED]: the
-        polarisation reduction factor per frequency from the emission stage, used where the ini has no `polred` -- every map with
-        the column of its frequency (the reference needs that column copied into a `polred` file by hand, A2E_MABU.py:1190-1195)."""
-        U, e, c = self.U, self.eng, self.cloud
-        if not (U.POLMAP > 0 and U.NPIX[1] > 0):
-            return []
-        if len(getattr(U, "file_polred", "")) > 0:
-            R = None
-        if R is None:
-            e.set_bfield(*self.polarisation_field())
-        I1, sel = self.polmap_frequencies()
-        NDIR, ODIR, RA, DE = launch.set_observer_directions(U.OBS_THETA, U.OBS_PHI)
-        centre = U.MAPCENTRE if U.MAPCENTRE[0] > -1e7 else (0.5 * c.NX, 0.5 * c.NY, 0.5 * c.NZ)   # ASOC_aux.py:791-793
-        KK = (1.0e23 / launch.FACTOR) * PLANCK / (4.0 * np.pi) * (U.GL * PARSEC)                 # ASOC.py:3753-3754
-        _, LENGTH_f = launch.kernel_literals(U.GL)
-        pix = U.GL * U.MAP_DX / (U.DISTANCE if U.DISTANCE > 0.0 else 1000.0)
-        polred = int(U.POLSTAT != 3 and (len(getattr(U, "file_polred", "")) > 0 or R is not None))    # -D POLRED (ASOC.py:349,359)
-        p0 = float("%.4f" % U.p0)                                                               # -D p00=%.4ff
-        written = []
-        for IFREQ in sel:
-            FREQ = float(self.FFREQ[IFREQ])
-            ABS, SCA = self._optical_for(IFREQ)
-            if R is not None:
-                e.set_bfield(*self.polarisation_field(R=R[:, IFREQ - I1]))
-            EMIT = np.asarray(KK * FREQ * EMITTED[:, IFREQ - I1], np.float32)                    # :3788
-            for idir in range(NDIR):
-                MAP = e.polmap(EMIT, ODIR[idir], RA[idir], DE[idir], U.NPIX, U.MAP_DX, centre, ABS, SCA, polstat=int(U.POLSTAT),
-                               polred=polred, rho_weight=int(U.POL_RHO_WEIGHT > 0), p0=p0, LENGTH=LENGTH_f)
-                if self.rank != 0:
-                    continue
-                name = "polmap_%.1f_%02d.fits" % (1.0e4 * launch.C_LIGHT / FREQ, idir)          # f2um (:3800)
-                files.write_fits(name, np.asarray(MAP, np.float32).reshape(4, U.NPIX[1], U.NPIX[0]), U.FITS_RA, U.FITS_DE, pix, planes=True)
-                written.append(name)
-        e.set_bfield(None)
-        return written
-
-    def write_healpix_polmaps(self, EMITTED, R=None):
-        """`polmap bx by bz [[minlos] maxlos]` with `mapping NSIDE -1 dx` and `perspective x y z`: all-sky polarisation maps
-        seen from inside the model (ASOC.py:3808-3958 -> PolHealpixMapping, kernel_ASOC_map_H.c, POLSTAT 0): for every
-        frequency of the emitted range inside `wavelength` (:3911-3918; no `mapum` in this branch) pol_healpix.fits.<IFREQ>,
-        a Healpix table with the columns I_STOKES, Q_STOKES, U_STOKES [Jy/sr] and N.  Unlike the flat maps these are not
-        written under `nomap` (:3808).  `interpolate` and `yshear` act here, and only here.  R: as in write_polmaps."""
-        U, e, c = self.U, self.eng, self.cloud
-        if not (U.POLMAP > 0 and U.NOMAP == 0 and U.NPIX[1] < 0):
-            return []
-        if len(getattr(U, "file_polred", "")) > 0:
-            R = None
-        # the field with `polred` encoded as THIS branch of the reference does it (:3867-3869): a file's R is not clipped and
-        # nothing is added under the root -- unlike the flat branch (:3710-3716)
-        polred = int(len(getattr(U, "file_polred", "")) > 0 or R is not None)                    # -D POLRED (ASOC.py:349,359)
-        if R is None:
-            e.set_bfield(*self.polarisation_field(healpix=True))
-        FFREQ = self.FFREQ
-        m = np.nonzero((FFREQ >= U.REMIT_F[0]) & (FFREQ <= U.REMIT_F[1]))[0]
-        I1, I2 = int(m[0]), int(m[-1])
-        sel = [i for i in range(I1, I2 + 1) if U.MAP_FREQ[0] <= float(FFREQ[i]) <= U.MAP_FREQ[1]]
-        KK = (1.0e23 / launch.FACTOR) * PLANCK / (4.0 * np.pi) * (U.GL * PARSEC)                 # :3909-3910
-        _, LENGTH_f = launch.kernel_literals(U.GL)
-        p0 = float("%.4f" % U.p0)                                                               # -D p00=%.4ff (ASOC.py:349)
-        minlos, maxlos = float("%.3e" % U.MINLOS), float("%.3e" % U.MAXLOS)                      # -D MINLOS=%.3ef -D MAXLOS=%.3ef
-        NSIDE = int(U.NPIX[0])
-        written = []
-        for IFREQ in sel:
-            FREQ = float(FFREQ[IFREQ])
-            ABS, SCA = self._optical_for(IFREQ)
-            EMIT = np.asarray(KK * FREQ * EMITTED[:, IFREQ - I1], np.float32)                    # :3944
-            if R is not None:
-                e.set_bfield(*self.polarisation_field(healpix=True, R=R[:, IFREQ - I1]))
-            MAP = e.polmap_healpix(EMIT, NSIDE, U.INTOBS, ABS, SCA, polred=polred, p0=p0, interpolate=int(U.INTERPOLATE), minlos=minlos,
-                                   maxlos=maxlos, y_shear=float(U.Y_SHEAR), LENGTH=LENGTH_f)
-            if self.rank != 0:
-                continue
-            name = "pol_healpix.fits.%d" % IFREQ
-            files.write_healpix_fits(name, np.asarray(MAP, np.float32).reshape(4, -1), files.HEALPIX_POL_COLUMNS, NSIDE)
-            written.append(name)
-        e.set_bfield(None)
-        return written
-
-    def write_ps_tau(self):
-        """`pssavetau file um`: for every observer direction <file>_<idir>.dat with one line per point source -- its index,
-        the column density [cm-2 per unit density] and the optical depth towards the observer at the frequency of the grid
-        closest to `um` (ASOC.py:3576-3645, PSTau)"""
-        U, e = self.U, self.eng
-        IFREQ = int(np.argmin(np.abs(self.FFREQ - U.pssavetau_freq)))
-        ABS, SCA = self._optical_for(IFREQ)
-        NDIR, ODIR, RA, DE = launch.set_observer_directions(U.OBS_THETA, U.OBS_PHI)
-        _, LENGTH_f = launch.kernel_literals(U.GL)
-        for idir in range(NDIR):
-            col, tau = e.ps_tau(U.PSPOS[:U.NO_PS, :3], ODIR[idir], ABS, SCA, LENGTH_f)
-            if self.rank == 0:
-                with open("%s_%d.dat" % (U.file_pssavetau, idir), "w") as fp:
-                    for i in range(U.NO_PS):
-                        fp.write('%6d  %12.4e  %12.4e\n' % (i, col[i], tau[i]))
-
-    def write_healpix_maps(self, EMITTED):
-        """`mapping NSIDE -1 dx`: all-sky map of the emission seen from `perspective` (HealpixMapping, kernel_ASOC_map.c),
-        file layout of ASOC.py:3185-3320: map_dir_00_H.bin = int32 [NPIX.x, NPIX.y], int32 [frequencies, LEVELS], then one
-        float32 [12*NSIDE^2] map [Jy/sr] per frequency of the emitted range inside `wavelength`.
-        The reference itself stops in this branch with a NameError (SAVE_COLDEN is never assigned, :3291/:3297) after
-        writing the two headers; this writes the file its loop describes, with SAVE_COLDEN = 0 (no column-density file:
-        its savetau tests compare a list with a float, :3303-3306)."""
-        U, e, c = self.U, self.eng, self.cloud
-        FFREQ = self.FFREQ
-        m = np.nonzero((FFREQ >= U.REMIT_F[0]) & (FFREQ <= U.REMIT_F[1]))[0]
-        I1, I2 = int(m[0]), int(m[-1])
-        NSIDE = int(U.NPIX[0])
-        _, ODIR, RA, DE = launch.set_observer_directions(U.OBS_THETA, U.OBS_PHI)
-        centre = U.MAPCENTRE if U.MAPCENTRE[0] > -1e7 else (0.5 * c.NX, 0.5 * c.NY, 0.5 * c.NZ)
-        KK = (1.0e23 / launch.FACTOR) * PLANCK / (4.0 * np.pi) * (U.GL * PARSEC)
-        _, LENGTH_f = launch.kernel_literals(U.GL)
-        if U.LIB_MAPS:                                             # ASOC.py:202-204, :3234-3250
-            I1, I2 = 0, self.NFREQ - 1
-        sel = [i for i in range(I1, I2 + 1) if U.MAP_FREQ[0] <= float(FFREQ[i]) <= U.MAP_FREQ[1] and not (U.LIB_MAPS and i not in self.lib_col)]
-        fp = None
-        if self.rank == 0:
-            fp = open("map_dir_%02d_H.bin" % 0, "wb")              # NDIR = 1 for Healpix maps (ASOC.py:2917)
-            np.asarray([U.NPIX[0], U.NPIX[1]], np.int32).tofile(fp)
-            np.asarray([len(sel), c.LEVELS], np.int32).tofile(fp)
-
-        def emission(IFREQ, save_spe=True):
-            col = self.lib_col[IFREQ] if U.LIB_MAPS else IFREQ - I1     # :3279-3280
-            return np.asarray(EMITTED[:, col] * np.float32(KK) * np.float32(float(FFREQ[IFREQ])), np.float32)    # :3283
-
-        if getattr(U, "MAP_LEVELS", 0) > 0:                       # `maplevels 1`: the same map through the batch path, and its levels
-            lfp = self._open_level_file(0, len(sel)) if self.rank == 0 else None
-            for batch, planes in self._map_blocks([(i, True, 0, 0) for i in sel], emission, [(ODIR[0], RA[0], DE[0])], centre, LENGTH_f,
-                                                  healpix=NSIDE, levels=True):
-                for k in range(len(batch)):
-                    if fp:
-                        np.asarray(planes[0][0][k], np.float32).tofile(fp)
-                        np.asarray(planes[0][3][k], np.float32).tofile(lfp)
-            if lfp:
-                lfp.close()
-        elif 2 <= U.FAST_MAP <= 998:                               # `mapping NSIDE -1 dx NF`: NF frequencies per walk
-            for batch, planes in self._map_blocks([(i, True, 0, 0) for i in sel], emission, [(ODIR[0], RA[0], DE[0])], centre, LENGTH_f,
-                                                  healpix=NSIDE):
-                for k in range(len(batch)):
-                    if fp:
-                        np.asarray(planes[0][0][k], np.float32).tofile(fp)
-        else:
-            for IFREQ in sel:
-                ABS, SCA = self._optical_for(IFREQ)
-                MAP, _ = e.map(emission(IFREQ), ODIR[0], RA[0], DE[0], U.NPIX, U.MAP_DX, centre, ABS, SCA, INTOBS=U.INTOBS, save_colden=0,
-                               LENGTH=LENGTH_f, healpix=NSIDE)
-                if fp:
-                    np.asarray(MAP, np.float32).tofile(fp)
-        if fp:
-            fp.close()
-
-    def _map_blocks(self, sel, emission, views, centre, LENGTH_f, healpix=0, levels=False):
-        """`mapping nx ny dx NF` (2 <= NF <= 998; ASOC.py:3442-3568): the frequencies of sel = [(IFREQ, save_spe, save_tau,
-        save_colden)] in batches of at most min(NF, engine.map_block_max).  A batch is uploaded once -- emission(IFREQ, save_spe)
-        as the columns of EMITX[CELLS, nf], the opacities _optical_for sets for the plain path (with abundances the per-cell
-        ones it builds, read back into OPTX[CELLS, nf, 2]) -- and mapped for every view = (DIR, RA, DE).  Yields (batch,
-        [(MAPX, TAUX, COLDEN) per view]); with levels (`maplevels 1`) every view's tuple has a fourth member, the planes
-        MAPL[nf, LEVELS, ...] of engine.map_block_levels for the same batch and view."""
-        U, e, c = self.U, self.eng, self.cloud
-        nb = max(1, min(int(U.FAST_MAP), int(e.map_block_max)))
-        for b0 in range(0, len(sel), nb):
-            batch = sel[b0:b0 + nb]
-            EMITX = np.zeros((c.CELLS, len(batch)), np.float32)
-            ABSX, SCAX = np.zeros(len(batch), np.float32), np.zeros(len(batch), np.float32)
-            OPTX = np.zeros((c.CELLS, len(batch), 2), np.float32) if self.WITH_ABU else None
-            for k, (IFREQ, save_spe, _, _) in enumerate(batch):
-                ABSX[k], SCAX[k] = self._optical_for(IFREQ)
-                if OPTX is not None:
-                    OPTX[:, k, :] = np.asarray(e.read_opt(), np.float32).reshape(c.CELLS, 2)
-                if save_spe:
-                    EMITX[:, k] = emission(IFREQ, save_spe)
-            e.set_map_block(EMITX, ABSX, SCAX, OPTX)
-            del EMITX, OPTX
-            planes = [e.map_block(d, ra, de, U.NPIX, U.MAP_DX, centre, INTOBS=U.INTOBS, LENGTH=LENGTH_f, healpix=healpix)
-                      for d, ra, de in views]
-            if levels:
-                planes = [tuple(p) + (e.map_block_levels(d, ra, de, U.NPIX, U.MAP_DX, centre, INTOBS=U.INTOBS, healpix=healpix),)
-                          for p, (d, ra, de) in zip(planes, views)]
-            yield batch, planes
-        e.set_map_block(None)
-
     def _bcast_seed(self, seed):
         t = self.comm.torch.tensor([seed], dtype=self.comm.torch.float64,
                                    device="cuda" if self.comm.backend == "nccl" else "cpu")

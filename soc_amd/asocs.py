@@ -23,7 +23,7 @@ import time
 import numpy as np
 
 from . import files, launch
-from .asoc import AbsorptionRun, UnsupportedOption, _float_local
+from .asoc import AbsorptionRun, UnsupportedOption, _local_routing
 from .ini import User
 from .launch import PLANCK, PARSEC, Fix
 
@@ -142,7 +142,7 @@ class ScatteringRun(AbsorptionRun):
         self.timers["Tpull"] += time.time() - t0
 
     # ---------------------------------------------------------------------------------
-    @_float_local
+    @_local_routing(abu=False)
     def simulate(self):
         """-> OUTCOMING[NFREQ, NDIR, NPIX.y, NPIX.x], photons per pixel before the final scaling"""
         U, e, c = self.U, self.eng, self.cloud

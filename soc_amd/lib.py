@@ -244,6 +244,11 @@ def _i(a):
     return None if a is None else a.ctypes.data_as(_I)
 
 
+def _view_vectors(*vectors):
+    """(DIR, RA, DE, CENTRE, INTOBS) of a map call as the float3 the C ABI takes: three contiguous floats each, None kept"""
+    return [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).ravel()[:3]) for a in vectors]
+
+
 class Engine:
     """One GPU's packet engine.  Method names follow the C ABI one to one."""
 
@@ -587,7 +592,7 @@ class Engine:
         EMIT = np.ascontiguousarray(EMIT, np.float32)
         if EMIT.size != self.CELLS:
             raise SocError("map: EMIT must hold CELLS floats")
-        v = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).ravel()[:3]) for a in (DIR, RA, DE, CENTRE, INTOBS)]
+        v = _view_vectors(DIR, RA, DE, CENTRE, INTOBS)
         nx, ny = (int(healpix), 1) if healpix else (int(NPIX[0]), int(NPIX[1]))
         shape = (12 * nx * nx,) if healpix else (ny, nx)
         MAP, TAU = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
@@ -629,7 +634,7 @@ class Engine:
         """The maps of the resident batch for one view, from one walk per pixel (the arguments and switches of map).  Returns
         (MAPX, TAUX, COLDEN): [nf, NPIX.y, NPIX.x] twice and [NPIX.y, NPIX.x] -- or [nf, 12*NSIDE^2] and [12*NSIDE^2]; plane f
         of MAPX and TAUX is what map gives for frequency f, COLDEN what it gives as SAVETAU with save_colden=1."""
-        v = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).ravel()[:3]) for a in (DIR, RA, DE, CENTRE, INTOBS)]
+        v = _view_vectors(DIR, RA, DE, CENTRE, INTOBS)
         nx, ny = (int(healpix), 1) if healpix else (int(NPIX[0]), int(NPIX[1]))
         shape = (12 * nx * nx,) if healpix else (max(ny, 0), max(nx, 0))
         nf = getattr(self, "_map_block_nf", 0)
@@ -645,7 +650,7 @@ class Engine:
         bit, what map gives for frequency f when the emission of every cell not on level l is 0: what level l emits towards the
         pixel, seen through everything in front of it.  The planes of a pixel add up to map_block's value up to the order of
         the additions.  The batch is read, not changed.  Not the reference's per-level product: that is map_levels."""
-        v = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).ravel()[:3]) for a in (DIR, RA, DE, CENTRE, INTOBS)]
+        v = _view_vectors(DIR, RA, DE, CENTRE, INTOBS)
         nx, ny = (int(healpix), 1) if healpix else (int(NPIX[0]), int(NPIX[1]))
         shape = (12 * nx * nx,) if healpix else (max(ny, 0), max(nx, 0))
         nf = getattr(self, "_map_block_nf", 0)
@@ -670,7 +675,7 @@ class Engine:
         EMIT = np.ascontiguousarray(EMIT, np.float32)
         if EMIT.size != self.CELLS:
             raise SocError("map_levels: EMIT must hold CELLS floats")
-        v = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).ravel()[:3]) for a in (DIR, RA, DE, CENTRE, INTOBS)]
+        v = _view_vectors(DIR, RA, DE, CENTRE, INTOBS)
         nx, ny = int(NPIX[0]), int(NPIX[1])
         MAP = np.zeros((self.LEVELS, max(ny, 0), max(nx, 0)), np.float32)
         self._chk(self.lib.soc_map_levels(self.h, nx, ny, np.float32(MAP_DX), _f(EMIT), _f(v[0]), _f(v[1]), _f(v[2]), _f(v[3]), _f(v[4]),

@@ -72,11 +72,11 @@ def test_double_index_hierarchy_does_not_ask(monkeypatch):
             return 7
     stub = Stub()
     stub.cloud = cloud
-    from soc_amd.asoc import _abu_local, _float_local
-    assert _abu_local(lambda self: self.body())(stub) == 7 and _float_local(lambda self: self.body())(stub) == 7
+    from soc_amd.asoc import _local_routing
+    assert _local_routing()(lambda self: self.body())(stub) == 7 and _local_routing(abu=False)(lambda self: self.body())(stub) == 7
     assert calls == []
     stub.cloud = synth.octree_cloud(8, levels=3, frac=0.15, seed=7)
-    assert _abu_local(lambda self: self.body())(stub) == 7
+    assert _local_routing()(lambda self: self.body())(stub) == 7
     assert calls == [dict(float_local=1), dict(float_local=0)]
 
 
