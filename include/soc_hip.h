@@ -318,7 +318,10 @@ int soc_last_form(soc_ctx *ctx);
  *   the scattered-light kernels (then the other fields are 0 but form 3, octree, double, and bits 12-13; on a single-level grid
  *   form 3 with octree = 0: the field has two bits, there is no form 4)
  *   bit 12 (sweeps of rays) the image was a Healpix map seen from a position (soc_sca_set_healpix)
- *   bit 13 (sweeps of rays) the sweep held a SimRAM_HP launch (soc_sca_sim_hp: the Healpix sky as the source) */
+ *   bit 13 (sweeps of rays) the sweep held a SimRAM_HP launch (soc_sca_sim_hp: the Healpix sky as the source)
+ *   bit 14 a launch of the packet-splitting kernels (soc_sim_bg_split, soc_sim_hp_split): then form 0, kind 0 SimBgSplit or
+ *          1 SimHpSplit, WINT 0 or 1, and octree, double (never on a Cartesian grid) and per-cell opacities name the compiled
+ *          instance; a split launch without work items leaves the code as it was */
 int soc_last_variant(soc_ctx *ctx);
 
 /* HIP-event timing on the handle's stream: bracket launches, then read elapsed ms */

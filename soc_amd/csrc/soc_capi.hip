@@ -950,6 +950,7 @@ int soc_sim_bg_split(soc_ctx *c, int PACKETS, int BATCH, float SEED, float BG, f
     SocSplit P;
     P.SELEM = SELEM;  P.max_split = max_split;  P.stack = c->dSplitStack;  P.counters = c->dSplitStats;
     HIPCHK(c, soc_launch_sim_bg_split(c->G, S, P, V, c->stream));
+    if (gid_count > 0) c->last.variant = soc_split_variant_code(0, V);      // (as run_direct: a launch without work items ran nothing)
     return SOC_OK;
 }
 
@@ -975,6 +976,7 @@ int soc_sim_hp_split(soc_ctx *c, int PACKETS, int BATCH, float SEED, float TW, i
     SocSplit P;
     P.SELEM = 1;  P.max_split = max_split;  P.stack = c->dSplitStack;  P.counters = c->dSplitStats;
     HIPCHK(c, soc_launch_sim_hp_split(c->G, S, P, V, c->stream));
+    if (gid_count > 0) c->last.variant = soc_split_variant_code(1, V);
     return SOC_OK;
 }
 

@@ -423,6 +423,27 @@ static inline int soc_variant_code(const SocSweepPlan &p)
            | (p.rays ? 1 << 11 : 0) | (p.hpx ? SOC_VAR_HEALPIX : 0) | (p.hpsky ? SOC_VAR_HPSKY : 0);
 }
 
+// The packet-splitting kernels (soc_split.hip): the instance <OCT, DBL, ABU, WINT> a launch runs, as the integer both launch wrappers
+// switch on -- octree 8, Index() in double 4 (cleared on Cartesian grids: Index() touches no double arithmetic at level 0), per-cell
+// opacities 2, the INT tally 1 -- and the same instance as soc_last_variant reports it: form 0, kind 0 SimBgSplit / 1 SimHpSplit, the
+// key's bits in their usual places, and bit 14
+#define SOC_VAR_SPLIT   (1 << 14)   // a launch of the packet-splitting kernels
+static inline int soc_split_key(const SocVariant &V)
+{
+    return (V.octree ? 8 : 0) | ((V.octree && V.dbl) ? 4 : 0) | (V.abu ? 2 : 0) | (V.wint ? 1 : 0);
+}
+static inline int soc_split_variant_code(int kind, const SocVariant &V)
+{
+    const int key = soc_split_key(V);
+    SocSweepPlan p{};
+    p.kind = kind;
+    p.wint = key & 1;
+    p.octree = (key & 8) != 0;
+    p.dbl = (key & 4) != 0;
+    p.abu = (key & 2) != 0;
+    return soc_variant_code(p) | SOC_VAR_SPLIT;
+}
+
 // What a brick sweep reports: passes (0 when no launch had work items), form (0 unless the sweep ran), variant (untouched when no kernel ran)
 struct SocSweepResult {
     int passes = 0, form = 0, variant = -1;

@@ -304,15 +304,12 @@ __global__ __launch_bounds__(64) void soc_sim_bg_split_kernel(const SocGrid G, c
     soc_split_count(S, P, n);
 }
 
-hipError_t soc_launch_sim_bg_split(const SocGrid &G, const SocSim &S, const SocSplit &P, const SocVariant &Vin, hipStream_t st)
+hipError_t soc_launch_sim_bg_split(const SocGrid &G, const SocSim &S, const SocSplit &P, const SocVariant &V, hipStream_t st)
 {
     if (S.gid_count == 0) return hipSuccess;
-    SocVariant V = Vin;
-    if (!V.octree) V.dbl = 0;        // Cartesian: Index() touches no double arithmetic at level 0
     const dim3 grid((S.gid_count + 63) / 64), block(64);
     const size_t lds = (size_t)S.BINS * 4 + 2 * SOC_MAXL * 4;
-    const int key = (V.octree ? 8 : 0) | (V.dbl ? 4 : 0) | (V.abu ? 2 : 0) | (V.wint ? 1 : 0);
-    switch (key) {
+    switch (soc_split_key(V)) {         // (soc_dev.h: what soc_last_variant reports comes from the same key)
     case 0:  soc_sim_bg_split_kernel<false, false, false, false><<<grid, block, lds, st>>>(G, S, P); break;
     case 1:  soc_sim_bg_split_kernel<false, false, false, true><<<grid, block, lds, st>>>(G, S, P); break;
     case 2:  soc_sim_bg_split_kernel<false, false, true, false><<<grid, block, lds, st>>>(G, S, P); break;
@@ -376,16 +373,13 @@ __global__ __launch_bounds__(64) void soc_sim_hp_split_kernel(const SocGrid G, c
     soc_split_count(S, P, n);
 }
 
-hipError_t soc_launch_sim_hp_split(const SocGrid &G, const SocSim &S, const SocSplit &P, const SocVariant &Vin, hipStream_t st)
+hipError_t soc_launch_sim_hp_split(const SocGrid &G, const SocSim &S, const SocSplit &P, const SocVariant &V, hipStream_t st)
 {
     if (S.gid_count == 0) return hipSuccess;
     if (!S.HPBG || (S.HPBG_WEIGHTED && !S.HPBGP)) return hipErrorInvalidValue;
-    SocVariant V = Vin;
-    if (!V.octree) V.dbl = 0;        // Cartesian: Index() touches no double arithmetic at level 0
     const dim3 grid((S.gid_count + 63) / 64), block(64);
     const size_t lds = (size_t)S.BINS * 4 + 2 * SOC_MAXL * 4;
-    const int key = (V.octree ? 8 : 0) | (V.dbl ? 4 : 0) | (V.abu ? 2 : 0) | (V.wint ? 1 : 0);
-    switch (key) {
+    switch (soc_split_key(V)) {         // (soc_dev.h: what soc_last_variant reports comes from the same key)
     case 0:  soc_sim_hp_split_kernel<false, false, false, false><<<grid, block, lds, st>>>(G, S, P); break;
     case 1:  soc_sim_hp_split_kernel<false, false, false, true><<<grid, block, lds, st>>>(G, S, P); break;
     case 2:  soc_sim_hp_split_kernel<false, false, true, false><<<grid, block, lds, st>>>(G, S, P); break;

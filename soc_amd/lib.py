@@ -176,7 +176,7 @@ def decode_variant(code):
         return None
     return dict(form=code & 3, kind=(code >> 2) & 7, wint=(code >> 5) & 3, octree=(code >> 7) & 1, dbl=(code >> 8) & 1,
                 abu=(code >> 9) & 1, ali=(code >> 10) & 1, rays=(code >> 11) & 1, healpix=(code >> 12) & 1, hpsky=(code >> 13) & 1,
-                code=code)
+                split=(code >> 14) & 1, code=code)
 
 
 class SocError(RuntimeError):

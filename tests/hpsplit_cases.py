@@ -1,7 +1,7 @@
 """The cases of packet splitting with a Healpix sky (`split 1` + `hpbg`, SimHpSplit) of tests/golden/hpsplit.npz: skies, models
 and launches.  Shared by the tests and by tools/make_hpsplit_golden.py, which records what the reference's kernel gives for
-them, work item by work item in id order.  The models are those of split_cases.py; every launch has GLOBAL 96 work items (one
-and a half waves) of BATCH 2-6 root rays.
+them, work item by work item in id order.  The models are those of split_cases.py; a launch has GLOBAL 96 work items (one
+and a half waves) of BATCH 2-6 root rays, the x104 cases -- the hierarchy whose Index() runs in double -- 1024 work items.
 
 The skies are generated here from a seed and not stored: a smooth dipole times log-normal noise, strictly positive; the
 weighted inputs (sky x pixel weight, cumulative probability) come through files.hpbg_for_frequency as in a run.
@@ -25,9 +25,9 @@ GLOBAL = 96
 COUNTERS = sc.COUNTERS
 
 
-def case(model, BATCH, max_split=64, SEED=0.5, ABS=1e-4, SCA=3e-4, variant="scalar", TW=1.0, weighted=0, sky=1, scale=1.0):
+def case(model, BATCH, max_split=64, SEED=0.5, ABS=1e-4, SCA=3e-4, variant="scalar", TW=1.0, weighted=0, sky=1, scale=1.0, GLOBAL=GLOBAL):
     return dict(model=model, BATCH=BATCH, max_split=max_split, SEED=SEED, ABS=ABS, SCA=SCA, variant=variant, TW=TW,
-                weighted=weighted, sky=sky, scale=scale)
+                weighted=weighted, sky=sky, scale=scale, GLOBAL=GLOBAL)
 
 
 CASES = {
@@ -43,6 +43,9 @@ CASES = {
     "nest5_ms16":   case("nest5", 6, max_split=16, SEED=0.1234),
     "jump3_ms17":   case("jump3", 6, max_split=17, SEED=0.3183),
     "oct6_w":       case("oct6", 2, SEED=0.8080, weighted=1, sky=3),
+    "x104":         case("x104", 3, SEED=0.2891, GLOBAL=1024),
+    "x104_w_int2":  case("x104", 3, SEED=0.2891, variant="int2", weighted=1, sky=2, GLOBAL=1024),
+    "x104_abu":     case("x104", 3, SEED=0.2891, variant="abu", GLOBAL=1024),
 }
 
 _skies = {}
@@ -93,7 +96,7 @@ def job(name):
     k = CASES[name]
     c = model(k["model"])
     HPBG, HPBGP = sky_inputs(name)
-    kw = dict(ABS=k["ABS"], SCA=k["SCA"], SOURCE=1, BATCH=k["BATCH"], SEED=k["SEED"], BG=0.0, TW=k["TW"], GLOBAL=GLOBAL, WITH_INT=1,
+    kw = dict(ABS=k["ABS"], SCA=k["SCA"], SOURCE=1, BATCH=k["BATCH"], SEED=k["SEED"], BG=0.0, TW=k["TW"], GLOBAL=k["GLOBAL"], WITH_INT=1,
               HPBG=HPBG, HPBGP=HPBGP)
     v = k["variant"]
     if v == "abu":
@@ -123,12 +126,14 @@ def coverage(stats_by_case):
     for name, s in stats_by_case.items():
         if int(s["guard"]) != 0:
             bad.append("%s: %d root rays born too deep for the stack (the reference writes past its slab)" % (name, int(s["guard"])))
-        if int(s["roots"]) != GLOBAL * CASES[name]["BATCH"]:
-            bad.append("%s: %d root rays for %d work items x %d" % (name, int(s["roots"]), GLOBAL, CASES[name]["BATCH"]))
+        if int(s["roots"]) != CASES[name]["GLOBAL"] * CASES[name]["BATCH"]:
+            bad.append("%s: %d root rays for %d work items x %d" % (name, int(s["roots"]), CASES[name]["GLOBAL"], CASES[name]["BATCH"]))
     for name, keys in WANT.items():
         for key in ((keys,) if isinstance(keys, str) else keys):
             if name in stats_by_case and int(stats_by_case[name][key]) < 1:
                 bad.append("%s does not reach '%s'" % (name, key))
+    if "x104" in stats_by_case and int(stats_by_case["x104"]["splits"]) < 500:     # the double-Index() case: see split_cases.coverage
+        bad.append("x104 reaches 'splits' %d times, not 500" % int(stats_by_case["x104"]["splits"]))
     if {CASES[n]["weighted"] for n in stats_by_case} != {0, 1}:
         bad.append("an unweighted and a weighted sky")
     if not {"abu", "abuh", "msf", "int2"} <= {CASES[n]["variant"] for n in stats_by_case}:

@@ -9,6 +9,8 @@ Together the cases reach every branch of the kernel (COVERAGE is asserted over t
   NBUF = 9 > MAX_SPLIT-10 only at the fourth refinement in a row);
   work items that return at ind >= AREA after their first elements (oct6_selem3: 96 work items x 3 elements for AREA 216),
   and, in every case, the work items of the launch's padding, which return at their first element.
+The x104 cases are the ones on a hierarchy whose Index() the reference evaluates in double (104 x 6 x 5 roots, 3 levels, 4864 cells:
+NX > 100 with three levels): thousands of splits, so that a walk in float would show in the tallies (tests/test_split.py).
 """
 import json
 
@@ -41,6 +43,9 @@ CASES = {
     "oct4b_msf":    case("oct4b", 3, SEED=0.93, variant="msf"),
     "nest5_ms16":   case("nest5", 4, max_split=16, SEED=0.1234),
     "oct6_selem3":  case("oct6", 4, SELEM=3, SEED=0.8080),
+    "x104":         case("x104", 2, SELEM=2, SEED=0.2891),
+    "x104_abu":     case("x104", 2, SELEM=2, SEED=0.2891, variant="abu"),
+    "x104_int2":    case("x104", 2, SELEM=2, SEED=0.2891, variant="int2"),
 }
 
 COUNTERS = ("roots", "splits", "deep_splits", "ended_below_RL", "overflow_drops", "long_returns")
@@ -58,6 +63,8 @@ def model(name):
             c = synth.octree_cloud(6, levels=3, frac=0.15, seed=5)
         elif name == "nest5":
             c = nested_cloud(5)
+        elif name == "x104":                       # Index() in double (DOUBLE_INDEX: NX > 100, three levels)
+            c = synth.noncubic_cloud("oct104x6x5")
         elif name == "full4":                      # every root cell refined once, uniform: the normalisation check
             c = synth.octree_cloud(4, levels=2, frac=1.0, uniform=1.0e3)
         else:
@@ -137,11 +144,27 @@ def coverage(stats_by_case):
     for name, key in want.items():
         if key and name in stats_by_case and int(stats_by_case[name][key]) < 1:
             bad.append("%s does not reach '%s'" % (name, key))
+    if "x104" in stats_by_case:                    # the double-Index() case: enough events for a float walk to show in the tallies
+        for key, least in (("splits", 1000), ("deep_splits", 50), ("initial", 100)):
+            if int(stats_by_case["x104"][key]) < least:
+                bad.append("x104 reaches '%s' %d times, not %d" % (key, int(stats_by_case["x104"][key]), least))
     k = CASES["oct6_selem3"]
     A, G = model(k["model"]).AREA, launch_shape(model(k["model"]).AREA, k["SELEM"])
     if not any(i + G < A <= i + (k["SELEM"] - 1) * G for i in range(G)):
         bad.append("oct6_selem3: no work item returns at ind >= AREA after its first elements")
     return bad
+
+
+def float_walk_differs(run, monkeypatch):
+    """run() -> TABS of the soc restatement.  The number of cells, among those above 1e-3 of the largest tally, whose tally moves by
+    more than 1e-5 relative when Index() is made to run in float (oracle.pyoracle.double_index forced to 0)."""
+    import oracle.pyoracle
+    T = run().astype(np.float64)
+    monkeypatch.setattr(oracle.pyoracle, "double_index", lambda NX, LEVELS: 0)
+    F = run().astype(np.float64)
+    monkeypatch.undo()
+    m = T > 1e-3 * T.max()
+    return int((np.abs(F[m] - T[m]) > 1e-5 * T[m]).sum()), int(m.sum())
 
 
 def meta():

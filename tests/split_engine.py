@@ -63,6 +63,18 @@ def restore_engine(eng, job):
         eng.set_abundances(None)
 
 
+def assert_vector_sums_close(INTV, want_INTV, want_INT, rtol=1e-5, floor_frac=1e-6):
+    """INTX, INTY, INTZ of runs with identical trajectories: signed sums of delta * u_k, so the order of the adds moves a sum by a
+    fraction of the sum of the magnitudes of its terms, which is at most INT (|u_k| <= 1) -- not by a fraction of the sum itself,
+    which cancels.  (Measured on the restatement alone, x104_int2 added up in another order: up to 3e-3 of |INTX|, 3e-7 of INT.)
+    The bound is util.assert_tally_close's with the cell's INT as the magnitude."""
+    I = np.asarray(want_INT, np.float64)
+    tol = rtol * I + floor_frac * rtol * I.max()
+    for k in range(3):
+        d = np.abs(np.asarray(INTV[k], np.float64) - np.asarray(want_INTV[k], np.float64))
+        assert not (d > tol).any(), "INTV[%d]: %d of %d cells differ; worst %.3e of INT" % (k, (d > tol).sum(), d.size, (d / np.maximum(I, 1e-300))[d > tol].max())
+
+
 def run_split(eng, job, SELEM, max_split, gid_first=0, gid_count=None):
     """Returns (TABS, INT, INTV or None, split_stats) of one launch on zeroed tallies"""
     setup_engine(eng, job)

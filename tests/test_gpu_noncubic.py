@@ -149,8 +149,9 @@ def test_per_cell_opacities_on_the_brick_local_walk(tune, engine, oracle_soc, tu
         engine.set_exec(-1, 4)
 
 
-# ---- packet splitting: soc_sim_bg_split_kernel and soc_sim_hp_split_kernel on oct759 ----
+# ---- packet splitting: soc_sim_bg_split_kernel and soc_sim_hp_split_kernel on oct759 (Index() in float) and oct104x6x5 (in double) ----
 KEYS = split_host.COUNTERS + ("max_depth",)
+SPLIT_MODELS = ["oct759", "oct104x6x5"]
 
 
 def _split_same(got, ref, keys):
@@ -164,8 +165,9 @@ def _split_same(got, ref, keys):
 
 
 @pytest.mark.parametrize("SELEM", [1, 3])
-def test_split_background_on_oct759(SELEM, engine):
-    cl = cloud("oct759")
+@pytest.mark.parametrize("name", SPLIT_MODELS)
+def test_split_background(name, SELEM, engine):
+    cl = cloud(name)
 
     def job():
         return Job(cl, sc._CSC, ABS=1e-4, SCA=3e-4, SOURCE=1, BATCH=2, SEED=0.2891, GLOBAL=sc.launch_shape(cl.AREA, SELEM), WITH_INT=1)
@@ -173,18 +175,22 @@ def test_split_background_on_oct759(SELEM, engine):
     got = run_split(engine, job(), SELEM, 64)
     _split_same(got, ref, KEYS)
     assert got[3]["roots"] == 2 * cl.AREA
+    assert engine.last_variant()["split"] == 1 and engine.last_variant()["dbl"] == (1 if name == "oct104x6x5" else 0)
 
 
-def test_split_healpix_background_on_oct759(engine):
-    cl = cloud("oct759")
+@pytest.mark.parametrize("name", SPLIT_MODELS)
+def test_split_healpix_background(name, engine):
+    cl = cloud(name)
     HPBG, HPBGP = hc.sky_inputs("oct4b_w")
+    GLOBAL = 1024 if name == "oct104x6x5" else hc.GLOBAL        # (96 work items split some hundred times on the long model; 1024 a thousand)
 
     def job():
-        return Job(cl, sc._CSC, ABS=1e-4, SCA=3e-4, SOURCE=1, BATCH=3, SEED=0.5772, BG=0.0, GLOBAL=hc.GLOBAL, WITH_INT=1, HPBG=HPBG, HPBGP=HPBGP)
+        return Job(cl, sc._CSC, ABS=1e-4, SCA=3e-4, SOURCE=1, BATCH=3, SEED=0.5772, BG=0.0, GLOBAL=GLOBAL, WITH_INT=1, HPBG=HPBG, HPBGP=HPBGP)
     ref = hpsplit_host.sim_hp_split("soc", job(), 64)
     got = run_hp_split(engine, job(), 64)
     _split_same(got, ref, hpsplit_host.COUNTERS + ("max_depth", "skipped_splits"))
-    assert got[3]["roots"] == 3 * hc.GLOBAL
+    assert got[3]["roots"] == 3 * GLOBAL
+    assert engine.last_variant()["split"] == 1 and engine.last_variant()["dbl"] == (1 if name == "oct104x6x5" else 0)
 
 
 # ---- scattered light: soc_sca_kernel (direct) on oct759, the sweep of rays on oct104x6x5 ----

@@ -67,6 +67,17 @@ def test_soc_mode_follows_the_same_trajectories(libm):
         assert np.allclose(T, libm[name][0], rtol=1e-4, atol=1e-6 * T.max())
 
 
+def test_x104_tells_a_float_walk_from_a_double_one(monkeypatch):
+    """The x104 case exists to catch a DBL kernel that walks in float: such a walk must move the tallies by more than the GPU
+    tests' rtol 1e-5 in many cells.  Observed: 104 cells of the 4601 that carry signal, largest relative difference 3.2e-4."""
+    import oracle.pyoracle
+    job, SELEM, ms = sc.job("x104")
+    assert oracle.pyoracle.double_index(job.cloud.NX, job.cloud.LEVELS) == 1
+    n, of = sc.float_walk_differs(lambda: split_host.sim_bg_split("soc", sc.job("x104")[0], SELEM, ms)[0], monkeypatch)
+    print("x104: %d of %d cells differ by more than 1e-5 when Index() runs in float" % (n, of))
+    assert n >= 50
+
+
 def test_half_ranges_sum_to_the_launch(libm):
     name = "oct6_selem3"
     job, SELEM, ms = sc.job(name)
