@@ -75,12 +75,17 @@ extern "C" __attribute__((visibility("default"))) void soc_prof_read(unsigned lo
 #define SOC_BRICK_PMAX 4096      // upper bound of packets per workgroup chunk (walks that keep the chunk's ranks in LDS)
 #define SOC_RANK_BITS 16         // a packet's rank among its workgroup's packets for one queue; the table entry sits above (<= 4096 queues or 1024 hash entries)
 #define SOC_LBRICK_PMAX 32768    // ... of soc_lbrick_walk, whose chunk lives in global memory only
+#define SOC_LB_BATCH 8           // soc_lbrick_walk, brick copy and flush: slots a thread has in flight between two waits for global memory
+// the SOC_LB_BATCH values of a batch have landed: a point the compiler moves none of their loads behind (it would sink a load into the branch that alone uses it)
+#define SOC_LANDED8(a) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]))
+static_assert(SOC_LB_BATCH == 8, "SOC_LANDED8 names the values of a batch one by one");
 
 enum { SOC_BM_STEP = 0, SOC_BM_CLIMB = 1, SOC_BM_SWAP = 3, SOC_BM_IDLE = 4 };
 
 struct __align__(16) SocPk2 { float4 A, B, C; uint4 D; };   // 64-B packet record, see soc_brick_walk
 
 struct SocDesc { int brick, start, count, pad; };
+static_assert(sizeof(SocDesc) == 16 && sizeof(SocLBrick) == 32, "soc_lbrick_walk reads both word by word");
 
 // Packet records and queue entries are touched once per pass.  Streaming them past the caches (-DSOC_BRICK_NT:
 // nontemporal) was measured: no change on a 256^3 hierarchy, -23 % on C2 (whose packets fit the last-level cache).
@@ -93,6 +98,7 @@ struct SocDesc { int brick, start, count, pad; };
 #endif
 typedef float soc_f4v __attribute__((ext_vector_type(4)));
 typedef uint32_t soc_u2v __attribute__((ext_vector_type(2)));
+typedef float soc_f2v __attribute__((ext_vector_type(2)));
 // Pointers that reach a kernel inside a struct are generic: the compiler emits FLAT loads and stores for them, and a flat
 // operation counts as an LDS operation too (lgkmcnt) -- every wait for an LDS read then waits for the global loads in flight
 // as well, the prefetched packet records included.  The walk's loop casts its pointers to the global address space.
@@ -102,6 +108,22 @@ typedef uint32_t soc_u2v __attribute__((ext_vector_type(2)));
 #define SOC_CHUNK_AT(base, slot) ((decltype(base))((SOC_GLOBAL const char *)(base) + (uint32_t)((uint32_t)(slot) << 2)))
 // (soc_lbrick_walk, swap arm) a field of the prefetched record becomes the lane's own: a move the compiler cannot fold into the record's register
 #define SOC_TAKE(dst, src) asm volatile("v_mov_b32 %0, %1" : "=v"(dst) : "v"(src))
+// a workgroup-uniform global pointer that came from memory, in scalar registers: accesses through it take their base from there
+template <typename T> __device__ __forceinline__ SOC_GLOBAL T *soc_uniform_ptr(SOC_GLOBAL T *p)
+{
+    const uint64_t a = (uint64_t)p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    return (SOC_GLOBAL T *)(((uint64_t)hi << 32) | lo);
+}
+// soc_tally (soc_walk.h) on a global pointer: an atomic that returns nothing and is no FLAT operation
+__device__ __forceinline__ void soc_tally_g(SOC_GLOBAL float *buf, int cell, float v)
+{
+#if defined(SOC_EXPERIMENT_NO_TALLY)
+    if (v == 1.2345e-30f) buf[cell] = v;
+#else
+    __hip_atomic_fetch_add(buf + cell, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
 __device__ __forceinline__ float4 soc_ld4(const float4 *p) { const soc_f4v v = SOC_NT_LOAD((const soc_f4v *)p);  return make_float4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ void soc_st4(float4 *p, float4 a) { soc_f4v v = { a.x, a.y, a.z, a.w };  SOC_NT_STORE(v, (soc_f4v *)p); }
 
@@ -690,11 +712,20 @@ __device__ __forceinline__ void soc_lbrick_tally(float *sT, float *sI, float *sV
 template <int WINT, bool RAY = false, bool ALI = false, bool LIM = false, bool CART = false, bool ABU = false, bool FLT = false>
 __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPack &K, const SocBrickArgs &A, const int bid)
 {
-    if (bid >= *A.ndesc) return;
-    SocDesc D = A.desc[bid];
+    // The prologue asks global memory three times, each time for everything it can name by then: (1) the pass's descriptor count, this
+    // workgroup's descriptor and the number of launches; (2) the brick's box and the launches' constants; (3) the brick's slots, a batch of
+    // loads in flight per thread.  What needs no load (the zeroes of the tallies, the arrivals table, the keys of a parked queue) is
+    // issued between a request and the first use of its answer (tools/isa_loop_count.py --around lists the waits).
+    const SOC_GLOBAL int *descp = (const SOC_GLOBAL int *)(A.desc + bid);            // desc holds a descriptor for every workgroup of the grid
+    const int nd = *(const SOC_GLOBAL int *)A.ndesc;                                  // (reserve_buffers: maxdesc entries, the grid walks maxdesc_now)
+    SocDesc D = { descp[0], descp[1], descp[2], descp[3] };
+    int Kn = *(const SOC_GLOBAL int *)&K.n;
+    asm volatile("" : "+v"(D.brick), "+v"(D.start), "+v"(D.count), "+v"(D.pad), "+v"(Kn));      // all asked for before the first is used
+    if (bid >= nd) return;
     D.brick = __builtin_amdgcn_readfirstlane(D.brick);  D.start = __builtin_amdgcn_readfirstlane(D.start);  D.count = __builtin_amdgcn_readfirstlane(D.count);
     if (D.brick >= A.NBQ) return;                          // an event queue: soc_brick_events
     const bool parked = __builtin_amdgcn_readfirstlane(D.pad) != 0;      // too few packets for a workgroup: they stay in the queue this pass (soc_brick_scan)
+    Kn = __builtin_amdgcn_readfirstlane(Kn);
     SOC_PROF_ENTRY;
     const int BV = A.CAP;                                  // slots in LDS
     const int nthr = (int)blockDim.x;
@@ -713,34 +744,75 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
     int   *sCtl = sH + (A.HS ? 2 * A.HS : ((NQ + 3) & ~3));   // [0] next packet, [1] tally events
     float *sL   = (float *)(sCtl + 4);                     // [4 * MAXLAUNCH] ABS, SCA, TW, flags (bit 0: SimRAM_CL) of every launch
     const SocSim &S = K.S[0];
-    for (int l = threadIdx.x; l < K.n; l += nthr) {
+    const int mybrick = (A.NBQ > A.NB) ? (D.brick % A.NB) : D.brick;
+    const int qbase = D.brick - mybrick;                   // first brick queue of this workgroup's launch (0 when the launches share queues)
+    // second request: the box, and launch threadIdx.x (a thread beyond the last launch reads the last one again and stores nothing;
+    // K.n >= 1: a sweep has a launch, soc_brick_run_pb refuses nlaunch < 1)
+    const SOC_GLOBAL int *lbrp = (const SOC_GLOBAL int *)(A.lbr + mybrick);
+    SocLBrick KB = { lbrp[0], lbrp[1], lbrp[2], lbrp[3], lbrp[4], lbrp[5], lbrp[6], lbrp[7] };
+    const SOC_GLOBAL SocSim *Sl = (const SOC_GLOBAL SocSim *)K.S + min((int)threadIdx.x, Kn - 1);
+    const float l_abs = Sl->ABS, l_sca = Sl->SCA, l_tw = Sl->TW;
+    const int l_source = Sl->SOURCE, l_scakind = LIM ? Sl->SCAKIND : 0;
+    // Every tally slot of the LDS starts at zero: all CAP of them, not the brick's nslot as the flush would need -- nslot is part of the
+    // box that is on its way, and these stores fill that wait.  A brick far below the cap (small models) pays LDS stores it did not pay
+    // before; the bricks of a partition fill their LDS, and the float form on 99 bricks of oct64_l4 still gained.
+    if (!parked) {
+        for (int i = threadIdx.x; i < BV; i += nthr) {
+            if (!RAY && WINT != 3) sT[i] = 0.0f;
+            if (WINT) sI[i] = 0.0f;
+            if (WINT == 2) { sV[i] = 0.0f;  sV[BV + i] = 0.0f;  sV[2 * BV + i] = 0.0f; }
+            if (ALI) sX[i] = 0.0f;
+        }
+    }
+    soc_qh_init(sH, A.HS, NQ);
+    if (threadIdx.x < 2) sCtl[threadIdx.x] = 0;
+    if (parked) for (int j = threadIdx.x; j < D.count; j += nthr) A.keyq[D.start + j] = (uint32_t)D.brick;
+    if ((int)threadIdx.x < Kn) {
+        const int l = threadIdx.x;
+        sL[4 * l] = l_abs;  sL[4 * l + 1] = l_sca;  sL[4 * l + 2] = l_tw;
+        sL[4 * l + 3] = __int_as_float(((l_source == SOC_SOURCE_CL) ? 1 : 0) | ((LIM && l_scakind == SOC_SCA_PB + 1) ? 2 : 0));
+    }
+    for (int l = threadIdx.x + nthr; l < Kn; l += nthr) {  // (a workgroup of fewer threads than launches)
         sL[4 * l] = K.S[l].ABS;  sL[4 * l + 1] = K.S[l].SCA;  sL[4 * l + 2] = K.S[l].TW;
         sL[4 * l + 3] = __int_as_float(((K.S[l].SOURCE == SOC_SOURCE_CL) ? 1 : 0) | ((LIM && K.S[l].SCAKIND == SOC_SCA_PB + 1) ? 2 : 0));
     }
-    const int mybrick = (A.NBQ > A.NB) ? (D.brick % A.NB) : D.brick;
-    const int qbase = D.brick - mybrick;                   // first brick queue of this workgroup's launch (0 when the launches share queues)
-    SocLBrick KB = A.lbr[mybrick];
     // workgroup-uniform values that came from global memory go to scalar registers now: a use inside the loop would
     // otherwise wait for every load in flight (s_waitcnt vmcnt(0)), the prefetched packets included
     KB.x0 = __builtin_amdgcn_readfirstlane(KB.x0);  KB.y0 = __builtin_amdgcn_readfirstlane(KB.y0);  KB.z0 = __builtin_amdgcn_readfirstlane(KB.z0);
     KB.bx = __builtin_amdgcn_readfirstlane(KB.bx);  KB.by = __builtin_amdgcn_readfirstlane(KB.by);  KB.bz = __builtin_amdgcn_readfirstlane(KB.bz);
     KB.base = __builtin_amdgcn_readfirstlane(KB.base);  KB.nslot = __builtin_amdgcn_readfirstlane(KB.nslot);
     if (!parked) {
-        const float *src = A.btree + KB.base;
-        for (int i = threadIdx.x; i < KB.nslot; i += nthr) {
-            sD[i] = src[i];  if (!RAY && WINT != 3) sT[i] = 0.0f;  if (WINT) sI[i] = 0.0f;
-            if (WINT == 2) { sV[i] = 0.0f;  sV[BV + i] = 0.0f;  sV[2 * BV + i] = 0.0f; }
-            if (ALI) { sX[i] = 0.0f;  sC[i] = A.bcell[KB.base + i]; }
-        }
-        if (ABU) {                                         // the opacities of this queue's group of launches, in slot order (entries of refined cells are never used)
-            const float2 *ksrc = A.kopt + (long long)(qbase / A.NB) * A.kopt_stride + KB.base;
-            float2 *dst = (float2 *)(sD + BV);
-            for (int i = threadIdx.x; i < KB.nslot; i += nthr) dst[i] = ksrc[i];
+        // third request: the brick's slots.  A thread asks for SOC_LB_BATCH of its slots, then writes them to LDS: one wait per batch, not
+        // one per slot (dword loads: the aim is the latency, and the arrays need no padding or alignment for them).  A slot index past
+        // the brick's last is clamped for the load and not stored.
+        const SOC_GLOBAL float *src = (const SOC_GLOBAL float *)A.btree + KB.base;
+        const SOC_GLOBAL int *csrc = (const SOC_GLOBAL int *)A.bcell + KB.base;
+        // (ABU) the opacities of this queue's group of launches, in slot order (entries of refined cells are never used)
+        const SOC_GLOBAL soc_f2v *ksrc = (const SOC_GLOBAL soc_f2v *)A.kopt + (ABU ? ((long long)(qbase / A.NB) * A.kopt_stride + KB.base) : 0);
+        soc_f2v *dK = (soc_f2v *)(sD + BV);
+        const int last = KB.nslot - 1;
+        for (int i0 = threadIdx.x; i0 < KB.nslot; i0 += SOC_LB_BATCH * nthr) {
+            float d[SOC_LB_BATCH];  int c[SOC_LB_BATCH];  soc_f2v k[SOC_LB_BATCH];
+#pragma unroll
+            for (int u = 0; u < SOC_LB_BATCH; u++) {
+                const int i = min(i0 + u * nthr, last);
+                d[u] = src[i];
+                if (ALI) c[u] = csrc[i];
+                if (ABU) k[u] = ksrc[i];
+            }
+            SOC_LANDED8(d);                                // every load of the batch is issued before the first is waited for
+            if (ALI) SOC_LANDED8(c);
+#pragma unroll
+            for (int u = 0; u < SOC_LB_BATCH; u++) {
+                const int i = i0 + u * nthr;
+                if (i <= last) {
+                    sD[i] = d[u];
+                    if (ALI) sC[i] = c[u];
+                    if (ABU) dK[i] = k[u];
+                }
+            }
         }
     }
-    soc_qh_init(sH, A.HS, NQ);
-    if (threadIdx.x < 2) sCtl[threadIdx.x] = 0;
-    if (parked) for (int j = threadIdx.x; j < D.count; j += nthr) A.keyq[D.start + j] = (uint32_t)D.brick;
     __syncthreads();
 
     // Uniform values the loop needs now and then.  Left as plain kernel arguments the compiler, out of scalar registers,
@@ -1061,24 +1133,68 @@ __device__ __forceinline__ void soc_lbrick_walk(const SocGrid &G, const SocSimPa
 
     SOC_PROF_T(5);                                         // (what the last iteration left: next to nothing)
     atomicAdd(&sCtl[1], (int)n_tally);
+    // The flush of the tallies.  What it needs from global memory is asked for before the barrier -- the loop's registers are free, and
+    // the answers arrive while the wave waits for the workgroup's others: the tally pointers of the workgroup's launches (to scalar
+    // registers, as global pointers: the atomics then return nothing and count in vmcnt only) and the cell numbers of the thread's
+    // first SOC_LB_BATCH slots.  Inside, the next batch's cell numbers are requested before the atomics of the current one, so a batch
+    // waits once: for those cell numbers and, vmcnt retiring in order, for its own atomics in flight beside them (tools/isa_loop_count.py --around).
+    const bool flush = !parked && !RAY && KB.nslot > 0;
+    const SOC_GLOBAL int *cells = (const SOC_GLOBAL int *)A.bcell + KB.base;
+    const int last = KB.nslot - 1;
+    SOC_GLOBAL float *gT = nullptr, *gI = nullptr, *gX = nullptr, *gV = nullptr;
+    float gtw = 0.0f;
+    int gcells = 0;
+    int cell[SOC_LB_BATCH];
+    if (flush) {
+        const SOC_GLOBAL SocSim *S0 = (const SOC_GLOBAL SocSim *)K.S;
+        gT = (SOC_GLOBAL float *)S0->TABS;
+        if (ALI) gX = (SOC_GLOBAL float *)S0->XAB;
+        if (WINT == 2) gcells = S0->CELLS;
+        if (WINT) {
+            const SOC_GLOBAL SocSim *Sg = S0 + *((const SOC_GLOBAL int *)K.gfirst + qbase / A.NB);      // the launches this workgroup's queue belongs to
+            gI = (SOC_GLOBAL float *)Sg->INT;
+            if (WINT == 2) gV = (SOC_GLOBAL float *)Sg->INTV;
+            if (WINT == 3) gtw = Sg->TW;
+        }
+#pragma unroll
+        for (int u = 0; u < SOC_LB_BATCH; u++) cell[u] = cells[min((int)threadIdx.x + u * nthr, last)];
+    }
     __syncthreads();
     SOC_PROF_T(6);                                         // the wait for the workgroup's other waves
-    if (!parked && !RAY) {
-        const int *cells = A.bcell + KB.base;
-        for (int i = threadIdx.x; i < KB.nslot; i += nthr) {
-            const float vi = WINT ? sI[i] : 0.0f;
-            const float v = (WINT == 3) ? (vi * K.S[K.gfirst[qbase / A.NB]].TW) : sT[i];
-            if (v != 0.0f || vi != 0.0f || (ALI && sX[i] != 0.0f)) {
-                const int cell = cells[i];
-                soc_tally(S.TABS, cell, v);
-                if (WINT) soc_tally(K.S[K.gfirst[qbase / A.NB]].INT, cell, vi);      // the launches this workgroup's queue belongs to
-                if (ALI && (sX[i] != 0.0f)) soc_tally(S.XAB, cell, sX[i]);
-                if (WINT == 2) {
-                    float *IV = K.S[K.gfirst[qbase / A.NB]].INTV;
-                    const long C = K.S[0].CELLS;
-                    soc_tally(IV, cell, sV[i]);  soc_tally(IV + C, cell, sV[BV + i]);  soc_tally(IV + 2 * C, cell, sV[2 * BV + i]);
+    if (flush) {
+        { uint32_t w = __float_as_uint(gtw);  w = __builtin_amdgcn_readfirstlane(w);  gtw = __uint_as_float(w); }
+        gcells = __builtin_amdgcn_readfirstlane(gcells);
+        gT = soc_uniform_ptr(gT);
+        if (WINT) gI = soc_uniform_ptr(gI);
+        if (ALI) gX = soc_uniform_ptr(gX);
+        if (WINT == 2) gV = soc_uniform_ptr(gV);
+        for (int i0 = threadIdx.x; i0 < KB.nslot; i0 += SOC_LB_BATCH * nthr) {
+            float v[SOC_LB_BATCH], vi[SOC_LB_BATCH], vx[SOC_LB_BATCH], v0[SOC_LB_BATCH], v1[SOC_LB_BATCH], v2[SOC_LB_BATCH];
+            int ncell[SOC_LB_BATCH];
+#pragma unroll
+            for (int u = 0; u < SOC_LB_BATCH; u++) {       // a slot past the brick's last reads as empty
+                const int i = i0 + u * nthr;
+                const bool in = (i <= last);
+                const int j = in ? i : 0;
+                vi[u] = (WINT && in) ? sI[j] : 0.0f;
+                v[u]  = (WINT == 3) ? (vi[u] * gtw) : (in ? sT[j] : 0.0f);
+                vx[u] = (ALI && in) ? sX[j] : 0.0f;
+                if (WINT == 2) { v0[u] = in ? sV[j] : 0.0f;  v1[u] = in ? sV[BV + j] : 0.0f;  v2[u] = in ? sV[2 * BV + j] : 0.0f; }
+            }
+            const int n0 = i0 + SOC_LB_BATCH * nthr;       // (past the brick's last slot: that slot's number again, never used)
+#pragma unroll
+            for (int u = 0; u < SOC_LB_BATCH; u++) ncell[u] = cells[min(n0 + u * nthr, last)];
+#pragma unroll
+            for (int u = 0; u < SOC_LB_BATCH; u++) {
+                if (v[u] != 0.0f || vi[u] != 0.0f || (ALI && vx[u] != 0.0f)) {
+                    soc_tally_g(gT, cell[u], v[u]);
+                    if (WINT) soc_tally_g(gI, cell[u], vi[u]);
+                    if (ALI && (vx[u] != 0.0f)) soc_tally_g(gX, cell[u], vx[u]);
+                    if (WINT == 2) { soc_tally_g(gV, cell[u], v0[u]);  soc_tally_g(gV + (long)gcells, cell[u], v1[u]);  soc_tally_g(gV + 2 * (long)gcells, cell[u], v2[u]); }
                 }
             }
+#pragma unroll
+            for (int u = 0; u < SOC_LB_BATCH; u++) cell[u] = ncell[u];
         }
     }
     SOC_PROF_T(7);                                         // tallies -> global memory
