@@ -682,6 +682,37 @@ int soc_mabu_accumulate_p(soc_ctx *ctx, int idust);
 int soc_mabu_ratio(soc_ctx *ctx);
 int soc_mabu_download_p(soc_ctx *ctx, int64_t c0, int64_t n, float *R);
 
+/* ---- the emission of one dust re-emission iteration, RESIDENT for the cell-emission launches of the next ---- */
+
+/* With `iterations N` and `cellpackets` the emission solved from the absorptions of iteration k-1 is what SimRAM_CL sends at every
+ * frequency of iteration k (ASOC.py:1593-1810).  The multi-dust stage leaves it as SUM[cells][NFREQ], a launch wants EMIT[CELLS] of one
+ * frequency: a column, 4 useful bytes per 128-byte line, at every one of NFREQ launches.  So the resident copy is held transposed,
+ * ET[NFREQ][CELLS], filled by one tiled transpose per iteration, and a launch's EMIT is made from one contiguous row of it:
+ *   soc_emitted_begin(NFREQ) reserves ET for the cells of the grid (after soc_set_grid), zeroed.  Where it does not fit the free device
+ *       memory the call fails with SOC_ERR_STATE and nothing is reserved or released; a second soc_emitted_begin replaces the first;
+ *       soc_set_grid, soc_emitted_end and soc_destroy release it;
+ *   soc_emitted_upload(c0, n, rows) writes rows[n][NFREQ], as the emitted file holds them, to cells [c0, c0+n) (any chunking);
+ *   soc_emitted_from_mabu(c0) writes SUM of the open soc_mabu_begin, device to device, to cells [c0, c0 + its cells): before
+ *       soc_mabu_end, after the last soc_mabu_accumulate.  SOC_ERR_STATE without an open soc_mabu_begin, SOC_ERR_ARG where its NFREQ
+ *       differs or its cells run past CELLS;
+ *   soc_emitted_download(c0, n, rows) reads rows back, bit for bit what went in;
+ *   soc_set_emission_column(ifreq, COEFF) fills the EMIT of the next soc_sim_cl as soc_set_emission would from the host statement
+ *       (ASOC.py:1737-1740): EMIT[c] = ET[ifreq][c] * (COEFF[level(c)] * DENS[c]), COEFF[LEVELS] = GL*PARSEC/8^level/FACTOR as float,
+ *       both products rounded to float, no fused multiply-add; exactly 0 where DENS[c] < 1e-10 (links, empty cells), by selection: a NaN
+ *       or the -1e20 of a link's row does not survive.  EMWEI stays what it is.  Like soc_set_emission it does not wait for deferred
+ *       launches, which keep their own copy;
+ *   soc_read_emission(EMIT, n) reads the first n values of what the next soc_sim_cl would use (tests);
+ *   soc_emitted_end() frees it.
+ * Every call but _begin and _end is SOC_ERR_STATE before soc_emitted_begin; ifreq outside [0, NFREQ), c0 < 0, n < 1 or c0 + n > CELLS
+ * are SOC_ERR_ARG.  A refused call leaves ET as it was. */
+int soc_emitted_begin(soc_ctx *ctx, int NFREQ);
+int soc_emitted_upload(soc_ctx *ctx, int64_t c0, int64_t n, const float *rows);
+int soc_emitted_from_mabu(soc_ctx *ctx, int64_t c0);
+int soc_emitted_download(soc_ctx *ctx, int64_t c0, int64_t n, float *rows);
+int soc_set_emission_column(soc_ctx *ctx, int ifreq, const float *COEFF);
+int soc_read_emission(soc_ctx *ctx, float *EMIT, int64_t n);
+int soc_emitted_end(soc_ctx *ctx);
+
 /* ---- the library method for dust emission: soc_library.py with kernel_soc_library.c ---- */
 
 /* A model with stochastically heated grains is simulated at three reference frequencies only; the emission of a cell is then

@@ -726,6 +726,136 @@ class AbsorptionRun(MapProducts):
         self.timers["Tpull"] += time.time() - t0
 
     # ---------------------------------------------------------------------------------
+    def require_emission_at_every_frequency(self):
+        I1, I2 = self.emitted_range()
+        if (I2 - I1 + 1 < self.NFREQ) and self.U.ITERATIONS > 0 and self.CLPAC > 0:
+            raise ValueError("remit cannot restrict the frequencies when cell emission is simulated (ASOC.py:209-211)")
+
+    @_local_routing()
+    def simulate_cell_emission(self, EMITTED, FABSORBED, resident=False):
+        """One dust re-emission iteration as a run of its own with `iterations 1` does it (soc_amd.driver's loop): TABS zeroed, the host
+        generator made anew, the emission EMITTED[CELLS, NFREQ] of the previous iteration sent from the cells at every simulated
+        frequency, each frequency's INT tally added to its column of FABSORBED.  resident: see _cell_emission_pass."""
+        self.require_emission_at_every_frequency()
+        self.eng.zero(0)
+        hostrng = np.random.default_rng(int(self.U.SEED * 2 ** 31) if self.U.SEED > 0 else None)
+        self._cell_emission_pass(EMITTED, hostrng, FABSORBED, True, resident=resident)
+
+    def _cell_emission_pass(self, EMITTED, hostrng, FABSORBED=None, read_int=False, OEMITTED=None, XEM=None, resident=False):
+        """One iteration's SimRAM_CL launches (ASOC.py:1700-1910): the dust emission EMITTED[CELLS, emitted_range()] of the previous
+        iteration, sent with `cellpackets` packets at every simulated frequency.  The absorptions go to the engine's TABS (zeroed by the
+        caller) and, with read_int, the INT tally of every frequency is added to its column of FABSORBED (and goes to the intensity file).
+        hostrng: the host generator of `emweight` and of the seeds of a run without `seed`; the iterations of one run share it.
+        OEMITTED (reference field): the packets carry EMITTED - OEMITTED, and OEMITTED becomes EMITTED; XEM (ALI): receives the integral
+        of the emitted energy.
+        resident: the engine holds EMITTED itself (emitted_begin ... emitted_from_mabu) and makes a frequency's emission from it
+        (set_emission_column) -- the bits the host statements below hand to set_emission; EMITTED is not looked at (`emweight 0` only)."""
+        U, e, c = self.U, self.eng, self.cloud
+        CELLS, NFREQ, FFREQ = c.CELLS, self.NFREQ, self.FFREQ
+        I1, I2 = self.emitted_range()
+        ali = XEM is not None
+        if resident and (U.USE_EMWEIGHT > 0 or ali or OEMITTED is not None):
+            raise ValueError("the resident emission serves `emweight 0` without ALI and without the reference field")
+        COEFF = [U.GL * PARSEC / (8.0 ** level) / launch.FACTOR for level in range(c.LEVELS)]
+        EMWEI = np.ones(CELLS, np.float32) * np.float32(self.CLPAC / CELLS) if U.USE_EMWEIGHT > 0 else None
+        EMPAC = None
+        EMIT = None if resident else np.zeros(CELLS, np.float32)
+        GLOBAL, BATCH = self.GLOBAL_0, max(1, int(self.CLPAC / CELLS))
+        first, count = self.comm.shard(GLOBAL) if self.comm else (0, GLOBAL)
+        skip = U.EMWEIGHT_SKIP - 1
+        # TABS-only iterations: the frequencies are handed to the engine together; with `global` raised to
+        # about the number of cells they share brick sweeps (include/soc_hip.h: soc_batch_begin, soc_sim_cl)
+        deferred = (not self.with_int) and (not ali) and U.USE_EMWEIGHT < 2
+        if deferred:
+            e.batch_begin(0)
+        for IFREQ in range(NFREQ):
+            FREQ = float(FFREQ[IFREQ])
+            if self.with_int:
+                e.zero(1)
+            if (FREQ < U.SIM_F[0]) or (FREQ > U.SIM_F[1]):
+                continue
+            t0 = time.time()
+            ABS_f, _ = self._optical_for(IFREQ)
+            FF = np.float32(launch.trapezoid_weight(FFREQ, IFREQ))
+            self._scatter_tables_for(IFREQ)
+            if IFREQ < I1 or IFREQ > I2:
+                continue
+            if resident:
+                e.set_emission_column(IFREQ - I1, np.asarray(COEFF, np.float32))
+            else:
+                if OEMITTED is not None:                       # ASOC.py:1728-1735
+                    EMIT[:] = EMITTED[:, IFREQ - I1] - OEMITTED[:, IFREQ - I1]
+                    OEMITTED[:, IFREQ - I1] = EMITTED[:, IFREQ - I1]
+                else:
+                    EMIT[:] = EMITTED[:, IFREQ - I1]
+                for level in range(c.LEVELS):
+                    a, b = int(c.OFF[level]), int(c.OFF[level] + c.LCELLS[level])
+                    EMIT[a:b] *= COEFF[level] * c.DENS[a:b]
+                EMIT[c.DENS < 1.0e-10] = 0.0
+            if ali:
+                XEM += EMIT * np.float64(FF)                   # integral of the emitted energy (ASOC.py:1741)
+            if U.USE_EMWEIGHT > 0:                             # ASOC.py:1745-1771
+                skip += 1
+                if skip % U.EMWEIGHT_SKIP == 0:
+                    tmp = np.asarray(EMITTED[:, IFREQ - I1], np.float64).copy()
+                    tmp[~np.isfinite(tmp)] = 0.0
+                    tmp[:] = self.CLPAC * tmp / (np.sum(tmp) + 1.0e-65)
+                    EMWEI[:] = np.clip(tmp, U.EMWEIGHT_LIM[0], U.EMWEIGHT_LIM[1])
+                    EMWEI[hostrng.random(CELLS) > EMWEI] = 0.0
+                    if U.EMWEIGHT_LIM[2] > 0.0:
+                        EMWEI[EMWEI < U.EMWEIGHT_LIM[2]] = 0.0
+                    if U.USE_EMWEIGHT == 2:                    # packets per cell in multiples of 100 (ASOC.py:1773-1780)
+                        EMPAC = np.asarray(100 * np.round(tmp / 100), np.int32)
+                        EMWEI[:] = 1.0 / (EMPAC + 1e-10)
+            if not resident:
+                e.set_emission(EMIT, EMWEI)
+            if U.SEED > 0:
+                seed = float(np.fmod(U.SEED + IFREQ * launch.SEED1, 1.0))      # ASOC.py:1807 (no SEED0 here)
+            else:
+                seed = float(hostrng.random())
+                if self.comm and self.world > 1:
+                    seed = self._bcast_seed(seed)
+            self.timers["Tpush"] += time.time() - t0
+            t0 = time.time()
+            if U.USE_EMWEIGHT == 2 and EMPAC is not None:
+                # the host lists the cells that still owe packets, 100 per cell and launch (ASOC.py:1811-1840)
+                EMDONE = np.zeros(CELLS, np.int32)
+                EMINDEX = np.zeros(CELLS, np.int32)
+                f2, c2 = self.comm.shard(8192) if self.comm else (0, 8192)
+                while True:
+                    mm = np.nonzero(EMDONE < EMPAC)[0]
+                    if len(mm) < 1:
+                        break
+                    EMINDEX[:len(mm)] = mm
+                    EMINDEX[len(mm):] = -1
+                    e.set_emindex(EMINDEX)
+                    e.sim_cl(2, self.CLPAC, BATCH, seed, FF, 8192, gid_first=f2, gid_count=c2)
+                    EMDONE[mm] += 100
+                    self.packets += 100 * len(mm)
+            else:
+                e.sim_cl(2, self.CLPAC, BATCH, seed, FF, GLOBAL, gid_first=first, gid_count=count)
+            if self.with_int and self.comm:
+                self.comm.all_reduce_tally(e, 1)
+            if not deferred:
+                e.sync()
+            self.timers["Tkernel"] += time.time() - t0
+            self.packets += CELLS * BATCH
+            if read_int and (FABSORBED is not None or U.SAVE_INTENSITY > 0):
+                TMP = e.read_tally(1)
+                if FABSORBED is not None:
+                    FABSORBED[:, IFREQ] += TMP[0::self.absthin]
+                if U.SAVE_INTENSITY > 0:                       # ASOC.py:1885-1908
+                    self._save_intensity(IFREQ, FREQ, ABS_f, TMP)
+        if deferred:
+            t0 = time.time()
+            e.batch_end()
+            e.sync()
+            self.timers["Tkernel"] += time.time() - t0
+        if self.comm:
+            self.comm.all_reduce_tally(e, 0)
+            if ali:
+                self.comm.all_reduce_tally(e, 2)
+
     @_local_routing()
     def emission_iterations(self, CTABS, FABSORBED):
         """Simulation <-> temperature cycles (ASOC.py:1593-2260, the paths without reference field and
@@ -741,8 +871,7 @@ class AbsorptionRun(MapProducts):
         solve = (not U.NOSOLVE) and bool(U.NOABSORBED)
         if solve and self.NDUST > 1:
             raise ValueError("temperatures can be solved here for a single dust component only (ASOC.py:260-263)")
-        if (I2 - I1 + 1 < NFREQ) and U.ITERATIONS > 0 and self.CLPAC > 0:
-            raise ValueError("remit cannot restrict the frequencies when cell emission is simulated (ASOC.py:209-211)")
+        self.require_emission_at_every_frequency()
         EMITTED = None
         try:
             EMITTED = np.array(files.mmap_emitted(U.file_emitted, CELLS, I2 - I1 + 1))
@@ -752,14 +881,11 @@ class AbsorptionRun(MapProducts):
         if solve:
             Emin, kE, TTT = launch.temperature_table(FFREQ, self.AFABS[0], U.GL)
             FACTOR_f, LENGTH_f = launch.kernel_literals(U.GL)
-        EMWEI = np.ones(CELLS, np.float32) * np.float32(self.CLPAC / CELLS) if U.USE_EMWEIGHT > 0 else None
-        EMPAC = None
         ali = bool(U.WITH_ALI)
         if ali:
             e.set_ali(1)
         beta = None
         hostrng = np.random.default_rng(int(U.SEED * 2 ** 31) if U.SEED > 0 else None)
-        EMIT = np.zeros(CELLS, np.float32)
         # reference field (`reference` key, ASOC.py:796-812, :1571-1586): the packets of an iteration carry the CHANGE of
         # the emission since the previous one, EMITTED - OEMITTED; the absorptions the previous emission caused, OTABS,
         # are added back on the host.  Both are damped by k = iteration/ITERATIONS at the start of an iteration, so the
@@ -785,98 +911,7 @@ class AbsorptionRun(MapProducts):
                 OEMITTED *= np.float32(k)
                 OTABS *= np.float32(k)
             if self.CLPAC > 0:
-                GLOBAL, BATCH = self.GLOBAL_0, max(1, int(self.CLPAC / CELLS))
-                first, count = self.comm.shard(GLOBAL) if self.comm else (0, GLOBAL)
-                skip = U.EMWEIGHT_SKIP - 1
-                # TABS-only iterations: the frequencies are handed to the engine together; with `global` raised to
-                # about the number of cells they share brick sweeps (include/soc_hip.h: soc_batch_begin, soc_sim_cl)
-                deferred = (not self.with_int) and (not ali) and U.USE_EMWEIGHT < 2
-                if deferred:
-                    e.batch_begin(0)
-                for IFREQ in range(NFREQ):
-                    FREQ = float(FFREQ[IFREQ])
-                    if self.with_int:
-                        e.zero(1)
-                    if (FREQ < U.SIM_F[0]) or (FREQ > U.SIM_F[1]):
-                        continue
-                    t0 = time.time()
-                    ABS_f, _ = self._optical_for(IFREQ)
-                    FF = np.float32(launch.trapezoid_weight(FFREQ, IFREQ))
-                    self._scatter_tables_for(IFREQ)
-                    if IFREQ < I1 or IFREQ > I2:
-                        continue
-                    if OEMITTED is not None:                       # ASOC.py:1728-1735
-                        EMIT[:] = EMITTED[:, IFREQ - I1] - OEMITTED[:, IFREQ - I1]
-                        OEMITTED[:, IFREQ - I1] = EMITTED[:, IFREQ - I1]
-                    else:
-                        EMIT[:] = EMITTED[:, IFREQ - I1]
-                    for level in range(c.LEVELS):
-                        coeff = U.GL * PARSEC / (8.0 ** level) / launch.FACTOR
-                        a, b = int(c.OFF[level]), int(c.OFF[level] + c.LCELLS[level])
-                        EMIT[a:b] *= coeff * c.DENS[a:b]
-                    EMIT[c.DENS < 1.0e-10] = 0.0
-                    if ali:
-                        XEM += EMIT * np.float64(FF)               # integral of the emitted energy (ASOC.py:1741)
-                    if U.USE_EMWEIGHT > 0:                         # ASOC.py:1745-1771
-                        skip += 1
-                        if skip % U.EMWEIGHT_SKIP == 0:
-                            tmp = np.asarray(EMITTED[:, IFREQ - I1], np.float64).copy()
-                            tmp[~np.isfinite(tmp)] = 0.0
-                            tmp[:] = self.CLPAC * tmp / (np.sum(tmp) + 1.0e-65)
-                            EMWEI[:] = np.clip(tmp, U.EMWEIGHT_LIM[0], U.EMWEIGHT_LIM[1])
-                            EMWEI[hostrng.random(CELLS) > EMWEI] = 0.0
-                            if U.EMWEIGHT_LIM[2] > 0.0:
-                                EMWEI[EMWEI < U.EMWEIGHT_LIM[2]] = 0.0
-                            if U.USE_EMWEIGHT == 2:                # packets per cell in multiples of 100 (ASOC.py:1773-1780)
-                                EMPAC = np.asarray(100 * np.round(tmp / 100), np.int32)
-                                EMWEI[:] = 1.0 / (EMPAC + 1e-10)
-                    e.set_emission(EMIT, EMWEI)
-                    if U.SEED > 0:
-                        seed = float(np.fmod(U.SEED + IFREQ * launch.SEED1, 1.0))      # ASOC.py:1807 (no SEED0 here)
-                    else:
-                        seed = float(hostrng.random())
-                        if self.comm and self.world > 1:
-                            seed = self._bcast_seed(seed)
-                    self.timers["Tpush"] += time.time() - t0
-                    t0 = time.time()
-                    if U.USE_EMWEIGHT == 2 and EMPAC is not None:
-                        # the host lists the cells that still owe packets, 100 per cell and launch (ASOC.py:1811-1840)
-                        EMDONE = np.zeros(CELLS, np.int32)
-                        EMINDEX = np.zeros(CELLS, np.int32)
-                        f2, c2 = self.comm.shard(8192) if self.comm else (0, 8192)
-                        while True:
-                            mm = np.nonzero(EMDONE < EMPAC)[0]
-                            if len(mm) < 1:
-                                break
-                            EMINDEX[:len(mm)] = mm
-                            EMINDEX[len(mm):] = -1
-                            e.set_emindex(EMINDEX)
-                            e.sim_cl(2, self.CLPAC, BATCH, seed, FF, 8192, gid_first=f2, gid_count=c2)
-                            EMDONE[mm] += 100
-                            self.packets += 100 * len(mm)
-                    else:
-                        e.sim_cl(2, self.CLPAC, BATCH, seed, FF, GLOBAL, gid_first=first, gid_count=count)
-                    if self.with_int and self.comm:
-                        self.comm.all_reduce_tally(e, 1)
-                    if not deferred:
-                        e.sync()
-                    self.timers["Tkernel"] += time.time() - t0
-                    self.packets += CELLS * BATCH
-                    if iteration == U.ITERATIONS - 1 and (FABSORBED is not None or U.SAVE_INTENSITY > 0):
-                        TMP = e.read_tally(1)
-                        if FABSORBED is not None:
-                            FABSORBED[:, IFREQ] += TMP[0::self.absthin]
-                        if U.SAVE_INTENSITY > 0:                   # ASOC.py:1885-1908
-                            self._save_intensity(IFREQ, FREQ, ABS_f, TMP)
-                if deferred:
-                    t0 = time.time()
-                    e.batch_end()
-                    e.sync()
-                    self.timers["Tkernel"] += time.time() - t0
-                if self.comm:
-                    self.comm.all_reduce_tally(e, 0)
-                    if ali:
-                        self.comm.all_reduce_tally(e, 2)
+                self._cell_emission_pass(EMITTED, hostrng, FABSORBED, iteration == U.ITERATIONS - 1, OEMITTED, XEM)
                 if OEMITTED is not None:
                     # the device holds the absorptions of EMITTED - OEMITTED: add what OEMITTED caused (ASOC.py:1965-1975)
                     EABS = e.read_tally(0) + OTABS

@@ -278,6 +278,12 @@ hipError_t soc_launch_mabu_poleq(long long cells, int NFREQ, int NA, const float
                                  float *PEM, hipStream_t st);
 hipError_t soc_launch_mabu_ratio(long long cells, int NFREQ, const float *SUM, float *PSUM, hipStream_t st);
 
+// the resident emission of the re-emission iterations (soc_reemit.hip): ROWS[n][NFREQ] <-> cells [c0, c0 + n) of ET[NFREQ][CELLS], and
+// EMIT[c] = COL[c] * (COEFF[level(c)] * DENS[c]), 0 where DENS[c] < 1e-10 (COEFF: LEVELS host floats, COL: a row of ET)
+hipError_t soc_launch_reemit_to_columns(long long n, int NFREQ, long long CELLS, long long c0, const float *ROWS, float *ET, hipStream_t st);
+hipError_t soc_launch_reemit_to_rows(long long n, int NFREQ, long long CELLS, long long c0, const float *ET, float *ROWS, hipStream_t st);
+hipError_t soc_launch_reemit_column(const SocGrid &G, const float *COEFF, const float *COL, float *EMIT, hipStream_t st);
+
 // the library method (soc_library.hip).  The reference columns of cell `c` are ABS[c * stride + c0 | c1 | c2].
 struct SocLibSolve {
     long long    n;                  // cells

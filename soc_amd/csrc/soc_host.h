@@ -1,4 +1,4 @@
-// soc_host.h -- what the host units of libsoc_hip.so share (soc_capi.hip, soc_capi_post.hip, soc_capi_a2e.hip, soc_capi_library.hip, soc_capi_probe.hip):
+// soc_host.h -- what the host units of libsoc_hip.so share (soc_capi.hip, soc_capi_post.hip, soc_capi_a2e.hip, soc_capi_reemit.hip, soc_capi_library.hip, soc_capi_probe.hip):
 // the handle, the error and flush idioms.  Every device allocation of a handle is a DevBuf (soc_devbuf.h) that the handle owns: its
 // members, and the packet records, queues and bricks of its brick sweeps (SocSweepState, soc_brick.hip).  Kernels do not include it.
 #pragma once
@@ -129,6 +129,10 @@ struct soc_ctx {
     DevBuf<float>  mPSUM;                                    // soc_mabu_begin_pol: the abundance-weighted sum of the polarised emission, then R
     int     mabu_ndust = 0;
     bool    mabu_tables = false;
+    // the resident emission of the re-emission iterations (soc_emitted_*): ET[et_nfreq][CELLS], transposed so that a frequency is a
+    // contiguous row; eRows stages the rows of an upload or a download.  soc_set_grid releases both
+    DevBuf<float> eET, eRows;
+    int     et_nfreq = 0;              // 0: not open
     // the library method (soc_library_*): the resident table -- I1 | dI1 | I2 | dI2 | X | Y | Z | E0 in one block, the selected emission
     // columns [N^3][lib_nout] -- and the miss list of a look-up
     int     lib_N = 0, lib_nout = 0;

@@ -24,6 +24,17 @@ map is made with the column of its own frequency (the reference writes <emitted>
 hand, A2E_MABU.py:1190-1195); with `polred` the file wins; --keep-files writes <emitted>.R as well.  The neural-network and library
 shortcuts (nnmake, nnsolve, libabs ...) and cosmic-ray heating are not part of this path and are refused.  With several ranks the
 first stage shards work items (soc_amd.dist), the second the cells; rank 0 writes.
+
+Dust re-emission (`iterations N` with `cellpackets`): the constant sources are simulated once and their absorptions C kept unscaled;
+E_0 is solved from them; then, N times, the emission E_(k-1) is sent from the cells at every simulated frequency (SimRAM_CL, as a run
+with `iterations 1` and `nosolve` that reads the emitted file of the iteration before: the same packet seeds, the host generator of
+`emweight` made anew), its absorptions are added to a copy of C, and E_k is solved from the sum -- the chain
+soc_amd.asoc, soc_amd.mabu, soc_amd.asoc ... without its files.  The products are those of the last iteration.  Where the engine has
+the soc_emitted_* calls, stage 2 took its device path, there is one rank and `emweight 0`, the emission does not leave the device
+between the iterations: stage 2 leaves it transposed, ET[NFREQ][CELLS], and every launch makes its EMIT[CELLS] from one contiguous
+row (soc_set_emission_column); otherwise it goes through the host array and soc_set_emission, with the same bits.  Refused with
+iterations: `ali` (the escape probability feeds a temperature solve that this pipeline does not do), `reference` (the reference field
+needs the previous emission and its absorptions carried across the iterations) and a `remit` that cuts frequencies.
 """
 import sys
 import time
@@ -33,6 +44,7 @@ import numpy as np
 from . import a2e, files, mabu
 from .asoc import AbsorptionRun, UnsupportedOption
 from .ini import User
+from .lib import DoesNotFit
 
 # the stage-2 arithmetic lives in soc_amd.mabu (the program that runs it alone); the names stay importable from here
 from .mabu import (NE_EQ, dust_kind, eq_dust_table, planck_safe, relative_cross_sections, simple_name, solver_name,   # noqa: F401
@@ -42,7 +54,12 @@ from .mabu import (NE_EQ, dust_kind, eq_dust_table, planck_safe, relative_cross_
 class Pipeline:
     """soc.ini -> maps.  engine: soc_amd.lib.Engine (or an object with its methods); comm: soc_amd.dist.Comm"""
 
-    def __init__(self, ini, engine, comm=None, verbose=None):
+    def __init__(self, ini, engine, comm=None, verbose=None, emission_source=None):
+        """emission_source: None -- the re-emission iterations take the resident emission where they can (see iterate) -- or 'host' to
+        keep them on the host statements (tests, measurements)"""
+        if emission_source not in (None, 'host'):
+            raise ValueError("emission_source: None or 'host'")
+        self.emission_source = emission_source
         self.comm = comm
         self.rank = comm.rank if comm else 0
         self.world = comm.world if comm else 1
@@ -59,10 +76,17 @@ class Pipeline:
         self.want_maps = not U.NOMAP
         self.want_solve = True
         # what stage 2 needs, checked before any GPU work (the transfer run of a large model takes minutes): a solver file per
-        # stochastically heated dust -- soc_amd.a2e_pre writes them (ASOC_driver.py:196-228 calls A2E_pre.py there) -- and no dust
-        # re-emission iterations, which this in-memory pipeline does not do
+        # stochastically heated dust -- soc_amd.a2e_pre writes them (ASOC_driver.py:196-228 calls A2E_pre.py there) -- and, with dust
+        # re-emission iterations (`iterations N` with `cellpackets`), none of what the loop does not carry from one iteration to the next
         if U.ITERATIONS > 0 and U.CLPAC > 0:
-            raise UnsupportedOption("cellpackets (dust re-emission iterations) inside the pipeline: run soc_amd.asoc per iteration")
+            if U.WITH_ALI:
+                raise UnsupportedOption("ali with dust re-emission iterations (iterations with cellpackets) inside the pipeline: the escape "
+                                        "probability feeds a temperature solve, which the pipeline does not do (its emission comes from "
+                                        "the per-dust solvers)")
+            if int(U.WITH_REFERENCE) > 0:
+                raise UnsupportedOption("reference (the reference field) with dust re-emission iterations inside the pipeline: it needs the "
+                                        "previous emission and its absorptions, OEMITTED and OTABS, carried across the iterations; run "
+                                        "soc_amd.asoc per iteration")
         mabu.require_solvers(self.dusts, self.kinds)
         U.NOABSORBED, U.NOMAP, U.NOSOLVE = 0, 1, 1            # rt_simple.ini: absorptions per frequency, nomap, nosolve
         self.verbose = U.VERBOSE if verbose is None else verbose
@@ -75,11 +99,15 @@ class Pipeline:
             print(*a)
 
     # ---- stage 2 ----------------------------------------------------------------------------------------------
-    def solve_emission(self, FABSORBED, ABU):
+    def solve_emission(self, FABSORBED, ABU, keep_resident=False, download=True):
         """FABSORBED[CELLS, NFREQ] as the absorbed file holds it (scaled, files.scale_absorbed) -> EMITTED[CELLS, NFREQ]; with
-        `polarisation` lines self.R[CELLS, NFREQ] is the polarisation reduction factor"""
-        em, info = mabu.solve_emission(self.eng, self.dusts, self.kinds, FABSORBED, ABU, self.rank, self.world, log=self.log, pol=self.pol)
+        `polarisation` lines self.R[CELLS, NFREQ] is the polarisation reduction factor.  keep_resident, download: as
+        mabu.solve_emission; self.resident says whether the engine now holds this emission (then, with download=False, the arrays
+        returned are not filled)"""
+        em, info = mabu.solve_emission(self.eng, self.dusts, self.kinds, FABSORBED, ABU, self.rank, self.world, log=self.log, pol=self.pol,
+                                       keep_resident=keep_resident, download=download)
         self.timers["emission_path"] = info["path"]            # 'device' (soc_mabu_*) or 'host'
+        self.resident = info["resident"]
         self.R = info.get("R")
         if not (self.comm and self.world > 1):
             return em
@@ -96,6 +124,38 @@ class Pipeline:
             self.R = whole(self.R)
         return whole(em)
 
+    # ---- dust re-emission iterations ------------------------------------------------------------------------------------
+    def open_resident(self, NFREQ):
+        """The emission of an iteration can stay on the device for the next one's launches (engine.emitted_*: held transposed, a
+        frequency a contiguous row) where the engine has the calls, there is one rank (several: every rank solves its cells, and all
+        need all), `emweight 0` (the host draws the weights from the emission) and the array fits.  Reserves it; False: the host source."""
+        if self.emission_source == 'host' or not hasattr(self.eng, "emitted_begin") or self.world > 1 or self.U.USE_EMWEIGHT > 0:
+            return False
+        try:
+            self.eng.emitted_begin(NFREQ)
+        except DoesNotFit as err:
+            self.log("  %s" % err)
+            return False
+        return True
+
+    def iterate(self, rt, k, N, CONSTANT, EMITTED, ABU, want):
+        """Iteration k of N as a run of its own with `iterations 1`, `nosolve`, reading the emitted file of iteration k-1, and
+        soc_amd.mabu on the absorbed file it writes: the emission of k-1 is sent from the cells at every simulated frequency, its
+        absorptions join those of the constant sources, and the emission is solved from the sum.  The source of the launches is the
+        engine's resident copy where stage 2 left one (want, and the stage took the device path), else EMITTED on the host."""
+        t0 = time.time()
+        source = 'resident' if (want and self.resident) else 'host'
+        self.log("driver: iteration %d/%d takes the emission from the %s source" % (k, N, source))
+        FABSORBED = CONSTANT.copy() if k < N else CONSTANT
+        rt.simulate_cell_emission(EMITTED, FABSORBED, resident=source == 'resident')
+        files.scale_absorbed(FABSORBED, rt.cloud, self.U.GL, self.U.NNNLIMIT)
+        t1 = time.time()
+        # (an emission that stays on the device is read back only after the last iteration, for the products; where stage 2 does not
+        # leave it there -- its host path -- the array returned is filled whatever `download` says)
+        EMITTED = self.solve_emission(FABSORBED, ABU, keep_resident=want and k < N, download=k == N)
+        self.timers["iterations"].append(dict(transfer=t1 - t0, emission=time.time() - t1, source=source))
+        return FABSORBED, EMITTED
+
     # ---- the three stages -----------------------------------------------------------------------------------------
     def run(self, keep_files=False):
         U = self.U
@@ -103,17 +163,27 @@ class Pipeline:
         rt = AbsorptionRun(U, self.eng, self.comm, verbose=self.verbose)
         rt.write_packet_info()
         rt.setup_engine()
+        N = U.ITERATIONS if rt.CLPAC > 0 else 0                   # dust re-emission iterations
+        if N > 0:
+            rt.require_emission_at_every_frequency()               # (`remit` cutting frequencies, before minutes of transfer)
         CTABS, FABSORBED = rt.simulate_constant_sources()
-        if U.ITERATIONS > 0 and rt.CLPAC > 0:
-            raise UnsupportedOption("cellpackets (dust re-emission iterations) inside the pipeline: run soc_amd.asoc per iteration")
+        CONSTANT = FABSORBED.copy() if N > 0 else None             # the constant sources' absorptions, unscaled: every iteration adds to them
         files.scale_absorbed(FABSORBED, rt.cloud, U.GL, U.NNNLIMIT)
         self.timers["transfer"] = time.time() - t0
         # abundances: the columns of the transfer run (ASOC_aux.py read_abundances), ones where no file is given
         CELLS = rt.cloud.CELLS
         ABU = mabu.abundance_table(rt.ABU, U.SINGLE_ABU, CELLS, len(self.dusts))
         t0 = time.time()
-        EMITTED = self.solve_emission(FABSORBED, ABU)
-        self.timers["emission"] = time.time() - t0
+        want = N > 0 and self.open_resident(rt.NFREQ)
+        try:
+            EMITTED = self.solve_emission(FABSORBED, ABU, keep_resident=want, download=N == 0)
+            self.timers["emission"] = time.time() - t0
+            self.timers["iterations"] = []
+            for k in range(1, N + 1):
+                FABSORBED, EMITTED = self.iterate(rt, k, N, CONSTANT, EMITTED, ABU, want)
+        finally:
+            if want:
+                self.eng.emitted_end()
         if self.rank == 0:
             if len(U.file_emitted) > 0:
                 files.write_emitted(U.file_emitted, EMITTED)
@@ -132,7 +202,9 @@ class Pipeline:
             if self.R is not None:                                 # (all-sky polarisation maps are a product of this path with R only)
                 rt.write_healpix_polmaps(EMITTED, R=self.R)
         self.timers["maps"] = time.time() - t0
-        self.log("@@ driver: transfer %.2f s, emission %.2f s, maps %.2f s" % (self.timers["transfer"], self.timers["emission"], self.timers["maps"]))
+        self.log("@@ driver: transfer %.2f s, emission %.2f s, maps %.2f s" % (self.timers["transfer"], self.timers["emission"], self.timers["maps"])
+                 + "".join(";  iteration %d (%s): transfer %.2f s, emission %.2f s" % (k + 1, it["source"], it["transfer"], it["emission"])
+                           for k, it in enumerate(self.timers["iterations"])))
         return CTABS, FABSORBED, EMITTED
 
 

@@ -154,6 +154,13 @@ API = {
     "soc_mabu_accumulate_p": (C.c_int, [C.c_void_p, C.c_int]),
     "soc_mabu_ratio": (C.c_int, [C.c_void_p]),
     "soc_mabu_download_p": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
+    "soc_emitted_begin": (C.c_int, [C.c_void_p, C.c_int]),
+    "soc_emitted_upload": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
+    "soc_emitted_from_mabu": (C.c_int, [C.c_void_p, C.c_int64]),
+    "soc_emitted_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
+    "soc_set_emission_column": (C.c_int, [C.c_void_p, C.c_int, _F]),
+    "soc_read_emission": (C.c_int, [C.c_void_p, _F, C.c_int64]),
+    "soc_emitted_end": (C.c_int, [C.c_void_p]),
     "soc_library_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, _F, _F, _F, _F, _F, _F, _F, _F, C.c_int, _I]),
     "soc_library_solve": (C.c_int, [C.c_void_p, C.c_int64, _F, _F, _I, C.POINTER(C.c_int64)]),
     "soc_library_solve_resident": (C.c_int, [C.c_void_p, _I, _I, C.POINTER(C.c_int64)]),
@@ -184,7 +191,8 @@ class SocError(RuntimeError):
 
 
 class DoesNotFit(SocError):
-    """mabu_begin: the cells do not fit the free device memory; cells_fit of them would"""
+    """mabu_begin: the cells do not fit the free device memory; cells_fit of them would.  emitted_begin: the resident emission does
+    not fit (cells_fit 0: it is held for all cells or not at all)"""
 
     def __init__(self, text, cells_fit):
         SocError.__init__(self, text)
@@ -265,6 +273,7 @@ class Engine:
         self.NPAR = 0
         self.LEVELS = 0
         self._mabu = None                                  # (cells, NFREQ, NDUST) between mabu_begin and mabu_end
+        self._emitted = None                               # NFREQ between emitted_begin and emitted_end (set_grid ends it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -294,6 +303,7 @@ class Engine:
         self.CELLS = int(DENS.size)
         self.NPAR = self.CELLS - int(NX) * int(NY) * int(NZ)
         self.LEVELS = int(LEVELS)
+        self._emitted = None
 
     def set_cloud(self, cloud):
         self.set_grid(cloud.NX, cloud.NY, cloud.NZ, cloud.LEVELS, cloud.LCELLS, cloud.DENS)
@@ -1078,6 +1088,68 @@ class Engine:
     def mabu_end(self):
         self._chk(self.lib.soc_mabu_end(self.h))
         self._mabu = None
+
+    # ---- the emission of a re-emission iteration, resident for the next one's cell-emission launches (soc_emitted_*; driven by
+    # soc_amd.driver through mabu.solve_emission and AbsorptionRun.simulate_cell_emission) ----
+    def emitted_begin(self, NFREQ):
+        """ET[NFREQ, CELLS] of the grid's cells, zeroed; DoesNotFit where the free device memory does not take it (nothing is reserved)"""
+        if self.CELLS < 1:
+            raise SocError("emitted_begin: call set_grid first")
+        rc = self.lib.soc_emitted_begin(self.h, int(NFREQ))
+        if rc == -2:                                           # (an array that is open stays as it is)
+            raise DoesNotFit("%s (code %d)" % (self.lib.soc_last_error(self.h).decode(), rc), 0)
+        self._chk(rc)
+        self._emitted = int(NFREQ)
+
+    def _emitted_rows(self, who, n, rows):
+        """the open emitted_begin's NFREQ; rows, where given, must be a C-contiguous float32 [n, NFREQ] (a refused call must not read or
+        write past a host array; the device side checks the cell range)"""
+        if self._emitted is None:
+            raise SocError("%s: call emitted_begin first" % who)
+        if rows is not None and not (isinstance(rows, np.ndarray) and rows.dtype == np.float32 and rows.flags.c_contiguous
+                                     and rows.shape == (int(n), self._emitted)):
+            raise SocError("%s: a C-contiguous float32 array of shape (%d, %d) is needed" % (who, int(n), self._emitted))
+        return self._emitted
+
+    def emitted_upload(self, c0, rows):
+        """rows[n, NFREQ] as the emitted file holds them -> cells [c0, c0 + n)"""
+        rows = np.ascontiguousarray(rows, np.float32)
+        self._emitted_rows("emitted_upload", rows.shape[0], rows)
+        self._chk(self.lib.soc_emitted_upload(self.h, int(c0), rows.shape[0], _f(rows)))
+
+    def emitted_from_mabu(self, c0):
+        """the sum of the open mabu_begin, device to device -> cells [c0, c0 + its cells)"""
+        self._emitted_rows("emitted_from_mabu", 0, None)
+        self._chk(self.lib.soc_emitted_from_mabu(self.h, int(c0)))
+
+    def emitted_download(self, c0, n, out=None):
+        """rows [c0, c0 + n) back as [n, NFREQ]; out: a writeable C-contiguous float32 array of that shape to fill"""
+        NFREQ = self._emitted_rows("emitted_download", n, out)
+        if out is None:
+            out = np.zeros((int(n), NFREQ), np.float32)
+        elif not out.flags.writeable:
+            raise SocError("emitted_download: out must be writeable")
+        self._chk(self.lib.soc_emitted_download(self.h, int(c0), int(n), _f(out)))
+        return out
+
+    def set_emission_column(self, ifreq, COEFF):
+        """the emission of the next sim_cl from frequency ifreq of the resident array: EMIT = ET[ifreq] * (COEFF[level] * DENS), 0 in
+        links and empty cells; COEFF[LEVELS] float32 = GL*PARSEC/8**level/FACTOR"""
+        self._emitted_rows("set_emission_column", 0, None)
+        COEFF = np.ascontiguousarray(COEFF, np.float32)
+        if COEFF.size != self.LEVELS:
+            raise SocError("set_emission_column: COEFF must hold LEVELS = %d floats" % self.LEVELS)
+        self._chk(self.lib.soc_set_emission_column(self.h, int(ifreq), _f(COEFF)))
+
+    def read_emission(self):
+        """EMIT[CELLS] as the next sim_cl would use it (tests)"""
+        out = np.zeros(self.CELLS, np.float32)
+        self._chk(self.lib.soc_read_emission(self.h, _f(out), self.CELLS))
+        return out
+
+    def emitted_end(self):
+        self._chk(self.lib.soc_emitted_end(self.h))
+        self._emitted = None
 
     # ---- the library method for dust emission (soc_library_*; driven by soc_amd.library) ----
     LIBRARY_TABLES = ("I1", "dI1", "I2", "dI2", "X", "Y", "Z")

@@ -288,10 +288,12 @@ def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, lo
     return 1
 
 
-def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells, log, AALG=None, ptabs=None, R=None):
+def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells, log, AALG=None, ptabs=None, R=None, resident_c0=None,
+                  download=True):
     """the cells in ranges that fit the device (one range where all do): cells are independent, so this is a loop.  With AALG (per
     dust the minimum aligned sizes of these cells, or None) the two more resident arrays of the polarised emission are asked for,
-    the rows of a dust's aalg follow the cell range, and R receives polarised / total."""
+    the rows of a dust's aalg follow the cell range, and R receives polarised / total.  resident_c0 (the model's cell of row 0): the
+    sum of every range also goes, device to device, to the engine's resident emission (emitted_begin); download=False: nowhere else."""
     n, NFREQ = FABS.shape
     NDUST = len(dusts)
 
@@ -341,7 +343,9 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
                     engine.mabu_accumulate_p(idust)                                # A2E_MABU.py:1139-1147
             if AALG:
                 engine.mabu_ratio()                                                # A2E_MABU.py:1182
-            for i in range(a, b, CHUNK):
+            if resident_c0 is not None:
+                engine.emitted_from_mabu(resident_c0 + a)
+            for i in range(a, b, CHUNK) if download else ():
                 m = min(i + CHUNK, b) - i
                 engine.mabu_download(i - a, m, out=EM[i:i + m])
                 if AALG:
@@ -354,13 +358,17 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
     return ranges
 
 
-def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, path=None, range_cells=None, log=None, pol=None):
+def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, path=None, range_cells=None, log=None, pol=None,
+                   keep_resident=False, download=True):
     """Stage 2 of a multi-dust run for the cells a2e.cell_range(CELLS, rank, world) of this rank.  FABSORBED[CELLS, NFREQ] as the
     absorbed file holds it (scaled, files.scale_absorbed; a memory map will do), ABU[CELLS, NDUST] float32.
     Returns (EM[c1 - c0, NFREQ], info) with info["path"] 'device' or 'host' and info["ranges"], the number of cell ranges.
     path: None = the device path where the engine offers it, or 'device' / 'host' to insist (tests, measurements);
     range_cells: an upper limit for the cells resident at a time (default: what the free device memory takes);
-    pol: polarisation_lines' list -- per dust its aalg file or None; info["R"] is then R[c1 - c0, NFREQ], polarised / total."""
+    pol: polarisation_lines' list -- per dust its aalg file or None; info["R"] is then R[c1 - c0, NFREQ], polarised / total;
+    keep_resident: on the device path the sum also goes to the engine's resident emission (engine.emitted_begin was called: the
+    cell-emission launches of a re-emission iteration take it from there) -- info["resident"] says whether it did; download=False:
+    where it did, the sum is not read back (EM, and R, stay zero: an intermediate iteration needs neither on the host)."""
     log = log or (lambda *a: None)
     CELLS, NFREQ = FABSORBED.shape
     RABS, FREQ = relative_cross_sections(dusts, kinds)
@@ -379,13 +387,15 @@ def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, pat
     EM = np.zeros((c1 - c0, NFREQ), np.float32)
     R = np.zeros((c1 - c0, NFREQ), np.float32) if AALG else None
     ranges = 0
+    resident = bool(keep_resident) and device and c1 > c0
     if c1 > c0 and device:
-        ranges = _solve_device(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, EM, range_cells, log, AALG, ptabs, R)
+        ranges = _solve_device(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, EM, range_cells, log, AALG, ptabs, R,
+                               resident_c0=c0 if resident else None, download=download or not resident)
     elif c1 > c0:
         ranges = _solve_host(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, c0, CELLS, EM, log, AALG, ptabs, R)
         if AALG:
             R[:] = reduction_factor(R, EM)                         # (R held the sum of the polarised emission)
-    info = dict(path='device' if device else 'host', ranges=ranges)
+    info = dict(path='device' if device else 'host', ranges=ranges, resident=resident)
     if AALG:
         info["R"] = R
     return EM, info
