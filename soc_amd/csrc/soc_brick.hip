@@ -235,12 +235,42 @@ __device__ __forceinline__ uint32_t soc_qh_place(const int *sH, int HS, uint32_t
 
 // ---------------------------------------------------------------------------------------
 
-__device__ __forceinline__ void soc_cell_brick(const SocBrickArgs &A, float px, float py, float pz, int &brick, int &lid)
+// Cartesian grids: bricks are cubes of 1 << LB root cells; brick and tally slot of root cell (ix, iy, iz)
+__device__ __forceinline__ void soc_root_brick(const SocBrickArgs &A, const int ix, const int iy, const int iz, int &brick, int &lid)
 {
-    const int ix = (int)soc_floorf(px), iy = (int)soc_floorf(py), iz = (int)soc_floorf(pz);
     const int M = (1 << A.LB) - 1;
     brick = ((iz >> A.LB) * A.NBY + (iy >> A.LB)) * A.NBX + (ix >> A.LB);
     lid   = ((iz & M) << (2 * A.LB)) | ((iy & M) << A.LB) | (ix & M);
+}
+
+// Brick and tally slot of cell (level, ind) for the two forms whose packets carry a slot.  Hierarchies in global memory: both are
+// in the cell's DS entry (oind = OFF[level] + ind).  Cartesian grids: from the root cell's index.
+template <bool OCT>
+__device__ __forceinline__ void soc_cell_brick(const SocGrid &G, const SocBrickArgs &A, const int oind, const int ind, int &brick, int &lid)
+{
+    if (OCT) {
+        const uint32_t si = __float_as_uint(A.DS[oind].y);
+        brick = (int)(si >> SOC_SLOT_BITS);
+        lid   = (int)(si & SOC_SLOT_MASK);
+    } else {
+        soc_root_brick(A, ind % G.NX, (ind / G.NX) % G.NY, ind / (G.NX * G.NY), brick, lid);
+    }
+}
+
+// The same for a packet that IndexG has just placed: on Cartesian grids its position floors to its root cell, which takes fewer
+// instructions and registers than the index does
+template <bool OCT>
+__device__ __forceinline__ void soc_cell_brick(const SocGrid &G, const SocBrickArgs &A, const int oind, const float px, const float py,
+                                               const float pz, int &brick, int &lid)
+{
+    if (OCT) soc_cell_brick<true>(G, A, oind, 0, brick, lid);
+    else     soc_root_brick(A, (int)soc_floorf(px), (int)soc_floorf(py), (int)soc_floorf(pz), brick, lid);
+}
+
+// Brick-local hierarchies: the brick of the root cell above cell (ccx, ccy, ccz) of `level`
+__device__ __forceinline__ int soc_lt_queue(const SocGrid &G, const SocBrickArgs &A, const int level, const int ccx, const int ccy, const int ccz)
+{
+    return A.rbrick[((ccz >> level) * G.NY + (ccy >> level)) * G.NX + (ccx >> level)];
 }
 
 // minimal walker interface for soc_pb_create()
@@ -258,10 +288,7 @@ struct SocBrickLane {
     }
     __device__ __forceinline__ void begin(const SocSim &S)
     {
-        if (soc_fabsf(ux) < SOC_DEPS) ux = SOC_DEPS;
-        if (soc_fabsf(uy) < SOC_DEPS) uy = SOC_DEPS;
-        if (soc_fabsf(uz) < SOC_DEPS) uz = SOC_DEPS;
-        soc_normalize(ux, uy, uz);
+        soc_condition_direction(ux, uy, uz);
         scat = 0;
         tau  = 0.0f;
         free_path = soc_draw_free_path(S, &rng, photons);
@@ -1358,7 +1385,7 @@ __device__ __forceinline__ void soc_brick_events(const SocGrid &G, const SocSimP
             // the walk saw the packet step into the region of interest: its place in the record (kernel_ASOC.c:615-642, :1510-1535), then on
             // with the walk in the brick of its cell
             soc_roi_save(G, sOFF, *S.ROI, w.px, w.py, w.pz, w.ux, w.uy, w.uz, w.level, w.ind, w.photons);
-            key = qbase + A.rbrick[((ccz >> w.level) * G.NY + (ccy >> w.level)) * G.NX + (ccx >> w.level)];
+            key = qbase + soc_lt_queue(G, A, w.level, ccx, ccy, ccz);
         } else
         if (LT && (evk == 2)) {
             // slow step: Index() itself, in double (FLT: in float), for a step that exact geometry does not decide (soc_ltree.h).
@@ -1376,13 +1403,13 @@ __device__ __forceinline__ void soc_brick_events(const SocGrid &G, const SocSimP
                 create = true;                                                  // left the model: the work item's next packet
             } else {
                 soc_cell_coords(G, sOFF, w.level, w.ind, ccx, ccy, ccz);
-                key = qbase + A.rbrick[((ccz >> w.level) * G.NY + (ccy >> w.level)) * G.NX + (ccx >> w.level)];
+                key = qbase + soc_lt_queue(G, A, w.level, ccx, ccy, ccz);
             }
         } else
         if (mirrored) {
             create = false;
             soc_cell_coords(G, sOFF, w.level, w.ind, ccx, ccy, ccz);
-            key = qbase + A.rbrick[((ccz >> w.level) * G.NY + (ccy >> w.level)) * G.NX + (ccx >> w.level)];
+            key = qbase + soc_lt_queue(G, A, w.level, ccx, ccy, ccz);
         } else
         if (!create) {
             // scattering block (kernel_ASOC.c:700-804); the packet is at the start of the step
@@ -1420,17 +1447,10 @@ __device__ __forceinline__ void soc_brick_events(const SocGrid &G, const SocSimP
             w.tau = 0.0f;
             if (!CL && (w.scat > 20)) { w.ind = -1;  create = true; }         // dropped after 20 scatterings
             if (LT) {                                                        // back to the brick of its cell
-                key = qbase + A.rbrick[((ccz >> w.level) * G.NY + (ccy >> w.level)) * G.NX + (ccx >> w.level)];
+                key = qbase + soc_lt_queue(G, A, w.level, ccx, ccy, ccz);
             } else
             if (CL) {                                                        // back to the brick of its cell (D.w holds the emitting cell)
-                if (OCT) {
-                    const uint32_t si = __float_as_uint(A.DS[oind].y);
-                    key = (int)(si >> SOC_SLOT_BITS);  lid = (int)(si & SOC_SLOT_MASK);
-                } else {
-                    const int M = (1 << A.LB) - 1, ix = w.ind % G.NX, iy = (w.ind / G.NX) % G.NY, iz = w.ind / (G.NX * G.NY);
-                    key = ((iz >> A.LB) * A.NBY + (iy >> A.LB)) * A.NBX + (ix >> A.LB);
-                    lid = ((iz & M) << (2 * A.LB)) | ((iy & M) << A.LB) | (ix & M);
-                }
+                soc_cell_brick<OCT>(G, A, oind, w.ind, key, lid);
                 key += qbase;
             }
             }
@@ -1506,15 +1526,9 @@ __device__ __forceinline__ void soc_brick_events(const SocGrid &G, const SocSimP
                 w.begin(S);
                 if (LT) {
                     soc_cell_coords(G, sOFF, level, ind, ccx, ccy, ccz);
-                    key = A.rbrick[((ccz >> level) * G.NY + (ccy >> level)) * G.NX + (ccx >> level)];
-                } else
-                if (OCT) {
-                    const uint32_t si = __float_as_uint(A.DS[oabs].y);
-                    key = (int)(si >> SOC_SLOT_BITS);  lid = (int)(si & SOC_SLOT_MASK);
+                    key = soc_lt_queue(G, A, level, ccx, ccy, ccz);
                 } else {
-                    const int M = (1 << A.LB) - 1, ix = ind % G.NX, iy = (ind / G.NX) % G.NY, iz = ind / (G.NX * G.NY);
-                    key = ((iz >> A.LB) * A.NBY + (iy >> A.LB)) * A.NBX + (ix >> A.LB);
-                    lid = ((iz & M) << (2 * A.LB)) | ((iy & M) << A.LB) | (ix & M);
+                    soc_cell_brick<OCT>(G, A, oabs, ind, key, lid);
                 }
                 key += qbase;
             }
@@ -1548,13 +1562,9 @@ __device__ __forceinline__ void soc_brick_events(const SocGrid &G, const SocSimP
                 if (w.ind >= 0) {
                     if (LT) {
                         soc_cell_coords(G, sOFF, w.level, w.ind, ccx, ccy, ccz);
-                        key = A.rbrick[((ccz >> w.level) * G.NY + (ccy >> w.level)) * G.NX + (ccx >> w.level)];
-                    } else
-                    if (OCT) {
-                        const uint32_t si = __float_as_uint(A.DS[sOFF[w.level] + w.ind].y);
-                        key = (int)(si >> SOC_SLOT_BITS);  lid = (int)(si & SOC_SLOT_MASK);
+                        key = soc_lt_queue(G, A, w.level, ccx, ccy, ccz);
                     } else {
-                        soc_cell_brick(A, w.px, w.py, w.pz, key, lid);
+                        soc_cell_brick<OCT>(G, A, (OCT ? sOFF[w.level] : 0) + w.ind, w.px, w.py, w.pz, key, lid);
                     }
                     key += qbase;
                     break;
@@ -1884,36 +1894,15 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
             if (mode == SOC_RE_PEEL_END) {
                 if (idir >= 0) {
                     const float taup = tau;
-                    const float CL = CLW ? 0.9999f : 0.999f;
-                    const float cos_theta = soc_clampf(dx_ * w.ux + dy_ * w.uy + dz_ * w.uz, -CL, +CL);
-                    float delta;
-                    if (CLW) {
-                        const float g = 0.65f;
-                        const float fraction = (1.0f / (4.0f * SOC_PI)) * (1.0f - g * g) / soc_pow15f(1.0f + g * g - 2.0f * g * cos_theta);
-                        delta = w.photons * fraction * ((taup > SOC_TAULIM) ? (1.0f - soc_expf(-taup)) : (taup * (1.0f - 0.5f * taup)));
-                    } else {
-                        int b = (int)(S.BINS * (1.0f + cos_theta) * 0.5f);
-                        b = b < 0 ? 0 : (b > S.BINS - 1 ? S.BINS - 1 : b);
-                        delta = w.photons * soc_expf(-taup) * S.DSC[b];
-                    }
+                    float delta = soc_peel_delta(CLW, w.photons, taup, dx_, dy_, dz_, w.ux, w.uy, w.uz, S.DSC, S.BINS);
                     if (HPX) {
-                        // 1/d^2 and the pixel of the direction towards the observer (:352-360)
                         delta = invd2 * delta;
-                        const float theta = soc_acosf(-w.uz);
-                        const float phi   = soc_atan2f(w.uy, w.ux);
-                        const int pix = soc_angles2pixel_ring(-V.NDIR, phi, theta);
+                        const int pix = soc_sca_healpix_pixel(V, w.ux, w.uy, w.uz);
                         if (pix >= 0) soc_tally(S.OUT, pix, delta);
                         n_add++;
                     } else {
-                        const float qx = w.px - V.CX, qy = w.py - V.CY, qz = w.pz - V.CZ;
-                        const float4 ra = V.ORA[idir], de = V.ODE[idir];
-                        int i = (int)((0.5f * V.NPIX_X - 0.00005f) + (qx * ra.x + qy * ra.y + qz * ra.z) / V.MAP_DX);
-                        int jj = (int)((0.5f * V.NPIX_Y - 0.00005f) + (qx * de.x + qy * de.y + qz * de.z) / V.MAP_DX);
-                        if ((i >= 0) && (jj >= 0) && (i < V.NPIX_X) && (jj < V.NPIX_Y)) {
-                            i += idir * V.NPIX_X * V.NPIX_Y + jj * V.NPIX_X;
-                            soc_tally(S.OUT, i, delta);
-                            n_add++;
-                        }
+                        const int pix = soc_sca_pixel(V, idir, w.px, w.py, w.pz);
+                        if (pix >= 0) { soc_tally(S.OUT, pix, delta);  n_add++; }
                     }
                     idir++;
                 }
@@ -1941,17 +1930,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                     inside = false;
                     if (CLW) alive = false;                   // no random number drawn
                 }
-                if (alive) {
-                    float W;
-                    if (KIND == SOC_SCA_PS) {
-                        W = -soc_expm1f(-tau);
-                        free_path = -soc_logf(1.0f - W * soc_rand(&w.rng));
-                    } else {
-                        W = 1.0f - soc_expf(-tau);
-                        free_path = -(float)soc_logd(1.0 - (double)(W * soc_rand(&w.rng)));
-                    }
-                    w.photons *= W;
-                }
+                if (alive) free_path = soc_ffs_free_path(KIND == SOC_SCA_PS, tau, &w.rng, w.photons);
                 tau  = 0.0f;
                 scat = 0;
                 w.ind = inside ? 0 : -1;
@@ -1963,71 +1942,20 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                 rmode = SOC_RM_NONE;
                 if (KIND == SOC_SCA_CL) {
                     // :1158-1222; the work item's place is kept in the record: D.w = cell, III = packets sent from it
-                    int ICELL = (int)cl_cell, IRAY = III, batch = -1;
+                    long long ICELL = (int)cl_cell;
+                    int   IRAY = III, batch = -1;
                     float PWEI = 1.0f;
-                    if (ICELL >= 0) {
-                        if (S.USE_EMWEIGHT > 0) {
-                            PWEI  = S.EMWEI[ICELL];
-                            batch = (int)soc_floorf(PWEI);
-                            if (batch < 1) { batch = 1;  PWEI = (float)(1.0 / (double)(PWEI + 1.0e-30f)); }
-                            else           { PWEI = (float)(1.0 / (double)((float)batch + 1.0e-9f)); }
-                        } else {
-                            batch = S.BATCH;
-                            PWEI  = 1.0f / ((float)batch + 1.0e-9f);
-                        }
-                    }
+                    if (ICELL >= 0) soc_cl_packets(S, (S.USE_EMWEIGHT > 0) ? S.EMWEI[ICELL] : 0.0f, batch, PWEI);
                     bool more = true;
                     if (IRAY >= batch) {
                         IRAY = 0;
-                        PWEI = 1.0f;
-                        long long IC = ICELL;
-                        while (true) {
-                            IC += S.GLOBAL;
-                            if (IC >= G.CELLS) { more = false; break; }
-                            if (S.USE_EMWEIGHT > 0) {
-                                PWEI = S.EMWEI[IC];
-                                if ((PWEI < 1e-10f) || (G.DENS[IC] <= 0.0f)) continue;
-                                batch = (int)soc_floorf(PWEI);
-                                if (batch < 1) { batch = 1;  PWEI = (float)(1.0 / (double)(PWEI + 1.0e-30f)); }
-                                else           { PWEI = (float)(1.0 / (double)((float)batch + 1.0e-9f)); }
-                            } else {
-                                batch = S.BATCH;
-                                PWEI  = 1.0f / ((float)batch + 1.0e-9f);
-                            }
-                            break;
-                        }
-                        ICELL = (int)IC;
+                        more = soc_cl_next_cell(G, S, ICELL, batch, PWEI);
                     }
                     if (!more) {
                         mode = SOC_RE_DONE;
                     } else {
-                        int ind = ICELL, level;
                         IRAY += 1;
-                        for (level = 0; level < G.LEVELS - 1; level++) {
-                            if (ind < sOFF[level + 1] - sOFF[level]) break;
-                            ind -= sOFF[level + 1] - sOFF[level];
-                        }
-                        float X0, Y0, Z0;
-                        if (level == 0) {
-                            X0 = (float)(ind % G.NX);  Y0 = (float)((ind / G.NX) % G.NY);  Z0 = (float)(ind / (G.NX * G.NY));
-                        } else {
-                            const int sid = ind % 8;
-                            X0 = (float)(sid % 2);  Y0 = ((sid % 4) > 1) ? 1.0f : 0.0f;  Z0 = (float)(sid / 4);
-                        }
-                        w.level = level;  w.ind = ind;
-                        w.dens = G.DENS[sOFF[level] + ind];
-                        w.photons = S.EMIT[sOFF[level] + ind] * PWEI;
-                        w.px = X0 + soc_rand(&w.rng);
-                        w.py = Y0 + soc_rand(&w.rng);
-                        w.pz = Z0 + soc_rand(&w.rng);
-                        const float phi       = SOC_TWOPI * soc_rand(&w.rng);
-                        const float cos_theta = 0.999997f - 1.999995f * soc_rand(&w.rng);
-                        const float sin_theta = soc_sqrtf(1.0f - cos_theta * cos_theta);
-                        float sp, cp;
-                        soc_sincosf(phi, &sp, &cp);
-                        w.ux = sin_theta * cp;
-                        w.uy = sin_theta * sp;
-                        w.uz = cos_theta;
+                        (void)soc_cl_emit<true>(G, S, sOFF, (int)ICELL, PWEI, w);
                         have = true;
                     }
                     III = IRAY;
@@ -2053,10 +1981,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
                 if (have) {
                     if (!HPSKY || (KIND != SOC_SCA_HP)) {     // SimRAM_HP has conditioned the direction itself
                         n_pkt++;
-                        if (soc_fabsf(w.ux) < SOC_DEPS) w.ux = SOC_DEPS;
-                        if (soc_fabsf(w.uy) < SOC_DEPS) w.uy = SOC_DEPS;
-                        if (soc_fabsf(w.uz) < SOC_DEPS) w.uz = SOC_DEPS;
-                        soc_normalize(w.ux, w.uy, w.uz);
+                        soc_condition_direction(w.ux, w.uy, w.uz);
                     }
                     tau  = 0.0f;
                     scat = 0;
@@ -2078,7 +2003,7 @@ __device__ __forceinline__ void soc_sca_events(const SocGrid &G, const SocSimPac
         SocPk2 o, r;
         if (mode != SOC_RE_DONE) {
             if (!cc_ok) soc_cell_coords(SocGridHere<FLT>::get(G), sOFF, w.level, w.ind, ccx, ccy, ccz);
-            key = qbase + A.rbrick[((ccz >> w.level) * G.NY + (ccy >> w.level)) * G.NX + (ccx >> w.level)];
+            key = qbase + soc_lt_queue(G, A, w.level, ccx, ccy, ccz);
             rmode = mode;
         }
         const float kk = (mode == SOC_RM_PEEL) ? (kabs + ksca) : ksca;

@@ -33,8 +33,7 @@ __global__ __launch_bounds__(256) void soc_sim_pb_kernel(const SocGrid G, const 
     extern __shared__ float lds[];
     float *sCSC = lds;
     int   *sOFF = (int *)(lds + S.BINS);
-    int   *sLC  = sOFF + SOC_MAXL;
-    soc_stage_lds(G, S, sCSC, sOFF, sLC);
+    soc_stage_lds(G, S, sCSC, sOFF);
 
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= S.gid_count) return;
@@ -155,8 +154,7 @@ __global__ __launch_bounds__(256) void soc_sim_hp_kernel(const SocGrid G, const 
     extern __shared__ float lds[];
     float *sCSC = lds;
     int   *sOFF = (int *)(lds + S.BINS);
-    int   *sLC  = sOFF + SOC_MAXL;
-    soc_stage_lds(G, S, sCSC, sOFF, sLC);
+    soc_stage_lds(G, S, sCSC, sOFF);
 
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= S.gid_count) return;
@@ -212,14 +210,12 @@ __global__ __launch_bounds__(256) void soc_sim_cl_kernel(const SocGrid G, const 
     extern __shared__ float lds[];
     float *sCSC = lds;
     int   *sOFF = (int *)(lds + S.BINS);
-    int   *sLC  = sOFF + SOC_MAXL;
-    soc_stage_lds(G, S, sCSC, sOFF, sLC);
+    soc_stage_lds(G, S, sCSC, sOFF);
 
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= S.gid_count) return;
     const int id = (int)(S.gid0 + t);
     if (id >= G.CELLS) return;
-    const int NX = G.NX, NY = G.NY;
 
     SocWalker<OCT, DBL, ABU, WINT> w;
     w.rng = soc_seed_stream(S.seed_mul, S.seed_tab, (uint32_t)id);
@@ -251,67 +247,13 @@ __global__ __launch_bounds__(256) void soc_sim_cl_kernel(const SocGrid G, const 
                         if (e < 0) { mode = SOC_M_DONE; break; }
                         if (e > 0) { ICELL = e;  PWEI = S.EMWEI[e];  break; }
                     }
-                } else if (IRAY >= batch) {                // next emitting cell (kernel_ASOC.c:1318-1355)
+                } else if (IRAY >= batch) {
                     IRAY = 0;
-                    PWEI = 1.0f;
-                    while (true) {
-                        ICELL += S.GLOBAL;
-                        if (ICELL >= G.CELLS) { mode = SOC_M_DONE; break; }
-                        if (S.USE_EMWEIGHT > 0) {
-                            PWEI = S.EMWEI[ICELL];
-                            if ((PWEI < 1e-10f) || (G.DENS[ICELL] <= 0.0f)) continue;
-                            batch = (int)soc_floorf(PWEI);
-                            if (batch < 1) {
-                                batch = 1;
-                                PWEI  = (float)(1.0 / (double)(PWEI + 1.0e-30f));
-                            } else {
-                                PWEI = (float)(1.0 / (double)(batch + 1.0e-9f));
-                            }
-                        } else {
-                            batch = S.BATCH;
-                            PWEI  = 1.0f / (batch + 1.0e-9f);
-                        }
-                        break;
-                    }
+                    if (!soc_cl_next_cell(G, S, ICELL, batch, PWEI)) mode = SOC_M_DONE;
                 }
                 if (mode != SOC_M_DONE) {
-                    int ind = (int)ICELL;
                     IRAY += 1;
-                    int level;
-                    for (level = 0; level < G.LEVELS - 1; level++) {
-                        ind -= sLC[level];
-                        if (ind < 0) {
-                            ind += sLC[level];
-                            break;
-                        }
-                    }
-                    float X0, Y0, Z0;
-                    if (level == 0) {
-                        X0 = (ind % NX);
-                        Y0 = ((ind / NX) % NY);
-                        Z0 = (ind / (NX * NY));
-                    } else {
-                        int sid = ind % 8;
-                        X0 = (sid % 2);
-                        Y0 = ((sid % 4) > 1) ? 1.0f : 0.0f;
-                        Z0 = (sid / 4);
-                    }
-                    w.level   = level;
-                    w.ind     = ind;
-                    w.e_index = sOFF[level] + ind;
-                    w.dens    = G.DENS[sOFF[level] + ind];
-                    w.photons = S.EMIT[sOFF[level] + ind] * PWEI;
-                    w.px = X0 + soc_rand(&w.rng);
-                    w.py = Y0 + soc_rand(&w.rng);
-                    w.pz = Z0 + soc_rand(&w.rng);
-                    float phi       = SOC_TWOPI * soc_rand(&w.rng);
-                    float cos_theta = 0.999997f - 1.999995f * soc_rand(&w.rng);
-                    float sin_theta = soc_sqrtf(1.0f - cos_theta * cos_theta);
-                    float sp, cp;
-                    soc_sincosf(phi, &sp, &cp);
-                    w.ux = sin_theta * cp;
-                    w.uy = sin_theta * sp;
-                    w.uz = cos_theta;
+                    w.e_index = soc_cl_emit<OCT>(G, S, sOFF, (int)ICELL, PWEI, w);
                     n_pkt++;
                     w.begin(S);
                     if (w.roi_on) w.roi = soc_inroi(G, sOFF, *S.ROI, w.level, w.ind);       // kernel_ASOC.c:1439
@@ -424,7 +366,7 @@ __global__ void soc_trace_kernel(const SocGrid G, const float *pos, const float 
 // launch wrappers
 // ------------------------------------------------------------------------------------
 
-static inline size_t soc_lds_bytes(const SocSim &S) { return (size_t)S.BINS * 4 + 2 * SOC_MAXL * 4; }
+static inline size_t soc_lds_bytes(const SocSim &S) { return (size_t)S.BINS * 4 + SOC_MAXL * 4; }
 
 static inline void soc_launch_shape(uint32_t count, dim3 &grid, dim3 &block)
 {

@@ -44,14 +44,12 @@ __global__ __launch_bounds__(256) void soc_sca_kernel(const SocGrid G, const Soc
     float *sCSC = lds;
     float *sDSC = lds + S.BINS;
     int   *sOFF = (int *)(sDSC + S.BINS);
-    int   *sLC  = sOFF + SOC_MAXL;
     for (int i = threadIdx.x; i < S.BINS; i += blockDim.x) sDSC[i] = V.DSC[i];
-    soc_stage_lds(G, S, sCSC, sOFF, sLC);
+    soc_stage_lds(G, S, sCSC, sOFF);
 
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= S.gid_count) return;
     const int id = (int)(S.gid0 + t);
-    const int NX = G.NX, NY = G.NY;
     const int AREA = 2 * (G.NX * G.NY + G.NY * G.NZ + G.NZ * G.NX);
     if (KIND == SOC_SCA_PB) { if ((S.SOURCE == 1) && (id >= 8 * AREA)) return; }
     if (KIND == SOC_SCA_CL) { if (id >= G.CELLS) return; }
@@ -128,38 +126,18 @@ __global__ __launch_bounds__(256) void soc_sca_kernel(const SocGrid G, const Soc
             // ---- a peel-off ray has reached the surface: image contribution, next observer or deflection
             if (mode == SCA_M_PEEL_END) {
                 if (idir >= 0) {
-                    const float CL = CLW ? 0.9999f : 0.999f;
-                    const float cos_theta = soc_clampf(dx_ * w.ux + dy_ * w.uy + dz_ * w.uz, -CL, +CL);
                     // -D WITH_MSF: one species per peel-off, its DSC row (kernel_ASOC_sca.c:339-347, :382-390; SimRAM_CL draws too)
                     const int idust = (S.NDUST > 1) ? soc_msf_dust(S, &w.rng, sOFF[mlevel] + mind) : 0;
-                    float delta;
-                    if (CLW) {
-                        const float g = 0.65f;
-                        const float fraction = (1.0f / (4.0f * SOC_PI)) * (1.0f - g * g) / soc_pow15f(1.0f + g * g - 2.0f * g * cos_theta);
-                        delta = w.photons * fraction * ((taup > SOC_TAULIM) ? (1.0f - soc_expf(-taup)) : (taup * (1.0f - 0.5f * taup)));
-                    } else {
-                        int b = (int)(S.BINS * (1.0f + cos_theta) * 0.5f);
-                        b = b < 0 ? 0 : (b > S.BINS - 1 ? S.BINS - 1 : b);
-                        delta = w.photons * soc_expf(-taup) * ((S.NDUST > 1) ? V.DSC[(long)idust * S.BINS + b] : sDSC[b]);
-                    }
+                    float delta = soc_peel_delta(CLW, w.photons, taup, dx_, dy_, dz_, w.ux, w.uy, w.uz,
+                                                 (S.NDUST > 1) ? V.DSC + (long)idust * S.BINS : sDSC, S.BINS);
                     if (HPX) {
-                        // 1/d^2 and the pixel of the direction towards the observer (:352-360)
                         delta = invd2 * delta;
-                        const float theta = soc_acosf(-w.uz);
-                        const float phi   = soc_atan2f(w.uy, w.ux);
-                        const int pix = soc_angles2pixel_ring(-V.NDIR, phi, theta);
+                        const int pix = soc_sca_healpix_pixel(V, w.ux, w.uy, w.uz);
                         if (pix >= 0) soc_tally(V.OUT, pix, delta);
                         n_add++;
                     } else {
-                        const float qx = w.px - V.CX, qy = w.py - V.CY, qz = w.pz - V.CZ;
-                        const float4 ra = V.ORA[idir], de = V.ODE[idir];
-                        int i = (int)((0.5f * V.NPIX_X - 0.00005f) + (qx * ra.x + qy * ra.y + qz * ra.z) / V.MAP_DX);
-                        int j = (int)((0.5f * V.NPIX_Y - 0.00005f) + (qx * de.x + qy * de.y + qz * de.z) / V.MAP_DX);
-                        if ((i >= 0) && (j >= 0) && (i < V.NPIX_X) && (j < V.NPIX_Y)) {
-                            i += idir * V.NPIX_X * V.NPIX_Y + j * V.NPIX_X;
-                            soc_tally(V.OUT, i, delta);
-                            n_add++;
-                        }
+                        const int pix = soc_sca_pixel(V, idir, w.px, w.py, w.pz);
+                        if (pix >= 0) { soc_tally(V.OUT, pix, delta);  n_add++; }
                     }
                     idir++;
                 }
@@ -193,17 +171,7 @@ __global__ __launch_bounds__(256) void soc_sca_kernel(const SocGrid G, const Soc
                     w.ind = -1;
                     if (CLW) alive = false;                            // no random number drawn
                 }
-                if (alive) {
-                    float W;
-                    if (KIND == SOC_SCA_PS) {
-                        W = -soc_expm1f(-tau);
-                        free_path = -soc_logf(1.0f - W * soc_rand(&w.rng));
-                    } else {
-                        W = 1.0f - soc_expf(-tau);
-                        free_path = -(float)soc_logd(1.0 - (double)(W * soc_rand(&w.rng)));
-                    }
-                    w.photons *= W;
-                }
+                if (alive) free_path = soc_ffs_free_path(KIND == SOC_SCA_PS, tau, &w.rng, w.photons);
                 tau  = 0.0f;
                 scat = 0;
                 mode = (w.ind >= 0) ? SCA_M_MAIN : SCA_M_CREATE;
@@ -216,53 +184,13 @@ __global__ __launch_bounds__(256) void soc_sca_kernel(const SocGrid G, const Soc
                     bool more = true;
                     if (IRAY >= batch) {
                         IRAY = 0;
-                        PWEI = 1.0f;
-                        while (true) {
-                            ICELL += S.GLOBAL;
-                            if (ICELL >= G.CELLS) { more = false; break; }
-                            if (S.USE_EMWEIGHT > 0) {
-                                PWEI = S.EMWEI[ICELL];
-                                if ((PWEI < 1e-10f) || (G.DENS[ICELL] <= 0.0f)) continue;
-                                batch = (int)soc_floorf(PWEI);
-                                if (batch < 1) { batch = 1;  PWEI = (float)(1.0 / (double)(PWEI + 1.0e-30f)); }
-                                else           { PWEI = (float)(1.0 / (double)((float)batch + 1.0e-9f)); }
-                            } else {
-                                batch = S.BATCH;
-                                PWEI  = 1.0f / ((float)batch + 1.0e-9f);
-                            }
-                            break;
-                        }
+                        more = soc_cl_next_cell(G, S, ICELL, batch, PWEI);
                     }
                     if (!more) {
                         mode = SCA_M_DONE;
                     } else {
-                        int ind = (int)ICELL, level;
                         IRAY += 1;
-                        for (level = 0; level < G.LEVELS - 1; level++) {
-                            ind -= sLC[level];
-                            if (ind < 0) { ind += sLC[level]; break; }
-                        }
-                        float X0, Y0, Z0;
-                        if (level == 0) {
-                            X0 = (float)(ind % NX);  Y0 = (float)((ind / NX) % NY);  Z0 = (float)(ind / (NX * NY));
-                        } else {
-                            const int sid = ind % 8;
-                            X0 = (float)(sid % 2);  Y0 = ((sid % 4) > 1) ? 1.0f : 0.0f;  Z0 = (float)(sid / 4);
-                        }
-                        w.level = level;  w.ind = ind;
-                        w.dens = G.DENS[sOFF[level] + ind];
-                        w.photons = S.EMIT[sOFF[level] + ind] * PWEI;
-                        w.px = X0 + soc_rand(&w.rng);
-                        w.py = Y0 + soc_rand(&w.rng);
-                        w.pz = Z0 + soc_rand(&w.rng);
-                        const float phi       = SOC_TWOPI * soc_rand(&w.rng);
-                        const float cos_theta = 0.999997f - 1.999995f * soc_rand(&w.rng);
-                        const float sin_theta = soc_sqrtf(1.0f - cos_theta * cos_theta);
-                        float sp, cp;
-                        soc_sincosf(phi, &sp, &cp);
-                        w.ux = sin_theta * cp;
-                        w.uy = sin_theta * sp;
-                        w.uz = cos_theta;
+                        (void)soc_cl_emit<OCT>(G, S, sOFF, (int)ICELL, PWEI, w);
                         have = true;
                     }
                 } else if (KIND == SOC_SCA_HP) {
@@ -286,10 +214,7 @@ __global__ __launch_bounds__(256) void soc_sca_kernel(const SocGrid G, const Soc
                 if (have) {
                     if (KIND != SOC_SCA_HP) {                  // SimRAM_HP has conditioned the direction itself
                         n_pkt++;
-                        if (soc_fabsf(w.ux) < SOC_DEPS) w.ux = SOC_DEPS;
-                        if (soc_fabsf(w.uy) < SOC_DEPS) w.uy = SOC_DEPS;
-                        if (soc_fabsf(w.uz) < SOC_DEPS) w.uz = SOC_DEPS;
-                        soc_normalize(w.ux, w.uy, w.uz);
+                        soc_condition_direction(w.ux, w.uy, w.uz);
                     }
                     tau  = 0.0f;
                     scat = 0;
@@ -361,7 +286,7 @@ static hipError_t sca_dispatch(const SocGrid &G, const SocSim &S, const SocSca &
 {
     if (S.gid_count == 0) return hipSuccess;
     const dim3   block(256), grid((S.gid_count + 255) / 256);
-    const size_t lds = (size_t)(2 * S.BINS) * sizeof(float) + 2 * SOC_MAXL * sizeof(int);
+    const size_t lds = (size_t)(2 * S.BINS) * sizeof(float) + SOC_MAXL * sizeof(int);
     if (lds > 64 * 1024) return hipErrorInvalidValue;
 #define SCA_GO(O, D, A) soc_sca_kernel<O, D, A, KIND><<<grid, block, lds, st>>>(G, S, V)
     if (X.octree) {

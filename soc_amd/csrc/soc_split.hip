@@ -266,8 +266,7 @@ __global__ __launch_bounds__(64) void soc_sim_bg_split_kernel(const SocGrid G, c
     extern __shared__ float lds[];
     float *sCSC = lds;
     int   *sOFF = (int *)(lds + S.BINS);
-    int   *sLC  = sOFF + SOC_MAXL;
-    soc_stage_lds(G, S, sCSC, sOFF, sLC);
+    soc_stage_lds(G, S, sCSC, sOFF);
 
     const uint32_t t = blockIdx.x * 64u + threadIdx.x;
     if (t >= S.gid_count) return;
@@ -294,10 +293,7 @@ __global__ __launch_bounds__(64) void soc_sim_bg_split_kernel(const SocGrid G, c
             SocSplitRay r;
             r.px = w.px;  r.py = w.py;  r.pz = w.pz;  r.ux = w.ux;  r.uy = w.uy;  r.uz = w.uz;
             r.photons = w.photons;  r.dens = w.dens;  r.level = w.level;  r.ind = w.ind;  r.RL = 0;
-            if (soc_fabsf(r.ux) < SOC_DEPS) r.ux = SOC_DEPS;
-            if (soc_fabsf(r.uy) < SOC_DEPS) r.uy = SOC_DEPS;
-            if (soc_fabsf(r.uz) < SOC_DEPS) r.uz = SOC_DEPS;
-            soc_normalize(r.ux, r.uy, r.uz);
+            soc_condition_direction(r.ux, r.uy, r.uz);
             finished = soc_split_walk<OCT, DBL, ABU, WINT, false>(G, S, sCSC, sOFF, cap, st, r, &w.rng, n);
         }
     }
@@ -308,7 +304,7 @@ hipError_t soc_launch_sim_bg_split(const SocGrid &G, const SocSim &S, const SocS
 {
     if (S.gid_count == 0) return hipSuccess;
     const dim3 grid((S.gid_count + 63) / 64), block(64);
-    const size_t lds = (size_t)S.BINS * 4 + 2 * SOC_MAXL * 4;
+    const size_t lds = (size_t)S.BINS * 4 + SOC_MAXL * 4;
     switch (soc_split_key(V)) {         // (soc_dev.h: what soc_last_variant reports comes from the same key)
     case 0:  soc_sim_bg_split_kernel<false, false, false, false><<<grid, block, lds, st>>>(G, S, P); break;
     case 1:  soc_sim_bg_split_kernel<false, false, false, true><<<grid, block, lds, st>>>(G, S, P); break;
@@ -341,8 +337,7 @@ __global__ __launch_bounds__(64) void soc_sim_hp_split_kernel(const SocGrid G, c
     extern __shared__ float lds[];
     float *sCSC = lds;
     int   *sOFF = (int *)(lds + S.BINS);
-    int   *sLC  = sOFF + SOC_MAXL;
-    soc_stage_lds(G, S, sCSC, sOFF, sLC);
+    soc_stage_lds(G, S, sCSC, sOFF);
 
     const uint32_t t = blockIdx.x * 64u + threadIdx.x;
     if (t >= S.gid_count) return;
@@ -364,10 +359,7 @@ __global__ __launch_bounds__(64) void soc_sim_hp_split_kernel(const SocGrid G, c
         SocSplitRay r;
         r.px = w.px;  r.py = w.py;  r.pz = w.pz;  r.ux = w.ux;  r.uy = w.uy;  r.uz = w.uz;
         r.photons = w.photons;  r.dens = w.dens;  r.level = w.level;  r.ind = w.ind;  r.RL = 0;
-        if (soc_fabsf(r.ux) < SOC_DEPS) r.ux = SOC_DEPS;
-        if (soc_fabsf(r.uy) < SOC_DEPS) r.uy = SOC_DEPS;
-        if (soc_fabsf(r.uz) < SOC_DEPS) r.uz = SOC_DEPS;
-        soc_normalize(r.ux, r.uy, r.uz);
+        soc_condition_direction(r.ux, r.uy, r.uz);
         finished = soc_split_walk<OCT, DBL, ABU, WINT, true>(G, S, sCSC, sOFF, cap, st, r, &w.rng, n);
     }
     soc_split_count(S, P, n);
@@ -378,7 +370,7 @@ hipError_t soc_launch_sim_hp_split(const SocGrid &G, const SocSim &S, const SocS
     if (S.gid_count == 0) return hipSuccess;
     if (!S.HPBG || (S.HPBG_WEIGHTED && !S.HPBGP)) return hipErrorInvalidValue;
     const dim3 grid((S.gid_count + 63) / 64), block(64);
-    const size_t lds = (size_t)S.BINS * 4 + 2 * SOC_MAXL * 4;
+    const size_t lds = (size_t)S.BINS * 4 + SOC_MAXL * 4;
     switch (soc_split_key(V)) {         // (soc_dev.h: what soc_last_variant reports comes from the same key)
     case 0:  soc_sim_hp_split_kernel<false, false, false, false><<<grid, block, lds, st>>>(G, S, P); break;
     case 1:  soc_sim_hp_split_kernel<false, false, false, true><<<grid, block, lds, st>>>(G, S, P); break;

@@ -34,6 +34,16 @@ __device__ __forceinline__ void soc_normalize(float &x, float &y, float &z)
     z = z * s;
 }
 
+// What every kernel of the reference does to a new direction before GetStep divides by its components
+// (kernel_ASOC.c:508-511, :921-924, :1399-1402, kernel_ASOC_aux.c:557-560, kernel_ASOC_sca.c:138-141, :882-885, :1222-1225)
+__device__ __forceinline__ void soc_condition_direction(float &ux, float &uy, float &uz)
+{
+    if (soc_fabsf(ux) < SOC_DEPS) ux = SOC_DEPS;
+    if (soc_fabsf(uy) < SOC_DEPS) uy = SOC_DEPS;
+    if (soc_fabsf(uz) < SOC_DEPS) uz = SOC_DEPS;
+    soc_normalize(ux, uy, uz);
+}
+
 __device__ __forceinline__ void soc_tally(float *buf, int oind, float v)
 {
 #if defined(SOC_EXPERIMENT_NO_TALLY)
@@ -223,10 +233,7 @@ __device__ __forceinline__ void soc_scatter(float &ux, float &uy, float &uz, con
     float cos_theta = sCSC[bin];
     float phi = SOC_TWOPI * soc_rand(rng);
     soc_deflect(ux, uy, uz, cos_theta, phi);
-    if (soc_fabsf(ux) < SOC_DEPS) ux = SOC_DEPS;
-    if (soc_fabsf(uy) < SOC_DEPS) uy = SOC_DEPS;
-    if (soc_fabsf(uz) < SOC_DEPS) uz = SOC_DEPS;
-    soc_normalize(ux, uy, uz);
+    soc_condition_direction(ux, uy, uz);
 }
 
 // The first and every later free path (kernel_ASOC.c:516-535, :752-763 and the same lines of SimRAM_HP / SimRAM_CL):
@@ -388,10 +395,7 @@ struct SocWalker {
     // after creation: kernel_ASOC.c:508-519
     __device__ __forceinline__ void begin(const SocSim &S)
     {
-        if (soc_fabsf(ux) < SOC_DEPS) ux = SOC_DEPS;
-        if (soc_fabsf(uy) < SOC_DEPS) uy = SOC_DEPS;
-        if (soc_fabsf(uz) < SOC_DEPS) uz = SOC_DEPS;
-        soc_normalize(ux, uy, uz);
+        soc_condition_direction(ux, uy, uz);
         scat = 0;
         tau  = 0.0f;
         free_path = soc_draw_free_path(S, &rng, photons);
@@ -519,13 +523,10 @@ __device__ __forceinline__ bool soc_service_now(bool waiting, bool nobody_steps)
     return (m != 0ull) && (nobody_steps || (__popcll(m) >= SOC_SERVICE_LANES));
 }
 
-__device__ __forceinline__ void soc_stage_lds(const SocGrid &G, const SocSim &S, float *sCSC, int *sOFF, int *sLC)
+__device__ __forceinline__ void soc_stage_lds(const SocGrid &G, const SocSim &S, float *sCSC, int *sOFF)
 {
     for (int i = threadIdx.x; i < S.BINS; i += blockDim.x) sCSC[i] = S.CSC[i];
-    if (threadIdx.x < SOC_MAXL) {
-        sOFF[threadIdx.x] = G.OFF[threadIdx.x];
-        sLC[threadIdx.x]  = G.LCELLS[threadIdx.x];
-    }
+    if (threadIdx.x < SOC_MAXL) sOFF[threadIdx.x] = G.OFF[threadIdx.x];
     __syncthreads();
 }
 
@@ -704,6 +705,142 @@ __device__ __forceinline__ void soc_pb_create(const SocGrid &G, const SocSim &S,
     }
 }
 
+// ------------------------------------------------------------------------------------
+// SimRAM_CL: emission from the cells (kernel_ASOC.c:1283-1432, kernel_ASOC_sca.c:1158-1222).  A work item walks the
+// cells id, id + GLOBAL, ... and sends `batch` packets of weight PWEI from each.
+// ------------------------------------------------------------------------------------
+
+// Packets of a cell and the weight of each (kernel_ASOC.c:1332-1355): with USE_EMWEIGHT > 0 from the cell's EMWEI
+// (`emwei`, not read otherwise), else BATCH packets from every cell.  (float)batch + 1.0e-9f is what the reference's
+// int + float means in C, so the copies that wrote `batch + 1.0e-9f` had the same bits.
+__device__ __forceinline__ void soc_cl_packets(const SocSim &S, const float emwei, int &batch, float &PWEI)
+{
+    if (S.USE_EMWEIGHT > 0) {
+        PWEI  = emwei;
+        batch = (int)soc_floorf(PWEI);
+        if (batch < 1) { batch = 1;  PWEI = (float)(1.0 / (double)(PWEI + 1.0e-30f)); }
+        else           { PWEI = (float)(1.0 / (double)((float)batch + 1.0e-9f)); }
+    } else {
+        batch = S.BATCH;
+        PWEI  = 1.0f / ((float)batch + 1.0e-9f);
+    }
+}
+
+// The next emitting cell of the work item (kernel_ASOC.c:1323-1359): ICELL += GLOBAL past cells without weight or
+// without density (parents hold a link there); false when the work item is finished.
+__device__ __forceinline__ bool soc_cl_next_cell(const SocGrid &G, const SocSim &S, long long &ICELL, int &batch, float &PWEI)
+{
+    while (true) {
+        ICELL += S.GLOBAL;
+        if (ICELL >= G.CELLS) return false;
+        float emwei = 0.0f;
+        if (S.USE_EMWEIGHT > 0) {
+            emwei = S.EMWEI[ICELL];
+            if ((emwei < 1e-10f) || (G.DENS[ICELL] <= 0.0f)) continue;
+        }
+        soc_cl_packets(S, emwei, batch, PWEI);
+        return true;
+    }
+}
+
+// A packet from cell `cell` (kernel_ASOC.c:1367-1396): level and index from the cell number, density, photons, a
+// uniform position in the cell, an isotropic direction.  Returns the cell's place in the per-cell arrays.
+// The level's cell count is OFF[level + 1] - OFF[level] (soc_set_grid builds OFF as the running sum of LCELLS; the loop
+// stops before the last level), the same integer as the LCELLS[level] some copies read.
+template <bool OCT, typename W>
+__device__ __forceinline__ int soc_cl_emit(const SocGrid &G, const SocSim &S, const int *sOFF, const int cell, const float PWEI, W &w)
+{
+    int level = 0, ind = cell;
+    if (OCT) {
+        for (level = 0; level < G.LEVELS - 1; level++) {
+            if (ind < sOFF[level + 1] - sOFF[level]) break;
+            ind -= sOFF[level + 1] - sOFF[level];
+        }
+    }
+    float X0, Y0, Z0;
+    if (level == 0) {
+        X0 = (float)(ind % G.NX);  Y0 = (float)((ind / G.NX) % G.NY);  Z0 = (float)(ind / (G.NX * G.NY));
+    } else {
+        const int sid = ind % 8;
+        X0 = (float)(sid % 2);  Y0 = ((sid % 4) > 1) ? 1.0f : 0.0f;  Z0 = (float)(sid / 4);
+    }
+    const int oind = (OCT ? sOFF[level] : 0) + ind;
+    w.level   = level;
+    w.ind     = ind;
+    w.dens    = G.DENS[oind];
+    w.photons = S.EMIT[oind] * PWEI;
+    w.px = X0 + soc_rand(&w.rng);
+    w.py = Y0 + soc_rand(&w.rng);
+    w.pz = Z0 + soc_rand(&w.rng);
+    const float phi       = SOC_TWOPI * soc_rand(&w.rng);
+    const float cos_theta = 0.999997f - 1.999995f * soc_rand(&w.rng);
+    const float sin_theta = soc_sqrtf(1.0f - cos_theta * cos_theta);
+    float sp, cp;
+    soc_sincosf(phi, &sp, &cp);
+    w.ux = sin_theta * cp;
+    w.uy = sin_theta * sp;
+    w.uz = cos_theta;
+    return oind;
+}
+
+// ------------------------------------------------------------------------------------
+// scattered-light images (kernel_ASOC_sca.c): what a finished peel-off ray adds, the forced first scattering
+// ------------------------------------------------------------------------------------
+
+// What a peel-off ray of optical depth taup adds to its pixel, before the 1/d^2 of a Healpix view (:338-357, :381-400
+// PB; :1387-1392 CL).  (dx, dy, dz): the packet's direction, (ux, uy, uz): the ray's.  CLW (SimRAM_CL, SimRAM_HP): the
+// HG_TEST branch, see soc_sca.hip; else the bin of the discrete scattering function DSC (with WITH_MSF the species' row).
+__device__ __forceinline__ float soc_peel_delta(const bool CLW, const float photons, const float taup, const float dx, const float dy,
+                                                const float dz, const float ux, const float uy, const float uz, const float *DSC, const int BINS)
+{
+    const float CL = CLW ? 0.9999f : 0.999f;
+    const float cos_theta = soc_clampf(dx * ux + dy * uy + dz * uz, -CL, +CL);
+    if (CLW) {
+        const float g = 0.65f;
+        const float fraction = (1.0f / (4.0f * SOC_PI)) * (1.0f - g * g) / soc_pow15f(1.0f + g * g - 2.0f * g * cos_theta);
+        return photons * fraction * ((taup > SOC_TAULIM) ? (1.0f - soc_expf(-taup)) : (taup * (1.0f - 0.5f * taup)));
+    }
+    int b = (int)(BINS * (1.0f + cos_theta) * 0.5f);
+    b = b < 0 ? 0 : (b > BINS - 1 ? BINS - 1 : b);
+    return photons * soc_expf(-taup) * DSC[b];
+}
+
+// Pixel of observer idir's flat image that position (px, py, pz) falls on, as an index to OUT; -1 outside (:401-409)
+__device__ __forceinline__ int soc_sca_pixel(const SocSca &V, const int idir, const float px, const float py, const float pz)
+{
+    const float qx = px - V.CX, qy = py - V.CY, qz = pz - V.CZ;
+    const float4 ra = V.ORA[idir], de = V.ODE[idir];
+    const int i = (int)((0.5f * V.NPIX_X - 0.00005f) + (qx * ra.x + qy * ra.y + qz * ra.z) / V.MAP_DX);
+    const int j = (int)((0.5f * V.NPIX_Y - 0.00005f) + (qx * de.x + qy * de.y + qz * de.z) / V.MAP_DX);
+    if ((i < 0) || (j < 0) || (i >= V.NPIX_X) || (j >= V.NPIX_Y)) return -1;
+    return i + idir * V.NPIX_X * V.NPIX_Y + j * V.NPIX_X;
+}
+
+// Healpix view from a position (NDIR = -nside): pixel of the direction towards the observer (:358-361); -1: none
+__device__ __forceinline__ int soc_sca_healpix_pixel(const SocSca &V, const float ux, const float uy, const float uz)
+{
+    const float theta = soc_acosf(-uz);
+    const float phi   = soc_atan2f(uy, ux);
+    return soc_angles2pixel_ring(-V.NDIR, phi, theta);
+}
+
+// Forced first scattering: tau is the optical depth of scattering along the whole line of sight.  The packet keeps the
+// fraction W that scatters, and its first free path is drawn within tau (:899-909 PB, :1249-1258 CL, :1733-1745 PS).
+// PS: SimRAM_PS forms W with expm1 and takes the logarithm in fp32; the others in fp64.
+__device__ __forceinline__ float soc_ffs_free_path(const bool PS, const float tau, soc_rng_t *rng, float &photons)
+{
+    float W, free_path;
+    if (PS) {
+        W = -soc_expm1f(-tau);
+        free_path = -soc_logf(1.0f - W * soc_rand(rng));
+    } else {
+        W = 1.0f - soc_expf(-tau);
+        free_path = -(float)soc_logd(1.0 - (double)(W * soc_rand(rng)));
+    }
+    photons *= W;
+    return free_path;
+}
+
 // Pixel2AnglesRing (kernel_ASOC_aux.c:987-1026): Healpix RING pixel -> (phi, theta)
 __device__ __forceinline__ void soc_pixel2angles_ring(const int nside, const int ipix, float &phi, float &theta)
 {
@@ -824,10 +961,7 @@ __device__ __forceinline__ void soc_hp_create(const SocGrid &G, const SocSim &S,
     w.uy = +st * sp;
     w.uz = -ct;
     if (!RAW) {
-        if (soc_fabsf(w.ux) < SOC_DEPS) w.ux = SOC_DEPS;
-        if (soc_fabsf(w.uy) < SOC_DEPS) w.uy = SOC_DEPS;
-        if (soc_fabsf(w.uz) < SOC_DEPS) w.uz = SOC_DEPS;
-        soc_normalize(w.ux, w.uy, w.uz);
+        soc_condition_direction(w.ux, w.uy, w.uz);
     }
     float x = soc_fabsf(w.ux), y = soc_fabsf(w.uy), z = soc_fabsf(w.uz);
     float ds = x + y + z;
@@ -865,10 +999,7 @@ __device__ __forceinline__ void soc_hp_sca_create(const SocGrid &G, const SocSim
     w.ux = +st * cp;
     w.uy = +st * sp;
     w.uz = -ct;
-    if (soc_fabsf(w.ux) < SOC_DEPS) w.ux = SOC_DEPS;
-    if (soc_fabsf(w.uy) < SOC_DEPS) w.uy = SOC_DEPS;
-    if (soc_fabsf(w.uz) < SOC_DEPS) w.uz = SOC_DEPS;
-    soc_normalize(w.ux, w.uy, w.uz);
+    soc_condition_direction(w.ux, w.uy, w.uz);
     const float ds = 2.0f * SOC_PI * soc_rand(&w.rng);
     const float dx = soc_sqrtf(soc_rand(&w.rng));
     float sd, cd;

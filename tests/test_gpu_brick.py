@@ -6,7 +6,7 @@ import pytest
 import cases
 from oracle.pyoracle import Job
 from soc_amd import synth
-from util import run_engine, assert_tally_close
+from util import assert_tally_close, assert_zero_weights_skipped, cl_packets, emission_weights, run_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -384,6 +384,27 @@ def test_brick_sweep_cell_emission(name, engine, oracle_soc, tuned):
     Tg, Ig, st = run_engine(engine, job, kind, exec_mode=1, brick_log2=2)
     assert engine.last_passes() > 0
     assert st["tally_events"] == n, "trajectories diverged from the oracle"
+    assert_tally_close(Tg, T, rtol=1e-5)
+    engine.set_exec(-1, 4)
+
+
+@pytest.mark.parametrize("octree", [False, True])
+def test_brick_sweep_cell_emission_skips_cells_without_weight(octree, engine, oracle_soc, tuned):
+    """Cells with EMWEI < 1e-10 are stepped over (kernel_ASOC.c:1337): the case cl_oct8_emw and its Cartesian twin, the same
+    weights with every third one at zero, through the Cartesian sweep (form 1) and the one on the hierarchy in global memory (2)"""
+    tuned(brick_cells=300)
+    cl = cases._oct8() if octree else cases._c8()
+
+    def mk(e):
+        return Job(cl, cases._CSC, ABS=1e-4, SCA=3e-4, SOURCE=2, BATCH=3, SEED=0.9, GLOBAL=128, EMIT=cases._emit(cl),
+                   EMWEI=emission_weights(cl.CELLS, e, hi=3.0), USE_EMWEIGHT=1)
+    job = mk("zeros")
+    T, I, n = oracle_soc.sim(job, 1)
+    assert_zero_weights_skipped(job, mk(1), 0, job.GLOBAL, n, oracle_soc.sim(mk(1), 1)[2])
+    Tg, Ig, st = run_engine(engine, job, 1, exec_mode=1, brick_log2=2)
+    assert engine.last_passes() > 0 and engine.last_form() == (2 if octree else 1)
+    assert st["tally_events"] == n, "trajectories diverged from the oracle"
+    assert st["packets"] == cl_packets(job)
     assert_tally_close(Tg, T, rtol=1e-5)
     engine.set_exec(-1, 4)
 

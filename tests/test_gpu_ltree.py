@@ -8,7 +8,7 @@ import pytest
 import cases
 from oracle.pyoracle import Job
 from soc_amd import synth
-from util import assert_tally_close, run_engine
+from util import EMW, assert_tally_close, assert_zero_weights_skipped, cl_packets, emission_weights, run_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -100,18 +100,26 @@ def test_point_sources_inside_and_outside(slow, engine, oracle_soc, tuned):
     engine.set_exec(-1, 4)
 
 
-@pytest.mark.parametrize("emw", [0, 1])
+@pytest.mark.parametrize("emw", EMW)
 def test_cell_emission(emw, engine, oracle_soc, tuned):
-    """SimRAM_CL: without emission weights packets also start "in" refined cells (kernel_ASOC.c:1318-1355)"""
+    """SimRAM_CL: without emission weights packets also start "in" refined cells (kernel_ASOC.c:1318-1355); with them, cells
+    without weight are stepped over ("zeros")"""
     cl = cloud104()
     emit = np.where(cl.DENS > 0, cl.DENS * 1e-3, 1e-4).astype(np.float32)
-    emwei = np.random.default_rng(5).uniform(0, 2.5, cl.CELLS).astype(np.float32) if emw else None
-    job = Job(cl, cases._CSC, ABS=3e-6, SCA=3e-5, SOURCE=2, BATCH=1, SEED=0.9, GLOBAL=8192, EMIT=emit, EMWEI=emwei, USE_EMWEIGHT=emw)
+
+    def mk(e):
+        return Job(cl, cases._CSC, ABS=3e-6, SCA=3e-5, SOURCE=2, BATCH=1, SEED=0.9, GLOBAL=8192, EMIT=emit,
+                   EMWEI=emission_weights(cl.CELLS, e), USE_EMWEIGHT=1 if e else 0)
+    job = mk(emw)
     g0, g1 = 4000, 4096
     T, _, n = oracle_soc.sim(job, 1, gid0=g0, gid1=g1, nthreads=8)
+    if emw == "zeros":
+        assert_zero_weights_skipped(job, mk(1), g0, g1, n, oracle_soc.sim(mk(1), 1, gid0=g0, gid1=g1, nthreads=8)[2])
     tuned(slow_every=7)
     Tg, _, st = _sweep(engine, job, 1, gid_first=g0, gid_count=g1 - g0)
     assert st["tally_events"] == n
+    if emw == "zeros":
+        assert st["packets"] == cl_packets(job, g0, g1)
     assert_tally_close(Tg, T, rtol=1e-5)
     engine.set_exec(-1, 4)
 

@@ -16,7 +16,7 @@ import pytest
 import cases
 from oracle.pyoracle import Job
 from soc_amd import synth
-from util import assert_tally_close, run_engine
+from util import EMW, assert_tally_close, assert_zero_weights_skipped, cl_packets, emission_weights, run_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -165,17 +165,23 @@ def test_point_sources_inside_and_outside(engine, oracle_soc):
 
 
 # ---- 3: cell emission ----
-@pytest.mark.parametrize("emw", [0, 1])
+@pytest.mark.parametrize("emw", EMW)
 def test_cell_emission(emw, engine, oracle_soc, tuned):
     cl = cloud104()
-    emwei = np.random.default_rng(5).uniform(0, 2.5, cl.CELLS).astype(np.float32) if emw else None
-    job = Job(cl, cases._CSC, ABS=3e-6, SCA=3e-5, SOURCE=2, BATCH=1, SEED=0.9, GLOBAL=8192, EMIT=emit104(), EMWEI=emwei, USE_EMWEIGHT=emw,
-              OPT=opt104())
+
+    def mk(e):
+        return Job(cl, cases._CSC, ABS=3e-6, SCA=3e-5, SOURCE=2, BATCH=1, SEED=0.9, GLOBAL=8192, EMIT=emit104(),
+                   EMWEI=emission_weights(cl.CELLS, e), USE_EMWEIGHT=1 if e else 0, OPT=opt104())
+    job = mk(emw)
     g0, g1 = 4000, 4096
     T, _, n = oracle(oracle_soc, ("cl", emw), job, 1, gid0=g0, gid1=g1)
+    if emw == "zeros":                                   # (cells without weight are stepped over)
+        assert_zero_weights_skipped(job, mk(1), g0, g1, n, oracle(oracle_soc, ("cl", 1), mk(1), 1, gid0=g0, gid1=g1)[2])
     tuned(slow_every=7)
     Tg, _, st = _sweep(engine, job, 1, gid_first=g0, gid_count=g1 - g0)
     assert st["tally_events"] == n
+    if emw == "zeros":
+        assert st["packets"] == cl_packets(job, g0, g1)
     assert_tally_close(Tg, T, rtol=1e-5)
 
 

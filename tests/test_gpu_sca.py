@@ -78,6 +78,30 @@ def test_sca_hip_matches_oracle(name, engine, oracle_soc):
     assert abs(got.sum(dtype=np.float64) / GOLD[name].sum(dtype=np.float64) - 1.0) < 1e-2
 
 
+@pytest.mark.parametrize("octree", [False, True])
+def test_sca_cell_emission_skips_cells_without_weight(octree, engine, oracle_soc):
+    """Cells with EMWEI < 1e-10 are stepped over (kernel_ASOC_sca.c:1158-1222): the case sca_cl_oct8_emw and its Cartesian twin,
+    the same weights with every third one at zero, through the direct kernel"""
+    from oracle.pyoracle import Job
+    from util import assert_zero_weights_skipped, cl_packets, emission_weights
+    cl = cases._oct8() if octree else cases._c8()
+
+    def mk(e):
+        return Job(cl, cases._CSC, ABS=1e-4, SCA=3e-4, SOURCE=2, BATCH=3, SEED=0.9, GLOBAL=128, EMIT=cases._emit(cl),
+                   EMWEI=emission_weights(cl.CELLS, e, hi=3.0), USE_EMWEIGHT=1, DSC=cases._DSC)
+    job, view = mk("zeros"), cases.sca_view()
+    want, n = oracle_sim_sca(oracle_soc, job, view, 1)
+    assert_zero_weights_skipped(job, mk(1), 0, job.GLOBAL, n, oracle_sim_sca(oracle_soc, mk(1), view, 1)[1])
+    engine.set_exec(0, 4)
+    try:
+        got, st = run_sca(engine, job, view, 1)
+        assert engine.last_passes() == 0
+    finally:
+        engine.set_exec(-1, 4)
+    assert st["tally_events"] == n and st["packets"] == cl_packets(job)
+    assert_image_close(got, want)
+
+
 def test_sca_split_launch_adds_up(engine, oracle_soc):
     ref, kind, mk, vkw = cases.SCA_CASES["sca_bg_oct8"]
     job, view = mk(), cases.sca_view(**vkw)

@@ -12,6 +12,7 @@ from oracle.pyoracle import Job, ScaView, oracle_sim_sca
 from soc_amd import launch
 from test_gpu_ltree import cloud104
 from test_gpu_sca import assert_image_close, run_sca
+from util import EMW, assert_zero_weights_skipped, cl_packets, emission_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -79,18 +80,25 @@ def test_point_source_rays(engine, oracle_soc, parking):
         assert_image_close(got, want)
 
 
-@pytest.mark.parametrize("emw", [0, 1])
+@pytest.mark.parametrize("emw", EMW)
 def test_cell_emission_rays(emw, engine, oracle_soc, parking):
     cl = cloud104()
     k = 2.0 / (104 * float(cl.DENS[:104 ** 3][cl.DENS[:104 ** 3] > 0].mean()))
     emit = np.where(cl.DENS > 0, cl.DENS * 1e-3, 1e-4).astype(np.float32)
-    emwei = np.random.default_rng(5).uniform(0, 2.5, cl.CELLS).astype(np.float32) if emw else None
-    job = Job(cl, cases._CSC, ABS=0.3 * k, SCA=k, SOURCE=2, BATCH=1, SEED=0.9, GLOBAL=8192, EMIT=emit, EMWEI=emwei, USE_EMWEIGHT=emw, DSC=cases._DSC)
+
+    def mk(e):
+        return Job(cl, cases._CSC, ABS=0.3 * k, SCA=k, SOURCE=2, BATCH=1, SEED=0.9, GLOBAL=8192, EMIT=emit,
+                   EMWEI=emission_weights(cl.CELLS, e), USE_EMWEIGHT=1 if e else 0, DSC=cases._DSC)
+    job = mk(emw)
     view = view104()
     g0, g1 = 4000, 4024
     want, n = oracle_sim_sca(oracle_soc, job, view, 1, gid0=g0, gid1=g1, nthreads=8)
+    if emw == "zeros":                                   # (cells without weight are stepped over)
+        assert_zero_weights_skipped(job, mk(1), g0, g1, n, oracle_sim_sca(oracle_soc, mk(1), view, 1, gid0=g0, gid1=g1, nthreads=8)[1])
     got, st = _rays(engine, job, view, 1, g0, g1)
     assert st["tally_events"] == n and st["packets"] > 1000
+    if emw == "zeros":
+        assert st["packets"] == cl_packets(job, g0, g1)
     assert_image_close(got, want)
 
 

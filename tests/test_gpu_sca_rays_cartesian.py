@@ -16,6 +16,7 @@ from soc_amd import files, launch, synth
 from soc_amd.lib import SocError
 from test_gpu_sca import assert_image_close, run_sca
 from test_gpu_sca_rays import parking  # noqa: F401  (the three parking settings)
+from util import EMW, assert_zero_weights_skipped, cl_packets, emission_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -135,16 +136,24 @@ def test_point_source_rays(grid, meth, engine, oracle_soc):
         assert st["packets"] == 12 * 512
 
 
-@pytest.mark.parametrize("emw", [0, 1])
+@pytest.mark.parametrize("emw", EMW)
 @pytest.mark.parametrize("grid", GRIDS)
 def test_cell_emission_rays(grid, emw, engine, oracle_soc, parking):  # noqa: F811
     cl = cloud(grid)
     emit = (cl.DENS * 1e-3).astype(np.float32)
-    emwei = np.random.default_rng(5).uniform(0, 2.5, cl.CELLS).astype(np.float32) if emw else None
-    jb = job(cl, SOURCE=2, BATCH=1, SEED=0.9, GLOBAL=8192, EMIT=emit, EMWEI=emwei, USE_EMWEIGHT=emw)
+
+    def mk(e):
+        return job(cl, SOURCE=2, BATCH=1, SEED=0.9, GLOBAL=8192, EMIT=emit, EMWEI=emission_weights(cl.CELLS, e), USE_EMWEIGHT=1 if e else 0)
+    jb = mk(emw)
     g0, g1 = 4000, 4024 + (72 if grid == "odd" else 0)
+    if emw == "zeros":                                   # (cells without weight are stepped over)
+        assert_zero_weights_skipped(jb, mk(1), g0, g1, _oracle(oracle_soc, ("cl", grid, emw), jb, view(cl), 1, g0, g1)[1],
+                                    _oracle(oracle_soc, ("cl", grid, 1), mk(1), view(cl), 1, g0, g1)[1])
     st = _parity(engine, oracle_soc, ("cl", grid, emw), jb, view(cl), 1, g0, g1)
-    assert st["packets"] > 800
+    if emw == "zeros":                                   # a third fewer packets than with all weights positive: the exact number
+        assert st["packets"] == cl_packets(jb, g0, g1) > 600
+    else:
+        assert st["packets"] > 800
 
 
 @pytest.mark.parametrize("weighted", [False, True], ids=["uniform", "weighted"])

@@ -84,3 +84,41 @@ def same_bits(got, want):
     got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
     ok = np.isfinite(want)
     return np.array_equal(np.isfinite(got), ok) and np.array_equal(got[ok].view(np.uint32), want[ok].view(np.uint32))
+
+
+# Parametrisation of the cell-emission tests: USE_EMWEIGHT 0, 1, and 1 with cells whose weight is zero.  SimRAM_CL steps over such
+# cells (EMWEI < 1e-10, kernel_ASOC.c:1337); a real run has them in most of the model, uniform(0, hi) weights have none.
+EMW = [0, 1, "zeros"]
+
+
+def emission_weights(cells, emw, hi=2.5, seed=5):
+    """EMWEI of a cell-emission test: None (emw 0), uniform(0, hi) (emw 1), the same with every third cell at 0.0f ("zeros")"""
+    if not emw:
+        return None
+    w = np.random.default_rng(seed).uniform(0, hi, cells).astype(np.float32)
+    if emw == "zeros":
+        w[::3] = np.float32(0.0)
+    return w
+
+
+def cl_packets(job, g0=0, g1=None):
+    """Packets SimRAM_CL sends from work items [g0, g1) (kernel_ASOC.c:1323-1359): work item id has the cells id, id + GLOBAL, ...;
+    with USE_EMWEIGHT 1 a cell without weight or without density sends none, the others max(1, floor(EMWEI)); else BATCH each"""
+    g1 = job.GLOBAL if g1 is None else g1
+    item = np.arange(job.cloud.CELLS) % job.GLOBAL
+    mine = (item >= g0) & (item < g1)
+    if job.USE_EMWEIGHT == 0:
+        return int(mine.sum()) * job.BATCH
+    live = mine & ~(job.EMWEI < np.float32(1e-10)) & ~(job.DENS <= 0)
+    return int(np.maximum(np.floor(job.EMWEI[live]), 1).sum())
+
+
+def assert_zero_weights_skipped(job, dense, g0, g1, n, n_dense):
+    """The CPU side of an emw == "zeros" case.  `dense`: the same job with the all-positive weights; n, n_dense: the events the
+    oracle counted for the two (it has no counter of packets: those follow from the rule above, which it restates).  The input
+    has leaf cells without weight among the work items' cells, and the oracle sends fewer packets for it: the arm runs."""
+    item = np.arange(job.cloud.CELLS) % job.GLOBAL
+    mine = (item >= g0) & (item < g1) & (job.DENS > 0)
+    assert ((job.EMWEI == 0) & mine).any() and (dense.EMWEI[mine] > 0).all()
+    assert cl_packets(job, g0, g1) < cl_packets(dense, g0, g1)
+    assert n < n_dense
