@@ -713,6 +713,42 @@ int soc_set_emission_column(soc_ctx *ctx, int ifreq, const float *COEFF);
 int soc_read_emission(soc_ctx *ctx, float *EMIT, int64_t n);
 int soc_emitted_end(soc_ctx *ctx);
 
+/* ---- the absorptions of the transfer stage, RESIDENT between the launches that tally them and the multi-dust stage ---- */
+
+/* The mirror image of the above.  A launch leaves the absorptions of one frequency as an INT tally of CELLS floats; the multi-dust stage
+ * wants ABS[cells][NFREQ], scaled as the absorbed file holds them (ASOC.py:2793-2809).  Through the host that is, per iteration, a
+ * read-back per frequency, a strided add into a row-major array, a copy, a scaling pass and an upload (9.9 GB at 4.95e7 cells x 50
+ * frequencies).  Here the sum is held transposed, AT[NFREQ][CELLS]: a frequency is a contiguous row that its tally is added to, and one
+ * tiled transpose that scales on the way fills the rows of the multi-dust stage:
+ *   soc_absorbed_begin(NFREQ, keep_constant) reserves AT for the cells of the grid (after soc_set_grid), zeroed; with keep_constant != 0
+ *       also a second plane AC of the same size.  Where that does not fit the free device memory (1 GB kept back, as soc_emitted_begin)
+ *       the call fails with SOC_ERR_STATE, the size in GB in the message, and nothing is reserved or released; a second
+ *       soc_absorbed_begin replaces the first; soc_set_grid, soc_absorbed_end and soc_destroy release both planes;
+ *   soc_absorbed_add_tally(ifreq) AT[ifreq][:] += the INT tally (what soc_read_tally(SOC_TALLY_INT) reads), one float add per cell,
+ *       after deferred launches have run; the tally stays as it is;
+ *   soc_absorbed_add_slot(ifreq, k) the same from INT slot k of an ended batch, the buffer soc_batch_read_int(k) reads, with that
+ *       call's state checks (SOC_ERR_STATE before soc_batch_end, SOC_ERR_ARG for a slot the batch does not have);
+ *   soc_absorbed_keep() copies AT to AC, soc_absorbed_restore() AC to AT, device to device: the constant sources' absorptions, which
+ *       every re-emission iteration starts from.  SOC_ERR_STATE without the second plane; _restore also before any _keep;
+ *   soc_absorbed_to_mabu(c0, K, nnnlimit) fills all rows of the open soc_mabu_begin from cells [c0, c0 + its cells):
+ *       ABS[c][f] = AT[f][c0+c] * (K[level(c0+c)] / DENS[c0+c]), K[LEVELS] = 8^level * FACTOR / (GL*PARSEC) as float, one IEEE division
+ *       per cell and one product per value, both rounded to float, no fused multiply-add; -1e20 where DENS <= nnnlimit (a float
+ *       comparison: links, cells counted as empty), by selection.  The bits of files.scale_absorbed.  SOC_ERR_STATE without an open
+ *       soc_mabu_begin, SOC_ERR_ARG where its NFREQ differs, its cells run past CELLS or K is NULL;
+ *   soc_absorbed_download(c0, n, rows, K, nnnlimit) reads rows[n][NFREQ] of cells [c0, c0+n) back through the same kernel; K == NULL:
+ *       unscaled, bit for bit what was accumulated;
+ *   soc_absorbed_end() frees both planes.
+ * Every call but _begin and _end is SOC_ERR_STATE before soc_absorbed_begin; ifreq outside [0, NFREQ), c0 < 0, n < 1 or c0 + n > CELLS
+ * are SOC_ERR_ARG.  A refused call leaves AT and AC as they were. */
+int soc_absorbed_begin(soc_ctx *ctx, int NFREQ, int keep_constant);
+int soc_absorbed_add_tally(soc_ctx *ctx, int ifreq);
+int soc_absorbed_add_slot(soc_ctx *ctx, int ifreq, int k);
+int soc_absorbed_keep(soc_ctx *ctx);
+int soc_absorbed_restore(soc_ctx *ctx);
+int soc_absorbed_to_mabu(soc_ctx *ctx, int64_t c0, const float *K, float nnnlimit);
+int soc_absorbed_download(soc_ctx *ctx, int64_t c0, int64_t n, float *rows, const float *K, float nnnlimit);
+int soc_absorbed_end(soc_ctx *ctx);
+
 /* ---- the library method for dust emission: soc_library.py with kernel_soc_library.c ---- */
 
 /* A model with stochastically heated grains is simulated at three reference frequencies only; the emission of a cell is then

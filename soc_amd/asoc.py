@@ -183,6 +183,21 @@ def float_index(cloud):
     return cloud.LEVELS > 1 and cloud.NX <= (399 if cloud.LEVELS < 3 else 100)
 
 
+class ResidentAbsorptions:
+    """The engine's resident absorptions (Engine.absorbed_begin) as the sink of a transfer stage, in place of the host array
+    FABSORBED[CELLS, NFREQ]: where a stage does FABSORBED[:, col] += tally on the host, it adds the same buffer to row `col` on the device."""
+
+    def __init__(self, engine, CELLS, NFREQ):
+        self.eng = engine
+        self.shape = (int(CELLS), int(NFREQ))
+
+    def add_tally(self, col):
+        self.eng.absorbed_add_tally(col)
+
+    def add_slot(self, col, slot):
+        self.eng.absorbed_add_slot(col, slot)
+
+
 class AbsorptionRun(MapProducts):
     """The constant-source part of an ASOC run.  ``engine`` is a soc_amd.lib.Engine (or an
     object with the same methods); ``comm`` a soc_amd.dist.Comm."""
@@ -591,18 +606,40 @@ class AbsorptionRun(MapProducts):
         return [(self.LAUNCH_GROUPS if (absorbed and c.LEVELS == 1 and U.SAVE_INTENSITY == 0 and not U.WITH_ROI_SAVE and II != 3)
                  else self.SEQUENTIAL, ['PS', 'BG', 'DE', 'ROI'][II], [step(f, [(II, L)]) for f in freqs]) for II, L in blocks], owner
 
+    def resident_absorptions_refused(self):
+        """why this run cannot tally into the engine's resident absorptions (None: it can): they hold every cell at every frequency
+        of one rank, and the intensity file wants each tally on the host anyway"""
+        U = self.U
+        if not all(hasattr(self.eng, m) for m in ("absorbed_begin", "absorbed_add_tally", "absorbed_add_slot")):
+            return "the engine has no absorbed_* calls"
+        if self.world > 1:
+            return "several ranks"
+        if U.NOABSORBED or U.LIB_ABS:
+            return "noabsorbed or libabs"
+        if 'nnmake' in U.KEYS:
+            return "nnmake (absthin thinning)"
+        if U.SAVE_INTENSITY > 0:
+            return "saveint"
+        return None
+
     @_local_routing()
-    def simulate_constant_sources(self):
+    def simulate_constant_sources(self, absorbed=None):
         """for II in (point sources, background, diffuse): for IFREQ: launch (ASOC.py:1028-1545), in the order and batches of _plan.
-        Returns CTABS[CELLS] and FABSORBED[CELLS,NFREQ] (or None with noabsorbed)."""
+        Returns CTABS[CELLS] and FABSORBED[CELLS,NFREQ] (or None with noabsorbed).  absorbed: a ResidentAbsorptions (zeroed, of this run's
+        CELLS and NFREQ) that takes the tallies in place of a host array, and is what is returned as FABSORBED."""
         U, e, c = self.U, self.eng, self.cloud
         CELLS, NFREQ, FFREQ = c.CELLS, self.NFREQ, self.FFREQ
         CTABS = np.zeros(CELLS, np.float32)
         # `nnmake` with `absthin N`: the absorptions of every N-th cell only (ASOC.py:100-105, :632-638)
         thin = U.ABSTHIN if (U.ABSTHIN > 1 and 'nnmake' in U.KEYS) else 1
         self.absthin = thin
+        if absorbed is not None:
+            why = self.resident_absorptions_refused()
+            if why or absorbed.shape != (CELLS, NFREQ):
+                raise ValueError("the resident absorptions cannot be the sink of this run: %s" % (why or "%s for %d cells, %d frequencies" % (absorbed.shape, CELLS, NFREQ)))
         # (`libabs`: a column per frequency of its file, ASOC.py:621)
-        FABSORBED = None if U.NOABSORBED else np.zeros(((CELLS + thin - 1) // thin, len(U.FSELECT) if U.LIB_ABS else NFREQ), np.float32)
+        FABSORBED = absorbed if absorbed is not None else None if U.NOABSORBED else \
+            np.zeros(((CELLS + thin - 1) // thin, len(U.FSELECT) if U.LIB_ABS else NFREQ), np.float32)
         if len(U.file_constant_load) > 0:
             self.log("=== CLOAD => %s" % U.file_constant_load)
             return np.fromfile(U.file_constant_load, np.float32, CELLS), FABSORBED
@@ -664,7 +701,9 @@ class AbsorptionRun(MapProducts):
                         e.sync()
                     self.timers["Tkernel"] += time.time() - t0
                     t0 = time.time()
-                    if FABSORBED is not None or U.SAVE_INTENSITY > 0:
+                    if absorbed is not None:
+                        absorbed.add_tally(self._abs_col(IFREQ))
+                    elif FABSORBED is not None or U.SAVE_INTENSITY > 0:
                         TMP = e.read_tally(1)
                         if FABSORBED is not None:
                             FABSORBED[:, self._abs_col(IFREQ)] += TMP[0::thin]
@@ -706,7 +745,8 @@ class AbsorptionRun(MapProducts):
 
     def _read_int_groups(self, pend, FABSORBED, sync):
         """End the batch of INT groups pend = [(IFREQ, launched, summed)] and add each group's tally to FABSORBED: summed over the
-        ranks where the plan says so, zeros where this rank launched nothing in the group (the group has no tally slot)."""
+        ranks where the plan says so, zeros where this rank launched nothing in the group (the group has no tally slot).  FABSORBED a
+        ResidentAbsorptions: every slot is added to its row on the device (one rank: nothing is summed)."""
         e = self.eng
         t0 = time.time()
         e.batch_end()
@@ -715,7 +755,13 @@ class AbsorptionRun(MapProducts):
         self.timers["Tkernel"] += time.time() - t0
         t0 = time.time()
         slot = 0
+        resident = isinstance(FABSORBED, ResidentAbsorptions)
         for IFREQ, launched, summed in pend:
+            if resident:
+                if launched:
+                    FABSORBED.add_slot(self._abs_col(IFREQ), slot)
+                    slot += 1
+                continue
             arr = np.zeros(self.cloud.CELLS, np.float32)
             if launched:
                 arr, slot = e.batch_read_int(slot), slot + 1
@@ -735,8 +781,11 @@ class AbsorptionRun(MapProducts):
     def simulate_cell_emission(self, EMITTED, FABSORBED, resident=False):
         """One dust re-emission iteration as a run of its own with `iterations 1` does it (soc_amd.driver's loop): TABS zeroed, the host
         generator made anew, the emission EMITTED[CELLS, NFREQ] of the previous iteration sent from the cells at every simulated
-        frequency, each frequency's INT tally added to its column of FABSORBED.  resident: see _cell_emission_pass."""
+        frequency, each frequency's INT tally added to its column of FABSORBED (a host array, or a ResidentAbsorptions: its row on the
+        device).  resident: see _cell_emission_pass."""
         self.require_emission_at_every_frequency()
+        if isinstance(FABSORBED, ResidentAbsorptions) and self.resident_absorptions_refused():
+            raise ValueError("the resident absorptions cannot be the sink of this run: %s" % self.resident_absorptions_refused())
         self.eng.zero(0)
         hostrng = np.random.default_rng(int(self.U.SEED * 2 ** 31) if self.U.SEED > 0 else None)
         self._cell_emission_pass(EMITTED, hostrng, FABSORBED, True, resident=resident)
@@ -840,7 +889,9 @@ class AbsorptionRun(MapProducts):
                 e.sync()
             self.timers["Tkernel"] += time.time() - t0
             self.packets += CELLS * BATCH
-            if read_int and (FABSORBED is not None or U.SAVE_INTENSITY > 0):
+            if read_int and isinstance(FABSORBED, ResidentAbsorptions):
+                FABSORBED.add_tally(IFREQ)
+            elif read_int and (FABSORBED is not None or U.SAVE_INTENSITY > 0):
                 TMP = e.read_tally(1)
                 if FABSORBED is not None:
                     FABSORBED[:, IFREQ] += TMP[0::self.absthin]

@@ -283,6 +283,12 @@ hipError_t soc_launch_mabu_ratio(long long cells, int NFREQ, const float *SUM, f
 hipError_t soc_launch_reemit_to_columns(long long n, int NFREQ, long long CELLS, long long c0, const float *ROWS, float *ET, hipStream_t st);
 hipError_t soc_launch_reemit_to_rows(long long n, int NFREQ, long long CELLS, long long c0, const float *ET, float *ROWS, hipStream_t st);
 hipError_t soc_launch_reemit_column(const SocGrid &G, const float *COEFF, const float *COL, float *EMIT, hipStream_t st);
+// the resident absorptions, their mirror image (soc_reemit.hip): ROW[c] += TALLY[c] over CELLS cells, and the same tile walk from
+// AT[NFREQ][CELLS] to ROWS[n][NFREQ] with ROWS[c][f] = AT[f][c0+c] * (K[level] / DENS), -1e20 where DENS <= nnnlimit (K: LEVELS host
+// floats; NULL: the bits as they are)
+hipError_t soc_launch_absorbed_add(long long CELLS, const float *TALLY, float *ROW, hipStream_t st);
+hipError_t soc_launch_absorbed_to_rows(const SocGrid &G, long long n, int NFREQ, long long c0, const float *AT, float *ROWS, const float *K,
+                                       float nnnlimit, hipStream_t st);
 
 // the library method (soc_library.hip).  The reference columns of cell `c` are ABS[c * stride + c0 | c1 | c2].
 struct SocLibSolve {

@@ -1,4 +1,4 @@
-// soc_host.h -- what the host units of libsoc_hip.so share (soc_capi.hip, soc_capi_post.hip, soc_capi_a2e.hip, soc_capi_reemit.hip, soc_capi_library.hip, soc_capi_probe.hip):
+// soc_host.h -- what the host units of libsoc_hip.so share (soc_capi.hip, soc_capi_post.hip, soc_capi_a2e.hip, soc_capi_reemit.hip, soc_capi_absorbed.hip, soc_capi_library.hip, soc_capi_probe.hip):
 // the handle, the error and flush idioms.  Every device allocation of a handle is a DevBuf (soc_devbuf.h) that the handle owns: its
 // members, and the packet records, queues and bricks of its brick sweeps (SocSweepState, soc_brick.hip).  Kernels do not include it.
 #pragma once
@@ -133,6 +133,12 @@ struct soc_ctx {
     // contiguous row; eRows stages the rows of an upload or a download.  soc_set_grid releases both
     DevBuf<float> eET, eRows;
     int     et_nfreq = 0;              // 0: not open
+    // the resident absorptions, their mirror image (soc_absorbed_*): AT[at_nfreq][CELLS], a frequency's INT tally added to its row;
+    // bAC a second plane of the same size (soc_absorbed_keep / _restore: the constant sources' share), bRows stages a download.
+    // soc_set_grid releases all three
+    DevBuf<float> bAT, bAC, bRows;
+    int     at_nfreq = 0;              // 0: not open
+    bool    ac_kept = false;           // bAC holds what soc_absorbed_keep copied
     // the library method (soc_library_*): the resident table -- I1 | dI1 | I2 | dI2 | X | Y | Z | E0 in one block, the selected emission
     // columns [N^3][lib_nout] -- and the miss list of a look-up
     int     lib_N = 0, lib_nout = 0;

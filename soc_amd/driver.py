@@ -32,7 +32,10 @@ with `iterations 1` and `nosolve` that reads the emitted file of the iteration b
 soc_amd.asoc, soc_amd.mabu, soc_amd.asoc ... without its files.  The products are those of the last iteration.  Where the engine has
 the soc_emitted_* calls, stage 2 took its device path, there is one rank and `emweight 0`, the emission does not leave the device
 between the iterations: stage 2 leaves it transposed, ET[NFREQ][CELLS], and every launch makes its EMIT[CELLS] from one contiguous
-row (soc_set_emission_column); otherwise it goes through the host array and soc_set_emission, with the same bits.  Refused with
+row (soc_set_emission_column); otherwise it goes through the host array and soc_set_emission, with the same bits.  The absorptions
+stay there as well, with or without iterations, where the engine has the soc_absorbed_* calls, there is one rank, no `saveint` and
+stage 2 offers its device path: every INT tally is added to its row of AT[NFREQ][CELLS], a second plane keeps the constant sources'
+share, and stage 2 takes its rows from there scaled with the bits of files.scale_absorbed (open_absorbed).  Refused with
 iterations: `ali` (the escape probability feeds a temperature solve that this pipeline does not do), `reference` (the reference field
 needs the previous emission and its absorptions carried across the iterations) and a `remit` that cuts frequencies.
 """
@@ -42,7 +45,7 @@ import time
 import numpy as np
 
 from . import a2e, files, mabu
-from .asoc import AbsorptionRun, UnsupportedOption
+from .asoc import AbsorptionRun, ResidentAbsorptions, UnsupportedOption
 from .ini import User
 from .lib import DoesNotFit
 
@@ -54,12 +57,16 @@ from .mabu import (NE_EQ, dust_kind, eq_dust_table, planck_safe, relative_cross_
 class Pipeline:
     """soc.ini -> maps.  engine: soc_amd.lib.Engine (or an object with its methods); comm: soc_amd.dist.Comm"""
 
-    def __init__(self, ini, engine, comm=None, verbose=None, emission_source=None):
+    def __init__(self, ini, engine, comm=None, verbose=None, emission_source=None, absorbed_source=None):
         """emission_source: None -- the re-emission iterations take the resident emission where they can (see iterate) -- or 'host' to
-        keep them on the host statements (tests, measurements)"""
+        keep them on the host statements (tests, measurements); absorbed_source: the same for the absorptions on their way from the
+        transfer stage to stage 2 (see open_absorbed)"""
         if emission_source not in (None, 'host'):
             raise ValueError("emission_source: None or 'host'")
+        if absorbed_source not in (None, 'host'):
+            raise ValueError("absorbed_source: None or 'host'")
         self.emission_source = emission_source
+        self.absorbed_source = absorbed_source
         self.comm = comm
         self.rank = comm.rank if comm else 0
         self.world = comm.world if comm else 1
@@ -99,13 +106,13 @@ class Pipeline:
             print(*a)
 
     # ---- stage 2 ----------------------------------------------------------------------------------------------
-    def solve_emission(self, FABSORBED, ABU, keep_resident=False, download=True):
+    def solve_emission(self, FABSORBED, ABU, keep_resident=False, download=True, absorbed_scale=None):
         """FABSORBED[CELLS, NFREQ] as the absorbed file holds it (scaled, files.scale_absorbed) -> EMITTED[CELLS, NFREQ]; with
         `polarisation` lines self.R[CELLS, NFREQ] is the polarisation reduction factor.  keep_resident, download: as
         mabu.solve_emission; self.resident says whether the engine now holds this emission (then, with download=False, the arrays
-        returned are not filled)"""
+        returned are not filled).  FABSORBED a ResidentAbsorptions with absorbed_scale: as mabu.solve_emission"""
         em, info = mabu.solve_emission(self.eng, self.dusts, self.kinds, FABSORBED, ABU, self.rank, self.world, log=self.log, pol=self.pol,
-                                       keep_resident=keep_resident, download=download)
+                                       keep_resident=keep_resident, download=download, absorbed_scale=absorbed_scale)
         self.timers["emission_path"] = info["path"]            # 'device' (soc_mabu_*) or 'host'
         self.resident = info["resident"]
         self.R = info.get("R")
@@ -138,26 +145,60 @@ class Pipeline:
             return False
         return True
 
+    def open_absorbed(self, rt, N):
+        """The absorptions can stay on the device from the launches that tally them to stage 2 (engine.absorbed_*: held transposed, a
+        frequency's tally added to a contiguous row, scaled on their way into the rows of stage 2) where the engine has the calls, there
+        is one rank, no `nnmake` thinning, no `saveint` (the intensity file wants every tally on the host), stage 2 offers its device
+        path and the planes fit: one, with iterations a second for the constant sources' share.  Reserves them and returns the sink of
+        the transfer stage; None, with the condition that failed logged: the host array."""
+        why = "asked for (absorbed_source='host')" if self.absorbed_source == 'host' else rt.resident_absorptions_refused()
+        if not why and not hasattr(self.eng, "absorbed_to_mabu"):
+            why = "the engine has no absorbed_* calls"
+        if not why and not mabu.device_path_offered(self.eng, self.dusts, self.kinds, rt.NFREQ, self.pol):
+            why = "stage 2 does not offer its device path"
+        if not why:
+            try:
+                self.eng.absorbed_begin(rt.NFREQ, keep_constant=N > 0)
+            except DoesNotFit as err:
+                why = str(err)
+        if why:
+            self.log("driver: the absorptions go through the host: %s" % why)
+            return None
+        self.scale = (files.absorbed_scale_factors(rt.cloud, self.U.GL), self.U.NNNLIMIT)
+        return ResidentAbsorptions(self.eng, rt.cloud.CELLS, rt.NFREQ)
+
     def iterate(self, rt, k, N, CONSTANT, EMITTED, ABU, want):
         """Iteration k of N as a run of its own with `iterations 1`, `nosolve`, reading the emitted file of iteration k-1, and
         soc_amd.mabu on the absorbed file it writes: the emission of k-1 is sent from the cells at every simulated frequency, its
         absorptions join those of the constant sources, and the emission is solved from the sum.  The source of the launches is the
-        engine's resident copy where stage 2 left one (want, and the stage took the device path), else EMITTED on the host."""
+        engine's resident copy where stage 2 left one (want, and the stage took the device path), else EMITTED on the host.
+        CONSTANT a ResidentAbsorptions: the constant sources' share is the engine's second plane (absorbed_keep), the sum is made on
+        the device and stage 2 reads it there."""
         t0 = time.time()
         source = 'resident' if (want and self.resident) else 'host'
-        self.log("driver: iteration %d/%d takes the emission from the %s source" % (k, N, source))
-        FABSORBED = CONSTANT.copy() if k < N else CONSTANT
+        sink = isinstance(CONSTANT, ResidentAbsorptions)
+        self.log("driver: iteration %d/%d takes the emission from the %s source, the absorptions go through the %s"
+                 % (k, N, source, 'device' if sink else 'host'))
+        if sink:
+            self.eng.absorbed_restore()
+            FABSORBED = CONSTANT
+        else:
+            FABSORBED = CONSTANT.copy() if k < N else CONSTANT
         rt.simulate_cell_emission(EMITTED, FABSORBED, resident=source == 'resident')
-        files.scale_absorbed(FABSORBED, rt.cloud, self.U.GL, self.U.NNNLIMIT)
+        if not sink:
+            files.scale_absorbed(FABSORBED, rt.cloud, self.U.GL, self.U.NNNLIMIT)
         t1 = time.time()
         # (an emission that stays on the device is read back only after the last iteration, for the products; where stage 2 does not
         # leave it there -- its host path -- the array returned is filled whatever `download` says)
-        EMITTED = self.solve_emission(FABSORBED, ABU, keep_resident=want and k < N, download=k == N)
-        self.timers["iterations"].append(dict(transfer=t1 - t0, emission=time.time() - t1, source=source))
+        EMITTED = self.solve_emission(FABSORBED, ABU, keep_resident=want and k < N, download=k == N, absorbed_scale=self.scale if sink else None)
+        self.timers["iterations"].append(dict(transfer=t1 - t0, emission=time.time() - t1, source=source,
+                                              absorbed='resident' if sink else 'host'))
         return FABSORBED, EMITTED
 
     # ---- the three stages -----------------------------------------------------------------------------------------
-    def run(self, keep_files=False):
+    def run(self, keep_files=False, want_absorbed=True):
+        """Returns CTABS, FABSORBED (scaled, as the absorbed file holds it) and EMITTED.  want_absorbed=False: where the absorptions
+        stayed on the device they are not read back, and FABSORBED is None (keep_files reads them back for the file)"""
         U = self.U
         t0 = time.time()
         rt = AbsorptionRun(U, self.eng, self.comm, verbose=self.verbose)
@@ -166,28 +207,42 @@ class Pipeline:
         N = U.ITERATIONS if rt.CLPAC > 0 else 0                   # dust re-emission iterations
         if N > 0:
             rt.require_emission_at_every_frequency()               # (`remit` cutting frequencies, before minutes of transfer)
-        CTABS, FABSORBED = rt.simulate_constant_sources()
-        CONSTANT = FABSORBED.copy() if N > 0 else None             # the constant sources' absorptions, unscaled: every iteration adds to them
-        files.scale_absorbed(FABSORBED, rt.cloud, U.GL, U.NNNLIMIT)
-        self.timers["transfer"] = time.time() - t0
-        # abundances: the columns of the transfer run (ASOC_aux.py read_abundances), ones where no file is given
-        CELLS = rt.cloud.CELLS
-        ABU = mabu.abundance_table(rt.ABU, U.SINGLE_ABU, CELLS, len(self.dusts))
-        t0 = time.time()
-        want = N > 0 and self.open_resident(rt.NFREQ)
+        sink = self.open_absorbed(rt, N)
+        self.timers["absorbed_source"] = 'resident' if sink else 'host'
+        want = False
         try:
-            EMITTED = self.solve_emission(FABSORBED, ABU, keep_resident=want, download=N == 0)
+            CTABS, FABSORBED = rt.simulate_constant_sources(absorbed=sink)
+            if sink:
+                CONSTANT = sink                                    # (the second plane keeps the constant sources' share)
+                if N > 0:
+                    self.eng.absorbed_keep()
+            else:
+                CONSTANT = FABSORBED.copy() if N > 0 else None     # the constant sources' absorptions, unscaled: every iteration adds to them
+                files.scale_absorbed(FABSORBED, rt.cloud, U.GL, U.NNNLIMIT)
+            self.timers["transfer"] = time.time() - t0
+            # abundances: the columns of the transfer run (ASOC_aux.py read_abundances), ones where no file is given
+            CELLS = rt.cloud.CELLS
+            ABU = mabu.abundance_table(rt.ABU, U.SINGLE_ABU, CELLS, len(self.dusts))
+            t0 = time.time()
+            want = N > 0 and self.open_resident(rt.NFREQ)
+            EMITTED = self.solve_emission(FABSORBED, ABU, keep_resident=want, download=N == 0, absorbed_scale=self.scale if sink else None)
             self.timers["emission"] = time.time() - t0
             self.timers["iterations"] = []
             for k in range(1, N + 1):
                 FABSORBED, EMITTED = self.iterate(rt, k, N, CONSTANT, EMITTED, ABU, want)
+            if sink:                                               # read back once, scaled, and only where somebody wants them
+                FABSORBED = None
+                if want_absorbed or (keep_files and len(U.file_absorbed) > 0):
+                    FABSORBED = self.eng.absorbed_download(0, CELLS, *self.scale)
         finally:
             if want:
                 self.eng.emitted_end()
+            if sink:
+                self.eng.absorbed_end()
         if self.rank == 0:
             if len(U.file_emitted) > 0:
                 files.write_emitted(U.file_emitted, EMITTED)
-            if keep_files and len(U.file_absorbed) > 0:
+            if keep_files and len(U.file_absorbed) > 0 and FABSORBED is not None:
                 files.write_absorbed(U.file_absorbed, FABSORBED)
             if keep_files and self.R is not None and len(U.file_emitted) > 0:
                 mabu.write_reduction(U.file_emitted + '.R', self.R)
@@ -218,7 +273,8 @@ def main(argv=None):
     from .lib import Engine
     eng = Engine(comm.local_rank)
     try:
-        Pipeline(argv[1], eng, comm).run(keep_files="--keep-files" in argv)
+        keep = "--keep-files" in argv
+        Pipeline(argv[1], eng, comm).run(keep_files=keep, want_absorbed=keep)
     finally:
         eng.close()
         comm.close()

@@ -200,6 +200,12 @@ def scale_absorbed(FABSORBED, cloud, GL, nnnlimit=0.0, absthin=1):
     return FABSORBED
 
 
+def absorbed_scale_factors(cloud, GL):
+    """K[LEVELS] float32 with which scale_absorbed's statement is FABSORBED[c, :] * (K[level(c)] / DENS[c]) in float32: numpy rounds the
+    python float coeff of a level to float32 before it divides by the float32 densities (Engine.absorbed_to_mabu, absorbed_download)"""
+    return np.asarray([(8.0 ** level) * (FACTOR / (GL * PARSEC)) for level in range(cloud.LEVELS)], np.float32)
+
+
 def write_absorbed(filename, FABSORBED):
     """absorbed file: int32 CELLS,NFREQ; float32 [CELLS,NFREQ] (ASOC.py:2866-2875)"""
     FABSORBED = np.asarray(FABSORBED, np.float32)

@@ -161,6 +161,14 @@ API = {
     "soc_set_emission_column": (C.c_int, [C.c_void_p, C.c_int, _F]),
     "soc_read_emission": (C.c_int, [C.c_void_p, _F, C.c_int64]),
     "soc_emitted_end": (C.c_int, [C.c_void_p]),
+    "soc_absorbed_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "soc_absorbed_add_tally": (C.c_int, [C.c_void_p, C.c_int]),
+    "soc_absorbed_add_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "soc_absorbed_keep": (C.c_int, [C.c_void_p]),
+    "soc_absorbed_restore": (C.c_int, [C.c_void_p]),
+    "soc_absorbed_to_mabu": (C.c_int, [C.c_void_p, C.c_int64, _F, C.c_float]),
+    "soc_absorbed_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F, _F, C.c_float]),
+    "soc_absorbed_end": (C.c_int, [C.c_void_p]),
     "soc_library_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, _F, _F, _F, _F, _F, _F, _F, _F, C.c_int, _I]),
     "soc_library_solve": (C.c_int, [C.c_void_p, C.c_int64, _F, _F, _I, C.POINTER(C.c_int64)]),
     "soc_library_solve_resident": (C.c_int, [C.c_void_p, _I, _I, C.POINTER(C.c_int64)]),
@@ -192,7 +200,7 @@ class SocError(RuntimeError):
 
 class DoesNotFit(SocError):
     """mabu_begin: the cells do not fit the free device memory; cells_fit of them would.  emitted_begin: the resident emission does
-    not fit (cells_fit 0: it is held for all cells or not at all)"""
+    not fit (cells_fit 0: it is held for all cells or not at all); absorbed_begin: nor do the resident absorptions"""
 
     def __init__(self, text, cells_fit):
         SocError.__init__(self, text)
@@ -274,6 +282,7 @@ class Engine:
         self.LEVELS = 0
         self._mabu = None                                  # (cells, NFREQ, NDUST) between mabu_begin and mabu_end
         self._emitted = None                               # NFREQ between emitted_begin and emitted_end (set_grid ends it)
+        self._absorbed = None                              # NFREQ between absorbed_begin and absorbed_end (set_grid ends it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -304,6 +313,7 @@ class Engine:
         self.NPAR = self.CELLS - int(NX) * int(NY) * int(NZ)
         self.LEVELS = int(LEVELS)
         self._emitted = None
+        self._absorbed = None
 
     def set_cloud(self, cloud):
         self.set_grid(cloud.NX, cloud.NY, cloud.NZ, cloud.LEVELS, cloud.LCELLS, cloud.DENS)
@@ -1150,6 +1160,72 @@ class Engine:
     def emitted_end(self):
         self._chk(self.lib.soc_emitted_end(self.h))
         self._emitted = None
+
+    # ---- the absorptions of the transfer stage, resident for the multi-dust stage (soc_absorbed_*; driven by soc_amd.driver through
+    # AbsorptionRun.simulate_constant_sources / simulate_cell_emission and mabu.solve_emission) ----
+    def absorbed_begin(self, NFREQ, keep_constant=False):
+        """AT[NFREQ, CELLS] of the grid's cells, zeroed; keep_constant: also the second plane of absorbed_keep / absorbed_restore.
+        DoesNotFit where the free device memory does not take them (nothing is reserved)"""
+        if self.CELLS < 1:
+            raise SocError("absorbed_begin: call set_grid first")
+        rc = self.lib.soc_absorbed_begin(self.h, int(NFREQ), int(bool(keep_constant)))
+        if rc == -2:                                           # (arrays that are open stay as they are)
+            raise DoesNotFit("%s (code %d)" % (self.lib.soc_last_error(self.h).decode(), rc), 0)
+        self._chk(rc)
+        self._absorbed = int(NFREQ)
+
+    def _absorbed_open(self, who, K=None):
+        """the open absorbed_begin's NFREQ; K, where given, as the float32 [LEVELS] the library reads"""
+        if self._absorbed is None:
+            raise SocError("%s: call absorbed_begin first" % who)
+        if K is None:
+            return self._absorbed, None
+        K = np.ascontiguousarray(K, np.float32)
+        if K.ndim != 1 or K.size != self.LEVELS:
+            raise SocError("%s: K must hold LEVELS = %d floats" % (who, self.LEVELS))
+        return self._absorbed, K
+
+    def absorbed_add_tally(self, ifreq):
+        """AT[ifreq] += the INT tally (what read_tally(1) reads), on the device"""
+        self._absorbed_open("absorbed_add_tally")
+        self._chk(self.lib.soc_absorbed_add_tally(self.h, int(ifreq)))
+
+    def absorbed_add_slot(self, ifreq, k):
+        """AT[ifreq] += INT slot k of the ended batch (what batch_read_int(k) reads), on the device"""
+        self._absorbed_open("absorbed_add_slot")
+        self._chk(self.lib.soc_absorbed_add_slot(self.h, int(ifreq), int(k)))
+
+    def absorbed_keep(self):
+        self._absorbed_open("absorbed_keep")
+        self._chk(self.lib.soc_absorbed_keep(self.h))
+
+    def absorbed_restore(self):
+        self._absorbed_open("absorbed_restore")
+        self._chk(self.lib.soc_absorbed_restore(self.h))
+
+    def absorbed_to_mabu(self, c0, K, nnnlimit=0.0):
+        """all rows of the open mabu_begin from cells [c0, c0 + its cells), scaled as the absorbed file holds them: x K[level] / DENS,
+        -1e20 where DENS <= nnnlimit; K[LEVELS] float32 (files.absorbed_scale_factors)"""
+        if K is None:
+            raise SocError("absorbed_to_mabu: K must hold LEVELS = %d floats" % self.LEVELS)
+        _, K = self._absorbed_open("absorbed_to_mabu", K)
+        self._chk(self.lib.soc_absorbed_to_mabu(self.h, int(c0), _f(K), np.float32(nnnlimit)))
+
+    def absorbed_download(self, c0, n, K=None, nnnlimit=0.0, out=None):
+        """rows [c0, c0 + n) back as [n, NFREQ]: scaled as absorbed_to_mabu hands them over, or, with K None, bit for bit what was
+        accumulated; out: a writeable C-contiguous float32 array of that shape to fill"""
+        NFREQ, K = self._absorbed_open("absorbed_download", K)
+        if out is None:
+            out = np.zeros((max(int(n), 0), NFREQ), np.float32)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable
+                  and out.shape == (int(n), NFREQ)):
+            raise SocError("absorbed_download: out must be a writeable C-contiguous float32 array of shape (%d, %d)" % (int(n), NFREQ))
+        self._chk(self.lib.soc_absorbed_download(self.h, int(c0), int(n), _f(out), _f(K), np.float32(nnnlimit)))
+        return out
+
+    def absorbed_end(self):
+        self._chk(self.lib.soc_absorbed_end(self.h))
+        self._absorbed = None
 
     # ---- the library method for dust emission (soc_library_*; driven by soc_amd.library) ----
     LIBRARY_TABLES = ("I1", "dI1", "I2", "dI2", "X", "Y", "Z")

@@ -34,7 +34,7 @@ import numpy as np
 from scipy.interpolate import interp1d
 
 from . import a2e, files
-from .asoc import UnsupportedOption
+from .asoc import ResidentAbsorptions, UnsupportedOption
 from .ini import User
 from .launch import FACTOR
 from .lib import DoesNotFit
@@ -261,6 +261,12 @@ def offers_device_path(engine, kinds, tables, polarised=False):
         all(k == 'eqdust' or len(t["sizes"]) >= t["NSIZE"] for k, t in zip(kinds, tables))
 
 
+def device_path_offered(engine, dusts, kinds, NFREQ, pol=None):
+    """offers_device_path for a caller that has not read the tables: whether solve_emission will take its device path"""
+    polarised = pol is not None and any(p is not None for p in pol)
+    return offers_device_path(engine, kinds, _tables(dusts, kinds, NFREQ), polarised)
+
+
 def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, log, AALG=None, ptabs=None, PEM=None):
     n, NFREQ = FABS.shape
     for idust in range(len(dusts)):
@@ -289,11 +295,13 @@ def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, lo
 
 
 def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells, log, AALG=None, ptabs=None, R=None, resident_c0=None,
-                  download=True):
+                  download=True, absorbed=None):
     """the cells in ranges that fit the device (one range where all do): cells are independent, so this is a loop.  With AALG (per
     dust the minimum aligned sizes of these cells, or None) the two more resident arrays of the polarised emission are asked for,
     the rows of a dust's aalg follow the cell range, and R receives polarised / total.  resident_c0 (the model's cell of row 0): the
-    sum of every range also goes, device to device, to the engine's resident emission (emitted_begin); download=False: nowhere else."""
+    sum of every range also goes, device to device, to the engine's resident emission (emitted_begin); download=False: nowhere else.
+    absorbed = (c0, K, nnnlimit): FABS is the engine's resident absorptions (absorbed_begin), row 0 the model's cell c0, and every
+    range takes its rows from there, device to device, scaled on the way (absorbed_to_mabu), in place of the uploads."""
     n, NFREQ = FABS.shape
     NDUST = len(dusts)
 
@@ -316,7 +324,9 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
             log("  %s" % err)
             continue
         try:
-            for i in range(a, b, CHUNK):
+            if absorbed is not None:
+                engine.absorbed_to_mabu(absorbed[0] + a, absorbed[1], absorbed[2])
+            for i in range(a, b, CHUNK) if absorbed is None else ():
                 engine.mabu_upload(i - a, FABS[i:min(i + CHUNK, b)])
             engine.mabu_set_tables(ABU[a:b], RABS)
             for idust in range(NDUST):
@@ -359,9 +369,11 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
 
 
 def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, path=None, range_cells=None, log=None, pol=None,
-                   keep_resident=False, download=True):
+                   keep_resident=False, download=True, absorbed_scale=None):
     """Stage 2 of a multi-dust run for the cells a2e.cell_range(CELLS, rank, world) of this rank.  FABSORBED[CELLS, NFREQ] as the
-    absorbed file holds it (scaled, files.scale_absorbed; a memory map will do), ABU[CELLS, NDUST] float32.
+    absorbed file holds it (scaled, files.scale_absorbed; a memory map will do), ABU[CELLS, NDUST] float32.  Or FABSORBED a
+    ResidentAbsorptions -- the engine holds them unscaled (absorbed_begin) -- with absorbed_scale = (K[LEVELS], nnnlimit)
+    (files.absorbed_scale_factors): the device path alone, which scales them on their way to its rows.
     Returns (EM[c1 - c0, NFREQ], info) with info["path"] 'device' or 'host' and info["ranges"], the number of cell ranges.
     path: None = the device path where the engine offers it, or 'device' / 'host' to insist (tests, measurements);
     range_cells: an upper limit for the cells resident at a time (default: what the free device memory takes);
@@ -384,13 +396,17 @@ def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, pat
     if path not in (None, 'device', 'host') or (path == 'device' and not offered):
         raise ValueError("solve_emission: path %r is not available with this engine and these solver files" % (path,))
     device = offered if path is None else path == 'device'
+    from_resident = isinstance(FABSORBED, ResidentAbsorptions)
+    if from_resident and (not device or absorbed_scale is None):
+        raise ValueError("solve_emission: the resident absorptions need the device path and absorbed_scale = (K, nnnlimit)")
     EM = np.zeros((c1 - c0, NFREQ), np.float32)
     R = np.zeros((c1 - c0, NFREQ), np.float32) if AALG else None
     ranges = 0
     resident = bool(keep_resident) and device and c1 > c0
     if c1 > c0 and device:
-        ranges = _solve_device(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, EM, range_cells, log, AALG, ptabs, R,
-                               resident_c0=c0 if resident else None, download=download or not resident)
+        ranges = _solve_device(engine, dusts, kinds, tables, ResidentAbsorptions(engine, c1 - c0, NFREQ) if from_resident else FABSORBED[c0:c1],
+                               ABU[c0:c1], RABS, EM, range_cells, log, AALG, ptabs, R, resident_c0=c0 if resident else None,
+                               download=download or not resident, absorbed=(c0,) + tuple(absorbed_scale) if from_resident else None)
     elif c1 > c0:
         ranges = _solve_host(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, c0, CELLS, EM, log, AALG, ptabs, R)
         if AALG:
