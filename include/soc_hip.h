@@ -713,6 +713,25 @@ int soc_set_emission_column(soc_ctx *ctx, int ifreq, const float *COEFF);
 int soc_read_emission(soc_ctx *ctx, float *EMIT, int64_t n);
 int soc_emitted_end(soc_ctx *ctx);
 
+/* How much the resident emission changed since the iteration before: what a convergence criterion of the iterations needs, in one pass
+ * over ET (4 NFREQ + 16 bytes per cell) and without a second ET -- the frequency-integrated luminosity of every cell is kept instead:
+ *   soc_emitted_change(W, COEFF, stats, bad): for every cell B = sum_f (double)ET[f][c] * W[f], in double with f ascending, every product
+ *       and every sum rounded (no fused multiply-add); W[NFREQ] doubles, the integration weights (launch.trapezoid_weight).
+ *       L[c] = B * (double)(float)(COEFF[level(c)] * DENS[c]), the float product of soc_set_emission_column, COEFF[LEVELS] as there;
+ *       L[c] = 0 where DENS[c] < 1e-10 (links, empty cells), by selection, whatever the row holds; a live cell whose L is negative or not
+ *       finite is counted in *bad and gives 0.  With Lp the plane the call before left (all zero after soc_emitted_begin):
+ *       stats[0] = sum |L - Lp|, stats[1] = sum L, stats[2] = sum Lp, stats[3] = max |L - Lp| / max(L, Lp) over the cells where
+ *       max(L, Lp) > 0 (0 without such a cell).  L then replaces Lp.  One lane per cell, a block's partials reduced in a fixed order and
+ *       the blocks' by one workgroup in a fixed order: the same bits on every run and every device.  The plane (8 CELLS bytes) and the
+ *       scratch are reserved at the first call after soc_emitted_begin; where they do not fit the free device memory (1 GB kept back, as
+ *       soc_emitted_begin) the call fails with SOC_ERR_STATE, the size in GB in the message, and nothing is reserved.
+ *       soc_emitted_begin, soc_emitted_end, soc_set_grid and soc_destroy release them;
+ *   soc_emitted_read_luminosity(c0, n, L) reads L of cells [c0, c0+n) as the last soc_emitted_change left it, zeros before the first (tests).
+ * Both are SOC_ERR_STATE before soc_emitted_begin, SOC_ERR_ARG for a NULL argument or cells outside the grid.  A refused call leaves ET and
+ * Lp as they were. */
+int soc_emitted_change(soc_ctx *ctx, const double *W, const float *COEFF, double stats[4], int64_t *bad);
+int soc_emitted_read_luminosity(soc_ctx *ctx, int64_t c0, int64_t n, double *L);
+
 /* ---- the absorptions of the transfer stage, RESIDENT between the launches that tally them and the multi-dust stage ---- */
 
 /* The mirror image of the above.  A launch leaves the absorptions of one frequency as an INT tally of CELLS floats; the multi-dust stage

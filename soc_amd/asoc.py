@@ -139,6 +139,11 @@ def _check_supported(USER, NDUST, WITH_MSF, engine=None):
     if USER.LIB_MAPS and getattr(USER, "MAP_LEVELS", 0) > 0:
         bad.append("libmaps with maplevels (the per-level maps go through the batch path, libmaps through the plain one: ASOC.py:127 "
                    "sets FAST_MAP = 0)")
+    # `convergence eps [kmin]` (not a key of the reference) is the criterion of soc_amd.driver's loop, which takes it off the ini it hands
+    # to its transfer run; this program's own iterations solve temperatures and have none
+    if getattr(USER, "CONVERGENCE", -1.0) >= 0.0 and USER.ITERATIONS > 0 and USER.CLPAC > 0:
+        bad.append("convergence with iterations > 0 and cellpackets in this program (its temperature loop has no convergence criterion: "
+                   "the key ends the dust re-emission iterations of soc_amd.driver)")
     if USER.MAP_INTERPOLATION > 2 or USER.MAP_INTERPOLATION < 0:
         bad.append("mapint other than 0, 1, 2 (kernel_ASOC_map.c:656-810 knows those: a larger value leaves Adens, Aemit ... unset there)")
     if len(USER.kernel_defs.strip()) > 0:

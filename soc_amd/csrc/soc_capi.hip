@@ -278,7 +278,7 @@ int soc_set_grid(soc_ctx *c, int NX, int NY, int NZ, int LEVELS, const int32_t *
     HIPCHK(c, hipMemsetAsync(c->dPAR, 0, (size_t)(c->npar ? c->npar : 1) * 4, c->stream));
     G.DENS = c->dDENS;
     G.PAR = c->dPAR;
-    c->eET.release();  c->eRows.release();  c->et_nfreq = 0;   // (the resident emission belongs to the model it was solved for)
+    c->eET.release();  c->eRows.release();  c->release_change();  c->et_nfreq = 0;   // (the resident emission belongs to the model it was solved for)
     c->bAT.release();  c->bAC.release();  c->bRows.release();  c->at_nfreq = 0;  c->ac_kept = false;    // (and so do the absorptions)
     if ((int64_t)G.CELLS != c->G.CELLS || !c->have_grid) {
         // tallies follow the cell count

@@ -1,5 +1,6 @@
 // soc_capi_reemit.hip -- host side of libsoc_hip.so: the emission of one re-emission iteration, resident and transposed for the
-// cell-emission launches of the next (soc_emitted_*, soc_set_emission_column, soc_read_emission; kernels: soc_reemit.hip).
+// cell-emission launches of the next, and its change from one iteration to the next (soc_emitted_*, soc_set_emission_column,
+// soc_read_emission; kernels: soc_reemit.hip).
 #include "soc_host.h"
 
 #include <algorithm>
@@ -31,11 +32,12 @@ int soc_emitted_begin(soc_ctx *c, int NFREQ)
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
     const size_t n = (size_t)c->G.CELLS * (size_t)NFREQ, reserve = (size_t)1 << 30;
-    const size_t held = (c->eET ? c->eET.bytes() : 0) + (c->eRows ? c->eRows.bytes() : 0);      // (an open one is replaced: its memory counts as free)
+    const size_t held = (c->eET ? c->eET.bytes() : 0) + (c->eRows ? c->eRows.bytes() : 0) + (c->eLp ? c->eLp.bytes() : 0)
+                        + (c->eChange ? c->eChange.bytes() : 0);                                  // (an open one is replaced: its memory counts as free)
     if (n * 4 + reserve > free_b + held)                        // refused before anything changes: an open one stays as it is
         return fail(c, SOC_ERR_STATE, "soc_emitted_begin: %d cells x %d frequencies need %.1f GB of device memory, %.1f GB are free "
                                       "(the emission of an iteration goes through the host instead)", c->G.CELLS, NFREQ, n * 4e-9, free_b * 1e-9);
-    c->eRows.release();  c->et_nfreq = 0;
+    c->eRows.release();  c->release_change();  c->et_nfreq = 0;
     hipError_t e = c->eET.reset(n, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->eET, 0, n * 4, c->stream);
     if (e != hipSuccess) {
@@ -125,12 +127,65 @@ int soc_read_emission(soc_ctx *c, float *EMIT, int64_t n)
     return SOC_OK;
 }
 
+int soc_emitted_change(soc_ctx *c, const double *W, const float *COEFF, double stats[4], int64_t *bad)
+{
+    if (!c) return SOC_ERR_ARG;
+    EMITTED_OPEN(c, "soc_emitted_change");
+    if (!W || !COEFF || !stats || !bad)
+        return fail(c, SOC_ERR_ARG, "soc_emitted_change: %s is NULL", !W ? "W" : !COEFF ? "COEFF" : !stats ? "stats" : "bad");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)c->G.CELLS, nfreq = (size_t)c->et_nfreq;
+    const size_t blocks = (size_t)soc_emitted_change_blocks(c->G.CELLS), scratch = nfreq + 4 + 4 * blocks;
+    if (!c->eLp) {                                              // the first call since soc_emitted_begin: the plane, zeroed, and the scratch
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        const size_t need = 8 * (cells + scratch + 1), reserve = (size_t)1 << 30;
+        if (need + reserve > free_b)                            // refused before anything changes
+            return fail(c, SOC_ERR_STATE, "soc_emitted_change: the luminosities of %d cells need %.3f GB of device memory, %.1f GB are free",
+                        c->G.CELLS, need * 1e-9, free_b * 1e-9);
+        hipError_t e = c->eLp.reset(cells, c->stream);
+        if (e == hipSuccess) e = c->eChange.reset(scratch, c->stream);
+        if (e == hipSuccess) e = c->eBad.reset(1, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(c->eLp, 0, cells * 8, c->stream);
+        if (e != hipSuccess) {
+            c->release_change();
+            return fail(c, SOC_ERR_HIP, "soc_emitted_change: %s", hipGetErrorString(e));
+        }
+    }
+    double *dW = c->eChange, *dStats = dW + nfreq, *dPart = dStats + 4;
+    unsigned long long nbad = 0;
+    HIPCHK(c, hipMemcpyAsync(dW, W, nfreq * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->eBad, 0, 8, c->stream));
+    HIPCHK(c, soc_launch_emitted_change(c->G, c->et_nfreq, COEFF, c->eET, dW, c->eLp, dPart, dStats, c->eBad, c->stream));
+    HIPCHK(c, hipMemcpyAsync(stats, dStats, 4 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&nbad, c->eBad, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *bad = (int64_t)nbad;
+    return SOC_OK;
+}
+
+int soc_emitted_read_luminosity(soc_ctx *c, int64_t c0, int64_t n, double *L)
+{
+    if (!c || !L) return SOC_ERR_ARG;
+    EMITTED_OPEN(c, "soc_emitted_read_luminosity");
+    EMITTED_ROWS(c, "soc_emitted_read_luminosity", c0, n);
+    if (!c->eLp) {                                              // no soc_emitted_change since soc_emitted_begin: all zero
+        std::fill(L, L + n, 0.0);
+        return SOC_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(L, c->eLp + c0, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SOC_OK;
+}
+
 int soc_emitted_end(soc_ctx *c)
 {
     if (!c) return SOC_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->eET.release();  c->eRows.release();  c->et_nfreq = 0;
+    c->eET.release();  c->eRows.release();  c->release_change();  c->et_nfreq = 0;
     return SOC_OK;
 }
 

@@ -283,6 +283,12 @@ hipError_t soc_launch_mabu_ratio(long long cells, int NFREQ, const float *SUM, f
 hipError_t soc_launch_reemit_to_columns(long long n, int NFREQ, long long CELLS, long long c0, const float *ROWS, float *ET, hipStream_t st);
 hipError_t soc_launch_reemit_to_rows(long long n, int NFREQ, long long CELLS, long long c0, const float *ET, float *ROWS, hipStream_t st);
 hipError_t soc_launch_reemit_column(const SocGrid &G, const float *COEFF, const float *COL, float *EMIT, hipStream_t st);
+// the change of the resident emission between two iterations (soc_reemit.hip): L[c] = (sum_f (double)ET[f][c] * W[f]) * (double)(COEFF[level]
+// * DENS[c]) replaces LP[c]; STATS = sum |L - LP|, sum L, sum LP, max |L - LP| / max(L, LP); BAD += the live cells whose L is negative or
+// not finite.  PART: soc_emitted_change_blocks(CELLS) x 4 doubles of scratch.  W, LP, PART, STATS, BAD on the device, COEFF on the host
+long long soc_emitted_change_blocks(long long CELLS);
+hipError_t soc_launch_emitted_change(const SocGrid &G, int NFREQ, const float *COEFF, const float *ET, const double *W, double *LP, double *PART,
+                                     double *STATS, unsigned long long *BAD, hipStream_t st);
 // the resident absorptions, their mirror image (soc_reemit.hip): ROW[c] += TALLY[c] over CELLS cells, and the same tile walk from
 // AT[NFREQ][CELLS] to ROWS[n][NFREQ] with ROWS[c][f] = AT[f][c0+c] * (K[level] / DENS), -1e20 where DENS <= nnnlimit (K: LEVELS host
 // floats; NULL: the bits as they are)

@@ -133,6 +133,11 @@ struct soc_ctx {
     // contiguous row; eRows stages the rows of an upload or a download.  soc_set_grid releases both
     DevBuf<float> eET, eRows;
     int     et_nfreq = 0;              // 0: not open
+    // soc_emitted_change, reserved at its first call after soc_emitted_begin: the luminosities L[CELLS] of the call before, its scratch
+    // (W[et_nfreq] | STATS[4] | the partials [blocks][4]) and the count of bad cells.  Released wherever eET is (release_change)
+    DevBuf<double> eLp, eChange;
+    DevBuf<unsigned long long> eBad;
+    void release_change() { eLp.release();  eChange.release();  eBad.release(); }
     // the resident absorptions, their mirror image (soc_absorbed_*): AT[at_nfreq][CELLS], a frequency's INT tally added to its row;
     // bAC a second plane of the same size (soc_absorbed_keep / _restore: the constant sources' share), bRows stages a download.
     // soc_set_grid releases all three

@@ -1,4 +1,5 @@
-// soc_reemit.hip -- the dust emission of one iteration, resident for the next one's cell-emission launches (soc_emitted_*).
+// soc_reemit.hip -- the dust emission of one iteration, resident for the next one's cell-emission launches (soc_emitted_*), and how
+// much it changed since the iteration before (soc_emitted_change_kernel, further down).
 //
 // The emission leaves the multi-dust stage as SUM[cell][frequency], row-major like the emitted file; SimRAM_CL wants, per frequency,
 // EMIT[CELLS].  A column of the row-major array costs a 128-byte line per useful 4 bytes, at every one of NFREQ launches, so the
@@ -115,6 +116,101 @@ __global__ __launch_bounds__(REEMIT_T) void soc_absorbed_add_kernel(long long CE
         ROW[i] = ROW[i] + TALLY[i];
 }
 
+// The change of the emission between two iterations (soc_emitted_change), one pass over ET[NFREQ][CELLS].  One lane per cell, no
+// grid-stride loop: the grid, and with it the order of every sum, is a function of CELLS alone.  The lane walks its cell down the rows --
+// a wave reads 256 contiguous bytes per row, one word per lane (a row starts on no 16-byte boundary unless CELLS is a multiple of 4, see
+// soc_absorbed_add_kernel) -- CHANGE_U rows loaded before the first is used, and accumulates B = sum_f (double)E[c][f] * W[f] in double
+// with f ascending, every product and every sum rounded (-ffp-contract=off).  L = B * (double)(float)(COEFF[level] * DENS), the float
+// product of soc_reemit_column_kernel; 0 by selection in a link or an empty cell (DENS < 1e-10) whatever its row holds; a live cell
+// whose L is negative or not finite counts into BAD and gives 0.  LP[c] is read and replaced by L.  Per block four partials --
+// sum |L - LP|, sum L, sum LP, max |L - LP| / max(L, LP) -- reduced in a fixed order: within a wave lane i takes lane i + 32, 16 .. 1,
+// then thread 0 takes the waves in their order through LDS.  PART[block][4].
+#define CHANGE_T 256            // cells of a block
+#define CHANGE_U 8              // rows in flight per lane
+
+__device__ __forceinline__ double change_wave_sum(double v)
+{
+    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ double change_wave_max(double v)
+{
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+    return v;
+}
+
+__global__ __launch_bounds__(CHANGE_T) void soc_emitted_change_kernel(long long CELLS, int NFREQ, SocReemitLevels L, const float *__restrict__ DENS,
+                                                                      const float *__restrict__ ET, const double *__restrict__ W,
+                                                                      double *__restrict__ LP, double *__restrict__ PART,
+                                                                      unsigned long long *__restrict__ BAD)
+{
+    __shared__ double red[4][CHANGE_T / 64];
+    const long long c = (long long)blockIdx.x * CHANGE_T + threadIdx.x;
+    double s_abs = 0.0, s_new = 0.0, s_old = 0.0, m = 0.0;
+    bool bad = false;
+    if (c < CELLS) {
+        const float *col = ET + c;
+        double B = 0.0;
+        int f = 0;
+        for (; f + CHANGE_U <= NFREQ; f += CHANGE_U) {
+            float e[CHANGE_U];
+#pragma unroll
+            for (int u = 0; u < CHANGE_U; u++) e[u] = col[(size_t)(f + u) * (size_t)CELLS];
+#pragma unroll
+            for (int u = 0; u < CHANGE_U; u++) B = B + (double)e[u] * W[f + u];
+        }
+        for (; f < NFREQ; f++) B = B + (double)col[(size_t)f * (size_t)CELLS] * W[f];
+        const float d = DENS[c];
+        const float w = L.COEFF[reemit_level(L, (int)c)] * d;
+        const double lum = B * (double)w;
+        const bool dead = d < 1.0e-10f;
+        const bool fine = (lum >= 0.0) && (lum <= 1.7976931348623157e308);       // (false for a NaN)
+        bad = !dead && !fine;
+        const double l = (dead || !fine) ? 0.0 : lum;
+        const double lp = LP[c];
+        LP[c] = l;
+        const double diff = fabs(l - lp), top = fmax(l, lp);
+        s_abs = diff;  s_new = l;  s_old = lp;
+        m = (top > 0.0) ? diff / top : 0.0;
+    }
+    const unsigned long long nbad = __popcll(__ballot(bad));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0 && nbad) atomicAdd(BAD, nbad);
+    s_abs = change_wave_sum(s_abs);  s_new = change_wave_sum(s_new);  s_old = change_wave_sum(s_old);  m = change_wave_max(m);
+    if (lane == 0) { red[0][wave] = s_abs;  red[1][wave] = s_new;  red[2][wave] = s_old;  red[3][wave] = m; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < CHANGE_T / 64; k++) {
+            s_abs = s_abs + red[0][k];  s_new = s_new + red[1][k];  s_old = s_old + red[2][k];  m = fmax(m, red[3][k]);
+        }
+        double *out = PART + (size_t)blockIdx.x * 4;
+        out[0] = s_abs;  out[1] = s_new;  out[2] = s_old;  out[3] = m;
+    }
+}
+
+// STATS[4] from PART[blocks][4], one workgroup: thread t takes the blocks t, t + CHANGE_T, ... in ascending order, then the threads
+// combine as the lanes and waves of the first kernel do -- an order that depends on `blocks` alone.
+__global__ __launch_bounds__(CHANGE_T) void soc_emitted_change_final_kernel(long long blocks, const double *__restrict__ PART, double *__restrict__ STATS)
+{
+    __shared__ double red[4][CHANGE_T / 64];
+    double s_abs = 0.0, s_new = 0.0, s_old = 0.0, m = 0.0;
+    for (long long b = threadIdx.x; b < blocks; b += CHANGE_T) {
+        const double *p = PART + (size_t)b * 4;
+        s_abs = s_abs + p[0];  s_new = s_new + p[1];  s_old = s_old + p[2];  m = fmax(m, p[3]);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    s_abs = change_wave_sum(s_abs);  s_new = change_wave_sum(s_new);  s_old = change_wave_sum(s_old);  m = change_wave_max(m);
+    if (lane == 0) { red[0][wave] = s_abs;  red[1][wave] = s_new;  red[2][wave] = s_old;  red[3][wave] = m; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < CHANGE_T / 64; k++) {
+            s_abs = s_abs + red[0][k];  s_new = s_new + red[1][k];  s_old = s_old + red[2][k];  m = fmax(m, red[3][k]);
+        }
+        STATS[0] = s_abs;  STATS[1] = s_new;  STATS[2] = s_old;  STATS[3] = m;
+    }
+}
+
 template <bool TO_ROWS, typename Op>
 static hipError_t reemit_transpose(long long n, int NFREQ, long long CELLS, long long c0, float *ROWS, float *ET, const Op &op, hipStream_t st)
 {
@@ -166,5 +262,20 @@ hipError_t soc_launch_reemit_column(const SocGrid &G, const float *COEFF, const 
     const SocReemitLevels L = reemit_levels(G, COEFF);
     const long long blocks = ((long long)G.CELLS + REEMIT_T - 1) / REEMIT_T;
     soc_reemit_column_kernel<<<(int)(blocks < 16384 ? blocks : 16384), REEMIT_T, 0, st>>>(G.CELLS, L, G.DENS, COL, EMIT);
+    return hipGetLastError();
+}
+
+long long soc_emitted_change_blocks(long long CELLS) { return (CELLS + CHANGE_T - 1) / CHANGE_T; }
+
+hipError_t soc_launch_emitted_change(const SocGrid &G, int NFREQ, const float *COEFF, const float *ET, const double *W, double *LP, double *PART,
+                                     double *STATS, unsigned long long *BAD, hipStream_t st)
+{
+    if (G.CELLS < 1 || G.LEVELS < 1 || G.LEVELS > SOC_MAXL || NFREQ < 1 || !COEFF || !ET || !W || !LP || !PART || !STATS || !BAD) return hipErrorInvalidValue;
+    const SocReemitLevels L = reemit_levels(G, COEFF);
+    const long long blocks = soc_emitted_change_blocks(G.CELLS);
+    soc_emitted_change_kernel<<<(unsigned)blocks, CHANGE_T, 0, st>>>(G.CELLS, NFREQ, L, G.DENS, ET, W, LP, PART, BAD);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    soc_emitted_change_final_kernel<<<1, CHANGE_T, 0, st>>>(blocks, PART, STATS);
     return hipGetLastError();
 }

@@ -35,7 +35,12 @@ between the iterations: stage 2 leaves it transposed, ET[NFREQ][CELLS], and ever
 row (soc_set_emission_column); otherwise it goes through the host array and soc_set_emission, with the same bits.  The absorptions
 stay there as well, with or without iterations, where the engine has the soc_absorbed_* calls, there is one rank, no `saveint` and
 stage 2 offers its device path: every INT tally is added to its row of AT[NFREQ][CELLS], a second plane keeps the constant sources'
-share, and stage 2 takes its rows from there scaled with the bits of files.scale_absorbed (open_absorbed).  Refused with
+share, and stage 2 takes its rows from there scaled with the bits of files.scale_absorbed (open_absorbed).  `convergence eps [kmin]`
+(not a key of the reference, which has no criterion: N is what the ini says) ends the loop after the first step k >= kmin whose
+luminosity-weighted relative change of the emission d_l1 (soc_amd.converge) is below eps; the products are then those of `iterations k`,
+the figures of every step go to convergence.dat, timers["convergence"] and the log, and `converged` is the step or None.  The figures
+come from the resident emission (engine.emitted_change: one pass, one plane of CELLS doubles kept) where the step left it there, else
+from the host array.  Refused with
 iterations: `ali` (the escape probability feeds a temperature solve that this pipeline does not do), `reference` (the reference field
 needs the previous emission and its absorptions carried across the iterations) and a `remit` that cuts frequencies.
 """
@@ -44,7 +49,7 @@ import time
 
 import numpy as np
 
-from . import a2e, files, mabu
+from . import a2e, converge, files, launch, mabu
 from .asoc import AbsorptionRun, ResidentAbsorptions, UnsupportedOption
 from .ini import User
 from .lib import DoesNotFit
@@ -96,6 +101,10 @@ class Pipeline:
                                         "soc_amd.asoc per iteration")
         mabu.require_solvers(self.dusts, self.kinds)
         U.NOABSORBED, U.NOMAP, U.NOSOLVE = 0, 1, 1            # rt_simple.ini: absorptions per frequency, nomap, nosolve
+        # `convergence eps [kmin]` is this loop's key: the transfer run refuses it (its own temperature loop has no criterion) and gets none
+        self.eps, self.kmin = float(U.CONVERGENCE), int(U.CONVERGENCE_MIN)
+        U.CONVERGENCE = -1.0
+        self.converged = None                                  # the step the iterations were ended at by the criterion
         self.verbose = U.VERBOSE if verbose is None else verbose
         self.timers = {}
 
@@ -115,6 +124,7 @@ class Pipeline:
                                        keep_resident=keep_resident, download=download, absorbed_scale=absorbed_scale)
         self.timers["emission_path"] = info["path"]            # 'device' (soc_mabu_*) or 'host'
         self.resident = info["resident"]
+        self.on_host = download or not self.resident           # whether the array returned is filled
         self.R = info.get("R")
         if not (self.comm and self.world > 1):
             return em
@@ -167,13 +177,51 @@ class Pipeline:
         self.scale = (files.absorbed_scale_factors(rt.cloud, self.U.GL), self.U.NNNLIMIT)
         return ResidentAbsorptions(self.eng, rt.cloud.CELLS, rt.NFREQ)
 
-    def iterate(self, rt, k, N, CONSTANT, EMITTED, ABU, want):
+    # ---- `convergence eps [kmin]` ----------------------------------------------------------------------------------------
+    def measure(self, rt, k, EMITTED, want):
+        """The change of the emission of step k against step k-1 (soc_amd.converge): from the engine's resident copy where the step
+        left it there and the engine has emitted_change, else from EMITTED on the host (read back where it is not there: an engine
+        whose plane of luminosities does not fit).  Appends to timers["convergence"] and to convergence.dat, logs a line and returns
+        (whether the criterion ends the iterations after this step, EMITTED).  With several ranks every rank holds the whole emission
+        and finds the same figures; they act on rank 0's decision all the same, so that none is left alone in a collective."""
+        t0 = time.time()
+        c = rt.cloud
+        W = np.asarray([launch.trapezoid_weight(rt.FFREQ, f) for f in range(rt.NFREQ)], np.float64)
+        COEFF = np.asarray([self.U.GL * launch.PARSEC / (8.0 ** level) / launch.FACTOR for level in range(c.LEVELS)], np.float32)
+        stats = None
+        if want and self.resident and not self.host_every:
+            try:
+                stats, source = self.eng.emitted_change(W, COEFF), 'resident'
+            except DoesNotFit as err:                              # (at the first call or never: the plane stays reserved)
+                self.log("  %s: the figures of `convergence` come from the host array, which every iteration now reads back" % err)
+                self.host_every = True
+        if stats is None:
+            if not self.on_host:
+                EMITTED, self.on_host = self.eng.emitted_download(0, c.CELLS), True
+            L, bad = converge.luminosity(EMITTED, W, c.DENS, c.OFF, c.LCELLS, COEFF)
+            stats, source = converge.change(L, np.zeros_like(L) if self.Lp is None else self.Lp), 'host'
+            stats["bad"], self.Lp = bad, L
+        fig = converge.figures(stats)
+        stop = k >= max(1, self.kmin) and 0.0 < self.eps and fig["d_l1"] < self.eps       # (step 0 primes Lp: its d_l1 is 1, no decision)
+        if self.comm and self.world > 1:
+            stop = bool(self.comm.all_reduce_host(np.asarray([1.0 if (stop and self.rank == 0) else 0.0]))[0] > 0.0)
+        self.timers["convergence"].append(dict(k=k, bad=stats["bad"], source=source, seconds=time.time() - t0, **fig))
+        if self.rank == 0:
+            with open("convergence.dat", "w" if k == 0 else "a") as fp:
+                fp.write("%d %.17e %.17e %.17e\n" % (k, fig["d_l1"], fig["d_total"], fig["d_max"]))
+        self.log("driver: convergence step %d (%s): d_l1 %.4e  d_total %.4e  d_max %.4e%s%s"
+                 % (k, source, fig["d_l1"], fig["d_total"], fig["d_max"], "  (%d cells with a negative or non-finite luminosity count as 0)"
+                    % stats["bad"] if stats["bad"] else "", "  < eps %.4e: the iterations end here" % self.eps if stop else ""))
+        return stop, EMITTED
+
+    def iterate(self, rt, k, N, CONSTANT, EMITTED, ABU, want, conv=False):
         """Iteration k of N as a run of its own with `iterations 1`, `nosolve`, reading the emitted file of iteration k-1, and
         soc_amd.mabu on the absorbed file it writes: the emission of k-1 is sent from the cells at every simulated frequency, its
         absorptions join those of the constant sources, and the emission is solved from the sum.  The source of the launches is the
         engine's resident copy where stage 2 left one (want, and the stage took the device path), else EMITTED on the host.
         CONSTANT a ResidentAbsorptions: the constant sources' share is the engine's second plane (absorbed_keep), the sum is made on
-        the device and stage 2 reads it there."""
+        the device and stage 2 reads it there.  conv (`convergence`): no step knows that it is the last, so the emission of every
+        step stays resident where it can and is read back by run() once the loop has ended (every step only with host_every)."""
         t0 = time.time()
         source = 'resident' if (want and self.resident) else 'host'
         sink = isinstance(CONSTANT, ResidentAbsorptions)
@@ -190,7 +238,8 @@ class Pipeline:
         t1 = time.time()
         # (an emission that stays on the device is read back only after the last iteration, for the products; where stage 2 does not
         # leave it there -- its host path -- the array returned is filled whatever `download` says)
-        EMITTED = self.solve_emission(FABSORBED, ABU, keep_resident=want and k < N, download=k == N, absorbed_scale=self.scale if sink else None)
+        EMITTED = self.solve_emission(FABSORBED, ABU, keep_resident=want and (k < N or conv), download=self.host_every if conv else k == N,
+                                      absorbed_scale=self.scale if sink else None)
         self.timers["iterations"].append(dict(transfer=t1 - t0, emission=time.time() - t1, source=source,
                                               absorbed='resident' if sink else 'host'))
         return FABSORBED, EMITTED
@@ -225,11 +274,35 @@ class Pipeline:
             ABU = mabu.abundance_table(rt.ABU, U.SINGLE_ABU, CELLS, len(self.dusts))
             t0 = time.time()
             want = N > 0 and self.open_resident(rt.NFREQ)
-            EMITTED = self.solve_emission(FABSORBED, ABU, keep_resident=want, download=N == 0, absorbed_scale=self.scale if sink else None)
+            conv = N > 0 and self.eps >= 0.0                       # `convergence`: the figures after every step, k = 0 .. N
+            # ... which come from the resident emission; the host array is filled at every step only where something needs it there
+            self.host_every, self.Lp = False, None
+            if conv and want and not hasattr(self.eng, "emitted_change"):
+                self.host_every = True
+                self.log("driver: the engine has no emitted_change: with `convergence` every iteration reads its emission back")
+            elif conv and want and self.pol is not None:
+                self.host_every = True
+                self.log("driver: `polarisation` lines with `convergence`: every iteration reads its emission and R back (any step may be the last)")
+            EMITTED = self.solve_emission(FABSORBED, ABU, keep_resident=want, download=N == 0 or self.host_every,
+                                          absorbed_scale=self.scale if sink else None)
             self.timers["emission"] = time.time() - t0
             self.timers["iterations"] = []
+            stop = False
+            if conv:
+                self.timers["convergence"] = []
+                stop, EMITTED = self.measure(rt, 0, EMITTED, want)
             for k in range(1, N + 1):
-                FABSORBED, EMITTED = self.iterate(rt, k, N, CONSTANT, EMITTED, ABU, want)
+                FABSORBED, EMITTED = self.iterate(rt, k, N, CONSTANT, EMITTED, ABU, want, conv)
+                if conv:
+                    stop, EMITTED = self.measure(rt, k, EMITTED, want)
+                    if stop:
+                        self.converged = k
+                        break
+            if conv and not stop and self.eps > 0.0:
+                self.log("driver: convergence: %d iterations done and d_l1 = %.4e is not below eps = %.4e"
+                         % (N, self.timers["convergence"][-1]["d_l1"], self.eps))
+            if not self.on_host:                                   # (`convergence` on the resident source: read back once, now)
+                EMITTED = self.eng.emitted_download(0, CELLS)
             if sink:                                               # read back once, scaled, and only where somebody wants them
                 FABSORBED = None
                 if want_absorbed or (keep_files and len(U.file_absorbed) > 0):

@@ -144,6 +144,8 @@ class User:
         s.OUT_NSIDE = 128
         s.MAP_INTERPOLATION = 0
         s.MAP_LEVELS = 0                 # `maplevels N` (not a key of the reference): N > 0 adds map_dir_XX_L.bin, the plain map split by hierarchy level
+        s.CONVERGENCE = -1.0             # `convergence eps [kmin]` (not a key of the reference): soc_amd.driver ends the dust re-emission iterations
+        s.CONVERGENCE_MIN = 1            # after step k >= kmin once the luminosity-weighted relative change d_l1 < eps; eps 0 reports only; < 0 = off
         s.LIB_ABS = False                # `libabs file`: simulate the frequencies listed in the file only (the library method)
         s.LIB_MAPS = False               # `libmaps file`: maps of those frequencies from an emitted file that holds only them
         s.FSELECT = np.zeros(0, np.float64)
@@ -332,6 +334,17 @@ def _polmap(u, s):
         u.MINLOS, u.MAXLOS = float(s[4]), float(s[5])
 
 
+def _convergence(u, s):
+    """`convergence eps [kmin]` (soc_amd.converge, soc_amd.driver)"""
+    try:
+        eps, kmin = float(s[1]), int(s[2]) if len(s) > 2 else 1
+    except ValueError:
+        raise IniError("convergence eps [kmin]: a number and an integer are needed: %r" % " ".join(s))
+    if not (eps >= 0.0) or kmin < 1:                 # (a NaN is refused as well)
+        raise IniError("convergence eps [kmin]: eps >= 0 and kmin >= 1 are needed: %r" % " ".join(s))
+    u.CONVERGENCE, u.CONVERGENCE_MIN = eps, kmin
+
+
 def _fselect(flag):
     """`libabs file` / `libmaps file` (ASOC_aux.py:346-357): the frequencies [Hz] of the library method; one value is an array too"""
     def handler(u, s):
@@ -406,6 +419,7 @@ _KEYWORDS = [
     ('maxsplit', 1, _set('MAX_SPLIT', int)),
     ('mapint', 1, _set('MAP_INTERPOLATION', int)),
     ('maplevels', 1, _set('MAP_LEVELS', int)),
+    ('convergence', 1, _convergence),
     ('polstat', 1, _set('POLSTAT', int)),
     ('absthin', 1, _set('ABSTHIN', int)),
     ('nnnlimit', 1, _set('NNNLIMIT', float)),

@@ -161,6 +161,8 @@ API = {
     "soc_set_emission_column": (C.c_int, [C.c_void_p, C.c_int, _F]),
     "soc_read_emission": (C.c_int, [C.c_void_p, _F, C.c_int64]),
     "soc_emitted_end": (C.c_int, [C.c_void_p]),
+    "soc_emitted_change": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), _F, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "soc_emitted_read_luminosity": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_double)]),
     "soc_absorbed_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "soc_absorbed_add_tally": (C.c_int, [C.c_void_p, C.c_int]),
     "soc_absorbed_add_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -1155,6 +1157,32 @@ class Engine:
         """EMIT[CELLS] as the next sim_cl would use it (tests)"""
         out = np.zeros(self.CELLS, np.float32)
         self._chk(self.lib.soc_read_emission(self.h, _f(out), self.CELLS))
+        return out
+
+    def emitted_change(self, W, COEFF):
+        """the change of the resident emission since the call before (soc_amd.converge has the statements): W[NFREQ] float64, the
+        integration weights, COEFF[LEVELS] float32 as set_emission_column takes it -> dict(S_abs, S_new, S_old, M, bad); the
+        luminosities L[CELLS] of this call stay on the device for the next.  DoesNotFit where the free device memory does not take them"""
+        NFREQ = self._emitted_rows("emitted_change", 0, None)
+        W = np.ascontiguousarray(W, np.float64)
+        COEFF = np.ascontiguousarray(COEFF, np.float32)
+        if W.ndim != 1 or W.size != NFREQ:
+            raise SocError("emitted_change: W must hold NFREQ = %d doubles" % NFREQ)
+        if COEFF.ndim != 1 or COEFF.size != self.LEVELS:
+            raise SocError("emitted_change: COEFF must hold LEVELS = %d floats" % self.LEVELS)
+        stats, bad = np.zeros(4, np.float64), C.c_int64(0)
+        rc = self.lib.soc_emitted_change(self.h, W.ctypes.data_as(C.POINTER(C.c_double)), _f(COEFF),
+                                         stats.ctypes.data_as(C.POINTER(C.c_double)), C.byref(bad))
+        if rc == -2:                                           # (nothing was reserved, the emission stays as it is)
+            raise DoesNotFit("%s (code %d)" % (self.lib.soc_last_error(self.h).decode(), rc), 0)
+        self._chk(rc)
+        return dict(S_abs=float(stats[0]), S_new=float(stats[1]), S_old=float(stats[2]), M=float(stats[3]), bad=int(bad.value))
+
+    def emitted_read_luminosity(self, c0, n):
+        """L of cells [c0, c0 + n) as the last emitted_change left it, float64; zeros before the first (tests)"""
+        self._emitted_rows("emitted_read_luminosity", 0, None)
+        out = np.zeros(max(int(n), 0), np.float64)
+        self._chk(self.lib.soc_emitted_read_luminosity(self.h, int(c0), int(n), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
     def emitted_end(self):
