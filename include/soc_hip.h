@@ -321,7 +321,11 @@ int soc_last_form(soc_ctx *ctx);
  *   bit 13 (sweeps of rays) the sweep held a SimRAM_HP launch (soc_sca_sim_hp: the Healpix sky as the source)
  *   bit 14 a launch of the packet-splitting kernels (soc_sim_bg_split, soc_sim_hp_split): then form 0, kind 0 SimBgSplit or
  *          1 SimHpSplit, WINT 0 or 1, and octree, double (never on a Cartesian grid) and per-cell opacities name the compiled
- *          instance; a split launch without work items leaves the code as it was */
+ *          instance; a split launch without work items leaves the code as it was
+ *   bit 15 a launch of the direct scattered-light kernel (soc_sca_sim_* that did not run as a sweep of rays): then form 0, kind 0
+ *          SimRAM_PB, 1 SimRAM_CL, 2 SimRAM_PS or 3 SimRAM_HP (the scattered-light kernels' own numbering), WINT 0, and octree, double
+ *          and per-cell opacities name the compiled instance -- double as the kernel got it, which on a single-level grid with
+ *          NX > 399 is 1; a launch without work items leaves the code as it was */
 int soc_last_variant(soc_ctx *ctx);
 
 /* HIP-event timing on the handle's stream: bracket launches, then read elapsed ms */

@@ -277,6 +277,20 @@ def sca_ref_models():
     sys.path.insert(0, REPO)
     from soc_amd import synth
     oct8 = synth.octree_cloud(8, levels=3, frac=0.15, seed=7)
+    m = _sca_models_c8(oct8)
+    # the grids of tests/sca_instance_cases.py (one launch per instance of the direct scattered-light kernel): per grid the builds its
+    # cases use -- scalar and per-cell opacities, the weighted Healpix sky, MIRROR 21 -- all for two point sources
+    used = {"r759": ("", "abu", "abuhpw"), "c400": ("", "abu", "hpw"), "oct759": ("", "abu", "hpw"),
+            "deep104x6x5": ("", "abu", "abuhpw", "mir", "abumir"), "oct104x6x5l2": ("",), "oct400x3x2l2": ("",), "oct6x104x5": ("",)}
+    for name, kinds in used.items():
+        c = synth.sca_instance_cloud(name)
+        for k in kinds:
+            m["si_" + name + k] = dict(NX=c.NX, NY=c.NY, NZ=c.NZ, LEVELS=c.LEVELS, CELLS=c.CELLS, NO_PS=2, WITH_ABU=int("abu" in k),
+                                       HPBG_WEIGHTED=int("hpw" in k), MIRROR=21 if "mir" in k else 0)
+    return m
+
+
+def _sca_models_c8(oct8):
     return {
         "c8": dict(NX=8, NY=8, NZ=8, LEVELS=1, CELLS=512),
         "c8noffs": dict(NX=8, NY=8, NZ=8, LEVELS=1, CELLS=512, FFS=0),

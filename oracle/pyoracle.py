@@ -667,6 +667,15 @@ def oracle_sim_sca(orc, job, view, kind=0, gid0=0, gid1=None, nthreads=1, stride
     return OUT, int(n)
 
 
+def oracle_sca_counts(orc):
+    """(packets created, scatterings) of the oracle's last oracle_sim_sca call: the second and third counter of soc_stats"""
+    out = (C.c_long * 2)()
+    orc.lib.orc_sca_counts.restype = None
+    orc.lib.orc_sca_counts.argtypes = [C.POINTER(C.c_long)]
+    orc.lib.orc_sca_counts(out)
+    return int(out[0]), int(out[1])
+
+
 class RefSca:
     """x86 build of kernel_ASOC_sca.c for one model: oracle/_ref/refsca_<tag>.so"""
 

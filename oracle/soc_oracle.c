@@ -1185,6 +1185,18 @@ static int angles2pixel_ring(const int nside, float phi, float theta)
     return (ipix1 - 1);
 }
 
+/* packets created and scatterings of the last orc_sim_sca call (orc_sca_counts), as the scattered-light kernels count them:
+ * a packet per walk_packet_sca call and per SimRAM_HP packet that misses the cloud, a scattering per peel-off event */
+static long sca_packets, sca_scatterings;
+
+static void sca_count(long packets, long scatterings)
+{
+#pragma omp atomic
+    sca_packets += packets;
+#pragma omp atomic
+    sca_scatterings += scatterings;
+}
+
 static long walk_packet_sca(const orc_model *M, rng_t *rng, f3 POS, f3 DIR, float PHOTONS, int level, int ind, int variant)
 {
     const int conditioned = variant & 4;        /* direction already clamped + normalised by the caller (SimRAM_HP) */
@@ -1216,7 +1228,7 @@ static long walk_packet_sca(const orc_model *M, rng_t *rng, f3 POS, f3 DIR, floa
         }
         if (tau < 1.0e-22f) {
             ind = -1;
-            if (is_cl) return 0;
+            if (is_cl) { sca_count(1, 0);  return 0; }
         }
         if (variant == 2) {
             W = -M_EXPM1(-tau);
@@ -1334,6 +1346,7 @@ static long walk_packet_sca(const orc_model *M, rng_t *rng, f3 POS, f3 DIR, floa
         free_path = -M_LOG(Rand(rng));
         if (scatterings == MAX_SCATTERINGS) { ind = -1; continue; }
     }
+    sca_count(1, scatterings);
     return nadd;
 }
 
@@ -1457,7 +1470,7 @@ static long sim_sca_hp_workitem(const orc_model *M, int id)
         POS.z = 0.5f * NZ + Rout * POS.z;
         Surface(M, &POS, &DIR);
         IndexG(M, &POS, &level, &ind);
-        if (ind < 0) continue;
+        if (ind < 0) { sca_count(1, 0);  continue; }
         n += walk_packet_sca(M, &rng, POS, DIR, PHOTONS, level, ind, 1 | 4);
     }
     return n;
@@ -1812,6 +1825,7 @@ EXPORT long orc_sim_sca(orc_model *M, int kind, int gid0, int gid1, int stride, 
 {
     long total = 0;
     if (stride < 1) stride = 1;
+    sca_packets = sca_scatterings = 0;
     if (nthreads <= 1) {
         M->threaded = 0;
         for (int id = gid0; id < gid1; id += stride)
@@ -1826,6 +1840,13 @@ EXPORT long orc_sim_sca(orc_model *M, int kind, int gid0, int gid1, int stride, 
         }
     }
     return total;
+}
+
+/* out[0] packets created, out[1] scatterings of the last orc_sim_sca call (soc_stats' second and third counter) */
+EXPORT void orc_sca_counts(long *out)
+{
+    out[0] = sca_packets;
+    out[1] = sca_scatterings;
 }
 
 /* EqTemperature (kernel_ASOC_aux.c:745-790) for all levels; FACTOR and LENGTH are the -D literals */

@@ -89,7 +89,8 @@ static bool cart_rays_pay(const soc_ctx *c, long long items, bool batch)
 #define SOC_LT_LONE_LAUNCH 1000000                           // work items from which a lone launch goes to the sweep there
 
 // One launch through the direct kernel of its kind (SOURCE 4 and 5 mark Healpix and cell-emission launches for the brick sweep; the
-// direct kernels take them as 1 and 2).  A scattered-light launch adds to its own image; soc_last_variant reports absorption kernels only.
+// direct kernels take them as 1 and 2).  A scattered-light launch adds to its own image; soc_last_variant names its instance of
+// soc_sca_kernel with bit 15 (soc_dev.h: soc_sca_variant_code, from the variant sca_dispatch switches on).
 static int run_direct(soc_ctx *c, SocSim S, const SocVariant &V)
 {
     c->last.passes = 0;
@@ -98,6 +99,7 @@ static int run_direct(soc_ctx *c, SocSim S, const SocVariant &V)
     if (S.SCAKIND) {
         SocSca X = c->view;
         X.kind = S.SCAKIND - 1;  X.DSC = S.DSC;  X.OUT = S.OUT;
+        if (S.gid_count > 0) c->last.variant = soc_sca_variant_code(X.kind, V);      // (sca_dispatch runs nothing without work items)
         HIPCHK(c, soc_launch_sca(c->G, S, X, V, c->stream));
         return SOC_OK;
     }

@@ -462,6 +462,20 @@ static inline int soc_split_variant_code(int kind, const SocVariant &V)
     return soc_variant_code(p) | SOC_VAR_SPLIT;
 }
 
+// The direct scattered-light kernel (soc_sca.hip): the instance <OCT, DBL, ABU, KIND> a launch runs, as soc_last_variant reports it --
+// form 0, kind the SOC_SCA_* value, octree, Index() in double and per-cell opacities as sca_dispatch takes them from the variant
+// (dbl is not cleared on a Cartesian grid: NX > 399 there runs the <0, 1, *, *> instances), and bit 15
+#define SOC_VAR_SCA     (1 << 15)   // a launch of the direct scattered-light kernel
+static inline int soc_sca_variant_code(int kind, const SocVariant &V)
+{
+    SocSweepPlan p{};
+    p.kind = kind;
+    p.octree = V.octree != 0;
+    p.dbl = V.dbl != 0;
+    p.abu = V.abu != 0;
+    return soc_variant_code(p) | SOC_VAR_SCA;
+}
+
 // What a brick sweep reports: passes (0 when no launch had work items), form (0 unless the sweep ran), variant (untouched when no kernel ran)
 struct SocSweepResult {
     int passes = 0, form = 0, variant = -1;

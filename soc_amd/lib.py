@@ -193,7 +193,7 @@ def decode_variant(code):
         return None
     return dict(form=code & 3, kind=(code >> 2) & 7, wint=(code >> 5) & 3, octree=(code >> 7) & 1, dbl=(code >> 8) & 1,
                 abu=(code >> 9) & 1, ali=(code >> 10) & 1, rays=(code >> 11) & 1, healpix=(code >> 12) & 1, hpsky=(code >> 13) & 1,
-                split=(code >> 14) & 1, code=code)
+                split=(code >> 14) & 1, sca=(code >> 15) & 1, code=code)
 
 
 class SocError(RuntimeError):
@@ -366,7 +366,8 @@ class Engine:
         return int(self.lib.soc_last_form(self.h))
 
     def last_variant(self):
-        """the compiled absorption kernel of the last launch or sweep: decode_variant(soc_last_variant), None before any ran"""
+        """the compiled kernel of the last launch or sweep (absorption, packet splitting `split`, direct scattered light `sca`):
+        decode_variant(soc_last_variant), None before any ran"""
         return decode_variant(self.lib.soc_last_variant(self.h))
 
     def set_tuning(self, **params):

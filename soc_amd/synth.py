@@ -131,6 +131,29 @@ def noncubic_cloud(name):
     return octree_cloud(k[0], levels=k[3], frac=k[4], seed=k[5], NY=k[1], NZ=k[2])
 
 
+# The further grids of tests/sca_instance_cases.py (one launch per compiled instance of the direct scattered-light kernel), named here
+# for the tests, the golden generator and the reference builds of oracle/build.py alike: (NX, NY, NZ, levels, frac, seed)
+#   c400             single level with NX > 399: the direct scattered-light kernel runs its <OCT 0, DBL 1> instances there
+#   deep104x6x5      5 levels on 104 x 6 x 5 roots: Index() in double, and deep enough for a walk in float to show in an image
+#   oct104x6x5l2     two levels with 100 < NX <= 399: Index() in float;  oct400x3x2l2: two levels with NX > 399: in double
+SCA_INSTANCE_GRIDS = {
+    "c400": (400, 3, 2, 1, 0.0, 4),
+    "deep104x6x5": (104, 6, 5, 5, 0.15, 11),
+    "oct104x6x5l2": (104, 6, 5, 2, 0.15, 11),
+    "oct400x3x2l2": (400, 3, 2, 2, 0.15, 4),
+}
+SCA_INSTANCE_CELLS = {"c400": 2400, "deep104x6x5": 23224}
+
+
+def sca_instance_cloud(name):
+    if name in NONCUBIC:
+        return noncubic_cloud(name)
+    NX, NY, NZ, levels, frac, seed = SCA_INSTANCE_GRIDS[name]
+    if levels == 1:
+        return cartesian_cloud(NX, seed=seed, NY=NY, NZ=NZ)
+    return octree_cloud(NX, levels=levels, frac=frac, seed=seed, NY=NY, NZ=NZ)
+
+
 def kat_octree():
     """The 4^3-root, 3-level tree of SURVEY.md 8(c): LCELLS=[64,8,8]; leaf value = 1 + global
     index; root cell 21 and level-1 cell 7 are parents of the first octet of the next level."""

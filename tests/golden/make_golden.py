@@ -172,6 +172,21 @@ def sca_main():
     np.savez_compressed(os.path.join(HERE, "sca.npz"), **out)
 
 
+def sca_instances_main():
+    """The images of tests/sca_instance_cases.py from the x86 builds of kernel_ASOC_sca.c for its grids: recorded results only."""
+    from oracle.pyoracle import RefSca
+    import sca_instance_cases as si
+    out = {}
+    for key in si.CASES:
+        job, view = si.job(key), si.view(key)
+        g0, n = si.items(key)
+        OUT = RefSca(si.ref_tag(key)).sim(job, view, si.CASES[key]["kind"], g0, g0 + n)
+        out[si.case_id(key)] = OUT
+        print("%-14s %-22s sum(OUT) = %.9e   nonzero pixels %d / %d" % (si.case_id(key), si.ref_tag(key), OUT.sum(dtype=np.float64),
+                                                                        (OUT != 0).sum(), OUT.size))
+    np.savez_compressed(os.path.join(HERE, "sca_instances.npz"), **out)
+
+
 def maps_main():
     """Golden maps of tests/test_maps.py:MAP_CASES from the x86 build of kernel_ASOC_map.c."""
     from oracle.pyoracle import RefMap, Oracle
@@ -190,6 +205,9 @@ def maps_main():
 if __name__ == "__main__":
     if "--maps" in sys.argv:
         maps_main()
+        sys.exit(0)
+    if "--sca-instances" in sys.argv:
+        sca_instances_main()
         sys.exit(0)
     if "--sca" in sys.argv:
         sca_main()
