@@ -603,6 +603,24 @@ int soc_a2e_resident_upload_aalg(soc_ctx *ctx, int64_t c0, int64_t n, const floa
 int soc_a2e_set_size_aalg(soc_ctx *ctx, float asize, float asize_next, float lg_asize, float lg_step);
 int soc_a2e_resident_download_p(soc_ctx *ctx, int64_t c0, int64_t n, float *PEMIT);
 
+/* The equilibrium sizes of a dust (isize >= NSTOCH, A2E.py:456-547 -> kernel_A2E.c:110-154) on the RESIDENT cells: all of them in one
+ * sweep that reads the absorptions and reads and writes the sum once (12*NFREQ bytes per cell; 20*NFREQ + 8 with the polarised sum),
+ * with the bits of soc_a2e_eqtemp per size and the host statements around it.
+ *   soc_a2e_set_eq_sizes(nsizes, NFREQ, NIP, FACTOR, FREQ[NFREQ], AF[nsizes][NFREQ], KABS[nsizes][NFREQ], TTT[nsizes][NIP],
+ *       Emin[nsizes], kE[nsizes], oplgkE[nsizes], GD, S_FRAC[nsizes], SIZE_A[nsizes] or NULL) copies the tables of the sizes to the
+ *       device, in the order in which their emission is to be added (ascending sizes; the caller leaves out a size it skips).  A size
+ *       sees the absorptions a[i] * AF[size][i] (one float product), its emission is added to the sum as emit * (GD * S_FRAC[size]) and,
+ *       where SIZE_A is given, to the polarised sum as (emit * GD) * S_FRAC[size] in the cells with SIZE_A[size] >= a_alg (the hard
+ *       mask of A2E.py:533-539).  SOC_ERR_ARG where the row of one cell (NFREQ | 1 + nsizes floats, and NFREQ more) does not fit the
+ *       160 KB of LDS; the sizes set before then stay.
+ *   soc_a2e_resident_solve_eq() runs them over the resident cells of soc_a2e_resident_begin or soc_mabu_begin, after the stochastic
+ *       sizes' soc_a2e_resident_solve calls.  SOC_ERR_STATE without resident cells, without sizes set for their NFREQ, and where
+ *       SIZE_A was given but polarised output was not asked for. */
+int soc_a2e_set_eq_sizes(soc_ctx *ctx, int nsizes, int NFREQ, int NIP, float FACTOR, const float *FREQ, const float *AF,
+                         const float *KABS, const float *TTT, const float *Emin, const float *kE, const float *oplgkE, float GD,
+                         const float *S_FRAC, const float *SIZE_A);
+int soc_a2e_resident_solve_eq(soc_ctx *ctx);
+
 /* replaces kernel_T(...) = EqTemperature for one batch (A2E.py:511-530 -> kernel_A2E.c:110-154);
  * TTT holds NIP temperatures, ABS is [batch*NFREQ] (already multiplied by AF on the host),
  * outputs T[batch] and EMIT[batch*NFREQ] */

@@ -8,7 +8,10 @@ Drop-in for ``A2E.py solver absorbed emitted`` (reference A2E.py:64-66): same so
 all cells go through the HIP ``DoSolve`` (sizes < NSTOCH) or ``EqTemperature`` (sizes >= NSTOCH)
 and the emission is accumulated (A2E.py:453-600).  Differences that are the point of the
 rewrite: no run-time kernel build, no 266 MB global scratch matrix (the transition matrix
-lives in LDS), batches are sized by memory, not by the scratch buffer.
+lives in LDS), batches are sized by memory, not by the scratch buffer.  Where the cells fit the device they stay resident while the
+sizes are solved, the equilibrium sizes included: all of those in one launch that adds to the sum of the stochastic sizes
+(a2e_set_eq_sizes + a2e_resident_solve_eq), with the bits of the route through a2e_eqtemp size by size and batch by batch, which
+an engine without the call keeps.
 
 With the seventh argument, a file {CELLS} aalg[CELLS] of each cell's minimum aligned grain size, the emission of the grains larger
 than that is written to <emitted>.P as well (A2E.py:28-29, 192-197, 413-429, 533-539): the polarised emission.
@@ -34,7 +37,23 @@ def planck_safe(f, T):
 
 
 def eq_table(sol, isize):
-    """E -> T lookup table of one size on the host (A2E.py:466-488): Emin, kE, oplgkE, TTT[NIP], KABS."""
+    """E -> T lookup table of one size on the host (A2E.py:466-488): Emin, kE, oplgkE, TTT[NIP], KABS.  Built once per solver and
+    size and kept: the loop is 5000 turns of Python, and a pipeline with re-emission iterations comes here in every iteration, each
+    time with a dict freshly read from the solver file.  So the key is what the table is computed from -- the bits of FREQ, of the
+    size's row of SK_ABS, of GD and of the size's S_FRAC -- and the arrays returned are the kept ones (not to be written to)."""
+    key = tuple((a.dtype.str, a.tobytes()) for a in (np.asarray(sol["FREQ"]), np.asarray(sol["SK_ABS"][isize, :]),
+                                                     np.asarray(sol["GD"]), np.asarray(sol["S_FRAC"][isize])))
+    if key not in _EQ_TABLES:
+        if len(_EQ_TABLES) >= 256:                 # (256 sizes x 20 KB; more than any set of dust models in one process)
+            _EQ_TABLES.clear()
+        _EQ_TABLES[key] = _eq_table(sol, isize)
+    return _EQ_TABLES[key]
+
+
+_EQ_TABLES = {}
+
+
+def _eq_table(sol, isize):
     FREQ = np.asarray(sol["FREQ"], np.float64)
     KABS = sol["SK_ABS"][isize, :] / (sol["GD"] * sol["S_FRAC"][isize])
     TSTEP = 1600.0 / NIP
@@ -50,6 +69,25 @@ def eq_table(sol, isize):
     oplgkE = 1.0 / np.log10(kE)
     TTT = np.asarray(interp1d(Eout, TT)(Emin * kE ** np.arange(NIP)), np.float32)
     return Emin, kE, oplgkE, TTT, np.asarray(KABS, np.float32)
+
+
+def eq_sizes(sol, NSTOCH=999):
+    """the sizes that a2e.run solves as equilibrium sizes, ascending: isize >= NSTOCH or without tables in the solver file, less those
+    with S_FRAC < 1e-30, which it skips (A2E.py:466)"""
+    nstoch = min(int(NSTOCH), len(sol["sizes"]), sol["NSIZE"])
+    return [isize for isize in range(max(nstoch, 0), sol["NSIZE"]) if not sol["S_FRAC"][isize] < 1.0e-30]
+
+
+def eq_size_tables(sol, sizes, polarised=False):
+    """the arguments of engine.a2e_set_eq_sizes for these sizes of the solver: what the host route hands to a2e_eqtemp size by size
+    (eq_table, a2e_absorption_fraction), stacked"""
+    tabs = [eq_table(sol, isize) for isize in sizes]
+    f32 = np.float32
+    return (NIP, FACTOR, sol["FREQ"], np.stack([a2e_absorption_fraction(sol, isize) for isize in sizes]),
+            np.stack([t[4] for t in tabs]), np.stack([t[3] for t in tabs]), np.asarray([t[0] for t in tabs], f32),
+            np.asarray([t[1] for t in tabs], f32), np.asarray([t[2] for t in tabs], f32), f32(sol["GD"]),
+            np.asarray([sol["S_FRAC"][isize] for isize in sizes], f32),
+            np.asarray([sol["SIZE_A"][isize] for isize in sizes], f32) if polarised else None)
 
 
 def aalg_weights(ASIZE, isize, aalg, stochastic=True):
@@ -102,10 +140,13 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, 
     # The stochastically heated sizes with the cells resident in device memory (soc_a2e_resident_*): absorptions up once, every size a
     # launch over all cells that adds its emission to a sum on the device, the sum down once -- instead of NSIZE round trips of every
     # batch.  The sum is added in the order of the sizes, as the reference's host does (A2E.py:596-600), and the equilibrium sizes
-    # follow it (they come last in the loop: isize >= NSTOCH), so the result is the same to the bit.
-    nstoch = min(int(NSTOCH), len(sol["sizes"]), sol["NSIZE"])
-    resident = False
-    if nstoch > 0 and hasattr(engine, "a2e_resident_begin") and (aalg is None or hasattr(engine, "a2e_resident_upload_aalg")):
+    # follow it (they come last in the loop: isize >= NSTOCH), so the result is the same to the bit.  With an engine that has
+    # a2e_resident_solve_eq the equilibrium sizes are solved there as well, all in one launch that adds them to the same sum in the
+    # same order, before the one download; an engine without it gets them size by size through a2e_eqtemp, as before.
+    nstoch = max(min(int(NSTOCH), len(sol["sizes"]), sol["NSIZE"]), 0)
+    eq_live = eq_sizes(sol, NSTOCH) if hasattr(engine, "a2e_resident_solve_eq") else []
+    resident = eq_done = False
+    if (nstoch > 0 or eq_live) and hasattr(engine, "a2e_resident_begin") and (aalg is None or hasattr(engine, "a2e_resident_upload_aalg")):
         try:
             if aalg is None:
                 engine.a2e_resident_begin(CELLS, NFREQ)
@@ -129,6 +170,15 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, 
                 engine.a2e_resident_solve()
                 if verbose:
                     print("    isize = %d   stochastic heating" % isize)
+            if eq_live:
+                try:
+                    engine.a2e_set_eq_sizes(*eq_size_tables(sol, eq_live, aalg is not None))
+                    eq_done = True
+                except Exception as err:                          # no tile of this NFREQ fits the LDS: size by size, as before
+                    if verbose:
+                        print("    a2e: equilibrium sizes not on the device (%s)" % err)
+                if eq_done:
+                    engine.a2e_resident_solve_eq()
             for icell in range(0, CELLS, batch):
                 b = min(icell + batch, CELLS)
                 emit = engine.a2e_resident_download(icell, b - icell)
@@ -144,7 +194,7 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, 
     for isize in range(sol["NSIZE"]):
         AF = a2e_absorption_fraction(sol, isize)
         if isize >= NSTOCH or isize >= len(sol["sizes"]):
-            if sol["S_FRAC"][isize] < 1.0e-30:
+            if sol["S_FRAC"][isize] < 1.0e-30 or eq_done:
                 continue
             Emin, kE, oplgkE, TTT, KABS = eq_table(sol, isize)
             scale = sol["GD"] * sol["S_FRAC"][isize]

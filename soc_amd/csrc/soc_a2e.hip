@@ -20,7 +20,8 @@
 //   4. normalisation and emission: one frequency per lane, serial over the enthalpy bins from Ibeg[f] exactly as the reference.
 // Algorithmic HBM bytes per cell and size: 4*NFREQ in + 4*NFREQ out (tables are L2-resident).
 //
-// EqTemperature (kernel_A2E.c:110-154) is one lane per cell, operation for operation.
+// EqTemperature (kernel_A2E.c:110-154) is one lane per cell, operation for operation (soc_a2e_eqtemp_kernel: a batch of host arrays),
+// and, for the cells resident in HBM, one sweep over all equilibrium sizes of a dust with the same operations (soc_a2e_eqsizes_kernel).
 #include "soc_dev.h"
 #include "soc_math.h"
 
@@ -257,6 +258,115 @@ __global__ void soc_a2e_eqtemp_kernel(const SocEqTArgs A)
         A.EMIT[(size_t)id * A.NFREQ + f] =
             (2.79639459e-20f * A.FACTOR) * A.KABS[f] * (fr * fr / (soc_expf(4.7995074e-11f * fr / TP) - 1.0f));
     }
+}
+
+// EqTemperature for ALL equilibrium sizes of a dust in one sweep over the resident cells (soc_a2e_resident_solve_eq): what
+// soc_a2e_eqtemp_kernel and the host statements around it (soc_amd/a2e.py: ABSORBED * AF, EMITTED += emit * (GD * S_FRAC), the hard
+// mask of the polarised sum) do per size, operation for operation and in the same order, with 12*NFREQ bytes of HBM traffic per cell
+// (absorptions in, the sum in and out; 20*NFREQ + 8 with the polarised sum) however many sizes there are.  A workgroup takes a tile of
+// TC cells:
+//   stage  the tile's absorptions go to LDS, read as the array lies (lanes on neighbouring words); the rows get an odd stride, so that
+//          the 64 lanes of phase A, each on a row of its own, hit 64 banks;
+//   A      a lane per (cell, size): x_i = a[i] * AF[size][i] (the host's single fp32 product), Ein summed over i = 1..NFREQ-1 in the
+//          order of soc_a2e_eqtemp_kernel, the table look-up, wi, TP -> sT[size][cell];
+//   B      a lane per (cell, frequency) element of the tile in the order of the arrays: the sum's element into a register, the
+//          emission of every size added in ascending order (emit * scale[size], scale = GD * S_FRAC formed in fp32 by the host), one
+//          write; with POL the same for the polarised sum with (emit * GD) * S_FRAC where SIZE_A[size] >= a_alg of the cell.
+// The per-size tables AF, KABS [nsizes][NFREQ], TTT [nsizes][NIP] and scalars come from device memory (L2; the lanes of a wave read
+// neighbouring words or one word).
+#define A2E_EQ_T 256
+template <bool POL>
+__global__ __launch_bounds__(A2E_EQ_T) void soc_a2e_eqsizes_kernel(const SocEqSizesArgs A)
+{
+    extern __shared__ float lds[];
+    const int NFREQ = A.NFREQ, TC = A.TC, stride = A.stride, ns = A.nsizes, tid = threadIdx.x;
+    float *sA = lds;                                     // [TC][stride]
+    float *sT = sA + (size_t)TC * stride;                // [ns][TC]
+    float *sF = sT + (size_t)ns * TC;                    // [NFREQ]
+    const long long cell0 = (long long)blockIdx.x * TC;
+    const int nc = (A.cells - cell0 < TC) ? (int)(A.cells - cell0) : TC;   // cells of this tile (>= 1)
+    const size_t g0 = (size_t)cell0 * NFREQ;
+    const int ne = nc * NFREQ;
+    for (int e = tid; e < ne; e += A2E_EQ_T) {
+        const int c = e / NFREQ;
+        sA[c * stride + (e - c * NFREQ)] = A.ABS[g0 + e];
+    }
+    for (int i = tid; i < NFREQ; i += A2E_EQ_T) sF[i] = A.FREQ[i];
+    __syncthreads();
+    // A: the temperature of every (cell, size)
+    for (int p = tid; p < TC * ns; p += A2E_EQ_T) {
+        const int s = p / TC, c = p - s * TC;
+        if (c >= nc) continue;
+        const float *a = sA + c * stride, *af = A.AF + (size_t)s * NFREQ, *TTT = A.TTT + (size_t)s * A.NIP;
+        const float Emin = A.Emin[s], kE = A.kE[s], oplgkE = A.oplgkE[s];
+        float Ein = 0.0f, xp = a[0] * af[0];
+        for (int i = 1; i < NFREQ; i++) {
+            const float xi = a[i] * af[i];
+            Ein += (xi * sF[i] + xp * sF[i - 1]) * ((sF[i] - sF[i - 1]) * 3.3130348e-27f);
+            xp = xi;
+        }
+        int iE = (int)soc_floorf(oplgkE * soc_log10f(Ein / Emin));
+        iE = iE < 0 ? 0 : (iE > A.NIP - 2 ? A.NIP - 2 : iE);
+        const float wi = (Emin * soc_pownf(kE, iE + 1) - Ein) / (Emin * soc_pownf(kE, iE + 1) - soc_pownf(kE, iE));
+        sT[s * TC + c] = (float)((double)(wi * TTT[iE]) + (1.0 - (double)wi) * (double)TTT[iE + 1]);
+    }
+    __syncthreads();
+    // B: the emission of every size, added to the sums in ascending order of the sizes
+    const float K0 = 2.79639459e-20f * A.FACTOR;
+    for (int e = tid; e < ne; e += A2E_EQ_T) {
+        const int c = e / NFREQ, f = e - c * NFREQ;
+        const float fr = sF[f], ff = fr * fr, hf = 4.7995074e-11f * fr;
+        float sum = A.SUM[g0 + e], psum = 0.0f, aalg = 0.0f;
+        if constexpr (POL) { psum = A.PSUM[g0 + e];  aalg = A.AALG[2 * (size_t)(cell0 + c)]; }
+        for (int s = 0; s < ns; s++) {
+            const float TP = sT[s * TC + c];
+            const float emit = K0 * A.KABS[(size_t)s * NFREQ + f] * (ff / (soc_expf(hf / TP) - 1.0f));
+            sum = sum + emit * A.scale[s];
+            if constexpr (POL) {
+                if (A.SIZEA[s] >= aalg) psum = psum + (emit * A.GD) * A.SFRAC[s];      // the hard mask: no partial arm (A2E.py:533-539)
+            }
+        }
+        A.SUM[g0 + e] = sum;
+        if constexpr (POL) A.PSUM[g0 + e] = psum;
+    }
+}
+
+// the tile of the kernel above: out = { cells per workgroup, bytes of dynamic LDS }; false where not one cell's row fits (out[1] then
+// holds the bytes it needs)
+bool soc_a2e_eq_shape(int NFREQ, int nsizes, int out[2])
+{
+    const size_t stride = (size_t)NFREQ | 1;
+    for (int TC = 64; TC >= 1; TC >>= 1) {
+        const size_t lds = ((size_t)TC * (stride + (size_t)nsizes) + (size_t)NFREQ) * 4;
+        if (lds <= SOC_A2E_LDS) { out[0] = TC;  out[1] = (int)lds;  return true; }
+        if (TC == 1) out[1] = lds > 0x7fffffff ? 0x7fffffff : (int)lds;
+    }
+    out[0] = 0;
+    return false;
+}
+
+template <bool POL>
+static hipError_t a2e_eqsizes_launch(const SocEqSizesArgs &A, size_t lds, hipStream_t st)
+{
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)soc_a2e_eqsizes_kernel<POL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const long long tiles = (A.cells + A.TC - 1) / A.TC;
+    soc_a2e_eqsizes_kernel<POL><<<(unsigned)tiles, A2E_EQ_T, lds, st>>>(A);
+    return hipGetLastError();
+}
+
+hipError_t soc_launch_a2e_eqsizes(SocEqSizesArgs A, hipStream_t st)
+{
+    if (A.cells <= 0 || A.nsizes <= 0) return hipSuccess;
+    int shape[2];
+    if (!soc_a2e_eq_shape(A.NFREQ, A.nsizes, shape)) return hipErrorInvalidValue;
+    if (A.PSUM && (!A.AALG || !A.SIZEA)) return hipErrorInvalidValue;
+    A.TC = shape[0];  A.stride = A.NFREQ | 1;
+    if ((A.cells + A.TC - 1) / A.TC > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (A.PSUM) return a2e_eqsizes_launch<true>(A, (size_t)shape[1], st);
+    return a2e_eqsizes_launch<false>(A, (size_t)shape[1], st);
 }
 
 // kernel_eqsolver.c (A2E_MABU.py SolveEquilibriumDust): EqTemperature :5-62 and Emission :66-79 of one equilibrium

@@ -220,6 +220,62 @@ int soc_a2e_resident_solve(soc_ctx *c)
     return SOC_OK;
 }
 
+int soc_a2e_set_eq_sizes(soc_ctx *c, int nsizes, int NFREQ, int NIP, float FACTOR, const float *FREQ, const float *AF, const float *KABS,
+                         const float *TTT, const float *Emin, const float *kE, const float *oplgkE, float GD, const float *S_FRAC,
+                         const float *SIZE_A)
+{
+    if (!c) return SOC_ERR_ARG;
+    FLUSH(c);
+    if (nsizes < 1 || nsizes > 4096 || NFREQ < 2 || NIP < 2 || !FREQ || !AF || !KABS || !TTT || !Emin || !kE || !oplgkE || !S_FRAC)
+        return fail(c, SOC_ERR_ARG, "soc_a2e_set_eq_sizes: bad arguments (1 <= nsizes <= 4096, NFREQ >= 2, NIP >= 2)");
+    int shape[2];
+    if (!soc_a2e_eq_shape(NFREQ, nsizes, shape))            // (refused here, with the sizes set before untouched, not at the launch)
+        return fail(c, SOC_ERR_ARG, "soc_a2e_set_eq_sizes: NFREQ = %d with %d sizes needs %d bytes of LDS for one cell, the limit is %d",
+                    NFREQ, nsizes, shape[1], SOC_A2E_LDS);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (a launch may still read the tables set before)
+    const size_t nf = (size_t)nsizes * NFREQ, nt = (size_t)nsizes * NIP;
+    HIPCHK(c, c->aEqTab.reserve((size_t)NFREQ + 2 * nf + nt, c->stream));
+    HIPCHK(c, c->aEqPar.reserve((size_t)6 * nsizes, c->stream));
+    std::vector<float> par((size_t)6 * nsizes, 0.0f);
+    for (int s = 0; s < nsizes; s++) {
+        par[s] = Emin[s];  par[nsizes + s] = kE[s];  par[2 * nsizes + s] = oplgkE[s];
+        par[3 * nsizes + s] = GD * S_FRAC[s];               // one fp32 product, as numpy forms GD * S_FRAC[isize]
+        par[4 * nsizes + s] = S_FRAC[s];
+        if (SIZE_A) par[5 * nsizes + s] = SIZE_A[s];
+    }
+    float *dF = c->aEqTab, *dAF = dF + NFREQ, *dK = dAF + nf, *dT3 = dK + nf;
+    HIPCHK(c, hipMemcpy(dF, FREQ, (size_t)NFREQ * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dAF, AF, nf * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dK, KABS, nf * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dT3, TTT, nt * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->aEqPar, par.data(), par.size() * 4, hipMemcpyHostToDevice));
+    c->eq_nsizes = nsizes;  c->eq_NFREQ = NFREQ;  c->eq_NIP = NIP;  c->eq_FACTOR = FACTOR;  c->eq_GD = GD;  c->eq_pol = SIZE_A != nullptr;
+    return SOC_OK;
+}
+
+int soc_a2e_resident_solve_eq(soc_ctx *c)
+{
+    if (!c) return SOC_ERR_ARG;
+    if (!c->aAll || !c->aSum) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve_eq: call soc_a2e_resident_begin first");
+    if (c->eq_nsizes == 0 || c->eq_NFREQ != c->a2e_res_nfreq)
+        return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve_eq: soc_a2e_set_eq_sizes with NFREQ = %d first", c->a2e_res_nfreq);
+    if (c->eq_pol && (!c->aPSum || !c->aAalg))
+        return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve_eq: the sizes were set with SIZE_A, but polarised output was not asked for (soc_a2e_resident_begin_pol, soc_mabu_begin_pol)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int ns = c->eq_nsizes;
+    const size_t nf = (size_t)ns * c->eq_NFREQ;
+    SocEqSizesArgs A{};
+    A.cells = c->a2e_cells;  A.NFREQ = c->eq_NFREQ;  A.NIP = c->eq_NIP;  A.nsizes = ns;  A.FACTOR = c->eq_FACTOR;  A.GD = c->eq_GD;
+    A.FREQ = c->aEqTab;  A.AF = A.FREQ + c->eq_NFREQ;  A.KABS = A.AF + nf;  A.TTT = A.KABS + nf;
+    const float *par = c->aEqPar;
+    A.Emin = par;  A.kE = par + ns;  A.oplgkE = par + 2 * ns;  A.scale = par + 3 * ns;  A.SFRAC = par + 4 * ns;  A.SIZEA = par + 5 * ns;
+    A.ABS = c->aAll;  A.SUM = c->aSum;
+    if (c->eq_pol) { A.PSUM = c->aPSum;  A.AALG = c->aAalg; }
+    HIPCHK(c, soc_launch_a2e_eqsizes(A, c->stream));
+    return SOC_OK;
+}
+
 int soc_a2e_resident_download(soc_ctx *c, int64_t c0, int64_t n, float *AEMIT)
 {
     if (!c || !AEMIT) return SOC_ERR_ARG;

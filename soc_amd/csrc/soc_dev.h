@@ -258,11 +258,32 @@ struct SocEqTArgs {
     float *T, *EMIT;
 };
 
+// all equilibrium sizes of a dust on the resident cells (soc_a2e_eqsizes_kernel): the per-size tables and the arrays it works on
+struct SocEqSizesArgs {
+    long long cells;
+    int NFREQ, NIP, nsizes;
+    int TC, stride;                  // cells per tile and the row stride of its absorptions in LDS: set by soc_launch_a2e_eqsizes
+    float FACTOR, GD;
+    const float *FREQ;               // [NFREQ]
+    const float *AF, *KABS;          // [nsizes][NFREQ]
+    const float *TTT;                // [nsizes][NIP]
+    const float *Emin, *kE, *oplgkE; // [nsizes]
+    const float *scale;              // [nsizes] GD * S_FRAC, formed in fp32
+    const float *SFRAC, *SIZEA;      // [nsizes] (the polarised sum alone)
+    const float *ABS;                // [cells*NFREQ]
+    float       *SUM;                // [cells*NFREQ]
+    float       *PSUM;               // [cells*NFREQ], NULL without polarised output
+    const float *AALG;               // [cells][2]: a_alg and log10(a_alg) of the cell
+};
+
 #define SOC_A2E_LDS (160 * 1024)     // bytes of LDS a DoSolve workgroup may take (the CU's)
 // cells per workgroup, threads per workgroup and dynamic LDS bytes of DoSolve at this size; false: one cell does not fit (it needs out[2] bytes)
 bool soc_a2e_shape(int NE, int NFREQ, int out[3]);
 hipError_t soc_launch_a2e_dosolve(const SocA2EArgs &A, hipStream_t st);
 hipError_t soc_launch_a2e_eqtemp(const SocEqTArgs &A, hipStream_t st);
+// cells per tile and dynamic LDS bytes of the equilibrium-sizes kernel; false: the row of one cell does not fit (it needs out[1] bytes)
+bool soc_a2e_eq_shape(int NFREQ, int nsizes, int out[2]);
+hipError_t soc_launch_a2e_eqsizes(SocEqSizesArgs A, hipStream_t st);
 hipError_t soc_launch_eqsolver(const SocEqTArgs &A, hipStream_t st);
 
 // the multi-dust emission stage (soc_mabu.hip): split of the absorptions between the dust components, clip of the last channel

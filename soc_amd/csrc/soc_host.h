@@ -122,6 +122,12 @@ struct soc_ctx {
     int64_t a2e_cells = 0;                                   // cells resident in aAll and aSum, a2e_res_nfreq floats each: the rows a call may address
     int     a2e_res_nfreq = 0;
     DevBuf<int> aFirst, aLast, aIwOff, aDst, aIbeg;
+    // the equilibrium sizes of a dust (soc_a2e_set_eq_sizes): aEqTab = FREQ[NFREQ] | AF | KABS [nsizes][NFREQ] | TTT[nsizes][NIP],
+    // aEqPar = Emin | kE | oplgkE | GD * S_FRAC | S_FRAC | SIZE_A, nsizes floats each
+    DevBuf<float> aEqTab, aEqPar;
+    int     eq_nsizes = 0, eq_NFREQ = 0, eq_NIP = 0;         // eq_nsizes 0: none are set
+    float   eq_FACTOR = 0.0f, eq_GD = 0.0f;
+    bool    eq_pol = false;                                  // SIZE_A was given: the sizes also add to the polarised sum
     // the multi-dust stage (soc_mabu_*): absorptions as the absorbed file holds them, the sum over the dusts, abundances, relative cross
     // sections, temperatures and tables of an equilibrium dust; the current dust's share and its emission are aAll and aSum
     DevBuf<float>  mABS, mSUM, mABU, mT, mTab;

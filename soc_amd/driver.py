@@ -14,7 +14,9 @@ at config 3) and the emission over through files.  Here
      equilibrium component with soc_eqsolver (SolveEquilibriumDust, A2E_MABU.py:436-640 -> kernel_eqsolver.c), a
      stochastically heated one with soc_amd.a2e.run on its <dust>.solver file (A2E.py) -- and summed weighted by the
      abundances (A2E_MABU.py:1128-1140): soc_amd.mabu.solve_emission, the stage that python -m soc_amd.mabu runs alone -- on
-     the device from the absorptions to the sum where the engine has the soc_mabu_* calls;
+     the device from the absorptions to the sum where the engine has the soc_mabu_* calls; the sizes from the `nstoch N` of a
+     gsetdust file on (A2E_MABU.py:124-143) are solved at their equilibrium temperature, on the device as well
+     (a2e_resident_solve_eq), so such a dust takes neither stage 2 nor the resident emission and absorptions below off the device;
   3. the maps are written from that emission array (AbsorptionRun.write_maps: maps.ini of ASOC_driver.py:447-473).
 
 Same ini keys, same dust / solver / abundance / cloud files.  `emitted` is written (it is a product); the

@@ -136,6 +136,8 @@ API = {
     "soc_a2e_resident_upload_aalg": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F, _F]),
     "soc_a2e_set_size_aalg": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]),
     "soc_a2e_resident_download_p": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
+    "soc_a2e_set_eq_sizes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, _F, _F, _F, _F, _F, _F, _F, C.c_float, _F, _F]),
+    "soc_a2e_resident_solve_eq": (C.c_int, [C.c_void_p]),
     "soc_a2e_eqtemp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                  C.c_float, C.c_float, _F, _F, _F, _F, _F, _F]),
     "soc_eqsolver": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
@@ -969,6 +971,26 @@ class Engine:
 
     def a2e_resident_solve(self):
         self._chk(self.lib.soc_a2e_resident_solve(self.h))
+
+    def a2e_set_eq_sizes(self, NIP, FACTOR, FREQ, AF, KABS, TTT, Emin, kE, oplgkE, GD, S_FRAC, SIZE_A=None):
+        """the tables of the equilibrium sizes of a dust, in the order in which a2e_resident_solve_eq adds their emission: AF, KABS
+        [nsizes, NFREQ], TTT[nsizes, NIP], Emin, kE, oplgkE, S_FRAC [nsizes]; SIZE_A[nsizes]: they also add to the polarised sum"""
+        AF, KABS, TTT = (np.ascontiguousarray(a, np.float32) for a in (AF, KABS, TTT))
+        FREQ, Emin, kE, oplgkE, S_FRAC = (np.ascontiguousarray(a, np.float32).ravel() for a in (FREQ, Emin, kE, oplgkE, S_FRAC))
+        SIZE_A = None if SIZE_A is None else np.ascontiguousarray(SIZE_A, np.float32).ravel()
+        if AF.ndim != 2:
+            raise SocError("a2e_set_eq_sizes: AF[nsizes, NFREQ], an array of shape %s was given" % (AF.shape,))
+        ns, NFREQ = AF.shape
+        if KABS.shape != (ns, NFREQ) or TTT.shape != (ns, int(NIP)) or FREQ.size != NFREQ or \
+                any(a.size != ns for a in (Emin, kE, oplgkE, S_FRAC)) or (SIZE_A is not None and SIZE_A.size != ns):
+            raise SocError("a2e_set_eq_sizes: array sizes do not match nsizes=%d NFREQ=%d NIP=%d" % (ns, NFREQ, NIP))
+        self._chk(self.lib.soc_a2e_set_eq_sizes(self.h, ns, NFREQ, int(NIP), np.float32(FACTOR), _f(FREQ), _f(AF), _f(KABS), _f(TTT),
+                                                _f(Emin), _f(kE), _f(oplgkE), np.float32(GD), _f(S_FRAC), _f(SIZE_A)))
+
+    def a2e_resident_solve_eq(self):
+        """the sizes of a2e_set_eq_sizes on the resident cells (a2e_resident_begin or mabu_begin), added to the sum after the
+        stochastic sizes' a2e_resident_solve calls"""
+        self._chk(self.lib.soc_a2e_resident_solve_eq(self.h))
 
     def a2e_resident_download(self, c0, n, out=None):
         out = np.zeros((int(n), self._a2e_res[1]), np.float32) if out is None else out

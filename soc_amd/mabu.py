@@ -13,6 +13,13 @@ solve_emission is that stage, shared with soc_amd.driver.  With an engine that h
 in device memory from the absorbed file to the sum (the absorptions go up once, the sum comes down once); with any
 other engine the stage runs as numpy around the engine's per-dust solvers.  The two give the same bits.
 
+A gsetdust file's line ``nstoch N`` (A2E_MABU.py:124-143; DustLib writes it at the first size above amin_equ) is honoured as the
+reference honours it: the sizes below N are solved stochastically, those from N on -- and sizes without tables in the solver file --
+at their equilibrium temperature (A2E.py:456-547), on either path; on the device path all equilibrium sizes of a dust in one launch
+on the resident cells (engine.a2e_set_eq_sizes + a2e_resident_solve_eq), which an engine needs to be offered that path for such a
+dust.  A negative N or no line: every size is stochastically heated.  (Before, the line was not read; a file with N below its number
+of sizes is the one input whose result this changed.)
+
 Ini lines ``polarisation <dust> <aalg file>`` (A2E_MABU.py:158-167; the key is matched by its prefix `polari`) name, for a dust of
 the ini, the file {CELLS} aalg[CELLS] of each cell's minimum aligned grain size.  Such a dust gets a polarised emission beside its
 emission -- a stochastically heated one from the solver (soc_amd.a2e with aalg, A2E_MABU.py:971-984), an equilibrium one from the
@@ -41,6 +48,7 @@ from .lib import DoesNotFit
 from .synth import a2e_absorption_fraction
 
 NE_EQ = 30000                    # A2E_MABU.py:478
+NSTOCH_ALL = 9999                # A2E_MABU.py:124: a gsetdust file without an `nstoch` line -- every size is stochastically heated
 REFUSED_KEYS = ('nnmake', 'nnsolve', 'nnabs', 'nnemit', 'nnthin', 'absthin', 'libabs', 'libmaps', 'aalg', 'crheating')
 CHUNK = 1 << 20                  # cells per upload / download call
 
@@ -71,6 +79,28 @@ def solver_name(name):
     if b.startswith('gs_'):
         b = b[3:]
     return os.path.join(d, b + '.solver')
+
+
+def read_nstoch(name, kind=None):
+    """The number of stochastically heated sizes of a gsetdust file (A2E_MABU.py:124-136): the value of its line `nstoch N` (the last
+    one, should there be several; only lines of at least two tokens whose first is `nstoch` count), NSTOCH_ALL where it is negative
+    or there is no such line.  The sizes from N on are solved at their equilibrium temperature.  An eqdust file is not searched."""
+    nstoch = NSTOCH_ALL
+    if (kind or dust_kind(name)) != 'eqdust':
+        with open(name) as fp:
+            for line in fp:
+                s = line.split()
+                if len(s) > 1 and s[0] == 'nstoch':
+                    nstoch = int(s[1])
+                    if nstoch < 0:
+                        nstoch = NSTOCH_ALL
+    return nstoch
+
+
+def stochastic_sizes(sol):
+    """how many sizes of a solver file (read by _tables) are solved stochastically: its dust file's `nstoch`, at most the sizes the
+    file has tables for; the rest are equilibrium sizes"""
+    return max(min(int(sol.get("nstoch", NSTOCH_ALL)), len(sol["sizes"]), sol["NSIZE"]), 0)
 
 
 def require_solvers(dusts, kinds):
@@ -241,7 +271,8 @@ def abundance_table(ABU, single, CELLS, NDUST):
 
 # ---- the stage ------------------------------------------------------------------------------------------------------
 def _tables(dusts, kinds, NFREQ):
-    """per dust what its solver needs: eq_dust_table of an equilibrium dust, the solver file of a stochastically heated one"""
+    """per dust what its solver needs: eq_dust_table of an equilibrium dust, the solver file of a stochastically heated one with
+    the `nstoch` of its dust file (read_nstoch) under that key"""
     out = []
     for d, k in zip(dusts, kinds):
         if k == 'eqdust':
@@ -250,15 +281,18 @@ def _tables(dusts, kinds, NFREQ):
             sol = files.read_solver(solver_name(d))
             if sol["NFREQ"] != NFREQ:
                 raise ValueError("absorbed file has %d frequencies, solver %d" % (NFREQ, sol["NFREQ"]))
+            sol["nstoch"] = read_nstoch(d, k)
             out.append(sol)
     return out
 
 
 def offers_device_path(engine, kinds, tables, polarised=False):
-    """THE probe of the stage: the engine has the soc_mabu_* calls (with `polarisation` lines those too), and every size of every
-    solver file is solved stochastically (a size without its tables goes through a2e.run's equilibrium branch, which works on host arrays)"""
+    """THE probe of the stage: the engine has the soc_mabu_* calls (with `polarisation` lines those too) and, where a size of a solver
+    file is an equilibrium size (from the dust file's `nstoch` on, or without its tables in the solver file), a2e_resident_solve_eq,
+    which solves those on the resident cells (without it they go through a2e.run's equilibrium branch, which works on host arrays)"""
     return hasattr(engine, "mabu_begin") and (not polarised or hasattr(engine, "mabu_pol_eq")) and \
-        all(k == 'eqdust' or len(t["sizes"]) >= t["NSIZE"] for k, t in zip(kinds, tables))
+        (hasattr(engine, "a2e_resident_solve_eq") or
+         all(k == 'eqdust' or stochastic_sizes(t) >= t["NSIZE"] for k, t in zip(kinds, tables)))
 
 
 def device_path_offered(engine, dusts, kinds, NFREQ, pol=None):
@@ -283,10 +317,10 @@ def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, lo
                 _, em[a:b] = engine.eqsolver(c0 + a, CELLS, NE_EQ, FACTOR, kE, oplgkE, Emin, Fq, KABS, TTT, part[a:b])
             if aalg is not None:
                 pem = polarised_eq(em, aalg, *ptabs[idust])    # A2E_MABU.py:615-637
-        elif aalg is not None:
-            em, pem, _ = a2e.run(engine, tables[idust], part, verbose=False, aalg=aalg)      # A2E_MABU.py:971-984
+        elif aalg is not None:                                 # (NSTOCH: the dust file's `nstoch`, A2E_MABU.py:938)
+            em, pem, _ = a2e.run(engine, tables[idust], part, NSTOCH=tables[idust].get("nstoch", NSTOCH_ALL), verbose=False, aalg=aalg)   # A2E_MABU.py:971-984
         else:
-            em, _ = a2e.run(engine, tables[idust], part, verbose=False)
+            em, _ = a2e.run(engine, tables[idust], part, NSTOCH=tables[idust].get("nstoch", NSTOCH_ALL), verbose=False)
         EM += em * ABU[:, idust:idust + 1]                     # A2E_MABU.py:1128-1140
         if pem is not None:
             PEM += pem * ABU[:, idust:idust + 1]               # A2E_MABU.py:1139-1147
@@ -343,11 +377,16 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
                     engine.mabu_split(idust, clip_last=True)                       # A2E.py:184-185
                     if aalg is not None:
                         upload_aalg(aalg, a, b)
-                    for isize in range(sol["NSIZE"]):                              # the sum over the sizes: A2E.py:596-600
+                    nstoch = stochastic_sizes(sol)
+                    for isize in range(nstoch):                                    # the sum over the sizes: A2E.py:596-600
                         engine.a2e_set_size(sol["NE"], NFREQ, sol["sizes"][isize], a2e_absorption_fraction(sol, isize))
                         if aalg is not None:
                             engine.a2e_set_size_aalg(sol["SIZE_A"], isize)         # A2E.py:413-429, in the kernel's epilogue
                         engine.a2e_resident_solve()
+                    eq = a2e.eq_sizes(sol, nstoch)                                 # the equilibrium sizes after them, as a2e.run adds them
+                    if eq:                                                         # (A2E.py:456-547; with aalg its hard mask, :533-539)
+                        engine.a2e_set_eq_sizes(*a2e.eq_size_tables(sol, eq, aalg is not None))
+                        engine.a2e_resident_solve_eq()
                 engine.mabu_accumulate(idust)
                 if aalg is not None:
                     engine.mabu_accumulate_p(idust)                                # A2E_MABU.py:1139-1147
