@@ -71,11 +71,15 @@ def _eq_table(sol, isize):
     return Emin, kE, oplgkE, TTT, np.asarray(KABS, np.float32)
 
 
+def stochastic_count(sol, NSTOCH):
+    """how many sizes of a solver file are solved stochastically: NSTOCH, at most the sizes the file has tables for"""
+    return max(min(int(NSTOCH), len(sol["sizes"]), sol["NSIZE"]), 0)
+
+
 def eq_sizes(sol, NSTOCH=999):
     """the sizes that a2e.run solves as equilibrium sizes, ascending: isize >= NSTOCH or without tables in the solver file, less those
     with S_FRAC < 1e-30, which it skips (A2E.py:466)"""
-    nstoch = min(int(NSTOCH), len(sol["sizes"]), sol["NSIZE"])
-    return [isize for isize in range(max(nstoch, 0), sol["NSIZE"]) if not sol["S_FRAC"][isize] < 1.0e-30]
+    return [isize for isize in range(stochastic_count(sol, NSTOCH), sol["NSIZE"]) if not sol["S_FRAC"][isize] < 1.0e-30]
 
 
 def eq_size_tables(sol, sizes, polarised=False):
@@ -88,6 +92,33 @@ def eq_size_tables(sol, sizes, polarised=False):
             np.asarray([t[1] for t in tabs], f32), np.asarray([t[2] for t in tabs], f32), f32(sol["GD"]),
             np.asarray([sol["S_FRAC"][isize] for isize in sizes], f32),
             np.asarray([sol["SIZE_A"][isize] for isize in sizes], f32) if polarised else None)
+
+
+def solve_sizes_resident(engine, sol, nstoch, polarised, eq=True, log=None):
+    """THE size loop on resident cells -- the block that a2e_resident_begin, or mabu_begin and mabu_split, opened: the sizes below nstoch
+    one launch each, in their order (A2E.py:596-600; polarised: with the weights of A2E.py:413-429 for the kernel's epilogue), then all
+    equilibrium sizes in one launch that adds them to the same sums (A2E.py:456-547; its hard mask, :533-539).  eq False leaves those to
+    the caller; eq 'try' does so as well where the engine refuses their tables (no tile of this NFREQ fits the LDS), and says so
+    through log.  Returns whether the equilibrium sizes were solved here."""
+    log = log or (lambda line: None)
+    for isize in range(nstoch):
+        engine.a2e_set_size(sol["NE"], sol["NFREQ"], sol["sizes"][isize], a2e_absorption_fraction(sol, isize))
+        if polarised:
+            engine.a2e_set_size_aalg(sol["SIZE_A"], isize)
+        engine.a2e_resident_solve()
+        log("    isize = %d   stochastic heating" % isize)
+    sizes = eq_sizes(sol, nstoch) if eq else []
+    if not sizes:
+        return False
+    try:
+        engine.a2e_set_eq_sizes(*eq_size_tables(sol, sizes, polarised))
+    except Exception as err:
+        if eq != 'try':
+            raise
+        log("    a2e: equilibrium sizes not on the device (%s)" % err)
+        return False
+    engine.a2e_resident_solve_eq()
+    return True
 
 
 def aalg_weights(ASIZE, isize, aalg, stochastic=True):
@@ -139,14 +170,12 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, 
     tker = 0.0
     # The stochastically heated sizes with the cells resident in device memory (soc_a2e_resident_*): absorptions up once, every size a
     # launch over all cells that adds its emission to a sum on the device, the sum down once -- instead of NSIZE round trips of every
-    # batch.  The sum is added in the order of the sizes, as the reference's host does (A2E.py:596-600), and the equilibrium sizes
-    # follow it (they come last in the loop: isize >= NSTOCH), so the result is the same to the bit.  With an engine that has
-    # a2e_resident_solve_eq the equilibrium sizes are solved there as well, all in one launch that adds them to the same sum in the
-    # same order, before the one download; an engine without it gets them size by size through a2e_eqtemp, as before.
-    nstoch = max(min(int(NSTOCH), len(sol["sizes"]), sol["NSIZE"]), 0)
-    eq_live = eq_sizes(sol, NSTOCH) if hasattr(engine, "a2e_resident_solve_eq") else []
+    # batch (solve_sizes_resident).  The sum is added in the order of the sizes, as the reference's host does, equilibrium sizes last,
+    # so the result is the same to the bit.  An engine without a2e_resident_solve_eq gets those size by size through a2e_eqtemp.
+    nstoch = stochastic_count(sol, NSTOCH)
+    eq = 'try' if hasattr(engine, "a2e_resident_solve_eq") else False       # (a refusal of the tables: size by size, as before)
     resident = eq_done = False
-    if (nstoch > 0 or eq_live) and hasattr(engine, "a2e_resident_begin") and (aalg is None or hasattr(engine, "a2e_resident_upload_aalg")):
+    if (nstoch > 0 or (eq and eq_sizes(sol, nstoch))) and hasattr(engine, "a2e_resident_begin") and (aalg is None or hasattr(engine, "a2e_resident_upload_aalg")):
         try:
             if aalg is None:
                 engine.a2e_resident_begin(CELLS, NFREQ)
@@ -163,29 +192,10 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, 
                 engine.a2e_resident_upload(icell, ABSORBED[icell:min(icell + batch, CELLS), :])
                 if aalg is not None:
                     engine.a2e_resident_upload_aalg(icell, aalg[icell:min(icell + batch, CELLS)])
-            for isize in range(nstoch):
-                engine.a2e_set_size(sol["NE"], NFREQ, sol["sizes"][isize], a2e_absorption_fraction(sol, isize))
-                if aalg is not None:
-                    engine.a2e_set_size_aalg(ASIZE, isize)       # (the kernel's epilogue adds W * emission to the second sum)
-                engine.a2e_resident_solve()
-                if verbose:
-                    print("    isize = %d   stochastic heating" % isize)
-            if eq_live:
-                try:
-                    engine.a2e_set_eq_sizes(*eq_size_tables(sol, eq_live, aalg is not None))
-                    eq_done = True
-                except Exception as err:                          # no tile of this NFREQ fits the LDS: size by size, as before
-                    if verbose:
-                        print("    a2e: equilibrium sizes not on the device (%s)" % err)
-                if eq_done:
-                    engine.a2e_resident_solve_eq()
+            eq_done = solve_sizes_resident(engine, sol, nstoch, aalg is not None, eq, print if verbose else None)
             for icell in range(0, CELLS, batch):
                 b = min(icell + batch, CELLS)
-                emit = engine.a2e_resident_download(icell, b - icell)
-                if IFREQ >= 0:
-                    EMITTED[icell:b, 0] += emit[:, IFREQ]
-                else:
-                    EMITTED[icell:b, :] += emit
+                EMITTED[icell:b] += engine.a2e_resident_download(icell, b - icell)[:, cols]
                 if aalg is not None:
                     PEMITTED[icell:b, :] += engine.a2e_resident_download_p(icell, b - icell)[:, cols]
             tker += time.time() - t0
@@ -204,10 +214,7 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, 
                 t0 = time.time()
                 T, emit = engine.a2e_eqtemp(icell, CELLS, NIP, FACTOR, kE, oplgkE, Emin, sol["FREQ"], KABS, TTT, tmp)
                 tker += time.time() - t0
-                if IFREQ >= 0:
-                    EMITTED[icell:b, 0] += emit[:, IFREQ] * scale
-                else:
-                    EMITTED[icell:b, :] += emit * scale
+                EMITTED[icell:b] += emit[:, cols] * scale
                 if aalg is not None:                               # A2E.py:533-539: the hard mask, the reference's own product
                     full = aalg_weights(ASIZE, isize, aalg[icell:b], stochastic=False)[0]
                     PEMITTED[icell:b][full] += emit[full][:, cols] * sol["GD"] * sol["S_FRAC"][isize]
@@ -220,10 +227,7 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, 
             t0 = time.time()
             emit = engine.a2e_solve(ABSORBED[icell:b, :])
             tker += time.time() - t0
-            if IFREQ >= 0:
-                EMITTED[icell:b, 0] += emit[:, IFREQ]
-            else:
-                EMITTED[icell:b, :] += emit
+            EMITTED[icell:b] += emit[:, cols]
             if aalg is not None:                                   # A2E.py:413-429, on the emission of this batch and size
                 _add_polarised(PEMITTED[icell:b], emit[:, cols], *aalg_weights(ASIZE, isize, aalg[icell:b]))
         if verbose:

@@ -93,16 +93,24 @@ int soc_a2e_upload(soc_ctx *c, int batch, const float *AABS)
     return SOC_OK;
 }
 
+// the kernel's arguments with the tables of the current size (soc_a2e_set_size) filled in; the cells are the caller's
+static SocA2EArgs a2e_tables(const soc_ctx *c)
+{
+    SocA2EArgs A{};
+    A.NE = c->a2e_NE;  A.NFREQ = c->a2e_NFREQ;  A.npair = c->a2e_npair;
+    A.Iw = c->aIw;  A.pair_first = c->aFirst;  A.pair_last = c->aLast;  A.pair_iw = c->aIwOff;  A.pair_dst = c->aDst;
+    A.Tdown = c->aTdown;  A.EA = c->aEA;  A.Ibeg = c->aIbeg;  A.AF = c->aAF;
+    return A;
+}
+
 int soc_a2e_run(soc_ctx *c, int batch)
 {
     if (!c) return SOC_ERR_ARG;
     FLUSH(c);
     HIPCHK(c, hipSetDevice(c->device));
     if (c->a2e_NE == 0 || batch < 1 || (size_t)batch * c->a2e_NFREQ > c->aEMIT.n) return fail(c, SOC_ERR_STATE, "soc_a2e_run: upload a batch first");
-    SocA2EArgs A{};
-    A.NE = c->a2e_NE;  A.NFREQ = c->a2e_NFREQ;  A.npair = c->a2e_npair;  A.batch = batch;
-    A.Iw = c->aIw;  A.pair_first = c->aFirst;  A.pair_last = c->aLast;  A.pair_iw = c->aIwOff;  A.pair_dst = c->aDst;
-    A.Tdown = c->aTdown;  A.EA = c->aEA;  A.Ibeg = c->aIbeg;  A.AF = c->aAF;  A.AABS = c->aABS;  A.AEMIT = c->aEMIT;
+    SocA2EArgs A = a2e_tables(c);
+    A.batch = batch;  A.AABS = c->aABS;  A.AEMIT = c->aEMIT;
     HIPCHK(c, soc_launch_a2e_dosolve(A, c->stream));
     return SOC_OK;
 }
@@ -124,6 +132,37 @@ static void resident_release(soc_ctx *c)
     c->a2e_cells = 0;  c->a2e_pol_set = false;
 }
 
+// aAll | aSum, zeroed, for cells x NFREQ floats; with polarised output aPSum, zeroed, and aAalg (else neither).  Both begins come here;
+// after an error the caller releases whatever it holds
+static hipError_t resident_alloc(soc_ctx *c, int64_t cells, int NFREQ, bool polarised)
+{
+    const size_t n = (size_t)cells * NFREQ;
+    hipError_t e = c->aAll.reset(n, c->stream);
+    if (e == hipSuccess) e = c->aSum.reset(n, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->aSum, 0, n * 4, c->stream);
+    if (polarised) {
+        if (e == hipSuccess) e = c->aPSum.reset(n, c->stream);
+        if (e == hipSuccess) e = c->aAalg.reset((size_t)cells * 2, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(c->aPSum, 0, n * 4, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(c->aAalg, 0xff, (size_t)cells * 8, c->stream);    // (NaN: rows never uploaded are aligned for no size)
+    } else {
+        c->aPSum.release();  c->aAalg.release();
+    }
+    c->a2e_pol_set = false;
+    return e;
+}
+
+// rows [c0, c0 + n) of a resident block, c->a2e_res_nfreq floats each, from or to the host; the range is the caller's to check
+static int rows_copy(soc_ctx *c, float *dst, const float *src, int64_t n, hipMemcpyKind kind)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(dst, src, (size_t)n * c->a2e_res_nfreq * 4, kind, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host buffer may be a temporary)
+    return SOC_OK;
+}
+static int rows_up(soc_ctx *c, float *buf, int64_t c0, int64_t n, const float *host) { return rows_copy(c, buf + (size_t)c0 * c->a2e_res_nfreq, host, n, hipMemcpyHostToDevice); }
+static int rows_down(soc_ctx *c, const float *buf, int64_t c0, int64_t n, float *host) { return rows_copy(c, host, buf + (size_t)c0 * c->a2e_res_nfreq, n, hipMemcpyDeviceToHost); }
+
 int soc_a2e_resident_begin(soc_ctx *c, int64_t cells, int NFREQ)
 {
     return soc_a2e_resident_begin_pol(c, cells, NFREQ, 0);
@@ -144,19 +183,7 @@ int soc_a2e_resident_begin_pol(soc_ctx *c, int64_t cells, int NFREQ, int polaris
     if (need + ((size_t)1 << 30) > free_b + held)
         return fail(c, SOC_ERR_STATE, "soc_a2e_resident_begin: %lld cells x %d frequencies need %.1f GB of device memory, %.1f GB are free (use soc_a2e_solve in batches)",
                     (long long)cells, NFREQ, need * 1e-9, free_b * 1e-9);
-    const size_t n = (size_t)cells * NFREQ;
-    hipError_t e = c->aAll.reset(n, c->stream);
-    if (e == hipSuccess) e = c->aSum.reset(n, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->aSum, 0, n * 4, c->stream);
-    if (polarised) {
-        if (e == hipSuccess) e = c->aPSum.reset(n, c->stream);
-        if (e == hipSuccess) e = c->aAalg.reset((size_t)cells * 2, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(c->aPSum, 0, n * 4, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(c->aAalg, 0xff, (size_t)cells * 8, c->stream);    // (NaN: rows never uploaded are aligned for no size)
-    } else {
-        c->aPSum.release();  c->aAalg.release();
-    }
-    c->a2e_pol_set = false;
+    const hipError_t e = resident_alloc(c, cells, NFREQ, polarised != 0);
     if (e != hipSuccess) {                                  // all or nothing: half of the arrays would be gigabytes nobody can use
         resident_release(c);
         return fail(c, SOC_ERR_HIP, "soc_a2e_resident_begin: %s", hipGetErrorString(e));
@@ -168,18 +195,15 @@ int soc_a2e_resident_begin_pol(soc_ctx *c, int64_t cells, int NFREQ, int polaris
 int soc_a2e_resident_upload(soc_ctx *c, int64_t c0, int64_t n, const float *AABS)
 {
     if (!c || !AABS) return SOC_ERR_ARG;
-    if (!c->aAll || c0 < 0 || n < 1 || c0 + n > c->a2e_cells) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_upload: cells [%lld, %lld) of %lld", (long long)c0, (long long)(c0 + n), (long long)c->a2e_cells);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->aAll + (size_t)c0 * c->a2e_res_nfreq, AABS, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host buffer may be a temporary)
-    return SOC_OK;
+    SOC_ROWS(c, "soc_a2e_resident_upload", c0, n, c->aAll ? c->a2e_cells : 0);      // (nothing open: no row can be addressed)
+    return rows_up(c, c->aAll, c0, n, AABS);
 }
 
 int soc_a2e_resident_upload_aalg(soc_ctx *c, int64_t c0, int64_t n, const float *aalg, const float *lgaalg)
 {
     if (!c || !aalg || !lgaalg) return SOC_ERR_ARG;
     if (!c->aAalg || !c->aPSum) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_upload_aalg: polarised output was not asked for (soc_a2e_resident_begin_pol, soc_mabu_begin_pol)");
-    if (c0 < 0 || n < 1 || c0 + n > c->a2e_cells) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_upload_aalg: cells [%lld, %lld) of %lld", (long long)c0, (long long)(c0 + n), (long long)c->a2e_cells);
+    SOC_ROWS(c, "soc_a2e_resident_upload_aalg", c0, n, c->a2e_cells);
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<float> both((size_t)n * 2);
     for (int64_t i = 0; i < n; i++) { both[2 * i] = aalg[i];  both[2 * i + 1] = lgaalg[i]; }
@@ -203,10 +227,7 @@ int soc_a2e_resident_solve(soc_ctx *c)
     if (!c->aAll) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve: call soc_a2e_resident_begin first");
     if (c->a2e_NE == 0 || c->a2e_NFREQ != c->a2e_res_nfreq) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve: soc_a2e_set_size with NFREQ = %d first", c->a2e_res_nfreq);
     HIPCHK(c, hipSetDevice(c->device));
-    SocA2EArgs A{};
-    A.NE = c->a2e_NE;  A.NFREQ = c->a2e_NFREQ;  A.npair = c->a2e_npair;
-    A.Iw = c->aIw;  A.pair_first = c->aFirst;  A.pair_last = c->aLast;  A.pair_iw = c->aIwOff;  A.pair_dst = c->aDst;
-    A.Tdown = c->aTdown;  A.EA = c->aEA;  A.Ibeg = c->aIbeg;  A.AF = c->aAF;
+    SocA2EArgs A = a2e_tables(c);
     A.accumulate = 1;
     const bool pol = c->aPSum && c->aAalg && c->a2e_pol_set;   // (a size without soc_a2e_set_size_aalg adds nothing to the polarised sum)
     if (pol) { A.p_size = c->a2e_pol[0];  A.p_next = c->a2e_pol[1];  A.p_lgsize = c->a2e_pol[2];  A.p_lgden = c->a2e_pol[3]; }
@@ -279,22 +300,16 @@ int soc_a2e_resident_solve_eq(soc_ctx *c)
 int soc_a2e_resident_download(soc_ctx *c, int64_t c0, int64_t n, float *AEMIT)
 {
     if (!c || !AEMIT) return SOC_ERR_ARG;
-    if (!c->aSum || c0 < 0 || n < 1 || c0 + n > c->a2e_cells) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_download: cells [%lld, %lld) of %lld", (long long)c0, (long long)(c0 + n), (long long)c->a2e_cells);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(AEMIT, c->aSum + (size_t)c0 * c->a2e_res_nfreq, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SOC_OK;
+    SOC_ROWS(c, "soc_a2e_resident_download", c0, n, c->aSum ? c->a2e_cells : 0);
+    return rows_down(c, c->aSum, c0, n, AEMIT);
 }
 
 int soc_a2e_resident_download_p(soc_ctx *c, int64_t c0, int64_t n, float *PEMIT)
 {
     if (!c || !PEMIT) return SOC_ERR_ARG;
     if (!c->aPSum) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_download_p: polarised output was not asked for (soc_a2e_resident_begin_pol, soc_mabu_begin_pol)");
-    if (c0 < 0 || n < 1 || c0 + n > c->a2e_cells) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_download_p: cells [%lld, %lld) of %lld", (long long)c0, (long long)(c0 + n), (long long)c->a2e_cells);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(PEMIT, c->aPSum + (size_t)c0 * c->a2e_res_nfreq, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SOC_OK;
+    SOC_ROWS(c, "soc_a2e_resident_download_p", c0, n, c->a2e_cells);
+    return rows_down(c, c->aPSum, c0, n, PEMIT);
 }
 
 int soc_a2e_resident_end(soc_ctx *c)
@@ -397,22 +412,14 @@ int soc_mabu_begin_pol(soc_ctx *c, int64_t cells, int NFREQ, int NDUST, int pola
                     (long long)cells, NFREQ, NDUST, need * 1e-9, free_b * 1e-9, (long long)(free_b > reserve ? (free_b - reserve) / per_cell : 0));
     const size_t n = (size_t)cells * NFREQ;
     hipError_t e = c->mABS.reset(n, c->stream);
-    if (e == hipSuccess) e = c->aAll.reset(n, c->stream);
-    if (e == hipSuccess) e = c->aSum.reset(n, c->stream);
+    if (e == hipSuccess) e = resident_alloc(c, cells, NFREQ, polarised != 0);
     if (e == hipSuccess) e = c->mSUM.reset(n, c->stream);
     if (e == hipSuccess) e = c->mABU.reset((size_t)cells * NDUST, c->stream);
     if (e == hipSuccess) e = c->mT.reset((size_t)cells, c->stream);
     if (e == hipSuccess) e = c->mRABS.reset((size_t)NFREQ * NDUST, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->mSUM, 0, n * 4, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->aSum, 0, n * 4, c->stream);
-    if (polarised) {
-        if (e == hipSuccess) e = c->aPSum.reset(n, c->stream);
-        if (e == hipSuccess) e = c->mPSUM.reset(n, c->stream);
-        if (e == hipSuccess) e = c->aAalg.reset((size_t)cells * 2, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(c->aPSum, 0, n * 4, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(c->mPSUM, 0, n * 4, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(c->aAalg, 0xff, (size_t)cells * 8, c->stream);
-    }
+    if (e == hipSuccess && polarised) e = c->mPSUM.reset(n, c->stream);
+    if (e == hipSuccess && polarised) e = hipMemsetAsync(c->mPSUM, 0, n * 4, c->stream);
     if (e != hipSuccess) {
         mabu_release(c);
         return fail(c, SOC_ERR_HIP, "soc_mabu_begin: %s", hipGetErrorString(e));
@@ -425,21 +432,13 @@ int soc_mabu_begin_pol(soc_ctx *c, int64_t cells, int NFREQ, int NDUST, int pola
     do {                                                                                                    \
         if (!(c)->mABS || !(c)->aAll || !(c)->aSum) return fail((c), SOC_ERR_STATE, who ": call soc_mabu_begin first");   \
     } while (0)
-#define MABU_ROWS(c, who, c0, n)                                                                            \
-    do {                                                                                                    \
-        if ((c0) < 0 || (n) < 1 || (c0) + (n) > (c)->a2e_cells)                                             \
-            return fail((c), SOC_ERR_ARG, who ": cells [%lld, %lld) of %lld", (long long)(c0), (long long)((c0) + (n)), (long long)(c)->a2e_cells);   \
-    } while (0)
 
 int soc_mabu_upload(soc_ctx *c, int64_t c0, int64_t n, const float *ABS)
 {
     if (!c || !ABS) return SOC_ERR_ARG;
     MABU_OPEN(c, "soc_mabu_upload");
-    MABU_ROWS(c, "soc_mabu_upload", c0, n);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->mABS + (size_t)c0 * c->a2e_res_nfreq, ABS, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host buffer may be a temporary)
-    return SOC_OK;
+    SOC_ROWS(c, "soc_mabu_upload", c0, n, c->a2e_cells);
+    return rows_up(c, c->mABS, c0, n, ABS);
 }
 
 int soc_mabu_set_tables(soc_ctx *c, const float *ABU, const double *RABS)
@@ -549,20 +548,12 @@ int soc_mabu_ratio(soc_ctx *c)
     return SOC_OK;
 }
 
-static int mabu_read(soc_ctx *c, const float *src, int64_t c0, int64_t n, float *out)
-{
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, src + (size_t)c0 * c->a2e_res_nfreq, (size_t)n * c->a2e_res_nfreq * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SOC_OK;
-}
-
 int soc_mabu_download(soc_ctx *c, int64_t c0, int64_t n, float *SUM)
 {
     if (!c || !SUM) return SOC_ERR_ARG;
     MABU_OPEN(c, "soc_mabu_download");
-    MABU_ROWS(c, "soc_mabu_download", c0, n);
-    return mabu_read(c, c->mSUM, c0, n, SUM);
+    SOC_ROWS(c, "soc_mabu_download", c0, n, c->a2e_cells);
+    return rows_down(c, c->mSUM, c0, n, SUM);
 }
 
 int soc_mabu_download_p(soc_ctx *c, int64_t c0, int64_t n, float *PSUM)
@@ -570,16 +561,16 @@ int soc_mabu_download_p(soc_ctx *c, int64_t c0, int64_t n, float *PSUM)
     if (!c || !PSUM) return SOC_ERR_ARG;
     MABU_OPEN(c, "soc_mabu_download_p");
     MABU_POL(c, "soc_mabu_download_p");
-    MABU_ROWS(c, "soc_mabu_download_p", c0, n);
-    return mabu_read(c, c->mPSUM, c0, n, PSUM);
+    SOC_ROWS(c, "soc_mabu_download_p", c0, n, c->a2e_cells);
+    return rows_down(c, c->mPSUM, c0, n, PSUM);
 }
 
 int soc_mabu_read_part(soc_ctx *c, int64_t c0, int64_t n, float *PART)
 {
     if (!c || !PART) return SOC_ERR_ARG;
     MABU_OPEN(c, "soc_mabu_read_part");
-    MABU_ROWS(c, "soc_mabu_read_part", c0, n);
-    return mabu_read(c, c->aAll, c0, n, PART);
+    SOC_ROWS(c, "soc_mabu_read_part", c0, n, c->a2e_cells);
+    return rows_down(c, c->aAll, c0, n, PART);
 }
 
 int soc_mabu_end(soc_ctx *c)

@@ -11,12 +11,7 @@
     do {                                                                                                    \
         if (!(c)->eET || (c)->et_nfreq < 1) return fail((c), SOC_ERR_STATE, who ": call soc_emitted_begin first");   \
     } while (0)
-#define EMITTED_ROWS(c, who, c0, n)                                                                         \
-    do {                                                                                                    \
-        if ((c0) < 0 || (n) < 1 || (c0) > (int64_t)(c)->G.CELLS || (n) > (int64_t)(c)->G.CELLS - (c0))      \
-            return fail((c), SOC_ERR_ARG, who ": cells [%lld, %lld) of %d", (long long)(c0),                \
-                        (long long)((unsigned long long)(c0) + (unsigned long long)(n)), (c)->G.CELLS);     \
-    } while (0)
+#define EMITTED_ROWS(c, who, c0, n) SOC_ROWS(c, who, c0, n, (c)->G.CELLS)
 
 #pragma GCC visibility push(default)
 extern "C" {

@@ -5,6 +5,7 @@
 #include "../../include/soc_hip.h"
 #include "soc_dev.h"
 #include "soc_devbuf.h"
+#include "soc_rows.h"
 
 #include <string>
 #include <vector>
@@ -167,6 +168,15 @@ SOC_HIDDEN int fail(soc_ctx *c, int code, const char *fmt, ...);
         hipError_t e_ = (call);                                                               \
         if (e_ != hipSuccess)                                                                 \
             return fail((c), SOC_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));     \
+    } while (0)
+
+// Rows [c0, c0 + n) of a resident block of `cells` rows, or the call is refused: THE range check of every transfer call (soc_a2e_resident_*,
+// soc_mabu_*, soc_emitted_*, soc_absorbed_*).  The sum is formed for the text alone, unsigned, so a refused huge range prints without overflow
+#define SOC_ROWS(c, who, c0, n, cells)                                                                      \
+    do {                                                                                                    \
+        if (!soc_rows_ok((c0), (n), (cells)))                                                               \
+            return fail((c), SOC_ERR_ARG, who ": cells [%lld, %lld) of %lld", (long long)(c0),              \
+                        (long long)((unsigned long long)(c0) + (unsigned long long)(n)), (long long)(cells));   \
     } while (0)
 
 // Execute the launches deferred since soc_batch_begin (soc_capi.hip)

@@ -264,6 +264,15 @@ def _i(a):
     return None if a is None else a.ctypes.data_as(_I)
 
 
+def _rows_out(who, n, NFREQ, out):
+    """the rows [n, NFREQ] that a download fills: new ones, or the caller's `out` -- the library writes n x NFREQ floats to whatever it gets"""
+    if out is None:
+        return np.zeros((max(int(n), 0), NFREQ), np.float32)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable and out.shape == (int(n), NFREQ)):
+        raise SocError("%s: out must be a writeable C-contiguous float32 array of shape (%d, %d)" % (who, int(n), NFREQ))
+    return out
+
+
 def _view_vectors(*vectors):
     """(DIR, RA, DE, CENTRE, INTOBS) of a map call as the float3 the C ABI takes: three contiguous floats each, None kept"""
     return [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).ravel()[:3]) for a in vectors]
@@ -284,6 +293,7 @@ class Engine:
         self.CELLS = 0
         self.NPAR = 0
         self.LEVELS = 0
+        self._a2e_res = (0, 0)                             # (cells, NFREQ) of the resident block of the last a2e_resident_begin or mabu_begin
         self._mabu = None                                  # (cells, NFREQ, NDUST) between mabu_begin and mabu_end
         self._emitted = None                               # NFREQ between emitted_begin and emitted_end (set_grid ends it)
         self._absorbed = None                              # NFREQ between absorbed_begin and absorbed_end (set_grid ends it)
@@ -961,12 +971,14 @@ class Engine:
         self._chk(self.lib.soc_a2e_set_size_aalg(self.h, ASIZE[isize], np.float32(0.0) if last else ASIZE[isize + 1], np.float32(lg), np.float32(step)))
 
     def a2e_resident_download_p(self, c0, n, out=None):
-        out = np.zeros((int(n), self._a2e_res[1]), np.float32) if out is None else out
+        out = _rows_out("a2e_resident_download_p", n, self._a2e_res[1], out)
         self._chk(self.lib.soc_a2e_resident_download_p(self.h, int(c0), int(n), _f(out)))
         return out
 
     def a2e_resident_upload(self, c0, AABS):
         AABS = np.ascontiguousarray(AABS, np.float32)
+        if AABS.ndim != 2 or AABS.shape[1] != self._a2e_res[1]:
+            raise SocError("a2e_resident_upload: an array of shape %s for rows of %d frequencies" % (AABS.shape, self._a2e_res[1]))
         self._chk(self.lib.soc_a2e_resident_upload(self.h, int(c0), AABS.shape[0], _f(AABS)))
 
     def a2e_resident_solve(self):
@@ -993,7 +1005,7 @@ class Engine:
         self._chk(self.lib.soc_a2e_resident_solve_eq(self.h))
 
     def a2e_resident_download(self, c0, n, out=None):
-        out = np.zeros((int(n), self._a2e_res[1]), np.float32) if out is None else out
+        out = _rows_out("a2e_resident_download", n, self._a2e_res[1], out)
         self._chk(self.lib.soc_a2e_resident_download(self.h, int(c0), int(n), _f(out)))
         return out
 
@@ -1043,6 +1055,7 @@ class Engine:
             raise DoesNotFit("%s (code %d)" % (self.lib.soc_last_error(self.h).decode(), rc), fit.value)
         self._chk(rc)
         self._mabu = (int(cells), int(NFREQ), int(NDUST))
+        self._a2e_res = self._mabu[:2]                     # (the dust's share and its emission are the arrays of a2e_resident_*)
 
     def _mabu_open(self, who):
         """(cells, NFREQ, NDUST) of the open mabu_begin"""
@@ -1080,12 +1093,7 @@ class Engine:
 
     def mabu_download(self, c0, n, out=None):
         """rows [c0, c0 + n) of the sum; out: a C-contiguous float32 array [n, NFREQ] to fill (anything else is refused)"""
-        NFREQ = self._mabu_open("mabu_download")[1]
-        if out is None:
-            out = np.zeros((int(n), NFREQ), np.float32)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable
-                  and out.shape == (int(n), NFREQ)):
-            raise SocError("mabu_download: out must be a writeable C-contiguous float32 array of shape (%d, %d)" % (int(n), NFREQ))
+        out = _rows_out("mabu_download", n, self._mabu_open("mabu_download")[1], out)
         self._chk(self.lib.soc_mabu_download(self.h, int(c0), int(n), _f(out)))
         return out
 
@@ -1106,17 +1114,12 @@ class Engine:
 
     def mabu_download_p(self, c0, n, out=None):
         """rows [c0, c0 + n) of the polarised sum -- after mabu_ratio, of R; out as in mabu_download"""
-        NFREQ = self._mabu_open("mabu_download_p")[1]
-        if out is None:
-            out = np.zeros((int(n), NFREQ), np.float32)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable
-                  and out.shape == (int(n), NFREQ)):
-            raise SocError("mabu_download_p: out must be a writeable C-contiguous float32 array of shape (%d, %d)" % (int(n), NFREQ))
+        out = _rows_out("mabu_download_p", n, self._mabu_open("mabu_download_p")[1], out)
         self._chk(self.lib.soc_mabu_download_p(self.h, int(c0), int(n), _f(out)))
         return out
 
     def mabu_read_part(self, c0, n):
-        out = np.zeros((int(n), self._mabu_open("mabu_read_part")[1]), np.float32)
+        out = _rows_out("mabu_read_part", n, self._mabu_open("mabu_read_part")[1], None)
         self._chk(self.lib.soc_mabu_read_part(self.h, int(c0), int(n), _f(out)))
         return out
 
@@ -1159,11 +1162,7 @@ class Engine:
 
     def emitted_download(self, c0, n, out=None):
         """rows [c0, c0 + n) back as [n, NFREQ]; out: a writeable C-contiguous float32 array of that shape to fill"""
-        NFREQ = self._emitted_rows("emitted_download", n, out)
-        if out is None:
-            out = np.zeros((int(n), NFREQ), np.float32)
-        elif not out.flags.writeable:
-            raise SocError("emitted_download: out must be writeable")
+        out = _rows_out("emitted_download", n, self._emitted_rows("emitted_download", 0, None), out)
         self._chk(self.lib.soc_emitted_download(self.h, int(c0), int(n), _f(out)))
         return out
 
@@ -1266,11 +1265,7 @@ class Engine:
         """rows [c0, c0 + n) back as [n, NFREQ]: scaled as absorbed_to_mabu hands them over, or, with K None, bit for bit what was
         accumulated; out: a writeable C-contiguous float32 array of that shape to fill"""
         NFREQ, K = self._absorbed_open("absorbed_download", K)
-        if out is None:
-            out = np.zeros((max(int(n), 0), NFREQ), np.float32)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable
-                  and out.shape == (int(n), NFREQ)):
-            raise SocError("absorbed_download: out must be a writeable C-contiguous float32 array of shape (%d, %d)" % (int(n), NFREQ))
+        out = _rows_out("absorbed_download", n, NFREQ, out)
         self._chk(self.lib.soc_absorbed_download(self.h, int(c0), int(n), _f(out), _f(K), np.float32(nnnlimit)))
         return out
 
@@ -1332,7 +1327,7 @@ class Engine:
             cells, cols = ABS3.shape[0], None
         else:
             cols = np.ascontiguousarray(cols, np.int32)
-            if cols.size != 3 or getattr(self, "_a2e_res", None) is None:
+            if cols.size != 3 or not self._a2e_res[0]:
                 raise SocError("library_build: ABS3, or three columns of the resident absorptions")
             cells = self._a2e_res[0]
         if not 2 <= N <= 64:

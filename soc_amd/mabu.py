@@ -45,7 +45,6 @@ from .asoc import ResidentAbsorptions, UnsupportedOption
 from .ini import User
 from .launch import FACTOR
 from .lib import DoesNotFit
-from .synth import a2e_absorption_fraction
 
 NE_EQ = 30000                    # A2E_MABU.py:478
 NSTOCH_ALL = 9999                # A2E_MABU.py:124: a gsetdust file without an `nstoch` line -- every size is stochastically heated
@@ -100,7 +99,7 @@ def read_nstoch(name, kind=None):
 def stochastic_sizes(sol):
     """how many sizes of a solver file (read by _tables) are solved stochastically: its dust file's `nstoch`, at most the sizes the
     file has tables for; the rest are equilibrium sizes"""
-    return max(min(int(sol.get("nstoch", NSTOCH_ALL)), len(sol["sizes"]), sol["NSIZE"]), 0)
+    return a2e.stochastic_count(sol, sol.get("nstoch", NSTOCH_ALL))
 
 
 def require_solvers(dusts, kinds):
@@ -377,16 +376,7 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
                     engine.mabu_split(idust, clip_last=True)                       # A2E.py:184-185
                     if aalg is not None:
                         upload_aalg(aalg, a, b)
-                    nstoch = stochastic_sizes(sol)
-                    for isize in range(nstoch):                                    # the sum over the sizes: A2E.py:596-600
-                        engine.a2e_set_size(sol["NE"], NFREQ, sol["sizes"][isize], a2e_absorption_fraction(sol, isize))
-                        if aalg is not None:
-                            engine.a2e_set_size_aalg(sol["SIZE_A"], isize)         # A2E.py:413-429, in the kernel's epilogue
-                        engine.a2e_resident_solve()
-                    eq = a2e.eq_sizes(sol, nstoch)                                 # the equilibrium sizes after them, as a2e.run adds them
-                    if eq:                                                         # (A2E.py:456-547; with aalg its hard mask, :533-539)
-                        engine.a2e_set_eq_sizes(*a2e.eq_size_tables(sol, eq, aalg is not None))
-                        engine.a2e_resident_solve_eq()
+                    a2e.solve_sizes_resident(engine, sol, stochastic_sizes(sol), aalg is not None)   # (a refusal of a call ends the stage)
                 engine.mabu_accumulate(idust)
                 if aalg is not None:
                     engine.mabu_accumulate_p(idust)                                # A2E_MABU.py:1139-1147

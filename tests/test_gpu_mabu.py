@@ -131,8 +131,83 @@ def test_binding_refuses_what_the_library_cannot_check(engine):
     try:
         with pytest.raises(SocError, match="soc_a2e_resident_end first"):
             engine.mabu_begin(10, 4, 2)
+        with pytest.raises(SocError, match=r"shape \(5, 3\)"):
+            engine.a2e_resident_upload(0, np.zeros((5, 3), np.float32))   # narrower rows: the library would read past the array
+        readonly = np.zeros((5, 4), np.float32)
+        readonly.flags.writeable = False
+        for out in (np.zeros((5, 4), np.float64), np.zeros((5, 8), np.float32)[:, ::2], readonly, np.zeros((4, 4), np.float32),
+                    np.zeros((5, 5), np.float32), np.zeros(20, np.float32)):   # the library would write 5 x 4 floats to any of them
+            with pytest.raises(SocError, match=r"writeable C-contiguous float32 array of shape \(5, 4\)"):
+                engine.a2e_resident_download(0, 5, out=out)
+        assert not readonly.any() and engine.a2e_resident_download(0, 5, out=np.ones((5, 4), np.float32)).sum() == 0
     finally:
         engine.a2e_resident_end()
+
+
+REFUSED = [(8, 4), (10, 1), (-1, 1), (0, 0)]         # rows [c0, c0 + n) of 10: past the end, from the end on, from before the first, none
+ACCEPTED = [(9, 1), (0, 10)]
+
+
+def rows_are_checked(upload, download, want=None):
+    """every range of REFUSED through the two calls (either may be None) is refused with the library's text, every one of ACCEPTED is
+    taken; the rows that come down are those that went up -- or, with no upload, `want` -- to the bit"""
+    from soc_amd.lib import SocError
+    rows = np.random.default_rng(10).integers(0, 2 ** 32, (10, 4), dtype=np.uint64).astype(np.uint32).view(np.float32) if want is None else want
+    for c0, n in REFUSED:
+        for call in ([lambda: upload(c0, np.zeros((n, 4), np.float32))] if upload else []) + ([lambda: download(c0, n)] if download else []):
+            with pytest.raises(SocError, match=r"cells \[%d, %d\) of 10" % (c0, c0 + n)):
+                call()
+    for c0, n in ACCEPTED:
+        if upload:
+            upload(c0, rows[c0:c0 + n])
+        if download:
+            got = download(c0, n)
+            assert got.shape == (n, 4) and np.array_equal(got.view(np.uint32), rows[c0:c0 + n].view(np.uint32)), (c0, n)
+
+
+def test_every_transfer_call_checks_its_rows(engine):
+    """10 cells, 4 frequencies, 2 dusts, polarised: the one range check of the library (SOC_ROWS) as every transfer call makes it"""
+    from soc_amd import mabu
+    from soc_amd.lib import SocError
+    zero = np.zeros((10, 4), np.float32)
+    engine.a2e_resident_begin(10, 4, polarised=True)
+    try:
+        rows_are_checked(engine.a2e_resident_upload, None)
+        rows_are_checked(None, engine.a2e_resident_download, zero)         # (the sums of a block just opened)
+        rows_are_checked(None, engine.a2e_resident_download_p, zero)
+        for c0, n in REFUSED[:3]:
+            with pytest.raises(SocError, match=r"cells \[%d, %d\) of 10" % (c0, c0 + n)):
+                engine.a2e_resident_upload_aalg(c0, np.ones(n, np.float32))
+        with pytest.raises(SocError, match="one value per cell"):
+            engine.a2e_resident_upload_aalg(0, np.ones(0, np.float32))
+        for c0, n in ACCEPTED:
+            engine.a2e_resident_upload_aalg(c0, np.ones(n, np.float32))
+    finally:
+        engine.a2e_resident_end()
+    engine.mabu_begin(10, 4, 2, polarised=True)
+    try:
+        rows_are_checked(engine.a2e_resident_upload, engine.mabu_read_part)   # (the dust's share: what a2e_resident_upload fills)
+        rows_are_checked(None, engine.mabu_download, zero)
+        rows_are_checked(None, engine.mabu_download_p, zero)
+        ABS, ABU, R = split_inputs(4, 2, 11)
+        ABS, ABU = ABS[:10], ABU[:10]
+        rows_are_checked(engine.mabu_upload, None, ABS)
+        engine.mabu_set_tables(ABU, R)
+        engine.mabu_split(1)                                                  # ... and the rows that went up are those it splits
+        assert np.array_equal(engine.mabu_read_part(0, 10), mabu.split_absorbed(ABS, R, ABU, 1), equal_nan=True)
+    finally:
+        engine.mabu_end()
+    engine.set_grid(5, 2, 1, 1, [10], np.ones(10, np.float32))
+    engine.emitted_begin(4)
+    try:
+        rows_are_checked(engine.emitted_upload, engine.emitted_download)
+    finally:
+        engine.emitted_end()
+    engine.absorbed_begin(4)
+    try:
+        rows_are_checked(None, engine.absorbed_download, zero)
+    finally:
+        engine.absorbed_end()
 
 
 def test_calls_out_of_order_and_out_of_range_are_refused(engine):
@@ -152,6 +227,7 @@ def test_calls_out_of_order_and_out_of_range_are_refused(engine):
             engine.mabu_split(2)
     finally:
         engine.mabu_end()
+    test_every_transfer_call_checks_its_rows(engine)             # (the ranges of every transfer call: the test above, here in its order)
 
 
 @pytest.fixture(scope="module")
