@@ -830,6 +830,47 @@ int soc_library_solve_resident(soc_ctx *ctx, const int32_t *col, int32_t *miss, 
 int soc_library_build(soc_ctx *ctx, int N, int64_t cells, const float *ABS3, const int32_t *col, float *I0, float *dI0, float *I1,
                       float *dI1, float *I2, float *dI2, int32_t *IND, float *XX, float *YY, float *ZZ);
 
+/* ---- the library method for a model with several dust components: a library per dust, one fused look-up ---- */
+
+/* Every dust d of a multi-dust model has its own library (a <dust>.mlib file in the byte layout of .lib), indexed by the log10 of
+ * that dust's share of the absorptions at the three reference frequencies,
+ * share_f = ABS3[f] * RABS3[f][d] / sum_j ABU[j] * RABS3[f][j] with the types of soc_mabu_split (every product in double, the sum
+ * rounded to float after every dust, the quotient in double, rounded once).  One kernel forms the shares, looks every dust up
+ * with the arithmetic of soc_library_solve and writes SUM = ((0 + E_0*ABU_0) + E_1*ABU_1) + ...: float products, float sums, in
+ * dust order, a dust without an answer adding 0 * ABU_d (what a zeroed row adds on the host).
+ *   soc_mabu_library_begin(cells, NDUST, nout, &fit) reserves ABS3[cells][3], ABU[cells][NDUST], SUM[cells][nout] and MISS[cells]
+ *       (12 + 4*NDUST + 4*nout + 4 bytes per cell).  1 <= NDUST <= 32, the width of the miss mask, and 1 <= nout <= 4096, else
+ *       SOC_ERR_ARG.  *fit (may be NULL) receives the number of cells that fit the free device memory; when `cells` do not, the call
+ *       fails with SOC_ERR_STATE and the caller loops over ranges of at most *fit, as with soc_mabu_begin.  A second _begin replaces
+ *       the first, the libraries included;
+ *   soc_mabu_library_set(idust, N, NFREQ, I0, ..., E, nout, ocol) makes the library of dust idust resident: the arguments of
+ *       soc_library_set, E reduced to the nout columns ocol[nout] at upload (ocol NULL: all, and nout is taken as NFREQ); the
+ *       number of columns must be the nout of _begin.  2 <= N <= 64;
+ *   soc_mabu_library_upload(c0, n, ABS3) fills rows [c0, c0+n) of the absorptions at the reference frequencies (any chunking);
+ *   soc_mabu_library_set_tables(ABU, RABS3) uploads ABU[cells][NDUST] and RABS3[3][NDUST] (double), once;
+ *   soc_mabu_library_solve() runs the kernel over all cells: SOC_ERR_STATE unless every dust has its library and the tables are set;
+ *   soc_mabu_library_download(c0, n, SUM) reads rows [c0, c0+n) of SUM[cells][nout];
+ *   soc_mabu_library_misses(c0, n, MISS) reads MISS of those cells: bit d set where dust d had no answer;
+ *   soc_mabu_library_end() frees it all.
+ * Every call but _begin and _end is SOC_ERR_STATE before soc_mabu_library_begin; rows outside [0, cells) are SOC_ERR_ARG.  The
+ * family shares nothing with soc_mabu_begin or soc_library_set: either may be open beside it. */
+int soc_mabu_library_begin(soc_ctx *ctx, int64_t cells, int NDUST, int nout, int64_t *cells_fit);
+int soc_mabu_library_set(soc_ctx *ctx, int idust, int N, int NFREQ, float I0, float dI0, const float *I1, const float *dI1,
+                         const float *I2, const float *dI2, const float *X, const float *Y, const float *Z, const float *E, int nout,
+                         const int32_t *ocol);
+int soc_mabu_library_upload(soc_ctx *ctx, int64_t c0, int64_t n, const float *ABS3);
+int soc_mabu_library_set_tables(soc_ctx *ctx, const float *ABU, const double *RABS3);
+int soc_mabu_library_solve(soc_ctx *ctx);
+int soc_mabu_library_download(soc_ctx *ctx, int64_t c0, int64_t n, float *SUM);
+int soc_mabu_library_misses(soc_ctx *ctx, int64_t c0, int64_t n, uint32_t *MISS);
+int soc_mabu_library_end(soc_ctx *ctx);
+
+/* Building such a library is a by-product of the full solve: after a dust's emission is in EM of the open soc_mabu_begin (and
+ * soc_library_build has named the representative cells from its share PART),
+ *   soc_mabu_gather_rows(idx, n, out) reads out[n][NFREQ] = the rows idx[n] of EM (repeats allowed; an index outside the resident
+ *       cells is SOC_ERR_ARG, no open soc_mabu_begin SOC_ERR_STATE). */
+int soc_mabu_gather_rows(soc_ctx *ctx, const int32_t *idx, int64_t n, float *out);
+
 /* ---- verification probes (used by the parity tests only) ---- */
 /* RNG stream states and first draws of logical work items [gid_first, gid_first+n)
  * (MWC64X_SeedStreams + MWC64X_NextUint, mwc64x_rng.cl:35-48) */

@@ -13,9 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsoc_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["soc_kernels.hip", "soc_split.hip", "soc_brick.hip", "soc_a2e.hip", "soc_a2e_pre.hip", "soc_mabu.hip", "soc_reemit.hip", "soc_library.hip", "soc_sca.hip", "soc_emit.hip", "soc_map.hip", "soc_capi.hip",
-           "soc_capi_post.hip", "soc_capi_a2e.hip", "soc_capi_reemit.hip", "soc_capi_absorbed.hip", "soc_capi_library.hip", "soc_capi_probe.hip"]
-HEADERS = ["soc_host.h", "soc_rows.h", "soc_devbuf.h", "soc_dev.h", "soc_math.h", "soc_rng.h", "soc_walk.h", "soc_ltree.h", "soc_lbricks.h", "soc_octbricks.h", os.path.join("..", "..", "include", "soc_hip.h")]
+SOURCES = ["soc_kernels.hip", "soc_split.hip", "soc_brick.hip", "soc_a2e.hip", "soc_a2e_pre.hip", "soc_mabu.hip", "soc_mabu_library.hip", "soc_reemit.hip", "soc_library.hip", "soc_sca.hip", "soc_emit.hip", "soc_map.hip", "soc_capi.hip",
+           "soc_capi_post.hip", "soc_capi_a2e.hip", "soc_capi_reemit.hip", "soc_capi_absorbed.hip", "soc_capi_library.hip", "soc_capi_mabu_library.hip", "soc_capi_probe.hip"]
+HEADERS = ["soc_host.h", "soc_rows.h", "soc_devbuf.h", "soc_dev.h", "soc_math.h", "soc_lookup.h", "soc_rng.h", "soc_walk.h", "soc_ltree.h", "soc_lbricks.h", "soc_octbricks.h", os.path.join("..", "..", "include", "soc_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-munsafe-fp-atomics", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 

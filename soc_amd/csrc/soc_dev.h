@@ -349,6 +349,33 @@ hipError_t soc_launch_library_range(const SocLibBuild &A, int level, unsigned *T
 // BEST[N^3] all ones before the launch; IND, XX, YY, ZZ [N^3]
 hipError_t soc_launch_library_pick(const SocLibBuild &A, unsigned long long *BEST, int *IND, float *XX, float *YY, float *ZZ, hipStream_t st);
 
+// the library method for several dust components (soc_mabu_library.hip): a library per dust, indexed by that dust's share of the
+// absorptions at the three reference frequencies; one kernel looks every dust up and forms the abundance-weighted sum
+#define SOC_MABU_LIB_DUSTS 32        // the width of the miss mask
+// the tables of one resident library: what a look-up reads of it
+struct SocLibTables {
+    int          N, nout;            // bins per axis; emission columns of E
+    float        I0, dI0;
+    const float *I1, *dI1;           // [N]
+    const float *I2, *dI2;           // [N*N]
+    const float *X, *Y, *Z;          // [N^3]
+    const float *E0;                 // [N^3] the first stored emission value of every bin (> 1e31: the bin is empty)
+    const float *E;                  // [N^3][nout]
+};
+struct SocMabuLib {
+    long long    n;                  // cells
+    int          NDUST, nout;        // dust components; emission columns of every library's E and of a row of SUM
+    const float *ABS3;               // [n][3] the absorptions at the reference frequencies
+    const float *ABU;                // [n][NDUST]
+    const double *RABS3;             // [3][NDUST] relative cross sections at the reference frequencies
+    const SocLibTables *LIB;         // [NDUST], in device memory
+    float       *SUM;                // [n][nout]
+    unsigned    *MISS;               // [n] bit d: dust d had no answer
+};
+hipError_t soc_launch_mabu_library(const SocMabuLib &A, hipStream_t st);
+// OUT[n][NFREQ] = rows IDX[n] of EM[cells][NFREQ] (the caller checks the indices)
+hipError_t soc_launch_mabu_gather_rows(long long n, int NFREQ, const float *EM, const int *IDX, float *OUT, hipStream_t st);
+
 // Shape of the brick sweep; 0 = the built-in choice for the grid (measured).  Set per context with
 // soc_set_tuning (include/soc_hip.h); the parity tests use small CAP / HS values to exercise brick boundaries.
 struct SocBrickTune {

@@ -1,4 +1,4 @@
-// soc_host.h -- what the host units of libsoc_hip.so share (soc_capi.hip, soc_capi_post.hip, soc_capi_a2e.hip, soc_capi_reemit.hip, soc_capi_absorbed.hip, soc_capi_library.hip, soc_capi_probe.hip):
+// soc_host.h -- what the host units of libsoc_hip.so share (soc_capi.hip, soc_capi_post.hip, soc_capi_a2e.hip, soc_capi_reemit.hip, soc_capi_absorbed.hip, soc_capi_library.hip, soc_capi_mabu_library.hip, soc_capi_probe.hip):
 // the handle, the error and flush idioms.  Every device allocation of a handle is a DevBuf (soc_devbuf.h) that the handle owns: its
 // members, and the packet records, queues and bricks of its brick sweeps (SocSweepState, soc_brick.hip).  Kernels do not include it.
 #pragma once
@@ -158,6 +158,18 @@ struct soc_ctx {
     DevBuf<float> lTab, lE;
     DevBuf<int>   lMiss;
     DevBuf<unsigned long long> lCount;
+    // the library method for several dusts (soc_mabu_library_*): the reference absorptions, abundances, sum and miss masks of the
+    // resident cells, RABS3[3][ndust], and per dust the tables of soc_library_set (qTab: I1 | dI1 | I2 | dI2 | X | Y | Z | E0; qE the
+    // selected emission columns) with their device addresses in qLib[ndust]
+    DevBuf<float>    qABS3, qABU, qSUM;
+    DevBuf<unsigned> qMISS;
+    DevBuf<double>   qRABS3;
+    DevBuf<float>    qTab[SOC_MABU_LIB_DUSTS], qE[SOC_MABU_LIB_DUSTS];
+    DevBuf<SocLibTables> qLib;
+    int64_t mlib_cells = 0;            // 0: not open
+    int     mlib_ndust = 0, mlib_nout = 0;
+    unsigned mlib_have = 0;            // bit d: dust d has its library
+    bool    mlib_tables = false;
 };
 
 // the error text of a refused call, for soc_last_error (c == nullptr: of soc_create); returns code

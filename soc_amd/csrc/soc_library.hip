@@ -17,32 +17,18 @@
 // workgroup in LDS -- floats compared as ordered integers -- flushed with vector atomics, and the representative cell of a bin
 // by one 64-bit atomicMin on (bits of the distance << 32 | cell): least distance, then lowest cell, whatever the order.
 #include "soc_dev.h"
+#include "soc_lookup.h"
 #include "soc_math.h"
 
 #define LIB_T 256
 
-// OpenCL round(): halves away from zero (x - trunc(x) is exact)
-__device__ __forceinline__ float lib_round_away(float x)
-{
-    const float t = __builtin_truncf(x);
-    return (soc_fabsf(x - t) >= 0.5f) ? t + __builtin_copysignf(1.0f, x) : t;
-}
-
-// clamp((int)r, 0, N-1) for an integral float r, without the undefined conversion of a value no int holds (a NaN gives 0)
-__device__ __forceinline__ int lib_clip_index(float r, int N)
-{
-    if (!(r > 0.0f)) return 0;
-    if (r >= (float)(N - 1)) return N - 1;
-    return (int)r;
-}
-
-__device__ __forceinline__ float lib_solve_ref(float a) { return soc_log10f(soc_clampf(a, 1.0e-29f, 1.0e10f)); }
 __device__ __forceinline__ float lib_build_ref(float a) { return soc_log10f(soc_clampf(a, 1.0e-25f, 1.0f)); }
 
 __global__ __launch_bounds__(LIB_T) void soc_library_solve_kernel(SocLibSolve A)
 {
     __shared__ int sBin[LIB_T];
-    const int N = A.N, nout = A.nout;
+    const int nout = A.nout;
+    const SocLibTables L = { A.N, A.nout, A.I0, A.dI0, A.I1, A.dI1, A.I2, A.dI2, A.X, A.Y, A.Z, A.E0, A.E };
     const long long tiles = (A.n + LIB_T - 1) / LIB_T;
     const int dq = LIB_T / nout, dr = LIB_T % nout;
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -50,17 +36,8 @@ __global__ __launch_bounds__(LIB_T) void soc_library_solve_kernel(SocLibSolve A)
         int bin = -1;
         if (cell < A.n) {
             const float *a = A.ABS + cell * A.stride;
-            const float x = (lib_solve_ref(a[A.c0]) - A.I0) / A.dI0;
-            const int   i = lib_clip_index(lib_round_away(x), N);
-            const float y = (lib_solve_ref(a[A.c1]) - A.I1[i]) / A.dI1[i];
-            const int   j = lib_clip_index(lib_round_away(y), N);
-            const float z = (lib_solve_ref(a[A.c2]) - A.I2[i * N + j]) / A.dI2[i * N + j];
-            const int   k = lib_clip_index(lib_round_away(z), N);
-            bin = k + N * (j + N * i);
-            if (soc_fabsf(x - A.X[bin]) > 1.1f || soc_fabsf(y - A.Y[bin]) > 1.1f || soc_fabsf(z - A.Z[bin]) > 1.1f || A.E0[bin] > 1.0e31f) {
-                bin = -1;
-                A.miss[atomicAdd(A.nmiss, 1ull)] = (int)cell;          // (at most one entry per cell: below n)
-            }
+            bin = lib_solve_bin(L, a[A.c0], a[A.c1], a[A.c2]);       // (soc_lookup.h: shared with soc_mabu_library_kernel)
+            if (bin < 0) A.miss[atomicAdd(A.nmiss, 1ull)] = (int)cell;   // (at most one entry per cell: below n)
         }
         sBin[threadIdx.x] = bin;
         __syncthreads();

@@ -11,6 +11,7 @@
 // division happens once per workgroup.  RABS (NFREQ x NDUST doubles) sits in LDS; a cell's abundances come through the
 // cache (4 x NDUST bytes per cell from memory).
 #include "soc_dev.h"
+#include "soc_lookup.h"
 
 #define MABU_T    256
 #define MABU_TILE (MABU_T * 4)
@@ -33,15 +34,7 @@ struct MabuWalk {
     }
 };
 
-// PART = ABS * RABS[:, idust] / den, den = sum_j ABU[:, j] * RABS[:, j]: every product in double, den rounded to float
-// after each addition (dusts in index order), the quotient taken in double and rounded once
-__device__ __forceinline__ float mabu_part(float a, const float *abu, const double *R, int NDUST, int idust)
-{
-    float den = 0.0f;
-    for (int j = 0; j < NDUST; j++) den = (float)((double)den + (double)abu[j] * R[j]);
-    return (float)((double)a * R[idust] / (double)den);
-}
-
+// (mabu_part, the split of one value: soc_lookup.h, shared with soc_mabu_library_kernel)
 __global__ __launch_bounds__(MABU_T) void soc_mabu_split_kernel(long long N, int NFREQ, int NDUST, int idust, const float *__restrict__ ABS,
                                                                 const float *__restrict__ ABU, const double *__restrict__ RABS,
                                                                 float *__restrict__ PART)

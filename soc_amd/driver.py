@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """driver -- the three stages of a SOC run with several dust components, in one process and in memory:
 
-    python -m soc_amd.driver soc.ini [--keep-files]
+    python -m soc_amd.driver soc.ini [--keep-files] [--makelib LFREQ [--bins N]]
 
 Counterpart of ``ASOC_driver.py soc.ini`` + ``A2E_MABU.py`` (reference ASOC_driver.py:200-473, A2E_MABU.py:236-342,
 700-1180): the reference chains three programs with os.system and hands the absorptions (CELLS x NFREQ floats: 5-17 GB
@@ -23,9 +23,18 @@ Same ini keys, same dust / solver / abundance / cloud files.  `emitted` is writt
 `absorbed` file only with --keep-files.  `polarisation <dust> <aalg file>` lines (A2E_MABU.py:158-167) go to the same stage 2: the
 polarisation reduction factor R[CELLS, NFREQ] stays in memory, and where the ini asks for `polmap` without `polred` every polarisation
 map is made with the column of its own frequency (the reference writes <emitted>.R and needs one column copied into a `polred` file by
-hand, A2E_MABU.py:1190-1195); with `polred` the file wins; --keep-files writes <emitted>.R as well.  The neural-network and library
-shortcuts (nnmake, nnsolve, libabs ...) and cosmic-ray heating are not part of this path and are refused.  With several ranks the
+hand, A2E_MABU.py:1190-1195); with `polred` the file wins; --keep-files writes <emitted>.R as well.  The neural-network
+shortcuts (nnmake, nnsolve ...) and cosmic-ray heating are not part of this path and are refused.  With several ranks the
 first stage shards work items (soc_amd.dist), the second the cells; rank 0 writes.
+
+The library method (`ASOC_driver.py soc-ini [uselib] [makelib]`): --makelib LFREQ [--bins N] writes a library <dust>.mlib per dust as a
+by-product of the full run (soc_amd.mabu), whose products do not change; not with re-emission iterations (build the libraries from the
+absorbed file of the finished model with python -m soc_amd.mabu --makelib).  With `libabs FILE` in the ini stage 1 simulates the three
+frequencies of FILE only, their absorptions go to stage 2 as a host array [CELLS, 3] (12 bytes per cell; the resident-absorptions
+sink holds all frequencies and is not used), stage 2 is the look-up in those libraries (mabu.solve_emission_library) and stage 3
+writes all frequencies -- or, with `libmaps FILE2` as well, the maps of the frequencies of FILE2 from an emission array of just
+those columns, the bytes python -m soc_amd.asoc with `libmaps` writes from the emitted file written here.  `libmaps` without
+`libabs` is refused; with a library run also re-emission iterations, `polarisation` lines, saveint, nnmake / absthin and several ranks.
 
 Dust re-emission (`iterations N` with `cellpackets`): the constant sources are simulated once and their absorptions C kept unscaled;
 E_0 is solved from them; then, N times, the emission E_(k-1) is sent from the cells at every simulated frequency (SimRAM_CL, as a run
@@ -51,7 +60,7 @@ import time
 
 import numpy as np
 
-from . import a2e, converge, files, launch, mabu
+from . import a2e, converge, files, launch, library, mabu
 from .asoc import AbsorptionRun, ResidentAbsorptions, UnsupportedOption
 from .ini import User
 from .lib import DoesNotFit
@@ -64,8 +73,9 @@ from .mabu import (NE_EQ, dust_kind, eq_dust_table, planck_safe, relative_cross_
 class Pipeline:
     """soc.ini -> maps.  engine: soc_amd.lib.Engine (or an object with its methods); comm: soc_amd.dist.Comm"""
 
-    def __init__(self, ini, engine, comm=None, verbose=None, emission_source=None, absorbed_source=None):
-        """emission_source: None -- the re-emission iterations take the resident emission where they can (see iterate) -- or 'host' to
+    def __init__(self, ini, engine, comm=None, verbose=None, emission_source=None, absorbed_source=None, makelib=None):
+        """makelib = (lfreq file, N): the libraries <dust>.mlib are written besides (mabu.solve_emission(makelib=...));
+        emission_source: None -- the re-emission iterations take the resident emission where they can (see iterate) -- or 'host' to
         keep them on the host statements (tests, measurements); absorbed_source: the same for the absorptions on their way from the
         transfer stage to stage 2 (see open_absorbed)"""
         if emission_source not in (None, 'host'):
@@ -79,12 +89,31 @@ class Pipeline:
         self.world = comm.world if comm else 1
         self.eng = engine
         U = User(ini)
-        self.refuse(U)
         self.U = U
         # dust list as the user wrote it, and the simple dusts the transfer run works with (ASOC_driver.py:240-250)
         self.dusts = list(U.file_optical)
-        self.kinds = [dust_kind(d) for d in self.dusts]
         self.pol = mabu.polarisation_lines(ini, self.dusts)       # per dust its aalg file or None; None without such lines
+        self.refuse(U, self.pol, self.world)
+        self.kinds = [dust_kind(d) for d in self.dusts]
+        # the library method: `libabs` makes this a library run (run_library); `libmaps` names the frequencies it maps.  The transfer
+        # run sees `libabs` alone (one list of frequencies serves both keys there, and it refuses the two together)
+        self.library = 'libabs' in U.KEYS
+        self.makelib = makelib
+        self.fmaps = None
+        if makelib is not None and (self.library or (U.ITERATIONS > 0 and U.CLPAC > 0)):
+            raise UnsupportedOption("makelib %s" % ("in a library run (libabs): the libraries are built from a run with all frequencies" if self.library else
+                                                    "with dust re-emission iterations (iterations with cellpackets): no step of the loop knows that it is "
+                                                    "the last; build the libraries from the absorbed file of the finished model (--keep-files) with "
+                                                    "python -m soc_amd.mabu --makelib"))
+        if self.library:
+            if U.FSELECT_ERROR:
+                raise ValueError(U.FSELECT_ERROR)
+            if U.LIB_MAPS:
+                if getattr(U, "MAP_LEVELS", 0) > 0:
+                    raise UnsupportedOption("libmaps with maplevels (the per-level maps go through the batch path, libmaps through the plain one)")
+                self.fmaps = np.asarray(U.FSELECT_LIB_MAPS, np.float64)
+            U.LIB_MAPS, U.FSELECT = False, U.FSELECT_LIB_ABS
+            mabu.require_libraries(self.dusts)
         self.R = None
         U.file_optical = [d if k != 'gsetdust' else simple_name(d) for d, k in zip(self.dusts, self.kinds)]
         self.want_maps = not U.NOMAP
@@ -117,13 +146,15 @@ class Pipeline:
             print(*a)
 
     # ---- stage 2 ----------------------------------------------------------------------------------------------
-    def solve_emission(self, FABSORBED, ABU, keep_resident=False, download=True, absorbed_scale=None):
+    def solve_emission(self, FABSORBED, ABU, keep_resident=False, download=True, absorbed_scale=None, makelib=None):
         """FABSORBED[CELLS, NFREQ] as the absorbed file holds it (scaled, files.scale_absorbed) -> EMITTED[CELLS, NFREQ]; with
         `polarisation` lines self.R[CELLS, NFREQ] is the polarisation reduction factor.  keep_resident, download: as
         mabu.solve_emission; self.resident says whether the engine now holds this emission (then, with download=False, the arrays
         returned are not filled).  FABSORBED a ResidentAbsorptions with absorbed_scale: as mabu.solve_emission"""
         em, info = mabu.solve_emission(self.eng, self.dusts, self.kinds, FABSORBED, ABU, self.rank, self.world, log=self.log, pol=self.pol,
-                                       keep_resident=keep_resident, download=download, absorbed_scale=absorbed_scale)
+                                       keep_resident=keep_resident, download=download, absorbed_scale=absorbed_scale, makelib=makelib)
+        if makelib is not None and self.rank == 0:
+            mabu.write_libraries(self.dusts, info["libraries"], self.log)
         self.timers["emission_path"] = info["path"]            # 'device' (soc_mabu_*) or 'host'
         self.resident = info["resident"]
         self.on_host = download or not self.resident           # whether the array returned is filled
@@ -247,9 +278,64 @@ class Pipeline:
         return FABSORBED, EMITTED
 
     # ---- the three stages -----------------------------------------------------------------------------------------
+    def run_library(self, keep_files=False):
+        """A library run (`libabs FILE`): returns CTABS, the absorptions at the three reference frequencies [CELLS, 3] (scaled, as the
+        absorbed file holds them) and EMITTED[CELLS, NFREQ] -- with `libmaps FILE2` [CELLS, the frequencies of FILE2 in table order]"""
+        U = self.U
+        t0 = time.time()
+        rt = AbsorptionRun(U, self.eng, self.comm, verbose=self.verbose)
+        rt.write_packet_info()
+        rt.setup_engine()
+        self.log("driver: library run: the absorptions at the reference frequencies go to stage 2 as a host array, 12 bytes per cell "
+                 "(the resident absorptions are not used: %s)" % (rt.resident_absorptions_refused() or "they hold every frequency"))
+        self.timers["absorbed_source"] = 'host'
+        CTABS, ABS3 = rt.simulate_constant_sources()
+        cols = [f for f, _ in sorted(rt.lib_col.items(), key=lambda fk: fk[1])]
+        if len(cols) != 3 or ABS3.shape[1] != 3:
+            raise ValueError("libabs: the library method needs three reference frequencies of the dust file's table, the file selects %d" % len(cols))
+        files.scale_absorbed(ABS3, rt.cloud, U.GL, U.NNNLIMIT)
+        self.timers["transfer"] = time.time() - t0
+        t0 = time.time()
+        CELLS = rt.cloud.CELLS
+        ABU = mabu.abundance_table(rt.ABU, U.SINGLE_ABU, CELLS, len(self.dusts))
+        libs = mabu.read_libraries(self.dusts, rt.NFREQ)
+        ocol = lib_col = None
+        if self.fmaps is not None:                                 # the table frequencies within 0.1 % of one of `libmaps`, in table order
+            hit = [f for f in range(rt.NFREQ) if np.min(np.abs((float(rt.FFREQ[f]) - self.fmaps) / float(rt.FFREQ[f]))) <= 0.001]
+            if len(hit) < 1 or len(hit) > len(self.fmaps):
+                raise ValueError("libmaps lists %d frequencies, %d of the dust file's lie within 0.1 %% of one" % (len(self.fmaps), len(hit)))
+            ocol, lib_col = np.asarray(hit, np.int32), {f: k for k, f in enumerate(hit)}
+        EMITTED, info = mabu.solve_emission_library(self.eng, self.dusts, self.kinds, ABS3, ABU, libs, cols, ocol, log=self.log)
+        self.timers["emission_path"], self.timers["missed"] = info["path"], info["missed"]
+        self.timers["emission"] = time.time() - t0
+        self.timers["iterations"] = []
+        if self.rank == 0:
+            if self.verbose:
+                mabu.print_misses(self.dusts, info, CELLS, False)
+            if len(U.file_emitted) > 0:
+                files.write_emitted(U.file_emitted, EMITTED)
+            if keep_files and len(U.file_absorbed) > 0:
+                files.write_absorbed(U.file_absorbed, ABS3)
+        t0 = time.time()
+        if self.want_maps:
+            U.NOMAP = 0
+            if lib_col is not None:                                # what a run of soc_amd.asoc with `libmaps` sets up (ASOC.py:124-129)
+                U.LIB_ABS, U.LIB_MAPS, U.FSELECT, rt.lib_col = False, True, self.fmaps, lib_col
+                U.ITERATIONS, U.NOSOLVE, U.FAST_MAP = 0, 1, 0
+                U.MAP_FREQ = [1.0e-10, 1.0e30]
+            else:
+                U.LIB_ABS = False                                  # (all frequencies: an emission array like any other)
+            rt.write_maps(EMITTED)
+        self.timers["maps"] = time.time() - t0
+        self.log("@@ driver: library run: transfer %.2f s, emission %.2f s (%s path), maps %.2f s"
+                 % (self.timers["transfer"], self.timers["emission"], info["path"], self.timers["maps"]))
+        return CTABS, ABS3, EMITTED
+
     def run(self, keep_files=False, want_absorbed=True):
         """Returns CTABS, FABSORBED (scaled, as the absorbed file holds it) and EMITTED.  want_absorbed=False: where the absorptions
         stayed on the device they are not read back, and FABSORBED is None (keep_files reads them back for the file)"""
+        if self.library:
+            return self.run_library(keep_files)
         U = self.U
         t0 = time.time()
         rt = AbsorptionRun(U, self.eng, self.comm, verbose=self.verbose)
@@ -285,8 +371,11 @@ class Pipeline:
             elif conv and want and self.pol is not None:
                 self.host_every = True
                 self.log("driver: `polarisation` lines with `convergence`: every iteration reads its emission and R back (any step may be the last)")
+            makelib = None
+            if self.makelib is not None:                           # (lfreq file, N) -> (the reference columns, N); N == 0 here
+                makelib = (library.reference_columns(np.asarray(rt.FFREQ, np.float64), library.load_frequencies(self.makelib[0])), int(self.makelib[1]))
             EMITTED = self.solve_emission(FABSORBED, ABU, keep_resident=want, download=N == 0 or self.host_every,
-                                          absorbed_scale=self.scale if sink else None)
+                                          absorbed_scale=self.scale if sink else None, makelib=makelib)
             self.timers["emission"] = time.time() - t0
             self.timers["iterations"] = []
             stop = False
@@ -340,16 +429,22 @@ class Pipeline:
 
 def main(argv=None):
     argv = sys.argv if argv is None else argv
-    if len(argv) < 2:
-        print("Usage:  python -m soc_amd.driver soc.ini [--keep-files]")
+    args, opts = mabu.parse_options(argv, ("makelib", "bins"))
+    if args is None or len(args) < 2:
+        print("Usage:  python -m soc_amd.driver soc.ini [--keep-files] [--makelib LFREQ [--bins N]]")
+        return 1
+    try:
+        makelib = mabu.makelib_option(opts)
+    except ValueError as err:
+        print(err)
         return 1
     from .dist import Comm
     comm = Comm()                      # (imports torch first when there are several ranks: see lib.load_library)
     from .lib import Engine
     eng = Engine(comm.local_rank)
     try:
-        keep = "--keep-files" in argv
-        Pipeline(argv[1], eng, comm).run(keep_files=keep, want_absorbed=keep)
+        keep = "--keep-files" in args
+        Pipeline(args[1], eng, comm, makelib=makelib).run(keep_files=keep, want_absorbed=keep)
     finally:
         eng.close()
         comm.close()

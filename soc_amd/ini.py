@@ -150,6 +150,7 @@ class User:
         s.LIB_MAPS = False               # `libmaps file`: maps of those frequencies from an emitted file that holds only them
         s.FSELECT = np.zeros(0, np.float64)
         s.FSELECT_ERROR = ''             # why the file of `libabs` / `libmaps` could not be read
+        s.FSELECT_LIB_ABS = s.FSELECT_LIB_MAPS = None   # the two lists kept apart (soc_amd.driver takes both keys; FSELECT is the last one read)
         s.FITS = 0
         s.FITS_PREFIX = 'map'
         s.FITS_RA = 0.0
@@ -353,9 +354,11 @@ def _fselect(flag):
             f = np.loadtxt(s[1])
         except OSError as err:                       # reported by the run, after the combinations it refuses whatever the file holds
             u.FSELECT, u.FSELECT_ERROR = np.zeros(0, np.float64), "%s %s: %s" % (s[0], s[1], err)
+            setattr(u, 'FSELECT_' + flag, u.FSELECT)
             return
         u.FSELECT = np.asarray(f, np.float32).reshape(1,) if np.size(f) == 1 else np.asarray(f)
         u.FSELECT_ERROR = ''
+        setattr(u, 'FSELECT_' + flag, u.FSELECT)
     return handler
 
 

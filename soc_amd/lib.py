@@ -177,6 +177,15 @@ API = {
     "soc_library_solve": (C.c_int, [C.c_void_p, C.c_int64, _F, _F, _I, C.POINTER(C.c_int64)]),
     "soc_library_solve_resident": (C.c_int, [C.c_void_p, _I, _I, C.POINTER(C.c_int64)]),
     "soc_library_build": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _F, _I, _F, _F, _F, _F, _F, _F, _I, _F, _F, _F]),
+    "soc_mabu_library_begin": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "soc_mabu_library_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _F, _F, _F, _F, _F, _F, _F, _F, C.c_int, _I]),
+    "soc_mabu_library_upload": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
+    "soc_mabu_library_set_tables": (C.c_int, [C.c_void_p, _F, C.POINTER(C.c_double)]),
+    "soc_mabu_library_solve": (C.c_int, [C.c_void_p]),
+    "soc_mabu_library_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
+    "soc_mabu_library_misses": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _U]),
+    "soc_mabu_library_end": (C.c_int, [C.c_void_p]),
+    "soc_mabu_gather_rows": (C.c_int, [C.c_void_p, _I, C.c_int64, _F]),
     "soc_probe_rng": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_int, _U, _U]),
     "soc_probe_math": (C.c_int, [C.c_void_p, C.c_int, _F, _F, C.c_int64]),
     "soc_probe_math2": (C.c_int, [C.c_void_p, C.c_int, _F, _F, _F, C.c_int64]),
@@ -1340,6 +1349,79 @@ class Engine:
         self._chk(self.lib.soc_library_build(self.h, N, int(cells), _f(ABS3), _i(cols), _f(I0), _f(dI0), _f(I1), _f(dI1), _f(I2), _f(dI2),
                                              _i(IND), _f(X), _f(Y), _f(Z)))
         return dict(N=N, I0=I0[0], dI0=dI0[0], I1=I1, dI1=dI1, I2=I2, dI2=dI2, IND=IND, X=X, Y=Y, Z=Z)
+
+    # ---- the library method for several dust components (soc_mabu_library_*; driven by soc_amd.mabu.solve_emission_library) ----
+    def mabu_library_begin(self, cells, NDUST, nout):
+        """reserve the arrays of a look-up of `cells` cells: NDUST libraries of nout emission columns each; DoesNotFit where the
+        cells do not fit the free device memory (cells_fit of them would)"""
+        fit = C.c_int64(0)
+        rc = self.lib.soc_mabu_library_begin(self.h, int(cells), int(NDUST), int(nout), C.byref(fit))
+        if rc == SOC_ERR_STATE and 0 < fit.value < int(cells):
+            raise DoesNotFit("%s (code %d)" % (self.lib.soc_last_error(self.h).decode(), rc), fit.value)
+        self._chk(rc)
+        self._mlib = (int(cells), int(NDUST), int(nout))
+
+    def _mlib_open(self, who):
+        """(cells, NDUST, nout) of the open mabu_library_begin"""
+        if getattr(self, "_mlib", None) is None:
+            raise SocError("%s: call mabu_library_begin first" % who)
+        return self._mlib
+
+    def mabu_library_set(self, idust, lib, ocol=None):
+        """the library of dust idust (the dict of soc_amd.library.read_library), its E reduced to the columns ocol at upload"""
+        self._mlib_open("mabu_library_set")
+        N = int(lib["N"])
+        t = [np.ascontiguousarray(lib[k], np.float32) for k in self.LIBRARY_TABLES]
+        E = np.ascontiguousarray(lib["E"], np.float32)
+        if N < 1 or [a.size for a in t] != [N, N, N * N, N * N, N ** 3, N ** 3, N ** 3] or E.ndim != 2 or E.shape[0] != N ** 3:
+            raise SocError("mabu_library_set: the tables do not have the sizes of N = %d" % N)
+        oc = None if ocol is None else np.ascontiguousarray(ocol, np.int32)
+        nout = E.shape[1] if oc is None else oc.size
+        self._chk(self.lib.soc_mabu_library_set(self.h, int(idust), N, int(E.shape[1]), np.float32(lib["I0"]), np.float32(lib["dI0"]),
+                                                *[_f(a) for a in t], _f(E), int(nout), _i(oc)))
+
+    def mabu_library_upload(self, c0, ABS3):
+        self._mlib_open("mabu_library_upload")
+        ABS3 = np.ascontiguousarray(ABS3, np.float32)
+        if ABS3.ndim != 2 or ABS3.shape[1] != 3:
+            raise SocError("mabu_library_upload: ABS3 must be [n, 3]")
+        self._chk(self.lib.soc_mabu_library_upload(self.h, int(c0), ABS3.shape[0], _f(ABS3)))
+
+    def mabu_library_set_tables(self, ABU, RABS3):
+        cells, NDUST, _ = self._mlib_open("mabu_library_set_tables")
+        ABU, RABS3 = np.ascontiguousarray(ABU, np.float32), np.ascontiguousarray(RABS3, np.float64)
+        if ABU.shape != (cells, NDUST) or RABS3.shape != (3, NDUST):
+            raise SocError("mabu_library_set_tables: ABU%s, RABS3%s for %d cells, %d dusts" % (ABU.shape, RABS3.shape, cells, NDUST))
+        self._chk(self.lib.soc_mabu_library_set_tables(self.h, _f(ABU), RABS3.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def mabu_library_solve(self):
+        self._chk(self.lib.soc_mabu_library_solve(self.h))
+
+    def mabu_library_download(self, c0, n, out=None):
+        """rows [c0, c0 + n) of the sum as [n, nout]; out as in mabu_download"""
+        out = _rows_out("mabu_library_download", n, self._mlib_open("mabu_library_download")[2], out)
+        self._chk(self.lib.soc_mabu_library_download(self.h, int(c0), int(n), _f(out)))
+        return out
+
+    def mabu_library_misses(self, c0, n):
+        """uint32 [n]: bit d set where dust d had no answer for the cell"""
+        self._mlib_open("mabu_library_misses")
+        out = np.zeros(max(int(n), 0), np.uint32)
+        self._chk(self.lib.soc_mabu_library_misses(self.h, int(c0), int(n), out.ctypes.data_as(_U)))
+        return out
+
+    def mabu_library_end(self):
+        self._chk(self.lib.soc_mabu_library_end(self.h))
+        self._mlib = None
+
+    def mabu_gather_rows(self, idx):
+        """rows idx[n] (repeats allowed) of the current dust's emission in the open mabu_begin, as [n, NFREQ]"""
+        NFREQ = self._mabu_open("mabu_gather_rows")[1]
+        idx = np.ascontiguousarray(idx, np.int32).ravel()
+        out = np.zeros((idx.size, NFREQ), np.float32)
+        if idx.size:
+            self._chk(self.lib.soc_mabu_gather_rows(self.h, _i(idx), idx.size, _f(out)))
+        return out
 
     # ---- probes ----
     def probe_rng(self, SEED, gid_first, n, ndraw):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """mabu -- emission of a model with several dust components from its absorptions:
 
-    python -m soc_amd.mabu  soc.ini  absorbed.data  emitted.data
+    python -m soc_amd.mabu  soc.ini  absorbed.data  emitted.data  [ofreq.dat]  [--makelib LFREQ [--bins N]]  [--uselib LFREQ]
 
 Counterpart of ``A2E_MABU.py ini absorbed.data emitted.data`` (reference A2E_MABU.py:236-342, 700-1180): the dust list,
 the abundance files and `singleabu` come from the ini, an equilibrium dust is solved from its dust file, a
@@ -31,7 +31,19 @@ are compared with `.dust` stripped on both sides.  Without such lines nothing ch
 
 With N GPUs (python -m torch.distributed.run --nproc-per-node N -m soc_amd.mabu ...) every rank solves its share of
 the cells and writes its rows of the emitted file.  The reference's optional fourth argument (ofreq.dat: emission on a
-subset of the frequencies) and the library / neural-network shortcuts are refused.
+subset of the frequencies) is refused for a direct run, as are the neural-network shortcuts.
+
+The library method for several dusts (the `uselib` / `makelib` of ASOC_driver.py's usage line): every dust of the ini, equilibrium or
+stochastically heated, has a library <dust name without .dust>.mlib (library_name) in the byte layout of soc_amd.library's .lib,
+indexed by the log of that dust's share split_absorbed(...) of the absorptions at three reference frequencies.  --makelib LFREQ
+[--bins N] (run(makelib=(LFREQ, N))) writes them as a by-product of the normal solve, whose products do not change: the grid and the
+representative cells from engine.library_build on the share, the rows from the emission that dust's solve has just left, no second
+solve; one rank and, on the device path, one cell range, else it is refused.  An ini with `libabs FILE` and an absorbed file of exactly
+three columns takes the look-up (solve_emission_library: one fused kernel on the device, the composition split -> library_solve ->
+weighted sum on the host, the same bits); a (cell, dust) without an answer adds zero, the counts are printed per dust; ofreq.dat then
+selects the library columns nearest to its frequencies.  --uselib LFREQ with an absorbed file of all frequencies does the same look-up
+from its reference columns and then solves every cell with a miss in any dust directly, overwriting those rows: a library checked
+against the direct solve on one run.  <dust>.mlib.new is not written.
 """
 import os
 import sys
@@ -40,7 +52,7 @@ import time
 import numpy as np
 from scipy.interpolate import interp1d
 
-from . import a2e, files
+from . import a2e, files, library
 from .asoc import ResidentAbsorptions, UnsupportedOption
 from .ini import User
 from .launch import FACTOR
@@ -48,14 +60,35 @@ from .lib import DoesNotFit
 
 NE_EQ = 30000                    # A2E_MABU.py:478
 NSTOCH_ALL = 9999                # A2E_MABU.py:124: a gsetdust file without an `nstoch` line -- every size is stochastically heated
-REFUSED_KEYS = ('nnmake', 'nnsolve', 'nnabs', 'nnemit', 'nnthin', 'absthin', 'libabs', 'libmaps', 'aalg', 'crheating')
+REFUSED_KEYS = ('nnmake', 'nnsolve', 'nnabs', 'nnemit', 'nnthin', 'absthin', 'aalg', 'crheating')
 CHUNK = 1 << 20                  # cells per upload / download call
 
 
-def refuse(U):
+def refuse(U, pol=None, world=1):
+    """what the in-memory pipeline does not take; with `libabs` (a library run) also what a library cannot give, each with its reason.
+    pol: polarisation_lines' list; world: the number of ranks"""
+    if 'libmaps' in U.KEYS and 'libabs' not in U.KEYS:
+        raise UnsupportedOption("libmaps without libabs: the maps of a library's frequencies come from a library run (`libabs FILE` with it); "
+                                "python -m soc_amd.asoc maps an emitted file that holds only those columns")
+    if 'libabs' in U.KEYS:
+        bad = []
+        if U.ITERATIONS > 0 and U.CLPAC > 0:
+            bad.append("iterations > 0 with cellpackets (the dust re-emission needs the emission at every frequency sent from the cells and "
+                       "absorptions at every frequency to solve it again; a library run simulates three)")
+        if pol is not None:
+            bad.append("polarisation lines (the libraries hold the total emission only: no polarised emission comes from a library)")
+        if 'saveint' in U.KEYS:
+            bad.append("saveint (the intensity file holds all frequencies, a library run simulates three)")
+        for k in ('nnmake', 'absthin'):
+            if k in U.KEYS:
+                bad.append("%s (the thinned absorptions train a network on all frequencies; a library run has three)" % k)
+        if world > 1:
+            bad.append("more than one rank (%d: the look-up is one memory-bound pass over the cells of one device)" % world)
+        if bad:
+            raise UnsupportedOption("libabs (a library run) together with " + "; ".join(bad))
     bad = [k for k in REFUSED_KEYS if k in U.KEYS]
     if bad:
-        raise UnsupportedOption("ini options outside the in-memory pipeline (neural-network / library shortcuts, "
+        raise UnsupportedOption("ini options outside the in-memory pipeline (neural-network shortcuts, "
                                 "cosmic-ray heating): " + ", ".join(bad))
 
 
@@ -78,6 +111,12 @@ def solver_name(name):
     if b.startswith('gs_'):
         b = b[3:]
     return os.path.join(d, b + '.solver')
+
+
+def library_name(name):
+    """the library of a dust of a multi-dust model: <dust name without .dust>.mlib, beside the dust file.  Not <solver>.lib of
+    soc_amd.library, which is built from unsplit absorptions"""
+    return strip_dust(name) + '.mlib'
 
 
 def read_nstoch(name, kind=None):
@@ -269,6 +308,13 @@ def abundance_table(ABU, single, CELLS, NDUST):
 
 
 # ---- the stage ------------------------------------------------------------------------------------------------------
+MAKELIB_ONE_RANK = ("makelib with %d ranks: every rank holds a share of the cells, and a library is built from all of them "
+                    "(from one rank and one cell range); build it with one rank")
+MAKELIB_ONE_RANGE = ("makelib: the libraries are built on the device from one cell range, and the %d cells of this run need several (%s); "
+                     "a library from part of the model would miss the rest: build it on a device that holds the cells, or with an engine "
+                     "that takes the host path")
+
+
 def _tables(dusts, kinds, NFREQ):
     """per dust what its solver needs: eq_dust_table of an equilibrium dust, the solver file of a stochastically heated one with
     the `nstoch` of its dust file (read_nstoch) under that key"""
@@ -300,7 +346,20 @@ def device_path_offered(engine, dusts, kinds, NFREQ, pol=None):
     return offers_device_path(engine, kinds, _tables(dusts, kinds, NFREQ), polarised)
 
 
-def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, log, AALG=None, ptabs=None, PEM=None):
+def _library_rows(grid, rows_of, NFREQ, FREQ):
+    """the library of one dust from its grid (engine.library_build on its share) and rows_of(cells) -> the emission its solve left
+    for those cells: clipped to [1e-30, 1e30], 1e32 in the bins without a representative (library.build does the same)"""
+    N = int(grid["N"])
+    m = np.nonzero(grid["IND"] >= 0)[0]
+    E = np.full((N ** 3, NFREQ), 1.0e32, np.float32)
+    if len(m):
+        E[m, :] = np.clip(rows_of(grid["IND"][m]), np.float32(1.0e-30), np.float32(1.0e30))
+    lib = dict(grid)
+    lib.update(NFREQ=NFREQ, FREQ=np.asarray(FREQ, np.float32), E=E)
+    return lib
+
+
+def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, log, AALG=None, ptabs=None, PEM=None, makelib=None, libs=None):
     n, NFREQ = FABS.shape
     for idust in range(len(dusts)):
         t0 = time.time()
@@ -320,6 +379,9 @@ def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, lo
             em, pem, _ = a2e.run(engine, tables[idust], part, NSTOCH=tables[idust].get("nstoch", NSTOCH_ALL), verbose=False, aalg=aalg)   # A2E_MABU.py:971-984
         else:
             em, _ = a2e.run(engine, tables[idust], part, NSTOCH=tables[idust].get("nstoch", NSTOCH_ALL), verbose=False)
+        if makelib is not None:                                # (cols, N, FREQ): the library of this dust, from what is at hand
+            grid = engine.library_build(makelib[1], ABS3=np.ascontiguousarray(part[:, makelib[0]], np.float32))
+            libs.append(_library_rows(grid, lambda cells: em[cells], NFREQ, makelib[2]))
         EM += em * ABU[:, idust:idust + 1]                     # A2E_MABU.py:1128-1140
         if pem is not None:
             PEM += pem * ABU[:, idust:idust + 1]               # A2E_MABU.py:1139-1147
@@ -328,15 +390,20 @@ def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, lo
 
 
 def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells, log, AALG=None, ptabs=None, R=None, resident_c0=None,
-                  download=True, absorbed=None):
+                  download=True, absorbed=None, makelib=None, libs=None):
     """the cells in ranges that fit the device (one range where all do): cells are independent, so this is a loop.  With AALG (per
     dust the minimum aligned sizes of these cells, or None) the two more resident arrays of the polarised emission are asked for,
     the rows of a dust's aalg follow the cell range, and R receives polarised / total.  resident_c0 (the model's cell of row 0): the
     sum of every range also goes, device to device, to the engine's resident emission (emitted_begin); download=False: nowhere else.
     absorbed = (c0, K, nnnlimit): FABS is the engine's resident absorptions (absorbed_begin), row 0 the model's cell c0, and every
-    range takes its rows from there, device to device, scaled on the way (absorbed_to_mabu), in place of the uploads."""
+    range takes its rows from there, device to device, scaled on the way (absorbed_to_mabu), in place of the uploads.
+    makelib = (cols, N, FREQ): after every dust's solve its library goes to libs -- the grid from library_build on the resident share
+    (the plain split: where a reference column is the last channel, which clip_last changes, the share is split once more for the
+    solver), the rows gathered from the resident emission.  One range then, or UnsupportedOption."""
     n, NFREQ = FABS.shape
     NDUST = len(dusts)
+    if makelib is not None and range_cells and int(range_cells) < n:
+        raise UnsupportedOption(MAKELIB_ONE_RANGE % (n, "the caller limits a range to %d" % int(range_cells)))
 
     def upload_aalg(aalg, a, b):
         for i in range(a, b, CHUNK):
@@ -353,6 +420,8 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
             else:
                 engine.mabu_begin(b - a, NFREQ, NDUST)
         except DoesNotFit as err:
+            if makelib is not None:
+                raise UnsupportedOption(MAKELIB_ONE_RANGE % (n, "%d fit the free device memory" % err.cells_fit))
             step = err.cells_fit
             log("  %s" % err)
             continue
@@ -364,19 +433,29 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
             engine.mabu_set_tables(ABU[a:b], RABS)
             for idust in range(NDUST):
                 aalg = AALG[idust] if AALG else None
+                grid = None
                 if kinds[idust] == 'eqdust':
                     Fq, KABS, Emin, kE, oplgkE, TTT = tables[idust]
                     engine.mabu_split(idust)
+                    if makelib is not None:
+                        grid = engine.library_build(makelib[1], cols=makelib[0])
                     engine.mabu_solve_eq(NE_EQ, FACTOR, kE, oplgkE, Emin, Fq, KABS, TTT)
                     if aalg is not None:                                           # A2E_MABU.py:615-637
                         upload_aalg(aalg, a, b)
                         engine.mabu_pol_eq(*ptabs[idust])
                 else:
                     sol = tables[idust]
+                    if makelib is not None and (NFREQ - 1) in list(makelib[0]):    # (the grid wants the share before the clip)
+                        engine.mabu_split(idust)
+                        grid = engine.library_build(makelib[1], cols=makelib[0])
                     engine.mabu_split(idust, clip_last=True)                       # A2E.py:184-185
+                    if makelib is not None and grid is None:
+                        grid = engine.library_build(makelib[1], cols=makelib[0])
                     if aalg is not None:
                         upload_aalg(aalg, a, b)
                     a2e.solve_sizes_resident(engine, sol, stochastic_sizes(sol), aalg is not None)   # (a refusal of a call ends the stage)
+                if grid is not None:
+                    libs.append(_library_rows(grid, engine.mabu_gather_rows, NFREQ, makelib[2]))
                 engine.mabu_accumulate(idust)
                 if aalg is not None:
                     engine.mabu_accumulate_p(idust)                                # A2E_MABU.py:1139-1147
@@ -398,7 +477,7 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
 
 
 def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, path=None, range_cells=None, log=None, pol=None,
-                   keep_resident=False, download=True, absorbed_scale=None):
+                   keep_resident=False, download=True, absorbed_scale=None, makelib=None):
     """Stage 2 of a multi-dust run for the cells a2e.cell_range(CELLS, rank, world) of this rank.  FABSORBED[CELLS, NFREQ] as the
     absorbed file holds it (scaled, files.scale_absorbed; a memory map will do), ABU[CELLS, NDUST] float32.  Or FABSORBED a
     ResidentAbsorptions -- the engine holds them unscaled (absorbed_begin) -- with absorbed_scale = (K[LEVELS], nnnlimit)
@@ -409,10 +488,20 @@ def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, pat
     pol: polarisation_lines' list -- per dust its aalg file or None; info["R"] is then R[c1 - c0, NFREQ], polarised / total;
     keep_resident: on the device path the sum also goes to the engine's resident emission (engine.emitted_begin was called: the
     cell-emission launches of a re-emission iteration take it from there) -- info["resident"] says whether it did; download=False:
-    where it did, the sum is not read back (EM, and R, stay zero: an intermediate iteration needs neither on the host)."""
+    where it did, the sum is not read back (EM, and R, stay zero: an intermediate iteration needs neither on the host);
+    makelib = (cols[3], N): info["libraries"] is, per dust, its library (the dict library.write_library takes, with IND besides), a
+    by-product of the solve, which it does not change -- one rank and, on the device path, one cell range, else UnsupportedOption."""
     log = log or (lambda *a: None)
     CELLS, NFREQ = FABSORBED.shape
     RABS, FREQ = relative_cross_sections(dusts, kinds)
+    libs = None
+    if makelib is not None:
+        if world > 1:
+            raise UnsupportedOption(MAKELIB_ONE_RANK % world)
+        cols, N = np.asarray(makelib[0], np.int32), int(makelib[1])
+        if cols.size != 3 or cols.min() < 0 or cols.max() >= NFREQ or not 2 <= N <= 64:
+            raise ValueError("makelib: three reference columns below %d and 2 <= N <= 64 (got %s, %d)" % (NFREQ, cols, N))
+        makelib, libs = (cols, N, FREQ), []
     if RABS.shape[0] != NFREQ:
         raise ValueError("the dusts have %d frequencies, the absorptions %d" % (RABS.shape[0], NFREQ))
     tables = _tables(dusts, kinds, NFREQ)
@@ -435,42 +524,232 @@ def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, pat
     if c1 > c0 and device:
         ranges = _solve_device(engine, dusts, kinds, tables, ResidentAbsorptions(engine, c1 - c0, NFREQ) if from_resident else FABSORBED[c0:c1],
                                ABU[c0:c1], RABS, EM, range_cells, log, AALG, ptabs, R, resident_c0=c0 if resident else None,
-                               download=download or not resident, absorbed=(c0,) + tuple(absorbed_scale) if from_resident else None)
+                               download=download or not resident, absorbed=(c0,) + tuple(absorbed_scale) if from_resident else None,
+                               makelib=makelib, libs=libs)
     elif c1 > c0:
-        ranges = _solve_host(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, c0, CELLS, EM, log, AALG, ptabs, R)
+        ranges = _solve_host(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, c0, CELLS, EM, log, AALG, ptabs, R,
+                             makelib=makelib, libs=libs)
         if AALG:
             R[:] = reduction_factor(R, EM)                         # (R held the sum of the polarised emission)
     info = dict(path='device' if device else 'host', ranges=ranges, resident=resident)
     if AALG:
         info["R"] = R
+    if libs is not None:
+        info["libraries"] = libs
     return EM, info
 
 
+# ---- the look-up: a library per dust ------------------------------------------------------------------------------------
+def write_libraries(dusts, libs, log=None):
+    """<dust>.mlib of every dust, what solve_emission(makelib=...) left in info["libraries"]"""
+    for d, lib in zip(dusts, libs):
+        library.write_library(library_name(d), lib)
+        if log:
+            log("  %s: (N=%d)^3 = %d bins, cells existed for %d" % (library_name(d), lib["N"], lib["N"] ** 3, int(np.sum(lib["IND"] >= 0))))
+
+
+def require_libraries(dusts, lfreq='lfreq.dat'):
+    """a library per dust, or an error that names the missing file and says how it is made"""
+    for d in dusts:
+        if not os.path.exists(library_name(d)):
+            raise FileNotFoundError("%s: the library of %s is missing; a run with all frequencies writes it: "
+                                    "python -m soc_amd.mabu soc.ini absorbed.data emitted.data --makelib %s" % (library_name(d), d, lfreq))
+
+
+def read_libraries(dusts, NFREQ, lfreq='lfreq.dat'):
+    """the libraries of the dusts (require_libraries first)"""
+    require_libraries(dusts, lfreq)
+    libs = []
+    for d in dusts:
+        name = library_name(d)
+        lib = library.read_library(name)
+        if lib["E"].shape[1] != NFREQ:
+            raise ValueError("%s holds %d frequencies, the dusts %d" % (name, lib["E"].shape[1], NFREQ))
+        libs.append(lib)
+    return libs
+
+
+def _lookup_host(engine, ABS3, ABU, RABS3, libs, ocol, EM, MISS):
+    """the composition the fused kernel equals bit for bit: per dust the split, the look-up with missed rows zeroed, the weighted sum"""
+    for d, lib in enumerate(libs):
+        part = split_absorbed(ABS3, RABS3, ABU, d)
+        engine.library_set(lib, ocol)
+        try:
+            for a in range(0, len(part), CHUNK):
+                EMI, miss = engine.library_solve(part[a:a + CHUNK])
+                EMI[miss, :] = 0.0
+                EM[a:a + CHUNK] += EMI * ABU[a:a + CHUNK, d:d + 1]
+                MISS[a + np.asarray(miss, np.int64)] |= np.uint32(1 << d)
+        finally:
+            engine.library_set(None)
+
+
+def _lookup_device(engine, ABS3, ABU, RABS3, libs, ocol, EM, MISS, range_cells, log):
+    n, nout = EM.shape
+    step = n if not range_cells else max(1, min(n, int(range_cells)))
+    a = ranges = 0
+    while a < n:
+        b = min(a + step, n)
+        try:
+            engine.mabu_library_begin(b - a, len(libs), nout)
+        except DoesNotFit as err:
+            step = err.cells_fit
+            log("  %s" % err)
+            continue
+        try:
+            for d, lib in enumerate(libs):
+                engine.mabu_library_set(d, lib, ocol)
+            for i in range(a, b, CHUNK):
+                engine.mabu_library_upload(i - a, ABS3[i:min(i + CHUNK, b)])
+            engine.mabu_library_set_tables(ABU[a:b], RABS3)
+            engine.mabu_library_solve()
+            for i in range(a, b, CHUNK):
+                m = min(i + CHUNK, b) - i
+                engine.mabu_library_download(i - a, m, out=EM[i:i + m])
+                MISS[i:i + m] = engine.mabu_library_misses(i - a, m)
+        finally:
+            engine.mabu_library_end()
+        ranges += 1
+        a = b
+    return ranges
+
+
+def solve_emission_library(engine, dusts, kinds, ABS3, ABU, libs, cols, ocol=None, full=None, *, path=None, range_cells=None, log=None):
+    """Stage 2 from the libraries of the dusts (read_libraries): ABS3[CELLS, 3], the absorptions at the reference frequencies -- the
+    columns cols[3] of the dusts' frequency table --, as a `libabs` run's absorbed file holds them; ABU[CELLS, NDUST] float32.
+    Returns (EM[CELLS, nout], info): nout the libraries' frequencies, or those ocol selects and orders.  info["missed"] holds per dust
+    the number of cells its library had no answer for -- such a (cell, dust) adds zero --, info["miss"] the uint32 mask per cell (bit d:
+    dust d), info["path"] 'device' (the fused kernel, where the engine has mabu_library_begin) or 'host' (the composition around
+    engine.library_solve), with the same bits; path insists on one.  full = FABSORBED[CELLS, NFREQ], the absorptions at all
+    frequencies: every cell with a miss in any dust is then solved directly, all dusts (solve_emission on the gathered rows), and
+    its row overwritten; info["solved"] are those cells."""
+    log = log or (lambda *a: None)
+    ABS3 = np.asarray(ABS3)
+    CELLS = ABS3.shape[0]
+    NDUST = len(dusts)
+    if ABS3.ndim != 2 or ABS3.shape[1] != 3 or ABU.shape != (CELLS, NDUST) or len(libs) != NDUST:
+        raise ValueError("solve_emission_library: ABS3[CELLS, 3], ABU[CELLS, %d] and a library per dust" % NDUST)
+    if NDUST > 32:
+        raise UnsupportedOption("%d dusts: a library run takes at most 32 (the width of the miss mask)" % NDUST)
+    RABS, FREQ = relative_cross_sections(dusts, kinds)
+    cols = np.asarray(cols, np.int64)
+    if cols.size != 3 or cols.min() < 0 or cols.max() >= RABS.shape[0]:
+        raise ValueError("solve_emission_library: three reference columns below %d" % RABS.shape[0])
+    RABS3 = np.ascontiguousarray(RABS[cols])
+    NFREQ = int(libs[0]["E"].shape[1])
+    if any(int(lib["E"].shape[1]) != NFREQ for lib in libs):
+        raise ValueError("the libraries hold different numbers of frequencies: %s" % [int(lib["E"].shape[1]) for lib in libs])
+    oc = None if ocol is None else np.asarray(ocol, np.int32)
+    nout = NFREQ if oc is None else int(oc.size)
+    offered = hasattr(engine, "mabu_library_begin")
+    if path not in (None, 'device', 'host') or (path == 'device' and not offered):
+        raise ValueError("solve_emission_library: path %r is not available with this engine" % (path,))
+    device = offered if path is None else path == 'device'
+    EM, MISS = np.zeros((CELLS, nout), np.float32), np.zeros(CELLS, np.uint32)
+    ranges = 1
+    if CELLS > 0 and device:
+        ranges = _lookup_device(engine, ABS3, np.ascontiguousarray(ABU, np.float32), RABS3, libs, oc, EM, MISS, range_cells, log)
+    elif CELLS > 0:
+        _lookup_host(engine, np.ascontiguousarray(ABS3, np.float32), ABU, RABS3, libs, oc, EM, MISS)
+    missed = [int(np.count_nonzero(MISS & np.uint32(1 << d))) for d in range(NDUST)]
+    info = dict(path='device' if device else 'host', ranges=ranges, missed=missed, miss=MISS, resident=False)
+    if full is not None:
+        cells = np.flatnonzero(MISS)
+        info["solved"] = cells
+        if len(cells):
+            rows = np.ascontiguousarray(np.asarray(full)[cells, :], np.float32)
+            direct, _ = solve_emission(engine, dusts, kinds, rows, np.ascontiguousarray(ABU[cells]), log=log)
+            EM[cells, :] = direct if oc is None else direct[:, oc]
+    return EM, info
+
+
+def print_misses(dusts, info, CELLS, full, out=print):
+    """per dust what soc_library.py:484-490 prints for its one"""
+    for d, m in zip(dusts, info["missed"]):
+        if m < 1:
+            out("*** %s: all cells matched by entries in the library ***" % d)
+        elif full:
+            out("*** %s: %d cells without answer in the library, %.3f %% of all cells: solved directly" % (d, m, 100.0 * m / max(CELLS, 1)))
+        else:
+            out("*** %s: %d cells without answer in the library, and the absorptions hold 3 frequencies only:" % (d, m))
+            out("***    the emission of this dust in those cells is set to ZERO")
+
+
+def reference_columns_ascending(FREQ, FREF, what):
+    """library.reference_columns for the columns of an absorbed file, which follow the frequency table: they must ascend"""
+    cols = library.reference_columns(FREQ, FREF)
+    if not (cols[0] < cols[1] < cols[2]):
+        raise ValueError("%s: the three reference frequencies must be distinct frequencies of the dusts' table in its order "
+                         "(columns %s): the three columns of a libabs run's absorbed file follow the table" % (what, list(cols)))
+    return cols
+
+
 # ---- the program ----------------------------------------------------------------------------------------------------
-def run(ini, absorbed, emitted, engine, comm=None, ofreq=None, verbose=False, **stage):
+def run(ini, absorbed, emitted, engine, comm=None, ofreq=None, verbose=False, makelib=None, uselib=None, **stage):
     """The whole program for one rank of `comm` (or alone): memory-map the absorbed file, solve this rank's cells, write them
     into this rank's rows of the emitted file.  No collective on the data path (as a2e.run_sharded): the ranks only wait for
-    rank 0 to have created the file, and for each other at the end.  Returns solve_emission's info."""
-    if ofreq is not None:
-        raise UnsupportedOption("a fourth argument (%s: emission on a subset of the frequencies, A2E_MABU.py ofreq.dat) is not supported: "
-                                "the emitted file holds every frequency of the absorbed file" % ofreq)
+    rank 0 to have created the file, and for each other at the end.  Returns solve_emission's info.
+    makelib = (lfreq file, N): the libraries <dust>.mlib are written besides; uselib = lfreq file, or `libabs` in the ini with an
+    absorbed file of three columns: the emission comes from those libraries (solve_emission_library; ofreq selects its columns)."""
     rank, world = (comm.rank, comm.world) if comm else (0, 1)
     U = User(ini)
-    refuse(U)
     dusts = list(U.file_optical)
     if len(dusts) < 1:
         raise ValueError("%s names no dust (keyword optical)" % ini)
     pol = polarisation_lines(ini, dusts)
-    kinds = [dust_kind(d) for d in dusts]
-    require_solvers(dusts, kinds)
     dims = np.fromfile(absorbed, np.int32, 2)
     CELLS, NFREQ = int(dims[0]), int(dims[1])
-    FABS = np.memmap(absorbed, dtype=np.float32, mode='r', offset=8, shape=(CELLS, NFREQ))
+    lookup = uselib is not None or ('libabs' in U.KEYS and NFREQ == 3)
+    if ofreq is not None and not lookup:
+        raise UnsupportedOption("a fourth argument (%s: emission on a subset of the frequencies, A2E_MABU.py ofreq.dat) is not supported "
+                                "for a direct run: the emitted file holds every frequency of the absorbed file" % ofreq)
+    refuse(U, pol, world)
+    if uselib is not None and (pol is not None or world > 1):
+        raise UnsupportedOption("uselib together with %s" % ("polarisation lines (no polarised emission comes from a library)"
+                                                               if pol is not None else "more than one rank"))
+    kinds = [dust_kind(d) for d in dusts]
+    require_solvers(dusts, kinds)
     ABU = abundance_table(files.read_abundances(U.file_abundance, CELLS), U.SINGLE_ABU, CELLS, len(dusts))
     log = print if (verbose and rank == 0) else None
+    if lookup:
+        if makelib is not None:
+            raise UnsupportedOption("makelib in a run that takes its emission from the libraries: they are built from a direct solve")
+        FREQ = relative_cross_sections(dusts, kinds)[1]
+        FABS = np.memmap(absorbed, dtype=np.float32, mode='r', offset=8, shape=(CELLS, NFREQ))
+        if NFREQ == 3:
+            if 'libabs' not in U.KEYS:
+                raise UnsupportedOption("%s holds three columns: the ini must name their frequencies (`libabs FILE`)" % absorbed)
+            if U.FSELECT_ERROR:
+                raise ValueError(U.FSELECT_ERROR)
+            fsel = U.FSELECT_LIB_ABS if U.FSELECT_LIB_ABS is not None else U.FSELECT
+            cols, ABS3, full = reference_columns_ascending(FREQ, np.asarray(fsel, np.float64), "libabs"), FABS, None
+        else:
+            if NFREQ != len(FREQ):
+                raise ValueError("%s holds %d frequencies: 3 or the dusts' %d" % (absorbed, NFREQ, len(FREQ)))
+            cols = reference_columns_ascending(FREQ, library.load_frequencies(uselib), "uselib")
+            ABS3, full = np.ascontiguousarray(FABS[:, cols], np.float32), FABS
+        libs = read_libraries(dusts, len(FREQ), "lfreq.dat" if uselib is None else uselib)
+        ocol = None
+        if ofreq is not None:                                      # soc_library.py:298-306: the nearest library frequencies
+            ocol = np.asarray([np.argmin(np.abs(f - libs[0]["FREQ"].astype(np.float64))) for f in library.load_frequencies(ofreq)], np.int32)
+        EM, info = solve_emission_library(engine, dusts, kinds, ABS3, ABU, libs, cols, ocol, full, log=log, **stage)
+        if rank == 0:
+            print_misses(dusts, info, CELLS, full is not None)
+        files.write_emitted(emitted, EM)
+        return info
+    if 'libabs' in U.KEYS and log:
+        log("mabu: `libabs` in the ini, but %s holds %d columns: a direct run" % (absorbed, NFREQ))
+    FABS = np.memmap(absorbed, dtype=np.float32, mode='r', offset=8, shape=(CELLS, NFREQ))
+    if makelib is not None:
+        if world > 1:                                              # (before rank 0 creates the emitted file)
+            raise UnsupportedOption(MAKELIB_ONE_RANK % world)
+        FREQ = relative_cross_sections(dusts, kinds)[1]
+        stage["makelib"] = (library.reference_columns(FREQ, library.load_frequencies(makelib[0])), int(makelib[1]))
     if world == 1:
         EM, info = solve_emission(engine, dusts, kinds, FABS, ABU, log=log, pol=pol, **stage)
         files.write_emitted(emitted, EM)
+        if makelib is not None:
+            write_libraries(dusts, info.pop("libraries"), log)
         if pol is not None:
             write_reduction(emitted + '.R', info.pop("R"))
         return info
@@ -500,11 +779,44 @@ def write_reduction(filename, R):
         np.asarray(R, np.float32).tofile(fp)
 
 
+def parse_options(argv, names):
+    """(positional arguments, {name: value}) of a command line with `--name VALUE` options; None for one without its value"""
+    opts, args = {}, []
+    it = iter(argv)
+    for a in it:
+        if a.startswith("--") and a[2:] in names:
+            opts[a[2:]] = next(it, None)
+            if opts[a[2:]] is None:
+                print("%s needs a value" % a)
+                return None, None
+        else:
+            args.append(a)
+    return args, opts
+
+
+def makelib_option(opts):
+    """(lfreq file, N) of --makelib LFREQ [--bins N], or None; ValueError for an N outside 2..64"""
+    if "makelib" not in opts:
+        if "bins" in opts:
+            raise ValueError("--bins goes with --makelib")
+        return None
+    N = int(opts.get("bins", 30))
+    if not 2 <= N <= 64:
+        raise ValueError("--bins %d: 2 <= N <= 64" % N)
+    return opts["makelib"], N
+
+
 def main(argv=None):
     argv = sys.argv if argv is None else argv
-    if len(argv) < 4:
-        print("Usage:  python -m soc_amd.mabu  soc.ini absorbed emitted")
+    args, opts = parse_options(argv, ("makelib", "bins", "uselib"))
+    if args is None or len(args) < 4:
+        print("Usage:  python -m soc_amd.mabu  soc.ini absorbed emitted [ofreq.dat] [--makelib LFREQ [--bins N]] [--uselib LFREQ]")
         print("        (N GPUs: python -m torch.distributed.run --nproc-per-node N -m soc_amd.mabu ...)")
+        return 1
+    try:
+        makelib = makelib_option(opts)
+    except ValueError as err:
+        print(err)
         return 1
     from .dist import Comm
     comm = Comm()                      # (imports torch first when there are several ranks: see lib.load_library)
@@ -512,8 +824,8 @@ def main(argv=None):
     t0 = time.time()
     eng = Engine(comm.local_rank)
     try:
-        info = run(argv[1], argv[2], argv[3], eng, comm if comm.world > 1 else None, ofreq=argv[4] if len(argv) > 4 else None,
-                   verbose=True)
+        info = run(args[1], args[2], args[3], eng, comm if comm.world > 1 else None, ofreq=args[4] if len(args) > 4 else None,
+                   verbose=True, makelib=makelib, uselib=opts.get("uselib"))
     finally:
         eng.close()
         comm.close()
