@@ -704,6 +704,29 @@ int soc_mabu_accumulate_p(soc_ctx *ctx, int idust);
 int soc_mabu_ratio(soc_ctx *ctx);
 int soc_mabu_download_p(soc_ctx *ctx, int64_t c0, int64_t n, float *R);
 
+/* ---- dust temperatures and enthalpy-level populations: what the solvers above compute on the way to the emission ----
+ * Opt-in, each call beside the one it extends; without them nothing above changes.
+ *   soc_mabu_download_t(c0, n, T) reads rows [c0, c0+n) of the temperatures that the last soc_mabu_solve_eq left, one float per cell:
+ *       what A2E_MABU.py:551 writes to <dust>.T (kernel_eqsolver.c:5-62).  The next soc_mabu_solve_eq overwrites them.  SOC_ERR_STATE
+ *       outside soc_mabu_begin ... soc_mabu_end and before any soc_mabu_solve_eq.
+ *   soc_a2e_resident_keep_teq(on): with on != 0 every soc_a2e_resident_solve_eq from now on also keeps the temperature of every
+ *       (size, cell), [nsizes][cells] floats of device memory; soc_a2e_resident_end / soc_mabu_end free them and switch this off again.
+ *       SOC_ERR_STATE without resident cells (soc_a2e_resident_begin or soc_mabu_begin).
+ *   soc_a2e_resident_download_teq(slot, c0, n, T) reads rows [c0, c0+n) of size number `slot`, counted in the order in which
+ *       soc_a2e_set_eq_sizes got the sizes: T[CELLS] of A2E.py:506-522 (kernel_A2E.c:110-154).  SOC_ERR_STATE before a
+ *       soc_a2e_resident_solve_eq that kept them.
+ *   soc_a2e_solve_dump(batch, AABS, AEMIT, X) is soc_a2e_solve that also returns X[batch][NE], the populations of the enthalpy levels
+ *       clamped to [1e-35, 10]: the DUMP_TDUST=1 build of DoSolve (A2E.py:393-400 -> kernel_A2E.c:14-16, 101-103).  AEMIT has the bits
+ *       of soc_a2e_solve.
+ *   soc_a2e_resident_solve_dump(X) is soc_a2e_resident_solve that also returns X[cells][NE] (host memory).  The cells are solved in
+ *       chunks and X is read back chunk by chunk, so the device holds the populations of one chunk only (65536 cells x NE floats);
+ *       SOC_ERR_STATE, naming the bytes, where even that cannot be allocated.  The sums get the bits soc_a2e_resident_solve gives. */
+int soc_mabu_download_t(soc_ctx *ctx, int64_t c0, int64_t n, float *T);
+int soc_a2e_resident_keep_teq(soc_ctx *ctx, int on);
+int soc_a2e_resident_download_teq(soc_ctx *ctx, int slot, int64_t c0, int64_t n, float *T);
+int soc_a2e_solve_dump(soc_ctx *ctx, int batch, const float *AABS, float *AEMIT, float *X);
+int soc_a2e_resident_solve_dump(soc_ctx *ctx, float *X);
+
 /* ---- the emission of one dust re-emission iteration, RESIDENT for the cell-emission launches of the next ---- */
 
 /* With `iterations N` and `cellpackets` the emission solved from the absorptions of iteration k-1 is what SimRAM_CL sends at every

@@ -13,6 +13,10 @@ sizes are solved, the equilibrium sizes included: all of those in one launch tha
 (a2e_set_eq_sizes + a2e_resident_solve_eq), with the bits of the route through a2e_eqtemp size by size and batch by batch, which
 an engine without the call keeps.
 
+With DUMP_TDUST=1 in the environment (A2E.py:108-114, 324-326, 378-400, 506-522) every grain size also leaves
+<solver name without .solver>_size%03d.dump: {CELLS, NE} and the populations of the enthalpy levels X[CELLS, NE] of a stochastically
+heated size, clamped to [1e-35, 10] (kernel_A2E.c:101-103), {CELLS, 1} and the temperatures T[CELLS] of an equilibrium size; one rank.
+
 With the seventh argument, a file {CELLS} aalg[CELLS] of each cell's minimum aligned grain size, the emission of the grains larger
 than that is written to <emitted>.P as well (A2E.py:28-29, 192-197, 413-429, 533-539): the polarised emission.
 """
@@ -94,18 +98,39 @@ def eq_size_tables(sol, sizes, polarised=False):
             np.asarray([sol["SIZE_A"][isize] for isize in sizes], f32) if polarised else None)
 
 
-def solve_sizes_resident(engine, sol, nstoch, polarised, eq=True, log=None):
+def dump_name(prefix, isize):
+    """the file of one grain size of a DUMP_TDUST=1 run (A2E.py:379, :508)"""
+    return '%s_size%03d.dump' % (prefix, isize)
+
+
+def write_dump(prefix, isize, X):
+    """One size's dump file: {CELLS, NE} int32 and X[CELLS, NE] float32, the populations of the enthalpy levels of a stochastically
+    heated size (A2E.py:379-400); {CELLS, 1} and T[CELLS], the temperatures of an equilibrium size (A2E.py:506-522)"""
+    X = np.asarray(X, np.float32)
+    X = X.reshape(X.shape[0], -1)
+    with open(dump_name(prefix, isize), 'wb') as fp:
+        np.asarray(X.shape, np.int32).tofile(fp)
+        X.tofile(fp)
+
+
+def solve_sizes_resident(engine, sol, nstoch, polarised, eq=True, log=None, populations=None, keep_teq=False):
     """THE size loop on resident cells -- the block that a2e_resident_begin, or mabu_begin and mabu_split, opened: the sizes below nstoch
     one launch each, in their order (A2E.py:596-600; polarised: with the weights of A2E.py:413-429 for the kernel's epilogue), then all
     equilibrium sizes in one launch that adds them to the same sums (A2E.py:456-547; its hard mask, :533-539).  eq False leaves those to
     the caller; eq 'try' does so as well where the engine refuses their tables (no tile of this NFREQ fits the LDS), and says so
-    through log.  Returns whether the equilibrium sizes were solved here."""
+    through log.  Returns whether the equilibrium sizes were solved here.
+    populations(isize, X[cells, NE]): every stochastic size is solved with a2e_resident_solve_dump and its populations handed over;
+    keep_teq: the launch of the equilibrium sizes keeps their temperatures (a2e_resident_keep_teq), which the caller reads with
+    a2e_resident_download_teq(slot, ...), slot counting eq_sizes(sol, nstoch).  Neither changes the sums."""
     log = log or (lambda line: None)
     for isize in range(nstoch):
         engine.a2e_set_size(sol["NE"], sol["NFREQ"], sol["sizes"][isize], a2e_absorption_fraction(sol, isize))
         if polarised:
             engine.a2e_set_size_aalg(sol["SIZE_A"], isize)
-        engine.a2e_resident_solve()
+        if populations is not None:
+            populations(isize, engine.a2e_resident_solve_dump())
+        else:
+            engine.a2e_resident_solve()
         log("    isize = %d   stochastic heating" % isize)
     sizes = eq_sizes(sol, nstoch) if eq else []
     if not sizes:
@@ -117,6 +142,8 @@ def solve_sizes_resident(engine, sol, nstoch, polarised, eq=True, log=None):
             raise
         log("    a2e: equilibrium sizes not on the device (%s)" % err)
         return False
+    if keep_teq:
+        engine.a2e_resident_keep_teq(True)
     engine.a2e_resident_solve_eq()
     return True
 
@@ -150,9 +177,14 @@ def _add_polarised(PEM, emit, full, part, w):
         PEM[part] += w[part, None] * emit[part]
 
 
-def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, aalg=None):
+def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, aalg=None, dump=None, teq=None):
     """ABSORBED[CELLS,NFREQ] -> EMITTED[CELLS,NFREQ or 1].  Returns (EMITTED, kernel_seconds), or with aalg[CELLS] -- the minimum
-    aligned grain size of every cell -- (EMITTED, PEMITTED, kernel_seconds), PEMITTED the emission of the aligned grains."""
+    aligned grain size of every cell -- (EMITTED, PEMITTED, kernel_seconds), PEMITTED the emission of the aligned grains.
+    dump: a file prefix -- every size the run handles leaves <prefix>_size%03d.dump (write_dump: the populations of a stochastically
+    heated size, the temperatures of an equilibrium size; a size with S_FRAC < 1e-30 is skipped before its file is opened, A2E.py:465),
+    what the reference writes with DUMP_TDUST=1.  teq: a dict that receives {isize: T[CELLS]} of the equilibrium sizes.  Neither
+    changes the emission; both need the engine's calls for them on the route taken (a2e_solve_dump / a2e_resident_solve_dump,
+    a2e_resident_keep_teq), and an engine without those of the resident route is taken through the batches."""
     CELLS, NFREQ = ABSORBED.shape
     if NFREQ != sol["NFREQ"]:
         raise ValueError("absorbed file has %d frequencies, solver %d" % (NFREQ, sol["NFREQ"]))
@@ -168,14 +200,22 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, 
     cols = slice(IFREQ, IFREQ + 1) if IFREQ >= 0 else slice(None)
     ASIZE = sol["SIZE_A"]
     tker = 0.0
+    want_t = dump is not None or teq is not None
+
+    def temperatures(isize, T):
+        if dump is not None:
+            write_dump(dump, isize, T)
+        if teq is not None:
+            teq[isize] = T
     # The stochastically heated sizes with the cells resident in device memory (soc_a2e_resident_*): absorptions up once, every size a
     # launch over all cells that adds its emission to a sum on the device, the sum down once -- instead of NSIZE round trips of every
     # batch (solve_sizes_resident).  The sum is added in the order of the sizes, as the reference's host does, equilibrium sizes last,
     # so the result is the same to the bit.  An engine without a2e_resident_solve_eq gets those size by size through a2e_eqtemp.
     nstoch = stochastic_count(sol, NSTOCH)
-    eq = 'try' if hasattr(engine, "a2e_resident_solve_eq") else False       # (a refusal of the tables: size by size, as before)
+    eq = 'try' if hasattr(engine, "a2e_resident_solve_eq") and (not want_t or hasattr(engine, "a2e_resident_keep_teq")) else False   # (a refusal of the tables: size by size, as before)
     resident = eq_done = False
-    if (nstoch > 0 or (eq and eq_sizes(sol, nstoch))) and hasattr(engine, "a2e_resident_begin") and (aalg is None or hasattr(engine, "a2e_resident_upload_aalg")):
+    if (nstoch > 0 or (eq and eq_sizes(sol, nstoch))) and hasattr(engine, "a2e_resident_begin") and (aalg is None or hasattr(engine, "a2e_resident_upload_aalg")) \
+            and (dump is None or nstoch == 0 or hasattr(engine, "a2e_resident_solve_dump")):
         try:
             if aalg is None:
                 engine.a2e_resident_begin(CELLS, NFREQ)
@@ -192,7 +232,14 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, 
                 engine.a2e_resident_upload(icell, ABSORBED[icell:min(icell + batch, CELLS), :])
                 if aalg is not None:
                     engine.a2e_resident_upload_aalg(icell, aalg[icell:min(icell + batch, CELLS)])
-            eq_done = solve_sizes_resident(engine, sol, nstoch, aalg is not None, eq, print if verbose else None)
+            eq_done = solve_sizes_resident(engine, sol, nstoch, aalg is not None, eq, print if verbose else None,
+                                           populations=None if dump is None else (lambda isize, X: write_dump(dump, isize, X)), keep_teq=want_t)
+            for slot, isize in enumerate(eq_sizes(sol, nstoch)) if (eq_done and want_t) else ():
+                T = np.zeros(CELLS, np.float32)
+                for icell in range(0, CELLS, batch):
+                    b = min(icell + batch, CELLS)
+                    engine.a2e_resident_download_teq(slot, icell, b - icell, out=T[icell:b])
+                temperatures(isize, T)
             for icell in range(0, CELLS, batch):
                 b = min(icell + batch, CELLS)
                 EMITTED[icell:b] += engine.a2e_resident_download(icell, b - icell)[:, cols]
@@ -208,28 +255,45 @@ def run(engine, sol, ABSORBED, NSTOCH=999, IFREQ=-1, batch=65536, verbose=True, 
                 continue
             Emin, kE, oplgkE, TTT, KABS = eq_table(sol, isize)
             scale = sol["GD"] * sol["S_FRAC"][isize]
+            Tall = np.zeros(CELLS, np.float32) if want_t else None
             for icell in range(0, CELLS, batch):
                 b = min(icell + batch, CELLS)
                 tmp = np.asarray(ABSORBED[icell:b, :] * AF, np.float32)
                 t0 = time.time()
                 T, emit = engine.a2e_eqtemp(icell, CELLS, NIP, FACTOR, kE, oplgkE, Emin, sol["FREQ"], KABS, TTT, tmp)
                 tker += time.time() - t0
+                if want_t:
+                    Tall[icell:b] = T
                 EMITTED[icell:b] += emit[:, cols] * scale
                 if aalg is not None:                               # A2E.py:533-539: the hard mask, the reference's own product
                     full = aalg_weights(ASIZE, isize, aalg[icell:b], stochastic=False)[0]
                     PEMITTED[icell:b][full] += emit[full][:, cols] * sol["GD"] * sol["S_FRAC"][isize]
+            if want_t:
+                temperatures(isize, Tall)
             continue
         if resident:
             continue
         engine.a2e_set_size(sol["NE"], NFREQ, sol["sizes"][isize], AF)
-        for icell in range(0, CELLS, batch):
-            b = min(icell + batch, CELLS)
-            t0 = time.time()
-            emit = engine.a2e_solve(ABSORBED[icell:b, :])
-            tker += time.time() - t0
-            EMITTED[icell:b] += emit[:, cols]
-            if aalg is not None:                                   # A2E.py:413-429, on the emission of this batch and size
-                _add_polarised(PEMITTED[icell:b], emit[:, cols], *aalg_weights(ASIZE, isize, aalg[icell:b]))
+        fpX = None
+        if dump is not None:                                       # A2E.py:379-380, :400: the header, then the rows batch by batch
+            fpX = open(dump_name(dump, isize), 'wb')
+            np.asarray([CELLS, sol["NE"]], np.int32).tofile(fpX)
+        try:
+            for icell in range(0, CELLS, batch):
+                b = min(icell + batch, CELLS)
+                t0 = time.time()
+                if fpX is not None:
+                    emit, X = engine.a2e_solve_dump(ABSORBED[icell:b, :])
+                    np.asarray(X, np.float32).tofile(fpX)
+                else:
+                    emit = engine.a2e_solve(ABSORBED[icell:b, :])
+                tker += time.time() - t0
+                EMITTED[icell:b] += emit[:, cols]
+                if aalg is not None:                                   # A2E.py:413-429, on the emission of this batch and size
+                    _add_polarised(PEMITTED[icell:b], emit[:, cols], *aalg_weights(ASIZE, isize, aalg[icell:b]))
+        finally:
+            if fpX is not None:
+                fpX.close()
         if verbose:
             print("    isize = %d   stochastic heating" % isize)
     if aalg is not None:
@@ -247,18 +311,36 @@ def read_aalg(filename, CELLS):
     return np.memmap(filename, dtype=np.float32, mode='r', offset=4, shape=(CELLS,))
 
 
+DUMP_ONE_RANK = ("DUMP_TDUST=1 with %d ranks: every rank solves a share of the cells, and a dump file holds all of them "
+                 "(no dump from part of the cells); run it with one rank")
+
+
+class DumpNeedsOneRank(RuntimeError):
+    """the per-size dump files were asked for in a run of several ranks"""
+
+
+def dump_prefix(solver, environ=None):
+    """The reference's switch (A2E.py:108-117): with DUMP_TDUST=1 in the environment the prefix of the dump files, the solver's name
+    with `.solver` removed; else None"""
+    environ = os.environ if environ is None else environ
+    return solver.replace('.solver', '') if environ.get("DUMP_TDUST") == "1" else None
+
+
 def cell_range(CELLS, rank, world):
     """cells [c0, c1) of rank `rank`: the cells of a grid are independent in A2E, so N GPUs split them"""
     per = (CELLS + world - 1) // world
     return min(rank * per, CELLS), min((rank + 1) * per, CELLS)
 
 
-def run_sharded(engine_factory, solver, absorbed, emitted, NSTOCH=999, IFREQ=-1, comm=None, verbose=True, aalg=None):
+def run_sharded(engine_factory, solver, absorbed, emitted, NSTOCH=999, IFREQ=-1, comm=None, verbose=True, aalg=None, dump=None):
     """The whole program for one rank of `comm` (or alone): memory-map the absorbed file, solve this rank's cells,
     write them into this rank's part of the emitted file.  No collective on the data path -- the ranks only wait
     for rank 0 to have created the file, and for each other at the end.  aalg: the file of the minimum aligned grain sizes; the
-    polarised emission then goes to <emitted>.P in the same way.  Returns (cells solved, kernel seconds)."""
+    polarised emission then goes to <emitted>.P in the same way.  dump: the prefix of the per-size dump files (run); refused with
+    several ranks.  Returns (cells solved, kernel seconds)."""
     rank, world = (comm.rank, comm.world) if comm else (0, 1)
+    if dump is not None and world > 1:                         # (before rank 0 creates the emitted file)
+        raise DumpNeedsOneRank(DUMP_ONE_RANK % world)
     sol = files.read_solver(solver)
     dims = np.fromfile(absorbed, np.int32, 2)
     CELLS, NFREQ = int(dims[0]), int(dims[1])
@@ -278,7 +360,7 @@ def run_sharded(engine_factory, solver, absorbed, emitted, NSTOCH=999, IFREQ=-1,
     if c1 > c0:
         eng = engine_factory()
         try:
-            res = run(eng, sol, ABS[c0:c1, :], NSTOCH, IFREQ, verbose=verbose and rank == 0, aalg=None if AALG is None else AALG[c0:c1])
+            res = run(eng, sol, ABS[c0:c1, :], NSTOCH, IFREQ, verbose=verbose and rank == 0, aalg=None if AALG is None else AALG[c0:c1], dump=dump)
             tker = res[-1]
         finally:
             if hasattr(eng, "close"):
@@ -306,8 +388,13 @@ def main(argv=None):
     aalg = argv[7] if len(argv) > 7 else None                  # A2E.py:104
     t0 = time.time()
     comm = Comm()
-    n, tker = run_sharded(lambda: Engine(comm.local_rank), argv[1], argv[2], argv[3], NSTOCH, IFREQ,
-                          comm if comm.world > 1 else None, aalg=aalg)
+    try:
+        n, tker = run_sharded(lambda: Engine(comm.local_rank), argv[1], argv[2], argv[3], NSTOCH, IFREQ,
+                              comm if comm.world > 1 else None, aalg=aalg, dump=dump_prefix(argv[1]))
+    except DumpNeedsOneRank as err:
+        print(err)
+        comm.close()
+        return 1
     DT = time.time() - t0
     if comm.rank == 0:
         print('@@  a2e %.3f SECONDS   (solver calls %.3f s on rank 0, %d ranks)' % (DT, tker, comm.world))

@@ -69,7 +69,11 @@ __device__ __forceinline__ float a2e_row_sum(const float *Lr, const float *X, co
 // host); the subtraction, the division, the product w * I and the sum are single fp32 operations (the build has -ffp-contract=off), so
 // the bits are those of numpy's float32 expressions.  Without POL the kernel is the one it was: the three plain instances keep their
 // instructions.
-template <int C, bool POL>
+// DUMP: the normalised populations of the enthalpy levels also go out, clamped as the reference's dump is (kernel_A2E.c:14-16, 101-103:
+// XX[id * NE + i] = clamp(XL[i], 1e-35f, 10.0f), written as fmin(fmax()) so that a NaN gives the lower bound), the row of a cell by the
+// wave that has solved it, the lanes on neighbouring words.  XL is read, not written, so the emission is the one it was; built as POL
+// was: the instances without DUMP keep their instructions.
+template <int C, bool POL, bool DUMP>
 __global__ __launch_bounds__(A2E_T) void soc_a2e_dosolve_kernel(const SocA2EArgs A)
 {
     extern __shared__ float lds[];
@@ -213,6 +217,10 @@ __global__ __launch_bounds__(A2E_T) void soc_a2e_dosolve_kernel(const SocA2EArgs
     A2E_PROF(3);                                         // normalisation
     // 4. emission (kernel_A2E.c:95-100): one frequency per lane, serial over the bins
     if (mine) {
+        if constexpr (DUMP) {
+            float *XX = A.XX + (size_t)(cell0 + wv) * NE;
+            for (int i = lane; i < NE; i += 64) XX[i] = __builtin_fminf(__builtin_fmaxf(XL[i], 1.0e-35f), 10.0f);
+        }
         float *EMIT = A.AEMIT + (size_t)(cell0 + wv) * NFREQ;
         int   arm = 0;                                        // 0: this size is not aligned in the cell, 1: wholly, 2: in part (weight pw)
         float pw = 0.0f;
@@ -274,8 +282,10 @@ __global__ void soc_a2e_eqtemp_kernel(const SocEqTArgs A)
 //          write; with POL the same for the polarised sum with (emit * GD) * S_FRAC where SIZE_A[size] >= a_alg of the cell.
 // The per-size tables AF, KABS [nsizes][NFREQ], TTT [nsizes][NIP] and scalars come from device memory (L2; the lanes of a wave read
 // neighbouring words or one word).
+// KEEP: phase A also writes the temperature to TOUT[size][cell] (the lanes of a wave on neighbouring cells of one size) -- what
+// A2E.py:506-522 dumps per size; a template parameter, so that the instances without it keep their instructions.
 #define A2E_EQ_T 256
-template <bool POL>
+template <bool POL, bool KEEP>
 __global__ __launch_bounds__(A2E_EQ_T) void soc_a2e_eqsizes_kernel(const SocEqSizesArgs A)
 {
     extern __shared__ float lds[];
@@ -308,7 +318,9 @@ __global__ __launch_bounds__(A2E_EQ_T) void soc_a2e_eqsizes_kernel(const SocEqSi
         int iE = (int)soc_floorf(oplgkE * soc_log10f(Ein / Emin));
         iE = iE < 0 ? 0 : (iE > A.NIP - 2 ? A.NIP - 2 : iE);
         const float wi = (Emin * soc_pownf(kE, iE + 1) - Ein) / (Emin * soc_pownf(kE, iE + 1) - soc_pownf(kE, iE));
-        sT[s * TC + c] = (float)((double)(wi * TTT[iE]) + (1.0 - (double)wi) * (double)TTT[iE + 1]);
+        const float TP = (float)((double)(wi * TTT[iE]) + (1.0 - (double)wi) * (double)TTT[iE + 1]);
+        sT[s * TC + c] = TP;
+        if constexpr (KEEP) A.TOUT[(size_t)s * (size_t)A.cells + (size_t)(cell0 + c)] = TP;
     }
     __syncthreads();
     // B: the emission of every size, added to the sums in ascending order of the sizes
@@ -345,15 +357,15 @@ bool soc_a2e_eq_shape(int NFREQ, int nsizes, int out[2])
     return false;
 }
 
-template <bool POL>
+template <bool POL, bool KEEP>
 static hipError_t a2e_eqsizes_launch(const SocEqSizesArgs &A, size_t lds, hipStream_t st)
 {
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)soc_a2e_eqsizes_kernel<POL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void *)soc_a2e_eqsizes_kernel<POL, KEEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     const long long tiles = (A.cells + A.TC - 1) / A.TC;
-    soc_a2e_eqsizes_kernel<POL><<<(unsigned)tiles, A2E_EQ_T, lds, st>>>(A);
+    soc_a2e_eqsizes_kernel<POL, KEEP><<<(unsigned)tiles, A2E_EQ_T, lds, st>>>(A);
     return hipGetLastError();
 }
 
@@ -365,8 +377,9 @@ hipError_t soc_launch_a2e_eqsizes(SocEqSizesArgs A, hipStream_t st)
     if (A.PSUM && (!A.AALG || !A.SIZEA)) return hipErrorInvalidValue;
     A.TC = shape[0];  A.stride = A.NFREQ | 1;
     if ((A.cells + A.TC - 1) / A.TC > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (A.PSUM) return a2e_eqsizes_launch<true>(A, (size_t)shape[1], st);
-    return a2e_eqsizes_launch<false>(A, (size_t)shape[1], st);
+    if (A.TOUT) return A.PSUM ? a2e_eqsizes_launch<true, true>(A, (size_t)shape[1], st) : a2e_eqsizes_launch<false, true>(A, (size_t)shape[1], st);
+    if (A.PSUM) return a2e_eqsizes_launch<true, false>(A, (size_t)shape[1], st);
+    return a2e_eqsizes_launch<false, false>(A, (size_t)shape[1], st);
 }
 
 // kernel_eqsolver.c (A2E_MABU.py SolveEquilibriumDust): EqTemperature :5-62 and Emission :66-79 of one equilibrium
@@ -423,22 +436,23 @@ bool soc_a2e_shape(int NE, int NFREQ, int out[3])
     return true;
 }
 
-template <int C, bool POL>
+template <int C, bool POL, bool DUMP>
 static hipError_t a2e_launch_as(const SocA2EArgs &A, int T, size_t lds, hipStream_t st)
 {
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)soc_a2e_dosolve_kernel<C, POL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void *)soc_a2e_dosolve_kernel<C, POL, DUMP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    soc_a2e_dosolve_kernel<C, POL><<<(A.batch + C - 1) / C, T, lds, st>>>(A);
+    soc_a2e_dosolve_kernel<C, POL, DUMP><<<(A.batch + C - 1) / C, T, lds, st>>>(A);
     return hipGetLastError();
 }
 
 template <int C>
 static hipError_t a2e_launch(const SocA2EArgs &A, int T, size_t lds, hipStream_t st)
 {
-    if (A.PEMIT) return a2e_launch_as<C, true>(A, T, lds, st);
-    return a2e_launch_as<C, false>(A, T, lds, st);
+    if (A.XX) return A.PEMIT ? a2e_launch_as<C, true, true>(A, T, lds, st) : a2e_launch_as<C, false, true>(A, T, lds, st);
+    if (A.PEMIT) return a2e_launch_as<C, true, false>(A, T, lds, st);
+    return a2e_launch_as<C, false, false>(A, T, lds, st);
 }
 
 hipError_t soc_launch_a2e_dosolve(const SocA2EArgs &A, hipStream_t st)

@@ -129,7 +129,8 @@ int soc_a2e_download(soc_ctx *c, int batch, float *AEMIT)
 static void resident_release(soc_ctx *c)
 {
     c->aAll.release();  c->aSum.release();  c->aPSum.release();  c->aAalg.release();
-    c->a2e_cells = 0;  c->a2e_pol_set = false;
+    c->aTeq.release();  c->aXX.release();
+    c->a2e_cells = 0;  c->a2e_pol_set = false;  c->teq_keep = false;  c->teq_nsizes = 0;
 }
 
 // aAll | aSum, zeroed, for cells x NFREQ floats; with polarised output aPSum, zeroed, and aAalg (else neither).  Both begins come here;
@@ -149,6 +150,7 @@ static hipError_t resident_alloc(soc_ctx *c, int64_t cells, int NFREQ, bool pola
         c->aPSum.release();  c->aAalg.release();
     }
     c->a2e_pol_set = false;
+    c->teq_nsizes = 0;                                      // (temperatures kept for the cells of a block before are none of this one's)
     return e;
 }
 
@@ -221,24 +223,55 @@ int soc_a2e_set_size_aalg(soc_ctx *c, float asize, float asize_next, float lg_as
     return SOC_OK;
 }
 
-int soc_a2e_resident_solve(soc_ctx *c)
+// cells per launch of the resident solve (the grid is one workgroup per four cells); with the populations read back, the cells whose
+// populations the device holds at a time: 65536 x NE floats, 73 MB at the largest NE
+#define A2E_RES_STEP  ((int64_t)1 << 20)
+#define A2E_DUMP_STEP ((int64_t)1 << 16)
+
+// DoSolve of the current size over the resident cells, in chunks, added to the sums.  X (host, [cells][NE]), or NULL: the clamped
+// populations too, through a device plane of one chunk that is read back after the chunk's launch, before the next one writes it
+static int resident_solve(soc_ctx *c, const char *who, float *X)
 {
-    if (!c) return SOC_ERR_ARG;
-    if (!c->aAll) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve: call soc_a2e_resident_begin first");
-    if (c->a2e_NE == 0 || c->a2e_NFREQ != c->a2e_res_nfreq) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve: soc_a2e_set_size with NFREQ = %d first", c->a2e_res_nfreq);
+    if (!c->aAll) return fail(c, SOC_ERR_STATE, "%s: call soc_a2e_resident_begin first", who);
+    if (c->a2e_NE == 0 || c->a2e_NFREQ != c->a2e_res_nfreq) return fail(c, SOC_ERR_STATE, "%s: soc_a2e_set_size with NFREQ = %d first", who, c->a2e_res_nfreq);
     HIPCHK(c, hipSetDevice(c->device));
     SocA2EArgs A = a2e_tables(c);
     A.accumulate = 1;
     const bool pol = c->aPSum && c->aAalg && c->a2e_pol_set;   // (a size without soc_a2e_set_size_aalg adds nothing to the polarised sum)
     if (pol) { A.p_size = c->a2e_pol[0];  A.p_next = c->a2e_pol[1];  A.p_lgsize = c->a2e_pol[2];  A.p_lgden = c->a2e_pol[3]; }
-    const int64_t step = 1 << 20;                           // cells per launch (the grid is one workgroup per four cells)
+    const int64_t step = X ? A2E_DUMP_STEP : A2E_RES_STEP;
+    if (X) {
+        const size_t n = (size_t)std::min<int64_t>(step, c->a2e_cells) * A.NE;
+        if (c->aXX.reserve(n, c->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, SOC_ERR_STATE, "%s: the populations of a chunk of %lld cells x %d levels need %zu bytes of device memory, which are not free",
+                        who, (long long)std::min<int64_t>(step, c->a2e_cells), A.NE, n * sizeof(float));
+        }
+        A.XX = c->aXX;
+    }
     for (int64_t c0 = 0; c0 < c->a2e_cells; c0 += step) {
         A.batch = (int)std::min<int64_t>(step, c->a2e_cells - c0);
         A.AABS = c->aAll + (size_t)c0 * A.NFREQ;  A.AEMIT = c->aSum + (size_t)c0 * A.NFREQ;
         if (pol) { A.PEMIT = c->aPSum + (size_t)c0 * A.NFREQ;  A.AALG = c->aAalg + (size_t)c0 * 2; }
         HIPCHK(c, soc_launch_a2e_dosolve(A, c->stream));
+        if (X) {
+            HIPCHK(c, hipMemcpyAsync(X + (size_t)c0 * A.NE, c->aXX, (size_t)A.batch * A.NE * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
     }
     return SOC_OK;
+}
+
+int soc_a2e_resident_solve(soc_ctx *c)
+{
+    if (!c) return SOC_ERR_ARG;
+    return resident_solve(c, "soc_a2e_resident_solve", nullptr);
+}
+
+int soc_a2e_resident_solve_dump(soc_ctx *c, float *X)
+{
+    if (!c || !X) return SOC_ERR_ARG;
+    return resident_solve(c, "soc_a2e_resident_solve_dump", X);
 }
 
 int soc_a2e_set_eq_sizes(soc_ctx *c, int nsizes, int NFREQ, int NIP, float FACTOR, const float *FREQ, const float *AF, const float *KABS,
@@ -293,7 +326,38 @@ int soc_a2e_resident_solve_eq(soc_ctx *c)
     A.Emin = par;  A.kE = par + ns;  A.oplgkE = par + 2 * ns;  A.scale = par + 3 * ns;  A.SFRAC = par + 4 * ns;  A.SIZEA = par + 5 * ns;
     A.ABS = c->aAll;  A.SUM = c->aSum;
     if (c->eq_pol) { A.PSUM = c->aPSum;  A.AALG = c->aAalg; }
+    c->teq_nsizes = 0;                                      // (what an earlier solve kept is not of these sizes)
+    if (c->teq_keep) {
+        if (c->aTeq.reserve((size_t)ns * (size_t)c->a2e_cells, c->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, SOC_ERR_STATE, "soc_a2e_resident_solve_eq: the temperatures of %d sizes x %lld cells need %zu bytes of device memory, which are not free "
+                                          "(soc_a2e_resident_keep_teq is on; fewer cells at a time)", ns, (long long)c->a2e_cells, (size_t)ns * (size_t)c->a2e_cells * sizeof(float));
+        }
+        A.TOUT = c->aTeq;
+    }
     HIPCHK(c, soc_launch_a2e_eqsizes(A, c->stream));
+    if (c->teq_keep) c->teq_nsizes = ns;
+    return SOC_OK;
+}
+
+int soc_a2e_resident_keep_teq(soc_ctx *c, int on)
+{
+    if (!c) return SOC_ERR_ARG;
+    if (!c->aAll || !c->aSum) return fail(c, SOC_ERR_STATE, "soc_a2e_resident_keep_teq: call soc_a2e_resident_begin or soc_mabu_begin first");
+    c->teq_keep = on != 0;
+    return SOC_OK;
+}
+
+int soc_a2e_resident_download_teq(soc_ctx *c, int slot, int64_t c0, int64_t n, float *T)
+{
+    if (!c || !T) return SOC_ERR_ARG;
+    if (!c->aAll || !c->aTeq || c->teq_nsizes < 1)
+        return fail(c, SOC_ERR_STATE, "soc_a2e_resident_download_teq: no temperatures are kept (soc_a2e_resident_keep_teq, then soc_a2e_resident_solve_eq)");
+    if (slot < 0 || slot >= c->teq_nsizes) return fail(c, SOC_ERR_ARG, "soc_a2e_resident_download_teq: size %d of %d", slot, c->teq_nsizes);
+    SOC_ROWS(c, "soc_a2e_resident_download_teq", c0, n, c->a2e_cells);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(T, c->aTeq + (size_t)slot * (size_t)c->a2e_cells + (size_t)c0, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return SOC_OK;
 }
 
@@ -329,6 +393,25 @@ int soc_a2e_solve(soc_ctx *c, int batch, const float *AABS, float *AEMIT)
     r = soc_a2e_run(c, batch);
     if (r) return r;
     return soc_a2e_download(c, batch, AEMIT);
+}
+
+int soc_a2e_solve_dump(soc_ctx *c, int batch, const float *AABS, float *AEMIT, float *X)
+{
+    if (!c || !AEMIT || !X) return SOC_ERR_ARG;
+    int r = soc_a2e_upload(c, batch, AABS);
+    if (r) return r;
+    FLUSH(c);
+    const size_t n = (size_t)batch * c->a2e_NE;
+    if (c->aXX.reserve(n, c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, SOC_ERR_STATE, "soc_a2e_solve_dump: the populations of %d cells x %d levels need %zu bytes of device memory, which are not free",
+                    batch, c->a2e_NE, n * sizeof(float));
+    }
+    SocA2EArgs A = a2e_tables(c);
+    A.batch = batch;  A.AABS = c->aABS;  A.AEMIT = c->aEMIT;  A.XX = c->aXX;
+    HIPCHK(c, soc_launch_a2e_dosolve(A, c->stream));
+    HIPCHK(c, hipMemcpyAsync(X, c->aXX, n * 4, hipMemcpyDeviceToHost, c->stream));
+    return soc_a2e_download(c, batch, AEMIT);               // (waits for the stream: X has landed as well)
 }
 
 static int eqtemp_common(soc_ctx *c, const char *who, bool eqsolver, int batch, int icell, int CELLS, int NFREQ, int NIP, float FACTOR, float kE,
@@ -380,7 +463,7 @@ static void mabu_release(soc_ctx *c)
     c->mABS.release();  c->mSUM.release();  c->mABU.release();  c->mT.release();  c->mTab.release();  c->mRABS.release();
     c->mPSUM.release();  c->mPol.release();
     resident_release(c);
-    c->mabu_ndust = 0;  c->mabu_tables = false;
+    c->mabu_ndust = 0;  c->mabu_tables = false;  c->mabu_t_set = false;
 }
 
 int soc_mabu_begin(soc_ctx *c, int64_t cells, int NFREQ, int NDUST, int64_t *cells_fit)
@@ -487,6 +570,19 @@ int soc_mabu_solve_eq(soc_ctx *c, int NE, float FACTOR, float kE, float oplgkE, 
     A.FACTOR = FACTOR;  A.kE = kE;  A.oplgkE = oplgkE;  A.Emin = Emin;
     A.FREQ = dF;  A.KABS = dK;  A.TTT = dT3;  A.ABS = c->aAll;  A.T = c->mT;  A.EMIT = c->aSum;
     HIPCHK(c, soc_launch_eqsolver(A, c->stream));
+    c->mabu_t_set = true;
+    return SOC_OK;
+}
+
+int soc_mabu_download_t(soc_ctx *c, int64_t c0, int64_t n, float *T)
+{
+    if (!c || !T) return SOC_ERR_ARG;
+    MABU_OPEN(c, "soc_mabu_download_t");
+    if (!c->mT || !c->mabu_t_set) return fail(c, SOC_ERR_STATE, "soc_mabu_download_t: no soc_mabu_solve_eq since soc_mabu_begin");
+    SOC_ROWS(c, "soc_mabu_download_t", c0, n, c->a2e_cells);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(T, c->mT + (size_t)c0, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return SOC_OK;
 }
 

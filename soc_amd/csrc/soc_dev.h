@@ -249,6 +249,7 @@ struct SocA2EArgs {
     const float *AALG;               // [batch][2]: a_alg and log10(a_alg) of the cell
     float        p_size, p_next;     // ASIZE[isize]; ASIZE[isize+1], or 0 for the last size (no partial arm)
     float        p_lgsize, p_lgden;  // log10(ASIZE[isize]); log10(ASIZE[isize+1]) - log10(ASIZE[isize])
+    float       *XX;                 // [batch*NE], NULL without: the clamped populations of the enthalpy levels (kernel_A2E.c:101-103)
 };
 
 struct SocEqTArgs {
@@ -274,6 +275,7 @@ struct SocEqSizesArgs {
     float       *SUM;                // [cells*NFREQ]
     float       *PSUM;               // [cells*NFREQ], NULL without polarised output
     const float *AALG;               // [cells][2]: a_alg and log10(a_alg) of the cell
+    float       *TOUT;               // [nsizes][cells], NULL without: the temperature of every (size, cell) (A2E.py:506-522)
 };
 
 #define SOC_A2E_LDS (160 * 1024)     // bytes of LDS a DoSolve workgroup may take (the CU's)

@@ -129,6 +129,13 @@ struct soc_ctx {
     int     eq_nsizes = 0, eq_NFREQ = 0, eq_NIP = 0;         // eq_nsizes 0: none are set
     float   eq_FACTOR = 0.0f, eq_GD = 0.0f;
     bool    eq_pol = false;                                  // SIZE_A was given: the sizes also add to the polarised sum
+    // temperatures and populations on request: aTeq[teq_nsizes][a2e_cells] of the last soc_a2e_resident_solve_eq (teq_nsizes 0: none
+    // kept; teq_keep: soc_a2e_resident_keep_teq is on), aXX the clamped populations of one batch or one chunk of cells, a2e_NE floats
+    // each (soc_a2e_solve_dump, soc_a2e_resident_solve_dump).  The resident block's end releases them and the switch
+    DevBuf<float> aTeq, aXX;
+    bool    teq_keep = false;
+    int     teq_nsizes = 0;
+    bool    mabu_t_set = false;                              // a soc_mabu_solve_eq has filled mT since soc_mabu_begin
     // the multi-dust stage (soc_mabu_*): absorptions as the absorbed file holds them, the sum over the dusts, abundances, relative cross
     // sections, temperatures and tables of an equilibrium dust; the current dust's share and its emission are aAll and aSum
     DevBuf<float>  mABS, mSUM, mABU, mT, mTab;

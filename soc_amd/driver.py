@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """driver -- the three stages of a SOC run with several dust components, in one process and in memory:
 
-    python -m soc_amd.driver soc.ini [--keep-files] [--makelib LFREQ [--bins N]]
+    python -m soc_amd.driver soc.ini [--keep-files] [--makelib LFREQ [--bins N]] [--temperatures]
 
 Counterpart of ``ASOC_driver.py soc.ini`` + ``A2E_MABU.py`` (reference ASOC_driver.py:200-473, A2E_MABU.py:236-342,
 700-1180): the reference chains three programs with os.system and hands the absorptions (CELLS x NFREQ floats: 5-17 GB
@@ -35,6 +35,13 @@ sink holds all frequencies and is not used), stage 2 is the look-up in those lib
 writes all frequencies -- or, with `libmaps FILE2` as well, the maps of the frequencies of FILE2 from an emission array of just
 those columns, the bytes python -m soc_amd.asoc with `libmaps` writes from the emitted file written here.  `libmaps` without
 `libabs` is refused; with a library run also re-emission iterations, `polarisation` lines, saveint, nnmake / absthin and several ranks.
+
+--temperatures (Pipeline(temperatures=True)): stage 2 also hands out the dust temperatures it computes (mabu.solve_emission with
+temperatures: 4 bytes per cell and equilibrium dust or equilibrium size, read back after each dust's solve on the device path, which
+stays in use, as do the resident emission and absorptions), and rank 0 writes the files python -m soc_amd.mabu --temperatures writes
+from the absorbed file: '<dust>.T' and <solver name>_size%03d.dump (A2E_MABU.py:551, A2E.py:506-522).  With re-emission iterations the
+temperatures of every step's solve are kept and those of the step whose emission is the product -- the last, or the one `convergence`
+stopped at -- are written, once, after the loop.  One rank, and not in a library run (nothing is solved there), else refused.
 
 Dust re-emission (`iterations N` with `cellpackets`): the constant sources are simulated once and their absorptions C kept unscaled;
 E_0 is solved from them; then, N times, the emission E_(k-1) is sent from the cells at every simulated frequency (SimRAM_CL, as a run
@@ -73,8 +80,9 @@ from .mabu import (NE_EQ, dust_kind, eq_dust_table, planck_safe, relative_cross_
 class Pipeline:
     """soc.ini -> maps.  engine: soc_amd.lib.Engine (or an object with its methods); comm: soc_amd.dist.Comm"""
 
-    def __init__(self, ini, engine, comm=None, verbose=None, emission_source=None, absorbed_source=None, makelib=None):
+    def __init__(self, ini, engine, comm=None, verbose=None, emission_source=None, absorbed_source=None, makelib=None, temperatures=False):
         """makelib = (lfreq file, N): the libraries <dust>.mlib are written besides (mabu.solve_emission(makelib=...));
+        temperatures: the temperature files of soc_amd.mabu are written besides (mabu.write_temperatures), from stage 2;
         emission_source: None -- the re-emission iterations take the resident emission where they can (see iterate) -- or 'host' to
         keep them on the host statements (tests, measurements); absorbed_source: the same for the absorptions on their way from the
         transfer stage to stage 2 (see open_absorbed)"""
@@ -99,6 +107,11 @@ class Pipeline:
         # run sees `libabs` alone (one list of frequencies serves both keys there, and it refuses the two together)
         self.library = 'libabs' in U.KEYS
         self.makelib = makelib
+        self.temperatures, self.T = bool(temperatures), None
+        if self.temperatures and self.world > 1:
+            raise UnsupportedOption(mabu.TEMPERATURES_ONE_RANK % self.world)
+        if self.temperatures and self.library:
+            raise UnsupportedOption(mabu.TEMPERATURES_NO_LIBRARY % "libabs")
         self.fmaps = None
         if makelib is not None and (self.library or (U.ITERATIONS > 0 and U.CLPAC > 0)):
             raise UnsupportedOption("makelib %s" % ("in a library run (libabs): the libraries are built from a run with all frequencies" if self.library else
@@ -152,7 +165,9 @@ class Pipeline:
         mabu.solve_emission; self.resident says whether the engine now holds this emission (then, with download=False, the arrays
         returned are not filled).  FABSORBED a ResidentAbsorptions with absorbed_scale: as mabu.solve_emission"""
         em, info = mabu.solve_emission(self.eng, self.dusts, self.kinds, FABSORBED, ABU, self.rank, self.world, log=self.log, pol=self.pol,
-                                       keep_resident=keep_resident, download=download, absorbed_scale=absorbed_scale, makelib=makelib)
+                                       keep_resident=keep_resident, download=download, absorbed_scale=absorbed_scale, makelib=makelib,
+                                       temperatures=self.temperatures)
+        self.T = info.get("T")                                 # (of this solve: after the loop, of the step whose emission is the product)
         if makelib is not None and self.rank == 0:
             mabu.write_libraries(self.dusts, info["libraries"], self.log)
         self.timers["emission_path"] = info["path"]            # 'device' (soc_mabu_*) or 'host'
@@ -410,6 +425,8 @@ class Pipeline:
                 files.write_absorbed(U.file_absorbed, FABSORBED)
             if keep_files and self.R is not None and len(U.file_emitted) > 0:
                 mabu.write_reduction(U.file_emitted + '.R', self.R)
+            if self.T is not None:
+                mabu.write_temperatures(self.dusts, self.kinds, self.T, self.log)
         t0 = time.time()
         if self.want_maps:
             U.NOMAP = 0
@@ -431,7 +448,7 @@ def main(argv=None):
     argv = sys.argv if argv is None else argv
     args, opts = mabu.parse_options(argv, ("makelib", "bins"))
     if args is None or len(args) < 2:
-        print("Usage:  python -m soc_amd.driver soc.ini [--keep-files] [--makelib LFREQ [--bins N]]")
+        print("Usage:  python -m soc_amd.driver soc.ini [--keep-files] [--makelib LFREQ [--bins N]] [--temperatures]")
         return 1
     try:
         makelib = mabu.makelib_option(opts)
@@ -444,7 +461,12 @@ def main(argv=None):
     eng = Engine(comm.local_rank)
     try:
         keep = "--keep-files" in args
-        Pipeline(args[1], eng, comm, makelib=makelib).run(keep_files=keep, want_absorbed=keep)
+        Pipeline(args[1], eng, comm, makelib=makelib, temperatures="--temperatures" in args).run(keep_files=keep, want_absorbed=keep)
+    except UnsupportedOption as err:
+        if "--temperatures" not in args:
+            raise
+        print(err)
+        return 1
     finally:
         eng.close()
         comm.close()

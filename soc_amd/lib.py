@@ -156,6 +156,11 @@ API = {
     "soc_mabu_accumulate_p": (C.c_int, [C.c_void_p, C.c_int]),
     "soc_mabu_ratio": (C.c_int, [C.c_void_p]),
     "soc_mabu_download_p": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
+    "soc_mabu_download_t": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
+    "soc_a2e_resident_keep_teq": (C.c_int, [C.c_void_p, C.c_int]),
+    "soc_a2e_resident_download_teq": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, _F]),
+    "soc_a2e_solve_dump": (C.c_int, [C.c_void_p, C.c_int, _F, _F, _F]),
+    "soc_a2e_resident_solve_dump": (C.c_int, [C.c_void_p, _F]),
     "soc_emitted_begin": (C.c_int, [C.c_void_p, C.c_int]),
     "soc_emitted_upload": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _F]),
     "soc_emitted_from_mabu": (C.c_int, [C.c_void_p, C.c_int64]),
@@ -279,6 +284,15 @@ def _rows_out(who, n, NFREQ, out):
         return np.zeros((max(int(n), 0), NFREQ), np.float32)
     if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable and out.shape == (int(n), NFREQ)):
         raise SocError("%s: out must be a writeable C-contiguous float32 array of shape (%d, %d)" % (who, int(n), NFREQ))
+    return out
+
+
+def _vector_out(who, n, out):
+    """the n floats that a download of one value per cell fills: new ones, or the caller's `out`"""
+    if out is None:
+        return np.zeros(max(int(n), 0), np.float32)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable and out.shape == (int(n),)):
+        raise SocError("%s: out must be a writeable C-contiguous float32 array of shape (%d,)" % (who, int(n)))
     return out
 
 
@@ -935,6 +949,7 @@ class Engine:
         self._chk(self.lib.soc_a2e_set_size(self.h, int(NE), int(NFREQ), int(a["Iw"].size), _f(a["Iw"]), _i(a["L1"]),
                                             _i(a["L2"]), _f(a["Tdown"]), _f(a["EA"]), _i(a["Ibeg"]), _f(AF)))
         self._a2e_nfreq = NFREQ                              # (a refused size leaves the one before in place)
+        self._a2e_ne = int(NE)
 
     def a2e_launch_shape(self):
         """(cells per workgroup, threads per workgroup, dynamic LDS bytes) of DoSolve for the size of the last a2e_set_size."""
@@ -947,6 +962,19 @@ class Engine:
         out = np.zeros_like(AABS)
         self._chk(self.lib.soc_a2e_solve(self.h, AABS.shape[0], _f(AABS), _f(out)))
         return out
+
+    def a2e_solve_dump(self, AABS):
+        """a2e_solve that also returns the populations of the enthalpy levels, clamped to [1e-35, 10] as the reference's DUMP_TDUST
+        build leaves them: (EMIT[batch, NFREQ], X[batch, NE]); EMIT has the bits of a2e_solve"""
+        AABS = np.ascontiguousarray(AABS, np.float32)
+        NE = getattr(self, "_a2e_ne", 0)
+        if NE < 1:
+            raise SocError("a2e_solve_dump: call a2e_set_size first")
+        if AABS.ndim != 2 or AABS.shape[0] < 1 or AABS.shape[1] != self._a2e_nfreq:
+            raise SocError("a2e_solve_dump: an array of shape %s for rows of %d frequencies" % (AABS.shape, self._a2e_nfreq))
+        out, X = np.zeros_like(AABS), np.zeros((AABS.shape[0], NE), np.float32)
+        self._chk(self.lib.soc_a2e_solve_dump(self.h, AABS.shape[0], _f(AABS), _f(out), _f(X)))
+        return out, X
 
     def a2e_upload(self, AABS):
         AABS = np.ascontiguousarray(AABS, np.float32)
@@ -993,6 +1021,16 @@ class Engine:
     def a2e_resident_solve(self):
         self._chk(self.lib.soc_a2e_resident_solve(self.h))
 
+    def a2e_resident_solve_dump(self, out=None):
+        """a2e_resident_solve that also returns X[cells, NE], the clamped populations of the current size in every resident cell (read
+        back chunk by chunk: the device holds those of one chunk); out: a C-contiguous float32 array [cells, NE] to fill"""
+        NE = getattr(self, "_a2e_ne", 0)
+        if NE < 1 or self._a2e_res[0] < 1:
+            raise SocError("a2e_resident_solve_dump: call a2e_resident_begin (or mabu_begin) and a2e_set_size first")
+        X = _rows_out("a2e_resident_solve_dump", self._a2e_res[0], NE, out)
+        self._chk(self.lib.soc_a2e_resident_solve_dump(self.h, _f(X)))
+        return X
+
     def a2e_set_eq_sizes(self, NIP, FACTOR, FREQ, AF, KABS, TTT, Emin, kE, oplgkE, GD, S_FRAC, SIZE_A=None):
         """the tables of the equilibrium sizes of a dust, in the order in which a2e_resident_solve_eq adds their emission: AF, KABS
         [nsizes, NFREQ], TTT[nsizes, NIP], Emin, kE, oplgkE, S_FRAC [nsizes]; SIZE_A[nsizes]: they also add to the polarised sum"""
@@ -1012,6 +1050,18 @@ class Engine:
         """the sizes of a2e_set_eq_sizes on the resident cells (a2e_resident_begin or mabu_begin), added to the sum after the
         stochastic sizes' a2e_resident_solve calls"""
         self._chk(self.lib.soc_a2e_resident_solve_eq(self.h))
+
+    def a2e_resident_keep_teq(self, on=True):
+        """on: every a2e_resident_solve_eq of this resident block also keeps the temperature of every (size, cell) for
+        a2e_resident_download_teq; the block's end (a2e_resident_end, mabu_end) switches it off"""
+        self._chk(self.lib.soc_a2e_resident_keep_teq(self.h, int(bool(on))))
+
+    def a2e_resident_download_teq(self, slot, c0, n, out=None):
+        """T[n] of the cells [c0, c0 + n) for size number `slot` of the last a2e_set_eq_sizes, after an a2e_resident_solve_eq that
+        kept them; out: a C-contiguous float32 array [n] to fill"""
+        out = _vector_out("a2e_resident_download_teq", n, out)
+        self._chk(self.lib.soc_a2e_resident_download_teq(self.h, int(slot), int(c0), int(n), _f(out)))
+        return out
 
     def a2e_resident_download(self, c0, n, out=None):
         out = _rows_out("a2e_resident_download", n, self._a2e_res[1], out)
@@ -1104,6 +1154,14 @@ class Engine:
         """rows [c0, c0 + n) of the sum; out: a C-contiguous float32 array [n, NFREQ] to fill (anything else is refused)"""
         out = _rows_out("mabu_download", n, self._mabu_open("mabu_download")[1], out)
         self._chk(self.lib.soc_mabu_download(self.h, int(c0), int(n), _f(out)))
+        return out
+
+    def mabu_download_t(self, c0, n, out=None):
+        """T[n] of the cells [c0, c0 + n): the temperatures the last mabu_solve_eq left (the <dust>.T of A2E_MABU.py:551); out: a
+        C-contiguous float32 array [n] to fill"""
+        self._mabu_open("mabu_download_t")
+        out = _vector_out("mabu_download_t", n, out)
+        self._chk(self.lib.soc_mabu_download_t(self.h, int(c0), int(n), _f(out)))
         return out
 
     def mabu_pol_eq(self, apol, tab):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """mabu -- emission of a model with several dust components from its absorptions:
 
-    python -m soc_amd.mabu  soc.ini  absorbed.data  emitted.data  [ofreq.dat]  [--makelib LFREQ [--bins N]]  [--uselib LFREQ]
+    python -m soc_amd.mabu  soc.ini  absorbed.data  emitted.data  [ofreq.dat]  [--makelib LFREQ [--bins N]]  [--uselib LFREQ]  [--temperatures]
 
 Counterpart of ``A2E_MABU.py ini absorbed.data emitted.data`` (reference A2E_MABU.py:236-342, 700-1180): the dust list,
 the abundance files and `singleabu` come from the ini, an equilibrium dust is solved from its dust file, a
@@ -44,6 +44,13 @@ weighted sum on the host, the same bits); a (cell, dust) without an answer adds 
 selects the library columns nearest to its frequencies.  --uselib LFREQ with an absorbed file of all frequencies does the same look-up
 from its reference columns and then solves every cell with a miss in any dust directly, overwriting those rows: a library checked
 against the direct solve on one run.  <dust>.mlib.new is not written.
+
+--temperatures (run(temperatures=True), solve_emission(temperatures=True)): the dust temperatures that the solvers compute on the way
+to the emission are written as the reference writes them -- '<dust>.T', raw float32 [CELLS], for every equilibrium dust
+(A2E_MABU.py:551), and <solver name without .solver>_size%03d.dump, {CELLS, 1} then T[CELLS], for every equilibrium size of a
+stochastically heated dust (A2E.py:506-522 with DUMP_TDUST=1).  On the device path they are read back after each dust's solve (4 bytes
+per cell and dust or size); the emission does not change.  One rank, and no library look-up (nothing is solved there), else refused.
+The populations of stochastically heated sizes are the dump of python -m soc_amd.a2e, not of this program.
 """
 import os
 import sys
@@ -359,12 +366,14 @@ def _library_rows(grid, rows_of, NFREQ, FREQ):
     return lib
 
 
-def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, log, AALG=None, ptabs=None, PEM=None, makelib=None, libs=None):
+def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, log, AALG=None, ptabs=None, PEM=None, makelib=None, libs=None, TEMP=None):
+    """TEMP: temperature_arrays' list, filled from what eqsolver and a2e.run's equilibrium sizes return"""
     n, NFREQ = FABS.shape
     for idust in range(len(dusts)):
         t0 = time.time()
         aalg = AALG[idust] if AALG else None
         pem = None
+        teq = {} if (TEMP is not None and kinds[idust] != 'eqdust') else None
         part = split_absorbed(FABS, RABS, ABU, idust)
         if kinds[idust] == 'eqdust':
             Fq, KABS, Emin, kE, oplgkE, TTT = tables[idust]
@@ -372,13 +381,18 @@ def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, lo
             B = 32768                                          # A2E_MABU.py:493 (any batch gives the same cells)
             for a in range(0, n, B):
                 b = min(a + B, n)
-                _, em[a:b] = engine.eqsolver(c0 + a, CELLS, NE_EQ, FACTOR, kE, oplgkE, Emin, Fq, KABS, TTT, part[a:b])
+                T, em[a:b] = engine.eqsolver(c0 + a, CELLS, NE_EQ, FACTOR, kE, oplgkE, Emin, Fq, KABS, TTT, part[a:b])
+                if TEMP is not None:
+                    TEMP[idust][a:b] = T                       # A2E_MABU.py:543-551
             if aalg is not None:
                 pem = polarised_eq(em, aalg, *ptabs[idust])    # A2E_MABU.py:615-637
         elif aalg is not None:                                 # (NSTOCH: the dust file's `nstoch`, A2E_MABU.py:938)
-            em, pem, _ = a2e.run(engine, tables[idust], part, NSTOCH=tables[idust].get("nstoch", NSTOCH_ALL), verbose=False, aalg=aalg)   # A2E_MABU.py:971-984
+            em, pem, _ = a2e.run(engine, tables[idust], part, NSTOCH=tables[idust].get("nstoch", NSTOCH_ALL), verbose=False, aalg=aalg,
+                                 teq=teq)   # A2E_MABU.py:971-984
         else:
-            em, _ = a2e.run(engine, tables[idust], part, NSTOCH=tables[idust].get("nstoch", NSTOCH_ALL), verbose=False)
+            em, _ = a2e.run(engine, tables[idust], part, NSTOCH=tables[idust].get("nstoch", NSTOCH_ALL), verbose=False, teq=teq)
+        for isize, T in (teq or {}).items():
+            TEMP[idust][isize][:] = T
         if makelib is not None:                                # (cols, N, FREQ): the library of this dust, from what is at hand
             grid = engine.library_build(makelib[1], ABS3=np.ascontiguousarray(part[:, makelib[0]], np.float32))
             libs.append(_library_rows(grid, lambda cells: em[cells], NFREQ, makelib[2]))
@@ -390,7 +404,7 @@ def _solve_host(engine, dusts, kinds, tables, FABS, ABU, RABS, c0, CELLS, EM, lo
 
 
 def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells, log, AALG=None, ptabs=None, R=None, resident_c0=None,
-                  download=True, absorbed=None, makelib=None, libs=None):
+                  download=True, absorbed=None, makelib=None, libs=None, TEMP=None):
     """the cells in ranges that fit the device (one range where all do): cells are independent, so this is a loop.  With AALG (per
     dust the minimum aligned sizes of these cells, or None) the two more resident arrays of the polarised emission are asked for,
     the rows of a dust's aalg follow the cell range, and R receives polarised / total.  resident_c0 (the model's cell of row 0): the
@@ -399,7 +413,9 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
     range takes its rows from there, device to device, scaled on the way (absorbed_to_mabu), in place of the uploads.
     makelib = (cols, N, FREQ): after every dust's solve its library goes to libs -- the grid from library_build on the resident share
     (the plain split: where a reference column is the last channel, which clip_last changes, the share is split once more for the
-    solver), the rows gathered from the resident emission.  One range then, or UnsupportedOption."""
+    solver), the rows gathered from the resident emission.  One range then, or UnsupportedOption.
+    TEMP: temperature_arrays' list -- after every dust's solve the rows of this range are read into it (mabu_download_t,
+    a2e_resident_download_teq), before the next dust's solve reuses the device arrays they come from."""
     n, NFREQ = FABS.shape
     NDUST = len(dusts)
     if makelib is not None and range_cells and int(range_cells) < n:
@@ -440,6 +456,9 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
                     if makelib is not None:
                         grid = engine.library_build(makelib[1], cols=makelib[0])
                     engine.mabu_solve_eq(NE_EQ, FACTOR, kE, oplgkE, Emin, Fq, KABS, TTT)
+                    for i in range(a, b, CHUNK) if TEMP is not None else ():
+                        m = min(i + CHUNK, b) - i
+                        engine.mabu_download_t(i - a, m, out=TEMP[idust][i:i + m])
                     if aalg is not None:                                           # A2E_MABU.py:615-637
                         upload_aalg(aalg, a, b)
                         engine.mabu_pol_eq(*ptabs[idust])
@@ -453,7 +472,12 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
                         grid = engine.library_build(makelib[1], cols=makelib[0])
                     if aalg is not None:
                         upload_aalg(aalg, a, b)
-                    a2e.solve_sizes_resident(engine, sol, stochastic_sizes(sol), aalg is not None)   # (a refusal of a call ends the stage)
+                    a2e.solve_sizes_resident(engine, sol, stochastic_sizes(sol), aalg is not None,   # (a refusal of a call ends the stage)
+                                             keep_teq=TEMP is not None and len(TEMP[idust]) > 0)
+                    for slot, isize in enumerate(a2e.eq_sizes(sol, stochastic_sizes(sol))) if TEMP is not None else ():
+                        for i in range(a, b, CHUNK):
+                            m = min(i + CHUNK, b) - i
+                            engine.a2e_resident_download_teq(slot, i - a, m, out=TEMP[idust][isize][i:i + m])
                 if grid is not None:
                     libs.append(_library_rows(grid, engine.mabu_gather_rows, NFREQ, makelib[2]))
                 engine.mabu_accumulate(idust)
@@ -476,8 +500,22 @@ def _solve_device(engine, dusts, kinds, tables, FABS, ABU, RABS, EM, range_cells
     return ranges
 
 
+def temperature_arrays(kinds, tables, n):
+    """what solve_emission(temperatures=True) fills for n cells, a list along the dusts: T[n] of an equilibrium dust; {isize: T[n]} of a
+    stochastically heated one, for its equilibrium sizes only (a2e.eq_sizes: from the dust file's `nstoch` on or without tables in the
+    solver file, less those with S_FRAC < 1e-30) -- empty where every size is stochastically heated"""
+    return [np.zeros(n, np.float32) if k == 'eqdust' else {isize: np.zeros(n, np.float32) for isize in a2e.eq_sizes(t, stochastic_sizes(t))}
+            for k, t in zip(kinds, tables)]
+
+
+def offers_temperatures(engine, kinds, tables):
+    """whether the device path can hand out the temperatures: mabu_download_t, and a2e_resident_keep_teq where a size is an equilibrium size"""
+    return hasattr(engine, "mabu_download_t") and \
+        (hasattr(engine, "a2e_resident_keep_teq") or all(k == 'eqdust' or not a2e.eq_sizes(t, stochastic_sizes(t)) for k, t in zip(kinds, tables)))
+
+
 def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, path=None, range_cells=None, log=None, pol=None,
-                   keep_resident=False, download=True, absorbed_scale=None, makelib=None):
+                   keep_resident=False, download=True, absorbed_scale=None, makelib=None, temperatures=False):
     """Stage 2 of a multi-dust run for the cells a2e.cell_range(CELLS, rank, world) of this rank.  FABSORBED[CELLS, NFREQ] as the
     absorbed file holds it (scaled, files.scale_absorbed; a memory map will do), ABU[CELLS, NDUST] float32.  Or FABSORBED a
     ResidentAbsorptions -- the engine holds them unscaled (absorbed_begin) -- with absorbed_scale = (K[LEVELS], nnnlimit)
@@ -490,7 +528,11 @@ def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, pat
     cell-emission launches of a re-emission iteration take it from there) -- info["resident"] says whether it did; download=False:
     where it did, the sum is not read back (EM, and R, stay zero: an intermediate iteration needs neither on the host);
     makelib = (cols[3], N): info["libraries"] is, per dust, its library (the dict library.write_library takes, with IND besides), a
-    by-product of the solve, which it does not change -- one rank and, on the device path, one cell range, else UnsupportedOption."""
+    by-product of the solve, which it does not change -- one rank and, on the device path, one cell range, else UnsupportedOption;
+    temperatures: info["T"] is temperature_arrays' list for the cells of this rank -- what the solvers compute on the way to the
+    emission (A2E_MABU.py:551, A2E.py:506-522), 4 bytes per cell and dust or equilibrium size read back on the device path, the same
+    bits on both paths; the emission does not change.  The populations of stochastically heated sizes are not offered here (CELLS x NE
+    floats per size: soc_amd.a2e's dump).  An engine whose device path lacks the calls for them is refused by name."""
     log = log or (lambda *a: None)
     CELLS, NFREQ = FABSORBED.shape
     RABS, FREQ = relative_cross_sections(dusts, kinds)
@@ -514,21 +556,25 @@ def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, pat
     if path not in (None, 'device', 'host') or (path == 'device' and not offered):
         raise ValueError("solve_emission: path %r is not available with this engine and these solver files" % (path,))
     device = offered if path is None else path == 'device'
+    if temperatures and device and not offers_temperatures(engine, kinds, tables):
+        raise UnsupportedOption("temperatures: the engine's device path has no mabu_download_t / a2e_resident_keep_teq "
+                                "(path='host' takes them from the host solvers)")
     from_resident = isinstance(FABSORBED, ResidentAbsorptions)
     if from_resident and (not device or absorbed_scale is None):
         raise ValueError("solve_emission: the resident absorptions need the device path and absorbed_scale = (K, nnnlimit)")
     EM = np.zeros((c1 - c0, NFREQ), np.float32)
     R = np.zeros((c1 - c0, NFREQ), np.float32) if AALG else None
+    TEMP = temperature_arrays(kinds, tables, c1 - c0) if temperatures else None
     ranges = 0
     resident = bool(keep_resident) and device and c1 > c0
     if c1 > c0 and device:
         ranges = _solve_device(engine, dusts, kinds, tables, ResidentAbsorptions(engine, c1 - c0, NFREQ) if from_resident else FABSORBED[c0:c1],
                                ABU[c0:c1], RABS, EM, range_cells, log, AALG, ptabs, R, resident_c0=c0 if resident else None,
                                download=download or not resident, absorbed=(c0,) + tuple(absorbed_scale) if from_resident else None,
-                               makelib=makelib, libs=libs)
+                               makelib=makelib, libs=libs, TEMP=TEMP)
     elif c1 > c0:
         ranges = _solve_host(engine, dusts, kinds, tables, FABSORBED[c0:c1], ABU[c0:c1], RABS, c0, CELLS, EM, log, AALG, ptabs, R,
-                             makelib=makelib, libs=libs)
+                             makelib=makelib, libs=libs, TEMP=TEMP)
         if AALG:
             R[:] = reduction_factor(R, EM)                         # (R held the sum of the polarised emission)
     info = dict(path='device' if device else 'host', ranges=ranges, resident=resident)
@@ -536,7 +582,38 @@ def solve_emission(engine, dusts, kinds, FABSORBED, ABU, rank=0, world=1, *, pat
         info["R"] = R
     if libs is not None:
         info["libraries"] = libs
+    if TEMP is not None:
+        info["T"] = TEMP
     return EM, info
+
+
+TEMPERATURES_ONE_RANK = ("temperatures with %d ranks: every rank solves a share of the cells, and a temperature file holds all of them; "
+                         "run it with one rank")
+TEMPERATURES_NO_LIBRARY = ("temperatures together with a library look-up (%s): a library answers with the emission, nothing is solved, "
+                           "so there is no temperature")
+
+
+def temperature_files(dusts, kinds, TEMP):
+    """[(file name, header or None, T[CELLS])] of info["T"]: '<dust>.T' with the name as the ini gives it, raw float32 (A2E_MABU.py:551),
+    for an equilibrium dust; <solver name without .solver>_size%03d.dump with the header {CELLS, 1} (A2E.py:506-522, run there by
+    A2E_MABU.py:938 on the dust's solver file) for every equilibrium size of a stochastically heated one"""
+    out = []
+    for d, k, T in zip(dusts, kinds, TEMP):
+        if k == 'eqdust':
+            out.append(('%s.T' % d, None, T))
+        else:
+            out += [(a2e.dump_name(solver_name(d).replace('.solver', ''), isize), (len(T[isize]), 1), T[isize]) for isize in sorted(T)]
+    return out
+
+
+def write_temperatures(dusts, kinds, TEMP, log=None):
+    for name, header, T in temperature_files(dusts, kinds, TEMP):
+        with open(name, 'wb') as fp:
+            if header is not None:
+                np.asarray(header, np.int32).tofile(fp)
+            np.asarray(T, np.float32).tofile(fp)
+        if log:
+            log("  %s: %d temperatures" % (name, len(T)))
 
 
 # ---- the look-up: a library per dust ------------------------------------------------------------------------------------
@@ -685,12 +762,13 @@ def reference_columns_ascending(FREQ, FREF, what):
 
 
 # ---- the program ----------------------------------------------------------------------------------------------------
-def run(ini, absorbed, emitted, engine, comm=None, ofreq=None, verbose=False, makelib=None, uselib=None, **stage):
+def run(ini, absorbed, emitted, engine, comm=None, ofreq=None, verbose=False, makelib=None, uselib=None, temperatures=False, **stage):
     """The whole program for one rank of `comm` (or alone): memory-map the absorbed file, solve this rank's cells, write them
     into this rank's rows of the emitted file.  No collective on the data path (as a2e.run_sharded): the ranks only wait for
     rank 0 to have created the file, and for each other at the end.  Returns solve_emission's info.
     makelib = (lfreq file, N): the libraries <dust>.mlib are written besides; uselib = lfreq file, or `libabs` in the ini with an
-    absorbed file of three columns: the emission comes from those libraries (solve_emission_library; ofreq selects its columns)."""
+    absorbed file of three columns: the emission comes from those libraries (solve_emission_library; ofreq selects its columns).
+    temperatures: the temperature files are written besides (temperature_files); one rank and no library look-up, else refused."""
     rank, world = (comm.rank, comm.world) if comm else (0, 1)
     U = User(ini)
     dusts = list(U.file_optical)
@@ -704,6 +782,10 @@ def run(ini, absorbed, emitted, engine, comm=None, ofreq=None, verbose=False, ma
         raise UnsupportedOption("a fourth argument (%s: emission on a subset of the frequencies, A2E_MABU.py ofreq.dat) is not supported "
                                 "for a direct run: the emitted file holds every frequency of the absorbed file" % ofreq)
     refuse(U, pol, world)
+    if temperatures and world > 1:                                 # (before rank 0 creates the emitted file)
+        raise UnsupportedOption(TEMPERATURES_ONE_RANK % world)
+    if temperatures and lookup:
+        raise UnsupportedOption(TEMPERATURES_NO_LIBRARY % ("uselib" if uselib is not None else "libabs"))
     if uselib is not None and (pol is not None or world > 1):
         raise UnsupportedOption("uselib together with %s" % ("polarisation lines (no polarised emission comes from a library)"
                                                                if pol is not None else "more than one rank"))
@@ -746,8 +828,10 @@ def run(ini, absorbed, emitted, engine, comm=None, ofreq=None, verbose=False, ma
         FREQ = relative_cross_sections(dusts, kinds)[1]
         stage["makelib"] = (library.reference_columns(FREQ, library.load_frequencies(makelib[0])), int(makelib[1]))
     if world == 1:
-        EM, info = solve_emission(engine, dusts, kinds, FABS, ABU, log=log, pol=pol, **stage)
+        EM, info = solve_emission(engine, dusts, kinds, FABS, ABU, log=log, pol=pol, temperatures=bool(temperatures), **stage)
         files.write_emitted(emitted, EM)
+        if temperatures:
+            write_temperatures(dusts, kinds, info["T"], log)
         if makelib is not None:
             write_libraries(dusts, info.pop("libraries"), log)
         if pol is not None:
@@ -809,8 +893,11 @@ def makelib_option(opts):
 def main(argv=None):
     argv = sys.argv if argv is None else argv
     args, opts = parse_options(argv, ("makelib", "bins", "uselib"))
+    temperatures = args is not None and "--temperatures" in args
+    if temperatures:
+        args = [a for a in args if a != "--temperatures"]
     if args is None or len(args) < 4:
-        print("Usage:  python -m soc_amd.mabu  soc.ini absorbed emitted [ofreq.dat] [--makelib LFREQ [--bins N]] [--uselib LFREQ]")
+        print("Usage:  python -m soc_amd.mabu  soc.ini absorbed emitted [ofreq.dat] [--makelib LFREQ [--bins N]] [--uselib LFREQ] [--temperatures]")
         print("        (N GPUs: python -m torch.distributed.run --nproc-per-node N -m soc_amd.mabu ...)")
         return 1
     try:
@@ -825,7 +912,12 @@ def main(argv=None):
     eng = Engine(comm.local_rank)
     try:
         info = run(args[1], args[2], args[3], eng, comm if comm.world > 1 else None, ofreq=args[4] if len(args) > 4 else None,
-                   verbose=True, makelib=makelib, uselib=opts.get("uselib"))
+                   verbose=True, makelib=makelib, uselib=opts.get("uselib"), temperatures=temperatures)
+    except UnsupportedOption as err:
+        if not temperatures:
+            raise
+        print(err)
+        return 1
     finally:
         eng.close()
         comm.close()
